@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """bench.py — windows/s through EM + decode on BASELINE.json's workload, with the roofline of the
-dominant kernel and a CPU baseline beside it.
+dominant kernel beside it (and, under --full, a CPU baseline and the other legs listed in its help).
 
 One "step" = one EM pass over the whole synthetic diploid track: E-step on the GPU (emission,
 forward, backward, posterior decode, sufficient statistics, ordered reduction), the statistics
@@ -8,10 +8,12 @@ vector to the host, the M-step, and the next parameter block back up — i.e. ex
 runHMMFlagger repeats (hmm_flagger.c:337-445).  The windows are resident in HBM before the timed
 region.  With --gpus N the chunk list is sharded across N ranks (one process per GPU over RCCL: the driver's
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, or — when WORLD_SIZE is not set —
-bench.py re-executes itself under that launcher) and the statistics are all-gathered every step
+bench.py starts that launcher over itself as a child process) and the statistics are all-gathered every step
 (flagger_amd/dist.py).  It refuses to run when fewer than N GPUs are visible: it never reports a run of fewer
 ranks as N.  --scaling strong (default) shards the fixed BASELINE workload (configs[3]); --scaling weak gives every
 rank a whole configs[2] genome (N genomes in one EM: the statistics exchange is the same, the per-GPU work fixed).
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last timed
+step returned to its caller (statistics, parameters, labels) as .npy files, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -27,6 +29,7 @@ ALGO_BYTES_PER_WINDOW = 17.0   # 16-byte packed window record (chunk.c:669-697) 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X fp64 vector (VALU) peak: half of the 157.3 TF f32 vector peak of /opt/skills/guides/MI355X_MICROARCH.md
                                 # (256 CUs x 4 SIMDs x 16 lanes x 2 flops x 2.4 GHz)
+DUMP_MAX_LABELS = 12 << 20      # --dump-outputs: labels of at most this many windows (48 MB of float32), every n-th past it
 
 
 def effective_cores() -> int:
@@ -82,14 +85,14 @@ def main():
                          "5 = not a BASELINE config: configs[4] with coverage spread over 0..250 (worst case for the emission tables); "
                          "6 = not a BASELINE config: configs[2] with over-dispersed (negative-binomial, variance = 3 x mean) coverage")
     ap.add_argument("--overdispersion", type=float, default=3.0, help="config 6 only: variance / mean of the negative-binomial coverage")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-em-run", action="store_true", help="skip the `em_run` leg (a real EM to convergence in a fresh context, and the cold "
-                                                             "command line) that follows the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` leg")
+    ap.add_argument("--no-em-run", action="store_true", help="with --full: skip the `em_run` leg (a real EM to convergence in a fresh context, "
+                                                             "and the cold command line) that follows the timed region")
     ap.add_argument("--creates", type=int, default=9, help="fresh contexts of the em_run leg's hf_create timing (median / min / max reported)")
     ap.add_argument("--event-stride", type=int, default=0,
                     help="the dominant kernel is bracketed by a pair of HIP events in every n-th timed step; default 0 = max(1, min(32, steps // 5)): "
                          "at least 5 samples however short the timed region is (the driver's --steps 20: every 4th step; a pair costs the pass "
-                         "it is in 10 us of turn-around, profiles/r06_kstamp.txt — at every 2nd step that was 5 % of the timed region); the line "
+                         "it is in 10 us of turn-around, profiles/r06_kstamp.txt — at every 2nd step that was 5 %% of the timed region); the line "
                          "reports the MEDIAN of the samples and their number")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="no HIP events inside the timed region; the dominant kernel's duration then comes from the untimed "
@@ -107,17 +110,31 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong: the BASELINE workload sharded over the GPUs (configs[3]); weak: one whole configs[2] genome per GPU")
     ap.add_argument("--no-weak-leg", action="store_true",
-                    help="with --gpus N > 1 and strong scaling the line also carries a `weak_scaling` object (one whole genome per "
+                    help="with --full, --gpus N > 1 and strong scaling the line also carries a `weak_scaling` object (one whole genome per "
                          "GPU, timed after the main region); this switch skips it")
     ap.add_argument("--no-second-exchange", action="store_true",
-                    help="on the multi-GPU path the line also carries `other_exchange` (the exchange that was not timed as the headline) "
-                         "and `n_invariance` (a 5 % copy of the workload through --exchange chunks on all ranks against one context on "
+                    help="with --full, on the multi-GPU path the line also carries `other_exchange` (the exchange that was not timed as the headline) "
+                         "and `n_invariance` (a 5 %% copy of the workload through --exchange chunks on all ranks against one context on "
                          "rank 0: log-likelihoods bit-identical, labels identical); this switch skips both")
     ap.add_argument("--force-weak-leg", action="store_true",
-                    help="run the weak-scaling leg even with one rank (exercises that code path on a 1-GPU box; with --dist-path)")
+                    help="run the weak-scaling leg even with one rank (exercises that code path on a 1-GPU box; with --dist-path --full)")
     ap.add_argument("--dist-path", action="store_true",
                     help="take the multi-GPU code path (process group, all-gather, indexed reduction) even with one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, after the timed region: the timed steps once more without kernel events, "
+                         "the per-kernel breakdown (roofline.kernel_ms_all), the em_run leg, the CPU baseline and, on the multi-GPU path, the "
+                         "weak-scaling leg, the other exchange and n_invariance (each of them can still be left out with its --no-... switch). "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned to its caller as DIR/<name>.npy: statistics "
+                         "(the reduced sufficient-statistics vector, log-likelihood first, float64), loglikelihood (float64), parameters "
+                         "(the model after the M-step, float64), labels (the decoded state of every window, float32; every n-th window "
+                         "past %d windows). The inputs are seeded: the same arguments give the same inputs in every run" % DUMP_MAX_LABELS)
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1 (the line reports the time of the timed steps)")
+    if args.warmup < 0:
+        sys.exit("bench.py: --warmup must be >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
@@ -134,8 +151,11 @@ def main():
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
         sock.close()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        # a child process, not an exec: this process has already opened the GPU runtime (device_count)
+        import subprocess
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(rc if rc >= 0 else 128 - rc)
 
     import numpy as np
     import torch
@@ -203,6 +223,8 @@ def main():
     sharded.force_collective = args.dist_path
     target = em if not dist_path else sharded   # single GPU: no exchange buffers in the path
 
+    last_stats = [None]                    # the torch-exchange path's statistics vector of its last step (HMM_resetEstimators drops it)
+
     def step():
         if not dist_path:
             em.em_iterate(model, True, 1e-3)                      # E-step + decode + ordered reduce + M-step, one native call
@@ -210,8 +232,28 @@ def main():
             target.em_iterate(model, True, 1e-3)                  # the same + the RCCL all-gather, one native call (hf_multi_em_iterate)
         else:
             hmm.EM_runOneIterationForList(target, model)          # E-step + decode + all-gather + ordered reduce
+            last_stats[0] = model.estimators
             hmm.HMM_estimateParameters(model, 1e-3)               # M-step on the host (replicated on every rank)
             hmm.HMM_resetEstimators(model)
+
+    def timed_outputs():
+        """What the last step returned to its caller: the statistics vector, the log-likelihood, the model after the M-step and the
+        labels of every window (in global order; on the multi-GPU path gathered from all ranks: a collective)."""
+        if not dist_path:
+            labels = em.labels()
+        elif hasattr(sharded, "local_labels"):                    # RankEMList: this rank's windows at their global positions
+            parts = [None] * world
+            tdist.all_gather_object(parts, (sharded.first_window, sharded.local_labels().tobytes()))
+            labels = np.full(store.n_windows, -1, dtype=np.int8)
+            for f0, b in parts:
+                a = np.frombuffer(b, dtype=np.int8)
+                labels[f0:f0 + a.size] = a
+        else:
+            labels = sharded.gather_labels()
+        stats = model.estimators if model.estimators is not None else last_stats[0]
+        every = -(-labels.size // DUMP_MAX_LABELS)                # a fixed subsample past DUMP_MAX_LABELS windows (64 MB in all at most)
+        return {"statistics": np.array(stats, dtype=np.float64), "loglikelihood": np.array([model.loglikelihood], dtype=np.float64),
+                "parameters": np.asarray(model.param_vector(), dtype=np.float64), "labels": labels[::every].astype(np.float32)}
 
     def barrier():
         if dist_path:
@@ -236,6 +278,11 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     ll = model.loglikelihood               # after the last TIMED step (the loops below go on iterating the same model)
+    outputs = timed_outputs() if args.dump_outputs else None
+    if outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     if os.environ.get("BENCH_DUMP_SAMPLES") and rank == 0:   # the sequence of samples on stderr (how the kernel settles after a cold start)
         print("[bench] %s samples (us): " % dom + " ".join("%.1f" % (v * 1e3) for v in dom_samples), file=sys.stderr)
     if dom_samples:                        # median: the first sample follows the barrier's idle gap and runs at a lower clock
@@ -243,7 +290,7 @@ def main():
     # what the event pairs of the timed region cost it: the same K steps once more, right behind it, with no event in the stream (the timed
     # region's sampled launches carry a completion signal of their own and the runtime serialises around it: ~12 us per sampled step)
     plain_ms = None
-    if not args.no_kernel_events and not dist_path:
+    if args.full and not args.no_kernel_events and not dist_path:
         em.set_profiling([])
         barrier()
         p0 = time.perf_counter()
@@ -251,14 +298,17 @@ def main():
             step()
         barrier()
         plain_ms = (time.perf_counter() - p0) / args.steps * 1e3
-    # per-kernel breakdown from a few extra passes outside the timed region (every kernel bracketed)
-    em.set_profiling_stride(1)
-    em.set_profiling(True)
-    ksum, extra = {}, min(max(args.steps, 1), 10)
-    for _ in range(extra):
-        step()
-        for k, v in em.kernel_times().items():
-            ksum[k] = ksum.get(k, 0.0) + v
+    # per-kernel breakdown from a few extra passes outside the timed region (every kernel bracketed); without --full only where the
+    # dominant kernel's time has to come from them (--no-kernel-events)
+    ksum, extra = {}, 0
+    if args.full or args.no_kernel_events:
+        em.set_profiling_stride(1)
+        em.set_profiling(True)
+        extra = min(max(args.steps, 1), 10)
+        for _ in range(extra):
+            step()
+            for k, v in em.kernel_times().items():
+                ksum[k] = ksum.get(k, 0.0) + v
     barrier()
     if dist_path:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -270,7 +320,7 @@ def main():
     # same native calls as the timed region, and as a COLD process — the hmm_flagger command line on the same windows (.bin), which
     # times its own E-steps + M-steps (file reading, hf_create and output writing excluded, as the metric says) ----
     em_run = None
-    if world == 1 and not dist_path and not args.no_em_run:
+    if args.full and world == 1 and not dist_path and not args.no_em_run:
         try:
             rmodel = hmm.createModel(hmm.MODEL_TRUNC_EXP_GAUSSIAN, K, store, alpha)
             frac = 0.8 if args.config in (4, 5) else 0.95
@@ -341,7 +391,7 @@ def main():
 
     # second leg at N > 1: the same exchange with one WHOLE genome per GPU (weak scaling), outside the timed region above
     weak = None
-    if (world > 1 or (args.force_weak_leg and dist_path)) and args.scaling == "strong" and not args.no_weak_leg:
+    if args.full and (world > 1 or (args.force_weak_leg and dist_path)) and args.scaling == "strong" and not args.no_weak_leg:
         try:
             wstore = base_store.subset_chunks(list(range(base_store.n_chunks)) * world)
             wmodel = hmm.createModel(hmm.MODEL_TRUNC_EXP_GAUSSIAN, K, wstore, alpha)
@@ -379,7 +429,7 @@ def main():
     # at N > 1 (or --dist-path): the OTHER exchange, timed the same way, and a proof that the sharded run is the one-GPU run:
     # a small copy of the workload through `--exchange chunks` on all ranks against a single context on rank 0
     other, invariance = None, None
-    if dist_path and not args.no_second_exchange:
+    if args.full and dist_path and not args.no_second_exchange:
         try:
             oex = "chunks" if args.exchange == "ranks" else "ranks"
             omodel = hmm.createModel(hmm.MODEL_TRUNC_EXP_GAUSSIAN, K, store, alpha)
@@ -475,9 +525,9 @@ def main():
             invariance = {"error": repr(e)}
 
     if rank == 0:
-        kavg = {k: v / extra for k, v in ksum.items() if v > 0}
+        kavg = {k: v / extra for k, v in ksum.items() if v > 0} if extra else None
         if args.no_kernel_events:
-            dom_ms = kavg.get(dom, 0.0)
+            dom_ms = (kavg or {}).get(dom, 0.0)
         local_windows = sharded.n_local_windows if hasattr(sharded, "n_local_windows") else sharded.local_store.n_windows
         # a context past the Infinity Cache runs a pass in sub-passes (hf_sub_passes): the timed launch of the dominant kernel is the FIRST
         # sub-pass's, so the units of one launch are that sub-pass's windows (one sub-pass — every BASELINE configuration — all of them)
@@ -593,7 +643,7 @@ def main():
             out["other_exchange"] = other
         if invariance is not None:
             out["n_invariance"] = invariance
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(store, K, alpha, effective_cores())
         print(json.dumps(out))
     if dist_path:

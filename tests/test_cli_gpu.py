@@ -143,7 +143,7 @@ def test_bench_multi_gpu_line_is_complete_on_one_gpu():
     weak_scaling, roofline, cpu_baseline."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-path", "--force-weak-leg", "--scale", "0.05",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-path", "--force-weak-leg", "--full", "--scale", "0.05",
                         "--steps", "5", "--warmup", "2"], capture_output=True, text=True,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -177,6 +177,32 @@ def test_bench_single_gpu_and_distributed_code_paths_agree():
     assert outs[2]["config"]["statistics"] == "by emission row"
     assert outs[2]["loglikelihood_after_last_step"] == outs[0]["loglikelihood_after_last_step"]
     assert outs[1]["n_gpus"] == 1 and outs[1]["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_timed_step(tmp_path):
+    """Without --full the line carries the headline and the roofline of the timed region, none of the extra legs; --dump-outputs writes
+    what the last timed step returned (statistics, log-likelihood, parameters, labels), the same in two runs with the same arguments."""
+    import json
+    import sys
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.02", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1]))
+    line = lines[0]
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["unit"] == "windows/s" and line["dtype"] == "f64"
+    for leg in ("cpu_baseline", "em_run", "weak_scaling", "other_exchange", "n_invariance"):
+        assert leg not in line, leg
+    assert line["ms_per_step_without_kernel_events"] is None and line["roofline"]["kernel_ms_all"] is None
+    n = line["config"]["n_windows"]
+    for name in ("statistics", "loglikelihood", "parameters", "labels"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and (a == b).all(), name
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    assert lab.shape == (n,) and set(np.unique(lab)) <= {0.0, 1.0, 2.0, 3.0}
+    ll = np.load(tmp_path / "a" / "loglikelihood.npy")
+    assert ll[0] == line["loglikelihood_after_last_step"] == np.load(tmp_path / "a" / "statistics.npy")[0]
 
 
 def test_cli_summary_tables_and_contig_list(tmp_path):
