@@ -110,6 +110,10 @@ def lib() -> C.CDLL:
     sig("hf_get_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_forward_backward", C.c_int, vp, i64, i64, pd, pd, pd)
+    sig("hf_viterbi", C.c_int, vp, C.POINTER(hf_params), vp)
+    sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
+    sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
+    sig("hf_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
     sig("hf_last_kernel_ms", C.c_int, vp, C.POINTER(C.c_float))
     sig("hf_set_profiling", C.c_int, vp, C.c_uint)
     sig("hf_set_profiling_stride", C.c_int, vp, C.c_int)
@@ -151,6 +155,9 @@ def lib() -> C.CDLL:
     sig("hf_multi_estep", C.c_int, vp, C.POINTER(hf_params), C.c_int, pd)
     sig("hf_multi_get_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_multi_get_posterior", C.c_int, vp, i64, i64, pd)
+    sig("hf_multi_viterbi", C.c_int, vp, C.POINTER(hf_params), pd)
+    sig("hf_multi_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
+    sig("hf_multi_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
     sig("hf_multi_world", C.c_int, vp)
     sig("hf_multi_comm_ranks", C.c_int, vp)
     sig("hf_multi_em_iterate", C.c_int, vp, vp, C.c_int, C.c_int, C.c_double, pd, C.POINTER(C.c_int))

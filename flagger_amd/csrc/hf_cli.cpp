@@ -56,6 +56,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"hipAlgo", required_argument, nullptr, 1002},         // scan (default) | seq (the on-device sequential cross-check)
     {"gpus", required_argument, nullptr, 1003},            // chunks sharded over GPUs device..device+N-1, one RCCL all-gather per pass
     {"exchange", required_argument, nullptr, 1004},        // chunks (default: bit-identical for every N) | ranks (one vector per GPU: faster)
+    {"viterbi", no_argument, nullptr, 1005},               // final labels by most-probable path (hf_viterbi) instead of posterior argmax
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -88,7 +89,10 @@ static void usage(const char* program) {
             "         --exchange chunks|ranks      what the GPUs exchange: per-chunk vectors summed in chunk-list order (default: results are\n"
             "                                      bit-identical for every N) | one statistics vector per GPU summed in rank order (faster per\n"
             "                                      pass; equal across N only up to the rounding of the order of additions, which --accelerate\n"
-            "                                      can carry into the last printed digits)\n");
+            "                                      can carry into the last printed digits)\n"
+            "         --viterbi                    final labels (final BED, final summary tables) by the most probable state path with\n"
+            "                                      the final parameters instead of the posterior argmax; its log-probability goes to\n"
+            "                                      viterbi_log_probability.tsv (-P still writes the posterior BED)\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -130,6 +134,18 @@ struct Run {
     }
     int estep(hfm_model* m, int mode) { return estep(m, mode, stats.data()); }
     int labels(int8_t* out) { return multi ? hf_multi_get_labels(multi, out) : hf_get_labels(ctx, out); }
+    // most-probable path with the model's current parameters: labels (list order) and the run's log-probability
+    int viterbi(hfm_model* m, int8_t* out, double* log_prob) {
+        hf_params p;
+        hfm_params(m, &p);
+        if (multi) {
+            const int rc = hf_multi_viterbi(multi, &p, log_prob);
+            return rc != HF_OK ? rc : hf_multi_get_viterbi_labels(multi, out);
+        }
+        int rc = hf_viterbi(ctx, &p, nullptr);
+        if (rc == HF_OK) rc = hf_viterbi_finish(ctx, log_prob, nullptr);
+        return rc != HF_OK ? rc : hf_get_viterbi_labels(ctx, out);
+    }
     int posterior(int64_t first, int64_t n, double* out) {
         return multi ? hf_multi_get_posterior(multi, first, n, out) : hf_get_posterior(ctx, first, n, out);
     }
@@ -213,6 +229,7 @@ int main(int argc, char* argv[]) {
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
     double initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
+    bool viterbi = false;
     int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1, loopbackRanks = 0;
     const char* binArrayFilePath = nullptr;
     bool writeBenchmarkingStatsPerIteration = false;
@@ -280,6 +297,7 @@ int main(int argc, char* argv[]) {
             case 1001: device = atoi(optarg); break;
             case 1002: algo = !strcmp(optarg, "seq") ? HF_ALGO_SEQ : HF_ALGO_SCAN; break;
             case 1003: nGpus = atoi(optarg); break;
+            case 1005: viterbi = true; break;
             case 1004:
                 if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
                 else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
@@ -504,7 +522,23 @@ int main(int argc, char* argv[]) {
     write_params(model, dir, "final");
     std::vector<int8_t> labels((size_t) N);
     if ((rc = run.labels(labels.data())) != HF_OK) return die_estep(rc);
-    if ((rc = write_summary(run, dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, labels.data())) != HF_OK) return die_estep(rc);
+    // --viterbi: the final BED and the final tables take the most probable path under the final parameters; everything else
+    // (the posterior BED of -P among it) keeps the posterior labels of the final pass
+    std::vector<int8_t> vlabels;
+    if (viterbi) {
+        fprintf(stderr, "[%s] [Final Inference] Most probable state path of %d chunks ...\n", ts(), nChunks);
+        vlabels.resize((size_t) N);
+        double vlp = 0.0;
+        if ((rc = run.viterbi(model, vlabels.data(), &vlp)) != HF_OK) return die_estep(rc);
+        const std::string vp = dir + "/viterbi_log_probability.tsv";
+        FILE* vf = fopen(vp.c_str(), "w");
+        if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); return EXIT_FAILURE; }
+        fprintf(vf, "%.6f\n", vlp);
+        fclose(vf);
+        fprintf(stderr, "[%s] [Final Inference] Most probable path: log-probability %.6f\n", ts(), vlp);
+    }
+    const int8_t* finalLabels = viterbi ? vlabels.data() : labels.data();
+    if ((rc = write_summary(run, dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) return die_estep(rc);
     memcpy(hfio_prediction(tab), labels.data(), (size_t) N);
     if (writePosterior) {
         std::vector<double> post((size_t) N * 4);
@@ -521,7 +555,7 @@ int main(int argc, char* argv[]) {
     phase("EM + final inference");
     // 6. final BED
     fprintf(stderr, "[%s] Writing final BED file. \n", ts());
-    if (hfio_write_final_bed(tab, labels.data(), (dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
+    if (hfio_write_final_bed(tab, finalLabels, (dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
         fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), outputDir);
         return EXIT_FAILURE;
     }

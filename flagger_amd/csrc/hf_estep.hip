@@ -240,6 +240,7 @@ static void par_chunks(const int64_t* chunk_off, size_t C, Fn fn, size_t parts_p
 }
 struct hf_ctx;
 static int cseg0_of(const hf_ctx* ctx, int c);      // first segment of chunk c (c = C: the number of segments)
+static void vit_free(hf_ctx* ctx);                 // the buffers of hf_viterbi (hf_destroy)
 // slot of a segment's x-th window: lane x / L holds it as its x % L-th (hf_seg.h)
 static inline int32_t seg_slot(const SegDesc& d, int64_t x) { return d.slot0 + (int32_t) ((x % d.L) * 64 + x / d.L); }
 static int set_err(int code, const std::string& msg) { g_err = msg; return code; }
@@ -364,6 +365,18 @@ struct hf_ctx {
     bool pass_seg = false;             // the last pass ran the segment kernels (log-likelihood partials per segment)
     unsigned long long* d_seg_trace = nullptr;   // -DHF_SEG_TRACE builds only
     int n_slow = 0; int64_t* d_slow_w = nullptr; int32_t* d_slow_off = nullptr; double* d_Es = nullptr; double* d_Cs = nullptr;
+    // most-probable-path decoding (hf_viterbi.h): buffers of its own, allocated by the first hf_viterbi, never shared with a pass
+    struct Viterbi {
+        DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
+        double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
+        uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
+        int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr; unsigned* d_flags = nullptr;
+        double* d_P = nullptr; int* d_PE = nullptr; double* d_S = nullptr; int* d_SE = nullptr;   // SCAN: phase A
+        double* d_vin = nullptr; long long* d_vinE = nullptr;                                      // SCAN: phase B
+        uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;          // SCAN: phases C, D
+        bool alloc = false, launched = false, done = false;
+        std::vector<double> h_ll;                  // chunk scores of the last finished run
+    } vit;
 };
 
 static int cseg0_of(const hf_ctx* ctx, int c) { return ctx->h_cseg0[(size_t) c]; }
@@ -494,6 +507,7 @@ __global__ void k_pos_f(const int64_t* __restrict__ off, const int32_t* __restri
 #include "hf_rows.h"
 #include "hf_nb_rows.h"
 #include "hf_seg.h"
+#include "hf_viterbi.h"
 
 
 // ------------------------------------------------------------------------------------------
@@ -813,6 +827,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx_free(ctx, ctx->d_jobs); ctx_free(ctx, ctx->d_arow); ctx_free(ctx, ctx->d_arow_src); ctx_free(ctx, ctx->d_arow_cls); ctx_free(ctx, ctx->d_lutA);
     ctx_free(ctx, ctx->d_rw_off); ctx_free(ctx, ctx->d_rw_stats);
     ctx_free(ctx, ctx->d_tile_ll); ctx_free(ctx, ctx->d_tile_stats);
+    vit_free(ctx);
     if (ctx->h_part) hipHostFree(ctx->h_part);
     if (ctx->h_label) pin_cache().release(reinterpret_cast<char*>(ctx->h_label));
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
@@ -825,13 +840,13 @@ void hf_destroy(hf_ctx* ctx) {
 
 // pack one iteration's model: conditional transition tables (hmm_utils.c:2278-2292) and the
 // distinct alpha values of each column
-static int pack_params(hf_ctx* ctx, const hf_params* p) {
+static int pack_params(hf_ctx* ctx, const hf_params* p, DevParams* dst = nullptr) {
     if (p->n_regions != ctx->R) return set_err(HF_E_ARG, "hf_estep: n_regions differs from hf_create");
     for (int s = 0; s < 4; s++)
         if (p->ncomp[s] < 1 || p->ncomp[s] > ctx->K) return set_err(HF_E_ARG, "hf_estep: ncomp out of range");
     if (p->ncomp[1] != 1 || p->ncomp[2] != 1 || p->ncomp[0] != 1)
         return set_err(HF_E_ARG, "hf_estep: Err/Dup/Hap must have one component (hmm_flagger.c:180-182)");
-    DevParams* h = ctx->h_params;
+    DevParams* h = dst ? dst : ctx->h_params;
     h->model_type = p->model_type; h->n_regions = p->n_regions;
     h->beta_star = ctx->beta_star;
     for (int s = 0; s < 4; s++) h->ncomp[s] = p->ncomp[s];
@@ -1705,6 +1720,123 @@ int hf_get_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
         for (int s = 0; s < 4; s++) { post_host[i * 4 + s] = f[i * 4 + s] * b[i * 4 + s] * sc[i]; total += post_host[i * 4 + s]; }
         for (int s = 0; s < 4; s++) post_host[i * 4 + s] /= total;
     }
+    return HF_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// most-probable-path decoding (hf_viterbi.h): its own parameter block, rows, flags and outputs, so that the last pass's getters
+// (which re-run the segment kernel over the pass's tables) and the next pass see nothing of it
+// ------------------------------------------------------------------------------------------
+static int vit_alloc(hf_ctx* ctx) {
+    hf_ctx::Viterbi& v = ctx->vit;
+    if (v.alloc) return HF_OK;
+    const bool scan = ctx->algo == HF_ALGO_SCAN;
+    const size_t nrow = scan ? (size_t) ctx->n_slots : (size_t) ctx->N, G = scan ? (size_t) ctx->nseg : 0;
+    const size_t nC = (size_t) ctx->C;
+#define VALLOC(ptr, bytes) HIPCHK(hipMalloc((void**) &(ptr), (bytes) ? (bytes) : 8))
+    HIPCHK(hipHostMalloc((void**) &v.h_params, ctx->params_bytes));
+    VALLOC(v.d_params, ctx->params_bytes);
+    VALLOC(v.d_nbE, (size_t) ctx->R * 4 * HF_NB_NX * 8);
+    VALLOC(v.d_rows, nrow * 128);
+    VALLOC(v.d_bp, nrow);
+    VALLOC(v.d_label, (size_t) ctx->N);
+    VALLOC(v.d_ll, nC * 8);
+    VALLOC(v.d_final, nC);
+    VALLOC(v.d_flags, 4);
+    if (scan) {
+        VALLOC(v.d_P, G * 16 * 64 * 8); VALLOC(v.d_PE, G * 64 * 4); VALLOC(v.d_S, G * 16 * 8); VALLOC(v.d_SE, G * 4);
+        VALLOC(v.d_vin, G * 4 * 8); VALLOC(v.d_vinE, G * 8);
+        VALLOC(v.d_lmap, G * 64); VALLOC(v.d_smap, G); VALLOC(v.d_sexit, G);
+    }
+#undef VALLOC
+    v.alloc = true;
+    return HF_OK;
+}
+
+static void vit_free(hf_ctx* ctx) {
+    hf_ctx::Viterbi& v = ctx->vit;
+    if (v.h_params) hipHostFree(v.h_params);
+    void* dev[] = {v.d_params, v.d_nbE, v.d_rows, v.d_bp, v.d_label, v.d_ll, v.d_final, v.d_flags, v.d_P, v.d_PE, v.d_S, v.d_SE,
+                   v.d_vin, v.d_vinE, v.d_lmap, v.d_smap, v.d_sexit};
+    for (void* q : dev) if (q) hipFree(q);
+    v = hf_ctx::Viterbi();
+}
+
+int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
+    if (!ctx || !p) return set_err(HF_E_ARG, "hf_viterbi: bad argument");
+    hf_ctx::Viterbi& v = ctx->vit;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->algo == HF_ALGO_SCAN && ctx->N > 0 && ctx->C > 0 && ctx->nseg == 0)
+        return set_err(HF_E_ARG, "hf_viterbi: HF_ALGO_SCAN holds at most 2^30 windows per context");
+    if (v.launched) HIPCHK(hipDeviceSynchronize());   // a run nobody finished may still be reading the pinned parameter block
+    v.launched = false; v.done = false;
+    int rc = vit_alloc(ctx);
+    if (rc) return rc;
+    rc = pack_params(ctx, p, v.h_params);
+    if (rc) return rc;
+    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
+    if (nbm) {
+        if (!p->nb_E) return set_err(HF_E_ARG, "hf_viterbi: negative_binomial needs hf_params.nb_E");
+        if (p->nb_max_x > 0 && ctx->M - 1 > p->nb_max_x)
+            return set_err(HF_E_ARG, "hf_viterbi: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
+        // (synchronous: the caller's table may be rewritten as soon as this returns)
+        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) ctx->R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, ctx->params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
+    if (ctx->C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) ctx->C * 8, st));   // (chunks without windows: score 0)
+    const double* nbE = nbm ? v.d_nbE : nullptr;
+    if (ctx->C > 0 && ctx->N > 0) {
+        if (ctx->algo == HF_ALGO_SCAN) {
+            const unsigned G = (unsigned) ctx->nseg, CB = (unsigned) ((ctx->C + 63) / 64);
+            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, ctx->d_seg, ctx->d_rec, ctx->d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
+            hipLaunchKernelGGL(k_vit_prod, dim3(G), dim3(64), 0, st, ctx->d_seg, v.d_rows, v.d_P, v.d_PE, v.d_S, v.d_SE);
+            hipLaunchKernelGGL(k_vit_chain, dim3(CB), dim3(64), 0, st, ctx->C, ctx->d_chunk_seg0, v.d_S, v.d_SE, v.d_vin, v.d_vinE);
+            hipLaunchKernelGGL(k_vit_replay, dim3(G), dim3(64), 0, st, ctx->d_seg, ctx->d_rec, v.d_params, v.d_rows, v.d_P, v.d_PE, v.d_vin,
+                               v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_ll, v.d_flags);
+            hipLaunchKernelGGL(k_vit_exits, dim3(CB), dim3(64), 0, st, ctx->C, ctx->d_chunk_seg0, v.d_smap, v.d_final, v.d_sexit);
+            hipLaunchKernelGGL(k_vit_back, dim3(G), dim3(64), 0, st, ctx->d_seg, v.d_bp, v.d_lmap, v.d_sexit, v.d_label);
+        } else {
+            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((ctx->N + 255) / 256)), dim3(256), 0, st, ctx->N, ctx->d_rec, ctx->d_beta,
+                               v.d_params, nbE, v.d_rows, v.d_flags);
+            hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) ctx->C), dim3(64), 0, st, ctx->d_off, ctx->d_rec, v.d_params, v.d_rows, v.d_bp,
+                               v.d_label, v.d_ll, v.d_flags);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
+    if (!ctx || !ctx->vit.launched) return set_err(HF_E_ARG, "hf_viterbi_finish: no hf_viterbi to finish");
+    hf_ctx::Viterbi& v = ctx->vit;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    v.launched = false;
+    unsigned fl = 0;
+    HIPCHK(hipMemcpy(&fl, v.d_flags, 4, hipMemcpyDeviceToHost));
+    if (fl) return flags_to_code(fl);
+    v.h_ll.assign((size_t) ctx->C, 0.0);
+    if (ctx->C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) ctx->C * 8, hipMemcpyDeviceToHost));
+    double tot = 0.0;
+    for (double x : v.h_ll) tot += x;   // chunk-list order
+    if (log_prob_host) *log_prob_host = tot;
+    v.done = true;
+    return HF_OK;
+}
+
+int hf_get_viterbi_labels(hf_ctx* ctx, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_labels: no finished hf_viterbi");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) ctx->N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_viterbi_chunk_log_probs(hf_ctx* ctx, double* out_host) {
+    if (!ctx || !out_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_chunk_log_probs: no finished hf_viterbi");
+    if (ctx->C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) ctx->C * 8);
     return HF_OK;
 }
 

@@ -197,7 +197,7 @@ int hf_shard_bounds(const int64_t* chunk_off, int32_t n_chunks, int world, int32
 // hf_multi: one worker thread per device
 // ------------------------------------------------------------------------------------------
 namespace {
-enum Cmd { CMD_NONE = 0, CMD_ESTEP, CMD_LABELS, CMD_POSTERIOR, CMD_EXIT };
+enum Cmd { CMD_NONE = 0, CMD_ESTEP, CMD_LABELS, CMD_POSTERIOR, CMD_VITERBI, CMD_VLABELS, CMD_EXIT };
 
 struct RankState {
     int r = 0, device = 0;
@@ -210,6 +210,7 @@ struct RankState {
     int32_t c0 = 0, nc = 0;            // chunk range
     std::vector<int64_t> off;          // shard's chunk_off (starting at 0)
     std::vector<double> stats;
+    std::vector<double> vit_ll;        // hf_multi_viterbi: this shard's chunk scores
     int rc = HF_OK; std::string err;
     std::thread th;
     hipEvent_t xe0 = nullptr, xe1 = nullptr; double x_us = 0.0; long x_n = 0;   // HF_HOST_TRACE=1: the all-gather, bracketed by events
@@ -234,6 +235,7 @@ struct hf_multi {
     const hf_params* p = nullptr; int mode = HF_MODE_FULL;
     int8_t* labels_out = nullptr;
     int64_t post_first = 0, post_n = 0; double* post_out = nullptr;
+    std::vector<double> vit_ll; bool vit_done = false;   // hf_multi_viterbi: every chunk's score, list order
 };
 
 namespace {
@@ -345,6 +347,15 @@ int rank_estep_once(hf_multi* M, RankState& R) {
     return rc;
 }
 
+// most-probable-path decoding of this rank's shard: no exchange, the chunk scores stay with the rank
+int rank_viterbi(hf_multi* M, RankState& R) {
+    int rc = hf_viterbi(R.ctx, M->p, R.st);
+    if (rc == HF_OK) rc = hf_viterbi_finish(R.ctx, nullptr, R.st);
+    if (rc == HF_OK) { R.vit_ll.assign((size_t) R.nc, 0.0); rc = hf_get_viterbi_chunk_log_probs(R.ctx, R.vit_ll.data()); }
+    if (rc != HF_OK) R.err = hf_last_error();
+    return rc;
+}
+
 void worker(hf_multi* M, int r) {
     RankState& R = M->ranks[(size_t) r];
     hipSetDevice(R.device);
@@ -365,6 +376,9 @@ void worker(hf_multi* M, int r) {
         if (cmd == CMD_ESTEP) R.rc = rank_estep(M, R);
         else if (cmd == CMD_LABELS) {
             if (R.nw > 0) { R.rc = hf_get_labels(R.ctx, M->labels_out + R.w0); if (R.rc) R.err = hf_last_error(); }
+        } else if (cmd == CMD_VITERBI) R.rc = rank_viterbi(M, R);
+        else if (cmd == CMD_VLABELS) {
+            if (R.nw > 0) { R.rc = hf_get_viterbi_labels(R.ctx, M->labels_out + R.w0); if (R.rc) R.err = hf_last_error(); }
         } else if (cmd == CMD_POSTERIOR) {
             const int64_t a = M->post_first > R.w0 ? M->post_first : R.w0;
             const int64_t b = M->post_first + M->post_n < R.w0 + R.nw ? M->post_first + M->post_n : R.w0 + R.nw;
@@ -583,6 +597,63 @@ int hf_multi_get_labels(hf_multi* M, int8_t* labels_host) {
         return rc == HF_OK ? HF_OK : merr(rc, hf_last_error());
     }
     return run_all(M, CMD_LABELS);
+}
+
+int hf_multi_viterbi(hf_multi* M, const hf_params* p, double* log_prob_host) {
+    if (!M || !p) return merr(HF_E_ARG, "hf_multi_viterbi: bad argument");
+    M->p = p; M->vit_done = false;
+    std::vector<double> ll((size_t) M->C, 0.0);
+    if (M->local_rank >= 0) {           // one process per GPU: the chunk scores of every rank, all-gathered once, + every rank's status
+        RankState& R = M->ranks[0];
+        hipSetDevice(R.device);
+        int rc = rank_viterbi(M, R);
+        const std::string err = R.err;
+        const int64_t cnt = (int64_t) M->maxc + 1;   // [maxc] scores, then the status word
+        double* d = nullptr;
+        std::vector<double> h((size_t) (M->world * cnt), 0.0);
+        for (int32_t c = 0; c < R.nc && rc == HF_OK; c++) h[(size_t) (R.r * cnt + c)] = R.vit_ll[(size_t) c];
+        h[(size_t) (R.r * cnt + M->maxc)] = (double) rc;
+        bool ok = hipMalloc((void**) &d, (size_t) (M->world * cnt) * 8) == hipSuccess &&
+                  hipMemcpy(d + R.r * cnt, h.data() + R.r * cnt, (size_t) cnt * 8, hipMemcpyHostToDevice) == hipSuccess;
+        // (a rank whose decode failed still takes part: the others are waiting in the collective)
+        ok = hf_comm_allgather(R.comm, d + R.r * cnt, d, cnt, R.st) == HF_OK && ok;
+        ok = ok && hipStreamSynchronize(R.st) == hipSuccess && hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
+        if (d) hipFree(d);
+        if (rc != HF_OK) return merr(rc, "rank " + std::to_string(R.r) + " (GPU " + std::to_string(R.device) + "): " + err);
+        if (!ok) return merr(HF_E_HIP, "hf_multi_viterbi: the ranks could not exchange their chunk scores");
+        for (int r = 0; r < M->world; r++)
+            if (h[(size_t) (r * cnt + M->maxc)] != 0.0) return merr((int) h[(size_t) (r * cnt + M->maxc)], "hf_multi_viterbi: rank " + std::to_string(r) + " failed");
+        for (int r = 0; r < M->world; r++)
+            for (int32_t c = M->bounds[(size_t) r]; c < M->bounds[(size_t) r + 1]; c++) ll[(size_t) c] = h[(size_t) (r * cnt + (c - M->bounds[(size_t) r]))];
+    } else {
+        const int rc = run_all(M, CMD_VITERBI);
+        if (rc != HF_OK) return rc;
+        for (const auto& R : M->ranks)
+            for (int32_t c = 0; c < R.nc; c++) ll[(size_t) (R.c0 + c)] = R.vit_ll[(size_t) c];
+    }
+    double tot = 0.0;
+    for (double x : ll) tot += x;   // chunk-list order: the sum of one context
+    if (log_prob_host) *log_prob_host = tot;
+    M->vit_ll.swap(ll); M->vit_done = true;
+    return HF_OK;
+}
+
+int hf_multi_get_viterbi_chunk_log_probs(hf_multi* M, double* out_host) {
+    if (!M || !out_host || !M->vit_done) return merr(HF_E_ARG, "hf_multi_get_viterbi_chunk_log_probs: no finished hf_multi_viterbi");
+    if (M->C > 0) std::memcpy(out_host, M->vit_ll.data(), (size_t) M->C * 8);
+    return HF_OK;
+}
+
+int hf_multi_get_viterbi_labels(hf_multi* M, int8_t* labels_host) {
+    if (!M || !labels_host || !M->vit_done) return merr(HF_E_ARG, "hf_multi_get_viterbi_labels: no finished hf_multi_viterbi");
+    M->labels_out = labels_host;
+    if (M->local_rank >= 0) {
+        RankState& R = M->ranks[0];
+        if (R.nw <= 0) return HF_OK;
+        const int rc = hf_get_viterbi_labels(R.ctx, labels_host + R.w0);
+        return rc == HF_OK ? HF_OK : merr(rc, hf_last_error());
+    }
+    return run_all(M, CMD_VLABELS);
 }
 
 int hf_multi_get_posterior(hf_multi* M, int64_t first, int64_t n, double* post_host) {

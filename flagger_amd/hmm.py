@@ -248,6 +248,24 @@ class MultiEMList:
             raise MultiHFError(rc, "hf_multi_get_posterior")
         return out
 
+    def viterbi(self, model: "HMM"):
+        """Most-probable-path decoding of every shard (hf_multi_viterbi): (labels, chunk_log_probs, log_prob).  RankEMList: the
+        labels of other ranks' windows are -1, the scores cover every chunk."""
+        p = model.params()
+        lp = C.c_double(0.0)
+        rc = self._L.hf_multi_viterbi(self._h, C.byref(p), C.byref(lp))
+        if rc != N.HF_OK:
+            raise MultiHFError(rc, "hf_multi_viterbi")
+        labels = np.full(self.store.n_windows, -1, dtype=np.int8)
+        rc = self._L.hf_multi_get_viterbi_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
+        if rc != N.HF_OK:
+            raise MultiHFError(rc, "hf_multi_get_viterbi_labels")
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        rc = self._L.hf_multi_get_viterbi_chunk_log_probs(self._h, _dptr(ll))
+        if rc != N.HF_OK:
+            raise MultiHFError(rc, "hf_multi_get_viterbi_chunk_log_probs")
+        return labels, ll, float(lp.value)
+
 
 HF_COMM_ID_BYTES = 128
 
@@ -520,6 +538,19 @@ class EMList:
         N.check(self._L.hf_get_posterior(self._h, first, n, _dptr(out)), "hf_get_posterior")
         return out
 
+    def viterbi(self, model: HMM):
+        """Most-probable-path decoding (hf_viterbi + hf_viterbi_finish): (labels, chunk_log_probs, log_prob).  The last pass's
+        results (labels(), posterior(), forward_backward()) are left as they were."""
+        p = model.params()
+        lp = C.c_double(0.0)
+        N.check(self._L.hf_viterbi(self._h, C.byref(p), self.stream), "hf_viterbi")
+        N.check(self._L.hf_viterbi_finish(self._h, C.byref(lp), self.stream), "hf_viterbi_finish")
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        N.check(self._L.hf_get_viterbi_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_viterbi_labels")
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        N.check(self._L.hf_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_chunk_log_probs")
+        return labels, ll, float(lp.value)
+
     def forward_backward(self, first: int = 0, n: Optional[int] = None):
         n = self.store.n_windows - first if n is None else n
         f, b, sc = np.empty((n, 4)), np.empty((n, 4)), np.empty(n)
@@ -548,6 +579,15 @@ def EM_runForwardForList(emList, model: HMM, threads: int = 0) -> None:
         emList.launch(model, N.HF_MODE_FORWARD_ONLY)
         stats = emList.finish()
     model.loglikelihood = float(stats[0])
+
+
+def EM_runViterbiForList(emList, model: HMM):
+    """Most-probable-path decoding of every chunk with the model's current parameters (no counterpart in the reference, which
+    decodes by posterior argmax only): (labels: int8[n_windows], chunk_log_probs: float64[n_chunks], log_prob: float), the run's
+    score being the sum of the chunk scores in list order.  `emList`: an EMList, MultiEMList or RankEMList."""
+    if not hasattr(emList, "viterbi"):
+        raise TypeError("EM_runViterbiForList: %s has no most-probable-path decoder" % type(emList).__name__)
+    return emList.viterbi(model)
 
 
 def HMM_estimateParameters(model: HMM, convergenceTol: float) -> bool:

@@ -231,6 +231,19 @@ int hf_get_labels(hf_ctx *ctx, int8_t *labels_host);                            
 int hf_get_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_host);        /* [n][4] hmm.c:671-685 */
 int hf_get_forward_backward(hf_ctx *ctx, int64_t first, int64_t n, double *f_host, double *b_host,
                             double *scales_host);                                      /* EM.f/.b/.scales */
+/* Most-probable-path (Viterbi) decoding of every chunk (flagger_amd/csrc/hf_viterbi.h): with the parameters `p`, for a chunk of T windows
+ *   s* = argmax over s_0..s_{T-1} of first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}],
+ *   first[s] = trans[r_0][4][s] * e_0[s],  A_t = the row a pass builds (transition x emission),  end[s] = trans[r_{T-1}][s][4];
+ * ties go to the lowest state index (at every backpointer and at the final state).  The chunk's score is log of that maximum, the
+ * run's score the sum over chunks in list order.  HF_E_SCALE when no path of a chunk has weight, HF_E_NAN on a NaN.
+ * Decoding uses buffers of its own: the last pass's results (hf_get_labels / _posterior / _forward_backward) and the next hf_estep
+ * are unaffected.  hf_viterbi is asynchronous on `stream`; hf_viterbi_finish waits, translates the error flags and returns the run's
+ * score.  The getters answer for the last FINISHED run (HF_E_ARG before any). */
+int hf_viterbi(hf_ctx *ctx, const hf_params *p, void *stream);
+int hf_viterbi_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
+int hf_get_viterbi_labels(hf_ctx *ctx, int8_t *labels_host);                          /* [n_windows], layout of hf_labels_dev */
+int hf_get_viterbi_chunk_log_probs(hf_ctx *ctx, double *out_host);                    /* [n_chunks] */
+
 /* kernel time of the last hf_estep + reduce in milliseconds (HIP events on the stream used); recorded only while
  * hf_set_profiling's mask carries HF_PROF_PASS (two extra stream packets per pass) */
 int hf_last_kernel_ms(hf_ctx *ctx, float *ms);

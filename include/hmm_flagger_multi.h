@@ -87,6 +87,13 @@ struct hfm_model;
 int hf_multi_em_iterate(hf_multi *m, struct hfm_model *model, int mode, int do_mstep, double tol, double *stats_host, int *converged);
 int hf_multi_get_labels(hf_multi *m, int8_t *labels_host);                              /* [n_windows], list order */
 int hf_multi_get_posterior(hf_multi *m, int64_t first, int64_t n, double *post_host);   /* [n][4] */
+/* Most-probable-path decoding (hf_viterbi) of every shard: chunks are independent chains, so no GPU exchanges anything but the
+ * per-chunk scores (one all-gather in the one-process-per-GPU form); log_prob_host = their sum in chunk-list order, bit-identical for
+ * every number of GPUs.  hf_multi_get_viterbi_labels: list order, as hf_multi_get_labels (one process per GPU: this rank's windows);
+ * the getters answer HF_E_ARG before a finished run. */
+int hf_multi_viterbi(hf_multi *m, const hf_params *p, double *log_prob_host);
+int hf_multi_get_viterbi_labels(hf_multi *m, int8_t *labels_host);
+int hf_multi_get_viterbi_chunk_log_probs(hf_multi *m, double *out_host);   /* [n_chunks], every chunk (all ranks) */
 int hf_multi_world(const hf_multi *m);
 int hf_multi_comm_ranks(const hf_multi *m);   /* ranks of the RCCL communicator, as ncclCommCount reports them (loopback: the group size) */
 int64_t hf_multi_stats_len(const hf_multi *m);
