@@ -114,6 +114,17 @@ def lib() -> C.CDLL:
     sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
+    sig("hf_batch_capacity", C.c_int, vp)
+    sig("hf_batch_create", C.c_int, vp, C.c_int, C.POINTER(vp))
+    sig("hf_batch_destroy", None, vp)
+    sig("hf_batch_size", C.c_int, vp)
+    sig("hf_batch_shared_models", C.c_int, vp)
+    sig("hf_batch_estep", C.c_int, vp, C.POINTER(hf_params), C.POINTER(i32), C.c_int, C.c_int, vp)
+    sig("hf_batch_finish", C.c_int, vp, pd, C.POINTER(i32), vp)
+    sig("hf_batch_get_labels", C.c_int, vp, C.c_int, C.POINTER(C.c_int8))
+    sig("hf_batch_get_posterior", C.c_int, vp, C.c_int, i64, i64, pd)
+    sig("hf_em_iterate_batch", C.c_int, vp, C.POINTER(vp), C.POINTER(i32), C.c_int, C.c_int, C.c_int, dbl, pd, C.POINTER(i32),
+        C.POINTER(C.c_int), vp)
     sig("hf_last_kernel_ms", C.c_int, vp, C.POINTER(C.c_float))
     sig("hf_set_profiling", C.c_int, vp, C.c_uint)
     sig("hf_set_profiling_stride", C.c_int, vp, C.c_int)

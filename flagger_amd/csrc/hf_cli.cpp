@@ -57,6 +57,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"gpus", required_argument, nullptr, 1003},            // chunks sharded over GPUs device..device+N-1, one RCCL all-gather per pass
     {"exchange", required_argument, nullptr, 1004},        // chunks (default: bit-identical for every N) | ranks (one vector per GPU: faster)
     {"viterbi", no_argument, nullptr, 1005},               // final labels by most-probable path (hf_viterbi) instead of posterior argmax
+    {"sweepAlpha", required_argument, nullptr, 1006},      // one run per alpha TSV of a list, one load (not `alpha...`: --alpha stays unique)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -92,7 +93,10 @@ static void usage(const char* program) {
             "                                      can carry into the last printed digits)\n"
             "         --viterbi                    final labels (final BED, final summary tables) by the most probable state path with\n"
             "                                      the final parameters instead of the posterior argmax; its log-probability goes to\n"
-            "                                      viterbi_log_probability.tsv (-P still writes the posterior BED)\n");
+            "                                      viterbi_log_probability.tsv (-P still writes the posterior BED)\n"
+            "         --sweepAlpha LIST            one EM run per alpha TSV listed in LIST (one path per line; blank lines and lines starting\n"
+            "                                      with # are skipped), the input loaded once: line i writes every output file of an\n"
+            "                                      --alphaTsv run into <outputDir>/alpha_<i>/, and <outputDir>/alpha_sweep.tsv sums them up\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -166,6 +170,15 @@ struct SummaryJob {
 };
 static std::vector<std::unique_ptr<SummaryJob>> g_summaries;
 static void summary_wait_quietly() { for (auto& j : g_summaries) if (j->th.joinable()) j->th.join(); }
+// --sweepAlpha: wait for every table worker; a failed table set is reported and fails its candidate only (the sweep goes on)
+static bool summary_join_report() {
+    summary_wait_quietly();
+    bool ok = true;
+    for (auto& j : g_summaries)
+        if (j->rc != 0) { fprintf(stderr, "[%s] %s\n", ts(), j->err.c_str()); ok = false; }
+    g_summaries.clear();
+    return ok;
+}
 static void summary_join() {
     summary_wait_quietly();
     for (auto& j : g_summaries)
@@ -221,10 +234,39 @@ static void write_params(const hfm_model* m, const std::string& dir, const std::
     hfm_write_emission_tsv(m, (dir + "/emission_" + suffix + ".tsv").c_str());
 }
 
+// --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
+static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
+    FILE* f = fopen(listPath, "r");
+    if (!f) { fprintf(stderr, "[%s] Error: cannot read the --sweepAlpha list %s\n", ts(), listPath); return false; }
+    char line[8192];
+    while (fgets(line, sizeof line, f)) {
+        std::string t(line);
+        while (!t.empty() && (t.back() == '\n' || t.back() == '\r' || t.back() == ' ' || t.back() == '\t')) t.pop_back();
+        size_t a = 0;
+        while (a < t.size() && (t[a] == ' ' || t[a] == '\t')) a++;
+        t = t.substr(a);
+        if (t.empty() || t[0] == '#') continue;
+        paths.push_back(t);
+    }
+    fclose(f);
+    if (paths.empty()) { fprintf(stderr, "[%s] Error: the --sweepAlpha list %s names no alpha TSV.\n", ts(), listPath); return false; }
+    for (const auto& pth : paths) {
+        std::vector<double> al(16, 0.0);
+        const int rc = hfm_read_alpha_tsv(pth.c_str(), al.data());
+        if (rc == -2) { fprintf(stderr, "[%s] Error: There is at least one alpha value in '%s' not between 0 and 1. \n", ts(), pth.c_str()); return false; }
+        if (rc != 0) { fprintf(stderr, "[%s] Error: cannot read %s (--sweepAlpha list %s)\n", ts(), pth.c_str(), listPath); return false; }
+        alphas.push_back(al);
+    }
+    return true;
+}
+
+// closes the log-likelihood table of a run however the run ends (a failed E-step leaves what it wrote, as a separate process does)
+struct FileCloser { FILE*& f; ~FileCloser() { if (f) fclose(f); f = nullptr; } };
+
 int main(int argc, char* argv[]) {
     const char* trackName = "final_hmm_flagger";
     std::string preset = "hifi";
-    const char *inputPath = nullptr, *alphaTsvPath = nullptr, *contigListPath = nullptr, *outputDir = nullptr;
+    const char *inputPath = nullptr, *alphaTsvPath = nullptr, *contigListPath = nullptr, *outputDir = nullptr, *sweepListPath = nullptr;
     int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
     double initialRandomDeviation = 0.0;
@@ -298,6 +340,7 @@ int main(int argc, char* argv[]) {
             case 1002: algo = !strcmp(optarg, "seq") ? HF_ALGO_SEQ : HF_ALGO_SCAN; break;
             case 1003: nGpus = atoi(optarg); break;
             case 1005: viterbi = true; break;
+            case 1006: sweepListPath = optarg; break;
             case 1004:
                 if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
                 else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
@@ -339,6 +382,13 @@ int main(int argc, char* argv[]) {
     else if (preset == "ont-r10") { presetW = 8000; presetF = 0.8; }
     else { fprintf(stderr, "[%s] Error: preset can be one of hifi, ont-r9, ont-r10. It cannot be %s . \n", ts(), preset.c_str()); return EXIT_FAILURE; }
     double alpha[16] = {0};
+    // --sweepAlpha: the list and every TSV in it are checked before the input is read or a device is touched
+    std::vector<std::string> sweepPaths;
+    std::vector<std::vector<double>> sweepAlphas;
+    if (sweepListPath) {
+        if (alphaTsvPath) { fprintf(stderr, "[%s] Error: --sweepAlpha and --alphaTsv exclude each other.\n", ts()); return EXIT_FAILURE; }
+        if (!read_sweep_list(sweepListPath, sweepPaths, sweepAlphas)) return EXIT_FAILURE;
+    }
     if (alphaTsvPath) {
         const int rc = hfm_read_alpha_tsv(alphaTsvPath, alpha);
         if (rc == -2) { fprintf(stderr, "[%s] Error: There is at least one alpha value in '%s' not between 0 and 1. \n", ts(), alphaTsvPath); return EXIT_FAILURE; }
@@ -396,24 +446,29 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] The number of components for the 'collapsed' state is set by the program argument %d. \n", ts(), numberOfCollapsedComps);
     }
 
-    // 3. model (createModel, hmm_flagger.c:164-237)
-    fprintf(stderr, "[%s] Creating HMM model. \n", ts());
-    hfm_model* model = hfm_create(modelType, numberOfCollapsedComps, hfio_region_coverages(tab), hfio_n_regions(tab),
-                                  hfio_start_only(tab), hfio_avg_alignment_len(tab), hfio_window_len(tab), alpha,
+    // 3. model (createModel, hmm_flagger.c:164-237); --sweepAlpha builds every candidate's model the same way, with its own alpha
+    auto make_model = [&](const double* alpha16) -> hfm_model* {
+        fprintf(stderr, "[%s] Creating HMM model. \n", ts());
+        hfm_model* m = hfm_create(modelType, numberOfCollapsedComps, hfio_region_coverages(tab), hfio_n_regions(tab),
+                                  hfio_start_only(tab), hfio_avg_alignment_len(tab), hfio_window_len(tab), alpha16,
                                   maxHighMapqRatio, minHighMapqRatio);
-    if (!model) { fprintf(stderr, "[%s] Error: cannot create the model (collapsedComps must be 1..%d, regions 1..%d).\n", ts(), HF_MAXCOMP, HF_MAXREGIONS); return EXIT_FAILURE; }
-    if (modelType == HF_MODEL_NEGATIVE_BINOMIAL) {         // the model's per-x tables: only up to the largest coverage present
-        hf_windows wv;
-        hfio_windows(tab, &wv);
-        int maxx = 0;
-        for (int64_t i = 0; i < wv.n_windows; i++) { const int x = wv.cov[i] & 0xff; if (x > maxx) maxx = x; }
-        hfm_set_max_coverage(model, maxx);
-    }
-    if (initialRandomDeviation > 0.0) {                    // hmm_flagger.c:213-220: same factor within one second
-        std::vector<double> pv((size_t) hfm_param_len(model));
-        hfm_get_param_vector(model, pv.data());
-        hfm_scale_initial_means(model, random_factor(initialRandomDeviation));
-    }
+        if (!m) { fprintf(stderr, "[%s] Error: cannot create the model (collapsedComps must be 1..%d, regions 1..%d).\n", ts(), HF_MAXCOMP, HF_MAXREGIONS); return nullptr; }
+        if (modelType == HF_MODEL_NEGATIVE_BINOMIAL) {     // the model's per-x tables: only up to the largest coverage present
+            hf_windows wv;
+            hfio_windows(tab, &wv);
+            int maxx = 0;
+            for (int64_t i = 0; i < wv.n_windows; i++) { const int x = wv.cov[i] & 0xff; if (x > maxx) maxx = x; }
+            hfm_set_max_coverage(m, maxx);
+        }
+        if (initialRandomDeviation > 0.0) {                // hmm_flagger.c:213-220: same factor within one second
+            std::vector<double> pv((size_t) hfm_param_len(m));
+            hfm_get_param_vector(m, pv.data());
+            hfm_scale_initial_means(m, random_factor(initialRandomDeviation));
+        }
+        return m;
+    };
+    hfm_model* model = make_model(sweepListPath ? sweepAlphas[0].data() : alpha);
+    if (!model) return EXIT_FAILURE;
 
     phase("model");
     // 4. device context: windows resident in HBM for the whole run
@@ -447,16 +502,21 @@ int main(int argc, char* argv[]) {
     }
 
     phase("hf_create");
-    // 5. EM (runHMMFlagger, hmm_flagger.c:285-488)
+    const int nChunks = hfio_n_chunks(tab);
+    // what one run reports to the --sweepAlpha summary
+    struct RunResult { int iterations = 0; bool converged = false; double ll = 0.0; int status = HF_OK; bool have_ll = false; };
+    // 5.-6. one whole run with `model` into `dir`: EM, final inference, every output file (runHMMFlagger, hmm_flagger.c:285-488)
+    auto run_em = [&](hfm_model* model, const std::string& dir, RunResult& res) -> int {
+    int rc;
     fprintf(stderr, "[%s] Running EM for estimating parameters. \n", ts());
-    const std::string dir(outputDir);
     FILE* llf = fopen((dir + "/loglikelihood.tsv").c_str(), "w+");
-    if (!llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), outputDir); return EXIT_FAILURE; }
+    if (!llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
+    FileCloser llfClose{llf};
+    auto die = [&](int r) { res.status = r; return die_estep(r); };
     fprintf(llf, "#Iteration\tEffective_Iteration\tLoglikelihood\n");
     write_params(model, dir, "initial");
     int iter = 1;
     bool converged = false;
-    const int nChunks = hfio_n_chunks(tab);
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
     const double emStart = real_time();
@@ -473,15 +533,16 @@ int main(int argc, char* argv[]) {
     };
     while (iter <= numberOfIterations && !converged) {
         fprintf(stderr, "[%s] [Iteration %s = %d] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), acceleration ? "accelerated" : "", iter, nChunks, device);
-        if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die_estep(rc);
+        if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die(rc);
         passes++;
         fprintf(stderr, "[%s] [Iteration %s = %d] EM jobs are all finished.\n", ts(), acceleration ? "accelerated" : "", iter);
         fprintf(llf, "%d\t%d\t%.4f\n", iter - 1, acceleration ? 3 * (iter - 1) : iter - 1, run.stats[0]);
+        res.ll = run.stats[0]; res.have_ll = true;
         if (writeBenchmarkingStatsPerIteration || iter == 1) {   // hmm_flagger.c:360-379
             char suffix[64];
             if (iter == 1) snprintf(suffix, sizeof suffix, "initial");
             else snprintf(suffix, sizeof suffix, acceleration ? "iteration_accelerated_%d" : "iteration_%d", iter - 1);
-            if ((rc = write_summary(run, dir, suffix, labelNames, binArrayFilePath, overlapRatioThreshold, threads, nullptr)) != HF_OK) return die_estep(rc);
+            if ((rc = write_summary(run, dir, suffix, labelNames, binArrayFilePath, overlapRatioThreshold, threads, nullptr)) != HF_OK) return die(rc);
         }
         if (acceleration) {                                  // hmm_flagger.c:382-416
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Running SQUAREM acceleration.\n", ts(), iter);
@@ -494,7 +555,7 @@ int main(int argc, char* argv[]) {
             const double t0 = real_time();
             rc = squarem_iteration(&model, run.stats, convergenceTol, estep_cb, &passes);
             emTime += real_time() - t0;
-            if (rc != HF_OK) return die_estep(rc);
+            if (rc != HF_OK) return die(rc);
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Finished SQUAREM acceleration.\n", ts(), iter);
         }
         {
@@ -512,16 +573,19 @@ int main(int argc, char* argv[]) {
     }
     if (converged) fprintf(stderr, "[%s] Parameters converged after %d iterations (tol=%.2e)\n", ts(), iter - 1, convergenceTol);
     else fprintf(stderr, "[%s] Parameter estimation stopped (not yet converged based on the given tolerance) after %d iterations (tol=%.2e)\n", ts(), iter - 1, convergenceTol);
+    res.iterations = iter - 1; res.converged = converged;
     fprintf(stderr, "[%s] [Final Inference] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), nChunks, device);
-    if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die_estep(rc);
+    if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die(rc);
     passes++;
     const double emWall = real_time() - emStart;
     fprintf(stderr, "[%s] [Final Inference] EM jobs are all finished.\n", ts());
     fprintf(llf, "%d\t%d\t%.4f\n", iter - 1, acceleration ? 3 * (iter - 1) : iter - 1, run.stats[0]);
+    res.ll = run.stats[0]; res.have_ll = true;
     fclose(llf);
+    llf = nullptr;
     write_params(model, dir, "final");
     std::vector<int8_t> labels((size_t) N);
-    if ((rc = run.labels(labels.data())) != HF_OK) return die_estep(rc);
+    if ((rc = run.labels(labels.data())) != HF_OK) return die(rc);
     // --viterbi: the final BED and the final tables take the most probable path under the final parameters; everything else
     // (the posterior BED of -P among it) keeps the posterior labels of the final pass
     std::vector<int8_t> vlabels;
@@ -529,7 +593,7 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] [Final Inference] Most probable state path of %d chunks ...\n", ts(), nChunks);
         vlabels.resize((size_t) N);
         double vlp = 0.0;
-        if ((rc = run.viterbi(model, vlabels.data(), &vlp)) != HF_OK) return die_estep(rc);
+        if ((rc = run.viterbi(model, vlabels.data(), &vlp)) != HF_OK) return die(rc);
         const std::string vp = dir + "/viterbi_log_probability.tsv";
         FILE* vf = fopen(vp.c_str(), "w");
         if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); return EXIT_FAILURE; }
@@ -538,11 +602,11 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] [Final Inference] Most probable path: log-probability %.6f\n", ts(), vlp);
     }
     const int8_t* finalLabels = viterbi ? vlabels.data() : labels.data();
-    if ((rc = write_summary(run, dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) return die_estep(rc);
+    if ((rc = write_summary(run, dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) return die(rc);
     memcpy(hfio_prediction(tab), labels.data(), (size_t) N);
     if (writePosterior) {
         std::vector<double> post((size_t) N * 4);
-        if ((rc = run.posterior(0, N, post.data())) != HF_OK) return die_estep(rc);
+        if ((rc = run.posterior(0, N, post.data())) != HF_OK) return die(rc);
         const std::string pp = dir + "/posterior_prediction_final.bed";
         fprintf(stderr, "[%s] Writing posterior bed : %s\n", ts(), pp.c_str());
         hfio_write_posterior_bed(tab, post.data(), labels.data(), pp.c_str());
@@ -556,14 +620,177 @@ int main(int argc, char* argv[]) {
     // 6. final BED
     fprintf(stderr, "[%s] Writing final BED file. \n", ts());
     if (hfio_write_final_bed(tab, finalLabels, (dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
-        fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), outputDir);
+        fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), dir.c_str());
         return EXIT_FAILURE;
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);
     phase("final BED");
-    summary_join();                                // the table workers (the reference writes the tables before the BED; the files are the same)
+    if (!sweepListPath) summary_join();            // the table workers (the reference writes the tables before the BED; the files are the same)
+    else if (!summary_join_report()) return EXIT_FAILURE;
     phase("summary tables joined");
+    return 0;
+    };
+    if (!sweepListPath) {
+        RunResult res;
+        const int r = run_em(model, std::string(outputDir), res);
+        if (r != 0) return r;
+    } else {
+        const size_t n = sweepPaths.size();
+        std::vector<RunResult> results(n);
+        bool anyFailed = false;
+        // plain EM on one context of the default algorithm, Gaussian models: the BATCHED engine (hf_batch_*, flagger_amd/csrc/hf_batch.h) —
+        // every pass runs all unconverged candidates of a group together; a candidate leaves the active set after its final inference
+        // pass, so its iterations and files are those of a separate --alphaTsv run.  Everything else: the candidates one after another.
+        const int cap = (!run.multi && !acceleration && modelType != HF_MODEL_NEGATIVE_BINOMIAL) ? hf_batch_capacity(run.ctx) : 0;
+        if (cap > 0) {
+            const int G = (int) std::min<size_t>((size_t) cap, n);
+            fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: batched (hf_batch), %d models per group\n", ts(), n, G);
+            const int64_t V = hf_chunk_stats_len(run.ctx);
+            struct Cand { hfm_model* m = nullptr; FILE* llf = nullptr; int iter = 1; bool converged = false, final = false, done = false; std::string dir; };
+            for (size_t g0 = 0; g0 < n; g0 += (size_t) G) {
+                const int ng = (int) std::min<size_t>((size_t) G, n - g0);
+                hf_batch* bt = nullptr;
+                if (hf_batch_create(run.ctx, ng, &bt) != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_last_error()); return EXIT_FAILURE; }
+                std::vector<Cand> cs((size_t) ng);
+                for (int j = 0; j < ng; j++) {
+                    const size_t i = g0 + (size_t) j;
+                    Cand& c = cs[(size_t) j];
+                    c.dir = std::string(outputDir) + "/alpha_" + std::to_string(i + 1);
+                    if (!dir_exists(c.dir.c_str()) && mkdir(c.dir.c_str(), 0777) != 0) { fprintf(stderr, "[%s] Error: cannot create %s\n", ts(), c.dir.c_str()); return EXIT_FAILURE; }
+                    c.m = i == 0 ? model : make_model(sweepAlphas[i].data());
+                    if (!c.m) return EXIT_FAILURE;
+                    fprintf(stderr, "[%s] --sweepAlpha: candidate %zu of %zu (%s) into %s\n", ts(), i + 1, n, sweepPaths[i].c_str(), c.dir.c_str());
+                    c.llf = fopen((c.dir + "/loglikelihood.tsv").c_str(), "w+");
+                    if (!c.llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), c.dir.c_str()); return EXIT_FAILURE; }
+                    fprintf(c.llf, "#Iteration\tEffective_Iteration\tLoglikelihood\n");
+                    write_params(c.m, c.dir, "initial");
+                    c.final = numberOfIterations < 1;
+                }
+                std::vector<int8_t> lab((size_t) N);
+                while (true) {
+                    std::vector<int32_t> act;
+                    std::vector<hf_params> ps;
+                    for (int j = 0; j < ng; j++) if (!cs[(size_t) j].done) { act.push_back(j); ps.emplace_back(); hfm_params(cs[(size_t) j].m, &ps.back()); }
+                    if (act.empty()) break;
+                    std::vector<double> stats(act.size() * (size_t) V);
+                    std::vector<int32_t> status(act.size(), HF_OK);
+                    int rc = hf_batch_estep(bt, ps.data(), act.data(), (int) act.size(), HF_MODE_FULL, nullptr);
+                    if (rc == HF_OK) rc = hf_batch_finish(bt, stats.data(), status.data(), nullptr);
+                    if (rc != HF_OK) return die_estep(rc);
+                    for (size_t k = 0; k < act.size(); k++) {
+                        const int j = act[k];
+                        Cand& c = cs[(size_t) j];
+                        RunResult& res = results[g0 + (size_t) j];
+                        const double* st = stats.data() + k * (size_t) V;
+                        auto fail = [&](int r) {
+                            if (r == HF_E_SCALE) fprintf(stderr, "scale is very low!\n");
+                            else if (r == HF_E_NAN) fprintf(stderr, "[Error] prob is NAN\n");
+                            else fprintf(stderr, "[%s] Error: %s\n", ts(), cli_error_or(hf_last_error()));
+                            g_cli_error.clear();
+                            res.status = r == HF_OK ? HF_E_ARG : r; anyFailed = true; c.done = true;
+                            if (c.llf) fclose(c.llf);
+                            c.llf = nullptr;
+                        };
+                        if (status[k] != HF_OK) { fail(status[k]); continue; }
+                        fprintf(c.llf, "%d\t%d\t%.4f\n", c.iter - 1, c.iter - 1, st[0]);
+                        res.ll = st[0]; res.have_ll = true;
+                        if (!c.final) {
+                            if (writeBenchmarkingStatsPerIteration || c.iter == 1) {
+                                char suffix[64];
+                                if (c.iter == 1) snprintf(suffix, sizeof suffix, "initial");
+                                else snprintf(suffix, sizeof suffix, "iteration_%d", c.iter - 1);
+                                if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK ||
+                                    (rc = write_summary(run, c.dir, suffix, labelNames, binArrayFilePath, overlapRatioThreshold, threads, lab.data())) != HF_OK) { fail(rc); continue; }
+                            }
+                            c.converged = hfm_estimate(c.m, st, convergenceTol) != 0;
+                            if (writeParamsPerIter) {
+                                char suffix[64];
+                                snprintf(suffix, sizeof suffix, "iteration_%d", c.iter);
+                                write_params(c.m, c.dir, suffix);
+                            }
+                            c.iter += 1;
+                            if (c.iter > numberOfIterations || c.converged) {
+                                res.iterations = c.iter - 1; res.converged = c.converged;
+                                c.final = true;                          // the next pass of this candidate is its final inference
+                            }
+                            continue;
+                        }
+                        // the final inference pass: every output of a separate run
+                        res.iterations = c.iter - 1; res.converged = c.converged;
+                        fclose(c.llf);
+                        c.llf = nullptr;
+                        write_params(c.m, c.dir, "final");
+                        if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK) { fail(rc); continue; }
+                        std::vector<int8_t> vlabels;
+                        if (viterbi) {
+                            vlabels.resize((size_t) N);
+                            double vlp = 0.0;
+                            if ((rc = run.viterbi(c.m, vlabels.data(), &vlp)) != HF_OK) { fail(rc); continue; }
+                            const std::string vp = c.dir + "/viterbi_log_probability.tsv";
+                            FILE* vf = fopen(vp.c_str(), "w");
+                            if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); fail(HF_E_ARG); continue; }
+                            fprintf(vf, "%.6f\n", vlp);
+                            fclose(vf);
+                        }
+                        const int8_t* finalLabels = viterbi ? vlabels.data() : lab.data();
+                        if ((rc = write_summary(run, c.dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) { fail(rc); continue; }
+                        memcpy(hfio_prediction(tab), lab.data(), (size_t) N);
+                        if (writePosterior) {
+                            std::vector<double> post((size_t) N * 4);
+                            if ((rc = hf_batch_get_posterior(bt, j, 0, N, post.data())) != HF_OK) { fail(rc); continue; }
+                            hfio_write_posterior_bed(tab, post.data(), lab.data(), (c.dir + "/posterior_prediction_final.bed").c_str());
+                        }
+                        if (hfio_write_final_bed(tab, finalLabels, (c.dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
+                            fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), c.dir.c_str()); fail(HF_E_ARG); continue;
+                        }
+                        c.done = true;
+                    }
+                }
+                if (!summary_join_report()) { anyFailed = true; }
+                hf_batch_destroy(bt);
+            }
+        } else {
+        // --sweepAlpha: the candidates one after another on the context (or GPU list) loaded above, each exactly a separate run
+        fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: sequential (%s), 1 model per group\n", ts(), n,
+                run.multi ? "sharded GPU list" : "one context");
+        for (size_t i = 0; i < n; i++) {
+            const std::string cdir = std::string(outputDir) + "/alpha_" + std::to_string(i + 1);
+            if (!dir_exists(cdir.c_str()) && mkdir(cdir.c_str(), 0777) != 0) {
+                fprintf(stderr, "[%s] Error: cannot create %s\n", ts(), cdir.c_str()); return EXIT_FAILURE;
+            }
+            hfm_model* m = i == 0 ? model : make_model(sweepAlphas[i].data());
+            if (!m) return EXIT_FAILURE;
+            fprintf(stderr, "[%s] --sweepAlpha: candidate %zu of %zu (%s) into %s\n", ts(), i + 1, n, sweepPaths[i].c_str(), cdir.c_str());
+            const int r = run_em(m, cdir, results[i]);
+            if (r != 0) {
+                anyFailed = true;
+                if (results[i].status == HF_OK) results[i].status = HF_E_ARG;
+                g_cli_error.clear();
+                // (a failed table set of this candidate has been reported; the next candidate starts with no worker of its own pending)
+                summary_wait_quietly();
+                g_summaries.clear();
+            }
+        }
+        }
+        const std::string sp = std::string(outputDir) + "/alpha_sweep.tsv";
+        FILE* sf = fopen(sp.c_str(), "w");
+        if (!sf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), sp.c_str()); return EXIT_FAILURE; }
+        fprintf(sf, "#Index\tAlpha_Tsv\tIterations\tConverged\tLoglikelihood\tStatus\n");
+        for (size_t i = 0; i < n; i++) {
+            const RunResult& r = results[i];
+            const char* st = r.status == HF_OK ? "ok" : r.status == HF_E_SCALE ? "scale_too_low" : r.status == HF_E_NAN ? "nan" : "error";
+            if (r.have_ll) fprintf(sf, "%zu\t%s\t%d\t%d\t%.4f\t%s\n", i + 1, sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, r.ll, st);
+            else fprintf(sf, "%zu\t%s\t%d\t%d\tNA\t%s\n", i + 1, sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, st);
+        }
+        fclose(sf);
+        if (anyFailed) {
+            if (run.multi) hf_multi_destroy(run.multi);
+            fprintf(stderr, "[%s] Error: at least one --sweepAlpha candidate failed (%s)\n", ts(), sp.c_str());
+            fflush(nullptr);
+            _exit(EXIT_FAILURE);
+        }
+    }
     if (run.multi) hf_multi_destroy(run.multi);   // (joins the ranks' threads and communicators: RCCL wants an orderly end)
     // the one-GPU context, the model and the window table are NOT destroyed: the process ends below without unwinding anything
     // (freeing ~40 device allocations one by one was 5 ms of a 0.15 s run)

@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include <thread>
+#include <unistd.h>
 #include <immintrin.h>
 static thread_local std::string g_err;
 
@@ -942,16 +943,22 @@ static bool pack_kparams(hf_ctx* ctx, const hf_params* p) {
 // everything one pass enqueues on `st` after the parameters were packed into the pinned block
 // retry: the pass again after HF_E_RETRY (hf_finish) — the caller's negative_binomial tables went up with the first attempt and
 // may have been freed or rewritten since (hf_estep and hf_finish are separate calls): they are NOT read again
-static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t st, bool retry = false) {
+// phase (hf_batch.h): the parts of the pass to enqueue — PASS_PRE the parameter block and the tables, PASS_SEG the segment kernel, PASS_POST
+// the statistics; a batch enqueues PRE and POST per model and the segment kernel of all models in one launch
+enum { PASS_PRE = 1, PASS_SEG = 2, PASS_POST = 4, PASS_ALL = 7 };
+static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t st, bool retry = false, int phase = PASS_ALL) {
+    const bool ph_pre = (phase & PASS_PRE) != 0, ph_seg = (phase & PASS_SEG) != 0, ph_post = (phase & PASS_POST) != 0;
     // the parameter block: through the kernel arguments of k_tables when it fits them (one region, HF_ALGO_SCAN, Gaussian models:
     // hf_device.h KParams), a copy ahead of the pass otherwise
-    ctx->kp_now = ctx->kp_ok && ctx->C > 0 && ctx->algo == HF_ALGO_SCAN && p->model_type != HF_MODEL_NEGATIVE_BINOMIAL && pack_kparams(ctx, p);
-    if (!ctx->kp_now) HIPCHK(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->params_bytes, hipMemcpyHostToDevice, st));
-    for (int i = 0; i < HF_NKERNELS; i++) { ctx->kran[i] = false; ctx->klast_ok[i] = false; }
-    ctx->prof_now = ctx->prof_stride <= 1 || (ctx->prof_pass++ % ctx->prof_stride) == 0;
+    if (ph_pre) {
+        ctx->kp_now = ctx->kp_ok && ctx->C > 0 && ctx->algo == HF_ALGO_SCAN && p->model_type != HF_MODEL_NEGATIVE_BINOMIAL && pack_kparams(ctx, p);
+        if (!ctx->kp_now) HIPCHK(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->params_bytes, hipMemcpyHostToDevice, st));
+        for (int i = 0; i < HF_NKERNELS; i++) { ctx->kran[i] = false; ctx->klast_ok[i] = false; }
+        ctx->prof_now = ctx->prof_stride <= 1 || (ctx->prof_pass++ % ctx->prof_stride) == 0;
+    }
     ctx->pass_rows = false; ctx->pass_bound = false;
     ctx->pass_seg = false;
-    if (ctx->C == 0) HIPCHK(hipMemsetAsync(ctx->d_flags, 0, 4, st));
+    if (ctx->C == 0 && ph_pre) HIPCHK(hipMemsetAsync(ctx->d_flags, 0, 4, st));
     if (ctx->C > 0) {
         const RowSrc S = row_src(ctx);
         const bool full = mode == HF_MODE_FULL;
@@ -998,7 +1005,7 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
                 ctx->nb_ev_used[b] = true;
             }
         }
-        {   // also clears the flag word: first kernel of every pass
+        if (ph_pre) {   // also clears the flag word: first kernel of every pass
             KTimer t(ctx, st, HF_K_TABLES);
             // statistics by emission row: the job list of the Gaussian tables is the (key, class) list of the rows of A (hf_seg.h)
             const bool arows = !nbm && seg_pass(ctx);
@@ -1050,19 +1057,19 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
                     std::fprintf(stderr, "[hf host trace] segment kernels (%s): %d workgroups of 64 threads, %zu B of LDS; resident per CU: k_seg_prod %d, k_seg_fb %d\n",
                                  ctx->seg_fused ? "one launch" : "two launches", ctx->nseg, lds, o1, o2);
                 }
-                if (nbm) {   // k_tables_nb leaves the emission rows; the Gaussian k_tables writes the rows of A itself
+                if (nbm && ph_pre) {   // k_tables_nb leaves the emission rows; the Gaussian k_tables writes the rows of A itself
                     KTimer t(ctx, st, HF_K_AROWS);
                     hipLaunchKernelGGL(k_arows, dim3((unsigned) (((int64_t) ctx->n_arows * 16 + 255) / 256)), dim3(256), 0, st, ctx->n_arows,
                                        ctx->d_arow_src, ctx->d_arow_cls, ctx->d_lutE, ctx->d_params, ctx->d_lutA);
                 }
-                if (!ctx->seg_fused) {
+                if (!ctx->seg_fused && ph_seg) {
                     if (!ctx->d_segQ) HIPCHK(hipMalloc((void**) &ctx->d_segQ, (size_t) ctx->nseg * 64 * 16 * 8));   // lane products: two-launch mode only
                     KTimer t(ctx, st, HF_K_SEG_PROD);
                     hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) ctx->nseg), dim3(64), seg_lds_bytes(), st, ctx->d_seg, ctx->d_arow, ctx->d_lutA, ctx->d_segQ, ctx->d_Pseg);
                 }
                 const bool tfb = ((ctx->prof_mask >> HF_K_SEG_FB) & 1u) && ctx->prof_now;
                 if (tfb) ctx->kran[HF_K_SEG_FB] = true;
-                const unsigned epoch = ++ctx->seg_epoch;
+                const unsigned epoch = ph_seg ? ++ctx->seg_epoch : ctx->seg_epoch;
                 // HF_SEG_TEST_TIMEOUT=1 (tests/test_estep_gpu.py): the first one-launch pass waits for flags nobody writes, so that
                 // the time-out, HF_E_RETRY and the fall-back to two launches are exercised
                 const unsigned wait_epoch = (ctx->seg_test_timeout && epoch == 1) ? 0xffffffffu : epoch;
@@ -1078,8 +1085,9 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
                     for (size_t si = 0; si < ctx->subs.size(); si++) {
                         const auto& sb = ctx->subs[si];
                         double* const recs_eff = alias ? ctx->d_recs - sb.p0 * 8 : ctx->d_recs;
-                        launch_seg_fb(ctx, st, true, recs_eff, (int) si, epoch, wait_epoch, tfb && first, false);   // (timed: the first sub-pass's launch, hf_sub_pass_windows; no scales)
+                        if (ph_seg) launch_seg_fb(ctx, st, true, recs_eff, (int) si, epoch, wait_epoch, tfb && first, false);   // (timed: the first sub-pass's launch, hf_sub_pass_windows; no scales)
                         first = false;
+                        if (!ph_post) continue;
                         KTimer t(ctx, st, HF_K_PAIR_SUMS);              // (event pairs around k_pair_sums: the last sub-pass's is what is read)
                         launch_pair_sums(ctx, st, sb, recs_eff);
                     }
@@ -1089,7 +1097,7 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
                 } else {
                     double* recs = ctx->d_recs;
                     if (full && ctx->subs.size() > 1) { const int rc_ = all_records_buffer(ctx); if (rc_) return rc_; recs = ctx->d_recs_all; }
-                    launch_seg_fb(ctx, st, full, recs, -1, epoch, wait_epoch, tfb, false);
+                    if (ph_seg) launch_seg_fb(ctx, st, full, recs, -1, epoch, wait_epoch, tfb, false);
                     if (full) { ctx->recs_all = true; ctx->scales_all = false; }
                 }
                 ctx->pass_seg = true;
@@ -1099,6 +1107,7 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
         }
         const int kc = p->ncomp[3];
         const int fl = full && ctx->ntiles > 0;
+        if (!ph_post) { HIPCHK(hipGetLastError()); return HF_OK; }
         ctx->pass_nb = false;
         if (nbm && fl && rows_pass(ctx)) {   // statistics by emission row, negative_binomial (hf_nb_rows.h)
             {   // (k_pair_sums ran behind every sub-pass's k_seg_fb, above)
@@ -1940,3 +1949,5 @@ int hf_last_kernel_ms(hf_ctx* ctx, float* ms) {
 }
 
 } // extern "C"
+
+#include "hf_batch.h"

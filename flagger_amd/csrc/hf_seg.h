@@ -584,14 +584,15 @@ __global__ void __launch_bounds__(64, 4) k_seg_prod(const SegDesc* __restrict__ 
 // ------------------------------------------------------------------------------------------
 // CACHED = false: nc is the constant 0 (a device full of segments: BASELINE configs[2]) — with nc a run-time value the same kernel was 4-5 us
 // slower at that size (scalar branches and block arithmetic in every step of the three walks; profiles/r05_ab_segfb_regression.txt)
-template <bool BWD, bool FUSED, bool CACHED = false>
-__global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb(const SegDesc* __restrict__ sd, const int32_t* __restrict__ arow,
-                                                           const double* __restrict__ lutA, const DevParams* __restrict__ P,
-                                                           const double* __restrict__ Qs, double* Pseg, unsigned* ready, unsigned epoch, unsigned wait_epoch,
-                                                           const int32_t* __restrict__ pos, double* __restrict__ recs, double* __restrict__ scale_s,
-                                                           int8_t* __restrict__ label, double* __restrict__ seg_ll,
-                                                           unsigned* __restrict__ flags, int32_t g0, int nc_arg,
-                                                           const int32_t* __restrict__ seg_of_block) {
+// The body of k_seg_fb and k_seg_fb_batch: `bx` is the launch's block index along the segments.
+template <bool BWD, bool FUSED, bool CACHED>
+__device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, const int32_t* __restrict__ arow,
+                                            const double* __restrict__ lutA, const DevParams* __restrict__ P,
+                                            const double* __restrict__ Qs, double* Pseg, unsigned* ready, unsigned epoch, unsigned wait_epoch,
+                                            const int32_t* __restrict__ pos, double* __restrict__ recs, double* __restrict__ scale_s,
+                                            int8_t* __restrict__ label, double* __restrict__ seg_ll,
+                                            unsigned* __restrict__ flags, int32_t g0, int nc_arg,
+                                            const int32_t* __restrict__ seg_of_block, int bx) {
     static_assert(FUSED || !CACHED, "cached row blocks: one-launch mode only");
     const int nc = CACHED ? nc_arg : 0;
     constexpr int LM = HF_SEG_LMAX;
@@ -609,7 +610,7 @@ __global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb(const SegDesc* __rest
     // p0 records before the buffer, so that the plan's global positions land inside it: hf_estep.hip enqueue_pass)
     // seg_of_block (round 6, hf_create's XCD plan): the launch's block b runs segment seg_of_block[g0 + b] — all segments of a chunk on block
     // indices congruent mod 8, i.e. (observed, for speed only) on one XCD; < 0: a padding block of the plan.  Null: block b runs segment g0 + b.
-    int g = (int) blockIdx.x + g0;
+    int g = bx + g0;
     const int lane = threadIdx.x;
     if (FUSED && BWD) KSTAMP(1);
     if (seg_of_block) { g = seg_of_block[g]; if (g < 0) return; }
@@ -999,4 +1000,42 @@ __global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb(const SegDesc* __rest
     }
 #endif
     if (bad) atomicOr(flags, bad);
+}
+
+template <bool BWD, bool FUSED, bool CACHED = false>
+__global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb(const SegDesc* __restrict__ sd, const int32_t* __restrict__ arow,
+                                                           const double* __restrict__ lutA, const DevParams* __restrict__ P,
+                                                           const double* __restrict__ Qs, double* Pseg, unsigned* ready, unsigned epoch, unsigned wait_epoch,
+                                                           const int32_t* __restrict__ pos, double* __restrict__ recs, double* __restrict__ scale_s,
+                                                           int8_t* __restrict__ label, double* __restrict__ seg_ll,
+                                                           unsigned* __restrict__ flags, int32_t g0, int nc_arg,
+                                                           const int32_t* __restrict__ seg_of_block) {
+    seg_fb_body<BWD, FUSED, CACHED>(sd, arow, lutA, P, Qs, Pseg, ready, epoch, wait_epoch, pos, recs, scale_s, label, seg_ll, flags, g0, nc_arg,
+                                    seg_of_block, (int) blockIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_seg_fb_batch (hf_batch.h): the segments of SEVERAL models of one context in one launch — blockIdx.x is the segment (or the block of
+// the XCD plan) as in k_seg_fb, blockIdx.y the model's place in the launch.  The segment descriptors, the row stream arow and the record
+// positions are the context's, shared by every model; everything a model reads or writes per pass comes from its row of `tab` (device
+// memory, written once by hf_batch_create), its hand-off epochs from the launch's arguments.  A model's blocks run k_seg_fb's body with
+// that model's pointers: the same arithmetic in the same order.  The blocks of a launch are dispatched x fastest, so every segment of a
+// model is dispatched after the segments of its chunk it waits for, as in k_seg_fb.
+// ------------------------------------------------------------------------------------------
+struct SegFbModel {
+    const double* lutA; const DevParams* P; const double* Qs; double* Pseg; unsigned* ready;
+    double* recs; double* scale_s; int8_t* label; double* seg_ll; unsigned* flags;
+};
+#define HF_SEG_BATCH_MAX 64                  // models per launch of k_seg_fb_batch (its arguments: 768 bytes)
+struct SegFbBatch { int32_t model[HF_SEG_BATCH_MAX]; unsigned epoch[HF_SEG_BATCH_MAX]; unsigned wait_epoch[HF_SEG_BATCH_MAX]; };
+
+template <bool BWD, bool FUSED, bool CACHED = false>
+__global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb_batch(const SegDesc* __restrict__ sd, const int32_t* __restrict__ arow,
+                                                                 const SegFbModel* __restrict__ tab, SegFbBatch bt,
+                                                                 const int32_t* __restrict__ pos, int32_t g0, int nc_arg,
+                                                                 const int32_t* __restrict__ seg_of_block) {
+    const int y = (int) blockIdx.y;
+    const SegFbModel& m = tab[bt.model[y]];
+    seg_fb_body<BWD, FUSED, CACHED>(sd, arow, m.lutA, m.P, m.Qs, m.Pseg, m.ready, bt.epoch[y], bt.wait_epoch[y], pos, m.recs, m.scale_s, m.label,
+                                    m.seg_ll, m.flags, g0, nc_arg, seg_of_block, (int) blockIdx.x);
 }

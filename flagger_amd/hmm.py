@@ -590,6 +590,108 @@ def EM_runViterbiForList(emList, model: HMM):
     return emList.viterbi(model)
 
 
+class EMBatch:
+    """Many models over ONE window store (hf_batch_*, flagger_amd/csrc/hf_batch.h): one device context, the windows uploaded and planned
+    once, and the pass state of len(models) models beside it.  Model m of a batch gets the single context's bits for the same
+    parameters.  `store`: a WindowStore (a context is created from it with models[0]'s region and component layout) or an EMList
+    whose context the batch then shares (the EMList itself is not touched by the batch's passes).  The context must be of the
+    default algorithm with one sub-pass, and the models trunc_exp_gaussian or gaussian: else hf_batch_create raises."""
+
+    def __init__(self, store, models: Sequence[HMM], adjustContigEnds: bool = True, minReadFractionAtEnds: float = 0.95,
+                 device: int = 0, algo: int = N.HF_ALGO_SCAN, stream: int = 0):
+        if len(models) < 1:
+            raise ValueError("EMBatch: no models")
+        L = N.lib()
+        self._L = L
+        self._b = None
+        self.models = list(models)
+        if isinstance(store, EMList):
+            self.em = store
+        else:
+            self.em = EMList(store, self.models[0], adjustContigEnds, minReadFractionAtEnds, device=device, algo=algo, stream=stream)
+        self.stream = self.em.stream
+        self.stats_len = self.em.stats_len
+        b = C.c_void_p()
+        N.check(L.hf_batch_create(self.em._h, len(self.models), C.byref(b)), "hf_batch_create")
+        self._b = b
+
+    @property
+    def size(self) -> int:
+        return len(self.models)
+
+    @property
+    def shared_models(self) -> int:
+        """Models of the last pass whose segment kernel ran in the shared launch (k_seg_fb_batch); the others ran their own pass."""
+        return int(self._L.hf_batch_shared_models(self._b))
+
+    def capacity(self) -> int:
+        """hf_batch_capacity of the underlying context: models whose pass state fits the device's free memory."""
+        return int(self._L.hf_batch_capacity(self.em._h))
+
+    def close(self):
+        if getattr(self, "_b", None):
+            self._L.hf_batch_destroy(self._b)
+            self._b = None
+
+    def __del__(self):
+        self.close()
+
+    def _active(self, active) -> np.ndarray:
+        act = np.arange(self.size, dtype=np.int32) if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        if act.ndim != 1:
+            raise ValueError("EMBatch: `active` is a list of model indices")
+        return act
+
+    def launch(self, models: Optional[Sequence[HMM]] = None, active=None, mode: int = N.HF_MODE_FULL) -> np.ndarray:
+        """Enqueue one pass of the models `active` (default: all); models[i] (default: the batch's own) parameterises active[i]."""
+        act = self._active(active)
+        ms = [self.models[int(m)] for m in act] if models is None else list(models)
+        if len(ms) != len(act):
+            raise ValueError("EMBatch: one model per active index")
+        ps = (N.hf_params * max(len(act), 1))()
+        for i, m in enumerate(ms):
+            ps[i] = m.params()
+        self._keep = ms                                  # (the parameter views point into the models until the pass is enqueued)
+        N.check(self._L.hf_batch_estep(self._b, ps, act.ctypes.data_as(C.POINTER(C.c_int32)), len(act), mode, self.stream), "hf_batch_estep")
+        return act
+
+    def finish(self, n_active: int):
+        stats = np.empty((n_active, self.stats_len), dtype=np.float64)
+        status = np.zeros(n_active, dtype=np.int32)
+        N.check(self._L.hf_batch_finish(self._b, _dptr(stats), status.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_batch_finish")
+        return stats, status
+
+    def estep(self, models: Optional[Sequence[HMM]] = None, active=None, mode: int = N.HF_MODE_FULL):
+        """One batched pass: (stats[len(active)][V], status[len(active)]) — status[i] is model active[i]'s HF_E_* (HF_OK, HF_E_SCALE,
+        HF_E_NAN, ...); a failing model does not disturb the others."""
+        act = self.launch(models, active, mode)
+        return self.finish(len(act))
+
+    def labels(self, m: int) -> np.ndarray:
+        out = np.empty(self.em.store.n_windows, dtype=np.int8)
+        N.check(self._L.hf_batch_get_labels(self._b, int(m), out.ctypes.data_as(C.POINTER(C.c_int8))), "hf_batch_get_labels")
+        return out
+
+    def posterior(self, m: int, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        n = self.em.store.n_windows - first if n is None else n
+        out = np.empty((n, 4), dtype=np.float64)
+        N.check(self._L.hf_batch_get_posterior(self._b, int(m), int(first), int(n), _dptr(out)), "hf_batch_get_posterior")
+        return out
+
+
+def EM_runBatchForList(emBatch: EMBatch, models: Optional[Sequence[HMM]] = None, active=None, mode: int = N.HF_MODE_FULL) -> np.ndarray:
+    """EM_runOneIterationForList for the models of a batch: one batched pass; every model whose status is HF_OK gets its statistics
+    and log-likelihood (model.estimators, model.loglikelihood) as EM_runOneIterationForList would set them.  Returns the statuses."""
+    act = emBatch._active(active)
+    ms = [emBatch.models[int(m)] for m in act] if models is None else list(models)
+    stats, status = emBatch.estep(ms, act, mode)
+    for i, m in enumerate(ms):
+        if status[i] == N.HF_OK:
+            m.estimators = stats[i].copy()
+            m.loglikelihood = float(stats[i][0])
+    return status
+
+
 def HMM_estimateParameters(model: HMM, convergenceTol: float) -> bool:
     """hmm.c:120-127; consumes the statistics left by EM_runOneIterationForList."""
     if model.estimators is None:

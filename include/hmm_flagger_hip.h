@@ -244,6 +244,39 @@ int hf_viterbi_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_labels(hf_ctx *ctx, int8_t *labels_host);                          /* [n_windows], layout of hf_labels_dev */
 int hf_get_viterbi_chunk_log_probs(hf_ctx *ctx, double *out_host);                    /* [n_chunks] */
 
+/* Many models on one context (flagger_amd/csrc/hf_batch.h): e.g. one EM per candidate alpha matrix over the same track, with the
+ * windows loaded, uploaded and planned once.  A batch keeps the pass state of n_models models beside the context: every model has its
+ * own parameter block, tables, rows of A, hand-off flags and epochs, pair records, sums, labels, error flags and result block, and shares
+ * the context's windows, segment plan, row stream and statistics plan.  The context's own pass buffers are never written:
+ * hf_estep / hf_get_* / hf_viterbi on `ctx` behave as without a batch, before, between and after batched passes.
+ * Model m of a batch runs the kernels, the arithmetic and the order of hf_estep on `ctx` with the same hf_params, in the context's
+ * statistics mode and launch mode: its statistics, log-likelihood and labels are the single path's bits.
+ * The batch engine covers HF_ALGO_SCAN contexts of one sub-pass (hf_sub_passes == 1) and the trunc_exp_gaussian and gaussian models;
+ * otherwise hf_batch_capacity returns 0 and hf_batch_create HF_E_ARG (hf_last_error says why).  hf_create takes no model type, so a
+ * context is known to serve negative_binomial only once it has run such a pass: from then on capacity is 0 and hf_batch_create
+ * refuses it; before that, hf_batch_estep refuses negative_binomial parameters (HF_E_ARG).  The context must outlive the batch.
+ * Full passes of the default pass (one-launch segment kernel, statistics by emission row) run the segment kernel of all their
+ * models in ONE launch (k_seg_fb_batch: blockIdx.y = model); the tables and the statistics run per model.
+ *   hf_batch_capacity   models whose pass state fits nine tenths of the device's free memory and whose pinned host blocks fit an
+ *                       eighth of the host's physical memory (at most HF_BATCH_MAX_MODELS)
+ *   hf_batch_estep      one pass of each of the n_active models models[0..n_active-1] (distinct indices < n_models) with p[i] for
+ *                       model models[i], enqueued on `stream` in that order; the other models keep the results of their last pass
+ *   hf_batch_finish     waits for the models of the last hf_batch_estep: stats_host[i][hf_chunk_stats_len] and status[i] (HF_OK,
+ *                       HF_E_SCALE, HF_E_NAN, ...) for models[i].  A model's own failure is its status only; the call returns HF_OK
+ *                       unless the runtime or an argument failed.  A timed-out hand-off (HF_E_RETRY) re-runs that model's pass inside.
+ *   hf_batch_get_labels / hf_batch_get_posterior: as hf_get_labels / hf_get_posterior, for the last finished pass of `model` */
+#define HF_BATCH_MAX_MODELS 1024
+typedef struct hf_batch hf_batch;
+int hf_batch_capacity(const hf_ctx *ctx);
+int hf_batch_create(hf_ctx *ctx, int n_models, hf_batch **out);
+void hf_batch_destroy(hf_batch *b);
+int hf_batch_size(const hf_batch *b);
+int hf_batch_shared_models(const hf_batch *b);   /* models of the last hf_batch_estep whose segment kernel ran in the shared launch */
+int hf_batch_estep(hf_batch *b, const hf_params *p, const int32_t *models, int n_active, int mode, void *stream);
+int hf_batch_finish(hf_batch *b, double *stats_host, int32_t *status, void *stream);
+int hf_batch_get_labels(hf_batch *b, int model, int8_t *labels_host);
+int hf_batch_get_posterior(hf_batch *b, int model, int64_t first, int64_t n, double *post_host);
+
 /* kernel time of the last hf_estep + reduce in milliseconds (HIP events on the stream used); recorded only while
  * hf_set_profiling's mask carries HF_PROF_PASS (two extra stream packets per pass) */
 int hf_last_kernel_ms(hf_ctx *ctx, float *ms);

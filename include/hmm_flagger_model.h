@@ -82,6 +82,13 @@ void hfm_set_loglikelihood(hfm_model *m, double ll);
 int hf_em_iterate(hf_ctx *ctx, hfm_model *model, int mode, int do_mstep, double tol, double *stats_host, int *converged,
                   void *stream);
 
+/* hf_em_iterate for the models of a batch (hf_batch_create): one batched E-step of models[i] = the batch's model active[i] with the
+ * parameters of model_objs[i], then per model its log-likelihood, and (do_mstep, full passes, status HF_OK) hfm_estimate with its
+ * convergence test.  stats_host: [n_active][hf_chunk_stats_len]; status[i]: HF_E_* of model active[i]; converged[i] (may be NULL).
+ * A model whose status is not HF_OK is not estimated.  Returns HF_OK unless the runtime or an argument failed. */
+int hf_em_iterate_batch(hf_batch *b, hfm_model **model_objs, const int32_t *active, int n_active, int mode, int do_mstep, double tol,
+                        double *stats_host, int32_t *status, int *converged, void *stream);
+
 /* hf_warmup(device) and then one miniature synthetic EM per kernel family of the default pass (a few milliseconds): the first real pass
  * then finds every kernel launched once.  Optional; for the thread that brings the runtime up while the input is read. */
 int hfm_warmup_pipeline(int device);
