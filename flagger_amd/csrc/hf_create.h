@@ -7,13 +7,13 @@
 // function — included by hf_estep.hip behind the context, the kernels and the upload helpers:
 //   create_pack_windows      first pass over the windows: packed upload words, packed records, the contig-end ("slow") windows,
 //                            which emission keys and (key, transition class) rows occur; the window arrays go up
-//   create_device_store      the context's device arrays and pinned result block, k_setup / k_regmask enqueued
-//   create_key_tables        slow-window list, emission keys, the per-pass row tables, tiles of the per-chunk statistics
+//   create_device_store      the track's device arrays, k_setup / k_regmask enqueued
+//   create_key_tables        slow-window list, emission keys, tiles of the per-chunk statistics
 //   create_rows_and_segments rows of A (second pass), sub-passes, segment descriptors
 //   create_statistics_plan   groups, row slots, the position of every window's record (third pass), the plan's uploads
 //   create_launch_config     one-launch guard, cached row blocks, XCD plan, the job list of the per-pass tables, environment switches
-// Everything a step allocates on the device comes out of the context's slab and is released by hf_destroy: a step that fails just
-// returns its code and hf_create destroys the context.
+// The steps build the TRACK: everything they allocate on the device comes out of its slab and is released by hf_destroy — a step that fails
+// just returns its code and hf_create destroys the context.  The context's pass state comes last (pass_create, hf_estep.hip).
 #pragma once
 
 namespace {
@@ -54,7 +54,7 @@ std::atomic<uint64_t> g_create_gen{0};
 
 struct CreateWork {
     hf_ctx* ctx = nullptr; const hf_windows* w = nullptr;
-    int n_regions = 1, max_comps = 1, device = 0, algo = HF_ALGO_SCAN;
+    int n_regions = 1, device = 0, algo = HF_ALGO_SCAN;
     size_t N = 0, C = 0; int32_t maxT = 0;
     // phases (hf_create_phases; HF_HOST_TRACE prints them)
     bool ctrace = false;
@@ -62,7 +62,7 @@ struct CreateWork {
     void phase(const char* name) {
         const auto now = std::chrono::steady_clock::now();
         const double ms = std::chrono::duration<double, std::milli>(now - t_last).count();
-        ctx->create_phases.emplace_back(name, ms);
+        ctx->tr.create_phases.emplace_back(name, ms);
         if (ctrace) std::fprintf(stderr, "[hf_create] %-34s %7.2f ms\n", name, ms);
         t_last = now;
     }
@@ -88,7 +88,7 @@ struct CreateWork {
     bool key_class(size_t k256, size_t cl) const { return (keymark[k256] >> cl) & 1u; }
 };
 #define CTRY(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
-#define CALLOC(p, bytes) do { (p) = static_cast<decltype(p)>(ctx_alloc(ctx, (bytes))); \
+#define CALLOC(p, bytes) do { (p) = static_cast<decltype(p)>(tr.slab.alloc((bytes))); \
     if (!(p)) return set_err(HF_E_HIP, "hf_create: out of device memory"); } while (0)
 
 // ------------------------------------------------------------------------------------------
@@ -97,12 +97,12 @@ struct CreateWork {
 // fits a byte — window values are at most 250, chunk.c:393-441 — the four arrays as they are otherwise)
 // ------------------------------------------------------------------------------------------
 int create_pack_windows(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const size_t N = cw.N, C = cw.C;
     const int n_regions = cw.n_regions, device = cw.device;
     cw.arena.c = pin_cache().acquire((size_t) 8 << 20);
     cw.stg.p = cw.arena.c; cw.stg.cap = cw.arena.c ? (size_t) 8 << 20 : 0;
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_off, w->chunk_off, C + 1));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_off, w->chunk_off, C + 1));
     cw.phase("context, chunk offsets up");
     if (N > 0) {
         cw.arena.a = pin_cache().acquire(N * 4);
@@ -171,7 +171,7 @@ int create_pack_windows(CreateWork& cw) {
                     double bt;
                     const uint32_t r = window_record(cv, mq, cp, region, pre_region, (int64_t) (t - t0), cs_, ce_, cl_, w->window_len,
                                                      w->mean_read_len, w->adjust_contig_ends, w->min_read_frac, w->max_high_mapq_ratio,
-                                                     w->min_high_mapq_ratio, w->min_highly_clipped_ratio, ctx->beta_star, &bt);
+                                                     w->min_high_mapq_ratio, w->min_highly_clipped_ratio, tr.beta_star, &bt);
                     hrecp[t] = r;
                     if (region >= nreg) badr = true;
                     else if (REC_SLOW(r)) mine.push_back((int64_t) t);
@@ -201,7 +201,7 @@ int create_pack_windows(CreateWork& cw) {
             unsigned cur = maxx_all.load(std::memory_order_relaxed);
             while (mx > cur && !maxx_all.compare_exchange_weak(cur, mx, std::memory_order_relaxed)) {}
         });
-        ctx->M = (int) maxx_all.load() + 1;
+        tr.M = (int) maxx_all.load() + 1;
     }
     {   // the threads' marks, OR-ed (a thread's table stays its own until its next hf_create: nothing else runs on the pool meanwhile)
         cw.keymark.assign(marks.words, 0);
@@ -213,80 +213,47 @@ int create_pack_windows(CreateWork& cw) {
     if (N > 0) {
         if (w->chunk_off[0] != 0 || (size_t) w->chunk_off[C] != N) wide.store(1);   // (a window outside every chunk: take the plain path)
         if (!wide.load()) {
-            cw.d_packed = static_cast<uint32_t*>(ctx_alloc(ctx, N * 4));
+            cw.d_packed = static_cast<uint32_t*>(tr.slab.alloc(N * 4));
             hipError_t e1 = cw.d_packed ? hipSuccess : hipErrorOutOfMemory;
             if (e1 == hipSuccess) e1 = hipMemcpyAsync(cw.d_packed, cw.P0, N * 4, hipMemcpyHostToDevice, nullptr);   // (k_setup follows on the same stream; P0 is not written again)
             if (e1 != hipSuccess) { (void) hipGetLastError(); cw.d_packed = nullptr; }
         }
     }
     if (!cw.d_packed) {
-        CTRY(dev_upload(ctx, cw.stg, &cw.d_cov, w->cov, N)); CTRY(dev_upload(ctx, cw.stg, &cw.d_mapq, w->mapq, N)); CTRY(dev_upload(ctx, cw.stg, &cw.d_clip, w->clip, N));
-        CTRY(dev_upload(ctx, cw.stg, &cw.d_annot, w->annot, N));
+        CTRY(dev_upload(tr.slab, cw.stg, &cw.d_cov, w->cov, N)); CTRY(dev_upload(tr.slab, cw.stg, &cw.d_mapq, w->mapq, N)); CTRY(dev_upload(tr.slab, cw.stg, &cw.d_clip, w->clip, N));
+        CTRY(dev_upload(tr.slab, cw.stg, &cw.d_annot, w->annot, N));
     }
-    CTRY(dev_upload(ctx, cw.stg, &cw.d_cs, w->chunk_s, C)); CTRY(dev_upload(ctx, cw.stg, &cw.d_ce, w->chunk_e, C)); CTRY(dev_upload(ctx, cw.stg, &cw.d_cl, w->chunk_ctg_len, C));
+    CTRY(dev_upload(tr.slab, cw.stg, &cw.d_cs, w->chunk_s, C)); CTRY(dev_upload(tr.slab, cw.stg, &cw.d_ce, w->chunk_e, C)); CTRY(dev_upload(tr.slab, cw.stg, &cw.d_cl, w->chunk_ctg_len, C));
     cw.phase("window arrays up");
     return HF_OK;
 }
 
 // ------------------------------------------------------------------------------------------
-// 2. the context's device arrays, its pinned result block, and the set-up kernels (no wait: the host computed every record itself)
+// 2. the track's device arrays and the set-up kernels (no wait: the host computed every record itself)
 // ------------------------------------------------------------------------------------------
 int create_device_store(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const size_t N = cw.N, C = cw.C;
     const int n_regions = cw.n_regions;
-    CALLOC(ctx->d_rec, N * 4); CALLOC(ctx->d_beta, N * 8); CALLOC(ctx->d_regmask, C * 8);
-    if (cw.algo == HF_ALGO_SEQ) CALLOC(ctx->d_E, N * 16 * 8);
-    if (cw.algo == HF_ALGO_SEQ) CALLOC(ctx->d_scale, N * 8);   // window-order scales: the sequential cross-check only (hf_seg.h keeps them by slot)
-    CALLOC(ctx->d_label, N + 16);
-    CALLOC(ctx->d_chunk_stats, C * (size_t) ctx->V * 8); CALLOC(ctx->d_total, ((size_t) ctx->V + 1) * 8);
-    CALLOC(ctx->d_flags, 4);
-    CALLOC(ctx->d_done, HF_DONE_BYTES);         // tickets and scratch of the in-launch hand-offs (hf_rows.h)
-    hipMemsetAsync(ctx->d_done, 0, HF_DONE_BYTES, nullptr);
-    CALLOC(ctx->d_cks, 8);
-    hipMemsetAsync(ctx->d_cks, 0, 8, nullptr);
-    ctx->params_bytes = sizeof(DevParams) + (size_t) (n_regions - 1) * sizeof(DevRegion);
-    CALLOC(ctx->d_params, ctx->params_bytes);
-    hipMemsetAsync(ctx->d_params, 0, ctx->params_bytes, nullptr);   // (the kernel-argument path writes the bytes in use only)
-    {   // one pinned block: the result vector (+ flag word, stamp, checksums) | the flag word of hf_check | the parameter block
-        const size_t tot_bytes = (((size_t) ctx->V + 2 + HF_MAXREGIONS) * 8 + 63) / 64 * 64;   // (what follows stays 64-byte aligned)
-        const size_t par_bytes = (ctx->params_bytes + 63) / 64 * 64;
-        // (from the process-wide cache: pinning even this small block was 0.1-0.2 ms of hf_create; zeroed — a stale stamp word must not look like a future one)
-        char* pin = pin_cache().acquire(tot_bytes + 64 + par_bytes);
-        if (!pin) return set_err(HF_E_HIP, "hf_create: out of host memory");
-        std::memset(pin, 0, tot_bytes + 64 + par_bytes);
-        ctx->h_total = reinterpret_cast<double*>(pin);
-        ctx->h_flags = reinterpret_cast<unsigned*>(pin + tot_bytes);
-        ctx->h_params = reinterpret_cast<DevParams*>(pin + tot_bytes + 64);
-    }
-    {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, ctx->h_total, 0) == hipSuccess) ctx->d_total_host = (double*) dp;
-        else {
-            // (the cache falls back to pageable memory when pinning fails — a block the device cannot address: no zero-copy totals,
-            // no stream stamp into it; passes then complete through a copy and hipStreamSynchronize)
-            (void) hipGetLastError();
-            ctx->d_total_host = nullptr; ctx->stream_stamp_ok = false;
-        }
-    }
+    CALLOC(tr.d_rec, N * 4); CALLOC(tr.d_beta, N * 8); CALLOC(tr.d_regmask, C * 8);
+    CALLOC(tr.d_setup_flags, 4);
+    tr.params_bytes = sizeof(DevParams) + (size_t) (n_regions - 1) * sizeof(DevRegion);
     cw.phase("device + pinned allocations");
-    hipEventCreate(&ctx->ev0); hipEventCreate(&ctx->ev1);
-    hipMemsetAsync(ctx->d_flags, 0, 4, nullptr);
-    hipMemsetAsync(ctx->d_label, 0xff, N ? N : 1, nullptr);
+    hipMemsetAsync(tr.d_setup_flags, 0, 4, nullptr);
     if (N > 0 && C > 0) {
         dim3 grid((unsigned) ((cw.maxT + 255) / 256), (unsigned) C);
-        hipLaunchKernelGGL(k_setup, grid, dim3(256), 0, 0, ctx->d_off, cw.d_packed, cw.d_cov, cw.d_mapq, cw.d_clip, cw.d_annot, cw.d_cs, cw.d_ce, cw.d_cl,
+        hipLaunchKernelGGL(k_setup, grid, dim3(256), 0, 0, tr.d_off, cw.d_packed, cw.d_cov, cw.d_mapq, cw.d_clip, cw.d_annot, cw.d_cs, cw.d_ce, cw.d_cl,
                            w->window_len, w->mean_read_len, w->adjust_contig_ends, w->min_read_frac,
                            w->max_high_mapq_ratio, w->min_high_mapq_ratio, w->min_highly_clipped_ratio, n_regions,
-                           ctx->beta_star, ctx->d_rec, ctx->d_beta, ctx->d_flags);
-        hipLaunchKernelGGL(k_regmask, dim3((unsigned) C), dim3(256), 0, 0, ctx->d_off, ctx->d_rec, ctx->d_regmask);
+                           tr.beta_star, tr.d_rec, tr.d_beta, tr.d_setup_flags);
+        hipLaunchKernelGGL(k_regmask, dim3((unsigned) C), dim3(256), 0, 0, tr.d_off, tr.d_rec, tr.d_regmask);
     }
     cw.phase("events, memsets, k_setup enqueued");
-    // (no wait for k_setup: a region index out of range has been refused already; the device's own flag word is read behind the ONE
-    // synchronisation at the end of hf_create)
+    // (no wait for k_setup: a region index out of range has been refused already; its flag word — the track's, so that the set-up needs no
+    // pass state — is read behind the ONE synchronisation at the end of hf_create)
     if (N && std::getenv("HF_CREATE_VERIFY")) {   // the test suite: the device's records against the host's, bit for bit
         std::vector<uint32_t> dev(N);
-        bool same = hipMemcpy(dev.data(), ctx->d_rec, N * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        bool same = hipMemcpy(dev.data(), tr.d_rec, N * 4, hipMemcpyDeviceToHost) == hipSuccess;
         for (size_t c = 0; c < C && same; c++) {
             const size_t t0 = (size_t) w->chunk_off[c], n = (size_t) (w->chunk_off[c + 1] - w->chunk_off[c]);
             same = std::memcmp(dev.data() + t0, cw.hrec + t0, n * 4) == 0;
@@ -299,34 +266,30 @@ int create_device_store(CreateWork& cw) {
 
 // ------------------------------------------------------------------------------------------
 // 3. slow windows (chunk-first, or beta differs from beta_star) and the emission keys — bits of the packed records and the key marks of the
-// first pass, nothing comes back from the device —, the per-pass row tables, the tiles of the per-chunk statistics
+// first pass, nothing comes back from the device —, the tiles of the per-chunk statistics
 // ------------------------------------------------------------------------------------------
 int create_key_tables(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const size_t C = cw.C;
-    const int n_regions = cw.n_regions, max_comps = cw.max_comps;
-    if (cw.N == 0) ctx->M = 1;
-    const size_t MM = (size_t) ctx->M * ctx->M;
+    const int n_regions = cw.n_regions;
+    if (cw.N == 0) tr.M = 1;
+    const size_t MM = (size_t) tr.M * tr.M;
     cw.soff.assign(C + 1, 0);
     for (size_t c = 0; c < C; c++) cw.soff[c + 1] = cw.soff[c] + cw.nslow[c];
     cw.slow.reserve((size_t) cw.soff[C]);
     for (auto& v : cw.part_slow) cw.slow.insert(cw.slow.end(), v.begin(), v.end());   // parts are consecutive chunk ranges: ascending
     for (size_t reg = 0; reg < (size_t) n_regions; reg++)                              // keys in (region, x, x_prev) order
-        for (size_t x = 0; x < (size_t) ctx->M; x++)
-            for (size_t xp = 0; xp < (size_t) ctx->M; xp++)
-                if (cw.key_seen((reg << 16) | (x << 8) | xp)) cw.keys.push_back((int32_t) ((reg * ctx->M + x) * ctx->M + xp));
-    ctx->n_slow = (int) cw.slow.size();
-    ctx->n_keys = (int) cw.keys.size();
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_slow_w, cw.slow.data(), cw.slow.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_slow_off, cw.soff.data(), cw.soff.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_keys, cw.keys.data(), cw.keys.size()));
-    // one buffer per table: rows of the (region, x, x_prev) keys first, then the private rows of the slow windows
+        for (size_t x = 0; x < (size_t) tr.M; x++)
+            for (size_t xp = 0; xp < (size_t) tr.M; xp++)
+                if (cw.key_seen((reg << 16) | (x << 8) | xp)) cw.keys.push_back((int32_t) ((reg * tr.M + x) * tr.M + xp));
+    tr.n_slow = (int) cw.slow.size();
+    tr.n_keys = (int) cw.keys.size();
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_slow_w, cw.slow.data(), cw.slow.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_slow_off, cw.soff.data(), cw.soff.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_keys, cw.keys.data(), cw.keys.size()));
+    // a pass's row tables (pass_layout): rows of the (region, x, x_prev) keys first, then the private rows of the slow windows
     // (a row index fits 32 bits; + 1 row of padding)
-    ctx->n_lut = (int64_t) n_regions * (int64_t) MM;
-    CALLOC(ctx->d_lutE, ((size_t) ctx->n_lut + cw.slow.size() + 1) * 16 * 8);
-    CALLOC(ctx->d_lutC, ((size_t) ctx->n_lut + cw.slow.size() + 1) * 4 * (size_t) max_comps * 8);
-    ctx->d_Es = ctx->d_lutE + (size_t) ctx->n_lut * 16;
-    ctx->d_Cs = ctx->d_lutC + (size_t) ctx->n_lut * 4 * (size_t) max_comps;
+    tr.n_lut = (int64_t) n_regions * (int64_t) MM;
     cw.phase("contig-end list, keys, row tables");
     // tiles of 64*HF_SCAN_L windows, enumerated chunk by chunk
     std::vector<int32_t> ctile0(C + 1, 0);
@@ -344,17 +307,11 @@ int create_key_tables(CreateWork& cw) {
         }
     }
     ctile0[C] = (int32_t) desc.size();
-    ctx->ntiles = (int) desc.size();
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_tile_desc, desc.data(), desc.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_chunk_tile0, ctile0.data(), ctile0.size()));
-    const size_t nt = (size_t) ctx->ntiles;
-    CALLOC(ctx->d_tile_ll, nt * 8);
-    if (cw.algo == HF_ALGO_SEQ) {   // f, b tile-major / lane-minor (hf_device.h fb_slot): only the sequential cross-check keeps them
-        CALLOC(ctx->d_f, nt * 64 * HF_SCAN_L * 4 * 8); CALLOC(ctx->d_b, nt * 64 * HF_SCAN_L * 4 * 8);
-    }
-    ctx->h_off.assign(w->chunk_off, w->chunk_off + C + 1);
-    ctx->h_tile0 = ctile0;
-    CALLOC(ctx->d_tile_stats, nt * (size_t) n_regions * (16 + 9 + 2 + 3 * 16 + 1) * 8);
+    tr.ntiles = (int) desc.size();
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_tile_desc, desc.data(), desc.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_chunk_tile0, ctile0.data(), ctile0.size()));
+    tr.h_off.assign(w->chunk_off, w->chunk_off + C + 1);
+    tr.h_tile0 = ctile0;
     cw.phase("tiles + work arrays");
     return HF_OK;
 }
@@ -364,7 +321,7 @@ int create_key_tables(CreateWork& cw) {
 // windows) with the pairs per (sub-pass, row of A); the sub-passes; the segments of the workgroup-per-segment forward-backward (hf_seg.h)
 // ------------------------------------------------------------------------------------------
 int create_rows_and_segments(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const size_t N = cw.N, C = cw.C;
     const int n_regions = cw.n_regions;
     cw.pcnt.assign(HF_PARTS, {});
@@ -382,25 +339,25 @@ int create_rows_and_segments(CreateWork& cw) {
     {
         constexpr int NC = HF_AROW_CLASSES;
         auto cls_of = [](uint32_t r) { return REC_REGCHG(r) ? 8 : (int) REC_VMASK(r); };
-        std::vector<int32_t> combo_id((size_t) ctx->n_lut * NC, 0);
+        std::vector<int32_t> combo_id((size_t) tr.n_lut * NC, 0);
         int32_t* cid = combo_id.data();
         // (region and coverage from the packed upload words of the first pass when there are any — 4 bytes per window instead of the
         // 10 of annot + cov: these passes run at the speed of the host's memory)
         const uint32_t* const pk = cw.d_packed ? cw.P0 : nullptr;
         auto key_of = [&](size_t t) {
-            if (pk) return ((size_t) (pk[t] >> 24) * ctx->M + (pk[t] & 0xffu)) * ctx->M + (pk[t - 1] & 0xffu);
+            if (pk) return ((size_t) (pk[t] >> 24) * tr.M + (pk[t] & 0xffu)) * tr.M + (pk[t - 1] & 0xffu);
             const size_t reg = (size_t) ((w->annot[t] & 0xFC00000000000000ULL) >> 58);
-            return (reg * ctx->M + (w->cov[t] & 0xffu)) * ctx->M + (w->cov[t - 1] & 0xffu);
+            return (reg * tr.M + (w->cov[t] & 0xffu)) * tr.M + (w->cov[t - 1] & 0xffu);
         };
         std::vector<int32_t>& a_src = cw.h_arow_src;
         std::vector<int32_t> a_cls;
         // the (key, class) pairs the first pass marked, numbered in (region, x, x_prev, class) order
         for (size_t reg = 0; reg < (size_t) n_regions; reg++)
-            for (size_t x = 0; x < (size_t) ctx->M; x++)
-                for (size_t xp = 0; xp < (size_t) ctx->M; xp++) {
+            for (size_t x = 0; x < (size_t) tr.M; x++)
+                for (size_t xp = 0; xp < (size_t) tr.M; xp++) {
                     const size_t k256 = (reg << 16) | (x << 8) | xp;
                     if (!cw.key_seen(k256)) continue;
-                    const size_t key = (reg * ctx->M + x) * ctx->M + xp;
+                    const size_t key = (reg * tr.M + x) * tr.M + xp;
                     for (size_t cl = 0; cl < (size_t) NC; cl++)
                         if (cw.key_class(k256, cl)) {
                             cid[key * NC + cl] = (int32_t) a_src.size() + 1;            // id + 1
@@ -413,7 +370,7 @@ int create_rows_and_segments(CreateWork& cw) {
         const size_t n_ar_all = a_src.size();
         int32_t* const arow = cw.h_arow;
         cw.phase("(key, class) list");
-        {   // sub-passes (hf_ctx::SubPass): whole chunks, about equal window counts, <= ~1.6 M windows (~140 MB of records) each
+        {   // sub-passes (Track::SubPass): whole chunks, about equal window counts, <= ~1.6 M windows (~140 MB of records) each
             int S = 1;
             if ((int64_t) N > 2800000) S = (int) (((int64_t) N + 1599999) / 1600000);   // (one launch wins up to ~2.8 M windows, sub-passes of ~1.5 M beyond: profiles/r05_subpass_count2.txt)
             if (const char* e = std::getenv("HF_SUBPASSES")) { const int v = std::atoi(e); if (v >= 1 && v <= 256) S = v; }   // tests, A/B runs
@@ -445,7 +402,7 @@ int create_rows_and_segments(CreateWork& cw) {
                     int32_t id;
                     if (REC_SLOW(r)) {
                         id = n_combo + sp;
-                        a_src[(size_t) id] = (int32_t) (ctx->n_lut + sp);
+                        a_src[(size_t) id] = (int32_t) (tr.n_lut + sp);
                         a_cls[(size_t) id] = (x == 0 ? 9 : cls_of(r)) | (int32_t) (REC_REGION(r) << 8);
                         arow[t] = id | (x == 0 ? (int32_t) 0x80000000 : 0);
                         sp++;
@@ -455,31 +412,18 @@ int create_rows_and_segments(CreateWork& cw) {
             }
         }, cw.plan_ppt);
         cw.phase("rows of A (second pass)");
-        ctx->n_combo = n_combo; ctx->n_arows = (int) a_src.size();
+        tr.n_combo = n_combo; tr.n_arows = (int) a_src.size();
         if (a_src.size() >= ((size_t) 1 << 25))     // the segment kernels address a row by a 32-bit BYTE offset (index << 7)
             return set_err(HF_E_ARG, "hf_create: more than 2^25 distinct rows of A (contig-end windows included): shard the chunk list (hmm_flagger_multi.h)");
-        CALLOC(ctx->d_arow, N * 4);
-        if (hipMemcpyAsync(ctx->d_arow, arow, N * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess) return set_err(HF_E_HIP, "hf_create: rows of A up");   // (P1: pinned, not written again)
-        CTRY(dev_upload(ctx, cw.stg, &ctx->d_arow_src, a_src.data(), a_src.size()));
-        CTRY(dev_upload(ctx, cw.stg, &ctx->d_arow_cls, a_cls.data(), a_cls.size()));
-        CALLOC(ctx->d_lutA, (a_src.size() + 1) * 16 * 8);
-        {   // one row behind the rows of A: the IDENTITY (hf_seg.h: what a lane multiplies by past its last window); no kernel writes it
-            double ident[16];
-            for (int k = 0; k < 16; k++) ident[k] = (k % 5 == 0) ? 1.0 : 0.0;
-            // (through the staging buffer: a synchronous copy here waited for the 6 MB of rows of A enqueued just above — 0.25 ms)
-            hipError_t ei;
-            if (cw.stg.p && cw.stg.used + 128 <= cw.stg.cap) {
-                std::memcpy(cw.stg.p + cw.stg.used, ident, sizeof ident);
-                ei = hipMemcpyAsync(ctx->d_lutA + a_src.size() * 16, cw.stg.p + cw.stg.used, sizeof ident, hipMemcpyHostToDevice, nullptr);
-                cw.stg.used += 128;
-            } else ei = hipMemcpy(ctx->d_lutA + a_src.size() * 16, ident, sizeof ident, hipMemcpyHostToDevice);
-            if (ei != hipSuccess) return set_err(HF_E_HIP, "hf_create: the identity row");
-        }
+        CALLOC(tr.d_arow, N * 4);
+        if (hipMemcpyAsync(tr.d_arow, arow, N * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess) return set_err(HF_E_HIP, "hf_create: rows of A up");   // (P1: pinned, not written again)
+        CTRY(dev_upload(tr.slab, cw.stg, &tr.d_arow_src, a_src.data(), a_src.size()));
+        CTRY(dev_upload(tr.slab, cw.stg, &tr.d_arow_cls, a_cls.data(), a_cls.size()));
         if (cw.ctrace) std::fprintf(stderr, "[hf_create] %d emission keys, %d (key, transition class) rows, %d slow windows\n",
-                                    ctx->n_keys, n_combo, ctx->n_slow);
+                                    tr.n_keys, n_combo, tr.n_slow);
     }
     // a chunk of T windows is cut into ceil(T / SMAX) equal segments; window w of a segment (w = j*L + i) lives in slot slot0 + i*64 + j
-    std::vector<SegDesc>& segs = ctx->h_segs;
+    std::vector<SegDesc>& segs = tr.h_segs;
     std::vector<int32_t>& cseg0 = cw.cseg0;
     cseg0.assign(C + 1, 0);
     int64_t nslots = 0;
@@ -495,8 +439,8 @@ int create_rows_and_segments(CreateWork& cw) {
             const int64_t w0 = k * sz, n = T - w0 < sz ? T - w0 : sz;
             d.t0 = t0 + w0; d.n = (int) n; d.L = (int) ((n + NL - 1) / NL);
             d.slot0 = (int32_t) nslots; nslots += (int64_t) d.L * NL;
-            d.chunk_slow0 = ctx->n_combo + cw.soff[c];               // the A row of the chunk's first window
-            d.seg0 = first; d.k = (int) k; d.chunk = (int) c; d.ident_row = ctx->n_arows;
+            d.chunk_slow0 = tr.n_combo + cw.soff[c];               // the A row of the chunk's first window
+            d.seg0 = first; d.k = (int) k; d.chunk = (int) c; d.ident_row = tr.n_arows;
             d.reg_first = (int32_t) ((w->annot[t0] & 0xFC00000000000000ULL) >> 58);
             d.reg_last = (int32_t) ((w->annot[t0 + T - 1] & 0xFC00000000000000ULL) >> 58);
             segs.push_back(d);
@@ -509,14 +453,10 @@ int create_rows_and_segments(CreateWork& cw) {
         }
     }
     cseg0[C] = (int32_t) segs.size();
-    ctx->h_cseg0 = cseg0;
+    tr.h_cseg0 = cseg0;
     if (nslots < INT32_MAX) {
-        ctx->nseg = (int) segs.size(); ctx->n_slots = nslots;
-        CTRY(dev_upload(ctx, cw.stg, &ctx->d_chunk_seg0, cseg0.data(), cseg0.size()));   // (the descriptors go up with the plan's positions in them)
-        CALLOC(ctx->d_seg_ready, segs.size() * 4);
-        hipMemsetAsync(ctx->d_seg_ready, 0, segs.size() * 4, nullptr);
-        CALLOC(ctx->d_seg_ll, segs.size() * 8);
-        CALLOC(ctx->d_Pseg, segs.size() * 16 * 8);
+        tr.nseg = (int) segs.size(); tr.n_slots = nslots;
+        CTRY(dev_upload(tr.slab, cw.stg, &tr.d_chunk_seg0, cseg0.data(), cseg0.size()));   // (the descriptors go up with the plan's positions in them)
     } else segs.clear();
     cw.phase("segments");
     return HF_OK;
@@ -543,16 +483,16 @@ struct StatsPlan {            // what the plan's two halves hand to each other
 // extras and spare records of sub-pass sp from position `from` on: windows 0, 1 of its chunks (with a plan) and the chunk's spare record,
 // then one spare record per segment
 int64_t plan_place_extras(CreateWork& cw, StatsPlan& pl, size_t sp, int64_t from, bool with_first_two) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     int64_t p = from;
-    const auto& sb = ctx->subs[sp];
+    const auto& sb = tr.subs[sp];
     for (int c = sb.c0; c < sb.c1; c++) {
         const int64_t T = w->chunk_off[c + 1] - w->chunk_off[c];
         pl.extra0[(size_t) c] = p;
         p += T <= 0 ? 0 : (with_first_two ? (T < 2 ? T : 2) : 0) + 1;
         pl.extra0[(size_t) c + 1] = p;      // (read as "end of chunk c" below: the chunks of a sub-pass are consecutive)
     }
-    for (int k = sb.seg0; k < sb.seg1; k++) ctx->h_segs[(size_t) k].trash_pos = (int32_t) p++;
+    for (int k = sb.seg0; k < sb.seg1; k++) tr.h_segs[(size_t) k].trash_pos = (int32_t) p++;
     return p;
 }
 
@@ -562,24 +502,24 @@ int64_t plan_place_extras(CreateWork& cw, StatsPlan& pl, size_t sp, int64_t from
 // EMISSION row (its transition classes are adjacent) fills slots of up to HF_ROWSLOT_GROUPS consecutive groups — then the arrays are sized
 // once and filled by plain stores.
 void plan_groups_and_slots(CreateWork& cw, StatsPlan& pl, int bpw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const int n_regions = cw.n_regions;
     const size_t n_ar = cw.h_arow_src.size(), S = (size_t) cw.n_sub;
     const bool compact = pl.compact;
-    std::vector<hf_ctx::SubPass>& subs = ctx->subs;
+    std::vector<Track::SubPass>& subs = tr.subs;
     // rows of A that occur, ordered by (region, row of A): combos are numbered by (emission key, class), keys are region-major; the
     // contig-end windows' rows follow in window order
     struct Occ { int32_t region, ar; };
     std::vector<Occ> occ;
-    const size_t MMr = (size_t) ctx->M * ctx->M;
+    const size_t MMr = (size_t) tr.M * tr.M;
     for (size_t r = 0; r < n_ar; r++) {
         bool any = false;
         for (size_t sp = 0; sp < S && !any; sp++) any = pl.cnt[sp * n_ar + r] != 0;
         if (!any) continue;
         const int64_t er = cw.h_arow_src[r];            // emission row: a key, or n_lut + slow index
         int32_t reg;
-        if (er < ctx->n_lut) reg = (int32_t) ((size_t) er / MMr);
-        else reg = (int32_t) ((w->annot[(size_t) cw.slow[(size_t) (er - ctx->n_lut)]] & 0xFC00000000000000ULL) >> 58);
+        if (er < tr.n_lut) reg = (int32_t) ((size_t) er / MMr);
+        else reg = (int32_t) ((w->annot[(size_t) cw.slow[(size_t) (er - tr.n_lut)]] & 0xFC00000000000000ULL) >> 58);
         occ.push_back({reg, (int32_t) r});
     }
     if (n_regions > 1) std::stable_sort(occ.begin(), occ.end(), [](const Occ& a, const Occ& b) { return a.region < b.region; });
@@ -645,8 +585,8 @@ void plan_groups_and_slots(CreateWork& cw, StatsPlan& pl, int bpw) {
             const RowBase B = rb[sp * nocc + oi];
             pl.g_pos0[sp * n_ar + r] = (int32_t) B.p0;
             int32_t xpx;
-            if (er < ctx->n_lut) xpx = (int32_t) (((size_t) er / (size_t) ctx->M) % (size_t) ctx->M) | ((int32_t) ((size_t) er % (size_t) ctx->M) << 8);
-            else { const size_t t = (size_t) cw.slow[(size_t) (er - ctx->n_lut)]; xpx = (int32_t) (w->cov[t] & 0xffu) | ((int32_t) (w->cov[t - 1] & 0xffu) << 8); }
+            if (er < tr.n_lut) xpx = (int32_t) (((size_t) er / (size_t) tr.M) % (size_t) tr.M) | ((int32_t) ((size_t) er % (size_t) tr.M) << 8);
+            else { const size_t t = (size_t) cw.slow[(size_t) (er - tr.n_lut)]; xpx = (int32_t) (w->cov[t] & 0xffu) | ((int32_t) (w->cov[t - 1] & 0xffu) << 8); }
             int64_t p = B.p0;
             for (int32_t j = 0, left = c_; left > 0; j++, left -= HF_GRP_PAIRS) {
                 const size_t g = (size_t) (B.g0 + j);
@@ -659,55 +599,49 @@ void plan_groups_and_slots(CreateWork& cw, StatsPlan& pl, int bpw) {
             }
         }
     pl.rwoff[(size_t) n_regions] = (int32_t) (pl.rslots.size() / unit);
-    ctx->n_parts = 1;
-    for (int reg = 0; reg < n_regions; reg++) if (pl.rwoff[(size_t) reg + 1] > pl.rwoff[(size_t) reg]) ctx->n_parts++;
-    ctx->n_groups = (int) n_grp;
+    tr.n_parts = 1;
+    for (int reg = 0; reg < n_regions; reg++) if (pl.rwoff[(size_t) reg + 1] > pl.rwoff[(size_t) reg]) tr.n_parts++;
+    tr.n_groups = (int) n_grp;
     pl.grp_off[n_grp] = (int32_t) (n_grp ? pl.grp_off[n_grp - 1] + (compact ? pl.grp_n[n_grp - 1] : HF_GRP_PAIRS) : 0);
-    ctx->plan_compact = compact;
+    tr.plan_compact = compact;
     pl.planned = true;
 }
 
-// the plan's device side: the negative-binomial count-data bins, groups, row slots, work arrays
+// the plan's device side: the negative-binomial count-data bins, groups, row slots
 int plan_upload(CreateWork& cw, StatsPlan& pl) {
-    hf_ctx* ctx = cw.ctx;
+    Track& tr = cw.ctx->tr;
     const int n_regions = cw.n_regions;
-    const size_t C = cw.C;
     {   // negative_binomial count data: the row slots of every (region, min(x, 249)) bin, in plan order
         std::vector<int32_t> boff((size_t) n_regions * 256 + 1, 0), blist;
         auto bin_of = [&](size_t k) {
             const int x = pl.rslots[k].xpx & 0xff;
-            return (size_t) pl.rwreg[k / ((size_t) 16 * (size_t) ctx->rs_bpw)] * 256 + (size_t) (x < HF_NB_MAX_COVERAGE ? x : HF_NB_MAX_COVERAGE - 1);
+            return (size_t) pl.rwreg[k / ((size_t) 16 * (size_t) tr.rs_bpw)] * 256 + (size_t) (x < HF_NB_MAX_COVERAGE ? x : HF_NB_MAX_COVERAGE - 1);
         };
         for (size_t k = 0; k < pl.rslots.size(); k++) if (pl.rslots[k].row >= 0) boff[bin_of(k) + 1]++;
         for (size_t b = 0; b + 1 < boff.size(); b++) boff[b + 1] += boff[b];
         blist.resize((size_t) boff.back());
         std::vector<int32_t> fill(boff.begin(), boff.end() - 1);
         for (size_t k = 0; k < pl.rslots.size(); k++) if (pl.rslots[k].row >= 0) blist[(size_t) fill[bin_of(k)]++] = (int32_t) k;
-        CTRY(dev_upload(ctx, cw.stg, &ctx->d_bin_off, boff.data(), boff.size()));
-        CTRY(dev_upload(ctx, cw.stg, &ctx->d_bin_list, blist.data(), blist.size()));
-        CALLOC(ctx->d_slot_h, pl.rslots.size() * 4 * 8);
-        CALLOC(ctx->d_H, (size_t) n_regions * 4 * 256 * 8);
+        CTRY(dev_upload(tr.slab, cw.stg, &tr.d_bin_off, boff.data(), boff.size()));
+        CTRY(dev_upload(tr.slab, cw.stg, &tr.d_bin_list, blist.data(), blist.size()));
     }
-    ctx->n_rowwaves = (int) (pl.rslots.size() / ((size_t) 16 * (size_t) ctx->rs_bpw));   // 16 * bpw slots per wavefront, whole blocks per region
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_grp_ar, pl.grp_ar.data(), pl.grp_ar.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_grp_n, pl.grp_n.data(), pl.grp_n.size()));
-    if (pl.compact) CTRY(dev_upload(ctx, cw.stg, &ctx->d_grp_off, pl.grp_off.data(), pl.grp_off.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_rowslots, pl.rslots.data(), pl.rslots.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_rw_region, pl.rwreg.data(), pl.rwreg.size()));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_rw_off, pl.rwoff.data(), pl.rwoff.size()));
-    ctx->h_rw_off = pl.rwoff;
-    CALLOC(ctx->d_grp_sums, (size_t) pl.grp_ar.size() * 16 * 8);
-    CALLOC(ctx->d_chunk_ll, C * 8);
-    CALLOC(ctx->d_rw_stats, (size_t) ctx->n_rowwaves * (16 + 9 + 2 + 3 * 16 + 1) * 8);
-    ctx->rows_ready = true;
+    tr.n_rowwaves = (int) (pl.rslots.size() / ((size_t) 16 * (size_t) tr.rs_bpw));   // 16 * bpw slots per wavefront, whole blocks per region
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_grp_ar, pl.grp_ar.data(), pl.grp_ar.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_grp_n, pl.grp_n.data(), pl.grp_n.size()));
+    if (pl.compact) CTRY(dev_upload(tr.slab, cw.stg, &tr.d_grp_off, pl.grp_off.data(), pl.grp_off.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_rowslots, pl.rslots.data(), pl.rslots.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_rw_region, pl.rwreg.data(), pl.rwreg.size()));
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_rw_off, pl.rwoff.data(), pl.rwoff.size()));
+    tr.h_rw_off = pl.rwoff;
+    tr.rows_ready = true;
     return HF_OK;
 }
 
 int create_statistics_plan(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx; const hf_windows* w = cw.w;
+    Track& tr = cw.ctx->tr; const hf_windows* w = cw.w;
     const size_t N = cw.N, C = cw.C;
     const int n_regions = cw.n_regions;
-    if (!(N > 0 && C > 0 && ctx->nseg > 0)) return HF_OK;
+    if (!(N > 0 && C > 0 && tr.nseg > 0)) return HF_OK;
     const size_t n_ar = cw.h_arow_src.size();
     const size_t S = (size_t) cw.n_sub;
     StatsPlan pl;
@@ -741,16 +675,16 @@ int create_statistics_plan(CreateWork& cw) {
     int bpw = 1;
     while (bpw < 8 && n_groups_all / 16 / (2 * bpw) >= 1000) bpw *= 2;   // (below that a second batch per wavefront costs more than it saves: cfg-2 +4 us)
     if (force) { const char* b = std::strstr(force, "bpw="); if (b) { const int v = std::atoi(b + 4); if (v >= 1 && v <= 64) bpw = v; } }
-    ctx->rs_bpw = bpw;
+    tr.rs_bpw = bpw;
     cw.phase("plan: pairs");
     int32_t* const pos = cw.P2;                   // record position of every window (b half); the position of the record with its f: k_pos_f
     if (w->chunk_off[0] != 0 || (size_t) w->chunk_off[C] != N) std::memset(pos, 0, N * 4);   // windows outside every chunk
     // the sub-passes' chunk and segment ranges
-    std::vector<hf_ctx::SubPass>& subs = ctx->subs;
-    subs.assign(S, hf_ctx::SubPass{0, 0, 0, 0, 0, 0, 0, 0});
+    std::vector<Track::SubPass>& subs = tr.subs;
+    subs.assign(S, Track::SubPass{0, 0, 0, 0, 0, 0, 0, 0});
     for (size_t sp = 0; sp < S; sp++) { subs[sp].c0 = (int) C; subs[sp].c1 = 0; }
     for (size_t c = 0; c < C; c++) {
-        hf_ctx::SubPass& sb = subs[(size_t) cw.sub_of[c]];
+        Track::SubPass& sb = subs[(size_t) cw.sub_of[c]];
         if ((int) c < sb.c0) sb.c0 = (int) c;
         if ((int) c + 1 > sb.c1) sb.c1 = (int) c + 1;
     }
@@ -758,7 +692,7 @@ int create_statistics_plan(CreateWork& cw) {
         if (subs[sp].c1 < subs[sp].c0) { subs[sp].c0 = subs[sp].c1 = sp ? subs[sp - 1].c1 : 0; }   // (an empty sub-pass)
         subs[sp].seg0 = cw.cseg0[(size_t) subs[sp].c0]; subs[sp].seg1 = cw.cseg0[(size_t) subs[sp].c1];
     }
-    const bool can_plan = pl.np > 0 && (pl.compact ? (int64_t) pl.np : n_groups_all * HF_GRP_PAIRS) + 3 * (int64_t) C + 4 * HF_GRP_PAIRS + (int64_t) ctx->nseg < INT32_MAX && N < (size_t) INT32_MAX;
+    const bool can_plan = pl.np > 0 && (pl.compact ? (int64_t) pl.np : n_groups_all * HF_GRP_PAIRS) + 3 * (int64_t) C + 4 * HF_GRP_PAIRS + (int64_t) tr.nseg < INT32_MAX && N < (size_t) INT32_MAX;
     if (can_plan) {
         plan_groups_and_slots(cw, pl, bpw);
         cw.phase("plan: groups, row slots");
@@ -766,9 +700,9 @@ int create_statistics_plan(CreateWork& cw) {
         // no plan (sparse rows past the position range): the per-chunk statistics read the records by window; positions in slot order,
         // one "sub-pass" holds everything
         cw.n_sub = 1;
-        subs.assign(1, hf_ctx::SubPass{0, (int) C, 0, ctx->nseg, 0, 0, 0, 0});
+        subs.assign(1, Track::SubPass{0, (int) C, 0, tr.nseg, 0, 0, 0, 0});
         std::fill(cw.sub_of.begin(), cw.sub_of.end(), 0);
-        pl.n_pos = plan_place_extras(cw, pl, 0, ctx->n_slots, false);
+        pl.n_pos = plan_place_extras(cw, pl, 0, tr.n_slots, false);
         subs[0].p1 = pl.n_pos;
     }
     // third pass: the position of every window's record.  Pairs of a (sub-pass, row of A) in window order; the windows without a pair of
@@ -790,34 +724,30 @@ int create_statistics_plan(CreateWork& cw) {
                 }
             } else {
                 for (int k = cw.cseg0[c]; k < cw.cseg0[c + 1]; k++) {
-                    const SegDesc& d = ctx->h_segs[(size_t) k];
+                    const SegDesc& d = tr.h_segs[(size_t) k];
                     for (int64_t x = 0; x < d.n; x++) pos[(size_t) (d.t0 + x)] = seg_slot(d, x);
                 }
             }
             const int32_t spare = (int32_t) (ex + (planned ? (T < 2 ? T : 2) : 0));   // takes the f of the chunk's last window
             pl.h_spare[c] = spare;
-            for (int k = cw.cseg0[c]; k < cw.cseg0[c + 1]; k++) ctx->h_segs[(size_t) k].spare_pos = spare;
+            for (int k = cw.cseg0[c]; k < cw.cseg0[c + 1]; k++) tr.h_segs[(size_t) k].spare_pos = spare;
         }
     }, cw.plan_ppt);
     cw.phase("plan: positions (third pass)");
     if (planned) CTRY(plan_upload(cw, pl));
-    CTRY(dev_upload(ctx, cw.stg, &ctx->d_seg, ctx->h_segs.data(), ctx->h_segs.size()));
-    ctx->n_pos = pl.n_pos;
-    CALLOC(ctx->d_pos, N * 4); CALLOC(ctx->d_pos_f, N * 4);
-    if (hipMemcpyAsync(ctx->d_pos, pos, N * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess) return set_err(HF_E_HIP, "hf_create: record positions up");
+    CTRY(dev_upload(tr.slab, cw.stg, &tr.d_seg, tr.h_segs.data(), tr.h_segs.size()));
+    tr.n_pos = pl.n_pos;
+    CALLOC(tr.d_pos, N * 4); CALLOC(tr.d_pos_f, N * 4);
+    if (hipMemcpyAsync(tr.d_pos, pos, N * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess) return set_err(HF_E_HIP, "hf_create: record positions up");
     {   // pos_f[t] = the position of window t + 1's record (which holds f_t), the chunk's spare record for its last window: on the device
-        CTRY(dev_upload(ctx, cw.stg, &cw.d_spare, pl.h_spare.data(), C));
-        if (w->chunk_off[0] != 0 || (size_t) w->chunk_off[C] != N) hipMemsetAsync(ctx->d_pos_f, 0, N * 4, nullptr);
-        hipLaunchKernelGGL(k_pos_f, dim3((unsigned) ((cw.maxT + 255) / 256), (unsigned) C), dim3(256), 0, 0, ctx->d_off, ctx->d_pos, cw.d_spare, ctx->d_pos_f);
+        CTRY(dev_upload(tr.slab, cw.stg, &cw.d_spare, pl.h_spare.data(), C));
+        if (w->chunk_off[0] != 0 || (size_t) w->chunk_off[C] != N) hipMemsetAsync(tr.d_pos_f, 0, N * 4, nullptr);
+        hipLaunchKernelGGL(k_pos_f, dim3((unsigned) ((cw.maxT + 255) / 256), (unsigned) C), dim3(256), 0, 0, tr.d_off, tr.d_pos, cw.d_spare, tr.d_pos_f);
     }
     if (pl.n_pos >= INT32_MAX) return set_err(HF_E_ARG, "hf_create: more than 2^31 record positions (shard the chunk list: hmm_flagger_multi.h)");
-    int64_t cap = 0;                          // positions the pass buffer holds: the largest sub-pass (everything, with one)
-    for (const auto& sb : ctx->subs) if (sb.p1 - sb.p0 > cap) cap = sb.p1 - sb.p0;
-    CALLOC(ctx->d_recs, (size_t) (cap + 1) * 64);
-    if (ctx->subs.size() == 1) ctx->d_recs_all = ctx->d_recs;      // (several sub-passes: the all-windows buffer on first use, all_records_buffer)
     if (cw.ctrace) std::fprintf(stderr, "[hf_create] statistics plan: %s, %d groups, %d row-slot wavefronts of %d x 16 slots, %lld positions for %lld pairs; %zu sub-pass(es), record buffer %.0f MB\n",
-                                !planned ? "none (per-chunk statistics)" : ctx->plan_compact ? "compact" : "padded", ctx->n_groups, ctx->n_rowwaves,
-                                ctx->rs_bpw, (long long) pl.n_pos, (long long) pl.np, ctx->subs.size(), (double) (cap + 1) * 64 / 1e6);
+                                !planned ? "none (per-chunk statistics)" : tr.plan_compact ? "compact" : "padded", tr.n_groups, tr.n_rowwaves,
+                                tr.rs_bpw, (long long) pl.n_pos, (long long) pl.np, tr.subs.size(), (double) pass_layout(tr).recs / 1e6);
     cw.phase("plan: uploads, allocations");
     return HF_OK;
 }
@@ -833,16 +763,16 @@ int create_statistics_plan(CreateWork& cw) {
 // 13 us SLOWER (60 us against 47, same box, three alternations), at 1/4 and 1/8 of the size it changes nothing.  Block b runs segment b, as
 // in rounds 3-5; HF_SEG_XCD=1 switches the plan on.
 int create_xcd_plan(CreateWork& cw, int64_t resident, int max_nseg) {
-    hf_ctx* ctx = cw.ctx;
+    Track& tr = cw.ctx->tr;
     const char* e = std::getenv("HF_SEG_XCD");
     const bool want = e && e[0] == '1';
-    if (!(want && ctx->seg_fused && resident > 0 && (int64_t) max_nseg * 8 * 2 <= resident && !ctx->subs.empty())) return HF_OK;
-    std::vector<int32_t>& tab = ctx->h_seg_of_block;
+    if (!(want && cw.ctx->pass.seg_fused && resident > 0 && (int64_t) max_nseg * 8 * 2 <= resident && !tr.subs.empty())) return HF_OK;
+    std::vector<int32_t>& tab = tr.h_seg_of_block;
     tab.clear();
-    for (auto& sb : ctx->subs) {
+    for (auto& sb : tr.subs) {
         std::vector<int32_t> lane[8];
         for (int c = sb.c0; c < sb.c1; c++) {
-            const int s0 = cseg0_of(ctx, c), s1 = cseg0_of(ctx, c + 1);
+            const int s0 = tr.h_cseg0[(size_t) c], s1 = tr.h_cseg0[(size_t) c + 1];
             if (s1 <= s0) continue;
             int best = 0;
             for (int x = 1; x < 8; x++) if (lane[x].size() < lane[best].size()) best = x;
@@ -856,26 +786,27 @@ int create_xcd_plan(CreateWork& cw, int64_t resident, int max_nseg) {
             for (size_t r = 0; r < lane[x].size(); r++) tab[(size_t) sb.b0 + r * 8 + (size_t) x] = lane[x][r];
         sb.b1 = (int) tab.size();
     }
-    return dev_upload(ctx, cw.stg, &ctx->d_seg_of_block, tab.data(), tab.size());
+    return dev_upload(tr.slab, cw.stg, &tr.d_seg_of_block, tab.data(), tab.size());
 }
 
+// (and the settings of the context's pass, before pass_create)
 int create_launch_config(CreateWork& cw) {
-    hf_ctx* ctx = cw.ctx;
-    const int device = cw.device, algo = cw.algo;
-    { const char* e = std::getenv("HF_HOST_TRACE"); ctx->host_trace = e && e[0] == '1'; }
-    { const char* e = std::getenv("HF_SEG_LAUNCHES"); ctx->seg_fused = !(e && e[0] == '2'); }   // HF_SEG_LAUNCHES=2: k_seg_prod + k_seg_fb
-    if (ctx->seg_fused && ctx->nseg > 0) {
+    Track& tr = cw.ctx->tr; Pass& ps = cw.ctx->pass;
+    const int device = cw.device;
+    { const char* e = std::getenv("HF_HOST_TRACE"); ps.host_trace = e && e[0] == '1'; }
+    { const char* e = std::getenv("HF_SEG_LAUNCHES"); ps.seg_fused = !(e && e[0] == '2'); }   // HF_SEG_LAUNCHES=2: k_seg_prod + k_seg_fb
+    if (ps.seg_fused && tr.nseg > 0) {
         // Static guard of the one-launch hand-off: the segments of a chunk wait for each other INSIDE the launch, so all
         // of them have to be resident together.  A chunk with more segments than the device holds workgroups of k_seg_fb (small
         // --windowLen with a large --chunkLen: > 1.57 M windows in one chunk on 256 CUs x 12) could only time out (65 536 polls per
         // waiting lane) and re-run every first pass in two launches: such a context starts in two-launch mode.
         int per_cu = 0, cus = 0, max_nseg = 0;
-        for (const SegDesc& d : ctx->h_segs) if (d.nseg > max_nseg) max_nseg = d.nseg;
+        for (const SegDesc& d : tr.h_segs) if (d.nseg > max_nseg) max_nseg = d.nseg;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_seg_fb<true, true>, 64, seg_lds_bytes()) != hipSuccess) { (void) hipGetLastError(); per_cu = 0; }
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void) hipGetLastError(); cus = 0; }
         int64_t resident = (int64_t) per_cu * cus;
         if (const char* e = std::getenv("HF_SEG_RESIDENT")) resident = std::atoll(e);   // tests: pretend a smaller device
-        if (resident > 0 && max_nseg > resident) ctx->seg_fused = false;
+        if (resident > 0 && max_nseg > resident) ps.seg_fused = false;
         CTRY(create_xcd_plan(cw, resident, max_nseg));
         // Cached row blocks (hf_seg.h, round 5): the LDS that a device with FEWER segments than it could hold leaves idle goes to the
         // workgroups — the largest nc at which every segment is still resident at once.  Decided from the occupancy the runtime reports for
@@ -885,10 +816,10 @@ int create_launch_config(CreateWork& cw) {
                    hipFuncSetAttribute(reinterpret_cast<const void*>(k_seg_fb<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) == hipSuccess;
         };
         int nc = 0;
-        if (ctx->seg_fused && cus > 0) {
+        if (ps.seg_fused && cus > 0) {
             for (int c = HF_SEG_LMAX; c >= 1; c--) {
                 const size_t lds = seg_lds_bytes(c);
-                if (lds > ctx->lds_max && lds > 64 * 1024 && !raise_lds(lds)) { (void) hipGetLastError(); continue; }
+                if (lds > tr.lds_max && lds > 64 * 1024 && !raise_lds(lds)) { (void) hipGetLastError(); continue; }
                 int pc = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k_seg_fb<true, true, true>, 64, lds) != hipSuccess) { (void) hipGetLastError(); continue; }
                 int64_t res_c = (int64_t) pc * cus;
@@ -896,7 +827,7 @@ int create_launch_config(CreateWork& cw) {
                 // 15 % of room to spare: where the segments filled the device to the last workgroup the API allows (1 531 segments at six
                 // per CU) k_seg_fb took 59 us instead of 41 — one workgroup per CU fewer was actually resident, and the segments of a chunk
                 // wait for each other (profiles/r05_scale_nc.txt)
-                if (res_c * 85 / 100 >= ctx->nseg) { nc = c; break; }
+                if (res_c * 85 / 100 >= tr.nseg) { nc = c; break; }
             }
             // all of a lane's steps or none: with only some of them cached the kernel's run-time block arithmetic costs what the saved fetches
             // bring (same box, 3 of 8 steps at 1/4 of configs[2]: 29.2 us against 28.9 without; all 8 at 1/8: 25.6 against 26.5 —
@@ -909,41 +840,40 @@ int create_launch_config(CreateWork& cw) {
                 if (lds > 64 * 1024 && !raise_lds(lds)) { (void) hipGetLastError(); nc = 0; }
             }
         }
-        ctx->seg_nc = nc;
-        if (cw.ctrace || ctx->host_trace)
+        tr.seg_nc = nc;
+        if (cw.ctrace || ps.host_trace)
             std::fprintf(stderr, "[hf_create] segment kernel: %d segments, longest chunk %d; %lld workgroups resident (%d per CU x %d CUs): %s; %d of %d row blocks cached in LDS (%zu B per workgroup)%s\n",
-                         ctx->nseg, max_nseg, (long long) resident, per_cu, cus,
-                         ctx->seg_fused ? "one launch" : "TWO launches (a chunk has more segments than the device holds workgroups)", nc, HF_SEG_LMAX, seg_lds_bytes(nc),
-                         ctx->d_seg_of_block ? "; XCD plan" : "");
+                         tr.nseg, max_nseg, (long long) resident, per_cu, cus,
+                         ps.seg_fused ? "one launch" : "TWO launches (a chunk has more segments than the device holds workgroups)", nc, HF_SEG_LMAX, seg_lds_bytes(nc),
+                         tr.d_seg_of_block ? "; XCD plan" : "");
     }
     {   // the job list of the per-pass tables (hf_scan.h), built once: the (key, class) list of the rows of A when the segment kernels run,
         // the emission keys otherwise (HF_ALGO_SEQ); then the slow windows
-        const bool arows = ctx->nseg > 0 && ctx->d_lutA && algo == HF_ALGO_SCAN;
-        const int nk = arows ? ctx->n_combo : ctx->n_keys;
-        const int jobs = nk + ctx->n_slow;
-        CALLOC(ctx->d_jobs, (size_t) (jobs + 1) * sizeof(TableJob));
+        const bool arows = arow_jobs(tr);
+        const int nk = arows ? tr.n_combo : tr.n_keys;
+        const int jobs = nk + tr.n_slow;
+        CALLOC(tr.d_jobs, (size_t) (jobs + 1) * sizeof(TableJob));
         if (jobs > 0) {
-            hipLaunchKernelGGL(k_build_jobs, dim3((unsigned) ((jobs + 255) / 256)), dim3(256), 0, 0, nk, arows ? ctx->d_arow_src : ctx->d_keys,
-                               arows ? ctx->d_arow_cls : (const int32_t*) nullptr, ctx->n_slow, ctx->d_slow_w, ctx->d_rec, ctx->d_beta, ctx->M,
-                               ctx->n_lut, ctx->beta_star, ctx->d_jobs);
+            hipLaunchKernelGGL(k_build_jobs, dim3((unsigned) ((jobs + 255) / 256)), dim3(256), 0, 0, nk, arows ? tr.d_arow_src : tr.d_keys,
+                               arows ? tr.d_arow_cls : (const int32_t*) nullptr, tr.n_slow, tr.d_slow_w, tr.d_rec, tr.d_beta, tr.M,
+                               tr.n_lut, tr.beta_star, tr.d_jobs);
             if (hipGetLastError() != hipSuccess) return set_err(HF_E_HIP, "hf_create: k_build_jobs");
         }
-        TabWork& tw = ctx->tabwork;
-        tw.n_jobs = jobs; tw.K = ctx->K; tw.jobs = ctx->d_jobs; tw.lutE = ctx->d_lutE; tw.lutC = ctx->d_lutC; tw.lutA = arows ? ctx->d_lutA : nullptr;
+        tr.tabwork.n_jobs = jobs; tr.tabwork.K = tr.K; tr.tabwork.jobs = tr.d_jobs;   // (a pass adds its tables: pass_create)
     }
-    ctx->seg_test_timeout = std::getenv("HF_SEG_TEST_TIMEOUT") != nullptr;
-    { const char* e = std::getenv("HF_STREAM_STAMP"); if (e && e[0] == '0') ctx->stream_stamp_ok = false; }
-    { const char* e = std::getenv("HF_PARAMS_COPY"); if (e && e[0] == '1') ctx->kp_ok = false; }                    // the parameter block by a copy ahead of every pass
-    { const char* e = std::getenv("HF_TOTAL"); if (e && !std::strcmp(e, "device")) ctx->host_total_ok = false; }   // HF_TOTAL=device: the pass's last blocks sum the partials (rounds 3-4)
+    ps.seg_test_timeout = std::getenv("HF_SEG_TEST_TIMEOUT") != nullptr;
+    { const char* e = std::getenv("HF_STREAM_STAMP"); if (e && e[0] == '0') ps.stream_stamp_ok = false; }
+    { const char* e = std::getenv("HF_PARAMS_COPY"); if (e && e[0] == '1') ps.kp_ok = false; }                    // the parameter block by a copy ahead of every pass
+    { const char* e = std::getenv("HF_TOTAL"); if (e && !std::strcmp(e, "device")) ps.host_total_ok = false; }   // HF_TOTAL=device: the pass's last blocks sum the partials (rounds 3-4)
     {
         const char* e = std::getenv("HF_STATS");
-        ctx->stats_mode = (e && std::strcmp(e, "chunks") == 0) ? HF_STATS_CHUNKS : HF_STATS_ROWS;
+        ps.stats_mode = (e && std::strcmp(e, "chunks") == 0) ? HF_STATS_CHUNKS : HF_STATS_ROWS;
     }
 #ifdef HF_SEG_TRACE
-    if (ctx->nseg > 0 && std::getenv("HF_SEG_TRACE_FILE")) {
-        CALLOC(ctx->d_seg_trace, (size_t) ctx->nseg * HF_SEG_TRACE_N * 8);
-        hipMemsetAsync(ctx->d_seg_trace, 0, (size_t) ctx->nseg * HF_SEG_TRACE_N * 8, nullptr);
-        hipMemcpyToSymbol(HIP_SYMBOL(g_seg_trace), &ctx->d_seg_trace, sizeof(void*));
+    if (tr.nseg > 0 && std::getenv("HF_SEG_TRACE_FILE")) {
+        CALLOC(tr.d_seg_trace, (size_t) tr.nseg * HF_SEG_TRACE_N * 8);
+        hipMemsetAsync(tr.d_seg_trace, 0, (size_t) tr.nseg * HF_SEG_TRACE_N * 8, nullptr);
+        hipMemcpyToSymbol(HIP_SYMBOL(g_seg_trace), &tr.d_seg_trace, sizeof(void*));
     }
 #endif
     cw.phase("switches, job list");
@@ -958,58 +888,58 @@ extern "C" int hf_create(const hf_windows* w, int n_regions, int max_comps, int 
         return set_err(HF_E_ARG, "hf_create: bad argument");
     if (hf_device_count() <= 0) return set_err(HF_E_NOGPU, "hf_create: no HIP device (there is no CPU fallback)");
     HIPCHK(hipSetDevice(device));
-    hf_ctx* ctx = new hf_ctx();
-    ctx->device = device; ctx->algo = algo;
+    std::unique_ptr<hf_ctx> own = std::make_unique<hf_ctx>();
+    hf_ctx* ctx = own.get();
+    Track& tr = ctx->tr;
+    tr.device = device; tr.algo = algo;
     CreateWork cw;
-    cw.ctx = ctx; cw.w = w; cw.n_regions = n_regions; cw.max_comps = max_comps; cw.device = device; cw.algo = algo;
+    cw.ctx = ctx; cw.w = w; cw.n_regions = n_regions; cw.device = device; cw.algo = algo;
     cw.ctrace = std::getenv("HF_HOST_TRACE") != nullptr;
     cw.t_begin = cw.t_last = std::chrono::steady_clock::now();
     {
         int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0) ctx->lds_max = (size_t) v;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0) tr.lds_max = (size_t) v;
     }
-    ctx->N = w->n_windows; ctx->C = w->n_chunks; ctx->R = n_regions; ctx->K = max_comps;
-    ctx->V = hf_stats_len(n_regions, max_comps);
-    ctx->meta = *w;
-    ctx->meta.chunk_off = nullptr; ctx->meta.cov = ctx->meta.mapq = ctx->meta.clip = nullptr;
-    ctx->meta.annot = nullptr; ctx->meta.chunk_s = ctx->meta.chunk_e = ctx->meta.chunk_ctg_len = nullptr;
+    tr.N = w->n_windows; tr.C = w->n_chunks; tr.R = n_regions; tr.K = max_comps;
+    tr.V = hf_stats_len(n_regions, max_comps);
+    tr.meta = *w;
+    tr.meta.chunk_off = nullptr; tr.meta.cov = tr.meta.mapq = tr.meta.clip = nullptr;
+    tr.meta.annot = nullptr; tr.meta.chunk_s = tr.meta.chunk_e = tr.meta.chunk_ctg_len = nullptr;
     for (int c = 0; c < w->n_chunks; c++) {
         const int64_t T = w->chunk_off[c + 1] - w->chunk_off[c];
-        if (T < 0 || T > INT32_MAX) { delete ctx; return set_err(HF_E_ARG, "hf_create: bad chunk_off"); }
+        if (T < 0 || T > INT32_MAX) return set_err(HF_E_ARG, "hf_create: bad chunk_off");
         if (T > cw.maxT) cw.maxT = (int32_t) T;
     }
-    ctx->maxT = cw.maxT;
+    tr.maxT = cw.maxT;
     {   // beta of every interior window (hmm.c:301-316): u - l = L - 1 there
         const int L = w->mean_read_len;
         double bs = 1.0;
         if (w->adjust_contig_ends) { bs = (double) (L - 1) / L; if (!(bs > 0.25)) bs = 0.25; }
-        ctx->beta_star = bs;
+        tr.beta_star = bs;
     }
-    cw.N = (size_t) ctx->N; cw.C = (size_t) ctx->C;
-    // (the first slab holds what this function allocates — ~(29 + 2.4 R) bytes per window of arrays, ~85 per window of pair
-    // records, and a context in sub-passes keeps ONE sub-pass's records, not all windows': 4 x configs[2] reserved 814 MB, now 470)
-    {
-        const size_t rec_windows = cw.N > 2800000 ? (size_t) 1800000 : cw.N;
-        ctx->slab_first = cw.N * (size_t) (32 + 3 * n_regions) + rec_windows * 90 + ((size_t) 16 << 20);
-    }
+    cw.N = (size_t) tr.N; cw.C = (size_t) tr.C;
+    // the first block of the track's slab holds what the steps allocate: ~28 bytes per window of arrays, 38 without packed upload words (the
+    // pass state has a slab of its own, sized by pass_layout)
+    tr.slab.first = cw.N * 40 + ((size_t) 16 << 20);
     int rc = create_pack_windows(cw);
     if (!rc) rc = create_device_store(cw);
     if (!rc) rc = create_key_tables(cw);
     if (!rc) rc = create_rows_and_segments(cw);
-    if (!rc && algo == HF_ALGO_SCAN && cw.N > 0 && cw.C > 0 && ctx->nseg == 0)
+    if (!rc && algo == HF_ALGO_SCAN && cw.N > 0 && cw.C > 0 && tr.nseg == 0)
         rc = set_err(HF_E_ARG, "hf_create: HF_ALGO_SCAN holds at most 2^30 windows per context (shard the chunk list: hmm_flagger_multi.h)");
     if (!rc) rc = create_statistics_plan(cw);
     if (!rc) rc = create_launch_config(cw);
-    if (rc) { hf_destroy(ctx); return rc; }
+    if (!rc) rc = pass_create(tr, ctx->pass, &ctx->pass, &cw.stg);   // (the settings create_launch_config made)
+    if (rc) { hf_destroy(own.release()); return rc; }
     {   // the ONE synchronisation of this function: uploads and set-up kernels done, the staging buffers may go back to the cache
         const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) { hf_destroy(ctx); return set_err(HF_E_HIP, std::string("setup: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { hf_destroy(own.release()); return set_err(HF_E_HIP, std::string("setup: ") + hipGetErrorString(e)); }
         unsigned fl = 0;
-        if (cw.N > 0 && cw.C > 0) hipMemcpy(&fl, ctx->d_flags, 4, hipMemcpyDeviceToHost);
-        if (fl & HF_FLAG_REGION) { hf_destroy(ctx); return set_err(HF_E_REGION, "a window's region index is >= n_regions"); }
+        if (cw.N > 0 && cw.C > 0) hipMemcpy(&fl, tr.d_setup_flags, 4, hipMemcpyDeviceToHost);
+        if (fl & HF_FLAG_REGION) { hf_destroy(own.release()); return set_err(HF_E_REGION, "a window's region index is >= n_regions"); }
     }
     cw.phase("uploads and set-up kernels done");
-    ctx->create_phases.emplace_back("total", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - cw.t_begin).count());
-    *out = ctx;
+    tr.create_phases.emplace_back("total", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - cw.t_begin).count());
+    *out = own.release();
     return HF_OK;
 }

@@ -240,7 +240,6 @@ static void par_chunks(const int64_t* chunk_off, size_t C, Fn fn, size_t parts_p
     for (auto& t : th) t.join();
 }
 struct hf_ctx;
-static int cseg0_of(const hf_ctx* ctx, int c);      // first segment of chunk c (c = C: the number of segments)
 static void vit_free(hf_ctx* ctx);                 // the buffers of hf_viterbi (hf_destroy)
 // slot of a segment's x-th window: lane x / L holds it as its x % L-th (hf_seg.h)
 static inline int32_t seg_slot(const SegDesc& d, int64_t x) { return d.slot0 + (int32_t) ((x % d.L) * 64 + x / d.L); }
@@ -248,164 +247,196 @@ static int set_err(int code, const std::string& msg) { g_err = msg; return code;
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     return set_err(HF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
-struct hf_ctx {
+// entries of one statistics vector (hf_chunks.h StatAcc<KT>): what k_row_stats' blocks hand on per region
+static constexpr size_t stat_acc_len(int kt) { return (size_t) (16 + 9 + 2 + 3 * kt + 1); }
+
+// Device memory of hf_create and of every pass comes out of a few SLABS (round 5: ~45 hipMalloc calls and as many hipFree were ~0.5 ms
+// of a 4 ms hf_create): bump allocation, 256-byte granules, freed all at once.  `first` sizes the first block; later blocks are 64 MiB.
+struct Slab {
+    std::vector<std::pair<char*, size_t>> blocks; char* cur = nullptr; size_t left = 0, first = 0;
+    static size_t granule(size_t bytes) { return ((bytes ? bytes : 8) + 255) & ~(size_t) 255; }
+    void* alloc(size_t bytes) {
+        bytes = granule(bytes);
+        if (bytes > left) {
+            const size_t want = std::max(bytes, blocks.empty() ? first : (size_t) 64 << 20);
+            char* p = nullptr;
+            if (hipMalloc((void**) &p, want) != hipSuccess) {
+                (void) hipGetLastError();
+                if (want == bytes || hipMalloc((void**) &p, bytes) != hipSuccess) return nullptr;   // (a smaller block: just this request)
+                blocks.emplace_back(p, bytes);
+                return p;                                                                         // (the current block keeps its remainder)
+            }
+            blocks.emplace_back(p, want);
+            cur = p; left = want;
+        }
+        char* r = cur;
+        cur += bytes; left -= bytes;
+        return r;
+    }
+    void release() { for (auto& b : blocks) hipFree(b.first); blocks.clear(); cur = nullptr; left = 0; }
+};
+
+// THE TRACK: what hf_create builds from the windows and nothing writes afterwards — the window store, the emission keys and slow windows,
+// the tiles, the rows of A, the segment plan, the statistics plan, the job list of k_tables.  Every pass over it reads it.
+struct Track {
     int device = 0, algo = HF_ALGO_SCAN;
-    // device memory of hf_create comes out of a few SLABS (round 5: ~45 hipMalloc calls and as many hipFree were ~0.5 ms of a 4 ms hf_create):
-    // bump allocation, 256-byte aligned; what hf_create frees again (temporaries) simply stays until hf_destroy.  ctx_free knows which
-    // pointers are the context's own later hipMallocs.
-    std::vector<std::pair<char*, size_t>> slabs; char* slab_cur = nullptr; size_t slab_left = 0, slab_first = 0;
+    Slab slab;
     int64_t N = 0; int32_t C = 0; int32_t maxT = 0;
     int R = 1, K = 2;
     int64_t V = 0;                 // per-chunk stats vector length
     hf_windows meta{};             // scalar options only (pointers cleared)
+    size_t lds_max = 64 * 1024;    // LDS one workgroup may use (hipDeviceAttributeMaxSharedMemoryPerBlock)
+    double beta_star = 1.0;
+    size_t params_bytes = 0;       // the parameter block (DevParams + one DevRegion per region past the first)
     // device-resident window store
     int64_t* d_off = nullptr;      // [C+1]
     uint32_t* d_rec = nullptr;     // [N]
     double* d_beta = nullptr;      // [N]
     uint64_t* d_regmask = nullptr; // [C] bit r set if region r occurs in the chunk
-    // per-pass work arrays
-    double* d_E = nullptr;         // [N][16] emission rows, HF_ALGO_SEQ only
-    double* d_f = nullptr;         // [ntiles][L][2][64] double2: tile-major, lane-minor (hf_scan.h fb_slot)
-    double* d_b = nullptr;         // same layout
+    unsigned* d_setup_flags = nullptr;   // k_setup's flag word (a region index out of range): read once, at the end of hf_create
     std::vector<int64_t> h_off; std::vector<int32_t> h_tile0;   // host copies for hf_get_forward_backward
-    double* d_scale = nullptr;     // [N]
-    int8_t* d_label = nullptr;     // [N]
-    double* d_chunk_stats = nullptr; // [C][V]; own_chunk_stats: allocated here (else bound to an exchange buffer, hf_bind_chunk_stats)
-    bool own_chunk_stats = true;
-    double* d_total = nullptr;     // [V]
-    double* d_total_host = nullptr; // device address of the pinned h_total: k_reduce writes the result straight to the host
-    // scan algorithm: tile tables and per-tile work arrays
+    // scan algorithm: tile table (per-chunk statistics, HF_ALGO_SEQ)
     TileDesc* d_tile_desc = nullptr;
     int ntiles = 0; int32_t* d_chunk_tile0 = nullptr;
+    // per-iteration emission rows (k_tables): keys = occurring (region, x, x_prev) of interior windows,
+    // slow = chunk-first and contig-end windows (beta != beta_star), ascending; slow_off[c] = chunk c's first entry
+    int M = 1; int64_t n_lut = 0;
+    int n_keys = 0; int32_t* d_keys = nullptr;
+    int n_slow = 0; int64_t* d_slow_w = nullptr; int32_t* d_slow_off = nullptr;
+    TableJob* d_jobs = nullptr; TabWork tabwork{};   // the job list of the per-pass tables (hf_scan.h k_build_jobs), built once; a pass adds its tables
+    // rows of A_t = T_t∘e_t (hf_seg.h): one per (emission key, transition class) that occurs at an interior window, then one
+    // per slow window; d_arow[t] = the row of window t (bit 31: chunk-first), d_arow_src / d_arow_cls = where a row comes from
+    int32_t* d_arow = nullptr; int32_t* d_arow_src = nullptr; int32_t* d_arow_cls = nullptr;
+    int n_arows = 0, n_combo = 0;
+    // segment kernels (hf_seg.h): the forward-backward of the statistics-by-row path
+    SegDesc* d_seg = nullptr; int nseg = 0; int32_t* d_chunk_seg0 = nullptr; int64_t n_slots = 0;
+    std::vector<SegDesc> h_segs;                // the segment descriptors (the getters derive a window's slot from them)
+    std::vector<int32_t> h_cseg0;               // first segment of every chunk (+ the end)
+    int seg_nc = 0;                    // row blocks a segment workgroup keeps in LDS across its three walks (hf_seg.h: chosen so that all segments stay resident)
+    // XCD plan (round 6): block b of k_seg_fb runs segment seg_of_block[b]; the segments of a chunk sit on block indices congruent mod 8
+    // (observed: block b runs on XCD b % 8 — for speed only, the hand-off protocol is system-scope whatever the placement).  Null: identity.
+    int32_t* d_seg_of_block = nullptr; std::vector<int32_t> h_seg_of_block;
+    // SUB-PASSES (round 5): a context whose records would not fit the Infinity Cache (256 MB; BASELINE configs[2] writes 130 MB) cuts its
+    // chunk list into sub-passes of whole chunks; a pass runs k_seg_fb then k_pair_sums per sub-pass through ONE buffer that holds a
+    // sub-pass's positions [p0, p1) at a time (Pass::d_recs; the plan's groups are numbered sub-pass by sub-pass, so a sub-pass's records are
+    // contiguous) — the records never travel to HBM and back.  Everything that needs the records of ALL windows at once (the getters,
+    // per-chunk statistics) runs the segment kernel into Pass::d_recs_all instead (allocated on first use; = d_recs with one sub-pass).
+    struct SubPass { int c0, c1, seg0, seg1, g0, g1; int64_t p0, p1; int b0 = 0, b1 = 0; };   // b0, b1: its blocks in the XCD plan (d_seg_of_block)
+    std::vector<SubPass> subs;
+    // statistics by emission row (hf_rows.h): the static plan
+    bool rows_ready = false;
+    int n_groups = 0, n_rowwaves = 0, n_parts = 1;   // n_parts: regions that have a row, + 1 (the log-likelihood blocks): hf_rows.h hand-offs
+    int rs_bpw = 1;                   // batches of 16 row slots per wavefront of k_row_stats
+    bool plan_compact = false;        // the groups' records back to back (sparse rows) instead of 64 positions per group
+    int32_t* d_grp_off = nullptr;     // compact plan: first position of every group (+ the end)
+    int32_t* d_grp_ar = nullptr; int32_t* d_grp_n = nullptr;   // per group: its row of A, its pairs
+    int32_t* d_pos = nullptr; int64_t n_pos = 0;   // [N] position of every window's pair record in the records (plan order; slot order without a plan)
+    int32_t* d_pos_f = nullptr;    // [N] position of the record that holds every window's f (getters)
+    RowSlot* d_rowslots = nullptr; int32_t* d_rw_region = nullptr; int32_t* d_rw_off = nullptr; std::vector<int32_t> h_rw_off;
+    int32_t* d_bin_off = nullptr; int32_t* d_bin_list = nullptr;   // negative_binomial count-data plan: the row slots of every (region, x) bin
+    std::vector<std::pair<const char*, double>> create_phases;   // hf_create_phases
+    unsigned long long* d_seg_trace = nullptr;   // -DHF_SEG_TRACE builds only
+};
+
+// THE PASS STATE over a track: everything hf_estep, hf_finish and the getters write — parameter block, tables, rows of A, hand-off flags and
+// epochs, pair records, sums, labels, flag word, totals, the pinned result block, profiling events.  A context has one; a batch
+// (hf_batch.h) one per model, over the context's track.  Its device arrays come out of its own slab, sized by pass_layout.
+struct Pass {
+    const Track* tr = nullptr;
+    Slab slab;
+    // settings (a batch model starts from the context's: hf_batch_create)
+    int stats_mode = HF_STATS_CHUNKS;
+    bool seg_fused = true, seg_test_timeout = false;   // one-launch mode (hf_seg.h); a timed-out wait switches the pass to two launches
+    bool kp_ok = true;             // HF_PARAMS_COPY=1 switches the kernel-argument path off
+    bool host_total_ok = true;     // the total of a one-GPU pass summed by the HOST (HF_TOTAL=device: off)
+    bool stream_stamp_ok = true;   // wait_total: completion through hipStreamWriteValue32 (HF_STREAM_STAMP=0: off)
     bool host_trace = false; double ht[5] = {0, 0, 0, 0, 0}; long ht_n = 0;   // HF_HOST_TRACE=1: where an EM step's host time goes
+    // device arrays (slab)
+    int8_t* d_label = nullptr;     // [N]
+    double* d_chunk_stats = nullptr; // [C][V]: d_chunk_stats_own, or an exchange buffer (hf_bind_chunk_stats)
+    double* d_chunk_stats_own = nullptr;
+    double* d_total = nullptr;     // [V]
+    unsigned* d_flags = nullptr;
+    unsigned* d_done = nullptr;    // k_reduce / k_row_stats: blocks finished (the last one sums the parts and stamps the host block)
+    unsigned long long* d_cks = nullptr;   // k_reduce: XOR of the words written (checksum of a polled pass)
+    DevParams* d_params = nullptr;
+    double* d_lutE = nullptr; double* d_lutC = nullptr; double* d_Es = nullptr; double* d_Cs = nullptr;   // emission rows: keys, then slow windows
+    double* d_lutA = nullptr;      // rows of A, then the identity row (pass_create writes it; no kernel does)
     double* d_tile_ll = nullptr;
     double* d_tile_stats = nullptr; // [ntiles][R][NA(16)]
-    unsigned* d_flags = nullptr;
-    TableJob* d_jobs = nullptr; TabWork tabwork{};   // the job list of the per-pass tables (hf_scan.h k_build_jobs), built once
-    DevParams* d_params = nullptr; DevParams* h_params = nullptr; size_t params_bytes = 0;
-    KParams kparams{};             // the parameter block as kernel arguments of k_tables (one region: pack_kparams)
-    bool kp_ok = true, kp_now = false;   // HF_PARAMS_COPY=1 switches the kernel-argument path off; this pass uses it
-    unsigned* h_flags = nullptr;
+    unsigned* d_seg_ready = nullptr; double* d_seg_ll = nullptr; double* d_Pseg = nullptr;
+    double* d_recs = nullptr;      // pair records { f_{t-1}, b_t } of k_seg_fb, plan order; fb_recs: the last full pass wrote them
+    double* d_grp_sums = nullptr; double* d_chunk_ll = nullptr; double* d_rw_stats = nullptr;   // statistics by emission row: per group, per chunk, per row wavefront
+    double* d_E = nullptr;         // [N][16] emission rows, HF_ALGO_SEQ only
+    double* d_f = nullptr;         // [ntiles][L][2][64] double2: tile-major, lane-minor (hf_scan.h fb_slot), HF_ALGO_SEQ only
+    double* d_b = nullptr;         // same layout
+    double* d_scale = nullptr;     // [N], HF_ALGO_SEQ only (hf_seg.h keeps the scales by slot)
+    TabWork tabwork{};             // the track's job list with this pass's tables
+    // allocated on first use (pass_destroy frees them)
+    double* d_recs_all = nullptr;  // the records of ALL windows (= d_recs with one sub-pass)
+    double* d_segQ = nullptr;      // [nseg][8][64] double2: lane products, lane-minor (two-launch mode only)
+    double* d_scale_s = nullptr;   // [n_slots] scales by slot (hf_get_forward_backward)
+    int32_t* d_slot_of = nullptr;  // window -> slot, built from the track's h_segs by the first getter call
+    // negative_binomial model: device copies of hf_params.nb_* and the count data (first negative_binomial pass)
+    double *d_nbE = nullptr, *d_nbP = nullptr, *d_nbDig = nullptr, *d_nbR = nullptr, *d_nbBeta = nullptr;   // d_nbE owns ONE buffer: E | P | dig | r | beta
+    double *d_tile_hist = nullptr, *d_slot_h = nullptr, *d_H = nullptr;                                   // d_tile_hist owns ONE buffer: tile_hist | slot_h | H
+    char* h_nb[2] = {nullptr, nullptr}; hipEvent_t nb_ev[2] = {nullptr, nullptr}; bool nb_ev_used[2] = {false, false}; unsigned nb_turn = 0;   // pinned staging of those tables
+    double* h_part = nullptr; double* d_part_host = nullptr; size_t part_cap = 0;   // pinned partials [n_rw_blocks][NA] | [C] | flag word, their device address
     int8_t* h_label = nullptr;     // pinned [N]: staging of hf_get_labels, taken from the process's pinned cache on first use (1.5 MB of pinning = 0.15 ms of hf_create until round 5)
     int8_t* d_label_host = nullptr; // its device address (a kernel writes the labels there)
+    // the pinned block: result vector (+ flag word, stamp, checksums) | flag word of hf_check | parameter block
     double* h_total = nullptr;     // pinned [V+1]: reduced vector + flag word, one copy per pass
+    double* d_total_host = nullptr; // device address of the pinned h_total: k_reduce writes the result straight to the host
+    unsigned* h_flags = nullptr; DevParams* h_params = nullptr;
+    KParams kparams{};             // the parameter block as kernel arguments of k_tables (one region: pack_kparams)
+    bool kp_now = false;           // this pass uses them
+    // profiling
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool ev_valid = false;
     double ksum[HF_NKERNELS] = {}; int64_t kcount[HF_NKERNELS] = {};   // accumulated by hf_finish while profiling is on
     float klast[HF_NKERNELS] = {}; bool klast_ok[HF_NKERNELS] = {};      // the last pass's durations as hf_finish read them (hf_kernel_times returns these)
     unsigned prof_mask = 0;        // bit k: kernel k (HF_K_*) is bracketed by kev[2k], kev[2k+1]
     int prof_stride = 1; long prof_pass = 0; bool prof_now = true;   // events only in every prof_stride-th pass (hf_set_profiling_stride)
     hipEvent_t kev[2 * HF_NKERNELS] = {}; bool kran[HF_NKERNELS] = {};
-    bool have_full = false;
-    size_t lds_max = 64 * 1024;    // LDS one workgroup may use (hipDeviceAttributeMaxSharedMemoryPerBlock)
-    bool launch_failed = false;
-    double beta_star = 1.0;
-    // per-iteration emission rows (k_tables): keys = occurring (region, x, x_prev) of interior windows,
-    // slow = chunk-first and contig-end windows (beta != beta_star), ascending; slow_off[c] = chunk c's first entry
-    int M = 1; double* d_lutE = nullptr; double* d_lutC = nullptr; int64_t n_lut = 0;
-    int n_keys = 0; int32_t* d_keys = nullptr;
-    // negative_binomial model: device copies of hf_params.nb_* and the per-tile count data (allocated on first use)
-    double *d_nbE = nullptr, *d_nbP = nullptr, *d_nbDig = nullptr, *d_nbR = nullptr, *d_nbBeta = nullptr, *d_tile_hist = nullptr;   // d_nbE owns ONE buffer: E | P | dig | r | beta
-    char* h_nb[2] = {nullptr, nullptr}; hipEvent_t nb_ev[2] = {nullptr, nullptr}; bool nb_ev_used[2] = {false, false}; unsigned nb_turn = 0;   // pinned staging of those tables
-    // statistics by emission row (hf_rows.h): the static plan and its work arrays
-    int stats_mode = HF_STATS_CHUNKS; bool rows_ready = false, pass_rows = false; int pass_kc = 0, pass_wpb = 4;
-    double poll_seq = 0.0;         // completion stamp of the last polled pass (hf_finish)
-    // the total of a one-GPU pass summed by the HOST (hf_rows.h part_host): pinned partials [n_rw_blocks][NA] | [C] | flag word, their device address
-    double* h_part = nullptr; double* d_part_host = nullptr; size_t part_cap = 0; bool host_total_ok = true, pass_host_total = false; int pass_rw_blocks = 0;
-    std::vector<int32_t> h_rw_off;
-    double* d_rank_out = nullptr; double* d_rank_flag = nullptr;   // hf_bind_rank_total: where a rows-mode pass writes its total / flag word
-    bool pass_bound = false;       // the last pass wrote them there
-    bool stream_stamp_ok = true; uint32_t stream_stamp = 0;   // wait_total: completion through hipStreamWriteValue32 (HF_STREAM_STAMP=0: off)
-    bool pass_polled = false;      // the last rows-mode pass carried a stamp (decided at launch: k_row_stats writes the total itself)
-    unsigned* d_done = nullptr;    // k_reduce / k_row_stats: blocks finished (the last one sums the parts and stamps the host block)
-    unsigned long long* d_cks = nullptr;   // k_reduce: XOR of the words written (checksum of a polled pass)
-    int poll_kind = 0;             // what the last polled kernel was: 1 k_row_stats' total (a checksum per region), 2 k_reduce (one)
-    int n_groups = 0, n_rowwaves = 0, n_parts = 1;   // n_parts: regions that have a row, + 1 (the log-likelihood blocks): hf_rows.h hand-offs
-    bool pass_nb = false;          // the last rows-mode pass ran the negative_binomial kernels (hf_nb_rows.h)
-    int32_t* d_bin_off = nullptr; int32_t* d_bin_list = nullptr; double* d_slot_h = nullptr; double* d_H = nullptr;   // count-data plan
-    double* d_chunk_ll = nullptr;  // [C] log-likelihood per chunk (rows mode)
-    double* d_recs = nullptr;      // pair records { f_{t-1}, b_t } of k_seg_fb, plan order; fb_recs: the last full pass wrote them
-    bool fb_recs = false, pass_pairs_done = false;   // pass_pairs_done: enqueue_pass ran k_pair_sums itself (per sub-pass)
-    // SUB-PASSES (round 5): a context whose records would not fit the Infinity Cache (256 MB; BASELINE configs[2] writes 130 MB) cuts its
-    // chunk list into sub-passes of whole chunks; a pass runs k_seg_fb then k_pair_sums per sub-pass through ONE buffer that holds a
-    // sub-pass's positions [p0, p1) at a time (d_recs; the plan's groups are numbered sub-pass by sub-pass, so a sub-pass's records are
-    // contiguous) — the records never travel to HBM and back.  Everything that needs the records of ALL windows at once (the getters,
-    // per-chunk statistics) runs the segment kernel into d_recs_all instead (allocated on first use; = d_recs with one sub-pass).
-    struct SubPass { int c0, c1, seg0, seg1, g0, g1; int64_t p0, p1; int b0 = 0, b1 = 0; };   // b0, b1: its blocks in the XCD plan (d_seg_of_block)
-    std::vector<SubPass> subs;
-    double* d_recs_all = nullptr; bool recs_all = false;   // recs_all: d_recs_all holds the records of every window of the last full pass
-    bool scales_all = false;       // ... and d_scale_s its scales (an EM pass writes none: 8 of its 72 bytes per window that only
-                                   // hf_get_forward_backward reads — the getter runs the segment kernel again, with the array)
-    int32_t* d_grp_off = nullptr;     // compact plan: first position of every group (+ the end)
-    bool plan_compact = false;        // the groups' records back to back (sparse rows) instead of 64 positions per group
-    int rs_bpw = 1;                   // batches of 16 row slots per wavefront of k_row_stats
-    int32_t* d_grp_ar = nullptr; int32_t* d_grp_n = nullptr; double* d_grp_sums = nullptr;   // per group: its row of A, its pairs
-    int32_t* d_pos_f = nullptr;    // [N] position of the record that holds every window's f (getters)
-    int32_t* d_slot_of = nullptr;  // window -> slot, built from h_segs and uploaded by the first getter call
-    int32_t* d_pos = nullptr; int64_t n_pos = 0;   // [N] position of every window's pair record in d_recs (plan order; slot order without a plan)
-    RowSlot* d_rowslots = nullptr; int32_t* d_rw_region = nullptr; int32_t* d_rw_off = nullptr; double* d_rw_stats = nullptr;
-    // segment kernels (hf_seg.h): the forward-backward of the statistics-by-row path
-    SegDesc* d_seg = nullptr; int nseg = 0; int32_t* d_chunk_seg0 = nullptr; double* d_seg_ll = nullptr; double* d_Pseg = nullptr;
-    double* d_segQ = nullptr;          // [nseg][8][64] double2: lane products, lane-minor (two-launch mode only: allocated on first use)
-    // one-launch mode (hf_seg.h): k_seg_fb computes the lane products itself and the segments of a chunk hand their products to
-    // each other inside the launch (flags stamped with the launch's epoch); a timed-out wait switches the context to two launches
-    unsigned* d_seg_ready = nullptr; unsigned seg_epoch = 0; bool seg_fused = true, seg_test_timeout = false;
-    int seg_nc = 0;                    // row blocks a segment workgroup keeps in LDS across its three walks (hf_seg.h: chosen so that all segments stay resident)
-    // XCD plan (round 6): block b of k_seg_fb runs segment seg_of_block[b]; the segments of a chunk sit on block indices congruent mod 8
-    // (observed: block b runs on XCD b % 8 — for speed only, the hand-off protocol is system-scope whatever the placement).  Null: identity.
-    int32_t* d_seg_of_block = nullptr; std::vector<int32_t> h_seg_of_block;
+    // what the last pass was and did
     hf_params last_p{}; int last_mode = HF_MODE_FULL;   // what the last hf_estep was given (the fallback re-runs the pass)
     hipStream_t last_stream = nullptr;                  // ... and the stream it ran on (the getters' re-run of the segment kernel goes there)
-    // rows of A_t = T_t∘e_t (hf_seg.h): one per (emission key, transition class) that occurs at an interior window, then one
-    // per slow window; d_arow[t] = the row of window t (bit 31: chunk-first), d_arow_src / d_arow_cls = where a row comes from
-    int32_t* d_arow = nullptr; int32_t* d_arow_src = nullptr; int32_t* d_arow_cls = nullptr; double* d_lutA = nullptr;
-    int n_arows = 0, n_combo = 0;
-    double* d_scale_s = nullptr; int64_t n_slots = 0;
-    std::vector<SegDesc> h_segs;                // the segment descriptors (the getters derive a window's slot from them)
-    std::vector<int32_t> h_cseg0;               // first segment of every chunk (+ the end)
-    std::vector<std::pair<const char*, double>> create_phases;   // hf_create_phases
-    bool pass_seg = false;             // the last pass ran the segment kernels (log-likelihood partials per segment)
-    unsigned long long* d_seg_trace = nullptr;   // -DHF_SEG_TRACE builds only
-    int n_slow = 0; int64_t* d_slow_w = nullptr; int32_t* d_slow_off = nullptr; double* d_Es = nullptr; double* d_Cs = nullptr;
-    // most-probable-path decoding (hf_viterbi.h): buffers of its own, allocated by the first hf_viterbi, never shared with a pass
-    struct Viterbi {
-        DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
-        double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
-        uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
-        int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr; unsigned* d_flags = nullptr;
-        double* d_P = nullptr; int* d_PE = nullptr; double* d_S = nullptr; int* d_SE = nullptr;   // SCAN: phase A
-        double* d_vin = nullptr; long long* d_vinE = nullptr;                                      // SCAN: phase B
-        uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;          // SCAN: phases C, D
-        bool alloc = false, launched = false, done = false;
-        std::vector<double> h_ll;                  // chunk scores of the last finished run
-    } vit;
+    bool have_full = false, launch_failed = false;
+    bool pass_seg = false;         // the last pass ran the segment kernels (log-likelihood partials per segment)
+    bool pass_rows = false; int pass_kc = 0, pass_wpb = 4;
+    bool pass_nb = false;          // the last rows-mode pass ran the negative_binomial kernels (hf_nb_rows.h)
+    bool pass_host_total = false; int pass_rw_blocks = 0;
+    bool pass_polled = false;      // the last rows-mode pass carried a stamp (decided at launch: k_row_stats writes the total itself)
+    int poll_kind = 0;             // what the last polled kernel was: 1 k_row_stats' total (a checksum per region), 2 k_reduce (one)
+    double poll_seq = 0.0;         // completion stamp of the last polled pass (hf_finish)
+    uint32_t stream_stamp = 0;
+    double* d_rank_out = nullptr; double* d_rank_flag = nullptr;   // hf_bind_rank_total: where a rows-mode pass writes its total / flag word
+    bool pass_bound = false;       // the last pass wrote them there
+    bool fb_recs = false, pass_pairs_done = false;   // pass_pairs_done: enqueue_pass ran k_pair_sums itself (per sub-pass)
+    bool recs_all = false;         // d_recs_all holds the records of every window of the last full pass
+    bool scales_all = false;       // ... and d_scale_s its scales (an EM pass writes none: 8 of its 72 bytes per window that only
+                                   // hf_get_forward_backward reads — the getter runs the segment kernel again, with the array)
+    unsigned seg_epoch = 0;        // hand-off flags of the one-launch segment kernel are stamped with the launch's epoch
 };
 
-static int cseg0_of(const hf_ctx* ctx, int c) { return ctx->h_cseg0[(size_t) c]; }
-static void* ctx_alloc(hf_ctx* ctx, size_t bytes) {
-    bytes = (bytes ? bytes : 8);
-    bytes = (bytes + 255) & ~(size_t) 255;
-    if (bytes > ctx->slab_left) {
-        const size_t want = std::max(bytes, ctx->slabs.empty() ? ctx->slab_first : (size_t) 64 << 20);
-        char* p = nullptr;
-        if (hipMalloc((void**) &p, want) != hipSuccess) {
-            (void) hipGetLastError();
-            if (want == bytes || hipMalloc((void**) &p, bytes) != hipSuccess) return nullptr;   // (a smaller slab: just this request)
-            ctx->slabs.emplace_back(p, bytes);
-            return p;                                                                         // (the current slab keeps its remainder)
-        }
-        ctx->slabs.emplace_back(p, want);
-        ctx->slab_cur = p; ctx->slab_left = want;
-    }
-    char* r = ctx->slab_cur;
-    ctx->slab_cur += bytes; ctx->slab_left -= bytes;
-    return r;
-}
-static void ctx_free(hf_ctx* ctx, void* p) {          // hipFree unless the pointer lives in a slab
-    if (!p) return;
-    for (const auto& sl : ctx->slabs)
-        if ((char*) p >= sl.first && (char*) p < sl.first + sl.second) return;
-    hipFree(p);
-}
+// most-probable-path decoding (hf_viterbi.h): buffers of its own, allocated by the first hf_viterbi, never shared with a pass
+struct Viterbi {
+    DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
+    double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
+    uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
+    int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr; unsigned* d_flags = nullptr;
+    double* d_P = nullptr; int* d_PE = nullptr; double* d_S = nullptr; int* d_SE = nullptr;   // SCAN: phase A
+    double* d_vin = nullptr; long long* d_vinE = nullptr;                                      // SCAN: phase B
+    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;          // SCAN: phases C, D
+    bool alloc = false, launched = false, done = false;
+    std::vector<double> h_ll;                  // chunk scores of the last finished run
+};
+
+// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoder's buffers
+struct hf_ctx {
+    Track tr;
+    Pass pass;
+    Viterbi vit;
+};
 
 // ------------------------------------------------------------------------------------------
 // setup: packed records + contig-end factor beta (hmm.c:301-316), once per run
@@ -515,31 +546,33 @@ __global__ void k_pos_f(const int64_t* __restrict__ off, const int32_t* __restri
 // host side of the C ABI
 // ------------------------------------------------------------------------------------------
 // the event pair around a whole pass (hf_last_kernel_ms) costs two extra packets per step: only while profiling is on
-static bool pass_events(const hf_ctx* ctx) {
-    return (ctx->prof_mask & HF_PROF_PASS) != 0 || ctx->host_trace;
+static bool pass_events(const Pass& ps) {
+    return (ps.prof_mask & HF_PROF_PASS) != 0 || ps.host_trace;
 }
 
-// small uploads of hf_create: out of the context's slab, through a pinned staging area when there is room (memcpy + ASYNCHRONOUS copy on the
-// null stream: hf_create synchronises once, at its end) — a hipMalloc and a synchronous copy out of pageable memory per array were ~30 us each
+// small uploads of hf_create: through a pinned staging area when there is room (memcpy + ASYNCHRONOUS copy on the null stream: hf_create
+// synchronises once, at its end) — a hipMalloc and a synchronous copy out of pageable memory per array were ~30 us each
 struct UploadStage { char* p = nullptr; size_t cap = 0, used = 0; };
-template <typename T>
-static int dev_upload(hf_ctx* ctx, UploadStage& stg, T** dst, const T* src, size_t n) {
-    *dst = static_cast<T*>(ctx_alloc(ctx, (n ? n : 1) * sizeof(T)));
-    if (!*dst) return set_err(HF_E_HIP, "hf_create: out of device memory");
-    if (!n) return 0;
-    const size_t bytes = n * sizeof(T), need = (bytes + 63) & ~(size_t) 63;
-    if (stg.p && stg.used + need <= stg.cap) {
-        std::memcpy(stg.p + stg.used, src, bytes);
-        HIPCHK(hipMemcpyAsync(*dst, stg.p + stg.used, bytes, hipMemcpyHostToDevice, nullptr));
-        stg.used += need;
-    } else HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+static int stage_upload(UploadStage* stg, void* dst, const void* src, size_t bytes) {
+    const size_t need = (bytes + 63) & ~(size_t) 63;
+    if (stg && stg->p && stg->used + need <= stg->cap) {
+        std::memcpy(stg->p + stg->used, src, bytes);
+        HIPCHK(hipMemcpyAsync(dst, stg->p + stg->used, bytes, hipMemcpyHostToDevice, nullptr));
+        stg->used += need;
+    } else HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return 0;
+}
+template <typename T>
+static int dev_upload(Slab& slab, UploadStage& stg, T** dst, const T* src, size_t n) {
+    *dst = static_cast<T*>(slab.alloc((n ? n : 1) * sizeof(T)));
+    if (!*dst) return set_err(HF_E_HIP, "hf_create: out of device memory");
+    return n ? stage_upload(&stg, *dst, src, n * sizeof(T)) : 0;
 }
 
 // event pair around one kernel launch, only for the kernels selected by hf_set_profiling
 struct KTimer {
-    hf_ctx* c; hipStream_t st; int k; bool on;
-    KTimer(hf_ctx* c_, hipStream_t s_, int k_) : c(c_), st(s_), k(k_), on(((c_->prof_mask >> k_) & 1u) && c_->prof_now) {
+    Pass* c; hipStream_t st; int k; bool on;
+    KTimer(Pass& c_, hipStream_t s_, int k_) : c(&c_), st(s_), k(k_), on(((c_.prof_mask >> k_) & 1u) && c_.prof_now) {
         if (on) hipEventRecord(c->kev[2 * k], st);
     }
     ~KTimer() { if (on) { hipEventRecord(c->kev[2 * k + 1], st); c->kran[k] = true; } }
@@ -550,37 +583,38 @@ struct KTimer {
 // default 64 KiB is requested explicitly.
 struct TileGeom { unsigned blocks = 0, threads = 256; size_t lds = 0; bool ok = false; };
 template <class Kern>
-static TileGeom tile_geom(const hf_ctx* ctx, Kern kernel, size_t per_wave_bytes, bool with_tab = true, int wmax = 4) {
+static TileGeom tile_geom(const Track& tr, Kern kernel, size_t per_wave_bytes, bool with_tab = true, int wmax = 4) {
     TileGeom g;
-    const size_t tab = with_tab ? (size_t) ctx->R * HF_TAB_STRIDE * 8 : 0;
+    const size_t tab = with_tab ? (size_t) tr.R * HF_TAB_STRIDE * 8 : 0;
     int w = wmax;
-    while (w >= 1 && tab + (size_t) w * per_wave_bytes > ctx->lds_max) w--;
+    while (w >= 1 && tab + (size_t) w * per_wave_bytes > tr.lds_max) w--;
     if (w < 1) return g;
     g.threads = 64u * (unsigned) w;
-    g.blocks = (unsigned) ((ctx->ntiles + w - 1) / w);
+    g.blocks = (unsigned) ((tr.ntiles + w - 1) / w);
     g.lds = tab + (size_t) w * per_wave_bytes;
     g.ok = true;
     if (g.lds > 64 * 1024)
         g.ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) g.lds) == hipSuccess;
     return g;
 }
-#define TILE_GEOM_OR_FAIL(g) do { if (!(g).ok) { set_err(HF_E_ARG, "the per-region tables do not fit the LDS of one workgroup"); ctx->launch_failed = true; return; } } while (0)
+#define TILE_GEOM_OR_FAIL(g) do { if (!(g).ok) { set_err(HF_E_ARG, "the per-region tables do not fit the LDS of one workgroup"); ps.launch_failed = true; return; } } while (0)
 
-static RowSrc row_src(const hf_ctx* ctx) {
+static RowSrc row_src(const Pass& ps) {
+    const Track& tr = *ps.tr;
     RowSrc S;
-    S.lutE = ctx->d_lutE; S.lutC = ctx->d_lutC; S.Es = ctx->d_Es; S.Cs = ctx->d_Cs; S.M = ctx->M; S.K = ctx->K; S.n_lut = (int) ctx->n_lut;
+    S.lutE = ps.d_lutE; S.lutC = ps.d_lutC; S.Es = ps.d_Es; S.Cs = ps.d_Cs; S.M = tr.M; S.K = tr.K; S.n_lut = (int) tr.n_lut;
     return S;
 }
 
 // where the log-likelihood partials of the last forward pass are: per segment (hf_seg.h) or per tile (hf_scan.h)
-static const int32_t* ll_off(const hf_ctx* ctx) { return ctx->pass_seg ? ctx->d_chunk_seg0 : ctx->d_chunk_tile0; }
-static const double* ll_part(const hf_ctx* ctx) { return ctx->pass_seg ? ctx->d_seg_ll : ctx->d_tile_ll; }
+static const int32_t* ll_off(const Pass& ps) { return ps.pass_seg ? ps.tr->d_chunk_seg0 : ps.tr->d_chunk_tile0; }
+static const double* ll_part(const Pass& ps) { return ps.pass_seg ? ps.d_seg_ll : ps.d_tile_ll; }
 
 // HF_ALGO_SCAN runs the segment kernels (hf_seg.h) whatever the statistics path
-static bool seg_pass(const hf_ctx* ctx) { return ctx->algo == HF_ALGO_SCAN && ctx->nseg > 0; }
+static bool seg_pass(const Track& tr) { return tr.algo == HF_ALGO_SCAN && tr.nseg > 0; }
 
 // does a full pass of the Gaussian models take the statistics-by-row path?
-static bool rows_pass(const hf_ctx* ctx) { return ctx->stats_mode == HF_STATS_ROWS && ctx->rows_ready && ctx->algo == HF_ALGO_SCAN; }
+static bool rows_pass(const Pass& ps) { return ps.stats_mode == HF_STATS_ROWS && ps.tr->rows_ready && ps.tr->algo == HF_ALGO_SCAN; }
 
 // polled completion of a pass: see wait_total
 static int poll_mode() {
@@ -592,131 +626,135 @@ static int poll_mode() {
     }();
     return mode;
 }
-static bool poll_ok(const hf_ctx* ctx, int last_kernel) {
-    return poll_mode() != 0 && ctx->d_total_host && !((ctx->prof_mask >> last_kernel) & 1u) && !(ctx->prof_mask & HF_PROF_PASS) &&
-           !ctx->host_trace;
+static bool poll_ok(const Pass& ps, int last_kernel) {
+    return poll_mode() != 0 && ps.d_total_host && !((ps.prof_mask >> last_kernel) & 1u) && !(ps.prof_mask & HF_PROF_PASS) &&
+           !ps.host_trace;
 }
-static double next_stamp(hf_ctx* ctx) { ctx->poll_seq += 1.0; ctx->h_total[ctx->V + 1] = 0.0; return ctx->poll_seq; }
+static double next_stamp(Pass& ps) { ps.poll_seq += 1.0; ps.h_total[ps.tr->V + 1] = 0.0; return ps.poll_seq; }
 
 // the groups' sums of f (x) b, times their row of A: padded plan (whole groups streamed) or compact plan (hf_create)
-// the groups of ONE sub-pass (hf_ctx::SubPass): padded plan — whole groups streamed from the sub-pass's first position on; compact plan — the
+// the groups of ONE sub-pass (Track::SubPass): padded plan — whole groups streamed from the sub-pass's first position on; compact plan — the
 // groups' own (global) positions.  recs_eff: the address position 0 would have (a pass buffer that holds one sub-pass starts p0 records later)
-static void launch_pair_sums(hf_ctx* ctx, hipStream_t st, const hf_ctx::SubPass& sb, const double* recs_eff) {
+static void launch_pair_sums(Pass& ps, hipStream_t st, const Track::SubPass& sb, const double* recs_eff) {
+    const Track& tr = *ps.tr;
     const int n = sb.g1 - sb.g0;
     if (n <= 0) return;
-    if (ctx->plan_compact)
-        hipLaunchKernelGGL(k_pair_sums_compact, dim3((unsigned) ((n + 63) / 64)), dim3(256), 0, st, n, ctx->d_grp_ar + sb.g0, ctx->d_grp_off + sb.g0,
-                           ctx->d_grp_n + sb.g0, ctx->d_lutA, recs_eff, ctx->d_grp_sums + (size_t) sb.g0 * 16);
+    if (tr.plan_compact)
+        hipLaunchKernelGGL(k_pair_sums_compact, dim3((unsigned) ((n + 63) / 64)), dim3(256), 0, st, n, tr.d_grp_ar + sb.g0, tr.d_grp_off + sb.g0,
+                           tr.d_grp_n + sb.g0, ps.d_lutA, recs_eff, ps.d_grp_sums + (size_t) sb.g0 * 16);
     else
-        hipLaunchKernelGGL(k_pair_sums, dim3((unsigned) ((n + 15) / 16)), dim3(256), 0, st, n, ctx->d_grp_ar + sb.g0, ctx->d_grp_n + sb.g0,
-                           ctx->d_lutA, recs_eff + sb.p0 * 8, ctx->d_grp_sums + (size_t) sb.g0 * 16);
+        hipLaunchKernelGGL(k_pair_sums, dim3((unsigned) ((n + 15) / 16)), dim3(256), 0, st, n, tr.d_grp_ar + sb.g0, tr.d_grp_n + sb.g0,
+                           ps.d_lutA, recs_eff + sb.p0 * 8, ps.d_grp_sums + (size_t) sb.g0 * 16);
 }
 
 // k_seg_fb over the segments [g0, g0 + n) (hf_seg.h); timed: by the dispatch's own start / stop timestamps (hipExtLaunchKernelGGL hands the two
 // events to the launch: what rocprofv3 reports for the kernel, without the two marker packets of an event pair around it — those measured 3 us
 // more than the kernel and cost the step ~15 us)
 // sub >= 0: the segments of that sub-pass; < 0: all segments
-static void launch_seg_fb(hf_ctx* ctx, hipStream_t st, bool full, double* recs_eff, int sub, unsigned epoch, unsigned wait_epoch, bool timed, bool with_scales = true) {
-    int g0 = sub >= 0 ? ctx->subs[(size_t) sub].seg0 : 0, n = sub >= 0 ? ctx->subs[(size_t) sub].seg1 - g0 : ctx->nseg;
-    const int32_t* const sob = ctx->seg_fused ? ctx->d_seg_of_block : nullptr;   // (the XCD plan: one-launch mode only — two launches have no hand-off inside the launch)
+static void launch_seg_fb(Pass& ps, hipStream_t st, bool full, double* recs_eff, int sub, unsigned epoch, unsigned wait_epoch, bool timed, bool with_scales = true) {
+    const Track& tr = *ps.tr;
+    int g0 = sub >= 0 ? tr.subs[(size_t) sub].seg0 : 0, n = sub >= 0 ? tr.subs[(size_t) sub].seg1 - g0 : tr.nseg;
+    const int32_t* const sob = ps.seg_fused ? tr.d_seg_of_block : nullptr;   // (the XCD plan: one-launch mode only — two launches have no hand-off inside the launch)
     if (sob) {       // blocks of the plan instead of segments (a sub-pass's blocks are contiguous, and so are all of them)
-        g0 = sub >= 0 ? ctx->subs[(size_t) sub].b0 : 0;
-        n = (sub >= 0 ? ctx->subs[(size_t) sub].b1 : ctx->subs.back().b1) - g0;
+        g0 = sub >= 0 ? tr.subs[(size_t) sub].b0 : 0;
+        n = (sub >= 0 ? tr.subs[(size_t) sub].b1 : tr.subs.back().b1) - g0;
     }
     if (n <= 0) return;
-    const int nc = ctx->seg_fused ? ctx->seg_nc : 0;     // cached row blocks: one-launch mode only (the lane products are computed in the same kernel)
+    const int nc = ps.seg_fused ? tr.seg_nc : 0;     // cached row blocks: one-launch mode only (the lane products are computed in the same kernel)
     const size_t lds = seg_lds_bytes(nc);
-#define HF_SEG_FB_ARGS ctx->d_seg, ctx->d_arow, ctx->d_lutA, ctx->d_params, ctx->d_segQ, ctx->d_Pseg, ctx->d_seg_ready, epoch, wait_epoch, ctx->d_pos, recs_eff, \
-                        with_scales ? ctx->d_scale_s : (double*) nullptr, ctx->d_label, ctx->d_seg_ll, ctx->d_flags, (int32_t) g0, nc, sob
+#define HF_SEG_FB_ARGS tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_params, ps.d_segQ, ps.d_Pseg, ps.d_seg_ready, epoch, wait_epoch, tr.d_pos, recs_eff, \
+                        with_scales ? ps.d_scale_s : (double*) nullptr, ps.d_label, ps.d_seg_ll, ps.d_flags, (int32_t) g0, nc, sob
 #define HF_SEG_FB_LAUNCH(B, F, CA) do { \
         if (timed) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_fb<B, F, CA>), dim3((unsigned) n), dim3(64), (uint32_t) lds, st, \
-                                         ctx->kev[2 * HF_K_SEG_FB], ctx->kev[2 * HF_K_SEG_FB + 1], 0, HF_SEG_FB_ARGS); \
+                                         ps.kev[2 * HF_K_SEG_FB], ps.kev[2 * HF_K_SEG_FB + 1], 0, HF_SEG_FB_ARGS); \
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_fb<B, F, CA>), dim3((unsigned) n), dim3(64), lds, st, HF_SEG_FB_ARGS); } while (0)
     if (nc > 0) { if (full) HF_SEG_FB_LAUNCH(true, true, true); else HF_SEG_FB_LAUNCH(false, true, true); }
-    else if (full) { if (ctx->seg_fused) HF_SEG_FB_LAUNCH(true, true, false); else HF_SEG_FB_LAUNCH(true, false, false); }
-    else { if (ctx->seg_fused) HF_SEG_FB_LAUNCH(false, true, false); else HF_SEG_FB_LAUNCH(false, false, false); }
+    else if (full) { if (ps.seg_fused) HF_SEG_FB_LAUNCH(true, true, false); else HF_SEG_FB_LAUNCH(true, false, false); }
+    else { if (ps.seg_fused) HF_SEG_FB_LAUNCH(false, true, false); else HF_SEG_FB_LAUNCH(false, false, false); }
 #undef HF_SEG_FB_LAUNCH
 #undef HF_SEG_FB_ARGS
 }
 
 // the buffer that holds the records of ALL windows (one sub-pass: the pass buffer itself)
-static int all_records_buffer(hf_ctx* ctx) {
-    if (ctx->d_recs_all) return HF_OK;
+static int all_records_buffer(Pass& ps) {
+    if (ps.d_recs_all) return HF_OK;
     int64_t n_pos = 0;
-    for (const auto& sb : ctx->subs) if (sb.p1 > n_pos) n_pos = sb.p1;
-    HIPCHK(hipMalloc((void**) &ctx->d_recs_all, (size_t) (n_pos + 1) * 64));
+    for (const auto& sb : ps.tr->subs) if (sb.p1 > n_pos) n_pos = sb.p1;
+    HIPCHK(hipMalloc((void**) &ps.d_recs_all, (size_t) (n_pos + 1) * 64));
     return HF_OK;
 }
 
 template <int KT>
-static void launch_stats(hf_ctx* ctx, hipStream_t st, int full, int ncol) {
-    ctx->pass_rows = false; ctx->pass_host_total = false;
-    if (full && rows_pass(ctx)) {
+static void launch_stats(Pass& ps, hipStream_t st, int full, int ncol) {
+    const Track& tr = *ps.tr;
+    ps.pass_rows = false; ps.pass_host_total = false;
+    if (full && rows_pass(ps)) {
         // statistics by emission row (hf_rows.h); the total of the pass comes out of k_row_stats' last blocks
         // (k_pair_sums ran behind every sub-pass's k_seg_fb: enqueue_pass)
-        KTimer t(ctx, st, HF_K_ROW_STATS);
-        constexpr size_t NA = 16 + 9 + 2 + 3 * KT + 1;
+        KTimer t(ps, st, HF_K_ROW_STATS);
+        constexpr size_t NA = stat_acc_len(KT);
         // the wavefronts' sums: HF_RS_WPB wavefronts per block (a block stays inside one region: hf_create pads the regions to that multiple) — four
         // for a sparse plan, whose wavefronts take several batches of slots each: eight of those per block ran config 5 in 83 us instead of 51
-        const int want_wpb = ctx->rs_bpw > 1 ? 4 : HF_RS_WPB;
-        TileGeom g = tile_geom(ctx, k_row_stats<KT>, NA * 8, false, want_wpb);
+        const int want_wpb = tr.rs_bpw > 1 ? 4 : HF_RS_WPB;
+        TileGeom g = tile_geom(tr, k_row_stats<KT>, NA * 8, false, want_wpb);
         TILE_GEOM_OR_FAIL(g);
-        if ((int) g.threads != 64 * want_wpb) { set_err(HF_E_ARG, "k_row_stats: the block's partial sums do not fit the LDS"); ctx->launch_failed = true; return; }
+        if ((int) g.threads != 64 * want_wpb) { set_err(HF_E_ARG, "k_row_stats: the block's partial sums do not fit the LDS"); ps.launch_failed = true; return; }
         const int wpb = (int) g.threads / 64;
-        const int n_rw_blocks = (ctx->n_rowwaves + wpb - 1) / wpb, n_ll_blocks = (ctx->C + wpb - 1) / wpb;
+        const int n_rw_blocks = (tr.n_rowwaves + wpb - 1) / wpb, n_ll_blocks = (tr.C + wpb - 1) / wpb;
         // the launch's last block also sums the partials (rows_total): into d_total and straight into the pinned host block
-        const bool bound = ctx->d_rank_out != nullptr;    // multi-GPU `ranks` exchange: the total goes into the exchange buffer, not to the host
-        const bool polled = !bound && poll_ok(ctx, HF_K_ROW_STATS);
-        const double seq = polled ? next_stamp(ctx) : 0.0;
-        ctx->pass_polled = polled; ctx->pass_bound = bound;
+        const bool bound = ps.d_rank_out != nullptr;    // multi-GPU `ranks` exchange: the total goes into the exchange buffer, not to the host
+        const bool polled = !bound && poll_ok(ps, HF_K_ROW_STATS);
+        const double seq = polled ? next_stamp(ps) : 0.0;
+        ps.pass_polled = polled; ps.pass_bound = bound;
         // one GPU, nobody polling, nothing bound: the blocks' partial vectors go to pinned host memory and the HOST sums them (host_rows_total)
-        bool host_total = !bound && !polled && ctx->host_total_ok && ctx->d_total_host != nullptr;
+        bool host_total = !bound && !polled && ps.host_total_ok && ps.d_total_host != nullptr;
         if (host_total) {
-            const size_t need = (size_t) n_rw_blocks * NA + (size_t) ctx->C + 1;
-            if (need > ctx->part_cap) {
-                if (ctx->h_part) hipHostFree(ctx->h_part);
-                ctx->h_part = nullptr; ctx->d_part_host = nullptr; ctx->part_cap = 0;
+            const size_t need = (size_t) n_rw_blocks * NA + (size_t) tr.C + 1;
+            if (need > ps.part_cap) {
+                if (ps.h_part) hipHostFree(ps.h_part);
+                ps.h_part = nullptr; ps.d_part_host = nullptr; ps.part_cap = 0;
                 void* dp = nullptr;
-                if (hipHostMalloc((void**) &ctx->h_part, (need + 64) * 8) == hipSuccess && hipHostGetDevicePointer(&dp, ctx->h_part, 0) == hipSuccess) {
-                    ctx->d_part_host = (double*) dp; ctx->part_cap = need + 64;
-                } else { (void) hipGetLastError(); if (ctx->h_part) hipHostFree(ctx->h_part); ctx->h_part = nullptr; ctx->host_total_ok = false; host_total = false; }
+                if (hipHostMalloc((void**) &ps.h_part, (need + 64) * 8) == hipSuccess && hipHostGetDevicePointer(&dp, ps.h_part, 0) == hipSuccess) {
+                    ps.d_part_host = (double*) dp; ps.part_cap = need + 64;
+                } else { (void) hipGetLastError(); if (ps.h_part) hipHostFree(ps.h_part); ps.h_part = nullptr; ps.host_total_ok = false; host_total = false; }
             }
         }
-        ctx->pass_host_total = host_total; ctx->pass_rw_blocks = n_rw_blocks;
+        ps.pass_host_total = host_total; ps.pass_rw_blocks = n_rw_blocks;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_row_stats<KT>), dim3((unsigned) (n_rw_blocks + n_ll_blocks)), dim3(g.threads), g.lds, st,
-                           ctx->n_rowwaves, n_rw_blocks, ctx->d_rw_region, ctx->d_rowslots, ctx->d_grp_sums, row_src(ctx), ctx->d_params,
-                           ctx->d_rw_stats, ctx->C, ll_off(ctx), ll_part(ctx), ctx->d_chunk_stats, ctx->V, ctx->d_chunk_ll,
-                           ctx->d_rw_off, ctx->K, bound ? ctx->d_rank_out : ctx->d_total, bound ? (double*) nullptr : ctx->d_total_host,
-                           bound ? ctx->d_rank_flag : (double*) nullptr, ctx->d_flags, seq, ctx->d_done, ctx->n_parts, ctx->rs_bpw,
-                           host_total ? ctx->d_part_host : (double*) nullptr);
-        ctx->pass_wpb = wpb;
-        ctx->pass_rows = true;
-        ctx->pass_kc = ncol;
+                           tr.n_rowwaves, n_rw_blocks, tr.d_rw_region, tr.d_rowslots, ps.d_grp_sums, row_src(ps), ps.d_params,
+                           ps.d_rw_stats, tr.C, ll_off(ps), ll_part(ps), ps.d_chunk_stats, tr.V, ps.d_chunk_ll,
+                           tr.d_rw_off, tr.K, bound ? ps.d_rank_out : ps.d_total, bound ? (double*) nullptr : ps.d_total_host,
+                           bound ? ps.d_rank_flag : (double*) nullptr, ps.d_flags, seq, ps.d_done, tr.n_parts, tr.rs_bpw,
+                           host_total ? ps.d_part_host : (double*) nullptr);
+        ps.pass_wpb = wpb;
+        ps.pass_rows = true;
+        ps.pass_kc = ncol;
         return;
     }
     if (full) {
-        KTimer t(ctx, st, HF_K_STATS_TILE);
-        const TileGeom g = tile_geom(ctx, k_stats_tile<KT>, (size_t) (3 * ncol > 28 ? 3 * ncol : 28) * 65 * 8);
+        KTimer t(ps, st, HF_K_STATS_TILE);
+        const TileGeom g = tile_geom(tr, k_stats_tile<KT>, (size_t) (3 * ncol > 28 ? 3 * ncol : 28) * 65 * 8);
         TILE_GEOM_OR_FAIL(g);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stats_tile<KT>), dim3(g.blocks), dim3(g.threads), g.lds, st, ctx->ntiles,
-                           ctx->d_tile_desc, ctx->d_rec, row_src(ctx), ctx->d_params, ctx->pass_seg ? ctx->d_recs_all : ctx->d_f, ctx->d_b, ctx->d_regmask,
-                           ctx->d_tile_stats, ctx->pass_seg ? ctx->d_pos : (const int32_t*) nullptr);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stats_tile<KT>), dim3(g.blocks), dim3(g.threads), g.lds, st, tr.ntiles,
+                           tr.d_tile_desc, tr.d_rec, row_src(ps), ps.d_params, ps.pass_seg ? ps.d_recs_all : ps.d_f, ps.d_b, tr.d_regmask,
+                           ps.d_tile_stats, ps.pass_seg ? tr.d_pos : (const int32_t*) nullptr);
     }
-    KTimer t(ctx, st, HF_K_CHUNK_STATS);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chunk_stats<KT>), dim3((unsigned) ctx->C), dim3(128), 0, st, ctx->d_chunk_tile0, ll_off(ctx),
-                       ctx->d_regmask, ctx->d_tile_stats, ll_part(ctx), ctx->d_params, ctx->d_chunk_stats, ctx->V, ctx->K,
+    KTimer t(ps, st, HF_K_CHUNK_STATS);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chunk_stats<KT>), dim3((unsigned) tr.C), dim3(128), 0, st, tr.d_chunk_tile0, ll_off(ps),
+                       tr.d_regmask, ps.d_tile_stats, ll_part(ps), ps.d_params, ps.d_chunk_stats, tr.V, tr.K,
                        full);
 }
 
 // the last kernel of a negative_binomial pass in HF_STATS_ROWS mode: total vector (+ flag word) into `out`
 // (the Gaussian models' total is written by the last block of k_row_stats itself: hf_rows.h rows_total)
-static int launch_nb_total(hf_ctx* ctx, hipStream_t st, double* out, bool with_flags = true, double seq = 0.0) {
-    KTimer t(ctx, st, HF_K_ROWS_TOTAL);
+static int launch_nb_total(Pass& ps, hipStream_t st, double* out, bool with_flags = true, double seq = 0.0) {
+    const Track& tr = *ps.tr;
+    KTimer t(ps, st, HF_K_ROWS_TOTAL);
     NbTables nt;
-    nt.E = ctx->d_nbE; nt.P = ctx->d_nbP; nt.dig = ctx->d_nbDig; nt.r = ctx->d_nbR; nt.beta = ctx->d_nbBeta;
-    hipLaunchKernelGGL(k_nb_total, dim3((unsigned) ctx->R), dim3(1024), 0, st, ctx->d_rw_off, ctx->pass_wpb, ctx->d_rw_stats, ctx->d_H,
-                       ctx->d_params, nt, ctx->d_chunk_ll, (int64_t) ctx->C, ctx->V, ctx->K, out,
-                       with_flags ? ctx->d_flags : (const unsigned*) nullptr, seq, ctx->d_done);
+    nt.E = ps.d_nbE; nt.P = ps.d_nbP; nt.dig = ps.d_nbDig; nt.r = ps.d_nbR; nt.beta = ps.d_nbBeta;
+    hipLaunchKernelGGL(k_nb_total, dim3((unsigned) tr.R), dim3(1024), 0, st, tr.d_rw_off, ps.pass_wpb, ps.d_rw_stats, ps.d_H,
+                       ps.d_params, nt, ps.d_chunk_ll, (int64_t) tr.C, tr.V, tr.K, out,
+                       with_flags ? ps.d_flags : (const unsigned*) nullptr, seq, ps.d_done);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -738,6 +776,120 @@ __global__ void k_gather_fb(int64_t first, int64_t n, const int32_t* __restrict_
 #pragma unroll
     for (int s = 0; s < 4; s++) { f[i * 4 + s] = rf[s]; b[i * 4 + s] = rb[s]; }
     sc[i] = scale_s[slot_of[t]];
+}
+
+// Every per-pass device array of a track in bytes (0: the track has no use for it), and the pinned block: the ONE place that sizes a pass
+// (pass_create allocates it, hf_batch_capacity counts it)
+struct PassLayout {
+    size_t label, chunk_stats, total, flags, done, cks, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg, recs,
+           grp_sums, chunk_ll, rw_stats, E, f, b, scale;
+    size_t pin_total, pin_block;   // pinned: result vector (+ flag word, stamp, checksums) | flag word of hf_check | parameter block
+    size_t device_bytes() const {
+        size_t s = 0;
+        for (size_t x : {label, chunk_stats, total, flags, done, cks, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg,
+                         recs, grp_sums, chunk_ll, rw_stats, E, f, b, scale})
+            if (x) s += Slab::granule(x);
+        return s;
+    }
+};
+static PassLayout pass_layout(const Track& tr) {
+    PassLayout L{};
+    const size_t N = (size_t) tr.N, C = (size_t) tr.C, V = (size_t) tr.V, nt = (size_t) tr.ntiles, ns = (size_t) tr.nseg;
+    const size_t rows = (size_t) tr.n_lut + (size_t) tr.n_slow + 1;   // emission rows: the keys, the slow windows, one row of padding
+    auto some = [](size_t bytes) { return bytes ? bytes : 1; };      // (allocated even when empty)
+    L.label = N + 16; L.chunk_stats = some(C * V * 8); L.total = (V + 1) * 8; L.flags = 4; L.done = HF_DONE_BYTES; L.cks = 8;
+    L.params = tr.params_bytes; L.lutE = rows * 16 * 8; L.lutC = rows * 4 * (size_t) tr.K * 8;
+    L.lutA = tr.d_arow ? ((size_t) tr.n_arows + 1) * 16 * 8 : 0;    // (+ the identity row)
+    L.tile_ll = some(nt * 8); L.tile_stats = some(nt * (size_t) tr.R * stat_acc_len(16) * 8);
+    if (ns) { L.seg_ready = ns * 4; L.seg_ll = ns * 8; L.Pseg = ns * 16 * 8; }
+    int64_t cap = 0;                      // positions the pass buffer holds: the largest sub-pass (everything, with one)
+    for (const auto& sb : tr.subs) cap = std::max<int64_t>(cap, sb.p1 - sb.p0);
+    L.recs = tr.subs.empty() ? 0 : (size_t) (cap + 1) * 64;
+    if (tr.rows_ready) {
+        L.grp_sums = some((size_t) ((tr.n_groups + 3) / 4 * 4) * 16 * 8);   // (k_pair_sums: four groups per wavefront)
+        L.chunk_ll = some(C * 8); L.rw_stats = some((size_t) tr.n_rowwaves * stat_acc_len(16) * 8);
+    }
+    if (tr.algo == HF_ALGO_SEQ) {         // the sequential cross-check: emission rows, window-order scales, f and b by tile (hf_device.h fb_slot)
+        L.E = some(N * 16 * 8); L.scale = some(N * 8); L.f = L.b = some(nt * 64 * HF_SCAN_L * 4 * 8);
+    }
+    L.pin_total = ((V + 2 + HF_MAXREGIONS) * 8 + 63) / 64 * 64;   // (what follows stays 64-byte aligned)
+    L.pin_block = L.pin_total + 64 + (tr.params_bytes + 63) / 64 * 64;
+    return L;
+}
+
+// does k_tables write the rows of A (the job list is the (key, class) list)?
+static bool arow_jobs(const Track& tr) { return tr.nseg > 0 && tr.d_arow && tr.algo == HF_ALGO_SCAN; }
+
+// The pass state of `tr` in *out: the settings copied from `settings` (the context's own pass may be both), the device arrays out of a slab of
+// its own, the pinned block (from the process-wide cache: pinning even this small block was 0.1-0.2 ms of hf_create), the events; zeroed where a
+// pass expects zeros, and the identity row behind the rows of A (hf_seg.h: what a lane multiplies by past its last window; no kernel writes it)
+// written through `stg` when it has room — a synchronous copy in hf_create waited for the 6 MB of rows of A enqueued before it (0.25 ms).
+// On failure the caller destroys *out.
+static int pass_create(const Track& tr, const Pass& settings, Pass* out, UploadStage* stg = nullptr) {
+    Pass& ps = *out;
+    ps.tr = &tr;
+    ps.stats_mode = settings.stats_mode; ps.seg_fused = settings.seg_fused; ps.seg_test_timeout = settings.seg_test_timeout;
+    ps.kp_ok = settings.kp_ok; ps.host_total_ok = settings.host_total_ok; ps.stream_stamp_ok = settings.stream_stamp_ok;
+    const PassLayout L = pass_layout(tr);
+    ps.slab.first = L.device_bytes();
+    bool ok = true;
+    auto take = [&](auto*& p, size_t bytes) {
+        if (bytes && ok) { p = static_cast<std::remove_reference_t<decltype(p)>>(ps.slab.alloc(bytes)); ok = p != nullptr; }
+    };
+    take(ps.d_label, L.label); take(ps.d_chunk_stats_own, L.chunk_stats); take(ps.d_total, L.total); take(ps.d_flags, L.flags);
+    take(ps.d_done, L.done); take(ps.d_cks, L.cks); take(ps.d_params, L.params); take(ps.d_lutE, L.lutE); take(ps.d_lutC, L.lutC);
+    take(ps.d_lutA, L.lutA); take(ps.d_tile_ll, L.tile_ll); take(ps.d_tile_stats, L.tile_stats); take(ps.d_seg_ready, L.seg_ready);
+    take(ps.d_seg_ll, L.seg_ll); take(ps.d_Pseg, L.Pseg); take(ps.d_recs, L.recs); take(ps.d_grp_sums, L.grp_sums);
+    take(ps.d_chunk_ll, L.chunk_ll); take(ps.d_rw_stats, L.rw_stats);
+    take(ps.d_E, L.E); take(ps.d_f, L.f); take(ps.d_b, L.b); take(ps.d_scale, L.scale);
+    if (!ok) { (void) hipGetLastError(); return set_err(HF_E_HIP, "out of device memory for the pass state"); }
+    ps.d_chunk_stats = ps.d_chunk_stats_own;
+    ps.d_Es = ps.d_lutE + (size_t) tr.n_lut * 16;
+    ps.d_Cs = ps.d_lutC + (size_t) tr.n_lut * 4 * (size_t) tr.K;
+    if (tr.subs.size() == 1) ps.d_recs_all = ps.d_recs;      // (several sub-passes: the all-windows buffer on first use, all_records_buffer)
+    ps.tabwork = tr.tabwork;
+    ps.tabwork.lutE = ps.d_lutE; ps.tabwork.lutC = ps.d_lutC; ps.tabwork.lutA = arow_jobs(tr) ? ps.d_lutA : nullptr;
+    char* pin = pin_cache().acquire(L.pin_block);
+    if (!pin) return set_err(HF_E_HIP, "out of host memory for the pass state");
+    std::memset(pin, 0, L.pin_block);                        // (a stale stamp word must not look like a future one)
+    ps.h_total = reinterpret_cast<double*>(pin);
+    ps.h_flags = reinterpret_cast<unsigned*>(pin + L.pin_total);
+    ps.h_params = reinterpret_cast<DevParams*>(pin + L.pin_total + 64);
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, ps.h_total, 0) == hipSuccess) ps.d_total_host = (double*) dp;
+    else {
+        // (the cache falls back to pageable memory when pinning fails — a block the device cannot address: no zero-copy totals,
+        // no stream stamp into it; passes then complete through a copy and hipStreamSynchronize)
+        (void) hipGetLastError();
+        ps.d_total_host = nullptr; ps.stream_stamp_ok = false;
+    }
+    HIPCHK(hipEventCreate(&ps.ev0)); HIPCHK(hipEventCreate(&ps.ev1));
+    HIPCHK(hipMemsetAsync(ps.d_flags, 0, 4, nullptr));
+    HIPCHK(hipMemsetAsync(ps.d_done, 0, HF_DONE_BYTES, nullptr));   // tickets and scratch of the in-launch hand-offs (hf_rows.h)
+    HIPCHK(hipMemsetAsync(ps.d_cks, 0, 8, nullptr));
+    HIPCHK(hipMemsetAsync(ps.d_params, 0, tr.params_bytes, nullptr));   // (the kernel-argument path writes the bytes in use only)
+    HIPCHK(hipMemsetAsync(ps.d_label, 0xff, tr.N ? (size_t) tr.N : 1, nullptr));
+    if (ps.d_seg_ready) HIPCHK(hipMemsetAsync(ps.d_seg_ready, 0, L.seg_ready, nullptr));
+    if (ps.d_lutA) {
+        double ident[16];
+        for (int k = 0; k < 16; k++) ident[k] = (k % 5 == 0) ? 1.0 : 0.0;
+        return stage_upload(stg, ps.d_lutA + (size_t) tr.n_arows * 16, ident, sizeof ident);
+    }
+    return HF_OK;
+}
+
+// everything pass_create and the pass's first uses allocated
+static void pass_destroy(Pass& ps) {
+    for (void* p : {(void*) ps.d_segQ, (void*) ps.d_scale_s, (void*) ps.d_slot_of, (void*) ps.d_nbE, (void*) ps.d_tile_hist}) hipFree(p);
+    if (ps.d_recs_all != ps.d_recs) hipFree(ps.d_recs_all);
+    for (int b = 0; b < 2; b++) { if (ps.h_nb[b]) hipHostFree(ps.h_nb[b]); if (ps.nb_ev[b]) hipEventDestroy(ps.nb_ev[b]); }
+    if (ps.h_part) hipHostFree(ps.h_part);
+    if (ps.h_label) pin_cache().release(reinterpret_cast<char*>(ps.h_label));
+    for (hipEvent_t e : {ps.ev0, ps.ev1}) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : ps.kev) if (e) hipEventDestroy(e);
+    ps.slab.release();
+    // the pinned block (h_flags and h_params live in it), back to the cache once nothing can write it any more
+    if (ps.h_total) { hipDeviceSynchronize(); pin_cache().release(reinterpret_cast<char*>(ps.h_total)); }
 }
 
 #include "hf_create.h"
@@ -795,61 +947,45 @@ void hf_destroy(hf_ctx* ctx) {
 #ifdef HF_KSTAMP
     if (ctx && std::getenv("HF_KSTAMP_FILE")) {
         unsigned long long h[64 * 4 + 1];
-        hipSetDevice(ctx->device); hipDeviceSynchronize();
+        hipSetDevice(ctx->tr.device); hipDeviceSynchronize();
         if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_kstamp), sizeof(h)) == hipSuccess)
             if (FILE* fp = std::fopen(std::getenv("HF_KSTAMP_FILE"), "ab")) { std::fwrite(h, 8, 64 * 4 + 1, fp); std::fclose(fp); }
     }
 #endif
     if (!ctx) return;
-    hipSetDevice(ctx->device);
+    const Track& tr = ctx->tr;
+    hipSetDevice(tr.device);
 #ifdef HF_SEG_TRACE
-    if (ctx->d_seg_trace) {
+    if (tr.d_seg_trace) {
         hipDeviceSynchronize();
-        std::vector<unsigned long long> h((size_t) ctx->nseg * HF_SEG_TRACE_N);
-        hipMemcpy(h.data(), ctx->d_seg_trace, h.size() * 8, hipMemcpyDeviceToHost);
+        std::vector<unsigned long long> h((size_t) tr.nseg * HF_SEG_TRACE_N);
+        hipMemcpy(h.data(), tr.d_seg_trace, h.size() * 8, hipMemcpyDeviceToHost);
         if (FILE* fp = std::fopen(std::getenv("HF_SEG_TRACE_FILE"), "wb")) { std::fwrite(h.data(), 8, h.size(), fp); std::fclose(fp); }
         unsigned long long* null_p = nullptr;
         hipMemcpyToSymbol(HIP_SYMBOL(g_seg_trace), &null_p, sizeof(void*));
-        ctx_free(ctx, ctx->d_seg_trace);
     }
 #endif
-    if (ctx->host_trace && ctx->ht_n)
+    const Pass& ps = ctx->pass;
+    if (ps.host_trace && ps.ht_n)
         std::fprintf(stderr, "[hf host trace] %ld EM steps: parameter view (hfm_params: the negative-binomial tables) %.1f us, enqueue %.1f us, wait %.1f us, m-step %.1f us, gpu span (first launch .. reduction) %.1f us\n",
-                     ctx->ht_n, ctx->ht[4] / ctx->ht_n, ctx->ht[0] / ctx->ht_n, ctx->ht[1] / ctx->ht_n, ctx->ht[2] / ctx->ht_n, ctx->ht[3] / ctx->ht_n);
-    ctx_free(ctx, ctx->d_off); ctx_free(ctx, ctx->d_rec); ctx_free(ctx, ctx->d_beta); ctx_free(ctx, ctx->d_regmask); ctx_free(ctx, ctx->d_E);
-    ctx_free(ctx, ctx->d_f); ctx_free(ctx, ctx->d_b); ctx_free(ctx, ctx->d_scale); ctx_free(ctx, ctx->d_label); if (ctx->own_chunk_stats) ctx_free(ctx, ctx->d_chunk_stats);
-    ctx_free(ctx, ctx->d_total); ctx_free(ctx, ctx->d_flags); ctx_free(ctx, ctx->d_params);
-    ctx_free(ctx, ctx->d_lutE); ctx_free(ctx, ctx->d_lutC); ctx_free(ctx, ctx->d_slow_w); ctx_free(ctx, ctx->d_slow_off); ctx_free(ctx, ctx->d_keys);
-    ctx_free(ctx, ctx->d_nbE); ctx_free(ctx, ctx->d_tile_hist);   // (d_nbP .. d_nbBeta point into d_nbE's buffer)
-    for (int b = 0; b < 2; b++) { if (ctx->h_nb[b]) hipHostFree(ctx->h_nb[b]); if (ctx->nb_ev[b]) hipEventDestroy(ctx->nb_ev[b]); }
-    ctx_free(ctx, ctx->d_tile_desc); ctx_free(ctx, ctx->d_chunk_tile0);
-    ctx_free(ctx, ctx->d_done); ctx_free(ctx, ctx->d_cks); ctx_free(ctx, ctx->d_bin_off); ctx_free(ctx, ctx->d_bin_list); ctx_free(ctx, ctx->d_slot_h); ctx_free(ctx, ctx->d_H); if (ctx->d_recs_all != ctx->d_recs) ctx_free(ctx, ctx->d_recs_all); ctx_free(ctx, ctx->d_recs); ctx_free(ctx, ctx->d_chunk_ll); ctx_free(ctx, ctx->d_grp_ar); ctx_free(ctx, ctx->d_grp_n); ctx_free(ctx, ctx->d_grp_off); ctx_free(ctx, ctx->d_pos); ctx_free(ctx, ctx->d_pos_f); ctx_free(ctx, ctx->d_slot_of); ctx_free(ctx, ctx->d_grp_sums); ctx_free(ctx, ctx->d_rowslots); ctx_free(ctx, ctx->d_rw_region);
-    ctx_free(ctx, ctx->d_seg_of_block); ctx_free(ctx, ctx->d_seg); ctx_free(ctx, ctx->d_chunk_seg0); ctx_free(ctx, ctx->d_seg_ll); ctx_free(ctx, ctx->d_Pseg); ctx_free(ctx, ctx->d_segQ); ctx_free(ctx, ctx->d_seg_ready); ctx_free(ctx, ctx->d_scale_s);
-    ctx_free(ctx, ctx->d_jobs); ctx_free(ctx, ctx->d_arow); ctx_free(ctx, ctx->d_arow_src); ctx_free(ctx, ctx->d_arow_cls); ctx_free(ctx, ctx->d_lutA);
-    ctx_free(ctx, ctx->d_rw_off); ctx_free(ctx, ctx->d_rw_stats);
-    ctx_free(ctx, ctx->d_tile_ll); ctx_free(ctx, ctx->d_tile_stats);
+                     ps.ht_n, ps.ht[4] / ps.ht_n, ps.ht[0] / ps.ht_n, ps.ht[1] / ps.ht_n, ps.ht[2] / ps.ht_n, ps.ht[3] / ps.ht_n);
+    pass_destroy(ctx->pass);
     vit_free(ctx);
-    if (ctx->h_part) hipHostFree(ctx->h_part);
-    if (ctx->h_label) pin_cache().release(reinterpret_cast<char*>(ctx->h_label));
-    if (ctx->ev0) hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) hipEventDestroy(ctx->ev1);
-    for (int i = 0; i < 2 * HF_NKERNELS; i++) if (ctx->kev[i]) hipEventDestroy(ctx->kev[i]);
-    for (auto& sl : ctx->slabs) hipFree(sl.first);
-    if (ctx->h_total) { hipDeviceSynchronize(); pin_cache().release(reinterpret_cast<char*>(ctx->h_total)); }   // one pinned block (h_flags and h_params live in it), back to the cache once nothing can write it any more
+    ctx->tr.slab.release();
     delete ctx;
 }
 
 // pack one iteration's model: conditional transition tables (hmm_utils.c:2278-2292) and the
 // distinct alpha values of each column
-static int pack_params(hf_ctx* ctx, const hf_params* p, DevParams* dst = nullptr) {
-    if (p->n_regions != ctx->R) return set_err(HF_E_ARG, "hf_estep: n_regions differs from hf_create");
+static int pack_params(const Track& tr, const hf_params* p, DevParams* dst) {
+    if (p->n_regions != tr.R) return set_err(HF_E_ARG, "hf_estep: n_regions differs from hf_create");
     for (int s = 0; s < 4; s++)
-        if (p->ncomp[s] < 1 || p->ncomp[s] > ctx->K) return set_err(HF_E_ARG, "hf_estep: ncomp out of range");
+        if (p->ncomp[s] < 1 || p->ncomp[s] > tr.K) return set_err(HF_E_ARG, "hf_estep: ncomp out of range");
     if (p->ncomp[1] != 1 || p->ncomp[2] != 1 || p->ncomp[0] != 1)
         return set_err(HF_E_ARG, "hf_estep: Err/Dup/Hap must have one component (hmm_flagger.c:180-182)");
-    DevParams* h = dst ? dst : ctx->h_params;
+    DevParams* h = dst;
     h->model_type = p->model_type; h->n_regions = p->n_regions;
-    h->beta_star = ctx->beta_star;
+    h->beta_star = tr.beta_star;
     for (int s = 0; s < 4; s++) h->ncomp[s] = p->ncomp[s];
     for (int pre = 0; pre < 4; pre++)
         for (int s = 0; s < 4; s++) h->alpha[pre * 4 + s] = p->alpha[pre][s];
@@ -876,7 +1012,7 @@ static int pack_params(hf_ctx* ctx, const hf_params* p, DevParams* dst = nullptr
         }
         h->n_items = n;
     }
-    for (int r = 0; r < ctx->R; r++) {
+    for (int r = 0; r < tr.R; r++) {
         DevRegion* g = &h->reg[r];
         std::memcpy(g->trans, p->trans + (size_t) r * 25, sizeof(double) * 25);
         g->lambda = p->lambda ? p->lambda[r] : 1.0;
@@ -884,7 +1020,7 @@ static int pack_params(hf_ctx* ctx, const hf_params* p, DevParams* dst = nullptr
         std::memcpy(g->mean, p->mean + (size_t) r * 4 * HF_MAXCOMP, sizeof(g->mean));
         std::memcpy(g->var, p->var + (size_t) r * 4 * HF_MAXCOMP, sizeof(g->var));
         std::memcpy(g->weight, p->weight + (size_t) r * 4 * HF_MAXCOMP, sizeof(g->weight));
-        const double bs = ctx->beta_star;
+        const double bs = tr.beta_star;
         for (int s = 0; s < 4; s++)
             for (int c = 0; c < p->ncomp[s]; c++) {             // (per EM step and region: the components in use, not HF_MAXCOMP)
                 double var = g->var[s][c];
@@ -909,10 +1045,10 @@ static int pack_params(hf_ctx* ctx, const hf_params* p, DevParams* dst = nullptr
 
 
 // the 8-byte words of the packed block that are in use, each with its place in the image (hf_device.h KParams); false: they do not fit
-static bool pack_kparams(hf_ctx* ctx, const hf_params* p) {
-    if (ctx->R != 1) return false;
-    const DevParams* h = ctx->h_params;
-    KParams& kp = ctx->kparams;
+static bool pack_kparams(Pass& ps, const hf_params* p) {
+    if (ps.tr->R != 1) return false;
+    const DevParams* h = ps.h_params;
+    KParams& kp = ps.kparams;
     const char* const base = reinterpret_cast<const char*>(h);
     int nw = 0;
     bool fits = true;
@@ -946,40 +1082,43 @@ static bool pack_kparams(hf_ctx* ctx, const hf_params* p) {
 // phase (hf_batch.h): the parts of the pass to enqueue — PASS_PRE the parameter block and the tables, PASS_SEG the segment kernel, PASS_POST
 // the statistics; a batch enqueues PRE and POST per model and the segment kernel of all models in one launch
 enum { PASS_PRE = 1, PASS_SEG = 2, PASS_POST = 4, PASS_ALL = 7 };
-static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t st, bool retry = false, int phase = PASS_ALL) {
+static int enqueue_pass(Pass& ps, const hf_params* p, int mode, hipStream_t st, bool retry = false, int phase = PASS_ALL) {
+    const Track& tr = *ps.tr;
     const bool ph_pre = (phase & PASS_PRE) != 0, ph_seg = (phase & PASS_SEG) != 0, ph_post = (phase & PASS_POST) != 0;
     // the parameter block: through the kernel arguments of k_tables when it fits them (one region, HF_ALGO_SCAN, Gaussian models:
     // hf_device.h KParams), a copy ahead of the pass otherwise
     if (ph_pre) {
-        ctx->kp_now = ctx->kp_ok && ctx->C > 0 && ctx->algo == HF_ALGO_SCAN && p->model_type != HF_MODEL_NEGATIVE_BINOMIAL && pack_kparams(ctx, p);
-        if (!ctx->kp_now) HIPCHK(hipMemcpyAsync(ctx->d_params, ctx->h_params, ctx->params_bytes, hipMemcpyHostToDevice, st));
-        for (int i = 0; i < HF_NKERNELS; i++) { ctx->kran[i] = false; ctx->klast_ok[i] = false; }
-        ctx->prof_now = ctx->prof_stride <= 1 || (ctx->prof_pass++ % ctx->prof_stride) == 0;
+        ps.kp_now = ps.kp_ok && tr.C > 0 && tr.algo == HF_ALGO_SCAN && p->model_type != HF_MODEL_NEGATIVE_BINOMIAL && pack_kparams(ps, p);
+        if (!ps.kp_now) HIPCHK(hipMemcpyAsync(ps.d_params, ps.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+        for (int i = 0; i < HF_NKERNELS; i++) { ps.kran[i] = false; ps.klast_ok[i] = false; }
+        ps.prof_now = ps.prof_stride <= 1 || (ps.prof_pass++ % ps.prof_stride) == 0;
     }
-    ctx->pass_rows = false; ctx->pass_bound = false;
-    ctx->pass_seg = false;
-    if (ctx->C == 0 && ph_pre) HIPCHK(hipMemsetAsync(ctx->d_flags, 0, 4, st));
-    if (ctx->C > 0) {
-        const RowSrc S = row_src(ctx);
+    ps.pass_rows = false; ps.pass_bound = false;
+    ps.pass_seg = false;
+    if (tr.C == 0 && ph_pre) HIPCHK(hipMemsetAsync(ps.d_flags, 0, 4, st));
+    if (tr.C > 0) {
+        const RowSrc S = row_src(ps);
         const bool full = mode == HF_MODE_FULL;
         const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
         if (nbm) {   // the caller's per-x tables go up with the parameters
             if (!retry && (!p->nb_E || !p->nb_P || !p->nb_dig || !p->nb_r || !p->nb_beta))
                 return set_err(HF_E_ARG, "hf_estep: negative_binomial needs hf_params.nb_E/nb_P/nb_dig/nb_r/nb_beta");
-            if (p->nb_max_x > 0 && ctx->M - 1 > p->nb_max_x)
+            if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
                 return set_err(HF_E_ARG, "hf_estep: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
-            const size_t nE = (size_t) ctx->R * 4 * HF_NB_NX * 8, nP = (size_t) ctx->R * 4 * ctx->K * HF_NB_NX * 8,
-                         nR = (size_t) ctx->R * 4 * ctx->K * 8;
+            const size_t nE = (size_t) tr.R * 4 * HF_NB_NX * 8, nP = (size_t) tr.R * 4 * tr.K * HF_NB_NX * 8,
+                         nR = (size_t) tr.R * 4 * tr.K * 8;
             // ONE device buffer and ONE copy per pass for the five tables (round 4; five copies out of pageable memory were ~50 us of a
             // 0.24 ms step): E | P | dig | r | beta, gathered into one of two pinned staging buffers (an event per buffer says when its
             // last copy has left it: a caller may enqueue the next pass before this one has run)
             const size_t nAll = nE + 2 * nP + 2 * nR;
-            if (!ctx->d_nbE) {
+            if (!ps.d_nbE) {
                 // everything into locals first: the context is touched only when ALL of it exists (a failure half way used to leave
                 // d_nbE set and a staging buffer null — the next pass skipped this block and copied through the null pointer)
+                // the count data: tile_hist [ntiles][R][HF_NB_TILE_VEC] | slot_h [row slots][4] | H [R][4][256]
+                const size_t nT = Slab::granule(((size_t) tr.ntiles * tr.R * HF_NB_TILE_VEC + 1) * 8),
+                             nS = Slab::granule((size_t) tr.n_rowwaves * 16 * tr.rs_bpw * 4 * 8);
                 double *dE = nullptr, *dH = nullptr; char* hb[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
-                bool ok = hipMalloc((void**) &dE, nAll) == hipSuccess &&
-                          hipMalloc((void**) &dH, ((size_t) ctx->ntiles * ctx->R * HF_NB_TILE_VEC + 1) * 8) == hipSuccess;
+                bool ok = hipMalloc((void**) &dE, nAll) == hipSuccess && hipMalloc((void**) &dH, nT + nS + (size_t) tr.R * 4 * 256 * 8) == hipSuccess;
                 for (int b = 0; ok && b < 2; b++)
                     ok = hipHostMalloc((void**) &hb[b], nAll) == hipSuccess && hipEventCreateWithFlags(&ev[b], hipEventDisableTiming) == hipSuccess;
                 if (!ok) {
@@ -989,37 +1128,38 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
                     return set_err(HF_E_HIP, std::string("hf_estep: negative-binomial staging: ") + hipGetErrorString(e_));
                 }
                 char* base = reinterpret_cast<char*>(dE);
-                ctx->d_nbE = dE; ctx->d_tile_hist = dH;
-                ctx->d_nbP = reinterpret_cast<double*>(base + nE); ctx->d_nbDig = reinterpret_cast<double*>(base + nE + nP);
-                ctx->d_nbR = reinterpret_cast<double*>(base + nE + 2 * nP); ctx->d_nbBeta = reinterpret_cast<double*>(base + nE + 2 * nP + nR);
-                for (int b = 0; b < 2; b++) { ctx->h_nb[b] = hb[b]; ctx->nb_ev[b] = ev[b]; }
+                ps.d_nbE = dE; ps.d_tile_hist = dH;
+                ps.d_slot_h = reinterpret_cast<double*>(reinterpret_cast<char*>(dH) + nT); ps.d_H = reinterpret_cast<double*>(reinterpret_cast<char*>(dH) + nT + nS);
+                ps.d_nbP = reinterpret_cast<double*>(base + nE); ps.d_nbDig = reinterpret_cast<double*>(base + nE + nP);
+                ps.d_nbR = reinterpret_cast<double*>(base + nE + 2 * nP); ps.d_nbBeta = reinterpret_cast<double*>(base + nE + 2 * nP + nR);
+                for (int b = 0; b < 2; b++) { ps.h_nb[b] = hb[b]; ps.nb_ev[b] = ev[b]; }
             }
             if (!retry) {
-                const int b = (int) (ctx->nb_turn++ & 1u);
-                if (ctx->nb_ev_used[b]) HIPCHK(hipEventSynchronize(ctx->nb_ev[b]));
-                char* h = ctx->h_nb[b];
+                const int b = (int) (ps.nb_turn++ & 1u);
+                if (ps.nb_ev_used[b]) HIPCHK(hipEventSynchronize(ps.nb_ev[b]));
+                char* h = ps.h_nb[b];
                 std::memcpy(h, p->nb_E, nE); std::memcpy(h + nE, p->nb_P, nP); std::memcpy(h + nE + nP, p->nb_dig, nP);
                 std::memcpy(h + nE + 2 * nP, p->nb_r, nR); std::memcpy(h + nE + 2 * nP + nR, p->nb_beta, nR);
-                HIPCHK(hipMemcpyAsync(ctx->d_nbE, h, nAll, hipMemcpyHostToDevice, st));
-                HIPCHK(hipEventRecord(ctx->nb_ev[b], st));
-                ctx->nb_ev_used[b] = true;
+                HIPCHK(hipMemcpyAsync(ps.d_nbE, h, nAll, hipMemcpyHostToDevice, st));
+                HIPCHK(hipEventRecord(ps.nb_ev[b], st));
+                ps.nb_ev_used[b] = true;
             }
         }
         if (ph_pre) {   // also clears the flag word: first kernel of every pass
-            KTimer t(ctx, st, HF_K_TABLES);
+            KTimer t(ps, st, HF_K_TABLES);
             // statistics by emission row: the job list of the Gaussian tables is the (key, class) list of the rows of A (hf_seg.h)
-            const bool arows = !nbm && seg_pass(ctx);
-            const int nk = arows ? ctx->n_combo : ctx->n_keys;
-            const int jobs = nk + ctx->n_slow;
+            const bool arows = !nbm && seg_pass(tr);
+            const int nk = arows ? tr.n_combo : tr.n_keys;
+            const int jobs = nk + tr.n_slow;
             if (nbm)
-                hipLaunchKernelGGL(k_tables_nb, dim3((unsigned) (jobs / 256 + 1)), dim3(256), 0, st, ctx->n_keys, ctx->d_keys, ctx->n_slow,
-                                   ctx->d_slow_w, ctx->d_rec, ctx->M, ctx->d_nbE, ctx->d_lutE, ctx->d_Es, ctx->d_flags);
+                hipLaunchKernelGGL(k_tables_nb, dim3((unsigned) (jobs / 256 + 1)), dim3(256), 0, st, tr.n_keys, tr.d_keys, tr.n_slow,
+                                   tr.d_slow_w, tr.d_rec, tr.M, ps.d_nbE, ps.d_lutE, ps.d_Es, ps.d_flags);
             else
             {
 #define HF_LAUNCH_TABLES(J, KA, KP) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables<J, KA>), dim3((unsigned) ((jobs + J - 1) / J + (jobs == 0))), dim3(256), 0, st, \
-                               ctx->tabwork, ctx->d_params, ctx->d_flags, KP, ctx->d_params)
-                if (ctx->kp_now) {     // the parameter block travels in the kernel arguments (pack_kparams): no copy was enqueued
-                    if (jobs < 64 * 1024) HF_LAUNCH_TABLES(HF_TABLE_JOBS_SMALL, true, ctx->kparams); else HF_LAUNCH_TABLES(HF_TABLE_JOBS_LARGE, true, ctx->kparams);
+                               ps.tabwork, ps.d_params, ps.d_flags, KP, ps.d_params)
+                if (ps.kp_now) {     // the parameter block travels in the kernel arguments (pack_kparams): no copy was enqueued
+                    if (jobs < 64 * 1024) HF_LAUNCH_TABLES(HF_TABLE_JOBS_SMALL, true, ps.kparams); else HF_LAUNCH_TABLES(HF_TABLE_JOBS_LARGE, true, ps.kparams);
                 } else {
                     const NoKParams none{0};
                     if (jobs < 64 * 1024) HF_LAUNCH_TABLES(HF_TABLE_JOBS_SMALL, false, none); else HF_LAUNCH_TABLES(HF_TABLE_JOBS_LARGE, false, none);
@@ -1027,120 +1167,120 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
 #undef HF_LAUNCH_TABLES
             }
         }
-        if (ctx->ntiles > 0) {
-            if (ctx->algo == HF_ALGO_SEQ) {
+        if (tr.ntiles > 0) {
+            if (tr.algo == HF_ALGO_SEQ) {
                 {
-                    KTimer t(ctx, st, HF_K_EMIT_ROWS);
-                    hipLaunchKernelGGL(k_emit_rows, dim3((unsigned) ((ctx->N + 255) / 256)), dim3(256), 0, st, ctx->N, ctx->d_rec,
-                                       ctx->d_beta, ctx->d_params, nbm ? ctx->d_nbE : (const double*) nullptr, ctx->d_E, ctx->d_flags);
+                    KTimer t(ps, st, HF_K_EMIT_ROWS);
+                    hipLaunchKernelGGL(k_emit_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec,
+                                       tr.d_beta, ps.d_params, nbm ? ps.d_nbE : (const double*) nullptr, ps.d_E, ps.d_flags);
                 }
                 {
-                    KTimer t(ctx, st, HF_K_FWD_SEQ);
-                    hipLaunchKernelGGL(k_fwd_seq, dim3((unsigned) ctx->C), dim3(64), 0, st, ctx->d_off, ctx->d_chunk_tile0, ctx->d_rec,
-                                       ctx->d_E, ctx->d_params, ctx->d_f, ctx->d_scale, ctx->d_tile_ll, ctx->d_flags);
+                    KTimer t(ps, st, HF_K_FWD_SEQ);
+                    hipLaunchKernelGGL(k_fwd_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_chunk_tile0, tr.d_rec,
+                                       ps.d_E, ps.d_params, ps.d_f, ps.d_scale, ps.d_tile_ll, ps.d_flags);
                 }
-                if (full) ctx->fb_recs = false;
+                if (full) ps.fb_recs = false;
                 if (full) {
-                    KTimer t(ctx, st, HF_K_BWD_SEQ);
-                    hipLaunchKernelGGL(k_bwd_seq, dim3((unsigned) ctx->C), dim3(64), 0, st, ctx->d_off, ctx->d_chunk_tile0, ctx->d_rec,
-                                       ctx->d_E, ctx->d_params, ctx->d_f, ctx->d_scale, ctx->d_b, ctx->d_label, ctx->d_flags);
+                    KTimer t(ps, st, HF_K_BWD_SEQ);
+                    hipLaunchKernelGGL(k_bwd_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_chunk_tile0, tr.d_rec,
+                                       ps.d_E, ps.d_params, ps.d_f, ps.d_scale, ps.d_b, ps.d_label, ps.d_flags);
                 }
-            } else if (seg_pass(ctx)) {
+            } else if (seg_pass(tr)) {
                 // one workgroup per chunk segment does the whole forward-backward (hf_seg.h)
-                const int nc = ctx->seg_fused ? ctx->seg_nc : 0;
+                const int nc = ps.seg_fused ? tr.seg_nc : 0;
                 const size_t lds = seg_lds_bytes(nc);
-                if (ctx->host_trace && !ctx->ht_n) {
+                if (ps.host_trace && !ps.ht_n) {
                     int o1 = 0, o2 = 0;
                     hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, k_seg_prod, 64, seg_lds_bytes());
-                    if (ctx->seg_fused) hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k_seg_fb<true, true>, 64, lds);
+                    if (ps.seg_fused) hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k_seg_fb<true, true>, 64, lds);
                     else hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k_seg_fb<true, false>, 64, lds);
                     std::fprintf(stderr, "[hf host trace] segment kernels (%s): %d workgroups of 64 threads, %zu B of LDS; resident per CU: k_seg_prod %d, k_seg_fb %d\n",
-                                 ctx->seg_fused ? "one launch" : "two launches", ctx->nseg, lds, o1, o2);
+                                 ps.seg_fused ? "one launch" : "two launches", tr.nseg, lds, o1, o2);
                 }
                 if (nbm && ph_pre) {   // k_tables_nb leaves the emission rows; the Gaussian k_tables writes the rows of A itself
-                    KTimer t(ctx, st, HF_K_AROWS);
-                    hipLaunchKernelGGL(k_arows, dim3((unsigned) (((int64_t) ctx->n_arows * 16 + 255) / 256)), dim3(256), 0, st, ctx->n_arows,
-                                       ctx->d_arow_src, ctx->d_arow_cls, ctx->d_lutE, ctx->d_params, ctx->d_lutA);
+                    KTimer t(ps, st, HF_K_AROWS);
+                    hipLaunchKernelGGL(k_arows, dim3((unsigned) (((int64_t) tr.n_arows * 16 + 255) / 256)), dim3(256), 0, st, tr.n_arows,
+                                       tr.d_arow_src, tr.d_arow_cls, ps.d_lutE, ps.d_params, ps.d_lutA);
                 }
-                if (!ctx->seg_fused && ph_seg) {
-                    if (!ctx->d_segQ) HIPCHK(hipMalloc((void**) &ctx->d_segQ, (size_t) ctx->nseg * 64 * 16 * 8));   // lane products: two-launch mode only
-                    KTimer t(ctx, st, HF_K_SEG_PROD);
-                    hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) ctx->nseg), dim3(64), seg_lds_bytes(), st, ctx->d_seg, ctx->d_arow, ctx->d_lutA, ctx->d_segQ, ctx->d_Pseg);
+                if (!ps.seg_fused && ph_seg) {
+                    if (!ps.d_segQ) HIPCHK(hipMalloc((void**) &ps.d_segQ, (size_t) tr.nseg * 64 * 16 * 8));   // lane products: two-launch mode only
+                    KTimer t(ps, st, HF_K_SEG_PROD);
+                    hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) tr.nseg), dim3(64), seg_lds_bytes(), st, tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_segQ, ps.d_Pseg);
                 }
-                const bool tfb = ((ctx->prof_mask >> HF_K_SEG_FB) & 1u) && ctx->prof_now;
-                if (tfb) ctx->kran[HF_K_SEG_FB] = true;
-                const unsigned epoch = ph_seg ? ++ctx->seg_epoch : ctx->seg_epoch;
+                const bool tfb = ((ps.prof_mask >> HF_K_SEG_FB) & 1u) && ps.prof_now;
+                if (tfb) ps.kran[HF_K_SEG_FB] = true;
+                const unsigned epoch = ph_seg ? ++ps.seg_epoch : ps.seg_epoch;
                 // HF_SEG_TEST_TIMEOUT=1 (tests/test_estep_gpu.py): the first one-launch pass waits for flags nobody writes, so that
                 // the time-out, HF_E_RETRY and the fall-back to two launches are exercised
-                const unsigned wait_epoch = (ctx->seg_test_timeout && epoch == 1) ? 0xffffffffu : epoch;
-                // Sub-passes (hf_ctx::SubPass).  A full pass whose statistics go by emission row runs sub-pass by sub-pass through the pass
+                const unsigned wait_epoch = (ps.seg_test_timeout && epoch == 1) ? 0xffffffffu : epoch;
+                // Sub-passes (Track::SubPass).  A full pass whose statistics go by emission row runs sub-pass by sub-pass through the pass
                 // buffer: k_seg_fb writes a sub-pass's records, k_pair_sums reads them back while they are still in the Infinity Cache, the next
                 // sub-pass overwrites them.  Any other pass (per-chunk statistics read the records by window afterwards; a forward-only pass writes
                 // none) is ONE launch over all segments into the all-windows buffer.
-                const bool want_rows = full && rows_pass(ctx);
-                ctx->pass_pairs_done = false;
+                const bool want_rows = full && rows_pass(ps);
+                ps.pass_pairs_done = false;
                 if (want_rows) {
-                    const bool alias = ctx->subs.size() > 1;
+                    const bool alias = tr.subs.size() > 1;
                     bool first = true;
-                    for (size_t si = 0; si < ctx->subs.size(); si++) {
-                        const auto& sb = ctx->subs[si];
-                        double* const recs_eff = alias ? ctx->d_recs - sb.p0 * 8 : ctx->d_recs;
-                        if (ph_seg) launch_seg_fb(ctx, st, true, recs_eff, (int) si, epoch, wait_epoch, tfb && first, false);   // (timed: the first sub-pass's launch, hf_sub_pass_windows; no scales)
+                    for (size_t si = 0; si < tr.subs.size(); si++) {
+                        const auto& sb = tr.subs[si];
+                        double* const recs_eff = alias ? ps.d_recs - sb.p0 * 8 : ps.d_recs;
+                        if (ph_seg) launch_seg_fb(ps, st, true, recs_eff, (int) si, epoch, wait_epoch, tfb && first, false);   // (timed: the first sub-pass's launch, hf_sub_pass_windows; no scales)
                         first = false;
                         if (!ph_post) continue;
-                        KTimer t(ctx, st, HF_K_PAIR_SUMS);              // (event pairs around k_pair_sums: the last sub-pass's is what is read)
-                        launch_pair_sums(ctx, st, sb, recs_eff);
+                        KTimer t(ps, st, HF_K_PAIR_SUMS);              // (event pairs around k_pair_sums: the last sub-pass's is what is read)
+                        launch_pair_sums(ps, st, sb, recs_eff);
                     }
-                    ctx->pass_pairs_done = true;
-                    ctx->recs_all = !alias;
-                    ctx->scales_all = false;
+                    ps.pass_pairs_done = true;
+                    ps.recs_all = !alias;
+                    ps.scales_all = false;
                 } else {
-                    double* recs = ctx->d_recs;
-                    if (full && ctx->subs.size() > 1) { const int rc_ = all_records_buffer(ctx); if (rc_) return rc_; recs = ctx->d_recs_all; }
-                    if (ph_seg) launch_seg_fb(ctx, st, full, recs, -1, epoch, wait_epoch, tfb, false);
-                    if (full) { ctx->recs_all = true; ctx->scales_all = false; }
+                    double* recs = ps.d_recs;
+                    if (full && tr.subs.size() > 1) { const int rc_ = all_records_buffer(ps); if (rc_) return rc_; recs = ps.d_recs_all; }
+                    if (ph_seg) launch_seg_fb(ps, st, full, recs, -1, epoch, wait_epoch, tfb, false);
+                    if (full) { ps.recs_all = true; ps.scales_all = false; }
                 }
-                ctx->pass_seg = true;
-                if (full) ctx->fb_recs = true;
+                ps.pass_seg = true;
+                if (full) ps.fb_recs = true;
             } else
                 return set_err(HF_E_ARG, "hf_estep: HF_ALGO_SCAN holds at most 2^30 windows per context (shard the chunk list: hmm_flagger_multi.h)");
         }
         const int kc = p->ncomp[3];
-        const int fl = full && ctx->ntiles > 0;
+        const int fl = full && tr.ntiles > 0;
         if (!ph_post) { HIPCHK(hipGetLastError()); return HF_OK; }
-        ctx->pass_nb = false;
-        if (nbm && fl && rows_pass(ctx)) {   // statistics by emission row, negative_binomial (hf_nb_rows.h)
+        ps.pass_nb = false;
+        if (nbm && fl && rows_pass(ps)) {   // statistics by emission row, negative_binomial (hf_nb_rows.h)
             {   // (k_pair_sums ran behind every sub-pass's k_seg_fb, above)
-                KTimer t(ctx, st, HF_K_ROW_STATS);
-                const int n_rw_blocks = (ctx->n_rowwaves + 3) / 4, n_ll_blocks = (ctx->C + 3) / 4;
-                hipLaunchKernelGGL(k_row_stats_nb, dim3((unsigned) (n_rw_blocks + n_ll_blocks)), dim3(256), 0, st, ctx->n_rowwaves, n_rw_blocks,
-                                   ctx->d_rowslots, ctx->d_grp_sums, ctx->d_slot_h, ctx->d_rw_stats, ctx->C, ll_off(ctx), ll_part(ctx),
-                                   ctx->d_chunk_stats, ctx->V, ctx->d_chunk_ll, ctx->rs_bpw);
-                const int n_bins = ctx->R * 256;
-                hipLaunchKernelGGL(k_nb_hist, dim3((unsigned) ((n_bins + 3) / 4)), dim3(256), 0, st, n_bins, ctx->d_bin_off, ctx->d_bin_list,
-                                   ctx->d_slot_h, ctx->d_H);
+                KTimer t(ps, st, HF_K_ROW_STATS);
+                const int n_rw_blocks = (tr.n_rowwaves + 3) / 4, n_ll_blocks = (tr.C + 3) / 4;
+                hipLaunchKernelGGL(k_row_stats_nb, dim3((unsigned) (n_rw_blocks + n_ll_blocks)), dim3(256), 0, st, tr.n_rowwaves, n_rw_blocks,
+                                   tr.d_rowslots, ps.d_grp_sums, ps.d_slot_h, ps.d_rw_stats, tr.C, ll_off(ps), ll_part(ps),
+                                   ps.d_chunk_stats, tr.V, ps.d_chunk_ll, tr.rs_bpw);
+                const int n_bins = tr.R * 256;
+                hipLaunchKernelGGL(k_nb_hist, dim3((unsigned) ((n_bins + 3) / 4)), dim3(256), 0, st, n_bins, tr.d_bin_off, tr.d_bin_list,
+                                   ps.d_slot_h, ps.d_H);
             }
-            ctx->pass_rows = true; ctx->pass_nb = true; ctx->pass_wpb = 4;
+            ps.pass_rows = true; ps.pass_nb = true; ps.pass_wpb = 4;
         }
         else if (nbm) {
             if (fl) {
-                KTimer t(ctx, st, HF_K_STATS_TILE);
-                const TileGeom g = tile_geom(ctx, k_stats_tile_nb<HF_SCAN_L>, (size_t) HF_NB_WAVE_LDS * 8);
+                KTimer t(ps, st, HF_K_STATS_TILE);
+                const TileGeom g = tile_geom(tr, k_stats_tile_nb<HF_SCAN_L>, (size_t) HF_NB_WAVE_LDS * 8);
                 if (!g.ok) return set_err(HF_E_ARG, "the per-region tables do not fit the LDS of one workgroup");
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stats_tile_nb<HF_SCAN_L>), dim3(g.blocks), dim3(g.threads), g.lds, st, ctx->ntiles, ctx->d_tile_desc,
-                                   ctx->d_rec, S, ctx->d_params, ctx->pass_seg ? ctx->d_recs_all : ctx->d_f, ctx->d_b, ctx->d_regmask, ctx->d_tile_hist,
-                                   ctx->pass_seg ? ctx->d_pos : (const int32_t*) nullptr);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stats_tile_nb<HF_SCAN_L>), dim3(g.blocks), dim3(g.threads), g.lds, st, tr.ntiles, tr.d_tile_desc,
+                                   tr.d_rec, S, ps.d_params, ps.pass_seg ? ps.d_recs_all : ps.d_f, ps.d_b, tr.d_regmask, ps.d_tile_hist,
+                                   ps.pass_seg ? tr.d_pos : (const int32_t*) nullptr);
             }
             NbTables nt;
-            nt.E = ctx->d_nbE; nt.P = ctx->d_nbP; nt.dig = ctx->d_nbDig; nt.r = ctx->d_nbR; nt.beta = ctx->d_nbBeta;
-            KTimer t(ctx, st, HF_K_CHUNK_STATS);
-            hipLaunchKernelGGL(k_chunk_stats_nb, dim3((unsigned) ctx->C), dim3(256), 0, st, ctx->d_chunk_tile0, ll_off(ctx), ctx->d_regmask,
-                               ctx->d_tile_hist, ll_part(ctx), ctx->d_params, nt, ctx->d_chunk_stats, ctx->V, ctx->K, fl);
+            nt.E = ps.d_nbE; nt.P = ps.d_nbP; nt.dig = ps.d_nbDig; nt.r = ps.d_nbR; nt.beta = ps.d_nbBeta;
+            KTimer t(ps, st, HF_K_CHUNK_STATS);
+            hipLaunchKernelGGL(k_chunk_stats_nb, dim3((unsigned) tr.C), dim3(256), 0, st, tr.d_chunk_tile0, ll_off(ps), tr.d_regmask,
+                               ps.d_tile_hist, ll_part(ps), ps.d_params, nt, ps.d_chunk_stats, tr.V, tr.K, fl);
         }
-        else if (kc <= 4) launch_stats<4>(ctx, st, fl, kc);
-        else if (kc <= 8) launch_stats<8>(ctx, st, fl, kc);
-        else launch_stats<16>(ctx, st, fl, kc);
-        if (ctx->launch_failed) { ctx->launch_failed = false; return HF_E_ARG; }
+        else if (kc <= 4) launch_stats<4>(ps, st, fl, kc);
+        else if (kc <= 8) launch_stats<8>(ps, st, fl, kc);
+        else launch_stats<16>(ps, st, fl, kc);
+        if (ps.launch_failed) { ps.launch_failed = false; return HF_E_ARG; }
     }
     HIPCHK(hipGetLastError());
     return HF_OK;
@@ -1148,111 +1288,118 @@ static int enqueue_pass(hf_ctx* ctx, const hf_params* p, int mode, hipStream_t s
 
 int hf_estep(hf_ctx* ctx, const hf_params* p, int mode, void* stream) {
     if (!ctx || !p || (mode != HF_MODE_FULL && mode != HF_MODE_FORWARD_ONLY)) return set_err(HF_E_ARG, "hf_estep: bad argument");
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc = pack_params(ctx, p);
+    HIPCHK(hipSetDevice(tr.device));
+    int rc = pack_params(tr, p, ps.h_params);
     if (rc) return rc;
-    ctx->last_p = *p; ctx->last_mode = mode; ctx->last_stream = st;
-    if (pass_events(ctx)) HIPCHK(hipEventRecord(ctx->ev0, st));
-    rc = enqueue_pass(ctx, p, mode, st);
+    ps.last_p = *p; ps.last_mode = mode; ps.last_stream = st;
+    if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev0, st));
+    rc = enqueue_pass(ps, p, mode, st);
     if (rc) return rc;
-    if (pass_events(ctx)) HIPCHK(hipEventRecord(ctx->ev1, st));
-    ctx->ev_valid = pass_events(ctx);
-    ctx->have_full = (mode == HF_MODE_FULL);
+    if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
+    ps.ev_valid = pass_events(ps);
+    ps.have_full = (mode == HF_MODE_FULL);
     return HF_OK;
 }
 
-int32_t hf_n_chunks(const hf_ctx* ctx) { return ctx ? ctx->C : 0; }
-int64_t hf_n_windows(const hf_ctx* ctx) { return ctx ? ctx->N : 0; }
-int64_t hf_chunk_stats_len(const hf_ctx* ctx) { return ctx ? ctx->V : 0; }
-double* hf_chunk_stats_dev(hf_ctx* ctx) { return ctx ? ctx->d_chunk_stats : nullptr; }
-int8_t* hf_labels_dev(hf_ctx* ctx) { return ctx ? ctx->d_label : nullptr; }
+int32_t hf_n_chunks(const hf_ctx* ctx) { return ctx ? ctx->tr.C : 0; }
+int64_t hf_n_windows(const hf_ctx* ctx) { return ctx ? ctx->tr.N : 0; }
+int64_t hf_chunk_stats_len(const hf_ctx* ctx) { return ctx ? ctx->tr.V : 0; }
+double* hf_chunk_stats_dev(hf_ctx* ctx) { return ctx ? ctx->pass.d_chunk_stats : nullptr; }
+int8_t* hf_labels_dev(hf_ctx* ctx) { return ctx ? ctx->pass.d_label : nullptr; }
 
 int hf_set_stats_mode(hf_ctx* ctx, int mode) {
     if (!ctx || (mode != HF_STATS_CHUNKS && mode != HF_STATS_ROWS)) return set_err(HF_E_ARG, "hf_set_stats_mode: bad argument");
-    ctx->stats_mode = mode;
+    ctx->pass.stats_mode = mode;
     return HF_OK;
 }
 int hf_get_stats_mode(const hf_ctx* ctx) {
-    return ctx && ctx->stats_mode == HF_STATS_ROWS && ctx->rows_ready && ctx->algo == HF_ALGO_SCAN ? HF_STATS_ROWS : HF_STATS_CHUNKS;
+    return ctx && ctx->pass.stats_mode == HF_STATS_ROWS && ctx->tr.rows_ready && ctx->tr.algo == HF_ALGO_SCAN ? HF_STATS_ROWS : HF_STATS_CHUNKS;
 }
 
-int hf_seg_launches(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx) ? 0 : (ctx->seg_fused ? 1 : 2); }
-int hf_sub_passes(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx) ? 0 : (int) ctx->subs.size(); }
+int hf_seg_launches(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx->tr) ? 0 : (ctx->pass.seg_fused ? 1 : 2); }
+int hf_sub_passes(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx->tr) ? 0 : (int) ctx->tr.subs.size(); }
 int64_t hf_sub_pass_windows(const hf_ctx* ctx, int k) {
-    if (!ctx || k < 0 || (size_t) k >= ctx->subs.size()) return 0;
-    return ctx->h_off[(size_t) ctx->subs[(size_t) k].c1] - ctx->h_off[(size_t) ctx->subs[(size_t) k].c0];
+    if (!ctx || k < 0 || (size_t) k >= ctx->tr.subs.size()) return 0;
+    return ctx->tr.h_off[(size_t) ctx->tr.subs[(size_t) k].c1] - ctx->tr.h_off[(size_t) ctx->tr.subs[(size_t) k].c0];
 }
-int hf_seg_cached_steps(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx) || !ctx->seg_fused ? 0 : ctx->seg_nc; }
-int hf_seg_xcd_plan(const hf_ctx* ctx) { return ctx && seg_pass(ctx) && ctx->seg_fused && ctx->d_seg_of_block ? 1 : 0; }
+int hf_seg_cached_steps(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx->tr) || !ctx->pass.seg_fused ? 0 : ctx->tr.seg_nc; }
+int hf_seg_xcd_plan(const hf_ctx* ctx) { return ctx && seg_pass(ctx->tr) && ctx->pass.seg_fused && ctx->tr.d_seg_of_block ? 1 : 0; }
 int64_t hf_seg_block_table(const hf_ctx* ctx, int32_t* seg_of_block, int64_t n) {
     if (!ctx) return 0;
-    const int64_t have = (int64_t) ctx->h_seg_of_block.size();
-    if (seg_of_block) for (int64_t i = 0; i < n && i < have; i++) seg_of_block[i] = ctx->h_seg_of_block[(size_t) i];
+    const Track& tr = ctx->tr;
+    const int64_t have = (int64_t) tr.h_seg_of_block.size();
+    if (seg_of_block) for (int64_t i = 0; i < n && i < have; i++) seg_of_block[i] = tr.h_seg_of_block[(size_t) i];
     return have;
 }
 int hf_create_phases(const hf_ctx* ctx, int max, double* ms, const char** names) {
     if (!ctx) return 0;
-    const int n = (int) ctx->create_phases.size();
-    for (int i = 0; i < n && i < max; i++) { if (ms) ms[i] = ctx->create_phases[(size_t) i].second; if (names) names[i] = ctx->create_phases[(size_t) i].first; }
+    const Track& tr = ctx->tr;
+    const int n = (int) tr.create_phases.size();
+    for (int i = 0; i < n && i < max; i++) { if (ms) ms[i] = tr.create_phases[(size_t) i].second; if (names) names[i] = tr.create_phases[(size_t) i].first; }
     return n;
 }
 
 int hf_copy_chunk_stats(hf_ctx* ctx, double* dst_dev, void* stream) {
     if (!ctx || !dst_dev) return set_err(HF_E_ARG, "hf_copy_chunk_stats: bad argument");
-    if (ctx->pass_rows) return set_err(HF_E_ARG, "hf_copy_chunk_stats: the last pass ran in HF_STATS_ROWS mode (no per-chunk vectors)");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (dst_dev == ctx->d_chunk_stats) return HF_OK;   // bound to the exchange buffer: the kernels already wrote in place
-    HIPCHK(hipMemcpyAsync(dst_dev, ctx->d_chunk_stats, (size_t) ctx->C * ctx->V * 8, hipMemcpyDeviceToDevice,
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
+    if (ps.pass_rows) return set_err(HF_E_ARG, "hf_copy_chunk_stats: the last pass ran in HF_STATS_ROWS mode (no per-chunk vectors)");
+    HIPCHK(hipSetDevice(tr.device));
+    if (dst_dev == ps.d_chunk_stats) return HF_OK;   // bound to the exchange buffer: the kernels already wrote in place
+    HIPCHK(hipMemcpyAsync(dst_dev, ps.d_chunk_stats, (size_t) tr.C * tr.V * 8, hipMemcpyDeviceToDevice,
                           (hipStream_t) stream));
     return HF_OK;
 }
 
 int hf_rank_total(hf_ctx* ctx, double* out_dev, void* stream) {
     if (!ctx || !out_dev) return set_err(HF_E_ARG, "hf_rank_total: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->pass_rows && ctx->pass_nb) return launch_nb_total(ctx, (hipStream_t) stream, out_dev, false);
-    if (ctx->pass_rows && ctx->pass_bound && out_dev == ctx->d_rank_out) return HF_OK;   // hf_bind_rank_total: already there
-    if (ctx->pass_rows && ctx->pass_host_total) {   // the pass sent its partials to the host: the total on the device from the copies in blk_stats / chunk_ll
-        const int wpb = ctx->pass_wpb;
-        const dim3 grid((unsigned) (ctx->R + 1)), blk((unsigned) (64 * wpb));
-#define HF_LATE(KT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rows_total_late<KT>), grid, blk, 0, (hipStream_t) stream, ctx->d_rw_off, wpb, ctx->d_rw_stats, ctx->d_params, \
-                                       ctx->K, ctx->d_chunk_ll, (int64_t) ctx->C, out_dev, done_scratch(ctx->d_done))
-        if (ctx->pass_kc <= 4) HF_LATE(4); else if (ctx->pass_kc <= 8) HF_LATE(8); else HF_LATE(16);
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (ps.pass_rows && ps.pass_nb) return launch_nb_total(ps, (hipStream_t) stream, out_dev, false);
+    if (ps.pass_rows && ps.pass_bound && out_dev == ps.d_rank_out) return HF_OK;   // hf_bind_rank_total: already there
+    if (ps.pass_rows && ps.pass_host_total) {   // the pass sent its partials to the host: the total on the device from the copies in blk_stats / chunk_ll
+        const int wpb = ps.pass_wpb;
+        const dim3 grid((unsigned) (tr.R + 1)), blk((unsigned) (64 * wpb));
+#define HF_LATE(KT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rows_total_late<KT>), grid, blk, 0, (hipStream_t) stream, tr.d_rw_off, wpb, ps.d_rw_stats, ps.d_params, \
+                                       tr.K, ps.d_chunk_ll, (int64_t) tr.C, out_dev, done_scratch(ps.d_done))
+        if (ps.pass_kc <= 4) HF_LATE(4); else if (ps.pass_kc <= 8) HF_LATE(8); else HF_LATE(16);
 #undef HF_LATE
         HIPCHK(hipGetLastError());
         return HF_OK;
     }
-    if (ctx->pass_rows) {   // the pass left its total in d_total (or where it was bound to)
-        hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(256), 0, (hipStream_t) stream, ctx->pass_bound ? ctx->d_rank_out : ctx->d_total, out_dev, ctx->V);
+    if (ps.pass_rows) {   // the pass left its total in d_total (or where it was bound to)
+        hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(256), 0, (hipStream_t) stream, ps.pass_bound ? ps.d_rank_out : ps.d_total, out_dev, tr.V);
         HIPCHK(hipGetLastError());
         return HF_OK;
     }
-    return hf_reduce_chunks_indexed(ctx, ctx->d_chunk_stats, nullptr, ctx->C, out_dev, stream);
+    return hf_reduce_chunks_indexed(ctx, ps.d_chunk_stats, nullptr, tr.C, out_dev, stream);
 }
 
 struct ExchangeGeom { int n_ranks = 0, rows_per_rank = 0, flag_row = 0; };   // n_ranks == 0: no flag rows to merge
-static int reduce_chunks_seq(hf_ctx* ctx, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
+static int reduce_chunks_seq(Pass& ps, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
                              double* out_dev, void* stream, double seq, ExchangeGeom xg = ExchangeGeom()) {
-    if (!ctx || !chunk_stats_dev || !out_dev || n_chunks < 0) return set_err(HF_E_ARG, "hf_reduce_chunks: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    const bool own = chunk_stats_dev == ctx->d_chunk_stats;
-    const unsigned keep = ctx->prof_mask;
-    if (!own) ctx->prof_mask = 0;
+    const Track& tr = *ps.tr;
+    if (!chunk_stats_dev || !out_dev || n_chunks < 0) return set_err(HF_E_ARG, "hf_reduce_chunks: bad argument");
+    HIPCHK(hipSetDevice(tr.device));
+    const bool own = chunk_stats_dev == ps.d_chunk_stats;
+    const unsigned keep = ps.prof_mask;
+    if (!own) ps.prof_mask = 0;
     {
-        KTimer t(ctx, (hipStream_t) stream, HF_K_REDUCE);
-        hipLaunchKernelGGL(k_reduce, dim3((unsigned) (ctx->V + 1)), dim3(64), 0, (hipStream_t) stream, chunk_stats_dev, row_index_dev,
-                           n_chunks, ctx->V, out_dev,
-                           (out_dev == ctx->d_total || out_dev == ctx->d_total_host) ? ctx->d_flags : (const unsigned*) nullptr,
-                           xg.n_ranks, xg.rows_per_rank, xg.flag_row, seq, ctx->d_done, ctx->d_cks);
+        KTimer t(ps, (hipStream_t) stream, HF_K_REDUCE);
+        hipLaunchKernelGGL(k_reduce, dim3((unsigned) (tr.V + 1)), dim3(64), 0, (hipStream_t) stream, chunk_stats_dev, row_index_dev,
+                           n_chunks, tr.V, out_dev,
+                           (out_dev == ps.d_total || out_dev == ps.d_total_host) ? ps.d_flags : (const unsigned*) nullptr,
+                           xg.n_ranks, xg.rows_per_rank, xg.flag_row, seq, ps.d_done, ps.d_cks);
     }
-    ctx->prof_mask = keep;
+    ps.prof_mask = keep;
     HIPCHK(hipGetLastError());
     return HF_OK;
 }
 int hf_reduce_chunks_indexed(hf_ctx* ctx, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
                              double* out_dev, void* stream) {
-    return reduce_chunks_seq(ctx, chunk_stats_dev, row_index_dev, n_chunks, out_dev, stream, 0.0);
+    if (!ctx) return set_err(HF_E_ARG, "hf_reduce_chunks: bad argument");
+    return reduce_chunks_seq(ctx->pass, chunk_stats_dev, row_index_dev, n_chunks, out_dev, stream, 0.0);
 }
 
 int hf_reduce_chunks(hf_ctx* ctx, const double* chunk_stats_dev, int64_t n_chunks, double* out_dev, void* stream) {
@@ -1260,12 +1407,12 @@ int hf_reduce_chunks(hf_ctx* ctx, const double* chunk_stats_dev, int64_t n_chunk
 }
 
 // running sums for hf_kernel_time_sums; the stream has been synchronised
-static void accumulate_kernel_times(hf_ctx* ctx) {
-    if (!ctx->prof_mask) return;
+static void accumulate_kernel_times(Pass& ps) {
+    if (!ps.prof_mask) return;
     for (int i = 0; i < HF_NKERNELS; i++)
-        if (ctx->kran[i]) {
+        if (ps.kran[i]) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ctx->kev[2 * i], ctx->kev[2 * i + 1]) == hipSuccess) { ctx->ksum[i] += ms; ctx->kcount[i]++; ctx->klast[i] = ms; ctx->klast_ok[i] = true; }
+            if (hipEventElapsedTime(&ms, ps.kev[2 * i], ps.kev[2 * i + 1]) == hipSuccess) { ps.ksum[i] += ms; ps.kcount[i]++; ps.klast[i] = ms; ps.klast_ok[i] = true; }
         }
 }
 
@@ -1277,19 +1424,25 @@ static int flags_to_code(unsigned fl) {
     return HF_OK;
 }
 
+// the one-launch segment kernel gave up a wait (flag word `fl`): this pass runs two launches from now on, and the caller repeats the pass
+static bool sync_fallback(Pass& ps, unsigned fl) {
+    if (!(fl & HF_FLAG_SYNC) || !ps.seg_fused) return false;
+    ps.seg_fused = false;
+    std::fprintf(stderr, "[hmm_flagger_hip] one-launch segment kernel: a hand-off timed out; this context falls back to k_seg_prod + k_seg_fb\n");
+    return true;
+}
+
 int hf_check(hf_ctx* ctx, void* stream) {
     if (!ctx) return set_err(HF_E_ARG, "hf_check: bad argument");
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipSetDevice(tr.device));
+    HIPCHK(hipMemcpyAsync(ps.h_flags, ps.d_flags, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    accumulate_kernel_times(ctx);
-    if ((*ctx->h_flags & HF_FLAG_SYNC) && ctx->seg_fused) {   // as hf_finish: two launches from now on, the caller repeats the pass
-        ctx->seg_fused = false;
-        std::fprintf(stderr, "[hmm_flagger_hip] one-launch segment kernel: a hand-off timed out; this context falls back to k_seg_prod + k_seg_fb\n");
+    accumulate_kernel_times(ps);
+    if (sync_fallback(ps, *ps.h_flags))   // as hf_finish
         return set_err(HF_E_RETRY, "a hand-off of the one-launch segment kernel timed out: the context now runs two launches, repeat hf_estep");
-    }
-    return flags_to_code(*ctx->h_flags);
+    return flags_to_code(*ps.h_flags);
 }
 
 // Completion of a pass.  Default: hipStreamSynchronize on the launch stream — the HIP-defined way to see the statistics
@@ -1307,18 +1460,19 @@ int hf_check(hf_ctx* ctx, void* stream) {
 // pattern x position weight, summed mod 2^64) plus the pass's stamp value; the host accepts the block only when what it
 // READ has that checksum — stale data, a stale checksum or both fail the comparison and the host keeps polling.  (A plain
 // XOR was not enough either: the estimator layout repeats values, and two equal stale words cancel — seen once in 300 000.)
-static bool polled_block_consistent(const hf_ctx* ctx) {
-    const double* h = ctx->h_total;
-    const int64_t V = ctx->V;
+static bool polled_block_consistent(const Pass& ps) {
+    const Track& tr = *ps.tr;
+    const double* h = ps.h_total;
+    const int64_t V = tr.V;
     auto bits = [](double d) { unsigned long long u; std::memcpy(&u, &d, 8); return u; };
-    const unsigned long long s = bits(ctx->poll_seq);
-    if (ctx->poll_kind == 2) {
+    const unsigned long long s = bits(ps.poll_seq);
+    if (ps.poll_kind == 2) {
         unsigned long long x = s;
         for (int64_t v = 0; v <= V; v++) x += hf_cks_term(bits(h[v]), v);
         return x == bits(h[V + 2]);
     }
-    const int64_t rstride = 24 * (int64_t) ctx->K + 16;
-    for (int r = 0; r < ctx->R; r++) {
+    const int64_t rstride = 24 * (int64_t) tr.K + 16;
+    for (int r = 0; r < tr.R; r++) {
         unsigned long long x = s;
         for (int64_t v = 0; v < rstride; v++) { const int64_t at = 1 + r * rstride + v; x += hf_cks_term(bits(h[at]), at); }
         if (r == 0) x += hf_cks_term(bits(h[0]), 0) + hf_cks_term(bits(h[V]), V);
@@ -1331,22 +1485,23 @@ static bool polled_block_consistent(const hf_ctx* ctx) {
 // by 64 strided sums and a halving tree), so h_total holds the bits the launch's own last blocks would have written.
 extern "C++" {
 template <int KT>
-static void host_rows_total_t(hf_ctx* ctx) {
-    constexpr int NA = 16 + 9 + 2 + 3 * KT + 1;
-    const double* part = ctx->h_part;
-    const int nblk = ctx->pass_rw_blocks, wpb = ctx->pass_wpb, nt = 64 * wpb, Kctx = ctx->K, nreg = ctx->R;
-    const int64_t V = ctx->V, C = ctx->C;
-    const DevParams* P = ctx->h_params;
+static void host_rows_total_t(Pass& ps) {
+    const Track& tr = *ps.tr;
+    constexpr int NA = (int) stat_acc_len(KT);
+    const double* part = ps.h_part;
+    const int nblk = ps.pass_rw_blocks, wpb = ps.pass_wpb, nt = 64 * wpb, Kctx = tr.K, nreg = tr.R;
+    const int64_t V = tr.V, C = tr.C;
+    const DevParams* P = ps.h_params;
     const int ncol = P->ncomp[3];
     const bool te = P->model_type == HF_MODEL_TRUNC_EXP_GAUSSIAN;
     const int rstride = 24 * Kctx + 16;
-    double* out = ctx->h_total;
+    double* out = ps.h_total;
     int nq = nt / NA;
     nq = nq < 1 ? 1 : (nq > 16 ? 16 : nq);
     for (int r = 0; r < nreg; r++) {
         double* dst = out + 1 + (int64_t) r * rstride;
         for (int v = 0; v < rstride; v++) dst[v] = 0.0;
-        const int w0 = ctx->h_rw_off[(size_t) r] / wpb, w1 = ctx->h_rw_off[(size_t) r + 1] / wpb;
+        const int w0 = tr.h_rw_off[(size_t) r] / wpb, w1 = tr.h_rw_off[(size_t) r + 1] / wpb;
         if (w1 <= w0) continue;
         double red[NA], acc[16][NA];
         for (int q = 0; q < nq; q++) for (int i = 0; i < NA; i++) acc[q][i] = 0.0;
@@ -1387,32 +1542,33 @@ static void host_rows_total_t(hf_ctx* ctx) {
     out[V] = part[(size_t) nblk * NA + (size_t) C];      // the flag word
 }
 }
-static void host_rows_total(hf_ctx* ctx) {
-    if (ctx->pass_kc <= 4) host_rows_total_t<4>(ctx); else if (ctx->pass_kc <= 8) host_rows_total_t<8>(ctx); else host_rows_total_t<16>(ctx);
+static void host_rows_total(Pass& ps) {
+    if (ps.pass_kc <= 4) host_rows_total_t<4>(ps); else if (ps.pass_kc <= 8) host_rows_total_t<8>(ps); else host_rows_total_t<16>(ps);
 }
 
-static int wait_total(hf_ctx* ctx, hipStream_t st, bool polled, double* stats_host, bool host_total = false) {
+static int wait_total(Pass& ps, hipStream_t st, bool polled, double* stats_host, bool host_total = false) {
+    const Track& tr = *ps.tr;
     bool seen = false;
     if (polled) {
-        volatile double* stamp = ctx->h_total + ctx->V + 1;
+        volatile double* stamp = ps.h_total + tr.V + 1;
         const auto t0 = std::chrono::steady_clock::now();
         long spins = 0;
         for (;;) {
-            if (*stamp == ctx->poll_seq) {
+            if (*stamp == ps.poll_seq) {
                 std::atomic_thread_fence(std::memory_order_acquire);
-                if (polled_block_consistent(ctx)) { seen = true; break; }
+                if (polled_block_consistent(ps)) { seen = true; break; }
             }
             __builtin_ia32_pause();
             if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;   // let the stream report
         }
     }
-    if (!seen && ctx->stream_stamp_ok) {
+    if (!seen && ps.stream_stamp_ok) {
         // Completion through the stream itself: a 32-bit value that the command processor writes into the pinned block AFTER
         // everything enqueued before it has completed (hipStreamWriteValue32: a stream-ordered memory operation, so — unlike a
         // stamp written by the kernel, HF_POLL — its order against the kernel's own writes is defined), polled by the host.
         // Measured 4-5 us less per EM step than hipStreamSynchronize.  Bail-out: the stream after 2 s.
-        volatile uint32_t* word = reinterpret_cast<volatile uint32_t*>(ctx->h_flags) + 1;
-        const uint32_t want = ++ctx->stream_stamp;
+        volatile uint32_t* word = reinterpret_cast<volatile uint32_t*>(ps.h_flags) + 1;
+        const uint32_t want = ++ps.stream_stamp;
         if (hipStreamWriteValue32(st, (void*) word, want, 0) == hipSuccess) {
             const auto t0 = std::chrono::steady_clock::now();
             long spins = 0;
@@ -1422,78 +1578,72 @@ static int wait_total(hf_ctx* ctx, hipStream_t st, bool polled, double* stats_ho
             }
             std::atomic_thread_fence(std::memory_order_acquire);
             seen = *word == want;
-        } else { (void) hipGetLastError(); ctx->stream_stamp_ok = false; }
+        } else { (void) hipGetLastError(); ps.stream_stamp_ok = false; }
         if (seen) {
-            accumulate_kernel_times(ctx);
-            if (host_total) host_rows_total(ctx);
-            std::memcpy(stats_host, ctx->h_total, (size_t) ctx->V * 8);
-            const unsigned fl2 = (unsigned) ctx->h_total[ctx->V];
-            if ((fl2 & HF_FLAG_SYNC) && ctx->seg_fused) {
-                ctx->seg_fused = false;
-                std::fprintf(stderr, "[hmm_flagger_hip] one-launch segment kernel: a hand-off timed out; this context falls back to k_seg_prod + k_seg_fb\n");
-                return HF_E_RETRY;
-            }
-            return flags_to_code(fl2);
+            accumulate_kernel_times(ps);
+            if (host_total) host_rows_total(ps);
+            std::memcpy(stats_host, ps.h_total, (size_t) tr.V * 8);
+            const unsigned fl2 = (unsigned) ps.h_total[tr.V];
+            return sync_fallback(ps, fl2) ? HF_E_RETRY : flags_to_code(fl2);
         }
     }
     if (!seen) {
         HIPCHK(hipStreamSynchronize(st));
         // the stream has drained and the stamp still is not there: hipStreamWriteValue32 returns success on this stack but the write
         // does not land where the host polls — stop paying the 2 s bail-out in every later pass
-        if (ctx->stream_stamp_ok && ctx->stream_stamp != 0 &&
-            *(reinterpret_cast<volatile uint32_t*>(ctx->h_flags) + 1) != ctx->stream_stamp) {
-            ctx->stream_stamp_ok = false;
+        if (ps.stream_stamp_ok && ps.stream_stamp != 0 &&
+            *(reinterpret_cast<volatile uint32_t*>(ps.h_flags) + 1) != ps.stream_stamp) {
+            ps.stream_stamp_ok = false;
             std::fprintf(stderr, "[hmm_flagger_hip] the stream's completion stamp did not arrive; passes complete through hipStreamSynchronize from now on\n");
         }
     }
     if (seen && poll_mode() == 2) {   // HF_POLL=debug: did anything still arrive after the block was accepted?
-        std::vector<double> snap(ctx->h_total, ctx->h_total + ctx->V + 1);
+        std::vector<double> snap(ps.h_total, ps.h_total + tr.V + 1);
         HIPCHK(hipStreamSynchronize(st));
-        for (int64_t v = 0; v <= ctx->V; v++)
-            if (std::memcmp(&snap[(size_t) v], &ctx->h_total[v], 8) != 0)
-                std::fprintf(stderr, "[poll debug] seq %.0f kind %d element %ld changed after acceptance: %.17g -> %.17g\n", ctx->poll_seq,
-                             ctx->poll_kind, (long) v, snap[(size_t) v], ctx->h_total[v]);
+        for (int64_t v = 0; v <= tr.V; v++)
+            if (std::memcmp(&snap[(size_t) v], &ps.h_total[v], 8) != 0)
+                std::fprintf(stderr, "[poll debug] seq %.0f kind %d element %ld changed after acceptance: %.17g -> %.17g\n", ps.poll_seq,
+                             ps.poll_kind, (long) v, snap[(size_t) v], ps.h_total[v]);
     }
-    accumulate_kernel_times(ctx);   // events of the kernels before the last one have completed
-    if (host_total) host_rows_total(ctx);
-    std::memcpy(stats_host, ctx->h_total, (size_t) ctx->V * 8);
-    const unsigned fl = (unsigned) ctx->h_total[ctx->V];
-    if ((fl & HF_FLAG_SYNC) && ctx->seg_fused) {   // the one-launch segment kernel gave up a wait: this context runs two launches from now on
-        ctx->seg_fused = false;
-        std::fprintf(stderr, "[hmm_flagger_hip] one-launch segment kernel: a hand-off timed out; this context falls back to k_seg_prod + k_seg_fb\n");
-        return HF_E_RETRY;
-    }
-    return flags_to_code(fl);
+    accumulate_kernel_times(ps);   // events of the kernels before the last one have completed
+    if (host_total) host_rows_total(ps);
+    std::memcpy(stats_host, ps.h_total, (size_t) tr.V * 8);
+    const unsigned fl = (unsigned) ps.h_total[tr.V];
+    return sync_fallback(ps, fl) ? HF_E_RETRY : flags_to_code(fl);
 }
 
-int hf_finish(hf_ctx* ctx, double* stats_host, void* stream) {
-    if (!ctx || !stats_host) return set_err(HF_E_ARG, "hf_finish: bad argument");
+static int pass_finish(Pass& ps, double* stats_host, void* stream) {
+    const Track& tr = *ps.tr;
+    if (!stats_host) return set_err(HF_E_ARG, "hf_finish: bad argument");
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(tr.device));
     // the reduction writes the V+1 doubles into pinned host memory over PCIe: no device-to-host copy afterwards
-    double* out = ctx->d_total_host ? ctx->d_total_host : ctx->d_total;
-    const bool own_total = ctx->pass_rows && !ctx->pass_nb;   // k_row_stats already wrote the total (and the stamp, when polled)
-    const bool polled = own_total ? ctx->pass_polled : poll_ok(ctx, ctx->pass_rows ? HF_K_ROWS_TOTAL : HF_K_REDUCE);
-    const double seq = own_total ? 0.0 : (polled ? next_stamp(ctx) : 0.0);
-    ctx->poll_kind = ctx->pass_rows ? 1 : 2;
+    double* out = ps.d_total_host ? ps.d_total_host : ps.d_total;
+    const bool own_total = ps.pass_rows && !ps.pass_nb;   // k_row_stats already wrote the total (and the stamp, when polled)
+    const bool polled = own_total ? ps.pass_polled : poll_ok(ps, ps.pass_rows ? HF_K_ROWS_TOTAL : HF_K_REDUCE);
+    const double seq = own_total ? 0.0 : (polled ? next_stamp(ps) : 0.0);
+    ps.poll_kind = ps.pass_rows ? 1 : 2;
     int rc = own_total ? HF_OK
-                       : (ctx->pass_rows ? launch_nb_total(ctx, st, out, true, seq)
-                                         : reduce_chunks_seq(ctx, ctx->d_chunk_stats, nullptr, ctx->C, out, stream, seq));
+                       : (ps.pass_rows ? launch_nb_total(ps, st, out, true, seq)
+                                         : reduce_chunks_seq(ps, ps.d_chunk_stats, nullptr, tr.C, out, stream, seq));
     if (rc) return rc;
-    if (pass_events(ctx)) HIPCHK(hipEventRecord(ctx->ev1, st));
-    if (own_total && ctx->pass_bound) {   // the pass wrote its total into a bound exchange slot (hf_bind_rank_total): fetch it from there
-        HIPCHK(hipMemcpyAsync(ctx->h_total, ctx->d_rank_out, (size_t) ctx->V * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ctx->h_total + ctx->V, ctx->d_rank_flag, 8, hipMemcpyDeviceToHost, st));
-    } else if (!ctx->d_total_host)
-        HIPCHK(hipMemcpyAsync(ctx->h_total, ctx->d_total, ((size_t) ctx->V + 1) * 8, hipMemcpyDeviceToHost, st));
-    rc = wait_total(ctx, st, polled, stats_host, own_total && ctx->pass_host_total);
+    if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
+    if (own_total && ps.pass_bound) {   // the pass wrote its total into a bound exchange slot (hf_bind_rank_total): fetch it from there
+        HIPCHK(hipMemcpyAsync(ps.h_total, ps.d_rank_out, (size_t) tr.V * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ps.h_total + tr.V, ps.d_rank_flag, 8, hipMemcpyDeviceToHost, st));
+    } else if (!ps.d_total_host)
+        HIPCHK(hipMemcpyAsync(ps.h_total, ps.d_total, ((size_t) tr.V + 1) * 8, hipMemcpyDeviceToHost, st));
+    rc = wait_total(ps, st, polled, stats_host, own_total && ps.pass_host_total);
     if (rc == HF_E_RETRY) {   // the pass again, in two launches (the packed parameters are still in the pinned block)
-        if (pass_events(ctx)) HIPCHK(hipEventRecord(ctx->ev0, st));
-        rc = enqueue_pass(ctx, &ctx->last_p, ctx->last_mode, st, true);
+        if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev0, st));
+        rc = enqueue_pass(ps, &ps.last_p, ps.last_mode, st, true);
         if (rc) return rc;
-        return hf_finish(ctx, stats_host, stream);
+        return pass_finish(ps, stats_host, stream);
     }
     return rc;
+}
+int hf_finish(hf_ctx* ctx, double* stats_host, void* stream) {
+    return ctx ? pass_finish(ctx->pass, stats_host, stream) : set_err(HF_E_ARG, "hf_finish: bad argument");
 }
 
 // Multi-GPU counterpart of hf_finish: the rows of ALL chunks are in `rows_dev` (all-gathered, row_index_dev maps list
@@ -1503,18 +1653,19 @@ int hf_finish(hf_ctx* ctx, double* stats_host, void* stream) {
 static int finish_rows(hf_ctx* ctx, const double* rows_dev, const int32_t* row_index_dev, int64_t n_rows, ExchangeGeom xg,
                        double* stats_host, void* stream, const char* who) {
     if (!ctx || !rows_dev || !stats_host || n_rows < 0) return set_err(HF_E_ARG, std::string(who) + ": bad argument");
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    double* out = ctx->d_total_host ? ctx->d_total_host : ctx->d_total;
-    const bool polled = poll_ok(ctx, HF_K_REDUCE);
-    const double seq = polled ? next_stamp(ctx) : 0.0;
-    ctx->poll_kind = 2;
-    int rc = reduce_chunks_seq(ctx, rows_dev, row_index_dev, n_rows, out, stream, seq, xg);
+    HIPCHK(hipSetDevice(tr.device));
+    double* out = ps.d_total_host ? ps.d_total_host : ps.d_total;
+    const bool polled = poll_ok(ps, HF_K_REDUCE);
+    const double seq = polled ? next_stamp(ps) : 0.0;
+    ps.poll_kind = 2;
+    int rc = reduce_chunks_seq(ps, rows_dev, row_index_dev, n_rows, out, stream, seq, xg);
     if (rc) return rc;
-    if (pass_events(ctx)) HIPCHK(hipEventRecord(ctx->ev1, st));
-    if (!ctx->d_total_host)
-        HIPCHK(hipMemcpyAsync(ctx->h_total, ctx->d_total, ((size_t) ctx->V + 1) * 8, hipMemcpyDeviceToHost, st));
-    return wait_total(ctx, st, polled, stats_host);
+    if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
+    if (!ps.d_total_host)
+        HIPCHK(hipMemcpyAsync(ps.h_total, ps.d_total, ((size_t) tr.V + 1) * 8, hipMemcpyDeviceToHost, st));
+    return wait_total(ps, st, polled, stats_host);
 }
 
 int hf_finish_gathered(hf_ctx* ctx, const double* rows_dev, const int32_t* row_index_dev, int64_t n_chunks, double* stats_host,
@@ -1533,29 +1684,23 @@ int hf_finish_exchange(hf_ctx* ctx, const double* rows_dev, const int32_t* row_i
 
 int hf_bind_chunk_stats(hf_ctx* ctx, double* rows_dev) {
     if (!ctx) return set_err(HF_E_ARG, "hf_bind_chunk_stats: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (rows_dev) {
-        if (ctx->own_chunk_stats) ctx_free(ctx, ctx->d_chunk_stats);
-        ctx->d_chunk_stats = rows_dev; ctx->own_chunk_stats = false;
-    } else if (!ctx->own_chunk_stats) {
-        ctx->d_chunk_stats = nullptr;
-        HIPCHK(hipMalloc((void**) &ctx->d_chunk_stats, ((size_t) ctx->C * (size_t) ctx->V + 1) * 8));
-        ctx->own_chunk_stats = true;
-    }
+    ctx->pass.d_chunk_stats = rows_dev ? rows_dev : ctx->pass.d_chunk_stats_own;   // (null: the pass's own array again)
     return HF_OK;
 }
 
 int hf_bind_rank_total(hf_ctx* ctx, double* total_dev, double* flag_row_dev) {
     if (!ctx || ((total_dev == nullptr) != (flag_row_dev == nullptr))) return set_err(HF_E_ARG, "hf_bind_rank_total: bad argument");
-    ctx->d_rank_out = total_dev; ctx->d_rank_flag = flag_row_dev;
+    Pass& ps = ctx->pass;
+    ps.d_rank_out = total_dev; ps.d_rank_flag = flag_row_dev;
     return HF_OK;
 }
 
 int hf_write_flag_row(hf_ctx* ctx, double* row_dev, void* stream) {
     if (!ctx || !row_dev) return set_err(HF_E_ARG, "hf_write_flag_row: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->pass_rows && !ctx->pass_nb && ctx->pass_bound && row_dev == ctx->d_rank_flag) return HF_OK;   // written by the pass itself
-    hipLaunchKernelGGL(k_flag_row, dim3(1), dim3(64), 0, (hipStream_t) stream, ctx->d_flags, row_dev);
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (ps.pass_rows && !ps.pass_nb && ps.pass_bound && row_dev == ps.d_rank_flag) return HF_OK;   // written by the pass itself
+    hipLaunchKernelGGL(k_flag_row, dim3(1), dim3(64), 0, (hipStream_t) stream, ps.d_flags, row_dev);
     HIPCHK(hipGetLastError());
     return HF_OK;
 }
@@ -1567,6 +1712,7 @@ int hf_em_iterate(hf_ctx* ctx, hfm_model* model, int mode, int do_mstep, double 
                   void* stream) {
     if (!ctx || !model || !stats_host || (mode != HF_MODE_FULL && mode != HF_MODE_FORWARD_ONLY))
         return set_err(HF_E_ARG, "hf_em_iterate: bad argument");
+    Pass& ps = ctx->pass;
     using clk = std::chrono::steady_clock;
     const auto tp = clk::now();
     hf_params p;
@@ -1584,79 +1730,83 @@ int hf_em_iterate(hf_ctx* ctx, hfm_model* model, int mode, int do_mstep, double 
         const int cv = hfm_estimate(model, stats_host, tol);
         if (converged) *converged = cv;
     }
-    if (ctx->host_trace) {
+    if (ps.host_trace) {
         const auto t3 = clk::now();
         float gpu_ms = 0.f;
-        (void) hipEventElapsedTime(&gpu_ms, ctx->ev0, ctx->ev1);
+        (void) hipEventElapsedTime(&gpu_ms, ps.ev0, ps.ev1);
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        ctx->ht[0] += us(t0, t1); ctx->ht[1] += us(t1, t2); ctx->ht[2] += us(t2, t3); ctx->ht[3] += gpu_ms * 1e3; ctx->ht[4] += us(tp, t0); ctx->ht_n++;
+        ps.ht[0] += us(t0, t1); ps.ht[1] += us(t1, t2); ps.ht[2] += us(t2, t3); ps.ht[3] += gpu_ms * 1e3; ps.ht[4] += us(tp, t0); ps.ht_n++;
     }
     return HF_OK;
 }
 
-int hf_get_labels(hf_ctx* ctx, int8_t* labels_host) {
-    if (!ctx || !labels_host) return set_err(HF_E_ARG, "hf_get_labels: bad argument");
-    if (!ctx->have_full) return set_err(HF_E_ARG, "hf_get_labels: the last pass was not HF_MODE_FULL (a forward-only pass decodes nothing)");
-    HIPCHK(hipSetDevice(ctx->device));
+static int pass_labels(Pass& ps, int8_t* labels_host) {
+    const Track& tr = *ps.tr;
+    if (!labels_host) return set_err(HF_E_ARG, "hf_get_labels: bad argument");
+    if (!ps.have_full) return set_err(HF_E_ARG, "hf_get_labels: the last pass was not HF_MODE_FULL (a forward-only pass decodes nothing)");
+    HIPCHK(hipSetDevice(tr.device));
     // through the context's pinned block (a pageable destination costs a staging copy inside the runtime: the first 1.5 MB download of a
     // process was measured at several milliseconds, in the middle of the command line's EM loop)
     // A KERNEL writes them into the context's pinned block (as the passes write their totals), the host copies them on: a process's first
     // device-to-host COPY into a fresh pinned block was measured at 8.9 ms (the second at 0.15 ms: profiles/r04e_cli_wall.txt) — in the
     // middle of the command line's EM loop, for the "initial" summary tables; the kernel takes ~0.1 ms the first time too.
-    if (!ctx->h_label && ctx->N > 0 && ctx->d_total_host) {
-        char* p = pin_cache().acquire((size_t) ctx->N + 16);
+    if (!ps.h_label && tr.N > 0 && ps.d_total_host) {
+        char* p = pin_cache().acquire((size_t) tr.N + 16);
         void* dp = nullptr;
-        if (p && hipHostGetDevicePointer(&dp, p, 0) == hipSuccess) { ctx->h_label = reinterpret_cast<int8_t*>(p); ctx->d_label_host = reinterpret_cast<int8_t*>(dp); }
+        if (p && hipHostGetDevicePointer(&dp, p, 0) == hipSuccess) { ps.h_label = reinterpret_cast<int8_t*>(p); ps.d_label_host = reinterpret_cast<int8_t*>(dp); }
         else { (void) hipGetLastError(); pin_cache().release(p); }
     }
-    if (ctx->d_label_host && ctx->N > 0) {
-        const int64_t n16 = (ctx->N + 15) / 16;      // (d_label and the pinned block are padded to 16 bytes)
-        hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, ctx->last_stream, reinterpret_cast<const uint4*>(ctx->d_label),
-                           reinterpret_cast<uint4*>(ctx->d_label_host), n16);   // (behind the pass, on its stream)
+    if (ps.d_label_host && tr.N > 0) {
+        const int64_t n16 = (tr.N + 15) / 16;      // (d_label and the pinned block are padded to 16 bytes)
+        hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, ps.last_stream, reinterpret_cast<const uint4*>(ps.d_label),
+                           reinterpret_cast<uint4*>(ps.d_label_host), n16);   // (behind the pass, on its stream)
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(ctx->last_stream));
-        std::memcpy(labels_host, ctx->h_label, (size_t) ctx->N);
-    } else { HIPCHK(hipStreamSynchronize(ctx->last_stream)); HIPCHK(hipMemcpy(labels_host, ctx->d_label, (size_t) ctx->N, hipMemcpyDeviceToHost)); }
+        HIPCHK(hipStreamSynchronize(ps.last_stream));
+        std::memcpy(labels_host, ps.h_label, (size_t) tr.N);
+    } else { HIPCHK(hipStreamSynchronize(ps.last_stream)); HIPCHK(hipMemcpy(labels_host, ps.d_label, (size_t) tr.N, hipMemcpyDeviceToHost)); }
     return HF_OK;
 }
 
-int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_host, double* b_host, double* scales_host) {
-    if (!ctx || first < 0 || n < 0 || first + n > ctx->N) return set_err(HF_E_ARG, "hf_get_forward_backward: bad range");
-    if (!ctx->have_full)   // a forward-only pass of the segment kernels keeps everything in registers: nothing of THIS pass to return
+int hf_get_labels(hf_ctx* ctx, int8_t* labels_host) {
+    return ctx ? pass_labels(ctx->pass, labels_host) : set_err(HF_E_ARG, "hf_get_labels: bad argument");
+}
+
+static int pass_forward_backward(Pass& ps, int64_t first, int64_t n, double* f_host, double* b_host, double* scales_host) {
+    const Track& tr = *ps.tr;
+    if (first < 0 || n < 0 || first + n > tr.N) return set_err(HF_E_ARG, "hf_get_forward_backward: bad range");
+    if (!ps.have_full)   // a forward-only pass of the segment kernels keeps everything in registers: nothing of THIS pass to return
         return set_err(HF_E_ARG, "hf_get_forward_backward: the last pass was not HF_MODE_FULL (forward, backward and scale values would be stale)");
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(tr.device));
     if (n == 0) return HF_OK;
-    HIPCHK(hipStreamSynchronize(ctx->last_stream));   // (the copies below run on the null stream: not ordered against a non-blocking stream by itself)
-    if (scales_host && !ctx->fb_recs) HIPCHK(hipMemcpy(scales_host, ctx->d_scale + first, (size_t) n * 8, hipMemcpyDeviceToHost));
-    if (!f_host && !b_host && !ctx->fb_recs) return HF_OK;
-    if (ctx->fb_recs) {   // pair records (hf_seg.h): b_t is the second half of the record at pos[t], f_t the first half of the one at pos_f[t]
-        if (!ctx->recs_all || !ctx->scales_all) {
+    HIPCHK(hipStreamSynchronize(ps.last_stream));   // (the copies below run on the null stream: not ordered against a non-blocking stream by itself)
+    if (scales_host && !ps.fb_recs) HIPCHK(hipMemcpy(scales_host, ps.d_scale + first, (size_t) n * 8, hipMemcpyDeviceToHost));
+    if (!f_host && !b_host && !ps.fb_recs) return HF_OK;
+    if (ps.fb_recs) {   // pair records (hf_seg.h): b_t is the second half of the record at pos[t], f_t the first half of the one at pos_f[t]
+        if (!ps.recs_all || !ps.scales_all) {
             // the last full pass wrote no scales (statistics by emission row), or ran in sub-passes through the pass buffer (only its last sub-pass's records are left).  The segment kernel once
             // more over all segments, into the all-windows buffer (the tables of the pass are still in place: rows of A, parameters; labels,
             // scales and log-likelihood partials are rewritten with the same values)
-            const int rc_ = all_records_buffer(ctx);
+            const int rc_ = all_records_buffer(ps);
             if (rc_) return rc_;
-            if (!ctx->d_scale_s) HIPCHK(hipMalloc((void**) &ctx->d_scale_s, (size_t) ctx->n_slots * 8));   // the scales: on first use (an EM pass writes none)
+            if (!ps.d_scale_s) HIPCHK(hipMalloc((void**) &ps.d_scale_s, (size_t) tr.n_slots * 8));   // the scales: on first use (an EM pass writes none)
             // On the stream of the pass itself (the null stream is not ordered against a non-blocking user stream), and its flag
             // word is read like a pass's: a hand-off that timed out in THIS launch would otherwise leave silently wrong vectors — the context
             // falls back to two launches and the re-run is repeated; any other flag is the pass's own error, reported as hf_check would.
-            hipStream_t st = ctx->last_stream;
+            hipStream_t st = ps.last_stream;
             for (int attempt = 0;; attempt++) {
-                if (!ctx->seg_fused) {
-                    if (!ctx->d_segQ) HIPCHK(hipMalloc((void**) &ctx->d_segQ, (size_t) ctx->nseg * 64 * 16 * 8));
-                    hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) ctx->nseg), dim3(64), seg_lds_bytes(), st, ctx->d_seg, ctx->d_arow, ctx->d_lutA, ctx->d_segQ, ctx->d_Pseg);
+                if (!ps.seg_fused) {
+                    if (!ps.d_segQ) HIPCHK(hipMalloc((void**) &ps.d_segQ, (size_t) tr.nseg * 64 * 16 * 8));
+                    hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) tr.nseg), dim3(64), seg_lds_bytes(), st, tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_segQ, ps.d_Pseg);
                 }
-                const unsigned epoch = ++ctx->seg_epoch;
-                launch_seg_fb(ctx, st, true, ctx->d_recs_all, -1, epoch, epoch, false);
+                const unsigned epoch = ++ps.seg_epoch;
+                launch_seg_fb(ps, st, true, ps.d_recs_all, -1, epoch, epoch, false);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(ps.h_flags, ps.d_flags, 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
-                const unsigned fl = *ctx->h_flags;
-                if ((fl & HF_FLAG_SYNC) && ctx->seg_fused && attempt == 0) {
-                    ctx->seg_fused = false;
-                    std::fprintf(stderr, "[hmm_flagger_hip] one-launch segment kernel: a hand-off timed out; this context falls back to k_seg_prod + k_seg_fb\n");
+                const unsigned fl = *ps.h_flags;
+                if (attempt == 0 && sync_fallback(ps, fl)) {
                     unsigned keep = fl & ~(unsigned) HF_FLAG_SYNC;        // (the pass's own flags stay for a later hf_check)
-                    HIPCHK(hipMemcpyAsync(ctx->d_flags, &keep, 4, hipMemcpyHostToDevice, st));
+                    HIPCHK(hipMemcpyAsync(ps.d_flags, &keep, 4, hipMemcpyHostToDevice, st));
                     HIPCHK(hipStreamSynchronize(st));
                     continue;
                 }
@@ -1664,21 +1814,21 @@ int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_hos
                 if (code != HF_OK) return code;
                 break;
             }
-            ctx->recs_all = true; ctx->scales_all = true;
+            ps.recs_all = true; ps.scales_all = true;
         }
         // the positions of a range are scattered over the plan: gathered on the device, one copy back (maps uploaded on first use)
-        if (!ctx->d_slot_of) {
-            HIPCHK(hipMalloc((void**) &ctx->d_slot_of, (size_t) ctx->N * 4));
-            std::vector<int32_t> so((size_t) ctx->N, 0);     // window -> slot (the scales are kept in slot order)
-            for (const SegDesc& d : ctx->h_segs)
+        if (!ps.d_slot_of) {
+            HIPCHK(hipMalloc((void**) &ps.d_slot_of, (size_t) tr.N * 4));
+            std::vector<int32_t> so((size_t) tr.N, 0);     // window -> slot (the scales are kept in slot order)
+            for (const SegDesc& d : tr.h_segs)
                 for (int64_t x = 0; x < d.n; x++) so[(size_t) (d.t0 + x)] = seg_slot(d, x);
-            HIPCHK(hipMemcpy(ctx->d_slot_of, so.data(), (size_t) ctx->N * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(ps.d_slot_of, so.data(), (size_t) tr.N * 4, hipMemcpyHostToDevice));
         }
         double* d_out = nullptr;
         HIPCHK(hipMalloc((void**) &d_out, (size_t) n * 9 * 8));
-        hipLaunchKernelGGL(k_gather_fb, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->last_stream, first, n, ctx->d_pos, ctx->d_pos_f, ctx->d_slot_of,
-                           ctx->d_recs_all, ctx->d_scale_s, d_out, d_out + n * 4, d_out + n * 8);
-        HIPCHK(hipStreamSynchronize(ctx->last_stream));
+        hipLaunchKernelGGL(k_gather_fb, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ps.last_stream, first, n, tr.d_pos, tr.d_pos_f, ps.d_slot_of,
+                           ps.d_recs_all, ps.d_scale_s, d_out, d_out + n * 4, d_out + n * 8);
+        HIPCHK(hipStreamSynchronize(ps.last_stream));
         hipError_t e1 = hipSuccess, e2 = hipSuccess, e3 = hipSuccess;
         if (f_host) e1 = hipMemcpy(f_host, d_out, (size_t) n * 32, hipMemcpyDeviceToHost);
         if (b_host) e2 = hipMemcpy(b_host, d_out + n * 4, (size_t) n * 32, hipMemcpyDeviceToHost);
@@ -1691,9 +1841,9 @@ int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_hos
     // put every window's four values back in window order
     constexpr int64_t L = HF_SCAN_L, TW = 64 * L;
     auto locate = [&](int64_t t, int64_t* tile, int* lane, int* j) {
-        size_t c = (size_t) (std::upper_bound(ctx->h_off.begin(), ctx->h_off.end(), t) - ctx->h_off.begin()) - 1;
-        const int64_t w = t - ctx->h_off[c];
-        *tile = ctx->h_tile0[c] + w / TW;
+        size_t c = (size_t) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), t) - tr.h_off.begin()) - 1;
+        const int64_t w = t - tr.h_off[c];
+        *tile = tr.h_tile0[c] + w / TW;
         const int rem = (int) (w % TW);
         *lane = rem / (int) L; *j = rem % (int) L;
     };
@@ -1705,7 +1855,7 @@ int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_hos
     for (int which = 0; which < 2; which++) {
         double* dst = which == 0 ? f_host : b_host;
         if (!dst) continue;
-        const double* src = which == 0 ? ctx->d_f : ctx->d_b;
+        const double* src = which == 0 ? ps.d_f : ps.d_b;
         HIPCHK(hipMemcpy(buf.data(), src + (size_t) tile_lo * tile_doubles, buf.size() * 8, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; i++) {
             int64_t tile;
@@ -1719,10 +1869,14 @@ int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_hos
     return HF_OK;
 }
 
-int hf_get_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
-    if (!ctx || !post_host) return set_err(HF_E_ARG, "hf_get_posterior: bad argument");
+int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_host, double* b_host, double* scales_host) {
+    return ctx ? pass_forward_backward(ctx->pass, first, n, f_host, b_host, scales_host) : set_err(HF_E_ARG, "hf_get_forward_backward: bad range");
+}
+
+static int pass_posterior(Pass& ps, int64_t first, int64_t n, double* post_host) {
+    if (!post_host) return set_err(HF_E_ARG, "hf_get_posterior: bad argument");
     std::vector<double> f((size_t) n * 4), b((size_t) n * 4), sc((size_t) n);
-    int rc = hf_get_forward_backward(ctx, first, n, f.data(), b.data(), sc.data());
+    int rc = pass_forward_backward(ps, first, n, f.data(), b.data(), sc.data());
     if (rc) return rc;
     for (int64_t i = 0; i < n; i++) { // hmm.c:671-685
         double total = 0.0;
@@ -1731,24 +1885,27 @@ int hf_get_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
     }
     return HF_OK;
 }
+int hf_get_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
+    return ctx ? pass_posterior(ctx->pass, first, n, post_host) : set_err(HF_E_ARG, "hf_get_posterior: bad argument");
+}
 
 // ------------------------------------------------------------------------------------------
 // most-probable-path decoding (hf_viterbi.h): its own parameter block, rows, flags and outputs, so that the last pass's getters
 // (which re-run the segment kernel over the pass's tables) and the next pass see nothing of it
 // ------------------------------------------------------------------------------------------
 static int vit_alloc(hf_ctx* ctx) {
-    hf_ctx::Viterbi& v = ctx->vit;
+    const Track& tr = ctx->tr; Viterbi& v = ctx->vit;
     if (v.alloc) return HF_OK;
-    const bool scan = ctx->algo == HF_ALGO_SCAN;
-    const size_t nrow = scan ? (size_t) ctx->n_slots : (size_t) ctx->N, G = scan ? (size_t) ctx->nseg : 0;
-    const size_t nC = (size_t) ctx->C;
+    const bool scan = tr.algo == HF_ALGO_SCAN;
+    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
+    const size_t nC = (size_t) tr.C;
 #define VALLOC(ptr, bytes) HIPCHK(hipMalloc((void**) &(ptr), (bytes) ? (bytes) : 8))
-    HIPCHK(hipHostMalloc((void**) &v.h_params, ctx->params_bytes));
-    VALLOC(v.d_params, ctx->params_bytes);
-    VALLOC(v.d_nbE, (size_t) ctx->R * 4 * HF_NB_NX * 8);
+    HIPCHK(hipHostMalloc((void**) &v.h_params, tr.params_bytes));
+    VALLOC(v.d_params, tr.params_bytes);
+    VALLOC(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8);
     VALLOC(v.d_rows, nrow * 128);
     VALLOC(v.d_bp, nrow);
-    VALLOC(v.d_label, (size_t) ctx->N);
+    VALLOC(v.d_label, (size_t) tr.N);
     VALLOC(v.d_ll, nC * 8);
     VALLOC(v.d_final, nC);
     VALLOC(v.d_flags, 4);
@@ -1763,53 +1920,54 @@ static int vit_alloc(hf_ctx* ctx) {
 }
 
 static void vit_free(hf_ctx* ctx) {
-    hf_ctx::Viterbi& v = ctx->vit;
+    Viterbi& v = ctx->vit;
     if (v.h_params) hipHostFree(v.h_params);
     void* dev[] = {v.d_params, v.d_nbE, v.d_rows, v.d_bp, v.d_label, v.d_ll, v.d_final, v.d_flags, v.d_P, v.d_PE, v.d_S, v.d_SE,
                    v.d_vin, v.d_vinE, v.d_lmap, v.d_smap, v.d_sexit};
     for (void* q : dev) if (q) hipFree(q);
-    v = hf_ctx::Viterbi();
+    v = Viterbi();
 }
 
 int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
     if (!ctx || !p) return set_err(HF_E_ARG, "hf_viterbi: bad argument");
-    hf_ctx::Viterbi& v = ctx->vit;
+    const Track& tr = ctx->tr;
+    Viterbi& v = ctx->vit;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->algo == HF_ALGO_SCAN && ctx->N > 0 && ctx->C > 0 && ctx->nseg == 0)
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
         return set_err(HF_E_ARG, "hf_viterbi: HF_ALGO_SCAN holds at most 2^30 windows per context");
     if (v.launched) HIPCHK(hipDeviceSynchronize());   // a run nobody finished may still be reading the pinned parameter block
     v.launched = false; v.done = false;
     int rc = vit_alloc(ctx);
     if (rc) return rc;
-    rc = pack_params(ctx, p, v.h_params);
+    rc = pack_params(tr, p, v.h_params);
     if (rc) return rc;
     const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
     if (nbm) {
         if (!p->nb_E) return set_err(HF_E_ARG, "hf_viterbi: negative_binomial needs hf_params.nb_E");
-        if (p->nb_max_x > 0 && ctx->M - 1 > p->nb_max_x)
+        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
             return set_err(HF_E_ARG, "hf_viterbi: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
         // (synchronous: the caller's table may be rewritten as soon as this returns)
-        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) ctx->R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, ctx->params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
-    if (ctx->C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) ctx->C * 8, st));   // (chunks without windows: score 0)
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
     const double* nbE = nbm ? v.d_nbE : nullptr;
-    if (ctx->C > 0 && ctx->N > 0) {
-        if (ctx->algo == HF_ALGO_SCAN) {
-            const unsigned G = (unsigned) ctx->nseg, CB = (unsigned) ((ctx->C + 63) / 64);
-            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, ctx->d_seg, ctx->d_rec, ctx->d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
-            hipLaunchKernelGGL(k_vit_prod, dim3(G), dim3(64), 0, st, ctx->d_seg, v.d_rows, v.d_P, v.d_PE, v.d_S, v.d_SE);
-            hipLaunchKernelGGL(k_vit_chain, dim3(CB), dim3(64), 0, st, ctx->C, ctx->d_chunk_seg0, v.d_S, v.d_SE, v.d_vin, v.d_vinE);
-            hipLaunchKernelGGL(k_vit_replay, dim3(G), dim3(64), 0, st, ctx->d_seg, ctx->d_rec, v.d_params, v.d_rows, v.d_P, v.d_PE, v.d_vin,
+    if (tr.C > 0 && tr.N > 0) {
+        if (tr.algo == HF_ALGO_SCAN) {
+            const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64);
+            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
+            hipLaunchKernelGGL(k_vit_prod, dim3(G), dim3(64), 0, st, tr.d_seg, v.d_rows, v.d_P, v.d_PE, v.d_S, v.d_SE);
+            hipLaunchKernelGGL(k_vit_chain, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, v.d_S, v.d_SE, v.d_vin, v.d_vinE);
+            hipLaunchKernelGGL(k_vit_replay, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, v.d_params, v.d_rows, v.d_P, v.d_PE, v.d_vin,
                                v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_ll, v.d_flags);
-            hipLaunchKernelGGL(k_vit_exits, dim3(CB), dim3(64), 0, st, ctx->C, ctx->d_chunk_seg0, v.d_smap, v.d_final, v.d_sexit);
-            hipLaunchKernelGGL(k_vit_back, dim3(G), dim3(64), 0, st, ctx->d_seg, v.d_bp, v.d_lmap, v.d_sexit, v.d_label);
+            hipLaunchKernelGGL(k_vit_exits, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, v.d_smap, v.d_final, v.d_sexit);
+            hipLaunchKernelGGL(k_vit_back, dim3(G), dim3(64), 0, st, tr.d_seg, v.d_bp, v.d_lmap, v.d_sexit, v.d_label);
         } else {
-            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((ctx->N + 255) / 256)), dim3(256), 0, st, ctx->N, ctx->d_rec, ctx->d_beta,
+            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta,
                                v.d_params, nbE, v.d_rows, v.d_flags);
-            hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) ctx->C), dim3(64), 0, st, ctx->d_off, ctx->d_rec, v.d_params, v.d_rows, v.d_bp,
+            hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, v.d_bp,
                                v.d_label, v.d_ll, v.d_flags);
         }
     }
@@ -1820,15 +1978,16 @@ int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
 
 int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
     if (!ctx || !ctx->vit.launched) return set_err(HF_E_ARG, "hf_viterbi_finish: no hf_viterbi to finish");
-    hf_ctx::Viterbi& v = ctx->vit;
-    HIPCHK(hipSetDevice(ctx->device));
+    const Track& tr = ctx->tr;
+    Viterbi& v = ctx->vit;
+    HIPCHK(hipSetDevice(tr.device));
     HIPCHK(hipStreamSynchronize((hipStream_t) stream));
     v.launched = false;
     unsigned fl = 0;
     HIPCHK(hipMemcpy(&fl, v.d_flags, 4, hipMemcpyDeviceToHost));
     if (fl) return flags_to_code(fl);
-    v.h_ll.assign((size_t) ctx->C, 0.0);
-    if (ctx->C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) ctx->C * 8, hipMemcpyDeviceToHost));
+    v.h_ll.assign((size_t) tr.C, 0.0);
+    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
     double tot = 0.0;
     for (double x : v.h_ll) tot += x;   // chunk-list order
     if (log_prob_host) *log_prob_host = tot;
@@ -1838,49 +1997,55 @@ int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
 
 int hf_get_viterbi_labels(hf_ctx* ctx, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_labels: no finished hf_viterbi");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (ctx->N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) ctx->N, hipMemcpyDeviceToHost));
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
     return HF_OK;
 }
 
 int hf_get_viterbi_chunk_log_probs(hf_ctx* ctx, double* out_host) {
     if (!ctx || !out_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_chunk_log_probs: no finished hf_viterbi");
-    if (ctx->C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) ctx->C * 8);
+    const Track& tr = ctx->tr;
+    if (tr.C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) tr.C * 8);
     return HF_OK;
 }
 
 int hf_set_profiling(hf_ctx* ctx, unsigned kernel_mask) {
     if (!ctx) return set_err(HF_E_ARG, "hf_set_profiling: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
+    Pass& ps = ctx->pass; const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
     // timing-only events: no system-scope fence when they fire (the default event writes back and invalidates the caches — k_seg_fb's 130 MB
     // of records would leave the L2 before k_pair_sums reads them: a sampled step was measured 15 us slower than an unsampled one)
-    if (kernel_mask && !ctx->kev[0])
+    if (kernel_mask && !ps.kev[0])
         for (int i = 0; i < 2 * HF_NKERNELS; i++)
-            if (hipEventCreateWithFlags(&ctx->kev[i], hipEventDisableSystemFence) != hipSuccess) { (void) hipGetLastError(); HIPCHK(hipEventCreate(&ctx->kev[i])); }
-    ctx->prof_mask = kernel_mask & (((1u << HF_NKERNELS) - 1u) | HF_PROF_PASS);
-    for (int i = 0; i < HF_NKERNELS; i++) { ctx->kran[i] = false; ctx->ksum[i] = 0.0; ctx->kcount[i] = 0; }
+            if (hipEventCreateWithFlags(&ps.kev[i], hipEventDisableSystemFence) != hipSuccess) { (void) hipGetLastError(); HIPCHK(hipEventCreate(&ps.kev[i])); }
+    ps.prof_mask = kernel_mask & (((1u << HF_NKERNELS) - 1u) | HF_PROF_PASS);
+    for (int i = 0; i < HF_NKERNELS; i++) { ps.kran[i] = false; ps.ksum[i] = 0.0; ps.kcount[i] = 0; }
     return HF_OK;
 }
 
 int hf_set_profiling_stride(hf_ctx* ctx, int every_nth_pass) {
     if (!ctx || every_nth_pass < 1) return set_err(HF_E_ARG, "hf_set_profiling_stride: bad argument");
-    ctx->prof_stride = every_nth_pass; ctx->prof_pass = 0;
+    Pass& ps = ctx->pass;
+    ps.prof_stride = every_nth_pass; ps.prof_pass = 0;
     return HF_OK;
 }
 
 int hf_kernel_time_sums(hf_ctx* ctx, double sum_ms[HF_NKERNELS], int64_t launches[HF_NKERNELS]) {
     if (!ctx || !sum_ms || !launches) return set_err(HF_E_ARG, "hf_kernel_time_sums: bad argument");
-    for (int i = 0; i < HF_NKERNELS; i++) { sum_ms[i] = ctx->ksum[i]; launches[i] = ctx->kcount[i]; }
+    Pass& ps = ctx->pass;
+    for (int i = 0; i < HF_NKERNELS; i++) { sum_ms[i] = ps.ksum[i]; launches[i] = ps.kcount[i]; }
     return HF_OK;
 }
 
 int hf_kernel_times(hf_ctx* ctx, float ms[HF_NKERNELS]) {
-    if (!ctx || !ms || !ctx->prof_mask) return set_err(HF_E_ARG, "hf_kernel_times: profiling is off");
+    if (!ctx || !ms || !ctx->pass.prof_mask) return set_err(HF_E_ARG, "hf_kernel_times: profiling is off");
+    Pass& ps = ctx->pass;
     for (int i = 0; i < HF_NKERNELS; i++) {
         ms[i] = 0.f;
-        if (ctx->kran[i]) {
-            if (ctx->klast_ok[i]) ms[i] = ctx->klast[i];       // hf_finish has read this pair already
-            else HIPCHK(hipEventElapsedTime(&ms[i], ctx->kev[2 * i], ctx->kev[2 * i + 1]));
+        if (ps.kran[i]) {
+            if (ps.klast_ok[i]) ms[i] = ps.klast[i];       // hf_finish has read this pair already
+            else HIPCHK(hipEventElapsedTime(&ms[i], ps.kev[2 * i], ps.kev[2 * i + 1]));
         }
     }
     return HF_OK;
@@ -1942,9 +2107,10 @@ int hf_selftest_exp(int device, int64_t n, const double* x, double* dev_out, dou
 }
 
 int hf_last_kernel_ms(hf_ctx* ctx, float* ms) {
-    if (!ctx || !ms || !ctx->ev_valid) return set_err(HF_E_ARG, "hf_last_kernel_ms: nothing timed yet");
-    HIPCHK(hipEventSynchronize(ctx->ev1));
-    HIPCHK(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+    if (!ctx || !ms || !ctx->pass.ev_valid) return set_err(HF_E_ARG, "hf_last_kernel_ms: nothing timed yet");
+    Pass& ps = ctx->pass;
+    HIPCHK(hipEventSynchronize(ps.ev1));
+    HIPCHK(hipEventElapsedTime(ms, ps.ev0, ps.ev1));
     return HF_OK;
 }
 

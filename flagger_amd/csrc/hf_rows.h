@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) k_pair_sums_compact(int n_groups, const i
 __device__ __forceinline__ void xcu_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ double xcu_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
-// scratch of the hand-offs (hf_ctx.d_done): tickets, then the parts' checksum sums and the log-likelihood for the finalizer
+// scratch of the hand-offs (Pass::d_done): tickets, then the parts' checksum sums and the log-likelihood for the finalizer
 #define HF_DONE_REGION0 1                                    // tickets of region r at HF_DONE_REGION0 + r, r = n_regions: the log-likelihood blocks
 #define HF_DONE_PARTS (HF_DONE_REGION0 + HF_MAXREGIONS + 1)  // ticket of the finished parts
 #define HF_DONE_WORDS (HF_DONE_PARTS + 1)                    // unsigned words; then (8-byte aligned) HF_MAXREGIONS + 1 doubles
