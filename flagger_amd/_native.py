@@ -114,6 +114,10 @@ def lib() -> C.CDLL:
     sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
+    sig("hf_sample_capacity", C.c_int, vp)
+    sig("hf_sample_paths", C.c_int, vp, C.POINTER(hf_params), i64, C.c_int, C.c_uint64, vp)
+    sig("hf_sample_finish", C.c_int, vp, vp)
+    sig("hf_get_sample_labels", C.c_int, vp, C.c_int, C.POINTER(C.c_int8))
     sig("hf_batch_capacity", C.c_int, vp)
     sig("hf_batch_create", C.c_int, vp, C.c_int, C.POINTER(vp))
     sig("hf_batch_destroy", None, vp)

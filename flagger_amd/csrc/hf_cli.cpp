@@ -11,6 +11,8 @@
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,6 +60,8 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"exchange", required_argument, nullptr, 1004},        // chunks (default: bit-identical for every N) | ranks (one vector per GPU: faster)
     {"viterbi", no_argument, nullptr, 1005},               // final labels by most-probable path (hf_viterbi) instead of posterior argmax
     {"sweepAlpha", required_argument, nullptr, 1006},      // one run per alpha TSV of a list, one load (not `alpha...`: --alpha stays unique)
+    {"uncertaintySamples", required_argument, nullptr, 1007},   // N posterior path samples after the final inference (hf_sample_paths)
+    {"uncertaintySeed", required_argument, nullptr, 1008},      // their seed [0]
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -96,7 +100,13 @@ static void usage(const char* program) {
             "                                      viterbi_log_probability.tsv (-P still writes the posterior BED)\n"
             "         --sweepAlpha LIST            one EM run per alpha TSV listed in LIST (one path per line; blank lines and lines starting\n"
             "                                      with # are skipped), the input loaded once: line i writes every output file of an\n"
-            "                                      --alphaTsv run into <outputDir>/alpha_<i>/, and <outputDir>/alpha_sweep.tsv sums them up\n");
+            "                                      --alphaTsv run into <outputDir>/alpha_<i>/, and <outputDir>/alpha_sweep.tsv sums them up\n"
+            "         --uncertaintySamples N       after the final inference, draw N state paths from the posterior with the final parameters\n"
+            "                                      and write posterior_samples_summary.tsv (bases per region and label: final labels, mean,\n"
+            "                                      SD, 2.5/50/97.5 %% quantiles over the samples) and final_label_runs_support.bed (every run of\n"
+            "                                      equal final label: fraction of samples that give the whole run its label, mean fraction of\n"
+            "                                      its windows); one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --uncertaintySeed S          seed of those samples (a sample depends on the seed and its index only) [0]\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -234,6 +244,120 @@ static void write_params(const hfm_model* m, const std::string& dir, const std::
     hfm_write_emission_tsv(m, (dir + "/emission_" + suffix + ".tsv").c_str());
 }
 
+// --uncertaintySamples: N posterior path samples (hf_sample_paths) with the final parameters, reduced on the host per sample as each
+// group of hf_sample_capacity samples comes down.  Two files:
+//   posterior_samples_summary.tsv   per (region, label): the final labels' bases, and over the samples the mean, standard deviation
+//                                   (divisor N - 1) and the values at index floor(q (N-1)) of the sorted N (q = 0.025, 0.5, 0.975) of the
+//                                   bases, and the mean of the windows; region "all", then region_<r>
+//   final_label_runs_support.bed    per maximal run of equal final label over consecutive windows of one contig (the runs of
+//                                   hfio_write_final_bed before --minimumLengths): the fraction of samples in which the whole run has
+//                                   that label, and the mean over samples of the fraction of its windows that have it
+static const char* const kRunLabelNames[] = {"Err", "Dup", "Hap", "Col"};   // the final BED's names (hf_io.cpp kLabelNames)
+
+static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
+                                uint64_t seed, const std::vector<std::string>& labelNames, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    // window i of chunk c covers [s + i W, min(s + (i+1) W - 1, e)]
+    std::vector<int64_t> wbases((size_t) N);
+    std::vector<int32_t> wreg((size_t) N);
+    for (int c = 0; c < C; c++)
+        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+            const int64_t i = t - w.chunk_off[c];
+            const int64_t s = (int64_t) w.chunk_s[c] + i * w.window_len;
+            const int64_t e = std::min<int64_t>((int64_t) w.chunk_s[c] + (i + 1) * w.window_len - 1, (int64_t) w.chunk_e[c]);
+            wbases[(size_t) t] = e - s + 1;
+            wreg[(size_t) t] = (int32_t) (w.annot[t] >> 58);
+        }
+    // the runs of the final labels: a new run where the label changes or a chunk starts a different contig
+    struct LRun { int64_t a, b; int label; int64_t s, e; const char* ctg; };
+    std::vector<LRun> runs;
+    std::vector<int32_t> runOf((size_t) N);
+    const char* preCtg = nullptr;
+    for (int c = 0; c < C; c++) {
+        const char* ctg = hfio_chunk_ctg(tab, c);
+        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+            const int64_t i = t - w.chunk_off[c];
+            const int64_t s = (int64_t) w.chunk_s[c] + i * w.window_len;
+            const int64_t e = s + wbases[(size_t) t] - 1;
+            const bool newCtg = t == w.chunk_off[c] && (!preCtg || strcmp(preCtg, ctg) != 0);
+            if (runs.empty() || newCtg || runs.back().label != finalLabels[t]) runs.push_back(LRun{t, t, finalLabels[t], s, e, ctg});
+            runs.back().b = t + 1; runs.back().e = e;
+            runOf[(size_t) t] = (int32_t) (runs.size() - 1);
+            if (t == w.chunk_off[c]) preCtg = ctg;
+        }
+    }
+    const size_t G = (size_t) R + 1, NR = runs.size();
+    std::vector<int64_t> basesS((size_t) nSamples * G * 4), winS(G * 4, 0), cnt(NR);
+    std::vector<double> support(NR, 0.0), meanFrac(NR, 0.0);
+    std::vector<int64_t> basesFinal(G * 4, 0);
+    for (int64_t t = 0; t < N; t++) {
+        const int l = finalLabels[t];
+        if (l < 0 || l > 3) continue;
+        basesFinal[(size_t) l] += wbases[(size_t) t];
+        basesFinal[((size_t) wreg[(size_t) t] + 1) * 4 + (size_t) l] += wbases[(size_t) t];
+    }
+    std::vector<int8_t> lab((size_t) N);
+    hf_params p;
+    hfm_params(model, &p);
+    const int cap = hf_sample_capacity(ctx);
+    if (cap < 1) return cap < 0 ? cap : HF_E_ARG;
+    for (int k0 = 0; k0 < nSamples; k0 += cap) {
+        const int n = std::min(cap, nSamples - k0);
+        int rc = hf_sample_paths(ctx, &p, k0, n, seed, nullptr);
+        if (rc == HF_OK) rc = hf_sample_finish(ctx, nullptr);
+        if (rc != HF_OK) return rc;
+        for (int k = 0; k < n; k++) {
+            if ((rc = hf_get_sample_labels(ctx, k, lab.data())) != HF_OK) return rc;
+            int64_t* b = basesS.data() + (size_t) (k0 + k) * G * 4;
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (int64_t t = 0; t < N; t++) {
+                const size_t l = (size_t) lab[(size_t) t], g = (size_t) wreg[(size_t) t] + 1;
+                b[l] += wbases[(size_t) t]; b[g * 4 + l] += wbases[(size_t) t];
+                winS[l]++; winS[g * 4 + l]++;
+                const int32_t r = runOf[(size_t) t];
+                cnt[(size_t) r] += (int) l == runs[(size_t) r].label;
+            }
+            for (size_t r = 0; r < NR; r++) {
+                const int64_t len = runs[r].b - runs[r].a;
+                support[r] += cnt[r] == len;
+                meanFrac[r] += (double) cnt[r] / (double) len;
+            }
+        }
+    }
+    const std::string sp = dir + "/posterior_samples_summary.tsv";
+    FILE* f = fopen(sp.c_str(), "w");
+    if (!f) { hf_cli_set_error(sp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#Region\tLabel\tBases_Final\tBases_Mean\tBases_SD\tBases_Q025\tBases_Q500\tBases_Q975\tWindows_Mean\n");
+    std::vector<int64_t> v((size_t) nSamples);
+    for (size_t g = 0; g < G; g++)
+        for (size_t l = 0; l < 4; l++) {
+            double mean = 0.0, ss = 0.0;
+            for (int k = 0; k < nSamples; k++) { v[(size_t) k] = basesS[((size_t) k * G + g) * 4 + l]; mean += (double) v[(size_t) k]; }
+            mean /= nSamples;
+            for (int k = 0; k < nSamples; k++) ss += ((double) v[(size_t) k] - mean) * ((double) v[(size_t) k] - mean);
+            const double sd = nSamples > 1 ? std::sqrt(ss / (nSamples - 1)) : 0.0;
+            std::sort(v.begin(), v.end());
+            auto q = [&](double x) { return v[(size_t) std::floor(x * (nSamples - 1))]; };
+            const std::string region = g == 0 ? std::string("all") : "region_" + std::to_string(g - 1);
+            const char* name = labelNames.size() > l ? labelNames[l].c_str() : kRunLabelNames[l];
+            fprintf(f, "%s\t%s\t%ld\t%.4f\t%.4f\t%ld\t%ld\t%ld\t%.4f\n", region.c_str(), name, (long) basesFinal[g * 4 + l], mean, sd,
+                    (long) q(0.025), (long) q(0.5), (long) q(0.975), (double) winS[g * 4 + l] / nSamples);
+        }
+    if (fclose(f) != 0) { hf_cli_set_error(sp + " cannot be written"); return HF_E_ARG; }
+    const std::string bp = dir + "/final_label_runs_support.bed";
+    f = fopen(bp.c_str(), "w");
+    if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#ctg\tstart\tend\tlabel\tsupport\tmean_fraction\n");
+    for (size_t r = 0; r < NR; r++)
+        fprintf(f, "%s\t%ld\t%ld\t%s\t%.4f\t%.4f\n", runs[r].ctg, (long) runs[r].s, (long) runs[r].e + 1,
+                runs[r].label >= 0 && runs[r].label < 4 ? kRunLabelNames[runs[r].label] : "Unk", support[r] / nSamples, meanFrac[r] / nSamples);
+    if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
     FILE* f = fopen(listPath, "r");
@@ -272,6 +396,8 @@ int main(int argc, char* argv[]) {
     double initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
     bool viterbi = false;
+    int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
+    uint64_t uncertaintySeed = 0;
     int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1, loopbackRanks = 0;
     const char* binArrayFilePath = nullptr;
     bool writeBenchmarkingStatsPerIteration = false;
@@ -341,6 +467,19 @@ int main(int argc, char* argv[]) {
             case 1003: nGpus = atoi(optarg); break;
             case 1005: viterbi = true; break;
             case 1006: sweepListPath = optarg; break;
+            case 1007: {
+                char* end = nullptr;
+                const long v = strtol(optarg, &end, 10);
+                uncertaintySet = true;
+                uncertaintySamples = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
+                break;
+            }
+            case 1008: {
+                char* end = nullptr;
+                uncertaintySeed = strtoull(optarg, &end, 10);
+                uncertaintySeedBad = end == optarg || *end != 0 || optarg[0] == '-';
+                break;
+            }
             case 1004:
                 if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
                 else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
@@ -362,6 +501,13 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[phase] %-28s %8.1f ms\n", name, (now - phaseStart) * 1e3);
         phaseStart = now;
     };
+    // --uncertaintySamples: refused combinations, before the input is read
+    if (uncertaintySet && uncertaintySamples < 1) { fprintf(stderr, "[%s] Error: --uncertaintySamples should be a positive integer.\n", ts()); return EXIT_FAILURE; }
+    if (uncertaintySeedBad) { fprintf(stderr, "[%s] Error: --uncertaintySeed should be a non-negative integer.\n", ts()); return EXIT_FAILURE; }
+    if (uncertaintySamples > 0 && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --uncertaintySamples runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
     // test transport, not an option: HF_LOOPBACK_RANKS=N runs N ranks that share ONE GPU (no RCCL) through the multi-GPU path
     if (const char* e = getenv("HF_LOOPBACK_RANKS")) loopbackRanks = atoi(e);
     if (nGpus < 0 || nGpus > 64 || loopbackRanks < 0 || loopbackRanks > 64) { fprintf(stderr, "[%s] Error: --gpus should be between 1 and 64.\n", ts()); return EXIT_FAILURE; }
@@ -622,6 +768,16 @@ int main(int argc, char* argv[]) {
     if (hfio_write_final_bed(tab, finalLabels, (dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
         fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), dir.c_str());
         return EXIT_FAILURE;
+    }
+    // --uncertaintySamples: after every other output of the run (they do not depend on it)
+    if (uncertaintySamples > 0) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --uncertaintySamples needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        fprintf(stderr, "[%s] [Final Inference] Drawing %d posterior state paths (seed %llu) ...\n", ts(), uncertaintySamples,
+                (unsigned long long) uncertaintySeed);
+        const double t0 = real_time();
+        if ((rc = write_sample_outputs(run.ctx, model, tab, finalLabels, uncertaintySamples, uncertaintySeed, labelNames, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] posterior_samples_summary.tsv and final_label_runs_support.bed are written (%.1f ms).\n", ts(),
+                (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

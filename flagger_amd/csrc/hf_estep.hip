@@ -241,6 +241,7 @@ static void par_chunks(const int64_t* chunk_off, size_t C, Fn fn, size_t parts_p
 }
 struct hf_ctx;
 static void vit_free(hf_ctx* ctx);                 // the buffers of hf_viterbi (hf_destroy)
+static void smp_free(hf_ctx* ctx);                 // the buffers of hf_sample_paths (hf_destroy)
 // slot of a segment's x-th window: lane x / L holds it as its x % L-th (hf_seg.h)
 static inline int32_t seg_slot(const SegDesc& d, int64_t x) { return d.slot0 + (int32_t) ((x % d.L) * 64 + x / d.L); }
 static int set_err(int code, const std::string& msg) { g_err = msg; return code; }
@@ -431,11 +432,32 @@ struct Viterbi {
     std::vector<double> h_ll;                  // chunk scores of the last finished run
 };
 
-// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoder's buffers
+// posterior path sampling (hf_sample.h): buffers of its own, allocated by the first hf_sample_paths, never shared with a pass or Viterbi.
+// The fixed part is allocated once; the per-sample part holds `cap` samples and is reallocated when a call asks for more.
+struct Sampler {
+    DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
+    double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
+    double* d_P = nullptr; double* d_S = nullptr; double* d_vin = nullptr;   // SCAN: phases A, B
+    unsigned* d_flags = nullptr;
+    bool alloc = false;
+    // per sample k of a call
+    int cap = 0;
+    uint64_t* d_keys = nullptr;                // [cap] key_k
+    uint8_t* d_maps = nullptr;                 // [cap][n_slots] (SCAN, slot order) / [cap][N] (SEQ, window order) map bytes
+    int8_t* d_final = nullptr;                 // [cap][C] final states (SCAN)
+    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: [cap][nseg][64], [cap][nseg], [cap][nseg]
+    int8_t* d_label = nullptr;                 // [cap][N], the layout of hf_labels_dev per sample
+    std::vector<uint64_t> h_keys;
+    bool launched = false, done = false;
+    int n = 0;                                 // samples of the last call (the getters answer for it once it is finished)
+};
+
+// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers
 struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
+    Sampler smp;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -971,6 +993,7 @@ void hf_destroy(hf_ctx* ctx) {
                      ps.ht_n, ps.ht[4] / ps.ht_n, ps.ht[0] / ps.ht_n, ps.ht[1] / ps.ht_n, ps.ht[2] / ps.ht_n, ps.ht[3] / ps.ht_n);
     pass_destroy(ctx->pass);
     vit_free(ctx);
+    smp_free(ctx);
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2117,3 +2140,167 @@ int hf_last_kernel_ms(hf_ctx* ctx, float* ms) {
 } // extern "C"
 
 #include "hf_batch.h"
+
+// ------------------------------------------------------------------------------------------
+// posterior path sampling (hf_sample.h): its own parameter block, rows, flags and outputs — the last pass's getters, Viterbi's and the
+// next pass see nothing of it.  Last in the file, its kernels included, so that no existing kernel's code moves relative to the
+// ones around it.
+// ------------------------------------------------------------------------------------------
+#include "hf_sample.h"
+
+struct SmpSizes { size_t fixed, per; };
+static SmpSizes smp_sizes(const Track& tr) {
+    const bool scan = tr.algo == HF_ALGO_SCAN;
+    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
+    auto gr = [](size_t b) { return ((b ? b : 8) + 255) & ~(size_t) 255; };   // (hipMalloc's granule, roughly)
+    SmpSizes z;
+    z.fixed = gr(tr.params_bytes) + gr((size_t) tr.R * 4 * HF_NB_NX * 8) + gr(nrow * 128) + gr(4);
+    if (scan) z.fixed += gr(G * 16 * 64 * 8) + gr(G * 16 * 8) + gr(G * 4 * 8);
+    z.per = 8 + nrow + (size_t) tr.N + (scan ? (size_t) tr.C + G * 66 : 0);   // key, maps, labels; SCAN: final states, lane / segment maps, exits
+    return z;
+}
+
+static void smp_free_samples(Sampler& s) {
+    void* dev[] = {s.d_keys, s.d_maps, s.d_final, s.d_lmap, s.d_smap, s.d_sexit, s.d_label};
+    for (void* q : dev) if (q) hipFree(q);
+    s.d_keys = nullptr; s.d_maps = nullptr; s.d_final = nullptr; s.d_lmap = nullptr; s.d_smap = nullptr; s.d_sexit = nullptr; s.d_label = nullptr;
+    s.cap = 0;
+}
+
+static int smp_alloc(hf_ctx* ctx, int n) {
+    const Track& tr = ctx->tr; Sampler& s = ctx->smp;
+    const bool scan = tr.algo == HF_ALGO_SCAN;
+    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
+#define SALLOC(ptr, bytes) HIPCHK(hipMalloc((void**) &(ptr), (bytes) ? (bytes) : 8))
+    if (!s.alloc) {
+        HIPCHK(hipHostMalloc((void**) &s.h_params, tr.params_bytes));
+        SALLOC(s.d_params, tr.params_bytes);
+        SALLOC(s.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8);
+        SALLOC(s.d_rows, nrow * 128);
+        SALLOC(s.d_flags, 4);
+        if (scan) { SALLOC(s.d_P, G * 16 * 64 * 8); SALLOC(s.d_S, G * 16 * 8); SALLOC(s.d_vin, G * 4 * 8); }
+        s.alloc = true;
+    }
+    if (n > s.cap) {
+        smp_free_samples(s);
+        const size_t k = (size_t) n;
+        SALLOC(s.d_keys, k * 8);
+        SALLOC(s.d_maps, k * nrow);
+        SALLOC(s.d_label, k * (size_t) tr.N);
+        if (scan) {
+            SALLOC(s.d_final, k * (size_t) tr.C);
+            SALLOC(s.d_lmap, k * G * 64); SALLOC(s.d_smap, k * G); SALLOC(s.d_sexit, k * G);
+        }
+        s.cap = n;
+    }
+#undef SALLOC
+    return HF_OK;
+}
+
+static void smp_free(hf_ctx* ctx) {
+    Sampler& s = ctx->smp;
+    smp_free_samples(s);
+    if (s.h_params) hipHostFree(s.h_params);
+    void* dev[] = {s.d_params, s.d_nbE, s.d_rows, s.d_P, s.d_S, s.d_vin, s.d_flags};
+    for (void* q : dev) if (q) hipFree(q);
+    s = Sampler();
+}
+
+// the largest grid.y of the per-sample launches
+#define HF_SMP_MAX_PER_CALL 65535
+
+int hf_sample_capacity(const hf_ctx* ctx) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_sample_capacity: bad argument");
+    const Track& tr = ctx->tr; const Sampler& s = ctx->smp;
+    HIPCHK(hipSetDevice(tr.device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const SmpSizes z = smp_sizes(tr);
+    // what the sampler holds already counts as free: a call reuses (or replaces) it
+    const double held = (s.alloc ? (double) z.fixed : 0.0) + (double) s.cap * (double) z.per;
+    const double budget = 0.9 * ((double) free_b + held) - (double) z.fixed;
+    if (budget < (double) z.per) return 0;
+    const double cap = std::floor(budget / (double) z.per);
+    return cap > HF_SMP_MAX_PER_CALL ? HF_SMP_MAX_PER_CALL : (int) cap;
+}
+
+int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n_samples, uint64_t seed, void* stream) {
+    if (!ctx || !p) return set_err(HF_E_ARG, "hf_sample_paths: bad argument");
+    if (n_samples < 1) return set_err(HF_E_ARG, "hf_sample_paths: n_samples must be >= 1");
+    if (first_sample < 0) return set_err(HF_E_ARG, "hf_sample_paths: first_sample must be >= 0");
+    const Track& tr = ctx->tr;
+    Sampler& s = ctx->smp;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
+        return set_err(HF_E_ARG, "hf_sample_paths: HF_ALGO_SCAN holds at most 2^30 windows per context");
+    if (s.launched) HIPCHK(hipDeviceSynchronize());   // a call nobody finished may still be reading the pinned parameter block and the keys
+    s.launched = false; s.done = false;
+    if (n_samples > s.cap) {
+        const int cap = hf_sample_capacity(ctx);
+        if (cap < 0) return cap;
+        if (n_samples > cap) return set_err(HF_E_ARG, "hf_sample_paths: n_samples exceeds hf_sample_capacity (" + std::to_string(cap) + ")");
+    }
+    int rc = smp_alloc(ctx, n_samples);
+    if (rc) return rc;
+    rc = pack_params(tr, p, s.h_params);
+    if (rc) return rc;
+    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
+    if (nbm) {
+        if (!p->nb_E) return set_err(HF_E_ARG, "hf_sample_paths: negative_binomial needs hf_params.nb_E");
+        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
+            return set_err(HF_E_ARG, "hf_sample_paths: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
+        HIPCHK(hipMemcpy(s.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+    }
+    s.h_keys.resize((size_t) n_samples);
+    for (int k = 0; k < n_samples; k++) s.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first_sample + k));
+    HIPCHK(hipMemcpy(s.d_keys, s.h_keys.data(), (size_t) n_samples * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpyAsync(s.d_params, s.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(s.d_flags, 0, 4, st));
+    const double* nbE = nbm ? s.d_nbE : nullptr;
+    if (tr.C > 0 && tr.N > 0) {
+        if (tr.algo == HF_ALGO_SCAN) {
+            const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64), K = (unsigned) n_samples;
+            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, s.d_params, nbE, s.d_rows, s.d_flags);
+            hipLaunchKernelGGL(k_smp_prod, dim3(G), dim3(64), 0, st, tr.d_seg, s.d_rows, s.d_P, s.d_S);
+            hipLaunchKernelGGL(k_smp_chain, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, s.d_S, s.d_vin);
+            hipLaunchKernelGGL(k_smp_replay, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, s.d_params, s.d_rows, s.d_P, s.d_vin, s.d_keys,
+                               n_samples, tr.N, tr.C, tr.n_slots, s.d_maps, s.d_final, s.d_flags);
+            hipLaunchKernelGGL(k_smp_maps, dim3(G, K), dim3(64), 0, st, tr.d_seg, s.d_maps, tr.n_slots, (int) G, s.d_lmap, s.d_smap);
+            hipLaunchKernelGGL(k_smp_exits, dim3(CB, K), dim3(64), 0, st, tr.C, (int) G, tr.d_chunk_seg0, s.d_smap, s.d_final, s.d_sexit);
+            hipLaunchKernelGGL(k_smp_back, dim3(G, K), dim3(64), 0, st, tr.d_seg, s.d_maps, tr.n_slots, (int) G, tr.N, s.d_lmap, s.d_sexit,
+                               s.d_label);
+        } else {
+            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta,
+                               s.d_params, nbE, s.d_rows, s.d_flags);
+            hipLaunchKernelGGL(k_smp_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, s.d_params, s.d_rows, s.d_keys,
+                               n_samples, tr.N, tr.C, s.d_maps, s.d_label, s.d_flags);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    s.n = n_samples;
+    s.launched = true;
+    return HF_OK;
+}
+
+int hf_sample_finish(hf_ctx* ctx, void* stream) {
+    if (!ctx || !ctx->smp.launched) return set_err(HF_E_ARG, "hf_sample_finish: no hf_sample_paths to finish");
+    Sampler& s = ctx->smp;
+    HIPCHK(hipSetDevice(ctx->tr.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    s.launched = false;
+    unsigned fl = 0;
+    HIPCHK(hipMemcpy(&fl, s.d_flags, 4, hipMemcpyDeviceToHost));
+    if (fl) return flags_to_code(fl);
+    s.done = true;
+    return HF_OK;
+}
+
+int hf_get_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->smp.done) return set_err(HF_E_ARG, "hf_get_sample_labels: no finished hf_sample_paths");
+    if (k < 0 || k >= ctx->smp.n) return set_err(HF_E_ARG, "hf_get_sample_labels: k out of range");
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->smp.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}

@@ -551,6 +551,34 @@ class EMList:
         N.check(self._L.hf_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_chunk_log_probs")
         return labels, ll, float(lp.value)
 
+    @property
+    def sample_capacity(self) -> int:
+        """Samples one hf_sample_paths call may draw (nine tenths of the free device memory; hf_sample_capacity)."""
+        cap = int(self._L.hf_sample_capacity(self._h))
+        if cap < 0:
+            raise N.HFError(cap, "hf_sample_capacity")
+        return cap
+
+    def sample_paths(self, model: HMM, n_samples: int, seed: int, first_sample: int = 0) -> np.ndarray:
+        """Posterior path samples first_sample .. first_sample + n_samples - 1 (hf_sample_paths, in calls of at most
+        sample_capacity samples): int8[n_samples][n_windows].  The last pass's results and Viterbi's are left as they were."""
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("sample_paths: n_samples must be >= 1")
+        p = model.params()
+        out = np.empty((n_samples, self.store.n_windows), dtype=np.int8)
+        cap = self.sample_capacity
+        if cap < 1:
+            raise N.HFError(N.HF_E_ARG, "hf_sample_capacity: no room for one sample")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for k0 in range(0, n_samples, cap):
+            n = min(cap, n_samples - k0)
+            N.check(self._L.hf_sample_paths(self._h, C.byref(p), int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths")
+            N.check(self._L.hf_sample_finish(self._h, self.stream), "hf_sample_finish")
+            for k in range(n):
+                N.check(self._L.hf_get_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_sample_labels")
+        return out
+
     def forward_backward(self, first: int = 0, n: Optional[int] = None):
         n = self.store.n_windows - first if n is None else n
         f, b, sc = np.empty((n, 4)), np.empty((n, 4)), np.empty(n)
@@ -588,6 +616,14 @@ def EM_runViterbiForList(emList, model: HMM):
     if not hasattr(emList, "viterbi"):
         raise TypeError("EM_runViterbiForList: %s has no most-probable-path decoder" % type(emList).__name__)
     return emList.viterbi(model)
+
+
+def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:
+    """Draws of whole state paths from P(path | data) with the model's current parameters (forward filtering, backward sampling; no
+    counterpart in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k) alone.  `emList`: an EMList."""
+    if not hasattr(emList, "sample_paths"):
+        raise TypeError("EM_samplePathsForList: %s has no path sampler" % type(emList).__name__)
+    return emList.sample_paths(model, n_samples, seed)
 
 
 class EMBatch:

@@ -244,6 +244,28 @@ int hf_viterbi_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_labels(hf_ctx *ctx, int8_t *labels_host);                          /* [n_windows], layout of hf_labels_dev */
 int hf_get_viterbi_chunk_log_probs(hf_ctx *ctx, double *out_host);                    /* [n_chunks] */
 
+/* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
+ * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
+ *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]
+ * (the distribution whose marginals hf_get_posterior returns).  Uniforms are counter-based, so a sample depends only on
+ * (seed, absolute sample index, window index): not on the algorithm, the segment plan or how samples are grouped into calls.
+ * With splitmix64(x) the standard finaliser of x + 0x9E3779B97F4A7C15:
+ *   key_k  = splitmix64(seed ^ splitmix64(k))           k = absolute sample index
+ *   u(k,i) = (splitmix64(key_k + i) >> 11) * 2^-53      i = global window index t (the draw of window t),
+ *                                                       i = n_windows + c (the final-state draw of chunk c)
+ * Draw rule: window t >= 1 of a chunk, state s at t: w_p = alpha_{t-1}[p] * A_t[p][s] (alpha: the forward vector, any power-of-two
+ * scale), c_0 = w_0, c_p = c_{p-1} + w_p, x = u * c_3; the state at t-1 is the smallest p with x < c_p, else the largest p with
+ * w_p > 0, else 0.  The final state: the same rule with w_s = alpha_{T-1}[s] * end[s].
+ * hf_sample_paths draws samples first_sample .. first_sample + n_samples - 1 asynchronously on `stream`; hf_sample_finish waits and
+ * translates the flags (HF_E_NAN: a NaN in a row or the end column, HF_E_SCALE: a chunk's forward vector or final weights all 0).
+ * HF_E_ARG: n_samples < 1 or above hf_sample_capacity (samples per call that fit nine tenths of the free device memory), k out of
+ * range, a getter before any finished call.  The sampler's buffers are its own: the last pass's results, Viterbi's and the next
+ * hf_estep are unaffected. */
+int hf_sample_capacity(const hf_ctx *ctx);
+int hf_sample_paths(hf_ctx *ctx, const hf_params *p, int64_t first_sample, int n_samples, uint64_t seed, void *stream);
+int hf_sample_finish(hf_ctx *ctx, void *stream);
+int hf_get_sample_labels(hf_ctx *ctx, int k, int8_t *labels_host);                    /* sample first_sample + k, [n_windows] */
+
 /* Many models on one context (flagger_amd/csrc/hf_batch.h): e.g. one EM per candidate alpha matrix over the same track, with the
  * windows loaded, uploaded and planned once.  A batch keeps the pass state of n_models models beside the context: every model has its
  * own parameter block, tables, rows of A, hand-off flags and epochs, pair records, sums, labels, error flags and result block, and shares
