@@ -239,9 +239,6 @@ static void par_chunks(const int64_t* chunk_off, size_t C, Fn fn, size_t parts_p
     work();
     for (auto& t : th) t.join();
 }
-struct hf_ctx;
-static void vit_free(hf_ctx* ctx);                 // the buffers of hf_viterbi (hf_destroy)
-static void smp_free(hf_ctx* ctx);                 // the buffers of hf_sample_paths (hf_destroy)
 // slot of a segment's x-th window: lane x / L holds it as its x % L-th (hf_seg.h)
 static inline int32_t seg_slot(const SegDesc& d, int64_t x) { return d.slot0 + (int32_t) ((x % d.L) * 64 + x / d.L); }
 static int set_err(int code, const std::string& msg) { g_err = msg; return code; }
@@ -419,28 +416,30 @@ struct Pass {
     unsigned seg_epoch = 0;        // hand-off flags of the one-launch segment kernel are stamped with the launch's epoch
 };
 
-// most-probable-path decoding (hf_viterbi.h): buffers of its own, allocated by the first hf_viterbi, never shared with a pass
-struct Viterbi {
-    DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
+// THE DECODER STATE of the path decoders (hf_decode.h): buffers of its own, allocated by the decoder's first call, never shared with a pass or
+// the other decoder.  The device arrays come out of a slab sized by the decoder's layout (vit_arrays, smp_arrays).
+struct Decoder {
+    Slab slab;
+    DevParams* h_params = nullptr;             // pinned
+    DevParams* d_params = nullptr; double* d_nbE = nullptr; unsigned* d_flags = nullptr;
     double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
-    uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
-    int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr; unsigned* d_flags = nullptr;
-    double* d_P = nullptr; int* d_PE = nullptr; double* d_S = nullptr; int* d_SE = nullptr;   // SCAN: phase A
-    double* d_vin = nullptr; long long* d_vinE = nullptr;                                      // SCAN: phase B
-    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;          // SCAN: phases C, D
+    double* d_P = nullptr; double* d_S = nullptr; double* d_vin = nullptr;     // SCAN: phases A, B
+    int* d_PE = nullptr; int* d_SE = nullptr; long long* d_vinE = nullptr;     // ... their exponent sums (a decoder with a score)
     bool alloc = false, launched = false, done = false;
+    void release() { if (h_params) hipHostFree(h_params); slab.release(); }
+};
+
+// most-probable-path decoding (hf_viterbi.h)
+struct Viterbi : Decoder {
+    uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
+    int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr;
+    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: phases C, D
     std::vector<double> h_ll;                  // chunk scores of the last finished run
 };
 
-// posterior path sampling (hf_sample.h): buffers of its own, allocated by the first hf_sample_paths, never shared with a pass or Viterbi.
-// The fixed part is allocated once; the per-sample part holds `cap` samples and is reallocated when a call asks for more.
-struct Sampler {
-    DevParams* h_params = nullptr; DevParams* d_params = nullptr; double* d_nbE = nullptr;
-    double2* d_rows = nullptr;                 // SCAN: [n_slots][8] slot-ordered pieces; SEQ: [N][8] window order
-    double* d_P = nullptr; double* d_S = nullptr; double* d_vin = nullptr;   // SCAN: phases A, B
-    unsigned* d_flags = nullptr;
-    bool alloc = false;
-    // per sample k of a call
+// posterior path sampling (hf_sample.h).  The per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more.
+struct Sampler : Decoder {
+    Slab samples;
     int cap = 0;
     uint64_t* d_keys = nullptr;                // [cap] key_k
     uint8_t* d_maps = nullptr;                 // [cap][n_slots] (SCAN, slot order) / [cap][N] (SEQ, window order) map bytes
@@ -448,8 +447,8 @@ struct Sampler {
     uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: [cap][nseg][64], [cap][nseg], [cap][nseg]
     int8_t* d_label = nullptr;                 // [cap][N], the layout of hf_labels_dev per sample
     std::vector<uint64_t> h_keys;
-    bool launched = false, done = false;
     int n = 0;                                 // samples of the last call (the getters answer for it once it is finished)
+    void release() { samples.release(); Decoder::release(); }
 };
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers
@@ -561,7 +560,6 @@ __global__ void k_pos_f(const int64_t* __restrict__ off, const int32_t* __restri
 #include "hf_rows.h"
 #include "hf_nb_rows.h"
 #include "hf_seg.h"
-#include "hf_viterbi.h"
 
 
 // ------------------------------------------------------------------------------------------
@@ -992,8 +990,8 @@ void hf_destroy(hf_ctx* ctx) {
         std::fprintf(stderr, "[hf host trace] %ld EM steps: parameter view (hfm_params: the negative-binomial tables) %.1f us, enqueue %.1f us, wait %.1f us, m-step %.1f us, gpu span (first launch .. reduction) %.1f us\n",
                      ps.ht_n, ps.ht[4] / ps.ht_n, ps.ht[0] / ps.ht_n, ps.ht[1] / ps.ht_n, ps.ht[2] / ps.ht_n, ps.ht[3] / ps.ht_n);
     pass_destroy(ctx->pass);
-    vit_free(ctx);
-    smp_free(ctx);
+    ctx->vit.release();
+    ctx->smp.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -1912,127 +1910,6 @@ int hf_get_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
     return ctx ? pass_posterior(ctx->pass, first, n, post_host) : set_err(HF_E_ARG, "hf_get_posterior: bad argument");
 }
 
-// ------------------------------------------------------------------------------------------
-// most-probable-path decoding (hf_viterbi.h): its own parameter block, rows, flags and outputs, so that the last pass's getters
-// (which re-run the segment kernel over the pass's tables) and the next pass see nothing of it
-// ------------------------------------------------------------------------------------------
-static int vit_alloc(hf_ctx* ctx) {
-    const Track& tr = ctx->tr; Viterbi& v = ctx->vit;
-    if (v.alloc) return HF_OK;
-    const bool scan = tr.algo == HF_ALGO_SCAN;
-    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
-    const size_t nC = (size_t) tr.C;
-#define VALLOC(ptr, bytes) HIPCHK(hipMalloc((void**) &(ptr), (bytes) ? (bytes) : 8))
-    HIPCHK(hipHostMalloc((void**) &v.h_params, tr.params_bytes));
-    VALLOC(v.d_params, tr.params_bytes);
-    VALLOC(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8);
-    VALLOC(v.d_rows, nrow * 128);
-    VALLOC(v.d_bp, nrow);
-    VALLOC(v.d_label, (size_t) tr.N);
-    VALLOC(v.d_ll, nC * 8);
-    VALLOC(v.d_final, nC);
-    VALLOC(v.d_flags, 4);
-    if (scan) {
-        VALLOC(v.d_P, G * 16 * 64 * 8); VALLOC(v.d_PE, G * 64 * 4); VALLOC(v.d_S, G * 16 * 8); VALLOC(v.d_SE, G * 4);
-        VALLOC(v.d_vin, G * 4 * 8); VALLOC(v.d_vinE, G * 8);
-        VALLOC(v.d_lmap, G * 64); VALLOC(v.d_smap, G); VALLOC(v.d_sexit, G);
-    }
-#undef VALLOC
-    v.alloc = true;
-    return HF_OK;
-}
-
-static void vit_free(hf_ctx* ctx) {
-    Viterbi& v = ctx->vit;
-    if (v.h_params) hipHostFree(v.h_params);
-    void* dev[] = {v.d_params, v.d_nbE, v.d_rows, v.d_bp, v.d_label, v.d_ll, v.d_final, v.d_flags, v.d_P, v.d_PE, v.d_S, v.d_SE,
-                   v.d_vin, v.d_vinE, v.d_lmap, v.d_smap, v.d_sexit};
-    for (void* q : dev) if (q) hipFree(q);
-    v = Viterbi();
-}
-
-int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
-    if (!ctx || !p) return set_err(HF_E_ARG, "hf_viterbi: bad argument");
-    const Track& tr = ctx->tr;
-    Viterbi& v = ctx->vit;
-    hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
-        return set_err(HF_E_ARG, "hf_viterbi: HF_ALGO_SCAN holds at most 2^30 windows per context");
-    if (v.launched) HIPCHK(hipDeviceSynchronize());   // a run nobody finished may still be reading the pinned parameter block
-    v.launched = false; v.done = false;
-    int rc = vit_alloc(ctx);
-    if (rc) return rc;
-    rc = pack_params(tr, p, v.h_params);
-    if (rc) return rc;
-    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
-    if (nbm) {
-        if (!p->nb_E) return set_err(HF_E_ARG, "hf_viterbi: negative_binomial needs hf_params.nb_E");
-        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
-            return set_err(HF_E_ARG, "hf_viterbi: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
-        // (synchronous: the caller's table may be rewritten as soon as this returns)
-        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
-    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
-    const double* nbE = nbm ? v.d_nbE : nullptr;
-    if (tr.C > 0 && tr.N > 0) {
-        if (tr.algo == HF_ALGO_SCAN) {
-            const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64);
-            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
-            hipLaunchKernelGGL(k_vit_prod, dim3(G), dim3(64), 0, st, tr.d_seg, v.d_rows, v.d_P, v.d_PE, v.d_S, v.d_SE);
-            hipLaunchKernelGGL(k_vit_chain, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, v.d_S, v.d_SE, v.d_vin, v.d_vinE);
-            hipLaunchKernelGGL(k_vit_replay, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, v.d_params, v.d_rows, v.d_P, v.d_PE, v.d_vin,
-                               v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_ll, v.d_flags);
-            hipLaunchKernelGGL(k_vit_exits, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, v.d_smap, v.d_final, v.d_sexit);
-            hipLaunchKernelGGL(k_vit_back, dim3(G), dim3(64), 0, st, tr.d_seg, v.d_bp, v.d_lmap, v.d_sexit, v.d_label);
-        } else {
-            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta,
-                               v.d_params, nbE, v.d_rows, v.d_flags);
-            hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, v.d_bp,
-                               v.d_label, v.d_ll, v.d_flags);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    v.launched = true;
-    return HF_OK;
-}
-
-int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
-    if (!ctx || !ctx->vit.launched) return set_err(HF_E_ARG, "hf_viterbi_finish: no hf_viterbi to finish");
-    const Track& tr = ctx->tr;
-    Viterbi& v = ctx->vit;
-    HIPCHK(hipSetDevice(tr.device));
-    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
-    v.launched = false;
-    unsigned fl = 0;
-    HIPCHK(hipMemcpy(&fl, v.d_flags, 4, hipMemcpyDeviceToHost));
-    if (fl) return flags_to_code(fl);
-    v.h_ll.assign((size_t) tr.C, 0.0);
-    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
-    double tot = 0.0;
-    for (double x : v.h_ll) tot += x;   // chunk-list order
-    if (log_prob_host) *log_prob_host = tot;
-    v.done = true;
-    return HF_OK;
-}
-
-int hf_get_viterbi_labels(hf_ctx* ctx, int8_t* labels_host) {
-    if (!ctx || !labels_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_labels: no finished hf_viterbi");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
-}
-
-int hf_get_viterbi_chunk_log_probs(hf_ctx* ctx, double* out_host) {
-    if (!ctx || !out_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_chunk_log_probs: no finished hf_viterbi");
-    const Track& tr = ctx->tr;
-    if (tr.C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) tr.C * 8);
-    return HF_OK;
-}
-
 int hf_set_profiling(hf_ctx* ctx, unsigned kernel_mask) {
     if (!ctx) return set_err(HF_E_ARG, "hf_set_profiling: bad argument");
     Pass& ps = ctx->pass; const Track& tr = ctx->tr;
@@ -2141,69 +2018,178 @@ int hf_last_kernel_ms(hf_ctx* ctx, float* ms) {
 
 #include "hf_batch.h"
 
+
 // ------------------------------------------------------------------------------------------
-// posterior path sampling (hf_sample.h): its own parameter block, rows, flags and outputs — the last pass's getters, Viterbi's and the
-// next pass see nothing of it.  Last in the file, its kernels included, so that no existing kernel's code moves relative to the
+// the path decoders (hf_decode.h): Viterbi (hf_viterbi.h) and posterior path sampling (hf_sample.h).  Each has its own parameter block,
+// rows, flags and outputs, so that the last pass's getters (which re-run the segment kernel over the pass's tables), the next pass and
+// the other decoder see nothing of it.  Last in the file, their kernels included, so that no pass kernel's code moves relative to the
 // ones around it.
 // ------------------------------------------------------------------------------------------
+#include "hf_viterbi.h"
 #include "hf_sample.h"
 
-struct SmpSizes { size_t fixed, per; };
-static SmpSizes smp_sizes(const Track& tr) {
-    const bool scan = tr.algo == HF_ALGO_SCAN;
-    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
-    auto gr = [](size_t b) { return ((b ? b : 8) + 255) & ~(size_t) 255; };   // (hipMalloc's granule, roughly)
-    SmpSizes z;
-    z.fixed = gr(tr.params_bytes) + gr((size_t) tr.R * 4 * HF_NB_NX * 8) + gr(nrow * 128) + gr(4);
-    if (scan) z.fixed += gr(G * 16 * 64 * 8) + gr(G * 16 * 8) + gr(G * 4 * 8);
-    z.per = 8 + nrow + (size_t) tr.N + (scan ? (size_t) tr.C + G * 66 : 0);   // key, maps, labels; SCAN: final states, lane / segment maps, exits
-    return z;
+static bool dec_scan(const Track& tr) { return tr.algo == HF_ALGO_SCAN; }
+static size_t dec_nrow(const Track& tr) { return dec_scan(tr) ? (size_t) tr.n_slots : (size_t) tr.N; }   // rows and map bytes per path
+static size_t dec_nseg(const Track& tr) { return dec_scan(tr) ? (size_t) tr.nseg : 0; }
+
+// Every device array of a decoder, f(array, bytes) in turn: the ONE place that sizes them (dec_take allocates them, hf_sample_capacity
+// counts them).  The shared part: parameter block, negative-binomial table, flag word, rows; SCAN: the arrays of A and B, with their
+// exponent sums when the decoder reports a score.
+template <class D, class F> static void dec_arrays(const Track& tr, D& d, bool score, F&& f) {
+    const size_t G = dec_nseg(tr);
+    f(d.d_params, tr.params_bytes); f(d.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(d.d_rows, dec_nrow(tr) * 128); f(d.d_flags, 4);
+    if (dec_scan(tr)) {
+        f(d.d_P, G * 16 * 64 * 8); f(d.d_S, G * 16 * 8); f(d.d_vin, G * 4 * 8);
+        if (score) { f(d.d_PE, G * 64 * 4); f(d.d_SE, G * 4); f(d.d_vinE, G * 8); }
+    }
+}
+template <class F> static void vit_arrays(const Track& tr, Viterbi& v, F&& f) {
+    const size_t G = dec_nseg(tr);
+    dec_arrays(tr, v, true, f);
+    f(v.d_bp, dec_nrow(tr)); f(v.d_label, (size_t) tr.N); f(v.d_ll, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+    if (dec_scan(tr)) { f(v.d_lmap, G * 64); f(v.d_smap, G); f(v.d_sexit, G); }
+}
+// the per-sample part for k samples: keys, map bytes, labels; SCAN: final states, lane and segment maps, exit states
+template <class S, class F> static void smp_arrays(const Track& tr, S& s, size_t k, F&& f) {
+    const size_t G = dec_nseg(tr);
+    f(s.d_keys, k * 8); f(s.d_maps, k * dec_nrow(tr)); f(s.d_label, k * (size_t) tr.N);
+    if (dec_scan(tr)) { f(s.d_final, k * (size_t) tr.C); f(s.d_lmap, k * G * 64); f(s.d_smap, k * G); f(s.d_sexit, k * G); }
 }
 
-static void smp_free_samples(Sampler& s) {
-    void* dev[] = {s.d_keys, s.d_maps, s.d_final, s.d_lmap, s.d_smap, s.d_sexit, s.d_label};
-    for (void* q : dev) if (q) hipFree(q);
-    s.d_keys = nullptr; s.d_maps = nullptr; s.d_final = nullptr; s.d_lmap = nullptr; s.d_smap = nullptr; s.d_sexit = nullptr; s.d_label = nullptr;
-    s.cap = 0;
-}
-
-static int smp_alloc(hf_ctx* ctx, int n) {
-    const Track& tr = ctx->tr; Sampler& s = ctx->smp;
-    const bool scan = tr.algo == HF_ALGO_SCAN;
-    const size_t nrow = scan ? (size_t) tr.n_slots : (size_t) tr.N, G = scan ? (size_t) tr.nseg : 0;
-#define SALLOC(ptr, bytes) HIPCHK(hipMalloc((void**) &(ptr), (bytes) ? (bytes) : 8))
-    if (!s.alloc) {
-        HIPCHK(hipHostMalloc((void**) &s.h_params, tr.params_bytes));
-        SALLOC(s.d_params, tr.params_bytes);
-        SALLOC(s.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8);
-        SALLOC(s.d_rows, nrow * 128);
-        SALLOC(s.d_flags, 4);
-        if (scan) { SALLOC(s.d_P, G * 16 * 64 * 8); SALLOC(s.d_S, G * 16 * 8); SALLOC(s.d_vin, G * 4 * 8); }
-        s.alloc = true;
-    }
-    if (n > s.cap) {
-        smp_free_samples(s);
-        const size_t k = (size_t) n;
-        SALLOC(s.d_keys, k * 8);
-        SALLOC(s.d_maps, k * nrow);
-        SALLOC(s.d_label, k * (size_t) tr.N);
-        if (scan) {
-            SALLOC(s.d_final, k * (size_t) tr.C);
-            SALLOC(s.d_lmap, k * G * 64); SALLOC(s.d_smap, k * G); SALLOC(s.d_sexit, k * G);
-        }
-        s.cap = n;
-    }
-#undef SALLOC
+// a slab of exactly the arrays `arrays` lists (arrays(f) calls f(array, bytes) for each), every one of them taken from it
+template <class A> static int dec_take(Slab& slab, A&& arrays) {
+    slab.first = 0;
+    arrays([&](auto&, size_t bytes) { slab.first += Slab::granule(bytes); });
+    bool ok = true;
+    arrays([&](auto& p, size_t bytes) {
+        if (ok) { p = static_cast<std::remove_reference_t<decltype(p)>>(slab.alloc(bytes)); ok = p != nullptr; }
+    });
+    if (!ok) { (void) hipGetLastError(); return set_err(HF_E_HIP, "out of device memory for the decoder's buffers"); }
     return HF_OK;
 }
 
-static void smp_free(hf_ctx* ctx) {
-    Sampler& s = ctx->smp;
-    smp_free_samples(s);
-    if (s.h_params) hipHostFree(s.h_params);
-    void* dev[] = {s.d_params, s.d_nbE, s.d_rows, s.d_P, s.d_S, s.d_vin, s.d_flags};
-    for (void* q : dev) if (q) hipFree(q);
-    s = Sampler();
+// the fixed part of a decoder on its first call: the pinned parameter block and the slab of `arrays`
+template <class A> static int dec_alloc(const Track& tr, Decoder& d, A&& arrays) {
+    if (d.alloc) return HF_OK;
+    HIPCHK(hipHostMalloc((void**) &d.h_params, tr.params_bytes));
+    const int rc = dec_take(d.slab, arrays);
+    if (rc) return rc;
+    d.alloc = true;
+    return HF_OK;
+}
+
+static bool dec_work(const Track& tr) { return tr.C > 0 && tr.N > 0; }
+
+// What a decoder call does before its own kernels, error messages naming the entry point `who`: the refusal of a scan context without a
+// segment plan, the wait for a run nobody finished (it may still be reading the pinned parameter block), `prepare` (the decoder's buffers
+// and inputs; it may refuse the call), the parameter block and the negative-binomial table, the flag word, then on `st` the rows and, on
+// the scan path, steps A and B in the semiring SR.
+template <class SR, class Prep>
+static int dec_begin(const Track& tr, Decoder& d, const hf_params* p, hipStream_t st, const char* who, Prep&& prepare) {
+    HIPCHK(hipSetDevice(tr.device));
+    const std::string w = who;
+    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
+        return set_err(HF_E_ARG, w + ": HF_ALGO_SCAN holds at most 2^30 windows per context");
+    if (d.launched) HIPCHK(hipDeviceSynchronize());
+    d.launched = false; d.done = false;
+    int rc = prepare();
+    if (rc) return rc;
+    rc = pack_params(tr, p, d.h_params);
+    if (rc) return rc;
+    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
+    if (nbm) {
+        if (!p->nb_E) return set_err(HF_E_ARG, w + ": negative_binomial needs hf_params.nb_E");
+        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
+            return set_err(HF_E_ARG, w + ": the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
+        // (synchronous: the caller's table may be rewritten as soon as this returns)
+        HIPCHK(hipMemcpy(d.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpyAsync(d.d_params, d.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d.d_flags, 0, 4, st));
+    if (!dec_work(tr)) return HF_OK;
+    const double* nbE = nbm ? d.d_nbE : nullptr;
+    if (dec_scan(tr)) {
+        const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64);
+        hipLaunchKernelGGL(k_dec_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, d.d_params, nbE, d.d_rows, d.d_flags);
+        hipLaunchKernelGGL(k_dec_prod<SR>, dim3(G), dim3(64), 0, st, tr.d_seg, d.d_rows, d.d_P, d.d_PE, d.d_S, d.d_SE);
+        hipLaunchKernelGGL(k_dec_chain<SR>, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, d.d_S, d.d_SE, d.d_vin, d.d_vinE);
+    } else {
+        hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, d.d_params, nbE,
+                           d.d_rows, d.d_flags);
+    }
+    return HF_OK;
+}
+
+// D on the scan path: K paths' exit states and labels from their maps
+static void dec_back(const Track& tr, hipStream_t st, unsigned K, const uint8_t* maps, const uint8_t* lmap, const uint8_t* smap,
+                     const int8_t* final_state, uint8_t* sexit, int8_t* label) {
+    const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64);
+    hipLaunchKernelGGL(k_dec_exits, dim3(CB, K), dim3(64), 0, st, tr.C, (int) G, tr.d_chunk_seg0, smap, final_state, sexit);
+    hipLaunchKernelGGL(k_dec_back, dim3(G, K), dim3(64), 0, st, tr.d_seg, maps, tr.n_slots, (int) G, tr.N, lmap, sexit, label);
+}
+
+// the wait for a decoder's run and its flag word
+static int dec_finish(const Track& tr, Decoder& d, void* stream) {
+    HIPCHK(hipSetDevice(tr.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    d.launched = false;
+    unsigned fl = 0;
+    HIPCHK(hipMemcpy(&fl, d.d_flags, 4, hipMemcpyDeviceToHost));
+    return fl ? flags_to_code(fl) : HF_OK;
+}
+
+int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
+    if (!ctx || !p) return set_err(HF_E_ARG, "hf_viterbi: bad argument");
+    const Track& tr = ctx->tr;
+    Viterbi& v = ctx->vit;
+    hipStream_t st = (hipStream_t) stream;
+    int rc = dec_begin<MaxTimes>(tr, v, p, st, "hf_viterbi",
+                                 [&] { return dec_alloc(tr, v, [&](auto&& f) { vit_arrays(tr, v, f); }); });
+    if (rc) return rc;
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
+    if (dec_work(tr)) {
+        if (dec_scan(tr)) {
+            hipLaunchKernelGGL(k_vit_replay, dim3((unsigned) tr.nseg), dim3(64), 0, st, tr.d_seg, tr.d_rec, v.d_params, v.d_rows, v.d_P,
+                               v.d_PE, v.d_vin, v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_ll, v.d_flags);
+            dec_back(tr, st, 1, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_sexit, v.d_label);   // (the backpointers: one path's maps)
+        } else {
+            hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, v.d_bp,
+                               v.d_label, v.d_ll, v.d_flags);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
+    if (!ctx || !ctx->vit.launched) return set_err(HF_E_ARG, "hf_viterbi_finish: no hf_viterbi to finish");
+    const Track& tr = ctx->tr;
+    Viterbi& v = ctx->vit;
+    const int rc = dec_finish(tr, v, stream);
+    if (rc) return rc;
+    v.h_ll.assign((size_t) tr.C, 0.0);
+    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
+    double tot = 0.0;
+    for (double x : v.h_ll) tot += x;   // chunk-list order
+    if (log_prob_host) *log_prob_host = tot;
+    v.done = true;
+    return HF_OK;
+}
+
+int hf_get_viterbi_labels(hf_ctx* ctx, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_labels: no finished hf_viterbi");
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_viterbi_chunk_log_probs(hf_ctx* ctx, double* out_host) {
+    if (!ctx || !out_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_chunk_log_probs: no finished hf_viterbi");
+    const Track& tr = ctx->tr;
+    if (tr.C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) tr.C * 8);
+    return HF_OK;
 }
 
 // the largest grid.y of the per-sample launches
@@ -2215,13 +2201,38 @@ int hf_sample_capacity(const hf_ctx* ctx) {
     HIPCHK(hipSetDevice(tr.device));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const SmpSizes z = smp_sizes(tr);
+    size_t fixed = 0, per = 0;   // the fixed slab; the per-sample arrays of one sample
+    dec_arrays(tr, s, false, [&](auto&, size_t bytes) { fixed += Slab::granule(bytes); });
+    smp_arrays(tr, s, 1, [&](auto&, size_t bytes) { per += bytes; });
     // what the sampler holds already counts as free: a call reuses (or replaces) it
-    const double held = (s.alloc ? (double) z.fixed : 0.0) + (double) s.cap * (double) z.per;
-    const double budget = 0.9 * ((double) free_b + held) - (double) z.fixed;
-    if (budget < (double) z.per) return 0;
-    const double cap = std::floor(budget / (double) z.per);
+    const double held = (s.alloc ? (double) fixed : 0.0) + (double) s.cap * (double) per;
+    const double budget = 0.9 * ((double) free_b + held) - (double) fixed;
+    if (budget < (double) per) return 0;
+    const double cap = std::floor(budget / (double) per);
     return cap > HF_SMP_MAX_PER_CALL ? HF_SMP_MAX_PER_CALL : (int) cap;
+}
+
+// the sampler's buffers for n samples (the per-sample slab replaced when it holds fewer) and the keys of samples first .. first + n - 1
+static int smp_prepare(hf_ctx* ctx, int64_t first, int n, uint64_t seed) {
+    const Track& tr = ctx->tr; Sampler& s = ctx->smp;
+    if (n > s.cap) {
+        const int cap = hf_sample_capacity(ctx);
+        if (cap < 0) return cap;
+        if (n > cap) return set_err(HF_E_ARG, "hf_sample_paths: n_samples exceeds hf_sample_capacity (" + std::to_string(cap) + ")");
+    }
+    int rc = dec_alloc(tr, s, [&](auto&& f) { dec_arrays(tr, s, false, f); });
+    if (rc) return rc;
+    if (n > s.cap) {
+        s.samples.release();
+        s.cap = 0;
+        rc = dec_take(s.samples, [&](auto&& f) { smp_arrays(tr, s, (size_t) n, f); });
+        if (rc) return rc;
+        s.cap = n;
+    }
+    s.h_keys.resize((size_t) n);
+    for (int k = 0; k < n; k++) s.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first + k));
+    HIPCHK(hipMemcpy(s.d_keys, s.h_keys.data(), (size_t) n * 8, hipMemcpyHostToDevice));
+    return HF_OK;
 }
 
 int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n_samples, uint64_t seed, void* stream) {
@@ -2231,48 +2242,16 @@ int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n
     const Track& tr = ctx->tr;
     Sampler& s = ctx->smp;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
-        return set_err(HF_E_ARG, "hf_sample_paths: HF_ALGO_SCAN holds at most 2^30 windows per context");
-    if (s.launched) HIPCHK(hipDeviceSynchronize());   // a call nobody finished may still be reading the pinned parameter block and the keys
-    s.launched = false; s.done = false;
-    if (n_samples > s.cap) {
-        const int cap = hf_sample_capacity(ctx);
-        if (cap < 0) return cap;
-        if (n_samples > cap) return set_err(HF_E_ARG, "hf_sample_paths: n_samples exceeds hf_sample_capacity (" + std::to_string(cap) + ")");
-    }
-    int rc = smp_alloc(ctx, n_samples);
+    const int rc = dec_begin<SumTimes>(tr, s, p, st, "hf_sample_paths", [&] { return smp_prepare(ctx, first_sample, n_samples, seed); });
     if (rc) return rc;
-    rc = pack_params(tr, p, s.h_params);
-    if (rc) return rc;
-    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
-    if (nbm) {
-        if (!p->nb_E) return set_err(HF_E_ARG, "hf_sample_paths: negative_binomial needs hf_params.nb_E");
-        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
-            return set_err(HF_E_ARG, "hf_sample_paths: the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
-        HIPCHK(hipMemcpy(s.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
-    }
-    s.h_keys.resize((size_t) n_samples);
-    for (int k = 0; k < n_samples; k++) s.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first_sample + k));
-    HIPCHK(hipMemcpy(s.d_keys, s.h_keys.data(), (size_t) n_samples * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpyAsync(s.d_params, s.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(s.d_flags, 0, 4, st));
-    const double* nbE = nbm ? s.d_nbE : nullptr;
-    if (tr.C > 0 && tr.N > 0) {
-        if (tr.algo == HF_ALGO_SCAN) {
-            const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64), K = (unsigned) n_samples;
-            hipLaunchKernelGGL(k_vit_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, s.d_params, nbE, s.d_rows, s.d_flags);
-            hipLaunchKernelGGL(k_smp_prod, dim3(G), dim3(64), 0, st, tr.d_seg, s.d_rows, s.d_P, s.d_S);
-            hipLaunchKernelGGL(k_smp_chain, dim3(CB), dim3(64), 0, st, tr.C, tr.d_chunk_seg0, s.d_S, s.d_vin);
+    if (dec_work(tr)) {
+        if (dec_scan(tr)) {
+            const unsigned G = (unsigned) tr.nseg, K = (unsigned) n_samples;
             hipLaunchKernelGGL(k_smp_replay, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, s.d_params, s.d_rows, s.d_P, s.d_vin, s.d_keys,
                                n_samples, tr.N, tr.C, tr.n_slots, s.d_maps, s.d_final, s.d_flags);
             hipLaunchKernelGGL(k_smp_maps, dim3(G, K), dim3(64), 0, st, tr.d_seg, s.d_maps, tr.n_slots, (int) G, s.d_lmap, s.d_smap);
-            hipLaunchKernelGGL(k_smp_exits, dim3(CB, K), dim3(64), 0, st, tr.C, (int) G, tr.d_chunk_seg0, s.d_smap, s.d_final, s.d_sexit);
-            hipLaunchKernelGGL(k_smp_back, dim3(G, K), dim3(64), 0, st, tr.d_seg, s.d_maps, tr.n_slots, (int) G, tr.N, s.d_lmap, s.d_sexit,
-                               s.d_label);
+            dec_back(tr, st, K, s.d_maps, s.d_lmap, s.d_smap, s.d_final, s.d_sexit, s.d_label);
         } else {
-            hipLaunchKernelGGL(k_vit_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta,
-                               s.d_params, nbE, s.d_rows, s.d_flags);
             hipLaunchKernelGGL(k_smp_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, s.d_params, s.d_rows, s.d_keys,
                                n_samples, tr.N, tr.C, s.d_maps, s.d_label, s.d_flags);
         }
@@ -2285,14 +2264,9 @@ int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n
 
 int hf_sample_finish(hf_ctx* ctx, void* stream) {
     if (!ctx || !ctx->smp.launched) return set_err(HF_E_ARG, "hf_sample_finish: no hf_sample_paths to finish");
-    Sampler& s = ctx->smp;
-    HIPCHK(hipSetDevice(ctx->tr.device));
-    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
-    s.launched = false;
-    unsigned fl = 0;
-    HIPCHK(hipMemcpy(&fl, s.d_flags, 4, hipMemcpyDeviceToHost));
-    if (fl) return flags_to_code(fl);
-    s.done = true;
+    const int rc = dec_finish(ctx->tr, ctx->smp, stream);
+    if (rc) return rc;
+    ctx->smp.done = true;
     return HF_OK;
 }
 
