@@ -110,6 +110,7 @@ def lib() -> C.CDLL:
     sig("hf_get_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_forward_backward", C.c_int, vp, i64, i64, pd, pd, pd)
+    sig("hf_get_interval_log_probs", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), pd)
     sig("hf_viterbi", C.c_int, vp, C.POINTER(hf_params), vp)
     sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))

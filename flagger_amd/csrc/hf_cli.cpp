@@ -12,11 +12,14 @@
 #include <sys/time.h>
 #include <unistd.h>
 #include <algorithm>
+#include <array>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -62,6 +65,8 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"sweepAlpha", required_argument, nullptr, 1006},      // one run per alpha TSV of a list, one load (not `alpha...`: --alpha stays unique)
     {"uncertaintySamples", required_argument, nullptr, 1007},   // N posterior path samples after the final inference (hf_sample_paths)
     {"uncertaintySeed", required_argument, nullptr, 1008},      // their seed [0]
+    {"runConfidence", no_argument, nullptr, 1009},              // exact per-run label probabilities (hf_get_interval_log_probs)
+    {"regionProbs", required_argument, nullptr, 1010},          // exact per-region label probabilities for the regions of a BED file
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -106,7 +111,13 @@ static void usage(const char* program) {
             "                                      SD, 2.5/50/97.5 %% quantiles over the samples) and final_label_runs_support.bed (every run of\n"
             "                                      equal final label: fraction of samples that give the whole run its label, mean fraction of\n"
             "                                      its windows); one GPU, not with --gpus N>1 or --sweepAlpha\n"
-            "         --uncertaintySeed S          seed of those samples (a sample depends on the seed and its index only) [0]\n");
+            "         --uncertaintySeed S          seed of those samples (a sample depends on the seed and its index only) [0]\n"
+            "         --runConfidence              write final_label_runs_confidence.bed: for every run of equal final label (the runs of\n"
+            "                                      final_label_runs_support.bed) the exact probability that all its windows have that label,\n"
+            "                                      as a Phred quality, and the mean posterior; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --regionProbs FILE           for every region of a BED file (ctg start end [name]) write the exact probabilities that\n"
+            "                                      any / every window it meets has each label, and the mean posterior, to\n"
+            "                                      region_label_probabilities.tsv; one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -254,27 +265,27 @@ static void write_params(const hfm_model* m, const std::string& dir, const std::
 //                                   that label, and the mean over samples of the fraction of its windows that have it
 static const char* const kRunLabelNames[] = {"Err", "Dup", "Hap", "Col"};   // the final BED's names (hf_io.cpp kLabelNames)
 
-static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
-                                uint64_t seed, const std::vector<std::string>& labelNames, const std::string& dir) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    // window i of chunk c covers [s + i W, min(s + (i+1) W - 1, e)]
-    std::vector<int64_t> wbases((size_t) N);
-    std::vector<int32_t> wreg((size_t) N);
+// window i of chunk c covers [s + i W, min(s + (i+1) W - 1, e)]: its number of bases (and, with wreg, its region)
+static void window_bases(const hf_windows& w, int C, std::vector<int64_t>& wbases, std::vector<int32_t>* wreg) {
+    wbases.assign((size_t) w.n_windows, 0);
+    if (wreg) wreg->assign((size_t) w.n_windows, 0);
     for (int c = 0; c < C; c++)
         for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
             const int64_t i = t - w.chunk_off[c];
             const int64_t s = (int64_t) w.chunk_s[c] + i * w.window_len;
             const int64_t e = std::min<int64_t>((int64_t) w.chunk_s[c] + (i + 1) * w.window_len - 1, (int64_t) w.chunk_e[c]);
             wbases[(size_t) t] = e - s + 1;
-            wreg[(size_t) t] = (int32_t) (w.annot[t] >> 58);
+            if (wreg) (*wreg)[(size_t) t] = (int32_t) (w.annot[t] >> 58);
         }
-    // the runs of the final labels: a new run where the label changes or a chunk starts a different contig
-    struct LRun { int64_t a, b; int label; int64_t s, e; const char* ctg; };
+}
+
+// the runs of the final labels (final_label_runs_support.bed, final_label_runs_confidence.bed): a new run where the label changes or a
+// chunk starts a different contig; windows a .. b - 1, bases s .. e; runOf (optional): every window's run
+struct LRun { int64_t a, b; int label; int64_t s, e; const char* ctg; };
+static std::vector<LRun> label_runs(const hfio_table* tab, const hf_windows& w, int C, const std::vector<int64_t>& wbases,
+                                    const int8_t* finalLabels, std::vector<int32_t>* runOf) {
     std::vector<LRun> runs;
-    std::vector<int32_t> runOf((size_t) N);
+    if (runOf) runOf->assign((size_t) w.n_windows, 0);
     const char* preCtg = nullptr;
     for (int c = 0; c < C; c++) {
         const char* ctg = hfio_chunk_ctg(tab, c);
@@ -285,10 +296,24 @@ static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table*
             const bool newCtg = t == w.chunk_off[c] && (!preCtg || strcmp(preCtg, ctg) != 0);
             if (runs.empty() || newCtg || runs.back().label != finalLabels[t]) runs.push_back(LRun{t, t, finalLabels[t], s, e, ctg});
             runs.back().b = t + 1; runs.back().e = e;
-            runOf[(size_t) t] = (int32_t) (runs.size() - 1);
+            if (runOf) (*runOf)[(size_t) t] = (int32_t) (runs.size() - 1);
             if (t == w.chunk_off[c]) preCtg = ctg;
         }
     }
+    return runs;
+}
+
+static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
+                                uint64_t seed, const std::vector<std::string>& labelNames, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<int64_t> wbases;
+    std::vector<int32_t> wreg;
+    window_bases(w, C, wbases, &wreg);
+    std::vector<int32_t> runOf;
+    const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, &runOf);
     const size_t G = (size_t) R + 1, NR = runs.size();
     std::vector<int64_t> basesS((size_t) nSamples * G * 4), winS(G * 4, 0), cnt(NR);
     std::vector<double> support(NR, 0.0), meanFrac(NR, 0.0);
@@ -358,6 +383,156 @@ static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table*
     return HF_OK;
 }
 
+// --regionProbs: the regions of a BED3+ file (ctg start end [name]), every line checked before the input is read
+struct Region { std::string ctg, name; int64_t start, end; };
+static bool read_regions(const char* path, std::vector<Region>& regions) {
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "[%s] Error: --regionProbs: cannot read %s\n", ts(), path); return false; }
+    char* line = nullptr; size_t cap = 0; ssize_t len; long ln = 0;
+    bool ok = true;
+    while ((len = getline(&line, &cap, f)) >= 0) {
+        ln++;
+        std::string l(line, (size_t) len);
+        while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+        if (l.find_first_not_of(" \t") == std::string::npos || l[0] == '#' || l.compare(0, 5, "track") == 0 || l.compare(0, 7, "browser") == 0) continue;
+        std::vector<std::string> fld;
+        size_t a = 0;
+        while (a <= l.size()) {
+            size_t b = l.find_first_of(" \t", a);
+            if (b == std::string::npos) b = l.size();
+            if (b > a) fld.push_back(l.substr(a, b - a));
+            a = b + 1;
+        }
+        auto integer = [](const std::string& x, int64_t* v) {
+            char* end = nullptr;
+            errno = 0;
+            const long long r = strtoll(x.c_str(), &end, 10);
+            if (x.empty() || *end != 0 || errno != 0) return false;
+            *v = (int64_t) r;
+            return true;
+        };
+        Region r;
+        if (fld.size() < 3) { fprintf(stderr, "[%s] Error: --regionProbs %s line %ld: expected at least 3 fields (ctg start end [name])\n", ts(), path, ln); ok = false; break; }
+        if (!integer(fld[1], &r.start) || !integer(fld[2], &r.end)) {
+            fprintf(stderr, "[%s] Error: --regionProbs %s line %ld: start and end should be integers\n", ts(), path, ln); ok = false; break;
+        }
+        if (r.start < 0 || r.start >= r.end) { fprintf(stderr, "[%s] Error: --regionProbs %s line %ld: expected 0 <= start < end\n", ts(), path, ln); ok = false; break; }
+        r.ctg = fld[0];
+        r.name = fld.size() > 3 ? fld[3] : ".";
+        regions.push_back(r);
+    }
+    free(line);
+    fclose(f);
+    return ok;
+}
+
+// --runConfidence / --regionProbs: exact label probabilities of windows ranges (hf_get_interval_log_probs) under the model of the last
+// full pass, and the mean posterior (hf_get_posterior).
+//   final_label_runs_confidence.bed    per run of final_label_runs_support.bed (same rows, same order): p_all = P(every window has the
+//                                      run's label), qual = min(100, -10 log10(1 - p_all)), mean_posterior of that label
+//   region_label_probabilities.tsv     per region (file order), for every label L: p_any_L = P(some window has L), p_all_L, mean_L over
+//                                      the windows whose bases meet [start, end) (a union of index ranges: the sum of their logs)
+static int write_interval_outputs(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, bool runConfidence,
+                                  const std::vector<Region>* regions, const std::vector<std::string>& labelNames, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<int64_t> wbases;
+    window_bases(w, C, wbases, nullptr);
+    std::vector<double> post((size_t) N * 4);
+    int rc = N > 0 ? hf_get_posterior(ctx, 0, N, post.data()) : HF_OK;
+    if (rc != HF_OK) return rc;
+    auto mean_post = [&](int64_t a, int64_t b, int l) {   // windows a .. b - 1
+        double m = 0.0;
+        for (int64_t t = a; t < b; t++) m += post[(size_t) t * 4 + (size_t) l];
+        return m / (double) (b - a);
+    };
+    if (runConfidence) {
+        const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, nullptr);
+        std::vector<int64_t> first, last;
+        std::vector<uint8_t> mask;
+        for (const LRun& r : runs)
+            if (r.label >= 0 && r.label < 4) { first.push_back(r.a); last.push_back(r.b - 1); mask.push_back((uint8_t) (1u << r.label)); }
+        std::vector<double> lp(first.size());
+        if ((rc = hf_get_interval_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), lp.data())) != HF_OK) return rc;
+        const std::string bp = dir + "/final_label_runs_confidence.bed";
+        FILE* f = fopen(bp.c_str(), "w");
+        if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
+        fprintf(f, "#ctg\tstart\tend\tlabel\tp_all\tqual\tmean_posterior\n");
+        size_t k = 0;
+        for (const LRun& r : runs) {
+            const bool lab = r.label >= 0 && r.label < 4;
+            fprintf(f, "%s\t%ld\t%ld\t%s\t", r.ctg, (long) r.s, (long) r.e + 1, lab ? kRunLabelNames[r.label] : "Unk");
+            if (!lab) { fprintf(f, "NA\tNA\tNA\n"); continue; }
+            const double l = lp[k++];
+            const double miss = -std::expm1(l);
+            const double qual = miss > 0.0 ? std::min(100.0, -10.0 * std::log10(miss)) + 0.0 : 100.0;
+            fprintf(f, "%.6g\t%.2f\t%.6f\n", std::exp(l), qual, mean_post(r.a, r.b, r.label));
+        }
+        if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
+    }
+    if (regions) {
+        // every contig's windows in base order: (first base, last base, window)
+        std::map<std::string, std::vector<std::array<int64_t, 3>>> byCtg;
+        for (int c = 0; c < C; c++) {
+            auto& v = byCtg[hfio_chunk_ctg(tab, c)];
+            for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+                const int64_t s = (int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len;
+                v.push_back({s, s + wbases[(size_t) t] - 1, t});
+            }
+        }
+        for (auto& kv : byCtg) std::sort(kv.second.begin(), kv.second.end());
+        // the windows of every region, as maximal index ranges; one job per range and mask (Err..Col alone, and all but each)
+        std::vector<std::vector<int64_t>> wins(regions->size());
+        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges(regions->size());
+        std::vector<int64_t> first, last;
+        std::vector<uint8_t> mask;
+        for (size_t i = 0; i < regions->size(); i++) {
+            const Region& g = (*regions)[i];
+            auto it = byCtg.find(g.ctg);
+            if (it == byCtg.end()) continue;
+            for (const auto& x : it->second)
+                if (x[0] < g.end && x[1] >= g.start) wins[i].push_back(x[2]);
+            std::sort(wins[i].begin(), wins[i].end());
+            for (int64_t t : wins[i]) {
+                if (!ranges[i].empty() && ranges[i].back().second + 1 == t) ranges[i].back().second = t;
+                else ranges[i].push_back({t, t});
+            }
+            for (const auto& r : ranges[i])
+                for (int m = 0; m < 8; m++) { first.push_back(r.first); last.push_back(r.second); mask.push_back((uint8_t) (m < 4 ? 1u << m : 15u & ~(1u << (m - 4)))); }
+        }
+        std::vector<double> lp(first.size());
+        if ((rc = hf_get_interval_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), lp.data())) != HF_OK) return rc;
+        const std::string rp = dir + "/region_label_probabilities.tsv";
+        FILE* f = fopen(rp.c_str(), "w");
+        if (!f) { hf_cli_set_error(rp + " cannot be opened"); return HF_E_ARG; }
+        fprintf(f, "#ctg\tstart\tend\tname\tn_windows");
+        for (int l = 0; l < 4; l++) {
+            const char* name = labelNames.size() > (size_t) l ? labelNames[(size_t) l].c_str() : kRunLabelNames[l];
+            fprintf(f, "\tp_any_%s\tp_all_%s\tmean_%s", name, name, name);
+        }
+        fprintf(f, "\n");
+        size_t k = 0;
+        for (size_t i = 0; i < regions->size(); i++) {
+            const Region& g = (*regions)[i];
+            fprintf(f, "%s\t%ld\t%ld\t%s\t%zu", g.ctg.c_str(), (long) g.start, (long) g.end, g.name.c_str(), wins[i].size());
+            double all[4] = {0, 0, 0, 0}, none[4] = {0, 0, 0, 0};     // sums over the ranges, range order
+            for (size_t r = 0; r < ranges[i].size(); r++, k += 8)
+                for (int l = 0; l < 4; l++) { all[l] += lp[k + (size_t) l]; none[l] += lp[k + 4 + (size_t) l]; }
+            for (int l = 0; l < 4; l++) {
+                if (wins[i].empty()) { fprintf(f, "\tNA\tNA\tNA"); continue; }
+                double m = 0.0;
+                for (int64_t t : wins[i]) m += post[(size_t) t * 4 + (size_t) l];
+                fprintf(f, "\t%.6g\t%.6g\t%.6f", -std::expm1(none[l]) + 0.0, std::exp(all[l]), m / (double) wins[i].size());
+            }
+            fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) { hf_cli_set_error(rp + " cannot be written"); return HF_E_ARG; }
+    }
+    return HF_OK;
+}
+
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
     FILE* f = fopen(listPath, "r");
@@ -398,6 +573,8 @@ int main(int argc, char* argv[]) {
     bool viterbi = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
+    bool runConfidence = false;
+    const char* regionProbsPath = nullptr;
     int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1, loopbackRanks = 0;
     const char* binArrayFilePath = nullptr;
     bool writeBenchmarkingStatsPerIteration = false;
@@ -480,6 +657,8 @@ int main(int argc, char* argv[]) {
                 uncertaintySeedBad = end == optarg || *end != 0 || optarg[0] == '-';
                 break;
             }
+            case 1009: runConfidence = true; break;
+            case 1010: regionProbsPath = optarg; break;
             case 1004:
                 if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
                 else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
@@ -508,6 +687,14 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] Error: --uncertaintySamples runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
+    // --runConfidence / --regionProbs: refused combinations, and every line of the region file, before the input is read
+    if ((runConfidence || regionProbsPath) && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts(),
+                runConfidence ? "--runConfidence" : "--regionProbs");
+        return EXIT_FAILURE;
+    }
+    std::vector<Region> regions;
+    if (regionProbsPath && !read_regions(regionProbsPath, regions)) return EXIT_FAILURE;
     // test transport, not an option: HF_LOOPBACK_RANKS=N runs N ranks that share ONE GPU (no RCCL) through the multi-GPU path
     if (const char* e = getenv("HF_LOOPBACK_RANKS")) loopbackRanks = atoi(e);
     if (nGpus < 0 || nGpus > 64 || loopbackRanks < 0 || loopbackRanks > 64) { fprintf(stderr, "[%s] Error: --gpus should be between 1 and 64.\n", ts()); return EXIT_FAILURE; }
@@ -778,6 +965,14 @@ int main(int argc, char* argv[]) {
         if ((rc = write_sample_outputs(run.ctx, model, tab, finalLabels, uncertaintySamples, uncertaintySeed, labelNames, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] posterior_samples_summary.tsv and final_label_runs_support.bed are written (%.1f ms).\n", ts(),
                 (real_time() - t0) * 1e3);
+    }
+    // --runConfidence / --regionProbs: after every other output of the run (they do not depend on it)
+    if (runConfidence || regionProbsPath) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --runConfidence and --regionProbs need a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_interval_outputs(run.ctx, tab, finalLabels, runConfidence, regionProbsPath ? &regions : nullptr, labelNames, dir)) != HF_OK)
+            return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] exact interval probabilities written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

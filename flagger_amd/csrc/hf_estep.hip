@@ -451,12 +451,19 @@ struct Sampler : Decoder {
     void release() { samples.release(); Decoder::release(); }
 };
 
-// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers
+// exact interval probabilities (hf_interval.h): one device buffer of their own, grown on demand (pieces, parts, piece products, results)
+struct IntervalBufs {
+    char* d_buf = nullptr; size_t cap = 0;
+    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
+};
+
+// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer
 struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
     Sampler smp;
+    IntervalBufs iv;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -992,6 +999,7 @@ void hf_destroy(hf_ctx* ctx) {
     pass_destroy(ctx->pass);
     ctx->vit.release();
     ctx->smp.release();
+    ctx->iv.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -1792,6 +1800,47 @@ int hf_get_labels(hf_ctx* ctx, int8_t* labels_host) {
     return ctx ? pass_labels(ctx->pass, labels_host) : set_err(HF_E_ARG, "hf_get_labels: bad argument");
 }
 
+// The lazy block of the getters that read pair records (hf_get_forward_backward / hf_get_posterior, hf_get_interval_log_probs): the
+// records of ALL windows and their scales, from the last full pass of the default algorithm
+static int pass_all_records(Pass& ps) {
+    const Track& tr = *ps.tr;
+    if (!ps.recs_all || !ps.scales_all) {
+        // the last full pass wrote no scales (statistics by emission row), or ran in sub-passes through the pass buffer (only its last sub-pass's records are left).  The segment kernel once
+        // more over all segments, into the all-windows buffer (the tables of the pass are still in place: rows of A, parameters; labels,
+        // scales and log-likelihood partials are rewritten with the same values)
+        const int rc_ = all_records_buffer(ps);
+        if (rc_) return rc_;
+        if (!ps.d_scale_s) HIPCHK(hipMalloc((void**) &ps.d_scale_s, (size_t) tr.n_slots * 8));   // the scales: on first use (an EM pass writes none)
+        // On the stream of the pass itself (the null stream is not ordered against a non-blocking user stream), and its flag
+        // word is read like a pass's: a hand-off that timed out in THIS launch would otherwise leave silently wrong vectors — the context
+        // falls back to two launches and the re-run is repeated; any other flag is the pass's own error, reported as hf_check would.
+        hipStream_t st = ps.last_stream;
+        for (int attempt = 0;; attempt++) {
+            if (!ps.seg_fused) {
+                if (!ps.d_segQ) HIPCHK(hipMalloc((void**) &ps.d_segQ, (size_t) tr.nseg * 64 * 16 * 8));
+                hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) tr.nseg), dim3(64), seg_lds_bytes(), st, tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_segQ, ps.d_Pseg);
+            }
+            const unsigned epoch = ++ps.seg_epoch;
+            launch_seg_fb(ps, st, true, ps.d_recs_all, -1, epoch, epoch, false);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(ps.h_flags, ps.d_flags, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            const unsigned fl = *ps.h_flags;
+            if (attempt == 0 && sync_fallback(ps, fl)) {
+                unsigned keep = fl & ~(unsigned) HF_FLAG_SYNC;        // (the pass's own flags stay for a later hf_check)
+                HIPCHK(hipMemcpyAsync(ps.d_flags, &keep, 4, hipMemcpyHostToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));
+                continue;
+            }
+            const int code = flags_to_code(fl);
+            if (code != HF_OK) return code;
+            break;
+        }
+        ps.recs_all = true; ps.scales_all = true;
+    }
+    return HF_OK;
+}
+
 static int pass_forward_backward(Pass& ps, int64_t first, int64_t n, double* f_host, double* b_host, double* scales_host) {
     const Track& tr = *ps.tr;
     if (first < 0 || n < 0 || first + n > tr.N) return set_err(HF_E_ARG, "hf_get_forward_backward: bad range");
@@ -1803,40 +1852,8 @@ static int pass_forward_backward(Pass& ps, int64_t first, int64_t n, double* f_h
     if (scales_host && !ps.fb_recs) HIPCHK(hipMemcpy(scales_host, ps.d_scale + first, (size_t) n * 8, hipMemcpyDeviceToHost));
     if (!f_host && !b_host && !ps.fb_recs) return HF_OK;
     if (ps.fb_recs) {   // pair records (hf_seg.h): b_t is the second half of the record at pos[t], f_t the first half of the one at pos_f[t]
-        if (!ps.recs_all || !ps.scales_all) {
-            // the last full pass wrote no scales (statistics by emission row), or ran in sub-passes through the pass buffer (only its last sub-pass's records are left).  The segment kernel once
-            // more over all segments, into the all-windows buffer (the tables of the pass are still in place: rows of A, parameters; labels,
-            // scales and log-likelihood partials are rewritten with the same values)
-            const int rc_ = all_records_buffer(ps);
-            if (rc_) return rc_;
-            if (!ps.d_scale_s) HIPCHK(hipMalloc((void**) &ps.d_scale_s, (size_t) tr.n_slots * 8));   // the scales: on first use (an EM pass writes none)
-            // On the stream of the pass itself (the null stream is not ordered against a non-blocking user stream), and its flag
-            // word is read like a pass's: a hand-off that timed out in THIS launch would otherwise leave silently wrong vectors — the context
-            // falls back to two launches and the re-run is repeated; any other flag is the pass's own error, reported as hf_check would.
-            hipStream_t st = ps.last_stream;
-            for (int attempt = 0;; attempt++) {
-                if (!ps.seg_fused) {
-                    if (!ps.d_segQ) HIPCHK(hipMalloc((void**) &ps.d_segQ, (size_t) tr.nseg * 64 * 16 * 8));
-                    hipLaunchKernelGGL(k_seg_prod, dim3((unsigned) tr.nseg), dim3(64), seg_lds_bytes(), st, tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_segQ, ps.d_Pseg);
-                }
-                const unsigned epoch = ++ps.seg_epoch;
-                launch_seg_fb(ps, st, true, ps.d_recs_all, -1, epoch, epoch, false);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(ps.h_flags, ps.d_flags, 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                const unsigned fl = *ps.h_flags;
-                if (attempt == 0 && sync_fallback(ps, fl)) {
-                    unsigned keep = fl & ~(unsigned) HF_FLAG_SYNC;        // (the pass's own flags stay for a later hf_check)
-                    HIPCHK(hipMemcpyAsync(ps.d_flags, &keep, 4, hipMemcpyHostToDevice, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    continue;
-                }
-                const int code = flags_to_code(fl);
-                if (code != HF_OK) return code;
-                break;
-            }
-            ps.recs_all = true; ps.scales_all = true;
-        }
+        const int rc_ = pass_all_records(ps);
+        if (rc_) return rc_;
         // the positions of a range are scattered over the plan: gathered on the device, one copy back (maps uploaded on first use)
         if (!ps.d_slot_of) {
             HIPCHK(hipMalloc((void**) &ps.d_slot_of, (size_t) tr.N * 4));
@@ -2276,5 +2293,112 @@ int hf_get_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
     const Track& tr = ctx->tr;
     HIPCHK(hipSetDevice(tr.device));
     if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->smp.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact interval probabilities (hf_interval.h) over the last full pass: the host cuts every job into chunk-local parts and every part's
+// interior windows into pieces, k_iv_piece multiplies the pieces, k_iv_chain every part's vectors through them, the host sums the parts
+// of a job in chunk order.  Last in the file, like the decoders, so that no pass kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_interval.h"
+
+// pieces and parts per device batch (a job is never split across batches, and a batch holds at least one job)
+#define HF_IV_BATCH_PIECES (1 << 20)
+#define HF_IV_BATCH_PARTS (1 << 20)
+
+int hf_get_interval_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, double* log_p_host) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_get_interval_log_probs: bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    if (n < 0) return set_err(HF_E_ARG, "hf_get_interval_log_probs: n < 0");
+    if (n > 0 && (!first || !last || !state_mask || !log_p_host)) return set_err(HF_E_ARG, "hf_get_interval_log_probs: NULL array");
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, "hf_get_interval_log_probs: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    for (int64_t i = 0; i < n; i++) {
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
+            return set_err(HF_E_ARG, "hf_get_interval_log_probs: bad range (job " + std::to_string(i) + ")");
+        if (state_mask[i] < 1 || state_mask[i] > 15)
+            return set_err(HF_E_ARG, "hf_get_interval_log_probs: state_mask must be 1..15 (job " + std::to_string(i) + ")");
+    }
+    HIPCHK(hipSetDevice(tr.device));
+    if (n == 0) return HF_OK;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_interval_log_probs: the last pass kept no pair records");
+    if (!seq) {
+        const int rc = pass_all_records(ps);
+        if (rc) return rc;
+    }
+    hipStream_t st = ps.last_stream;
+    IntervalBufs& ib = ctx->iv;
+    std::vector<IvPiece> pieces;
+    std::vector<IvPart> parts;
+    std::vector<int64_t> job_p0;
+    std::vector<double> val;
+    for (int64_t j0 = 0; j0 < n;) {
+        // the jobs of this batch, cut into parts and pieces
+        pieces.clear(); parts.clear(); job_p0.clear();
+        int64_t j1 = j0;
+        while (j1 < n && (j1 == j0 || (pieces.size() < HF_IV_BATCH_PIECES && parts.size() < HF_IV_BATCH_PARTS))) {
+            job_p0.push_back((int64_t) parts.size());
+            const int mask = state_mask[j1];
+            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
+            for (int64_t a = first[j1]; a <= last[j1]; c++) {
+                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
+                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
+                IvPart pt{a, b, (int) pieces.size(), 0, mask, c};
+                for (int64_t t = a + 1; t <= b;) {
+                    const int64_t e = std::min<int64_t>(b, (t / HF_IV_PIECE + 1) * HF_IV_PIECE - 1);
+                    pieces.push_back(IvPiece{t, (int) (e - t + 1), mask});
+                    t = e + 1;
+                }
+                pt.p1 = (int) pieces.size();
+                parts.push_back(pt);
+                a = b + 1;
+            }
+            j1++;
+        }
+        job_p0.push_back((int64_t) parts.size());
+        const size_t np = pieces.size(), nq = parts.size();
+        const size_t o_parts = Slab::granule(np * sizeof(IvPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(IvPart));
+        const size_t o_pe = o_pm + Slab::granule(np * 32 * 8), o_out = o_pe + Slab::granule(np * 2 * 4), bytes = o_out + Slab::granule(nq * 8);
+        if (bytes > ib.cap) {
+            ib.release();
+            if (hipMalloc((void**) &ib.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); ib.d_buf = nullptr;
+                return set_err(HF_E_HIP, "hf_get_interval_log_probs: out of device memory"); }
+            ib.cap = bytes;
+        }
+        IvPiece* d_pieces = reinterpret_cast<IvPiece*>(ib.d_buf);
+        IvPart* d_parts = reinterpret_cast<IvPart*>(ib.d_buf + o_parts);
+        double* d_pm = reinterpret_cast<double*>(ib.d_buf + o_pm);
+        int* d_pe = reinterpret_cast<int*>(ib.d_buf + o_pe);
+        double* d_out = reinterpret_cast<double*>(ib.d_buf + o_out);
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(IvPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(IvPart), hipMemcpyHostToDevice, st));
+        if (seq) {
+            if (np) hipLaunchKernelGGL(k_iv_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, (const int32_t*) nullptr,
+                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, d_pm, d_pe);
+            hipLaunchKernelGGL(k_iv_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe,
+                               (const int32_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr, tr.d_off, tr.d_chunk_tile0,
+                               ps.d_f, ps.d_b, d_out);
+        } else {
+            if (np) hipLaunchKernelGGL(k_iv_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, tr.d_arow, ps.d_lutA,
+                                       (const uint32_t*) nullptr, (const double*) nullptr, (const DevParams*) nullptr, d_pm, d_pe);
+            hipLaunchKernelGGL(k_iv_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe,
+                               tr.d_pos, tr.d_pos_f, ps.d_recs_all, (const int64_t*) nullptr, (const int32_t*) nullptr,
+                               (const double*) nullptr, (const double*) nullptr, d_out);
+        }
+        HIPCHK(hipGetLastError());
+        val.resize(nq);
+        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
+            double s = 0.0;
+            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) s += val[(size_t) k];
+            log_p_host[j] = s;
+        }
+        j0 = j1;
+    }
     return HF_OK;
 }

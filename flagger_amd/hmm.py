@@ -579,6 +579,22 @@ class EMList:
                 N.check(self._L.hf_get_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_sample_labels")
         return out
 
+    def interval_log_probs(self, first, last, mask) -> np.ndarray:
+        """Exact interval probabilities under the model of the last full pass (hf_get_interval_log_probs): for every job i,
+        log P(every window of first[i]..last[i] (inclusive) has a state in the set mask[i] (bit s = state s) | data) -> float64[n].
+        Scalars broadcast against arrays.  P(some window in state k) = -expm1 of the job with mask 15 & ~(1 << k)."""
+        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("interval_log_probs: a state mask must be 1..15")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        out = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_interval_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  _dptr(out)), "hf_get_interval_log_probs")
+        return out
+
     def forward_backward(self, first: int = 0, n: Optional[int] = None):
         n = self.store.n_windows - first if n is None else n
         f, b, sc = np.empty((n, 4)), np.empty((n, 4)), np.empty(n)
@@ -624,6 +640,14 @@ def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.n
     if not hasattr(emList, "sample_paths"):
         raise TypeError("EM_samplePathsForList: %s has no path sampler" % type(emList).__name__)
     return emList.sample_paths(model, n_samples, seed)
+
+
+def EM_getIntervalLogProbsForList(emList, first, last, mask) -> np.ndarray:
+    """log P(every window of first[i]..last[i] has a state in mask[i] | data) under the model of the last full pass, per job (no
+    counterpart in the reference): float64[n].  `emList`: an EMList."""
+    if not hasattr(emList, "interval_log_probs"):
+        raise TypeError("EM_getIntervalLogProbsForList: %s has no interval getter" % type(emList).__name__)
+    return emList.interval_log_probs(first, last, mask)
 
 
 class EMBatch:

@@ -231,6 +231,22 @@ int hf_get_labels(hf_ctx *ctx, int8_t *labels_host);                            
 int hf_get_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_host);        /* [n][4] hmm.c:671-685 */
 int hf_get_forward_backward(hf_ctx *ctx, int64_t first, int64_t n, double *f_host, double *b_host,
                             double *scales_host);                                      /* EM.f/.b/.scales */
+/* Exact interval probabilities (flagger_amd/csrc/hf_interval.h), under the model of the last HF_MODE_FULL pass like hf_get_posterior.
+ * Job i is the window range first[i]..last[i] (global indices, inclusive, 0 <= first <= last < n_windows; it may span chunks) and the
+ * state set S = state_mask[i] (bit s = state s: 0 Err, 1 Dup, 2 Hap, 3 Col; 1..15):
+ *   log_p[i] = log P(s_t in S for every t in first..last | data)
+ * Chunks are independent chains: the value is the sum, in chunk order, over the job's chunk-local parts [a, b] of log(N_S / N),
+ *   N_S = sum_{p in S} sum_{q in S} f_a[p] M_S[p][q] b_b[q],   M_S = prod_{t=a+1..b} (A_t D_S) (the identity when a == b),
+ *   D_S = diag(1_S), N = the same with all four states; f, b the pass's scaled forward and backward vectors (hf_get_forward_backward),
+ *   A_t the row the pass multiplied by at window t.
+ * -inf when no path of the interval stays in S; mask 15 gives exactly 0.0.  P(some window of the range in state k) is
+ * -expm1(log_p) of the job with mask 15 & ~(1 << k).  A job's value depends only on (first, last, mask) and the pass, bitwise: not on
+ * the other jobs of the call, their order or their number.  Synchronous on the pass's stream; the first call after an EM pass of the
+ * default algorithm re-runs the segment kernel once, as hf_get_posterior's does.  Buffers of its own: nothing an EM pass, hf_viterbi
+ * or hf_sample_paths reads is written.  HF_E_ARG: no full pass yet or the last pass forward-only, n < 0, a NULL array with n > 0, a
+ * bad range, a mask of 0 or above 15. */
+int hf_get_interval_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last,
+                              const uint8_t *state_mask, double *log_p_host);
 /* Most-probable-path (Viterbi) decoding of every chunk (flagger_amd/csrc/hf_viterbi.h): with the parameters `p`, for a chunk of T windows
  *   s* = argmax over s_0..s_{T-1} of first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}],
  *   first[s] = trans[r_0][4][s] * e_0[s],  A_t = the row a pass builds (transition x emission),  end[s] = trans[r_{T-1}][s][4];
