@@ -111,6 +111,9 @@ def lib() -> C.CDLL:
     sig("hf_get_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_forward_backward", C.c_int, vp, i64, i64, pd, pd, pd)
     sig("hf_get_interval_log_probs", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), pd)
+    sig("hf_set_alpha_stats", C.c_int, vp, C.c_int)
+    sig("hf_alpha_stats_len", i64, vp)
+    sig("hf_get_alpha_stats", C.c_int, vp, pd)
     sig("hf_viterbi", C.c_int, vp, C.POINTER(hf_params), vp)
     sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
@@ -205,6 +208,9 @@ def lib() -> C.CDLL:
     sig("hfm_set_param_vector", None, vp, pd)
     sig("hfm_best_collapsed_comps", C.c_int, C.POINTER(C.c_uint16), i64, C.POINTER(i32), C.c_int)
     sig("hfm_read_alpha_tsv", C.c_int, C.c_char_p, pd)
+    sig("hfm_get_alpha", None, vp, pd)
+    sig("hfm_set_alpha", C.c_int, vp, pd)
+    sig("hfm_estimate_alpha", C.c_int, vp, pd, pd, C.POINTER(C.c_uint8), dbl, dbl, dbl)
     sig("hf_em_iterate", C.c_int, vp, vp, C.c_int, C.c_int, dbl, pd, C.POINTER(C.c_int), vp)
     # summary tables (include/hmm_flagger_summary.h)
     sig("hfs_write_all_tables", C.c_int, C.POINTER(hfs_input), C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, dbl, C.c_int)

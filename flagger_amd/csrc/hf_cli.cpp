@@ -67,6 +67,10 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"uncertaintySeed", required_argument, nullptr, 1008},      // their seed [0]
     {"runConfidence", no_argument, nullptr, 1009},              // exact per-run label probabilities (hf_get_interval_log_probs)
     {"regionProbs", required_argument, nullptr, 1010},          // exact per-region label probabilities for the regions of a BED file
+    {"fitAlpha", no_argument, nullptr, 1011},                   // fit the alpha matrix inside the EM (hf_get_alpha_stats, hfm_estimate_alpha)
+    {"fitAlphaEntries", required_argument, nullptr, 1012},      // the free entries, pre,state pairs separated by ':'
+    {"fitAlphaMax", required_argument, nullptr, 1013},          // their upper bound [0.8]
+    {"fitAlphaEvery", required_argument, nullptr, 1014},        // every P-th iteration is an alpha-iteration [2]
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -117,7 +121,17 @@ static void usage(const char* program) {
             "                                      as a Phred quality, and the mean posterior; one GPU, not with --gpus N>1 or --sweepAlpha\n"
             "         --regionProbs FILE           for every region of a BED file (ctg start end [name]) write the exact probabilities that\n"
             "                                      any / every window it meets has each label, and the mean posterior, to\n"
-            "                                      region_label_probabilities.tsv; one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      region_label_probabilities.tsv; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --fitAlpha                   fit the alpha matrix inside the EM, starting from --alphaTsv (or 0): every P-th iteration\n"
+            "                                      updates the free alpha entries (each to the maximiser of the expected log-likelihood, from the\n"
+            "                                      exact gradient and curvature of its pass) instead of the other parameters; writes\n"
+            "                                      alpha_fitted.tsv (readable by --alphaTsv) and alpha_trace.tsv (per alpha-iteration: iteration,\n"
+            "                                      log-likelihood, 16 alpha before, 16 gradients, 16 curvatures); gaussian and trunc_exp_gaussian,\n"
+            "                                      one GPU, not with --accelerate, --gpus N>1 or --sweepAlpha\n"
+            "         --fitAlphaEntries LIST       the free entries as pre,state pairs separated by ':' (states 0 Err, 1 Dup, 2 Hap, 3 Col)\n"
+            "                                      [0,0:0,2:1,1:1,2:2,0:2,1:2,2:2,3:3,2:3,3]\n"
+            "         --fitAlphaMax X              upper bound of a fitted entry, 0 <= X < 1 (the lower bound is 0) [0.8]\n"
+            "         --fitAlphaEvery P            iterations P, 2P, ... are alpha-iterations [2]\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -575,6 +589,10 @@ int main(int argc, char* argv[]) {
     uint64_t uncertaintySeed = 0;
     bool runConfidence = false;
     const char* regionProbsPath = nullptr;
+    bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
+    uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
+    double fitAlphaMax = 0.8;                                                          // its --upperBound (its --lowerBound is 0)
+    int fitAlphaEvery = 2;
     int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1, loopbackRanks = 0;
     const char* binArrayFilePath = nullptr;
     bool writeBenchmarkingStatsPerIteration = false;
@@ -659,6 +677,35 @@ int main(int argc, char* argv[]) {
             }
             case 1009: runConfidence = true; break;
             case 1010: regionProbsPath = optarg; break;
+            case 1011: fitAlpha = true; break;
+            case 1012: {                                         // pre,state[:pre,state...]
+                fitAlphaOptions = true;
+                memset(fitAlphaMask, 0, sizeof fitAlphaMask);
+                const char* q = optarg;
+                bool ok = *q != 0;
+                while (ok && *q) {
+                    ok = q[0] >= '0' && q[0] <= '3' && q[1] == ',' && q[2] >= '0' && q[2] <= '3' && (q[3] == 0 || (q[3] == ':' && q[4] != 0));
+                    if (!ok) break;
+                    fitAlphaMask[(q[0] - '0') * 4 + (q[2] - '0')] = 1;
+                    q += q[3] ? 4 : 3;
+                }
+                if (!ok) fitAlphaBad = true;
+                break;
+            }
+            case 1013: {
+                char* end = nullptr;
+                fitAlphaOptions = true;
+                fitAlphaMax = strtod(optarg, &end);
+                if (end == optarg || *end != 0 || !(fitAlphaMax >= 0.0 && fitAlphaMax < 1.0)) fitAlphaMax = -1.0;
+                break;
+            }
+            case 1014: {
+                char* end = nullptr;
+                fitAlphaOptions = true;
+                const long v = strtol(optarg, &end, 10);
+                fitAlphaEvery = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
+                break;
+            }
             case 1004:
                 if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
                 else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
@@ -691,6 +738,29 @@ int main(int argc, char* argv[]) {
     if ((runConfidence || regionProbsPath) && (nGpus > 1 || sweepListPath)) {
         fprintf(stderr, "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts(),
                 runConfidence ? "--runConfidence" : "--regionProbs");
+        return EXIT_FAILURE;
+    }
+    // --fitAlpha: its own arguments and the refused combinations, before the input is read
+    if (fitAlphaBad) {
+        fprintf(stderr, "[%s] Error: --fitAlphaEntries should be pre,state pairs of state indices 0..3 separated by ':' (e.g. 0,0:2,2).\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (fitAlphaMax < 0.0) { fprintf(stderr, "[%s] Error: --fitAlphaMax should be a number in [0, 1).\n", ts()); return EXIT_FAILURE; }
+    if (fitAlphaEvery < 1) { fprintf(stderr, "[%s] Error: --fitAlphaEvery should be a positive integer.\n", ts()); return EXIT_FAILURE; }
+    if (fitAlphaOptions && !fitAlpha) {
+        fprintf(stderr, "[%s] Error: --fitAlphaEntries, --fitAlphaMax and --fitAlphaEvery need --fitAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (fitAlpha && acceleration) {
+        fprintf(stderr, "[%s] Error: --fitAlpha cannot be combined with --accelerate (SQUAREM extrapolates the other parameters only).\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (fitAlpha && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --fitAlpha runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (fitAlpha && modelType == HF_MODEL_NEGATIVE_BINOMIAL) {
+        fprintf(stderr, "[%s] Error: --fitAlpha needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial emission has no alpha).\n", ts());
         return EXIT_FAILURE;
     }
     std::vector<Region> regions;
@@ -850,6 +920,23 @@ int main(int argc, char* argv[]) {
     write_params(model, dir, "initial");
     int iter = 1;
     bool converged = false;
+    // --fitAlpha: iterations P, 2P, ... are alpha-iterations (their pass is followed by hfm_estimate_alpha alone), the others today's; the
+    // run has converged when the latest iteration of each kind reported convergence
+    bool convergedEm = false, convergedAlpha = false;
+    FILE* atf = nullptr;
+    std::vector<double> alphaStats;
+    if (fitAlpha) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --fitAlpha needs a single-GPU context (no --exchange).\n", ts()); return EXIT_FAILURE; }
+        if ((rc = hf_set_alpha_stats(run.ctx, 1)) != HF_OK) return die(rc);
+        alphaStats.assign((size_t) hf_alpha_stats_len(run.ctx), 0.0);
+        atf = fopen((dir + "/alpha_trace.tsv").c_str(), "w");
+        if (!atf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
+        fprintf(atf, "#Iteration\tLoglikelihood");
+        for (const char* what : {"alpha", "G", "H"})
+            for (int k = 0; k < 16; k++) fprintf(atf, "\t%s_%d_%d", what, k / 4, k % 4);
+        fprintf(atf, "\n");
+    }
+    FileCloser atfClose{atf};
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
     const double emStart = real_time();
@@ -891,10 +978,27 @@ int main(int argc, char* argv[]) {
             if (rc != HF_OK) return die(rc);
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Finished SQUAREM acceleration.\n", ts(), iter);
         }
-        {
+        if (fitAlpha && iter % fitAlphaEvery == 0) {
+            const double t0 = real_time();
+            if ((rc = hf_get_alpha_stats(run.ctx, alphaStats.data())) != HF_OK) return die(rc);
+            double a0[16], gh[32] = {0};
+            hfm_get_alpha(model, a0);
+            for (size_t r = 0; r * 32 < alphaStats.size(); r++)          // region order
+                for (int k = 0; k < 32; k++) gh[k] += alphaStats[r * 32 + (size_t) k];
+            const int cv = hfm_estimate_alpha(model, alphaStats.data(), run.stats.data(), fitAlphaMask, 0.0, fitAlphaMax, convergenceTol);
+            emTime += real_time() - t0;
+            if (cv < 0) { fprintf(stderr, "[%s] Error: hfm_estimate_alpha refused its arguments.\n", ts()); return EXIT_FAILURE; }
+            convergedAlpha = cv != 0;
+            converged = convergedEm && convergedAlpha;
+            fprintf(atf, "%d\t%.17g", iter - 1, run.stats[0]);
+            for (int k = 0; k < 16; k++) fprintf(atf, "\t%.17g", a0[k]);
+            for (int k = 0; k < 32; k++) fprintf(atf, "\t%.17g", gh[k]);
+            fprintf(atf, "\n");
+        } else {
             const double t0 = real_time();
             converged = hfm_estimate(model, run.stats.data(), convergenceTol) != 0;
             emTime += real_time() - t0;
+            if (fitAlpha) { convergedEm = converged; converged = convergedEm && convergedAlpha; }
         }
         fprintf(stderr, "[%s] [Iteration %s = %d] Parameters are estimated and updated.\n", ts(), acceleration ? "accelerated" : "", iter);
         if (writeParamsPerIter) {
@@ -917,6 +1021,15 @@ int main(int argc, char* argv[]) {
     fclose(llf);
     llf = nullptr;
     write_params(model, dir, "final");
+    if (fitAlpha) {        // four tab-separated rows that --alphaTsv reads back to the same doubles
+        double a[16];
+        hfm_get_alpha(model, a);
+        FILE* af = fopen((dir + "/alpha_fitted.tsv").c_str(), "w");
+        if (!af) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
+        for (int i = 0; i < 4; i++) fprintf(af, "%.17g\t%.17g\t%.17g\t%.17g\n", a[i * 4], a[i * 4 + 1], a[i * 4 + 2], a[i * 4 + 3]);
+        fclose(af);
+        (void) hf_set_alpha_stats(run.ctx, 0);
+    }
     std::vector<int8_t> labels((size_t) N);
     if ((rc = run.labels(labels.data())) != HF_OK) return die(rc);
     // --viterbi: the final BED and the final tables take the most probable path under the final parameters; everything else

@@ -457,13 +457,29 @@ struct IntervalBufs {
     void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
 };
 
-// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer
+// the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
+struct AlphaStats {
+    bool on = false;          // hf_set_alpha_stats
+    bool pass = false;        // the last pass was a full pass with the switch on
+    bool cached = false;      // `last` holds the statistics of the last pass
+    bool planned = false;
+    int64_t n_pairs = 0; int n_blocks = 0;
+    char* d_buf = nullptr;    // pair_t | pair_c | blocks | rblk0 | part | out | terms
+    long long* d_pair_t = nullptr; int32_t* d_pair_c = nullptr; void* d_blocks = nullptr; int32_t* d_rblk0 = nullptr;
+    double* d_part = nullptr; double* d_out = nullptr; double* d_terms = nullptr;   // d_terms: [rows of A][32], HF_ALGO_SCAN
+    std::vector<double> last;
+    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; planned = false; }
+};
+
+// the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
+// the alpha statistics' plan and buffers
 struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
     Sampler smp;
     IntervalBufs iv;
+    AlphaStats al;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1000,6 +1016,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->vit.release();
     ctx->smp.release();
     ctx->iv.release();
+    ctx->al.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -1323,9 +1340,11 @@ int hf_estep(hf_ctx* ctx, const hf_params* p, int mode, void* stream) {
     int rc = pack_params(tr, p, ps.h_params);
     if (rc) return rc;
     ps.last_p = *p; ps.last_mode = mode; ps.last_stream = st;
+    ctx->al.pass = false; ctx->al.cached = false;
     if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev0, st));
     rc = enqueue_pass(ps, p, mode, st);
     if (rc) return rc;
+    ctx->al.pass = ctx->al.on && mode == HF_MODE_FULL;
     if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
     ps.ev_valid = pass_events(ps);
     ps.have_full = (mode == HF_MODE_FULL);
@@ -2400,5 +2419,155 @@ int hf_get_interval_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
         }
         j0 = j1;
     }
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// the alpha statistics (hf_alpha.h) of the last full pass: like the interval getter, nothing of it runs inside a pass — hf_set_alpha_stats
+// only marks the passes whose statistics may be asked for, and hf_get_alpha_stats computes them from what the pass left (on the scan path
+// after the getters' lazy re-run of the segment kernel).  Last in the file, so that no pass kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_alpha.h"
+
+// the plan: every pair (t-1, t) of every chunk, sorted by region of t, in blocks of one region
+static int alpha_plan(hf_ctx* ctx) {
+    const Track& tr = ctx->tr;
+    AlphaStats& al = ctx->al;
+    if (al.planned) return HF_OK;
+    std::vector<uint32_t> rec((size_t) tr.N);
+    if (tr.N > 0) HIPCHK(hipMemcpy(rec.data(), tr.d_rec, (size_t) tr.N * 4, hipMemcpyDeviceToHost));
+    // the order of a region's pairs: HF_ALGO_SCAN by the position of window t's pair record (the plan keeps the records of one row of A
+    // together: the record reads of a wavefront are contiguous and its rows few), HF_ALGO_SEQ by t
+    std::vector<long long> ord_t; std::vector<int32_t> ord_c;
+    ord_t.reserve((size_t) tr.N); ord_c.reserve((size_t) tr.N);
+    bool by_pos = tr.algo == HF_ALGO_SCAN && tr.d_pos && tr.n_pos > 0;
+    if (by_pos) {
+        std::vector<int32_t> pos((size_t) tr.N);
+        HIPCHK(hipMemcpy(pos.data(), tr.d_pos, (size_t) tr.N * 4, hipMemcpyDeviceToHost));
+        std::vector<int64_t> inv_t((size_t) tr.n_pos, -1); std::vector<int32_t> inv_c((size_t) tr.n_pos, 0);
+        for (int c = 0; c < tr.C && by_pos; c++)
+            for (int64_t t = tr.h_off[(size_t) c] + 1; t < tr.h_off[(size_t) c + 1]; t++) {
+                const int64_t q = pos[(size_t) t];
+                if (q < 0 || q >= tr.n_pos || inv_t[(size_t) q] >= 0) { by_pos = false; break; }    // (not a plan this order understands: by t)
+                inv_t[(size_t) q] = t; inv_c[(size_t) q] = c;
+            }
+        if (by_pos)
+            for (int64_t q = 0; q < tr.n_pos; q++)
+                if (inv_t[(size_t) q] >= 0) { ord_t.push_back(inv_t[(size_t) q]); ord_c.push_back(inv_c[(size_t) q]); }
+    }
+    if (!by_pos) {
+        ord_t.clear(); ord_c.clear();
+        for (int c = 0; c < tr.C; c++)
+            for (int64_t t = tr.h_off[(size_t) c] + 1; t < tr.h_off[(size_t) c + 1]; t++) { ord_t.push_back(t); ord_c.push_back(c); }
+    }
+    std::vector<int64_t> cnt((size_t) tr.R + 1, 0);
+    for (const long long t : ord_t) {
+        const unsigned r = REC_REGION(rec[(size_t) t]);
+        if (r < (unsigned) tr.R) cnt[r + 1]++;
+    }
+    for (int r = 0; r < tr.R; r++) cnt[(size_t) r + 1] += cnt[(size_t) r];
+    const int64_t np = cnt[(size_t) tr.R];
+    std::vector<long long> pair_t((size_t) np);
+    std::vector<int32_t> pair_c((size_t) np);
+    {
+        std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
+        for (size_t i = 0; i < ord_t.size(); i++) {      // every region's pairs in that order
+            const unsigned r = REC_REGION(rec[(size_t) ord_t[i]]);
+            if (r >= (unsigned) tr.R) continue;
+            const int64_t k = fill[r]++;
+            pair_t[(size_t) k] = ord_t[i]; pair_c[(size_t) k] = ord_c[i];
+        }
+    }
+    std::vector<AlBlock> blocks;
+    std::vector<int32_t> rblk0((size_t) tr.R + 1, 0);
+    for (int r = 0; r < tr.R; r++) {
+        rblk0[(size_t) r] = (int32_t) blocks.size();
+        for (int64_t p0 = cnt[(size_t) r]; p0 < cnt[(size_t) r + 1]; p0 += HF_AL_BLOCK)
+            blocks.push_back(AlBlock{p0, (int) std::min<int64_t>(HF_AL_BLOCK, cnt[(size_t) r + 1] - p0), r});
+    }
+    rblk0[(size_t) tr.R] = (int32_t) blocks.size();
+    const size_t nb = blocks.size();
+    const size_t o_c = Slab::granule((size_t) np * 8), o_b = o_c + Slab::granule((size_t) np * 4), o_r = o_b + Slab::granule(nb * sizeof(AlBlock)),
+                 o_p = o_r + Slab::granule(((size_t) tr.R + 1) * 4), o_o = o_p + Slab::granule(nb * 32 * 8), o_t = o_o + Slab::granule((size_t) tr.R * 32 * 8),
+                 bytes = o_t + Slab::granule(tr.algo == HF_ALGO_SCAN ? (size_t) tr.tabwork.n_jobs * 32 * 8 : 0);
+    al.release();      // (a buffer an earlier, failed attempt left)
+    if (hipMalloc((void**) &al.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); al.d_buf = nullptr;
+        return set_err(HF_E_HIP, "hf_get_alpha_stats: out of device memory"); }
+    al.d_pair_t = reinterpret_cast<long long*>(al.d_buf); al.d_pair_c = reinterpret_cast<int32_t*>(al.d_buf + o_c);
+    al.d_blocks = al.d_buf + o_b; al.d_rblk0 = reinterpret_cast<int32_t*>(al.d_buf + o_r);
+    al.d_part = reinterpret_cast<double*>(al.d_buf + o_p); al.d_out = reinterpret_cast<double*>(al.d_buf + o_o);
+    al.d_terms = reinterpret_cast<double*>(al.d_buf + o_t);
+    if (np) {
+        HIPCHK(hipMemcpy(al.d_pair_t, pair_t.data(), (size_t) np * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(al.d_pair_c, pair_c.data(), (size_t) np * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(al.d_blocks, blocks.data(), nb * sizeof(AlBlock), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(al.d_rblk0, rblk0.data(), ((size_t) tr.R + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());      // (the copies ran on the null stream, the kernels will run on the stream of the pass)
+    al.n_pairs = np; al.n_blocks = (int) nb; al.planned = true;
+    return HF_OK;
+}
+
+int hf_set_alpha_stats(hf_ctx* ctx, int on) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_set_alpha_stats: bad argument");
+    if (on && ctx->pass.d_nbE)
+        return set_err(HF_E_ARG, "hf_set_alpha_stats: the context has run negative_binomial passes, whose emission has no alpha");
+    ctx->al.on = on != 0;
+    if (!on) { ctx->al.pass = false; ctx->al.cached = false; }
+    return HF_OK;
+}
+
+int64_t hf_alpha_stats_len(const hf_ctx* ctx) { return ctx ? 32 * (int64_t) ctx->tr.R : 0; }
+
+int hf_get_alpha_stats(hf_ctx* ctx, double* out_host) {
+    if (!ctx || !out_host) return set_err(HF_E_ARG, "hf_get_alpha_stats: bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    AlphaStats& al = ctx->al;
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, "hf_get_alpha_stats: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    if (!al.pass) return set_err(HF_E_ARG, "hf_get_alpha_stats: the last pass ran without hf_set_alpha_stats(ctx, 1)");
+    if (ps.last_p.model_type == HF_MODEL_NEGATIVE_BINOMIAL)
+        return set_err(HF_E_ARG, "hf_get_alpha_stats: the negative_binomial emission has no alpha");
+    const size_t len = (size_t) tr.R * 32;
+    if (al.cached) { std::memcpy(out_host, al.last.data(), len * 8); return HF_OK; }
+    HIPCHK(hipSetDevice(tr.device));
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    al.last.assign(len, 0.0);
+    if (tr.C > 0 && tr.N > 0) {
+        if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_alpha_stats: the last pass kept no pair records");
+        if (!seq && tr.tabwork.n_jobs != tr.n_arows) return set_err(HF_E_ARG, "hf_get_alpha_stats: the job list of the context is not the list of its rows of A");
+        if (!seq) {
+            const int rc = pass_all_records(ps);
+            if (rc) return rc;
+        }
+        const int rc = alpha_plan(ctx);
+        if (rc) return rc;
+        hipStream_t st = ps.last_stream;
+        const AlBlock* blocks = reinterpret_cast<const AlBlock*>(al.d_blocks);
+        if (al.n_blocks > 0) {
+            if (seq)
+                hipLaunchKernelGGL(k_alpha_pairs<true>, dim3((unsigned) al.n_blocks), dim3(HF_AL_THREADS), 0, st, blocks, al.d_pair_t, al.d_pair_c,
+                                   tr.d_rec, tr.d_beta, ps.d_params, (const int32_t*) nullptr, (const double*) nullptr, (const double*) nullptr, ps.d_E,
+                                   (const int32_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr, tr.d_off, tr.d_chunk_tile0,
+                                   ps.d_f, ps.d_b, al.d_part);
+            else {
+                // (the rows of A of a segment pass are the jobs of the track's list: enqueue_pass)
+                const int nj = tr.tabwork.n_jobs;
+                hipLaunchKernelGGL(k_alpha_terms, dim3((unsigned) ((nj + 255) / 256)), dim3(256), 0, st, nj, tr.d_jobs, ps.d_params, al.d_terms);
+                hipLaunchKernelGGL(k_alpha_pairs<false>, dim3((unsigned) al.n_blocks), dim3(HF_AL_THREADS), 0, st, blocks, al.d_pair_t, al.d_pair_c,
+                                   tr.d_rec, tr.d_beta, ps.d_params, tr.d_arow, ps.d_lutA, al.d_terms, (const double*) nullptr, tr.d_pos, tr.d_pos_f,
+                                   ps.d_recs_all, (const int64_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr,
+                                   (const double*) nullptr, al.d_part);
+            }
+        }
+        hipLaunchKernelGGL(k_alpha_sum, dim3((unsigned) tr.R), dim3(HF_AL_SUM_THREADS), 0, st, al.d_rblk0, al.d_part, al.d_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(al.last.data(), al.d_out, len * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    al.cached = true;
+    std::memcpy(out_host, al.last.data(), len * 8);
     return HF_OK;
 }

@@ -387,6 +387,41 @@ int hfm_estimate(hfm_model* m, const double* stats, double tol) {
     return converged ? 1 : 0;
 }
 
+// ---- the alpha matrix: getter, setter and its conditional maximisation from the alpha statistics of a pass ----
+void hfm_get_alpha(const hfm_model* m, double* alpha16) { std::memcpy(alpha16, m->alpha, sizeof(m->alpha)); }
+
+int hfm_set_alpha(hfm_model* m, const double* alpha16) {
+    if (!m || !alpha16) return -1;
+    for (int k = 0; k < 16; k++) if (!(0.0 <= alpha16[k] && alpha16[k] < 1.0)) return -1;
+    std::memcpy(m->alpha, alpha16, sizeof(m->alpha));
+    return 0;
+}
+
+int hfm_estimate_alpha(hfm_model* m, const double* alpha_stats, const double* stats, const uint8_t* free_mask16, double lo, double hi,
+                       double tol) {
+    if (!m || !alpha_stats || !stats || !free_mask16 || m->nb() || !(0.0 <= lo && lo <= hi && hi < 1.0)) return -1;
+    const int64_t stride = hf_region_stride(m->K);
+    bool converged = true;
+    for (int p = 0; p < S; p++)
+        for (int s = 0; s < S; s++) {
+            if (!free_mask16[p * 4 + s]) continue;
+            double G = 0.0, H = 0.0, count = 0.0;
+            for (int r = 0; r < m->R; r++) {               // region order
+                G += alpha_stats[(size_t) r * 32 + p * 4 + s];
+                H += alpha_stats[(size_t) r * 32 + 16 + p * 4 + s];
+                count += stats[1 + r * stride + 24 * m->K + p * 4 + s];
+            }
+            if (!(0.0 < H) || !(kMinCountForUpdate < count)) continue;
+            const double old = m->alpha[p][s];
+            double nv = old + G / H;
+            if (!(nv == nv)) continue;
+            nv = nv < lo ? lo : hi < nv ? hi : nv;
+            m->alpha[p][s] = nv;
+            converged &= std::fabs(nv - old) < tol;
+        }
+    return converged ? 1 : 0;
+}
+
 // ---- TSV writers: hmm.c:137-239 ----
 static const char* kStateNames[5] = {"Err", "Dup", "Hap", "Col", "Msj"};
 

@@ -76,6 +76,21 @@ class HMM:
         assert v.size == self._L.hfm_param_len(self._h)
         self._L.hfm_set_param_vector(self._h, _dptr(v))
 
+    @property
+    def alpha(self) -> np.ndarray:
+        """The alpha matrix alpha[preState][state] (hfm_get_alpha): float64[4][4], a copy."""
+        a = np.empty((4, 4), dtype=np.float64)
+        self._L.hfm_get_alpha(self._h, _dptr(a))
+        return a
+
+    def set_alpha(self, alpha) -> None:
+        """hfm_set_alpha: every entry in [0, 1)."""
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        if a.shape != (4, 4):
+            raise ValueError("set_alpha: a 4x4 matrix")
+        if self._L.hfm_set_alpha(self._h, _dptr(a)) != 0:
+            raise ValueError("set_alpha: every alpha value must be in [0, 1)")
+
     def copy(self) -> "HMM":
         m = HMM(self._L.hfm_copy(self._h))
         m.loglikelihood = self.loglikelihood
@@ -595,6 +610,17 @@ class EMList:
                                                   _dptr(out)), "hf_get_interval_log_probs")
         return out
 
+    def set_alpha_stats(self, on: bool = True) -> None:
+        """hf_set_alpha_stats: full passes from now on can be asked for the alpha statistics (alpha_stats)."""
+        N.check(self._L.hf_set_alpha_stats(self._h, int(bool(on))), "hf_set_alpha_stats")
+
+    def alpha_stats(self) -> np.ndarray:
+        """The alpha statistics of the last full pass (hf_get_alpha_stats): float64[n_regions][2][4][4], [r][0] = G the derivative of the
+        log-likelihood in alpha[pre][s], [r][1] = H the curvature of the expected complete-data log-likelihood."""
+        out = np.empty(int(self._L.hf_alpha_stats_len(self._h)), dtype=np.float64)
+        N.check(self._L.hf_get_alpha_stats(self._h, _dptr(out)), "hf_get_alpha_stats")
+        return out.reshape(-1, 2, 4, 4)
+
     def forward_backward(self, first: int = 0, n: Optional[int] = None):
         n = self.store.n_windows - first if n is None else n
         f, b, sc = np.empty((n, 4)), np.empty((n, 4)), np.empty(n)
@@ -760,6 +786,39 @@ def HMM_estimateParameters(model: HMM, convergenceTol: float) -> bool:
     return bool(N.lib().hfm_estimate(model._h, _dptr(st), float(convergenceTol)))
 
 
+# the ten entries (pre, state) the reference's tuner frees (programs/src/tune_alpha_hmm_flagger.py), its bounds
+FIT_ALPHA_ENTRIES = ((0, 0), (0, 2), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2), (2, 3), (3, 2), (3, 3))
+FIT_ALPHA_MAX = 0.8
+
+
+def alpha_free_mask(entries=FIT_ALPHA_ENTRIES) -> np.ndarray:
+    m = np.zeros((4, 4), dtype=np.uint8)
+    for p, s in entries:
+        if not (0 <= int(p) < 4 and 0 <= int(s) < 4):
+            raise ValueError("alpha entry (%r, %r): pre and state must be 0..3" % (p, s))
+        m[int(p), int(s)] = 1
+    return m
+
+
+def HMM_estimateAlpha(model: HMM, alphaStats: np.ndarray, convergenceTol: float, entries=FIT_ALPHA_ENTRIES, lo: float = 0.0,
+                      hi: float = FIT_ALPHA_MAX) -> bool:
+    """hfm_estimate_alpha: one conditional maximisation of the free alpha entries from the alpha statistics of the pass whose statistics
+    vector is in model.estimators (EMList.alpha_stats after EM_runOneIterationForList); True when every free entry moved by less than
+    the tolerance."""
+    if model.estimators is None:
+        raise RuntimeError("HMM_estimateAlpha: no statistics (run EM_runOneIterationForList first)")
+    st = np.ascontiguousarray(model.estimators, dtype=np.float64)
+    a = np.ascontiguousarray(alphaStats, dtype=np.float64).ravel()
+    if a.size != 32 * model.numberOfRegions:
+        raise ValueError("HMM_estimateAlpha: alphaStats must hold 32 doubles per region")
+    mask = np.ascontiguousarray(alpha_free_mask(entries).ravel())
+    rc = N.lib().hfm_estimate_alpha(model._h, _dptr(a), _dptr(st), mask.ctypes.data_as(C.POINTER(C.c_uint8)), float(lo), float(hi),
+                                    float(convergenceTol))
+    if rc < 0:
+        raise ValueError("HMM_estimateAlpha: bad argument (bounds outside [0, 1), or a negative_binomial model)")
+    return bool(rc)
+
+
 def HMM_resetEstimators(model: HMM) -> None:
     """hmm.c:129-134."""
     model.estimators = None
@@ -767,9 +826,16 @@ def HMM_resetEstimators(model: HMM) -> None:
 
 def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergenceTol: float = 0.001,
                   outputDir: Optional[str] = None, writeParameterStatsPerIteration: bool = False,
-                  is_writer: bool = True) -> List[float]:
+                  is_writer: bool = True, fitAlpha: bool = False, fitAlphaEntries=FIT_ALPHA_ENTRIES, fitAlphaMax: float = FIT_ALPHA_MAX,
+                  fitAlphaEvery: int = 2) -> List[float]:
     """EM outer loop of hmm_flagger.c:285-488 (no --accelerate here: that loop is flagger_amd/csrc/hf_squarem.h, driven by the command line).  Returns the
-    log-likelihood of every E-pass (the rows of loglikelihood.tsv)."""
+    log-likelihood of every E-pass (the rows of loglikelihood.tsv).
+    fitAlpha (an EMList only): the k-th iteration, k = 1, 2, ..., is an alpha-iteration when k is a multiple of fitAlphaEvery — its pass is
+    followed by HMM_estimateAlpha alone; the others are ordinary iterations (HMM_estimateParameters alone).  The run has converged when
+    the latest iteration of each kind reported convergence."""
+    if fitAlpha:
+        return _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
+                                      is_writer, fitAlphaEntries, fitAlphaMax, int(fitAlphaEvery))
     lls: List[float] = []
     llf = None
     write = outputDir is not None and is_writer
@@ -802,4 +868,62 @@ def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergence
         llf.close()
         model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
         model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
+    return lls
+
+
+def _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration, is_writer,
+                           entries, alphaMax, every) -> List[float]:
+    if not hasattr(emList, "alpha_stats"):
+        raise TypeError("runHMMFlagger(fitAlpha=True): %s has no alpha statistics" % type(emList).__name__)
+    if every < 1:
+        raise ValueError("fitAlphaEvery must be at least 1")
+    if model.modelType == MODEL_NEGATIVE_BINOMIAL:
+        raise ValueError("fitAlpha: the negative_binomial emission has no alpha")
+    alpha_free_mask(entries)
+    emList.set_alpha_stats(True)
+    lls: List[float] = []
+    write = outputDir is not None and is_writer
+    llf = trf = None
+    if write:
+        llf = open(os.path.join(outputDir, "loglikelihood.tsv"), "w")
+        llf.write("#Iteration\tEffective_Iteration\tLoglikelihood\n")
+        trf = open(os.path.join(outputDir, "alpha_trace.tsv"), "w")
+        model.writeTransitionTsv(os.path.join(outputDir, "transition_initial.tsv"))
+        model.writeEmissionTsv(os.path.join(outputDir, "emission_initial.tsv"))
+    it = 1
+    conv_em, conv_alpha = False, False
+    try:
+        while it <= numberOfIterations and not (conv_em and conv_alpha):
+            EM_runOneIterationForList(emList, model)
+            lls.append(model.loglikelihood)
+            if llf:
+                llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
+            if it % every == 0:
+                st = emList.alpha_stats().sum(axis=0)
+                if trf:
+                    trf.write("\t".join(["%d" % (it - 1), "%.17g" % model.loglikelihood] + ["%.17g" % v for v in model.alpha.ravel()] +
+                                        ["%.17g" % v for v in st.ravel()]) + "\n")
+                conv_alpha = HMM_estimateAlpha(model, emList.alpha_stats(), convergenceTol, entries, 0.0, alphaMax)
+            else:
+                conv_em = HMM_estimateParameters(model, convergenceTol)
+            HMM_resetEstimators(model)
+            if write and writeParameterStatsPerIteration:
+                model.writeTransitionTsv(os.path.join(outputDir, f"transition_iteration_{it}.tsv"))
+                model.writeEmissionTsv(os.path.join(outputDir, f"emission_iteration_{it}.tsv"))
+            it += 1
+        EM_runOneIterationForList(emList, model)   # final inference
+        lls.append(model.loglikelihood)
+        if llf:
+            llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
+            model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
+            model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
+            with open(os.path.join(outputDir, "alpha_fitted.tsv"), "w") as f:
+                for row in model.alpha:
+                    f.write("\t".join("%.17g" % v for v in row) + "\n")
+    finally:
+        if llf:
+            llf.close()
+        if trf:
+            trf.close()
+        emList.set_alpha_stats(False)
     return lls

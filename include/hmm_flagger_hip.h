@@ -247,6 +247,38 @@ int hf_get_forward_backward(hf_ctx *ctx, int64_t first, int64_t n, double *f_hos
  * bad range, a mask of 0 or above 15. */
 int hf_get_interval_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last,
                               const uint8_t *state_mask, double *log_p_host);
+/* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
+ * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
+ * and t-1 as the pass sees them (8 bits), beta = beta_t:
+ *   xi_t[p][s] = f_{t-1}[p] * A_t[p][s] * b_t[s] / 1e-4      (f, b: hf_get_forward_backward; A_t: the row the pass multiplied by)
+ * and for a Gaussian state s (every state but Err under trunc_exp_gaussian), component c, a = alpha[p][s]:
+ *   v_c = var_c beta,  d_c = x - ((1 - a) mu_c + a x_prev) beta,  u_c = beta (x_prev - mu_c),
+ *   P_c = w_c / sqrt(2 PI v_c) exp(-d_c^2 / (2 v_c)), floored at 1e-40 as the emission does; g_c = P_c / sum_c P_c; phi_c = 0 if floored, else 1
+ *   G[r][p][s] = sum_t xi_t[p][s] sum_c g_c phi_c d_c u_c / v_c        H[r][p][s] = sum_t xi_t[p][s] sum_c g_c phi_c u_c^2 / v_c  (>= 0)
+ * over ALL pairs of every chunk whose window t lies in region r — the pair (0, 1) too, which the estimators of the statistics vector
+ * skip.  A chunk of one window contributes nothing; Err under trunc_exp_gaussian has G = H = 0.
+ * Summed over the regions, G is the exact derivative of the pass's log-likelihood (element 0 of the statistics vector) in alpha[p][s],
+ * PROVIDED the End column of `trans` is the same for all four states: then sum_ps xi_t = 1 and xi_t is the pair posterior.  The host model
+ * keeps it so (hf_model.cpp sets trans[r][s][End] = 1e-4 at creation and after every M-step, SQUAREM's prime model too).  alpha + G / H is
+ * the maximiser of the expected complete-data log-likelihood in that entry with everything else fixed (hfm_estimate_alpha).
+ *   hf_set_alpha_stats(ctx, 1)  full passes from now on may be asked for G and H.  The pass itself does not change — same launches, and
+ *                       everything it returns is bit-identical to the switch off; the statistics are computed by the first
+ *                       hf_get_alpha_stats after the pass (later calls on the same pass return the same bits).  HF_E_ARG on a context
+ *                       that has run negative_binomial passes (that emission has no alpha).
+ *   hf_alpha_stats_len  32 * n_regions
+ *   hf_get_alpha_stats  out[r][0][p][s] = G, out[r][1][p][s] = H.  Synchronous on the pass's stream.  HF_ALGO_SCAN, in HF_STATS_ROWS and
+ *                       HF_STATS_CHUNKS alike: the component terms are evaluated once per row of A of the pass, the pair counts xi come
+ *                       per window from the pair records of all windows — so the first call after an EM pass of the default algorithm
+ *                       re-runs the segment kernel once, as hf_get_posterior's does, also in several sub-passes — and the pair (0, 1)
+ *                       of a chunk is a pair like any other.  HF_ALGO_SEQ: terms and counts per window from the pass's f, b and
+ *                       emission rows (the on-device cross-check).  The first call of a context also builds the plan of the pairs
+ *                       (sorted by region; one download of the window records and positions, one upload of 12 bytes per window).
+ *                       The order of all additions is fixed by that plan: reproducible bit for bit.  HF_E_ARG: no full pass with the
+ *                       switch on yet, the last pass forward-only or negative_binomial.
+ * hf_batch_* and hf_multi_* do not produce them. */
+int hf_set_alpha_stats(hf_ctx *ctx, int on);
+int64_t hf_alpha_stats_len(const hf_ctx *ctx);
+int hf_get_alpha_stats(hf_ctx *ctx, double *out_host);
 /* Most-probable-path (Viterbi) decoding of every chunk (flagger_amd/csrc/hf_viterbi.h): with the parameters `p`, for a chunk of T windows
  *   s* = argmax over s_0..s_{T-1} of first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}],
  *   first[s] = trans[r_0][4][s] * e_0[s],  A_t = the row a pass builds (transition x emission),  end[s] = trans[r_{T-1}][s][4];

@@ -96,6 +96,20 @@ int hfm_warmup_pipeline(int device);
 int hfm_best_collapsed_comps(const uint16_t *cov, int64_t n_windows, const int32_t *region_coverages, int n_regions);
 int hfm_read_alpha_tsv(const char *path, double *alpha16);
 
+/* The alpha matrix of the model, row-major alpha[preState][state].  hfm_set_alpha refuses (-1, nothing changed) a value outside [0, 1):
+ * at 1 the component mean no longer depends on the state's own mean. */
+void hfm_get_alpha(const hfm_model *m, double *alpha16);
+int hfm_set_alpha(hfm_model *m, const double *alpha16);
+/* Conditional maximisation of the alpha matrix from one pass's alpha statistics (hf_get_alpha_stats: [r][0][p][s] = G, [r][1][p][s] = H)
+ * and its statistics vector `stats` (for the transition counts).  G, H and countMatrix[p][s] are summed over the regions in region
+ * order; every entry with free_mask16[p*4+s] != 0, H > 0 and kMinCountForUpdate < count (10 < count, the gate of hfm_estimate) becomes
+ *   alpha = clamp(alpha + G / H, lo, hi)
+ * the maximiser of the expected complete-data log-likelihood in that entry with everything else fixed.  The other entries keep their
+ * value.  Returns 1 when every free entry moved by less than `tol` (|new - old|, an entry that was not updated moved by 0), else 0;
+ * -1 on a bad argument (NULL, lo < 0, hi >= 1, lo > hi, negative_binomial: its emission has no alpha). */
+int hfm_estimate_alpha(hfm_model *m, const double *alpha_stats, const double *stats, const uint8_t *free_mask16, double lo, double hi,
+                       double tol);
+
 #ifdef __cplusplus
 }
 #endif
