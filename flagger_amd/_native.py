@@ -127,6 +127,7 @@ def lib() -> C.CDLL:
     sig("hf_batch_destroy", None, vp)
     sig("hf_batch_size", C.c_int, vp)
     sig("hf_batch_shared_models", C.c_int, vp)
+    sig("hf_batch_handoff", C.c_int64, vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), i64)
     sig("hf_batch_estep", C.c_int, vp, C.POINTER(hf_params), C.POINTER(i32), C.c_int, C.c_int, vp)
     sig("hf_batch_finish", C.c_int, vp, pd, C.POINTER(i32), vp)
     sig("hf_batch_get_labels", C.c_int, vp, C.c_int, C.POINTER(C.c_int8))

@@ -89,6 +89,19 @@ void hf_batch_destroy(hf_batch* b) {
 int hf_batch_size(const hf_batch* b) { return b ? (int) b->m.size() : 0; }
 int hf_batch_shared_models(const hf_batch* b) { return b ? b->last_batched : 0; }
 
+// diagnostics (tests/test_batch_gpu.py): model `model`'s hand-off epoch and the flag words its segments have published so far
+int64_t hf_batch_handoff(hf_batch* b, int model, uint32_t* epoch, uint32_t* ready_host, int64_t n) {
+    if (!b || model < 0 || model >= (int) b->m.size() || n < 0 || (n > 0 && !ready_host)) return set_err(HF_E_ARG, "hf_batch_handoff: bad argument");
+    Pass& s = *b->m[(size_t) model];
+    const Track& tr = b->ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    HIPCHK(hipStreamSynchronize(s.last_stream));
+    if (epoch) *epoch = s.seg_epoch;
+    const int64_t k = std::min<int64_t>(n, tr.nseg);
+    if (k > 0 && s.d_seg_ready) HIPCHK(hipMemcpy(ready_host, s.d_seg_ready, (size_t) k * 4, hipMemcpyDeviceToHost));
+    return tr.nseg;
+}
+
 static int batch_models_ok(const hf_batch* b, const int32_t* models, int n_active, const char* who) {
     if (!b || (n_active > 0 && !models) || n_active < 0) return set_err(HF_E_ARG, std::string(who) + ": bad argument");
     for (int i = 0; i < n_active; i++) {

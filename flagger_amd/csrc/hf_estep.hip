@@ -1932,6 +1932,8 @@ int hf_get_forward_backward(hf_ctx* ctx, int64_t first, int64_t n, double* f_hos
 
 static int pass_posterior(Pass& ps, int64_t first, int64_t n, double* post_host) {
     if (!post_host) return set_err(HF_E_ARG, "hf_get_posterior: bad argument");
+    // (before the buffers below are sized by n: a negative n would throw out of the C ABI)
+    if (first < 0 || n < 0 || first + n > ps.tr->N) return set_err(HF_E_ARG, "hf_get_posterior: bad range");
     std::vector<double> f((size_t) n * 4), b((size_t) n * 4), sc((size_t) n);
     int rc = pass_forward_backward(ps, first, n, f.data(), b.data(), sc.data());
     if (rc) return rc;

@@ -710,6 +710,18 @@ class EMBatch:
         """Models of the last pass whose segment kernel ran in the shared launch (k_seg_fb_batch); the others ran their own pass."""
         return int(self._L.hf_batch_shared_models(self._b))
 
+    def handoff(self, m: int):
+        """(epoch, flags uint32[segments]) of model m: its hand-off epoch and the flag word of every chunk segment (hf_batch_handoff)."""
+        epoch = C.c_uint32(0)
+        n = int(self._L.hf_batch_handoff(self._b, int(m), C.byref(epoch), None, 0))
+        if n < 0:
+            raise N.HFError(n, "hf_batch_handoff")
+        flags = np.zeros(n, dtype=np.uint32)
+        n = int(self._L.hf_batch_handoff(self._b, int(m), C.byref(epoch), flags.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        if n < 0:
+            raise N.HFError(n, "hf_batch_handoff")
+        return int(epoch.value), flags
+
     def capacity(self) -> int:
         """hf_batch_capacity of the underlying context: models whose pass state fits the device's free memory."""
         return int(self._L.hf_batch_capacity(self.em._h))

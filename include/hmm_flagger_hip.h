@@ -342,6 +342,11 @@ int hf_batch_create(hf_ctx *ctx, int n_models, hf_batch **out);
 void hf_batch_destroy(hf_batch *b);
 int hf_batch_size(const hf_batch *b);
 int hf_batch_shared_models(const hf_batch *b);   /* models of the last hf_batch_estep whose segment kernel ran in the shared launch */
+/* Diagnostics (the test suite): *epoch = the hand-off epoch of model `model`'s pass (advanced once per launch of a segment kernel that
+ * the model takes part in); ready_host[0 .. min(n, segments)) = the flag word of every chunk segment, in segment order: the epoch of
+ * the last one-launch pass in which the segment published its product (segments of one-segment chunks publish nothing: 0).  Waits for
+ * the model's last pass.  Returns the number of segments of the context, or a negative HF_E_*. */
+int64_t hf_batch_handoff(hf_batch *b, int model, uint32_t *epoch, uint32_t *ready_host, int64_t n);
 int hf_batch_estep(hf_batch *b, const hf_params *p, const int32_t *models, int n_active, int mode, void *stream);
 int hf_batch_finish(hf_batch *b, double *stats_host, int32_t *status, void *stream);
 int hf_batch_get_labels(hf_batch *b, int model, int8_t *labels_host);

@@ -94,3 +94,5 @@ def test_batch_abi_refuses_without_a_context():
     status = (C.c_int32 * 1)()
     assert L.hf_batch_finish(None, st, status, None) == N.HF_E_ARG
     assert L.hf_batch_get_labels(None, 0, None) == N.HF_E_ARG
+    assert L.hf_batch_get_posterior(None, 0, 0, 0, None) == N.HF_E_ARG
+    assert L.hf_batch_handoff(None, 0, None, None, 0) == N.HF_E_ARG
