@@ -19,6 +19,7 @@ HF_STATS_CHUNKS, HF_STATS_ROWS = 0, 1
 HF_EXCHANGE_CHUNKS, HF_EXCHANGE_RANKS = 0, 1
 HF_TRANSPORT_RCCL, HF_TRANSPORT_LOOPBACK = 0, 1
 HF_PROF_PASS = 0x80000000
+HF_COUNT_WINDOWS, HF_COUNT_BASES = 0, 1
 HF_OK, HF_E_ARG, HF_E_HIP, HF_E_SCALE, HF_E_NAN, HF_E_REGION, HF_E_NOGPU, HF_E_RETRY = 0, -1, -2, -3, -4, -5, -6, -7
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libhmmflagger_hip.so")
@@ -111,6 +112,8 @@ def lib() -> C.CDLL:
     sig("hf_get_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_forward_backward", C.c_int, vp, i64, i64, pd, pd, pd)
     sig("hf_get_interval_log_probs", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), pd)
+    sig("hf_get_count_moments", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+        C.c_int, pd, pd)
     sig("hf_set_alpha_stats", C.c_int, vp, C.c_int)
     sig("hf_alpha_stats_len", i64, vp)
     sig("hf_get_alpha_stats", C.c_int, vp, pd)

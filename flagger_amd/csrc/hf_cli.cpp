@@ -71,6 +71,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"fitAlphaEntries", required_argument, nullptr, 1012},      // the free entries, pre,state pairs separated by ':'
     {"fitAlphaMax", required_argument, nullptr, 1013},          // their upper bound [0.8]
     {"fitAlphaEvery", required_argument, nullptr, 1014},        // every P-th iteration is an alpha-iteration [2]
+    {"exactTotals", no_argument, nullptr, 1015},                // exact mean and SD of the label totals (hf_get_count_moments)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -131,7 +132,11 @@ static void usage(const char* program) {
             "         --fitAlphaEntries LIST       the free entries as pre,state pairs separated by ':' (states 0 Err, 1 Dup, 2 Hap, 3 Col)\n"
             "                                      [0,0:0,2:1,1:1,2:2,0:2,1:2,2:2,3:3,2:3,3]\n"
             "         --fitAlphaMax X              upper bound of a fitted entry, 0 <= X < 1 (the lower bound is 0) [0.8]\n"
-            "         --fitAlphaEvery P            iterations P, 2P, ... are alpha-iterations [2]\n");
+            "         --fitAlphaEvery P            iterations P, 2P, ... are alpha-iterations [2]\n"
+            "         --exactTotals                after the final inference, write label_totals_exact.tsv: for the whole track, every contig and\n"
+            "                                      every annotation region, and for Err, Dup, Hap, Col and Err+Dup+Col, the windows of the scope,\n"
+            "                                      the bases of the final labels, and the exact posterior mean and standard deviation of the bases\n"
+            "                                      (what --uncertaintySamples estimates from samples); one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -547,6 +552,78 @@ static int write_interval_outputs(hf_ctx* ctx, const hfio_table* tab, const int8
     return HF_OK;
 }
 
+// --exactTotals: exact posterior mean and standard deviation of the label totals (hf_get_count_moments, HF_COUNT_BASES) under the model
+// of the last full pass.
+//   label_totals_exact.tsv   one row per scope and label set.  Scopes: "all", every contig by name (order of first appearance in the
+//                            chunk list; a contig's chunks are independent chains, so its mean and variance are the sums over its
+//                            maximal runs of consecutive chunks, in list order), region_<r> for every annotation region (the whole
+//                            track with the region filter r).  Label sets: Err, Dup, Hap, Col, Err+Dup+Col.  Columns: windows (of
+//                            the scope), bases_final_labels (bases whose final label lies in the set), bases_expected, bases_sd.
+static int write_exact_totals(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<int64_t> wbases;
+    std::vector<int32_t> wreg;
+    window_bases(w, C, wbases, &wreg);
+    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
+    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
+    // a scope: its name, its window ranges [a, b), its region filter
+    struct Scope { std::string name; std::vector<std::pair<int64_t, int64_t>> ranges; int region; };
+    std::vector<Scope> scopes;
+    scopes.push_back(Scope{"all", {}, -1});
+    if (N > 0) scopes.back().ranges.push_back({0, N});
+    std::map<std::string, size_t> ctgScope;
+    for (int c = 0; c < C; c++) {
+        const int64_t a = w.chunk_off[c], b = w.chunk_off[c + 1];
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        auto it = ctgScope.find(ctg);
+        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}, -1}); }
+        if (a == b) continue;
+        auto& rg = scopes[it->second].ranges;
+        if (!rg.empty() && rg.back().second == a) rg.back().second = b;
+        else rg.push_back({a, b});
+    }
+    for (int r = 0; r < R; r++) {
+        scopes.push_back(Scope{"region_" + std::to_string(r), {}, r});
+        if (N > 0) scopes.back().ranges.push_back({0, N});
+    }
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> mask;
+    std::vector<int32_t> region;
+    for (const Scope& sc : scopes)
+        for (const auto& rg : sc.ranges)
+            for (int k = 0; k < 5; k++) { first.push_back(rg.first); last.push_back(rg.second - 1); mask.push_back(kSets[k]); region.push_back(sc.region); }
+    std::vector<double> mean(first.size()), var(first.size());
+    const int rc = hf_get_count_moments(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), region.data(), HF_COUNT_BASES,
+                                        mean.data(), var.data());
+    if (rc != HF_OK) return rc;
+    const std::string tp = dir + "/label_totals_exact.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\tlabel_set\twindows\tbases_final_labels\tbases_expected\tbases_sd\n");
+    size_t j = 0;
+    for (const Scope& sc : scopes) {
+        int64_t windows = 0, finalBases[5] = {0, 0, 0, 0, 0};
+        double m[5] = {0, 0, 0, 0, 0}, v[5] = {0, 0, 0, 0, 0};       // sums over the ranges, list order
+        for (const auto& rg : sc.ranges) {
+            for (int64_t t = rg.first; t < rg.second; t++) {
+                if (sc.region >= 0 && wreg[(size_t) t] != sc.region) continue;
+                windows++;
+                const int l = finalLabels[t];
+                if (l < 0 || l > 3) continue;
+                for (int k = 0; k < 5; k++) if ((kSets[k] >> l) & 1) finalBases[k] += wbases[(size_t) t];
+            }
+            for (int k = 0; k < 5; k++, j++) { m[k] += mean[j]; v[k] += var[j]; }
+        }
+        for (int k = 0; k < 5; k++)
+            fprintf(f, "%s\t%s\t%ld\t%ld\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (long) windows, (long) finalBases[k], m[k], std::sqrt(v[k]));
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
     FILE* f = fopen(listPath, "r");
@@ -587,7 +664,7 @@ int main(int argc, char* argv[]) {
     bool viterbi = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
-    bool runConfidence = false;
+    bool runConfidence = false, exactTotals = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -601,6 +678,19 @@ int main(int argc, char* argv[]) {
     int32_t minLenPerState[4] = {0, 0, 0, 0};
     const char* program = strrchr(argv[0], '/');
     program = program ? program + 1 : argv[0];
+    // "--e" and "--ex" were unique prefixes of --exchange until --exactTotals came: they keep their meaning (the rule of long_options above:
+    // a prefix that resolved once resolves to the same option in every later build)
+    std::vector<std::string> rewritten;
+    rewritten.reserve((size_t) argc);
+    for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; i++)
+        for (const char* pre : {"--ex", "--e"}) {
+            const size_t n = strlen(pre);
+            if (strncmp(argv[i], pre, n) == 0 && (argv[i][n] == '\0' || argv[i][n] == '=')) {
+                rewritten.push_back(std::string("--exchange") + (argv[i] + n));
+                argv[i] = rewritten.back().data();
+                break;
+            }
+        }
     int c;
     while (~(c = getopt_long(argc, argv, "i:x:f:en:t:m:q:C:W:c:@:p:A:a:wkPo:v:l:D:BN:M:s", long_options, nullptr))) {
         switch (c) {
@@ -676,6 +766,7 @@ int main(int argc, char* argv[]) {
                 break;
             }
             case 1009: runConfidence = true; break;
+            case 1015: exactTotals = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -738,6 +829,10 @@ int main(int argc, char* argv[]) {
     if ((runConfidence || regionProbsPath) && (nGpus > 1 || sweepListPath)) {
         fprintf(stderr, "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts(),
                 runConfidence ? "--runConfidence" : "--regionProbs");
+        return EXIT_FAILURE;
+    }
+    if (exactTotals && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --exactTotals runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
     // --fitAlpha: its own arguments and the refused combinations, before the input is read
@@ -1086,6 +1181,13 @@ int main(int argc, char* argv[]) {
         if ((rc = write_interval_outputs(run.ctx, tab, finalLabels, runConfidence, regionProbsPath ? &regions : nullptr, labelNames, dir)) != HF_OK)
             return die(rc);
         fprintf(stderr, "[%s] [Final Inference] exact interval probabilities written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --exactTotals: likewise
+    if (exactTotals) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --exactTotals needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_exact_totals(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] label_totals_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

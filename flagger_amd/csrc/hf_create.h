@@ -905,6 +905,7 @@ extern "C" int hf_create(const hf_windows* w, int n_regions, int max_comps, int 
     tr.meta = *w;
     tr.meta.chunk_off = nullptr; tr.meta.cov = tr.meta.mapq = tr.meta.clip = nullptr;
     tr.meta.annot = nullptr; tr.meta.chunk_s = tr.meta.chunk_e = tr.meta.chunk_ctg_len = nullptr;
+    tr.h_cs.assign(w->chunk_s, w->chunk_s + w->n_chunks); tr.h_ce.assign(w->chunk_e, w->chunk_e + w->n_chunks);
     for (int c = 0; c < w->n_chunks; c++) {
         const int64_t T = w->chunk_off[c + 1] - w->chunk_off[c];
         if (T < 0 || T > INT32_MAX) return set_err(HF_E_ARG, "hf_create: bad chunk_off");

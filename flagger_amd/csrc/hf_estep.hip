@@ -293,6 +293,7 @@ struct Track {
     uint64_t* d_regmask = nullptr; // [C] bit r set if region r occurs in the chunk
     unsigned* d_setup_flags = nullptr;   // k_setup's flag word (a region index out of range): read once, at the end of hf_create
     std::vector<int64_t> h_off; std::vector<int32_t> h_tile0;   // host copies for hf_get_forward_backward
+    std::vector<int32_t> h_cs, h_ce;                            // Chunk.s / Chunk.e (a window's length in bases: hf_get_count_moments)
     // scan algorithm: tile table (per-chunk statistics, HF_ALGO_SEQ)
     TileDesc* d_tile_desc = nullptr;
     int ntiles = 0; int32_t* d_chunk_tile0 = nullptr;
@@ -457,6 +458,12 @@ struct IntervalBufs {
     void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
 };
 
+// exact count moments (hf_moments.h): one device buffer of their own, grown on demand (pieces, parts, piece triples, piece means, results)
+struct MomentBufs {
+    char* d_buf = nullptr; size_t cap = 0;
+    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -472,7 +479,7 @@ struct AlphaStats {
 };
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
-// the alpha statistics' plan and buffers
+// the alpha statistics' plan and buffers, the count moments' buffer
 struct hf_ctx {
     Track tr;
     Pass pass;
@@ -480,6 +487,7 @@ struct hf_ctx {
     Sampler smp;
     IntervalBufs iv;
     AlphaStats al;
+    MomentBufs mo;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1017,6 +1025,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->smp.release();
     ctx->iv.release();
     ctx->al.release();
+    ctx->mo.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2571,5 +2580,119 @@ int hf_get_alpha_stats(hf_ctx* ctx, double* out_host) {
     }
     al.cached = true;
     std::memcpy(out_host, al.last.data(), len * 8);
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact mean and variance of label totals (hf_moments.h) over the last full pass: the host cuts every job into chunk-local parts and every
+// part's interior windows into pieces as the interval getter does, k_mo_piece multiplies the pieces' jets, k_mo_chain carries every part's
+// vectors through them, the host sums the parts of a job in chunk order.  Last in the file, so that no pass kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_moments.h"
+
+// pieces and parts per device batch (a piece's triple is 384 bytes: 96 MB of them at most; a job is never split across batches, and a
+// batch holds at least one job)
+#define HF_MO_BATCH_PIECES (1 << 18)
+#define HF_MO_BATCH_PARTS (1 << 20)
+
+int hf_get_count_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, const int32_t* region,
+                         int unit, double* mean_host, double* var_host) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_get_count_moments: bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    if (n < 0) return set_err(HF_E_ARG, "hf_get_count_moments: n < 0");
+    if (unit != HF_COUNT_WINDOWS && unit != HF_COUNT_BASES) return set_err(HF_E_ARG, "hf_get_count_moments: unknown unit");
+    if (n > 0 && (!first || !last || !state_mask || !mean_host || !var_host)) return set_err(HF_E_ARG, "hf_get_count_moments: NULL array");
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, "hf_get_count_moments: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    for (int64_t i = 0; i < n; i++) {
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
+            return set_err(HF_E_ARG, "hf_get_count_moments: bad range (job " + std::to_string(i) + ")");
+        if (state_mask[i] < 1 || state_mask[i] > 15)
+            return set_err(HF_E_ARG, "hf_get_count_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
+        if (region && (region[i] < -1 || region[i] >= tr.R))
+            return set_err(HF_E_ARG, "hf_get_count_moments: region must be -1..n_regions-1 (job " + std::to_string(i) + ")");
+    }
+    HIPCHK(hipSetDevice(tr.device));
+    if (n == 0) return HF_OK;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_count_moments: the last pass kept no pair records");
+    if (!seq) {
+        const int rc = pass_all_records(ps);
+        if (rc) return rc;
+    }
+    hipStream_t st = ps.last_stream;
+    const int W = unit == HF_COUNT_BASES ? tr.meta.window_len : 0;
+    if (unit == HF_COUNT_BASES && W < 1) return set_err(HF_E_ARG, "hf_get_count_moments: the context has no window length");
+    MomentBufs& mb = ctx->mo;
+    MoFB fb{};
+    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
+    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
+    std::vector<MoPiece> pieces;
+    std::vector<MoPart> parts;
+    std::vector<int64_t> job_p0;
+    std::vector<double> val;
+    for (int64_t j0 = 0; j0 < n;) {
+        // the jobs of this batch, cut into parts and pieces
+        pieces.clear(); parts.clear(); job_p0.clear();
+        int64_t j1 = j0;
+        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
+            job_p0.push_back((int64_t) parts.size());
+            const int mask = state_mask[j1], reg = region ? region[j1] : -1;
+            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
+            for (int64_t a = first[j1]; a <= last[j1]; c++) {
+                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
+                const int64_t o = tr.h_off[(size_t) c], b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
+                const int cs = tr.h_cs[(size_t) c], ce = tr.h_ce[(size_t) c];
+                MoPart pt{a, b, (int) pieces.size(), 0, mask, reg, c, (int) (a - o), cs, ce};
+                for (int64_t t = a + 1; t <= b;) {
+                    const int64_t e = std::min<int64_t>(b, (t / HF_MO_PIECE + 1) * HF_MO_PIECE - 1);
+                    pieces.push_back(MoPiece{t, (int) (e - t + 1), mask, reg, c, (int) (t - o), cs, ce});
+                    t = e + 1;
+                }
+                pt.p1 = (int) pieces.size();
+                parts.push_back(pt);
+                a = b + 1;
+            }
+            j1++;
+        }
+        job_p0.push_back((int64_t) parts.size());
+        const size_t np = pieces.size(), nq = parts.size();
+        const size_t o_parts = Slab::granule(np * sizeof(MoPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(MoPart));
+        const size_t o_mean = o_pm + Slab::granule(np * 48 * 8), o_out = o_mean + Slab::granule(np * 8), bytes = o_out + Slab::granule(nq * 16);
+        if (bytes > mb.cap) {
+            mb.release();
+            if (hipMalloc((void**) &mb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); mb.d_buf = nullptr;
+                return set_err(HF_E_HIP, "hf_get_count_moments: out of device memory"); }
+            mb.cap = bytes;
+        }
+        MoPiece* d_pieces = reinterpret_cast<MoPiece*>(mb.d_buf);
+        MoPart* d_parts = reinterpret_cast<MoPart*>(mb.d_buf + o_parts);
+        double* d_pm = reinterpret_cast<double*>(mb.d_buf + o_pm);
+        double* d_mean = reinterpret_cast<double*>(mb.d_buf + o_mean);
+        double* d_out = reinterpret_cast<double*>(mb.d_buf + o_out);
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(MoPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(MoPart), hipMemcpyHostToDevice, st));
+        if (seq) {
+            if (np) hipLaunchKernelGGL(k_mo_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, W, (const int32_t*) nullptr,
+                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_pm, d_mean);
+            hipLaunchKernelGGL(k_mo_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, W, tr.d_rec, d_pm, d_mean, fb, d_out);
+        } else {
+            if (np) hipLaunchKernelGGL(k_mo_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, W, tr.d_arow, ps.d_lutA, tr.d_rec,
+                                       (const double*) nullptr, (const DevParams*) nullptr, fb, d_pm, d_mean);
+            hipLaunchKernelGGL(k_mo_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, W, tr.d_rec, d_pm, d_mean, fb, d_out);
+        }
+        HIPCHK(hipGetLastError());
+        val.resize(nq * 2);
+        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
+            double m = 0.0, v = 0.0;
+            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) { m += val[(size_t) k * 2]; v += val[(size_t) k * 2 + 1]; }
+            mean_host[j] = m; var_host[j] = v;
+        }
+        j0 = j1;
+    }
     return HF_OK;
 }

@@ -610,6 +610,32 @@ class EMList:
                                                   _dptr(out)), "hf_get_interval_log_probs")
         return out
 
+    def count_moments(self, first, last, mask, region=None, unit="windows"):
+        """Exact posterior mean and variance of label totals under the model of the last full pass (hf_get_count_moments): for every
+        job i, of N = sum over the windows t of first[i]..last[i] (inclusive) of w_t * [the state of t is in the set mask[i]], with
+        w_t = 1 (unit "windows") or the window's length in bases (unit "bases"), and 0 where region[i] >= 0 differs from the window's
+        annotation region index (region None or -1: every window) -> (mean float64[n], var float64[n]).  Scalars broadcast."""
+        units = {"windows": N.HF_COUNT_WINDOWS, "bases": N.HF_COUNT_BASES}
+        if unit not in units:
+            raise ValueError("count_moments: unit must be 'windows' or 'bases'")
+        f, l, m, r = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64),
+                                         np.asarray(-1 if region is None else region, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("count_moments: a state mask must be 1..15")
+        if r.size and (r.min() < -2 ** 31 or r.max() >= 2 ** 31):
+            raise ValueError("count_moments: a region must be -1 or a region index")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        r = np.ascontiguousarray(r.ravel(), np.int32)
+        mean = np.empty(f.size, dtype=np.float64)
+        var = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_count_moments(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             None if region is None else r.ctypes.data_as(C.POINTER(C.c_int32)), units[unit],
+                                             _dptr(mean), _dptr(var)), "hf_get_count_moments")
+        return mean, var
+
     def set_alpha_stats(self, on: bool = True) -> None:
         """hf_set_alpha_stats: full passes from now on can be asked for the alpha statistics (alpha_stats)."""
         N.check(self._L.hf_set_alpha_stats(self._h, int(bool(on))), "hf_set_alpha_stats")
@@ -674,6 +700,15 @@ def EM_getIntervalLogProbsForList(emList, first, last, mask) -> np.ndarray:
     if not hasattr(emList, "interval_log_probs"):
         raise TypeError("EM_getIntervalLogProbsForList: %s has no interval getter" % type(emList).__name__)
     return emList.interval_log_probs(first, last, mask)
+
+
+def EM_getCountMomentsForList(emList, first, last, mask, region=None, unit="windows"):
+    """Exact posterior (mean, variance) of the number of windows (or bases) of first[i]..last[i] whose state lies in mask[i], optionally
+    only those of annotation region region[i], under the model of the last full pass, per job (no counterpart in the reference):
+    (float64[n], float64[n]).  `emList`: an EMList."""
+    if not hasattr(emList, "count_moments"):
+        raise TypeError("EM_getCountMomentsForList: %s has no count-moments getter" % type(emList).__name__)
+    return emList.count_moments(first, last, mask, region, unit)
 
 
 class EMBatch:

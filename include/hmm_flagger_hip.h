@@ -247,6 +247,26 @@ int hf_get_forward_backward(hf_ctx *ctx, int64_t first, int64_t n, double *f_hos
  * bad range, a mask of 0 or above 15. */
 int hf_get_interval_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last,
                               const uint8_t *state_mask, double *log_p_host);
+/* Exact mean and variance of label totals (flagger_amd/csrc/hf_moments.h), under the model of the last HF_MODE_FULL pass like hf_get_posterior.
+ * Job i is the window range first[i]..last[i] and the state set S = state_mask[i] as for hf_get_interval_log_probs, a region filter
+ * region[i] (-1: every window, else only the windows whose annotation region index equals it; region == NULL: -1 for every job) and the
+ * unit of the call: HF_COUNT_WINDOWS gives window t the weight w_t = 1, HF_COUNT_BASES its length in bases (window k of a chunk:
+ * min(chunk_s + (k+1) window_len - 1, chunk_e) - (chunk_s + k window_len) + 1); w_t = 0 where the filter rejects the window.  With
+ * N = sum_{t in range} w_t 1[s_t in S]:
+ *   mean[i] = E[N | data] = sum_t w_t gamma_t(S),  gamma_t(S) = sum_{s in S} posterior_t[s] (hf_get_posterior's values; a fixed summation
+ *             order, not a by-product of the variance)
+ *   var[i]  = Var[N | data], exactly (all pairwise covariances of the chain), from the second-order jet of the chain's product with the
+ *             weights centred by gamma_t; never negative, never NaN (a negative rounding residue is 0.0)
+ * Chunks are independent chains: both values are the sums, in chunk order, of the values of the job's chunk-local parts.  Mask 15 gives
+ * var exactly 0.0 and mean exactly the sum of the job's weights; a job whose filter leaves no window gives (0.0, 0.0).  A job's two values
+ * depend only on (first, last, mask, region, unit) and the pass, bitwise: not on the other jobs of the call, their order or their number.
+ * Synchronous on the pass's stream; the first call after an EM pass of the default algorithm re-runs the segment kernel once, as
+ * hf_get_posterior's does.  Buffers of its own: nothing an EM pass, hf_viterbi, hf_sample_paths, hf_get_interval_log_probs or
+ * hf_get_alpha_stats reads is written.  n = 0 is a successful no-op.  HF_E_ARG: the cases of hf_get_interval_log_probs, a region outside
+ * -1..n_regions-1, an unknown unit.  hf_batch_* and hf_multi_* have no counterpart. */
+enum { HF_COUNT_WINDOWS = 0, HF_COUNT_BASES = 1 };
+int hf_get_count_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
+                         const int32_t *region /* NULL: all -1 */, int unit, double *mean_host, double *var_host);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
