@@ -72,6 +72,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"fitAlphaMax", required_argument, nullptr, 1013},          // their upper bound [0.8]
     {"fitAlphaEvery", required_argument, nullptr, 1014},        // every P-th iteration is an alpha-iteration [2]
     {"exactTotals", no_argument, nullptr, 1015},                // exact mean and SD of the label totals (hf_get_count_moments)
+    {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -136,7 +137,12 @@ static void usage(const char* program) {
             "         --exactTotals                after the final inference, write label_totals_exact.tsv: for the whole track, every contig and\n"
             "                                      every annotation region, and for Err, Dup, Hap, Col and Err+Dup+Col, the windows of the scope,\n"
             "                                      the bases of the final labels, and the exact posterior mean and standard deviation of the bases\n"
-            "                                      (what --uncertaintySamples estimates from samples); one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      (what --uncertaintySamples estimates from samples); one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --numBlocks                  after the final inference, write label_blocks_exact.tsv: for the whole track and every contig,\n"
+            "                                      and for Err, Dup, Hap, Col and Err+Dup+Col, the number of blocks (maximal runs of windows, merged\n"
+            "                                      across the chunks of a contig as the final BED merges them) in the final labels, and the exact\n"
+            "                                      posterior mean and standard deviation of that number; no annotation-region scope (a block does\n"
+            "                                      not belong to one region); one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -624,6 +630,79 @@ static int write_exact_totals(hf_ctx* ctx, const hfio_table* tab, const int8_t* 
     return HF_OK;
 }
 
+// --numBlocks: exact posterior mean and standard deviation of the block counts (hf_get_run_moments) under the model of the last full pass.
+//   label_blocks_exact.tsv   one row per scope and label set.  Scopes: "all" and every contig by name (order of first appearance in the
+//                            chunk list; its mean and variance are the sums over its maximal runs of consecutive chunks, in list
+//                            order).  No annotation-region scope: a block does not belong to one region.  Label sets: Err, Dup, Hap,
+//                            Col, Err+Dup+Col.  Columns: blocks_final_labels (the runs of the set in the final labels), blocks_expected,
+//                            blocks_sd.  A run continues from chunk c-1 into chunk c where the two are adjacent in the chunk list and
+//                            carry the same contig name: the rule hfio_write_final_bed merges by, so that for a single label and the
+//                            default --minimumLengths blocks_final_labels of "all" is the number of the label's rows in the final BED.
+static int write_exact_blocks(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
+    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
+    // a scope: its name and its chunk ranges [c0, c1)
+    struct Scope { std::string name; std::vector<std::pair<int, int>> ranges; };
+    std::vector<Scope> scopes;
+    scopes.push_back(Scope{"all", {}});
+    if (C > 0) scopes.back().ranges.push_back({0, C});
+    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
+    std::map<std::string, size_t> ctgScope;
+    for (int c = 0; c < C; c++) {
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
+        auto it = ctgScope.find(ctg);
+        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
+        auto& rg = scopes[it->second].ranges;
+        if (!rg.empty() && rg.back().second == c) rg.back().second = c + 1;
+        else rg.push_back({c, c + 1});
+    }
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> mask;
+    for (const Scope& sc : scopes)
+        for (const auto& rg : sc.ranges) {
+            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
+            for (int k = 0; k < 5; k++) { first.push_back(w.chunk_off[rg.first]); last.push_back(w.chunk_off[rg.second] - 1); mask.push_back(kSets[k]); }
+        }
+    std::vector<double> mean(first.size()), var(first.size());
+    const int rc = hf_get_run_moments(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), joined.data(), mean.data(), var.data());
+    if (rc != HF_OK) return rc;
+    (void) N;
+    const std::string tp = dir + "/label_blocks_exact.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\tlabel_set\tblocks_final_labels\tblocks_expected\tblocks_sd\n");
+    size_t j = 0;
+    for (const Scope& sc : scopes) {
+        int64_t finalBlocks[5] = {0, 0, 0, 0, 0};
+        double m[5] = {0, 0, 0, 0, 0}, v[5] = {0, 0, 0, 0, 0};       // sums over the ranges, list order
+        for (const auto& rg : sc.ranges) {
+            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
+            bool in[5] = {false, false, false, false, false};        // the window before lies in the set and continues into this one
+            for (int c = rg.first; c < rg.second; c++) {
+                if (c == rg.first || !joined[(size_t) c]) for (int k = 0; k < 5; k++) in[k] = false;
+                for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+                    const int l = finalLabels[t];
+                    for (int k = 0; k < 5; k++) {
+                        const bool now = l >= 0 && l <= 3 && ((kSets[k] >> l) & 1);
+                        if (now && !in[k]) finalBlocks[k]++;
+                        in[k] = now;
+                    }
+                }
+            }
+            for (int k = 0; k < 5; k++, j++) { m[k] += mean[j]; v[k] += var[j]; }
+        }
+        for (int k = 0; k < 5; k++)
+            fprintf(f, "%s\t%s\t%ld\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (long) finalBlocks[k], m[k], std::sqrt(v[k]));
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
     FILE* f = fopen(listPath, "r");
@@ -664,7 +743,7 @@ int main(int argc, char* argv[]) {
     bool viterbi = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
-    bool runConfidence = false, exactTotals = false;
+    bool runConfidence = false, exactTotals = false, numBlocks = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -767,6 +846,7 @@ int main(int argc, char* argv[]) {
             }
             case 1009: runConfidence = true; break;
             case 1015: exactTotals = true; break;
+            case 1016: numBlocks = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -833,6 +913,10 @@ int main(int argc, char* argv[]) {
     }
     if (exactTotals && (nGpus > 1 || sweepListPath)) {
         fprintf(stderr, "[%s] Error: --exactTotals runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (numBlocks && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --numBlocks runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
     // --fitAlpha: its own arguments and the refused combinations, before the input is read
@@ -1188,6 +1272,13 @@ int main(int argc, char* argv[]) {
         const double t0 = real_time();
         if ((rc = write_exact_totals(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] label_totals_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --numBlocks: likewise
+    if (numBlocks) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --numBlocks needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_exact_blocks(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] label_blocks_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

@@ -464,6 +464,12 @@ struct MomentBufs {
     void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
 };
 
+// exact run moments (hf_runs.h): one device buffer of their own, grown on demand (pieces, parts, piece triples, piece sums of xi, results)
+struct RunBufs {
+    char* d_buf = nullptr; size_t cap = 0;
+    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -479,7 +485,7 @@ struct AlphaStats {
 };
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
-// the alpha statistics' plan and buffers, the count moments' buffer
+// the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer
 struct hf_ctx {
     Track tr;
     Pass pass;
@@ -488,6 +494,7 @@ struct hf_ctx {
     IntervalBufs iv;
     AlphaStats al;
     MomentBufs mo;
+    RunBufs rn;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1026,6 +1033,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->iv.release();
     ctx->al.release();
     ctx->mo.release();
+    ctx->rn.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2691,6 +2699,136 @@ int hf_get_count_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int
             double m = 0.0, v = 0.0;
             for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) { m += val[(size_t) k * 2]; v += val[(size_t) k * 2 + 1]; }
             mean_host[j] = m; var_host[j] = v;
+        }
+        j0 = j1;
+    }
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact mean and variance of block counts (hf_runs.h) over the last full pass: the host cuts every job into chunk-local parts and every
+// part's interior windows into pieces as the count moments do, k_run_piece multiplies the pieces' jets, k_run_chain carries every part's
+// vectors through them and writes the part's seven numbers, the host stitches the parts of a job left to right (the joins between
+// chunks: include/hmm_flagger_hip.h).  Last in the file, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_runs.h"
+
+int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, const uint8_t* joined,
+                       double* mean_host, double* var_host) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_get_run_moments: bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    if (n < 0) return set_err(HF_E_ARG, "hf_get_run_moments: n < 0");
+    if (n > 0 && (!first || !last || !state_mask || !mean_host || !var_host)) return set_err(HF_E_ARG, "hf_get_run_moments: NULL array");
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, "hf_get_run_moments: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    if (joined && tr.C > 0 && joined[0]) return set_err(HF_E_ARG, "hf_get_run_moments: joined[0] must be 0 (the first chunk continues nothing)");
+    for (int64_t i = 0; i < n; i++) {
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
+            return set_err(HF_E_ARG, "hf_get_run_moments: bad range (job " + std::to_string(i) + ")");
+        if (state_mask[i] < 1 || state_mask[i] > 15)
+            return set_err(HF_E_ARG, "hf_get_run_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
+    }
+    HIPCHK(hipSetDevice(tr.device));
+    if (n == 0) return HF_OK;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_run_moments: the last pass kept no pair records");
+    if (!seq) {
+        const int rc = pass_all_records(ps);
+        if (rc) return rc;
+    }
+    hipStream_t st = ps.last_stream;
+    RunBufs& rb = ctx->rn;
+    MoFB fb{};
+    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
+    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
+    std::vector<RnPiece> pieces;
+    std::vector<RnPart> parts;
+    std::vector<int64_t> job_p0;
+    std::vector<double> val;
+    for (int64_t j0 = 0; j0 < n;) {
+        // the jobs of this batch, cut into parts and pieces
+        pieces.clear(); parts.clear(); job_p0.clear();
+        int64_t j1 = j0;
+        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
+            job_p0.push_back((int64_t) parts.size());
+            const int mask = state_mask[j1];
+            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
+            for (int64_t a = first[j1]; a <= last[j1]; c++) {
+                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
+                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
+                RnPart pt{a, b, (int) pieces.size(), 0, mask, c};
+                for (int64_t t = a + 1; t <= b;) {
+                    const int64_t e = std::min<int64_t>(b, (t / HF_RN_PIECE + 1) * HF_RN_PIECE - 1);
+                    pieces.push_back(RnPiece{t, (int) (e - t + 1), mask, c});
+                    t = e + 1;
+                }
+                pt.p1 = (int) pieces.size();
+                parts.push_back(pt);
+                a = b + 1;
+            }
+            j1++;
+        }
+        job_p0.push_back((int64_t) parts.size());
+        const size_t np = pieces.size(), nq = parts.size();
+        const size_t o_parts = Slab::granule(np * sizeof(RnPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(RnPart));
+        const size_t o_xi = o_pm + Slab::granule(np * 48 * 8), o_out = o_xi + Slab::granule(np * 8),
+                     bytes = o_out + Slab::granule(nq * HF_RN_OUT * 8);
+        if (bytes > rb.cap) {
+            rb.release();
+            if (hipMalloc((void**) &rb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); rb.d_buf = nullptr;
+                return set_err(HF_E_HIP, "hf_get_run_moments: out of device memory"); }
+            rb.cap = bytes;
+        }
+        RnPiece* d_pieces = reinterpret_cast<RnPiece*>(rb.d_buf);
+        RnPart* d_parts = reinterpret_cast<RnPart*>(rb.d_buf + o_parts);
+        double* d_pm = reinterpret_cast<double*>(rb.d_buf + o_pm);
+        double* d_xi = reinterpret_cast<double*>(rb.d_buf + o_xi);
+        double* d_out = reinterpret_cast<double*>(rb.d_buf + o_out);
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(RnPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(RnPart), hipMemcpyHostToDevice, st));
+        if (seq) {
+            if (np) hipLaunchKernelGGL(k_run_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, (const int32_t*) nullptr,
+                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_pm, d_xi);
+            hipLaunchKernelGGL(k_run_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_xi, fb, d_out);
+        } else {
+            if (np) hipLaunchKernelGGL(k_run_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, tr.d_arow, ps.d_lutA, tr.d_rec,
+                                       (const double*) nullptr, (const DevParams*) nullptr, fb, d_pm, d_xi);
+            hipLaunchKernelGGL(k_run_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_xi, fb, d_out);
+        }
+        HIPCHK(hipGetLastError());
+        val.resize(nq * HF_RN_OUT);
+        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * HF_RN_OUT * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {
+            // the parts of a job in chunk order.  x = (E[R], Var(R), s, e, Cov(R, E0), Cov(R, S0), Cov(S0, E0)) of a part; part k is joined
+            // to part k - 1 when it lies in the next chunk and that chunk continues the one before.  Three sums, each left to right:
+            //   mean = sum E[R] - sum_joined q,  var = sum Var(R) + sum_joined [...] + 2 sum_{both joined} [...]   (q = e_{k-1} s_k)
+            // so a job without a join is the plain sum of its parts.
+            const int64_t k0 = job_p0[(size_t) (j - j0)], k1 = job_p0[(size_t) (j - j0) + 1];
+            double m = 0.0, mq = 0.0, v = 0.0, vj = 0.0, vjj = 0.0;
+            bool prev_join = false;
+            for (int64_t k = k0; k < k1; k++) {
+                const double* x = &val[(size_t) k * HF_RN_OUT];
+                m += x[0]; v += x[1];
+                bool join = false;
+                if (k > k0 && joined) {
+                    const int c = parts[(size_t) k].c;
+                    join = parts[(size_t) k - 1].c == c - 1 && joined[c] != 0;
+                }
+                if (join) {
+                    const double* y = x - HF_RN_OUT;      // the part before
+                    const double q = y[3] * x[2];
+                    mq += q;
+                    vj += q * (1.0 - q) - 2.0 * (x[2] * y[4] + y[3] * x[5]);
+                    if (prev_join) vjj += (y - HF_RN_OUT)[3] * x[2] * y[6];
+                }
+                prev_join = join;
+            }
+            double var = (v + vj) + 2.0 * vjj;
+            if (!(var > 0.0)) var = 0.0;      // (a negative rounding residue)
+            mean_host[j] = m - mq; var_host[j] = var;
         }
         j0 = j1;
     }

@@ -636,6 +636,30 @@ class EMList:
                                              _dptr(mean), _dptr(var)), "hf_get_count_moments")
         return mean, var
 
+    def run_moments(self, first, last, mask, joined=None):
+        """Exact posterior mean and variance of block counts under the model of the last full pass (hf_get_run_moments): for every job
+        i, of the number of maximal runs of windows of first[i]..last[i] (inclusive) whose state is in the set mask[i].  joined: None, or
+        a bool array of n_chunks, joined[c] true where chunk c continues chunk c - 1 (a run across that boundary is one run; joined[0]
+        must be false) -> (mean float64[n], var float64[n]).  Scalars broadcast."""
+        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("run_moments: a state mask must be 1..15")
+        jn = None
+        if joined is not None:
+            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
+            if jn.size != int(self._L.hf_n_chunks(self._h)):
+                raise ValueError("run_moments: joined must have one entry per chunk")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        mean = np.empty(f.size, dtype=np.float64)
+        var = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_run_moments(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           _dptr(mean), _dptr(var)), "hf_get_run_moments")
+        return mean, var
+
     def set_alpha_stats(self, on: bool = True) -> None:
         """hf_set_alpha_stats: full passes from now on can be asked for the alpha statistics (alpha_stats)."""
         N.check(self._L.hf_set_alpha_stats(self._h, int(bool(on))), "hf_set_alpha_stats")
@@ -709,6 +733,15 @@ def EM_getCountMomentsForList(emList, first, last, mask, region=None, unit="wind
     if not hasattr(emList, "count_moments"):
         raise TypeError("EM_getCountMomentsForList: %s has no count-moments getter" % type(emList).__name__)
     return emList.count_moments(first, last, mask, region, unit)
+
+
+def EM_getRunMomentsForList(emList, first, last, mask, joined=None):
+    """Exact posterior (mean, variance) of the number of blocks (maximal runs of windows) of first[i]..last[i] whose state lies in
+    mask[i], under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run across
+    the boundary counts once (no counterpart in the reference): (float64[n], float64[n]).  `emList`: an EMList."""
+    if not hasattr(emList, "run_moments"):
+        raise TypeError("EM_getRunMomentsForList: %s has no run-moments getter" % type(emList).__name__)
+    return emList.run_moments(first, last, mask, joined)
 
 
 class EMBatch:

@@ -267,6 +267,30 @@ int hf_get_interval_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, cons
 enum { HF_COUNT_WINDOWS = 0, HF_COUNT_BASES = 1 };
 int hf_get_count_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
                          const int32_t *region /* NULL: all -1 */, int unit, double *mean_host, double *var_host);
+/* Exact mean and variance of block counts (flagger_amd/csrc/hf_runs.h), under the model of the last HF_MODE_FULL pass like hf_get_posterior.
+ * Job i is the window range first[i]..last[i] and the state set S = state_mask[i] as for hf_get_interval_log_probs.  For a chunk-local
+ * part [a, b] of the job:
+ *   R  = 1[s_a in S] + sum_{t=a+1..b} 1[s_{t-1} not in S, s_t in S]    (the runs of S that start inside the part)
+ *   S0 = 1[s_a in S],  E0 = 1[s_b in S]
+ * joined (NULL: all 0; joined[0] must be 0): joined[c] != 0 says that chunk c continues chunk c-1 on the same contig, so that a run of S
+ * over the last window of c-1 and the first window of c is ONE run.  With the job's parts 1..m in chunk order, part j+1 is joined to
+ * part j when it lies in the next chunk and that chunk has joined != 0.  The job's count is
+ *   B = sum_j R_j - sum_{joined j} E0_j S0_{j+1}
+ * and, chunks being independent chains, with e_j = E[E0_j], s_j = E[S0_j], q_j = e_j s_{j+1}:
+ *   mean[i] = sum_j E[R_j] - sum_{joined j} q_j
+ *   var[i]  = sum_j Var(R_j) + sum_{joined j} [ q_j (1 - q_j) - 2 (s_{j+1} Cov(R_j, E0_j) + e_j Cov(R_{j+1}, S0_{j+1})) ]
+ *             + 2 sum_{j, j+1 both joined} e_j s_{j+2} Cov(S0_{j+1}, E0_{j+1})
+ * each sum in chunk order; never negative, never NaN (a negative rounding residue is 0.0).  The per-part values are exact: E[R] =
+ * gamma_a(S) + the sum of the pair posteriors P(s_{t-1} not in S, s_t in S | data) in a fixed order, the variance and the covariances from
+ * the second-order jet of the chain's product with the pair tilt 1[p not in S] 1[s in S] centred by that pair posterior.  Mask 15 gives
+ * var exactly 0.0 and mean exactly the number of maximal joined groups of the job's parts.  A job's two values depend only on (first,
+ * last, mask, joined) and the pass, bitwise: not on the other jobs of the call, their order or their number; without a join they are the
+ * left-to-right sums of the parts' values.  Synchronous on the pass's stream; the first call after an EM pass of the default algorithm
+ * re-runs the segment kernel once, as hf_get_posterior's does.  Buffers of its own: nothing an EM pass or another getter reads is
+ * written.  n = 0 is a successful no-op.  HF_E_ARG: the cases of hf_get_interval_log_probs, joined[0] != 0.  hf_batch_* and hf_multi_*
+ * have no counterpart. */
+int hf_get_run_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
+                       const uint8_t *joined /* [n_chunks], NULL: none */, double *mean_host, double *var_host);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
