@@ -73,6 +73,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"fitAlphaEvery", required_argument, nullptr, 1014},        // every P-th iteration is an alpha-iteration [2]
     {"exactTotals", no_argument, nullptr, 1015},                // exact mean and SD of the label totals (hf_get_count_moments)
     {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
+    {"jointEntropy", no_argument, nullptr, 1017},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -142,7 +143,12 @@ static void usage(const char* program) {
             "                                      and for Err, Dup, Hap, Col and Err+Dup+Col, the number of blocks (maximal runs of windows, merged\n"
             "                                      across the chunks of a contig as the final BED merges them) in the final labels, and the exact\n"
             "                                      posterior mean and standard deviation of that number; no annotation-region scope (a block does\n"
-            "                                      not belong to one region); one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      not belong to one region); one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --jointEntropy               after the final inference, write path_uncertainty.tsv: for the whole track and every contig, the\n"
+            "                                      exact entropy (nats) of the posterior distribution over label paths (exp of it: the effective\n"
+            "                                      number of plausible segmentations), that entropy per window, the sum of the per-window posterior\n"
+            "                                      entropies (which ignores the chain's correlations and is never smaller), and the exact\n"
+            "                                      log-probability of the final labels; one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -703,6 +709,77 @@ static int write_exact_blocks(hf_ctx* ctx, const hfio_table* tab, const int8_t* 
     return HF_OK;
 }
 
+// --jointEntropy: exact path entropy and log-probability of the final labels (hf_get_path_entropy, hf_get_path_log_probs,
+// hf_get_entropy_profile) under the model of the last full pass.
+//   path_uncertainty.tsv   one row per scope.  Scopes: "all" and every contig by name (order of first appearance in the chunk list; chunks
+//                          are independent chains, so a contig's values are the sums over its maximal runs of consecutive chunks, in list
+//                          order: the rule of --numBlocks).  Columns: windows, path_entropy_nats, entropy_nats_per_window,
+//                          window_entropy_sum_nats (the sum of the per-window posterior entropies in window order: what the posterior
+//                          alone gives), final_labels_log_prob (-inf where the labels are impossible, NA where a label of the scope is
+//                          outside 0..3).
+static int write_path_uncertainty(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    // a scope: its name and its window ranges [a, b)
+    struct Scope { std::string name; std::vector<std::pair<int64_t, int64_t>> ranges; };
+    std::vector<Scope> scopes;
+    scopes.push_back(Scope{"all", {}});
+    if (N > 0) scopes.back().ranges.push_back({0, N});
+    std::map<std::string, size_t> ctgScope;
+    for (int c = 0; c < C; c++) {
+        const int64_t a = w.chunk_off[c], b = w.chunk_off[c + 1];
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        auto it = ctgScope.find(ctg);
+        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
+        if (a == b) continue;
+        auto& rg = scopes[it->second].ranges;
+        if (!rg.empty() && rg.back().second == a) rg.back().second = b;
+        else rg.push_back({a, b});
+    }
+    // the jobs: every range of every scope; the labelled ones only where every label of the range is a state
+    std::vector<int64_t> first, last, lfirst, llast;
+    std::vector<char> labelled;
+    for (const Scope& sc : scopes)
+        for (const auto& rg : sc.ranges) {
+            first.push_back(rg.first); last.push_back(rg.second - 1);
+            bool ok = true;
+            for (int64_t t = rg.first; t < rg.second && ok; t++) ok = finalLabels[t] >= 0 && finalLabels[t] <= 3;
+            labelled.push_back(ok);
+            if (ok) { lfirst.push_back(rg.first); llast.push_back(rg.second - 1); }
+        }
+    std::vector<double> ent(first.size()), lp(lfirst.size()), marg((size_t) N);
+    int rc = hf_get_path_entropy(ctx, (int64_t) first.size(), first.data(), last.data(), ent.data());
+    if (rc != HF_OK) return rc;
+    if ((rc = hf_get_path_log_probs(ctx, (int64_t) lfirst.size(), lfirst.data(), llast.data(), finalLabels, lp.data())) != HF_OK) return rc;
+    if (N > 0 && (rc = hf_get_entropy_profile(ctx, 0, N, marg.data(), nullptr)) != HF_OK) return rc;
+    const std::string tp = dir + "/path_uncertainty.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\twindows\tpath_entropy_nats\tentropy_nats_per_window\twindow_entropy_sum_nats\tfinal_labels_log_prob\n");
+    size_t j = 0, jl = 0;
+    for (const Scope& sc : scopes) {
+        int64_t windows = 0;
+        double h = 0.0, hw = 0.0, l = 0.0;       // sums over the ranges, list order
+        bool known = true;
+        for (const auto& rg : sc.ranges) {
+            windows += rg.second - rg.first;
+            h += ent[j];
+            for (int64_t t = rg.first; t < rg.second; t++) hw += marg[(size_t) t];
+            if (labelled[j]) l += lp[jl++];
+            else known = false;
+            j++;
+        }
+        fprintf(f, "%s\t%ld\t%.9g\t%.9g\t%.9g\t", sc.name.c_str(), (long) windows, h, windows > 0 ? h / (double) windows : 0.0, hw);
+        if (!known) fprintf(f, "NA\n");
+        else if (std::isinf(l)) fprintf(f, "-inf\n");
+        else fprintf(f, "%.9g\n", l);
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
     FILE* f = fopen(listPath, "r");
@@ -743,7 +820,7 @@ int main(int argc, char* argv[]) {
     bool viterbi = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
-    bool runConfidence = false, exactTotals = false, numBlocks = false;
+    bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -847,6 +924,7 @@ int main(int argc, char* argv[]) {
             case 1009: runConfidence = true; break;
             case 1015: exactTotals = true; break;
             case 1016: numBlocks = true; break;
+            case 1017: jointEntropy = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -917,6 +995,10 @@ int main(int argc, char* argv[]) {
     }
     if (numBlocks && (nGpus > 1 || sweepListPath)) {
         fprintf(stderr, "[%s] Error: --numBlocks runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
+    if (jointEntropy && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --jointEntropy runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
     // --fitAlpha: its own arguments and the refused combinations, before the input is read
@@ -1279,6 +1361,13 @@ int main(int argc, char* argv[]) {
         const double t0 = real_time();
         if ((rc = write_exact_blocks(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] label_blocks_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --jointEntropy: likewise
+    if (jointEntropy) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --jointEntropy needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_path_uncertainty(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] path_uncertainty.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

@@ -470,6 +470,18 @@ struct RunBufs {
     void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
 };
 
+// exact path entropy and labelling log-probability (hf_entropy.h): one device buffer of their own, grown on demand (pieces, parts, piece
+// sums, results / the profile's two arrays) and one for the labels of a call
+struct EntBufs {
+    char* d_buf = nullptr; size_t cap = 0;
+    int8_t* d_lab = nullptr; size_t lab_cap = 0;
+    void release() {
+        if (d_buf) hipFree(d_buf);
+        if (d_lab) hipFree(d_lab);
+        d_buf = nullptr; cap = 0; d_lab = nullptr; lab_cap = 0;
+    }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -485,7 +497,7 @@ struct AlphaStats {
 };
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
-// the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer
+// the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer, the entropy getters' buffers
 struct hf_ctx {
     Track tr;
     Pass pass;
@@ -495,6 +507,7 @@ struct hf_ctx {
     AlphaStats al;
     MomentBufs mo;
     RunBufs rn;
+    EntBufs en;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1034,6 +1047,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->al.release();
     ctx->mo.release();
     ctx->rn.release();
+    ctx->en.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2831,6 +2845,208 @@ int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
             mean_host[j] = m - mq; var_host[j] = var;
         }
         j0 = j1;
+    }
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact path entropy and labelling log-probability (hf_entropy.h) over the last full pass: the host cuts every job into chunk-local parts
+// and every part's interior windows into pieces as the run moments do, k_ent_piece sums the pieces' local terms, k_ent_chain adds every
+// part's first window and its piece sums, the host sums the parts of a job in chunk order.  Last in the file, so that no other kernel's
+// code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_entropy.h"
+
+// what the three entry points share: the state of the pass they answer for
+static int ent_ready(hf_ctx* ctx, const char* who, MoFB& fb) {
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, std::string(who) + ": the last pass kept no pair records");
+    if (!seq) {
+        const int rc = pass_all_records(ps);
+        if (rc) return rc;
+    }
+    fb = MoFB{};
+    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
+    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
+    return HF_OK;
+}
+
+// labels == nullptr: the path entropy of every job; else the log-probability of the labelling inside every job's range
+static int ent_jobs(hf_ctx* ctx, const char* who, int64_t n, const int64_t* first, const int64_t* last, const int8_t* labels, bool with_labels,
+                    double* out_host) {
+    const std::string name(who);
+    if (!ctx) return set_err(HF_E_ARG, name + ": bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    if (n < 0) return set_err(HF_E_ARG, name + ": n < 0");
+    if (n > 0 && (!first || !last || !out_host || (with_labels && !labels))) return set_err(HF_E_ARG, name + ": NULL array");
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, name + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    for (int64_t i = 0; i < n; i++)
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N) return set_err(HF_E_ARG, name + ": bad range (job " + std::to_string(i) + ")");
+    // the labels of the call: the union of the ranges, and nothing outside it, is looked at; lo .. hi is the span of the union
+    std::vector<int8_t> lab;
+    int64_t lo = 0, hi = -1;
+    if (with_labels && n > 0) {
+        std::vector<std::pair<int64_t, int64_t>> rg((size_t) n);
+        for (int64_t i = 0; i < n; i++) rg[(size_t) i] = {first[i], last[i]};
+        std::sort(rg.begin(), rg.end());
+        lo = rg.front().first;
+        for (const auto& r : rg) hi = std::max(hi, r.second);
+        lab.assign((size_t) (hi - lo + 1), 0);
+        int64_t done = lo;                        // every window below `done` is checked and copied
+        for (const auto& r : rg) {
+            for (int64_t t = std::max(done, r.first); t <= r.second; t++) {
+                if (labels[t] < 0 || labels[t] > 3) return set_err(HF_E_ARG, name + ": a label outside 0..3 (window " + std::to_string(t) + ")");
+                lab[(size_t) (t - lo)] = labels[t];
+            }
+            done = std::max(done, r.second + 1);
+        }
+    }
+    HIPCHK(hipSetDevice(tr.device));
+    if (n == 0) return HF_OK;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    MoFB fb;
+    const int rc0 = ent_ready(ctx, who, fb);
+    if (rc0) return rc0;
+    hipStream_t st = ps.last_stream;
+    EntBufs& eb = ctx->en;
+    if (with_labels) {
+        if (lab.size() > eb.lab_cap) {
+            if (eb.d_lab) hipFree(eb.d_lab);
+            eb.d_lab = nullptr; eb.lab_cap = 0;
+            if (hipMalloc((void**) &eb.d_lab, lab.size()) != hipSuccess) { (void) hipGetLastError(); eb.d_lab = nullptr;
+                return set_err(HF_E_HIP, name + ": out of device memory"); }
+            eb.lab_cap = lab.size();
+        }
+        HIPCHK(hipMemcpyAsync(eb.d_lab, lab.data(), lab.size(), hipMemcpyHostToDevice, st));
+    }
+    std::vector<EnPiece> pieces;
+    std::vector<EnPart> parts;
+    std::vector<int64_t> job_p0;
+    std::vector<double> val;
+    for (int64_t j0 = 0; j0 < n;) {
+        // the jobs of this batch, cut into parts and pieces
+        pieces.clear(); parts.clear(); job_p0.clear();
+        int64_t j1 = j0;
+        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
+            job_p0.push_back((int64_t) parts.size());
+            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
+            for (int64_t a = first[j1]; a <= last[j1]; c++) {
+                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
+                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
+                EnPart pt{a, (int) pieces.size(), 0, c, 0};
+                for (int64_t t = a + 1; t <= b;) {
+                    const int64_t e = std::min<int64_t>(b, (t / HF_EN_PIECE + 1) * HF_EN_PIECE - 1);
+                    pieces.push_back(EnPiece{t, (int) (e - t + 1), c});
+                    t = e + 1;
+                }
+                pt.p1 = (int) pieces.size();
+                parts.push_back(pt);
+                a = b + 1;
+            }
+            j1++;
+        }
+        job_p0.push_back((int64_t) parts.size());
+        const size_t np = pieces.size(), nq = parts.size();
+        const size_t o_parts = Slab::granule(np * sizeof(EnPiece)), o_px = o_parts + Slab::granule(nq * sizeof(EnPart));
+        const size_t o_out = o_px + Slab::granule(np * 8), bytes = o_out + Slab::granule(nq * 8);
+        if (bytes > eb.cap) {
+            if (eb.d_buf) hipFree(eb.d_buf);
+            eb.d_buf = nullptr; eb.cap = 0;
+            if (hipMalloc((void**) &eb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); eb.d_buf = nullptr;
+                return set_err(HF_E_HIP, name + ": out of device memory"); }
+            eb.cap = bytes;
+        }
+        EnPiece* d_pieces = reinterpret_cast<EnPiece*>(eb.d_buf);
+        EnPart* d_parts = reinterpret_cast<EnPart*>(eb.d_buf + o_parts);
+        double* d_px = reinterpret_cast<double*>(eb.d_buf + o_px);
+        double* d_out = reinterpret_cast<double*>(eb.d_buf + o_out);
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(EnPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(EnPart), hipMemcpyHostToDevice, st));
+        const dim3 gp((unsigned) np), gc((unsigned) ((nq + 63) / 64)), blk(64);
+        const int32_t* arow = seq ? nullptr : tr.d_arow;
+        const double* lutA = seq ? nullptr : ps.d_lutA;
+        const double* E = seq ? ps.d_E : nullptr;
+        const DevParams* Pm = seq ? ps.d_params : nullptr;
+        const int8_t* d_lab = eb.d_lab;
+        const long long lab0 = lo;
+#define HF_EN_LAUNCH(SEQ, LAB)                                                                                                         \
+        do {                                                                                                                           \
+            if (np) hipLaunchKernelGGL((k_ent_piece<SEQ, LAB>), gp, blk, 0, st, d_pieces, arow, lutA, tr.d_rec, E, Pm, fb, d_lab, lab0, d_px); \
+            hipLaunchKernelGGL((k_ent_chain<SEQ, LAB>), gc, blk, 0, st, (int) nq, d_parts, d_px, fb, d_lab, lab0, d_out);                  \
+        } while (0)
+        if (seq) { if (with_labels) HF_EN_LAUNCH(true, true); else HF_EN_LAUNCH(true, false); }
+        else { if (with_labels) HF_EN_LAUNCH(false, true); else HF_EN_LAUNCH(false, false); }
+#undef HF_EN_LAUNCH
+        HIPCHK(hipGetLastError());
+        val.resize(nq);
+        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
+            double v = 0.0;
+            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) v += val[(size_t) k];
+            out_host[j] = v;
+        }
+        j0 = j1;
+    }
+    return HF_OK;
+}
+
+int hf_get_path_entropy(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, double* entropy_host) {
+    return ent_jobs(ctx, "hf_get_path_entropy", n, first, last, nullptr, false, entropy_host);
+}
+
+int hf_get_path_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const int8_t* labels_host, double* log_p_host) {
+    return ent_jobs(ctx, "hf_get_path_log_probs", n, first, last, labels_host, true, log_p_host);
+}
+
+// windows per launch of k_ent_profile (16 bytes of results per window)
+#define HF_EN_PROFILE_BATCH ((int64_t) 1 << 22)
+
+int hf_get_entropy_profile(hf_ctx* ctx, int64_t first, int64_t n, double* marg_host, double* cond_host) {
+    if (!ctx) return set_err(HF_E_ARG, "hf_get_entropy_profile: bad argument");
+    const Track& tr = ctx->tr;
+    Pass& ps = ctx->pass;
+    if (!marg_host && !cond_host) return set_err(HF_E_ARG, "hf_get_entropy_profile: both output arrays are NULL");
+    if (first < 0 || n < 0 || first > tr.N || n > tr.N - first) return set_err(HF_E_ARG, "hf_get_entropy_profile: bad range");
+    if (!ps.have_full)
+        return set_err(HF_E_ARG, "hf_get_entropy_profile: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    HIPCHK(hipSetDevice(tr.device));
+    if (n == 0) return HF_OK;
+    const bool seq = tr.algo == HF_ALGO_SEQ;
+    MoFB fb;
+    const int rc0 = ent_ready(ctx, "hf_get_entropy_profile", fb);
+    if (rc0) return rc0;
+    hipStream_t st = ps.last_stream;
+    EntBufs& eb = ctx->en;
+    const int64_t nb = std::min<int64_t>(n, HF_EN_PROFILE_BATCH);
+    const size_t o_cond = Slab::granule((size_t) nb * 8), bytes = 2 * o_cond;
+    if (bytes > eb.cap) {
+        if (eb.d_buf) hipFree(eb.d_buf);
+        eb.d_buf = nullptr; eb.cap = 0;
+        if (hipMalloc((void**) &eb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); eb.d_buf = nullptr;
+            return set_err(HF_E_HIP, "hf_get_entropy_profile: out of device memory"); }
+        eb.cap = bytes;
+    }
+    double* d_marg = marg_host ? reinterpret_cast<double*>(eb.d_buf) : nullptr;
+    double* d_cond = cond_host ? reinterpret_cast<double*>(eb.d_buf + o_cond) : nullptr;
+    for (int64_t i0 = 0; i0 < n; i0 += nb) {
+        const int64_t m = std::min<int64_t>(nb, n - i0);
+        const dim3 grid((unsigned) ((m + 255) / 256)), blk(256);
+        if (seq)
+            hipLaunchKernelGGL(k_ent_profile<true>, grid, blk, 0, st, (long long) (first + i0), (long long) m, tr.d_off, tr.C, (const int32_t*) nullptr,
+                               (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_marg, d_cond);
+        else
+            hipLaunchKernelGGL(k_ent_profile<false>, grid, blk, 0, st, (long long) (first + i0), (long long) m, tr.d_off, tr.C, tr.d_arow, ps.d_lutA,
+                               tr.d_rec, (const double*) nullptr, (const DevParams*) nullptr, fb, d_marg, d_cond);
+        HIPCHK(hipGetLastError());
+        if (marg_host) HIPCHK(hipMemcpyAsync(marg_host + i0, d_marg, (size_t) m * 8, hipMemcpyDeviceToHost, st));
+        if (cond_host) HIPCHK(hipMemcpyAsync(cond_host + i0, d_cond, (size_t) m * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     return HF_OK;
 }

@@ -660,6 +660,47 @@ class EMList:
                                            _dptr(mean), _dptr(var)), "hf_get_run_moments")
         return mean, var
 
+    def path_entropy(self, first, last) -> np.ndarray:
+        """Exact path entropy under the model of the last full pass (hf_get_path_entropy): for every job i, the Shannon entropy in nats
+        of the joint posterior distribution of the labels of the windows first[i]..last[i] (inclusive; chunks are independent chains)
+        -> float64[n].  exp of it is the effective number of plausible labellings of the range.  Scalars broadcast."""
+        f, l = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64))
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        out = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_path_entropy(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            l.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(out)), "hf_get_path_entropy")
+        return out
+
+    def path_log_probs(self, first, last, labels) -> np.ndarray:
+        """Exact log-probability of a labelling under the model of the last full pass (hf_get_path_log_probs): for every job i,
+        log P(the windows first[i]..last[i] (inclusive) have the labels labels[first[i]..last[i]] | data) -> float64[n], -inf where the
+        labelling is impossible.  labels: n_windows values 0..3, read only inside the jobs' ranges.  Scalars broadcast."""
+        f, l = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64))
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.size != self.store.n_windows:
+            raise ValueError("path_log_probs: labels must hold one label per window")
+        if lab.dtype != np.int8:
+            lab = np.clip(lab, -128, 127)                      # (a label outside 0..3 stays outside)
+        lab = np.ascontiguousarray(lab, np.int8)
+        out = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_path_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              l.ctypes.data_as(C.POINTER(C.c_int64)), lab.ctypes.data_as(C.POINTER(C.c_int8)),
+                                              _dptr(out)), "hf_get_path_log_probs")
+        return out
+
+    def entropy_profile(self, first: int = 0, n: Optional[int] = None):
+        """Per-window entropies under the model of the last full pass (hf_get_entropy_profile) for windows [first, first+n):
+        (marg, cond), marg[i] the entropy of the window's posterior, cond[i] the entropy of its label given the label of the window
+        before (marg[i] at the first window of a chunk), in nats.  The path entropy of a range inside one chunk is marg of its first
+        window plus the sum of cond over the others."""
+        n = self.store.n_windows - first if n is None else n
+        marg, cond = np.empty(max(n, 0)), np.empty(max(n, 0))
+        N.check(self._L.hf_get_entropy_profile(self._h, first, n, _dptr(marg), _dptr(cond)), "hf_get_entropy_profile")
+        return marg, cond
+
     def set_alpha_stats(self, on: bool = True) -> None:
         """hf_set_alpha_stats: full passes from now on can be asked for the alpha statistics (alpha_stats)."""
         N.check(self._L.hf_set_alpha_stats(self._h, int(bool(on))), "hf_set_alpha_stats")
@@ -742,6 +783,30 @@ def EM_getRunMomentsForList(emList, first, last, mask, joined=None):
     if not hasattr(emList, "run_moments"):
         raise TypeError("EM_getRunMomentsForList: %s has no run-moments getter" % type(emList).__name__)
     return emList.run_moments(first, last, mask, joined)
+
+
+def EM_getPathEntropyForList(emList, first, last) -> np.ndarray:
+    """Exact Shannon entropy (nats) of the posterior distribution over the label paths of the windows first[i]..last[i], under the model
+    of the last full pass, per job (no counterpart in the reference): float64[n].  `emList`: an EMList."""
+    if not hasattr(emList, "path_entropy"):
+        raise TypeError("EM_getPathEntropyForList: %s has no path-entropy getter" % type(emList).__name__)
+    return emList.path_entropy(first, last)
+
+
+def EM_getPathLogProbsForList(emList, first, last, labels) -> np.ndarray:
+    """log P(the windows first[i]..last[i] have the labels labels[first[i]..last[i]] | data) under the model of the last full pass, per
+    job (no counterpart in the reference): float64[n].  `emList`: an EMList."""
+    if not hasattr(emList, "path_log_probs"):
+        raise TypeError("EM_getPathLogProbsForList: %s has no path log-probability getter" % type(emList).__name__)
+    return emList.path_log_probs(first, last, labels)
+
+
+def EM_getEntropyProfileForList(emList, first: int = 0, n: Optional[int] = None):
+    """(marg, cond): per window, the entropy of its posterior and the entropy of its label given the label of the window before, under
+    the model of the last full pass (no counterpart in the reference).  `emList`: an EMList."""
+    if not hasattr(emList, "entropy_profile"):
+        raise TypeError("EM_getEntropyProfileForList: %s has no entropy profile" % type(emList).__name__)
+    return emList.entropy_profile(first, n)
 
 
 class EMBatch:

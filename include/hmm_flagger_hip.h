@@ -291,6 +291,44 @@ int hf_get_count_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int
  * have no counterpart. */
 int hf_get_run_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
                        const uint8_t *joined /* [n_chunks], NULL: none */, double *mean_host, double *var_host);
+/* Exact path entropy and labelling log-probability (flagger_amd/csrc/hf_entropy.h), under the model of the last HF_MODE_FULL pass like
+ * hf_get_posterior.  f, b are that pass's scaled forward and backward vectors (hf_get_forward_backward), A_t the row the pass multiplied
+ * by at window t.  Given the data, the label path of a chunk is an inhomogeneous Markov chain whose transition at window t is the pair
+ * posterior over its row marginal.  For a window t that is not the first of its chunk:
+ *   x_t[p][s] = f_{t-1}[p] * A_t[p][s] * b_t[s]   (multiplied in that order)
+ *   m_t[p]    = sum_s x_t[p][s]                   (summed in state order)
+ *   Z_t       = sum_p m_t[p]
+ *   cond_t    = - sum_p sum_s (x_t[p][s] / Z_t) log(x_t[p][s] / m_t[p])      (an entry with x = 0 contributes 0)
+ * x <= m_p holds in floating point too (m_p is a sum of non-negatives that contains x): every term is >= 0, and neither a clamp nor a
+ * difference of large numbers appears.  For any window:
+ *   gamma_t[s] = f_t[s] b_t[s] / sum_s f_t[s] b_t[s]      (hf_get_posterior's value, the sum in state order)
+ *   marg_t     = - sum_s gamma_t[s] log gamma_t[s]        (a zero contributes 0)
+ * and cond_t := marg_t at the first window of a chunk.  Job i is the window range first[i]..last[i] (global indices, inclusive, 0 <= first
+ * <= last < n_windows; it may span chunks).  Chunks are independent chains: a job's value is the sum, in chunk order, of the values of its
+ * chunk-local parts [a, b]:
+ *   entropy(part)     = marg_a + sum_{t=a+1..b} cond_t: the Shannon entropy of the joint posterior of (s_a..s_b), in nats (the chain
+ *                       rule H(s_a..s_b) = H(s_a) + sum_t H(s_t | s_{t-1}) of a Markov chain; exp of it is the effective number of
+ *                       plausible labellings of the range)
+ *   log_prob(part; y) = log gamma_a[y_a] + sum_{t=a+1..b} log(x_t[y_{t-1}][y_t] / m_t[y_{t-1}]) = log P(s_a..s_b = y_a..y_b | data);
+ *                       -inf as soon as one factor is 0 (a zero m makes that factor 0)
+ *   hf_get_path_entropy     entropy_host[i] >= 0, never NaN
+ *   hf_get_path_log_probs   log_p_host[i] <= 0 or -inf, never NaN, for the labelling labels_host[t] (0..3) of the windows of the job;
+ *                           labels_host has n_windows entries, of which only those inside some job's range are read
+ *   hf_get_entropy_profile  marg_host[i] = marg_t and cond_host[i] = cond_t for t = first + i, i < n (either array may be NULL): 0 <=
+ *                           cond_t <= marg_t up to rounding, since conditioning cannot raise entropy; the sum of marg_t over a range is
+ *                           what the per-window posteriors alone give, and it is never below the path entropy beyond rounding
+ * A job's value depends only on (first, last), the labels inside the range and the pass, bitwise: not on the other jobs of the call, their
+ * order or their number; a chunk-spanning job is bitwise the left-to-right sum of its parts asked as separate jobs.  Synchronous on the
+ * pass's stream; the first call after an EM pass of the default algorithm re-runs the segment kernel once, as hf_get_posterior's does,
+ * also in several sub-passes.  HF_ALGO_SCAN and HF_ALGO_SEQ, all three model types (nothing here depends on the emission).  Buffers of
+ * their own: nothing an EM pass or another getter reads is written.  n = 0 is a successful no-op.  HF_E_ARG: the cases of
+ * hf_get_interval_log_probs (no full pass yet or the last pass forward-only, n < 0, a NULL array with n > 0, a bad range), a label
+ * outside 0..3 inside some job's range (labels outside every range are not looked at), the profile call with both output arrays NULL.
+ * hf_batch_* and hf_multi_* have no counterpart. */
+int hf_get_path_entropy(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, double *entropy_host);
+int hf_get_path_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last,
+                          const int8_t *labels_host /* [n_windows], read only inside the jobs' ranges */, double *log_p_host);
+int hf_get_entropy_profile(hf_ctx *ctx, int64_t first, int64_t n, double *marg_host /* or NULL */, double *cond_host /* or NULL */);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
