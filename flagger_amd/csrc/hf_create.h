@@ -248,6 +248,28 @@ int create_device_store(CreateWork& cw) {
                            tr.beta_star, tr.d_rec, tr.d_beta, tr.d_setup_flags);
         hipLaunchKernelGGL(k_regmask, dim3((unsigned) C), dim3(256), 0, 0, tr.d_off, tr.d_rec, tr.d_regmask);
     }
+    if (N > 0 && C > 0 && (w->chunk_off[0] != 0 || (size_t) w->chunk_off[C] != N)) {
+        // Windows outside every chunk: k_setup writes nothing for them, yet the per-window kernels of HF_ALGO_SEQ (k_emit_rows) and of its
+        // decoders (k_dec_rows_win) visit every window of the arrays and index the parameter block by the record's region.  They get the
+        // record and beta of a chunk's first window — a valid record that looks at no window before it —, and nothing reads what is
+        // computed from them.  (The one place of hf_create that waits for k_setup; a track without such windows does not come here.)
+        uint32_t r = 1u << 19;      // (no chunk holds a window: a chunk-first window of region 0 without coverage, beta 1)
+        double b = 1.0;
+        for (size_t c = 0; c < C; c++)
+            if (w->chunk_off[c + 1] > w->chunk_off[c]) {
+                r = cw.hrec[(size_t) w->chunk_off[c]];
+                HIPCHK(hipMemcpy(&b, tr.d_beta + w->chunk_off[c], 8, hipMemcpyDeviceToHost));
+                break;
+            }
+        const size_t front = (size_t) w->chunk_off[0], back0 = (size_t) w->chunk_off[C], gap = std::max(front, N - back0);
+        const std::vector<uint32_t> hr(gap, r);
+        const std::vector<double> hb(gap, b);
+        if (front) { HIPCHK(hipMemcpy(tr.d_rec, hr.data(), front * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(tr.d_beta, hb.data(), front * 8, hipMemcpyHostToDevice)); }
+        if (N > back0) {
+            HIPCHK(hipMemcpy(tr.d_rec + back0, hr.data(), (N - back0) * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(tr.d_beta + back0, hb.data(), (N - back0) * 8, hipMemcpyHostToDevice));
+        }
+    }
     cw.phase("events, memsets, k_setup enqueued");
     // (no wait for k_setup: a region index out of range has been refused already; its flag word — the track's, so that the set-up needs no
     // pass state — is read behind the ONE synchronisation at the end of hf_create)
@@ -906,7 +928,10 @@ extern "C" int hf_create(const hf_windows* w, int n_regions, int max_comps, int 
     tr.meta.chunk_off = nullptr; tr.meta.cov = tr.meta.mapq = tr.meta.clip = nullptr;
     tr.meta.annot = nullptr; tr.meta.chunk_s = tr.meta.chunk_e = tr.meta.chunk_ctg_len = nullptr;
     tr.h_cs.assign(w->chunk_s, w->chunk_s + w->n_chunks); tr.h_ce.assign(w->chunk_e, w->chunk_e + w->n_chunks);
+    // (windows may lie in front of the first chunk and behind the last one, but no chunk outside the window arrays)
+    if (w->n_chunks > 0 && w->chunk_off[0] < 0) return set_err(HF_E_ARG, "hf_create: bad chunk_off (chunk_off[0] < 0)");
     for (int c = 0; c < w->n_chunks; c++) {
+        if (w->chunk_off[c + 1] > w->n_windows) return set_err(HF_E_ARG, "hf_create: bad chunk_off (a chunk ends behind n_windows)");
         const int64_t T = w->chunk_off[c + 1] - w->chunk_off[c];
         if (T < 0 || T > INT32_MAX) return set_err(HF_E_ARG, "hf_create: bad chunk_off");
         if (T > cw.maxT) cw.maxT = (int32_t) T;

@@ -1819,6 +1819,13 @@ int hf_em_iterate(hf_ctx* ctx, hfm_model* model, int mode, int do_mstep, double 
     return HF_OK;
 }
 
+// Windows may lie in no chunk (chunk_off[0] > 0, chunk_off[n_chunks] < n_windows: hf_create); the chunks themselves are contiguous.  A pass
+// computes nothing for such a window, so the getters that answer for a range refuse one that touches it.
+static bool in_chunks(const Track& tr, int64_t first, int64_t last) {
+    return tr.C > 0 && first >= tr.h_off.front() && last < tr.h_off.back();
+}
+static bool all_in_chunks(const Track& tr) { return tr.N == 0 || in_chunks(tr, 0, tr.N - 1); }
+
 static int pass_labels(Pass& ps, int8_t* labels_host) {
     const Track& tr = *ps.tr;
     if (!labels_host) return set_err(HF_E_ARG, "hf_get_labels: bad argument");
@@ -1894,6 +1901,7 @@ static int pass_all_records(Pass& ps) {
 static int pass_forward_backward(Pass& ps, int64_t first, int64_t n, double* f_host, double* b_host, double* scales_host) {
     const Track& tr = *ps.tr;
     if (first < 0 || n < 0 || first + n > tr.N) return set_err(HF_E_ARG, "hf_get_forward_backward: bad range");
+    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, "hf_get_forward_backward: the range holds a window outside every chunk");
     if (!ps.have_full)   // a forward-only pass of the segment kernels keeps everything in registers: nothing of THIS pass to return
         return set_err(HF_E_ARG, "hf_get_forward_backward: the last pass was not HF_MODE_FULL (forward, backward and scale values would be stale)");
     HIPCHK(hipSetDevice(tr.device));
@@ -1965,6 +1973,7 @@ static int pass_posterior(Pass& ps, int64_t first, int64_t n, double* post_host)
     if (!post_host) return set_err(HF_E_ARG, "hf_get_posterior: bad argument");
     // (before the buffers below are sized by n: a negative n would throw out of the C ABI)
     if (first < 0 || n < 0 || first + n > ps.tr->N) return set_err(HF_E_ARG, "hf_get_posterior: bad range");
+    if (n > 0 && !in_chunks(*ps.tr, first, first + n - 1)) return set_err(HF_E_ARG, "hf_get_posterior: the range holds a window outside every chunk");
     std::vector<double> f((size_t) n * 4), b((size_t) n * 4), sc((size_t) n);
     int rc = pass_forward_backward(ps, first, n, f.data(), b.data(), sc.data());
     if (rc) return rc;
@@ -2216,6 +2225,7 @@ int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
                                  [&] { return dec_alloc(tr, v, [&](auto&& f) { vit_arrays(tr, v, f); }); });
     if (rc) return rc;
     if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
     if (dec_work(tr)) {
         if (dec_scan(tr)) {
             hipLaunchKernelGGL(k_vit_replay, dim3((unsigned) tr.nseg), dim3(64), 0, st, tr.d_seg, tr.d_rec, v.d_params, v.d_rows, v.d_P,
@@ -2313,6 +2323,7 @@ int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n
     hipStream_t st = (hipStream_t) stream;
     const int rc = dec_begin<SumTimes>(tr, s, p, st, "hf_sample_paths", [&] { return smp_prepare(ctx, first_sample, n_samples, seed); });
     if (rc) return rc;
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(s.d_label, 0xff, (size_t) n_samples * (size_t) tr.N, st));   // (windows outside every chunk: label -1)
     if (dec_work(tr)) {
         if (dec_scan(tr)) {
             const unsigned G = (unsigned) tr.nseg, K = (unsigned) n_samples;
@@ -2371,6 +2382,8 @@ int hf_get_interval_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
     for (int64_t i = 0; i < n; i++) {
         if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
             return set_err(HF_E_ARG, "hf_get_interval_log_probs: bad range (job " + std::to_string(i) + ")");
+        if (!in_chunks(tr, first[i], last[i]))
+            return set_err(HF_E_ARG, "hf_get_interval_log_probs: a window outside every chunk (job " + std::to_string(i) + ")");
         if (state_mask[i] < 1 || state_mask[i] > 15)
             return set_err(HF_E_ARG, "hf_get_interval_log_probs: state_mask must be 1..15 (job " + std::to_string(i) + ")");
     }
@@ -2631,6 +2644,8 @@ int hf_get_count_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int
     for (int64_t i = 0; i < n; i++) {
         if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
             return set_err(HF_E_ARG, "hf_get_count_moments: bad range (job " + std::to_string(i) + ")");
+        if (!in_chunks(tr, first[i], last[i]))
+            return set_err(HF_E_ARG, "hf_get_count_moments: a window outside every chunk (job " + std::to_string(i) + ")");
         if (state_mask[i] < 1 || state_mask[i] > 15)
             return set_err(HF_E_ARG, "hf_get_count_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
         if (region && (region[i] < -1 || region[i] >= tr.R))
@@ -2741,6 +2756,8 @@ int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
     for (int64_t i = 0; i < n; i++) {
         if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
             return set_err(HF_E_ARG, "hf_get_run_moments: bad range (job " + std::to_string(i) + ")");
+        if (!in_chunks(tr, first[i], last[i]))
+            return set_err(HF_E_ARG, "hf_get_run_moments: a window outside every chunk (job " + std::to_string(i) + ")");
         if (state_mask[i] < 1 || state_mask[i] > 15)
             return set_err(HF_E_ARG, "hf_get_run_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
     }
@@ -2885,8 +2902,10 @@ static int ent_jobs(hf_ctx* ctx, const char* who, int64_t n, const int64_t* firs
     if (n > 0 && (!first || !last || !out_host || (with_labels && !labels))) return set_err(HF_E_ARG, name + ": NULL array");
     if (!ps.have_full)
         return set_err(HF_E_ARG, name + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    for (int64_t i = 0; i < n; i++)
+    for (int64_t i = 0; i < n; i++) {
         if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N) return set_err(HF_E_ARG, name + ": bad range (job " + std::to_string(i) + ")");
+        if (!in_chunks(tr, first[i], last[i])) return set_err(HF_E_ARG, name + ": a window outside every chunk (job " + std::to_string(i) + ")");
+    }
     // the labels of the call: the union of the ranges, and nothing outside it, is looked at; lo .. hi is the span of the union
     std::vector<int8_t> lab;
     int64_t lo = 0, hi = -1;
@@ -3013,6 +3032,7 @@ int hf_get_entropy_profile(hf_ctx* ctx, int64_t first, int64_t n, double* marg_h
     Pass& ps = ctx->pass;
     if (!marg_host && !cond_host) return set_err(HF_E_ARG, "hf_get_entropy_profile: both output arrays are NULL");
     if (first < 0 || n < 0 || first > tr.N || n > tr.N - first) return set_err(HF_E_ARG, "hf_get_entropy_profile: bad range");
+    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, "hf_get_entropy_profile: the range holds a window outside every chunk");
     if (!ps.have_full)
         return set_err(HF_E_ARG, "hf_get_entropy_profile: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
     HIPCHK(hipSetDevice(tr.device));

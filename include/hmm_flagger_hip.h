@@ -53,7 +53,10 @@ enum {
 typedef struct hf_ctx hf_ctx;
 
 /* The windowed coverage track, in the reference's packed-record fields (chunk.c:669-697):
- * one entry per window, chunks delimited by chunk_off; all arrays in HOST memory. */
+ * one entry per window, chunks delimited by chunk_off; all arrays in HOST memory.  A chunk may hold no window.  Windows may lie in
+ * front of the first chunk and behind the last one (0 <= chunk_off[0], chunk_off[n_chunks] <= n_windows, else HF_E_ARG): values exist
+ * only for windows inside a chunk — the labels of hf_get_labels, hf_get_viterbi_labels and hf_get_sample_labels are -1 outside, and
+ * every getter that takes a window range or jobs returns HF_E_ARG for one that touches a window outside every chunk. */
 typedef struct hf_windows {
     int64_t n_windows;
     int32_t n_chunks;
@@ -274,7 +277,8 @@ int hf_get_count_moments(hf_ctx *ctx, int64_t n, const int64_t *first, const int
  *   S0 = 1[s_a in S],  E0 = 1[s_b in S]
  * joined (NULL: all 0; joined[0] must be 0): joined[c] != 0 says that chunk c continues chunk c-1 on the same contig, so that a run of S
  * over the last window of c-1 and the first window of c is ONE run.  With the job's parts 1..m in chunk order, part j+1 is joined to
- * part j when it lies in the next chunk and that chunk has joined != 0.  The job's count is
+ * part j when it lies in the next chunk and that chunk has joined != 0; a chunk without windows has no part, so it ends a run of
+ * joined chunks whatever its and its successor's entries say.  The job's count is
  *   B = sum_j R_j - sum_{joined j} E0_j S0_{j+1}
  * and, chunks being independent chains, with e_j = E[E0_j], s_j = E[S0_j], q_j = e_j s_{j+1}:
  *   mean[i] = sum_j E[R_j] - sum_{joined j} q_j

@@ -1,0 +1,259 @@
+"""The grid store of tests/test_geometry_cpu.py and tests/test_geometry_gpu.py: a track whose chunk list is laid against the range
+getters' global piece grid (pieces of 512 windows cut at global multiples of 512, lanes of 8 windows), its jobs, its references and
+the variants of it with chunks that hold no window and with windows that lie in no chunk.
+
+Chunks (one contig each), first window .. last window:
+    0..0, 511..511, 512..512, 513..513   one window, at the track's start, one before, on and one after a grid point
+    1..2, 1023..1024                     two windows; the second pair lies across a grid point
+    3..503                               ends on a lane boundary (504)
+    504..510, 514..1022                  between the one-window chunks
+    1025..1535                           ends on the grid
+    1536..2047                           exactly one aligned piece
+    2048..3072                           starts on the grid: a first window, two pieces less that window, one window over
+    3073..4172                           long and unaligned
+Jobs: every pair first <= last over the boundary points (POINTS: every chunk's first and last window +- 1, every multiple of 512 +- 1,
+and 7, 8, 9, 503, 504, 505), a random mask 1..15 and a random region filter each."""
+import dataclasses
+import functools
+
+import numpy as np
+
+from flagger_amd import synth
+from test_bruteforce_cpu import _tiny_store
+from test_moments_cpu import TINY
+from test_viterbi_cpu import perturbed_model
+import entropy_ref as ER
+import interval_ref as IR
+import moments_ref as MR
+import posterior_ref as PR
+import runs_ref as RR
+import sampling_ref as S
+import viterbi_ref
+
+OFF = [0, 1, 3, 504, 511, 512, 513, 514, 1023, 1025, 1536, 2048, 3073, 4173]
+N_WINDOWS = OFF[-1]
+JOINED = (4, 5, 6, 7, 9)            # chunks that continue their predecessor (hf_get_run_moments): 504..1022 and 1023..1535 are one contig each
+PIECE, LANE = 512, 8
+CASES = TINY                         # trunc-exp-Gaussian / HiFi alpha / two regions; Gaussian / alpha 0 / one region; negative binomial
+SAMPLES, SAMPLE_SEED = 8, 41
+# the generator of a case's store and model: chosen so that every boundary point matters to every getter (tests/test_geometry_cpu.py)
+STORE_SEED = {0: 9100, 1: 9101, 2: 9102}
+# coverage set by hand at the few windows whose posterior the draw left certain (window: coverage, mapq the same, no clipping)
+COV_AT = {0: {0: 30, 2560: 30, 4095: 46, 4096: 6, 4172: 18}, 1: {9: 30, 3073: 26, 3583: 30, 3584: 34}, 2: {}}
+
+
+def _points():
+    B = set()
+    for o in OFF:
+        B.update([o - 1, o, o + 1])
+    for g in range(PIECE, N_WINDOWS, PIECE):
+        B.update([g - 1, g, g + 1])
+    B.update([503, 504, 505, 7, 8, 9])
+    return np.array(sorted(b for b in B if 0 <= b < N_WINDOWS), np.int64)
+
+
+POINTS = _points()
+
+
+def joins():
+    j = np.zeros(len(OFF) - 1, bool)
+    j[list(JOINED)] = True
+    return j
+
+
+@functools.lru_cache(maxsize=None)
+def case(model_type, seed):
+    """(store, model, alpha, (F, L, M, R)) of a case, once for every test that uses it; nothing of it is changed later (a pass with
+    the model writes its estimators only)."""
+    rng = np.random.default_rng(STORE_SEED[seed])
+    alpha = synth.HIFI_ALPHA if seed % 2 == 0 else np.zeros((4, 4))
+    regions = [20, 31] if seed % 2 == 0 else [25]
+    store = _tiny_store(rng, list(np.diff(OFF)), regions)
+    assert list(store.chunk_off) == OFF
+    for t, v in COV_AT[seed].items():
+        store.cov[t] = store.mapq[t] = v
+        store.clip[t] = 0
+    if len(regions) > 1:                                    # a region change exactly on the grid points 512 and 1024
+        reg = store.regions().astype(np.uint64)
+        reg[[511, 1023]], reg[[512, 1024]] = 0, 1
+        store.annot = (store.annot & np.uint64((1 << 58) - 1)) | (reg << np.uint64(58))
+    ctg = list(store.chunk_ctg)
+    for c in JOINED:                                        # a joined chunk lies on its predecessor's contig
+        ctg[c] = ctg[c - 1]
+    store.chunk_ctg = ctg
+    model = perturbed_model(store, model_type, 2 + seed % 3, alpha, rng)
+    F, L = np.meshgrid(POINTS, POINTS, indexing="ij")
+    keep = F <= L
+    F, L = F[keep], L[keep]
+    M = np.random.default_rng(9202 + seed).integers(1, 16, F.size)     # (a generator of its own: the full mask in at least 50 jobs)
+    R = np.random.default_rng(9150 + seed).integers(-1, len(regions), F.size)
+    for a in (F, L, M, R):
+        a.setflags(write=False)
+    return store, model, alpha, (F, L, M, R)
+
+
+@functools.lru_cache(maxsize=None)
+def rows(model_type, seed):
+    store, model, alpha, _ = case(model_type, seed)
+    return S.rows(store, model, alpha)
+
+
+def pieces_of(off, first, last):
+    """(parts, pieces) of every job as the getters cut it: a part per chunk the job touches, and per part the 512-blocks of the global
+    grid that intersect its interior windows (a, b]."""
+    off = np.asarray(off, np.int64)
+    first, last = np.asarray(first, np.int64), np.asarray(last, np.int64)
+    parts, pieces = np.zeros(first.size, np.int64), np.zeros(first.size, np.int64)
+    for c in range(off.size - 1):
+        if off[c + 1] <= off[c]:
+            continue
+        a, b = np.maximum(first, off[c]), np.minimum(last, off[c + 1] - 1)
+        hit = a <= b
+        parts += hit
+        pieces += np.where(hit & (b > a), b // PIECE - (a + 1) // PIECE + 1, 0)
+    return parts, pieces
+
+
+# ---- the references, each once per case ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def interval_reference(model_type, seed):
+    _, _, _, (F, L, M, _) = case(model_type, seed)
+    A, end = rows(model_type, seed)
+    return IR.log_probs(A, end, OFF, F, L, M)
+
+
+@functools.lru_cache(maxsize=None)
+def long_double(model_type, seed):
+    A, end = rows(model_type, seed)
+    return ER.LongDouble(A, end, np.asarray(OFF, np.int64))
+
+
+@functools.lru_cache(maxsize=None)
+def entropy_reference(model_type, seed):
+    _, _, _, (F, L, _, _) = case(model_type, seed)
+    return long_double(model_type, seed).entropy(F, L)
+
+
+@functools.lru_cache(maxsize=None)
+def labellings(model_type, seed):
+    A, end = rows(model_type, seed)
+    return ER.labellings(A, end, np.asarray(OFF, np.int64), 70 + seed)
+
+
+@functools.lru_cache(maxsize=None)
+def log_prob_reference(model_type, seed):
+    """[(name, labels, log-probability of every job)]"""
+    _, _, _, (F, L, _, _) = case(model_type, seed)
+    ld = long_double(model_type, seed)
+    return [(name, y, ld.log_probs(F, L, y)) for name, y in labellings(model_type, seed)]
+
+
+@functools.lru_cache(maxsize=None)
+def count_reference(model_type, seed, unit):
+    store, _, _, (F, L, M, R) = case(model_type, seed)
+    A, end = rows(model_type, seed)
+    return MR.moments_long(A, end, OFF, MR.weights(store, unit), store.regions().astype(np.int64), F, L, M, R)
+
+
+def joins_key(j):
+    return None if j is None else tuple(bool(x) for x in j)
+
+
+@functools.lru_cache(maxsize=None)
+def run_reference(model_type, seed, joined_key):
+    """(mean, var, scale) with the joins of joined_key (a tuple, or None)."""
+    _, _, _, (F, L, M, _) = case(model_type, seed)
+    A, end = rows(model_type, seed)
+    return RR.jet_long(A, end, OFF, F, L, M, None if joined_key is None else np.array(joined_key, bool))
+
+
+@functools.lru_cache(maxsize=None)
+def pass_reference(model_type, seed):
+    """(posterior [N][4], chunk log-likelihoods [C], marg [N], cond [N])"""
+    store, model, _, _ = case(model_type, seed)
+    A, end = rows(model_type, seed)
+    post, _, ll = PR.forward_backward(A, end, OFF, PR.regions_of(store), model.numberOfRegions)
+    marg, cond = ER.profile(A, end, OFF)
+    return post, ll, marg, cond
+
+
+@functools.lru_cache(maxsize=None)
+def viterbi_reference(model_type, seed):
+    store, model, alpha, _ = case(model_type, seed)
+    return viterbi_ref.reference(store, model, alpha)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_reference(model_type, seed):
+    A, end = rows(model_type, seed)
+    return S.ffbs(A, end, OFF, SAMPLE_SEED + seed, range(SAMPLES))
+
+
+# ---- the variants --------------------------------------------------------------------------------------------------------------------
+# chunks without windows, as positions in the grid store's chunk list they are put in front of (13: behind the last chunk): first, last,
+# two in a row in the middle, one between the joined chunks 5 and 6
+EMPTY_BEFORE = (0, 6, 11, 11, 13)
+
+
+def with_empty_chunks(store):
+    """(the store with chunks without windows put in, for every chunk of it the chunk of `store` it is or -1).  No window moves."""
+    src = []
+    for c in range(store.n_chunks + 1):
+        src += [-1] * EMPTY_BEFORE.count(c)
+        if c < store.n_chunks:
+            src.append(c)
+    src = np.array(src)
+    near = np.where(src >= 0, src, 0)                       # (an empty chunk: a contig of its own, no bases)
+    off, t = [0], 0
+    for s in src:
+        t += int(store.chunk_off[s + 1] - store.chunk_off[s]) if s >= 0 else 0
+        off.append(t)
+    ctg = [store.chunk_ctg[s] if s >= 0 else "empty_%d" % k for k, s in enumerate(src)]
+    st = dataclasses.replace(store, chunk_off=np.asarray(off, np.int64), chunk_ctg=ctg, chunk_ctg_len=store.chunk_ctg_len[near].copy(),
+                             chunk_s=np.where(src >= 0, store.chunk_s[near], 0).astype(np.int32),
+                             chunk_e=np.where(src >= 0, store.chunk_e[near], 0).astype(np.int32))
+    assert st.n_windows == store.n_windows and st.n_chunks == store.n_chunks + len(EMPTY_BEFORE)
+    return st, src
+
+
+def empty_chunk_joins(src, j):
+    """(joined over the chunks of with_empty_chunks: every chunk without windows and its successor marked as continuing, joined over
+    the chunks of the store it was made from as the getter must read that: a chunk without windows ends a run of joined chunks)."""
+    dev = np.zeros(src.size, bool)
+    ref = np.array(j, bool)
+    for k, s in enumerate(src):
+        if s >= 0:
+            dev[k] = j[s] or (k > 0 and src[k - 1] < 0 and s > 0)
+            if k > 0 and src[k - 1] < 0:
+                ref[s] = False
+        else:
+            dev[k] = k > 0
+    dev[0] = False
+    return dev, ref
+
+
+FRONT, BEHIND = 5, 7                 # windows in no chunk, before the first chunk and behind the last one
+
+
+@dataclasses.dataclass
+class UncoveredStore(synth.WindowStore):
+    """A store whose window arrays hold windows that lie in no chunk: chunk_off[0] > 0 and chunk_off[-1] < n_windows."""
+    total: int = 0
+
+    @property
+    def n_windows(self) -> int:
+        return self.total
+
+
+def with_uncovered_windows(store, rng):
+    """The store with FRONT windows in front of its first chunk and BEHIND windows behind its last one (random values in them)."""
+    n = store.n_windows + FRONT + BEHIND
+    def pad(a, hi):
+        a = np.asarray(a)
+        return np.concatenate([rng.integers(0, hi, FRONT).astype(a.dtype), a, rng.integers(0, hi, BEHIND).astype(a.dtype)])
+    fields = {f.name: getattr(store, f.name) for f in dataclasses.fields(store)}
+    fields.update(cov=pad(store.cov, 70), mapq=pad(store.mapq, 70), clip=pad(store.clip, 70),
+                  annot=np.concatenate([store.annot[:1].repeat(FRONT), store.annot, store.annot[-1:].repeat(BEHIND)]),
+                  truth=pad(store.truth, 1), prediction=pad(store.prediction, 1),
+                  chunk_off=np.asarray(store.chunk_off, np.int64) + FRONT)
+    return UncoveredStore(**fields, total=n)

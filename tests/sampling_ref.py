@@ -96,13 +96,14 @@ def forward(A, chunk_off):
     return W, Cm, alast
 
 
-def ffbs(A, end, chunk_off, seed, ks, fwd=None):
+def ffbs(A, end, chunk_off, seed, ks, fwd=None, n_windows=None):
     """Samples `ks` (absolute indices), vectorised over samples and chunks: (labels int8[K][N], window margins float32[K][N] (0 at
-    chunk-first windows), final margins float32[K][C])."""
+    chunk-first windows), final margins float32[K][C]).  n_windows: the track's window count where it is not chunk_off[-1] (windows
+    outside every chunk: their labels stay 0 here); the final-state draw of chunk c takes uniform n_windows + c."""
     off = np.asarray(chunk_off, np.int64)
     T = np.diff(off)
     C_ = T.size
-    n = int(off[-1])
+    n = int(off[-1]) if n_windows is None else int(n_windows)
     W, Cm, alast = forward(A, off) if fwd is None else fwd
     keys = np.array([sample_key(seed, k) for k in ks], np.uint64)
     K = keys.size

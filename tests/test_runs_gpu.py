@@ -9,8 +9,9 @@ tests/test_runs_cpu.py::test_centred_float64_against_the_long_double_jet (the hu
 differently rounded rows and posterior); under the standing 1e-9.  scale is the reference variance; with joins the variance is a sum of
 terms of both signs, and scale is the sum of the absolute values of the stitching formula's terms (runs_ref.stitch).
 A mean: |dev - ref| <= 1e-12 + 1e-9 |ref|, the posterior tests' bound.
-Every test prints its largest absolute and relative deviations before it asserts (pytest -s); the values measured on an MI355X are
-not recorded here yet (DESIGN.md section 7g says the same)."""
+Every test prints its largest absolute and relative deviations before it asserts (pytest -s).  Measured on an MI355X (both algorithms,
+apart and joined): tiny stores 2.5e-14 runs^2 absolute, 9.4e-13 of the scale (the other two stores 1.6e-13 and 9.4e-14), means 1.2e-14
+relative; reduced configs, as they are and with their chunks cut, 5.7e-14 absolute, 8.6e-14 of the scale, means 5.8e-15 relative."""
 import ctypes as C
 import functools
 import math
