@@ -1503,6 +1503,15 @@ static int flags_to_code(unsigned fl) {
     return HF_OK;
 }
 
+// the flag word of a PASS, as hf_finish / hf_check report it: a pass that failed leaves nothing for the getters to answer for (they
+// return HF_E_ARG until the next full pass, as hf_get_sample_labels does after a failed hf_sample_paths) — its labels, records and
+// vectors are whatever the NaN or the underflow left
+static int pass_flags_to_code(Pass& ps, unsigned fl) {
+    const int code = flags_to_code(fl);
+    if (code != HF_OK) ps.have_full = false;
+    return code;
+}
+
 // the one-launch segment kernel gave up a wait (flag word `fl`): this pass runs two launches from now on, and the caller repeats the pass
 static bool sync_fallback(Pass& ps, unsigned fl) {
     if (!(fl & HF_FLAG_SYNC) || !ps.seg_fused) return false;
@@ -1521,7 +1530,7 @@ int hf_check(hf_ctx* ctx, void* stream) {
     accumulate_kernel_times(ps);
     if (sync_fallback(ps, *ps.h_flags))   // as hf_finish
         return set_err(HF_E_RETRY, "a hand-off of the one-launch segment kernel timed out: the context now runs two launches, repeat hf_estep");
-    return flags_to_code(*ps.h_flags);
+    return pass_flags_to_code(ps, *ps.h_flags);
 }
 
 // Completion of a pass.  Default: hipStreamSynchronize on the launch stream — the HIP-defined way to see the statistics
@@ -1663,7 +1672,7 @@ static int wait_total(Pass& ps, hipStream_t st, bool polled, double* stats_host,
             if (host_total) host_rows_total(ps);
             std::memcpy(stats_host, ps.h_total, (size_t) tr.V * 8);
             const unsigned fl2 = (unsigned) ps.h_total[tr.V];
-            return sync_fallback(ps, fl2) ? HF_E_RETRY : flags_to_code(fl2);
+            return sync_fallback(ps, fl2) ? HF_E_RETRY : pass_flags_to_code(ps, fl2);
         }
     }
     if (!seen) {
@@ -1688,7 +1697,7 @@ static int wait_total(Pass& ps, hipStream_t st, bool polled, double* stats_host,
     if (host_total) host_rows_total(ps);
     std::memcpy(stats_host, ps.h_total, (size_t) tr.V * 8);
     const unsigned fl = (unsigned) ps.h_total[tr.V];
-    return sync_fallback(ps, fl) ? HF_E_RETRY : flags_to_code(fl);
+    return sync_fallback(ps, fl) ? HF_E_RETRY : pass_flags_to_code(ps, fl);
 }
 
 static int pass_finish(Pass& ps, double* stats_host, void* stream) {

@@ -127,7 +127,10 @@ int hf_create(const hf_windows *w, int n_regions, int max_comps, int device, int
 void hf_destroy(hf_ctx *ctx);
 
 /* Launch one E-step pass over every chunk of this context on `stream` (a hipStream_t, NULL =
- * default stream); asynchronous.  Leaves one statistics vector PER CHUNK on the device. */
+ * default stream); asynchronous.  Leaves one statistics vector PER CHUNK on the device.
+ * Streams (DESIGN.md "Streams", tests/test_streams_gpu.py): `stream` may be any stream of the caller's on the context's device, a
+ * non-blocking one included; everything the pass reads and writes is ordered on it.  The stream of the LAST hf_estep is the stream
+ * every getter of the context runs on; it must outlive the context (hf_destroy first, then hipStreamDestroy). */
 int hf_estep(hf_ctx *ctx, const hf_params *p, int mode, void *stream);
 
 int32_t hf_n_chunks(const hf_ctx *ctx);
@@ -173,12 +176,15 @@ int hf_bind_rank_total(hf_ctx *ctx, double *total_dev, double *flag_row_dev);
 int hf_write_flag_row(hf_ctx *ctx, double *row_dev, void *stream);
 
 /* Single-GPU convenience: reduce this context's chunks, copy the vector to `stats_host`,
- * wait for the stream and translate the device error flags (HF_E_SCALE / HF_E_NAN / ...). */
+ * wait for the stream and translate the device error flags (HF_E_SCALE / HF_E_NAN / ...).  Blocks the host until `stream` (the
+ * stream of the hf_estep it completes) has drained.  A pass whose flags report an error leaves nothing to get: every getter of the
+ * pass's results returns HF_E_ARG until the next HF_MODE_FULL pass (hf_check likewise). */
 /* (hf_finish synchronises the stream.  Environment HF_POLL=1 opts into polling a checksummed completion stamp in the
  * pinned result block instead — a few microseconds less per pass, see hf_estep.hip — HF_POLL=debug verifies it.) */
 int hf_finish(hf_ctx *ctx, double *stats_host, void *stream);
 /* Only wait + error flags (multi-GPU callers reduce the gathered vectors themselves).  HF_E_RETRY: a hand-off of the one-launch
- * segment kernel timed out; the context has switched to two launches and the caller repeats the pass from hf_estep. */
+ * segment kernel timed out; the context has switched to two launches and the caller repeats the pass from hf_estep.  Blocks the
+ * host until `stream` has drained, as hf_finish does. */
 int hf_check(hf_ctx *ctx, void *stream);
 
 /* How a HF_MODE_FULL pass of HF_ALGO_SCAN produces the statistics:
@@ -198,7 +204,8 @@ enum { HF_STATS_CHUNKS = 0, HF_STATS_ROWS = 1 };
 int hf_set_stats_mode(hf_ctx *ctx, int mode);
 /* The statistics vector of THIS context's chunks after a pass, in either mode, into device memory (hf_chunk_stats_len
  * doubles): what ranks exchange when the per-chunk vectors are not needed — all-gather one vector per rank, then
- * hf_finish_gathered(rows = the gathered vectors, row_index = NULL, n = world size) sums them in rank order. */
+ * hf_finish_gathered(rows = the gathered vectors, row_index = NULL, n = world size) sums them in rank order.  Asynchronous on
+ * `stream`, after the pass. */
 int hf_rank_total(hf_ctx *ctx, double *out_dev, void *stream);
 int hf_get_stats_mode(const hf_ctx *ctx);          /* the mode the NEXT full pass will use */
 /* Launches of the segment forward-backward in the NEXT pass: 1 = k_seg_fb alone (its segments hand their products over inside the
@@ -227,9 +234,14 @@ int64_t hf_seg_block_table(const hf_ctx *ctx, int32_t *seg_of_block, int64_t n);
 int hf_create_phases(const hf_ctx *ctx, int max, double *ms, const char **names);
 
 /* Results of the last HF_MODE_FULL pass (HF_E_ARG when the last pass was HF_MODE_FORWARD_ONLY: f and scales would be new,
- * b and the labels stale).  hf_get_posterior / hf_get_forward_backward: an EM pass of the default algorithm keeps no per-window scale (and,
+ * b and the labels stale; HF_E_ARG also once hf_finish / hf_check — hf_finish_gathered / hf_finish_exchange, hf_batch_finish for the
+ * model's status — have reported an error of the pass (HF_E_NAN, HF_E_SCALE, ...): its labels and vectors are what the NaN or the
+ * underflow left; the same holds for every getter below that answers "under the model of the last HF_MODE_FULL pass" and for
+ * hf_batch_get_labels / hf_batch_get_posterior of a model whose status was an error).  hf_get_posterior / hf_get_forward_backward: an EM pass of the default algorithm keeps no per-window scale (and,
  * in several sub-passes, only the last sub-pass's records) — the first call after a pass runs the segment kernel once more over the pass's
- * tables, with the scale array (~0.05 ms per 1.5 M windows; the array itself is allocated by that first call); same values as the pass. */
+ * tables, with the scale array (~0.05 ms per 1.5 M windows; the array itself is allocated by that first call); same values as the pass.
+ * No stream argument: the three run on the stream of the last hf_estep, behind the pass, and block the host until their result is
+ * there — whatever else the caller has enqueued on that stream first is waited for too. */
 int hf_get_labels(hf_ctx *ctx, int8_t *labels_host);                                   /* hmm.c:730-736 */
 int hf_get_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_host);        /* [n][4] hmm.c:671-685 */
 int hf_get_forward_backward(hf_ctx *ctx, int64_t first, int64_t n, double *f_host, double *b_host,
@@ -372,7 +384,9 @@ int hf_get_alpha_stats(hf_ctx *ctx, double *out_host);
  * run's score the sum over chunks in list order.  HF_E_SCALE when no path of a chunk has weight, HF_E_NAN on a NaN.
  * Decoding uses buffers of its own: the last pass's results (hf_get_labels / _posterior / _forward_backward) and the next hf_estep
  * are unaffected.  hf_viterbi is asynchronous on `stream`; hf_viterbi_finish waits, translates the error flags and returns the run's
- * score.  The getters answer for the last FINISHED run (HF_E_ARG before any). */
+ * score.  The getters answer for the last FINISHED run (HF_E_ARG before any).
+ * `stream` need not be the stream of the last pass (a second stream of the caller's decodes while the first is busy); hf_viterbi_finish
+ * takes the stream hf_viterbi ran on.  The getters have no stream argument: they copy a finished run's results, synchronously. */
 int hf_viterbi(hf_ctx *ctx, const hf_params *p, void *stream);
 int hf_viterbi_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_labels(hf_ctx *ctx, int8_t *labels_host);                          /* [n_windows], layout of hf_labels_dev */
@@ -394,7 +408,7 @@ int hf_get_viterbi_chunk_log_probs(hf_ctx *ctx, double *out_host);              
  * translates the flags (HF_E_NAN: a NaN in a row or the end column, HF_E_SCALE: a chunk's forward vector or final weights all 0).
  * HF_E_ARG: n_samples < 1 or above hf_sample_capacity (samples per call that fit nine tenths of the free device memory), k out of
  * range, a getter before any finished call.  The sampler's buffers are its own: the last pass's results, Viterbi's and the next
- * hf_estep are unaffected. */
+ * hf_estep are unaffected.  Streams: as hf_viterbi (any stream of the caller's; hf_sample_finish takes the same one). */
 int hf_sample_capacity(const hf_ctx *ctx);
 int hf_sample_paths(hf_ctx *ctx, const hf_params *p, int64_t first_sample, int n_samples, uint64_t seed, void *stream);
 int hf_sample_finish(hf_ctx *ctx, void *stream);
@@ -420,7 +434,9 @@ int hf_get_sample_labels(hf_ctx *ctx, int k, int8_t *labels_host);              
  *   hf_batch_finish     waits for the models of the last hf_batch_estep: stats_host[i][hf_chunk_stats_len] and status[i] (HF_OK,
  *                       HF_E_SCALE, HF_E_NAN, ...) for models[i].  A model's own failure is its status only; the call returns HF_OK
  *                       unless the runtime or an argument failed.  A timed-out hand-off (HF_E_RETRY) re-runs that model's pass inside.
- *   hf_batch_get_labels / hf_batch_get_posterior: as hf_get_labels / hf_get_posterior, for the last finished pass of `model` */
+ *   hf_batch_get_labels / hf_batch_get_posterior: as hf_get_labels / hf_get_posterior, for the last finished pass of `model`
+ * Streams: hf_batch_estep is asynchronous on `stream` (any stream of the caller's, as hf_estep), hf_batch_finish blocks until that
+ * stream has drained; the two getters run on the stream of the model's last pass and block until their result is there. */
 #define HF_BATCH_MAX_MODELS 1024
 typedef struct hf_batch hf_batch;
 int hf_batch_capacity(const hf_ctx *ctx);

@@ -1,0 +1,707 @@
+"""The C ABI on caller-owned streams and in mixed call orders (DESIGN.md "Streams").
+
+Every entry point that enqueues GPU work takes a `void *stream`; the getters run on the stream of the last pass.  Here the stream is a
+non-blocking one of the caller's (tests/hip_streams.py), and directly in front of every library call the caller enqueues filler work on
+it, so that whatever the library does on the null stream instead, or reads on the host without waiting for the stream, runs ahead of the
+stream's work and sees stale data.  Right after an entry point that is asynchronous by contract has returned, hipStreamQuery must still
+say hipErrorNotReady: the filler was long enough to matter.
+
+Every comparison is BITWISE (np.array_equal, equal return codes) against a twin that makes the same calls on stream 0 without filler:
+the library promises bitwise reproducibility, so there is no tolerance."""
+import ctypes as C
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from flagger_amd import _native as N
+from flagger_amd import hmm, synth
+import hip_streams as HS
+import stream_sequences as SQ
+from test_posterior_gpu import _ranges, _regions_store, _sizes_store
+
+pytestmark = pytest.mark.gpu
+
+TEG, NB = N.HF_MODEL_TRUNC_EXP_GAUSSIAN, N.HF_MODEL_NEGATIVE_BINOMIAL
+# name -> (store, model type, components, alpha, minReadFractionAtEnds)
+INPUTS = {
+    "config2": (lambda: synth.config(2, 0.03), TEG, 4, synth.HIFI_ALPHA, 0.95),
+    "sizes": (_sizes_store, TEG, 3, synth.HIFI_ALPHA, 0.95),           # chunks of 1, 2, 63, 64, 65, 511, 512, 513, 4097 and 13 000 windows
+    "regions": (_regions_store, TEG, 6, synth.ONT_R10_ALPHA, 0.8),     # 7 regions
+    "negative_binomial": (lambda: synth.config(2, 0.03), NB, 4, np.zeros((4, 4)), 0.95),
+}
+# name -> (algorithm, statistics mode, environment)
+KINDS = {
+    "seq": (N.HF_ALGO_SEQ, None, {}),
+    "scan-rows": (N.HF_ALGO_SCAN, N.HF_STATS_ROWS, {}),
+    "scan-chunks": (N.HF_ALGO_SCAN, N.HF_STATS_CHUNKS, {}),
+    # the contexts whose getters run the segment kernel again, into a buffer allocated on first use
+    "scan-rows-2-launches": (N.HF_ALGO_SCAN, N.HF_STATS_ROWS, {"HF_SEG_LAUNCHES": "2"}),
+    "scan-rows-3-sub-passes": (N.HF_ALGO_SCAN, N.HF_STATS_ROWS, {"HF_SUBPASSES": "3"}),
+    "scan-chunks-3-sub-passes": (N.HF_ALGO_SCAN, N.HF_STATS_CHUNKS, {"HF_SUBPASSES": "3"}),
+}
+GETTERS = SQ.GETTERS
+SAMPLES, SAMPLE_SEED = 8, 20261019
+
+
+class Jobs:
+    """The arguments of the getters for one store: whole-track ranges, and sub-ranges across a chunk border and across a 512-window
+    border inside the longest chunk (the segment length of the scan path)."""
+
+    def __init__(self, store):
+        off = np.asarray(store.chunk_off, np.int64)
+        n = int(off[-1])
+        assert off[0] == 0 and n == store.n_windows
+        T = np.diff(off)
+        c = int(np.argmax(T))
+        border = int(off[1 + int(np.argmax(T[:-1] > 0))])
+        rng = np.random.default_rng(5)
+        a = rng.integers(0, n, 12)
+        b = np.minimum(n - 1, a + rng.integers(0, 1500, 12))
+        F = [0, max(border - 3, 0), border - 1, 0, n - 1, int(off[c])]
+        L = [n - 1, min(border + 3, n - 1), border, 0, n - 1, int(off[c + 1]) - 1]
+        assert T[c] > 520                                                                   # (regions: 932 windows in the longest chunk)
+        F += [int(off[c]) + 500, int(off[c]) + 511, int(off[c]) + 3]
+        L += [int(off[c]) + 520, int(off[c]) + 512, int(off[c]) + min(1100, int(T[c]) - 1)]
+        self.n = n
+        self.F = np.concatenate([np.asarray(F, np.int64), a])
+        self.L = np.concatenate([np.asarray(L, np.int64), b])
+        assert np.all(self.F <= self.L)
+        self.M = (1 + (np.arange(self.F.size) % 15)).astype(np.int64)
+        self.y = np.where(rng.random(n) < 0.95, 2, rng.integers(0, 4, n)).astype(np.int8)
+        self.ranges = [(0, n)] + _ranges(store)
+        assert any(a0 < border < a0 + cnt for a0, cnt in self.ranges)                      # across a chunk border
+        assert any(a0 < int(off[c]) + 512 < a0 + cnt <= int(off[c + 1]) for a0, cnt in self.ranges[1:])   # across a 512-window border
+
+
+@functools.lru_cache(maxsize=None)
+def _input(name):
+    """(store, model type, K, alpha, frac, parameters A, parameters B, jobs): B is A after one M-step, so the two models' tables, labels
+    and posteriors differ."""
+    make, mt, K, alpha, frac = INPUTS[name]
+    store = make()
+    model = hmm.createModel(mt, K, store, alpha)
+    va = model.param_vector().copy()
+    em = hmm.EMList(store, model, True, frac)
+    hmm.EM_runOneIterationForList(em, model)
+    la = em.labels()
+    hmm.HMM_estimateParameters(model, 1e-3)
+    hmm.HMM_resetEstimators(model)
+    vb = model.param_vector().copy()
+    hmm.EM_runOneIterationForList(em, model)
+    assert not np.array_equal(la, em.labels())                 # a getter that answers for the other pass is told apart
+    em.close()
+    assert not np.array_equal(va, vb)
+    return store, mt, K, alpha, frac, va, vb, Jobs(store)
+
+
+def _model(name, which):
+    store, mt, K, alpha, frac, va, vb, _ = _input(name)
+    model = hmm.createModel(mt, K, store, alpha)
+    model.set_param_vector(vb if which == "b" else va)
+    return model
+
+
+def _call(fn, *args, **kw):
+    """(return code, results) of a wrapper of flagger_amd.hmm: the code of the HFError it raises, or HF_OK and copies of what it returns."""
+    try:
+        out = fn(*args, **kw)
+    except N.HFError as e:
+        assert e.code != N.HF_OK
+        return int(e.code), ()
+    if out is None:
+        return N.HF_OK, ()
+    return N.HF_OK, tuple(np.array(x, copy=True) for x in (out if isinstance(out, tuple) else (out,)))
+
+
+def _getter_calls(em, kind, J):
+    """The calls of one getter operation: [(code, arrays)], the whole track first, then the sub-ranges."""
+    if kind == "labels":
+        return [_call(em.labels)]
+    if kind == "posterior":
+        return [_call(em.posterior, a, c) for a, c in J.ranges]
+    if kind == "forward_backward":
+        return [_call(em.forward_backward, a, c) for a, c in J.ranges]
+    if kind == "interval_log_probs":
+        return [_call(em.interval_log_probs, J.F, J.L, J.M)]
+    if kind == "count_moments":
+        return [_call(em.count_moments, J.F, J.L, J.M), _call(em.count_moments, J.F[:4], J.L[:4], J.M[:4], unit="bases")]
+    if kind == "run_moments":
+        return [_call(em.run_moments, J.F, J.L, J.M)]
+    if kind == "path_entropy":
+        return [_call(em.path_entropy, J.F, J.L)]
+    if kind == "path_log_probs":
+        return [_call(em.path_log_probs, J.F, J.L, J.y)]
+    if kind == "entropy_profile":
+        return [_call(em.entropy_profile, a, c) for a, c in J.ranges]
+    if kind == "alpha_stats":
+        return [_call(em.alpha_stats)]
+    raise KeyError(kind)
+
+
+def _equal(a, b, what):
+    """Two records [(code, arrays)] of the same calls: equal codes, bitwise equal arrays."""
+    assert len(a) == len(b), what
+    for i, ((ca, xa), (cb, xb)) in enumerate(zip(a, b)):
+        assert ca == cb, (what, i, ca, cb)
+        assert len(xa) == len(xb), (what, i)
+        for k, (x, y) in enumerate(zip(xa, xb)):
+            assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), \
+                (what, "call %d, array %d" % (i, k), int(np.sum(x != y)) if x.shape == y.shape else (x.shape, y.shape))
+
+
+def _codes(calls):
+    return [c for c, _ in calls]
+
+
+class Side:
+    """One side of a comparison: the caller's streams with filler in front of every call and the busy-stream assertions, or (streams all
+    0) the twin on the null stream without either.  Contexts made through it are closed before its streams go."""
+
+    def __init__(self, name, kind, streams, non_blocking=True):
+        self.name, self.kind, self.streams, self.non_blocking = name, kind, list(streams), non_blocking
+        self.store, self.mt, self.K, self.alpha, self.frac, _, _, self.J = _input(name)
+        self.h = HS.hip()
+        self.contexts = []
+        self.busy_checked = 0
+
+    @property
+    def stream(self):
+        return self.streams[0]
+
+    def delay(self, s=None):
+        self.h.delay(self.stream if s is None else s)
+
+    def assert_busy(self, s, what):
+        """The stream still has work when an asynchronous entry point has returned: the filler outlasted the call's host side."""
+        if s and self.non_blocking:            # (a null-stream operation inside the call waits for a blocking stream: no hazard, and no claim)
+            assert self.h.stream_query(s) == HS.hipErrorNotReady, "%s returned with its stream idle: the filler is too short, or the call blocked" % what
+            self.busy_checked += 1
+
+    def context(self, stream=None, model=None, alpha_stats=False):
+        algo, mode, env = KINDS[self.kind]
+        s = self.stream if stream is None else stream
+        em = hmm.EMList(self.store, model or _model(self.name, "a"), True, self.frac, algo=algo, stream=s)
+        self.contexts.append(em)
+        if algo == N.HF_ALGO_SCAN:
+            assert em.seg_launches == int(env.get("HF_SEG_LAUNCHES", 1)) and em.sub_passes == int(env.get("HF_SUBPASSES", 1))
+            em.set_stats_mode(mode)
+        if alpha_stats and self.mt != NB:
+            em.set_alpha_stats(True)
+        return em
+
+    def close(self):
+        for em in self.contexts:
+            em.close()
+        self.contexts = []
+
+    # --- the calls, each behind a delay -------------------------------------------------------------------------------------
+    def estep(self, em, model, mode=N.HF_MODE_FULL):
+        """hf_estep + hf_finish: (code, (statistics,))."""
+        s = em.stream.value or 0
+        self.delay(s)
+        code, _ = _call(em.launch, model, mode)
+        if code != N.HF_OK:
+            return code, ()
+        self.assert_busy(s, "hf_estep")
+        return self.finish(em)
+
+    def finish(self, em):
+        self.delay(em.stream.value or 0)
+        return _call(em.finish)
+
+    def getter(self, em, kind):
+        self.delay(em.stream.value or 0)
+        return _getter_calls(em, kind, self.J)
+
+    def viterbi(self, em, model, s=None):
+        """hf_viterbi + hf_viterbi_finish on stream `s` (default: the context's) and its getters: (code, (labels, chunk scores, score))."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        p, lp = model.params(), C.c_double(0.0)
+        self.delay(s)
+        rc = L.hf_viterbi(em._h, C.byref(p), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.assert_busy(s, "hf_viterbi")
+        rc = L.hf_viterbi_finish(em._h, C.byref(lp), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        self.delay(s)
+        r1 = L.hf_get_viterbi_labels(em._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
+        r2 = L.hf_get_viterbi_chunk_log_probs(em._h, ll.ctypes.data_as(C.POINTER(C.c_double)))
+        assert r1 == N.HF_OK and r2 == N.HF_OK
+        return N.HF_OK, (labels, ll, np.float64(lp.value))
+
+    def sample(self, em, model, s=None, n=SAMPLES, seed=SAMPLE_SEED):
+        """hf_sample_paths + hf_sample_finish on stream `s` and the samples' labels: (code, (int8[n][n_windows],))."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        assert em.sample_capacity >= n
+        p = model.params()
+        self.delay(s)
+        rc = L.hf_sample_paths(em._h, C.byref(p), 0, n, seed, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.assert_busy(s, "hf_sample_paths")
+        rc = L.hf_sample_finish(em._h, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        out = np.empty((n, self.store.n_windows), dtype=np.int8)
+        self.delay(s)
+        for k in range(n):
+            assert L.hf_get_sample_labels(em._h, k, out[k].ctypes.data_as(C.POINTER(C.c_int8))) == N.HF_OK
+        return N.HF_OK, (out,)
+
+
+def _run_both(name, kind, monkeypatch, scenario, n_streams=1, non_blocking=True):
+    """`scenario(side)` -> {tag: [(code, arrays)]} on the caller's streams and on the null stream: the two records are equal.  Returns the
+    record of the streams' side."""
+    for k, v in KINDS[kind][2].items():
+        monkeypatch.setenv(k, v)
+    _input(name)
+    recs = []
+    with HS.Streams() as streams:
+        for which in ("streams", "twin"):
+            side = Side(name, kind, [streams.new(non_blocking) if which == "streams" else 0 for _ in range(n_streams)], non_blocking)
+            try:
+                recs.append(scenario(side))
+            finally:
+                side.close()
+    got, twin = recs
+    assert list(got) == list(twin)
+    for tag in got:
+        _equal(got[tag], twin[tag], "%s / %s / %s" % (name, kind, tag))
+    return got
+
+
+CASES = [pytest.param(n, k, id="%s-%s" % (n, k)) for n in INPUTS for k in KINDS]
+ON_CONFIG2 = [pytest.param("config2", k, id=k) for k in KINDS]
+
+
+# ---- a. the pass -------------------------------------------------------------------------------------------------------------------
+def _pass_scenario(side):
+    ma, mb = _model(side.name, "a"), _model(side.name, "b")
+    em = side.context()
+    rec = {}
+    rec["full a"] = [side.estep(em, ma)]
+    side.delay()
+    rec["labels a"] = [_call(em.labels)]
+    rec["full b"] = [side.estep(em, mb)]                         # must not see a's parameter block or tables
+    side.delay()
+    rec["labels b"] = [_call(em.labels)]
+    # two passes back to back: hf_estep(a), hf_estep(b), then one hf_finish — b is enqueued while a's parameter upload and tables still
+    # wait behind the filler (the pinned parameter block is packed again under a pending copy): b's results must be b's
+    side.delay()
+    c1, _ = _call(em.launch, ma, N.HF_MODE_FULL)
+    c2, _ = _call(em.launch, mb, N.HF_MODE_FULL)
+    side.assert_busy(side.stream, "hf_estep")
+    rec["a then b, back to back"] = [(c1, ()), (c2, ()), side.finish(em)]
+    side.delay()
+    rec["labels b, back to back"] = [_call(em.labels)]
+    rec["forward a"] = [side.estep(em, ma, N.HF_MODE_FORWARD_ONLY)]
+    rec["forward b"] = [side.estep(em, mb, N.HF_MODE_FORWARD_ONLY)]
+    # hf_estep + hf_check (what the multi-GPU path of flagger_amd/dist.py calls), then the statistics through hf_finish
+    side.delay()
+    code, _ = _call(em.launch, ma, N.HF_MODE_FULL)
+    side.assert_busy(side.stream, "hf_estep")
+    side.delay()
+    rec["check a"] = [(code, ()), _call(em.check), _call(em.finish)]
+    # hf_em_iterate: two iterations, the model moves in between
+    mi = _model(side.name, "a")
+    it = []
+    for _ in range(2):
+        side.delay()
+        code, out = _call(em.em_iterate, mi, True, 1e-3)
+        it.append((code, out + (mi.estimators.copy(), mi.param_vector().copy(), np.float64(mi.loglikelihood))))
+    rec["em_iterate"] = it
+    side.delay()
+    rec["labels after em_iterate"] = [_call(em.labels)]
+    return rec
+
+
+def _check_pass_record(rec):
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls)), {t: _codes(c) for t, c in rec.items()}
+    sa, sb = rec["full a"][0][1][0], rec["full b"][0][1][0]
+    assert not np.array_equal(sa, sb) and not np.array_equal(rec["labels a"][0][1][0], rec["labels b"][0][1][0])
+    assert rec["forward a"][0][1][0][0] != rec["forward b"][0][1][0][0]                               # the log-likelihoods
+    assert np.array_equal(rec["check a"][2][1][0], sa)
+    assert np.array_equal(rec["a then b, back to back"][2][1][0], sb)
+    _equal(rec["labels b, back to back"], rec["labels b"], "labels of b enqueued right behind a")
+    assert np.array_equal(rec["em_iterate"][0][1][1], sa)
+
+
+@pytest.mark.parametrize("name,kind", CASES)
+def test_pass_on_a_non_blocking_stream(name, kind, monkeypatch):
+    _check_pass_record(_run_both(name, kind, monkeypatch, _pass_scenario))
+
+
+@pytest.mark.parametrize("name,kind", ON_CONFIG2)
+def test_pass_on_a_blocking_stream(name, kind, monkeypatch):
+    """The same on a stream created with the default flags (the null stream waits for it, so nothing can run ahead: the values only)."""
+    _check_pass_record(_run_both(name, kind, monkeypatch, _pass_scenario, non_blocking=False))
+
+
+# ---- b. every getter, first and second call ----------------------------------------------------------------------------------------
+def _getters_of(side):
+    return [g for g in GETTERS if not (g == "alpha_stats" and side.mt == NB)]
+
+
+@pytest.mark.parametrize("name,kind", CASES)
+def test_getters_first_and_second_call(name, kind, monkeypatch):
+    def scenario(side):
+        em = side.context(alpha_stats=True)
+        rec = {"pass a": [side.estep(em, _model(name, "a"))], "pass b": [side.estep(em, _model(name, "b"))]}
+        for g in _getters_of(side):
+            rec[g + ", first call"] = side.getter(em, g)            # builds the getter's lazy state
+            rec[g + ", second call"] = side.getter(em, g)           # uses it
+        return rec
+
+    rec = _run_both(name, kind, monkeypatch, scenario)
+    for tag, calls in rec.items():
+        assert all(c == N.HF_OK for c in _codes(calls)), (tag, _codes(calls))
+        if tag.endswith("first call"):
+            _equal(calls, rec[tag.replace("first", "second")], tag)
+    whole = rec["posterior, first call"][0][1][0]
+    assert np.array_equal(whole.argmax(axis=1).astype(np.int8), rec["labels, first call"][0][1][0])
+    for (a, c), (_, part) in zip(_input(name)[7].ranges, rec["posterior, first call"]):
+        assert np.array_equal(part[0], whole[a:a + c]), (a, c)
+
+
+@pytest.mark.parametrize("name,kind", CASES)
+def test_each_getter_as_the_first_after_the_pass(name, kind, monkeypatch):
+    """A context of its own per getter: the getter's first call is the first thing after the pass, behind a delay, with nothing of any
+    other getter's lazy state in place."""
+    def scenario(side):
+        rec = {}
+        for i, g in enumerate(_getters_of(side)):
+            em = side.context(alpha_stats=True)
+            w = "ab"[i % 2]
+            side.estep(em, _model(name, "ab"[1 - i % 2]))
+            rec[g + " pass " + w] = [side.estep(em, _model(name, w))]
+            rec[g] = side.getter(em, g)
+            em.close()
+        return rec
+
+    rec = _run_both(name, kind, monkeypatch, scenario)
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls))
+
+
+# ---- c. decoders --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("where", ["same-stream", "second-stream"])
+@pytest.mark.parametrize("name,kind", CASES)
+def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
+    """hf_viterbi and hf_sample_paths with parameters other than the pass's, on the pass's stream or on a second non-blocking stream:
+    their own results, and afterwards every getter still answers for the pass — its first (lazy) call included."""
+    def scenario(side):
+        ma, mb = _model(name, "a"), _model(name, "b")
+        s2 = side.streams[1] if where == "second-stream" else None
+        em = side.context(alpha_stats=True)
+        rec = {"pass b": [side.estep(em, mb)]}
+        rec["viterbi a"] = [side.viterbi(em, ma, s2)]
+        rec["sample a"] = [side.sample(em, ma, s2)]
+        for g in _getters_of(side):
+            rec[g + " after the decoders"] = side.getter(em, g)
+        rec["viterbi a again"] = [side.viterbi(em, ma, s2)]
+        rec["sample a again"] = [side.sample(em, ma, s2)]
+        for g in _getters_of(side):
+            rec[g + " after the decoders again"] = side.getter(em, g)
+        # what the getters must still answer: the pass alone, on a context that never decoded
+        alone = side.context(alpha_stats=True)
+        rec["alone pass b"] = [side.estep(alone, mb)]
+        for g in _getters_of(side):
+            rec[g + " alone"] = side.getter(alone, g)
+        rec["viterbi b alone"] = [side.viterbi(alone, mb, s2)]
+        return rec
+
+    rec = _run_both(name, kind, monkeypatch, scenario, n_streams=2)
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls)), {t: _codes(c) for t, c in rec.items()}
+    _equal(rec["viterbi a"], rec["viterbi a again"], "viterbi")
+    _equal(rec["sample a"], rec["sample a again"], "sample")
+    assert not np.array_equal(rec["viterbi a"][0][1][0], rec["viterbi b alone"][0][1][0])          # (the decoders' model is another one)
+    for g in GETTERS:
+        if g + " alone" in rec:
+            _equal(rec[g + " after the decoders"], rec[g + " alone"], g)
+            _equal(rec[g + " after the decoders again"], rec[g + " alone"], g)
+
+
+# ---- d. mixed orders ----------------------------------------------------------------------------------------------------------------
+def _mixed_scenario(side, seed):
+    """One sequence of tests/stream_sequences.py on a context; after every getter, the same getter on a FRESH context that ran only the last
+    pass (with the switches as they stood then, and as they stand now for the getter)."""
+    name = side.name
+    scan = KINDS[side.kind][0] == N.HF_ALGO_SCAN
+    base_mode = KINDS[side.kind][1]
+    other_mode = {N.HF_STATS_ROWS: N.HF_STATS_CHUNKS, N.HF_STATS_CHUNKS: N.HF_STATS_ROWS}.get(base_mode)
+    models = {"pass_a": _model(name, "a"), "pass_b": _model(name, "b")}
+    em = side.context()
+    rec, fresh_cache = {}, {}
+    last_model = "pass_a"
+
+    def run_pass(ctx, op, which):
+        if op == "forward":
+            return side.estep(ctx, models[which], N.HF_MODE_FORWARD_ONLY)
+        return side.estep(ctx, models[op])
+
+    def fresh(op, st, which):
+        key = (op, st["last_pass"], which if st["last_pass"] == "forward" else None, st["pass_alpha"], st["pass_flipped"], st["alpha"], st["flipped"],
+               st["alpha_answers"])
+        if key not in fresh_cache:
+            f = side.context()
+            if scan and st["pass_flipped"]:
+                f.set_stats_mode(other_mode)
+            if st["pass_alpha"]:
+                _call(f.set_alpha_stats, True)
+            if st["last_pass"]:
+                run_pass(f, st["last_pass"], which)
+            if scan and st["flipped"] != st["pass_flipped"]:
+                f.set_stats_mode(other_mode if st["flipped"] else base_mode)
+            if st["pass_alpha"] and not st["alpha_answers"]:                      # (switched off since the pass, and perhaps on again)
+                _call(f.set_alpha_stats, False)
+            if st["alpha"] != (st["pass_alpha"] and st["alpha_answers"]):
+                _call(f.set_alpha_stats, st["alpha"])
+            fresh_cache[key] = side.getter(f, op)
+            f.close()
+        return fresh_cache[key]
+
+    fwd_model = "pass_a"
+    for i, (op, st) in enumerate(SQ.replay(SQ.sequence(seed))):
+        tag = "%02d %s" % (i, op)
+        if op in ("pass_a", "pass_b"):
+            rec[tag] = [run_pass(em, op, None)]
+            last_model = op
+        elif op == "forward":
+            fwd_model = "pass_b" if last_model == "pass_a" else "pass_a"
+            rec[tag] = [run_pass(em, op, fwd_model)]
+            last_model = fwd_model
+        elif op == "flip":
+            if scan:
+                em.set_stats_mode(base_mode if st["flipped"] else other_mode)
+        elif op in ("alpha_on", "alpha_off"):
+            rec[tag] = [_call(em.set_alpha_stats, op == "alpha_on")]
+        elif op in SQ.DECODERS:
+            other = models["pass_b" if last_model == "pass_a" else "pass_a"]                     # parameters other than the last pass's
+            rec[tag] = [side.viterbi(em, other) if op == "viterbi" else side.sample(em, other)]
+        else:
+            got = side.getter(em, op)
+            rec[tag] = got
+            if side.stream:                                                                       # (once: the twin equals this side)
+                _equal(got, fresh(op, st, fwd_model), "%s against a fresh context" % tag)
+            if st["last_pass"] in (None, "forward"):
+                assert all(c == N.HF_E_ARG for c in _codes(got)), (tag, _codes(got))
+            elif op != "alpha_stats":
+                assert all(c == N.HF_OK for c in _codes(got)), (tag, _codes(got))
+            elif st["alpha_answers"] and side.mt != NB:
+                assert _codes(got) == [N.HF_OK], (tag, _codes(got))
+            else:
+                assert _codes(got) == [N.HF_E_ARG], (tag, _codes(got))
+    return rec
+
+
+MIXED = [pytest.param("config2", k, s, id="config2-%s-seed%d" % (k, s)) for k in KINDS for s in SQ.SEEDS] + \
+        [pytest.param(n, k, SQ.SEEDS[i % len(SQ.SEEDS)], id="%s-%s-seed%d" % (n, k, SQ.SEEDS[i % len(SQ.SEEDS)]))
+         for i, (n, k) in enumerate((n, k) for n in ("sizes", "regions", "negative_binomial") for k in ("seq", "scan-rows", "scan-chunks-3-sub-passes"))]
+
+
+@pytest.mark.parametrize("name,kind,seed", MIXED)
+def test_mixed_orders(name, kind, seed, monkeypatch):
+    _run_both(name, kind, monkeypatch, lambda side: _mixed_scenario(side, seed))
+
+
+# ---- e. two contexts, two streams ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,kind", ON_CONFIG2 + [pytest.param("negative_binomial", "scan-rows", id="negative_binomial-scan-rows")])
+def test_two_contexts_on_two_streams(name, kind, monkeypatch):
+    """estep(a), estep(b), finish(b), finish(a), then getters alternating between the two: each context's results as if it ran alone."""
+    def scenario(side):
+        ma, mb = _model(name, "a"), _model(name, "b")
+        s1, s2 = side.streams
+        a, b = side.context(s1, alpha_stats=True), side.context(s2, alpha_stats=True)
+        rec = {}
+        side.delay(s1)
+        ca, _ = _call(a.launch, ma)
+        side.assert_busy(s1, "hf_estep")
+        side.delay(s2)
+        cb, _ = _call(b.launch, mb)
+        side.assert_busy(s2, "hf_estep")
+        rec["b pass"] = [(cb, ()), side.finish(b)]
+        rec["a pass"] = [(ca, ()), side.finish(a)]
+        for g in _getters_of(side):
+            rec["a " + g] = side.getter(a, g)
+            rec["b " + g] = side.getter(b, g)
+        for g in reversed(_getters_of(side)):
+            rec["b again " + g] = side.getter(b, g)
+            rec["a again " + g] = side.getter(a, g)
+        for w, m in (("a", ma), ("b", mb)):
+            alone = side.context(s1, alpha_stats=True)
+            rec[w + " alone pass"] = [(N.HF_OK, ()), side.estep(alone, m)]
+            for g in _getters_of(side):
+                rec[w + " alone " + g] = side.getter(alone, g)
+            alone.close()
+        return rec
+
+    rec = _run_both(name, kind, monkeypatch, scenario, n_streams=2)
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls))
+    for w in "ab":
+        _equal(rec[w + " pass"], rec[w + " alone pass"], w)
+        for g in GETTERS:
+            if w + " " + g in rec:
+                _equal(rec[w + " " + g], rec[w + " alone " + g], w + " " + g)
+                _equal(rec[w + " again " + g], rec[w + " alone " + g], w + " again " + g)
+    assert not np.array_equal(rec["a labels"][0][1][0], rec["b labels"][0][1][0])
+
+
+# ---- f. the batch ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("stats_mode", [N.HF_STATS_ROWS, N.HF_STATS_CHUNKS], ids=["rows", "chunks"])
+@pytest.mark.parametrize("name", ["config2", "regions"])
+def test_batch_on_a_stream(name, stats_mode, monkeypatch):
+    """EMBatch(..., stream=s) with three models: statistics, statuses, labels(m) and posterior(m) of the stream-0 batch; then a pass and
+    getters on the underlying single context, and the batch's results are still there."""
+    def scenario(side):
+        store, mt, K, alpha, frac = side.store, side.mt, side.K, side.alpha, side.frac
+        models = [_model(name, "a"), _model(name, "b"), hmm.createModel(mt, K, store, np.zeros((4, 4)))]
+        em = hmm.EMList(store, models[0], True, frac, stream=side.stream)
+        side.contexts.append(em)
+        em.set_stats_mode(stats_mode)
+        batch = hmm.EMBatch(em, models)
+        assert (batch.stream.value or 0) == side.stream
+        rec = {}
+        try:
+            for rnd in range(2):
+                side.delay()
+                act = batch.launch()
+                side.assert_busy(side.stream, "hf_batch_estep")
+                side.delay()
+                stats, status = batch.finish(len(act))
+                rec["batch pass %d" % rnd] = [(N.HF_OK, (stats.copy(), status.copy()))]
+                assert (status == N.HF_OK).all()
+                for m in range(3):
+                    side.delay()
+                    rec["batch labels %d.%d" % (rnd, m)] = [_call(batch.labels, m)]
+                    side.delay()
+                    rec["batch posterior %d.%d" % (rnd, m)] = [_call(batch.posterior, m)] + [_call(batch.posterior, m, a, c) for a, c in side.J.ranges[1:4]]
+                if rnd == 0:
+                    for i, m in enumerate(models):                       # other parameters for the second round
+                        m.estimators = stats[i].copy()
+                        hmm.HMM_estimateParameters(m, 1e-3)
+                        hmm.HMM_resetEstimators(m)
+            rec["single pass"] = [side.estep(em, _model(name, "b"))]
+            rec["single posterior"] = side.getter(em, "posterior")
+            rec["single interval_log_probs"] = side.getter(em, "interval_log_probs")
+            side.delay()
+            rec["batch labels after the single pass"] = [_call(batch.labels, 1)]
+        finally:
+            batch.close()
+        return rec
+
+    rec = _run_both(name, "scan-rows", monkeypatch, scenario)
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls))
+    _equal(rec["batch labels after the single pass"], rec["batch labels 1.1"], "the batch's labels after a pass of the single context")
+    assert not np.array_equal(rec["batch labels 0.1"][0][1][0], rec["batch labels 1.1"][0][1][0])
+
+
+# ---- g. after a failed pass --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["seq", "scan-rows", "scan-chunks"])
+def test_after_a_failed_pass(kind):
+    """The negative-variance model of tests/test_estep_gpu.py::test_nan_emission_is_reported on a caller's stream: hf_finish and every
+    getter return the twin's codes, and no getter answers HF_OK for a pass that failed."""
+    store = synth.synthesize([400_000, 150_000], 1000, 200_000, [20], seed=3)
+    K = 3
+    model = hmm.createModel(hmm.MODEL_TRUNC_EXP_GAUSSIAN, K, store, synth.HIFI_ALPHA)
+    v = model.param_vector()
+    km = (v.size - 27) // 12
+    v[27 + 4 * km + 2 * km] = -1.0           # variance of the Hap state
+    model.set_param_vector(v)
+    n = store.n_windows
+    algo, mode, _ = KINDS[kind]
+    h = HS.hip()
+    recs = []
+    with HS.Streams() as streams:
+        for s in (streams.new(), 0):
+            em = hmm.EMList(store, model, algo=algo, stream=s)
+            try:
+                if mode is not None:
+                    em.set_stats_mode(mode)
+                em.set_alpha_stats(True)
+                rec = []
+                h.delay(s)
+                rec.append(_call(em.launch, model)[0])
+                h.delay(s)
+                rec.append(_call(em.finish)[0])
+                F, L_, M = np.array([0, 5]), np.array([n - 1, 40]), np.array([15, 4])
+                calls = {"labels": (em.labels,), "posterior": (em.posterior,), "forward_backward": (em.forward_backward,),
+                         "interval_log_probs": (em.interval_log_probs, F, L_, M), "count_moments": (em.count_moments, F, L_, M),
+                         "run_moments": (em.run_moments, F, L_, M), "path_entropy": (em.path_entropy, F, L_),
+                         "path_log_probs": (em.path_log_probs, F, L_, np.full(n, 2, np.int8)), "entropy_profile": (em.entropy_profile,),
+                         "alpha_stats": (em.alpha_stats,)}
+                assert sorted(calls) == sorted(GETTERS)
+                for g in GETTERS:
+                    h.delay(s)
+                    rec.append(_call(*calls[g])[0])
+                recs.append(rec)
+            finally:
+                em.close()
+    got, twin = recs
+    assert got == twin
+    assert got[0] == N.HF_OK and got[1] == N.HF_E_NAN
+    assert all(c != N.HF_OK for c in got[2:]), dict(zip(GETTERS, got[2:]))
+
+
+def test_batch_after_a_failed_model():
+    """A batch of a good model and the negative-variance one on a caller's stream: the bad model's status is HF_E_NAN and its getters
+    return HF_E_ARG, the good model's labels and posterior are those of a batch without the bad one; all as on stream 0."""
+    store = synth.synthesize([400_000, 150_000], 1000, 200_000, [20], seed=3)
+    good = hmm.createModel(hmm.MODEL_TRUNC_EXP_GAUSSIAN, 3, store, synth.HIFI_ALPHA)
+    bad = good.copy()
+    v = bad.param_vector()
+    km = (v.size - 27) // 12
+    v[27 + 4 * km + 2 * km] = -1.0           # variance of the Hap state
+    bad.set_param_vector(v)
+    h = HS.hip()
+    recs = []
+    with HS.Streams() as streams:
+        for s in (streams.new(), 0):
+            for models in ([good, bad], [good]):
+                batch = hmm.EMBatch(store, models, stream=s)
+                try:
+                    h.delay(s)
+                    act = batch.launch()
+                    h.delay(s)
+                    stats, status = batch.finish(len(act))
+                    rec = [(N.HF_OK, (status.copy(), stats[0].copy()))]
+                    for m in range(len(models)):
+                        h.delay(s)
+                        rec += [_call(batch.labels, m), _call(batch.posterior, m)]
+                    recs.append(rec)
+                finally:
+                    batch.close()
+                    batch.em.close()
+    both, alone, both0, alone0 = recs
+    _equal(both, both0, "good and bad model against stream 0")
+    _equal(alone, alone0, "good model alone against stream 0")
+    assert list(both[0][1][0]) == [N.HF_OK, N.HF_E_NAN]
+    assert _codes(both[1:]) == [N.HF_OK, N.HF_OK, N.HF_E_ARG, N.HF_E_ARG]
+    _equal(both[1:3], alone[1:3], "the good model beside a failing one")
+    assert np.array_equal(both[0][1][1], alone[0][1][1])
+
+
+# ---- h. PyTorch plumbing ---------------------------------------------------------------------------------------------------------------
+def test_torch_stream():
+    """A torch.cuda.Stream's handle, passed the way flagger_amd/dist.py passes the current stream's: in a fresh process that imports
+    torch BEFORE the library, as a dist.py caller does (tests/torch_stream_child.py).  Skips only when that process reports that torch
+    sees no GPU; torch and the library on two HIP runtime objects is a failure — the handle would mean nothing to the library."""
+    pytest.importorskip("torch")
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "torch_stream_child.py")
+    r = subprocess.run([sys.executable, child], capture_output=True, text=True, timeout=120)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    res = json.loads(lines[0][len("RESULT "):])
+    if res["status"] == "no gpu":
+        pytest.skip("torch sees no GPU in a fresh process")
+    assert res["status"] == "ok", res
+    assert len(res["runtimes"]) == 1, res                 # torch and the library share one HIP runtime object
+    assert res["busy_after_estep"] and res["codes_ok"] and res["equal"], res
+    assert res["compared_arrays"] >= 4 and res["current_stream_is_the_handle"], res
