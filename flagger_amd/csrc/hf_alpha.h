@@ -5,7 +5,7 @@
 // Definition (gaussian and trunc_exp_gaussian).  For a pair of windows (t-1, t) of one chunk, t >= 1 (the pair (0, 1) INCLUDED), with
 // r the region of window t, x / x_prev the 8-bit coverage of t / t-1, beta = beta_t:
 //   xi[p][s] = f_{t-1}[p] * A_t[p][s] * b_t[s] / HF_TERMINATION_PROB
-// f, b the pass's scaled forward and backward vectors (hf_get_forward_backward) and A_t the row the pass multiplied by (hf_interval.h
+// f, b the pass's scaled forward and backward vectors (hf_get_forward_backward) and A_t the row the pass multiplied by (hf_view.h
 // iv_row).  For a Gaussian state s and component c, with a = alpha[p][s]:
 //   v_c = var_c * beta,  d_c = x - ((1 - a) mu_c + a x_prev) beta,  u_c = beta (x_prev - mu_c)
 //   P_c = w_c / sqrt(2 PI v_c) exp(-d_c^2 / (2 v_c)) floored at 1e-40 (phi_c = 0 where the floor was taken, else 1), g_c = P_c / sum_c P_c
@@ -33,7 +33,7 @@
 //                  order, then j = 0..31 in order.  Out: out[r][32].
 // The order of every addition is fixed by the plan: a run is reproducible bit for bit.
 #pragma once
-#include "hf_interval.h"
+#include "hf_view.h"
 
 #define HF_AL_THREADS 256
 #define HF_AL_BLOCK (4 * HF_AL_THREADS)      // pairs per block at most (measured at configs[2]: 16 per lane 148 us, 4 per lane 105 us, 2 per lane 116 us)
@@ -93,17 +93,11 @@ __global__ void __launch_bounds__(256) k_alpha_terms(int n_jobs, const TableJob*
     for (int k = 0; k < 16; k++) dst[k] = make_double2(out[2 * k], out[2 * k + 1]);
 }
 
+// f_{t-1} (mo_f) and b_t (mo_b) of a pair, and its row A_t: hf_view.h
 template <bool SEQ>
 __global__ void __launch_bounds__(HF_AL_THREADS) k_alpha_pairs(const AlBlock* __restrict__ blocks, const long long* __restrict__ pair_t,
-                                                               const int32_t* __restrict__ pair_c, const uint32_t* __restrict__ rec,
-                                                               const double* __restrict__ beta, const DevParams* __restrict__ P,
-                                                               const int32_t* __restrict__ arow, const double* __restrict__ lutA,
-                                                               const double* __restrict__ terms,
-                                                               const double* __restrict__ E, const int32_t* __restrict__ pos,
-                                                               const int32_t* __restrict__ pos_f, const double* __restrict__ recs,
-                                                               const int64_t* __restrict__ off, const int32_t* __restrict__ chunk_tile0,
-                                                               const double* __restrict__ F, const double* __restrict__ B,
-                                                               double* __restrict__ part) {
+                                                               const int32_t* __restrict__ pair_c, const double* __restrict__ beta,
+                                                               const double* __restrict__ terms, PassView pv, double* __restrict__ part) {
     const AlBlock bk = blocks[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double acc[32];
@@ -113,29 +107,19 @@ __global__ void __launch_bounds__(HF_AL_THREADS) k_alpha_pairs(const AlBlock* __
     for (int i = tid; i < bk.n; i += HF_AL_THREADS) {
         const int64_t t = pair_t[bk.p0 + i];
         double A[16], f[4], b[4], tm[32];
-        iv_row<SEQ>(arow, lutA, rec, E, P, t, A);
+        iv_row<SEQ>(pv, t, A);
+        int c = 0;                                   // (the chunk of the pair: the tiles of HF_ALGO_SEQ only)
         if constexpr (SEQ) {
-            const uint32_t r1 = rec[t], r0 = rec[t - 1];
-            alpha_terms(P, &P->reg[bk.r], (double) REC_X(r1), (double) REC_X(r0), beta[t], tm);
-            const int c = pair_c[bk.p0 + i];
-            const int64_t t0 = off[c];
-            const int tile0 = chunk_tile0[c];
-            const double2* __restrict__ F2 = reinterpret_cast<const double2*>(F);
-            const double2* __restrict__ B2 = reinterpret_cast<const double2*>(B);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const double2 u = F2[fb_slot_w<HF_SCAN_L>(tile0, t - 1 - t0, h)], v = B2[fb_slot_w<HF_SCAN_L>(tile0, t - t0, h)];
-                f[2 * h] = u.x; f[2 * h + 1] = u.y; b[2 * h] = v.x; b[2 * h + 1] = v.y;
-            }
-        } else {   // b_t: second half of the record at pos[t]; f_{t-1}: first half of the one at pos_f[t-1]
-            const double2* __restrict__ src = reinterpret_cast<const double2*>(terms) + (int64_t) ((uint32_t) arow[t] & 0x7fffffffu) * 16;
+            const uint32_t r1 = pv.rec[t], r0 = pv.rec[t - 1];
+            alpha_terms(pv.Pm, &pv.Pm->reg[bk.r], (double) REC_X(r1), (double) REC_X(r0), beta[t], tm);
+            c = pair_c[bk.p0 + i];
+        } else {
+            const double2* __restrict__ src = reinterpret_cast<const double2*>(terms) + (int64_t) ((uint32_t) pv.arow[t] & 0x7fffffffu) * 16;
 #pragma unroll
             for (int k = 0; k < 16; k++) { const double2 v = src[k]; tm[2 * k] = v.x; tm[2 * k + 1] = v.y; }
-            const double* __restrict__ rf = recs + (int64_t) pos_f[t - 1] * 8;
-            const double* __restrict__ rb = recs + (int64_t) pos[t] * 8 + 4;
-#pragma unroll
-            for (int s = 0; s < 4; s++) { f[s] = rf[s]; b[s] = rb[s]; }
         }
+        mo_f<SEQ>(pv, c, t - 1, f);
+        mo_b<SEQ>(pv, c, t, b);
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             const double w = f[k >> 2] * A[k] * b[k & 3];          // xi without its division by the termination probability: taken once, below

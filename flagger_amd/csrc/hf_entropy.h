@@ -25,6 +25,7 @@
 //   k_ent_profile  one thread per window: marg_t and / or cond_t (cond_t := marg_t at a chunk-first window).
 // The parts of a job are summed on the host in chunk order.  Nothing depends on the other jobs of a call.
 #pragma once
+#include "hf_view.h"
 #include "hf_runs.h"
 
 #define HF_EN_LANE 8                      // windows per lane of a piece
@@ -101,16 +102,14 @@ __device__ __forceinline__ double en_gamma_log(const double f[4], const double b
 
 // out[g] = the piece's sum of cond_t (LABELS: of log(x_t[y_{t-1}][y_t] / m_t[y_{t-1}]); lab is indexed by t - lab0)
 template <bool SEQ, bool LABELS>
-__global__ void __launch_bounds__(64) k_ent_piece(const EnPiece* __restrict__ pieces, const int32_t* __restrict__ arow,
-                                                  const double* __restrict__ lutA, const uint32_t* __restrict__ rec,
-                                                  const double* __restrict__ E, const DevParams* __restrict__ Pm, MoFB fb,
-                                                  const int8_t* __restrict__ lab, long long lab0, double* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_ent_piece(const EnPiece* __restrict__ pieces, PassView pv, const int8_t* __restrict__ lab, long long lab0,
+                                                  double* __restrict__ out) {
     const EnPiece pc = pieces[blockIdx.x];
     const int j = threadIdx.x;
     double m = 0.0;
     if (j * HF_EN_LANE < pc.n) {
         double fp[4], b[4];
-        mo_fb<SEQ>(fb, pc.c, pc.t0 + j * HF_EN_LANE - 1, fp, b);      // f of the lane's first predecessor
+        mo_fb<SEQ>(pv, pc.c, pc.t0 + j * HF_EN_LANE - 1, fp, b);      // f of the lane's first predecessor
         int yp = 0;
         if constexpr (LABELS) yp = lab[pc.t0 + j * HF_EN_LANE - 1 - lab0];
 #pragma unroll 1
@@ -119,8 +118,8 @@ __global__ void __launch_bounds__(64) k_ent_piece(const EnPiece* __restrict__ pi
             if (x >= pc.n) break;
             const int64_t t = pc.t0 + x;
             double A[16], f[4];
-            iv_row<SEQ>(arow, lutA, rec, E, Pm, t, A);
-            mo_fb<SEQ>(fb, pc.c, t, f, b);
+            iv_row<SEQ>(pv, t, A);
+            mo_fb<SEQ>(pv, pc.c, t, f, b);
             if constexpr (LABELS) {
                 const int ys = lab[t - lab0];
                 m += en_pair_log(fp, A, b, yp, ys);
@@ -142,13 +141,13 @@ __global__ void __launch_bounds__(64) k_ent_piece(const EnPiece* __restrict__ pi
 
 // one thread per part: out[i] = the first window's term + the part's piece sums in order
 template <bool SEQ, bool LABELS>
-__global__ void __launch_bounds__(64) k_ent_chain(int n_parts, const EnPart* __restrict__ parts, const double* __restrict__ px, MoFB fb,
+__global__ void __launch_bounds__(64) k_ent_chain(int n_parts, const EnPart* __restrict__ parts, const double* __restrict__ px, PassView pv,
                                                   const int8_t* __restrict__ lab, long long lab0, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parts) return;
     const EnPart pt = parts[i];
     double f[4], b[4];
-    mo_fb<SEQ>(fb, pt.c, pt.a, f, b);
+    mo_fb<SEQ>(pv, pt.c, pt.a, f, b);
     double v;
     if constexpr (LABELS) v = en_gamma_log(f, b, lab[pt.a - lab0]);
     else v = en_marg(f, b);
@@ -158,11 +157,8 @@ __global__ void __launch_bounds__(64) k_ent_chain(int n_parts, const EnPart* __r
 
 // one thread per window first + i, i < n: marg[i] and / or cond[i] (either may be NULL).  off: the C + 1 chunk offsets.
 template <bool SEQ>
-__global__ void __launch_bounds__(256) k_ent_profile(long long first, long long n, const int64_t* __restrict__ off, int C,
-                                                     const int32_t* __restrict__ arow, const double* __restrict__ lutA,
-                                                     const uint32_t* __restrict__ rec, const double* __restrict__ E,
-                                                     const DevParams* __restrict__ Pm, MoFB fb, double* __restrict__ marg,
-                                                     double* __restrict__ cond) {
+__global__ void __launch_bounds__(256) k_ent_profile(long long first, long long n, const int64_t* __restrict__ off, int C, PassView pv,
+                                                     double* __restrict__ marg, double* __restrict__ cond) {
     const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t t = first + i;
@@ -172,7 +168,7 @@ __global__ void __launch_bounds__(256) k_ent_profile(long long first, long long 
         if (off[mid] <= t) lo = mid; else hi = mid;
     }
     double f[4], b[4];
-    mo_fb<SEQ>(fb, lo, t, f, b);
+    mo_fb<SEQ>(pv, lo, t, f, b);
     const bool chunk_first = t == off[lo];
     if (marg || chunk_first) {
         const double h = en_marg(f, b);
@@ -181,8 +177,8 @@ __global__ void __launch_bounds__(256) k_ent_profile(long long first, long long 
     }
     if (cond && !chunk_first) {
         double fp[4], bp[4], A[16];
-        mo_fb<SEQ>(fb, lo, t - 1, fp, bp);
-        iv_row<SEQ>(arow, lutA, rec, E, Pm, t, A);
+        mo_fb<SEQ>(pv, lo, t - 1, fp, bp);
+        iv_row<SEQ>(pv, t, A);
         cond[i] = en_cond(fp, A, b);
     }
 }

@@ -452,33 +452,17 @@ struct Sampler : Decoder {
     void release() { samples.release(); Decoder::release(); }
 };
 
-// exact interval probabilities (hf_interval.h): one device buffer of their own, grown on demand (pieces, parts, piece products, results)
-struct IntervalBufs {
+// device scratch of a range getter (hf_get_interval_log_probs and those after it): one buffer per getter family, grown on demand and
+// never shrunk, so that every getter's buffer stays as it is behind calls to the others
+struct DevBuf {
     char* d_buf = nullptr; size_t cap = 0;
     void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
-};
-
-// exact count moments (hf_moments.h): one device buffer of their own, grown on demand (pieces, parts, piece triples, piece means, results)
-struct MomentBufs {
-    char* d_buf = nullptr; size_t cap = 0;
-    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
-};
-
-// exact run moments (hf_runs.h): one device buffer of their own, grown on demand (pieces, parts, piece triples, piece sums of xi, results)
-struct RunBufs {
-    char* d_buf = nullptr; size_t cap = 0;
-    void release() { if (d_buf) hipFree(d_buf); d_buf = nullptr; cap = 0; }
-};
-
-// exact path entropy and labelling log-probability (hf_entropy.h): one device buffer of their own, grown on demand (pieces, parts, piece
-// sums, results / the profile's two arrays) and one for the labels of a call
-struct EntBufs {
-    char* d_buf = nullptr; size_t cap = 0;
-    int8_t* d_lab = nullptr; size_t lab_cap = 0;
-    void release() {
-        if (d_buf) hipFree(d_buf);
-        if (d_lab) hipFree(d_lab);
-        d_buf = nullptr; cap = 0; d_lab = nullptr; lab_cap = 0;
+    int reserve(size_t bytes, const std::string& who) {
+        if (bytes <= cap) return HF_OK;
+        release();
+        if (hipMalloc((void**) &d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); d_buf = nullptr; return set_err(HF_E_HIP, who + ": out of device memory"); }
+        cap = bytes;
+        return HF_OK;
     }
 };
 
@@ -503,11 +487,11 @@ struct hf_ctx {
     Pass pass;
     Viterbi vit;
     Sampler smp;
-    IntervalBufs iv;
+    DevBuf iv;                // hf_interval.h: pieces, parts, piece products, results
     AlphaStats al;
-    MomentBufs mo;
-    RunBufs rn;
-    EntBufs en;
+    DevBuf mo;                // hf_moments.h: pieces, parts, piece triples, piece means, results
+    DevBuf rn;                // hf_runs.h: pieces, parts, piece triples, piece sums of xi, results
+    DevBuf en, en_lab;        // hf_entropy.h: pieces, parts, piece sums, results / the profile's two arrays; the labels of a call
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1048,6 +1032,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->mo.release();
     ctx->rn.release();
     ctx->en.release();
+    ctx->en_lab.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2370,111 +2355,174 @@ int hf_get_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
 
 
 // ------------------------------------------------------------------------------------------
-// exact interval probabilities (hf_interval.h) over the last full pass: the host cuts every job into chunk-local parts and every part's
-// interior windows into pieces, k_iv_piece multiplies the pieces, k_iv_chain every part's vectors through them, the host sums the parts
-// of a job in chunk order.  Last in the file, like the decoders, so that no pass kernel's code moves.
+// The range getters: values over window ranges under the model of the last full pass (hf_interval.h, hf_moments.h, hf_runs.h,
+// hf_entropy.h) and the alpha statistics (hf_alpha.h).  Nothing of them runs inside a pass: they read what the pass left (on the scan
+// path after the lazy re-run of the segment kernel, pass_all_records) and write buffers of their own.  Last in the file, behind
+// hf_batch.h and the decoders, so that no pass kernel's code moves.
+//
+// THE SCAFFOLD of the four piece / chain getters (interval, count moments, run moments, entropy and labelling log-probability): rg_check
+// refuses what every one of them refuses, pass_view says where the pass left its rows, f and b (hf_view.h), and rg_run takes the jobs through the
+// device batch by batch: it cuts a batch into chunk-local parts and their pieces (hf_jobs.h), lays out the getter's scratch (pieces |
+// parts | per-piece results, one or two arrays | per-part results), uploads, launches the getter's piece kernel and then its chain
+// kernel, fetches the parts' results and hands the parts of every job, in chunk order, to the getter's fold.  A getter keeps its record
+// builders, its scratch sizes, its two launches and its fold.
 // ------------------------------------------------------------------------------------------
+#include "hf_jobs.h"
+#include "hf_view.h"
 #include "hf_interval.h"
+#include "hf_moments.h"
+#include "hf_runs.h"
+#include "hf_entropy.h"
+#include <type_traits>
 
-// pieces and parts per device batch (a job is never split across batches, and a batch holds at least one job)
+// pieces and parts per device batch (hf_jobs.h): the interval getter's, and those of the moments, run moments and entropy getters (a
+// piece's triple is 384 bytes: 96 MB of them at most)
+#ifndef HF_IV_BATCH_PIECES
 #define HF_IV_BATCH_PIECES (1 << 20)
+#endif
+#ifndef HF_IV_BATCH_PARTS
 #define HF_IV_BATCH_PARTS (1 << 20)
+#endif
+#ifndef HF_MO_BATCH_PIECES
+#define HF_MO_BATCH_PIECES (1 << 18)
+#endif
+#ifndef HF_MO_BATCH_PARTS
+#define HF_MO_BATCH_PARTS (1 << 20)
+#endif
 
-int hf_get_interval_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, double* log_p_host) {
-    if (!ctx) return set_err(HF_E_ARG, "hf_get_interval_log_probs: bad argument");
+static_assert(HF_IV_PIECE == 512 && HF_MO_PIECE == 512 && HF_RN_PIECE == 512 && HF_EN_PIECE == 512, "one piece grid for every getter");
+
+// f(std::true_type) for HF_ALGO_SEQ, f(std::false_type) for HF_ALGO_SCAN: one launch per kernel, its template argument the only difference
+template <class F>
+static void by_algo(const Track& tr, F&& f) {
+    if (tr.algo == HF_ALGO_SEQ) f(std::true_type{}); else f(std::false_type{});
+}
+
+// What every range getter refuses, in this order: n < 0, `early` (a refusal of the getter's own that ranks here, or nullptr), NULL arrays,
+// no full pass, `late` (the same), and job by job a bad range, a window outside every chunk, a state mask outside 1..15 (state_mask ==
+// nullptr: the getter has none) and a region outside -1..n_regions-1 (region == nullptr: no filter).
+static int rg_check(const hf_ctx* ctx, const std::string& who, int64_t n, bool null_array, const int64_t* first, const int64_t* last,
+                    const uint8_t* state_mask, const int32_t* region = nullptr, const char* early = nullptr, const char* late = nullptr) {
+    const Track& tr = ctx->tr;
+    if (n < 0) return set_err(HF_E_ARG, who + ": n < 0");
+    if (early) return set_err(HF_E_ARG, who + ": " + early);
+    if (n > 0 && null_array) return set_err(HF_E_ARG, who + ": NULL array");
+    if (!ctx->pass.have_full)
+        return set_err(HF_E_ARG, who + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    if (late) return set_err(HF_E_ARG, who + ": " + late);
+    for (int64_t i = 0; i < n; i++) {
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N) return set_err(HF_E_ARG, who + ": bad range (job " + std::to_string(i) + ")");
+        if (!in_chunks(tr, first[i], last[i])) return set_err(HF_E_ARG, who + ": a window outside every chunk (job " + std::to_string(i) + ")");
+        if (state_mask && (state_mask[i] < 1 || state_mask[i] > 15))
+            return set_err(HF_E_ARG, who + ": state_mask must be 1..15 (job " + std::to_string(i) + ")");
+        if (region && (region[i] < -1 || region[i] >= tr.R))
+            return set_err(HF_E_ARG, who + ": region must be -1..n_regions-1 (job " + std::to_string(i) + ")");
+    }
+    return HF_OK;
+}
+
+// where the last full pass left its rows, f and b (hf_view.h)
+static PassView view_of(const hf_ctx* ctx) {
+    const Track& tr = ctx->tr;
+    const Pass& ps = ctx->pass;
+    PassView pv{};
+    pv.rec = tr.d_rec;
+    if (tr.algo == HF_ALGO_SEQ) { pv.off = tr.d_off; pv.chunk_tile0 = tr.d_chunk_tile0; pv.F = ps.d_f; pv.B = ps.d_b; pv.E = ps.d_E; pv.Pm = ps.d_params; }
+    else { pv.pos = tr.d_pos; pv.pos_f = tr.d_pos_f; pv.recs = ps.d_recs_all; pv.arow = tr.d_arow; pv.lutA = ps.d_lutA; }
+    return pv;
+}
+
+// The state of the pass a getter answers for, after its own checks: the device, and for n > 0 (n == 0: nothing will be read, the getter
+// returns) the pair records of the scan path and the view.
+static int pass_view(hf_ctx* ctx, const std::string& who, int64_t n, PassView& pv) {
     const Track& tr = ctx->tr;
     Pass& ps = ctx->pass;
-    if (n < 0) return set_err(HF_E_ARG, "hf_get_interval_log_probs: n < 0");
-    if (n > 0 && (!first || !last || !state_mask || !log_p_host)) return set_err(HF_E_ARG, "hf_get_interval_log_probs: NULL array");
-    if (!ps.have_full)
-        return set_err(HF_E_ARG, "hf_get_interval_log_probs: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    for (int64_t i = 0; i < n; i++) {
-        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
-            return set_err(HF_E_ARG, "hf_get_interval_log_probs: bad range (job " + std::to_string(i) + ")");
-        if (!in_chunks(tr, first[i], last[i]))
-            return set_err(HF_E_ARG, "hf_get_interval_log_probs: a window outside every chunk (job " + std::to_string(i) + ")");
-        if (state_mask[i] < 1 || state_mask[i] > 15)
-            return set_err(HF_E_ARG, "hf_get_interval_log_probs: state_mask must be 1..15 (job " + std::to_string(i) + ")");
-    }
     HIPCHK(hipSetDevice(tr.device));
+    pv = PassView{};
     if (n == 0) return HF_OK;
     const bool seq = tr.algo == HF_ALGO_SEQ;
-    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_interval_log_probs: the last pass kept no pair records");
+    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, who + ": the last pass kept no pair records");
     if (!seq) {
         const int rc = pass_all_records(ps);
         if (rc) return rc;
     }
-    hipStream_t st = ps.last_stream;
-    IntervalBufs& ib = ctx->iv;
-    std::vector<IvPiece> pieces;
-    std::vector<IvPart> parts;
-    std::vector<int64_t> job_p0;
+    pv = view_of(ctx);
+    return HF_OK;
+}
+
+// a batch on the device: np pieces, nq parts, the per-piece results pm and px of the piece kernel, the per-part results of the chain kernel
+template <class Piece, class Part>
+struct RgBatch {
+    size_t np, nq;
+    const Piece* pieces; const Part* parts;
+    double* pm; double* px; double* out;
+    dim3 piece_grid() const { return dim3((unsigned) np); }                  // one 64-lane workgroup per piece
+    dim3 chain_grid() const { return dim3((unsigned) ((nq + 63) / 64)); }    // one thread per part
+};
+
+// The jobs of a call, batch by batch, on the stream of the pass.  pm_bytes, px_bytes: the piece kernel's results per piece (px_bytes == 0:
+// one array only); out_doubles: the chain kernel's results per part.  launch(batch) enqueues the two kernels (the piece kernel only when
+// the batch has pieces); fold(job, parts, val, k0, k1) gets the host's part records and the results of the batch and writes the value
+// of the job from its parts k0 .. k1 - 1.
+template <class Piece, class Part, int64_t GRID, class MkPart, class MkPiece, class Launch, class Fold>
+static int rg_run(hf_ctx* ctx, const std::string& who, DevBuf& buf, int64_t n, const int64_t* first, const int64_t* last, size_t cap_pieces,
+                  size_t cap_parts, size_t pm_bytes, size_t px_bytes, size_t out_doubles, MkPart&& mk_part, MkPiece&& mk_piece, Launch&& launch,
+                  Fold&& fold) {
+    hipStream_t st = ctx->pass.last_stream;
+    JobCut<Piece, Part, GRID> jc;
     std::vector<double> val;
     for (int64_t j0 = 0; j0 < n;) {
-        // the jobs of this batch, cut into parts and pieces
-        pieces.clear(); parts.clear(); job_p0.clear();
-        int64_t j1 = j0;
-        while (j1 < n && (j1 == j0 || (pieces.size() < HF_IV_BATCH_PIECES && parts.size() < HF_IV_BATCH_PARTS))) {
-            job_p0.push_back((int64_t) parts.size());
-            const int mask = state_mask[j1];
-            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
-            for (int64_t a = first[j1]; a <= last[j1]; c++) {
-                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
-                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
-                IvPart pt{a, b, (int) pieces.size(), 0, mask, c};
-                for (int64_t t = a + 1; t <= b;) {
-                    const int64_t e = std::min<int64_t>(b, (t / HF_IV_PIECE + 1) * HF_IV_PIECE - 1);
-                    pieces.push_back(IvPiece{t, (int) (e - t + 1), mask});
-                    t = e + 1;
-                }
-                pt.p1 = (int) pieces.size();
-                parts.push_back(pt);
-                a = b + 1;
-            }
-            j1++;
-        }
-        job_p0.push_back((int64_t) parts.size());
-        const size_t np = pieces.size(), nq = parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(IvPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(IvPart));
-        const size_t o_pe = o_pm + Slab::granule(np * 32 * 8), o_out = o_pe + Slab::granule(np * 2 * 4), bytes = o_out + Slab::granule(nq * 8);
-        if (bytes > ib.cap) {
-            ib.release();
-            if (hipMalloc((void**) &ib.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); ib.d_buf = nullptr;
-                return set_err(HF_E_HIP, "hf_get_interval_log_probs: out of device memory"); }
-            ib.cap = bytes;
-        }
-        IvPiece* d_pieces = reinterpret_cast<IvPiece*>(ib.d_buf);
-        IvPart* d_parts = reinterpret_cast<IvPart*>(ib.d_buf + o_parts);
-        double* d_pm = reinterpret_cast<double*>(ib.d_buf + o_pm);
-        int* d_pe = reinterpret_cast<int*>(ib.d_buf + o_pe);
-        double* d_out = reinterpret_cast<double*>(ib.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(IvPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(IvPart), hipMemcpyHostToDevice, st));
-        if (seq) {
-            if (np) hipLaunchKernelGGL(k_iv_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, (const int32_t*) nullptr,
-                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, d_pm, d_pe);
-            hipLaunchKernelGGL(k_iv_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe,
-                               (const int32_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr, tr.d_off, tr.d_chunk_tile0,
-                               ps.d_f, ps.d_b, d_out);
-        } else {
-            if (np) hipLaunchKernelGGL(k_iv_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, tr.d_arow, ps.d_lutA,
-                                       (const uint32_t*) nullptr, (const double*) nullptr, (const DevParams*) nullptr, d_pm, d_pe);
-            hipLaunchKernelGGL(k_iv_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe,
-                               tr.d_pos, tr.d_pos_f, ps.d_recs_all, (const int64_t*) nullptr, (const int32_t*) nullptr,
-                               (const double*) nullptr, (const double*) nullptr, d_out);
-        }
+        const int64_t j1 = jc.cut(ctx->tr.h_off, n, first, last, j0, cap_pieces, cap_parts, mk_part, mk_piece);
+        const size_t np = jc.pieces.size(), nq = jc.parts.size();
+        const size_t o_parts = Slab::granule(np * sizeof(Piece)), o_pm = o_parts + Slab::granule(nq * sizeof(Part));
+        const size_t o_px = o_pm + Slab::granule(np * pm_bytes), o_out = px_bytes ? o_px + Slab::granule(np * px_bytes) : o_px;
+        const int rc = buf.reserve(o_out + Slab::granule(nq * out_doubles * 8), who);
+        if (rc) return rc;
+        Piece* d_pieces = reinterpret_cast<Piece*>(buf.d_buf);
+        Part* d_parts = reinterpret_cast<Part*>(buf.d_buf + o_parts);
+        const RgBatch<Piece, Part> bt{np, nq, d_pieces, d_parts, reinterpret_cast<double*>(buf.d_buf + o_pm),
+                                      px_bytes ? reinterpret_cast<double*>(buf.d_buf + o_px) : nullptr, reinterpret_cast<double*>(buf.d_buf + o_out)};
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(Piece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(Part), hipMemcpyHostToDevice, st));
+        launch(bt);
         HIPCHK(hipGetLastError());
-        val.resize(nq);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 8, hipMemcpyDeviceToHost, st));
+        val.resize(nq * out_doubles);
+        HIPCHK(hipMemcpyAsync(val.data(), bt.out, nq * out_doubles * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
-            double s = 0.0;
-            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) s += val[(size_t) k];
-            log_p_host[j] = s;
-        }
+        for (int64_t j = j0; j < j1; j++)      // the parts of a job in chunk order
+            fold(j, jc.parts.data(), val.data(), jc.job_p0[(size_t) (j - j0)], jc.job_p0[(size_t) (j - j0) + 1]);
         j0 = j1;
     }
     return HF_OK;
+}
+
+// exact interval probabilities (hf_interval.h): k_iv_piece multiplies the pieces, k_iv_chain every part's vectors through them, a job is
+// the sum of its parts
+int hf_get_interval_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, double* log_p_host) {
+    const std::string who = "hf_get_interval_log_probs";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
+    int rc = rg_check(ctx, who, n, !first || !last || !state_mask || !log_p_host, first, last, state_mask);
+    if (rc) return rc;
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
+    return rg_run<IvPiece, IvPart, HF_IV_PIECE>(ctx, who, ctx->iv, n, first, last, HF_IV_BATCH_PIECES, HF_IV_BATCH_PARTS, 32 * 8, 2 * 4, 1,
+        [&](int64_t j, int c, int64_t a, int64_t b) { return IvPart{a, b, 0, 0, state_mask[j], c}; },
+        [](const IvPart& pt, int64_t t, int len) { return IvPiece{t, len, pt.mask}; },
+        [&](const RgBatch<IvPiece, IvPart>& bt) {
+            int* d_pe = reinterpret_cast<int*>(bt.px);
+            by_algo(ctx->tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                if (bt.np) hipLaunchKernelGGL(k_iv_piece<SEQ>, bt.piece_grid(), dim3(64), 0, st, bt.pieces, pv, bt.pm, d_pe);
+                hipLaunchKernelGGL(k_iv_chain<SEQ>, bt.chain_grid(), dim3(64), 0, st, (int) bt.nq, bt.parts, bt.pm, d_pe, pv, bt.out);
+            });
+        },
+        [&](int64_t j, const IvPart*, const double* val, int64_t k0, int64_t k1) {
+            double s = 0.0;
+            for (int64_t k = k0; k < k1; k++) s += val[k];
+            log_p_host[j] = s;
+        });
 }
 
 
@@ -2602,20 +2650,15 @@ int hf_get_alpha_stats(hf_ctx* ctx, double* out_host) {
         hipStream_t st = ps.last_stream;
         const AlBlock* blocks = reinterpret_cast<const AlBlock*>(al.d_blocks);
         if (al.n_blocks > 0) {
-            if (seq)
-                hipLaunchKernelGGL(k_alpha_pairs<true>, dim3((unsigned) al.n_blocks), dim3(HF_AL_THREADS), 0, st, blocks, al.d_pair_t, al.d_pair_c,
-                                   tr.d_rec, tr.d_beta, ps.d_params, (const int32_t*) nullptr, (const double*) nullptr, (const double*) nullptr, ps.d_E,
-                                   (const int32_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr, tr.d_off, tr.d_chunk_tile0,
-                                   ps.d_f, ps.d_b, al.d_part);
-            else {
-                // (the rows of A of a segment pass are the jobs of the track's list: enqueue_pass)
+            if (!seq) {      // (the rows of A of a segment pass are the jobs of the track's list: enqueue_pass)
                 const int nj = tr.tabwork.n_jobs;
                 hipLaunchKernelGGL(k_alpha_terms, dim3((unsigned) ((nj + 255) / 256)), dim3(256), 0, st, nj, tr.d_jobs, ps.d_params, al.d_terms);
-                hipLaunchKernelGGL(k_alpha_pairs<false>, dim3((unsigned) al.n_blocks), dim3(HF_AL_THREADS), 0, st, blocks, al.d_pair_t, al.d_pair_c,
-                                   tr.d_rec, tr.d_beta, ps.d_params, tr.d_arow, ps.d_lutA, al.d_terms, (const double*) nullptr, tr.d_pos, tr.d_pos_f,
-                                   ps.d_recs_all, (const int64_t*) nullptr, (const int32_t*) nullptr, (const double*) nullptr,
-                                   (const double*) nullptr, al.d_part);
             }
+            const PassView pv = view_of(ctx);
+            by_algo(tr, [&](auto S) {
+                hipLaunchKernelGGL(k_alpha_pairs<decltype(S)::value>, dim3((unsigned) al.n_blocks), dim3(HF_AL_THREADS), 0, st, blocks, al.d_pair_t,
+                                   al.d_pair_c, tr.d_beta, seq ? nullptr : al.d_terms, pv, al.d_part);
+            });
         }
         hipLaunchKernelGGL(k_alpha_sum, dim3((unsigned) tr.R), dim3(HF_AL_SUM_THREADS), 0, st, al.d_rblk0, al.d_part, al.d_out);
         HIPCHK(hipGetLastError());
@@ -2628,225 +2671,72 @@ int hf_get_alpha_stats(hf_ctx* ctx, double* out_host) {
 }
 
 
-// ------------------------------------------------------------------------------------------
-// exact mean and variance of label totals (hf_moments.h) over the last full pass: the host cuts every job into chunk-local parts and every
-// part's interior windows into pieces as the interval getter does, k_mo_piece multiplies the pieces' jets, k_mo_chain carries every part's
-// vectors through them, the host sums the parts of a job in chunk order.  Last in the file, so that no pass kernel's code moves.
-// ------------------------------------------------------------------------------------------
-#include "hf_moments.h"
-
-// pieces and parts per device batch (a piece's triple is 384 bytes: 96 MB of them at most; a job is never split across batches, and a
-// batch holds at least one job)
-#define HF_MO_BATCH_PIECES (1 << 18)
-#define HF_MO_BATCH_PARTS (1 << 20)
-
+// exact mean and variance of label totals (hf_moments.h): k_mo_piece multiplies the pieces' jets, k_mo_chain carries every part's vectors
+// through them, a job's mean and variance are the sums of its parts'
 int hf_get_count_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, const int32_t* region,
                          int unit, double* mean_host, double* var_host) {
-    if (!ctx) return set_err(HF_E_ARG, "hf_get_count_moments: bad argument");
+    const std::string who = "hf_get_count_moments";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
     const Track& tr = ctx->tr;
-    Pass& ps = ctx->pass;
-    if (n < 0) return set_err(HF_E_ARG, "hf_get_count_moments: n < 0");
-    if (unit != HF_COUNT_WINDOWS && unit != HF_COUNT_BASES) return set_err(HF_E_ARG, "hf_get_count_moments: unknown unit");
-    if (n > 0 && (!first || !last || !state_mask || !mean_host || !var_host)) return set_err(HF_E_ARG, "hf_get_count_moments: NULL array");
-    if (!ps.have_full)
-        return set_err(HF_E_ARG, "hf_get_count_moments: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    for (int64_t i = 0; i < n; i++) {
-        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
-            return set_err(HF_E_ARG, "hf_get_count_moments: bad range (job " + std::to_string(i) + ")");
-        if (!in_chunks(tr, first[i], last[i]))
-            return set_err(HF_E_ARG, "hf_get_count_moments: a window outside every chunk (job " + std::to_string(i) + ")");
-        if (state_mask[i] < 1 || state_mask[i] > 15)
-            return set_err(HF_E_ARG, "hf_get_count_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
-        if (region && (region[i] < -1 || region[i] >= tr.R))
-            return set_err(HF_E_ARG, "hf_get_count_moments: region must be -1..n_regions-1 (job " + std::to_string(i) + ")");
-    }
-    HIPCHK(hipSetDevice(tr.device));
-    if (n == 0) return HF_OK;
-    const bool seq = tr.algo == HF_ALGO_SEQ;
-    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_count_moments: the last pass kept no pair records");
-    if (!seq) {
-        const int rc = pass_all_records(ps);
-        if (rc) return rc;
-    }
-    hipStream_t st = ps.last_stream;
+    int rc = rg_check(ctx, who, n, !first || !last || !state_mask || !mean_host || !var_host, first, last, state_mask, region,
+                      unit != HF_COUNT_WINDOWS && unit != HF_COUNT_BASES ? "unknown unit" : nullptr);
+    if (rc) return rc;
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
     const int W = unit == HF_COUNT_BASES ? tr.meta.window_len : 0;
-    if (unit == HF_COUNT_BASES && W < 1) return set_err(HF_E_ARG, "hf_get_count_moments: the context has no window length");
-    MomentBufs& mb = ctx->mo;
-    MoFB fb{};
-    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
-    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
-    std::vector<MoPiece> pieces;
-    std::vector<MoPart> parts;
-    std::vector<int64_t> job_p0;
-    std::vector<double> val;
-    for (int64_t j0 = 0; j0 < n;) {
-        // the jobs of this batch, cut into parts and pieces
-        pieces.clear(); parts.clear(); job_p0.clear();
-        int64_t j1 = j0;
-        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
-            job_p0.push_back((int64_t) parts.size());
-            const int mask = state_mask[j1], reg = region ? region[j1] : -1;
-            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
-            for (int64_t a = first[j1]; a <= last[j1]; c++) {
-                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
-                const int64_t o = tr.h_off[(size_t) c], b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
-                const int cs = tr.h_cs[(size_t) c], ce = tr.h_ce[(size_t) c];
-                MoPart pt{a, b, (int) pieces.size(), 0, mask, reg, c, (int) (a - o), cs, ce};
-                for (int64_t t = a + 1; t <= b;) {
-                    const int64_t e = std::min<int64_t>(b, (t / HF_MO_PIECE + 1) * HF_MO_PIECE - 1);
-                    pieces.push_back(MoPiece{t, (int) (e - t + 1), mask, reg, c, (int) (t - o), cs, ce});
-                    t = e + 1;
-                }
-                pt.p1 = (int) pieces.size();
-                parts.push_back(pt);
-                a = b + 1;
-            }
-            j1++;
-        }
-        job_p0.push_back((int64_t) parts.size());
-        const size_t np = pieces.size(), nq = parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(MoPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(MoPart));
-        const size_t o_mean = o_pm + Slab::granule(np * 48 * 8), o_out = o_mean + Slab::granule(np * 8), bytes = o_out + Slab::granule(nq * 16);
-        if (bytes > mb.cap) {
-            mb.release();
-            if (hipMalloc((void**) &mb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); mb.d_buf = nullptr;
-                return set_err(HF_E_HIP, "hf_get_count_moments: out of device memory"); }
-            mb.cap = bytes;
-        }
-        MoPiece* d_pieces = reinterpret_cast<MoPiece*>(mb.d_buf);
-        MoPart* d_parts = reinterpret_cast<MoPart*>(mb.d_buf + o_parts);
-        double* d_pm = reinterpret_cast<double*>(mb.d_buf + o_pm);
-        double* d_mean = reinterpret_cast<double*>(mb.d_buf + o_mean);
-        double* d_out = reinterpret_cast<double*>(mb.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(MoPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(MoPart), hipMemcpyHostToDevice, st));
-        if (seq) {
-            if (np) hipLaunchKernelGGL(k_mo_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, W, (const int32_t*) nullptr,
-                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_pm, d_mean);
-            hipLaunchKernelGGL(k_mo_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, W, tr.d_rec, d_pm, d_mean, fb, d_out);
-        } else {
-            if (np) hipLaunchKernelGGL(k_mo_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, W, tr.d_arow, ps.d_lutA, tr.d_rec,
-                                       (const double*) nullptr, (const DevParams*) nullptr, fb, d_pm, d_mean);
-            hipLaunchKernelGGL(k_mo_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, W, tr.d_rec, d_pm, d_mean, fb, d_out);
-        }
-        HIPCHK(hipGetLastError());
-        val.resize(nq * 2);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
+    if (unit == HF_COUNT_BASES && W < 1) return set_err(HF_E_ARG, who + ": the context has no window length");
+    return rg_run<MoPiece, MoPart, HF_MO_PIECE>(ctx, who, ctx->mo, n, first, last, HF_MO_BATCH_PIECES, HF_MO_BATCH_PARTS, 48 * 8, 8, 2,
+        [&](int64_t j, int c, int64_t a, int64_t b) {
+            return MoPart{a, b, 0, 0, state_mask[j], region ? region[j] : -1, c, (int) (a - tr.h_off[(size_t) c]), tr.h_cs[(size_t) c], tr.h_ce[(size_t) c]};
+        },
+        [](const MoPart& pt, int64_t t, int len) { return MoPiece{t, len, pt.mask, pt.region, pt.c, pt.ka + (int) (t - pt.a), pt.cs, pt.ce}; },
+        [&](const RgBatch<MoPiece, MoPart>& bt) {
+            by_algo(tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                if (bt.np) hipLaunchKernelGGL(k_mo_piece<SEQ>, bt.piece_grid(), dim3(64), 0, st, bt.pieces, W, pv, bt.pm, bt.px);
+                hipLaunchKernelGGL(k_mo_chain<SEQ>, bt.chain_grid(), dim3(64), 0, st, (int) bt.nq, bt.parts, W, bt.pm, bt.px, pv, bt.out);
+            });
+        },
+        [&](int64_t j, const MoPart*, const double* val, int64_t k0, int64_t k1) {
             double m = 0.0, v = 0.0;
-            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) { m += val[(size_t) k * 2]; v += val[(size_t) k * 2 + 1]; }
+            for (int64_t k = k0; k < k1; k++) { m += val[(size_t) k * 2]; v += val[(size_t) k * 2 + 1]; }
             mean_host[j] = m; var_host[j] = v;
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }
 
 
-// ------------------------------------------------------------------------------------------
-// exact mean and variance of block counts (hf_runs.h) over the last full pass: the host cuts every job into chunk-local parts and every
-// part's interior windows into pieces as the count moments do, k_run_piece multiplies the pieces' jets, k_run_chain carries every part's
-// vectors through them and writes the part's seven numbers, the host stitches the parts of a job left to right (the joins between
-// chunks: include/hmm_flagger_hip.h).  Last in the file, so that no other kernel's code moves.
-// ------------------------------------------------------------------------------------------
-#include "hf_runs.h"
-
+// exact mean and variance of block counts (hf_runs.h): k_run_piece multiplies the pieces' jets, k_run_chain carries every part's vectors
+// through them and writes the part's seven numbers, the host stitches the parts of a job left to right (the joins between chunks:
+// include/hmm_flagger_hip.h)
 int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, const uint8_t* joined,
                        double* mean_host, double* var_host) {
-    if (!ctx) return set_err(HF_E_ARG, "hf_get_run_moments: bad argument");
+    const std::string who = "hf_get_run_moments";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
     const Track& tr = ctx->tr;
-    Pass& ps = ctx->pass;
-    if (n < 0) return set_err(HF_E_ARG, "hf_get_run_moments: n < 0");
-    if (n > 0 && (!first || !last || !state_mask || !mean_host || !var_host)) return set_err(HF_E_ARG, "hf_get_run_moments: NULL array");
-    if (!ps.have_full)
-        return set_err(HF_E_ARG, "hf_get_run_moments: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    if (joined && tr.C > 0 && joined[0]) return set_err(HF_E_ARG, "hf_get_run_moments: joined[0] must be 0 (the first chunk continues nothing)");
-    for (int64_t i = 0; i < n; i++) {
-        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N)
-            return set_err(HF_E_ARG, "hf_get_run_moments: bad range (job " + std::to_string(i) + ")");
-        if (!in_chunks(tr, first[i], last[i]))
-            return set_err(HF_E_ARG, "hf_get_run_moments: a window outside every chunk (job " + std::to_string(i) + ")");
-        if (state_mask[i] < 1 || state_mask[i] > 15)
-            return set_err(HF_E_ARG, "hf_get_run_moments: state_mask must be 1..15 (job " + std::to_string(i) + ")");
-    }
-    HIPCHK(hipSetDevice(tr.device));
-    if (n == 0) return HF_OK;
-    const bool seq = tr.algo == HF_ALGO_SEQ;
-    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, "hf_get_run_moments: the last pass kept no pair records");
-    if (!seq) {
-        const int rc = pass_all_records(ps);
-        if (rc) return rc;
-    }
-    hipStream_t st = ps.last_stream;
-    RunBufs& rb = ctx->rn;
-    MoFB fb{};
-    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
-    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
-    std::vector<RnPiece> pieces;
-    std::vector<RnPart> parts;
-    std::vector<int64_t> job_p0;
-    std::vector<double> val;
-    for (int64_t j0 = 0; j0 < n;) {
-        // the jobs of this batch, cut into parts and pieces
-        pieces.clear(); parts.clear(); job_p0.clear();
-        int64_t j1 = j0;
-        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
-            job_p0.push_back((int64_t) parts.size());
-            const int mask = state_mask[j1];
-            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
-            for (int64_t a = first[j1]; a <= last[j1]; c++) {
-                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
-                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
-                RnPart pt{a, b, (int) pieces.size(), 0, mask, c};
-                for (int64_t t = a + 1; t <= b;) {
-                    const int64_t e = std::min<int64_t>(b, (t / HF_RN_PIECE + 1) * HF_RN_PIECE - 1);
-                    pieces.push_back(RnPiece{t, (int) (e - t + 1), mask, c});
-                    t = e + 1;
-                }
-                pt.p1 = (int) pieces.size();
-                parts.push_back(pt);
-                a = b + 1;
-            }
-            j1++;
-        }
-        job_p0.push_back((int64_t) parts.size());
-        const size_t np = pieces.size(), nq = parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(RnPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(RnPart));
-        const size_t o_xi = o_pm + Slab::granule(np * 48 * 8), o_out = o_xi + Slab::granule(np * 8),
-                     bytes = o_out + Slab::granule(nq * HF_RN_OUT * 8);
-        if (bytes > rb.cap) {
-            rb.release();
-            if (hipMalloc((void**) &rb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); rb.d_buf = nullptr;
-                return set_err(HF_E_HIP, "hf_get_run_moments: out of device memory"); }
-            rb.cap = bytes;
-        }
-        RnPiece* d_pieces = reinterpret_cast<RnPiece*>(rb.d_buf);
-        RnPart* d_parts = reinterpret_cast<RnPart*>(rb.d_buf + o_parts);
-        double* d_pm = reinterpret_cast<double*>(rb.d_buf + o_pm);
-        double* d_xi = reinterpret_cast<double*>(rb.d_buf + o_xi);
-        double* d_out = reinterpret_cast<double*>(rb.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(RnPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(RnPart), hipMemcpyHostToDevice, st));
-        if (seq) {
-            if (np) hipLaunchKernelGGL(k_run_piece<true>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, (const int32_t*) nullptr,
-                                       (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_pm, d_xi);
-            hipLaunchKernelGGL(k_run_chain<true>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_xi, fb, d_out);
-        } else {
-            if (np) hipLaunchKernelGGL(k_run_piece<false>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, tr.d_arow, ps.d_lutA, tr.d_rec,
-                                       (const double*) nullptr, (const DevParams*) nullptr, fb, d_pm, d_xi);
-            hipLaunchKernelGGL(k_run_chain<false>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_xi, fb, d_out);
-        }
-        HIPCHK(hipGetLastError());
-        val.resize(nq * HF_RN_OUT);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * HF_RN_OUT * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {
+    int rc = rg_check(ctx, who, n, !first || !last || !state_mask || !mean_host || !var_host, first, last, state_mask, nullptr, nullptr,
+                      joined && tr.C > 0 && joined[0] ? "joined[0] must be 0 (the first chunk continues nothing)" : nullptr);
+    if (rc) return rc;
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
+    return rg_run<RnPiece, RnPart, HF_RN_PIECE>(ctx, who, ctx->rn, n, first, last, HF_MO_BATCH_PIECES, HF_MO_BATCH_PARTS, 48 * 8, 8, HF_RN_OUT,
+        [&](int64_t j, int c, int64_t a, int64_t b) { return RnPart{a, b, 0, 0, state_mask[j], c}; },
+        [](const RnPart& pt, int64_t t, int len) { return RnPiece{t, len, pt.mask, pt.c}; },
+        [&](const RgBatch<RnPiece, RnPart>& bt) {
+            by_algo(tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                if (bt.np) hipLaunchKernelGGL(k_run_piece<SEQ>, bt.piece_grid(), dim3(64), 0, st, bt.pieces, pv, bt.pm, bt.px);
+                hipLaunchKernelGGL(k_run_chain<SEQ>, bt.chain_grid(), dim3(64), 0, st, (int) bt.nq, bt.parts, bt.pm, bt.px, pv, bt.out);
+            });
+        },
+        [&](int64_t j, const RnPart* parts, const double* val, int64_t k0, int64_t k1) {
             // the parts of a job in chunk order.  x = (E[R], Var(R), s, e, Cov(R, E0), Cov(R, S0), Cov(S0, E0)) of a part; part k is joined
             // to part k - 1 when it lies in the next chunk and that chunk continues the one before.  Three sums, each left to right:
             //   mean = sum E[R] - sum_joined q,  var = sum Var(R) + sum_joined [...] + 2 sum_{both joined} [...]   (q = e_{k-1} s_k)
             // so a job without a join is the plain sum of its parts.
-            const int64_t k0 = job_p0[(size_t) (j - j0)], k1 = job_p0[(size_t) (j - j0) + 1];
             double m = 0.0, mq = 0.0, v = 0.0, vj = 0.0, vjj = 0.0;
             bool prev_join = false;
             for (int64_t k = k0; k < k1; k++) {
@@ -2869,52 +2759,19 @@ int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
             double var = (v + vj) + 2.0 * vjj;
             if (!(var > 0.0)) var = 0.0;      // (a negative rounding residue)
             mean_host[j] = m - mq; var_host[j] = var;
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }
 
 
-// ------------------------------------------------------------------------------------------
-// exact path entropy and labelling log-probability (hf_entropy.h) over the last full pass: the host cuts every job into chunk-local parts
-// and every part's interior windows into pieces as the run moments do, k_ent_piece sums the pieces' local terms, k_ent_chain adds every
-// part's first window and its piece sums, the host sums the parts of a job in chunk order.  Last in the file, so that no other kernel's
-// code moves.
-// ------------------------------------------------------------------------------------------
-#include "hf_entropy.h"
-
-// what the three entry points share: the state of the pass they answer for
-static int ent_ready(hf_ctx* ctx, const char* who, MoFB& fb) {
-    const Track& tr = ctx->tr;
-    Pass& ps = ctx->pass;
-    const bool seq = tr.algo == HF_ALGO_SEQ;
-    if (!seq && (!ps.fb_recs || !tr.d_arow)) return set_err(HF_E_ARG, std::string(who) + ": the last pass kept no pair records");
-    if (!seq) {
-        const int rc = pass_all_records(ps);
-        if (rc) return rc;
-    }
-    fb = MoFB{};
-    if (seq) { fb.off = tr.d_off; fb.chunk_tile0 = tr.d_chunk_tile0; fb.F = ps.d_f; fb.B = ps.d_b; }
-    else { fb.pos = tr.d_pos; fb.pos_f = tr.d_pos_f; fb.recs = ps.d_recs_all; }
-    return HF_OK;
-}
-
+// exact path entropy and labelling log-probability (hf_entropy.h): k_ent_piece sums the pieces' local terms, k_ent_chain adds every part's
+// first window and its piece sums, a job is the sum of its parts.
 // labels == nullptr: the path entropy of every job; else the log-probability of the labelling inside every job's range
-static int ent_jobs(hf_ctx* ctx, const char* who, int64_t n, const int64_t* first, const int64_t* last, const int8_t* labels, bool with_labels,
+static int ent_jobs(hf_ctx* ctx, const std::string& who, int64_t n, const int64_t* first, const int64_t* last, const int8_t* labels, bool with_labels,
                     double* out_host) {
-    const std::string name(who);
-    if (!ctx) return set_err(HF_E_ARG, name + ": bad argument");
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
     const Track& tr = ctx->tr;
-    Pass& ps = ctx->pass;
-    if (n < 0) return set_err(HF_E_ARG, name + ": n < 0");
-    if (n > 0 && (!first || !last || !out_host || (with_labels && !labels))) return set_err(HF_E_ARG, name + ": NULL array");
-    if (!ps.have_full)
-        return set_err(HF_E_ARG, name + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    for (int64_t i = 0; i < n; i++) {
-        if (first[i] < 0 || first[i] > last[i] || last[i] >= tr.N) return set_err(HF_E_ARG, name + ": bad range (job " + std::to_string(i) + ")");
-        if (!in_chunks(tr, first[i], last[i])) return set_err(HF_E_ARG, name + ": a window outside every chunk (job " + std::to_string(i) + ")");
-    }
+    int rc = rg_check(ctx, who, n, !first || !last || !out_host || (with_labels && !labels), first, last, nullptr);
+    if (rc) return rc;
     // the labels of the call: the union of the ranges, and nothing outside it, is looked at; lo .. hi is the span of the union
     std::vector<int8_t> lab;
     int64_t lo = 0, hi = -1;
@@ -2928,100 +2785,39 @@ static int ent_jobs(hf_ctx* ctx, const char* who, int64_t n, const int64_t* firs
         int64_t done = lo;                        // every window below `done` is checked and copied
         for (const auto& r : rg) {
             for (int64_t t = std::max(done, r.first); t <= r.second; t++) {
-                if (labels[t] < 0 || labels[t] > 3) return set_err(HF_E_ARG, name + ": a label outside 0..3 (window " + std::to_string(t) + ")");
+                if (labels[t] < 0 || labels[t] > 3) return set_err(HF_E_ARG, who + ": a label outside 0..3 (window " + std::to_string(t) + ")");
                 lab[(size_t) (t - lo)] = labels[t];
             }
             done = std::max(done, r.second + 1);
         }
     }
-    HIPCHK(hipSetDevice(tr.device));
-    if (n == 0) return HF_OK;
-    const bool seq = tr.algo == HF_ALGO_SEQ;
-    MoFB fb;
-    const int rc0 = ent_ready(ctx, who, fb);
-    if (rc0) return rc0;
-    hipStream_t st = ps.last_stream;
-    EntBufs& eb = ctx->en;
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
     if (with_labels) {
-        if (lab.size() > eb.lab_cap) {
-            if (eb.d_lab) hipFree(eb.d_lab);
-            eb.d_lab = nullptr; eb.lab_cap = 0;
-            if (hipMalloc((void**) &eb.d_lab, lab.size()) != hipSuccess) { (void) hipGetLastError(); eb.d_lab = nullptr;
-                return set_err(HF_E_HIP, name + ": out of device memory"); }
-            eb.lab_cap = lab.size();
-        }
-        HIPCHK(hipMemcpyAsync(eb.d_lab, lab.data(), lab.size(), hipMemcpyHostToDevice, st));
+        rc = ctx->en_lab.reserve(lab.size(), who);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(ctx->en_lab.d_buf, lab.data(), lab.size(), hipMemcpyHostToDevice, st));
     }
-    std::vector<EnPiece> pieces;
-    std::vector<EnPart> parts;
-    std::vector<int64_t> job_p0;
-    std::vector<double> val;
-    for (int64_t j0 = 0; j0 < n;) {
-        // the jobs of this batch, cut into parts and pieces
-        pieces.clear(); parts.clear(); job_p0.clear();
-        int64_t j1 = j0;
-        while (j1 < n && (j1 == j0 || (pieces.size() < HF_MO_BATCH_PIECES && parts.size() < HF_MO_BATCH_PARTS))) {
-            job_p0.push_back((int64_t) parts.size());
-            int c = (int) (std::upper_bound(tr.h_off.begin(), tr.h_off.end(), first[j1]) - tr.h_off.begin()) - 1;
-            for (int64_t a = first[j1]; a <= last[j1]; c++) {
-                while (tr.h_off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
-                const int64_t b = std::min<int64_t>(last[j1], tr.h_off[(size_t) c + 1] - 1);
-                EnPart pt{a, (int) pieces.size(), 0, c, 0};
-                for (int64_t t = a + 1; t <= b;) {
-                    const int64_t e = std::min<int64_t>(b, (t / HF_EN_PIECE + 1) * HF_EN_PIECE - 1);
-                    pieces.push_back(EnPiece{t, (int) (e - t + 1), c});
-                    t = e + 1;
-                }
-                pt.p1 = (int) pieces.size();
-                parts.push_back(pt);
-                a = b + 1;
-            }
-            j1++;
-        }
-        job_p0.push_back((int64_t) parts.size());
-        const size_t np = pieces.size(), nq = parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(EnPiece)), o_px = o_parts + Slab::granule(nq * sizeof(EnPart));
-        const size_t o_out = o_px + Slab::granule(np * 8), bytes = o_out + Slab::granule(nq * 8);
-        if (bytes > eb.cap) {
-            if (eb.d_buf) hipFree(eb.d_buf);
-            eb.d_buf = nullptr; eb.cap = 0;
-            if (hipMalloc((void**) &eb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); eb.d_buf = nullptr;
-                return set_err(HF_E_HIP, name + ": out of device memory"); }
-            eb.cap = bytes;
-        }
-        EnPiece* d_pieces = reinterpret_cast<EnPiece*>(eb.d_buf);
-        EnPart* d_parts = reinterpret_cast<EnPart*>(eb.d_buf + o_parts);
-        double* d_px = reinterpret_cast<double*>(eb.d_buf + o_px);
-        double* d_out = reinterpret_cast<double*>(eb.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, pieces.data(), np * sizeof(EnPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, parts.data(), nq * sizeof(EnPart), hipMemcpyHostToDevice, st));
-        const dim3 gp((unsigned) np), gc((unsigned) ((nq + 63) / 64)), blk(64);
-        const int32_t* arow = seq ? nullptr : tr.d_arow;
-        const double* lutA = seq ? nullptr : ps.d_lutA;
-        const double* E = seq ? ps.d_E : nullptr;
-        const DevParams* Pm = seq ? ps.d_params : nullptr;
-        const int8_t* d_lab = eb.d_lab;
-        const long long lab0 = lo;
-#define HF_EN_LAUNCH(SEQ, LAB)                                                                                                         \
-        do {                                                                                                                           \
-            if (np) hipLaunchKernelGGL((k_ent_piece<SEQ, LAB>), gp, blk, 0, st, d_pieces, arow, lutA, tr.d_rec, E, Pm, fb, d_lab, lab0, d_px); \
-            hipLaunchKernelGGL((k_ent_chain<SEQ, LAB>), gc, blk, 0, st, (int) nq, d_parts, d_px, fb, d_lab, lab0, d_out);                  \
-        } while (0)
-        if (seq) { if (with_labels) HF_EN_LAUNCH(true, true); else HF_EN_LAUNCH(true, false); }
-        else { if (with_labels) HF_EN_LAUNCH(false, true); else HF_EN_LAUNCH(false, false); }
-#undef HF_EN_LAUNCH
-        HIPCHK(hipGetLastError());
-        val.resize(nq);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {      // the parts of a job in chunk order
+    const int8_t* d_lab = reinterpret_cast<const int8_t*>(ctx->en_lab.d_buf);
+    const long long lab0 = lo;
+    return rg_run<EnPiece, EnPart, HF_EN_PIECE>(ctx, who, ctx->en, n, first, last, HF_MO_BATCH_PIECES, HF_MO_BATCH_PARTS, 8, 0, 1,
+        [&](int64_t, int c, int64_t a, int64_t) { return EnPart{a, 0, 0, c, 0}; },
+        [](const EnPart& pt, int64_t t, int len) { return EnPiece{t, len, pt.c}; },
+        [&](const RgBatch<EnPiece, EnPart>& bt) {
+            auto launch = [&](auto S, auto LB) {
+                constexpr bool SEQ = decltype(S)::value, LAB = decltype(LB)::value;
+                if (bt.np) hipLaunchKernelGGL((k_ent_piece<SEQ, LAB>), bt.piece_grid(), dim3(64), 0, st, bt.pieces, pv, d_lab, lab0, bt.pm);
+                hipLaunchKernelGGL((k_ent_chain<SEQ, LAB>), bt.chain_grid(), dim3(64), 0, st, (int) bt.nq, bt.parts, bt.pm, pv, d_lab, lab0, bt.out);
+            };
+            by_algo(tr, [&](auto S) { if (with_labels) launch(S, std::true_type{}); else launch(S, std::false_type{}); });
+        },
+        [&](int64_t j, const EnPart*, const double* val, int64_t k0, int64_t k1) {
             double v = 0.0;
-            for (int64_t k = job_p0[(size_t) (j - j0)]; k < job_p0[(size_t) (j - j0) + 1]; k++) v += val[(size_t) k];
+            for (int64_t k = k0; k < k1; k++) v += val[k];
             out_host[j] = v;
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }
 
 int hf_get_path_entropy(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, double* entropy_host) {
@@ -3036,42 +2832,30 @@ int hf_get_path_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const in
 #define HF_EN_PROFILE_BATCH ((int64_t) 1 << 22)
 
 int hf_get_entropy_profile(hf_ctx* ctx, int64_t first, int64_t n, double* marg_host, double* cond_host) {
-    if (!ctx) return set_err(HF_E_ARG, "hf_get_entropy_profile: bad argument");
+    const std::string who = "hf_get_entropy_profile";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
     const Track& tr = ctx->tr;
-    Pass& ps = ctx->pass;
-    if (!marg_host && !cond_host) return set_err(HF_E_ARG, "hf_get_entropy_profile: both output arrays are NULL");
-    if (first < 0 || n < 0 || first > tr.N || n > tr.N - first) return set_err(HF_E_ARG, "hf_get_entropy_profile: bad range");
-    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, "hf_get_entropy_profile: the range holds a window outside every chunk");
-    if (!ps.have_full)
-        return set_err(HF_E_ARG, "hf_get_entropy_profile: no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
-    HIPCHK(hipSetDevice(tr.device));
-    if (n == 0) return HF_OK;
-    const bool seq = tr.algo == HF_ALGO_SEQ;
-    MoFB fb;
-    const int rc0 = ent_ready(ctx, "hf_get_entropy_profile", fb);
-    if (rc0) return rc0;
-    hipStream_t st = ps.last_stream;
-    EntBufs& eb = ctx->en;
+    if (!marg_host && !cond_host) return set_err(HF_E_ARG, who + ": both output arrays are NULL");
+    if (first < 0 || n < 0 || first > tr.N || n > tr.N - first) return set_err(HF_E_ARG, who + ": bad range");
+    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, who + ": the range holds a window outside every chunk");
+    if (!ctx->pass.have_full)
+        return set_err(HF_E_ARG, who + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    PassView pv;
+    int rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
     const int64_t nb = std::min<int64_t>(n, HF_EN_PROFILE_BATCH);
-    const size_t o_cond = Slab::granule((size_t) nb * 8), bytes = 2 * o_cond;
-    if (bytes > eb.cap) {
-        if (eb.d_buf) hipFree(eb.d_buf);
-        eb.d_buf = nullptr; eb.cap = 0;
-        if (hipMalloc((void**) &eb.d_buf, bytes) != hipSuccess) { (void) hipGetLastError(); eb.d_buf = nullptr;
-            return set_err(HF_E_HIP, "hf_get_entropy_profile: out of device memory"); }
-        eb.cap = bytes;
-    }
-    double* d_marg = marg_host ? reinterpret_cast<double*>(eb.d_buf) : nullptr;
-    double* d_cond = cond_host ? reinterpret_cast<double*>(eb.d_buf + o_cond) : nullptr;
+    const size_t o_cond = Slab::granule((size_t) nb * 8);
+    rc = ctx->en.reserve(2 * o_cond, who);
+    if (rc) return rc;
+    double* d_marg = marg_host ? reinterpret_cast<double*>(ctx->en.d_buf) : nullptr;
+    double* d_cond = cond_host ? reinterpret_cast<double*>(ctx->en.d_buf + o_cond) : nullptr;
     for (int64_t i0 = 0; i0 < n; i0 += nb) {
         const int64_t m = std::min<int64_t>(nb, n - i0);
-        const dim3 grid((unsigned) ((m + 255) / 256)), blk(256);
-        if (seq)
-            hipLaunchKernelGGL(k_ent_profile<true>, grid, blk, 0, st, (long long) (first + i0), (long long) m, tr.d_off, tr.C, (const int32_t*) nullptr,
-                               (const double*) nullptr, tr.d_rec, ps.d_E, ps.d_params, fb, d_marg, d_cond);
-        else
-            hipLaunchKernelGGL(k_ent_profile<false>, grid, blk, 0, st, (long long) (first + i0), (long long) m, tr.d_off, tr.C, tr.d_arow, ps.d_lutA,
-                               tr.d_rec, (const double*) nullptr, (const DevParams*) nullptr, fb, d_marg, d_cond);
+        by_algo(tr, [&](auto S) {
+            hipLaunchKernelGGL(k_ent_profile<decltype(S)::value>, dim3((unsigned) ((m + 255) / 256)), dim3(256), 0, st, (long long) (first + i0),
+                               (long long) m, tr.d_off, tr.C, pv, d_marg, d_cond);
+        });
         HIPCHK(hipGetLastError());
         if (marg_host) HIPCHK(hipMemcpyAsync(marg_host + i0, d_marg, (size_t) m * 8, hipMemcpyDeviceToHost, st));
         if (cond_host) HIPCHK(hipMemcpyAsync(cond_host + i0, d_cond, (size_t) m * 8, hipMemcpyDeviceToHost, st));

@@ -7,10 +7,7 @@
 //   N_S = sum_{p in S} sum_{q in S} f_a[p] M_S[p][q] b_b[q],   N = the same with S = all four states
 //   log_p(part) = log N_S - log N;  a job's value is the sum of its parts' in chunk order
 // f, b are the pass's scaled forward and backward vectors (hf_get_forward_backward) and A_t the row the pass multiplied by at window t:
-//   HF_ALGO_SCAN  the pass's deduplicated rows of A (Pass::d_lutA through the track's d_arow; bit 31 marks a chunk-first window), stored
-//                 state-major (o = s * 4 + pre, hf_seg.h HF_PS) and transposed on load
-//   HF_ALGO_SEQ   T_t o e_t: the pass's emission rows (Pass::d_E, k_emit_rows) times the transition row of its own parameter block
-//                 (k_fwd_seq applies (f . T) . e: the same factors)
+// hf_view.h says where either algorithm left them.
 //
 // PIECES.  The host cuts the interior windows (a, b] of every part at global window indices that are multiples of HF_IV_PIECE; a piece
 // therefore depends on its job alone.
@@ -23,33 +20,13 @@
 // The masked and unmasked halves run the same operations, so S = all four states gives exactly 0.  Nothing depends on the other jobs
 // of a call: a job's value is bitwise the same whatever the call holds.
 #pragma once
-#include "hf_decode.h"
+#include "hf_view.h"
 
 #define HF_IV_LANE 8                      // windows per lane of a piece
 #define HF_IV_PIECE (64 * HF_IV_LANE)     // windows per piece at most; pieces are cut at global indices that are multiples of this
 
 struct IvPiece { long long t0; int n, mask; };              // windows t0 .. t0 + n - 1, state mask
 struct IvPart { long long a, b; int p0, p1, mask, c; };     // chunk-local part [a, b] of chunk c, its pieces p0 .. p1 - 1
-
-// the row A_t of the pass at window t (layout [pre * 4 + s])
-template <bool SEQ>
-__device__ __forceinline__ void iv_row(const int32_t* __restrict__ arow, const double* __restrict__ lutA, const uint32_t* __restrict__ rec,
-                                       const double* __restrict__ E, const DevParams* __restrict__ P, int64_t t, double A[16]) {
-    if constexpr (SEQ) {
-        double Tm[16];
-        load_T(P, rec[t], Tm);
-        const double2* __restrict__ src = reinterpret_cast<const double2*>(E) + t * 8;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { const double2 v = src[k]; A[2 * k] = Tm[2 * k] * v.x; A[2 * k + 1] = Tm[2 * k + 1] * v.y; }
-    } else {   // (the table is state-major, o = s * 4 + pre: hf_seg.h HF_PS)
-        const double2* __restrict__ src = reinterpret_cast<const double2*>(lutA) + (int64_t) ((uint32_t) arow[t] & 0x7fffffffu) * 8;
-        double R[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { const double2 v = src[k]; R[2 * k] = v.x; R[2 * k + 1] = v.y; }
-#pragma unroll
-        for (int k = 0; k < 16; k++) A[k] = R[(k & 3) * 4 + (k >> 2)];
-    }
-}
 
 // Q <- Q (x) X, renormalised; returns the exponent taken out
 __device__ __forceinline__ int iv_mul(double Q[16], const double X[16]) {
@@ -63,10 +40,8 @@ __device__ __forceinline__ int iv_mul(double Q[16], const double X[16]) {
 
 // out[g][0..15] = M_S, out[g][16..31] = M; oute[g] = (e_S, e)
 template <bool SEQ>
-__global__ void __launch_bounds__(64) k_iv_piece(const IvPiece* __restrict__ pieces, const int32_t* __restrict__ arow,
-                                                 const double* __restrict__ lutA, const uint32_t* __restrict__ rec,
-                                                 const double* __restrict__ E, const DevParams* __restrict__ P,
-                                                 double* __restrict__ out, int* __restrict__ oute) {
+__global__ void __launch_bounds__(64) k_iv_piece(const IvPiece* __restrict__ pieces, PassView pv, double* __restrict__ out,
+                                                 int* __restrict__ oute) {
     const IvPiece pc = pieces[blockIdx.x];
     const int j = threadIdx.x;
     double QS[16], Q[16];
@@ -77,7 +52,7 @@ __global__ void __launch_bounds__(64) k_iv_piece(const IvPiece* __restrict__ pie
         const int x = j * HF_IV_LANE + i;
         if (x >= pc.n) break;
         double A[16], AS[16];
-        iv_row<SEQ>(arow, lutA, rec, E, P, pc.t0 + x, A);
+        iv_row<SEQ>(pv, pc.t0 + x, A);
 #pragma unroll
         for (int k = 0; k < 16; k++) AS[k] = ((pc.mask >> (k & 3)) & 1) ? A[k] : 0.0;
         eS += iv_mul(QS, AS);
@@ -120,34 +95,16 @@ __device__ __forceinline__ double iv_dot(const double v[4], const double b[4]) {
     return d;
 }
 
-// one thread per part: its log N_S - log N.  f_a, b_b: SCAN from the pair records (b_t: second half of the record at pos[t], f_t: first
-// half of the one at pos_f[t]); SEQ from the tiles of k_fwd_seq / k_bwd_seq (hf_device.h fb_slot)
+// one thread per part: its log N_S - log N
 template <bool SEQ>
 __global__ void __launch_bounds__(64) k_iv_chain(int n_parts, const IvPart* __restrict__ parts, const double* __restrict__ pm,
-                                                 const int* __restrict__ pe, const int32_t* __restrict__ pos, const int32_t* __restrict__ pos_f,
-                                                 const double* __restrict__ recs, const int64_t* __restrict__ off,
-                                                 const int32_t* __restrict__ chunk_tile0, const double* __restrict__ F,
-                                                 const double* __restrict__ B, double* __restrict__ out) {
+                                                 const int* __restrict__ pe, PassView pv, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parts) return;
     const IvPart pt = parts[i];
     double f[4], b[4];
-    if constexpr (SEQ) {
-        const int64_t t0 = off[pt.c];
-        const int tile0 = chunk_tile0[pt.c];
-        const double2* __restrict__ F2 = reinterpret_cast<const double2*>(F);
-        const double2* __restrict__ B2 = reinterpret_cast<const double2*>(B);
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const double2 x = F2[fb_slot_w<HF_SCAN_L>(tile0, pt.a - t0, h)], y = B2[fb_slot_w<HF_SCAN_L>(tile0, pt.b - t0, h)];
-            f[2 * h] = x.x; f[2 * h + 1] = x.y; b[2 * h] = y.x; b[2 * h + 1] = y.y;
-        }
-    } else {
-        const double* __restrict__ rf = recs + (int64_t) pos_f[pt.a] * 8;
-        const double* __restrict__ rb = recs + (int64_t) pos[pt.b] * 8 + 4;
-#pragma unroll
-        for (int s = 0; s < 4; s++) { f[s] = rf[s]; b[s] = rb[s]; }
-    }
+    mo_f<SEQ>(pv, pt.c, pt.a, f);
+    mo_b<SEQ>(pv, pt.c, pt.b, b);
     double vS[4], v[4], bS[4];
 #pragma unroll
     for (int s = 0; s < 4; s++) {

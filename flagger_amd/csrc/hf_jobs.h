@@ -1,0 +1,55 @@
+// hf_jobs.h — how the range getters (hf_get_interval_log_probs, hf_get_count_moments, hf_get_run_moments, hf_get_path_entropy,
+// hf_get_path_log_probs) cut a call's jobs into device work.  Host code only, no HIP header: tests/test_jobcut_cpu.py compiles it with
+// the host compiler (jobcut_check.cpp).
+//
+// THE CUTTING RULE.  A job is a window range [first, last] inside the chunks.  It becomes one PART per chunk it touches, [a, b] = the
+// job's windows in that chunk, in chunk order; chunks without windows are skipped.  A part's interior windows (a, b] become PIECES, cut at
+// global window indices that are multiples of GRID: a piece therefore depends on its job alone, and a part with a == b has none.
+//
+// THE BATCHING RULE.  A call's jobs go to the device in batches, in order: a job joins the batch while the batch holds fewer than
+// cap_pieces pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split.  The caller gives the caps (the
+// getters': HF_IV_BATCH_*, HF_MO_BATCH_* of hf_estep.hip).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+// One batch of a call.  Part has int members p0, p1 (its pieces p0 .. p1 - 1 of the batch), set here; everything else of a record is the
+// getter's: mk_part(job, chunk, a, b) builds a part and mk_piece(part, t, n) a piece of it (windows t .. t + n - 1; what a piece shares
+// with its part is read from the part, once per part).  The vectors are reused from batch to batch.
+template <class Piece, class Part, int64_t GRID>
+struct JobCut {
+    std::vector<Piece> pieces;
+    std::vector<Part> parts;
+    std::vector<int64_t> job_p0;      // the first part of every job of the batch, and the end
+
+    // cuts jobs j0 .. of the n of a call (off: the chunks' first windows and the end); returns the first job of the next batch
+    template <class MkPart, class MkPiece>
+    int64_t cut(const std::vector<int64_t>& off, int64_t n, const int64_t* first, const int64_t* last, int64_t j0, size_t cap_pieces,
+                size_t cap_parts, MkPart&& mk_part, MkPiece&& mk_piece) {
+        pieces.clear(); parts.clear(); job_p0.clear();
+        int64_t j1 = j0;
+        while (j1 < n && (j1 == j0 || (pieces.size() < cap_pieces && parts.size() < cap_parts))) {
+            job_p0.push_back((int64_t) parts.size());
+            int c = (int) (std::upper_bound(off.begin(), off.end(), first[j1]) - off.begin()) - 1;
+            for (int64_t a = first[j1]; a <= last[j1]; c++) {
+                while (off[(size_t) c + 1] <= a) c++;      // (chunks without windows)
+                const int64_t b = std::min<int64_t>(last[j1], off[(size_t) c + 1] - 1);
+                Part pt = mk_part(j1, c, a, b);
+                pt.p0 = (int) pieces.size();
+                for (int64_t t = a + 1; t <= b;) {
+                    const int64_t e = std::min<int64_t>(b, (t / GRID + 1) * GRID - 1);
+                    pieces.push_back(mk_piece(pt, t, (int) (e - t + 1)));
+                    t = e + 1;
+                }
+                pt.p1 = (int) pieces.size();
+                parts.push_back(pt);
+                a = b + 1;
+            }
+            j1++;
+        }
+        job_p0.push_back((int64_t) parts.size());
+        return j1;
+    }
+};

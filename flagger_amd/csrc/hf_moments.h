@@ -26,6 +26,7 @@
 // Nothing depends on the other jobs of a call: a job's two values are bitwise the same whatever the call holds.  S = all four states has
 // d = 0 exactly: var 0.0, mean the sum of the weights.
 #pragma once
+#include "hf_view.h"
 #include "hf_interval.h"
 
 #define HF_MO_LANE 8                      // windows per lane of a piece
@@ -35,34 +36,6 @@
 struct MoPiece { long long t0; int n, mask, region, c, k0, cs, ce; };
 // chunk-local part [a, b] of chunk c (ka = a - the chunk's first window), its pieces p0 .. p1 - 1
 struct MoPart { long long a, b; int p0, p1, mask, region, c, ka, cs, ce; };
-
-// where k_mo_piece / k_mo_chain find a window's f and b: SCAN the pair records (b_t: second half of the record at pos[t], f_t: first half
-// of the one at pos_f[t]); SEQ the tiles of k_fwd_seq / k_bwd_seq (hf_device.h fb_slot)
-struct MoFB {
-    const int32_t* pos; const int32_t* pos_f; const double* recs;
-    const int64_t* off; const int32_t* chunk_tile0; const double* F; const double* B;
-};
-
-template <bool SEQ>
-__device__ __forceinline__ void mo_fb(const MoFB& S, int c, int64_t t, double f[4], double b[4]) {
-    if constexpr (SEQ) {
-        const int64_t w = t - S.off[c];
-        const int tile0 = S.chunk_tile0[c];
-        const double2* __restrict__ F2 = reinterpret_cast<const double2*>(S.F);
-        const double2* __restrict__ B2 = reinterpret_cast<const double2*>(S.B);
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int64_t o = fb_slot_w<HF_SCAN_L>(tile0, w, h);
-            const double2 x = F2[o], y = B2[o];
-            f[2 * h] = x.x; f[2 * h + 1] = x.y; b[2 * h] = y.x; b[2 * h + 1] = y.y;
-        }
-    } else {
-        const double* __restrict__ rf = S.recs + (int64_t) S.pos_f[t] * 8;
-        const double* __restrict__ rb = S.recs + (int64_t) S.pos[t] * 8 + 4;
-#pragma unroll
-        for (int s = 0; s < 4; s++) { f[s] = rf[s]; b[s] = rb[s]; }
-    }
-}
 
 // the weight of window t (k-th of its chunk): 0 outside the region filter, else 1 or the window's bases (W = the window length; 0: count windows)
 __device__ __forceinline__ double mo_weight(const uint32_t* __restrict__ rec, int64_t t, int k, int region, int W, int cs, int ce) {
@@ -134,10 +107,8 @@ __device__ __forceinline__ void mo_mul(double P[16], double P1[16], double P2[16
 
 // out[g][0..15] = P, [16..31] = P', [32..47] = P''; outm[g] = the piece's sum of w_t gamma_t
 template <bool SEQ>
-__global__ void __launch_bounds__(64) k_mo_piece(const MoPiece* __restrict__ pieces, int W, const int32_t* __restrict__ arow,
-                                                 const double* __restrict__ lutA, const uint32_t* __restrict__ rec,
-                                                 const double* __restrict__ E, const DevParams* __restrict__ Pm, MoFB fb,
-                                                 double* __restrict__ out, double* __restrict__ outm) {
+__global__ void __launch_bounds__(64) k_mo_piece(const MoPiece* __restrict__ pieces, int W, PassView pv, double* __restrict__ out,
+                                                 double* __restrict__ outm) {
     const MoPiece pc = pieces[blockIdx.x];
     const int j = threadIdx.x;
     double P[16], P1[16], P2[16], m = 0.0;
@@ -150,9 +121,9 @@ __global__ void __launch_bounds__(64) k_mo_piece(const MoPiece* __restrict__ pie
         if (x >= pc.n) break;
         const int64_t t = pc.t0 + x;
         double A[16], f[4], b[4], d[4];
-        iv_row<SEQ>(arow, lutA, rec, E, Pm, t, A);
-        mo_fb<SEQ>(fb, pc.c, t, f, b);
-        m += mo_centre(f, b, pc.mask, mo_weight(rec, t, pc.k0 + x, pc.region, W, pc.cs, pc.ce), d);
+        iv_row<SEQ>(pv, t, A);
+        mo_fb<SEQ>(pv, pc.c, t, f, b);
+        m += mo_centre(f, b, pc.mask, mo_weight(pv.rec, t, pc.k0 + x, pc.region, W, pc.cs, pc.ce), d);
         mo_step(P, P1, P2, A, d);
     }
 #pragma unroll 1
@@ -176,16 +147,15 @@ __global__ void __launch_bounds__(64) k_mo_piece(const MoPiece* __restrict__ pie
 
 // one thread per part: out[i] = (mean, var)
 template <bool SEQ>
-__global__ void __launch_bounds__(64) k_mo_chain(int n_parts, const MoPart* __restrict__ parts, int W, const uint32_t* __restrict__ rec,
-                                                 const double* __restrict__ pm, const double* __restrict__ pmean, MoFB fb,
-                                                 double* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_mo_chain(int n_parts, const MoPart* __restrict__ parts, int W, const double* __restrict__ pm,
+                                                 const double* __restrict__ pmean, PassView pv, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parts) return;
     const MoPart pt = parts[i];
     double f[4], b[4], fe[4], bb[4], d[4];
-    mo_fb<SEQ>(fb, pt.c, pt.a, f, b);
-    mo_fb<SEQ>(fb, pt.c, pt.b, fe, bb);
-    double mean = mo_centre(f, b, pt.mask, mo_weight(rec, pt.a, pt.ka, pt.region, W, pt.cs, pt.ce), d);
+    mo_fb<SEQ>(pv, pt.c, pt.a, f, b);
+    mo_fb<SEQ>(pv, pt.c, pt.b, fe, bb);
+    double mean = mo_centre(f, b, pt.mask, mo_weight(pv.rec, pt.a, pt.ka, pt.region, W, pt.cs, pt.ce), d);
     double v[4], v1[4], v2[4];
 #pragma unroll
     for (int s = 0; s < 4; s++) { v[s] = f[s]; v1[s] = f[s] * d[s]; v2[s] = (f[s] * d[s]) * d[s]; }

@@ -36,6 +36,7 @@
 // The parts of a job are stitched on the host (hf_get_run_moments in hf_estep.hip), left to right.  Nothing depends on the other jobs of
 // a call.  S = all four states: d_a = 0 and D_t = 0 exactly, so Var(R) = 0.0 and every covariance is 0.0, E[R] = 1.0, s = e = 1.0.
 #pragma once
+#include "hf_view.h"
 #include "hf_moments.h"
 
 #define HF_RN_LANE 8                      // windows per lane of a piece
@@ -87,10 +88,8 @@ __device__ __forceinline__ void rn_step(double P[16], double P1[16], double P2[1
 
 // out[g][0..15] = P, [16..31] = P', [32..47] = P''; outx[g] = the piece's sum of xi_t
 template <bool SEQ>
-__global__ void __launch_bounds__(64) k_run_piece(const RnPiece* __restrict__ pieces, const int32_t* __restrict__ arow,
-                                                  const double* __restrict__ lutA, const uint32_t* __restrict__ rec,
-                                                  const double* __restrict__ E, const DevParams* __restrict__ Pm, MoFB fb,
-                                                  double* __restrict__ out, double* __restrict__ outx) {
+__global__ void __launch_bounds__(64) k_run_piece(const RnPiece* __restrict__ pieces, PassView pv, double* __restrict__ out,
+                                                  double* __restrict__ outx) {
     const RnPiece pc = pieces[blockIdx.x];
     const int j = threadIdx.x;
     double P[16], P1[16], P2[16], m = 0.0;
@@ -99,15 +98,15 @@ __global__ void __launch_bounds__(64) k_run_piece(const RnPiece* __restrict__ pi
     for (int k = 0; k < 16; k++) { P1[k] = 0.0; P2[k] = 0.0; }
     if (j * HF_RN_LANE < pc.n) {
         double fp[4], b[4];
-        mo_fb<SEQ>(fb, pc.c, pc.t0 + j * HF_RN_LANE - 1, fp, b);      // f of the lane's first predecessor
+        mo_fb<SEQ>(pv, pc.c, pc.t0 + j * HF_RN_LANE - 1, fp, b);      // f of the lane's first predecessor
 #pragma unroll 1
         for (int i = 0; i < HF_RN_LANE; i++) {
             const int x = j * HF_RN_LANE + i;
             if (x >= pc.n) break;
             const int64_t t = pc.t0 + x;
             double A[16], f[4];
-            iv_row<SEQ>(arow, lutA, rec, E, Pm, t, A);
-            mo_fb<SEQ>(fb, pc.c, t, f, b);
+            iv_row<SEQ>(pv, t, A);
+            mo_fb<SEQ>(pv, pc.c, t, f, b);
             const double xi = rn_xi(fp, A, b, pc.mask);
             m += xi;
             rn_step(P, P1, P2, A, pc.mask, xi);
@@ -137,13 +136,13 @@ __global__ void __launch_bounds__(64) k_run_piece(const RnPiece* __restrict__ pi
 // one thread per part: out[i][0..6] = E[R], Var(R), s, e, Cov(R, E0), Cov(R, S0), Cov(S0, E0)
 template <bool SEQ>
 __global__ void __launch_bounds__(64) k_run_chain(int n_parts, const RnPart* __restrict__ parts, const double* __restrict__ pm,
-                                                  const double* __restrict__ px, MoFB fb, double* __restrict__ out) {
+                                                  const double* __restrict__ px, PassView pv, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parts) return;
     const RnPart pt = parts[i];
     double f[4], b[4], fe[4], bb[4], d[4], de[4];
-    mo_fb<SEQ>(fb, pt.c, pt.a, f, b);
-    mo_fb<SEQ>(fb, pt.c, pt.b, fe, bb);
+    mo_fb<SEQ>(pv, pt.c, pt.a, f, b);
+    mo_fb<SEQ>(pv, pt.c, pt.b, fe, bb);
     const double s0 = mo_centre(f, b, pt.mask, 1.0, d), e0 = mo_centre(fe, bb, pt.mask, 1.0, de);
     double mean = s0;
     double v[4], v1[4], v2[4], u[4], u1[4], bS[4];

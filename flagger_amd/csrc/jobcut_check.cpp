@@ -1,0 +1,51 @@
+// jobcut_check — the range getters' job cutter (hf_jobs.h) on the host alone, for tests/test_jobcut_cpu.py (make jobcut_check: built with
+// the address and undefined-behaviour sanitizers).
+//   jobcut_check FILE    FILE: cap_pieces cap_parts, the number of chunk offsets and the offsets, the number of jobs and every job's
+//                        first and last window (whitespace-separated integers)
+// Prints rows of seven integers, batch by batch:
+//   0 job batch n_parts n_pieces 0 0      a job and the device batch it lands in
+//   1 job chunk a b p0 p1                 its parts, in order, each followed by
+//   2 job chunk t n g k                   the part's pieces: windows t .. t + n - 1, g = the piece's index and k = the part's in the batch
+#include "hf_jobs.h"
+#include <cstdio>
+
+struct Piece { long long t; int n, c; long long job; };
+struct Part { long long a, b; int p0, p1, c; long long job; };
+
+int main(int argc, char** argv) {
+    FILE* f = argc == 2 ? std::fopen(argv[1], "r") : nullptr;
+    if (!f) { std::fprintf(stderr, "usage: jobcut_check FILE\n"); return 2; }
+    long long cap_pieces, cap_parts, n_off, n;
+    if (std::fscanf(f, "%lld %lld %lld", &cap_pieces, &cap_parts, &n_off) != 3 || cap_pieces < 1 || cap_parts < 1 || n_off < 2) return 2;
+    std::vector<int64_t> off((size_t) n_off);
+    for (auto& o : off) { long long v; if (std::fscanf(f, "%lld", &v) != 1) return 2; o = v; }
+    if (std::fscanf(f, "%lld", &n) != 1 || n < 0) return 2;
+    std::vector<int64_t> first((size_t) n), last((size_t) n);
+    for (long long j = 0; j < n; j++) {
+        long long a, b;
+        if (std::fscanf(f, "%lld %lld", &a, &b) != 2 || a < off.front() || a > b || b >= off.back()) return 2;
+        first[(size_t) j] = a; last[(size_t) j] = b;
+    }
+    std::fclose(f);
+    JobCut<Piece, Part, 512> jc;
+    int batch = 0;
+    for (int64_t j0 = 0; j0 < n; batch++) {
+        const int64_t j1 = jc.cut(off, n, first.data(), last.data(), j0, (size_t) cap_pieces, (size_t) cap_parts,
+                                  [](int64_t j, int c, int64_t a, int64_t b) { return Part{a, b, 0, 0, c, j}; },
+                                  [](const Part& pt, int64_t t, int len) { return Piece{t, len, pt.c, pt.job}; });
+        for (int64_t j = j0; j < j1; j++) {
+            const int64_t k0 = jc.job_p0[(size_t) (j - j0)], k1 = jc.job_p0[(size_t) (j - j0) + 1];
+            std::printf("0 %lld %d %lld %d 0 0\n", (long long) j, batch, (long long) (k1 - k0), jc.parts[(size_t) k1 - 1].p1 - jc.parts[(size_t) k0].p0);
+            for (int64_t k = k0; k < k1; k++) {
+                const Part& pt = jc.parts[(size_t) k];
+                std::printf("1 %lld %d %lld %lld %d %d\n", pt.job, pt.c, pt.a, pt.b, pt.p0, pt.p1);
+                for (int g = pt.p0; g < pt.p1; g++) {
+                    const Piece& pc = jc.pieces[(size_t) g];
+                    std::printf("2 %lld %d %lld %d %d %lld\n", pc.job, pc.c, pc.t, pc.n, g, (long long) k);
+                }
+            }
+        }
+        j0 = j1;
+    }
+    return 0;
+}

@@ -114,6 +114,18 @@ def pieces_of(off, first, last):
     return parts, pieces
 
 
+def _batches(parts, pieces, cap_pieces, cap_parts):
+    """The first job of every device batch of a call, by the getters' rule: a job is added while the batch holds fewer than cap_pieces
+    pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split."""
+    cp, cq = np.concatenate([[0], np.cumsum(pieces)]), np.concatenate([[0], np.cumsum(parts)])
+    starts, j0, n = [], 0, parts.size
+    while j0 < n:
+        starts.append(j0)
+        j1 = min(n, int(np.searchsorted(cp, cp[j0] + cap_pieces, "left")), int(np.searchsorted(cq, cq[j0] + cap_parts, "left")))
+        j0 = max(j1, j0 + 1)          # (the job that reaches the cap is the batch's last)
+    return starts
+
+
 # ---- the references, each once per case ------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def interval_reference(model_type, seed):

@@ -213,18 +213,6 @@ def _caps():
     return caps
 
 
-def _batches(parts, pieces, cap_pieces, cap_parts):
-    """The first job of every device batch of a call, by the getters' rule: a job is added while the batch holds fewer than cap_pieces
-    pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split."""
-    cp, cq = np.concatenate([[0], np.cumsum(pieces)]), np.concatenate([[0], np.cumsum(parts)])
-    starts, j0, n = [], 0, parts.size
-    while j0 < n:
-        starts.append(j0)
-        j1 = min(n, int(np.searchsorted(cp, cp[j0] + cap_pieces, "left")), int(np.searchsorted(cq, cq[j0] + cap_parts, "left")))
-        j0 = max(j1, j0 + 1)          # (the job that reaches the cap is the batch's last)
-    return starts
-
-
 @functools.lru_cache(maxsize=None)
 def _pool():
     """The distinct jobs of the batch tests (trunc-exp-Gaussian case): index ranges (two-window jobs: one part, one piece each;
@@ -273,7 +261,7 @@ def _batch_case(getter, call, filler_kind, cap_name, close):
         (caps["HF_MO_BATCH_PIECES"], caps["HF_MO_BATCH_PARTS"])
     by_parts = cap_name.endswith("PARTS")
     order, n1 = _call_order(one if filler_kind == "one" else two, spans, parts if by_parts else pieces, caps[cap_name])
-    starts = _batches(parts[order], pieces[order], cap_pieces, cap_parts)
+    starts = G._batches(parts[order], pieces[order], cap_pieces, cap_parts)
     assert len(starts) >= 2 and starts[1] == n1 + 1, starts          # the whole-track job closes the first batch, a spanning job opens the second
     assert order[starts[1] - 1] == spans[0] and order[starts[1]] == spans[1] and order[-1] == spans[2]
     before = (np.cumsum(parts[order]) if by_parts else np.cumsum(pieces[order]))[n1 - 1]
