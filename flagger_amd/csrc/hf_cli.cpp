@@ -74,6 +74,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"exactTotals", no_argument, nullptr, 1015},                // exact mean and SD of the label totals (hf_get_count_moments)
     {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
     {"jointEntropy", no_argument, nullptr, 1017},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
+    {"runBoundaries", no_argument, nullptr, 1018},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -148,7 +149,12 @@ static void usage(const char* program) {
             "                                      exact entropy (nats) of the posterior distribution over label paths (exp of it: the effective\n"
             "                                      number of plausible segmentations), that entropy per window, the sum of the per-window posterior\n"
             "                                      entropies (which ignores the chain's correlations and is never smaller), and the exact\n"
-            "                                      log-probability of the final labels; one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      log-probability of the final labels; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --runBoundaries              after the final inference, write final_label_run_boundaries.tsv: for every two adjacent runs of\n"
+            "                                      equal final label (the runs of final_label_runs_support.bed) inside one chunk, the exact\n"
+            "                                      probability that the two runs' range switches once from the left label to the right one, and\n"
+            "                                      given that, the posterior of where: the probability of the called position, the 2.5 / 50 /\n"
+            "                                      97.5 %% quantiles and the mode; one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -636,6 +642,71 @@ static int write_exact_totals(hf_ctx* ctx, const hfio_table* tab, const int8_t* 
     return HF_OK;
 }
 
+// --runBoundaries: the exact posterior of the position of every boundary between two runs of the final labels (hf_get_breakpoints,
+// hf_get_breakpoint_profile) under the model of the last full pass.
+//   final_label_run_boundaries.tsv   one row per two adjacent runs of final_label_runs_support.bed on one contig, in run order.  With m the
+//                                    first window of the right run and m - 1, m in one chunk, the job is first = max(start of the left
+//                                    run, first window of the chunk), last = min(end of the right run, last window of the chunk), U =
+//                                    {left label}, V = {right label}: p_event = P(the range switches exactly once, U -> V), and given
+//                                    that, p_called = p_m, lo / median / hi = the 2.5 / 50 / 97.5 % quantiles and mode, mode_p.  pos, lo,
+//                                    median, hi and mode are the first base of the window named.  A boundary at a chunk start, and a job
+//                                    without weight, have NA from p_event on.
+static int write_run_boundaries(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<int64_t> wbases;
+    window_bases(w, C, wbases, nullptr);
+    const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, nullptr);
+    auto chunk_of = [&](int64_t t) { return (int) (std::upper_bound(w.chunk_off, w.chunk_off + C + 1, t) - w.chunk_off) - 1; };
+    auto base_of = [&](int c, int64_t t) { return (long) ((int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len); };
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> um, vm;
+    std::vector<int> job(runs.size(), -1), chunk(runs.size(), 0);      // of the boundary between runs i - 1 and i
+    for (size_t i = 1; i < runs.size(); i++) {
+        const LRun &l = runs[i - 1], &r = runs[i];
+        const int c = chunk_of(r.a);
+        chunk[i] = c;
+        if (l.b != r.a || r.a == w.chunk_off[c] || l.label < 0 || l.label > 3 || r.label < 0 || r.label > 3 || l.label == r.label) continue;
+        job[i] = (int) first.size();
+        first.push_back(std::max<int64_t>(l.a, w.chunk_off[c]));
+        last.push_back(std::min<int64_t>(r.b, w.chunk_off[c + 1]) - 1);
+        um.push_back((uint8_t) (1u << l.label));
+        vm.push_back((uint8_t) (1u << r.label));
+    }
+    const int64_t n = (int64_t) first.size();
+    const double probs[3] = {0.025, 0.5, 0.975};
+    std::vector<double> lpe((size_t) n), modeP((size_t) n), pCalled((size_t) n, 0.0), prof;
+    std::vector<int64_t> quant((size_t) n * 3), mode((size_t) n);
+    int rc = hf_get_breakpoints(ctx, n, first.data(), last.data(), um.data(), vm.data(), 3, probs, lpe.data(), quant.data(), mode.data(), modeP.data());
+    if (rc != HF_OK) return rc;
+    for (size_t i = 1; i < runs.size(); i++) {      // p_called: one profile per boundary
+        if (job[i] < 0) continue;
+        const size_t k = (size_t) job[i];
+        double lp = 0.0;
+        prof.resize((size_t) (last[k] - first[k]));
+        if ((rc = hf_get_breakpoint_profile(ctx, first[k], last[k], um[k], vm[k], prof.data(), &lp)) != HF_OK) return rc;
+        pCalled[k] = prof[(size_t) (runs[i].a - first[k] - 1)];
+    }
+    const std::string bp = dir + "/final_label_run_boundaries.tsv";
+    FILE* f = fopen(bp.c_str(), "w");
+    if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#ctg\tpos\tleft\tright\tp_event\tp_called\tlo\tmedian\thi\tmode\tmode_p\n");
+    for (size_t i = 1; i < runs.size(); i++) {
+        const LRun &l = runs[i - 1], &r = runs[i];
+        if (strcmp(l.ctg, r.ctg) != 0) continue;      // (the first run of a contig has no boundary on its left)
+        const int c = chunk[i];
+        fprintf(f, "%s\t%ld\t%s\t%s\t", r.ctg, (long) r.s, l.label >= 0 && l.label < 4 ? kRunLabelNames[l.label] : "Unk",
+                r.label >= 0 && r.label < 4 ? kRunLabelNames[r.label] : "Unk");
+        const int k = job[i];
+        if (k < 0 || mode[(size_t) k] < 0 || !(lpe[(size_t) k] > -INFINITY)) { fprintf(f, "NA\tNA\tNA\tNA\tNA\tNA\tNA\n"); continue; }
+        fprintf(f, "%.6g\t%.6g\t%ld\t%ld\t%ld\t%ld\t%.6g\n", std::exp(lpe[(size_t) k]), pCalled[(size_t) k], base_of(c, quant[(size_t) k * 3]),
+                base_of(c, quant[(size_t) k * 3 + 1]), base_of(c, quant[(size_t) k * 3 + 2]), base_of(c, mode[(size_t) k]), modeP[(size_t) k]);
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --numBlocks: exact posterior mean and standard deviation of the block counts (hf_get_run_moments) under the model of the last full pass.
 //   label_blocks_exact.tsv   one row per scope and label set.  Scopes: "all" and every contig by name (order of first appearance in the
 //                            chunk list; its mean and variance are the sums over its maximal runs of consecutive chunks, in list
@@ -820,7 +891,7 @@ int main(int argc, char* argv[]) {
     bool viterbi = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
-    bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false;
+    bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -834,15 +905,18 @@ int main(int argc, char* argv[]) {
     int32_t minLenPerState[4] = {0, 0, 0, 0};
     const char* program = strrchr(argv[0], '/');
     program = program ? program + 1 : argv[0];
-    // "--e" and "--ex" were unique prefixes of --exchange until --exactTotals came: they keep their meaning (the rule of long_options above:
-    // a prefix that resolved once resolves to the same option in every later build)
+    // "--e" and "--ex" were unique prefixes of --exchange until --exactTotals came, "--ru" and "--run" of --runConfidence until
+    // --runBoundaries came: they keep their meaning (the rule of long_options above: a prefix that resolved once resolves to the same
+    // option in every later build)
+    struct Kept { const char* pre; const char* full; };
+    static const Kept kept[] = {{"--ex", "--exchange"}, {"--e", "--exchange"}, {"--run", "--runConfidence"}, {"--ru", "--runConfidence"}};
     std::vector<std::string> rewritten;
     rewritten.reserve((size_t) argc);
     for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; i++)
-        for (const char* pre : {"--ex", "--e"}) {
-            const size_t n = strlen(pre);
-            if (strncmp(argv[i], pre, n) == 0 && (argv[i][n] == '\0' || argv[i][n] == '=')) {
-                rewritten.push_back(std::string("--exchange") + (argv[i] + n));
+        for (const Kept& k : kept) {
+            const size_t n = strlen(k.pre);
+            if (strncmp(argv[i], k.pre, n) == 0 && (argv[i][n] == '\0' || argv[i][n] == '=')) {
+                rewritten.push_back(std::string(k.full) + (argv[i] + n));
                 argv[i] = rewritten.back().data();
                 break;
             }
@@ -924,6 +998,7 @@ int main(int argc, char* argv[]) {
             case 1009: runConfidence = true; break;
             case 1015: exactTotals = true; break;
             case 1016: numBlocks = true; break;
+            case 1018: runBoundaries = true; break;
             case 1017: jointEntropy = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
@@ -987,6 +1062,10 @@ int main(int argc, char* argv[]) {
     if ((runConfidence || regionProbsPath) && (nGpus > 1 || sweepListPath)) {
         fprintf(stderr, "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts(),
                 runConfidence ? "--runConfidence" : "--regionProbs");
+        return EXIT_FAILURE;
+    }
+    if (runBoundaries && (nGpus > 1 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --runBoundaries runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
     if (exactTotals && (nGpus > 1 || sweepListPath)) {
@@ -1347,6 +1426,13 @@ int main(int argc, char* argv[]) {
         if ((rc = write_interval_outputs(run.ctx, tab, finalLabels, runConfidence, regionProbsPath ? &regions : nullptr, labelNames, dir)) != HF_OK)
             return die(rc);
         fprintf(stderr, "[%s] [Final Inference] exact interval probabilities written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --runBoundaries: beside them
+    if (runBoundaries) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --runBoundaries needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_run_boundaries(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] final_label_run_boundaries.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     // --exactTotals: likewise
     if (exactTotals) {

@@ -492,6 +492,7 @@ struct hf_ctx {
     DevBuf mo;                // hf_moments.h: pieces, parts, piece triples, piece means, results
     DevBuf rn;                // hf_runs.h: pieces, parts, piece triples, piece sums of xi, results
     DevBuf en, en_lab;        // hf_entropy.h: pieces, parts, piece sums, results / the profile's two arrays; the labels of a call
+    DevBuf bp;                // hf_breakpoint.h: pieces, parts, piece products, the chain's vectors, the windows' weights, results
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1033,6 +1034,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->rn.release();
     ctx->en.release();
     ctx->en_lab.release();
+    ctx->bp.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -2862,4 +2864,141 @@ int hf_get_entropy_profile(hf_ctx* ctx, int64_t first, int64_t n, double* marg_h
         HIPCHK(hipStreamSynchronize(st));
     }
     return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact breakpoint posteriors (hf_breakpoint.h): the first range getter with a value per window of a job.  It shares rg_check, pass_view
+// and the job cutter with the others; bp_run is rg_run's sibling for four launches and the per-window weight arrays of a batch.  Last in
+// the file, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_breakpoint.h"
+
+// pieces and parts per device batch: a window's weight is 12 bytes, 2^15 pieces of 512 windows about 200 MB.  A part has at least one
+// piece, so the parts' cap never binds before the pieces'
+#ifndef HF_BP_BATCH_PIECES
+#define HF_BP_BATCH_PIECES (1 << 15)
+#endif
+#ifndef HF_BP_BATCH_PARTS
+#define HF_BP_BATCH_PARTS (1 << 15)
+#endif
+
+static_assert(HF_BP_PIECE == 512, "one piece grid for every getter");
+
+// The jobs of a call, batch by batch, on the stream of the pass: k_bp_piece, k_bp_chain, k_bp_weights, k_bp_quant.  prof_host (a call of
+// one job): its p_k.
+static int bp_run(hf_ctx* ctx, const std::string& who, const PassView& pv, int64_t n, const int64_t* first, const int64_t* last,
+                  const uint8_t* um, const uint8_t* vm, const BpProbs& pr, double* lpe_host, int64_t* quant_host, int64_t* mode_host,
+                  double* mode_p_host, double* prof_host) {
+    hipStream_t st = ctx->pass.last_stream;
+    DevBuf& buf = ctx->bp;
+    JobCut<BpPiece, BpPart, HF_BP_PIECE> jc;
+    std::vector<double> vd;
+    std::vector<long long> vi;
+    constexpr size_t NI = HF_BP_MAX_PROBS + 1;
+    for (int64_t j0 = 0; j0 < n;) {
+        long long nw = 0;      // windows with a weight so far in the batch
+        const int64_t j1 = jc.cut(ctx->tr.h_off, n, first, last, j0, HF_BP_BATCH_PIECES, HF_BP_BATCH_PARTS,
+            [&](int64_t j, int c, int64_t a, int64_t b) { BpPart pt{a, b, nw, 0, 0, um[j], vm[j], c, 0}; nw += b - a; return pt; },
+            [](const BpPart& pt, int64_t t, int len) { return BpPiece{t, pt.w0 + (t - pt.a - 1), len, pt.um, pt.vm, 0}; });
+        const size_t np = jc.pieces.size(), nq = jc.parts.size();
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += Slab::granule(bytes); return at; };
+        const size_t o_pieces = take(np * sizeof(BpPiece)), o_parts = take(nq * sizeof(BpPart)), o_pm = take(np * 48 * 8), o_pe = take(np * 4 * 4);
+        const size_t o_lv = take(np * 4 * 8), o_le = take(np * 8), o_rv = take(np * 4 * 8), o_re = take(np * 8), o_nn = take(nq * 8);
+        const size_t o_wm = take((size_t) nw * 8), o_we = take((size_t) nw * 4), o_prof = prof_host ? take((size_t) nw * 8) : 0;
+        const size_t o_outd = take(nq * 2 * 8), o_outi = take(nq * NI * 8);
+        const int rc = buf.reserve(o, who);
+        if (rc) return rc;
+        char* d = buf.d_buf;
+        BpPiece* d_pieces = reinterpret_cast<BpPiece*>(d + o_pieces);
+        BpPart* d_parts = reinterpret_cast<BpPart*>(d + o_parts);
+        double* d_pm = reinterpret_cast<double*>(d + o_pm); int* d_pe = reinterpret_cast<int*>(d + o_pe);
+        double* d_lv = reinterpret_cast<double*>(d + o_lv); long long* d_le = reinterpret_cast<long long*>(d + o_le);
+        double* d_rv = reinterpret_cast<double*>(d + o_rv); long long* d_re = reinterpret_cast<long long*>(d + o_re);
+        double* d_nn = reinterpret_cast<double*>(d + o_nn);
+        double* d_wm = reinterpret_cast<double*>(d + o_wm); int* d_we = reinterpret_cast<int*>(d + o_we);
+        double* d_prof = prof_host ? reinterpret_cast<double*>(d + o_prof) : nullptr;
+        double* d_outd = reinterpret_cast<double*>(d + o_outd); long long* d_outi = reinterpret_cast<long long*>(d + o_outi);
+        HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(BpPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(BpPart), hipMemcpyHostToDevice, st));
+        by_algo(ctx->tr, [&](auto S) {
+            constexpr bool SEQ = decltype(S)::value;
+            hipLaunchKernelGGL(k_bp_piece<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_pm, d_pe);
+            hipLaunchKernelGGL(k_bp_chain<SEQ>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe, pv, d_lv, d_le,
+                               d_rv, d_re, d_nn);
+            hipLaunchKernelGGL(k_bp_weights<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_lv, d_le, d_rv, d_re, d_wm, d_we);
+        });
+        hipLaunchKernelGGL(k_bp_quant, dim3((unsigned) nq), dim3(64), 0, st, d_parts, d_wm, d_we, d_nn, pr, d_outd, d_outi, d_prof);
+        HIPCHK(hipGetLastError());
+        vd.resize(nq * 2);
+        vi.resize(nq * NI);
+        HIPCHK(hipMemcpyAsync(vd.data(), d_outd, nq * 2 * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(vi.data(), d_outi, nq * NI * 8, hipMemcpyDeviceToHost, st));
+        if (prof_host) HIPCHK(hipMemcpyAsync(prof_host, d_prof, (size_t) nw * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {      // a job is one part
+            const size_t k = (size_t) jc.job_p0[(size_t) (j - j0)];
+            if (lpe_host) lpe_host[j] = vd[k * 2];
+            if (mode_p_host) mode_p_host[j] = vd[k * 2 + 1];
+            if (mode_host) mode_host[j] = vi[k * NI];
+            for (int q = 0; q < pr.n; q++) quant_host[j * pr.n + q] = vi[k * NI + 1 + (size_t) q];
+        }
+        j0 = j1;
+    }
+    return HF_OK;
+}
+
+// what the two calls refuse beyond rg_check (which has taken the ranges and the left masks), job by job
+static int bp_check(const hf_ctx* ctx, const std::string& who, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* um,
+                    const uint8_t* vm) {
+    const std::vector<int64_t>& off = ctx->tr.h_off;
+    for (int64_t i = 0; i < n; i++) {
+        const std::string job = " (job " + std::to_string(i) + ")";
+        if (vm[i] < 1 || vm[i] > 15) return set_err(HF_E_ARG, who + ": right_mask must be 1..15" + job);
+        if (um[i] & vm[i]) return set_err(HF_E_ARG, who + ": left_mask and right_mask overlap" + job);
+        if (first[i] == last[i]) return set_err(HF_E_ARG, who + ": first == last, no window to switch at" + job);
+        if (*(std::upper_bound(off.begin(), off.end(), first[i])) <= last[i])
+            return set_err(HF_E_ARG, who + ": first and last lie in different chunks" + job);
+    }
+    return HF_OK;
+}
+
+int hf_get_breakpoints(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* left_mask, const uint8_t* right_mask,
+                       int n_probs, const double* probs, double* log_p_event_host, int64_t* quantile_host, int64_t* mode_host,
+                       double* mode_p_host) {
+    const std::string who = "hf_get_breakpoints";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
+    const char* early = nullptr;
+    BpProbs pr{};
+    if (n_probs < 0 || n_probs > HF_BP_MAX_PROBS) early = "n_probs must be 0..8";
+    else if (n_probs > 0 && (!probs || !quantile_host)) early = "NULL probs or quantile array with n_probs > 0";
+    else {
+        pr.n = n_probs;
+        for (int q = 0; q < n_probs; q++) {
+            if (!(probs[q] > 0.0 && probs[q] < 1.0)) early = "a probability outside (0, 1)";
+            pr.q[q] = probs[q];
+        }
+    }
+    int rc = rg_check(ctx, who, n, !first || !last || !left_mask || !right_mask || !log_p_event_host || !mode_host || !mode_p_host, first, last,
+                      left_mask, nullptr, early);
+    if (rc) return rc;
+    if ((rc = bp_check(ctx, who, n, first, last, left_mask, right_mask))) return rc;
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    return bp_run(ctx, who, pv, n, first, last, left_mask, right_mask, pr, log_p_event_host, quantile_host, mode_host, mode_p_host, nullptr);
+}
+
+int hf_get_breakpoint_profile(hf_ctx* ctx, int64_t first, int64_t last, uint8_t left_mask, uint8_t right_mask, double* p_host,
+                              double* log_p_event_host) {
+    const std::string who = "hf_get_breakpoint_profile";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
+    int rc = rg_check(ctx, who, 1, !p_host || !log_p_event_host, &first, &last, &left_mask);
+    if (rc) return rc;
+    if ((rc = bp_check(ctx, who, 1, &first, &last, &left_mask, &right_mask))) return rc;
+    PassView pv;
+    rc = pass_view(ctx, who, 1, pv);
+    if (rc) return rc;
+    return bp_run(ctx, who, pv, 1, &first, &last, &left_mask, &right_mask, BpProbs{}, log_p_event_host, nullptr, nullptr, nullptr, p_host);
 }

@@ -701,6 +701,45 @@ class EMList:
         N.check(self._L.hf_get_entropy_profile(self._h, first, n, _dptr(marg), _dptr(cond)), "hf_get_entropy_profile")
         return marg, cond
 
+    def breakpoints(self, first, last, left_mask, right_mask, probs=(0.025, 0.5, 0.975)):
+        """Exact breakpoint posteriors under the model of the last full pass (hf_get_breakpoints): job i says that the windows
+        first[i]..last[i] (inclusive, one chunk, first < last) switch once from a state in left_mask[i] to a state in right_mask[i]
+        (disjoint sets, bit s = state s); k, the first window of the right side, has the posterior p_k over first+1..last.
+        -> (log_p_event float64[n], the log-probability that the range switches exactly once in that way; quantiles int64[n, len(probs)],
+        the smallest k whose cumulated p reaches probs[j]; mode int64[n], the k of largest p; mode_p float64[n]).  A job without weight
+        gives (-inf, -1, -1, 0.0).  Scalars broadcast."""
+        f, l, u, v = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(left_mask, np.int64),
+                                         np.asarray(right_mask, np.int64))
+        if u.size and (min(u.min(), v.min()) < 0 or max(u.max(), v.max()) > 255):
+            raise ValueError("breakpoints: a state mask must be 1..15")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        u = np.ascontiguousarray(u.ravel(), np.uint8)
+        v = np.ascontiguousarray(v.ravel(), np.uint8)
+        q = np.ascontiguousarray(np.asarray(probs, np.float64).ravel())
+        lpe = np.empty(f.size, dtype=np.float64)
+        quant = np.empty((f.size, q.size), dtype=np.int64)
+        mode = np.empty(f.size, dtype=np.int64)
+        mode_p = np.empty(f.size, dtype=np.float64)
+        i64p = C.POINTER(C.c_int64)
+        N.check(self._L.hf_get_breakpoints(self._h, f.size, f.ctypes.data_as(i64p), l.ctypes.data_as(i64p),
+                                           u.ctypes.data_as(C.POINTER(C.c_uint8)), v.ctypes.data_as(C.POINTER(C.c_uint8)), q.size, _dptr(q),
+                                           _dptr(lpe), quant.ctypes.data_as(i64p), mode.ctypes.data_as(i64p), _dptr(mode_p)),
+                "hf_get_breakpoints")
+        return lpe, quant, mode, mode_p
+
+    def breakpoint_profile(self, first: int, last: int, left_mask: int, right_mask: int):
+        """The posterior of one breakpoint job (hf_get_breakpoint_profile): (p float64[last - first], p[i] the probability that window
+        first + 1 + i is the first of the right side, given that the range switches once; log_p_event).  The values the batch call
+        derives its quantiles and mode from, bit for bit."""
+        if not (0 <= int(left_mask) <= 255 and 0 <= int(right_mask) <= 255):
+            raise ValueError("breakpoint_profile: a state mask must be 1..15")
+        p = np.empty(max(int(last) - int(first), 0), dtype=np.float64)
+        lpe = np.empty(1, dtype=np.float64)
+        N.check(self._L.hf_get_breakpoint_profile(self._h, int(first), int(last), int(left_mask), int(right_mask), _dptr(p), _dptr(lpe)),
+                "hf_get_breakpoint_profile")
+        return p, float(lpe[0])
+
     def set_alpha_stats(self, on: bool = True) -> None:
         """hf_set_alpha_stats: full passes from now on can be asked for the alpha statistics (alpha_stats)."""
         N.check(self._L.hf_set_alpha_stats(self._h, int(bool(on))), "hf_set_alpha_stats")
@@ -807,6 +846,15 @@ def EM_getEntropyProfileForList(emList, first: int = 0, n: Optional[int] = None)
     if not hasattr(emList, "entropy_profile"):
         raise TypeError("EM_getEntropyProfileForList: %s has no entropy profile" % type(emList).__name__)
     return emList.entropy_profile(first, n)
+
+
+def EM_getBreakpointsForList(emList, first, last, left_mask, right_mask, probs=(0.025, 0.5, 0.975)):
+    """(log_p_event, quantiles, mode, mode_p) of the window at which first[i]..last[i] switches from a state of left_mask[i] to one of
+    right_mask[i], given that it switches once, under the model of the last full pass, per job (no counterpart in the reference).
+    `emList`: an EMList."""
+    if not hasattr(emList, "breakpoints"):
+        raise TypeError("EM_getBreakpointsForList: %s has no breakpoint getter" % type(emList).__name__)
+    return emList.breakpoints(first, last, left_mask, right_mask, probs)
 
 
 class EMBatch:

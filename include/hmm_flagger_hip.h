@@ -345,6 +345,43 @@ int hf_get_path_entropy(hf_ctx *ctx, int64_t n, const int64_t *first, const int6
 int hf_get_path_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last,
                           const int8_t *labels_host /* [n_windows], read only inside the jobs' ranges */, double *log_p_host);
 int hf_get_entropy_profile(hf_ctx *ctx, int64_t first, int64_t n, double *marg_host /* or NULL */, double *cond_host /* or NULL */);
+/* Exact breakpoint posteriors (flagger_amd/csrc/hf_breakpoint.h), under the model of the last HF_MODE_FULL pass like
+ * hf_get_interval_log_probs: given that a range switches once from a state set U to a state set V, the posterior over the switching
+ * window (the change-point-location posterior of a constrained HMM).  f, b are that pass's scaled forward and backward vectors
+ * (hf_get_forward_backward), A_t the row the pass multiplied by at window t.  Job i is the window range a = first[i] < b = last[i], both
+ * in the SAME chunk, a left set U = left_mask[i] and a right set V = right_mask[i], each 1..15 (bit s = state s), U & V == 0.  For
+ * k = a+1 .. b the event E_k is "s_t in U for a <= t < k and s_t in V for k <= t <= b": the events are disjoint and k is the first window
+ * of the right side.  With D_S = diag(1_S):
+ *   L_a = f_a o 1_U,  L_t = L_{t-1} (A_t D_U)       (row vectors, t = a+1 .. b-1)
+ *   r_b = b_b,        r_{t-1} = (A_t D_V) r_t       (column vectors, t = b .. a+1)
+ *   w_k = L_{k-1} . r_{k-1}                         (sum in state order)
+ *   N   = f_a (A_{a+1} ... A_b) b_b                 (the unmasked chain, the same operations as the masked one: hf_get_interval_log_probs' N)
+ *   P(E_k | data) = w_k / N,  W = sum_k w_k,  p_k = w_k / W
+ * Every vector and matrix is renormalised by a power of two after every product, with integer exponent sums, and a weight is carried as
+ * (mantissa in [1, 2), exponent) until the job's largest exponent emax is known: nothing underflows before that.  THE ORDER of the sums:
+ * x_k = mantissa_k 2^(e_k - emax) is summed in blocks of 64 consecutive k (block m holds k = a+1+64m .. a+64m+64); inside a block by
+ * an inclusive scan whose step off = 1, 2, 4 .. 32 adds, at place l >= off, the running value of place l - off on the left of the running
+ * value of place l; the sum of the blocks before is added on the left of that, and becomes the value at the block's last place.  W is
+ * the value at the last block's last place, p_k = x_k / W, and c_k is the same blocked scan over the p_k.  A job returns
+ *   log_p_event  log W - log N = log P(exactly one switch U -> V inside [a, b] | data): <= 0 up to rounding, -inf when no k has weight
+ *   quantile[j]  for probs[j] (0 < probs[j] < 1, n_probs in 0..8; quantile_host is [n][n_probs]): the smallest k with p_k > 0 and
+ *                c_k >= probs[j]; if rounding leaves none, the largest k with p_k > 0
+ *   mode, mode_p the smallest k of maximal p_k, and that p_k
+ * and quantile = mode = -1, mode_p = 0.0 for a job without weight.  No NaN, except that a pass that left no weight (N not > 0) gives NaN
+ * in log_p_event only, as hf_get_interval_log_probs does.  hf_get_breakpoint_profile returns p_k, k = first+1 .. last, of one job (zeros
+ * for a job without weight) and its log_p_event: bitwise the values the batch call derives its quantiles and mode from.  A job's
+ * outputs depend only on (first, last, U, V, probs) and the pass, bitwise: not on the other jobs of the call, their order, their number
+ * or the device batch they fall in (HF_BP_BATCH_PIECES).  Synchronous on the pass's stream; the first call after an EM pass of the default
+ * algorithm re-runs the segment kernel once, as hf_get_posterior's does, also in several sub-passes.  HF_ALGO_SCAN and HF_ALGO_SEQ, all
+ * three model types.  Buffers of their own: nothing an EM pass or another getter reads is written.  n = 0 is a successful no-op.
+ * HF_E_ARG: the cases of hf_get_interval_log_probs (no full pass yet or the last pass forward-only, n < 0, a NULL array with n > 0, a bad
+ * range, a mask of 0 or above 15), first == last, first and last in different chunks, overlapping masks, n_probs outside 0..8, a
+ * probability outside (0, 1), a NULL probs or quantile_host with n_probs > 0.  hf_batch_* and hf_multi_* have no counterpart. */
+int hf_get_breakpoints(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *left_mask,
+                       const uint8_t *right_mask, int n_probs, const double *probs, double *log_p_event_host /* [n] */,
+                       int64_t *quantile_host /* [n][n_probs] */, int64_t *mode_host /* [n] */, double *mode_p_host /* [n] */);
+int hf_get_breakpoint_profile(hf_ctx *ctx, int64_t first, int64_t last, uint8_t left_mask, uint8_t right_mask,
+                              double *p_host /* [last - first], k = first+1 .. last */, double *log_p_event_host);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
