@@ -20,6 +20,7 @@ HF_EXCHANGE_CHUNKS, HF_EXCHANGE_RANKS = 0, 1
 HF_TRANSPORT_RCCL, HF_TRANSPORT_LOOPBACK = 0, 1
 HF_PROF_PASS = 0x80000000
 HF_COUNT_WINDOWS, HF_COUNT_BASES = 0, 1
+HF_MINLEN_MAX_LANES = 64
 HF_OK, HF_E_ARG, HF_E_HIP, HF_E_SCALE, HF_E_NAN, HF_E_REGION, HF_E_NOGPU, HF_E_RETRY = 0, -1, -2, -3, -4, -5, -6, -7
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libhmmflagger_hip.so")
@@ -128,6 +129,10 @@ def lib() -> C.CDLL:
     sig("hf_viterbi_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
+    sig("hf_viterbi_minlen", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), vp)
+    sig("hf_viterbi_minlen_finish", C.c_int, vp, pd, vp)
+    sig("hf_get_viterbi_minlen_labels", C.c_int, vp, C.POINTER(C.c_int8))
+    sig("hf_get_viterbi_minlen_chunk_log_probs", C.c_int, vp, pd)
     sig("hf_sample_capacity", C.c_int, vp)
     sig("hf_sample_paths", C.c_int, vp, C.POINTER(hf_params), i64, C.c_int, C.c_uint64, vp)
     sig("hf_sample_finish", C.c_int, vp, vp)

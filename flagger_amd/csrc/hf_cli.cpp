@@ -75,6 +75,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
     {"jointEntropy", no_argument, nullptr, 1017},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
     {"runBoundaries", no_argument, nullptr, 1018},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
+    {"enforceMinimumLengths", no_argument, nullptr, 1019},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -154,7 +155,14 @@ static void usage(const char* program) {
             "                                      equal final label (the runs of final_label_runs_support.bed) inside one chunk, the exact\n"
             "                                      probability that the two runs' range switches once from the left label to the right one, and\n"
             "                                      given that, the posterior of where: the probability of the called position, the 2.5 / 50 /\n"
-            "                                      97.5 %% quantiles and the mode; one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      97.5 %% quantiles and the mode; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --enforceMinimumLengths      with --viterbi: the final labels are the most probable path AMONG THE PATHS WHOSE RUNS MEET\n"
+            "                                      --minimumLengths (Err, Dup, Col: ceil(length / windowLen) windows, at least 1; Hap: 1; at most 64\n"
+            "                                      windows in sum; runs at a chunk's ends are exempt, the final BED's filter still acts on those), not\n"
+            "                                      the best path with its short runs relabelled afterwards; viterbi_log_probability.tsv holds the score\n"
+            "                                      of the path written, viterbi_min_length_cost.tsv the four window counts, the constrained and the\n"
+            "                                      unconstrained score, their difference and the number of chunks whose two paths differ; one GPU, not\n"
+            "                                      with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -207,6 +215,14 @@ struct Run {
         int rc = hf_viterbi(ctx, &p, nullptr);
         if (rc == HF_OK) rc = hf_viterbi_finish(ctx, log_prob, nullptr);
         return rc != HF_OK ? rc : hf_get_viterbi_labels(ctx, out);
+    }
+    // ... among the paths whose runs meet min_len windows per state (one GPU)
+    int viterbi_minlen(hfm_model* m, const int32_t min_len[4], int8_t* out, double* log_prob) {
+        hf_params p;
+        hfm_params(m, &p);
+        int rc = hf_viterbi_minlen(ctx, &p, min_len, nullptr);
+        if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
+        return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
     }
     int posterior(int64_t first, int64_t n, double* out) {
         return multi ? hf_multi_get_posterior(multi, first, n, out) : hf_get_posterior(ctx, first, n, out);
@@ -888,7 +904,7 @@ int main(int argc, char* argv[]) {
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
     double initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false;
+    bool viterbi = false, enforceMinLen = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
@@ -1000,6 +1016,7 @@ int main(int argc, char* argv[]) {
             case 1016: numBlocks = true; break;
             case 1018: runBoundaries = true; break;
             case 1017: jointEntropy = true; break;
+            case 1019: enforceMinLen = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -1109,6 +1126,12 @@ int main(int argc, char* argv[]) {
     if (const char* e = getenv("HF_LOOPBACK_RANKS")) loopbackRanks = atoi(e);
     if (nGpus < 0 || nGpus > 64 || loopbackRanks < 0 || loopbackRanks > 64) { fprintf(stderr, "[%s] Error: --gpus should be between 1 and 64.\n", ts()); return EXIT_FAILURE; }
     if (nGpus > 0 && loopbackRanks > 0) { fprintf(stderr, "[%s] Error: --gpus and HF_LOOPBACK_RANKS exclude each other.\n", ts()); return EXIT_FAILURE; }
+    // --enforceMinimumLengths: refused combinations, before the input is read
+    if (enforceMinLen && !viterbi) { fprintf(stderr, "[%s] Error: --enforceMinimumLengths needs --viterbi.\n", ts()); return EXIT_FAILURE; }
+    if (enforceMinLen && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --enforceMinimumLengths runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
     if (!inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return EXIT_FAILURE; }
     if (convergenceTol <= 0.0 || convergenceTol > 1.0) {
         fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), convergenceTol);
@@ -1145,6 +1168,22 @@ int main(int argc, char* argv[]) {
     }
     if (modelType == -2) { fprintf(stderr, "[%s] Error: Model type is not defined. Specify the model type with --model (-m) argument.\n", ts()); return EXIT_FAILURE; }
     if (windowLen <= 0) { fprintf(stderr, "[%s] Error: windowLen cannot be <= 0.\n", ts()); return EXIT_FAILURE; }
+    // --enforceMinimumLengths: the lengths in windows.  A run of k windows passes the final BED's `len < minlen` test exactly when
+    // k * windowLen >= minlen; Hap has no minimum.  (A bin input carries its own window length: checked again once it is read.)
+    int32_t minLenWindows[4] = {1, 1, 1, 1};
+    auto min_len_windows = [&](int W) {
+        long long sum = 0;
+        for (int s = 0; s < 4; s++) {
+            const long long w = s == 2 ? 1 : std::max(1LL, ((long long) minLenPerState[s] + W - 1) / W);
+            minLenWindows[s] = (int32_t) std::min(w, 1000000LL);
+            sum += minLenWindows[s];
+        }
+        if (sum <= HF_MINLEN_MAX_LANES) return true;
+        fprintf(stderr, "[%s] Error: --enforceMinimumLengths: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
+                ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
+        return false;
+    };
+    if (enforceMinLen && !min_len_windows(windowLen)) return EXIT_FAILURE;
     if (0.5 < initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return EXIT_FAILURE; }
 
     // 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
@@ -1176,6 +1215,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), hfio_n_chunks(tab), (long) N, hfio_window_len(tab));
     if (N == 0 || hfio_n_chunks(tab) == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return EXIT_FAILURE; }
 
+    if (enforceMinLen && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
     phase("load input (+ HIP start-up)");
     // 2. number of collapsed components (hmm_flagger.c:1008-1022)
     hf_windows w;
@@ -1380,6 +1420,30 @@ int main(int argc, char* argv[]) {
         vlabels.resize((size_t) N);
         double vlp = 0.0;
         if ((rc = run.viterbi(model, vlabels.data(), &vlp)) != HF_OK) return die(rc);
+        // --enforceMinimumLengths: the path written is the best one that respects the lengths; the unconstrained run above is what it cost
+        if (enforceMinLen) {
+            if (!run.ctx) { fprintf(stderr, "[%s] Error: --enforceMinimumLengths needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+            std::vector<int8_t> clabels((size_t) N);
+            double clp = 0.0;
+            if ((rc = run.viterbi_minlen(model, minLenWindows, clabels.data(), &clp)) != HF_OK) return die(rc);
+            hf_windows wv;
+            memset(&wv, 0, sizeof wv);
+            hfio_windows(tab, &wv);
+            int differ = 0;
+            for (int c = 0; c < wv.n_chunks; c++)
+                differ += memcmp(clabels.data() + wv.chunk_off[c], vlabels.data() + wv.chunk_off[c], (size_t) (wv.chunk_off[c + 1] - wv.chunk_off[c])) != 0;
+            const std::string cp = dir + "/viterbi_min_length_cost.tsv";
+            FILE* cf = fopen(cp.c_str(), "w");
+            if (!cf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), cp.c_str()); return EXIT_FAILURE; }
+            fprintf(cf, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\tlog_prob_constrained\tlog_prob_unconstrained\tlog_prob_difference\tchunks_changed\n");
+            fprintf(cf, "%d\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%d\n", minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], clp, vlp,
+                    clp - vlp, differ);
+            fclose(cf);
+            fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows: log-probability %.6f (unconstrained %.6f), %d chunks changed\n",
+                    ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], clp, vlp, differ);
+            vlabels.swap(clabels);
+            vlp = clp;
+        }
         const std::string vp = dir + "/viterbi_log_probability.tsv";
         FILE* vf = fopen(vp.c_str(), "w");
         if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); return EXIT_FAILURE; }

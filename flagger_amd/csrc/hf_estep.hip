@@ -438,6 +438,13 @@ struct Viterbi : Decoder {
     std::vector<double> h_ll;                  // chunk scores of the last finished run
 };
 
+// minimum-run-length Viterbi (hf_minlen.h): rows always in window order, one 16-bit backpointer word per window
+struct MinLenViterbi : Decoder {
+    uint16_t* d_bp = nullptr; uint8_t* d_final = nullptr;     // ... and the final lane of every chunk
+    int8_t* d_label = nullptr; double* d_ll = nullptr;
+    std::vector<double> h_ll;                  // chunk scores of the last finished run
+};
+
 // posterior path sampling (hf_sample.h).  The per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more.
 struct Sampler : Decoder {
     Slab samples;
@@ -486,6 +493,7 @@ struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
+    MinLenViterbi mlv;
     Sampler smp;
     DevBuf iv;                // hf_interval.h: pieces, parts, piece products, results
     AlphaStats al;
@@ -1027,6 +1035,7 @@ void hf_destroy(hf_ctx* ctx) {
                      ps.ht_n, ps.ht[4] / ps.ht_n, ps.ht[0] / ps.ht_n, ps.ht[1] / ps.ht_n, ps.ht[2] / ps.ht_n, ps.ht[3] / ps.ht_n);
     pass_destroy(ctx->pass);
     ctx->vit.release();
+    ctx->mlv.release();
     ctx->smp.release();
     ctx->iv.release();
     ctx->al.release();
@@ -3001,4 +3010,95 @@ int hf_get_breakpoint_profile(hf_ctx* ctx, int64_t first, int64_t last, uint8_t 
     rc = pass_view(ctx, who, 1, pv);
     if (rc) return rc;
     return bp_run(ctx, who, pv, 1, &first, &last, &left_mask, &right_mask, BpProbs{}, log_p_event_host, nullptr, nullptr, nullptr, p_host);
+}
+
+
+// ------------------------------------------------------------------------------------------
+// minimum-run-length Viterbi (hf_minlen.h): a decoder of its own beside hf_viterbi, one code path for both kinds of context (rows in
+// window order, one wavefront per chunk).  Last in the file, its kernels included, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen.h"
+
+static_assert(HF_MINLEN_MAX_LANES == 64, "one wavefront holds the expanded chain");
+
+// every device array of the decoder, f(array, bytes) in turn (as vit_arrays)
+template <class F> static void mlv_arrays(const Track& tr, MinLenViterbi& v, F&& f) {
+    f(v.d_params, tr.params_bytes); f(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(v.d_rows, (size_t) tr.N * 128); f(v.d_flags, 4);
+    f(v.d_bp, (size_t) tr.N * 2); f(v.d_label, (size_t) tr.N); f(v.d_ll, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+}
+
+int hf_viterbi_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    const std::string w = "hf_viterbi_minlen";
+    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
+    int64_t lanes = 0;
+    for (int s = 0; s < 4; s++) {
+        if (min_len[s] < 1) return set_err(HF_E_ARG, w + ": every minimum length must be >= 1");
+        lanes += min_len[s];
+    }
+    if (lanes > HF_MINLEN_MAX_LANES)
+        return set_err(HF_E_ARG, w + ": the minimum lengths sum to " + std::to_string(lanes) + ", above HF_MINLEN_MAX_LANES (64)");
+    const Track& tr = ctx->tr;
+    MinLenViterbi& v = ctx->mlv;
+    hipStream_t st = (hipStream_t) stream;
+    // dec_begin without the scan path's steps: the wait for a run nobody finished (it may still be reading the pinned parameter block),
+    // the buffers, the parameter block, the negative-binomial table, the flag word
+    HIPCHK(hipSetDevice(tr.device));
+    if (v.launched) HIPCHK(hipDeviceSynchronize());
+    v.launched = false; v.done = false;
+    int rc = dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); });
+    if (rc) return rc;
+    rc = pack_params(tr, p, v.h_params);
+    if (rc) return rc;
+    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
+    if (nbm) {
+        if (!p->nb_E) return set_err(HF_E_ARG, w + ": negative_binomial needs hf_params.nb_E");
+        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
+            return set_err(HF_E_ARG, w + ": the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
+        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    if (dec_work(tr)) {
+        hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params,
+                           nbm ? v.d_nbE : nullptr, v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_mlv_fwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
+                           (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_ll, v.d_flags);
+        hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, (int) min_len[0], (int) min_len[1], (int) min_len[2],
+                           (int) min_len[3], v.d_bp, v.d_final, v.d_label);
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_viterbi_minlen_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
+    if (!ctx || !ctx->mlv.launched) return set_err(HF_E_ARG, "hf_viterbi_minlen_finish: no hf_viterbi_minlen to finish");
+    const Track& tr = ctx->tr;
+    MinLenViterbi& v = ctx->mlv;
+    const int rc = dec_finish(tr, v, stream);
+    if (rc) return rc;
+    v.h_ll.assign((size_t) tr.C, 0.0);
+    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
+    double tot = 0.0;
+    for (double x : v.h_ll) tot += x;   // chunk-list order
+    if (log_prob_host) *log_prob_host = tot;
+    v.done = true;
+    return HF_OK;
+}
+
+int hf_get_viterbi_minlen_labels(hf_ctx* ctx, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->mlv.done) return set_err(HF_E_ARG, "hf_get_viterbi_minlen_labels: no finished hf_viterbi_minlen");
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mlv.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx* ctx, double* out_host) {
+    if (!ctx || !out_host || !ctx->mlv.done) return set_err(HF_E_ARG, "hf_get_viterbi_minlen_chunk_log_probs: no finished hf_viterbi_minlen");
+    const Track& tr = ctx->tr;
+    if (tr.C > 0) std::memcpy(out_host, ctx->mlv.h_ll.data(), (size_t) tr.C * 8);
+    return HF_OK;
 }

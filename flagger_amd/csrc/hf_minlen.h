@@ -1,0 +1,197 @@
+// hf_minlen.h — minimum-run-length Viterbi (hf_viterbi_minlen): the most probable path among the paths whose runs meet a minimum length
+// per state.  A decoder beside hf_viterbi: the same first, A_t and end (hf_decode.h), buffers of its own, ONE code path for both kinds of
+// context (rows in window order, one wavefront per chunk).
+//
+// Definition.  min_len[s] >= 1 windows per state, sum <= HF_MINLEN_MAX_LANES.  A path of a chunk is ADMISSIBLE when every maximal run of
+// equal state s has at least min_len[s] windows; a run that contains the chunk's first or last window is exempt (a chunk is a cut of a
+// contig).  The decoder returns the admissible path of the largest weight first[s_0] * prod_t A_t[s_{t-1}][s_t] * end[s_{T-1}].
+//
+// The expanded chain.  Lanes (s, d), d = 1 .. min_len[s]: "in state s, the current run has d windows so far"; at d = min_len[s] "at least
+// that many" (the SATURATED lane; d = 1 is the ENTRY lane).  Lane index = sum_{q<s} min_len[q] + d - 1.
+//   window 0     delta[(s, min_len[s])] = first[s], nothing elsewhere (the exempt left end)
+//   entry        max over p in increasing order of delta[(p, min_len[p])] + A_t[p][s]; p = s only when min_len[s] == 1 (the "stay");
+//                replacement needs strict >, so the lowest p wins a tie
+//   1 < d < m    delta[(s, d-1)] + A_t[s][s]
+//   d = m > 1    delta[(s, d-1)] + A_t[s][s], then delta[(s, d)] + A_t[s][s], strict >
+//   end          max over all lanes in lane order of delta[(s, d)] + end[s], strict > (the exempt right end)
+// With all four lengths 1 this is hf_viterbi's recurrence and tie rule.
+//
+// Numerics: LOGS.  k_mlv_rows stores log of every entry of the row (-inf for 0), so a step of the chain is one add and one compare and
+// nothing under- or overflows at any chunk length; the (mantissa, exponent) form of hf_decode.h would need a wave-wide maximum per
+// window.  A chunk's score is the maximum itself.  HF_FLAG_NAN: a NaN in a row (k_mlv_rows, as dec_row) or in the end column;
+// HF_FLAG_SCALE: the maximum of a chunk is -inf, no admissible path has weight.
+//
+// k_mlv_fwd: one 64-lane workgroup per chunk, lane = expanded state.  Rows come 64 windows at a time through LDS (the next 64 are on
+// their way while these are walked); a lane reads its column A[0..3][s] and A[s][s].  Per window a lane takes the four saturated lanes'
+// values (readlane at wave-uniform indices) and the value of the lane below it (a DPP shift by one lane); nothing else crosses lanes.
+// BACKPOINTERS: one 16-bit word per window: bits 2s, 2s+1 the predecessor state of state s's entry lane, bit 8+s set when state s's
+// saturated lane stayed (clear: it arrived from d-1).  An owning lane keeps its own decisions of 16 windows in a register, 2 bits per
+// window; after the 16, lane l builds the word of window l from the eight owning lanes' registers, read at their (uniform) lane
+// indices, and the words of 64 windows go out in one store.
+// k_mlv_back: one 64-lane workgroup per chunk walks back from the chunk's final lane: lane q loads the word of window t-q, and (s, d)
+// is carried through the 64 words in registers on the scalar side — a word's address does not depend on the state — while lane q
+// keeps label[t-q] for one store.
+#pragma once
+#include "hf_decode.h"
+
+#define HF_MLV_NEG_INF (-__builtin_huge_val())
+
+__device__ __forceinline__ double mlv_readlane(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// the value of lane - 1 (lane 0: `v` itself): DPP wave_shr:1 on the two halves
+__device__ __forceinline__ double mlv_lane_below(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
+                            __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
+}
+
+// rows: log of the row of every window, window order, the layout of k_dec_rows_win
+__global__ void __launch_bounds__(256) k_mlv_rows(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
+                                                  const DevParams* __restrict__ P, const double* __restrict__ nbE,
+                                                  double2* __restrict__ rows, unsigned* __restrict__ flags) {
+    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N) return;
+    unsigned nan = 0;
+    double a[16];
+    dec_row(rec, beta, P, nbE, t, a, &nan);
+#pragma unroll
+    for (int k = 0; k < 16; k++) a[k] = a[k] == 0.0 ? HF_MLV_NEG_INF : log(a[k]);
+#pragma unroll
+    for (int k = 0; k < 8; k++) rows[t * 8 + k] = make_double2(a[2 * k], a[2 * k + 1]);
+    if (nan) atomicOr(flags, nan);
+}
+
+// min_len of state s out of the four lengths packed one per byte
+__device__ __forceinline__ int mlv_len(unsigned mpack, int s) { return (int) ((mpack >> (8 * s)) & 0xffu); }
+
+__global__ void __launch_bounds__(64) k_mlv_fwd(const int64_t* __restrict__ off, const uint32_t* __restrict__ rec,
+                                                const DevParams* __restrict__ P, const double2* __restrict__ rows, int m0, int m1, int m2,
+                                                int m3, uint16_t* __restrict__ bp, uint8_t* __restrict__ final_lane, double* __restrict__ ll,
+                                                unsigned* __restrict__ flags) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int64_t t0 = off[c], T = off[c + 1] - t0;
+    __shared__ double As[65][17];   // column 16: -inf, the "A[s][s]" of the lanes past the last one; row 64: read ahead, never used
+    if (T <= 0) { if (lane == 0) { ll[c] = 0.0; final_lane[c] = 0; } return; }
+    // the lane's (s, d) and the uniform lane indices of every state's entry and saturated lane
+    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2, total = b3 + m3;
+    const int ent0 = 0, ent1 = b1, ent2 = b2, ent3 = b3;
+    const int sat0 = b1 - 1, sat1 = b2 - 1, sat2 = b3 - 1, sat3 = total - 1;
+    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
+    const int s = (lane >= b1) + (lane >= b2) + (lane >= b3);
+    const int base_s = s == 0 ? 0 : s == 1 ? b1 : s == 2 ? b2 : b3;
+    const int m = mlv_len(mpack, s), d = lane - base_s + 1;
+    const bool active = lane < total;
+    const bool is_entry = active && d == 1, is_sat = active && d == m && m > 1;
+    const bool excl = m > 1;                                  // the entry lane takes no p == s
+    const int pf = (excl && s == 0) ? 1 : 0;                  // its first candidate
+    const int diag = active ? 5 * s : 16;                     // where the lane reads A[s][s]
+
+    double x = HF_MLV_NEG_INF;
+    double2 nx[8];
+    if (lane < T) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) nx[k] = rows[(t0 + lane) * 8 + k];
+    }
+    for (int64_t base = 0; base < T; base += 64) {
+        const int n = (int) ((T - base) < 64 ? (T - base) : 64);
+        if (lane < n) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) { As[lane][2 * k] = nx[k].x; As[lane][2 * k + 1] = nx[k].y; }
+            As[lane][16] = HF_MLV_NEG_INF;
+        }
+        if (base + 64 + lane < T) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) nx[k] = rows[(t0 + base + 64 + lane) * 8 + k];
+        }
+        __syncthreads();
+        const int q0 = base == 0 ? 1 : 0;
+        // window 0: first[s] (row pre = 0 of the chunk-first row) in every state's saturated lane
+        if (base == 0 && active && d == m) x = As[0][s];
+        int words = 0;
+        // the lane's column of the NEXT window is read while this one's step runs: LDS latency stays off the chain
+        double c0 = As[q0][s], c1 = As[q0][4 + s], c2 = As[q0][8 + s], c3 = As[q0][12 + s], css = As[q0][diag];
+        for (int qb = q0; qb < n; qb += 16) {
+            // 16 windows; a lane keeps its own decisions, 2 bits per window: an entry lane its predecessor, a saturated lane "stayed"
+            const int cnt = n - qb < 16 ? n - qb : 16;
+            unsigned hist = 0;
+            for (int q = qb; q < qb + cnt; q++) {
+                const double a0 = c0, a1 = c1, a2 = c2, a3 = c3, ass = css;
+                c0 = As[q + 1][s]; c1 = As[q + 1][4 + s]; c2 = As[q + 1][8 + s]; c3 = As[q + 1][12 + s]; css = As[q + 1][diag];
+                const double v0 = mlv_readlane(x, sat0) + a0, v1 = mlv_readlane(x, sat1) + a1;
+                const double v2 = mlv_readlane(x, sat2) + a2, v3 = mlv_readlane(x, sat3) + a3;
+                const double up = mlv_lane_below(x) + ass, stay = x + ass;
+                // the entry lane: candidates p = pf .. 3 in increasing order, p == s left out when the state has a minimum above 1
+                double best = pf ? v1 : v0;
+                unsigned arg = (unsigned) pf;
+                if (pf < 1 && !(excl && s == 1) && v1 > best) { best = v1; arg = 1; }
+                if (!(excl && s == 2) && v2 > best) { best = v2; arg = 2; }
+                if (!(excl && s == 3) && v3 > best) { best = v3; arg = 3; }
+                const bool stayed = is_sat && stay > up;
+                x = is_entry ? best : (stayed ? stay : up);   // (a lane past the last one: up = -inf)
+                hist = hist << 2 | (is_entry ? arg : (stayed ? 1u : 0u));
+            }
+            // the words of these windows: lane l takes the one of window l, its bits out of the eight owning lanes' histories
+            const int sh = 2 * ((qb + cnt - 1 - lane) & 15);
+            const unsigned e0 = (unsigned) __builtin_amdgcn_readlane((int) hist, ent0), e1 = (unsigned) __builtin_amdgcn_readlane((int) hist, ent1);
+            const unsigned e2 = (unsigned) __builtin_amdgcn_readlane((int) hist, ent2), e3 = (unsigned) __builtin_amdgcn_readlane((int) hist, ent3);
+            const unsigned s0 = (unsigned) __builtin_amdgcn_readlane((int) hist, sat0), s1 = (unsigned) __builtin_amdgcn_readlane((int) hist, sat1);
+            const unsigned s2 = (unsigned) __builtin_amdgcn_readlane((int) hist, sat2), s3 = (unsigned) __builtin_amdgcn_readlane((int) hist, sat3);
+            const unsigned w = ((e0 >> sh) & 3u) | ((e1 >> sh) & 3u) << 2 | ((e2 >> sh) & 3u) << 4 | ((e3 >> sh) & 3u) << 6 |
+                               ((s0 >> sh) & (m0 > 1 ? 1u : 0u)) << 8 | ((s1 >> sh) & (m1 > 1 ? 1u : 0u)) << 9 |
+                               ((s2 >> sh) & (m2 > 1 ? 1u : 0u)) << 10 | ((s3 >> sh) & (m3 > 1 ? 1u : 0u)) << 11;
+            if (lane >= qb && lane < qb + cnt) words = (int) w;
+        }
+        if (lane < n) bp[t0 + base + lane] = (uint16_t) words;   // (the word of a chunk's first window is never read)
+        __syncthreads();
+    }
+
+    // the end: the first largest lane in lane order
+    const DevRegion* __restrict__ Rl = &P->reg[REC_REGION(rec[t0 + T - 1])];
+    const double e = active ? Rl->trans[s][4] : 1.0;
+    unsigned bad = e != e ? HF_FLAG_NAN : 0u;
+    double fw = active ? x + (e == 0.0 ? HF_MLV_NEG_INF : log(e)) : HF_MLV_NEG_INF;
+    if (fw != fw) bad |= HF_FLAG_NAN;
+    int fl = lane;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double ow = __shfl_xor(fw, o, 64);
+        const int ol = __shfl_xor(fl, o, 64);
+        if (ow > fw || (ow == fw && ol < fl)) { fw = ow; fl = ol; }
+    }
+    if (!(fw > HF_MLV_NEG_INF) && fw == fw) bad |= HF_FLAG_SCALE;
+    if (lane == 0) { ll[c] = fw; final_lane[c] = (uint8_t) fl; }
+    if (bad) atomicOr(flags, bad);
+}
+
+// the walk back, wave-uniform: (cs, cd) through the words of 64 windows at a time
+__global__ void __launch_bounds__(64) k_mlv_back(const int64_t* __restrict__ off, int m0, int m1, int m2, int m3,
+                                                 const uint16_t* __restrict__ bp, const uint8_t* __restrict__ final_lane,
+                                                 int8_t* __restrict__ label) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int64_t t0 = off[c], T = off[c + 1] - t0;
+    if (T <= 0) return;
+    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2;
+    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
+    const int fl = __builtin_amdgcn_readfirstlane((int) final_lane[c]);
+    int cs = (fl >= b1) + (fl >= b2) + (fl >= b3);
+    int cd = fl - (cs == 0 ? 0 : cs == 1 ? b1 : cs == 2 ? b2 : b3) + 1;
+    for (int64_t hi = T - 1; hi >= 0; hi -= 64) {
+        const int n = (int) (hi + 1 < 64 ? hi + 1 : 64);
+        const int wd = (lane < n && hi - lane >= 1) ? (int) bp[t0 + hi - lane] : 0;
+        int lab = 0;
+        for (int q = 0; q < n; q++) {
+            lab = lane == q ? cs : lab;
+            const int w = __builtin_amdgcn_readlane(wd, q);
+            // an entry lane: to the saturated lane of its predecessor; else one lane down, unless the saturated lane stayed
+            const int p = (w >> (2 * cs)) & 3, stayed = (w >> (8 + cs)) & 1;
+            const bool entry = cd == 1;
+            const int down = (cd < mlv_len(mpack, cs)) | (stayed ^ 1);
+            cd = entry ? mlv_len(mpack, p) : cd - down;
+            cs = entry ? p : cs;
+        }
+        if (lane < n) label[t0 + hi - lane] = (int8_t) lab;
+    }
+}

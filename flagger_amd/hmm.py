@@ -566,6 +566,24 @@ class EMList:
         N.check(self._L.hf_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_chunk_log_probs")
         return labels, ll, float(lp.value)
 
+    def viterbi_minlen(self, model: HMM, min_len):
+        """The most probable path among the paths whose runs have at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at
+        a chunk's ends are exempt; hf_viterbi_minlen + hf_viterbi_minlen_finish): (labels, chunk_log_probs, log_prob).  The last pass's
+        results, viterbi()'s and the sampler's are left as they were."""
+        ml = np.asarray(min_len)
+        if ml.shape != (4,):
+            raise ValueError("viterbi_minlen: min_len holds four window counts (Err, Dup, Hap, Col)")
+        ml = np.ascontiguousarray(ml, dtype=np.int32)
+        p = model.params()
+        lp = C.c_double(0.0)
+        N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_viterbi_minlen")
+        N.check(self._L.hf_viterbi_minlen_finish(self._h, C.byref(lp), self.stream), "hf_viterbi_minlen_finish")
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        N.check(self._L.hf_get_viterbi_minlen_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_viterbi_minlen_labels")
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        N.check(self._L.hf_get_viterbi_minlen_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_minlen_chunk_log_probs")
+        return labels, ll, float(lp.value)
+
     @property
     def sample_capacity(self) -> int:
         """Samples one hf_sample_paths call may draw (nine tenths of the free device memory; hf_sample_capacity)."""
@@ -788,6 +806,15 @@ def EM_runViterbiForList(emList, model: HMM):
     if not hasattr(emList, "viterbi"):
         raise TypeError("EM_runViterbiForList: %s has no most-probable-path decoder" % type(emList).__name__)
     return emList.viterbi(model)
+
+
+def EM_runMinLengthViterbiForList(emList, model: HMM, min_len):
+    """Most-probable-path decoding under minimum run lengths (no counterpart in the reference, which relabels short runs after decoding):
+    the best path among those whose runs of state s have at least min_len[s] windows, runs at a chunk's ends exempt.  Returns what
+    EM_runViterbiForList returns.  `emList`: an EMList."""
+    if not hasattr(emList, "viterbi_minlen"):
+        raise TypeError("EM_runMinLengthViterbiForList: %s has no minimum-run-length decoder" % type(emList).__name__)
+    return emList.viterbi_minlen(model, min_len)
 
 
 def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:

@@ -429,6 +429,38 @@ int hf_viterbi_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_labels(hf_ctx *ctx, int8_t *labels_host);                          /* [n_windows], layout of hf_labels_dev */
 int hf_get_viterbi_chunk_log_probs(hf_ctx *ctx, double *out_host);                    /* [n_chunks] */
 
+/* Minimum-run-length Viterbi (flagger_amd/csrc/hf_minlen.h): the most probable path AMONG THE PATHS WHOSE RUNS MEET A MINIMUM LENGTH, the
+ * exact form of minimum-duration decoding.  first[s], A_t[pre][s], end[s] and the weight of a path are exactly those of hf_viterbi.
+ * min_len[4] holds windows per state (0 Err, 1 Dup, 2 Hap, 3 Col), 1 <= min_len[s] and sum_s min_len[s] <= HF_MINLEN_MAX_LANES.
+ * A path of a chunk of T windows is ADMISSIBLE when every maximal run of equal state s has at least min_len[s] windows; a run that
+ * contains the chunk's first or last window is exempt (a chunk is a cut of a contig, and the final BED merges runs across the chunks of
+ * a contig), so a constant path is always admissible.  The decoder returns
+ *   s* = argmax over admissible paths of first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}].
+ * It runs the expanded chain with lanes (s, d), d = 1..min_len[s]: "in state s, the current run has d windows so far", at
+ * d = min_len[s] "at least that many" (the saturated lane):
+ *   window 0:   delta[(s, min_len[s])] = first[s], every other lane has no weight (the exempt left end);
+ *   lane (s,1): the maximum over predecessors p in increasing order of delta[(p, min_len[p])] * A_t[p][s], with p != s when
+ *               min_len[s] > 1 (with min_len[s] == 1, p = s is the "stay", at its place); replacement needs strict >, so the lowest p
+ *               wins a tie;
+ *   lane (s,d), 1 < d < min_len[s]: delta[(s, d-1)] * A_t[s][s];
+ *   lane (s,d), d = min_len[s] > 1: delta[(s, d-1)] * A_t[s][s], then delta[(s, d)] * A_t[s][s], strict >;
+ *   end:        the maximum over all lanes, in order of s and then of d ascending, of delta[(s,d)] * end[s], strict > (the exempt
+ *               right end).
+ * With all four lengths 1 this is hf_viterbi's recurrence and tie rule.  The chain is carried IN LOGS (log of every row entry, -inf for
+ * 0; a product above is a sum), so nothing underflows at any chunk length and a step is one add and one compare.
+ * The chunk's score is the log of the maximum, the run's score the sum over chunks in list order; a chunk without windows scores 0;
+ * windows outside every chunk get label -1.  HF_E_SCALE when no admissible path of a chunk has weight, HF_E_NAN on a NaN in a row or in
+ * the end column.  HF_E_ARG: a NULL argument, a length below 1, a sum above HF_MINLEN_MAX_LANES, a getter before any finished run.
+ * Streams: as hf_viterbi (any stream of the caller's; hf_viterbi_minlen_finish takes the same one).  Buffers of its own: the last pass's
+ * results, hf_viterbi's results, the sampler's results and the next hf_estep are bitwise unaffected.  One code path serves HF_ALGO_SCAN
+ * and HF_ALGO_SEQ contexts and all three model types: the outputs are bitwise the same on both kinds of context and across repeated
+ * calls.  hf_batch_* and hf_multi_* have no counterpart. */
+#define HF_MINLEN_MAX_LANES 64
+int hf_viterbi_minlen(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4], void *stream);   /* asynchronous, as hf_viterbi */
+int hf_viterbi_minlen_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
+int hf_get_viterbi_minlen_labels(hf_ctx *ctx, int8_t *labels_host);                   /* [n_windows] */
+int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx *ctx, double *out_host);             /* [n_chunks] */
+
 /* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
  * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
  *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]
