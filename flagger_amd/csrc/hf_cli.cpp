@@ -5,6 +5,7 @@
 #include "../../include/hmm_flagger_io.h"
 #include "../../include/hmm_flagger_model.h"
 #include "../../include/hmm_flagger_multi.h"
+#include "hf_jobs.h"
 #include "hf_squarem.h"
 #include <getopt.h>
 #include <sys/resource.h>
@@ -75,6 +76,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
     {"jointEntropy", no_argument, nullptr, 1017},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
     {"runBoundaries", no_argument, nullptr, 1018},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
+    {"keptBlocks", no_argument, nullptr, 1020},                 // exact probability of a block --minimumLengths would keep (hf_get_long_run_log_probs)
     {"enforceMinimumLengths", no_argument, nullptr, 1019},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
     {nullptr, 0, nullptr, 0}};
 
@@ -162,7 +164,13 @@ static void usage(const char* program) {
             "                                      the best path with its short runs relabelled afterwards; viterbi_log_probability.tsv holds the score\n"
             "                                      of the path written, viterbi_min_length_cost.tsv the four window counts, the constrained and the\n"
             "                                      unconstrained score, their difference and the number of chunks whose two paths differ; one GPU, not\n"
-            "                                      with --gpus N>1 or --sweepAlpha\n");
+            "                                      with --gpus N>1 or --sweepAlpha\n"
+            "         --keptBlocks                 with --minimumLengths: after every other output, write kept_block_probabilities.tsv: for the whole\n"
+            "                                      track, every contig and (with --regionProbs FILE) every region, and for every label, the exact\n"
+            "                                      probability that the scope holds a block of the label long enough to be kept (lengths in windows\n"
+            "                                      as for --enforceMinimumLengths: ceil(length / windowLen), at least 1; Hap: 1; at most 58 windows),\n"
+            "                                      runs merged across the chunks of a contig as the final BED merges them; one GPU, not with\n"
+            "                                      --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -479,6 +487,36 @@ static bool read_regions(const char* path, std::vector<Region>& regions) {
     return ok;
 }
 
+// The windows of every region (those whose bases meet [start, end) on the region's contig), sorted, and the same as maximal ranges of
+// consecutive window indices; a region on an unknown contig has none.
+static void region_windows(const hfio_table* tab, const hf_windows& w, int C, const std::vector<int64_t>& wbases, const std::vector<Region>& regions,
+                           std::vector<std::vector<int64_t>>& wins, std::vector<std::vector<std::pair<int64_t, int64_t>>>& ranges) {
+    // every contig's windows in base order: (first base, last base, window)
+    std::map<std::string, std::vector<std::array<int64_t, 3>>> byCtg;
+    for (int c = 0; c < C; c++) {
+        auto& v = byCtg[hfio_chunk_ctg(tab, c)];
+        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+            const int64_t s = (int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len;
+            v.push_back({s, s + wbases[(size_t) t] - 1, t});
+        }
+    }
+    for (auto& kv : byCtg) std::sort(kv.second.begin(), kv.second.end());
+    wins.assign(regions.size(), {});
+    ranges.assign(regions.size(), {});
+    for (size_t i = 0; i < regions.size(); i++) {
+        const Region& g = regions[i];
+        auto it = byCtg.find(g.ctg);
+        if (it == byCtg.end()) continue;
+        for (const auto& x : it->second)
+            if (x[0] < g.end && x[1] >= g.start) wins[i].push_back(x[2]);
+        std::sort(wins[i].begin(), wins[i].end());
+        for (int64_t t : wins[i]) {
+            if (!ranges[i].empty() && ranges[i].back().second + 1 == t) ranges[i].back().second = t;
+            else ranges[i].push_back({t, t});
+        }
+    }
+}
+
 // --runConfidence / --regionProbs: exact label probabilities of windows ranges (hf_get_interval_log_probs) under the model of the last
 // full pass, and the mean posterior (hf_get_posterior).
 //   final_label_runs_confidence.bed    per run of final_label_runs_support.bed (same rows, same order): p_all = P(every window has the
@@ -526,32 +564,13 @@ static int write_interval_outputs(hf_ctx* ctx, const hfio_table* tab, const int8
         if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
     }
     if (regions) {
-        // every contig's windows in base order: (first base, last base, window)
-        std::map<std::string, std::vector<std::array<int64_t, 3>>> byCtg;
-        for (int c = 0; c < C; c++) {
-            auto& v = byCtg[hfio_chunk_ctg(tab, c)];
-            for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-                const int64_t s = (int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len;
-                v.push_back({s, s + wbases[(size_t) t] - 1, t});
-            }
-        }
-        for (auto& kv : byCtg) std::sort(kv.second.begin(), kv.second.end());
         // the windows of every region, as maximal index ranges; one job per range and mask (Err..Col alone, and all but each)
-        std::vector<std::vector<int64_t>> wins(regions->size());
-        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges(regions->size());
+        std::vector<std::vector<int64_t>> wins;
+        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
+        region_windows(tab, w, C, wbases, *regions, wins, ranges);
         std::vector<int64_t> first, last;
         std::vector<uint8_t> mask;
         for (size_t i = 0; i < regions->size(); i++) {
-            const Region& g = (*regions)[i];
-            auto it = byCtg.find(g.ctg);
-            if (it == byCtg.end()) continue;
-            for (const auto& x : it->second)
-                if (x[0] < g.end && x[1] >= g.start) wins[i].push_back(x[2]);
-            std::sort(wins[i].begin(), wins[i].end());
-            for (int64_t t : wins[i]) {
-                if (!ranges[i].empty() && ranges[i].back().second + 1 == t) ranges[i].back().second = t;
-                else ranges[i].push_back({t, t});
-            }
             for (const auto& r : ranges[i])
                 for (int m = 0; m < 8; m++) { first.push_back(r.first); last.push_back(r.second); mask.push_back((uint8_t) (m < 4 ? 1u << m : 15u & ~(1u << (m - 4)))); }
         }
@@ -796,6 +815,81 @@ static int write_exact_blocks(hf_ctx* ctx, const hfio_table* tab, const int8_t* 
     return HF_OK;
 }
 
+// --keptBlocks: the exact probability that a scope holds a block of a label that --minimumLengths would keep (hf_get_long_run_log_probs)
+// under the model of the last full pass.
+//   kept_block_probabilities.tsv   one row for the whole track ("all"), one per contig (order of first appearance in the chunk list) and,
+//                                  with --regionProbs FILE, one per region in file order (a region without windows: NA).  Per label L:
+//                                  min_windows_L (the length in windows), p_block_L = P(some run of at least that many consecutive
+//                                  windows of L), p_none_L = 1 - p_block_L.  A run goes on from chunk c-1 into chunk c where the two are
+//                                  adjacent in the chunk list and carry the same contig name (the rule of --numBlocks); the pieces of a
+//                                  scope that no such join connects are independent, and their log_p_none add.
+static int write_kept_blocks(hf_ctx* ctx, const hfio_table* tab, const std::vector<Region>* regions, const int32_t minLenWindows[4],
+                             const std::vector<std::string>& labelNames, const std::string& dir) {
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    // a row: scope, name, its windows and its window ranges [first, last]
+    struct Row { const char* scope; std::string name; int64_t n; std::vector<std::pair<int64_t, int64_t>> ranges; };
+    std::vector<Row> rows;
+    rows.push_back(Row{"all", "all", 0, {}});
+    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
+    std::map<std::string, size_t> ctgRow;
+    for (int c = 0; c < C; c++) {
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
+        auto it = ctgRow.find(ctg);
+        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{"contig", ctg, 0, {}}); }
+        if (w.chunk_off[c] == w.chunk_off[c + 1]) continue;
+        for (size_t ri : {(size_t) 0, it->second}) {
+            Row& r = rows[ri];
+            r.n += w.chunk_off[c + 1] - w.chunk_off[c];
+            if (!r.ranges.empty() && r.ranges.back().second + 1 == w.chunk_off[c]) r.ranges.back().second = w.chunk_off[c + 1] - 1;
+            else r.ranges.push_back({w.chunk_off[c], w.chunk_off[c + 1] - 1});
+        }
+    }
+    if (regions) {
+        std::vector<int64_t> wbases;
+        window_bases(w, C, wbases, nullptr);
+        std::vector<std::vector<int64_t>> wins;
+        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
+        region_windows(tab, w, C, wbases, *regions, wins, ranges);
+        for (size_t i = 0; i < regions->size(); i++) rows.push_back(Row{"region", (*regions)[i].name, (int64_t) wins[i].size(), ranges[i]});
+    }
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> mask;
+    std::vector<int32_t> len;
+    for (const Row& r : rows)
+        for (const auto& rg : r.ranges)
+            for (int l = 0; l < 4; l++) { first.push_back(rg.first); last.push_back(rg.second); mask.push_back((uint8_t) (1u << l)); len.push_back(minLenWindows[l]); }
+    std::vector<double> none(first.size());
+    const int rc = hf_get_long_run_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), len.data(), joined.data(),
+                                             none.data(), nullptr);
+    if (rc != HF_OK) return rc;
+    const std::string tp = dir + "/kept_block_probabilities.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\tname\tn_windows");
+    for (int l = 0; l < 4; l++) {
+        const char* name = labelNames.size() > (size_t) l ? labelNames[(size_t) l].c_str() : kRunLabelNames[l];
+        fprintf(f, "\tmin_windows_%s\tp_block_%s\tp_none_%s", name, name, name);
+    }
+    fprintf(f, "\n");
+    size_t j = 0;
+    for (const Row& r : rows) {
+        fprintf(f, "%s\t%s\t%ld", r.scope, r.name.c_str(), (long) r.n);
+        double s[4] = {0, 0, 0, 0};                                   // sums over the ranges, in order
+        for (size_t k = 0; k < r.ranges.size(); k++)
+            for (int l = 0; l < 4; l++) s[l] += none[j++];
+        for (int l = 0; l < 4; l++) {
+            if (r.n == 0) fprintf(f, "\tNA\tNA\tNA");
+            else fprintf(f, "\t%d\t%.6g\t%.6g", (int) minLenWindows[l], -std::expm1(s[l]) + 0.0, std::exp(s[l]));
+        }
+        fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --jointEntropy: exact path entropy and log-probability of the final labels (hf_get_path_entropy, hf_get_path_log_probs,
 // hf_get_entropy_profile) under the model of the last full pass.
 //   path_uncertainty.tsv   one row per scope.  Scopes: "all" and every contig by name (order of first appearance in the chunk list; chunks
@@ -904,7 +998,7 @@ int main(int argc, char* argv[]) {
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
     double initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false;
+    bool viterbi = false, enforceMinLen = false, keptBlocks = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
@@ -991,6 +1085,7 @@ int main(int argc, char* argv[]) {
                     return EXIT_FAILURE;
                 }
                 minLenPerState[0] = a; minLenPerState[1] = b; minLenPerState[3] = d;
+                minLenGiven = true;
                 break;
             }
             case 1001: device = atoi(optarg); break;
@@ -1017,6 +1112,7 @@ int main(int argc, char* argv[]) {
             case 1018: runBoundaries = true; break;
             case 1017: jointEntropy = true; break;
             case 1019: enforceMinLen = true; break;
+            case 1020: keptBlocks = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -1132,6 +1228,12 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] Error: --enforceMinimumLengths runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
+    // --keptBlocks: likewise
+    if (keptBlocks && !minLenGiven) { fprintf(stderr, "[%s] Error: --keptBlocks needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
+    if (keptBlocks && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --keptBlocks runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
     if (!inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return EXIT_FAILURE; }
     if (convergenceTol <= 0.0 || convergenceTol > 1.0) {
         fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), convergenceTol);
@@ -1178,12 +1280,20 @@ int main(int argc, char* argv[]) {
             minLenWindows[s] = (int32_t) std::min(w, 1000000LL);
             sum += minLenWindows[s];
         }
-        if (sum <= HF_MINLEN_MAX_LANES) return true;
+        // --keptBlocks: one label at a time, each within the lanes of hf_get_long_run_log_probs
+        for (int s = 0; keptBlocks && s < 4; s++)
+            if (long_run_lanes(1 << s, minLenWindows[s]) > HF_LONGRUN_MAX_LANES) {
+                fprintf(stderr, "[%s] Error: --keptBlocks: the minimum lengths %d,%d,%d (Err,Dup,Col) are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col); a label's may be %d windows at most.\n",
+                        ts(), minLenPerState[0], minLenPerState[1], minLenPerState[3], minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W,
+                        HF_LONGRUN_MAX_LANES - 6);
+                return false;
+            }
+        if (!enforceMinLen || sum <= HF_MINLEN_MAX_LANES) return true;
         fprintf(stderr, "[%s] Error: --enforceMinimumLengths: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
                 ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
         return false;
     };
-    if (enforceMinLen && !min_len_windows(windowLen)) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks) && !min_len_windows(windowLen)) return EXIT_FAILURE;
     if (0.5 < initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return EXIT_FAILURE; }
 
     // 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
@@ -1215,7 +1325,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), hfio_n_chunks(tab), (long) N, hfio_window_len(tab));
     if (N == 0 || hfio_n_chunks(tab) == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return EXIT_FAILURE; }
 
-    if (enforceMinLen && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
     phase("load input (+ HIP start-up)");
     // 2. number of collapsed components (hmm_flagger.c:1008-1022)
     hf_windows w;
@@ -1518,6 +1628,13 @@ int main(int argc, char* argv[]) {
         const double t0 = real_time();
         if ((rc = write_path_uncertainty(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] path_uncertainty.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --keptBlocks: after every other output
+    if (keptBlocks) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --keptBlocks needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        if ((rc = write_kept_blocks(run.ctx, tab, regionProbsPath ? &regions : nullptr, minLenWindows, labelNames, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] kept_block_probabilities.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

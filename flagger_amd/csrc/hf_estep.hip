@@ -488,7 +488,8 @@ struct AlphaStats {
 };
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
-// the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer, the entropy getters' buffers
+// the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer, the entropy getters' buffers, the breakpoint
+// getter's and the long-run getter's
 struct hf_ctx {
     Track tr;
     Pass pass;
@@ -501,6 +502,7 @@ struct hf_ctx {
     DevBuf rn;                // hf_runs.h: pieces, parts, piece triples, piece sums of xi, results
     DevBuf en, en_lab;        // hf_entropy.h: pieces, parts, piece sums, results / the profile's two arrays; the labels of a call
     DevBuf bp;                // hf_breakpoint.h: pieces, parts, piece products, the chain's vectors, the windows' weights, results
+    DevBuf lr;                // hf_longrun.h: parts, groups, results
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1044,6 +1046,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->en.release();
     ctx->en_lab.release();
     ctx->bp.release();
+    ctx->lr.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -3100,5 +3103,96 @@ int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx* ctx, double* out_host) {
     if (!ctx || !out_host || !ctx->mlv.done) return set_err(HF_E_ARG, "hf_get_viterbi_minlen_chunk_log_probs: no finished hf_viterbi_minlen");
     const Track& tr = ctx->tr;
     if (tr.C > 0) std::memcpy(out_host, ctx->mlv.h_ll.data(), (size_t) tr.C * 8);
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// exact long-run probabilities (hf_longrun.h): the job cutter's parts fall into groups of joined parts (hf_jobs.h group_parts), one
+// wavefront of k_lr_chain walks a group's expanded chain, a job is folded from its groups on the host.  Last in the file, its kernel
+// included, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_longrun.h"
+
+static_assert(HF_LONGRUN_MAX_LANES == 64, "one wavefront holds the expanded chain");
+
+// parts, and windows in pieces of 512 (the grid of the other getters), per device batch: a group is one workgroup and a window one step
+// of it, so the caps bound a launch's run time, not its memory.  The environment variables of the same names lower them (tests).
+#ifndef HF_LR_BATCH_PARTS
+#define HF_LR_BATCH_PARTS (1 << 16)
+#endif
+#ifndef HF_LR_BATCH_PIECES
+#define HF_LR_BATCH_PIECES (1 << 18)
+#endif
+
+static size_t lr_cap(const char* name, size_t dflt) {
+    if (const char* e = std::getenv(name)) { const long v = std::atol(e); if (v >= 1) return std::min<size_t>((size_t) v, dflt); }
+    return dflt;
+}
+
+// log(1 - exp(x)), x <= 0
+static double lr_log1mexp(double x) { return x > -0.69314718055994530942 ? std::log(-std::expm1(x)) : std::log1p(-std::exp(x)); }
+
+int hf_get_long_run_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, const int32_t* min_len,
+                              const uint8_t* joined, double* log_p_none_host, double* log_p_some_host) {
+    const std::string who = "hf_get_long_run_log_probs";
+    if (!ctx) return set_err(HF_E_ARG, who + ": bad argument");
+    const Track& tr = ctx->tr;
+    int rc = rg_check(ctx, who, n, !first || !last || !state_mask || !min_len || (!log_p_none_host && !log_p_some_host), first, last, state_mask,
+                      nullptr, nullptr, joined && tr.C > 0 && joined[0] ? "joined[0] must be 0 (the first chunk continues nothing)" : nullptr);
+    if (rc) return rc;
+    for (int64_t i = 0; i < n; i++) {
+        if (min_len[i] < 1) return set_err(HF_E_ARG, who + ": min_len must be at least 1 (job " + std::to_string(i) + ")");
+        if (long_run_lanes(state_mask[i], min_len[i]) > HF_LONGRUN_MAX_LANES)
+            return set_err(HF_E_ARG, who + ": the expanded chain needs more than " + std::to_string(HF_LONGRUN_MAX_LANES) + " lanes (job " + std::to_string(i) + ")");
+    }
+    PassView pv;
+    rc = pass_view(ctx, who, n, pv);
+    if (rc || n == 0) return rc;
+    hipStream_t st = ctx->pass.last_stream;
+    const size_t cap_pieces = lr_cap("HF_LR_BATCH_PIECES", HF_LR_BATCH_PIECES), cap_parts = lr_cap("HF_LR_BATCH_PARTS", HF_LR_BATCH_PARTS);
+    JobCut<LrPiece, LrPart, 512> jc;
+    std::vector<LrGroup> groups;
+    std::vector<int64_t> job_g0;
+    std::vector<double> val;
+    for (int64_t j0 = 0; j0 < n;) {
+        const int64_t j1 = jc.cut(tr.h_off, n, first, last, j0, cap_pieces, cap_parts,
+            [](int64_t, int c, int64_t a, int64_t b) { return LrPart{a, b, 0, 0, c, 0}; },
+            [](const LrPart&, int64_t, int) { return LrPiece{0}; });
+        group_parts(jc.parts, jc.job_p0, joined, groups, job_g0,
+            [&](int64_t j, int64_t q0, int64_t q1) { return LrGroup{(int) q0, (int) q1, state_mask[j0 + j], min_len[j0 + j]}; });
+        const size_t nq = jc.parts.size(), ng = groups.size();
+        const size_t o_groups = Slab::granule(nq * sizeof(LrPart)), o_out = o_groups + Slab::granule(ng * sizeof(LrGroup));
+        rc = ctx->lr.reserve(o_out + Slab::granule(ng * 2 * 8), who);
+        if (rc) return rc;
+        LrPart* d_parts = reinterpret_cast<LrPart*>(ctx->lr.d_buf);
+        LrGroup* d_groups = reinterpret_cast<LrGroup*>(ctx->lr.d_buf + o_groups);
+        double* d_out = reinterpret_cast<double*>(ctx->lr.d_buf + o_out);
+        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(LrPart), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_groups, groups.data(), ng * sizeof(LrGroup), hipMemcpyHostToDevice, st));
+        by_algo(tr, [&](auto S) {
+            constexpr bool SEQ = decltype(S)::value;
+            hipLaunchKernelGGL(k_lr_chain<SEQ>, dim3((unsigned) ng), dim3(64), 0, st, d_groups, d_parts, pv, d_out);
+        });
+        HIPCHK(hipGetLastError());
+        val.resize(ng * 2);
+        HIPCHK(hipMemcpyAsync(val.data(), d_out, ng * 2 * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int64_t j = j0; j < j1; j++) {
+            // the groups of a job in chunk order: log_p_none is their left-to-right sum.  log_p_some: -inf when no group can hold a run,
+            // the kernel's own value (accurate however small) when exactly one can, else log(1 - exp(log_p_none))
+            double none = 0.0, some = -__builtin_inf();
+            int hits = 0;
+            for (int64_t g = job_g0[(size_t) (j - j0)]; g < job_g0[(size_t) (j - j0) + 1]; g++) {
+                none += val[(size_t) g * 2];
+                const double s = val[(size_t) g * 2 + 1];
+                if (!(s == -__builtin_inf())) { hits++; some = s; }
+            }
+            if (hits > 1) some = lr_log1mexp(none);
+            if (log_p_none_host) log_p_none_host[j] = none;
+            if (log_p_some_host) log_p_some_host[j] = some;
+        }
+        j0 = j1;
+    }
     return HF_OK;
 }

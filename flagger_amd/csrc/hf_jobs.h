@@ -9,6 +9,10 @@
 // THE BATCHING RULE.  A call's jobs go to the device in batches, in order: a job joins the batch while the batch holds fewer than
 // cap_pieces pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split.  The caller gives the caps (the
 // getters': HF_IV_BATCH_*, HF_MO_BATCH_* of hf_estep.hip).
+//
+// THE GROUPING RULE (hf_get_long_run_log_probs).  joined[c] != 0 says that chunk c continues chunk c - 1 (joined == nullptr: no chunk
+// does).  Part k of a job is joined to part k - 1 when it lies in the next chunk and that chunk has joined != 0; a chunk without windows
+// has no part, so it ends a sequence of joined chunks.  A GROUP is a maximal sequence of parts joined to each other.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -53,3 +57,26 @@ struct JobCut {
         return j1;
     }
 };
+
+// The groups of a cut batch, in order: mk_group(job index in the batch, q0, q1) builds the group of parts q0 .. q1 - 1 (Part has an int
+// member c, its chunk).  job_g0: the first group of every job of the batch, and the end.
+template <class Part, class Group, class MkGroup>
+void group_parts(const std::vector<Part>& parts, const std::vector<int64_t>& job_p0, const uint8_t* joined, std::vector<Group>& groups,
+                 std::vector<int64_t>& job_g0, MkGroup&& mk_group) {
+    groups.clear(); job_g0.clear();
+    for (size_t j = 0; j + 1 < job_p0.size(); j++) {
+        job_g0.push_back((int64_t) groups.size());
+        for (int64_t q0 = job_p0[j], q = q0 + 1; q0 < job_p0[j + 1]; q++) {
+            const bool join = q < job_p0[j + 1] && joined && parts[(size_t) q].c == parts[(size_t) q - 1].c + 1 && joined[parts[(size_t) q].c] != 0;
+            if (!join) { groups.push_back(mk_group((int64_t) j, q0, q)); q0 = q; }
+        }
+    }
+    job_g0.push_back((int64_t) groups.size());
+}
+
+// lanes of the expanded chain of hf_get_long_run_log_probs: the states outside S, the counters (s, d), d = 1 .. L - 1, the four HIT lanes
+inline int64_t long_run_lanes(int mask, int64_t len) {
+    int k = 0;
+    for (int s = 0; s < 4; s++) k += (mask >> s) & 1;
+    return (4 - k) + k * (len - 1) + 4;
+}

@@ -678,6 +678,35 @@ class EMList:
                                            _dptr(mean), _dptr(var)), "hf_get_run_moments")
         return mean, var
 
+    def long_run_log_probs(self, first, last, mask, min_len, joined=None):
+        """Exact long-run probabilities under the model of the last full pass (hf_get_long_run_log_probs): for every job i, whether the
+        windows first[i]..last[i] (inclusive) hold a run of at least min_len[i] consecutive windows whose state is in the set mask[i]
+        (the states may change inside the set).  joined: as for run_moments, a run goes on across a joined chunk boundary
+        -> (log_p_none float64[n], log_p_some float64[n]): log P(no such run | data), log P(some such run | data).  Scalars broadcast."""
+        f, l, m, k = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64),
+                                         np.asarray(min_len, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("long_run_log_probs: a state mask must be 1..15")
+        if k.size and (k.min() < -2 ** 31 or k.max() >= 2 ** 31):
+            raise ValueError("long_run_log_probs: a length must be a positive number of windows")
+        jn = None
+        if joined is not None:
+            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
+            if jn.size != int(self._L.hf_n_chunks(self._h)):
+                raise ValueError("long_run_log_probs: joined must have one entry per chunk")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        k = np.ascontiguousarray(k.ravel(), np.int32)
+        none = np.empty(f.size, dtype=np.float64)
+        some = np.empty(f.size, dtype=np.float64)
+        N.check(self._L.hf_get_long_run_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  k.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  _dptr(none), _dptr(some)), "hf_get_long_run_log_probs")
+        return none, some
+
     def path_entropy(self, first, last) -> np.ndarray:
         """Exact path entropy under the model of the last full pass (hf_get_path_entropy): for every job i, the Shannon entropy in nats
         of the joint posterior distribution of the labels of the windows first[i]..last[i] (inclusive; chunks are independent chains)
@@ -849,6 +878,15 @@ def EM_getRunMomentsForList(emList, first, last, mask, joined=None):
     if not hasattr(emList, "run_moments"):
         raise TypeError("EM_getRunMomentsForList: %s has no run-moments getter" % type(emList).__name__)
     return emList.run_moments(first, last, mask, joined)
+
+
+def EM_getLongRunLogProbsForList(emList, first, last, mask, min_len, joined=None):
+    """(log P(no run), log P(some run)) of at least min_len[i] consecutive windows of first[i]..last[i] whose state lies in mask[i],
+    under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run goes on across the
+    boundary (no counterpart in the reference): (float64[n], float64[n]).  `emList`: an EMList."""
+    if not hasattr(emList, "long_run_log_probs"):
+        raise TypeError("EM_getLongRunLogProbsForList: %s has no long-run getter" % type(emList).__name__)
+    return emList.long_run_log_probs(first, last, mask, min_len, joined)
 
 
 def EM_getPathEntropyForList(emList, first, last) -> np.ndarray:

@@ -382,6 +382,54 @@ int hf_get_breakpoints(hf_ctx *ctx, int64_t n, const int64_t *first, const int64
                        int64_t *quantile_host /* [n][n_probs] */, int64_t *mode_host /* [n] */, double *mode_p_host /* [n] */);
 int hf_get_breakpoint_profile(hf_ctx *ctx, int64_t first, int64_t last, uint8_t left_mask, uint8_t right_mask,
                               double *p_host /* [last - first], k = first+1 .. last */, double *log_p_event_host);
+/* Exact long-run probabilities (flagger_amd/csrc/hf_longrun.h), under the model of the last HF_MODE_FULL pass like hf_get_posterior: how
+ * probable is it that a range holds a block of a label set that is long enough to be reported.  f, b are that pass's scaled forward and
+ * backward vectors (hf_get_forward_backward), A_t the row the pass multiplied by at window t.  Job i is the window range
+ * first[i]..last[i] (global, inclusive, it may span chunks), a state set S = state_mask[i] (1..15), a length L = min_len[i] >= 1 in
+ * windows, and the optional joined[n_chunks] of hf_get_run_moments with the same meaning and the same joined[0] == 0 rule.  The job's
+ * parts are its chunk-local ranges [a, b]; part j+1 is joined to part j under the rule hf_get_run_moments states; a GROUP is a maximal
+ * sequence of parts joined to each other, its label sequence the concatenation of its parts' windows.  HIT: the group's sequence contains
+ * at least L consecutive windows whose state is in S (runs are clipped at the job's ends; the windows of a run may change state inside
+ * S).  Chunks are independent chains given the data: the path distribution of a group is the product of its chunks' posterior path
+ * distributions.
+ *   log_p_none[i] = sum over the job's groups, in chunk order, of log P(no HIT in the group | data)
+ *   log_p_some[i] = log(1 - exp(log_p_none[i]))        (log P(some group has a HIT))
+ * The expanded chain of a group: one lane per state outside S, lanes (s, d) for s in S, d = 1..L-1 ("the current run of S has d
+ * windows"), four absorbing HIT lanes, one per state; a step from (s, L-1), or with L == 1 from anything, into a state of S goes to that
+ * state's HIT lane.
+ *   lanes(S, L) = (4 - |S|) + |S| (L - 1) + 4 <= HF_LONGRUN_MAX_LANES
+ * Window a of the first part starts the lanes with f_a[s]; a window inside a chunk multiplies by A_t; the step from the last window b of
+ * a part to the first window a' of the next joined part multiplies by the rank-one row b_b[p] * f_a'[s] (the previous chunk's posterior
+ * collapse times the next chunk's start: the counter runs on across the boundary); the last window of the group takes the dot product
+ * with b_b.  N_none is the sum over the non-HIT lanes, N_hit over the HIT lanes, P(no HIT) = N_none / (N_none + N_hit).
+ * THE ORDER of the operations.  Linear domain, value = x 2^E with separate integer exponent sums E_n (non-HIT lanes) and E_h (HIT lanes);
+ * the inflow into HIT is multiplied by 2^(E_n - E_h).  Every sum of a step runs over the source states p = 0..3 in order; the non-HIT
+ * total T[p] of a state of S is a sum over the wavefront in one fixed order (hf_longrun.h lr_wave_sum).  After every 8th step counted
+ * from the group's first window, each class is scaled by a power of two that brings the largest of its per-state totals, taken before
+ * that step, to exponent 300 (HIT lanes that were all zero take the non-HIT exponent, non-HIT lanes that are all zero the HIT exponent; otherwise E_n - E_h is
+ * kept <= 600): a group's bits depend on
+ * the job alone, and neither log N_none nor log N_hit underflows at any range length.  With d = (log N_hit - log N_none) + (E_h - E_n) ln 2,
+ * per group:
+ *   d < 0:   log P(no HIT) = -log1p(exp(d)),       log P(HIT) = d - log1p(exp(d))
+ *   d >= 0:  log P(no HIT) = -d - log1p(exp(-d)),  log P(HIT) = -log1p(exp(-d))
+ * so a tiny P(HIT) gives an accurate log P(HIT) and a log P(no HIT) that is -P(HIT) to rounding, and a tiny P(no HIT) stays finite down
+ * to the range hf_get_interval_log_probs reaches.  A job: log_p_none is the left-to-right sum of its groups' values from 0.0;
+ * log_p_some is -inf when no group has a HIT of positive weight, that group's log P(HIT) when exactly one has, else
+ * log(-expm1(log_p_none)) above -ln 2 and log1p(-exp(log_p_none)) below.
+ * Exact cases: N_hit == 0 gives log_p_none = 0.0 and log_p_some = -inf, so a group of fewer than L windows does; mask 15 with L <= the
+ * group's length gives (-inf, 0.0); with L == 1 the job is "some window in S" and log_p_none equals hf_get_interval_log_probs of mask
+ * 15 & ~S to rounding (mask 15: -inf).  No NaN, except where the pass itself left no weight (as hf_get_interval_log_probs).  A job's two
+ * values depend only on (first, last, mask, L, joined) and the pass, bitwise: not on the other jobs of the call, their order, their
+ * number or the device batch they fall in (HF_LR_BATCH_PARTS, HF_LR_BATCH_PIECES); without joins log_p_none is bitwise the left-to-right
+ * sum of the parts asked as separate jobs.  Synchronous on the pass's stream; the first call after an EM pass of the default algorithm
+ * re-runs the segment kernel once, as hf_get_posterior's does, also in several sub-passes.  HF_ALGO_SCAN and HF_ALGO_SEQ, all three model
+ * types.  Buffers of its own: nothing an EM pass or another getter reads is written.  n = 0 is a successful no-op.  Either output array
+ * may be NULL, not both.  HF_E_ARG: the cases of hf_get_interval_log_probs, min_len < 1, lanes(S, L) above the cap, joined[0] != 0, both
+ * outputs NULL with n > 0; any bad job refuses the whole call.  hf_batch_* and hf_multi_* have no counterpart. */
+#define HF_LONGRUN_MAX_LANES 64
+int hf_get_long_run_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
+                              const int32_t *min_len, const uint8_t *joined /* [n_chunks], NULL: none */,
+                              double *log_p_none_host, double *log_p_some_host /* either may be NULL, not both */);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
