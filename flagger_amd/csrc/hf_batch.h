@@ -139,9 +139,8 @@ int hf_batch_estep(hf_batch* b, const hf_params* p, const int32_t* models, int n
         if (shared) joint.push_back(i);
     }
     if (!joint.empty()) {
-        const int32_t* const sob = tr.d_seg_of_block;
         const auto& sb = tr.subs[0];
-        const int g0 = sob ? sb.b0 : sb.seg0, nblk = sob ? sb.b1 - sb.b0 : sb.seg1 - sb.seg0;
+        const int g0 = sb.seg0, nblk = sb.seg1 - sb.seg0;
         const int nc = tr.seg_nc;
         const size_t lds = seg_lds_bytes(nc);
         if (nc > 0 && lds > 64 * 1024 &&
@@ -160,9 +159,9 @@ int hf_batch_estep(hf_batch* b, const hf_params* p, const int32_t* models, int n
             }
             const dim3 grid((unsigned) nblk, (unsigned) nj);
             if (nc > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_fb_batch<true, true, true>), grid, dim3(64), lds, st, tr.d_seg, tr.d_arow, b->d_tab, bt,
-                                           tr.d_pos, (int32_t) g0, nc, sob);
+                                           tr.d_pos, (int32_t) g0, nc);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_fb_batch<true, true, false>), grid, dim3(64), lds, st, tr.d_seg, tr.d_arow, b->d_tab, bt,
-                                    tr.d_pos, (int32_t) g0, nc, sob);
+                                    tr.d_pos, (int32_t) g0, nc);
             HIPCHK(hipGetLastError());
         }
         for (int i : joint) {

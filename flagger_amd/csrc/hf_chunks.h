@@ -6,10 +6,7 @@
 
 // Round 6: the per-window arithmetic of k_stats_tile without its IEEE divisions where a prepared reciprocal (divp: within an ulp of the quotient)
 // or no division at all gives the same value to rounding — the kernel is bound by exactly this arithmetic (profiles/r05_chunks_path.txt), and
-// neither statistics path was ever bit-identical to a sequential run.  -DHF_CHUNKS_FASTDIV=0: the divisions of rounds 1-5.
-#ifndef HF_CHUNKS_FASTDIV
-#define HF_CHUNKS_FASTDIV 1
-#endif
+// neither statistics path was ever bit-identical to a sequential run.
 
 // ------------------------------------------------------------------------------------------
 // xi sufficient statistics (A6, A12).  For every pair (i, i+1), i = 1..T-2:
@@ -159,16 +156,11 @@ __global__ void __launch_bounds__(256, 2) k_stats_tile(int ntiles, const TileDes
                         const int k = HF_PS(p, s);
                         const double alpha = P->alpha[p * 4 + s];
                         // alpha == 0 (wave-uniform): (x - 0*px) / (1 - 0) is x itself
-#if HF_CHUNKS_FASTDIV
                         // (1 - alpha is wave-uniform and the same for every window: its reciprocal is prepared once — the compiler hoists it out of the
                         // window loop; count * prob / totProb of a one-component state is the count itself unless the emission value is zero, where
                         // the reference's 0 * 0 / 0 is a NaN: hmm_utils.c:812-839)
                         const double x_adj = alpha == 0.0 ? x : divp(x - alpha * px, prediv(1.0 - alpha));
                         const double w = Ev[k] == 0.0 ? __builtin_nan("") : adj[p];
-#else
-                        const double x_adj = alpha == 0.0 ? x : (x - alpha * px) / (1.0 - alpha);
-                        const double w = adj[p] * Ev[k] / Ev[k];
-#endif
                         a.g_mnum[s] += w * x_adj;
                         const double z = (x_adj - R->mean[s][0]) * (1.0 - alpha);
                         a.g_vnum[s] += w * z * z;
@@ -181,11 +173,7 @@ __global__ void __launch_bounds__(256, 2) k_stats_tile(int ntiles, const TileDes
 #pragma unroll
             for (int p = 0; p < 4; p++) {
                 const double alpha = P->alpha[p * 4 + 3];
-#if HF_CHUNKS_FASTDIV
                 xa[p] = alpha == 0.0 ? x : divp(x - alpha * px, prediv(1.0 - alpha));
-#else
-                xa[p] = alpha == 0.0 ? x : (x - alpha * px) / (1.0 - alpha);
-#endif
                 om[p] = 1.0 - alpha;
             }
             if (col_fast) {   // w = adj3 * pc / E3 with the four reciprocals of E3 prepared once for all components
@@ -343,21 +331,17 @@ __global__ void __launch_bounds__(128) k_chunk_stats(const int32_t* __restrict__
 // Error flags ride along as element V: this context's flag word, OR-ed with the flag rows of an exchange buffer
 // (n_ranks > 0: rank k's word is element 0 of row k*rows_per_rank + flag_row, written by k_flag_row) so that every rank
 // of a multi-GPU pass reports the same error.
-// seq != 0: `out` is the pinned host block and the host polls out[V+1]: the block that finishes last stamps it.
 __global__ void __launch_bounds__(64) k_reduce(const double* __restrict__ chunk_stats, const int32_t* __restrict__ row_index,
                                                int64_t n_chunks, int64_t V, double* __restrict__ out,
-                                               const unsigned* __restrict__ flags, int n_ranks, int rows_per_rank, int flag_row,
-                                               double seq, unsigned* __restrict__ done, unsigned long long* __restrict__ cks) {
+                                               const unsigned* __restrict__ flags, int n_ranks, int rows_per_rank, int flag_row) {
     const int64_t v = blockIdx.x;
     const int lane = threadIdx.x;
-    double written = 0.0;
     if (v == V) {
         if (flags) {
             unsigned fl = lane == 0 ? *flags : 0u;
             for (int k = lane; k < n_ranks; k += 64) fl |= (unsigned) chunk_stats[((int64_t) k * rows_per_rank + flag_row) * V];
             for (int o = 32; o > 0; o >>= 1) fl |= __shfl_xor(fl, o);
-            written = (double) fl;
-            if (lane == 0) out[V] = written;
+            if (lane == 0) out[V] = (double) fl;
         }
     } else {
         double acc = 0.0;
@@ -365,18 +349,6 @@ __global__ void __launch_bounds__(64) k_reduce(const double* __restrict__ chunk_
         for (int64_t c = lane; c < n_chunks; c += 64) acc += chunk_stats[(row_index ? (int64_t) row_index[c] : c) * V + v];
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
         if (lane == 0) out[v] = acc;
-        written = acc;
-    }
-    if (seq != 0.0 && lane == 0) {   // checksum of every word written (hf_cks_term), bound to the pass, then the stamp: see wait_total
-        atomicAdd(cks, hf_cks_term((unsigned long long) __double_as_longlong(written), v));
-        __threadfence_system();
-        if (atomicAdd(done, 1u) == gridDim.x - 1) {
-            const unsigned long long c = atomicAdd(cks, 0ull) + (unsigned long long) __double_as_longlong(seq);
-            *cks = 0ull; *done = 0u;
-            out[V + 2] = __longlong_as_double((long long) c);
-            out[V + 1] = seq;
-            __threadfence_system();
-        }
     }
 }
 

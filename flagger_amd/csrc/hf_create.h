@@ -11,7 +11,7 @@
 //   create_key_tables        slow-window list, emission keys, tiles of the per-chunk statistics
 //   create_rows_and_segments rows of A (second pass), sub-passes, segment descriptors
 //   create_statistics_plan   groups, row slots, the position of every window's record (third pass), the plan's uploads
-//   create_launch_config     one-launch guard, cached row blocks, XCD plan, the job list of the per-pass tables, environment switches
+//   create_launch_config     one-launch guard, cached row blocks, the job list of the per-pass tables, environment switches
 // The steps build the TRACK: everything they allocate on the device comes out of its slab and is released by hf_destroy — a step that fails
 // just returns its code and hf_create destroys the context.  The context's pass state comes last (pass_create, hf_estep.hip).
 #pragma once
@@ -621,8 +621,6 @@ void plan_groups_and_slots(CreateWork& cw, StatsPlan& pl, int bpw) {
             }
         }
     pl.rwoff[(size_t) n_regions] = (int32_t) (pl.rslots.size() / unit);
-    tr.n_parts = 1;
-    for (int reg = 0; reg < n_regions; reg++) if (pl.rwoff[(size_t) reg + 1] > pl.rwoff[(size_t) reg]) tr.n_parts++;
     tr.n_groups = (int) n_grp;
     pl.grp_off[n_grp] = (int32_t) (n_grp ? pl.grp_off[n_grp - 1] + (compact ? pl.grp_n[n_grp - 1] : HF_GRP_PAIRS) : 0);
     tr.plan_compact = compact;
@@ -777,40 +775,9 @@ int create_statistics_plan(CreateWork& cw) {
 // ------------------------------------------------------------------------------------------
 // 6. how the segment kernel will be launched, the job list of the per-pass tables, the environment's switches
 // ------------------------------------------------------------------------------------------
-// XCD plan (VERDICT r05 #2b): within every sub-pass the chunks are dealt to eight lists, each chunk to the list with the fewest segments so
-// far (ties: the lowest list), and list x's r-th segment runs as block b0 + 8 r + x — all segments of a chunk on blocks congruent mod 8
-// (observed: block b runs on XCD b % 8), the lists within one chunk's segments of each other (padding blocks: -1, they leave at once).  A
-// chunk's segments then span 8 x nseg block indices instead of nseg: the plan is only built where twice that span is resident, so the
-// one-launch guard still holds for it.  MEASURED AND NOT THE DEFAULT (profiles/r06_ab_handoff.txt): on configs[2] the plan makes k_seg_fb
-// 13 us SLOWER (60 us against 47, same box, three alternations), at 1/4 and 1/8 of the size it changes nothing.  Block b runs segment b, as
-// in rounds 3-5; HF_SEG_XCD=1 switches the plan on.
-int create_xcd_plan(CreateWork& cw, int64_t resident, int max_nseg) {
-    Track& tr = cw.ctx->tr;
-    const char* e = std::getenv("HF_SEG_XCD");
-    const bool want = e && e[0] == '1';
-    if (!(want && cw.ctx->pass.seg_fused && resident > 0 && (int64_t) max_nseg * 8 * 2 <= resident && !tr.subs.empty())) return HF_OK;
-    std::vector<int32_t>& tab = tr.h_seg_of_block;
-    tab.clear();
-    for (auto& sb : tr.subs) {
-        std::vector<int32_t> lane[8];
-        for (int c = sb.c0; c < sb.c1; c++) {
-            const int s0 = tr.h_cseg0[(size_t) c], s1 = tr.h_cseg0[(size_t) c + 1];
-            if (s1 <= s0) continue;
-            int best = 0;
-            for (int x = 1; x < 8; x++) if (lane[x].size() < lane[best].size()) best = x;
-            for (int k = s0; k < s1; k++) lane[best].push_back(k);
-        }
-        size_t rows = 0;
-        for (int x = 0; x < 8; x++) rows = std::max(rows, lane[x].size());
-        sb.b0 = (int) tab.size();
-        tab.resize(tab.size() + rows * 8, -1);
-        for (int x = 0; x < 8; x++)
-            for (size_t r = 0; r < lane[x].size(); r++) tab[(size_t) sb.b0 + r * 8 + (size_t) x] = lane[x][r];
-        sb.b1 = (int) tab.size();
-    }
-    return dev_upload(tr.slab, cw.stg, &tr.d_seg_of_block, tab.data(), tab.size());
-}
-
+// Block b of the segment kernel runs segment b.  (Round 6 dealt the chunks of a sub-pass to eight lists and ran list x's r-th segment as
+// block 8 r + x, all segments of a chunk on one XCD as observed: 13 us SLOWER on configs[2], 60 us against 47, nothing at 1/4 and 1/8 of the
+// size — profiles/r06_ab_handoff.txt.)
 // (and the settings of the context's pass, before pass_create)
 int create_launch_config(CreateWork& cw) {
     Track& tr = cw.ctx->tr; Pass& ps = cw.ctx->pass;
@@ -829,7 +796,6 @@ int create_launch_config(CreateWork& cw) {
         int64_t resident = (int64_t) per_cu * cus;
         if (const char* e = std::getenv("HF_SEG_RESIDENT")) resident = std::atoll(e);   // tests: pretend a smaller device
         if (resident > 0 && max_nseg > resident) ps.seg_fused = false;
-        CTRY(create_xcd_plan(cw, resident, max_nseg));
         // Cached row blocks (hf_seg.h, round 5): the LDS that a device with FEWER segments than it could hold leaves idle goes to the
         // workgroups — the largest nc at which every segment is still resident at once.  Decided from the occupancy the runtime reports for
         // that much dynamic LDS; HF_SEG_CACHED_STEPS forces a value (tests, A/B runs).
@@ -864,10 +830,9 @@ int create_launch_config(CreateWork& cw) {
         }
         tr.seg_nc = nc;
         if (cw.ctrace || ps.host_trace)
-            std::fprintf(stderr, "[hf_create] segment kernel: %d segments, longest chunk %d; %lld workgroups resident (%d per CU x %d CUs): %s; %d of %d row blocks cached in LDS (%zu B per workgroup)%s\n",
+            std::fprintf(stderr, "[hf_create] segment kernel: %d segments, longest chunk %d; %lld workgroups resident (%d per CU x %d CUs): %s; %d of %d row blocks cached in LDS (%zu B per workgroup)\n",
                          tr.nseg, max_nseg, (long long) resident, per_cu, cus,
-                         ps.seg_fused ? "one launch" : "TWO launches (a chunk has more segments than the device holds workgroups)", nc, HF_SEG_LMAX, seg_lds_bytes(nc),
-                         tr.d_seg_of_block ? "; XCD plan" : "");
+                         ps.seg_fused ? "one launch" : "TWO launches (a chunk has more segments than the device holds workgroups)", nc, HF_SEG_LMAX, seg_lds_bytes(nc));
     }
     {   // the job list of the per-pass tables (hf_scan.h), built once: the (key, class) list of the rows of A when the segment kernels run,
         // the emission keys otherwise (HF_ALGO_SEQ); then the slow windows

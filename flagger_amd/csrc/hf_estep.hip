@@ -127,7 +127,7 @@ struct PinCache {
         }
         // Portable AND coherent: with a non-zero flag word and no Coherent / Mapped bit the runtime lets HIP_HOST_COHERENT decide, and
         // its default is non-coherent — the kernels' zero-copy writes into the result block (totals, partial vectors, labels) would then be visible
-        // at the end of the kernel only, and the HF_POLL stamp never while it runs.  Plain flags as the fall-back, pageable memory as the last one
+        // at the end of the kernel only.  Plain flags as the fall-back, pageable memory as the last one
         // (a context whose result block is not device-addressable completes its passes through a copy: create_device_store).
         if (hipHostMalloc((void**) &s.p, s.cap, hipHostMallocPortable | hipHostMallocCoherent) == hipSuccess) s.pinned = true;
         else if ((void) hipGetLastError(), hipHostMalloc((void**) &s.p, s.cap, hipHostMallocDefault) == hipSuccess) s.pinned = true;
@@ -312,19 +312,16 @@ struct Track {
     std::vector<SegDesc> h_segs;                // the segment descriptors (the getters derive a window's slot from them)
     std::vector<int32_t> h_cseg0;               // first segment of every chunk (+ the end)
     int seg_nc = 0;                    // row blocks a segment workgroup keeps in LDS across its three walks (hf_seg.h: chosen so that all segments stay resident)
-    // XCD plan (round 6): block b of k_seg_fb runs segment seg_of_block[b]; the segments of a chunk sit on block indices congruent mod 8
-    // (observed: block b runs on XCD b % 8 — for speed only, the hand-off protocol is system-scope whatever the placement).  Null: identity.
-    int32_t* d_seg_of_block = nullptr; std::vector<int32_t> h_seg_of_block;
     // SUB-PASSES (round 5): a context whose records would not fit the Infinity Cache (256 MB; BASELINE configs[2] writes 130 MB) cuts its
     // chunk list into sub-passes of whole chunks; a pass runs k_seg_fb then k_pair_sums per sub-pass through ONE buffer that holds a
     // sub-pass's positions [p0, p1) at a time (Pass::d_recs; the plan's groups are numbered sub-pass by sub-pass, so a sub-pass's records are
     // contiguous) — the records never travel to HBM and back.  Everything that needs the records of ALL windows at once (the getters,
     // per-chunk statistics) runs the segment kernel into Pass::d_recs_all instead (allocated on first use; = d_recs with one sub-pass).
-    struct SubPass { int c0, c1, seg0, seg1, g0, g1; int64_t p0, p1; int b0 = 0, b1 = 0; };   // b0, b1: its blocks in the XCD plan (d_seg_of_block)
+    struct SubPass { int c0, c1, seg0, seg1, g0, g1; int64_t p0, p1; };
     std::vector<SubPass> subs;
     // statistics by emission row (hf_rows.h): the static plan
     bool rows_ready = false;
-    int n_groups = 0, n_rowwaves = 0, n_parts = 1;   // n_parts: regions that have a row, + 1 (the log-likelihood blocks): hf_rows.h hand-offs
+    int n_groups = 0, n_rowwaves = 0;
     int rs_bpw = 1;                   // batches of 16 row slots per wavefront of k_row_stats
     bool plan_compact = false;        // the groups' records back to back (sparse rows) instead of 64 positions per group
     int32_t* d_grp_off = nullptr;     // compact plan: first position of every group (+ the end)
@@ -356,8 +353,7 @@ struct Pass {
     double* d_chunk_stats_own = nullptr;
     double* d_total = nullptr;     // [V]
     unsigned* d_flags = nullptr;
-    unsigned* d_done = nullptr;    // k_reduce / k_row_stats: blocks finished (the last one sums the parts and stamps the host block)
-    unsigned long long* d_cks = nullptr;   // k_reduce: XOR of the words written (checksum of a polled pass)
+    unsigned* d_done = nullptr;    // k_row_stats: blocks finished per part (the last one sums the part: hf_rows.h)
     DevParams* d_params = nullptr;
     double* d_lutE = nullptr; double* d_lutC = nullptr; double* d_Es = nullptr; double* d_Cs = nullptr;   // emission rows: keys, then slow windows
     double* d_lutA = nullptr;      // rows of A, then the identity row (pass_create writes it; no kernel does)
@@ -383,7 +379,7 @@ struct Pass {
     double* h_part = nullptr; double* d_part_host = nullptr; size_t part_cap = 0;   // pinned partials [n_rw_blocks][NA] | [C] | flag word, their device address
     int8_t* h_label = nullptr;     // pinned [N]: staging of hf_get_labels, taken from the process's pinned cache on first use (1.5 MB of pinning = 0.15 ms of hf_create until round 5)
     int8_t* d_label_host = nullptr; // its device address (a kernel writes the labels there)
-    // the pinned block: result vector (+ flag word, stamp, checksums) | flag word of hf_check | parameter block
+    // the pinned block: result vector (+ flag word) | flag word of hf_check | parameter block
     double* h_total = nullptr;     // pinned [V+1]: reduced vector + flag word, one copy per pass
     double* d_total_host = nullptr; // device address of the pinned h_total: k_reduce writes the result straight to the host
     unsigned* h_flags = nullptr; DevParams* h_params = nullptr;
@@ -404,9 +400,6 @@ struct Pass {
     bool pass_rows = false; int pass_kc = 0, pass_wpb = 4;
     bool pass_nb = false;          // the last rows-mode pass ran the negative_binomial kernels (hf_nb_rows.h)
     bool pass_host_total = false; int pass_rw_blocks = 0;
-    bool pass_polled = false;      // the last rows-mode pass carried a stamp (decided at launch: k_row_stats writes the total itself)
-    int poll_kind = 0;             // what the last polled kernel was: 1 k_row_stats' total (a checksum per region), 2 k_reduce (one)
-    double poll_seq = 0.0;         // completion stamp of the last polled pass (hf_finish)
     uint32_t stream_stamp = 0;
     double* d_rank_out = nullptr; double* d_rank_flag = nullptr;   // hf_bind_rank_total: where a rows-mode pass writes its total / flag word
     bool pass_bound = false;       // the last pass wrote them there
@@ -682,22 +675,6 @@ static bool seg_pass(const Track& tr) { return tr.algo == HF_ALGO_SCAN && tr.nse
 // does a full pass of the Gaussian models take the statistics-by-row path?
 static bool rows_pass(const Pass& ps) { return ps.stats_mode == HF_STATS_ROWS && ps.tr->rows_ready && ps.tr->algo == HF_ALGO_SCAN; }
 
-// polled completion of a pass: see wait_total
-static int poll_mode() {
-    static const int mode = [] {
-        const char* e = std::getenv("HF_POLL");
-        if (!e) return 0;
-        if (!std::strcmp(e, "debug")) return 2;
-        return e[0] == '1' ? 1 : 0;
-    }();
-    return mode;
-}
-static bool poll_ok(const Pass& ps, int last_kernel) {
-    return poll_mode() != 0 && ps.d_total_host && !((ps.prof_mask >> last_kernel) & 1u) && !(ps.prof_mask & HF_PROF_PASS) &&
-           !ps.host_trace;
-}
-static double next_stamp(Pass& ps) { ps.poll_seq += 1.0; ps.h_total[ps.tr->V + 1] = 0.0; return ps.poll_seq; }
-
 // the groups' sums of f (x) b, times their row of A: padded plan (whole groups streamed) or compact plan (hf_create)
 // the groups of ONE sub-pass (Track::SubPass): padded plan — whole groups streamed from the sub-pass's first position on; compact plan — the
 // groups' own (global) positions.  recs_eff: the address position 0 would have (a pass buffer that holds one sub-pass starts p0 records later)
@@ -719,17 +696,12 @@ static void launch_pair_sums(Pass& ps, hipStream_t st, const Track::SubPass& sb,
 // sub >= 0: the segments of that sub-pass; < 0: all segments
 static void launch_seg_fb(Pass& ps, hipStream_t st, bool full, double* recs_eff, int sub, unsigned epoch, unsigned wait_epoch, bool timed, bool with_scales = true) {
     const Track& tr = *ps.tr;
-    int g0 = sub >= 0 ? tr.subs[(size_t) sub].seg0 : 0, n = sub >= 0 ? tr.subs[(size_t) sub].seg1 - g0 : tr.nseg;
-    const int32_t* const sob = ps.seg_fused ? tr.d_seg_of_block : nullptr;   // (the XCD plan: one-launch mode only — two launches have no hand-off inside the launch)
-    if (sob) {       // blocks of the plan instead of segments (a sub-pass's blocks are contiguous, and so are all of them)
-        g0 = sub >= 0 ? tr.subs[(size_t) sub].b0 : 0;
-        n = (sub >= 0 ? tr.subs[(size_t) sub].b1 : tr.subs.back().b1) - g0;
-    }
+    const int g0 = sub >= 0 ? tr.subs[(size_t) sub].seg0 : 0, n = sub >= 0 ? tr.subs[(size_t) sub].seg1 - g0 : tr.nseg;
     if (n <= 0) return;
     const int nc = ps.seg_fused ? tr.seg_nc : 0;     // cached row blocks: one-launch mode only (the lane products are computed in the same kernel)
     const size_t lds = seg_lds_bytes(nc);
 #define HF_SEG_FB_ARGS tr.d_seg, tr.d_arow, ps.d_lutA, ps.d_params, ps.d_segQ, ps.d_Pseg, ps.d_seg_ready, epoch, wait_epoch, tr.d_pos, recs_eff, \
-                        with_scales ? ps.d_scale_s : (double*) nullptr, ps.d_label, ps.d_seg_ll, ps.d_flags, (int32_t) g0, nc, sob
+                        with_scales ? ps.d_scale_s : (double*) nullptr, ps.d_label, ps.d_seg_ll, ps.d_flags, (int32_t) g0, nc
 #define HF_SEG_FB_LAUNCH(B, F, CA) do { \
         if (timed) hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_fb<B, F, CA>), dim3((unsigned) n), dim3(64), (uint32_t) lds, st, \
                                          ps.kev[2 * HF_K_SEG_FB], ps.kev[2 * HF_K_SEG_FB + 1], 0, HF_SEG_FB_ARGS); \
@@ -769,11 +741,9 @@ static void launch_stats(Pass& ps, hipStream_t st, int full, int ncol) {
         const int n_rw_blocks = (tr.n_rowwaves + wpb - 1) / wpb, n_ll_blocks = (tr.C + wpb - 1) / wpb;
         // the launch's last block also sums the partials (rows_total): into d_total and straight into the pinned host block
         const bool bound = ps.d_rank_out != nullptr;    // multi-GPU `ranks` exchange: the total goes into the exchange buffer, not to the host
-        const bool polled = !bound && poll_ok(ps, HF_K_ROW_STATS);
-        const double seq = polled ? next_stamp(ps) : 0.0;
-        ps.pass_polled = polled; ps.pass_bound = bound;
-        // one GPU, nobody polling, nothing bound: the blocks' partial vectors go to pinned host memory and the HOST sums them (host_rows_total)
-        bool host_total = !bound && !polled && ps.host_total_ok && ps.d_total_host != nullptr;
+        ps.pass_bound = bound;
+        // one GPU, nothing bound: the blocks' partial vectors go to pinned host memory and the HOST sums them (host_rows_total)
+        bool host_total = !bound && ps.host_total_ok && ps.d_total_host != nullptr;
         if (host_total) {
             const size_t need = (size_t) n_rw_blocks * NA + (size_t) tr.C + 1;
             if (need > ps.part_cap) {
@@ -790,7 +760,7 @@ static void launch_stats(Pass& ps, hipStream_t st, int full, int ncol) {
                            tr.n_rowwaves, n_rw_blocks, tr.d_rw_region, tr.d_rowslots, ps.d_grp_sums, row_src(ps), ps.d_params,
                            ps.d_rw_stats, tr.C, ll_off(ps), ll_part(ps), ps.d_chunk_stats, tr.V, ps.d_chunk_ll,
                            tr.d_rw_off, tr.K, bound ? ps.d_rank_out : ps.d_total, bound ? (double*) nullptr : ps.d_total_host,
-                           bound ? ps.d_rank_flag : (double*) nullptr, ps.d_flags, seq, ps.d_done, tr.n_parts, tr.rs_bpw,
+                           bound ? ps.d_rank_flag : (double*) nullptr, ps.d_flags, ps.d_done, tr.rs_bpw,
                            host_total ? ps.d_part_host : (double*) nullptr);
         ps.pass_wpb = wpb;
         ps.pass_rows = true;
@@ -813,14 +783,14 @@ static void launch_stats(Pass& ps, hipStream_t st, int full, int ncol) {
 
 // the last kernel of a negative_binomial pass in HF_STATS_ROWS mode: total vector (+ flag word) into `out`
 // (the Gaussian models' total is written by the last block of k_row_stats itself: hf_rows.h rows_total)
-static int launch_nb_total(Pass& ps, hipStream_t st, double* out, bool with_flags = true, double seq = 0.0) {
+static int launch_nb_total(Pass& ps, hipStream_t st, double* out, bool with_flags = true) {
     const Track& tr = *ps.tr;
     KTimer t(ps, st, HF_K_ROWS_TOTAL);
     NbTables nt;
     nt.E = ps.d_nbE; nt.P = ps.d_nbP; nt.dig = ps.d_nbDig; nt.r = ps.d_nbR; nt.beta = ps.d_nbBeta;
     hipLaunchKernelGGL(k_nb_total, dim3((unsigned) tr.R), dim3(1024), 0, st, tr.d_rw_off, ps.pass_wpb, ps.d_rw_stats, ps.d_H,
                        ps.d_params, nt, ps.d_chunk_ll, (int64_t) tr.C, tr.V, tr.K, out,
-                       with_flags ? ps.d_flags : (const unsigned*) nullptr, seq, ps.d_done);
+                       with_flags ? ps.d_flags : (const unsigned*) nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -847,12 +817,12 @@ __global__ void k_gather_fb(int64_t first, int64_t n, const int32_t* __restrict_
 // Every per-pass device array of a track in bytes (0: the track has no use for it), and the pinned block: the ONE place that sizes a pass
 // (pass_create allocates it, hf_batch_capacity counts it)
 struct PassLayout {
-    size_t label, chunk_stats, total, flags, done, cks, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg, recs,
+    size_t label, chunk_stats, total, flags, done, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg, recs,
            grp_sums, chunk_ll, rw_stats, E, f, b, scale;
-    size_t pin_total, pin_block;   // pinned: result vector (+ flag word, stamp, checksums) | flag word of hf_check | parameter block
+    size_t pin_total, pin_block;   // pinned: result vector (+ flag word) | flag word of hf_check | parameter block
     size_t device_bytes() const {
         size_t s = 0;
-        for (size_t x : {label, chunk_stats, total, flags, done, cks, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg,
+        for (size_t x : {label, chunk_stats, total, flags, done, params, lutE, lutC, lutA, tile_ll, tile_stats, seg_ready, seg_ll, Pseg,
                          recs, grp_sums, chunk_ll, rw_stats, E, f, b, scale})
             if (x) s += Slab::granule(x);
         return s;
@@ -863,7 +833,7 @@ static PassLayout pass_layout(const Track& tr) {
     const size_t N = (size_t) tr.N, C = (size_t) tr.C, V = (size_t) tr.V, nt = (size_t) tr.ntiles, ns = (size_t) tr.nseg;
     const size_t rows = (size_t) tr.n_lut + (size_t) tr.n_slow + 1;   // emission rows: the keys, the slow windows, one row of padding
     auto some = [](size_t bytes) { return bytes ? bytes : 1; };      // (allocated even when empty)
-    L.label = N + 16; L.chunk_stats = some(C * V * 8); L.total = (V + 1) * 8; L.flags = 4; L.done = HF_DONE_BYTES; L.cks = 8;
+    L.label = N + 16; L.chunk_stats = some(C * V * 8); L.total = (V + 1) * 8; L.flags = 4; L.done = HF_DONE_BYTES;
     L.params = tr.params_bytes; L.lutE = rows * 16 * 8; L.lutC = rows * 4 * (size_t) tr.K * 8;
     L.lutA = tr.d_arow ? ((size_t) tr.n_arows + 1) * 16 * 8 : 0;    // (+ the identity row)
     L.tile_ll = some(nt * 8); L.tile_stats = some(nt * (size_t) tr.R * stat_acc_len(16) * 8);
@@ -878,7 +848,7 @@ static PassLayout pass_layout(const Track& tr) {
     if (tr.algo == HF_ALGO_SEQ) {         // the sequential cross-check: emission rows, window-order scales, f and b by tile (hf_device.h fb_slot)
         L.E = some(N * 16 * 8); L.scale = some(N * 8); L.f = L.b = some(nt * 64 * HF_SCAN_L * 4 * 8);
     }
-    L.pin_total = ((V + 2 + HF_MAXREGIONS) * 8 + 63) / 64 * 64;   // (what follows stays 64-byte aligned)
+    L.pin_total = ((V + 1) * 8 + 63) / 64 * 64;   // (what follows stays 64-byte aligned)
     L.pin_block = L.pin_total + 64 + (tr.params_bytes + 63) / 64 * 64;
     return L;
 }
@@ -903,7 +873,7 @@ static int pass_create(const Track& tr, const Pass& settings, Pass* out, UploadS
         if (bytes && ok) { p = static_cast<std::remove_reference_t<decltype(p)>>(ps.slab.alloc(bytes)); ok = p != nullptr; }
     };
     take(ps.d_label, L.label); take(ps.d_chunk_stats_own, L.chunk_stats); take(ps.d_total, L.total); take(ps.d_flags, L.flags);
-    take(ps.d_done, L.done); take(ps.d_cks, L.cks); take(ps.d_params, L.params); take(ps.d_lutE, L.lutE); take(ps.d_lutC, L.lutC);
+    take(ps.d_done, L.done); take(ps.d_params, L.params); take(ps.d_lutE, L.lutE); take(ps.d_lutC, L.lutC);
     take(ps.d_lutA, L.lutA); take(ps.d_tile_ll, L.tile_ll); take(ps.d_tile_stats, L.tile_stats); take(ps.d_seg_ready, L.seg_ready);
     take(ps.d_seg_ll, L.seg_ll); take(ps.d_Pseg, L.Pseg); take(ps.d_recs, L.recs); take(ps.d_grp_sums, L.grp_sums);
     take(ps.d_chunk_ll, L.chunk_ll); take(ps.d_rw_stats, L.rw_stats);
@@ -931,8 +901,7 @@ static int pass_create(const Track& tr, const Pass& settings, Pass* out, UploadS
     }
     HIPCHK(hipEventCreate(&ps.ev0)); HIPCHK(hipEventCreate(&ps.ev1));
     HIPCHK(hipMemsetAsync(ps.d_flags, 0, 4, nullptr));
-    HIPCHK(hipMemsetAsync(ps.d_done, 0, HF_DONE_BYTES, nullptr));   // tickets and scratch of the in-launch hand-offs (hf_rows.h)
-    HIPCHK(hipMemsetAsync(ps.d_cks, 0, 8, nullptr));
+    HIPCHK(hipMemsetAsync(ps.d_done, 0, HF_DONE_BYTES, nullptr));   // tickets of the in-launch hand-offs (hf_rows.h)
     HIPCHK(hipMemsetAsync(ps.d_params, 0, tr.params_bytes, nullptr));   // (the kernel-argument path writes the bytes in use only)
     HIPCHK(hipMemsetAsync(ps.d_label, 0xff, tr.N ? (size_t) tr.N : 1, nullptr));
     if (ps.d_seg_ready) HIPCHK(hipMemsetAsync(ps.d_seg_ready, 0, L.seg_ready, nullptr));
@@ -1403,14 +1372,6 @@ int64_t hf_sub_pass_windows(const hf_ctx* ctx, int k) {
     return ctx->tr.h_off[(size_t) ctx->tr.subs[(size_t) k].c1] - ctx->tr.h_off[(size_t) ctx->tr.subs[(size_t) k].c0];
 }
 int hf_seg_cached_steps(const hf_ctx* ctx) { return !ctx || !seg_pass(ctx->tr) || !ctx->pass.seg_fused ? 0 : ctx->tr.seg_nc; }
-int hf_seg_xcd_plan(const hf_ctx* ctx) { return ctx && seg_pass(ctx->tr) && ctx->pass.seg_fused && ctx->tr.d_seg_of_block ? 1 : 0; }
-int64_t hf_seg_block_table(const hf_ctx* ctx, int32_t* seg_of_block, int64_t n) {
-    if (!ctx) return 0;
-    const Track& tr = ctx->tr;
-    const int64_t have = (int64_t) tr.h_seg_of_block.size();
-    if (seg_of_block) for (int64_t i = 0; i < n && i < have; i++) seg_of_block[i] = tr.h_seg_of_block[(size_t) i];
-    return have;
-}
 int hf_create_phases(const hf_ctx* ctx, int max, double* ms, const char** names) {
     if (!ctx) return 0;
     const Track& tr = ctx->tr;
@@ -1440,7 +1401,7 @@ int hf_rank_total(hf_ctx* ctx, double* out_dev, void* stream) {
         const int wpb = ps.pass_wpb;
         const dim3 grid((unsigned) (tr.R + 1)), blk((unsigned) (64 * wpb));
 #define HF_LATE(KT) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rows_total_late<KT>), grid, blk, 0, (hipStream_t) stream, tr.d_rw_off, wpb, ps.d_rw_stats, ps.d_params, \
-                                       tr.K, ps.d_chunk_ll, (int64_t) tr.C, out_dev, done_scratch(ps.d_done))
+                                       tr.K, ps.d_chunk_ll, (int64_t) tr.C, out_dev)
         if (ps.pass_kc <= 4) HF_LATE(4); else if (ps.pass_kc <= 8) HF_LATE(8); else HF_LATE(16);
 #undef HF_LATE
         HIPCHK(hipGetLastError());
@@ -1455,8 +1416,8 @@ int hf_rank_total(hf_ctx* ctx, double* out_dev, void* stream) {
 }
 
 struct ExchangeGeom { int n_ranks = 0, rows_per_rank = 0, flag_row = 0; };   // n_ranks == 0: no flag rows to merge
-static int reduce_chunks_seq(Pass& ps, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
-                             double* out_dev, void* stream, double seq, ExchangeGeom xg = ExchangeGeom()) {
+static int reduce_chunks(Pass& ps, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
+                         double* out_dev, void* stream, ExchangeGeom xg = ExchangeGeom()) {
     const Track& tr = *ps.tr;
     if (!chunk_stats_dev || !out_dev || n_chunks < 0) return set_err(HF_E_ARG, "hf_reduce_chunks: bad argument");
     HIPCHK(hipSetDevice(tr.device));
@@ -1468,7 +1429,7 @@ static int reduce_chunks_seq(Pass& ps, const double* chunk_stats_dev, const int3
         hipLaunchKernelGGL(k_reduce, dim3((unsigned) (tr.V + 1)), dim3(64), 0, (hipStream_t) stream, chunk_stats_dev, row_index_dev,
                            n_chunks, tr.V, out_dev,
                            (out_dev == ps.d_total || out_dev == ps.d_total_host) ? ps.d_flags : (const unsigned*) nullptr,
-                           xg.n_ranks, xg.rows_per_rank, xg.flag_row, seq, ps.d_done, ps.d_cks);
+                           xg.n_ranks, xg.rows_per_rank, xg.flag_row);
     }
     ps.prof_mask = keep;
     HIPCHK(hipGetLastError());
@@ -1477,7 +1438,7 @@ static int reduce_chunks_seq(Pass& ps, const double* chunk_stats_dev, const int3
 int hf_reduce_chunks_indexed(hf_ctx* ctx, const double* chunk_stats_dev, const int32_t* row_index_dev, int64_t n_chunks,
                              double* out_dev, void* stream) {
     if (!ctx) return set_err(HF_E_ARG, "hf_reduce_chunks: bad argument");
-    return reduce_chunks_seq(ctx->pass, chunk_stats_dev, row_index_dev, n_chunks, out_dev, stream, 0.0);
+    return reduce_chunks(ctx->pass, chunk_stats_dev, row_index_dev, n_chunks, out_dev, stream);
 }
 
 int hf_reduce_chunks(hf_ctx* ctx, const double* chunk_stats_dev, int64_t n_chunks, double* out_dev, void* stream) {
@@ -1532,41 +1493,6 @@ int hf_check(hf_ctx* ctx, void* stream) {
     return pass_flags_to_code(ps, *ps.h_flags);
 }
 
-// Completion of a pass.  Default: hipStreamSynchronize on the launch stream — the HIP-defined way to see the statistics
-// block that the last kernel wrote into pinned host memory.
-// Opt-in (environment HF_POLL=1): the last kernel also writes a completion stamp behind a system-scope fence and the host
-// spins on it instead of waiting for the stream's completion signal (3-12 us less per EM step, depending on the box).  The
-// order in which device writes to host memory become visible is NOT defined by the HIP memory model: round 1 measured a
-// stale element in one of ~2 000 passes with the stamp alone, so a polled block is only accepted when a position-weighted
-// checksum of what the host READ matches the one the kernel wrote (polled_block_consistent; none in 800 000 passes,
-// profiles/tools/poll_soak.py), and the memory must be coherent host memory (HIP_HOST_COHERENT=0 falls back to the
-// stream after the 2 s bail-out).  HF_POLL=debug additionally synchronises after acceptance and reports any word
-// that still changed.  It stays off by default: no EM step should depend on a probabilistic check.
-// The stamp alone is not enough: the device's writes to host memory may become visible out of order (a soak test saw a
-// stale element once in ~2 000 passes).  So the kernel also writes a checksum of everything it wrote (hf_cks_term: bit
-// pattern x position weight, summed mod 2^64) plus the pass's stamp value; the host accepts the block only when what it
-// READ has that checksum — stale data, a stale checksum or both fail the comparison and the host keeps polling.  (A plain
-// XOR was not enough either: the estimator layout repeats values, and two equal stale words cancel — seen once in 300 000.)
-static bool polled_block_consistent(const Pass& ps) {
-    const Track& tr = *ps.tr;
-    const double* h = ps.h_total;
-    const int64_t V = tr.V;
-    auto bits = [](double d) { unsigned long long u; std::memcpy(&u, &d, 8); return u; };
-    const unsigned long long s = bits(ps.poll_seq);
-    if (ps.poll_kind == 2) {
-        unsigned long long x = s;
-        for (int64_t v = 0; v <= V; v++) x += hf_cks_term(bits(h[v]), v);
-        return x == bits(h[V + 2]);
-    }
-    const int64_t rstride = 24 * (int64_t) tr.K + 16;
-    for (int r = 0; r < tr.R; r++) {
-        unsigned long long x = s;
-        for (int64_t v = 0; v < rstride; v++) { const int64_t at = 1 + r * rstride + v; x += hf_cks_term(bits(h[at]), at); }
-        if (r == 0) x += hf_cks_term(bits(h[0]), 0) + hf_cks_term(bits(h[V]), V);
-        if (x != bits(h[V + 2 + r])) return false;
-    }
-    return true;
-}
 // The total of a pass whose blocks wrote their partial vectors to the host (hf_rows.h part_host): rows_total_region and rows_total_ll restated —
 // the same additions in the same order (nq interleaved accumulators per element over the region's blocks, then their sum; the log-likelihood
 // by 64 strided sums and a halving tree), so h_total holds the bits the launch's own last blocks would have written.
@@ -1633,26 +1559,16 @@ static void host_rows_total(Pass& ps) {
     if (ps.pass_kc <= 4) host_rows_total_t<4>(ps); else if (ps.pass_kc <= 8) host_rows_total_t<8>(ps); else host_rows_total_t<16>(ps);
 }
 
-static int wait_total(Pass& ps, hipStream_t st, bool polled, double* stats_host, bool host_total = false) {
+// Completion of a pass: the stream's own stamp, or hipStreamSynchronize on the launch stream when the stamp is off or does not arrive —
+// the HIP-defined ways to see the statistics block that the last kernel wrote into pinned host memory.
+static int wait_total(Pass& ps, hipStream_t st, double* stats_host, bool host_total = false) {
     const Track& tr = *ps.tr;
     bool seen = false;
-    if (polled) {
-        volatile double* stamp = ps.h_total + tr.V + 1;
-        const auto t0 = std::chrono::steady_clock::now();
-        long spins = 0;
-        for (;;) {
-            if (*stamp == ps.poll_seq) {
-                std::atomic_thread_fence(std::memory_order_acquire);
-                if (polled_block_consistent(ps)) { seen = true; break; }
-            }
-            __builtin_ia32_pause();
-            if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;   // let the stream report
-        }
-    }
-    if (!seen && ps.stream_stamp_ok) {
+    if (ps.stream_stamp_ok) {
         // Completion through the stream itself: a 32-bit value that the command processor writes into the pinned block AFTER
-        // everything enqueued before it has completed (hipStreamWriteValue32: a stream-ordered memory operation, so — unlike a
-        // stamp written by the kernel, HF_POLL — its order against the kernel's own writes is defined), polled by the host.
+        // everything enqueued before it has completed (hipStreamWriteValue32: a stream-ordered memory operation, so its order
+        // against the kernel's own writes is defined — a stamp written by the last kernel itself has none: rounds 1-5 carried one behind
+        // a checksum, and saw a stale element in one of ~2 000 passes without it), polled by the host.
         // Measured 4-5 us less per EM step than hipStreamSynchronize.  Bail-out: the stream after 2 s.
         volatile uint32_t* word = reinterpret_cast<volatile uint32_t*>(ps.h_flags) + 1;
         const uint32_t want = ++ps.stream_stamp;
@@ -1684,14 +1600,6 @@ static int wait_total(Pass& ps, hipStream_t st, bool polled, double* stats_host,
             std::fprintf(stderr, "[hmm_flagger_hip] the stream's completion stamp did not arrive; passes complete through hipStreamSynchronize from now on\n");
         }
     }
-    if (seen && poll_mode() == 2) {   // HF_POLL=debug: did anything still arrive after the block was accepted?
-        std::vector<double> snap(ps.h_total, ps.h_total + tr.V + 1);
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t v = 0; v <= tr.V; v++)
-            if (std::memcmp(&snap[(size_t) v], &ps.h_total[v], 8) != 0)
-                std::fprintf(stderr, "[poll debug] seq %.0f kind %d element %ld changed after acceptance: %.17g -> %.17g\n", ps.poll_seq,
-                             ps.poll_kind, (long) v, snap[(size_t) v], ps.h_total[v]);
-    }
     accumulate_kernel_times(ps);   // events of the kernels before the last one have completed
     if (host_total) host_rows_total(ps);
     std::memcpy(stats_host, ps.h_total, (size_t) tr.V * 8);
@@ -1706,13 +1614,10 @@ static int pass_finish(Pass& ps, double* stats_host, void* stream) {
     HIPCHK(hipSetDevice(tr.device));
     // the reduction writes the V+1 doubles into pinned host memory over PCIe: no device-to-host copy afterwards
     double* out = ps.d_total_host ? ps.d_total_host : ps.d_total;
-    const bool own_total = ps.pass_rows && !ps.pass_nb;   // k_row_stats already wrote the total (and the stamp, when polled)
-    const bool polled = own_total ? ps.pass_polled : poll_ok(ps, ps.pass_rows ? HF_K_ROWS_TOTAL : HF_K_REDUCE);
-    const double seq = own_total ? 0.0 : (polled ? next_stamp(ps) : 0.0);
-    ps.poll_kind = ps.pass_rows ? 1 : 2;
+    const bool own_total = ps.pass_rows && !ps.pass_nb;   // k_row_stats already wrote the total
     int rc = own_total ? HF_OK
-                       : (ps.pass_rows ? launch_nb_total(ps, st, out, true, seq)
-                                         : reduce_chunks_seq(ps, ps.d_chunk_stats, nullptr, tr.C, out, stream, seq));
+                       : (ps.pass_rows ? launch_nb_total(ps, st, out)
+                                         : reduce_chunks(ps, ps.d_chunk_stats, nullptr, tr.C, out, stream));
     if (rc) return rc;
     if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
     if (own_total && ps.pass_bound) {   // the pass wrote its total into a bound exchange slot (hf_bind_rank_total): fetch it from there
@@ -1720,7 +1625,7 @@ static int pass_finish(Pass& ps, double* stats_host, void* stream) {
         HIPCHK(hipMemcpyAsync(ps.h_total + tr.V, ps.d_rank_flag, 8, hipMemcpyDeviceToHost, st));
     } else if (!ps.d_total_host)
         HIPCHK(hipMemcpyAsync(ps.h_total, ps.d_total, ((size_t) tr.V + 1) * 8, hipMemcpyDeviceToHost, st));
-    rc = wait_total(ps, st, polled, stats_host, own_total && ps.pass_host_total);
+    rc = wait_total(ps, st, stats_host, own_total && ps.pass_host_total);
     if (rc == HF_E_RETRY) {   // the pass again, in two launches (the packed parameters are still in the pinned block)
         if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev0, st));
         rc = enqueue_pass(ps, &ps.last_p, ps.last_mode, st, true);
@@ -1744,15 +1649,12 @@ static int finish_rows(hf_ctx* ctx, const double* rows_dev, const int32_t* row_i
     hipStream_t st = (hipStream_t) stream;
     HIPCHK(hipSetDevice(tr.device));
     double* out = ps.d_total_host ? ps.d_total_host : ps.d_total;
-    const bool polled = poll_ok(ps, HF_K_REDUCE);
-    const double seq = polled ? next_stamp(ps) : 0.0;
-    ps.poll_kind = 2;
-    int rc = reduce_chunks_seq(ps, rows_dev, row_index_dev, n_rows, out, stream, seq, xg);
+    int rc = reduce_chunks(ps, rows_dev, row_index_dev, n_rows, out, stream, xg);
     if (rc) return rc;
     if (pass_events(ps)) HIPCHK(hipEventRecord(ps.ev1, st));
     if (!ps.d_total_host)
         HIPCHK(hipMemcpyAsync(ps.h_total, ps.d_total, ((size_t) tr.V + 1) * 8, hipMemcpyDeviceToHost, st));
-    return wait_total(ps, st, polled, stats_host);
+    return wait_total(ps, st, stats_host);
 }
 
 int hf_finish_gathered(hf_ctx* ctx, const double* rows_dev, const int32_t* row_index_dev, int64_t n_chunks, double* stats_host,

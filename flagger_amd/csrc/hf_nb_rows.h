@@ -9,7 +9,7 @@
 //                    slot's contribution to the count data of its (region, x): the sum over previous states, per state
 //   k_nb_hist        one wavefront per (region, bin): the slots of the bin in plan order (a static list of hf_create)
 //   k_nb_total       one block per region: transition counts, the estimator increments of every (state, component) from
-//                    the region's count data, the log-likelihood; published like the total of k_row_stats (checksum + stamp)
+//                    the region's count data, the log-likelihood
 #pragma once
 #include "hf_rows.h"
 #include "hf_nb.h"
@@ -127,26 +127,23 @@ __global__ void __launch_bounds__(256) k_nb_hist(int n_bins, const int32_t* __re
 // estimator vector as k_chunk_stats_nb builds a chunk's: transition counts, then for every (state, component) the
 // theta / lambda / weight increments over the coverage values (hmm_utils.c:537-566; one wavefront per (state, component), lanes over x),
 // the weight denominators shared by the
-// components of a state (hmm_utils.c:66-74).  Published with the checksum and the stamp of k_row_stats' total (hf_rows.h).
+// components of a state (hmm_utils.c:66-74).
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(1024) k_nb_total(const int32_t* __restrict__ rw_off, int wpb, const double* __restrict__ blk_trans,
                                                   const double* __restrict__ H, const DevParams* __restrict__ P, const NbTables nb,
                                                   const double* __restrict__ chunk_ll, int64_t C, int64_t V, int K,
-                                                  double* __restrict__ out, const unsigned* __restrict__ flags, double seq,
-                                                  unsigned* __restrict__ done) {
+                                                  double* __restrict__ out, const unsigned* __restrict__ flags) {
     const int tid = threadIdx.x;
     __shared__ double counts[4][256];
     __shared__ double tpart[60][16];
     __shared__ double blockv[24 * HF_MAXCOMP + 16];
-    __shared__ double s_ll;
-    __shared__ unsigned long long s_x[16];
     const unsigned fl = (tid == 0 && flags) ? *flags : 0u;
     if (blockIdx.x == 0 && tid >= 960) {   // k_reduce's order over the chunk list
         const int lane = tid - 960;
         double acc = 0.0;
         for (int64_t c = lane; c < C; c += 64) acc += chunk_ll[c];
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-        if (lane == 0) { out[0] = acc; s_ll = acc; }
+        if (lane == 0) out[0] = acc;
     }
     const int nreg = P->n_regions;
     const int rstride = 24 * K + 16;
@@ -211,31 +208,8 @@ __global__ void __launch_bounds__(1024) k_nb_total(const int32_t* __restrict__ r
             for (int c2 = 0; c2 < nc; c2++) blockv[((tid * 3 + 2) * 2 + 1) * K + c2] = den;
         }
         __syncthreads();
-        unsigned long long x = 0ull;           // checksum of what this block writes (hf_cks_term)
-        for (int v = tid; v < rstride; v += 1024) {
-            const double d = blockv[v];
-            const int64_t at = 1 + (int64_t) r * rstride + v;
-            out[at] = d;
-            x += hf_cks_term((unsigned long long) __double_as_longlong(d), at);
-        }
-        if (seq != 0.0) {
-            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-            if ((tid & 63) == 0) s_x[tid >> 6] = x;
-            __syncthreads();
-            if (tid == 0) {
-                unsigned long long c = (unsigned long long) __double_as_longlong(seq);
-                for (int w = 0; w < 16; w++) c += s_x[w];
-                if (r == 0) c += hf_cks_term((unsigned long long) __double_as_longlong(s_ll), 0) +
-                                 hf_cks_term((unsigned long long) __double_as_longlong((double) fl), V);
-                out[V + 2 + r] = __longlong_as_double((long long) c);
-            }
-        }
+        for (int v = tid; v < rstride; v += 1024) out[1 + (int64_t) r * rstride + v] = blockv[v];
         __syncthreads();
     }
     if (tid == 0 && flags && blockIdx.x == 0) out[V] = (double) fl;
-    if (seq != 0.0) {
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0 && atomicAdd(done, 1u) == gridDim.x - 1) { *done = 0u; out[V + 1] = seq; __threadfence_system(); }
-    }
 }

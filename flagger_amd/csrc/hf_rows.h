@@ -135,9 +135,7 @@ __global__ void __launch_bounds__(256) k_pair_sums_compact(int n_groups, const i
 //     interleaved accumulators per element (fixed by the launch geometry), expanded into the estimator layout of
 //     include/hmm_flagger_hip.h exactly as k_chunk_stats does, assembled in LDS and written once — regions in parallel;
 //   * the last of the blocks that sum the chunks' log-likelihoods adds those up in k_reduce's order (the same bits as the
-//     per-chunk path) and zero-fills the blocks of regions without a row (rows_total_ll);
-//   * the last of THOSE parts to finish writes the flag word and, for a host that polls, a per-region checksum word bound
-//     to the pass (out[V+2+r]) and the completion stamp (out[V+1]): see wait_total.
+//     per-chunk path), zero-fills the blocks of regions without a row (rows_total_ll) and writes the flag word.
 // Every hand-off goes through write-through stores, a drained queue and a ticket (xcu_store / xcu_load below).
 // Results go to `out_dev` (V + 1 doubles, the flag word last — or to element 0 of `flag_row`, hf_bind_rank_total) and, when
 // the context has a pinned host block, to `out_host`.  rw_off[r]..rw_off[r+1]: the wavefronts of region r.
@@ -147,12 +145,8 @@ __global__ void __launch_bounds__(256) k_pair_sums_compact(int n_groups, const i
 __device__ __forceinline__ void xcu_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ double xcu_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
-// scratch of the hand-offs (Pass::d_done): tickets, then the parts' checksum sums and the log-likelihood for the finalizer
-#define HF_DONE_REGION0 1                                    // tickets of region r at HF_DONE_REGION0 + r, r = n_regions: the log-likelihood blocks
-#define HF_DONE_PARTS (HF_DONE_REGION0 + HF_MAXREGIONS + 1)  // ticket of the finished parts
-#define HF_DONE_WORDS (HF_DONE_PARTS + 1)                    // unsigned words; then (8-byte aligned) HF_MAXREGIONS + 1 doubles
-__host__ __device__ __forceinline__ double* done_scratch(unsigned* done) { return reinterpret_cast<double*>(done + ((HF_DONE_WORDS + 1) & ~1)); }
-#define HF_DONE_BYTES ((((HF_DONE_WORDS + 1) & ~1) * 4) + (HF_MAXREGIONS + 1) * 8)
+// tickets of the hand-offs (Pass::d_done): region r's at word r, the log-likelihood blocks' at word n_regions
+#define HF_DONE_BYTES ((HF_MAXREGIONS + 1) * 4)
 
 #ifndef HF_RS_WPB
 #define HF_RS_WPB 8    // wavefronts per block of k_row_stats (a multiple of 4: k_row_stats_nb keeps 4): the block that totals a region then reads
@@ -161,18 +155,17 @@ static_assert(HF_RS_WPB % 4 == 0 && HF_RS_WPB <= 16, "regions are padded to whol
 #ifndef HF_ROWS_TOTAL_INFLIGHT
 #define HF_ROWS_TOTAL_INFLIGHT 32   // loads a thread of the totalling block keeps in flight (a wavefront counts at most 63 outstanding)
 #endif
-// one region; returns (thread 0) the checksum sum of what was written
+// one region
 template <int KT>
-__device__ unsigned long long rows_total_region(int r, const int32_t* __restrict__ rw_off, int wpb, const double* __restrict__ blk_stats,
-                                                const DevParams* __restrict__ P, int Kctx, double* __restrict__ out_dev,
-                                                double* __restrict__ out_host) {
+__device__ void rows_total_region(int r, const int32_t* __restrict__ rw_off, int wpb, const double* __restrict__ blk_stats,
+                                  const DevParams* __restrict__ P, int Kctx, double* __restrict__ out_dev,
+                                  double* __restrict__ out_host) {
     constexpr int NA = 16 + 9 + 2 + 3 * KT + 1;
     constexpr int NQMAX = 16;
     const int tid = threadIdx.x, nt = blockDim.x;
     __shared__ double part[NQMAX][NA];
     __shared__ double red[NA];
     __shared__ double blockv[24 * HF_MAXCOMP + 16];   // the region's block of the vector, assembled in LDS
-    __shared__ unsigned long long s_x[16];
     const int ncol = P->ncomp[3];
     const bool te = hf_err_is_truncexp(P);
     const int rstride = 24 * Kctx + 16;
@@ -223,29 +216,21 @@ __device__ unsigned long long rows_total_region(int r, const int32_t* __restrict
         }
     }
     __syncthreads();
-    unsigned long long x = 0ull;           // checksum of what is written (hf_cks_term): the host verifies what it read
     for (int v = tid; v < rstride; v += nt) {
         const double dv = blockv[v];
         const int64_t at = 1 + (int64_t) r * rstride + v;
         out_dev[at] = dv;
         if (out_host) out_host[at] = dv;
-        x += hf_cks_term((unsigned long long) __double_as_longlong(dv), at);
     }
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if ((tid & 63) == 0) s_x[tid >> 6] = x;
-    __syncthreads();
-    unsigned long long c = 0ull;
-    if (tid == 0) for (int w = 0; w < (nt >> 6); w++) c += s_x[w];
-    return c;
 }
 
 // the log-likelihood (element 0) in k_reduce's order over the chunk list, by the block's first wavefront; zeros for the
-// regions that have no row at all.  Returns (thread 0) the log-likelihood.
-__device__ double rows_total_ll(const int32_t* __restrict__ rw_off, int nreg, int Kctx, const double* __restrict__ chunk_ll, int64_t C,
-                                double* __restrict__ out_dev, double* __restrict__ out_host, double* __restrict__ scratch) {
+// regions that have no row at all
+__device__ void rows_total_ll(const int32_t* __restrict__ rw_off, int nreg, int Kctx, const double* __restrict__ chunk_ll, int64_t C,
+                              double* __restrict__ out_dev, double* __restrict__ out_host) {
     const int tid = threadIdx.x, nt = blockDim.x;
-    double acc = 0.0;
     if (tid < 64) {
+        double acc = 0.0;
         int64_t c = tid;
         for (; c + 64 * 3 < C; c += 64 * 4) {
             const double x0 = xcu_load(chunk_ll + c), x1 = xcu_load(chunk_ll + c + 64), x2 = xcu_load(chunk_ll + c + 128), x3 = xcu_load(chunk_ll + c + 192);
@@ -257,11 +242,8 @@ __device__ double rows_total_ll(const int32_t* __restrict__ rw_off, int nreg, in
     }
     const int rstride = 24 * Kctx + 16;
     for (int r = 0; r < nreg; r++)
-        if (rw_off[r + 1] == rw_off[r]) {
+        if (rw_off[r + 1] == rw_off[r])
             for (int v = tid; v < rstride; v += nt) { const int64_t at = 1 + (int64_t) r * rstride + v; out_dev[at] = 0.0; if (out_host) out_host[at] = 0.0; }
-            if (tid == 0) xcu_store(scratch + r, 0.0);       // checksum sum of a block of zeros
-        }
-    return acc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -281,9 +263,9 @@ __global__ void __launch_bounds__(64 * HF_RS_WPB) k_row_stats(int n_rowwaves, in
                                                       const double* __restrict__ tile_ll, double* __restrict__ chunk_stats, int64_t V,
                                                       double* __restrict__ chunk_ll, const int32_t* __restrict__ rw_off, int Kctx,
                                                       double* __restrict__ out_dev, double* __restrict__ out_host, double* __restrict__ flag_row,
-                                                      const unsigned* __restrict__ flags, double seq, unsigned* __restrict__ done, int n_parts, int bpw,
+                                                      const unsigned* __restrict__ flags, unsigned* __restrict__ done, int bpw,
                                                       double* __restrict__ part_host) {
-    // part_host (round 5, the one-GPU path without a polling host): pinned HOST memory [n_rw_blocks][NA] | [C] | [1].  Every block writes its
+    // part_host (round 5, the one-GPU path): pinned HOST memory [n_rw_blocks][NA] | [C] | [1].  Every block writes its
     // partial vector (a log-likelihood wavefront its chunk's value, block 0 the flag word) there and is done — the HOST sums them after the
     // pass, in the order rows_total_region / rows_total_ll use (hf_estep.hip host_rows_total: the same bits).  Three dependent global round trips
     // (drained partial -> ticket -> the last block's loads) leave the launch's critical path: k_row_stats 13 -> ~6 us.  The partials also stay in
@@ -436,66 +418,32 @@ __global__ void __launch_bounds__(64 * HF_RS_WPB) k_row_stats(int n_rowwaves, in
         if (blockIdx.x == 0 && threadIdx.x == 0) part_host[(int64_t) n_rw_blocks * NA + C] = (double) (flags ? *flags : 0u);   // (final before this launch: k_seg_fb raised it)
         return;
     }
-    // ---- hand-offs: the last block of a part (a region / the log-likelihood blocks) sums the part; the last part writes flag
-    // word, checksums and stamp (producer: write-through stores, drained, block barrier, ticket; consumer: cache-bypassing loads) ----
+    // ---- hand-offs: the last block of a part (a region / the log-likelihood blocks) sums the part
+    // (producer: write-through stores, drained, block barrier, ticket; consumer: cache-bypassing loads) ----
     const int nreg = P->n_regions;
     const int part_id = (int) blockIdx.x < n_rw_blocks ? rw_region[(int) blockIdx.x * wpb] : nreg;
     const unsigned part_blocks = part_id < nreg ? (unsigned) ((rw_off[part_id + 1] - rw_off[part_id]) / wpb) : gridDim.x - (unsigned) n_rw_blocks;
-    double* __restrict__ scratch = done_scratch(done);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned ticket = __hip_atomic_fetch_add(done + HF_DONE_REGION0 + part_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned ticket = __hip_atomic_fetch_add(done + part_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = ticket == part_blocks - 1;
-        if (s_last) done[HF_DONE_REGION0 + part_id] = 0u;
+        if (s_last) done[part_id] = 0u;
     }
     __syncthreads();
     if (!s_last) return;
     if (part_id < nreg) {
-        const unsigned long long x = rows_total_region<KT>(part_id, rw_off, wpb, blk_stats, P, Kctx, out_dev, out_host);
-        if (seq == 0.0) return;
-        if (threadIdx.x == 0) xcu_store(scratch + part_id, __longlong_as_double((long long) x));
+        rows_total_region<KT>(part_id, rw_off, wpb, blk_stats, P, Kctx, out_dev, out_host);
     } else {
-        const double ll = rows_total_ll(rw_off, nreg, Kctx, chunk_ll, (int64_t) C, out_dev, out_host, scratch);
-        if (seq == 0.0) {
-            // No host polls the block (the default: completion is the stream's own stamp, hf_estep.hip wait_total): the parts need no common
-            // finish.  The flag word is final before this launch starts (k_seg_fb raised it), so this part writes it — one ticket round trip, one
-            // load and one store less on the launch's critical path than the round-3/4 "last part" stage (k_row_stats 13.3 -> ~11 us).
-            if (threadIdx.x == 0 && flags) {
-                const unsigned fl = *flags;
-                if (flag_row) flag_row[0] = (double) fl; else out_dev[V] = (double) fl;
-                if (out_host) out_host[V] = (double) fl;
-            }
-            return;
-        }
-        if (threadIdx.x == 0) xcu_store(scratch + HF_MAXREGIONS, ll);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned ticket = __hip_atomic_fetch_add(done + HF_DONE_PARTS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == (unsigned) n_parts - 1;
-        if (s_last) done[HF_DONE_PARTS] = 0u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) {
-        const unsigned fl = flags ? *flags : 0u;
-        if (flags) {   // the flag word: element V of the vector, or element 0 of a row of an exchange buffer (hf_bind_rank_total)
+        rows_total_ll(rw_off, nreg, Kctx, chunk_ll, (int64_t) C, out_dev, out_host);
+        // Completion is the stream's own stamp (hf_estep.hip wait_total), so the parts need no common finish.  The flag word is final
+        // before this launch starts (k_seg_fb raised it), so this part writes it — one ticket round trip, one load and one store less
+        // on the launch's critical path than the round-3/4 "last part" stage (k_row_stats 13.3 -> ~11 us).
+        // The flag word: element V of the vector, or element 0 of a row of an exchange buffer (hf_bind_rank_total).
+        if (threadIdx.x == 0 && flags) {
+            const unsigned fl = *flags;
             if (flag_row) flag_row[0] = (double) fl; else out_dev[V] = (double) fl;
             if (out_host) out_host[V] = (double) fl;
-        }
-        if (seq != 0.0 && out_host) {   // for a host that polls the pinned block: checksums bound to the pass, then the stamp
-            const double ll = xcu_load(scratch + HF_MAXREGIONS);
-            for (int r = 0; r < nreg; r++) {
-                unsigned long long c = (unsigned long long) __double_as_longlong(seq) + (unsigned long long) __double_as_longlong(xcu_load(scratch + r));
-                if (r == 0) c += hf_cks_term((unsigned long long) __double_as_longlong(ll), 0) +
-                                 hf_cks_term((unsigned long long) __double_as_longlong((double) fl), V);
-                out_host[V + 2 + r] = __longlong_as_double((long long) c);
-            }
-            __threadfence_system();
-            out_host[V + 1] = seq;
-            __threadfence_system();
         }
     }
 }
@@ -504,10 +452,10 @@ __global__ void __launch_bounds__(64 * HF_RS_WPB) k_row_stats(int n_rowwaves, in
 template <int KT>
 __global__ void __launch_bounds__(512) k_rows_total_late(const int32_t* __restrict__ rw_off, int wpb, const double* __restrict__ blk_stats,
                                                          const DevParams* __restrict__ P, int Kctx, const double* __restrict__ chunk_ll, int64_t C,
-                                                         double* __restrict__ out_dev, double* __restrict__ scratch) {
+                                                         double* __restrict__ out_dev) {
     const int nreg = P->n_regions;
-    if ((int) blockIdx.x < nreg) (void) rows_total_region<KT>((int) blockIdx.x, rw_off, wpb, blk_stats, P, Kctx, out_dev, nullptr);
-    else (void) rows_total_ll(rw_off, nreg, Kctx, chunk_ll, C, out_dev, nullptr, scratch);
+    if ((int) blockIdx.x < nreg) rows_total_region<KT>((int) blockIdx.x, rw_off, wpb, blk_stats, P, Kctx, out_dev, nullptr);
+    else rows_total_ll(rw_off, nreg, Kctx, chunk_ll, C, out_dev, nullptr);
 }
 
 // what ranks exchange (hf_rank_total): the total the pass left on the device, without the flag word

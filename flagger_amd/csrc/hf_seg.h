@@ -39,7 +39,7 @@
 // Round 4: the kernel is STRAIGHT-LINE wherever a lane used to be branched around work that is the identity
 // for it — scan levels multiply by an identity matrix where there is no neighbour, lanes past their last window multiply by an
 // identity row of the table, lanes without a window store to the segment's spare record — and renormalises once per two products
-// from an integer maximum; every piece has a -DHF_SEG_... switch below for same-box A/B runs (profiles/tools/build_variants.sh).
+// from an integer maximum.
 #pragma once
 #include "hf_scan.h"
 
@@ -61,25 +61,13 @@
 #error "hf_seg.h / hf_rows.h: the in-launch hand-offs rely on GFX9 (CDNA) vmcnt semantics; build with --offload-arch=gfx950"
 #endif
 #define HF_SEG_SPIN_MAX (1 << 16)            // polls of one flag before the wait is given up (HF_FLAG_SYNC: the host falls back to two launches)
-__device__ __forceinline__ void seg_xcu_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ __forceinline__ double seg_xcu_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 // Round 6 (VERDICT r05 #2a): a segment product travels as 8 x 16-byte `sc0 sc1` accesses instead of 16 + 16 eight-byte system-scope atomics
 // (MI355X_MICROARCH.md, Workgroup dispatch: a dwordx2 sc1 store costs 2.7x a dwordx4's time per byte, 8-byte sc1 loads run at 0.54-0.70x the
 // 16-byte rate).  Same scope bits as the atomics' lowering, same protocol: write-through data, drained queue, then the flag; the reader polls
 // the flag, then loads past its caches.  Inline assembly: hipcc has no builtin for a 16-byte store with both scope bits (a volatile access
-// gets them, with an s_waitcnt vmcnt(0) behind EVERY access).  -DHF_SEG_WIDE=0: the 8-byte atomics of rounds 3-5 (same-box A/B).
-#ifndef HF_SEG_WIDE
-#define HF_SEG_WIDE 1
-#endif
-#ifndef HF_SEG_STAGGER
-#define HF_SEG_STAGGER 0           // cycles between the starts of the grid's parts (0: all workgroups start together)
-#endif
-#ifndef HF_SEG_STAGGER_PARTS
-#define HF_SEG_STAGGER_PARTS 2
-#endif
+// gets them, with an s_waitcnt vmcnt(0) behind EVERY access).  The 8-byte atomics of rounds 3-5 were 0.4 us slower (profiles/r06_ab_handoff.txt).
 typedef unsigned hf_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void seg_xcu_store_m4(double* p, const double m[16]) {
-#if HF_SEG_WIDE
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         hf_u32x4 v;
@@ -87,15 +75,10 @@ __device__ __forceinline__ void seg_xcu_store_m4(double* p, const double m[16]) 
         v.z = (unsigned) __double2loint(m[2 * k + 1]); v.w = (unsigned) __double2hiint(m[2 * k + 1]);
         asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(p + 2 * k), "v"(v) : "memory");
     }
-#else
-#pragma unroll
-    for (int k = 0; k < 16; k++) seg_xcu_store(p + k, m[k]);
-#endif
 }
 // (the loads and their wait in ONE asm statement: the compiler does not count an asm load on its vmcnt scoreboard, so the registers are only
 // valid behind the statement's own s_waitcnt; nothing else of the wavefront is in flight at the two places this is called from)
 __device__ __forceinline__ void seg_xcu_load_m4(const double* p, double m[16]) {
-#if HF_SEG_WIDE
     hf_u32x4 v0, v1, v2, v3, v4, v5, v6, v7;
     asm volatile("global_load_dwordx4 %0, %8, off sc0 sc1\n\t"
                  "global_load_dwordx4 %1, %8, off offset:16 sc0 sc1\n\t"
@@ -110,10 +93,6 @@ __device__ __forceinline__ void seg_xcu_load_m4(const double* p, double m[16]) {
     const hf_u32x4 v[8] = {v0, v1, v2, v3, v4, v5, v6, v7};
 #pragma unroll
     for (int k = 0; k < 8; k++) { m[2 * k] = __hiloint2double((int) v[k].y, (int) v[k].x); m[2 * k + 1] = __hiloint2double((int) v[k].w, (int) v[k].z); }
-#else
-#pragma unroll
-    for (int k = 0; k < 16; k++) m[k] = seg_xcu_load(p + k);
-#endif
 }
 
 // -DHF_SEG_TRACE: s_memtime stamps of k_seg_fb<true>'s phases, one row of HF_SEG_TRACE_N words per workgroup, dumped by
@@ -134,23 +113,6 @@ __device__ unsigned long long* g_seg_trace = nullptr;
 #define TR_FLUSH(k0, n)
 #endif
 
-// 1 / sc of the replays.  The scale of a window is a normal number (> 1e-50: hmm.c:412-415 raises an error below; at a chunk's first window
-// >= 0.25e-40 by the emission floor), so the special cases that the IEEE division's expansion carries (v_div_scale / v_div_fmas / v_div_fixup:
-// twelve instructions) cannot occur.  -DHF_SEG_FASTRCP=1: v_rcp_f64 and two Newton steps (five instructions, within 1 ulp of the quotient: the
-// product nf * (1 / sc) already differs from nf / sc in the last bit); measured in round 6: profiles/r06_ab_micro.txt.
-#ifndef HF_SEG_FASTRCP
-#define HF_SEG_FASTRCP 0
-#endif
-__device__ __forceinline__ double seg_recip(double sc) {
-#if HF_SEG_FASTRCP
-    double r = __builtin_amdgcn_rcp(sc);
-    r = fma(fma(-sc, r, 1.0), r, r);
-    r = fma(fma(-sc, r, 1.0), r, r);
-    return r;
-#else
-    return 1.0 / sc;
-#endif
-}
 __device__ __forceinline__ void v4_renorm(double v[4]) {
     int e;
     (void) frexp(fmax(fmax(v[0], v[1]), fmax(v[2], v[3])), &e);
@@ -591,8 +553,7 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
                                             const double* __restrict__ Qs, double* Pseg, unsigned* ready, unsigned epoch, unsigned wait_epoch,
                                             const int32_t* __restrict__ pos, double* __restrict__ recs, double* __restrict__ scale_s,
                                             int8_t* __restrict__ label, double* __restrict__ seg_ll,
-                                            unsigned* __restrict__ flags, int32_t g0, int nc_arg,
-                                            const int32_t* __restrict__ seg_of_block, int bx) {
+                                            unsigned* __restrict__ flags, int32_t g0, int nc_arg, int bx) {
     static_assert(FUSED || !CACHED, "cached row blocks: one-launch mode only");
     const int nc = CACHED ? nc_arg : 0;
     constexpr int LM = HF_SEG_LMAX;
@@ -608,25 +569,13 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
     // g0: the launch's first segment (round 5: a context whose pair records exceed the Infinity Cache runs the pass in SUB-PASSES of whole
     // chunks — k_seg_fb, then k_pair_sums, per sub-pass — through one record buffer that holds a sub-pass at a time; `recs` then points
     // p0 records before the buffer, so that the plan's global positions land inside it: hf_estep.hip enqueue_pass)
-    // seg_of_block (round 6, hf_create's XCD plan): the launch's block b runs segment seg_of_block[g0 + b] — all segments of a chunk on block
-    // indices congruent mod 8, i.e. (observed, for speed only) on one XCD; < 0: a padding block of the plan.  Null: block b runs segment g0 + b.
-    int g = bx + g0;
+    // (Round 6, not kept: a block -> segment table that put a chunk's segments on block indices congruent mod 8 was 13 us slower on a full
+    // device — the dispatcher does not keep block b on XCD b % 8, profiles/r06_ab_handoff.txt; starting the grid's parts 5 000 .. 20 000
+    // cycles apart, so that one part's fetches meet another's scans, 46.6 .. 49.0 against 46.0 us: profiles/r06_ab_stagger.txt.)
+    const int g = bx + g0;
     const int lane = threadIdx.x;
     if (FUSED && BWD) KSTAMP(1);
-    if (seg_of_block) { g = seg_of_block[g]; if (g < 0) return; }
     const SegDesc d = sd[g];
-#if HF_SEG_STAGGER > 0
-    // EXPERIMENT (round 6): the workgroups of a launch all start together and walk the same phases in step — the row fetches of twelve wavefronts
-    // meet in the CU's one vector-memory path (64 B/clk: a forward step of all twelve takes 96 KB / 64 = 1 536 cycles, what the trace measures),
-    // the scans meet in the VALU.  Later parts of the grid start HF_SEG_STAGGER cycles later each, so that one part's fetches meet another's scans.
-    if (FUSED && BWD) {
-        const unsigned part = (unsigned) (((unsigned long long) blockIdx.x * HF_SEG_STAGGER_PARTS) / gridDim.x);
-        if (part) {
-            const unsigned long long t_end = clock64() + (unsigned long long) part * HF_SEG_STAGGER;
-            while (clock64() < t_end) __builtin_amdgcn_s_sleep(16);
-        }
-    }
-#endif
     const int L = d.L, n = d.n;
     const int a = lane * L;
     const int m = n - a < L ? (n - a > 0 ? n - a : 0) : L;
@@ -844,8 +793,9 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
                 // does to the reciprocal: it cannot occur.  Only a chunk's first window is exempt from the 1e-50 test, and there the scale is a
                 // sum of start x emission values of which the Gaussian states' carry the reference's 1e-40 floor per component
                 // (hmm_utils.c:787-790): >= 0.25e-40.  The negative-binomial tables have no floor, but a zero row gives 0 / 0 in the reference too.
-                // A guard here — even in the unrolled first step only — cost the kernel 1-2 us: profiles/r05_ab_segfb_regression.txt.)
-                const double rsc = seg_recip(sc);
+                // A guard here — even in the unrolled first step only — cost the kernel 1-2 us: profiles/r05_ab_segfb_regression.txt.
+                // v_rcp_f64 and two Newton steps in the division's place bought nothing, 46.0 against 46.1 us: profiles/r06_ab_micro.txt.)
+                const double rsc = 1.0 / sc;
 #pragma unroll
                 for (int s = 0; s < 4; s++) { f[s] = nf[s] * rsc; fs[i][s] = f[s]; }
                 { int e2; lm *= frexp(sc, &e2); le += e2; }                // hmm.c:428, see above
@@ -867,6 +817,13 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
     // ---- D: backward replay + labels (hmm.c:452-545, 671-692) ----
     if (BWD) {
         const int jl = m - 1;                                   // the lane's last window (< 0: none)
+        // the lane's first window again (= a), MULTIPLIED AGAIN from an L the compiler cannot trace back: left to share `a` with the phases
+        // above, the allocator of k_seg_fb_batch<true, true, true> keeps it in scratch from the kernel's start and reloads (and stores
+        // back) the index in every step below — 84 bytes of scratch and 42 spilled dwords against 76 and 24 with this one v_mul_lo_u32
+        // (profiles/retire_switches_isa.txt); a copy of `a` through an empty asm keeps the spill.
+        int Lr = L;
+        asm("" : "+s"(Lr));
+        const int ab = lane * Lr;
         const DevRegion* __restrict__ Rl = &P->reg[d.reg_last];
         const int64_t slot_ij = (int64_t) d.slot0 + lane;       // + i*64
         // f of the window before the lane's first one: the previous lane's last forward vector, the carried-in vector for lane 0
@@ -875,7 +832,7 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
         for (int s = 0; s < 4; s++) { fp[s] = __shfl_up(f[s], 1); if (lane == 0) fp[s] = fin[s]; }
         double b[4] = {0.0, 0.0, 0.0, 0.0};
         if (jl >= 0) {
-            if (d.k == d.nseg - 1 && a + jl == n - 1) {         // the chunk's last window, hmm.c:452-467
+            if (d.k == d.nseg - 1 && ab + jl == n - 1) {         // the chunk's last window, hmm.c:452-467
 #pragma unroll
                 for (int s = 0; s < 4; s++) b[s] = Rl->trans[s][4] / scl;
                 double2* __restrict__ dst = reinterpret_cast<double2*>(recs) + (int64_t) d.spare_pos * 4;   // its f: the chunk's spare record
@@ -889,7 +846,7 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
 #pragma unroll
                 for (int s = 0; s < 4; s++) b[s] = bdir[s] * kk;
             }
-            s_lab[a + jl] = (int8_t) posterior_label_fast(f, b, scl);
+            s_lab[ab + jl] = (int8_t) posterior_label_fast(f, b, scl);
         }
         // record k = { f_{k-1}, b_k } and scale k leave at the top of the step that consumes b_k; window k's row turns b_k into
         // b_{k-1}.  All lanes run k = L-1 .. 1 (cooperative fetch), a lane joins at its last window.  The first step still
@@ -900,18 +857,13 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
         // (measured: partial-line writes, profiles/r03c_ablation.txt).  Lanes without a window k write nothing.
         const int32_t* __restrict__ pos_seg = pos + d.t0;
         auto store_rec = [&](int k, bool act, int32_t pk, const double* __restrict__ fk, double sck) {
-            // Round 6 (HF_SEG_RECPAD, default on): the staged records lie 80 bytes apart instead of 64 — at a 64-byte stride the sixteen lanes of a
+            // Round 6: the staged records lie 80 bytes apart instead of 64 — at a 64-byte stride the sixteen lanes of a
             // quarter-wavefront hit four groups of four banks (a 16-way conflict on a quarter of the LDS: 1 024 conflict cycles per wavefront and
             // launch, 32 % of the LDS cycles: profiles/r05h_pmc_sq_b.json); 20 dwords apart they cover all 64 banks exactly once, on the write and
             // on the read side.  No extra instruction: only the address constants change (round 4 had ROTATED the pieces instead — selects per
-            // register — and lost 0.3 us).  5 120 of the row block's 8 192 bytes.  HF_SEG_RECPAD=2: 64 bytes apart, piece j of record r in slot
-            // j ^ ((r >> 2) & 3) — conflict-free on both sides, and 0.8 us slower than the padding (profiles/r06_ab_swizzle.txt): not the default.
-#ifndef HF_SEG_RECPAD
-#define HF_SEG_RECPAD 1
-#endif
-            constexpr int RS = HF_SEG_RECPAD == 1 ? 5 : 4;      // double2 per staged record
-            constexpr bool SWZ = HF_SEG_RECPAD == 2;            // (2: 64 bytes apart, piece j of record r at slot j ^ ((r >> 2) & 3))
-            const int wsz = SWZ ? ((lane >> 2) & 3) : 0;
+            // register — and lost 0.3 us).  5 120 of the row block's 8 192 bytes.  64 bytes apart with piece j of record r in slot
+            // j ^ ((r >> 2) & 3) — conflict-free on both sides — was 0.8 us slower than the padding (profiles/r06_ab_swizzle.txt).
+            constexpr int RS = 5;                               // double2 per staged record
             double2* __restrict__ mine = reinterpret_cast<double2*>(blk) + lane * RS;
             // (rotating the pieces so that these writes are free of bank conflicts — lane by lane at a 64-byte stride they hit four banks of
             // 64 — was measured 0.3 us SLOWER, profiles/r04e_ab_variants.txt: the conflicts are not on the kernel's critical path)
@@ -921,13 +873,13 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
             // the kernel ~1 us, profiles/r05_ab_segfb_regression.txt)
             double f0 = fk[0], f1 = fk[1], f2 = fk[2], f3 = fk[3], sc_ = sck;
             asm("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3), "+v"(sc_));
-            mine[0 ^ wsz] = make_double2(f0, f1); mine[1 ^ wsz] = make_double2(f2, f3);
-            mine[2 ^ wsz] = make_double2(b[0], b[1]); mine[3 ^ wsz] = make_double2(b[2], b[3]);
+            mine[0] = make_double2(f0, f1); mine[1] = make_double2(f2, f3);
+            mine[2] = make_double2(b[0], b[1]); mine[3] = make_double2(b[2], b[3]);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             // store instruction q writes records 16 q .. 16 q + 15: lane l holds piece l & 3 of record 16 q + (l >> 2)
-            const double2* __restrict__ img = reinterpret_cast<const double2*>(blk) + (lane >> 2) * RS + ((lane & 3) ^ (SWZ ? ((lane >> 4) & 3) : 0));
+            const double2* __restrict__ img = reinterpret_cast<const double2*>(blk) + (lane >> 2) * RS + (lane & 3);
             const double2 v0 = img[0], v1 = img[16 * RS], v2 = img[32 * RS], v3 = img[48 * RS];
             double2* __restrict__ R2 = reinterpret_cast<double2*>(recs) + (lane & 3);
             // lanes without a window k write THE SEGMENT'S SPARE RECORD (SegDesc.trash_pos, behind the sub-pass's positions) and a padding slot
@@ -942,7 +894,7 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();                    // the block has been read out: the next row fetch may land
         };
-        int32_t pk_next = jl >= 0 ? pos_seg[a + jl] : 0;        // position of the record of the lane's last window (the first step's, when that is window L-1)
+        int32_t pk_next = jl >= 0 ? pos_seg[ab + jl] : 0;        // position of the record of the lane's last window (the first step's, when that is window L-1)
         TR_STAMP(9);
         TR_RESET();
 #pragma unroll
@@ -955,7 +907,7 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
                 TR_LAP(3);
                 const bool act = k <= jl;                       // this lane has a window k
                 const int32_t pk = pk_next;
-                pk_next = (k - 1 <= jl && k - 1 >= 0) ? pos_seg[a + k - 1] : 0;   // in flight during this step
+                pk_next = (k - 1 <= jl && k - 1 >= 0) ? pos_seg[ab + k - 1] : 0;   // in flight during this step
                 store_rec(k, act, pk, fs[k - 1], ss[k]);
                 TR_LAP(4);
                 if (k >= 2 && k - 1 >= nc) rows_issue(F, k - 1);
@@ -971,10 +923,10 @@ __device__ __forceinline__ void seg_fb_body(const SegDesc* __restrict__ sd, cons
                     }
                     const double sc = ss[k - 1];
                     if (sc < 1e-50) bad |= HF_FLAG_SCALE;                     // hmm.c:521-524
-                    const double rsc = seg_recip(sc);
+                    const double rsc = 1.0 / sc;
 #pragma unroll
                     for (int s = 0; s < 4; s++) b[s] = nb[s] * rsc;
-                    s_lab[a + k - 1] = (int8_t) posterior_label_fast(fs[k - 1], b, sc);
+                    s_lab[ab + k - 1] = (int8_t) posterior_label_fast(fs[k - 1], b, sc);
                 }
                 TR_LAP(6);
             }
@@ -1008,15 +960,14 @@ __global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb(const SegDesc* __rest
                                                            const double* __restrict__ Qs, double* Pseg, unsigned* ready, unsigned epoch, unsigned wait_epoch,
                                                            const int32_t* __restrict__ pos, double* __restrict__ recs, double* __restrict__ scale_s,
                                                            int8_t* __restrict__ label, double* __restrict__ seg_ll,
-                                                           unsigned* __restrict__ flags, int32_t g0, int nc_arg,
-                                                           const int32_t* __restrict__ seg_of_block) {
+                                                           unsigned* __restrict__ flags, int32_t g0, int nc_arg) {
     seg_fb_body<BWD, FUSED, CACHED>(sd, arow, lutA, P, Qs, Pseg, ready, epoch, wait_epoch, pos, recs, scale_s, label, seg_ll, flags, g0, nc_arg,
-                                    seg_of_block, (int) blockIdx.x);
+                                    (int) blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
-// k_seg_fb_batch (hf_batch.h): the segments of SEVERAL models of one context in one launch — blockIdx.x is the segment (or the block of
-// the XCD plan) as in k_seg_fb, blockIdx.y the model's place in the launch.  The segment descriptors, the row stream arow and the record
+// k_seg_fb_batch (hf_batch.h): the segments of SEVERAL models of one context in one launch — blockIdx.x is the segment
+// as in k_seg_fb, blockIdx.y the model's place in the launch.  The segment descriptors, the row stream arow and the record
 // positions are the context's, shared by every model; everything a model reads or writes per pass comes from its row of `tab` (device
 // memory, written once by hf_batch_create), its hand-off epochs from the launch's arguments.  A model's blocks run k_seg_fb's body with
 // that model's pointers: the same arithmetic in the same order.  The blocks of a launch are dispatched x fastest, so every segment of a
@@ -1032,10 +983,9 @@ struct SegFbBatch { int32_t model[HF_SEG_BATCH_MAX]; unsigned epoch[HF_SEG_BATCH
 template <bool BWD, bool FUSED, bool CACHED = false>
 __global__ void __launch_bounds__(64, HF_SEG_OCC) k_seg_fb_batch(const SegDesc* __restrict__ sd, const int32_t* __restrict__ arow,
                                                                  const SegFbModel* __restrict__ tab, SegFbBatch bt,
-                                                                 const int32_t* __restrict__ pos, int32_t g0, int nc_arg,
-                                                                 const int32_t* __restrict__ seg_of_block) {
+                                                                 const int32_t* __restrict__ pos, int32_t g0, int nc_arg) {
     const int y = (int) blockIdx.y;
     const SegFbModel& m = tab[bt.model[y]];
     seg_fb_body<BWD, FUSED, CACHED>(sd, arow, m.lutA, m.P, m.Qs, m.Pseg, m.ready, bt.epoch[y], bt.wait_epoch[y], pos, m.recs, m.scale_s, m.label,
-                                    m.seg_ll, m.flags, g0, nc_arg, seg_of_block, (int) blockIdx.x);
+                                    m.seg_ll, m.flags, g0, nc_arg, (int) blockIdx.x);
 }

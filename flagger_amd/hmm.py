@@ -405,17 +405,6 @@ class EMList:
     def sub_pass_windows(self, k: int = 0) -> int:
         return int(self._L.hf_sub_pass_windows(self._h, int(k)))
 
-    @property
-    def seg_xcd_plan(self) -> bool:
-        """True when the one-launch segment kernel runs its blocks through hf_create's block -> segment table (hf_seg_xcd_plan)."""
-        return bool(self._L.hf_seg_xcd_plan(self._h)) if hasattr(self._L, "hf_seg_xcd_plan") else False
-
-    def seg_block_table(self) -> np.ndarray:
-        n = int(self._L.hf_seg_block_table(self._h, None, 0))
-        out = np.empty(n, dtype=np.int32)
-        self._L.hf_seg_block_table(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n)
-        return out
-
     def create_phases(self) -> dict:
         """{phase: ms} of this context's hf_create, in call order; the last entry is "total" (hf_create_phases)."""
         if not hasattr(self._L, "hf_create_phases"):

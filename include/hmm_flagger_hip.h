@@ -179,8 +179,7 @@ int hf_write_flag_row(hf_ctx *ctx, double *row_dev, void *stream);
  * wait for the stream and translate the device error flags (HF_E_SCALE / HF_E_NAN / ...).  Blocks the host until `stream` (the
  * stream of the hf_estep it completes) has drained.  A pass whose flags report an error leaves nothing to get: every getter of the
  * pass's results returns HF_E_ARG until the next HF_MODE_FULL pass (hf_check likewise). */
-/* (hf_finish synchronises the stream.  Environment HF_POLL=1 opts into polling a checksummed completion stamp in the
- * pinned result block instead — a few microseconds less per pass, see hf_estep.hip — HF_POLL=debug verifies it.) */
+/* (hf_finish waits for a value that hipStreamWriteValue32 writes behind the pass, or synchronises the stream: hf_estep.hip wait_total.) */
 int hf_finish(hf_ctx *ctx, double *stats_host, void *stream);
 /* Only wait + error flags (multi-GPU callers reduce the gathered vectors themselves).  HF_E_RETRY: a hand-off of the one-launch
  * segment kernel timed out; the context has switched to two launches and the caller repeats the pass from hf_estep.  Blocks the
@@ -222,12 +221,6 @@ int hf_seg_cached_steps(const hf_ctx *ctx);
  * hf_sub_pass_windows: the windows of sub-pass k (what ONE launch of the segment kernel processes: hf_set_profiling times the first). */
 int hf_sub_passes(const hf_ctx *ctx);
 int64_t hf_sub_pass_windows(const hf_ctx *ctx, int k);
-/* XCD plan of the one-launch segment kernel (round 6): 1 when the blocks of the NEXT pass run the segments through hf_create's block ->
- * segment table (all segments of a chunk on block indices congruent mod 8 — observed: one XCD; the hand-off stays system-scope, so this is
- * for speed only), 0 when block b runs segment b (environment HF_SEG_XCD=0, two-launch mode, or a chunk whose segments would span more
- * than half of the resident workgroups).  hf_seg_block_table: the table (n entries copied, -1 = padding block); returns its length. */
-int hf_seg_xcd_plan(const hf_ctx *ctx);
-int64_t hf_seg_block_table(const hf_ctx *ctx, int32_t *seg_of_block, int64_t n);
 /* Where hf_create's wall time went (what EM_construct + EM_renewParametersAndEstimatorsFromModel cost the reference per chunk and
  * iteration, hmm.c:253-298, paid once here): up to `max` phases in call order, ms[i] and a static name each; returns the number of
  * phases recorded.  The last entry is the total. */

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
-"""Soak test of the polled completion (hf_finish without stream synchronisation): alternate two parameter sets for N passes
-per statistics mode and compare every returned vector with the one of its own parameters; prints what differs.
-  python profiles/tools/poll_soak.py 400000 [nb]      (history: stamp only: 1 stale pass in ~2 000; + XOR checksum: 1 in ~300 000,
-  two equal stale words cancel; + position-weighted checksum: 0 in 800 000)"""
+"""Soak test of hf_finish's completion: alternate two parameter sets for N passes per statistics mode and compare every
+returned vector with the one of its own parameters; prints what differs.
+  python profiles/tools/poll_soak.py 400000 [nb]
+Record: written for the kernel-written stamp that the host polled (stamp only: 1 stale pass in ~2 000; + XOR checksum: 1 in
+~300 000, two equal stale words cancel; + position-weighted checksum: 0 in 800 000).  That path is gone from the library; what
+this now soaks is the stream's own stamp, the only completion hf_finish has."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))); sys.path.insert(0, "tests")
 import numpy as np

@@ -315,7 +315,6 @@ def _segments(store):
 
 
 SWITCHES = {
-    "xcd block plan": ({"HF_SEG_XCD": "1"}, lambda em: em.seg_xcd_plan),
     "no cached row blocks": ({"HF_SEG_CACHED_STEPS": "0"}, lambda em: em.seg_launches == 1 and em.seg_cached_steps == 0),
     "three cached row blocks": ({"HF_SEG_CACHED_STEPS": "3"}, lambda em: em.seg_launches == 1 and em.seg_cached_steps == 3),
     "a device that holds just the segments": ({"HF_SEG_RESIDENT": "segments"}, lambda em: em.seg_launches == 1 and em.seg_cached_steps == 0),
