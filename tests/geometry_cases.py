@@ -12,7 +12,9 @@ Chunks (one contig each), first window .. last window:
     2048..3072                           starts on the grid: a first window, two pieces less that window, one window over
     3073..4172                           long and unaligned
 Jobs: every pair first <= last over the boundary points (POINTS: every chunk's first and last window +- 1, every multiple of 512 +- 1,
-and 7, 8, 9, 503, 504, 505), a random mask 1..15 and a random region filter each."""
+and 7, 8, 9, 503, 504, 505), a random mask 1..15 and a random region filter each.  The breakpoint jobs (every pair first < last of the
+boundary points inside one chunk), the long-run jobs (the short ranges of the 903 and twenty long ones) and the length sets of the
+minimum-length decoder are here too, each with its reference, once for the getters' own device tests and the geometry tests."""
 import dataclasses
 import functools
 
@@ -20,10 +22,14 @@ import numpy as np
 
 from flagger_amd import synth
 from test_bruteforce_cpu import _tiny_store
+from test_longrun_cpu import max_len
 from test_moments_cpu import TINY
 from test_viterbi_cpu import perturbed_model
+import breakpoint_ref as BR
 import entropy_ref as ER
 import interval_ref as IR
+import longrun_ref as LR
+import minlen_ref
 import moments_ref as MR
 import posterior_ref as PR
 import runs_ref as RR
@@ -199,6 +205,74 @@ def viterbi_reference(model_type, seed):
 def sample_reference(model_type, seed):
     A, end = rows(model_type, seed)
     return S.ffbs(A, end, OFF, SAMPLE_SEED + seed, range(SAMPLES))
+
+
+# the length sets of hf_viterbi_minlen: the realistic one; one longer than the one-, two- and seven-window chunks, whose runs are all
+# exempt; one state owning 61 of the 64 lanes
+MINLEN_SETS = ((3, 5, 1, 7), (16, 16, 16, 16), (61, 1, 1, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def minlen_reference(model_type, seed, min_len):
+    """(labels, chunk scores, path_log_prob, unconstrained labels): minlen_ref.reference on the grid store; min_len a tuple."""
+    store, model, alpha, _ = case(model_type, seed)
+    return minlen_ref.reference(store, model, alpha, min_len)
+
+
+# the generators of the breakpoint jobs' masks, chosen on the CPU so that the REFERENCE meets test_breakpoint_gpu._not_empty with room:
+# of the finite jobs with at least 8 candidate windows, 17 of 48, 17 of 43 and 24 of 48 have mode_p < 0.99, none within 1e-3 of that bound
+BREAKPOINT_MASK_SEED = {0: 38, 1: 26, 2: 0}
+
+
+@functools.lru_cache(maxsize=None)
+def breakpoint_reference(model_type, seed):
+    """((F, L, U, V), log P(E_k) per job): every pair a < b of the boundary points inside one chunk, a random left mask and its
+    complement, route (ii) of tests/breakpoint_ref.py."""
+    A, end = rows(model_type, seed)
+    P = POINTS
+    chunk = np.searchsorted(np.asarray(OFF), P, "right") - 1
+    F, L = np.meshgrid(P, P, indexing="ij")
+    keep = (F < L) & (chunk[:, None] == chunk[None, :])
+    F, L = F[keep], L[keep]
+    U = np.random.default_rng(BREAKPOINT_MASK_SEED[seed]).integers(1, 15, F.size).astype(np.int64)
+    V = 15 & ~U                                             # (the complement: of the disjoint pairs the ones whose posterior spreads most)
+    events = BR.LongDouble(A, end, OFF).events(F, L, U, V)
+    _, pieces = pieces_of(OFF, F, L)
+    assert pieces.max() == 3 and np.sum(L - F == 1) >= 10 and F.size >= 80
+    for a in (F, L, U, V):
+        a.setflags(write=False)
+    return (F, L, U, V), events
+
+
+@functools.lru_cache(maxsize=None)
+def longrun_jobs(model_type, seed):
+    """(F, L, M, K): every range of the case of at most 48 windows (half of them span chunks) and 20 long ones, the case's masks, a
+    length out of 1, 2, 3, 7, 16, 58 cut to what 64 lanes hold; then the short ranges again with short lengths."""
+    _, _, _, (F, L, M, _) = case(model_type, seed)
+    n_ = L - F + 1
+    pick = np.concatenate([np.flatnonzero(n_ <= 48), np.random.default_rng(7).choice(np.flatnonzero(n_ > 64), 20, replace=False)])
+    F, L, M = F[pick], L[pick], M[pick]
+    M = np.where(L - F + 1 > 64, (M & ~4) | ((M & ~4) == 0), M)            # (long ranges: the other labels, tests/test_longrun_cpu.py jobs)
+    K = np.minimum(np.random.default_rng(8).choice([1, 2, 3, 7, 16, 58], F.size), [max_len(m) for m in M])
+    # in half of those the length is above the range's or the mask is full: exactly 0 and -inf.  The short ranges once more with a
+    # length of at most half the range's out of 1, 2, 3, 7, for a mask that is not full and for its complement, so that more than half of all jobs walk the chain to a
+    # value that is neither (tests/test_geometry_cpu.py)
+    short = np.flatnonzero(L - F + 1 <= 48)
+    rng = np.random.default_rng(9)
+    K2 = np.minimum(rng.choice([1, 2, 3, 7], F.size), np.maximum(1, (L - F + 2) // 2))
+    M2 = np.where(M == 15, rng.integers(1, 15, F.size), M)
+    F, L, M, K = (np.concatenate([x, y[short], z[short]]) for x, y, z in ((F, F, F), (L, L, L), (M, M2, 15 & ~M2), (K, K2, K2)))
+    for a in (F, L, M, K):
+        a.setflags(write=False)
+    return F, L, M, K
+
+
+@functools.lru_cache(maxsize=None)
+def longrun_reference(model_type, seed, joined_key):
+    """(log_p_none, log_p_some) of longrun_jobs with the joins of joined_key (a tuple, or None)."""
+    A, end = rows(model_type, seed)
+    F, L, M, K = longrun_jobs(model_type, seed)
+    return LR.Chain(A, end, OFF).log_probs(F, L, M, K, None if joined_key is None else np.array(joined_key, bool))
 
 
 # ---- the variants --------------------------------------------------------------------------------------------------------------------

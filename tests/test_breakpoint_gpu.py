@@ -163,35 +163,17 @@ def test_a_job_without_weight():
 
 
 # ---- 2. the grid store: the piece grid, the lane scans and the chain ------------------------------------------------------------------------
-# the generators of the grid jobs' masks, chosen on the CPU so that the REFERENCE meets _not_empty with room: of the finite jobs with at
-# least 8 candidate windows, 17 of 48, 17 of 43 and 24 of 48 have mode_p < 0.99, none within 1e-3 of that bound
-GRID_MASK_SEED = {0: 38, 1: 26, 2: 0}
-
-
-@functools.lru_cache(maxsize=None)
-def _grid_reference(model_type, seed):
-    """Every pair a < b of the boundary points inside one chunk, a random left mask and its complement, route (ii)."""
-    A, end = G.rows(model_type, seed)
-    P = G.POINTS
-    chunk = np.searchsorted(np.asarray(G.OFF), P, "right") - 1
-    F, L = np.meshgrid(P, P, indexing="ij")
-    keep = (F < L) & (chunk[:, None] == chunk[None, :])
-    F, L = F[keep], L[keep]
-    U = np.random.default_rng(GRID_MASK_SEED[seed]).integers(1, 15, F.size).astype(np.int64)
-    V = 15 & ~U                                             # (the complement: of the disjoint pairs the ones whose posterior spreads most)
-    events = BR.LongDouble(A, end, G.OFF).events(F, L, U, V)
-    _, pieces = G.pieces_of(G.OFF, F, L)
-    assert pieces.max() == 3 and np.sum(L - F == 1) >= 10 and F.size >= 80
-    return (F, L, U, V), events
+# the jobs (every pair a < b of the boundary points inside one chunk, a random left mask and its complement) and their reference, route
+# (ii), are geometry_cases.breakpoint_reference: tests/test_geometry_gpu.py runs them on the variants of the grid store as well
+_grid_reference = G.breakpoint_reference
 
 
 @pytest.mark.parametrize("model_type,seed,algo", [(mt, s, N.HF_ALGO_SCAN) for mt, s in G.CASES] + [G.CASES[0] + (N.HF_ALGO_SEQ,)])
 def test_grid_store_equals_reference(model_type, seed, algo):
+    import test_geometry_gpu as TG                          # (here: that module imports this one)
     store, model, _, _ = G.case(model_type, seed)
-    (F, L, U, V), events = _grid_reference(model_type, seed)
-    _not_empty(events, "grid %d" % seed)
     em = _pass(store, model, algo)
-    _check(em, F, L, U, V, events, "grid %d algo %d" % (seed, algo))
+    TG.check_breakpoints(em, model_type, seed, "grid %d algo %d" % (seed, algo), profile_every=1)      # every job, every profile
     em.close()
 
 

@@ -1,5 +1,6 @@
-"""hmm_flagger with ALL final-inference options in one run: --uncertaintySamples, --runConfidence, --regionProbs, --exactTotals, --numBlocks and
---jointEntropy (with and without --viterbi) run one after another on one context, each building lazy state on top of what the ones
+"""hmm_flagger with ALL final-inference options in one run: --uncertaintySamples, --runConfidence, --regionProbs, --exactTotals, --numBlocks,
+--jointEntropy, --runBoundaries and --keptBlocks (with and without --viterbi, with --viterbi --enforceMinimumLengths and with --fitAlpha)
+run one after another on one context, each building lazy state on top of what the ones
 before it left.  Every file an option writes must be byte-identical to the file of a run with that option alone: a getter that answered
 for a decoder's parameters, for a stale lazy block or for half-built state would change a digit somewhere.  The suite otherwise runs
 each option by itself."""
@@ -28,14 +29,18 @@ def _rows(path):
     return [l.split("\t") for l in path.read_text().splitlines() if not l.startswith("#")]
 
 
-@pytest.mark.parametrize("base", [[], ["--viterbi"], ["--fitAlpha"]], ids=["posterior", "viterbi", "fitAlpha"])
+MINIMUM_LENGTHS = ["--minimumLengths", "12000,20000,28000"]      # (the kept-block lengths come from it: every run carries it)
+
+
+@pytest.mark.parametrize("base", [[], ["--viterbi"], ["--fitAlpha"], ["--viterbi", "--enforceMinimumLengths"]],
+                         ids=["posterior", "viterbi", "fitAlpha", "viterbi-minlen"])
 def test_cli_all_final_inference_options_in_one_run(tmp_path, base):
     """The input and base arguments of tests/test_interval_gpu.py::test_cli_run_confidence_and_regions.  With --fitAlpha the alpha statistics are
     switched on during EM and off before the getters run."""
     store = synth.config(1, 0.5)
     binp = tmp_path / "in.bin"
     store.write_bin(str(binp))
-    args = ["-i", str(binp), "-W", "4000", "-n", "4", "-P"] + base
+    args = ["-i", str(binp), "-W", "4000", "-n", "4", "-P"] + MINIMUM_LENGTHS + base
     # each option alone (the first run also supplies the regions: a run, a one-window region, an unknown contig, a region of two runs)
     _cli(args + ["--uncertaintySamples", "4"], tmp_path / "samples")
     runs_sup = _rows(tmp_path / "samples" / "final_label_runs_support.bed")
@@ -52,6 +57,10 @@ def test_cli_all_final_inference_options_in_one_run(tmp_path, base):
         "totals": (["--exactTotals"], ["label_totals_exact.tsv"]),
         "blocks": (["--numBlocks"], ["label_blocks_exact.tsv"]),
         "entropy": (["--jointEntropy"], ["path_uncertainty.tsv"]),
+        "boundaries": (["--runBoundaries"], ["final_label_run_boundaries.tsv"]),
+        # (with --regionProbs the option adds a row per region to its rows for the track and the contigs, by design: the single run
+        # carries the regions too, and --keptBlocks by itself is compared below)
+        "kept": (["--keptBlocks", "--regionProbs", str(bed)], ["kept_block_probabilities.tsv", "region_label_probabilities.tsv"]),
     }
     for name, (opt, _) in alone.items():
         if name != "samples":
@@ -67,7 +76,17 @@ def test_cli_all_final_inference_options_in_one_run(tmp_path, base):
         # and everything else the single run wrote (summary tables, parameter files, the posterior BED) is the combined run's too
         for f in os.listdir(tmp_path / name):
             assert (every / f).read_bytes() == (tmp_path / name / f).read_bytes(), (name, f)
+    # --keptBlocks without the regions: its file is the combined run's up to the region rows, every other file the combined run's
+    _cli(args + ["--keptBlocks"], tmp_path / "kept_alone")
+    head = (tmp_path / "kept_alone" / "kept_block_probabilities.tsv").read_bytes()
+    both = (every / "kept_block_probabilities.tsv").read_bytes()
+    assert len(head) > 0 and both.startswith(head) and [l.split(b"\t")[0] for l in both[len(head):].splitlines()] == [b"region"] * len(regions)
+    for f in os.listdir(tmp_path / "kept_alone"):
+        if f != "kept_block_probabilities.tsv":
+            assert (every / f).read_bytes() == (tmp_path / "kept_alone" / f).read_bytes(), ("kept_alone", f)
     if base == ["--fitAlpha"]:
         assert "alpha_fitted.tsv" in written
-    if base == ["--viterbi"]:
+    if "--viterbi" in base:
         assert "viterbi_log_probability.tsv" in written
+    if "--enforceMinimumLengths" in base:                   # (compared above: every single run wrote it too)
+        assert "viterbi_min_length_cost.tsv" in written and "viterbi_min_length_cost.tsv" in os.listdir(tmp_path / "kept")

@@ -13,16 +13,28 @@ Every test prints what it measured before it asserts (pytest -s).  Measured on t
                 781 / 782 with a count variance and 766 to 795 with a run variance above 1e-3
     sensitive   47 to 100 % of the moved jobs move by more than 100 tolerances; per point and getter at least 1 and up to 23 jobs do
 The store's coverage is random, and with the draw as it came a few boundary windows had a posterior so certain that no job could tell a
-cut at them from a cut one window off: geometry_cases.COV_AT sets the coverage of those nine windows by hand."""
+cut at them from a cut one window off: geometry_cases.COV_AT sets the coverage of those nine windows by hand.
+
+4. The inputs of the minimum-length decoder, the breakpoint getter and the long-run getter on this store can fail: the constrained
+   reference path differs from the unconstrained one in at least three chunks for every length set (all three cases' draws give them:
+   chunks 2, 7, 9, 10, 11, 12 for every set, chunk 3 as well for the first two; COV_AT is as it was), it equals path enumeration on
+   the chunks of at most 7 windows, at least half of the breakpoint jobs have a finite log_p_event, and at least half of the long-run
+   jobs have two values that are finite and not 0 (248 to 315 of 431)."""
 import numpy as np
 import pytest
 
+from test_bruteforce_cpu import Params
+from test_longrun_cpu import comparable
 import geometry_cases as G
+import breakpoint_ref as BR
+import minlen_ref
+import viterbi_ref
 import test_entropy_cpu as TE
 import test_moments_cpu as TM
 import test_runs_cpu as TR
 import entropy_ref as ER
 import interval_ref as IR
+import longrun_ref as LR
 import moments_ref as MR
 import runs_ref as RR
 
@@ -174,3 +186,81 @@ def test_every_boundary_point_matters(model_type, seed, name):
     print("case %d %s: %.0f%% of the jobs of at most %d windows move by more than 100 tolerances with an end point; per point %d-%d such jobs"
           % (seed, name, 100 * share, SHORT, counts.min(), counts.max()))
     assert not bad, bad
+
+
+# ---- 4. the minimum-length decoder, breakpoints and long runs --------------------------------------------------------------------------
+def _runs(path):
+    return 1 + int(np.sum(np.diff(np.asarray(path, np.int64)) != 0))
+
+
+@pytest.mark.parametrize("min_len", G.MINLEN_SETS)
+@pytest.mark.parametrize("model_type,seed", G.CASES)
+def test_min_length_reference_bites_and_equals_enumeration(model_type, seed, min_len):
+    store, model, alpha, _ = G.case(model_type, seed)
+    lab, score, plp, free = G.minlen_reference(model_type, seed, min_len)
+    assert np.array_equal(free, G.viterbi_reference(model_type, seed)[0])
+    assert minlen_ref.admissible(lab, OFF, min_len).all()
+    T = np.diff(OFF)
+    same = np.array([np.array_equal(lab[OFF[c]:OFF[c + 1]], free[OFF[c]:OFF[c + 1]]) for c in range(T.size)])
+    print("case %d min_len %s: the constrained path differs from the unconstrained one in chunks %s" % (seed, min_len, [int(c) for c in np.flatnonzero(~same)]))
+    assert np.sum(~same) >= 3
+    assert np.all(score <= plp(free) + 1e-9 * np.abs(score)) and np.all(score[~same] < plp(free)[~same])     # the constraint costs something there
+    if min_len == (16, 16, 16, 16):
+        # a chunk of at most 16 windows has no room for a run that touches neither end: an admissible path has at most two runs, so
+        # the unconstrained path stays where it has at most two (every one- and two-window chunk) and goes where it has more
+        kinds = set()
+        for c in np.flatnonzero(T <= 16):
+            two = _runs(free[OFF[c]:OFF[c + 1]]) <= 2
+            assert same[c] == two and _runs(lab[OFF[c]:OFF[c + 1]]) <= 2, c
+            kinds.add(bool(two))
+        assert same[T <= 2].all() and kinds == {True, False}
+    # path enumeration in 50 digits on the chunks of at most 7 windows (one, two and seven windows)
+    regions = model.numberOfRegions
+    P = Params(model.param_vector(), regions, 2 + seed % 3, model_type, alpha)
+    nbE = None
+    if model_type == G.CASES[2][0]:
+        p = model.params()
+        nbE = np.ctypeslib.as_array(p.nb_E, shape=(regions * 4 * viterbi_ref.NX,)).reshape(regions, 4, viterbi_ref.NX).copy()
+    small = np.flatnonzero(T <= 7)
+    assert sorted(T[small]) == [1, 1, 1, 1, 2, 2, 7]
+    clear = 0
+    for c in small:
+        path, best, second = minlen_ref.best_admissible(_weights(model_type, seed, int(c), P, nbE), min_len)
+        assert abs(score[c] - float(best)) <= 1e-12 * abs(float(best)), (c, score[c], best)
+        if best - second > 1e-9 * abs(best):
+            assert tuple(int(v) for v in lab[OFF[c]:OFF[c + 1]]) == path, (c, path)
+            clear += 1
+    assert clear >= small.size - 1
+
+
+_WEIGHTS = {}
+
+
+def _weights(model_type, seed, c, P, nbE):
+    """All 4^T paths of a small chunk with their weights, once for the three length sets."""
+    key = (model_type, seed, c)
+    if key not in _WEIGHTS:
+        store, model, _, _ = G.case(model_type, seed)
+        _WEIGHTS[key] = minlen_ref.chunk_path_weights(store, c, P, model, nbE)
+    return _WEIGHTS[key]
+
+
+@pytest.mark.parametrize("model_type,seed", G.CASES)
+def test_breakpoint_and_long_run_jobs_are_exercised(model_type, seed):
+    (F, L, U, V), events = G.breakpoint_reference(model_type, seed)
+    chunk = np.searchsorted(OFF, np.arange(G.N_WINDOWS), "right") - 1
+    assert np.all(F < L) and np.all(chunk[F] == chunk[L]) and not np.any(U & V)
+    finite = sum(bool(np.isfinite(BR.summary(e)[0])) for e in events)
+    print("case %d breakpoints: %d of %d jobs with a finite log_p_event" % (seed, finite, F.size))
+    assert 2 * finite >= F.size
+    f, l, m, k = G.longrun_jobs(model_type, seed)
+    assert np.all(f <= l) and m.min() >= 1 and m.max() <= 15 and k.min() >= 1
+    assert max(LR.lanes(int(a), int(b)) for a, b in zip(m, k)) <= 64
+    for j in (None, G.joins()):
+        none, some = G.longrun_reference(model_type, seed, G.joins_key(j))
+        busy = np.isfinite(none) & np.isfinite(some) & (none != 0.0) & (some != 0.0)
+        use = comparable(none) & comparable(some)
+        print("case %d long runs (%s): %d of %d jobs with both values finite and not 0, %.1f%% compared"
+              % (seed, "apart" if j is None else "joined", int(busy.sum()), f.size, 100.0 * use.mean()))
+        assert 2 * busy.sum() >= f.size and use.mean() >= 0.95
+    assert np.any(G.longrun_reference(model_type, seed, None)[1] != some)                 # the joins matter

@@ -1,6 +1,7 @@
 """The range getters (hf_get_interval_log_probs, hf_get_count_moments, hf_get_run_moments, hf_get_path_entropy, hf_get_path_log_probs,
-hf_get_entropy_profile, hf_get_posterior, hf_get_forward_backward), Viterbi and the sampler on track geometries and call sizes that no
-other store of the suite produces (tests/geometry_cases.py; tests/test_geometry_cpu.py checks the references and that every boundary
+hf_get_entropy_profile, hf_get_posterior, hf_get_forward_backward, hf_get_breakpoints, hf_get_breakpoint_profile,
+hf_get_long_run_log_probs), Viterbi, minimum-length Viterbi and the sampler on track geometries and call sizes that no other store of
+the suite produces (tests/geometry_cases.py; tests/test_geometry_cpu.py checks the references and that every boundary
 point matters):
 
 A. a chunk list laid against the getters' global piece grid (chunks that start or end on, one before and one after a multiple of 512,
@@ -12,7 +13,8 @@ D. windows outside every chunk: labels -1, every range getter refuses a job that
    the window arrays.
 
 Tolerances are those of the getters' own device tests (test_interval_gpu._close, ATOL / RTOL of test_moments_cpu, test_runs_cpu and
-test_entropy_cpu, test_posterior_gpu._check_values); -inf must agree exactly, the full mask gives exactly 0 / variance exactly 0.
+test_entropy_cpu, test_posterior_gpu._check_values, test_breakpoint_gpu._check, test_longrun_gpu._check, test_minlen_gpu._check and
+its TOL); -inf must agree exactly, the full mask gives exactly 0 / variance exactly 0.
 Every test prints its largest deviations before it asserts (pytest -s).  Measured on an MI355X (the largest over the cases, both
 algorithms, the launch variants and parts C and D; relative: over the values with |ref| > 1e-3, variances over those above 1e-3):
     interval        7.6e-10 absolute, 1.0e-9 relative (the Gaussian case, the same figure from both algorithms; the bound is the sum 1e-10 +
@@ -25,6 +27,10 @@ algorithms, the launch variants and parts C and D; relative: over the values wit
                     event of the sampler
     two batches     1 051 574 interval jobs (by pieces and by parts) and 265 142 jobs of the other getters: every value the bits of
                     the job asked alone
+    breakpoints     log_p_event 9.1e-13 absolute, p_k 4.0e-14, mode_p 9.4e-14, |sum p_k - 1| 2.2e-16 (86 jobs, 46 profiles)
+    long runs       2.3e-13 absolute over the 431 jobs, apart and joined
+    min-length      the reference's labels in every window for the three length sets (7, 7 and 6 chunks bite), an empty chunk's score
+                    exactly 0, labels exactly -1 outside the chunks
 All of it passed as the code stood, except part D: see test_windows_outside_every_chunk."""
 import ctypes as C
 import functools
@@ -42,8 +48,11 @@ import interval_ref as IR
 import moments_ref as MR
 import runs_ref as RR
 import sampling_ref as S
+import test_breakpoint_gpu as TB
 import test_entropy_gpu as TE
 import test_interval_gpu as TI
+import test_longrun_gpu as TL
+import test_minlen_gpu as TML
 import test_moments_gpu as TM
 import test_posterior_gpu as TP
 import test_runs_gpu as TR
@@ -122,14 +131,56 @@ def _check_getters(em, model_type, seed, what, shift=0, joined=None, sel=None):
     fw, bw, sc = em.forward_backward(shift, NW)
     g = fw * bw
     TP._check_values(g / g.sum(axis=1, keepdims=True), post_ref, what + " (f b)")
+    if sel is None:
+        check_breakpoints(em, model_type, seed, what, shift)
+        check_long_runs(em, model_type, seed, what, shift, joined)
     return iv
+
+
+def check_breakpoints(em, model_type, seed, what, shift=0, profile_every=3):
+    """hf_get_breakpoints on the breakpoint jobs of the case (G.breakpoint_reference) with the default quantiles and with none, and
+    hf_get_breakpoint_profile on every profile_every-th job and every two-window job, by test_breakpoint_gpu._check (its bounds)."""
+    (F, L, U, V), events = G.breakpoint_reference(model_type, seed)
+    TB._not_empty(events, what)
+    f, l = F + shift, L + shift
+    base = TB._check(em, f, l, U, V, events, what + " breakpoints", profiles=False)
+    none = em.breakpoints(f, l, U, V, [])
+    assert none[1].shape == (F.size, 0) and TB._same_bits([none[0], none[2], none[3]], [base[0], base[2], base[3]])
+    pick = np.flatnonzero((np.arange(F.size) % profile_every == 0) | (L - F == 1))
+    assert np.sum((L - F)[pick] == 1) >= 10
+    if profile_every > 1:
+        got = TB._check(em, f[pick], l[pick], U[pick], V[pick], [events[i] for i in pick], what + " breakpoint profiles")
+        assert TB._same_bits(got, [x[pick] for x in base])
+    else:
+        TB._check(em, f, l, U, V, events, what + " breakpoint profiles")
+    return base
+
+
+def check_long_runs(em, model_type, seed, what, shift=0, joined=None):
+    """hf_get_long_run_log_probs on the long-run jobs of the case without and with joins (joined: as _check_getters), by
+    test_longrun_gpu._check; returns the values per pair of joins."""
+    F, L, M, K = G.longrun_jobs(model_type, seed)
+    out = []
+    for jd, jr in ((None, None), (G.joins(), G.joins())) if joined is None else joined:
+        got = em.long_run_log_probs(F + shift, L + shift, M, K, jd)
+        ref = G.longrun_reference(model_type, seed, G.joins_key(jr))
+        TL._check(got, ref, what + " long runs " + ("apart" if jd is None else "joined"))
+        assert np.all(got[0] <= 0.0) and np.all(got[1] <= 0.0)
+        fin = np.isfinite(ref[0]) & TL.comparable(ref[0])
+        print("%s long runs %s: %d jobs, max |d log_p_none| %.3g" % (what, "apart" if jd is None else "joined", F.size,
+                                                                      float(np.max(np.abs(got[0][fin] - ref[0][fin]), initial=0.0))))
+        out.append(got)
+    return out
 
 
 def _check_decoders(em, model_type, seed, what, shift=0):
     """Viterbi against viterbi_ref.reference, SAMPLES samples against sampling_ref under the same uniforms; returns both.  The
     uniform of a draw is indexed by the window's global index, and that of a chunk's final state by n_windows + the chunk's index in
     the list (include/hmm_flagger_hip.h): the samples of a track with chunks without windows or with windows outside every chunk are
-    those of the reference on that chunk list, not those of the grid store."""
+    those of the reference on that chunk list, not those of the grid store.  Then hf_viterbi_minlen for the three length sets of
+    geometry_cases.MINLEN_SETS by test_minlen_gpu._check (admissible, and optimal by evaluation within its TOL: a label may differ
+    from the reference's only where both paths evaluate to the same score at that level); returns {min_len: (labels, chunk scores,
+    score)} last."""
     store, model, alpha, _ = G.case(model_type, seed)
     labels, chunk_ll, lp = em.viterbi(model)
     live = np.diff(np.asarray(em.store.chunk_off)) > 0
@@ -150,7 +201,22 @@ def _check_decoders(em, model_type, seed, what, shift=0):
     print("%s: viterbi labels equal to the reference's in %.4f%% of the windows, sampler near-tie events %d"
           % (what, 100.0 * np.mean(labels[shift:shift + NW] == G.viterbi_reference(model_type, seed)[0]), events))
     assert events <= 1
-    return labels, chunk_ll, got
+    outside = np.r_[0:shift, shift + NW:em.store.n_windows]
+    minlen = {}
+    for ml in G.MINLEN_SETS:
+        ref = G.minlen_reference(model_type, seed, ml)
+        lab, cll, lp = em.viterbi_minlen(model, ml)
+        bites = TML._check(store, ref, ml, (lab[shift:shift + NW], cll[live], lp))
+        assert bites >= 3, (ml, bites)
+        assert np.all(cll[~live] == 0.0) and np.all(lab[outside] == -1) and lab[shift:shift + NW].min() >= 0
+        differ = [c for c in range(OFF.size - 1) if not np.array_equal(lab[shift + OFF[c]:shift + OFF[c + 1]], ref[0][OFF[c]:OFF[c + 1]])]
+        print("%s: min-length labels %s: %d chunks bite, labels other than the reference's (ties by evaluation) in chunks %s" % (what, ml, bites, differ))
+        assert not np.array_equal(lab[shift:shift + NW], labels[shift:shift + NW])               # the constrained path is another one
+        minlen[ml] = (lab, cll, lp)
+    lab, cll = TML._viterbi_results(em)                     # three decoders, none overwrites another
+    assert np.array_equal(lab, labels) and np.array_equal(cll, chunk_ll)
+    assert np.array_equal(TML._sample_results(em, G.SAMPLES), got)
+    return labels, chunk_ll, got, minlen
 
 
 # ---- A. the grid store --------------------------------------------------------------------------------------------------------------
@@ -354,9 +420,15 @@ def test_chunks_without_windows(algo, stats_mode):
     assert np.all(np.abs(stats - stats0) <= 1e-9 * scale)
     assert np.array_equal(em.labels(), em0.labels())
     what = "empty chunks algo %d" % algo
-    vit, cll, smp = _check_decoders(em, model_type, seed, what)
+    vit, cll, smp, minlen = _check_decoders(em, model_type, seed, what)
     vit0, cll0, lp0 = em0.viterbi(model)
     assert np.array_equal(vit, vit0) and np.array_equal(cll[src >= 0], cll0) and np.all(cll[empty] == 0.0)
+    for ml, (mlab, mcll, mlp) in minlen.items():           # the minimum-length decoder: an empty chunk scores exactly 0
+        mlab0, mcll0, _ = em0.viterbi_minlen(model, ml)
+        assert np.array_equal(mlab, mlab0) and np.array_equal(mcll[src >= 0], mcll0) and np.all(mcll[empty] == 0.0), ml
+        ref_ll = np.zeros(est.n_chunks)
+        ref_ll[src >= 0] = G.minlen_reference(model_type, seed, ml)[1]
+        assert np.all(np.abs(mcll - ref_ll) <= TML.TOL * np.abs(ref_ll)) and abs(mlp - ref_ll.sum()) <= TML.TOL * abs(ref_ll.sum()), ml
     assert np.any(smp != em0.sample_paths(model, G.SAMPLES, G.SAMPLE_SEED + seed))       # (other uniforms for the final states: _check_decoders)
     # the getters: every job, and most of them span an empty chunk (one lies in front of window 0, one behind the last window)
     spans = np.zeros(F.size, bool)
@@ -405,9 +477,12 @@ def test_windows_outside_every_chunk(algo):
     lab = em.labels()
     assert np.all(lab[outside] == -1) and np.array_equal(lab[a:b], em0.labels())
     what = "uncovered windows algo %d" % algo
-    vit, cll, smp = _check_decoders(em, model_type, seed, what, shift=a)
+    vit, cll, smp, minlen = _check_decoders(em, model_type, seed, what, shift=a)
     vit0, cll0, _ = em0.viterbi(model)
     assert np.all(vit[outside] == -1) and np.array_equal(vit[a:b], vit0) and np.array_equal(cll, cll0)
+    for ml, (mlab, mcll, mlp) in minlen.items():           # the minimum-length decoder: -1 outside the chunks, the rest the grid store's
+        mlab0, mcll0, mlp0 = em0.viterbi_minlen(model, ml)
+        assert np.all(mlab[outside] == -1) and np.array_equal(mlab[a:b], mlab0) and np.array_equal(mcll, mcll0) and mlp == mlp0, ml
     assert np.all(smp[:, outside] == -1) and smp[:, a:b].min() >= 0      # (in-chunk samples: other uniforms than the compacted store's, _check_decoders)
     # every getter refuses a range that touches an uncovered window, and answers afterwards
     y = np.zeros(n, np.int64)
@@ -423,6 +498,10 @@ def test_windows_outside_every_chunk(algo):
         _refused(lambda: em.entropy_profile(f, cnt))
         _refused(lambda: em.posterior(f, cnt))
         _refused(lambda: em.forward_backward(f, cnt))
+        _refused(lambda: em.breakpoints([a, f], [a + 1, max(l, f + 1)], 1, 4))
+        _refused(lambda: em.breakpoint_profile(f, max(l, f + 1), 1, 4))
+        _refused(lambda: em.long_run_log_probs([a, f], [a + 1, l], 5, 2))
+        _refused(lambda: em.long_run_log_probs([a, f, a], [a, l, a], 5, 2, G.joins()))
     assert em.posterior(a, 0).shape == (0, 4) and em.posterior(n, 0).shape == (0, 4)      # no window: nothing to refuse
     _check_getters(em, model_type, seed, what, shift=a)
     assert np.array_equal(em.posterior(a, NW), em0.posterior())

@@ -11,7 +11,7 @@ import pytest
 
 from flagger_amd import _native as N
 from flagger_amd import hmm, synth
-from test_longrun_cpu import JOINS, LENGTHS, SMALL_SPAN, close, comparable, jobs, max_len, store_case
+from test_longrun_cpu import JOINS, LENGTHS, SMALL_SPAN, close, comparable, jobs, store_case
 from test_moments_cpu import TINY
 from test_viterbi_gpu import SIZES, _trained
 import geometry_cases as G
@@ -61,30 +61,23 @@ def test_small_stores_equal_reference(algo, model_type, seed, which):
 
 def test_grid_store_with_empty_chunks_and_uncovered_windows():
     """One chunk list of tests/geometry_cases.py: chunks on the 512 grid, the same with chunks that hold no window (an empty chunk ends a
-    group), and windows outside every chunk (refused)."""
+    group), and windows outside every chunk (refused).  The jobs and their reference are geometry_cases.longrun_jobs /
+    longrun_reference, the value checks test_geometry_gpu.check_long_runs (which holds every call to _check above): the geometry tests
+    run the same on both algorithms and in the launch variants."""
+    import test_geometry_gpu as TG                          # (here: that module imports this one)
     model_type, seed = G.CASES[0]
-    store, model, alpha, (F, L, M, _) = G.case(model_type, seed)
-    n_ = L - F + 1                                                         # every range of at most 48 windows (half of them span chunks), 20 long ones
-    pick = np.concatenate([np.flatnonzero(n_ <= 48), np.random.default_rng(7).choice(np.flatnonzero(n_ > 64), 20, replace=False)])
-    F, L, M = F[pick], L[pick], M[pick]
-    M = np.where(L - F + 1 > 64, (M & ~4) | ((M & ~4) == 0), M)            # (long ranges: the other labels, tests/test_longrun_cpu.py jobs)
-    K = np.minimum(np.random.default_rng(8).choice([1, 2, 3, 7, 16, 58], F.size), [max_len(m) for m in M])
-    A, end = G.rows(model_type, seed)
-    chain = LR.Chain(A, end, store.chunk_off)
+    store, model, alpha, _ = G.case(model_type, seed)
+    F, L, M, K = G.longrun_jobs(model_type, seed)
     em = hmm.EMList(store, model)
     hmm.EM_runOneIterationForList(em, model)
-    base = {}
-    for key, joins in (("none", None), ("contig", G.joins())):
-        base[key] = em.long_run_log_probs(F, L, M, K, joins)
-        _check(base[key], chain.log_probs(F, L, M, K, joins), key)
+    base = dict(zip(("none", "contig"), TG.check_long_runs(em, model_type, seed, "grid")))
     em.close()
     # chunks without windows: the values of the store without them, with the joins an empty chunk cuts
     est, src = G.with_empty_chunks(store)
     jd, jr = G.empty_chunk_joins(src, G.joins())
     em = hmm.EMList(est, model)
     hmm.EM_runOneIterationForList(em, model)
-    got = em.long_run_log_probs(F, L, M, K, jd)
-    _check(got, chain.log_probs(F, L, M, K, jr), "empty chunks")
+    TG.check_long_runs(em, model_type, seed, "empty chunks", joined=((jd, jr),))
     em.close()
     # windows outside every chunk
     ust = G.with_uncovered_windows(store, np.random.default_rng(5))
@@ -95,7 +88,7 @@ def test_grid_store_with_empty_chunks_and_uncovered_windows():
         with pytest.raises(N.HFError) as e:
             em.long_run_log_probs([a, f], [a + 1, l], 5, 2)
         assert e.value.code == N.HF_E_ARG
-    got = em.long_run_log_probs(F + a, L + a, M, K, G.joins())
+    got = TG.check_long_runs(em, model_type, seed, "uncovered windows", shift=a)[1]
     close(got[0], base["contig"][0]); close(got[1], base["contig"][1])
     em.close()
 

@@ -1,4 +1,5 @@
-"""The C ABI on caller-owned streams and in mixed call orders (DESIGN.md "Streams").
+"""The C ABI on caller-owned streams and in mixed call orders (DESIGN.md "Streams"): the pass, the thirteen getters (the breakpoint and
+long-run getters among them), hf_viterbi, hf_sample_paths, hf_viterbi_minlen and the batch.
 
 Every entry point that enqueues GPU work takes a `void *stream`; the getters run on the stream of the last pass.  Here the stream is a
 non-blocking one of the caller's (tests/hip_streams.py), and directly in front of every library call the caller enqueues filler work on
@@ -12,6 +13,7 @@ import ctypes as C
 import functools
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -45,12 +47,24 @@ KINDS = {
     "scan-chunks-3-sub-passes": (N.HF_ALGO_SCAN, N.HF_STATS_CHUNKS, {"HF_SUBPASSES": "3"}),
 }
 GETTERS = SQ.GETTERS
+NEW_GETTERS = ("breakpoints", "breakpoint_profile", "long_run_log_probs")
 SAMPLES, SAMPLE_SEED = 8, 20261019
+MIN_LEN = (3, 5, 1, 7)
+BP_MASKS = ((4, 11), (6, 9), (1, 2), (8, 4))      # disjoint (left, right) state sets: one state and several
+
+
+def _longrun_max_lanes():
+    """HF_LONGRUN_MAX_LANES as the header defines it."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    m = re.search(r"#define\s+HF_LONGRUN_MAX_LANES\s+(\d+)", open(os.path.join(root, "include", "hmm_flagger_hip.h")).read())
+    assert m
+    return int(m.group(1))
 
 
 class Jobs:
     """The arguments of the getters for one store: whole-track ranges, and sub-ranges across a chunk border and across a 512-window
-    border inside the longest chunk (the segment length of the scan path)."""
+    border inside the longest chunk (the segment length of the scan path).  The breakpoint jobs (bF < bL inside one chunk) and the
+    long-run jobs (F, L, M with the lengths K; `joins`: a chunk continues its predecessor on the same contig) are derived from them."""
 
     def __init__(self, store):
         off = np.asarray(store.chunk_off, np.int64)
@@ -76,6 +90,28 @@ class Jobs:
         self.ranges = [(0, n)] + _ranges(store)
         assert any(a0 < border < a0 + cnt for a0, cnt in self.ranges)                      # across a chunk border
         assert any(a0 < int(off[c]) + 512 < a0 + cnt <= int(off[c + 1]) for a0, cnt in self.ranges[1:])   # across a 512-window border
+        # breakpoints: the two-window job over the border first, across it, a whole chunk, the random ranges clipped to their chunk
+        bF = [int(off[c]) + 511, int(off[c]) + 500, int(off[c]) + 3, int(off[c])]
+        bL = [int(off[c]) + 512, int(off[c]) + 520, int(off[c]) + min(1100, int(T[c]) - 1), int(off[c + 1]) - 1]
+        for a0, b0 in zip(a, b):
+            k = int(np.searchsorted(off, a0, "right")) - 1
+            if T[k] < 2:                                   # (a one-window chunk holds no job)
+                continue
+            lo = min(int(a0), int(off[k + 1]) - 2)
+            bF.append(lo)
+            bL.append(max(lo + 1, min(int(b0), int(off[k + 1]) - 1)))
+        self.bF, self.bL = np.asarray(bF, np.int64), np.asarray(bL, np.int64)
+        assert self.bF.size >= 12 and np.all(self.bF < self.bL)
+        assert np.array_equal(np.searchsorted(off, self.bF, "right"), np.searchsorted(off, self.bL, "right"))      # one chunk
+        assert (self.bF[0], self.bL[0]) == (off[c] + 511, off[c] + 512) and (self.bF[3], self.bL[3]) == (off[c], off[c + 1] - 1)
+        self.bU, self.bV = (np.array([BP_MASKS[i % len(BP_MASKS)][k] for i in range(self.bF.size)], np.int64) for k in (0, 1))
+        assert not np.any(self.bU & self.bV)
+        # long runs: lanes(S, L) = (4 - |S|) + |S| (L - 1) + 4 of include/hmm_flagger_hip.h within HF_LONGRUN_MAX_LANES
+        self.K = np.array([(1, 2, 3, 7, 16)[i % 5] for i in range(self.F.size)], np.int64)
+        size = np.array([bin(int(m)).count("1") for m in self.M])
+        assert np.all((4 - size) + size * (self.K - 1) + 4 <= _longrun_max_lanes()) and set(self.K) == {1, 2, 3, 7, 16}
+        ctg = list(store.chunk_ctg)
+        self.joins = np.array([k > 0 and ctg[k] == ctg[k - 1] for k in range(T.size)], bool)
 
 
 @functools.lru_cache(maxsize=None)
@@ -140,6 +176,12 @@ def _getter_calls(em, kind, J):
         return [_call(em.entropy_profile, a, c) for a, c in J.ranges]
     if kind == "alpha_stats":
         return [_call(em.alpha_stats)]
+    if kind == "breakpoints":
+        return [_call(em.breakpoints, J.bF, J.bL, J.bU, J.bV), _call(em.breakpoints, J.bF, J.bL, J.bU, J.bV, ())]
+    if kind == "breakpoint_profile":
+        return [_call(em.breakpoint_profile, int(J.bF[i]), int(J.bL[i]), int(J.bU[i]), int(J.bV[i])) for i in (0, 1, 5)]
+    if kind == "long_run_log_probs":
+        return [_call(em.long_run_log_probs, J.F, J.L, J.M, J.K), _call(em.long_run_log_probs, J.F, J.L, J.M, J.K, J.joins)]
     raise KeyError(kind)
 
 
@@ -152,6 +194,11 @@ def _equal(a, b, what):
         for k, (x, y) in enumerate(zip(xa, xb)):
             assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), \
                 (what, "call %d, array %d" % (i, k), int(np.sum(x != y)) if x.shape == y.shape else (x.shape, y.shape))
+
+
+def _differ(a, b):
+    """Two records of the same calls hold an array that is not bitwise the other's."""
+    return any(not np.array_equal(x, y) for (_, xa), (_, xb) in zip(a, b) for x, y in zip(xa, xb))
 
 
 def _codes(calls):
@@ -257,6 +304,60 @@ class Side:
             assert L.hf_get_sample_labels(em._h, k, out[k].ctypes.data_as(C.POINTER(C.c_int8))) == N.HF_OK
         return N.HF_OK, (out,)
 
+    def viterbi_minlen(self, em, model, s=None, min_len=MIN_LEN):
+        """hf_viterbi_minlen + hf_viterbi_minlen_finish on stream `s` (default: the context's) and its getters: (code, (labels, chunk
+        scores, score))."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        p, lp = model.params(), C.c_double(0.0)
+        ml = (C.c_int32 * 4)(*min_len)
+        self.delay(s)
+        rc = L.hf_viterbi_minlen(em._h, C.byref(p), ml, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.assert_busy(s, "hf_viterbi_minlen")
+        rc = L.hf_viterbi_minlen_finish(em._h, C.byref(lp), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        self.delay(s)
+        r1 = L.hf_get_viterbi_minlen_labels(em._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
+        r2 = L.hf_get_viterbi_minlen_chunk_log_probs(em._h, ll.ctypes.data_as(C.POINTER(C.c_double)))
+        assert r1 == N.HF_OK and r2 == N.HF_OK
+        return N.HF_OK, (labels, ll, np.float64(lp.value))
+
+    def decoder(self, em, which, model, s=None):
+        return {"viterbi": self.viterbi, "sample": self.sample, "viterbi_minlen": self.viterbi_minlen}[which](em, model, s)
+
+    def stored(self, em, which, s=None):
+        """What the getters of decoder `which` answer now, behind a delay: (code, arrays) with the arrays in the order of the decoder's
+        own record (its score, a value of the finish call, is not stored)."""
+        L = N.lib()
+        self.delay((em.stream.value or 0) if s is None else s)
+        if which == "sample":
+            out = np.empty((SAMPLES, self.store.n_windows), dtype=np.int8)
+            for k in range(SAMPLES):
+                rc = L.hf_get_sample_labels(em._h, k, out[k].ctypes.data_as(C.POINTER(C.c_int8)))
+                if rc != N.HF_OK:
+                    return int(rc), ()
+            return N.HF_OK, (out,)
+        get_labels, get_ll = (L.hf_get_viterbi_labels, L.hf_get_viterbi_chunk_log_probs) if which == "viterbi" else \
+            (L.hf_get_viterbi_minlen_labels, L.hf_get_viterbi_minlen_chunk_log_probs)
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        r1 = get_labels(em._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
+        r2 = get_ll(em._h, ll.ctypes.data_as(C.POINTER(C.c_double)))
+        if r1 != N.HF_OK or r2 != N.HF_OK:
+            return int(r1 or r2), ()
+        return N.HF_OK, (labels, ll)
+
+
+def _stored_equals(stored, returned, what):
+    """A decoder's stored results against the record of the call that made them."""
+    (code, arrays), (rcode, rarrays) = stored, returned
+    assert code == rcode == N.HF_OK, (what, code, rcode)
+    _equal([(code, arrays)], [(rcode, rarrays[:len(arrays)])], what)
+
 
 def _run_both(name, kind, monkeypatch, scenario, n_streams=1, non_blocking=True):
     """`scenario(side)` -> {tag: [(code, arrays)]} on the caller's streams and on the null stream: the two records are equal.  Returns the
@@ -355,7 +456,10 @@ def _getters_of(side):
 def test_getters_first_and_second_call(name, kind, monkeypatch):
     def scenario(side):
         em = side.context(alpha_stats=True)
-        rec = {"pass a": [side.estep(em, _model(name, "a"))], "pass b": [side.estep(em, _model(name, "b"))]}
+        rec = {"pass a": [side.estep(em, _model(name, "a"))]}
+        for g in NEW_GETTERS:
+            rec[g + ", after pass a"] = side.getter(em, g)          # (their lazy state is in place, for pass a, when pass b runs)
+        rec["pass b"] = [side.estep(em, _model(name, "b"))]
         for g in _getters_of(side):
             rec[g + ", first call"] = side.getter(em, g)            # builds the getter's lazy state
             rec[g + ", second call"] = side.getter(em, g)           # uses it
@@ -366,6 +470,8 @@ def test_getters_first_and_second_call(name, kind, monkeypatch):
         assert all(c == N.HF_OK for c in _codes(calls)), (tag, _codes(calls))
         if tag.endswith("first call"):
             _equal(calls, rec[tag.replace("first", "second")], tag)
+    for g in NEW_GETTERS:                                           # a getter that answers for the wrong pass is told apart
+        assert _differ(rec[g + ", first call"], rec[g + ", after pass a"]), g
     whole = rec["posterior, first call"][0][1][0]
     assert np.array_equal(whole.argmax(axis=1).astype(np.int8), rec["labels, first call"][0][1][0])
     for (a, c), (_, part) in zip(_input(name)[7].ranges, rec["posterior, first call"]):
@@ -395,8 +501,9 @@ def test_each_getter_as_the_first_after_the_pass(name, kind, monkeypatch):
 @pytest.mark.parametrize("where", ["same-stream", "second-stream"])
 @pytest.mark.parametrize("name,kind", CASES)
 def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
-    """hf_viterbi and hf_sample_paths with parameters other than the pass's, on the pass's stream or on a second non-blocking stream:
-    their own results, and afterwards every getter still answers for the pass — its first (lazy) call included."""
+    """hf_viterbi, hf_sample_paths and hf_viterbi_minlen with parameters other than the pass's, on the pass's stream or on a second
+    non-blocking stream: their own results, afterwards every getter still answers for the pass — its first (lazy) call included —
+    and each decoder's stored results are its own: three decoders, none overwrites another."""
     def scenario(side):
         ma, mb = _model(name, "a"), _model(name, "b")
         s2 = side.streams[1] if where == "second-stream" else None
@@ -404,12 +511,16 @@ def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
         rec = {"pass b": [side.estep(em, mb)]}
         rec["viterbi a"] = [side.viterbi(em, ma, s2)]
         rec["sample a"] = [side.sample(em, ma, s2)]
+        rec["viterbi_minlen a"] = [side.viterbi_minlen(em, ma, s2)]
         for g in _getters_of(side):
             rec[g + " after the decoders"] = side.getter(em, g)
         rec["viterbi a again"] = [side.viterbi(em, ma, s2)]
         rec["sample a again"] = [side.sample(em, ma, s2)]
+        rec["viterbi_minlen a again"] = [side.viterbi_minlen(em, ma, s2)]
         for g in _getters_of(side):
             rec[g + " after the decoders again"] = side.getter(em, g)
+        for d in SQ.DECODERS:
+            rec[d + " stored"] = [side.stored(em, d, s2)]
         # what the getters must still answer: the pass alone, on a context that never decoded
         alone = side.context(alpha_stats=True)
         rec["alone pass b"] = [side.estep(alone, mb)]
@@ -422,6 +533,10 @@ def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
     assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls)), {t: _codes(c) for t, c in rec.items()}
     _equal(rec["viterbi a"], rec["viterbi a again"], "viterbi")
     _equal(rec["sample a"], rec["sample a again"], "sample")
+    _equal(rec["viterbi_minlen a"], rec["viterbi_minlen a again"], "viterbi_minlen")
+    assert not np.array_equal(rec["viterbi_minlen a"][0][1][0], rec["viterbi a"][0][1][0])         # the constraint bites
+    for d in SQ.DECODERS:
+        _stored_equals(rec[d + " stored"][0], rec[d + " a again"][0], d + " stored")
     assert not np.array_equal(rec["viterbi a"][0][1][0], rec["viterbi b alone"][0][1][0])          # (the decoders' model is another one)
     for g in GETTERS:
         if g + " alone" in rec:
@@ -430,16 +545,17 @@ def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
 
 
 # ---- d. mixed orders ----------------------------------------------------------------------------------------------------------------
-def _mixed_scenario(side, seed):
+def _mixed_scenario(side, seed, generation=1):
     """One sequence of tests/stream_sequences.py on a context; after every getter, the same getter on a FRESH context that ran only the last
-    pass (with the switches as they stood then, and as they stand now for the getter)."""
+    pass (with the switches as they stood then, and as they stand now for the getter).  At the end every decoder's stored results are
+    read again: they are what that decoder returned at its last call in the sequence."""
     name = side.name
     scan = KINDS[side.kind][0] == N.HF_ALGO_SCAN
     base_mode = KINDS[side.kind][1]
     other_mode = {N.HF_STATS_ROWS: N.HF_STATS_CHUNKS, N.HF_STATS_CHUNKS: N.HF_STATS_ROWS}.get(base_mode)
     models = {"pass_a": _model(name, "a"), "pass_b": _model(name, "b")}
     em = side.context()
-    rec, fresh_cache = {}, {}
+    rec, fresh_cache, last_decoded = {}, {}, {}
     last_model = "pass_a"
 
     def run_pass(ctx, op, which):
@@ -469,7 +585,7 @@ def _mixed_scenario(side, seed):
         return fresh_cache[key]
 
     fwd_model = "pass_a"
-    for i, (op, st) in enumerate(SQ.replay(SQ.sequence(seed))):
+    for i, (op, st) in enumerate(SQ.replay(SQ.sequence(seed, generation))):
         tag = "%02d %s" % (i, op)
         if op in ("pass_a", "pass_b"):
             rec[tag] = [run_pass(em, op, None)]
@@ -485,7 +601,8 @@ def _mixed_scenario(side, seed):
             rec[tag] = [_call(em.set_alpha_stats, op == "alpha_on")]
         elif op in SQ.DECODERS:
             other = models["pass_b" if last_model == "pass_a" else "pass_a"]                     # parameters other than the last pass's
-            rec[tag] = [side.viterbi(em, other) if op == "viterbi" else side.sample(em, other)]
+            rec[tag] = [side.decoder(em, op, other)]
+            last_decoded[op] = tag
         else:
             got = side.getter(em, op)
             rec[tag] = got
@@ -499,17 +616,26 @@ def _mixed_scenario(side, seed):
                 assert _codes(got) == [N.HF_OK], (tag, _codes(got))
             else:
                 assert _codes(got) == [N.HF_E_ARG], (tag, _codes(got))
+    for op, tag in last_decoded.items():
+        rec["stored " + op] = [side.stored(em, op)]
+        _stored_equals(rec["stored " + op][0], rec[tag][0], "the stored results of %s at the end" % tag)
     return rec
 
 
-MIXED = [pytest.param("config2", k, s, id="config2-%s-seed%d" % (k, s)) for k in KINDS for s in SQ.SEEDS] + \
-        [pytest.param(n, k, SQ.SEEDS[i % len(SQ.SEEDS)], id="%s-%s-seed%d" % (n, k, SQ.SEEDS[i % len(SQ.SEEDS)]))
+def _mixed_cases(generation, tag):
+    seeds = SQ.GENERATIONS[generation][3]
+    return [pytest.param("config2", k, generation, s, id="config2-%s-%sseed%d" % (k, tag, s)) for k in KINDS for s in seeds] + \
+        [pytest.param(n, k, generation, seeds[i % len(seeds)], id="%s-%s-%sseed%d" % (n, k, tag, seeds[i % len(seeds)]))
          for i, (n, k) in enumerate((n, k) for n in ("sizes", "regions", "negative_binomial") for k in ("seq", "scan-rows", "scan-chunks-3-sub-passes"))]
 
 
-@pytest.mark.parametrize("name,kind,seed", MIXED)
-def test_mixed_orders(name, kind, seed, monkeypatch):
-    _run_both(name, kind, monkeypatch, lambda side: _mixed_scenario(side, seed))
+# generation 1: the ten getters and two decoders its seeds were chosen with; generation 2: all thirteen getters and three decoders
+MIXED = _mixed_cases(1, "") + _mixed_cases(2, "gen2-")
+
+
+@pytest.mark.parametrize("name,kind,generation,seed", MIXED)
+def test_mixed_orders(name, kind, generation, seed, monkeypatch):
+    _run_both(name, kind, monkeypatch, lambda side: _mixed_scenario(side, seed, generation))
 
 
 # ---- e. two contexts, two streams ------------------------------------------------------------------------------------------------------
@@ -636,7 +762,8 @@ def test_after_a_failed_pass(kind):
                          "interval_log_probs": (em.interval_log_probs, F, L_, M), "count_moments": (em.count_moments, F, L_, M),
                          "run_moments": (em.run_moments, F, L_, M), "path_entropy": (em.path_entropy, F, L_),
                          "path_log_probs": (em.path_log_probs, F, L_, np.full(n, 2, np.int8)), "entropy_profile": (em.entropy_profile,),
-                         "alpha_stats": (em.alpha_stats,)}
+                         "alpha_stats": (em.alpha_stats,), "breakpoints": (em.breakpoints, F, np.array([3, 40]), 1, 4),
+                         "breakpoint_profile": (em.breakpoint_profile, 5, 40, 1, 4), "long_run_log_probs": (em.long_run_log_probs, F, L_, M, 2)}
                 assert sorted(calls) == sorted(GETTERS)
                 for g in GETTERS:
                     h.delay(s)
