@@ -78,6 +78,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"runBoundaries", no_argument, nullptr, 1018},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
     {"keptBlocks", no_argument, nullptr, 1020},                 // exact probability of a block --minimumLengths would keep (hf_get_long_run_log_probs)
     {"enforceMinimumLengths", no_argument, nullptr, 1019},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
+    {"constrainedPosterior", no_argument, nullptr, 1021},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -170,7 +171,14 @@ static void usage(const char* program) {
             "                                      probability that the scope holds a block of the label long enough to be kept (lengths in windows\n"
             "                                      as for --enforceMinimumLengths: ceil(length / windowLen), at least 1; Hap: 1; at most 58 windows),\n"
             "                                      runs merged across the chunks of a contig as the final BED merges them; one GPU, not with\n"
-            "                                      --gpus N>1 or --sweepAlpha\n");
+            "                                      --gpus N>1 or --sweepAlpha\n"
+            "         --constrainedPosterior       with --minimumLengths: after the final inference, write admissible_mass.tsv: the four lengths in\n"
+            "                                      windows (as for --enforceMinimumLengths: ceil(length / windowLen), at least 1; Hap: 1; at most 64\n"
+            "                                      in sum), then for the whole track and every contig the chunks, the windows and the log of the\n"
+            "                                      posterior probability that every run meets its length (runs at a chunk's ends are exempt; chunks\n"
+            "                                      are independent, their logs add), and posterior_prediction_min_lengths.bed: the posterior BED of\n"
+            "                                      -P given that the path meets the lengths; the final labels and every other output stay as they\n"
+            "                                      are; one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -231,6 +239,12 @@ struct Run {
         int rc = hf_viterbi_minlen(ctx, &p, min_len, nullptr);
         if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
         return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
+    }
+    int minlen_posterior(hfm_model* m, const int32_t min_len[4], double* log_mass_total) {
+        hf_params p;
+        hfm_params(m, &p);
+        const int rc = hf_minlen_posterior(ctx, &p, min_len, nullptr);
+        return rc != HF_OK ? rc : hf_minlen_posterior_finish(ctx, log_mass_total, nullptr);
     }
     int posterior(int64_t first, int64_t n, double* out) {
         return multi ? hf_multi_get_posterior(multi, first, n, out) : hf_get_posterior(ctx, first, n, out);
@@ -890,6 +904,51 @@ static int write_kept_blocks(hf_ctx* ctx, const hfio_table* tab, const std::vect
     return HF_OK;
 }
 
+// --constrainedPosterior: the posterior under --minimumLengths (hf_minlen_posterior, run by the caller) and the mass the rule keeps.
+//   admissible_mass.tsv                      a header line and a line with the four lengths in windows; then a header line and one row for
+//                                            the whole track ("all") and one per contig (order of first appearance in the chunk list):
+//                                            chunks, windows, log_mass = the chunks' log P(path admissible | data) summed in list order.
+//   posterior_prediction_min_lengths.bed     hfio_write_posterior_bed with the constrained posterior and its argmax labels
+static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32_t minLenWindows[4], const std::string& dir) {
+    const int64_t N = hfio_n_windows(tab);
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<double> mass((size_t) std::max(C, 1));
+    int rc = hf_get_minlen_chunk_log_mass(ctx, mass.data(), nullptr);
+    if (rc != HF_OK) return rc;
+    struct Row { std::string name; int chunks; int64_t n; double log_mass; };
+    std::vector<Row> rows;
+    rows.push_back(Row{"all", 0, 0, 0.0});
+    std::map<std::string, size_t> ctgRow;
+    for (int c = 0; c < C; c++) {
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        auto it = ctgRow.find(ctg);
+        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{ctg, 0, 0, 0.0}); }
+        for (size_t ri : {(size_t) 0, it->second}) {
+            Row& r = rows[ri];
+            r.chunks++;
+            r.n += w.chunk_off[c + 1] - w.chunk_off[c];
+            r.log_mass += mass[(size_t) c];
+        }
+    }
+    const std::string tp = dir + "/admissible_mass.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\n%d\t%d\t%d\t%d\n", minLenWindows[0], minLenWindows[1],
+            minLenWindows[2], minLenWindows[3]);
+    fprintf(f, "#scope\tchunks\twindows\tlog_mass\n");
+    for (const Row& r : rows) fprintf(f, "%s\t%d\t%ld\t%.17g\n", r.name.c_str(), r.chunks, (long) r.n, r.log_mass + 0.0);
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    std::vector<double> post((size_t) N * 4);
+    std::vector<int8_t> lab((size_t) N);
+    if ((rc = hf_get_minlen_posterior(ctx, 0, N, post.data())) != HF_OK) return rc;
+    if ((rc = hf_get_minlen_posterior_labels(ctx, lab.data())) != HF_OK) return rc;
+    const std::string pp = dir + "/posterior_prediction_min_lengths.bed";
+    if (hfio_write_posterior_bed(tab, post.data(), lab.data(), pp.c_str()) != 0) { hf_cli_set_error(pp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --jointEntropy: exact path entropy and log-probability of the final labels (hf_get_path_entropy, hf_get_path_log_probs,
 // hf_get_entropy_profile) under the model of the last full pass.
 //   path_uncertainty.tsv   one row per scope.  Scopes: "all" and every contig by name (order of first appearance in the chunk list; chunks
@@ -998,7 +1057,7 @@ int main(int argc, char* argv[]) {
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
     double initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, keptBlocks = false, minLenGiven = false;
+    bool viterbi = false, enforceMinLen = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
@@ -1113,6 +1172,7 @@ int main(int argc, char* argv[]) {
             case 1017: jointEntropy = true; break;
             case 1019: enforceMinLen = true; break;
             case 1020: keptBlocks = true; break;
+            case 1021: constrainedPost = true; break;
             case 1010: regionProbsPath = optarg; break;
             case 1011: fitAlpha = true; break;
             case 1012: {                                         // pre,state[:pre,state...]
@@ -1234,6 +1294,12 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] Error: --keptBlocks runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
+    // --constrainedPosterior: likewise
+    if (constrainedPost && !minLenGiven) { fprintf(stderr, "[%s] Error: --constrainedPosterior needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
+    if (constrainedPost && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --constrainedPosterior runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
     if (!inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return EXIT_FAILURE; }
     if (convergenceTol <= 0.0 || convergenceTol > 1.0) {
         fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), convergenceTol);
@@ -1288,12 +1354,12 @@ int main(int argc, char* argv[]) {
                         HF_LONGRUN_MAX_LANES - 6);
                 return false;
             }
-        if (!enforceMinLen || sum <= HF_MINLEN_MAX_LANES) return true;
-        fprintf(stderr, "[%s] Error: --enforceMinimumLengths: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
-                ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
+        if (!(enforceMinLen || constrainedPost) || sum <= HF_MINLEN_MAX_LANES) return true;
+        fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
+                ts(), enforceMinLen && constrainedPost ? "enforceMinimumLengths, --constrainedPosterior" : enforceMinLen ? "enforceMinimumLengths" : "constrainedPosterior", minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
         return false;
     };
-    if ((enforceMinLen || keptBlocks) && !min_len_windows(windowLen)) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks || constrainedPost) && !min_len_windows(windowLen)) return EXIT_FAILURE;
     if (0.5 < initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return EXIT_FAILURE; }
 
     // 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
@@ -1325,7 +1391,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), hfio_n_chunks(tab), (long) N, hfio_window_len(tab));
     if (N == 0 || hfio_n_chunks(tab) == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return EXIT_FAILURE; }
 
-    if ((enforceMinLen || keptBlocks) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks || constrainedPost) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
     phase("load input (+ HIP start-up)");
     // 2. number of collapsed components (hmm_flagger.c:1008-1022)
     hf_windows w;
@@ -1635,6 +1701,16 @@ int main(int argc, char* argv[]) {
         const double t0 = real_time();
         if ((rc = write_kept_blocks(run.ctx, tab, regionProbsPath ? &regions : nullptr, minLenWindows, labelNames, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] kept_block_probabilities.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
+    }
+    // --constrainedPosterior: likewise (a decoder of its own: it reads the final parameters, not the last pass)
+    if (constrainedPost) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --constrainedPosterior needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        const double t0 = real_time();
+        double logMass = 0.0;
+        if ((rc = run.minlen_posterior(model, minLenWindows, &logMass)) != HF_OK) return die(rc);
+        if ((rc = write_constrained_posterior(run.ctx, tab, minLenWindows, dir)) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
+                ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], logMass, (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

@@ -466,6 +466,16 @@ struct DevBuf {
     }
 };
 
+// posteriors under minimum run lengths (hf_minlen_post.h): rows in window order; the forward lanes [N][sum of the lengths] are sized by
+// the lengths of a call, grown on demand and never shrunk
+struct MinLenPosterior : Decoder {
+    DevBuf fwd;
+    double* d_post = nullptr; int8_t* d_label = nullptr;
+    double* d_lz = nullptr;                    // [2][C]: log Z_adm, log Z
+    std::vector<double> h_lz;                  // ... of the last finished run
+    void release() { fwd.release(); Decoder::release(); }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -482,12 +492,13 @@ struct AlphaStats {
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
 // the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer, the entropy getters' buffers, the breakpoint
-// getter's and the long-run getter's
+// getter's and the long-run getter's, the buffers of the posterior under minimum run lengths
 struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
     MinLenViterbi mlv;
+    MinLenPosterior mlp;
     Sampler smp;
     DevBuf iv;                // hf_interval.h: pieces, parts, piece products, results
     AlphaStats al;
@@ -1007,6 +1018,7 @@ void hf_destroy(hf_ctx* ctx) {
     pass_destroy(ctx->pass);
     ctx->vit.release();
     ctx->mlv.release();
+    ctx->mlp.release();
     ctx->smp.release();
     ctx->iv.release();
     ctx->al.release();
@@ -3095,6 +3107,118 @@ int hf_get_long_run_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
             if (log_p_some_host) log_p_some_host[j] = some;
         }
         j0 = j1;
+    }
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// posteriors under minimum run lengths (hf_minlen_post.h): the sum-product twin of hf_viterbi_minlen, a decoder of its own with one code
+// path for both kinds of context.  Last in the file, its kernels included, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_post.h"
+
+// every device array of the decoder but the forward lanes (their size depends on the lengths of a call: MinLenPosterior::fwd)
+template <class F> static void mlp_arrays(const Track& tr, MinLenPosterior& v, F&& f) {
+    f(v.d_params, tr.params_bytes); f(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(v.d_rows, (size_t) tr.N * 128); f(v.d_flags, 4);
+    f(v.d_post, (size_t) tr.N * 32); f(v.d_label, (size_t) tr.N); f(v.d_lz, (size_t) tr.C * 16);
+}
+
+int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    const std::string w = "hf_minlen_posterior";
+    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
+    int64_t lanes = 0;
+    for (int s = 0; s < 4; s++) {
+        if (min_len[s] < 1) return set_err(HF_E_ARG, w + ": every minimum length must be >= 1");
+        lanes += min_len[s];
+    }
+    if (lanes > HF_MINLEN_MAX_LANES)
+        return set_err(HF_E_ARG, w + ": the minimum lengths sum to " + std::to_string(lanes) + ", above HF_MINLEN_MAX_LANES (64)");
+    const Track& tr = ctx->tr;
+    MinLenPosterior& v = ctx->mlp;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(hipSetDevice(tr.device));
+    if (v.launched) HIPCHK(hipDeviceSynchronize());
+    v.launched = false; v.done = false;
+    // the forward lanes: what the decoder holds of them already counts as free
+    const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
+    if (f_bytes > v.fwd.cap) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        if ((double) f_bytes > 0.9 * ((double) free_b + (double) v.fwd.cap))
+            return set_err(HF_E_ARG, w + ": the forward lanes need " + std::to_string(f_bytes) + " bytes (n_windows x sum of the lengths x 8), above nine tenths of the free device memory");
+    }
+    int rc = dec_alloc(tr, v, [&](auto&& f) { mlp_arrays(tr, v, f); });
+    if (rc) return rc;
+    if ((rc = v.fwd.reserve(f_bytes, w))) return rc;
+    rc = pack_params(tr, p, v.h_params);
+    if (rc) return rc;
+    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
+    if (nbm) {
+        if (!p->nb_E) return set_err(HF_E_ARG, w + ": negative_binomial needs hf_params.nb_E");
+        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
+            return set_err(HF_E_ARG, w + ": the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
+        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_lz, 0, (size_t) tr.C * 16, st));   // (chunks without windows: log Z_adm = log Z = 0)
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    if (dec_work(tr)) {
+        double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
+        hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params,
+                           nbm ? v.d_nbE : nullptr, v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows,
+                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_lz, v.d_flags);
+        hipLaunchKernelGGL(k_mlp_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
+                           (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_post, v.d_label, v.d_flags);
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_minlen_posterior_finish(hf_ctx* ctx, double* log_mass_total_host, void* stream) {
+    if (!ctx || !ctx->mlp.launched) return set_err(HF_E_ARG, "hf_minlen_posterior_finish: no hf_minlen_posterior to finish");
+    const Track& tr = ctx->tr;
+    MinLenPosterior& v = ctx->mlp;
+    const int rc = dec_finish(tr, v, stream);
+    if (rc) return rc;
+    v.h_lz.assign((size_t) tr.C * 2, 0.0);
+    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_lz.data(), v.d_lz, (size_t) tr.C * 16, hipMemcpyDeviceToHost));
+    double tot = 0.0;
+    for (int64_t c = 0; c < tr.C; c++) tot += v.h_lz[(size_t) c] - v.h_lz[(size_t) (tr.C + c)];   // chunk-list order
+    if (log_mass_total_host) *log_mass_total_host = tot;
+    v.done = true;
+    return HF_OK;
+}
+
+int hf_get_minlen_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_host) {
+    const std::string w = "hf_get_minlen_posterior";
+    if (!ctx || !post_host || !ctx->mlp.done) return set_err(HF_E_ARG, w + ": no finished hf_minlen_posterior");
+    const Track& tr = ctx->tr;
+    if (first < 0 || n < 0 || first + n > tr.N) return set_err(HF_E_ARG, w + ": bad range");
+    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, w + ": the range holds a window outside every chunk");
+    HIPCHK(hipSetDevice(tr.device));
+    if (n > 0) HIPCHK(hipMemcpy(post_host, ctx->mlp.d_post + first * 4, (size_t) n * 32, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_minlen_posterior_labels(hf_ctx* ctx, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->mlp.done) return set_err(HF_E_ARG, "hf_get_minlen_posterior_labels: no finished hf_minlen_posterior");
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mlp.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_minlen_chunk_log_mass(hf_ctx* ctx, double* log_mass_host, double* log_z_adm_host) {
+    if (!ctx || !log_mass_host || !ctx->mlp.done) return set_err(HF_E_ARG, "hf_get_minlen_chunk_log_mass: no finished hf_minlen_posterior");
+    const Track& tr = ctx->tr;
+    const std::vector<double>& z = ctx->mlp.h_lz;
+    for (int64_t c = 0; c < tr.C; c++) {
+        log_mass_host[c] = z[(size_t) c] - z[(size_t) (tr.C + c)];
+        if (log_z_adm_host) log_z_adm_host[c] = z[(size_t) c];
     }
     return HF_OK;
 }

@@ -573,6 +573,26 @@ class EMList:
         N.check(self._L.hf_get_viterbi_minlen_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_minlen_chunk_log_probs")
         return labels, ll, float(lp.value)
 
+    def minlen_posterior(self, model: HMM, min_len) -> "MinLenPosterior":
+        """The posterior given that every run has at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at a chunk's
+        ends are exempt; hf_minlen_posterior + hf_minlen_posterior_finish), and the posterior mass the rule keeps.  The last pass's
+        results, viterbi()'s, viterbi_minlen()'s and the sampler's are left as they were."""
+        ml = np.asarray(min_len)
+        if ml.shape != (4,):
+            raise ValueError("minlen_posterior: min_len holds four window counts (Err, Dup, Hap, Col)")
+        ml = np.ascontiguousarray(ml, dtype=np.int32)
+        p = model.params()
+        tot = C.c_double(0.0)
+        self._mlp_run = getattr(self, "_mlp_run", 0) + 1     # (older results stop answering posterior(): the context holds one run)
+        N.check(self._L.hf_minlen_posterior(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_minlen_posterior")
+        N.check(self._L.hf_minlen_posterior_finish(self._h, C.byref(tot), self.stream), "hf_minlen_posterior_finish")
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        N.check(self._L.hf_get_minlen_posterior_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_minlen_posterior_labels")
+        mass = np.empty(self.store.n_chunks, dtype=np.float64)
+        lza = np.empty(self.store.n_chunks, dtype=np.float64)
+        N.check(self._L.hf_get_minlen_chunk_log_mass(self._h, _dptr(mass), _dptr(lza)), "hf_get_minlen_chunk_log_mass")
+        return MinLenPosterior(self, labels, mass, lza, float(tot.value))
+
     @property
     def sample_capacity(self) -> int:
         """Samples one hf_sample_paths call may draw (nine tenths of the free device memory; hf_sample_capacity)."""
@@ -833,6 +853,42 @@ def EM_runMinLengthViterbiForList(emList, model: HMM, min_len):
     if not hasattr(emList, "viterbi_minlen"):
         raise TypeError("EM_runMinLengthViterbiForList: %s has no minimum-run-length decoder" % type(emList).__name__)
     return emList.viterbi_minlen(model, min_len)
+
+
+class MinLenPosterior:
+    """What EMList.minlen_posterior returns: `labels` (first-max argmax of the constrained posterior, -1 outside chunks),
+    `chunk_log_mass` (log P(path of the chunk admissible | data)), `chunk_log_z_adm`, `log_mass` (the sum over chunks in list order)
+    and posterior(first, n), which reads the context's buffers: it answers until the list's next minlen_posterior call or close(),
+    and raises RuntimeError afterwards."""
+
+    def __init__(self, em, labels, chunk_log_mass, chunk_log_z_adm, log_mass):
+        self._em = em
+        self._run = em._mlp_run
+        self.labels = labels
+        self.chunk_log_mass = chunk_log_mass
+        self.chunk_log_z_adm = chunk_log_z_adm
+        self.log_mass = log_mass
+
+    def posterior(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """P(s_t = s | data, path admissible) of windows [first, first + n)."""
+        em = self._em
+        if not getattr(em, "_h", None):
+            raise RuntimeError("MinLenPosterior.posterior: the list is closed")
+        if em._mlp_run != self._run:
+            raise RuntimeError("MinLenPosterior.posterior: the list has run minlen_posterior again; its buffers hold the later run")
+        n = em.store.n_windows - first if n is None else n
+        out = np.empty((max(int(n), 0), 4), dtype=np.float64)
+        N.check(em._L.hf_get_minlen_posterior(em._h, int(first), int(n), _dptr(out)), "hf_get_minlen_posterior")
+        return out
+
+
+def EM_runMinLengthPosteriorForList(emList, model: HMM, min_len) -> MinLenPosterior:
+    """The posterior under minimum run lengths (no counterpart in the reference): per-window label probabilities given that every run
+    of state s has at least min_len[s] windows, runs at a chunk's ends exempt, and the posterior mass of those paths per chunk.
+    `emList`: an EMList."""
+    if not hasattr(emList, "minlen_posterior"):
+        raise TypeError("EM_runMinLengthPosteriorForList: %s has no minimum-run-length posterior" % type(emList).__name__)
+    return emList.minlen_posterior(model, min_len)
 
 
 def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:

@@ -502,6 +502,58 @@ int hf_viterbi_minlen_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_minlen_labels(hf_ctx *ctx, int8_t *labels_host);                   /* [n_windows] */
 int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx *ctx, double *out_host);             /* [n_chunks] */
 
+/* Posteriors under minimum run lengths (flagger_amd/csrc/hf_minlen_post.h): the sum-product twin of hf_viterbi_minlen.  first[s],
+ * A_t[p][s], end[s], min_len[4], admissibility (runs that contain a chunk's first or last window are exempt), the lanes (s, d),
+ * d = 1..min_len[s], and the lane index sum_{q<s} min_len[q] + d - 1 are exactly those of hf_viterbi_minlen; so are 1 <= min_len[s] and
+ * sum_s min_len[s] <= HF_MINLEN_MAX_LANES.  Chunks are independent chains.  With m_s = min_len[s], for a chunk of T windows:
+ *   F_0[(s, m_s)] = first[s], 0 elsewhere
+ *   F_t[(s, 1)]   = sum over p = 0..3 in order of F_{t-1}[(p, m_p)] * A_t[p][s], p == s left out when m_s > 1
+ *   F_t[(s, d)]   = F_{t-1}[(s, d-1)] * A_t[s][s]                                               1 < d < m_s
+ *   F_t[(s, m_s)] = F_{t-1}[(s, m_s - 1)] * A_t[s][s] + F_{t-1}[(s, m_s)] * A_t[s][s]            m_s > 1
+ *   B_{T-1}[(s, d)] = end[s]
+ *   B_{t-1}[(s, d)] = A_t[s][s] * B_t[(s, d+1)]                                                 d < m_s
+ *   B_{t-1}[(s, m_s)] = [m_s > 1] A_t[s][s] * B_t[(s, m_s)] + sum over q = 0..3 in order of A_t[s][q] * B_t[(q, 1)], q == s only
+ *                       when m_q == 1
+ *   Z_adm = sum over lanes of F_{T-1}[lane] * end[s(lane)]
+ *   Z     = the same recursion with all four lengths 1 (the plain 4-state forward)
+ *   g_t[s] = sum over d of F_t[(s, d)] * B_t[(s, d)]
+ *   post[t][s] = g_t[s] / (g_t[0] + g_t[1] + g_t[2] + g_t[3]) = P(s_t = s | data, path admissible)
+ *   log_mass[c] = log Z_adm - log Z = log P(path of chunk c admissible | data)
+ * THE ORDER OF EVERY SUM.  The sums over p and over q: ((t_0 + t_1) + t_2) + t_3, a term that is left out replaced by 0; in B the stay
+ * term is added to the finished sum over q from the left.  The denominator of post: ((g_0 + g_1) + g_2) + g_3.  Z_adm, Z and every
+ * g_t[s] are sums over the 64 lanes of a wavefront with 0 in the lanes that take no part (for g_t[s]: the lanes of the other states),
+ * as ONE FIXED TREE: v += the value of lane ^ 1; v += that of lane ^ 2; v += that of the lane mirrored within its group of 8; v += that
+ * of the lane mirrored within its row of 16; then ((row 0 + row 1) + row 2) + row 3.  Z comes from the same kernel and the same
+ * operations as Z_adm, with the lengths (1, 1, 1, 1).
+ * RESCALING.  Linear domain, value = x * 2^E with an integer exponent sum E.  A rescaling with the largest lane mx: e = ilogb(mx) - 300
+ * (0 when mx is 0 or not finite), every lane is scaled by 2^-e and E += e.  It happens at the walk's first vector (F_0, or B_{T-1}),
+ * with mx its largest lane, before that vector is stored or stepped; and after every 8th step of a walk, counted from the chunk's
+ * first window (F) or its last window (B), with mx the largest lane BEFORE that step.  The largest lane is thus at exponent 300 at the
+ * start of every period of eight steps, the first included, and meets at most nine rows before the next rescaling: emission floors
+ * of 1e-40 keep it normal at either end of a chunk as well as inside it.  THE PRODUCTS IN g_t: with F_t[lane] = mf * 2^ef and
+ * B_t[lane] = mb * 2^eb (frexp: mantissas in [1/2, 1)), a lane's term is (mf * mb) * 2^(ef + eb - e_t), e_t the largest ef + eb over the
+ * lanes whose mf * mb is not 0: the two walks are each anywhere within their own period at a window, and the plain product of two
+ * lanes could underflow although neither factor does.  The largest term of a window is in [1/4, 1).  log Z_adm = log(the wave sum) + E ln 2, likewise log Z.  post is a ratio within
+ * one window, so it needs no exponent: any power-of-two scale of F_t and B_t cancels.
+ * Exact cases.  All four lengths 1: log_mass is exactly 0.0 in every chunk, and post equals hf_get_posterior of a full pass with the
+ * same parameters to rounding.  A chunk of one or two windows has mass 1 (log_mass within rounding of 0).  A chunk without windows has
+ * log_mass 0.0 and log Z_adm 0.0.  Windows outside every chunk get label -1, and a posterior range that touches one is HF_E_ARG.
+ * HF_E_SCALE: a chunk with Z_adm or Z not > 0 (or a window whose g_t sum to nothing).  HF_E_NAN: a NaN in a row or in the end column.
+ * No NaN is returned otherwise.
+ * HF_E_ARG: the argument cases of hf_viterbi_minlen; a getter before a finished run; the forward lanes (n_windows x sum(min_len) x 8
+ * bytes) do not fit nine tenths of the free device memory (hf_last_error names the size).
+ * hf_minlen_posterior_finish returns the sum of log_mass over the chunks in list order.  hf_get_minlen_posterior_labels: the first
+ * largest entry of post (replacement needs strict >).
+ * Streams: as hf_viterbi_minlen.  Buffers of its own: the results of the last pass, hf_viterbi, hf_viterbi_minlen and the sampler, and
+ * the next hf_estep, are bitwise unaffected.  One code path serves HF_ALGO_SCAN and HF_ALGO_SEQ contexts and all three model types:
+ * the outputs are bitwise the same on both kinds of context, across repeated calls and on any stream.  hf_batch_* and hf_multi_* have
+ * no counterpart. */
+int hf_minlen_posterior(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4], void *stream);   /* asynchronous, as hf_viterbi_minlen */
+int hf_minlen_posterior_finish(hf_ctx *ctx, double *log_mass_total_host, void *stream);
+int hf_get_minlen_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_host);              /* [n][4] */
+int hf_get_minlen_posterior_labels(hf_ctx *ctx, int8_t *labels_host);                 /* [n_windows], -1 outside chunks */
+int hf_get_minlen_chunk_log_mass(hf_ctx *ctx, double *log_mass_host, double *log_z_adm_host);       /* [n_chunks]; log_z_adm_host may be NULL */
+
 /* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
  * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
  *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]
