@@ -184,18 +184,28 @@ __global__ void __launch_bounds__(64) k_dec_rows_seg(const SegDesc* __restrict__
     if (nan) atomicOr(flags, nan);
 }
 
-// HF_ALGO_SEQ: one thread per window, window order
-__global__ void __launch_bounds__(256) k_dec_rows_win(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
-                                                      const DevParams* __restrict__ P, const double* __restrict__ nbE,
-                                                      double2* __restrict__ rows, unsigned* __restrict__ flags) {
+// HF_ALGO_SEQ: one thread per window, window order.  LOG: the log of every entry (-inf for 0), k_mlv_rows of hf_minlen.h
+template <bool LOG>
+__device__ __forceinline__ void dec_rows_win(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
+                                             const DevParams* __restrict__ P, const double* __restrict__ nbE, double2* __restrict__ rows,
+                                             unsigned* __restrict__ flags) {
     const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= N) return;
     unsigned nan = 0;
     double a[16];
     dec_row(rec, beta, P, nbE, t, a, &nan);
+    if (LOG) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) a[k] = a[k] == 0.0 ? -__builtin_huge_val() : log(a[k]);
+    }
 #pragma unroll
     for (int k = 0; k < 8; k++) rows[t * 8 + k] = make_double2(a[2 * k], a[2 * k + 1]);
     if (nan) atomicOr(flags, nan);
+}
+__global__ void __launch_bounds__(256) k_dec_rows_win(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
+                                                      const DevParams* __restrict__ P, const double* __restrict__ nbE,
+                                                      double2* __restrict__ rows, unsigned* __restrict__ flags) {
+    dec_rows_win<false>(N, rec, beta, P, nbE, rows, flags);
 }
 
 // ---- A: lane products and their exclusive scan over the lanes --------------------------------------------------------------------

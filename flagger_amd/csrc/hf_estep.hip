@@ -423,19 +423,23 @@ struct Decoder {
     void release() { if (h_params) hipHostFree(h_params); slab.release(); }
 };
 
-// most-probable-path decoding (hf_viterbi.h)
-struct Viterbi : Decoder {
-    uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
-    int8_t* d_label = nullptr; double* d_ll = nullptr; int8_t* d_final = nullptr;
-    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: phases C, D
-    std::vector<double> h_ll;                  // chunk scores of the last finished run
+// a decoder that leaves one label per window and values per chunk (dec_finish_chunks, dec_labels, dec_chunk_values)
+struct LabelDecoder : Decoder {
+    int8_t* d_label = nullptr;
+    double* d_chunk = nullptr;                 // [values per chunk][C]
+    std::vector<double> h_chunk;               // ... of the last finished run
 };
 
-// minimum-run-length Viterbi (hf_minlen.h): rows always in window order, one 16-bit backpointer word per window
-struct MinLenViterbi : Decoder {
+// most-probable-path decoding (hf_viterbi.h); the chunk values: the scores
+struct Viterbi : LabelDecoder {
+    uint8_t* d_bp = nullptr;                   // backpointer bytes (slot order / window order)
+    int8_t* d_final = nullptr;
+    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: phases C, D
+};
+
+// minimum-run-length Viterbi (hf_minlen.h): rows always in window order, one 16-bit backpointer word per window; the chunk values: the scores
+struct MinLenViterbi : LabelDecoder {
     uint16_t* d_bp = nullptr; uint8_t* d_final = nullptr;     // ... and the final lane of every chunk
-    int8_t* d_label = nullptr; double* d_ll = nullptr;
-    std::vector<double> h_ll;                  // chunk scores of the last finished run
 };
 
 // posterior path sampling (hf_sample.h).  The per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more.
@@ -467,12 +471,10 @@ struct DevBuf {
 };
 
 // posteriors under minimum run lengths (hf_minlen_post.h): rows in window order; the forward lanes [N][sum of the lengths] are sized by
-// the lengths of a call, grown on demand and never shrunk
-struct MinLenPosterior : Decoder {
+// the lengths of a call, grown on demand and never shrunk; the chunk values [2][C]: log Z_adm, log Z
+struct MinLenPosterior : LabelDecoder {
     DevBuf fwd;
-    double* d_post = nullptr; int8_t* d_label = nullptr;
-    double* d_lz = nullptr;                    // [2][C]: log Z_adm, log Z
-    std::vector<double> h_lz;                  // ... of the last finished run
+    double* d_post = nullptr;
     void release() { fwd.release(); Decoder::release(); }
 };
 
@@ -2033,11 +2035,14 @@ static size_t dec_nrow(const Track& tr) { return dec_scan(tr) ? (size_t) tr.n_sl
 static size_t dec_nseg(const Track& tr) { return dec_scan(tr) ? (size_t) tr.nseg : 0; }
 
 // Every device array of a decoder, f(array, bytes) in turn: the ONE place that sizes them (dec_take allocates them, hf_sample_capacity
-// counts them).  The shared part: parameter block, negative-binomial table, flag word, rows; SCAN: the arrays of A and B, with their
-// exponent sums when the decoder reports a score.
+// counts them).  What dec_front fills and every decoder has (dec_front_arrays; nrow rows): parameter block, negative-binomial table,
+// rows, flag word; SCAN: the arrays of A and B, with their exponent sums when the decoder reports a score.
+template <class D, class F> static void dec_front_arrays(const Track& tr, D& d, size_t nrow, F&& f) {
+    f(d.d_params, tr.params_bytes); f(d.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(d.d_rows, nrow * 128); f(d.d_flags, 4);
+}
 template <class D, class F> static void dec_arrays(const Track& tr, D& d, bool score, F&& f) {
     const size_t G = dec_nseg(tr);
-    f(d.d_params, tr.params_bytes); f(d.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(d.d_rows, dec_nrow(tr) * 128); f(d.d_flags, 4);
+    dec_front_arrays(tr, d, dec_nrow(tr), f);
     if (dec_scan(tr)) {
         f(d.d_P, G * 16 * 64 * 8); f(d.d_S, G * 16 * 8); f(d.d_vin, G * 4 * 8);
         if (score) { f(d.d_PE, G * 64 * 4); f(d.d_SE, G * 4); f(d.d_vinE, G * 8); }
@@ -2046,7 +2051,7 @@ template <class D, class F> static void dec_arrays(const Track& tr, D& d, bool s
 template <class F> static void vit_arrays(const Track& tr, Viterbi& v, F&& f) {
     const size_t G = dec_nseg(tr);
     dec_arrays(tr, v, true, f);
-    f(v.d_bp, dec_nrow(tr)); f(v.d_label, (size_t) tr.N); f(v.d_ll, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+    f(v.d_bp, dec_nrow(tr)); f(v.d_label, (size_t) tr.N); f(v.d_chunk, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
     if (dec_scan(tr)) { f(v.d_lmap, G * 64); f(v.d_smap, G); f(v.d_sexit, G); }
 }
 // the per-sample part for k samples: keys, map bytes, labels; SCAN: final states, lane and segment maps, exit states
@@ -2080,16 +2085,12 @@ template <class A> static int dec_alloc(const Track& tr, Decoder& d, A&& arrays)
 
 static bool dec_work(const Track& tr) { return tr.C > 0 && tr.N > 0; }
 
-// What a decoder call does before its own kernels, error messages naming the entry point `who`: the refusal of a scan context without a
-// segment plan, the wait for a run nobody finished (it may still be reading the pinned parameter block), `prepare` (the decoder's buffers
-// and inputs; it may refuse the call), the parameter block and the negative-binomial table, the flag word, then on `st` the rows and, on
-// the scan path, steps A and B in the semiring SR.
-template <class SR, class Prep>
-static int dec_begin(const Track& tr, Decoder& d, const hf_params* p, hipStream_t st, const char* who, Prep&& prepare) {
+// What every decoder call does before its kernels, error messages naming the entry point `who`: the wait for a run nobody finished (it
+// may still be reading the pinned parameter block), `prepare` (the decoder's buffers and inputs; it may refuse the call), the parameter
+// block and the negative-binomial table, the flag word.  nbE: the table as the rows kernels take it (null for the other models).
+template <class Prep>
+static int dec_front(const Track& tr, Decoder& d, const hf_params* p, hipStream_t st, const std::string& w, Prep&& prepare, const double*& nbE) {
     HIPCHK(hipSetDevice(tr.device));
-    const std::string w = who;
-    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
-        return set_err(HF_E_ARG, w + ": HF_ALGO_SCAN holds at most 2^30 windows per context");
     if (d.launched) HIPCHK(hipDeviceSynchronize());
     d.launched = false; d.done = false;
     int rc = prepare();
@@ -2106,8 +2107,21 @@ static int dec_begin(const Track& tr, Decoder& d, const hf_params* p, hipStream_
     }
     HIPCHK(hipMemcpyAsync(d.d_params, d.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d.d_flags, 0, 4, st));
-    if (!dec_work(tr)) return HF_OK;
-    const double* nbE = nbm ? d.d_nbE : nullptr;
+    nbE = nbm ? d.d_nbE : nullptr;
+    return HF_OK;
+}
+
+// hf_viterbi and the sampler: the refusal of a scan context without a segment plan, dec_front, then on `st` the rows and, on the scan
+// path, steps A and B in the semiring SR.
+template <class SR, class Prep>
+static int dec_begin(const Track& tr, Decoder& d, const hf_params* p, hipStream_t st, const char* who, Prep&& prepare) {
+    HIPCHK(hipSetDevice(tr.device));
+    const std::string w = who;
+    if (tr.algo == HF_ALGO_SCAN && tr.N > 0 && tr.C > 0 && tr.nseg == 0)
+        return set_err(HF_E_ARG, w + ": HF_ALGO_SCAN holds at most 2^30 windows per context");
+    const double* nbE = nullptr;
+    const int rc = dec_front(tr, d, p, st, w, prepare, nbE);
+    if (rc || !dec_work(tr)) return rc;
     if (dec_scan(tr)) {
         const unsigned G = (unsigned) tr.nseg, CB = (unsigned) ((tr.C + 63) / 64);
         hipLaunchKernelGGL(k_dec_rows_seg, dim3(G), dim3(64), 0, st, tr.d_seg, tr.d_rec, tr.d_beta, d.d_params, nbE, d.d_rows, d.d_flags);
@@ -2138,6 +2152,46 @@ static int dec_finish(const Track& tr, Decoder& d, void* stream) {
     return fl ? flags_to_code(fl) : HF_OK;
 }
 
+// ---- the decoders that leave labels and `per` values per chunk (LabelDecoder) ----
+// what the kernels do not write: the values of chunks without windows (0), the labels of windows outside every chunk (-1)
+static int dec_clear_outputs(const Track& tr, LabelDecoder& d, int per, hipStream_t st) {
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(d.d_chunk, 0, (size_t) tr.C * per * 8, st));
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(d.d_label, 0xff, (size_t) tr.N, st));
+    return HF_OK;
+}
+
+// dec_finish, then the chunk values to the host copy; the run counts as finished
+static int dec_finish_chunks(const Track& tr, LabelDecoder& d, int per, void* stream) {
+    const int rc = dec_finish(tr, d, stream);
+    if (rc) return rc;
+    d.h_chunk.assign((size_t) tr.C * per, 0.0);
+    if (tr.C > 0) HIPCHK(hipMemcpy(d.h_chunk.data(), d.d_chunk, (size_t) tr.C * per * 8, hipMemcpyDeviceToHost));
+    d.done = true;
+    return HF_OK;
+}
+
+// ... for a decoder with one score per chunk: their sum in chunk-list order
+static int dec_finish_scores(const Track& tr, LabelDecoder& d, double* log_prob_host, void* stream) {
+    const int rc = dec_finish_chunks(tr, d, 1, stream);
+    if (rc) return rc;
+    double tot = 0.0;
+    for (double x : d.h_chunk) tot += x;
+    if (log_prob_host) *log_prob_host = tot;
+    return HF_OK;
+}
+
+static int dec_labels(const Track& tr, const LabelDecoder& d, int8_t* labels_host) {
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, d.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+// the first value of every chunk
+static int dec_chunk_values(const Track& tr, const LabelDecoder& d, double* out_host) {
+    if (tr.C > 0) std::memcpy(out_host, d.h_chunk.data(), (size_t) tr.C * 8);
+    return HF_OK;
+}
+
 int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
     if (!ctx || !p) return set_err(HF_E_ARG, "hf_viterbi: bad argument");
     const Track& tr = ctx->tr;
@@ -2145,17 +2199,15 @@ int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
     hipStream_t st = (hipStream_t) stream;
     int rc = dec_begin<MaxTimes>(tr, v, p, st, "hf_viterbi",
                                  [&] { return dec_alloc(tr, v, [&](auto&& f) { vit_arrays(tr, v, f); }); });
-    if (rc) return rc;
-    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
-    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    if (rc || (rc = dec_clear_outputs(tr, v, 1, st))) return rc;
     if (dec_work(tr)) {
         if (dec_scan(tr)) {
             hipLaunchKernelGGL(k_vit_replay, dim3((unsigned) tr.nseg), dim3(64), 0, st, tr.d_seg, tr.d_rec, v.d_params, v.d_rows, v.d_P,
-                               v.d_PE, v.d_vin, v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_ll, v.d_flags);
+                               v.d_PE, v.d_vin, v.d_vinE, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_chunk, v.d_flags);
             dec_back(tr, st, 1, v.d_bp, v.d_lmap, v.d_smap, v.d_final, v.d_sexit, v.d_label);   // (the backpointers: one path's maps)
         } else {
             hipLaunchKernelGGL(k_vit_seq, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, v.d_bp,
-                               v.d_label, v.d_ll, v.d_flags);
+                               v.d_label, v.d_chunk, v.d_flags);
         }
     }
     HIPCHK(hipGetLastError());
@@ -2165,32 +2217,17 @@ int hf_viterbi(hf_ctx* ctx, const hf_params* p, void* stream) {
 
 int hf_viterbi_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
     if (!ctx || !ctx->vit.launched) return set_err(HF_E_ARG, "hf_viterbi_finish: no hf_viterbi to finish");
-    const Track& tr = ctx->tr;
-    Viterbi& v = ctx->vit;
-    const int rc = dec_finish(tr, v, stream);
-    if (rc) return rc;
-    v.h_ll.assign((size_t) tr.C, 0.0);
-    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
-    double tot = 0.0;
-    for (double x : v.h_ll) tot += x;   // chunk-list order
-    if (log_prob_host) *log_prob_host = tot;
-    v.done = true;
-    return HF_OK;
+    return dec_finish_scores(ctx->tr, ctx->vit, log_prob_host, stream);
 }
 
 int hf_get_viterbi_labels(hf_ctx* ctx, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_labels: no finished hf_viterbi");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->vit.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
+    return dec_labels(ctx->tr, ctx->vit, labels_host);
 }
 
 int hf_get_viterbi_chunk_log_probs(hf_ctx* ctx, double* out_host) {
     if (!ctx || !out_host || !ctx->vit.done) return set_err(HF_E_ARG, "hf_get_viterbi_chunk_log_probs: no finished hf_viterbi");
-    const Track& tr = ctx->tr;
-    if (tr.C > 0) std::memcpy(out_host, ctx->vit.h_ll.data(), (size_t) tr.C * 8);
-    return HF_OK;
+    return dec_chunk_values(ctx->tr, ctx->vit, out_host);
 }
 
 // the largest grid.y of the per-sample launches
@@ -2932,7 +2969,8 @@ int hf_get_breakpoint_profile(hf_ctx* ctx, int64_t first, int64_t last, uint8_t 
 
 // ------------------------------------------------------------------------------------------
 // minimum-run-length Viterbi (hf_minlen.h): a decoder of its own beside hf_viterbi, one code path for both kinds of context (rows in
-// window order, one wavefront per chunk).  Last in the file, its kernels included, so that no other kernel's code moves.
+// window order, one wavefront per chunk).  Last in the file, its kernels included, so that no other kernel's code moves.  With it comes
+// hf_chain.h, the core it shares with the two sections after it: wave primitives, lane geometry, row staging.
 // ------------------------------------------------------------------------------------------
 #include "hf_minlen.h"
 
@@ -2940,48 +2978,39 @@ static_assert(HF_MINLEN_MAX_LANES == 64, "one wavefront holds the expanded chain
 
 // every device array of the decoder, f(array, bytes) in turn (as vit_arrays)
 template <class F> static void mlv_arrays(const Track& tr, MinLenViterbi& v, F&& f) {
-    f(v.d_params, tr.params_bytes); f(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(v.d_rows, (size_t) tr.N * 128); f(v.d_flags, 4);
-    f(v.d_bp, (size_t) tr.N * 2); f(v.d_label, (size_t) tr.N); f(v.d_ll, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+    dec_front_arrays(tr, v, (size_t) tr.N, f);
+    f(v.d_bp, (size_t) tr.N * 2); f(v.d_label, (size_t) tr.N); f(v.d_chunk, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+}
+
+// the four minimum lengths of a call to `who`: every one >= 1, at most HF_MINLEN_MAX_LANES lanes together
+static int minlen_check(const std::string& who, const int32_t min_len[4], int64_t* lanes) {
+    *lanes = 0;
+    for (int s = 0; s < 4; s++) {
+        if (min_len[s] < 1) return set_err(HF_E_ARG, who + ": every minimum length must be >= 1");
+        *lanes += min_len[s];
+    }
+    if (*lanes > HF_MINLEN_MAX_LANES)
+        return set_err(HF_E_ARG, who + ": the minimum lengths sum to " + std::to_string(*lanes) + ", above HF_MINLEN_MAX_LANES (64)");
+    return HF_OK;
 }
 
 int hf_viterbi_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
     const std::string w = "hf_viterbi_minlen";
     if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
     int64_t lanes = 0;
-    for (int s = 0; s < 4; s++) {
-        if (min_len[s] < 1) return set_err(HF_E_ARG, w + ": every minimum length must be >= 1");
-        lanes += min_len[s];
-    }
-    if (lanes > HF_MINLEN_MAX_LANES)
-        return set_err(HF_E_ARG, w + ": the minimum lengths sum to " + std::to_string(lanes) + ", above HF_MINLEN_MAX_LANES (64)");
+    int rc = minlen_check(w, min_len, &lanes);
+    if (rc) return rc;
     const Track& tr = ctx->tr;
     MinLenViterbi& v = ctx->mlv;
     hipStream_t st = (hipStream_t) stream;
-    // dec_begin without the scan path's steps: the wait for a run nobody finished (it may still be reading the pinned parameter block),
-    // the buffers, the parameter block, the negative-binomial table, the flag word
-    HIPCHK(hipSetDevice(tr.device));
-    if (v.launched) HIPCHK(hipDeviceSynchronize());
-    v.launched = false; v.done = false;
-    int rc = dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); });
-    if (rc) return rc;
-    rc = pack_params(tr, p, v.h_params);
-    if (rc) return rc;
-    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
-    if (nbm) {
-        if (!p->nb_E) return set_err(HF_E_ARG, w + ": negative_binomial needs hf_params.nb_E");
-        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
-            return set_err(HF_E_ARG, w + ": the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
-        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
-    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_ll, 0, (size_t) tr.C * 8, st));   // (chunks without windows: score 0)
-    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    const double* nbE = nullptr;
+    rc = dec_front(tr, v, p, st, w, [&] { return dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); }); }, nbE);
+    if (rc || (rc = dec_clear_outputs(tr, v, 1, st))) return rc;
     if (dec_work(tr)) {
-        hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params,
-                           nbm ? v.d_nbE : nullptr, v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
+                           v.d_rows, v.d_flags);
         hipLaunchKernelGGL(k_mlv_fwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
-                           (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_ll, v.d_flags);
+                           (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_chunk, v.d_flags);
         hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, (int) min_len[0], (int) min_len[1], (int) min_len[2],
                            (int) min_len[3], v.d_bp, v.d_final, v.d_label);
     }
@@ -2992,32 +3021,17 @@ int hf_viterbi_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4],
 
 int hf_viterbi_minlen_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
     if (!ctx || !ctx->mlv.launched) return set_err(HF_E_ARG, "hf_viterbi_minlen_finish: no hf_viterbi_minlen to finish");
-    const Track& tr = ctx->tr;
-    MinLenViterbi& v = ctx->mlv;
-    const int rc = dec_finish(tr, v, stream);
-    if (rc) return rc;
-    v.h_ll.assign((size_t) tr.C, 0.0);
-    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_ll.data(), v.d_ll, (size_t) tr.C * 8, hipMemcpyDeviceToHost));
-    double tot = 0.0;
-    for (double x : v.h_ll) tot += x;   // chunk-list order
-    if (log_prob_host) *log_prob_host = tot;
-    v.done = true;
-    return HF_OK;
+    return dec_finish_scores(ctx->tr, ctx->mlv, log_prob_host, stream);
 }
 
 int hf_get_viterbi_minlen_labels(hf_ctx* ctx, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->mlv.done) return set_err(HF_E_ARG, "hf_get_viterbi_minlen_labels: no finished hf_viterbi_minlen");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mlv.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
+    return dec_labels(ctx->tr, ctx->mlv, labels_host);
 }
 
 int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx* ctx, double* out_host) {
     if (!ctx || !out_host || !ctx->mlv.done) return set_err(HF_E_ARG, "hf_get_viterbi_minlen_chunk_log_probs: no finished hf_viterbi_minlen");
-    const Track& tr = ctx->tr;
-    if (tr.C > 0) std::memcpy(out_host, ctx->mlv.h_ll.data(), (size_t) tr.C * 8);
-    return HF_OK;
+    return dec_chunk_values(ctx->tr, ctx->mlv, out_host);
 }
 
 
@@ -3120,56 +3134,39 @@ int hf_get_long_run_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
 
 // every device array of the decoder but the forward lanes (their size depends on the lengths of a call: MinLenPosterior::fwd)
 template <class F> static void mlp_arrays(const Track& tr, MinLenPosterior& v, F&& f) {
-    f(v.d_params, tr.params_bytes); f(v.d_nbE, (size_t) tr.R * 4 * HF_NB_NX * 8); f(v.d_rows, (size_t) tr.N * 128); f(v.d_flags, 4);
-    f(v.d_post, (size_t) tr.N * 32); f(v.d_label, (size_t) tr.N); f(v.d_lz, (size_t) tr.C * 16);
+    dec_front_arrays(tr, v, (size_t) tr.N, f);
+    f(v.d_post, (size_t) tr.N * 32); f(v.d_label, (size_t) tr.N); f(v.d_chunk, (size_t) tr.C * 16);
 }
 
 int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
     const std::string w = "hf_minlen_posterior";
     if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
     int64_t lanes = 0;
-    for (int s = 0; s < 4; s++) {
-        if (min_len[s] < 1) return set_err(HF_E_ARG, w + ": every minimum length must be >= 1");
-        lanes += min_len[s];
-    }
-    if (lanes > HF_MINLEN_MAX_LANES)
-        return set_err(HF_E_ARG, w + ": the minimum lengths sum to " + std::to_string(lanes) + ", above HF_MINLEN_MAX_LANES (64)");
+    int rc = minlen_check(w, min_len, &lanes);
+    if (rc) return rc;
     const Track& tr = ctx->tr;
     MinLenPosterior& v = ctx->mlp;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(hipSetDevice(tr.device));
-    if (v.launched) HIPCHK(hipDeviceSynchronize());
-    v.launched = false; v.done = false;
-    // the forward lanes: what the decoder holds of them already counts as free
-    const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
-    if (f_bytes > v.fwd.cap) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        if ((double) f_bytes > 0.9 * ((double) free_b + (double) v.fwd.cap))
-            return set_err(HF_E_ARG, w + ": the forward lanes need " + std::to_string(f_bytes) + " bytes (n_windows x sum of the lengths x 8), above nine tenths of the free device memory");
-    }
-    int rc = dec_alloc(tr, v, [&](auto&& f) { mlp_arrays(tr, v, f); });
-    if (rc) return rc;
-    if ((rc = v.fwd.reserve(f_bytes, w))) return rc;
-    rc = pack_params(tr, p, v.h_params);
-    if (rc) return rc;
-    const bool nbm = p->model_type == HF_MODEL_NEGATIVE_BINOMIAL;
-    if (nbm) {
-        if (!p->nb_E) return set_err(HF_E_ARG, w + ": negative_binomial needs hf_params.nb_E");
-        if (p->nb_max_x > 0 && tr.M - 1 > p->nb_max_x)
-            return set_err(HF_E_ARG, w + ": the windows hold coverage values above hf_params.nb_max_x (hfm_set_max_coverage)");
-        HIPCHK(hipMemcpy(v.d_nbE, p->nb_E, (size_t) tr.R * 4 * HF_NB_NX * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpyAsync(v.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(v.d_flags, 0, 4, st));
-    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_lz, 0, (size_t) tr.C * 16, st));   // (chunks without windows: log Z_adm = log Z = 0)
-    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    const double* nbE = nullptr;
+    rc = dec_front(tr, v, p, st, w, [&] {
+        // the forward lanes: what the decoder holds of them already counts as free
+        const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
+        if (f_bytes > v.fwd.cap) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            if ((double) f_bytes > 0.9 * ((double) free_b + (double) v.fwd.cap))
+                return set_err(HF_E_ARG, w + ": the forward lanes need " + std::to_string(f_bytes) + " bytes (n_windows x sum of the lengths x 8), above nine tenths of the free device memory");
+        }
+        const int rc = dec_alloc(tr, v, [&](auto&& f) { mlp_arrays(tr, v, f); });
+        return rc ? rc : v.fwd.reserve(f_bytes, w);
+    }, nbE);
+    if (rc || (rc = dec_clear_outputs(tr, v, 2, st))) return rc;
     if (dec_work(tr)) {
         double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
-        hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params,
-                           nbm ? v.d_nbE : nullptr, v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
+                           v.d_rows, v.d_flags);
         hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows,
-                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_lz, v.d_flags);
+                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_chunk, v.d_flags);
         hipLaunchKernelGGL(k_mlp_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
                            (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_post, v.d_label, v.d_flags);
     }
@@ -3181,15 +3178,12 @@ int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4
 int hf_minlen_posterior_finish(hf_ctx* ctx, double* log_mass_total_host, void* stream) {
     if (!ctx || !ctx->mlp.launched) return set_err(HF_E_ARG, "hf_minlen_posterior_finish: no hf_minlen_posterior to finish");
     const Track& tr = ctx->tr;
-    MinLenPosterior& v = ctx->mlp;
-    const int rc = dec_finish(tr, v, stream);
+    const int rc = dec_finish_chunks(tr, ctx->mlp, 2, stream);
     if (rc) return rc;
-    v.h_lz.assign((size_t) tr.C * 2, 0.0);
-    if (tr.C > 0) HIPCHK(hipMemcpy(v.h_lz.data(), v.d_lz, (size_t) tr.C * 16, hipMemcpyDeviceToHost));
+    const std::vector<double>& z = ctx->mlp.h_chunk;
     double tot = 0.0;
-    for (int64_t c = 0; c < tr.C; c++) tot += v.h_lz[(size_t) c] - v.h_lz[(size_t) (tr.C + c)];   // chunk-list order
+    for (int64_t c = 0; c < tr.C; c++) tot += z[(size_t) c] - z[(size_t) (tr.C + c)];   // chunk-list order
     if (log_mass_total_host) *log_mass_total_host = tot;
-    v.done = true;
     return HF_OK;
 }
 
@@ -3206,19 +3200,13 @@ int hf_get_minlen_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* post_
 
 int hf_get_minlen_posterior_labels(hf_ctx* ctx, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->mlp.done) return set_err(HF_E_ARG, "hf_get_minlen_posterior_labels: no finished hf_minlen_posterior");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mlp.d_label, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
+    return dec_labels(ctx->tr, ctx->mlp, labels_host);
 }
 
 int hf_get_minlen_chunk_log_mass(hf_ctx* ctx, double* log_mass_host, double* log_z_adm_host) {
     if (!ctx || !log_mass_host || !ctx->mlp.done) return set_err(HF_E_ARG, "hf_get_minlen_chunk_log_mass: no finished hf_minlen_posterior");
     const Track& tr = ctx->tr;
-    const std::vector<double>& z = ctx->mlp.h_lz;
-    for (int64_t c = 0; c < tr.C; c++) {
-        log_mass_host[c] = z[(size_t) c] - z[(size_t) (tr.C + c)];
-        if (log_z_adm_host) log_z_adm_host[c] = z[(size_t) c];
-    }
-    return HF_OK;
+    const std::vector<double>& z = ctx->mlp.h_chunk;
+    for (int64_t c = 0; c < tr.C; c++) log_mass_host[c] = z[(size_t) c] - z[(size_t) (tr.C + c)];
+    return log_z_adm_host ? dec_chunk_values(tr, ctx->mlp, log_z_adm_host) : HF_OK;
 }

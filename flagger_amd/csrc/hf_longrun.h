@@ -28,19 +28,18 @@
 // weight that far below the non-HIT scale is carried at the non-HIT exponent for this period); when m_n is 0 no non-HIT weight is left and
 // none can come back, and E_n = E_h.  The large target leaves a lane 2^-1300
 // below its class's largest total representable, so a counter lane of a very improbable run keeps its bits.  Every sum over lanes
-// (lr_wave_sum) has one order: lane ^ 1, lane ^ 2, the mirror in 8, the mirror in 16 by DPP, then the four rows left to right.
+// is ch_wave_sum (hf_chain.h), which has one order.
 // The two logs, with d = (log N_hit - log N_none) + (E_h - E_n) ln 2:
 //   d < 0:   log_p_none = -log1p(exp(d)),       log_p_some = d - log1p(exp(d))
 //   d >= 0:  log_p_none = -d - log1p(exp(-d)),  log_p_some = -log1p(exp(-d))
 //   N_hit == 0: (0.0, -inf).  N_none == 0: (-inf, 0.0).  Neither positive, or one not finite: NaN (the pass left no weight).
 //
-// k_lr_chain: one 64-lane workgroup per group.  Rows come 64 windows at a time through LDS, the next 64 on their way while these are
-// walked (the staging of k_mlv_fwd); a lane reads its column A[0..3][s] only.  Per window: up to four masked wave sums (T), up to seven
-// lane reads at wave-uniform indices (O, H), up to four permutes at fixed per-lane sources (lane (s, d+1) takes the |S| lanes of d).  No
-// scratch, no LDS beyond the staging.
+// k_lr_chain: one 64-lane workgroup per group.  The staging of hf_chain.h without a pad, the tiles following the group's parts; a lane
+// reads its column A[0..3][s] only.  Per window: up to four masked wave sums (T), up to seven lane reads at wave-uniform indices (O, H),
+// up to four permutes at fixed per-lane sources (lane (s, d+1) takes the |S| lanes of d).  No scratch, no LDS beyond the staging.
 #pragma once
 #include "hf_view.h"
-#include "hf_minlen.h"
+#include "hf_chain.h"
 
 #define HF_LR_RENORM 8          // steps between renormalisations
 #define HF_LR_TARGET 300        // exponent a class's largest total is brought to
@@ -51,21 +50,6 @@ struct LrPart { long long a, b; int p0, p1, c, pad; };    // chunk-local part [a
 struct LrGroup { int q0, q1, mask, len; };                // parts q0 .. q1 - 1 of the batch, state set, L
 
 enum { LR_ENTRY = 0, LR_COUNT = 1, LR_OUT = 2, LR_HIT = 3, LR_NONE = 4 };
-
-template <int CTRL>
-__device__ __forceinline__ double lr_dpp(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
-}
-
-// the sum of v over the wavefront, the same bits in every lane; all 64 lanes must be active
-__device__ __forceinline__ double lr_wave_sum(double v) {
-    v += lr_dpp<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-    v += lr_dpp<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-    v += lr_dpp<0x141>(v);      // row_half_mirror
-    v += lr_dpp<0x140>(v);      // row_mirror
-    return ((mlv_readlane(v, 0) + mlv_readlane(v, 16)) + mlv_readlane(v, 32)) + mlv_readlane(v, 48);
-}
 
 __device__ __forceinline__ double lr_pick(const double v[4], int s) { return s == 0 ? v[0] : s == 1 ? v[1] : s == 2 ? v[2] : v[3]; }
 
@@ -98,7 +82,7 @@ __global__ void __launch_bounds__(64) k_lr_chain(const LrGroup* __restrict__ gro
     const int mask = __builtin_amdgcn_readfirstlane(g.mask), L = __builtin_amdgcn_readfirstlane(g.len);
     const int q_first = __builtin_amdgcn_readfirstlane(g.q0), q_end = __builtin_amdgcn_readfirstlane(g.q1);
     const int k = __popc(mask), nc = k * (L - 1), h0 = nc + (4 - k), total = h0 + 4;
-    __shared__ double As[65][17];      // (row 64: read ahead, never used)
+    __shared__ ChainTile As;
 
     // the lane's class and state, and where its permutes read: the lanes of d - 1, for a HIT lane those of L - 1
     int cls = LR_NONE, st = 0, src0 = 0;
@@ -166,16 +150,17 @@ __global__ void __launch_bounds__(64) k_lr_chain(const LrGroup* __restrict__ gro
         if (have_next) lr_load<SEQ>(pv, parts, nq, q_first, npt, nbase + lane, nx);
         __syncthreads();
         const int w0 = (q == q_first && base == 0) ? 1 : 0;
-        double c0 = As[w0][st], c1 = As[w0][4 + st], c2 = As[w0][8 + st], c3 = As[w0][12 + st];
+        double c0, c1, c2, c3;
+        c0 = As[w0][st]; c1 = As[w0][4 + st]; c2 = As[w0][8 + st]; c3 = As[w0][12 + st];
         for (int w = w0; w < n; w++) {
             const double a0 = c0, a1 = c1, a2 = c2, a3 = c3;
             c0 = As[w + 1][st]; c1 = As[w + 1][4 + st]; c2 = As[w + 1][8 + st]; c3 = As[w + 1][12 + st];
             double T[4], O[4], H[4];
 #pragma unroll
             for (int p = 0; p < 4; p++) {
-                if ((mask >> p) & 1) { T[p] = lr_wave_sum(counter && st == p ? x : 0.0); O[p] = 0.0; }
-                else { O[p] = mlv_readlane(x, outl[p]); T[p] = O[p]; }
-                H[p] = mlv_readlane(x, h0 + p);
+                if ((mask >> p) & 1) { T[p] = ch_wave_sum(counter && st == p ? x : 0.0); O[p] = 0.0; }
+                else { O[p] = ch_readlane(x, outl[p]); T[p] = O[p]; }
+                H[p] = ch_readlane(x, h0 + p);
             }
             double U[4];
 #pragma unroll
@@ -218,7 +203,7 @@ __global__ void __launch_bounds__(64) k_lr_chain(const LrGroup* __restrict__ gro
     double bb[4];
     mo_b<SEQ>(pv, pt.c, pt.b, bb);
     const double xb = x * lr_pick(bb, st);
-    const double Nn = lr_wave_sum(counter || cls == LR_OUT ? xb : 0.0), Nh = lr_wave_sum(cls == LR_HIT ? xb : 0.0);
+    const double Nn = ch_wave_sum(counter || cls == LR_OUT ? xb : 0.0), Nh = ch_wave_sum(cls == LR_HIT ? xb : 0.0);
     if (lane != 0) return;
     double none, some;
     const double inf = __builtin_inf();

@@ -6,11 +6,9 @@
 // equal state s has at least min_len[s] windows; a run that contains the chunk's first or last window is exempt (a chunk is a cut of a
 // contig).  The decoder returns the admissible path of the largest weight first[s_0] * prod_t A_t[s_{t-1}][s_t] * end[s_{T-1}].
 //
-// The expanded chain.  Lanes (s, d), d = 1 .. min_len[s]: "in state s, the current run has d windows so far"; at d = min_len[s] "at least
-// that many" (the SATURATED lane; d = 1 is the ENTRY lane).  Lane index = sum_{q<s} min_len[q] + d - 1.
+// The expanded chain: lanes (s, d), entry and saturated lanes, the exclusion of p == s and the tie rule as hf_chain.h defines them.
 //   window 0     delta[(s, min_len[s])] = first[s], nothing elsewhere (the exempt left end)
-//   entry        max over p in increasing order of delta[(p, min_len[p])] + A_t[p][s]; p = s only when min_len[s] == 1 (the "stay");
-//                replacement needs strict >, so the lowest p wins a tie
+//   entry        max over the admitted p of delta[(p, min_len[p])] + A_t[p][s]
 //   1 < d < m    delta[(s, d-1)] + A_t[s][s]
 //   d = m > 1    delta[(s, d-1)] + A_t[s][s], then delta[(s, d)] + A_t[s][s], strict >
 //   end          max over all lanes in lane order of delta[(s, d)] + end[s], strict > (the exempt right end)
@@ -21,9 +19,9 @@
 // window.  A chunk's score is the maximum itself.  HF_FLAG_NAN: a NaN in a row (k_mlv_rows, as dec_row) or in the end column;
 // HF_FLAG_SCALE: the maximum of a chunk is -inf, no admissible path has weight.
 //
-// k_mlv_fwd: one 64-lane workgroup per chunk, lane = expanded state.  Rows come 64 windows at a time through LDS (the next 64 are on
-// their way while these are walked); a lane reads its column A[0..3][s] and A[s][s].  Per window a lane takes the four saturated lanes'
-// values (readlane at wave-uniform indices) and the value of the lane below it (a DPP shift by one lane); nothing else crosses lanes.
+// k_mlv_fwd: one 64-lane workgroup per chunk, lane = expanded state, the staging of hf_chain.h with -inf as the pad.  Per window a lane
+// takes the four saturated lanes' values (readlane at wave-uniform indices) and the value of the lane below it (a DPP shift by one
+// lane); nothing else crosses lanes.
 // BACKPOINTERS: one 16-bit word per window: bits 2s, 2s+1 the predecessor state of state s's entry lane, bit 8+s set when state s's
 // saturated lane stayed (clear: it arrived from d-1).  An owning lane keeps its own decisions of 16 windows in a register, 2 bits per
 // window; after the 16, lane l builds the word of window l from the eight owning lanes' registers, read at their (uniform) lane
@@ -32,40 +30,16 @@
 // is carried through the 64 words in registers on the scalar side — a word's address does not depend on the state — while lane q
 // keeps label[t-q] for one store.
 #pragma once
-#include "hf_decode.h"
+#include "hf_chain.h"
 
 #define HF_MLV_NEG_INF (-__builtin_huge_val())
-
-__device__ __forceinline__ double mlv_readlane(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// the value of lane - 1 (lane 0: `v` itself): DPP wave_shr:1 on the two halves
-__device__ __forceinline__ double mlv_lane_below(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
-}
 
 // rows: log of the row of every window, window order, the layout of k_dec_rows_win
 __global__ void __launch_bounds__(256) k_mlv_rows(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
                                                   const DevParams* __restrict__ P, const double* __restrict__ nbE,
                                                   double2* __restrict__ rows, unsigned* __restrict__ flags) {
-    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= N) return;
-    unsigned nan = 0;
-    double a[16];
-    dec_row(rec, beta, P, nbE, t, a, &nan);
-#pragma unroll
-    for (int k = 0; k < 16; k++) a[k] = a[k] == 0.0 ? HF_MLV_NEG_INF : log(a[k]);
-#pragma unroll
-    for (int k = 0; k < 8; k++) rows[t * 8 + k] = make_double2(a[2 * k], a[2 * k + 1]);
-    if (nan) atomicOr(flags, nan);
+    dec_rows_win<true>(N, rec, beta, P, nbE, rows, flags);
 }
-
-// min_len of state s out of the four lengths packed one per byte
-__device__ __forceinline__ int mlv_len(unsigned mpack, int s) { return (int) ((mpack >> (8 * s)) & 0xffu); }
 
 __global__ void __launch_bounds__(64) k_mlv_fwd(const int64_t* __restrict__ off, const uint32_t* __restrict__ rec,
                                                 const DevParams* __restrict__ P, const double2* __restrict__ rows, int m0, int m1, int m2,
@@ -73,21 +47,10 @@ __global__ void __launch_bounds__(64) k_mlv_fwd(const int64_t* __restrict__ off,
                                                 unsigned* __restrict__ flags) {
     const int c = blockIdx.x, lane = threadIdx.x;
     const int64_t t0 = off[c], T = off[c + 1] - t0;
-    __shared__ double As[65][17];   // column 16: -inf, the "A[s][s]" of the lanes past the last one; row 64: read ahead, never used
+    __shared__ ChainTile As;
     if (T <= 0) { if (lane == 0) { ll[c] = 0.0; final_lane[c] = 0; } return; }
-    // the lane's (s, d) and the uniform lane indices of every state's entry and saturated lane
-    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2, total = b3 + m3;
-    const int ent0 = 0, ent1 = b1, ent2 = b2, ent3 = b3;
-    const int sat0 = b1 - 1, sat1 = b2 - 1, sat2 = b3 - 1, sat3 = total - 1;
-    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
-    const int s = (lane >= b1) + (lane >= b2) + (lane >= b3);
-    const int base_s = s == 0 ? 0 : s == 1 ? b1 : s == 2 ? b2 : b3;
-    const int m = mlv_len(mpack, s), d = lane - base_s + 1;
-    const bool active = lane < total;
-    const bool is_entry = active && d == 1, is_sat = active && d == m && m > 1;
-    const bool excl = m > 1;                                  // the entry lane takes no p == s
-    const int pf = (excl && s == 0) ? 1 : 0;                  // its first candidate
-    const int diag = active ? 5 * s : 16;                     // where the lane reads A[s][s]
+    HF_CHAIN_LANE(m0, m1, m2, m3, lane);
+    const int pf = (excl && s == 0) ? 1 : 0;                // the entry lane's first candidate
 
     double x = HF_MLV_NEG_INF;
     double2 nx[8];
@@ -111,8 +74,8 @@ __global__ void __launch_bounds__(64) k_mlv_fwd(const int64_t* __restrict__ off,
         // window 0: first[s] (row pre = 0 of the chunk-first row) in every state's saturated lane
         if (base == 0 && active && d == m) x = As[0][s];
         int words = 0;
-        // the lane's column of the NEXT window is read while this one's step runs: LDS latency stays off the chain
-        double c0 = As[q0][s], c1 = As[q0][4 + s], c2 = As[q0][8 + s], c3 = As[q0][12 + s], css = As[q0][diag];
+        double c0, c1, c2, c3, css;
+        c0 = As[q0][s]; c1 = As[q0][4 + s]; c2 = As[q0][8 + s]; c3 = As[q0][12 + s]; css = As[q0][diag];
         for (int qb = q0; qb < n; qb += 16) {
             // 16 windows; a lane keeps its own decisions, 2 bits per window: an entry lane its predecessor, a saturated lane "stayed"
             const int cnt = n - qb < 16 ? n - qb : 16;
@@ -120,10 +83,10 @@ __global__ void __launch_bounds__(64) k_mlv_fwd(const int64_t* __restrict__ off,
             for (int q = qb; q < qb + cnt; q++) {
                 const double a0 = c0, a1 = c1, a2 = c2, a3 = c3, ass = css;
                 c0 = As[q + 1][s]; c1 = As[q + 1][4 + s]; c2 = As[q + 1][8 + s]; c3 = As[q + 1][12 + s]; css = As[q + 1][diag];
-                const double v0 = mlv_readlane(x, sat0) + a0, v1 = mlv_readlane(x, sat1) + a1;
-                const double v2 = mlv_readlane(x, sat2) + a2, v3 = mlv_readlane(x, sat3) + a3;
-                const double up = mlv_lane_below(x) + ass, stay = x + ass;
-                // the entry lane: candidates p = pf .. 3 in increasing order, p == s left out when the state has a minimum above 1
+                const double v0 = ch_readlane(x, sat0) + a0, v1 = ch_readlane(x, sat1) + a1;
+                const double v2 = ch_readlane(x, sat2) + a2, v3 = ch_readlane(x, sat3) + a3;
+                const double up = ch_lane_below(x) + ass, stay = x + ass;
+                // the entry lane: candidates p = pf .. 3 in increasing order, without the excluded p == s
                 double best = pf ? v1 : v0;
                 unsigned arg = (unsigned) pf;
                 if (pf < 1 && !(excl && s == 1) && v1 > best) { best = v1; arg = 1; }
@@ -173,8 +136,7 @@ __global__ void __launch_bounds__(64) k_mlv_back(const int64_t* __restrict__ off
     const int c = blockIdx.x, lane = threadIdx.x;
     const int64_t t0 = off[c], T = off[c + 1] - t0;
     if (T <= 0) return;
-    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2;
-    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
+    HF_CHAIN_LENS(m0, m1, m2, m3);
     const int fl = __builtin_amdgcn_readfirstlane((int) final_lane[c]);
     int cs = (fl >= b1) + (fl >= b2) + (fl >= b3);
     int cd = fl - (cs == 0 ? 0 : cs == 1 ? b1 : cs == 2 ? b2 : b3) + 1;
@@ -188,10 +150,11 @@ __global__ void __launch_bounds__(64) k_mlv_back(const int64_t* __restrict__ off
             // an entry lane: to the saturated lane of its predecessor; else one lane down, unless the saturated lane stayed
             const int p = (w >> (2 * cs)) & 3, stayed = (w >> (8 + cs)) & 1;
             const bool entry = cd == 1;
-            const int down = (cd < mlv_len(mpack, cs)) | (stayed ^ 1);
-            cd = entry ? mlv_len(mpack, p) : cd - down;
+            const int down = (cd < ch_len(mpack, cs)) | (stayed ^ 1);
+            cd = entry ? ch_len(mpack, p) : cd - down;
             cs = entry ? p : cs;
         }
         if (lane < n) label[t0 + hi - lane] = (int8_t) lab;
     }
 }
+

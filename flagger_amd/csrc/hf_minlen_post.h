@@ -1,8 +1,7 @@
 // hf_minlen_post.h — posteriors under minimum run lengths (hf_minlen_posterior): the sum-product twin of hf_minlen.h.  Over the expanded
-// chain of hf_viterbi_minlen (lanes (s, d), d = 1 .. min_len[s], lane index = sum_{q<s} min_len[q] + d - 1; the SATURATED lane d = min_len[s],
-// the ENTRY lane d = 1) one forward and one backward walk give, per chunk, the weight Z_adm of the admissible paths, the weight Z of all
-// paths, and per window the label probabilities given that the path is admissible.  A decoder beside hf_viterbi_minlen: the same first,
-// A_t and end, buffers of its own, ONE code path for both kinds of context (linear rows in window order, k_dec_rows_win).
+// chain of hf_viterbi_minlen (hf_chain.h: lanes (s, d), saturated and entry lanes) one forward and one backward walk give, per chunk,
+// the weight Z_adm of the admissible paths, the weight Z of all paths, and per window the label probabilities given that the path is
+// admissible.  A decoder beside hf_viterbi_minlen: the same first, A_t and end, buffers of its own, ONE code path for both kinds of context (linear rows in window order, k_dec_rows_win).
 //
 // Definition (include/hmm_flagger_hip.h has it in full), m = min_len[s]:
 //   F_0[(s, m)] = first[s], 0 elsewhere
@@ -16,8 +15,7 @@
 //   Z_adm = the wave sum of F_{T-1}[lane] * end[s(lane)];  g_t[s] = the wave sum of F_t[lane] * B_t[lane] * 2^-e_t over the lanes of
 //   state s, e_t the window's largest exponent sum of a lane's two factors (below)
 //   post[t][s] = g_t[s] / (((g_t[0] + g_t[1]) + g_t[2]) + g_t[3])
-// Every wave sum is lr_wave_sum (hf_longrun.h) with 0 in the lanes that do not take part: lane ^ 1, lane ^ 2, the mirror in 8, the mirror
-// in 16, then the four rows of 16 left to right.
+// Every wave sum is ch_wave_sum (hf_chain.h, where its one order is written down) with 0 in the lanes that do not take part.
 //
 // NUMERICS.  Linear domain, the scheme of hf_longrun.h: value = x * 2^E with one integer exponent sum E per walk.  A rescaling with the
 // largest lane mx: e = ilogb(mx) - HF_MLP_TARGET (0 when mx is 0 or not finite), every lane is scaled by 2^-e and E += e.  It happens
@@ -34,48 +32,16 @@
 // is not > 0, or a window's g_t sum to nothing.
 //
 // k_mlp_fwd: grid (C, 2), one 64-lane workgroup per chunk and chain; blockIdx.y == 1 walks the chain with all four lengths 1 over the same
-// rows with the same operations (lanes 0..3) and leaves log Z, it stores no F.  The staging of k_mlv_fwd: rows 64 windows at a time
-// through LDS, the next 64 on their way; a lane reads its column A[0..3][s] and A[s][s]; the four saturated lanes by readlane at uniform
-// indices, the lane below by DPP.  Every lane stores its F_t at [t][lane], row stride sum(min_len).
+// rows with the same operations (lanes 0..3) and leaves log Z, it stores no F.  The staging of hf_chain.h with 0 as the pad; the four
+// saturated lanes by readlane at uniform indices, the lane below by DPP.  Every lane stores its F_t at [t][lane], row stride sum(min_len).
 // k_mlp_bwd: one 64-lane workgroup per chunk walks back with B in registers: the lane above by DPP, the four entry lanes by readlane, a
 // lane reads its row A[s][0..3] and A[s][s]; F_t comes back 64 windows at a time through LDS (the block before is in registers while this
 // one is walked).  Lanes 0..3 write post[t][lane]; lane q keeps the label of the block's window q for one store.
 #pragma once
-#include "hf_longrun.h"
+#include "hf_chain.h"
 
 #define HF_MLP_RENORM 8         // steps between rescalings
 #define HF_MLP_TARGET 300       // exponent the largest lane is brought to
-
-// the value of lane + 1 (lane 63: `v` itself): DPP wave_shl:1 on the two halves
-__device__ __forceinline__ double mlp_lane_above(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false));
-}
-
-// the largest lane of v (>= 0 everywhere, a NaN is passed over), the same bits in every lane; all 64 lanes must be active
-__device__ __forceinline__ double mlp_wave_max(double v) {
-    v = fmax(v, lr_dpp<0xB1>(v));
-    v = fmax(v, lr_dpp<0x4E>(v));
-    v = fmax(v, lr_dpp<0x141>(v));
-    v = fmax(v, lr_dpp<0x140>(v));
-    return fmax(fmax(mlv_readlane(v, 0), mlv_readlane(v, 16)), fmax(mlv_readlane(v, 32), mlv_readlane(v, 48)));
-}
-
-// the largest lane of an integer, the same in every lane; all 64 lanes must be active
-__device__ __forceinline__ int mlp_wave_max_i(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-// the exponent a rescaling takes out: uniform
-__device__ __forceinline__ int mlp_shift(double mx) {
-    return (mx > 0.0 && !isinf(mx)) ? __builtin_amdgcn_readfirstlane(ilogb(mx)) - HF_MLP_TARGET : 0;
-}
 
 // lz[0][c] = log Z_adm, lz[1][c] = log Z; F[t][lane] for the windows of every chunk (row stride: the sum of the four lengths)
 __global__ void __launch_bounds__(64) k_mlp_fwd(int C, const int64_t* __restrict__ off, const uint32_t* __restrict__ rec,
@@ -84,20 +50,11 @@ __global__ void __launch_bounds__(64) k_mlp_fwd(int C, const int64_t* __restrict
     const int c = blockIdx.x, lane = threadIdx.x;
     const bool plain = blockIdx.y == 1;
     const int64_t t0 = off[c], T = off[c + 1] - t0;
-    __shared__ double As[65][17];   // column 16: 0, the "A[s][s]" of the lanes past the last one; row 64: read ahead, never used
+    __shared__ ChainTile As;
     if (T <= 0) { if (lane == 0) lz[(int64_t) blockIdx.y * C + c] = 0.0; return; }
     const int stride = m0 + m1 + m2 + m3;
     if (plain) m0 = m1 = m2 = m3 = 1;
-    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2, total = b3 + m3;
-    const int sat0 = b1 - 1, sat1 = b2 - 1, sat2 = b3 - 1, sat3 = total - 1;
-    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
-    const int s = (lane >= b1) + (lane >= b2) + (lane >= b3);
-    const int base_s = s == 0 ? 0 : s == 1 ? b1 : s == 2 ? b2 : b3;
-    const int m = mlv_len(mpack, s), d = lane - base_s + 1;
-    const bool active = lane < total;
-    const bool is_entry = active && d == 1, is_sat = active && d == m && m > 1;
-    const bool excl = m > 1;                                  // the entry lane takes no p == s
-    const int diag = active ? 5 * s : 16;                     // where the lane reads A[s][s]
+    HF_CHAIN_LANE(m0, m1, m2, m3, lane);
 
     double x = 0.0;
     long long E = 0;
@@ -122,26 +79,26 @@ __global__ void __launch_bounds__(64) k_mlp_fwd(int C, const int64_t* __restrict
         // window 0: first[s] (row pre = 0 of the chunk-first row) in every state's saturated lane
         if (base == 0) {
             if (active && d == m) x = As[0][s];
-            const int e0 = mlp_shift(mlp_wave_max(x));        // the walk starts at the target exponent as well
+            const int e0 = ch_shift(ch_wave_max(x), HF_MLP_TARGET);        // the walk starts at the target exponent as well
             x = ldexp(x, -e0);
             E += e0;
             if (!plain && active) F[t0 * stride + lane] = x;
         }
-        // the lane's column of the NEXT window is read while this one's step runs
-        double c0 = As[q0][s], c1 = As[q0][4 + s], c2 = As[q0][8 + s], c3 = As[q0][12 + s], css = As[q0][diag];
+        double c0, c1, c2, c3, css;
+        c0 = As[q0][s]; c1 = As[q0][4 + s]; c2 = As[q0][8 + s]; c3 = As[q0][12 + s]; css = As[q0][diag];
         for (int q = q0; q < n; q++) {
             const double a0 = c0, a1 = c1, a2 = c2, a3 = c3, ass = css;
             c0 = As[q + 1][s]; c1 = As[q + 1][4 + s]; c2 = As[q + 1][8 + s]; c3 = As[q + 1][12 + s]; css = As[q + 1][diag];
             const bool rs = ((base + q) % HF_MLP_RENORM) == 0;      // (uniform) the step into window base + q is step base + q
-            const double mx = rs ? mlp_wave_max(x) : 0.0;
-            const double v0 = mlv_readlane(x, sat0) * a0, v1 = mlv_readlane(x, sat1) * a1;
-            const double v2 = mlv_readlane(x, sat2) * a2, v3 = mlv_readlane(x, sat3) * a3;
+            const double mx = rs ? ch_wave_max(x) : 0.0;
+            const double v0 = ch_readlane(x, sat0) * a0, v1 = ch_readlane(x, sat1) * a1;
+            const double v2 = ch_readlane(x, sat2) * a2, v3 = ch_readlane(x, sat3) * a3;
             const double ent = (((excl && s == 0 ? 0.0 : v0) + (excl && s == 1 ? 0.0 : v1)) + (excl && s == 2 ? 0.0 : v2)) +
                                (excl && s == 3 ? 0.0 : v3);
-            const double up = mlv_lane_below(x) * ass, stay = x * ass;
+            const double up = ch_lane_below(x) * ass, stay = x * ass;
             x = is_entry ? ent : is_sat ? up + stay : active ? up : 0.0;
             if (rs) {
-                const int e = mlp_shift(mx);
+                const int e = ch_shift(mx, HF_MLP_TARGET);
                 x = ldexp(x, -e);
                 E += e;
             }
@@ -154,7 +111,7 @@ __global__ void __launch_bounds__(64) k_mlp_fwd(int C, const int64_t* __restrict
     const DevRegion* __restrict__ Rl = &P->reg[REC_REGION(rec[t0 + T - 1])];
     const double e = active ? Rl->trans[s][4] : 0.0;
     unsigned bad = e != e ? HF_FLAG_NAN : 0u;
-    const double z = lr_wave_sum(active ? x * e : 0.0);
+    const double z = ch_wave_sum(active ? x * e : 0.0);
     if (z != z) bad |= HF_FLAG_NAN;
     else if (!(z > 0.0)) bad |= HF_FLAG_SCALE;
     if (lane == 0) lz[(int64_t) blockIdx.y * C + c] = log(z) + (double) E * 0.69314718055994530942;
@@ -177,20 +134,11 @@ __global__ void __launch_bounds__(64) k_mlp_bwd(const int64_t* __restrict__ off,
     __shared__ double As[64][17];   // column 16: 0, for the lanes past the last one
     __shared__ double Fs[64][64];
     if (T <= 0) return;
-    const int b1 = m0, b2 = m0 + m1, b3 = b2 + m2, total = b3 + m3;
-    const int ent0 = 0, ent1 = b1, ent2 = b2, ent3 = b3;
-    const unsigned mpack = (unsigned) m0 | (unsigned) m1 << 8 | (unsigned) m2 << 16 | (unsigned) m3 << 24;
-    const int s = (lane >= b1) + (lane >= b2) + (lane >= b3);
-    const int base_s = s == 0 ? 0 : s == 1 ? b1 : s == 2 ? b2 : b3;
-    const int m = mlv_len(mpack, s), d = lane - base_s + 1;
-    const bool active = lane < total;
-    const bool inner = d < m;                                 // the lane hands on to the lane above it
-    const bool excl = m > 1;                                  // the saturated lane leaves to no q == s
-    const int diag = active ? 5 * s : 16;
+    HF_CHAIN_LANE(m0, m1, m2, m3, lane);
 
     const DevRegion* __restrict__ Rl = &P->reg[REC_REGION(rec[t0 + T - 1])];
     double B = active ? Rl->trans[s][4] : 0.0;
-    B = ldexp(B, -mlp_shift(mlp_wave_max(B)));                // the walk starts at the target exponent as well
+    B = ldexp(B, -ch_shift(ch_wave_max(B), HF_MLP_TARGET));                // the walk starts at the target exponent as well
     unsigned bad = 0;
 
     int64_t base = ((T - 1) / 64) * 64;
@@ -237,17 +185,17 @@ __global__ void __launch_bounds__(64) k_mlp_bwd(const int64_t* __restrict__ off,
             const double mf = frexp(f, &ef), mb = frexp(B, &eb);
             const double pm = active ? mf * mb : 0.0;         // 0, or in [1/4, 1)
             const int el = pm > 0.0 ? ef + eb : -(1 << 20);
-            const int sh = el - mlp_wave_max_i(el);           // <= 0
+            const int sh = el - ch_wave_max(el);           // <= 0
             const double fb = ldexp(pm, sh < -2000 ? -2000 : sh);
-            const double g0 = lr_wave_sum(s == 0 ? fb : 0.0), g1 = lr_wave_sum(s == 1 ? fb : 0.0);
-            const double g2 = lr_wave_sum(s == 2 ? fb : 0.0), g3 = lr_wave_sum(s == 3 ? fb : 0.0);
+            const double g0 = ch_wave_sum(s == 0 ? fb : 0.0), g1 = ch_wave_sum(s == 1 ? fb : 0.0);
+            const double g2 = ch_wave_sum(s == 2 ? fb : 0.0), g3 = ch_wave_sum(s == 3 ? fb : 0.0);
             const double tot = ((g0 + g1) + g2) + g3;
             if (tot != tot) bad |= HF_FLAG_NAN;
             else if (!(tot > 0.0)) bad |= HF_FLAG_SCALE;
             const int ls = lane & 3;
             const double pl = (ls == 0 ? g0 : ls == 1 ? g1 : ls == 2 ? g2 : g3) / tot;
             if (lane < 4) post[(t0 + base + q) * 4 + lane] = pl;
-            const double p0 = mlv_readlane(pl, 0), p1 = mlv_readlane(pl, 1), p2 = mlv_readlane(pl, 2), p3 = mlv_readlane(pl, 3);
+            const double p0 = ch_readlane(pl, 0), p1 = ch_readlane(pl, 1), p2 = ch_readlane(pl, 2), p3 = ch_readlane(pl, 3);
             double best = p0;
             int arg = 0;
             if (p1 > best) { best = p1; arg = 1; }
@@ -257,14 +205,15 @@ __global__ void __launch_bounds__(64) k_mlp_bwd(const int64_t* __restrict__ off,
             if (base + q == 0) break;
             // the step back over A of window base + q: step T - (base + q), counted from the chunk's last window
             const bool rs = ((T - (base + q)) % HF_MLP_RENORM) == 0;
-            const double mx = rs ? mlp_wave_max(B) : 0.0;
-            const double w0 = a0 * mlv_readlane(B, ent0), w1 = a1 * mlv_readlane(B, ent1);
-            const double w2 = a2 * mlv_readlane(B, ent2), w3 = a3 * mlv_readlane(B, ent3);
+            const double mx = rs ? ch_wave_max(B) : 0.0;
+            const double w0 = a0 * ch_readlane(B, ent0), w1 = a1 * ch_readlane(B, ent1);
+            const double w2 = a2 * ch_readlane(B, ent2), w3 = a3 * ch_readlane(B, ent3);
+            // (mirrored: the saturated lane leaves to no q == s)
             const double out = (((excl && s == 0 ? 0.0 : w0) + (excl && s == 1 ? 0.0 : w1)) + (excl && s == 2 ? 0.0 : w2)) +
                                (excl && s == 3 ? 0.0 : w3);
-            const double up = ass * mlp_lane_above(B), stay = excl ? ass * B : 0.0;
+            const double up = ass * ch_lane_above(B), stay = excl ? ass * B : 0.0;
             B = !active ? 0.0 : inner ? up : stay + out;
-            if (rs) B = ldexp(B, -mlp_shift(mx));
+            if (rs) B = ldexp(B, -ch_shift(mx, HF_MLP_TARGET));
         }
         if (lane < n) label[t0 + base + lane] = (int8_t) lab;
         __syncthreads();

@@ -555,14 +555,19 @@ class EMList:
         N.check(self._L.hf_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_chunk_log_probs")
         return labels, ll, float(lp.value)
 
+    @staticmethod
+    def _four_lengths(who: str, min_len) -> np.ndarray:
+        """min_len as the int32[4] the C ABI takes; `who` names the caller in the refusal."""
+        ml = np.asarray(min_len)
+        if ml.shape != (4,):
+            raise ValueError("%s: min_len holds four window counts (Err, Dup, Hap, Col)" % who)
+        return np.ascontiguousarray(ml, dtype=np.int32)
+
     def viterbi_minlen(self, model: HMM, min_len):
         """The most probable path among the paths whose runs have at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at
         a chunk's ends are exempt; hf_viterbi_minlen + hf_viterbi_minlen_finish): (labels, chunk_log_probs, log_prob).  The last pass's
         results, viterbi()'s and the sampler's are left as they were."""
-        ml = np.asarray(min_len)
-        if ml.shape != (4,):
-            raise ValueError("viterbi_minlen: min_len holds four window counts (Err, Dup, Hap, Col)")
-        ml = np.ascontiguousarray(ml, dtype=np.int32)
+        ml = self._four_lengths("viterbi_minlen", min_len)
         p = model.params()
         lp = C.c_double(0.0)
         N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_viterbi_minlen")
@@ -577,10 +582,7 @@ class EMList:
         """The posterior given that every run has at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at a chunk's
         ends are exempt; hf_minlen_posterior + hf_minlen_posterior_finish), and the posterior mass the rule keeps.  The last pass's
         results, viterbi()'s, viterbi_minlen()'s and the sampler's are left as they were."""
-        ml = np.asarray(min_len)
-        if ml.shape != (4,):
-            raise ValueError("minlen_posterior: min_len holds four window counts (Err, Dup, Hap, Col)")
-        ml = np.ascontiguousarray(ml, dtype=np.int32)
+        ml = self._four_lengths("minlen_posterior", min_len)
         p = model.params()
         tot = C.c_double(0.0)
         self._mlp_run = getattr(self, "_mlp_run", 0) + 1     # (older results stop answering posterior(): the context holds one run)
