@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -79,6 +80,7 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"keptBlocks", no_argument, nullptr, 1020},                 // exact probability of a block --minimumLengths would keep (hf_get_long_run_log_probs)
     {"enforceMinimumLengths", no_argument, nullptr, 1019},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
     {"constrainedPosterior", no_argument, nullptr, 1021},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
+    {"admissibleSamples", required_argument, nullptr, 1022},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -172,6 +174,11 @@ static void usage(const char* program) {
             "                                      as for --enforceMinimumLengths: ceil(length / windowLen), at least 1; Hap: 1; at most 58 windows),\n"
             "                                      runs merged across the chunks of a contig as the final BED merges them; one GPU, not with\n"
             "                                      --gpus N>1 or --sweepAlpha\n"
+            "         --admissibleSamples N        with --minimumLengths: after every other output, draw N state paths from the posterior GIVEN THAT\n"
+            "                                      EVERY RUN MEETS --minimumLengths (lengths in windows as for --enforceMinimumLengths, at most 64\n"
+            "                                      windows in sum; runs at a chunk's ends are exempt) with the final parameters, and write\n"
+            "                                      admissible_samples_summary.tsv and admissible_label_runs_support.bed in the formats of the two\n"
+            "                                      --uncertaintySamples files; the seed is --uncertaintySeed; one GPU, not with --gpus N>1 or --sweepAlpha\n"
             "         --constrainedPosterior       with --minimumLengths: after the final inference, write admissible_mass.tsv: the four lengths in\n"
             "                                      windows (as for --enforceMinimumLengths: ceil(length / windowLen), at least 1; Hap: 1; at most 64\n"
             "                                      in sum), then for the whole track and every contig the chunks, the windows and the log of the\n"
@@ -378,8 +385,16 @@ static std::vector<LRun> label_runs(const hfio_table* tab, const hf_windows& w, 
     return runs;
 }
 
-static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
-                                uint64_t seed, const std::vector<std::string>& labelNames, const std::string& dir) {
+// The sampler: capacity() = samples per call (< 1: none fit, or an HF_E_* code), draw(p, first, n) = the call and its finish,
+// labels(k, out) = sample k of the last call.  --admissibleSamples writes the same two files from hf_sample_paths_minlen.
+struct PathSampler {
+    std::function<int()> capacity;
+    std::function<int(const hf_params*, int64_t, int)> draw;
+    std::function<int(int, int8_t*)> labels;
+};
+static int write_sample_outputs(const PathSampler& smp, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
+                                const std::vector<std::string>& labelNames, const std::string& dir, const char* summaryName,
+                                const char* supportName) {
     const int64_t N = hfio_n_windows(tab);
     const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
     hf_windows w{};
@@ -402,15 +417,14 @@ static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table*
     std::vector<int8_t> lab((size_t) N);
     hf_params p;
     hfm_params(model, &p);
-    const int cap = hf_sample_capacity(ctx);
+    const int cap = smp.capacity();
     if (cap < 1) return cap < 0 ? cap : HF_E_ARG;
     for (int k0 = 0; k0 < nSamples; k0 += cap) {
         const int n = std::min(cap, nSamples - k0);
-        int rc = hf_sample_paths(ctx, &p, k0, n, seed, nullptr);
-        if (rc == HF_OK) rc = hf_sample_finish(ctx, nullptr);
+        int rc = smp.draw(&p, k0, n);
         if (rc != HF_OK) return rc;
         for (int k = 0; k < n; k++) {
-            if ((rc = hf_get_sample_labels(ctx, k, lab.data())) != HF_OK) return rc;
+            if ((rc = smp.labels(k, lab.data())) != HF_OK) return rc;
             int64_t* b = basesS.data() + (size_t) (k0 + k) * G * 4;
             std::fill(cnt.begin(), cnt.end(), 0);
             for (int64_t t = 0; t < N; t++) {
@@ -427,7 +441,7 @@ static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table*
             }
         }
     }
-    const std::string sp = dir + "/posterior_samples_summary.tsv";
+    const std::string sp = dir + "/" + summaryName;
     FILE* f = fopen(sp.c_str(), "w");
     if (!f) { hf_cli_set_error(sp + " cannot be opened"); return HF_E_ARG; }
     fprintf(f, "#Region\tLabel\tBases_Final\tBases_Mean\tBases_SD\tBases_Q025\tBases_Q500\tBases_Q975\tWindows_Mean\n");
@@ -447,7 +461,7 @@ static int write_sample_outputs(hf_ctx* ctx, hfm_model* model, const hfio_table*
                     (long) q(0.025), (long) q(0.5), (long) q(0.975), (double) winS[g * 4 + l] / nSamples);
         }
     if (fclose(f) != 0) { hf_cli_set_error(sp + " cannot be written"); return HF_E_ARG; }
-    const std::string bp = dir + "/final_label_runs_support.bed";
+    const std::string bp = dir + "/" + supportName;
     f = fopen(bp.c_str(), "w");
     if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
     fprintf(f, "#ctg\tstart\tend\tlabel\tsupport\tmean_fraction\n");
@@ -1060,6 +1074,7 @@ int main(int argc, char* argv[]) {
     bool viterbi = false, enforceMinLen = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
     uint64_t uncertaintySeed = 0;
+    int admissibleSamples = 0; bool admissibleSet = false;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
@@ -1163,6 +1178,13 @@ int main(int argc, char* argv[]) {
                 char* end = nullptr;
                 uncertaintySeed = strtoull(optarg, &end, 10);
                 uncertaintySeedBad = end == optarg || *end != 0 || optarg[0] == '-';
+                break;
+            }
+            case 1022: {
+                char* end = nullptr;
+                const long v = strtol(optarg, &end, 10);
+                admissibleSet = true;
+                admissibleSamples = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
                 break;
             }
             case 1009: runConfidence = true; break;
@@ -1300,6 +1322,13 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] Error: --constrainedPosterior runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
         return EXIT_FAILURE;
     }
+    // --admissibleSamples: likewise
+    if (admissibleSet && admissibleSamples < 1) { fprintf(stderr, "[%s] Error: --admissibleSamples should be a positive integer.\n", ts()); return EXIT_FAILURE; }
+    if (admissibleSet && !minLenGiven) { fprintf(stderr, "[%s] Error: --admissibleSamples needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
+    if (admissibleSet && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
+        fprintf(stderr, "[%s] Error: --admissibleSamples runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
+        return EXIT_FAILURE;
+    }
     if (!inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return EXIT_FAILURE; }
     if (convergenceTol <= 0.0 || convergenceTol > 1.0) {
         fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), convergenceTol);
@@ -1354,12 +1383,16 @@ int main(int argc, char* argv[]) {
                         HF_LONGRUN_MAX_LANES - 6);
                 return false;
             }
-        if (!(enforceMinLen || constrainedPost) || sum <= HF_MINLEN_MAX_LANES) return true;
+        if (!(enforceMinLen || constrainedPost || admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
+        std::string who;                                           // the options that walk the expanded chain, as given
+        for (const char* o : {enforceMinLen ? "enforceMinimumLengths" : nullptr, constrainedPost ? "constrainedPosterior" : nullptr,
+                              admissibleSet ? "admissibleSamples" : nullptr})
+            if (o) who += (who.empty() ? "" : ", --") + std::string(o);
         fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
-                ts(), enforceMinLen && constrainedPost ? "enforceMinimumLengths, --constrainedPosterior" : enforceMinLen ? "enforceMinimumLengths" : "constrainedPosterior", minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
+                ts(), who.c_str(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
         return false;
     };
-    if ((enforceMinLen || keptBlocks || constrainedPost) && !min_len_windows(windowLen)) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks || constrainedPost || admissibleSet) && !min_len_windows(windowLen)) return EXIT_FAILURE;
     if (0.5 < initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return EXIT_FAILURE; }
 
     // 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
@@ -1391,7 +1424,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), hfio_n_chunks(tab), (long) N, hfio_window_len(tab));
     if (N == 0 || hfio_n_chunks(tab) == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return EXIT_FAILURE; }
 
-    if ((enforceMinLen || keptBlocks || constrainedPost) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
+    if ((enforceMinLen || keptBlocks || constrainedPost || admissibleSet) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
     phase("load input (+ HIP start-up)");
     // 2. number of collapsed components (hmm_flagger.c:1008-1022)
     hf_windows w;
@@ -1655,7 +1688,15 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "[%s] [Final Inference] Drawing %d posterior state paths (seed %llu) ...\n", ts(), uncertaintySamples,
                 (unsigned long long) uncertaintySeed);
         const double t0 = real_time();
-        if ((rc = write_sample_outputs(run.ctx, model, tab, finalLabels, uncertaintySamples, uncertaintySeed, labelNames, dir)) != HF_OK) return die(rc);
+        hf_ctx* const sctx = run.ctx;
+        const PathSampler smp{[sctx] { return hf_sample_capacity(sctx); },
+                              [sctx, uncertaintySeed](const hf_params* p, int64_t first, int n) {
+                                  const int rc = hf_sample_paths(sctx, p, first, n, uncertaintySeed, nullptr);
+                                  return rc == HF_OK ? hf_sample_finish(sctx, nullptr) : rc;
+                              },
+                              [sctx](int k, int8_t* out) { return hf_get_sample_labels(sctx, k, out); }};
+        if ((rc = write_sample_outputs(smp, model, tab, finalLabels, uncertaintySamples, labelNames, dir, "posterior_samples_summary.tsv",
+                                       "final_label_runs_support.bed")) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] posterior_samples_summary.tsv and final_label_runs_support.bed are written (%.1f ms).\n", ts(),
                 (real_time() - t0) * 1e3);
     }
@@ -1711,6 +1752,25 @@ int main(int argc, char* argv[]) {
         if ((rc = write_constrained_posterior(run.ctx, tab, minLenWindows, dir)) != HF_OK) return die(rc);
         fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
                 ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], logMass, (real_time() - t0) * 1e3);
+    }
+    // --admissibleSamples: after every other output, the two files of --uncertaintySamples for paths drawn UNDER --minimumLengths
+    if (admissibleSamples > 0) {
+        if (!run.ctx) { fprintf(stderr, "[%s] Error: --admissibleSamples needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
+        fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows, seed %llu) ...\n", ts(),
+                admissibleSamples, minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], (unsigned long long) uncertaintySeed);
+        const double t0 = real_time();
+        hf_ctx* const sctx = run.ctx;
+        const int32_t* const ml = minLenWindows;
+        const PathSampler smp{[sctx, ml] { return hf_minlen_sample_capacity(sctx, ml); },
+                              [sctx, ml, uncertaintySeed](const hf_params* p, int64_t first, int n) {
+                                  const int rc = hf_sample_paths_minlen(sctx, p, ml, first, n, uncertaintySeed, nullptr);
+                                  return rc == HF_OK ? hf_sample_minlen_finish(sctx, nullptr) : rc;
+                              },
+                              [sctx](int k, int8_t* out) { return hf_get_minlen_sample_labels(sctx, k, out); }};
+        if ((rc = write_sample_outputs(smp, model, tab, finalLabels, admissibleSamples, labelNames, dir, "admissible_samples_summary.tsv",
+                                       "admissible_label_runs_support.bed")) != HF_OK) return die(rc);
+        fprintf(stderr, "[%s] [Final Inference] admissible_samples_summary.tsv and admissible_label_runs_support.bed are written (%.1f ms).\n", ts(),
+                (real_time() - t0) * 1e3);
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
             "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);

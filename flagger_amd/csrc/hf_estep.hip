@@ -478,6 +478,23 @@ struct MinLenPosterior : LabelDecoder {
     void release() { fwd.release(); Decoder::release(); }
 };
 
+// admissible path sampling (hf_minlen_sample.h): rows in window order, forward lanes of its own (as MinLenPosterior::fwd), log Z_adm per
+// chunk; the per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more (as Sampler::samples)
+struct MinLenSampler : Decoder {
+    DevBuf fwd;
+    double* d_chunk = nullptr;                 // [C] log Z_adm (k_mlp_fwd writes it; nothing returns it)
+    Slab samples;
+    int cap = 0;
+    size_t samples_bytes = 0;                  // what `samples` holds
+    uint64_t* d_keys = nullptr;                // [cap] key_k
+    uint16_t* d_words = nullptr;               // [N][Kp] words of k_mlv_fwd's format, Kp = a call's samples padded to HF_MLS_GROUP
+    uint8_t* d_final = nullptr;                // [C][Kp] final lanes
+    int8_t* d_label = nullptr;                 // [cap][N]
+    std::vector<uint64_t> h_keys;
+    int n = 0;                                 // samples of the last call
+    void release() { fwd.release(); samples.release(); Decoder::release(); }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -494,13 +511,14 @@ struct AlphaStats {
 
 // the opaque handle of the C ABI: one track, the pass state of hf_estep over it, the decoders' buffers, the interval getter's buffer,
 // the alpha statistics' plan and buffers, the count moments' buffer, the run moments' buffer, the entropy getters' buffers, the breakpoint
-// getter's and the long-run getter's, the buffers of the posterior under minimum run lengths
+// getter's and the long-run getter's, the buffers of the posterior under minimum run lengths and of the admissible path sampler
 struct hf_ctx {
     Track tr;
     Pass pass;
     Viterbi vit;
     MinLenViterbi mlv;
     MinLenPosterior mlp;
+    MinLenSampler mls;
     Sampler smp;
     DevBuf iv;                // hf_interval.h: pieces, parts, piece products, results
     AlphaStats al;
@@ -1021,6 +1039,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->vit.release();
     ctx->mlv.release();
     ctx->mlp.release();
+    ctx->mls.release();
     ctx->smp.release();
     ctx->iv.release();
     ctx->al.release();
@@ -3209,4 +3228,135 @@ int hf_get_minlen_chunk_log_mass(hf_ctx* ctx, double* log_mass_host, double* log
     const std::vector<double>& z = ctx->mlp.h_chunk;
     for (int64_t c = 0; c < tr.C; c++) log_mass_host[c] = z[(size_t) c] - z[(size_t) (tr.C + c)];
     return log_z_adm_host ? dec_chunk_values(tr, ctx->mlp, log_z_adm_host) : HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// admissible path sampling (hf_minlen_sample.h): whole paths drawn from the posterior under minimum run lengths, a decoder of its own
+// beside the three before it, one code path for both kinds of context.  Last in the file, its kernels included, so that no other
+// kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_sample.h"
+
+static size_t mls_pad(size_t k) { return (k + HF_MLS_GROUP - 1) / HF_MLS_GROUP * HF_MLS_GROUP; }
+
+// every device array of the fixed part but the forward lanes (MinLenSampler::fwd), and the per-sample part for k samples: the ONE place
+// that sizes them (dec_take allocates them, hf_minlen_sample_capacity counts them)
+template <class S, class F> static void mls_arrays(const Track& tr, S& v, F&& f) {
+    dec_front_arrays(tr, v, (size_t) tr.N, f);
+    f(v.d_chunk, (size_t) tr.C * 8);
+}
+template <class S, class F> static void mls_sample_arrays(const Track& tr, S& v, size_t k, F&& f) {
+    const size_t kp = mls_pad(k);
+    f(v.d_keys, k * 8); f(v.d_words, (size_t) tr.N * kp * 2); f(v.d_final, (size_t) tr.C * kp); f(v.d_label, k * (size_t) tr.N);
+}
+static double mls_sample_bytes(const Track& tr, const MinLenSampler& v, size_t k) {
+    double b = 0.0;
+    mls_sample_arrays(tr, v, k, [&](auto&, size_t bytes) { b += (double) Slab::granule(bytes); });
+    return b;
+}
+
+// samples per call at `lanes` lanes: the fixed part and the forward lanes come off nine tenths of the free device memory first; what the
+// sampler holds already counts as free
+static int mls_capacity(const hf_ctx* ctx, int64_t lanes, const std::string& w) {
+    const Track& tr = ctx->tr; const MinLenSampler& v = ctx->mls;
+    HIPCHK(hipSetDevice(tr.device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    double fixed = 0.0;
+    mls_arrays(tr, v, [&](auto&, size_t bytes) { fixed += (double) Slab::granule(bytes); });
+    const double f_bytes = (double) tr.N * (double) lanes * 8.0;
+    const double held = (v.alloc ? fixed : 0.0) + (double) v.fwd.cap + (double) v.samples_bytes;
+    const double budget = 0.9 * ((double) free_b + held) - fixed - f_bytes;
+    if (budget < mls_sample_bytes(tr, v, 1)) {
+        set_err(HF_E_ARG, w + ": the rows, the forward lanes (" + std::to_string((size_t) f_bytes) + " bytes) and one sample do not fit nine tenths of the free device memory");
+        return 0;
+    }
+    int lo = 1, hi = HF_SMP_MAX_PER_CALL;               // the largest k whose arrays fit
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (mls_sample_bytes(tr, v, (size_t) mid) <= budget) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+int hf_minlen_sample_capacity(const hf_ctx* ctx, const int32_t min_len[4]) {
+    const std::string w = "hf_minlen_sample_capacity";
+    if (!ctx || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
+    int64_t lanes = 0;
+    const int rc = minlen_check(w, min_len, &lanes);
+    return rc ? rc : mls_capacity(ctx, lanes, w);
+}
+
+int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], int64_t first_sample, int n_samples, uint64_t seed,
+                           void* stream) {
+    const std::string w = "hf_sample_paths_minlen";
+    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
+    int64_t lanes = 0;
+    int rc = minlen_check(w, min_len, &lanes);
+    if (rc) return rc;
+    if (n_samples < 1) return set_err(HF_E_ARG, w + ": n_samples must be >= 1");
+    if (first_sample < 0) return set_err(HF_E_ARG, w + ": first_sample must be >= 0");
+    const Track& tr = ctx->tr;
+    MinLenSampler& v = ctx->mls;
+    hipStream_t st = (hipStream_t) stream;
+    const double* nbE = nullptr;
+    rc = dec_front(tr, v, p, st, w, [&] {
+        const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
+        if (n_samples > v.cap || f_bytes > v.fwd.cap) {
+            const int cap = mls_capacity(ctx, lanes, w);
+            if (cap < 0) return cap;
+            if (n_samples > cap) return set_err(HF_E_ARG, w + ": n_samples exceeds hf_minlen_sample_capacity (" + std::to_string(cap) + ")");
+        }
+        int rc = dec_alloc(tr, v, [&](auto&& f) { mls_arrays(tr, v, f); });
+        if (rc || (rc = v.fwd.reserve(f_bytes, w))) return rc;
+        if (n_samples > v.cap) {
+            v.samples.release();
+            v.cap = 0; v.samples_bytes = 0;
+            rc = dec_take(v.samples, [&](auto&& f) { mls_sample_arrays(tr, v, (size_t) n_samples, f); });
+            if (rc) return rc;
+            v.cap = n_samples; v.samples_bytes = v.samples.first;
+        }
+        v.h_keys.resize((size_t) n_samples);
+        for (int k = 0; k < n_samples; k++) v.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first_sample + k));
+        HIPCHK(hipMemcpy(v.d_keys, v.h_keys.data(), (size_t) n_samples * 8, hipMemcpyHostToDevice));
+        return (int) HF_OK;
+    }, nbE);
+    if (rc) return rc;
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) n_samples * (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    if (dec_work(tr)) {
+        const int K = n_samples, Kp = (int) mls_pad((size_t) K);
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
+        const unsigned NB = (unsigned) ((tr.N + 255) / 256);
+        hipLaunchKernelGGL(k_dec_rows_win, dim3(NB), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 1), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1,
+                           l2, l3, d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mls_draw, dim3(NB), dim3(256), 0, st, tr.N, tr.d_rec, v.d_rows, l0, l1, l2, l3, d_F, v.d_keys, K, Kp, v.d_words);
+        hipLaunchKernelGGL(k_mls_final, dim3((unsigned) tr.C), dim3(64), 0, st, tr.N, tr.d_off, tr.d_rec, v.d_params, l0, l1, l2, l3, d_F,
+                           v.d_keys, K, Kp, v.d_final);
+        hipLaunchKernelGGL(k_mls_back, dim3((unsigned) tr.C, (unsigned) (Kp / HF_MLS_GROUP)), dim3(64), 0, st, tr.N, tr.d_off, l0, l1, l2, l3,
+                           v.d_words, v.d_final, K, Kp, v.d_label);
+    }
+    HIPCHK(hipGetLastError());
+    v.n = n_samples;
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_sample_minlen_finish(hf_ctx* ctx, void* stream) {
+    if (!ctx || !ctx->mls.launched) return set_err(HF_E_ARG, "hf_sample_minlen_finish: no hf_sample_paths_minlen to finish");
+    const int rc = dec_finish(ctx->tr, ctx->mls, stream);
+    if (rc) return rc;
+    ctx->mls.done = true;
+    return HF_OK;
+}
+
+int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
+    if (!ctx || !labels_host || !ctx->mls.done) return set_err(HF_E_ARG, "hf_get_minlen_sample_labels: no finished hf_sample_paths_minlen");
+    if (k < 0 || k >= ctx->mls.n) return set_err(HF_E_ARG, "hf_get_minlen_sample_labels: k out of range");
+    const Track& tr = ctx->tr;
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mls.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
 }

@@ -623,6 +623,38 @@ class EMList:
                 N.check(self._L.hf_get_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_sample_labels")
         return out
 
+    def minlen_sample_capacity(self, min_len) -> int:
+        """Samples one hf_sample_paths_minlen call may draw at these lengths (hf_minlen_sample_capacity)."""
+        ml = self._four_lengths("minlen_sample_capacity", min_len)
+        cap = int(self._L.hf_minlen_sample_capacity(self._h, ml.ctypes.data_as(C.POINTER(C.c_int32))))
+        if cap < 0:
+            raise N.HFError(cap, "hf_minlen_sample_capacity")
+        return cap
+
+    def sample_paths_minlen(self, model: HMM, min_len, n_samples: int, seed: int, first_sample: int = 0) -> np.ndarray:
+        """Samples first_sample .. first_sample + n_samples - 1 of the posterior given that every run has at least min_len[s] windows
+        (runs at a chunk's ends are exempt; hf_sample_paths_minlen, in calls of at most minlen_sample_capacity samples):
+        int8[n_samples][n_windows], every chunk's path admissible, -1 outside chunks.  The last pass's results and every other
+        decoder's are left as they were."""
+        ml = self._four_lengths("sample_paths_minlen", min_len)
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("sample_paths_minlen: n_samples must be >= 1")
+        p = model.params()
+        out = np.empty((n_samples, self.store.n_windows), dtype=np.int8)
+        cap = self.minlen_sample_capacity(ml)
+        if cap < 1:
+            raise N.HFError(N.HF_E_ARG, "hf_minlen_sample_capacity")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
+        for k0 in range(0, n_samples, cap):
+            n = min(cap, n_samples - k0)
+            N.check(self._L.hf_sample_paths_minlen(self._h, C.byref(p), mlp, int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths_minlen")
+            N.check(self._L.hf_sample_minlen_finish(self._h, self.stream), "hf_sample_minlen_finish")
+            for k in range(n):
+                N.check(self._L.hf_get_minlen_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_minlen_sample_labels")
+        return out
+
     def interval_log_probs(self, first, last, mask) -> np.ndarray:
         """Exact interval probabilities under the model of the last full pass (hf_get_interval_log_probs): for every job i,
         log P(every window of first[i]..last[i] (inclusive) has a state in the set mask[i] (bit s = state s) | data) -> float64[n].
@@ -899,6 +931,14 @@ def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.n
     if not hasattr(emList, "sample_paths"):
         raise TypeError("EM_samplePathsForList: %s has no path sampler" % type(emList).__name__)
     return emList.sample_paths(model, n_samples, seed)
+
+
+def EM_sampleMinLengthPathsForList(emList, model: HMM, min_len, n_samples: int, seed: int) -> np.ndarray:
+    """n_samples admissible paths drawn from the posterior under minimum run lengths with the model's current parameters (no counterpart
+    in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k, min_len) alone.  `emList`: an EMList."""
+    if not hasattr(emList, "sample_paths_minlen"):
+        raise TypeError("EM_sampleMinLengthPathsForList: %s has no admissible path sampler" % type(emList).__name__)
+    return emList.sample_paths_minlen(model, min_len, n_samples, seed)
 
 
 def EM_getIntervalLogProbsForList(emList, first, last, mask) -> np.ndarray:

@@ -554,6 +554,45 @@ int hf_get_minlen_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_
 int hf_get_minlen_posterior_labels(hf_ctx *ctx, int8_t *labels_host);                 /* [n_windows], -1 outside chunks */
 int hf_get_minlen_chunk_log_mass(hf_ctx *ctx, double *log_mass_host, double *log_z_adm_host);       /* [n_chunks]; log_z_adm_host may be NULL */
 
+/* Admissible path sampling (flagger_amd/csrc/hf_minlen_sample.h): whole paths drawn from the posterior under minimum run lengths.
+ * first[s], A_t[p][s], end[s], min_len[4], admissibility (runs that contain a chunk's first or last window are exempt), the lanes (s, d)
+ * and the lane index are hf_viterbi_minlen's; F_t is hf_minlen_posterior's forward vector: the same recursion, sum orders and rescaling,
+ * so the same bits.  A sample of a chunk is an admissible path drawn with probability weight(path) / Z_adm, the distribution whose
+ * marginals hf_get_minlen_posterior returns.  It is drawn by backward sampling over the expanded chain.
+ * UNIFORMS: hf_sample_paths': key_k, then u(k, i), i the global window index t for the draw of window t and i = n_windows + c for
+ * chunk c's final lane.  A sample depends on (seed, absolute sample index, window, lengths) and nothing else.
+ * THE DRAW RULE over a candidate list, hf_sample_paths': weights w_0..w_{n-1}; c_0 = w_0, c_i = c_{i-1} + w_i; x = u * c_{n-1}; the
+ * smallest i with x < c_i, else the largest i with w_i > 0, else 0.
+ *   the final lane of chunk c   the candidates are all sum(min_len) lanes in lane order, w_l = F_{T-1}[l] * end[s(l)]; the cumulative
+ *                               sums run strictly left to right (a prefix, not the tree of the wave sums)
+ *   the lane at t-1 given lane (s, d) at window t >= 1 of the chunk, m_s = min_len[s]:
+ *     d = 1 (the entry lane; the only lane when m_s = 1)   four slots p = 0..3, w_p = F_{t-1}[(p, m_p)] * A_t[p][s], w_s replaced by 0
+ *                                                          when m_s > 1; the result is (p, m_p)
+ *     1 < d < m_s                                          (s, d-1), no draw
+ *     d = m_s > 1                                          two slots, w_0 = F_{t-1}[(s, m_s - 1)] * A_t[s][s] ("arrived"),
+ *                                                          w_1 = F_{t-1}[(s, m_s)] * A_t[s][s] ("stayed"): (s, m_s - 1) or (s, m_s)
+ * SCALING BEFORE THE PRODUCTS.  The eight F_{t-1} values a window's draws read (the four saturated lanes (p, m_p) and the four lanes
+ * (p, m_p - 1) below them, where m_p > 1) are first scaled by 2^-e, e = ilogb of the largest of the eight (0 when that is 0 or not
+ * finite): the stored lanes can sit near 2e-270, and a floored row would push the products into the subnormals.  The final weights'
+ * lanes are scaled the same way by the largest lane of F_{T-1}.  A power of two changes no comparison.
+ * Exact cases.  With all four lengths 1 this is hf_sample_paths' rule word for word.  A chunk without windows draws nothing.  Windows
+ * outside every chunk get label -1.
+ * HF_E_SCALE: a chunk's Z_adm is not > 0.  HF_E_NAN: a NaN in a row or in the end column.  HF_E_ARG: the length cases of
+ * hf_viterbi_minlen; n_samples < 1 or above hf_minlen_sample_capacity; first_sample < 0; k out of range; a getter before a finished call.
+ * hf_minlen_sample_capacity: the samples per call at these lengths (at most 65535): the rows (128 bytes per window), the forward lanes
+ * (8 * sum(min_len) bytes per window) and about 3 bytes per window and sample (the words for a multiple of 64 samples) within nine
+ * tenths of the free device memory, what the sampler holds already counting as free; 0, with hf_last_error, when not one sample fits.
+ * Streams: as hf_viterbi_minlen (hf_sample_minlen_finish takes the stream of the call).  Buffers of its own, the forward lanes
+ * included: the results of the last pass, hf_viterbi, hf_viterbi_minlen, hf_sample_paths and hf_minlen_posterior, and the next
+ * hf_estep, are bitwise unaffected.  One code path serves HF_ALGO_SCAN and HF_ALGO_SEQ contexts and all three model types: the samples
+ * are bitwise the same on both kinds of context, across repeated calls, on any stream and however they are grouped into calls.
+ * hf_batch_* and hf_multi_* have no counterpart. */
+int hf_minlen_sample_capacity(const hf_ctx *ctx, const int32_t min_len[4]);   /* samples per call; <= 0 with hf_last_error when not even one fits */
+int hf_sample_paths_minlen(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4],
+                           int64_t first_sample, int n_samples, uint64_t seed, void *stream);   /* asynchronous */
+int hf_sample_minlen_finish(hf_ctx *ctx, void *stream);
+int hf_get_minlen_sample_labels(hf_ctx *ctx, int k, int8_t *labels_host);      /* sample first_sample + k, [n_windows], -1 outside chunks */
+
 /* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
  * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
  *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]

@@ -24,8 +24,10 @@ def kernels(path):
     for name in names:
         start = next(i for i, ln in enumerate(lines) if ln.startswith(name + ":"))
         end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        # the number of the function inside its labels moves with the file, not with the kernel
-        body = [re.sub(r"\.LBB\d+_", ".LBB_", ln) for ln in lines[start + 1:end]]
+        # the number of the function inside its labels moves with the file, not with the kernel (template kernels are emitted behind
+        # every plain one, so a new plain kernel renumbers them; the loop comments name the header as BB<n>_<m>, without the .L)
+        # ... and the comment column is padded after the label as written, a digit more or less
+        body = [re.sub(r"\s+;", " ;", re.sub(r"\bBB\d+_", "BB_", re.sub(r"\.LBB\d+_", ".LBB_", ln))) for ln in lines[start + 1:end]]
         info = {}
         for i in range(end, len(lines)):
             for key, pat in FIG:
