@@ -1,6 +1,14 @@
 // hf_cli.cpp — `hmm_flagger` command line of the MI355X build: same options, inputs and output files as
 // mobinasri/flagger programs/src/hmm_flagger.c (main :611-1077, runHMMFlagger :285-488), with every E-step
 // delegated to the HIP kernels through the C ABI (include/hmm_flagger_hip.h).  No CPU E-step exists here.
+//
+// The stages, in the order main() calls them; all but the first take the session (struct Run: options, table, context):
+//   parse_options, read_environment   argv and the three HF_* variables -> Options
+//   check_options      every refusal before the input is read; the preset, the --sweepAlpha list, the alpha TSV, the region file, the lengths
+//                      in windows (min_len_windows, called again once a .bin input has shown its window length)
+//   load_input, make_model, create_context   the table and the collapsed components; createModel; one hf_ctx or the sharded GPU list
+//   run_em             one whole run into a directory: em_loop, final_inference, final_outputs, late_outputs
+//   sweep_batched | sweep_sequential, write_sweep_table   --sweepAlpha: every candidate through hf_batch, or through run_em
 #include "../../include/hmm_flagger_hip.h"
 #include "../../include/hmm_flagger_io.h"
 #include "../../include/hmm_flagger_model.h"
@@ -41,7 +49,13 @@ static double cpu_time() {
 }
 static double peak_rss_gb() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024.0 / 1073741824.0; }
 
-static struct option long_options[] = {                    // hmm_flagger.c:578-608
+// the options without a letter: their codes in long_options and in parse_options' switch
+enum LongOnly {
+    kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
+    kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
+    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples
+};
+static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
     {"iterations", required_argument, nullptr, 'n'}, {"convergenceTol", required_argument, nullptr, 't'},
     {"disableAdjustContigEnds", no_argument, nullptr, 'e'}, {"minReadFractionAtEnds", required_argument, nullptr, 'f'},
@@ -59,28 +73,28 @@ static struct option long_options[] = {                    // hmm_flagger.c:578-
     {"minimumLengths", required_argument, nullptr, 'M'},
     // additions of this build (not in the reference), named so that every unique prefix the reference's getopt_long accepted
     // still resolves to the same option (tests/test_cli_prefix_cpu.py): nothing new starts like an existing name's prefix
-    {"device", required_argument, nullptr, 1001},
-    {"hipAlgo", required_argument, nullptr, 1002},         // scan (default) | seq (the on-device sequential cross-check)
-    {"gpus", required_argument, nullptr, 1003},            // chunks sharded over GPUs device..device+N-1, one RCCL all-gather per pass
-    {"exchange", required_argument, nullptr, 1004},        // chunks (default: bit-identical for every N) | ranks (one vector per GPU: faster)
-    {"viterbi", no_argument, nullptr, 1005},               // final labels by most-probable path (hf_viterbi) instead of posterior argmax
-    {"sweepAlpha", required_argument, nullptr, 1006},      // one run per alpha TSV of a list, one load (not `alpha...`: --alpha stays unique)
-    {"uncertaintySamples", required_argument, nullptr, 1007},   // N posterior path samples after the final inference (hf_sample_paths)
-    {"uncertaintySeed", required_argument, nullptr, 1008},      // their seed [0]
-    {"runConfidence", no_argument, nullptr, 1009},              // exact per-run label probabilities (hf_get_interval_log_probs)
-    {"regionProbs", required_argument, nullptr, 1010},          // exact per-region label probabilities for the regions of a BED file
-    {"fitAlpha", no_argument, nullptr, 1011},                   // fit the alpha matrix inside the EM (hf_get_alpha_stats, hfm_estimate_alpha)
-    {"fitAlphaEntries", required_argument, nullptr, 1012},      // the free entries, pre,state pairs separated by ':'
-    {"fitAlphaMax", required_argument, nullptr, 1013},          // their upper bound [0.8]
-    {"fitAlphaEvery", required_argument, nullptr, 1014},        // every P-th iteration is an alpha-iteration [2]
-    {"exactTotals", no_argument, nullptr, 1015},                // exact mean and SD of the label totals (hf_get_count_moments)
-    {"numBlocks", no_argument, nullptr, 1016},                  // exact mean and SD of the block counts (hf_get_run_moments)
-    {"jointEntropy", no_argument, nullptr, 1017},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
-    {"runBoundaries", no_argument, nullptr, 1018},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
-    {"keptBlocks", no_argument, nullptr, 1020},                 // exact probability of a block --minimumLengths would keep (hf_get_long_run_log_probs)
-    {"enforceMinimumLengths", no_argument, nullptr, 1019},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
-    {"constrainedPosterior", no_argument, nullptr, 1021},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
-    {"admissibleSamples", required_argument, nullptr, 1022},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
+    {"device", required_argument, nullptr, kOptDevice},
+    {"hipAlgo", required_argument, nullptr, kOptHipAlgo},         // scan (default) | seq (the on-device sequential cross-check)
+    {"gpus", required_argument, nullptr, kOptGpus},            // chunks sharded over GPUs device..device+N-1, one RCCL all-gather per pass
+    {"exchange", required_argument, nullptr, kOptExchange},        // chunks (default: bit-identical for every N) | ranks (one vector per GPU: faster)
+    {"viterbi", no_argument, nullptr, kOptViterbi},               // final labels by most-probable path (hf_viterbi) instead of posterior argmax
+    {"sweepAlpha", required_argument, nullptr, kOptSweepAlpha},      // one run per alpha TSV of a list, one load (not `alpha...`: --alpha stays unique)
+    {"uncertaintySamples", required_argument, nullptr, kOptUncertaintySamples},   // N posterior path samples after the final inference (hf_sample_paths)
+    {"uncertaintySeed", required_argument, nullptr, kOptUncertaintySeed},      // their seed [0]
+    {"runConfidence", no_argument, nullptr, kOptRunConfidence},              // exact per-run label probabilities (hf_get_interval_log_probs)
+    {"regionProbs", required_argument, nullptr, kOptRegionProbs},          // exact per-region label probabilities for the regions of a BED file
+    {"fitAlpha", no_argument, nullptr, kOptFitAlpha},                   // fit the alpha matrix inside the EM (hf_get_alpha_stats, hfm_estimate_alpha)
+    {"fitAlphaEntries", required_argument, nullptr, kOptFitAlphaEntries},      // the free entries, pre,state pairs separated by ':'
+    {"fitAlphaMax", required_argument, nullptr, kOptFitAlphaMax},          // their upper bound [0.8]
+    {"fitAlphaEvery", required_argument, nullptr, kOptFitAlphaEvery},        // every P-th iteration is an alpha-iteration [2]
+    {"exactTotals", no_argument, nullptr, kOptExactTotals},                // exact mean and SD of the label totals (hf_get_count_moments)
+    {"numBlocks", no_argument, nullptr, kOptNumBlocks},                  // exact mean and SD of the block counts (hf_get_run_moments)
+    {"jointEntropy", no_argument, nullptr, kOptJointEntropy},               // exact path entropy and log-probability of the final labels (hf_get_path_entropy)
+    {"runBoundaries", no_argument, nullptr, kOptRunBoundaries},              // exact posterior of every block boundary (hf_get_breakpoints; not `b...`: --b stays --binArrayFile)
+    {"keptBlocks", no_argument, nullptr, kOptKeptBlocks},                 // exact probability of a block --minimumLengths would keep (hf_get_long_run_log_probs)
+    {"enforceMinimumLengths", no_argument, nullptr, kOptEnforceMinLen},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
+    {"constrainedPosterior", no_argument, nullptr, kOptConstrainedPosterior},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
+    {"admissibleSamples", required_argument, nullptr, kOptAdmissibleSamples},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -197,40 +211,74 @@ static double random_factor(double dev) {                  // hmm_flagger.c:113-
     return (double) rand() / (double) (RAND_MAX / (end - start)) + start;
 }
 
-struct Run;
-static const char* run_error();
 static std::string g_cli_error;      // an error of the command line's own (a table set that failed), reported like the library's
 static void hf_cli_set_error(const std::string& e) { g_cli_error = e; }
 static const char* cli_error_or(const char* lib) { return g_cli_error.empty() ? lib : g_cli_error.c_str(); }
-static void summary_wait_quietly();
-static int die_estep(int rc) {
-    summary_wait_quietly();                                                         // (a worker still writing tables: let it finish before the process unwinds)
-    if (rc == HF_E_SCALE) fprintf(stderr, "scale is very low!\n");                 // hmm.c:413
-    else if (rc == HF_E_NAN) fprintf(stderr, "[Error] prob is NAN\n");             // hmm_utils.c:784
-    else fprintf(stderr, "[%s] Error: %s\n", ts(), run_error());
-    return EXIT_FAILURE;
-}
 
-// the E-step behind runHMMFlagger: one context on one GPU, or the sharded multi-GPU list (hmm_flagger_multi.h)
+// every value that comes from argv or from the environment, with its default; check_options fills in what the preset decides
+struct Options {
+    const char *program = nullptr, *trackName = "final_hmm_flagger";
+    std::string preset = "hifi";
+    const char *inputPath = nullptr, *alphaTsvPath = nullptr, *contigListPath = nullptr, *outputDir = nullptr, *sweepListPath = nullptr;
+    int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
+    double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0, initialRandomDeviation = 0.0;
+    bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
+    bool viterbi = false, enforceMinLen = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
+    int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
+    int admissibleSamples = 0; bool admissibleSet = false;
+    bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
+    const char* regionProbsPath = nullptr;
+    bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
+    uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
+    double fitAlphaMax = 0.8;                                                          // its --upperBound (its --lowerBound is 0)
+    int fitAlphaEvery = 2;
+    int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1;
+    const char* binArrayFilePath = nullptr;
+    bool writeBenchmarkingStatsPerIteration = false;
+    double overlapRatioThreshold = 0.4;
+    std::vector<std::string> labelNames;
+    int32_t minLenPerState[4] = {0, 0, 0, 0};
+    int loopbackRanks = 0;     // test transport, not an option: HF_LOOPBACK_RANKS=N runs N ranks that share ONE GPU (no RCCL) through the multi-GPU path
+    bool phaseTiming = false;  // HF_CLI_TIMING=1: wall time of every phase on stderr (where does a run go now that the E-step is milliseconds?)
+    bool warmPasses = true;    // HF_CLI_WARM=0: bring up the runtime only
+};
+
+// --regionProbs: a region of a BED3+ file (ctg start end [name])
+struct Region { std::string ctg, name; int64_t start, end; };
+
+// The session of a run, with the E-step behind runHMMFlagger: one context on one GPU, or the sharded multi-GPU list (hmm_flagger_multi.h)
 struct Run {
+    Options opt;
+    std::vector<Region> regions;                               // --regionProbs
+    std::vector<std::string> sweepPaths;                       // --sweepAlpha: the TSVs of the list and what they hold
+    std::vector<std::vector<double>> sweepAlphas;
+    double alpha[16] = {0};                                    // --alphaTsv
+    int32_t minLenWindows[4] = {1, 1, 1, 1};                   // --minimumLengths in windows (min_len_windows)
+    hf_windows w{};                                            // the table's windows, once the input is read (load_input)
+    int64_t N = 0; int nChunks = 0;
+    double realtimeStart = 0.0, phaseStart = 0.0;
+    void phase(const char* name) {
+        if (!opt.phaseTiming) return;
+        const double now = real_time();
+        fprintf(stderr, "[phase] %-28s %8.1f ms\n", name, (now - phaseStart) * 1e3);
+        phaseStart = now;
+    }
     hf_ctx* ctx = nullptr;
     hf_multi* multi = nullptr;
     hfio_table* tab = nullptr;
     std::vector<double> stats;
+    static hf_params params(hfm_model* m) { hf_params p; hfm_params(m, &p); return p; }
     int estep(hfm_model* m, int mode, double* out) {
-        hf_params p;
-        hfm_params(m, &p);
+        const hf_params p = params(m);
         if (multi) return hf_multi_estep(multi, &p, mode, out);
         int rc = hf_estep(ctx, &p, mode, nullptr);
         if (rc == HF_OK) rc = hf_finish(ctx, out, nullptr);
         return rc;
     }
-    int estep(hfm_model* m, int mode) { return estep(m, mode, stats.data()); }
     int labels(int8_t* out) { return multi ? hf_multi_get_labels(multi, out) : hf_get_labels(ctx, out); }
     // most-probable path with the model's current parameters: labels (list order) and the run's log-probability
     int viterbi(hfm_model* m, int8_t* out, double* log_prob) {
-        hf_params p;
-        hfm_params(m, &p);
+        const hf_params p = params(m);
         if (multi) {
             const int rc = hf_multi_viterbi(multi, &p, log_prob);
             return rc != HF_OK ? rc : hf_multi_get_viterbi_labels(multi, out);
@@ -241,15 +289,13 @@ struct Run {
     }
     // ... among the paths whose runs meet min_len windows per state (one GPU)
     int viterbi_minlen(hfm_model* m, const int32_t min_len[4], int8_t* out, double* log_prob) {
-        hf_params p;
-        hfm_params(m, &p);
+        const hf_params p = params(m);
         int rc = hf_viterbi_minlen(ctx, &p, min_len, nullptr);
         if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
         return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
     }
     int minlen_posterior(hfm_model* m, const int32_t min_len[4], double* log_mass_total) {
-        hf_params p;
-        hfm_params(m, &p);
+        const hf_params p = params(m);
         const int rc = hf_minlen_posterior(ctx, &p, min_len, nullptr);
         return rc != HF_OK ? rc : hf_minlen_posterior_finish(ctx, log_mass_total, nullptr);
     }
@@ -273,6 +319,13 @@ struct SummaryJob {
 };
 static std::vector<std::unique_ptr<SummaryJob>> g_summaries;
 static void summary_wait_quietly() { for (auto& j : g_summaries) if (j->th.joinable()) j->th.join(); }
+static int die_estep(int rc) {
+    summary_wait_quietly();                                                         // (a worker still writing tables: let it finish before the process unwinds)
+    if (rc == HF_E_SCALE) fprintf(stderr, "scale is very low!\n");                 // hmm.c:413
+    else if (rc == HF_E_NAN) fprintf(stderr, "[Error] prob is NAN\n");             // hmm_utils.c:784
+    else fprintf(stderr, "[%s] Error: %s\n", ts(), run_error());
+    return EXIT_FAILURE;
+}
 // --sweepAlpha: wait for every table worker; a failed table set is reported and fails its candidate only (the sweep goes on)
 static bool summary_join_report() {
     summary_wait_quietly();
@@ -288,8 +341,7 @@ static void summary_join() {
         if (j->rc != 0) { fprintf(stderr, "[%s] %s\n", ts(), j->err.c_str()); exit(EXIT_FAILURE); }
 }
 // `labels`: the labels of the pass when the caller has them already (N bytes), nullptr: they are fetched here
-static int write_summary(Run& run, const std::string& dir, const std::string& suffix, const std::vector<std::string>& labelNames,
-                         const char* binArrayFilePath, double overlapRatioThreshold, int threads, const int8_t* labels) {
+static int write_summary(Run& run, const std::string& dir, const std::string& suffix, const int8_t* labels) {
     const double t_begin = real_time();
     const int64_t N = hfio_n_windows(run.tab);
     // At most three table sets in flight (--writeBenchmarkingStatsPerIteration starts one per EM iteration, an iteration takes
@@ -314,8 +366,9 @@ static int write_summary(Run& run, const std::string& dir, const std::string& su
         if (rc != HF_OK) return rc;
     }
     job->path = dir + "/prediction_summary_" + suffix + ".tsv";
-    const bool timing = getenv("HF_CLI_TIMING") != nullptr;
-    job->th = std::thread([&run, job, labelNames, binArrayFilePath, overlapRatioThreshold, threads, suffix, timing, t_begin] {
+    const bool timing = run.opt.phaseTiming;
+    job->th = std::thread([&run, job, labelNames = run.opt.labelNames, binArrayFilePath = run.opt.binArrayFilePath,
+                           overlapRatioThreshold = run.opt.overlapRatioThreshold, threads = run.opt.threads, suffix, timing, t_begin] {
         std::vector<const char*> names;
         for (const auto& s : labelNames) names.push_back(s.c_str());
         if (hfio_write_summary(run.tab, job->labels.data(), job->path.c_str(), binArrayFilePath, names.empty() ? nullptr : names.data(),
@@ -473,7 +526,6 @@ static int write_sample_outputs(const PathSampler& smp, hfm_model* model, const 
 }
 
 // --regionProbs: the regions of a BED3+ file (ctg start end [name]), every line checked before the input is read
-struct Region { std::string ctg, name; int64_t start, end; };
 static bool read_regions(const char* path, std::vector<Region>& regions) {
     FILE* f = fopen(path, "r");
     if (!f) { fprintf(stderr, "[%s] Error: --regionProbs: cannot read %s\n", ts(), path); return false; }
@@ -1063,41 +1115,42 @@ static bool read_sweep_list(const char* listPath, std::vector<std::string>& path
 // closes the log-likelihood table of a run however the run ends (a failed E-step leaves what it wrote, as a separate process does)
 struct FileCloser { FILE*& f; ~FileCloser() { if (f) fclose(f); f = nullptr; } };
 
-int main(int argc, char* argv[]) {
-    const char* trackName = "final_hmm_flagger";
-    std::string preset = "hifi";
-    const char *inputPath = nullptr, *alphaTsvPath = nullptr, *contigListPath = nullptr, *outputDir = nullptr, *sweepListPath = nullptr;
-    int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
-    double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0;
-    double initialRandomDeviation = 0.0;
-    bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
-    int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false;
-    uint64_t uncertaintySeed = 0;
-    int admissibleSamples = 0; bool admissibleSet = false;
-    bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
-    const char* regionProbsPath = nullptr;
-    bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
-    uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
-    double fitAlphaMax = 0.8;                                                          // its --upperBound (its --lowerBound is 0)
-    int fitAlphaEvery = 2;
-    int modelType = -1, device = 0, algo = HF_ALGO_SCAN, nGpus = 0, exchange = -1, loopbackRanks = 0;
-    const char* binArrayFilePath = nullptr;
-    bool writeBenchmarkingStatsPerIteration = false;
-    double overlapRatioThreshold = 0.4;
-    std::vector<std::string> labelNames;
-    int32_t minLenPerState[4] = {0, 0, 0, 0};
-    const char* program = strrchr(argv[0], '/');
-    program = program ? program + 1 : argv[0];
+// a positive integer that fits an int, or -1
+static int positive_int(const char* s) {
+    char* end = nullptr;
+    const long v = strtol(s, &end, 10);
+    return (end != s && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
+}
+
+// the options that only raise a flag or store their argument (as text, atoi, atof): code -> member; parse_options' switch has the others
+static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
+    {'B', &Options::dumpBin}, {'k', &Options::writeBenchmarkingStatsPerIteration}, {'w', &Options::writeParamsPerIter}, {'P', &Options::writePosterior},
+    {'s', &Options::acceleration}, {kOptViterbi, &Options::viterbi}, {kOptRunConfidence, &Options::runConfidence}, {kOptExactTotals, &Options::exactTotals},
+    {kOptNumBlocks, &Options::numBlocks}, {kOptRunBoundaries, &Options::runBoundaries}, {kOptJointEntropy, &Options::jointEntropy}, {kOptFitAlpha, &Options::fitAlpha},
+    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}};
+static const struct { int code; const char* Options::*text; } kTextOptions[] = {
+    {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
+    {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath}};
+static const struct { int code; int Options::*number; } kIntOptions[] = {
+    {'n', &Options::numberOfIterations}, {'p', &Options::numberOfCollapsedComps}, {'@', &Options::threads}, {'C', &Options::chunkLen}, {'W', &Options::windowLen},
+    {kOptDevice, &Options::device}, {kOptGpus, &Options::nGpus}};
+static const struct { int code; double Options::*real; } kRealOptions[] = {
+    {'t', &Options::convergenceTol}, {'f', &Options::minReadFractionAtEnds}, {'v', &Options::overlapRatioThreshold}, {'D', &Options::initialRandomDeviation},
+    {'q', &Options::maxHighMapqRatio}, {'Q', &Options::minHighMapqRatio}};
+
+// argv -> o.  false: the command line ends here (a message or the usage is printed); only --minimumLengths' format and --exchange's value
+// are refused this early, so they win over every check of check_options
+static bool parse_options(int argc, char* argv[], Options& o) {
+    o.program = strrchr(argv[0], '/');
+    o.program = o.program ? o.program + 1 : argv[0];
     // "--e" and "--ex" were unique prefixes of --exchange until --exactTotals came, "--ru" and "--run" of --runConfidence until
     // --runBoundaries came: they keep their meaning (the rule of long_options above: a prefix that resolved once resolves to the same
     // option in every later build)
-    struct Kept { const char* pre; const char* full; };
-    static const Kept kept[] = {{"--ex", "--exchange"}, {"--e", "--exchange"}, {"--run", "--runConfidence"}, {"--ru", "--runConfidence"}};
-    std::vector<std::string> rewritten;
+    static const struct { const char *pre, *full; } kept[] = {{"--ex", "--exchange"}, {"--e", "--exchange"}, {"--run", "--runConfidence"}, {"--ru", "--runConfidence"}};
+    static std::vector<std::string> rewritten;                   // (argv points into it from here on)
     rewritten.reserve((size_t) argc);
     for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; i++)
-        for (const Kept& k : kept) {
+        for (const auto& k : kept) {
             const size_t n = strlen(k.pre);
             if (strncmp(argv[i], k.pre, n) == 0 && (argv[i][n] == '\0' || argv[i][n] == '=')) {
                 rewritten.push_back(std::string(k.full) + (argv[i] + n));
@@ -1107,365 +1160,279 @@ int main(int argc, char* argv[]) {
         }
     int c;
     while (~(c = getopt_long(argc, argv, "i:x:f:en:t:m:q:C:W:c:@:p:A:a:wkPo:v:l:D:BN:M:s", long_options, nullptr))) {
+        bool plain = false;
+        for (const auto& p : kFlagOptions) if (p.code == c) { o.*p.flag = true; plain = true; }
+        for (const auto& p : kTextOptions) if (p.code == c) { o.*p.text = optarg; plain = true; }
+        for (const auto& p : kIntOptions) if (p.code == c) { o.*p.number = atoi(optarg); plain = true; }
+        for (const auto& p : kRealOptions) if (p.code == c) { o.*p.real = atof(optarg); plain = true; }
+        if (plain) continue;
         switch (c) {
-            case 'i': inputPath = optarg; break;
-            case 'x': preset = optarg; break;
-            case 'n': numberOfIterations = atoi(optarg); break;
-            case 'B': dumpBin = true; break;
-            case 'N': trackName = optarg; break;
-            case 't': convergenceTol = atof(optarg); break;
-            case 'e': adjustContigEnds = false; break;
-            case 'f': minReadFractionAtEnds = atof(optarg); break;
+            case 'x': o.preset = optarg; break;
+            case 'e': o.adjustContigEnds = false; break;
             case 'm':                                           // hmm_utils.c:18-29
-                if (!strcmp(optarg, "gaussian")) modelType = HF_MODEL_GAUSSIAN;
+                if (!strcmp(optarg, "gaussian")) o.modelType = HF_MODEL_GAUSSIAN;
                 else if (!strcmp(optarg, "trunc_exp_gaussian") || !strcmp(optarg, "truncated_exponential_gaussian"))
-                    modelType = HF_MODEL_TRUNC_EXP_GAUSSIAN;
-                else if (!strcmp(optarg, "nb") || !strcmp(optarg, "negative_binomial")) modelType = HF_MODEL_NEGATIVE_BINOMIAL;
-                else modelType = -2;
+                    o.modelType = HF_MODEL_TRUNC_EXP_GAUSSIAN;
+                else if (!strcmp(optarg, "nb") || !strcmp(optarg, "negative_binomial")) o.modelType = HF_MODEL_NEGATIVE_BINOMIAL;
+                else o.modelType = -2;
                 break;
-            case 'a': binArrayFilePath = optarg; break;
-            case 'k': writeBenchmarkingStatsPerIteration = true; break;
-            case 'v': overlapRatioThreshold = atof(optarg); break;
             case 'l': {                                          // hmm_flagger.c:721-724: names + "Unk"
                 std::string s(optarg);
                 size_t a = 0;
-                labelNames.clear();
+                o.labelNames.clear();
                 while (true) {
                     const size_t b = s.find(',', a);
-                    labelNames.push_back(s.substr(a, b == std::string::npos ? std::string::npos : b - a));
+                    o.labelNames.push_back(s.substr(a, b == std::string::npos ? std::string::npos : b - a));
                     if (b == std::string::npos) break;
                     a = b + 1;
                 }
-                labelNames.push_back("Unk");
+                o.labelNames.push_back("Unk");
                 break;
             }
-            case 'c': contigListPath = optarg; break;
-            case 'p': numberOfCollapsedComps = atoi(optarg); break;
-            case '@': threads = atoi(optarg); break;
-            case 'A': alphaTsvPath = optarg; break;
-            case 'C': chunkLen = atoi(optarg); break;
-            case 'W': windowLen = atoi(optarg); break;
-            case 'w': writeParamsPerIter = true; break;
-            case 'P': writePosterior = true; break;
-            case 'o': outputDir = optarg; break;
-            case 'D': initialRandomDeviation = atof(optarg); break;
-            case 'q': maxHighMapqRatio = atof(optarg); break;
-            case 'Q': minHighMapqRatio = atof(optarg); break;
-            case 's': acceleration = true; break;
             case 'M': {                                          // hmm_flagger.c:737-749
                 int a, b, d;
                 if (sscanf(optarg, "%d,%d,%d", &a, &b, &d) != 3 || strchr(strchr(strchr(optarg, ',') + 1, ',') + 1, ',')) {
-                    fprintf(stderr, "[%s] Error: --minimumLengths should contain only 3 tab-delimited positive integers.\n", ts());
-                    return EXIT_FAILURE;
+                    fprintf(stderr, "[%s] Error: --minimumLengths should contain only 3 tab-delimited positive integers.\n", ts()); return false;
                 }
-                minLenPerState[0] = a; minLenPerState[1] = b; minLenPerState[3] = d;
-                minLenGiven = true;
+                o.minLenPerState[0] = a; o.minLenPerState[1] = b; o.minLenPerState[3] = d;
+                o.minLenGiven = true;
                 break;
             }
-            case 1001: device = atoi(optarg); break;
-            case 1002: algo = !strcmp(optarg, "seq") ? HF_ALGO_SEQ : HF_ALGO_SCAN; break;
-            case 1003: nGpus = atoi(optarg); break;
-            case 1005: viterbi = true; break;
-            case 1006: sweepListPath = optarg; break;
-            case 1007: {
+            case kOptHipAlgo: o.algo = !strcmp(optarg, "seq") ? HF_ALGO_SEQ : HF_ALGO_SCAN; break;
+            case kOptUncertaintySamples: o.uncertaintySet = true; o.uncertaintySamples = positive_int(optarg); break;
+            case kOptUncertaintySeed: {
                 char* end = nullptr;
-                const long v = strtol(optarg, &end, 10);
-                uncertaintySet = true;
-                uncertaintySamples = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
+                o.uncertaintySeed = strtoull(optarg, &end, 10);
+                o.uncertaintySeedBad = end == optarg || *end != 0 || optarg[0] == '-';
                 break;
             }
-            case 1008: {
-                char* end = nullptr;
-                uncertaintySeed = strtoull(optarg, &end, 10);
-                uncertaintySeedBad = end == optarg || *end != 0 || optarg[0] == '-';
-                break;
-            }
-            case 1022: {
-                char* end = nullptr;
-                const long v = strtol(optarg, &end, 10);
-                admissibleSet = true;
-                admissibleSamples = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
-                break;
-            }
-            case 1009: runConfidence = true; break;
-            case 1015: exactTotals = true; break;
-            case 1016: numBlocks = true; break;
-            case 1018: runBoundaries = true; break;
-            case 1017: jointEntropy = true; break;
-            case 1019: enforceMinLen = true; break;
-            case 1020: keptBlocks = true; break;
-            case 1021: constrainedPost = true; break;
-            case 1010: regionProbsPath = optarg; break;
-            case 1011: fitAlpha = true; break;
-            case 1012: {                                         // pre,state[:pre,state...]
-                fitAlphaOptions = true;
-                memset(fitAlphaMask, 0, sizeof fitAlphaMask);
+            case kOptAdmissibleSamples: o.admissibleSet = true; o.admissibleSamples = positive_int(optarg); break;
+            case kOptFitAlphaEntries: {                          // pre,state[:pre,state...]
+                o.fitAlphaOptions = true;
+                memset(o.fitAlphaMask, 0, sizeof o.fitAlphaMask);
                 const char* q = optarg;
                 bool ok = *q != 0;
                 while (ok && *q) {
                     ok = q[0] >= '0' && q[0] <= '3' && q[1] == ',' && q[2] >= '0' && q[2] <= '3' && (q[3] == 0 || (q[3] == ':' && q[4] != 0));
                     if (!ok) break;
-                    fitAlphaMask[(q[0] - '0') * 4 + (q[2] - '0')] = 1;
+                    o.fitAlphaMask[(q[0] - '0') * 4 + (q[2] - '0')] = 1;
                     q += q[3] ? 4 : 3;
                 }
-                if (!ok) fitAlphaBad = true;
+                if (!ok) o.fitAlphaBad = true;
                 break;
             }
-            case 1013: {
+            case kOptFitAlphaMax: {
                 char* end = nullptr;
-                fitAlphaOptions = true;
-                fitAlphaMax = strtod(optarg, &end);
-                if (end == optarg || *end != 0 || !(fitAlphaMax >= 0.0 && fitAlphaMax < 1.0)) fitAlphaMax = -1.0;
+                o.fitAlphaOptions = true;
+                o.fitAlphaMax = strtod(optarg, &end);
+                if (end == optarg || *end != 0 || !(o.fitAlphaMax >= 0.0 && o.fitAlphaMax < 1.0)) o.fitAlphaMax = -1.0;
                 break;
             }
-            case 1014: {
-                char* end = nullptr;
-                fitAlphaOptions = true;
-                const long v = strtol(optarg, &end, 10);
-                fitAlphaEvery = (end != optarg && *end == 0 && v > 0 && v <= INT32_MAX) ? (int) v : -1;
-                break;
-            }
-            case 1004:
-                if (!strcmp(optarg, "chunks")) exchange = HF_EXCHANGE_CHUNKS;
-                else if (!strcmp(optarg, "ranks")) exchange = HF_EXCHANGE_RANKS;
-                else { fprintf(stderr, "[%s] Error: --exchange can be chunks or ranks.\n", ts()); return EXIT_FAILURE; }
+            case kOptFitAlphaEvery: o.fitAlphaOptions = true; o.fitAlphaEvery = positive_int(optarg); break;
+            case kOptExchange:
+                if (!strcmp(optarg, "chunks")) o.exchange = HF_EXCHANGE_CHUNKS;
+                else if (!strcmp(optarg, "ranks")) o.exchange = HF_EXCHANGE_RANKS;
+                else { fprintf(stderr, "[%s] Error: --exchange can be chunks or ranks.\n", ts()); return false; }
                 break;
             default:
-                if (c != 'h') fprintf(stderr, "[E::%s] undefined option %c\n", __func__, c);
-                usage(program);
-                return 1;
+                if (c != 'h') fprintf(stderr, "[E::main] undefined option %c\n", c);
+                usage(o.program);
+                return false;
         }
     }
-    const double realtimeStart = real_time();
-    // HF_CLI_TIMING=1: wall time of every phase on stderr (where does a run go now that the E-step is milliseconds?)
-    const bool phaseTiming = getenv("HF_CLI_TIMING") != nullptr;
-    double phaseStart = realtimeStart;
-    auto phase = [&](const char* name) {
-        if (!phaseTiming) return;
-        const double now = real_time();
-        fprintf(stderr, "[phase] %-28s %8.1f ms\n", name, (now - phaseStart) * 1e3);
-        phaseStart = now;
+    return true;
+}
+
+static void read_environment(Options& o) {
+    if (const char* e = getenv("HF_LOOPBACK_RANKS")) o.loopbackRanks = atoi(e);
+    o.phaseTiming = getenv("HF_CLI_TIMING") != nullptr;
+    o.warmPasses = !(getenv("HF_CLI_WARM") && getenv("HF_CLI_WARM")[0] == '0');
+}
+
+// Which one-GPU rule an option's refusal follows.  The options that came up to --jointEntropy (and --fitAlpha) refuse --gpus N>1 and
+// --sweepAlpha only: under HF_LOOPBACK_RANKS they pass here and fail after the EM with "needs a single-GPU context".  The four that came
+// later refuse HF_LOOPBACK_RANKS here as well.  The difference is today's behaviour and is kept as it is.
+enum OneGpuRule { kNoGpuRule, kOneGpu, kOneGpuNoLoopback };
+// One row of refusals: the option as printed, whether it was given, then what is tried in this order: `refusal` (the rest of the sentence
+// when its argument is bad or an option it needs is missing; nullptr: fine) and its one-GPU rule
+struct OptionCheck { const char* name; bool given; const char* refusal; OneGpuRule rule; };
+template <size_t n> static bool check_rows(const Options& o, const OptionCheck (&rows)[n]) {
+    for (const OptionCheck& r : rows) {
+        if (!r.given) continue;
+        if (r.refusal) { fprintf(stderr, "[%s] Error: %s %s.\n", ts(), r.name, r.refusal); return false; }
+        if (r.rule == kNoGpuRule || !(o.nGpus > 1 || o.sweepListPath || (r.rule == kOneGpuNoLoopback && o.loopbackRanks > 0))) continue;
+        fprintf(stderr, r.rule == kOneGpu ? "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n"
+                                          : "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts(), r.name);
+        return false;
+    }
+    return true;
+}
+
+// --enforceMinimumLengths and its kin: the lengths in windows of W bases.  A run of k windows passes the final BED's `len < minlen` test
+// exactly when k * W >= minlen; Hap has no minimum.  false: they do not fit the lanes (said)
+static bool min_len_windows(Run& s, int W) {
+    const Options& o = s.opt;
+    long long sum = 0;
+    for (int st = 0; st < 4; st++) {
+        const long long w = st == 2 ? 1 : std::max(1LL, ((long long) o.minLenPerState[st] + W - 1) / W);
+        s.minLenWindows[st] = (int32_t) std::min(w, 1000000LL);
+        sum += s.minLenWindows[st];
+    }
+    const int32_t* const mw = s.minLenWindows;
+    // --keptBlocks: one label at a time, each within the lanes of hf_get_long_run_log_probs
+    for (int st = 0; o.keptBlocks && st < 4; st++)
+        if (long_run_lanes(1 << st, mw[st]) > HF_LONGRUN_MAX_LANES) {
+            fprintf(stderr, "[%s] Error: --keptBlocks: the minimum lengths %d,%d,%d (Err,Dup,Col) are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col); a label's may be %d windows at most.\n",
+                    ts(), o.minLenPerState[0], o.minLenPerState[1], o.minLenPerState[3], mw[0], mw[1], mw[2], mw[3], W, HF_LONGRUN_MAX_LANES - 6);
+            return false;
+        }
+    if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
+    std::string who;                                           // the options that walk the expanded chain, as given
+    for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
+                          o.admissibleSet ? "admissibleSamples" : nullptr})
+        if (n) who += (who.empty() ? "" : ", --") + std::string(n);
+    fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
+            ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
+    return false;
+}
+static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet; }
+
+// Everything that can be refused before the input is read, in a fixed order (tests/test_cli_refusals_cpu.py: of two bad options the one
+// checked first is reported).  false: refused (said).  Fills in the session: regions, sweep list, alpha, and the options the preset decides.
+static bool check_options(Run& s) {
+    Options& o = s.opt;
+    const char* const positive = "should be a positive integer";
+    const char* const needsMinLen = o.minLenGiven ? nullptr : "needs --minimumLengths";
+    // the rows in the order of the refusals (--uncertaintySamples has two: the seed's argument is checked between its own argument and its
+    // one-GPU rule); the --fitAlpha group has its place between --jointEntropy and the region file
+    const OptionCheck beforeRegions[] = {
+        {"--uncertaintySamples", o.uncertaintySet, o.uncertaintySamples < 1 ? positive : nullptr, kNoGpuRule},
+        {"--uncertaintySeed", true, o.uncertaintySeedBad ? "should be a non-negative integer" : nullptr, kNoGpuRule},
+        {"--uncertaintySamples", o.uncertaintySet, nullptr, kOneGpu},
+        {o.runConfidence ? "--runConfidence" : "--regionProbs", o.runConfidence || o.regionProbsPath, nullptr, kOneGpu},
+        {"--runBoundaries", o.runBoundaries, nullptr, kOneGpu},
+        {"--exactTotals", o.exactTotals, nullptr, kOneGpu},
+        {"--numBlocks", o.numBlocks, nullptr, kOneGpu},
+        {"--jointEntropy", o.jointEntropy, nullptr, kOneGpu},
+        {"--fitAlphaEntries", true, o.fitAlphaBad ? "should be pre,state pairs of state indices 0..3 separated by ':' (e.g. 0,0:2,2)" : nullptr, kNoGpuRule},
+        {"--fitAlphaMax", true, o.fitAlphaMax < 0.0 ? "should be a number in [0, 1)" : nullptr, kNoGpuRule},
+        {"--fitAlphaEvery", true, o.fitAlphaEvery < 1 ? positive : nullptr, kNoGpuRule},
+        {"--fitAlphaEntries, --fitAlphaMax and --fitAlphaEvery", o.fitAlphaOptions, o.fitAlpha ? nullptr : "need --fitAlpha", kNoGpuRule},
+        {"--fitAlpha", o.fitAlpha, o.acceleration ? "cannot be combined with --accelerate (SQUAREM extrapolates the other parameters only)" : nullptr, kOneGpu},
+        {"--fitAlpha", o.fitAlpha, o.modelType != HF_MODEL_NEGATIVE_BINOMIAL ? nullptr :
+                                   "needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial emission has no alpha)", kNoGpuRule},
     };
-    // --uncertaintySamples: refused combinations, before the input is read
-    if (uncertaintySet && uncertaintySamples < 1) { fprintf(stderr, "[%s] Error: --uncertaintySamples should be a positive integer.\n", ts()); return EXIT_FAILURE; }
-    if (uncertaintySeedBad) { fprintf(stderr, "[%s] Error: --uncertaintySeed should be a non-negative integer.\n", ts()); return EXIT_FAILURE; }
-    if (uncertaintySamples > 0 && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --uncertaintySamples runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    // --runConfidence / --regionProbs: refused combinations, and every line of the region file, before the input is read
-    if ((runConfidence || regionProbsPath) && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: %s runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts(),
-                runConfidence ? "--runConfidence" : "--regionProbs");
-        return EXIT_FAILURE;
-    }
-    if (runBoundaries && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --runBoundaries runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (exactTotals && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --exactTotals runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (numBlocks && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --numBlocks runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (jointEntropy && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --jointEntropy runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    // --fitAlpha: its own arguments and the refused combinations, before the input is read
-    if (fitAlphaBad) {
-        fprintf(stderr, "[%s] Error: --fitAlphaEntries should be pre,state pairs of state indices 0..3 separated by ':' (e.g. 0,0:2,2).\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (fitAlphaMax < 0.0) { fprintf(stderr, "[%s] Error: --fitAlphaMax should be a number in [0, 1).\n", ts()); return EXIT_FAILURE; }
-    if (fitAlphaEvery < 1) { fprintf(stderr, "[%s] Error: --fitAlphaEvery should be a positive integer.\n", ts()); return EXIT_FAILURE; }
-    if (fitAlphaOptions && !fitAlpha) {
-        fprintf(stderr, "[%s] Error: --fitAlphaEntries, --fitAlphaMax and --fitAlphaEvery need --fitAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (fitAlpha && acceleration) {
-        fprintf(stderr, "[%s] Error: --fitAlpha cannot be combined with --accelerate (SQUAREM extrapolates the other parameters only).\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (fitAlpha && (nGpus > 1 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --fitAlpha runs on one GPU: it cannot be combined with --gpus N>1 or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (fitAlpha && modelType == HF_MODEL_NEGATIVE_BINOMIAL) {
-        fprintf(stderr, "[%s] Error: --fitAlpha needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial emission has no alpha).\n", ts());
-        return EXIT_FAILURE;
-    }
-    std::vector<Region> regions;
-    if (regionProbsPath && !read_regions(regionProbsPath, regions)) return EXIT_FAILURE;
-    // test transport, not an option: HF_LOOPBACK_RANKS=N runs N ranks that share ONE GPU (no RCCL) through the multi-GPU path
-    if (const char* e = getenv("HF_LOOPBACK_RANKS")) loopbackRanks = atoi(e);
-    if (nGpus < 0 || nGpus > 64 || loopbackRanks < 0 || loopbackRanks > 64) { fprintf(stderr, "[%s] Error: --gpus should be between 1 and 64.\n", ts()); return EXIT_FAILURE; }
-    if (nGpus > 0 && loopbackRanks > 0) { fprintf(stderr, "[%s] Error: --gpus and HF_LOOPBACK_RANKS exclude each other.\n", ts()); return EXIT_FAILURE; }
-    // --enforceMinimumLengths: refused combinations, before the input is read
-    if (enforceMinLen && !viterbi) { fprintf(stderr, "[%s] Error: --enforceMinimumLengths needs --viterbi.\n", ts()); return EXIT_FAILURE; }
-    if (enforceMinLen && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --enforceMinimumLengths runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    // --keptBlocks: likewise
-    if (keptBlocks && !minLenGiven) { fprintf(stderr, "[%s] Error: --keptBlocks needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
-    if (keptBlocks && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --keptBlocks runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    // --constrainedPosterior: likewise
-    if (constrainedPost && !minLenGiven) { fprintf(stderr, "[%s] Error: --constrainedPosterior needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
-    if (constrainedPost && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --constrainedPosterior runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    // --admissibleSamples: likewise
-    if (admissibleSet && admissibleSamples < 1) { fprintf(stderr, "[%s] Error: --admissibleSamples should be a positive integer.\n", ts()); return EXIT_FAILURE; }
-    if (admissibleSet && !minLenGiven) { fprintf(stderr, "[%s] Error: --admissibleSamples needs --minimumLengths.\n", ts()); return EXIT_FAILURE; }
-    if (admissibleSet && (nGpus > 1 || loopbackRanks > 0 || sweepListPath)) {
-        fprintf(stderr, "[%s] Error: --admissibleSamples runs on one GPU: it cannot be combined with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha.\n", ts());
-        return EXIT_FAILURE;
-    }
-    if (!inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return EXIT_FAILURE; }
-    if (convergenceTol <= 0.0 || convergenceTol > 1.0) {
-        fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), convergenceTol);
-        return EXIT_FAILURE;
-    }
-    if (!outputDir) { fprintf(stderr, "[%s] Error: --outputDir, -o should be specified.\n", ts()); return EXIT_FAILURE; }
-    if (!dir_exists(outputDir)) { fprintf(stderr, "[%s] Error: Output directory %s does not exist!\n", ts(), outputDir); return EXIT_FAILURE; }
+    const OptionCheck afterRegions[] = {
+        {"--gpus", true, o.nGpus < 0 || o.nGpus > 64 || o.loopbackRanks < 0 || o.loopbackRanks > 64 ? "should be between 1 and 64" : nullptr, kNoGpuRule},
+        {"--gpus and HF_LOOPBACK_RANKS", o.nGpus > 0 && o.loopbackRanks > 0, "exclude each other", kNoGpuRule},
+        {"--enforceMinimumLengths", o.enforceMinLen, o.viterbi ? nullptr : "needs --viterbi", kOneGpuNoLoopback},
+        {"--keptBlocks", o.keptBlocks, needsMinLen, kOneGpuNoLoopback},
+        {"--constrainedPosterior", o.constrainedPost, needsMinLen, kOneGpuNoLoopback},
+        {"--admissibleSamples", o.admissibleSet, o.admissibleSamples < 1 ? positive : needsMinLen, kOneGpuNoLoopback},
+    };
+    // (every line of the region file is checked here)
+    if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
+    if (!o.inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return false; }
+    if (o.convergenceTol <= 0.0 || o.convergenceTol > 1.0) { fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), o.convergenceTol); return false; }
+    if (!o.outputDir) { fprintf(stderr, "[%s] Error: --outputDir, -o should be specified.\n", ts()); return false; }
+    if (!dir_exists(o.outputDir)) { fprintf(stderr, "[%s] Error: Output directory %s does not exist!\n", ts(), o.outputDir); return false; }
 
     // presets: hmm_flagger.c:17-58, 536-575, 945-956.  The preset alpha arrays are declared `int`, so every
     // preset alpha is 0: alpha is non-zero only through --alphaTsv (:21,36,50,518-533).
     int presetW; double presetF;
-    if (preset == "hifi") { presetW = 16000; presetF = 0.95; }
-    else if (preset == "ont-r9") { presetW = 16000; presetF = 1.0; }
-    else if (preset == "ont-r10") { presetW = 8000; presetF = 0.8; }
-    else { fprintf(stderr, "[%s] Error: preset can be one of hifi, ont-r9, ont-r10. It cannot be %s . \n", ts(), preset.c_str()); return EXIT_FAILURE; }
-    double alpha[16] = {0};
+    if (o.preset == "hifi") { presetW = 16000; presetF = 0.95; }
+    else if (o.preset == "ont-r9") { presetW = 16000; presetF = 1.0; }
+    else if (o.preset == "ont-r10") { presetW = 8000; presetF = 0.8; }
+    else { fprintf(stderr, "[%s] Error: preset can be one of hifi, ont-r9, ont-r10. It cannot be %s . \n", ts(), o.preset.c_str()); return false; }
     // --sweepAlpha: the list and every TSV in it are checked before the input is read or a device is touched
-    std::vector<std::string> sweepPaths;
-    std::vector<std::vector<double>> sweepAlphas;
-    if (sweepListPath) {
-        if (alphaTsvPath) { fprintf(stderr, "[%s] Error: --sweepAlpha and --alphaTsv exclude each other.\n", ts()); return EXIT_FAILURE; }
-        if (!read_sweep_list(sweepListPath, sweepPaths, sweepAlphas)) return EXIT_FAILURE;
+    if (o.sweepListPath) {
+        if (o.alphaTsvPath) { fprintf(stderr, "[%s] Error: --sweepAlpha and --alphaTsv exclude each other.\n", ts()); return false; }
+        if (!read_sweep_list(o.sweepListPath, s.sweepPaths, s.sweepAlphas)) return false;
     }
-    if (alphaTsvPath) {
-        const int rc = hfm_read_alpha_tsv(alphaTsvPath, alpha);
-        if (rc == -2) { fprintf(stderr, "[%s] Error: There is at least one alpha value in '%s' not between 0 and 1. \n", ts(), alphaTsvPath); return EXIT_FAILURE; }
-        if (rc != 0) { fprintf(stderr, "[%s] Error: cannot read %s\n", ts(), alphaTsvPath); return EXIT_FAILURE; }
+    if (o.alphaTsvPath) {
+        const int rc = hfm_read_alpha_tsv(o.alphaTsvPath, s.alpha);
+        if (rc == -2) { fprintf(stderr, "[%s] Error: There is at least one alpha value in '%s' not between 0 and 1. \n", ts(), o.alphaTsvPath); return false; }
+        if (rc != 0) { fprintf(stderr, "[%s] Error: cannot read %s\n", ts(), o.alphaTsvPath); return false; }
     }
-    if (minReadFractionAtEnds < 0.0 && adjustContigEnds) minReadFractionAtEnds = presetF;
-    if (windowLen < 0) windowLen = presetW;
-    if (modelType == -1) modelType = HF_MODEL_TRUNC_EXP_GAUSSIAN;
-    if (adjustContigEnds && (minReadFractionAtEnds > 1.0 || minReadFractionAtEnds < 0.0)) {
-        fprintf(stderr, "[%s] Error: --minReadFractionAtEnds, -f should be between 0 and 1.\n", ts()); return EXIT_FAILURE;
-    }
-    if (modelType == -2) { fprintf(stderr, "[%s] Error: Model type is not defined. Specify the model type with --model (-m) argument.\n", ts()); return EXIT_FAILURE; }
-    if (windowLen <= 0) { fprintf(stderr, "[%s] Error: windowLen cannot be <= 0.\n", ts()); return EXIT_FAILURE; }
-    // --enforceMinimumLengths: the lengths in windows.  A run of k windows passes the final BED's `len < minlen` test exactly when
-    // k * windowLen >= minlen; Hap has no minimum.  (A bin input carries its own window length: checked again once it is read.)
-    int32_t minLenWindows[4] = {1, 1, 1, 1};
-    auto min_len_windows = [&](int W) {
-        long long sum = 0;
-        for (int s = 0; s < 4; s++) {
-            const long long w = s == 2 ? 1 : std::max(1LL, ((long long) minLenPerState[s] + W - 1) / W);
-            minLenWindows[s] = (int32_t) std::min(w, 1000000LL);
-            sum += minLenWindows[s];
-        }
-        // --keptBlocks: one label at a time, each within the lanes of hf_get_long_run_log_probs
-        for (int s = 0; keptBlocks && s < 4; s++)
-            if (long_run_lanes(1 << s, minLenWindows[s]) > HF_LONGRUN_MAX_LANES) {
-                fprintf(stderr, "[%s] Error: --keptBlocks: the minimum lengths %d,%d,%d (Err,Dup,Col) are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col); a label's may be %d windows at most.\n",
-                        ts(), minLenPerState[0], minLenPerState[1], minLenPerState[3], minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W,
-                        HF_LONGRUN_MAX_LANES - 6);
-                return false;
-            }
-        if (!(enforceMinLen || constrainedPost || admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
-        std::string who;                                           // the options that walk the expanded chain, as given
-        for (const char* o : {enforceMinLen ? "enforceMinimumLengths" : nullptr, constrainedPost ? "constrainedPosterior" : nullptr,
-                              admissibleSet ? "admissibleSamples" : nullptr})
-            if (o) who += (who.empty() ? "" : ", --") + std::string(o);
-        fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
-                ts(), who.c_str(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], W, HF_MINLEN_MAX_LANES);
-        return false;
-    };
-    if ((enforceMinLen || keptBlocks || constrainedPost || admissibleSet) && !min_len_windows(windowLen)) return EXIT_FAILURE;
-    if (0.5 < initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return EXIT_FAILURE; }
+    if (o.minReadFractionAtEnds < 0.0 && o.adjustContigEnds) o.minReadFractionAtEnds = presetF;
+    if (o.windowLen < 0) o.windowLen = presetW;
+    if (o.modelType == -1) o.modelType = HF_MODEL_TRUNC_EXP_GAUSSIAN;
+    if (o.adjustContigEnds && (o.minReadFractionAtEnds > 1.0 || o.minReadFractionAtEnds < 0.0)) { fprintf(stderr, "[%s] Error: --minReadFractionAtEnds, -f should be between 0 and 1.\n", ts()); return false; }
+    if (o.modelType == -2) { fprintf(stderr, "[%s] Error: Model type is not defined. Specify the model type with --model (-m) argument.\n", ts()); return false; }
+    if (o.windowLen <= 0) { fprintf(stderr, "[%s] Error: windowLen cannot be <= 0.\n", ts()); return false; }
+    // (a bin input carries its own window length: load_input checks the lengths again once it is read)
+    if (uses_min_len_windows(o) && !min_len_windows(s, o.windowLen)) return false;
+    if (0.5 < o.initialRandomDeviation) { fprintf(stderr, "[%s] Error: Initial random deviation for the model parameters cannot be greater than 0.5. \n", ts()); return false; }
+    return true;
+}
 
-    // 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
+// 1. windows; the HIP runtime and the device context come up on a second thread while the input is read
+// 2. number of collapsed components (hmm_flagger.c:1008-1022)
+static bool load_input(Run& s) {
+    Options& o = s.opt;
     fprintf(stderr, "[%s] Parsing/Creating coverage chunks. \n", ts());
-    Run run;
-    g_run = &run;
-    const bool warmPasses = !(getenv("HF_CLI_WARM") && getenv("HF_CLI_WARM")[0] == '0');   // HF_CLI_WARM=0: bring up the runtime only
-    std::thread warm([device, warmPasses] { (void) (warmPasses ? hfm_warmup_pipeline(device) : hf_warmup(device)); });
-    run.tab = hfio_load(inputPath, chunkLen, windowLen);
+    std::thread warm([device = o.device, warmPasses = o.warmPasses] { (void) (warmPasses ? hfm_warmup_pipeline(device) : hf_warmup(device)); });
+    s.tab = hfio_load(o.inputPath, o.chunkLen, o.windowLen);
     warm.join();
-    if (!run.tab) { fprintf(stderr, "[%s] %s\n", ts(), hfio_last_error()); return EXIT_FAILURE; }
-    hfio_table* tab = run.tab;
-    if (contigListPath) {                                        // hmm_flagger.c:915-921, 93-99
+    if (!s.tab) { fprintf(stderr, "[%s] %s\n", ts(), hfio_last_error()); return false; }
+    hfio_table* tab = s.tab;
+    if (o.contigListPath) {                                      // hmm_flagger.c:915-921, 93-99
         int nNames = 0;
-        char** names = hfio_read_name_list(contigListPath, &nNames);
-        if (!names) { fprintf(stderr, "[%s] %s\n", ts(), hfio_last_error()); return EXIT_FAILURE; }
+        char** names = hfio_read_name_list(o.contigListPath, &nNames);
+        if (!names) { fprintf(stderr, "[%s] %s\n", ts(), hfio_last_error()); return false; }
         fprintf(stderr, "[%s] Including only the chunks whose contigs match the given contig list.\n", ts());
         hfio_subset_contigs(tab, names, nNames);
         for (int i = 0; i < nNames; i++) free(names[i]);
         free(names);
     }
-    if (dumpBin) {
+    if (o.dumpBin) {
         char binPath[2200];
-        snprintf(binPath, sizeof binPath, "%s/chunks.c_%d.w_%d.bin", outputDir, hfio_chunk_len(tab), hfio_window_len(tab));
+        snprintf(binPath, sizeof binPath, "%s/chunks.c_%d.w_%d.bin", o.outputDir, hfio_chunk_len(tab), hfio_window_len(tab));
         fprintf(stderr, "[%s] Writing bin file into %s . \n", ts(), binPath);
-        if (hfio_write_bin(tab, binPath) != 0) { fprintf(stderr, "[%s] Error: cannot write %s\n", ts(), binPath); return EXIT_FAILURE; }
+        if (hfio_write_bin(tab, binPath) != 0) { fprintf(stderr, "[%s] Error: cannot write %s\n", ts(), binPath); return false; }
     }
-    const int64_t N = hfio_n_windows(tab);
-    fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), hfio_n_chunks(tab), (long) N, hfio_window_len(tab));
-    if (N == 0 || hfio_n_chunks(tab) == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return EXIT_FAILURE; }
+    hfio_windows(tab, &s.w);
+    s.N = hfio_n_windows(tab);
+    s.nChunks = hfio_n_chunks(tab);
+    fprintf(stderr, "[%s] %d chunks are parsed (%ld windows of %d bases). \n", ts(), s.nChunks, (long) s.N, hfio_window_len(tab));
+    if (s.N == 0 || s.nChunks == 0) { fprintf(stderr, "[%s] Error: no windows in the input.\n", ts()); return false; }
 
-    if ((enforceMinLen || keptBlocks || constrainedPost || admissibleSet) && hfio_window_len(tab) != windowLen && !min_len_windows(hfio_window_len(tab))) return EXIT_FAILURE;
-    phase("load input (+ HIP start-up)");
-    // 2. number of collapsed components (hmm_flagger.c:1008-1022)
-    hf_windows w;
-    memset(&w, 0, sizeof w);
-    hfio_windows(tab, &w);
-    if (numberOfCollapsedComps == -1) {
-        numberOfCollapsedComps = hfm_best_collapsed_comps(w.cov, N, hfio_region_coverages(tab), hfio_n_regions(tab));
-        if (numberOfCollapsedComps < 0) { fprintf(stderr, "[%s] Error: a region coverage of 0 in the header.\n", ts()); return EXIT_FAILURE; }
-        fprintf(stderr, "[%s] The number of collapsed components (n=%d) is determined and adjusted automatically by taking the maximum observed coverage. \n", ts(), numberOfCollapsedComps);
+    if (uses_min_len_windows(o) && hfio_window_len(tab) != o.windowLen && !min_len_windows(s, hfio_window_len(tab))) return false;
+    s.phase("load input (+ HIP start-up)");
+    if (o.numberOfCollapsedComps == -1) {
+        o.numberOfCollapsedComps = hfm_best_collapsed_comps(s.w.cov, s.N, hfio_region_coverages(tab), hfio_n_regions(tab));
+        if (o.numberOfCollapsedComps < 0) { fprintf(stderr, "[%s] Error: a region coverage of 0 in the header.\n", ts()); return false; }
+        fprintf(stderr, "[%s] The number of collapsed components (n=%d) is determined and adjusted automatically by taking the maximum observed coverage. \n", ts(), o.numberOfCollapsedComps);
     } else {
-        fprintf(stderr, "[%s] The number of components for the 'collapsed' state is set by the program argument %d. \n", ts(), numberOfCollapsedComps);
+        fprintf(stderr, "[%s] The number of components for the 'collapsed' state is set by the program argument %d. \n", ts(), o.numberOfCollapsedComps);
     }
+    return true;
+}
 
-    // 3. model (createModel, hmm_flagger.c:164-237); --sweepAlpha builds every candidate's model the same way, with its own alpha
-    auto make_model = [&](const double* alpha16) -> hfm_model* {
-        fprintf(stderr, "[%s] Creating HMM model. \n", ts());
-        hfm_model* m = hfm_create(modelType, numberOfCollapsedComps, hfio_region_coverages(tab), hfio_n_regions(tab),
-                                  hfio_start_only(tab), hfio_avg_alignment_len(tab), hfio_window_len(tab), alpha16,
-                                  maxHighMapqRatio, minHighMapqRatio);
-        if (!m) { fprintf(stderr, "[%s] Error: cannot create the model (collapsedComps must be 1..%d, regions 1..%d).\n", ts(), HF_MAXCOMP, HF_MAXREGIONS); return nullptr; }
-        if (modelType == HF_MODEL_NEGATIVE_BINOMIAL) {     // the model's per-x tables: only up to the largest coverage present
-            hf_windows wv;
-            hfio_windows(tab, &wv);
-            int maxx = 0;
-            for (int64_t i = 0; i < wv.n_windows; i++) { const int x = wv.cov[i] & 0xff; if (x > maxx) maxx = x; }
-            hfm_set_max_coverage(m, maxx);
-        }
-        if (initialRandomDeviation > 0.0) {                // hmm_flagger.c:213-220: same factor within one second
-            std::vector<double> pv((size_t) hfm_param_len(m));
-            hfm_get_param_vector(m, pv.data());
-            hfm_scale_initial_means(m, random_factor(initialRandomDeviation));
-        }
-        return m;
-    };
-    hfm_model* model = make_model(sweepListPath ? sweepAlphas[0].data() : alpha);
-    if (!model) return EXIT_FAILURE;
+// 3. model (createModel, hmm_flagger.c:164-237); --sweepAlpha builds every candidate's model the same way, with its own alpha
+static hfm_model* make_model(const Run& s, const double* alpha16) {
+    const Options& o = s.opt;
+    hfio_table* tab = s.tab;
+    fprintf(stderr, "[%s] Creating HMM model. \n", ts());
+    hfm_model* m = hfm_create(o.modelType, o.numberOfCollapsedComps, hfio_region_coverages(tab), hfio_n_regions(tab), hfio_start_only(tab),
+                              hfio_avg_alignment_len(tab), hfio_window_len(tab), alpha16, o.maxHighMapqRatio, o.minHighMapqRatio);
+    if (!m) { fprintf(stderr, "[%s] Error: cannot create the model (collapsedComps must be 1..%d, regions 1..%d).\n", ts(), HF_MAXCOMP, HF_MAXREGIONS); return nullptr; }
+    if (o.modelType == HF_MODEL_NEGATIVE_BINOMIAL) {       // the model's per-x tables: only up to the largest coverage present
+        int maxx = 0;
+        for (int64_t i = 0; i < s.w.n_windows; i++) { const int x = s.w.cov[i] & 0xff; if (x > maxx) maxx = x; }
+        hfm_set_max_coverage(m, maxx);
+    }
+    if (o.initialRandomDeviation > 0.0) hfm_scale_initial_means(m, random_factor(o.initialRandomDeviation));   // hmm_flagger.c:213-220: same factor within one second
+    return m;
+}
 
-    phase("model");
-    // 4. device context: windows resident in HBM for the whole run
-    w.adjust_contig_ends = adjustContigEnds ? 1 : 0; w.min_read_frac = adjustContigEnds ? minReadFractionAtEnds : 0.0;
-    w.max_high_mapq_ratio = maxHighMapqRatio; w.min_high_mapq_ratio = minHighMapqRatio;
+// 4. device context: windows resident in HBM for the whole run
+static bool create_context(Run& s, const hfm_model* model) {
+    const Options& o = s.opt;
+    hfio_table* tab = s.tab;
+    hf_windows& w = s.w;
+    w.adjust_contig_ends = o.adjustContigEnds ? 1 : 0; w.min_read_frac = o.adjustContigEnds ? o.minReadFractionAtEnds : 0.0;
+    w.max_high_mapq_ratio = o.maxHighMapqRatio; w.min_high_mapq_ratio = o.minHighMapqRatio;
     w.min_highly_clipped_ratio = hfm_min_highly_clipped_ratio(model);
     // one GPU: one context (statistics by emission row).  --gpus N (or an explicit --exchange): the sharded list — by default with the
     // chunk-order exchange (per-chunk vectors summed in chunk-list order, the reference's own merge order hmm.c:759-763: a result that
@@ -1473,466 +1440,497 @@ int main(int argc, char* argv[]) {
     // must not depend on N).  --exchange ranks: every GPU sums its shard by emission row and one vector per GPU is gathered — the
     // north-star's single collective and the fast statistics kernels, equal across N up to rounding (plain EM prints the same files for
     // every N at full size, configs[2] and [4]: tests/test_multi_gpu.py); what bench.py --gpus N measures
-    const bool sharded = nGpus > 1 || loopbackRanks > 0 || (nGpus == 1 && exchange >= 0);
-    int rc;
+    const bool sharded = o.nGpus > 1 || o.loopbackRanks > 0 || (o.nGpus == 1 && o.exchange >= 0);
     if (sharded) {
-        const int world = loopbackRanks > 0 ? loopbackRanks : nGpus;
+        const int world = o.loopbackRanks > 0 ? o.loopbackRanks : o.nGpus;
         std::vector<int> devs((size_t) world);
-        for (int i = 0; i < world; i++) devs[(size_t) i] = loopbackRanks > 0 ? device : device + i;
-        rc = hf_multi_create(&w, hfio_n_regions(tab), numberOfCollapsedComps, world, devs.data(), algo,
-                             exchange < 0 ? HF_EXCHANGE_CHUNKS : exchange, loopbackRanks > 0 ? HF_TRANSPORT_LOOPBACK : HF_TRANSPORT_RCCL,
-                             &run.multi);
-        if (rc != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_multi_last_error()); return EXIT_FAILURE; }
+        for (int i = 0; i < world; i++) devs[(size_t) i] = o.loopbackRanks > 0 ? o.device : o.device + i;
+        const int rc = hf_multi_create(&w, hfio_n_regions(tab), o.numberOfCollapsedComps, world, devs.data(), o.algo,
+                                       o.exchange < 0 ? HF_EXCHANGE_CHUNKS : o.exchange, o.loopbackRanks > 0 ? HF_TRANSPORT_LOOPBACK : HF_TRANSPORT_RCCL, &s.multi);
+        if (rc != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_multi_last_error()); return false; }
         for (int r = 0; r < world; r++)
-            fprintf(stderr, "[%s] GPU %d: %d chunks, %ld windows\n", ts(), devs[(size_t) r], hf_multi_shard_chunks(run.multi, r),
-                    (long) hf_multi_shard_windows(run.multi, r));
-        run.stats.assign((size_t) hf_multi_stats_len(run.multi), 0.0);
+            fprintf(stderr, "[%s] GPU %d: %d chunks, %ld windows\n", ts(), devs[(size_t) r], hf_multi_shard_chunks(s.multi, r), (long) hf_multi_shard_windows(s.multi, r));
+        s.stats.assign((size_t) hf_multi_stats_len(s.multi), 0.0);
     } else {
-        rc = hf_create(&w, hfio_n_regions(tab), numberOfCollapsedComps, device, algo, &run.ctx);
-        if (rc != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_last_error()); return EXIT_FAILURE; }
-        run.stats.assign((size_t) hf_chunk_stats_len(run.ctx), 0.0);
+        const int rc = hf_create(&w, hfio_n_regions(tab), o.numberOfCollapsedComps, o.device, o.algo, &s.ctx);
+        if (rc != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_last_error()); return false; }
+        s.stats.assign((size_t) hf_chunk_stats_len(s.ctx), 0.0);
     }
+    return true;
+}
 
-    phase("hf_create");
-    const int nChunks = hfio_n_chunks(tab);
-    // what one run reports to the --sweepAlpha summary
-    struct RunResult { int iterations = 0; bool converged = false; double ll = 0.0; int status = HF_OK; bool have_ll = false; };
-    // 5.-6. one whole run with `model` into `dir`: EM, final inference, every output file (runHMMFlagger, hmm_flagger.c:285-488)
-    auto run_em = [&](hfm_model* model, const std::string& dir, RunResult& res) -> int {
-    int rc;
-    fprintf(stderr, "[%s] Running EM for estimating parameters. \n", ts());
+// what one run reports to the --sweepAlpha summary
+struct RunResult { int iterations = 0; bool converged = false; double ll = 0.0; int status = HF_OK; bool have_ll = false; };
+
+// What a run of run_em and a candidate of the batched --sweepAlpha engine write alike (failures are said here):
+// loglikelihood.tsv with its header, and a row of it
+static FILE* open_loglikelihood(const std::string& dir) {
     FILE* llf = fopen((dir + "/loglikelihood.tsv").c_str(), "w+");
-    if (!llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
-    FileCloser llfClose{llf};
-    auto die = [&](int r) { res.status = r; return die_estep(r); };
+    if (!llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return nullptr; }
     fprintf(llf, "#Iteration\tEffective_Iteration\tLoglikelihood\n");
-    write_params(model, dir, "initial");
-    int iter = 1;
-    bool converged = false;
-    // --fitAlpha: iterations P, 2P, ... are alpha-iterations (their pass is followed by hfm_estimate_alpha alone), the others today's; the
-    // run has converged when the latest iteration of each kind reported convergence
-    bool convergedEm = false, convergedAlpha = false;
-    FILE* atf = nullptr;
+    return llf;
+}
+static void loglikelihood_row(FILE* llf, int iter, bool accelerated, double ll) { fprintf(llf, "%d\t%d\t%.4f\n", iter - 1, accelerated ? 3 * (iter - 1) : iter - 1, ll); }
+static std::string iteration_suffix(bool accelerated, int k) { return (accelerated ? "iteration_accelerated_" : "iteration_") + std::to_string(k); }
+static bool write_viterbi_log_prob(const std::string& dir, double vlp) {
+    const std::string vp = dir + "/viterbi_log_probability.tsv";
+    FILE* vf = fopen(vp.c_str(), "w");
+    if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); return false; }
+    fprintf(vf, "%.6f\n", vlp);
+    fclose(vf);
+    return true;
+}
+static bool write_final_bed(const Run& s, const int8_t* finalLabels, const std::string& dir) {
+    if (hfio_write_final_bed(s.tab, finalLabels, (dir + "/final_flagger_prediction.bed").c_str(), s.opt.trackName, s.opt.minLenPerState) == 0) return true;
+    fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), dir.c_str());
+    return false;
+}
+// --sweepAlpha: candidate i's directory, its model (the first candidate's is the run's) and its announcement; nullptr: failed (said)
+static hfm_model* start_candidate(const Run& s, size_t i, hfm_model* first, std::string& dir) {
+    dir = std::string(s.opt.outputDir) + "/alpha_" + std::to_string(i + 1);
+    if (!dir_exists(dir.c_str()) && mkdir(dir.c_str(), 0777) != 0) { fprintf(stderr, "[%s] Error: cannot create %s\n", ts(), dir.c_str()); return nullptr; }
+    hfm_model* m = i == 0 ? first : make_model(s, s.sweepAlphas[i].data());
+    if (!m) return nullptr;
+    fprintf(stderr, "[%s] --sweepAlpha: candidate %zu of %zu (%s) into %s\n", ts(), i + 1, s.sweepPaths.size(), s.sweepPaths[i].c_str(), dir.c_str());
+    return m;
+}
+static bool has_single_gpu_context(const Run& s, const char* who, const char* tail = "") {   // who: the option(s) and the verb
+    if (!s.ctx) fprintf(stderr, "[%s] Error: %s a single-GPU context%s.\n", ts(), who, tail);
+    return s.ctx != nullptr;
+}
+
+// One run of run_em: what its stages hand on
+struct EmRun {
+    hfm_model* model;
+    const std::string& dir;
+    RunResult& res;
+    FILE *llf = nullptr, *atf = nullptr;                    // loglikelihood.tsv, --fitAlpha's alpha_trace.tsv
     std::vector<double> alphaStats;
-    if (fitAlpha) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --fitAlpha needs a single-GPU context (no --exchange).\n", ts()); return EXIT_FAILURE; }
-        if ((rc = hf_set_alpha_stats(run.ctx, 1)) != HF_OK) return die(rc);
-        alphaStats.assign((size_t) hf_alpha_stats_len(run.ctx), 0.0);
-        atf = fopen((dir + "/alpha_trace.tsv").c_str(), "w");
-        if (!atf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
-        fprintf(atf, "#Iteration\tLoglikelihood");
-        for (const char* what : {"alpha", "G", "H"})
-            for (int k = 0; k < 16; k++) fprintf(atf, "\t%s_%d_%d", what, k / 4, k % 4);
-        fprintf(atf, "\n");
-    }
-    FileCloser atfClose{atf};
+    int iter = 1, passes = 0;
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
-    const double emStart = real_time();
-    double emTime = 0.0;
+    double emStart = 0.0, emTime = 0.0, emWall = 0.0;
     std::vector<double> passMs;                             // HF_CLI_TIMING: every E-step of the loop
-    int passes = 0;
-    auto timed_estep = [&](hfm_model* m, int mode, double* st) -> int {
-        const double t0 = real_time();
-        const int r = run.estep(m, mode, st);
-        const double dt = real_time() - t0;
-        emTime += dt;
-        if (phaseTiming) passMs.push_back(dt * 1e3);
-        return r;
-    };
-    while (iter <= numberOfIterations && !converged) {
-        fprintf(stderr, "[%s] [Iteration %s = %d] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), acceleration ? "accelerated" : "", iter, nChunks, device);
-        if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die(rc);
-        passes++;
-        fprintf(stderr, "[%s] [Iteration %s = %d] EM jobs are all finished.\n", ts(), acceleration ? "accelerated" : "", iter);
-        fprintf(llf, "%d\t%d\t%.4f\n", iter - 1, acceleration ? 3 * (iter - 1) : iter - 1, run.stats[0]);
-        res.ll = run.stats[0]; res.have_ll = true;
-        if (writeBenchmarkingStatsPerIteration || iter == 1) {   // hmm_flagger.c:360-379
-            char suffix[64];
-            if (iter == 1) snprintf(suffix, sizeof suffix, "initial");
-            else snprintf(suffix, sizeof suffix, acceleration ? "iteration_accelerated_%d" : "iteration_%d", iter - 1);
-            if ((rc = write_summary(run, dir, suffix, labelNames, binArrayFilePath, overlapRatioThreshold, threads, nullptr)) != HF_OK) return die(rc);
-        }
-        if (acceleration) {                                  // hmm_flagger.c:382-416
+    std::vector<int8_t> labels, vlabels;                    // of the final pass; of --viterbi
+    const int8_t* finalLabels = nullptr;                    // the one of the two that the final BED and tables take
+    int die(int r) { res.status = r; return die_estep(r); }
+};
+static int timed_full_pass(Run& s, EmRun& em) {
+    const double t0 = real_time();
+    const int r = s.estep(em.model, HF_MODE_FULL, s.stats.data());
+    const double dt = real_time() - t0;
+    em.emTime += dt; em.passes++;
+    if (s.opt.phaseTiming) em.passMs.push_back(dt * 1e3);
+    return r;
+}
+
+// 5a. the EM loop (runHMMFlagger, hmm_flagger.c:285-488), with --accelerate and the --fitAlpha trace
+static int em_loop(Run& s, EmRun& em) {
+    const Options& o = s.opt;
+    const std::string& dir = em.dir;
+    const char* const accelerated = o.acceleration ? "accelerated" : "";
+    int rc;
+    // --fitAlpha: iterations P, 2P, ... are alpha-iterations (their pass is followed by hfm_estimate_alpha alone), the others today's; the
+    // run has converged when the latest iteration of each kind reported convergence
+    bool converged = false, convergedEm = false, convergedAlpha = false;
+    if (o.fitAlpha) {
+        if (!has_single_gpu_context(s, "--fitAlpha needs", " (no --exchange)")) return EXIT_FAILURE;
+        if ((rc = hf_set_alpha_stats(s.ctx, 1)) != HF_OK) return em.die(rc);
+        em.alphaStats.assign((size_t) hf_alpha_stats_len(s.ctx), 0.0);
+        em.atf = fopen((dir + "/alpha_trace.tsv").c_str(), "w");
+        if (!em.atf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
+        fprintf(em.atf, "#Iteration\tLoglikelihood");
+        for (const char* what : {"alpha", "G", "H"})
+            for (int k = 0; k < 16; k++) fprintf(em.atf, "\t%s_%d_%d", what, k / 4, k % 4);
+        fprintf(em.atf, "\n");
+    }
+    em.emStart = real_time();
+    int& iter = em.iter;
+    while (iter <= o.numberOfIterations && !converged) {
+        fprintf(stderr, "[%s] [Iteration %s = %d] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), accelerated, iter, s.nChunks, o.device);
+        if ((rc = timed_full_pass(s, em)) != HF_OK) return em.die(rc);
+        fprintf(stderr, "[%s] [Iteration %s = %d] EM jobs are all finished.\n", ts(), accelerated, iter);
+        loglikelihood_row(em.llf, iter, o.acceleration, s.stats[0]);
+        em.res.ll = s.stats[0]; em.res.have_ll = true;
+        if ((o.writeBenchmarkingStatsPerIteration || iter == 1) &&   // hmm_flagger.c:360-379
+            (rc = write_summary(s, dir, iter == 1 ? "initial" : iteration_suffix(o.acceleration, iter - 1), nullptr)) != HF_OK) return em.die(rc);
+        if (o.acceleration) {                                // hmm_flagger.c:382-416
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Running SQUAREM acceleration.\n", ts(), iter);
-            auto estep_cb = [&](hfm_model* m, int mode, double* st) -> int {   // (the whole accelerated iteration is timed as one block)
+            auto estep_cb = [&s, &em](hfm_model* m, int mode, double* st) -> int {   // (the whole accelerated iteration is timed as one block)
                 const double t1 = real_time();
-                const int r = run.estep(m, mode, st);
-                if (phaseTiming) passMs.push_back((real_time() - t1) * 1e3);
+                const int r = s.estep(m, mode, st);
+                if (s.opt.phaseTiming) em.passMs.push_back((real_time() - t1) * 1e3);
                 return r;
             };
             const double t0 = real_time();
-            rc = squarem_iteration(&model, run.stats, convergenceTol, estep_cb, &passes);
-            emTime += real_time() - t0;
-            if (rc != HF_OK) return die(rc);
+            rc = squarem_iteration(&em.model, s.stats, o.convergenceTol, estep_cb, &em.passes);
+            em.emTime += real_time() - t0;
+            if (rc != HF_OK) return em.die(rc);
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Finished SQUAREM acceleration.\n", ts(), iter);
         }
-        if (fitAlpha && iter % fitAlphaEvery == 0) {
+        if (o.fitAlpha && iter % o.fitAlphaEvery == 0) {
             const double t0 = real_time();
-            if ((rc = hf_get_alpha_stats(run.ctx, alphaStats.data())) != HF_OK) return die(rc);
+            if ((rc = hf_get_alpha_stats(s.ctx, em.alphaStats.data())) != HF_OK) return em.die(rc);
             double a0[16], gh[32] = {0};
-            hfm_get_alpha(model, a0);
-            for (size_t r = 0; r * 32 < alphaStats.size(); r++)          // region order
-                for (int k = 0; k < 32; k++) gh[k] += alphaStats[r * 32 + (size_t) k];
-            const int cv = hfm_estimate_alpha(model, alphaStats.data(), run.stats.data(), fitAlphaMask, 0.0, fitAlphaMax, convergenceTol);
-            emTime += real_time() - t0;
+            hfm_get_alpha(em.model, a0);
+            for (size_t r = 0; r * 32 < em.alphaStats.size(); r++)          // region order
+                for (int k = 0; k < 32; k++) gh[k] += em.alphaStats[r * 32 + (size_t) k];
+            const int cv = hfm_estimate_alpha(em.model, em.alphaStats.data(), s.stats.data(), o.fitAlphaMask, 0.0, o.fitAlphaMax, o.convergenceTol);
+            em.emTime += real_time() - t0;
             if (cv < 0) { fprintf(stderr, "[%s] Error: hfm_estimate_alpha refused its arguments.\n", ts()); return EXIT_FAILURE; }
             convergedAlpha = cv != 0;
             converged = convergedEm && convergedAlpha;
-            fprintf(atf, "%d\t%.17g", iter - 1, run.stats[0]);
-            for (int k = 0; k < 16; k++) fprintf(atf, "\t%.17g", a0[k]);
-            for (int k = 0; k < 32; k++) fprintf(atf, "\t%.17g", gh[k]);
-            fprintf(atf, "\n");
+            fprintf(em.atf, "%d\t%.17g", iter - 1, s.stats[0]);
+            for (int k = 0; k < 16; k++) fprintf(em.atf, "\t%.17g", a0[k]);
+            for (int k = 0; k < 32; k++) fprintf(em.atf, "\t%.17g", gh[k]);
+            fprintf(em.atf, "\n");
         } else {
             const double t0 = real_time();
-            converged = hfm_estimate(model, run.stats.data(), convergenceTol) != 0;
-            emTime += real_time() - t0;
-            if (fitAlpha) { convergedEm = converged; converged = convergedEm && convergedAlpha; }
+            converged = hfm_estimate(em.model, s.stats.data(), o.convergenceTol) != 0;
+            em.emTime += real_time() - t0;
+            if (o.fitAlpha) { convergedEm = converged; converged = convergedEm && convergedAlpha; }
         }
-        fprintf(stderr, "[%s] [Iteration %s = %d] Parameters are estimated and updated.\n", ts(), acceleration ? "accelerated" : "", iter);
-        if (writeParamsPerIter) {
-            char suffix[64];
-            snprintf(suffix, sizeof suffix, acceleration ? "iteration_accelerated_%d" : "iteration_%d", iter);
-            write_params(model, dir, suffix);
-        }
+        fprintf(stderr, "[%s] [Iteration %s = %d] Parameters are estimated and updated.\n", ts(), accelerated, iter);
+        if (o.writeParamsPerIter) write_params(em.model, dir, iteration_suffix(o.acceleration, iter));
         iter += 1;
     }
-    if (converged) fprintf(stderr, "[%s] Parameters converged after %d iterations (tol=%.2e)\n", ts(), iter - 1, convergenceTol);
-    else fprintf(stderr, "[%s] Parameter estimation stopped (not yet converged based on the given tolerance) after %d iterations (tol=%.2e)\n", ts(), iter - 1, convergenceTol);
-    res.iterations = iter - 1; res.converged = converged;
-    fprintf(stderr, "[%s] [Final Inference] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), nChunks, device);
-    if ((rc = timed_estep(model, HF_MODE_FULL, run.stats.data())) != HF_OK) return die(rc);
-    passes++;
-    const double emWall = real_time() - emStart;
+    if (converged) fprintf(stderr, "[%s] Parameters converged after %d iterations (tol=%.2e)\n", ts(), iter - 1, o.convergenceTol);
+    else fprintf(stderr, "[%s] Parameter estimation stopped (not yet converged based on the given tolerance) after %d iterations (tol=%.2e)\n", ts(), iter - 1, o.convergenceTol);
+    em.res.iterations = iter - 1; em.res.converged = converged;
+    return 0;
+}
+
+// 5b. the final inference: the last pass, its labels, --viterbi and --enforceMinimumLengths with the cost file
+static int final_inference(Run& s, EmRun& em) {
+    const Options& o = s.opt;
+    const std::string& dir = em.dir;
+    const int64_t N = s.N;
+    int rc;
+    fprintf(stderr, "[%s] [Final Inference] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), s.nChunks, o.device);
+    if ((rc = timed_full_pass(s, em)) != HF_OK) return em.die(rc);
+    em.emWall = real_time() - em.emStart;
     fprintf(stderr, "[%s] [Final Inference] EM jobs are all finished.\n", ts());
-    fprintf(llf, "%d\t%d\t%.4f\n", iter - 1, acceleration ? 3 * (iter - 1) : iter - 1, run.stats[0]);
-    res.ll = run.stats[0]; res.have_ll = true;
-    fclose(llf);
-    llf = nullptr;
-    write_params(model, dir, "final");
-    if (fitAlpha) {        // four tab-separated rows that --alphaTsv reads back to the same doubles
+    loglikelihood_row(em.llf, em.iter, o.acceleration, s.stats[0]);
+    em.res.ll = s.stats[0]; em.res.have_ll = true;
+    fclose(em.llf);
+    em.llf = nullptr;
+    write_params(em.model, dir, "final");
+    if (o.fitAlpha) {        // four tab-separated rows that --alphaTsv reads back to the same doubles
         double a[16];
-        hfm_get_alpha(model, a);
+        hfm_get_alpha(em.model, a);
         FILE* af = fopen((dir + "/alpha_fitted.tsv").c_str(), "w");
         if (!af) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
         for (int i = 0; i < 4; i++) fprintf(af, "%.17g\t%.17g\t%.17g\t%.17g\n", a[i * 4], a[i * 4 + 1], a[i * 4 + 2], a[i * 4 + 3]);
         fclose(af);
-        (void) hf_set_alpha_stats(run.ctx, 0);
+        (void) hf_set_alpha_stats(s.ctx, 0);
     }
-    std::vector<int8_t> labels((size_t) N);
-    if ((rc = run.labels(labels.data())) != HF_OK) return die(rc);
+    em.labels.resize((size_t) N);
+    if ((rc = s.labels(em.labels.data())) != HF_OK) return em.die(rc);
+    em.finalLabels = em.labels.data();
     // --viterbi: the final BED and the final tables take the most probable path under the final parameters; everything else
     // (the posterior BED of -P among it) keeps the posterior labels of the final pass
-    std::vector<int8_t> vlabels;
-    if (viterbi) {
-        fprintf(stderr, "[%s] [Final Inference] Most probable state path of %d chunks ...\n", ts(), nChunks);
-        vlabels.resize((size_t) N);
-        double vlp = 0.0;
-        if ((rc = run.viterbi(model, vlabels.data(), &vlp)) != HF_OK) return die(rc);
-        // --enforceMinimumLengths: the path written is the best one that respects the lengths; the unconstrained run above is what it cost
-        if (enforceMinLen) {
-            if (!run.ctx) { fprintf(stderr, "[%s] Error: --enforceMinimumLengths needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-            std::vector<int8_t> clabels((size_t) N);
-            double clp = 0.0;
-            if ((rc = run.viterbi_minlen(model, minLenWindows, clabels.data(), &clp)) != HF_OK) return die(rc);
-            hf_windows wv;
-            memset(&wv, 0, sizeof wv);
-            hfio_windows(tab, &wv);
-            int differ = 0;
-            for (int c = 0; c < wv.n_chunks; c++)
-                differ += memcmp(clabels.data() + wv.chunk_off[c], vlabels.data() + wv.chunk_off[c], (size_t) (wv.chunk_off[c + 1] - wv.chunk_off[c])) != 0;
-            const std::string cp = dir + "/viterbi_min_length_cost.tsv";
-            FILE* cf = fopen(cp.c_str(), "w");
-            if (!cf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), cp.c_str()); return EXIT_FAILURE; }
-            fprintf(cf, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\tlog_prob_constrained\tlog_prob_unconstrained\tlog_prob_difference\tchunks_changed\n");
-            fprintf(cf, "%d\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%d\n", minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], clp, vlp,
-                    clp - vlp, differ);
-            fclose(cf);
-            fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows: log-probability %.6f (unconstrained %.6f), %d chunks changed\n",
-                    ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], clp, vlp, differ);
-            vlabels.swap(clabels);
-            vlp = clp;
-        }
-        const std::string vp = dir + "/viterbi_log_probability.tsv";
-        FILE* vf = fopen(vp.c_str(), "w");
-        if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); return EXIT_FAILURE; }
-        fprintf(vf, "%.6f\n", vlp);
-        fclose(vf);
-        fprintf(stderr, "[%s] [Final Inference] Most probable path: log-probability %.6f\n", ts(), vlp);
+    if (!o.viterbi) return 0;
+    std::vector<int8_t>& vlabels = em.vlabels;
+    fprintf(stderr, "[%s] [Final Inference] Most probable state path of %d chunks ...\n", ts(), s.nChunks);
+    vlabels.resize((size_t) N);
+    double vlp = 0.0;
+    if ((rc = s.viterbi(em.model, vlabels.data(), &vlp)) != HF_OK) return em.die(rc);
+    // --enforceMinimumLengths: the path written is the best one that respects the lengths; the unconstrained run above is what it cost
+    if (o.enforceMinLen) {
+        if (!has_single_gpu_context(s, "--enforceMinimumLengths needs")) return EXIT_FAILURE;
+        const int32_t* const mw = s.minLenWindows;
+        std::vector<int8_t> clabels((size_t) N);
+        double clp = 0.0;
+        if ((rc = s.viterbi_minlen(em.model, mw, clabels.data(), &clp)) != HF_OK) return em.die(rc);
+        int differ = 0;
+        for (int c = 0; c < s.w.n_chunks; c++)
+            differ += memcmp(clabels.data() + s.w.chunk_off[c], vlabels.data() + s.w.chunk_off[c], (size_t) (s.w.chunk_off[c + 1] - s.w.chunk_off[c])) != 0;
+        const std::string cp = dir + "/viterbi_min_length_cost.tsv";
+        FILE* cf = fopen(cp.c_str(), "w");
+        if (!cf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), cp.c_str()); return EXIT_FAILURE; }
+        fprintf(cf, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\tlog_prob_constrained\tlog_prob_unconstrained\tlog_prob_difference\tchunks_changed\n");
+        fprintf(cf, "%d\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%d\n", mw[0], mw[1], mw[2], mw[3], clp, vlp, clp - vlp, differ);
+        fclose(cf);
+        fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows: log-probability %.6f (unconstrained %.6f), %d chunks changed\n",
+                ts(), mw[0], mw[1], mw[2], mw[3], clp, vlp, differ);
+        vlabels.swap(clabels);
+        vlp = clp;
     }
-    const int8_t* finalLabels = viterbi ? vlabels.data() : labels.data();
-    if ((rc = write_summary(run, dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) return die(rc);
-    memcpy(hfio_prediction(tab), labels.data(), (size_t) N);
-    if (writePosterior) {
-        std::vector<double> post((size_t) N * 4);
-        if ((rc = run.posterior(0, N, post.data())) != HF_OK) return die(rc);
+    if (!write_viterbi_log_prob(dir, vlp)) return EXIT_FAILURE;
+    fprintf(stderr, "[%s] [Final Inference] Most probable path: log-probability %.6f\n", ts(), vlp);
+    em.finalLabels = vlabels.data();
+    return 0;
+}
+
+// 5c.-6. the final outputs: the final tables (on their worker), the posterior BED of -P, the final BED
+static int final_outputs(Run& s, EmRun& em) {
+    const std::string& dir = em.dir;
+    int rc;
+    if ((rc = write_summary(s, dir, "final", em.finalLabels)) != HF_OK) return em.die(rc);
+    memcpy(hfio_prediction(s.tab), em.labels.data(), (size_t) s.N);
+    if (s.opt.writePosterior) {
+        std::vector<double> post((size_t) s.N * 4);
+        if ((rc = s.posterior(0, s.N, post.data())) != HF_OK) return em.die(rc);
         const std::string pp = dir + "/posterior_prediction_final.bed";
         fprintf(stderr, "[%s] Writing posterior bed : %s\n", ts(), pp.c_str());
-        hfio_write_posterior_bed(tab, post.data(), labels.data(), pp.c_str());
+        hfio_write_posterior_bed(s.tab, post.data(), em.labels.data(), pp.c_str());
     }
-    if (phaseTiming && !passMs.empty()) {
+    if (s.opt.phaseTiming && !em.passMs.empty()) {
         fprintf(stderr, "[phase]   E-step passes (ms):");
-        for (size_t k = 0; k < passMs.size(); k++) fprintf(stderr, " %.3f", passMs[k]);
+        for (size_t k = 0; k < em.passMs.size(); k++) fprintf(stderr, " %.3f", em.passMs[k]);
         fprintf(stderr, "\n");
     }
-    phase("EM + final inference");
-    // 6. final BED
+    s.phase("EM + final inference");
     fprintf(stderr, "[%s] Writing final BED file. \n", ts());
-    if (hfio_write_final_bed(tab, finalLabels, (dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
-        fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), dir.c_str());
-        return EXIT_FAILURE;
+    return write_final_bed(s, em.finalLabels, dir) ? 0 : EXIT_FAILURE;
+}
+
+// the samplers of --uncertaintySamples and --admissibleSamples (paths drawn UNDER --minimumLengths) behind write_sample_outputs
+static PathSampler posterior_sampler(hf_ctx* ctx, uint64_t seed) {
+    return PathSampler{[ctx] { return hf_sample_capacity(ctx); },
+                       [ctx, seed](const hf_params* p, int64_t first, int n) {
+                           const int rc = hf_sample_paths(ctx, p, first, n, seed, nullptr);
+                           return rc == HF_OK ? hf_sample_finish(ctx, nullptr) : rc;
+                       },
+                       [ctx](int k, int8_t* out) { return hf_get_sample_labels(ctx, k, out); }};
+}
+static PathSampler admissible_sampler(hf_ctx* ctx, const int32_t* ml, uint64_t seed) {
+    return PathSampler{[ctx, ml] { return hf_minlen_sample_capacity(ctx, ml); },
+                       [ctx, ml, seed](const hf_params* p, int64_t first, int n) {
+                           const int rc = hf_sample_paths_minlen(ctx, p, ml, first, n, seed, nullptr);
+                           return rc == HF_OK ? hf_sample_minlen_finish(ctx, nullptr) : rc;
+                       },
+                       [ctx](int k, int8_t* out) { return hf_get_minlen_sample_labels(ctx, k, out); }};
+}
+// 6b. The outputs behind the final BED: after every other output of the run (which does not depend on them), in the order of the table.
+// A row: whether the options ask for it, who needs the single-GPU context (the option(s) with the verb), what is reported when it is
+// done (nullptr: the call reports itself), and the call (an HF_* code).
+static int late_outputs(Run& s, EmRun& em) {
+    const Options& o = s.opt;
+    hf_ctx* const ctx = s.ctx;
+    hfio_table* const tab = s.tab;
+    const int8_t* const labels = em.finalLabels;
+    const std::string& dir = em.dir;
+    const std::vector<Region>* const regions = o.regionProbsPath ? &s.regions : nullptr;
+    const int32_t* const mw = s.minLenWindows;
+    double t0 = 0.0;
+    struct LateOutput { bool wanted; const char *who, *done; std::function<int()> write; };
+    const LateOutput outputs[] = {
+        {o.uncertaintySamples > 0, "--uncertaintySamples needs", "posterior_samples_summary.tsv and final_label_runs_support.bed are written", [&] {
+             fprintf(stderr, "[%s] [Final Inference] Drawing %d posterior state paths (seed %llu) ...\n", ts(), o.uncertaintySamples, (unsigned long long) o.uncertaintySeed);
+             return write_sample_outputs(posterior_sampler(ctx, o.uncertaintySeed), em.model, tab, labels, o.uncertaintySamples, o.labelNames, dir,
+                                         "posterior_samples_summary.tsv", "final_label_runs_support.bed");
+         }},
+        {o.runConfidence || o.regionProbsPath, "--runConfidence and --regionProbs need", "exact interval probabilities written",
+         [&] { return write_interval_outputs(ctx, tab, labels, o.runConfidence, regions, o.labelNames, dir); }},
+        {o.runBoundaries, "--runBoundaries needs", "final_label_run_boundaries.tsv is written", [&] { return write_run_boundaries(ctx, tab, labels, dir); }},
+        {o.exactTotals, "--exactTotals needs", "label_totals_exact.tsv is written", [&] { return write_exact_totals(ctx, tab, labels, dir); }},
+        {o.numBlocks, "--numBlocks needs", "label_blocks_exact.tsv is written", [&] { return write_exact_blocks(ctx, tab, labels, dir); }},
+        {o.jointEntropy, "--jointEntropy needs", "path_uncertainty.tsv is written", [&] { return write_path_uncertainty(ctx, tab, labels, dir); }},
+        {o.keptBlocks, "--keptBlocks needs", "kept_block_probabilities.tsv is written", [&] { return write_kept_blocks(ctx, tab, regions, mw, o.labelNames, dir); }},
+        // (a decoder of its own: it reads the final parameters, not the last pass; its line carries the mass it found)
+        {o.constrainedPost, "--constrainedPosterior needs", nullptr, [&] {
+             double logMass = 0.0;
+             int rc = s.minlen_posterior(em.model, mw, &logMass);
+             if (rc == HF_OK) rc = write_constrained_posterior(ctx, tab, mw, dir);
+             if (rc == HF_OK) fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
+                                      ts(), mw[0], mw[1], mw[2], mw[3], logMass, (real_time() - t0) * 1e3);
+             return rc;
+         }},
+        {o.admissibleSamples > 0, "--admissibleSamples needs", "admissible_samples_summary.tsv and admissible_label_runs_support.bed are written", [&] {
+             fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows, seed %llu) ...\n", ts(),
+                     o.admissibleSamples, mw[0], mw[1], mw[2], mw[3], (unsigned long long) o.uncertaintySeed);
+             return write_sample_outputs(admissible_sampler(ctx, mw, o.uncertaintySeed), em.model, tab, labels, o.admissibleSamples, o.labelNames, dir,
+                                         "admissible_samples_summary.tsv", "admissible_label_runs_support.bed");
+         }},
+    };
+    for (const LateOutput& out : outputs) {
+        if (!out.wanted) continue;
+        if (!has_single_gpu_context(s, out.who)) return EXIT_FAILURE;
+        t0 = real_time();
+        const int rc = out.write();
+        if (rc != HF_OK) return em.die(rc);
+        if (out.done) fprintf(stderr, "[%s] [Final Inference] %s (%.1f ms).\n", ts(), out.done, (real_time() - t0) * 1e3);
     }
-    // --uncertaintySamples: after every other output of the run (they do not depend on it)
-    if (uncertaintySamples > 0) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --uncertaintySamples needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        fprintf(stderr, "[%s] [Final Inference] Drawing %d posterior state paths (seed %llu) ...\n", ts(), uncertaintySamples,
-                (unsigned long long) uncertaintySeed);
-        const double t0 = real_time();
-        hf_ctx* const sctx = run.ctx;
-        const PathSampler smp{[sctx] { return hf_sample_capacity(sctx); },
-                              [sctx, uncertaintySeed](const hf_params* p, int64_t first, int n) {
-                                  const int rc = hf_sample_paths(sctx, p, first, n, uncertaintySeed, nullptr);
-                                  return rc == HF_OK ? hf_sample_finish(sctx, nullptr) : rc;
-                              },
-                              [sctx](int k, int8_t* out) { return hf_get_sample_labels(sctx, k, out); }};
-        if ((rc = write_sample_outputs(smp, model, tab, finalLabels, uncertaintySamples, labelNames, dir, "posterior_samples_summary.tsv",
-                                       "final_label_runs_support.bed")) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] posterior_samples_summary.tsv and final_label_runs_support.bed are written (%.1f ms).\n", ts(),
-                (real_time() - t0) * 1e3);
-    }
-    // --runConfidence / --regionProbs: after every other output of the run (they do not depend on it)
-    if (runConfidence || regionProbsPath) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --runConfidence and --regionProbs need a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_interval_outputs(run.ctx, tab, finalLabels, runConfidence, regionProbsPath ? &regions : nullptr, labelNames, dir)) != HF_OK)
-            return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] exact interval probabilities written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --runBoundaries: beside them
-    if (runBoundaries) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --runBoundaries needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_run_boundaries(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] final_label_run_boundaries.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --exactTotals: likewise
-    if (exactTotals) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --exactTotals needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_exact_totals(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] label_totals_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --numBlocks: likewise
-    if (numBlocks) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --numBlocks needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_exact_blocks(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] label_blocks_exact.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --jointEntropy: likewise
-    if (jointEntropy) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --jointEntropy needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_path_uncertainty(run.ctx, tab, finalLabels, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] path_uncertainty.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --keptBlocks: after every other output
-    if (keptBlocks) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --keptBlocks needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        if ((rc = write_kept_blocks(run.ctx, tab, regionProbsPath ? &regions : nullptr, minLenWindows, labelNames, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] kept_block_probabilities.tsv is written (%.1f ms).\n", ts(), (real_time() - t0) * 1e3);
-    }
-    // --constrainedPosterior: likewise (a decoder of its own: it reads the final parameters, not the last pass)
-    if (constrainedPost) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --constrainedPosterior needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        const double t0 = real_time();
-        double logMass = 0.0;
-        if ((rc = run.minlen_posterior(model, minLenWindows, &logMass)) != HF_OK) return die(rc);
-        if ((rc = write_constrained_posterior(run.ctx, tab, minLenWindows, dir)) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
-                ts(), minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], logMass, (real_time() - t0) * 1e3);
-    }
-    // --admissibleSamples: after every other output, the two files of --uncertaintySamples for paths drawn UNDER --minimumLengths
-    if (admissibleSamples > 0) {
-        if (!run.ctx) { fprintf(stderr, "[%s] Error: --admissibleSamples needs a single-GPU context.\n", ts()); return EXIT_FAILURE; }
-        fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows, seed %llu) ...\n", ts(),
-                admissibleSamples, minLenWindows[0], minLenWindows[1], minLenWindows[2], minLenWindows[3], (unsigned long long) uncertaintySeed);
-        const double t0 = real_time();
-        hf_ctx* const sctx = run.ctx;
-        const int32_t* const ml = minLenWindows;
-        const PathSampler smp{[sctx, ml] { return hf_minlen_sample_capacity(sctx, ml); },
-                              [sctx, ml, uncertaintySeed](const hf_params* p, int64_t first, int n) {
-                                  const int rc = hf_sample_paths_minlen(sctx, p, ml, first, n, uncertaintySeed, nullptr);
-                                  return rc == HF_OK ? hf_sample_minlen_finish(sctx, nullptr) : rc;
-                              },
-                              [sctx](int k, int8_t* out) { return hf_get_minlen_sample_labels(sctx, k, out); }};
-        if ((rc = write_sample_outputs(smp, model, tab, finalLabels, admissibleSamples, labelNames, dir, "admissible_samples_summary.tsv",
-                                       "admissible_label_runs_support.bed")) != HF_OK) return die(rc);
-        fprintf(stderr, "[%s] [Final Inference] admissible_samples_summary.tsv and admissible_label_runs_support.bed are written (%.1f ms).\n", ts(),
-                (real_time() - t0) * 1e3);
+    return 0;
+}
+
+// 5.-6. one whole run with `model` into `dir`: EM, final inference, every output file (runHMMFlagger, hmm_flagger.c:285-488).
+// 0, or the exit status of a run that failed (said; res.status holds the HF_* code of a failed device call)
+static int run_em(Run& s, hfm_model* model, const std::string& dir, RunResult& res) {
+    fprintf(stderr, "[%s] Running EM for estimating parameters. \n", ts());
+    EmRun em{model, dir, res};
+    if (!(em.llf = open_loglikelihood(dir))) return EXIT_FAILURE;
+    FileCloser llfClose{em.llf}, atfClose{em.atf};
+    write_params(model, dir, "initial");
+    for (int (*stage)(Run&, EmRun&) : {em_loop, final_inference, final_outputs, late_outputs}) {
+        const int r = stage(s, em);
+        if (r != 0) return r;
     }
     fprintf(stderr, "[%s] EM+decode: %d passes over %ld windows in %.4f s = %.3e windows/s on GPU %d (E-steps, M-steps; the loop with its "
-            "log lines and output files took %.4f s)\n", ts(), passes, (long) N, emTime, (double) N * passes / emTime, device, emWall);
-    phase("final BED");
-    if (!sweepListPath) summary_join();            // the table workers (the reference writes the tables before the BED; the files are the same)
+            "log lines and output files took %.4f s)\n", ts(), em.passes, (long) s.N, em.emTime, (double) s.N * em.passes / em.emTime, s.opt.device, em.emWall);
+    s.phase("final BED");
+    if (!s.opt.sweepListPath) summary_join();      // the table workers (the reference writes the tables before the BED; the files are the same)
     else if (!summary_join_report()) return EXIT_FAILURE;
-    phase("summary tables joined");
+    s.phase("summary tables joined");
     return 0;
-    };
-    if (!sweepListPath) {
+}
+
+// --sweepAlpha, the BATCHED engine (hf_batch_*, flagger_amd/csrc/hf_batch.h): every pass runs all unconverged candidates of a group of at
+// most `cap` together; a candidate leaves the active set after its final inference pass, so its iterations and files are those of a
+// separate --alphaTsv run.  A candidate that fails is reported in results and the sweep goes on (anyFailed); false: the sweep cannot (said)
+static bool sweep_batched(Run& s, hfm_model* model, int cap, std::vector<RunResult>& results, bool& anyFailed) {
+    const Options& o = s.opt;
+    const size_t n = s.sweepPaths.size();
+    const int64_t N = s.N;
+    const int G = (int) std::min<size_t>((size_t) cap, n);
+    fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: batched (hf_batch), %d models per group\n", ts(), n, G);
+    const int64_t V = hf_chunk_stats_len(s.ctx);
+    struct Cand { hfm_model* m = nullptr; FILE* llf = nullptr; int iter = 1; bool converged = false, final = false, done = false; std::string dir; };
+    for (size_t g0 = 0; g0 < n; g0 += (size_t) G) {
+        const int ng = (int) std::min<size_t>((size_t) G, n - g0);
+        hf_batch* bt = nullptr;
+        if (hf_batch_create(s.ctx, ng, &bt) != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_last_error()); return false; }
+        std::vector<Cand> cs((size_t) ng);
+        for (int j = 0; j < ng; j++) {
+            Cand& c = cs[(size_t) j];
+            if (!(c.m = start_candidate(s, g0 + (size_t) j, model, c.dir))) return false;
+            if (!(c.llf = open_loglikelihood(c.dir))) return false;
+            write_params(c.m, c.dir, "initial");
+            c.final = o.numberOfIterations < 1;
+        }
+        std::vector<int8_t> lab((size_t) N);
+        while (true) {
+            std::vector<int32_t> act;
+            std::vector<hf_params> ps;
+            for (int j = 0; j < ng; j++) if (!cs[(size_t) j].done) { act.push_back(j); ps.emplace_back(); hfm_params(cs[(size_t) j].m, &ps.back()); }
+            if (act.empty()) break;
+            std::vector<double> stats(act.size() * (size_t) V);
+            std::vector<int32_t> status(act.size(), HF_OK);
+            int rc = hf_batch_estep(bt, ps.data(), act.data(), (int) act.size(), HF_MODE_FULL, nullptr);
+            if (rc == HF_OK) rc = hf_batch_finish(bt, stats.data(), status.data(), nullptr);
+            if (rc != HF_OK) { die_estep(rc); return false; }
+            for (size_t k = 0; k < act.size(); k++) {
+                const int j = act[k];
+                Cand& c = cs[(size_t) j];
+                RunResult& res = results[g0 + (size_t) j];
+                const double* st = stats.data() + k * (size_t) V;
+                auto fail = [&](int r) {
+                    if (r == HF_E_SCALE) fprintf(stderr, "scale is very low!\n");
+                    else if (r == HF_E_NAN) fprintf(stderr, "[Error] prob is NAN\n");
+                    else fprintf(stderr, "[%s] Error: %s\n", ts(), cli_error_or(hf_last_error()));
+                    g_cli_error.clear();
+                    res.status = r == HF_OK ? HF_E_ARG : r; anyFailed = true; c.done = true;
+                    if (c.llf) fclose(c.llf);
+                    c.llf = nullptr;
+                };
+                if (status[k] != HF_OK) { fail(status[k]); continue; }
+                loglikelihood_row(c.llf, c.iter, false, st[0]);
+                res.ll = st[0]; res.have_ll = true;
+                if (!c.final) {
+                    if (o.writeBenchmarkingStatsPerIteration || c.iter == 1) {
+                        if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK ||
+                            (rc = write_summary(s, c.dir, c.iter == 1 ? "initial" : iteration_suffix(false, c.iter - 1), lab.data())) != HF_OK) { fail(rc); continue; }
+                    }
+                    c.converged = hfm_estimate(c.m, st, o.convergenceTol) != 0;
+                    if (o.writeParamsPerIter) write_params(c.m, c.dir, iteration_suffix(false, c.iter));
+                    c.iter += 1;
+                    if (c.iter > o.numberOfIterations || c.converged) {
+                        res.iterations = c.iter - 1; res.converged = c.converged;
+                        c.final = true;                          // the next pass of this candidate is its final inference
+                    }
+                    continue;
+                }
+                // the final inference pass: every output of a separate run
+                res.iterations = c.iter - 1; res.converged = c.converged;
+                fclose(c.llf);
+                c.llf = nullptr;
+                write_params(c.m, c.dir, "final");
+                if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK) { fail(rc); continue; }
+                std::vector<int8_t> vlabels;
+                if (o.viterbi) {
+                    vlabels.resize((size_t) N);
+                    double vlp = 0.0;
+                    if ((rc = s.viterbi(c.m, vlabels.data(), &vlp)) != HF_OK) { fail(rc); continue; }
+                    if (!write_viterbi_log_prob(c.dir, vlp)) { fail(HF_E_ARG); continue; }
+                }
+                const int8_t* finalLabels = o.viterbi ? vlabels.data() : lab.data();
+                if ((rc = write_summary(s, c.dir, "final", finalLabels)) != HF_OK) { fail(rc); continue; }
+                memcpy(hfio_prediction(s.tab), lab.data(), (size_t) N);
+                if (o.writePosterior) {
+                    std::vector<double> post((size_t) N * 4);
+                    if ((rc = hf_batch_get_posterior(bt, j, 0, N, post.data())) != HF_OK) { fail(rc); continue; }
+                    hfio_write_posterior_bed(s.tab, post.data(), lab.data(), (c.dir + "/posterior_prediction_final.bed").c_str());
+                }
+                if (!write_final_bed(s, finalLabels, c.dir)) { fail(HF_E_ARG); continue; }
+                c.done = true;
+            }
+        }
+        if (!summary_join_report()) { anyFailed = true; }
+        hf_batch_destroy(bt);
+    }
+    return true;
+}
+
+// --sweepAlpha: the candidates one after another on the context (or GPU list) of the session, each exactly a separate run
+static bool sweep_sequential(Run& s, hfm_model* model, std::vector<RunResult>& results, bool& anyFailed) {
+    const size_t n = s.sweepPaths.size();
+    fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: sequential (%s), 1 model per group\n", ts(), n, s.multi ? "sharded GPU list" : "one context");
+    for (size_t i = 0; i < n; i++) {
+        std::string cdir;
+        hfm_model* m = start_candidate(s, i, model, cdir);
+        if (!m) return false;
+        if (run_em(s, m, cdir, results[i]) != 0) {
+            anyFailed = true;
+            if (results[i].status == HF_OK) results[i].status = HF_E_ARG;
+            g_cli_error.clear();
+            // (a failed table set of this candidate has been reported; the next candidate starts with no worker of its own pending)
+            summary_wait_quietly();
+            g_summaries.clear();
+        }
+    }
+    return true;
+}
+
+// <outputDir>/alpha_sweep.tsv: one row per candidate
+static bool write_sweep_table(const Run& s, const std::vector<RunResult>& results, const std::string& sp) {
+    FILE* sf = fopen(sp.c_str(), "w");
+    if (!sf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), sp.c_str()); return false; }
+    fprintf(sf, "#Index\tAlpha_Tsv\tIterations\tConverged\tLoglikelihood\tStatus\n");
+    for (size_t i = 0; i < results.size(); i++) {
+        const RunResult& r = results[i];
+        const char* st = r.status == HF_OK ? "ok" : r.status == HF_E_SCALE ? "scale_too_low" : r.status == HF_E_NAN ? "nan" : "error";
+        if (r.have_ll) fprintf(sf, "%zu\t%s\t%d\t%d\t%.4f\t%s\n", i + 1, s.sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, r.ll, st);
+        else fprintf(sf, "%zu\t%s\t%d\t%d\tNA\t%s\n", i + 1, s.sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, st);
+    }
+    fclose(sf);
+    return true;
+}
+
+int main(int argc, char* argv[]) {
+    Run run;
+    g_run = &run;
+    if (!parse_options(argc, argv, run.opt)) return EXIT_FAILURE;
+    read_environment(run.opt);
+    run.realtimeStart = run.phaseStart = real_time();
+    if (!check_options(run) || !load_input(run)) return EXIT_FAILURE;
+    hfm_model* model = make_model(run, run.opt.sweepListPath ? run.sweepAlphas[0].data() : run.alpha);
+    if (!model) return EXIT_FAILURE;
+    run.phase("model");
+    if (!create_context(run, model)) return EXIT_FAILURE;
+    run.phase("hf_create");
+    if (!run.opt.sweepListPath) {
         RunResult res;
-        const int r = run_em(model, std::string(outputDir), res);
+        const int r = run_em(run, model, std::string(run.opt.outputDir), res);
         if (r != 0) return r;
     } else {
-        const size_t n = sweepPaths.size();
-        std::vector<RunResult> results(n);
+        std::vector<RunResult> results(run.sweepPaths.size());
         bool anyFailed = false;
-        // plain EM on one context of the default algorithm, Gaussian models: the BATCHED engine (hf_batch_*, flagger_amd/csrc/hf_batch.h) —
-        // every pass runs all unconverged candidates of a group together; a candidate leaves the active set after its final inference
-        // pass, so its iterations and files are those of a separate --alphaTsv run.  Everything else: the candidates one after another.
-        const int cap = (!run.multi && !acceleration && modelType != HF_MODEL_NEGATIVE_BINOMIAL) ? hf_batch_capacity(run.ctx) : 0;
-        if (cap > 0) {
-            const int G = (int) std::min<size_t>((size_t) cap, n);
-            fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: batched (hf_batch), %d models per group\n", ts(), n, G);
-            const int64_t V = hf_chunk_stats_len(run.ctx);
-            struct Cand { hfm_model* m = nullptr; FILE* llf = nullptr; int iter = 1; bool converged = false, final = false, done = false; std::string dir; };
-            for (size_t g0 = 0; g0 < n; g0 += (size_t) G) {
-                const int ng = (int) std::min<size_t>((size_t) G, n - g0);
-                hf_batch* bt = nullptr;
-                if (hf_batch_create(run.ctx, ng, &bt) != HF_OK) { fprintf(stderr, "[%s] Error: %s\n", ts(), hf_last_error()); return EXIT_FAILURE; }
-                std::vector<Cand> cs((size_t) ng);
-                for (int j = 0; j < ng; j++) {
-                    const size_t i = g0 + (size_t) j;
-                    Cand& c = cs[(size_t) j];
-                    c.dir = std::string(outputDir) + "/alpha_" + std::to_string(i + 1);
-                    if (!dir_exists(c.dir.c_str()) && mkdir(c.dir.c_str(), 0777) != 0) { fprintf(stderr, "[%s] Error: cannot create %s\n", ts(), c.dir.c_str()); return EXIT_FAILURE; }
-                    c.m = i == 0 ? model : make_model(sweepAlphas[i].data());
-                    if (!c.m) return EXIT_FAILURE;
-                    fprintf(stderr, "[%s] --sweepAlpha: candidate %zu of %zu (%s) into %s\n", ts(), i + 1, n, sweepPaths[i].c_str(), c.dir.c_str());
-                    c.llf = fopen((c.dir + "/loglikelihood.tsv").c_str(), "w+");
-                    if (!c.llf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), c.dir.c_str()); return EXIT_FAILURE; }
-                    fprintf(c.llf, "#Iteration\tEffective_Iteration\tLoglikelihood\n");
-                    write_params(c.m, c.dir, "initial");
-                    c.final = numberOfIterations < 1;
-                }
-                std::vector<int8_t> lab((size_t) N);
-                while (true) {
-                    std::vector<int32_t> act;
-                    std::vector<hf_params> ps;
-                    for (int j = 0; j < ng; j++) if (!cs[(size_t) j].done) { act.push_back(j); ps.emplace_back(); hfm_params(cs[(size_t) j].m, &ps.back()); }
-                    if (act.empty()) break;
-                    std::vector<double> stats(act.size() * (size_t) V);
-                    std::vector<int32_t> status(act.size(), HF_OK);
-                    int rc = hf_batch_estep(bt, ps.data(), act.data(), (int) act.size(), HF_MODE_FULL, nullptr);
-                    if (rc == HF_OK) rc = hf_batch_finish(bt, stats.data(), status.data(), nullptr);
-                    if (rc != HF_OK) return die_estep(rc);
-                    for (size_t k = 0; k < act.size(); k++) {
-                        const int j = act[k];
-                        Cand& c = cs[(size_t) j];
-                        RunResult& res = results[g0 + (size_t) j];
-                        const double* st = stats.data() + k * (size_t) V;
-                        auto fail = [&](int r) {
-                            if (r == HF_E_SCALE) fprintf(stderr, "scale is very low!\n");
-                            else if (r == HF_E_NAN) fprintf(stderr, "[Error] prob is NAN\n");
-                            else fprintf(stderr, "[%s] Error: %s\n", ts(), cli_error_or(hf_last_error()));
-                            g_cli_error.clear();
-                            res.status = r == HF_OK ? HF_E_ARG : r; anyFailed = true; c.done = true;
-                            if (c.llf) fclose(c.llf);
-                            c.llf = nullptr;
-                        };
-                        if (status[k] != HF_OK) { fail(status[k]); continue; }
-                        fprintf(c.llf, "%d\t%d\t%.4f\n", c.iter - 1, c.iter - 1, st[0]);
-                        res.ll = st[0]; res.have_ll = true;
-                        if (!c.final) {
-                            if (writeBenchmarkingStatsPerIteration || c.iter == 1) {
-                                char suffix[64];
-                                if (c.iter == 1) snprintf(suffix, sizeof suffix, "initial");
-                                else snprintf(suffix, sizeof suffix, "iteration_%d", c.iter - 1);
-                                if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK ||
-                                    (rc = write_summary(run, c.dir, suffix, labelNames, binArrayFilePath, overlapRatioThreshold, threads, lab.data())) != HF_OK) { fail(rc); continue; }
-                            }
-                            c.converged = hfm_estimate(c.m, st, convergenceTol) != 0;
-                            if (writeParamsPerIter) {
-                                char suffix[64];
-                                snprintf(suffix, sizeof suffix, "iteration_%d", c.iter);
-                                write_params(c.m, c.dir, suffix);
-                            }
-                            c.iter += 1;
-                            if (c.iter > numberOfIterations || c.converged) {
-                                res.iterations = c.iter - 1; res.converged = c.converged;
-                                c.final = true;                          // the next pass of this candidate is its final inference
-                            }
-                            continue;
-                        }
-                        // the final inference pass: every output of a separate run
-                        res.iterations = c.iter - 1; res.converged = c.converged;
-                        fclose(c.llf);
-                        c.llf = nullptr;
-                        write_params(c.m, c.dir, "final");
-                        if ((rc = hf_batch_get_labels(bt, j, lab.data())) != HF_OK) { fail(rc); continue; }
-                        std::vector<int8_t> vlabels;
-                        if (viterbi) {
-                            vlabels.resize((size_t) N);
-                            double vlp = 0.0;
-                            if ((rc = run.viterbi(c.m, vlabels.data(), &vlp)) != HF_OK) { fail(rc); continue; }
-                            const std::string vp = c.dir + "/viterbi_log_probability.tsv";
-                            FILE* vf = fopen(vp.c_str(), "w");
-                            if (!vf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), vp.c_str()); fail(HF_E_ARG); continue; }
-                            fprintf(vf, "%.6f\n", vlp);
-                            fclose(vf);
-                        }
-                        const int8_t* finalLabels = viterbi ? vlabels.data() : lab.data();
-                        if ((rc = write_summary(run, c.dir, "final", labelNames, binArrayFilePath, overlapRatioThreshold, threads, finalLabels)) != HF_OK) { fail(rc); continue; }
-                        memcpy(hfio_prediction(tab), lab.data(), (size_t) N);
-                        if (writePosterior) {
-                            std::vector<double> post((size_t) N * 4);
-                            if ((rc = hf_batch_get_posterior(bt, j, 0, N, post.data())) != HF_OK) { fail(rc); continue; }
-                            hfio_write_posterior_bed(tab, post.data(), lab.data(), (c.dir + "/posterior_prediction_final.bed").c_str());
-                        }
-                        if (hfio_write_final_bed(tab, finalLabels, (c.dir + "/final_flagger_prediction.bed").c_str(), trackName, minLenPerState) != 0) {
-                            fprintf(stderr, "[%s] Error: %s/final_flagger_prediction.bed cannot be opened.\n", ts(), c.dir.c_str()); fail(HF_E_ARG); continue;
-                        }
-                        c.done = true;
-                    }
-                }
-                if (!summary_join_report()) { anyFailed = true; }
-                hf_batch_destroy(bt);
-            }
-        } else {
-        // --sweepAlpha: the candidates one after another on the context (or GPU list) loaded above, each exactly a separate run
-        fprintf(stderr, "[%s] --sweepAlpha: %zu candidates on one loaded input, engine: sequential (%s), 1 model per group\n", ts(), n,
-                run.multi ? "sharded GPU list" : "one context");
-        for (size_t i = 0; i < n; i++) {
-            const std::string cdir = std::string(outputDir) + "/alpha_" + std::to_string(i + 1);
-            if (!dir_exists(cdir.c_str()) && mkdir(cdir.c_str(), 0777) != 0) {
-                fprintf(stderr, "[%s] Error: cannot create %s\n", ts(), cdir.c_str()); return EXIT_FAILURE;
-            }
-            hfm_model* m = i == 0 ? model : make_model(sweepAlphas[i].data());
-            if (!m) return EXIT_FAILURE;
-            fprintf(stderr, "[%s] --sweepAlpha: candidate %zu of %zu (%s) into %s\n", ts(), i + 1, n, sweepPaths[i].c_str(), cdir.c_str());
-            const int r = run_em(m, cdir, results[i]);
-            if (r != 0) {
-                anyFailed = true;
-                if (results[i].status == HF_OK) results[i].status = HF_E_ARG;
-                g_cli_error.clear();
-                // (a failed table set of this candidate has been reported; the next candidate starts with no worker of its own pending)
-                summary_wait_quietly();
-                g_summaries.clear();
-            }
-        }
-        }
-        const std::string sp = std::string(outputDir) + "/alpha_sweep.tsv";
-        FILE* sf = fopen(sp.c_str(), "w");
-        if (!sf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), sp.c_str()); return EXIT_FAILURE; }
-        fprintf(sf, "#Index\tAlpha_Tsv\tIterations\tConverged\tLoglikelihood\tStatus\n");
-        for (size_t i = 0; i < n; i++) {
-            const RunResult& r = results[i];
-            const char* st = r.status == HF_OK ? "ok" : r.status == HF_E_SCALE ? "scale_too_low" : r.status == HF_E_NAN ? "nan" : "error";
-            if (r.have_ll) fprintf(sf, "%zu\t%s\t%d\t%d\t%.4f\t%s\n", i + 1, sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, r.ll, st);
-            else fprintf(sf, "%zu\t%s\t%d\t%d\tNA\t%s\n", i + 1, sweepPaths[i].c_str(), r.iterations, r.converged ? 1 : 0, st);
-        }
-        fclose(sf);
+        // plain EM on one context of the default algorithm, Gaussian models: the batched engine.  Everything else: the candidates one after another.
+        const int cap = (!run.multi && !run.opt.acceleration && run.opt.modelType != HF_MODEL_NEGATIVE_BINOMIAL) ? hf_batch_capacity(run.ctx) : 0;
+        if (!(cap > 0 ? sweep_batched(run, model, cap, results, anyFailed) : sweep_sequential(run, model, results, anyFailed))) return EXIT_FAILURE;
+        const std::string sp = std::string(run.opt.outputDir) + "/alpha_sweep.tsv";
+        if (!write_sweep_table(run, results, sp)) return EXIT_FAILURE;
         if (anyFailed) {
             if (run.multi) hf_multi_destroy(run.multi);
             fprintf(stderr, "[%s] Error: at least one --sweepAlpha candidate failed (%s)\n", ts(), sp.c_str());
@@ -1944,8 +1942,8 @@ int main(int argc, char* argv[]) {
     // the one-GPU context, the model and the window table are NOT destroyed: the process ends below without unwinding anything
     // (freeing ~40 device allocations one by one was 5 ms of a 0.15 s run)
     fprintf(stderr, "[%s] Done! \n", ts());
-    phase("outputs");
-    const double realtime = real_time() - realtimeStart, cputime = cpu_time();
+    run.phase("outputs");
+    const double realtime = real_time() - run.realtimeStart, cputime = cpu_time();
     fprintf(stderr, "Real time:  %.3f sec; CPU: %.3f sec; Peak RSS: %.3f GB; CPU usage: %.1f%%\n", realtime, cputime,
             peak_rss_gb(), (cputime + 1e-9) / (realtime + 1e-9) * 100.0);
     // every output is written and closed: leave without unwinding the HIP runtime and the device allocations (the
