@@ -20,7 +20,11 @@
 //             b_b[p] * f_a'[s]
 //   the end: N_none = sum over the non-HIT lanes of x * b_b[state of the lane], N_hit the same over the HIT lanes
 //
-// NUMERICS.  Linear domain; value = x * 2^E with two integer exponent sums, E_n of the non-HIT lanes and E_h of the HIT lanes.  After
+// NUMERICS.  Linear domain; value = x * 2^E with two integer exponent sums, E_n of the non-HIT lanes and E_h of the HIT lanes.  The
+// group's first vector: e_0 = ilogb(max_s f_a[s]) - HF_LR_TARGET (0 when that maximum is 0 or not finite), every lane is scaled by 2^-e_0
+// and E_n = E_h = e_0, so that the first period starts from the target like every later one: a row's entries can be as small as a
+// transition probability times the emission floor of 1e-40, and HF_LR_RENORM such steps from magnitude 1 end at 3.7e-321, a subnormal
+// (from 2^HF_LR_TARGET at 1e-230).  A group that ends before its first renormalisation is scaled back by 2^e_0 before the end.  After
 // every HF_LR_RENORM-th step, counted from the group's first window (so a group's bits depend on the job alone), with m_n = max_p T[p]
 // and m_h = max_p H[p] taken BEFORE that step: e_n = ilogb(m_n) - HF_LR_TARGET (0 when m_n is 0 or not finite), the non-HIT lanes are
 // scaled by 2^-e_n and E_n += e_n; e_h = ilogb(m_h) - HF_LR_TARGET, or E_n - E_h when m_h is 0 (the HIT lanes then hold fresh inflow
@@ -29,6 +33,10 @@
 // none can come back, and E_n = E_h.  The large target leaves a lane 2^-1300
 // below its class's largest total representable, so a counter lane of a very improbable run keeps its bits.  Every sum over lanes
 // is ch_wave_sum (hf_chain.h), which has one order.
+// NOT COVERED: a joined boundary's row b_b[p] f_a'[s] is no probability.  The pass's vectors satisfy sum_s f_t[s] b_t[s] = 1e-4 / scale_t,
+// so behind a floored window b_b is about 1e36 (2^120).  One such boundary in a period is harmless; HF_LR_RENORM joined one-window
+// chunks on the floor in one period multiply by 2^960 on top of the target and overflow (Inf, then the NaN of the end).  Read from the
+// code, not run; a renormalisation at every joined boundary would remove it.
 // The two logs, with d = (log N_hit - log N_none) + (E_h - E_n) ln 2:
 //   d < 0:   log_p_none = -log1p(exp(d)),       log_p_some = d - log1p(exp(d))
 //   d >= 0:  log_p_none = -d - log1p(exp(-d)),  log_p_some = -log1p(exp(-d))
@@ -114,13 +122,21 @@ __global__ void __launch_bounds__(64) k_lr_chain(const LrGroup* __restrict__ gro
     int q = q_first;
     LrPart pt = parts[q];
     double x;
+    long long En = 0, Eh = 0;
     {
         double f[4];
         mo_f<SEQ>(pv, pt.c, pt.a, f);
         const double fs = lr_pick(f, st);
         x = (L == 1 ? (cls == LR_OUT || (cls == LR_HIT && st_in)) : (cls == LR_ENTRY || cls == LR_OUT)) ? fs : 0.0;
+        // the first vector goes to the target like every later period's: eight steps over floored rows (1e-40 each) from magnitude 1
+        // would end subnormal.  Both classes take the one exponent, a power of two: every value of the first period is the unscaled
+        // one times 2^-e0 exactly, and E_n, E_h after the first renormalisation are what they were without it
+        const double fm = fmax(fmax(f[0], f[1]), fmax(f[2], f[3]));
+        int e0 = 0;
+        if (fm > 0.0 && !isinf(fm)) e0 = ilogb(fm) - HF_LR_TARGET;
+        x = ldexp(x, -e0);
+        En = Eh = e0;
     }
-    long long En = 0, Eh = 0;
     int sh = 0;                 // E_n - E_h, clamped for ldexp
     unsigned step = 0;
 
@@ -200,6 +216,9 @@ __global__ void __launch_bounds__(64) k_lr_chain(const LrGroup* __restrict__ gro
     }
 
     // the end: the dot products with b of the group's last window
+    // (a group that was never renormalised goes back to the magnitude of its f_a first: log() of a value and of its 2^300-fold round
+    // differently, and the result of so short a group shall not depend on HF_LR_TARGET)
+    if (step < HF_LR_RENORM) x = ldexp(x, (int) En);        // (E_n = E_h = e_0 still)
     double bb[4];
     mo_b<SEQ>(pv, pt.c, pt.b, bb);
     const double xb = x * lr_pick(bb, st);
