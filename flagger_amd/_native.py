@@ -132,6 +132,7 @@ def lib() -> C.CDLL:
     sig("hf_get_viterbi_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_chunk_log_probs", C.c_int, vp, pd)
     sig("hf_viterbi_minlen", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), vp)
+    sig("hf_viterbi_minlen_joined", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), vp)
     sig("hf_viterbi_minlen_finish", C.c_int, vp, pd, vp)
     sig("hf_get_viterbi_minlen_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_minlen_chunk_log_probs", C.c_int, vp, pd)

@@ -53,7 +53,7 @@ static double peak_rss_gb() { struct rusage r; getrusage(RUSAGE_SELF, &r); retur
 enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
-    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples
+    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -95,6 +95,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"enforceMinimumLengths", no_argument, nullptr, kOptEnforceMinLen},      // --viterbi decodes UNDER --minimumLengths (hf_viterbi_minlen; not `min...`: --mini stays --minimumLengths)
     {"constrainedPosterior", no_argument, nullptr, kOptConstrainedPosterior},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
     {"admissibleSamples", required_argument, nullptr, kOptAdmissibleSamples},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
+    {"wholeContigs", no_argument, nullptr, kOptWholeContigs},             // --enforceMinimumLengths over the joined chunks of a contig (hf_viterbi_minlen_joined; nothing else starts with --wh, --w was ambiguous already; not `j...`: --j stays --jointEntropy)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -182,6 +183,15 @@ static void usage(const char* program) {
             "                                      of the path written, viterbi_min_length_cost.tsv the four window counts, the constrained and the\n"
             "                                      unconstrained score, their difference and the number of chunks whose two paths differ; one GPU, not\n"
             "                                      with --gpus N>1 or --sweepAlpha\n"
+            "         --wholeContigs               with --viterbi --enforceMinimumLengths: the minimum lengths hold over the whole contig, not per\n"
+            "                                      chunk: chunks adjacent in the chunk list with the same contig name are joined (the rule of\n"
+            "                                      --numBlocks), a run counts across their boundary, and only runs at the ends of such a group are\n"
+            "                                      exempt, so that the final BED's filter has nothing left to relabel inside a contig; the final\n"
+            "                                      labels and viterbi_log_probability.tsv are the joined decoder's, viterbi_min_length_cost.tsv is\n"
+            "                                      filled from the joined run and gains two columns: log_prob_constrained_per_chunk (the score\n"
+            "                                      under the per-chunk rule) and short_runs_per_chunk_rule (the runs of the per-chunk labels, merged\n"
+            "                                      over the chunks of a contig, that touch neither end of their group and are shorter than their\n"
+            "                                      minimum: what the BED filter relabelled); one GPU, not with --gpus N>1 or --sweepAlpha\n"
             "         --keptBlocks                 with --minimumLengths: after every other output, write kept_block_probabilities.tsv: for the whole\n"
             "                                      track, every contig and (with --regionProbs FILE) every region, and for every label, the exact\n"
             "                                      probability that the scope holds a block of the label long enough to be kept (lengths in windows\n"
@@ -223,7 +233,7 @@ struct Options {
     int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0, initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
+    bool viterbi = false, enforceMinLen = false, wholeContigs = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
     int admissibleSamples = 0; bool admissibleSet = false;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
@@ -291,6 +301,13 @@ struct Run {
     int viterbi_minlen(hfm_model* m, const int32_t min_len[4], int8_t* out, double* log_prob) {
         const hf_params p = params(m);
         int rc = hf_viterbi_minlen(ctx, &p, min_len, nullptr);
+        if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
+        return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
+    }
+    // ... with the rule over the groups of joined chunks (--wholeContigs)
+    int viterbi_minlen_joined(hfm_model* m, const int32_t min_len[4], const uint8_t* joined, int8_t* out, double* log_prob) {
+        const hf_params p = params(m);
+        int rc = hf_viterbi_minlen_joined(ctx, &p, min_len, joined, nullptr);
         if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
         return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
     }
@@ -1127,7 +1144,7 @@ static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
     {'B', &Options::dumpBin}, {'k', &Options::writeBenchmarkingStatsPerIteration}, {'w', &Options::writeParamsPerIter}, {'P', &Options::writePosterior},
     {'s', &Options::acceleration}, {kOptViterbi, &Options::viterbi}, {kOptRunConfidence, &Options::runConfidence}, {kOptExactTotals, &Options::exactTotals},
     {kOptNumBlocks, &Options::numBlocks}, {kOptRunBoundaries, &Options::runBoundaries}, {kOptJointEntropy, &Options::jointEntropy}, {kOptFitAlpha, &Options::fitAlpha},
-    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}};
+    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}};
 static const struct { int code; const char* Options::*text; } kTextOptions[] = {
     {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
     {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath}};
@@ -1288,7 +1305,7 @@ static bool min_len_windows(Run& s, int W) {
         }
     if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
     std::string who;                                           // the options that walk the expanded chain, as given
-    for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
+    for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
                           o.admissibleSet ? "admissibleSamples" : nullptr})
         if (n) who += (who.empty() ? "" : ", --") + std::string(n);
     fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
@@ -1325,6 +1342,8 @@ static bool check_options(Run& s) {
     const OptionCheck afterRegions[] = {
         {"--gpus", true, o.nGpus < 0 || o.nGpus > 64 || o.loopbackRanks < 0 || o.loopbackRanks > 64 ? "should be between 1 and 64" : nullptr, kNoGpuRule},
         {"--gpus and HF_LOOPBACK_RANKS", o.nGpus > 0 && o.loopbackRanks > 0, "exclude each other", kNoGpuRule},
+        // (--wholeContigs is refused wherever --enforceMinimumLengths is, and its row comes first so that the line names it)
+        {"--wholeContigs", o.wholeContigs, o.viterbi && o.enforceMinLen ? nullptr : "needs --viterbi --enforceMinimumLengths", kOneGpuNoLoopback},
         {"--enforceMinimumLengths", o.enforceMinLen, o.viterbi ? nullptr : "needs --viterbi", kOneGpuNoLoopback},
         {"--keptBlocks", o.keptBlocks, needsMinLen, kOneGpuNoLoopback},
         {"--constrainedPosterior", o.constrainedPost, needsMinLen, kOneGpuNoLoopback},
@@ -1600,6 +1619,33 @@ static int em_loop(Run& s, EmRun& em) {
     return 0;
 }
 
+// --wholeContigs: joined[c], chunk c continues chunk c-1 (adjacent in the chunk list, the same contig name: the rule of --numBlocks)
+static std::vector<uint8_t> joined_chunks(const hfio_table* tab) {
+    const int C = hfio_n_chunks(tab);
+    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
+    for (int c = 1; c < C; c++) joined[(size_t) c] = std::string(hfio_chunk_ctg(tab, c)) == hfio_chunk_ctg(tab, c - 1);
+    return joined;
+}
+
+// ... and the maximal runs of `labels`, merged over every group of joined chunks (a chunk without windows ends a group), that touch
+// neither end of their group and have fewer than min_len windows of their label
+static long long short_inner_runs(const hf_windows& w, const std::vector<uint8_t>& joined, const int8_t* labels, const int32_t min_len[4]) {
+    long long count = 0;
+    for (int c0 = 0; c0 < w.n_chunks;) {
+        int c1 = c0 + 1;
+        while (c1 < w.n_chunks && joined[(size_t) c1] && w.chunk_off[c1 + 1] > w.chunk_off[c1] && w.chunk_off[c1] > w.chunk_off[c1 - 1]) c1++;
+        const int64_t t0 = w.chunk_off[c0], t1 = w.chunk_off[c1];
+        for (int64_t a = t0; a < t1;) {
+            int64_t b = a;
+            while (b + 1 < t1 && labels[b + 1] == labels[a]) b++;
+            if (a > t0 && b < t1 - 1 && labels[a] >= 0 && labels[a] < 4 && b - a + 1 < min_len[labels[a]]) count++;
+            a = b + 1;
+        }
+        c0 = c1;
+    }
+    return count;
+}
+
 // 5b. the final inference: the last pass, its labels, --viterbi and --enforceMinimumLengths with the cost file
 static int final_inference(Run& s, EmRun& em) {
     const Options& o = s.opt;
@@ -1642,14 +1688,26 @@ static int final_inference(Run& s, EmRun& em) {
         std::vector<int8_t> clabels((size_t) N);
         double clp = 0.0;
         if ((rc = s.viterbi_minlen(em.model, mw, clabels.data(), &clp)) != HF_OK) return em.die(rc);
+        // --wholeContigs: the rule over the joined chunks of a contig; the per-chunk run above is what the whole-contig rule is compared with
+        double pclp = 0.0;
+        long long shortRuns = 0;
+        if (o.wholeContigs) {
+            const std::vector<uint8_t> joined = joined_chunks(s.tab);
+            pclp = clp;
+            shortRuns = short_inner_runs(s.w, joined, clabels.data(), mw);
+            if ((rc = s.viterbi_minlen_joined(em.model, mw, joined.data(), clabels.data(), &clp)) != HF_OK) return em.die(rc);
+        }
         int differ = 0;
         for (int c = 0; c < s.w.n_chunks; c++)
             differ += memcmp(clabels.data() + s.w.chunk_off[c], vlabels.data() + s.w.chunk_off[c], (size_t) (s.w.chunk_off[c + 1] - s.w.chunk_off[c])) != 0;
         const std::string cp = dir + "/viterbi_min_length_cost.tsv";
         FILE* cf = fopen(cp.c_str(), "w");
         if (!cf) { fprintf(stderr, "[%s] Error: %s cannot be opened.\n", ts(), cp.c_str()); return EXIT_FAILURE; }
-        fprintf(cf, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\tlog_prob_constrained\tlog_prob_unconstrained\tlog_prob_difference\tchunks_changed\n");
-        fprintf(cf, "%d\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%d\n", mw[0], mw[1], mw[2], mw[3], clp, vlp, clp - vlp, differ);
+        fprintf(cf, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\tlog_prob_constrained\tlog_prob_unconstrained\tlog_prob_difference\tchunks_changed%s\n",
+                o.wholeContigs ? "\tlog_prob_constrained_per_chunk\tshort_runs_per_chunk_rule" : "");
+        fprintf(cf, "%d\t%d\t%d\t%d\t%.6f\t%.6f\t%.6f\t%d", mw[0], mw[1], mw[2], mw[3], clp, vlp, clp - vlp, differ);
+        if (o.wholeContigs) fprintf(cf, "\t%.6f\t%lld", pclp, shortRuns);
+        fprintf(cf, "\n");
         fclose(cf);
         fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows: log-probability %.6f (unconstrained %.6f), %d chunks changed\n",
                 ts(), mw[0], mw[1], mw[2], mw[3], clp, vlp, differ);

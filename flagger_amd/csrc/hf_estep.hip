@@ -440,6 +440,9 @@ struct Viterbi : LabelDecoder {
 // minimum-run-length Viterbi (hf_minlen.h): rows always in window order, one 16-bit backpointer word per window; the chunk values: the scores
 struct MinLenViterbi : LabelDecoder {
     uint16_t* d_bp = nullptr; uint8_t* d_final = nullptr;     // ... and the final lane of every chunk
+    // hf_viterbi_minlen_joined (hf_minlen_joined.h): the groups of a call, window ranges [G + 1] and first chunks [G], G <= C
+    int64_t* d_goff = nullptr; int32_t* d_gchunk = nullptr;
+    std::vector<int64_t> h_goff; std::vector<int32_t> h_gchunk;
 };
 
 // posterior path sampling (hf_sample.h).  The per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more.
@@ -2999,6 +3002,7 @@ static_assert(HF_MINLEN_MAX_LANES == 64, "one wavefront holds the expanded chain
 template <class F> static void mlv_arrays(const Track& tr, MinLenViterbi& v, F&& f) {
     dec_front_arrays(tr, v, (size_t) tr.N, f);
     f(v.d_bp, (size_t) tr.N * 2); f(v.d_label, (size_t) tr.N); f(v.d_chunk, (size_t) tr.C * 8); f(v.d_final, (size_t) tr.C);
+    f(v.d_goff, ((size_t) tr.C + 1) * 8); f(v.d_gchunk, (size_t) tr.C * 4);
 }
 
 // the four minimum lengths of a call to `who`: every one >= 1, at most HF_MINLEN_MAX_LANES lanes together
@@ -3358,5 +3362,50 @@ int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
     const Track& tr = ctx->tr;
     HIPCHK(hipSetDevice(tr.device));
     if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mls.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// minimum-run-length Viterbi over whole contigs (hf_minlen_joined.h): hf_viterbi_minlen's decoder with the rule applied to groups of
+// joined chunks.  It shares ctx->mlv, its buffers, hf_viterbi_minlen_finish and the two getters; the groups of a call are cut here.  Last
+// in the file, its kernel included, so that no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_joined.h"
+
+int hf_viterbi_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, void* stream) {
+    const std::string w = "hf_viterbi_minlen_joined";
+    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
+    int64_t lanes = 0;
+    int rc = minlen_check(w, min_len, &lanes);
+    if (rc) return rc;
+    const Track& tr = ctx->tr;
+    if (joined && tr.C > 0 && joined[0]) return set_err(HF_E_ARG, w + ": joined[0] must be 0 (the first chunk continues nothing)");
+    MinLenViterbi& v = ctx->mlv;
+    hipStream_t st = (hipStream_t) stream;
+    const double* nbE = nullptr;
+    rc = dec_front(tr, v, p, st, w, [&] { return dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); }); }, nbE);
+    if (rc || (rc = dec_clear_outputs(tr, v, 1, st))) return rc;
+    if (dec_work(tr)) {
+        // a chunk starts a group unless it is joined to its predecessor and both have windows (a chunk without windows has no part)
+        const std::vector<int64_t>& off = tr.h_off;
+        v.h_goff.clear(); v.h_gchunk.clear();
+        for (int c = 0; c < tr.C; c++) {
+            const bool cont = c > 0 && joined && joined[c] && off[(size_t) c + 1] > off[(size_t) c] && off[(size_t) c] > off[(size_t) c - 1];
+            if (!cont) { v.h_gchunk.push_back(c); v.h_goff.push_back(off[(size_t) c]); }
+        }
+        v.h_goff.push_back(off[(size_t) tr.C]);
+        const size_t G = v.h_gchunk.size();
+        HIPCHK(hipMemcpyAsync(v.d_goff, v.h_goff.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(v.d_gchunk, v.h_gchunk.data(), G * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
+                           v.d_rows, v.d_flags);
+        hipLaunchKernelGGL(k_mlvj_fwd, dim3((unsigned) G), dim3(64), 0, st, v.d_goff, v.d_gchunk, tr.d_rec, v.d_params, v.d_rows,
+                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) G), dim3(64), 0, st, v.d_goff, (int) min_len[0], (int) min_len[1], (int) min_len[2],
+                           (int) min_len[3], v.d_bp, v.d_final, v.d_label);
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
     return HF_OK;
 }

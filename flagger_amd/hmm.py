@@ -563,14 +563,25 @@ class EMList:
             raise ValueError("%s: min_len holds four window counts (Err, Dup, Hap, Col)" % who)
         return np.ascontiguousarray(ml, dtype=np.int32)
 
-    def viterbi_minlen(self, model: HMM, min_len):
+    def viterbi_minlen(self, model: HMM, min_len, joined=None):
         """The most probable path among the paths whose runs have at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at
         a chunk's ends are exempt; hf_viterbi_minlen + hf_viterbi_minlen_finish): (labels, chunk_log_probs, log_prob).  The last pass's
-        results, viterbi()'s and the sampler's are left as they were."""
+        results, viterbi()'s and the sampler's are left as they were.  joined: None, or a bool array of n_chunks as for run_moments,
+        joined[c] true where chunk c continues chunk c - 1 (joined_chunks(store) derives it from the contig names): the rule then holds
+        over every group of joined chunks, only runs at a group's ends are exempt (hf_viterbi_minlen_joined), and chunk_log_probs holds
+        a group's score in the entry of its first chunk and 0.0 in the others."""
         ml = self._four_lengths("viterbi_minlen", min_len)
         p = model.params()
         lp = C.c_double(0.0)
-        N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_viterbi_minlen")
+        mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
+        if joined is None:
+            N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), mlp, self.stream), "hf_viterbi_minlen")
+        else:
+            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
+            if jn.size != int(self._L.hf_n_chunks(self._h)):
+                raise ValueError("viterbi_minlen: joined must have one entry per chunk")
+            N.check(self._L.hf_viterbi_minlen_joined(self._h, C.byref(p), mlp, jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream),
+                    "hf_viterbi_minlen_joined")
         N.check(self._L.hf_viterbi_minlen_finish(self._h, C.byref(lp), self.stream), "hf_viterbi_minlen_finish")
         labels = np.empty(self.store.n_windows, dtype=np.int8)
         N.check(self._L.hf_get_viterbi_minlen_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_viterbi_minlen_labels")
@@ -880,13 +891,26 @@ def EM_runViterbiForList(emList, model: HMM):
     return emList.viterbi(model)
 
 
-def EM_runMinLengthViterbiForList(emList, model: HMM, min_len):
+def EM_runMinLengthViterbiForList(emList, model: HMM, min_len, joined=None):
     """Most-probable-path decoding under minimum run lengths (no counterpart in the reference, which relabels short runs after decoding):
     the best path among those whose runs of state s have at least min_len[s] windows, runs at a chunk's ends exempt.  Returns what
-    EM_runViterbiForList returns.  `emList`: an EMList."""
+    EM_runViterbiForList returns.  joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole
+    groups of joined chunks and only runs at a group's ends are exempt.  `emList`: an EMList."""
     if not hasattr(emList, "viterbi_minlen"):
         raise TypeError("EM_runMinLengthViterbiForList: %s has no minimum-run-length decoder" % type(emList).__name__)
-    return emList.viterbi_minlen(model, min_len)
+    if joined is None:
+        return emList.viterbi_minlen(model, min_len)
+    return emList.viterbi_minlen(model, min_len, joined)
+
+
+def joined_chunks(store) -> np.ndarray:
+    """The `joined` array of a store: bool[n_chunks], true where chunk c carries the contig name of chunk c - 1 (the chunks of a contig
+    as the final BED merges them; the rule of hmm_flagger --numBlocks)."""
+    ctg = np.asarray(store.chunk_ctg)
+    out = np.zeros(ctg.size, bool)
+    if ctg.size > 1:
+        out[1:] = ctg[1:] == ctg[:-1]
+    return out
 
 
 class MinLenPosterior:

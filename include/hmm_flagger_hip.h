@@ -502,6 +502,39 @@ int hf_viterbi_minlen_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_minlen_labels(hf_ctx *ctx, int8_t *labels_host);                   /* [n_windows] */
 int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx *ctx, double *out_host);             /* [n_chunks] */
 
+/* Minimum-run-length Viterbi over whole contigs (flagger_amd/csrc/hf_minlen_joined.h): hf_viterbi_minlen with the rule applied to GROUPS
+ * of joined chunks instead of chunks.  joined follows the rule hf_get_run_moments states: NULL means all 0; joined[0] must be 0;
+ * joined[c] != 0 says that chunk c continues chunk c-1; a chunk without windows has no part, so it ends a group whatever its own entry
+ * and its successor's entry say.  A GROUP is a maximal sequence of chunks joined to each other; chunk offsets are one array, so a group
+ * is one contiguous window range, and its path is the concatenation of its chunks' paths.  Chunks are independent chains: the weight of
+ * a group's path is the product of its chunks' weights, first * prod_t A_t * end per chunk, exactly as in hf_viterbi.
+ * A group's path is ADMISSIBLE when every maximal run of equal state s IN THE GROUP'S LABEL SEQUENCE has at least min_len[s] windows;
+ * only a run that contains the group's first or last window is exempt.  The decoder returns the admissible group path of the largest
+ * weight.  The expanded chain, its lanes, the entry, in-between and saturated steps and every tie rule are those of hf_viterbi_minlen,
+ * carried in logs, with
+ *   window 0 and the end: the group's first window and the end at the group's last window take the place of the chunk's;
+ *   the step into the first window t of a chunk c joined to c-1: an ordinary step with the row
+ *               J_t[p][s] = log end_{c-1}[p] + log first_c[s],   end_{c-1}[p] = trans[r_{t-1}][p][4],
+ *               formed first as one double (-inf when either term is -inf), then used like any log A_t[p][s].  The run counter runs on
+ *               across the boundary: staying in s goes from (s, d) to (s, min(d+1, min_len[s])), a change of state needs the saturated
+ *               lane of p and enters (s, 1), and p == s is excluded when min_len[s] > 1 as everywhere.
+ * Restated: the joined decoder on (chunk list, joined) is hf_viterbi_minlen on the chunk list whose chunks are the groups, with the row
+ * of every joined chunk-first window replaced by J_t and end taken from the group's last chunk.
+ * Scores: a group's score is the log of its maximum, the run's score the sum over groups in list order.
+ * hf_get_viterbi_minlen_chunk_log_probs returns the group's score in the entry of the group's first chunk and exactly 0.0 in the
+ * entries of its other chunks, so that its list-order sum is the run's score; a chunk without windows scores 0.0; windows outside every
+ * chunk get label -1.  HF_E_SCALE when no admissible path of a group has weight; HF_E_NAN on a NaN in a row or in an end column, the end
+ * columns read at joined boundaries included; HF_E_ARG: the cases of hf_viterbi_minlen, and joined[0] != 0.
+ * Exact cases: joined NULL or all zero gives the labels, chunk scores and run score of hf_viterbi_minlen bit for bit; all four lengths 1
+ * gives the labels of hf_viterbi whatever joined says; the joined-admissible paths are a subset of the per-chunk-admissible ones, so a
+ * group's score is never above the sum of its chunks' hf_viterbi_minlen scores, to rounding.
+ * The call is asynchronous as hf_viterbi_minlen is and shares that decoder's state: hf_viterbi_minlen_finish,
+ * hf_get_viterbi_minlen_labels and hf_get_viterbi_minlen_chunk_log_probs answer for the last finished run of either entry point.  Its
+ * buffers are that decoder's own: the last pass, hf_viterbi, both samplers, hf_minlen_posterior and the next hf_estep are bitwise
+ * unaffected.  One code path serves both kinds of context and all three model types.  hf_batch_* and hf_multi_* have no counterpart. */
+int hf_viterbi_minlen_joined(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4],
+                             const uint8_t *joined /* [n_chunks], NULL: none */, void *stream);
+
 /* Posteriors under minimum run lengths (flagger_amd/csrc/hf_minlen_post.h): the sum-product twin of hf_viterbi_minlen.  first[s],
  * A_t[p][s], end[s], min_len[4], admissibility (runs that contain a chunk's first or last window are exempt), the lanes (s, d),
  * d = 1..min_len[s], and the lane index sum_{q<s} min_len[q] + d - 1 are exactly those of hf_viterbi_minlen; so are 1 <= min_len[s] and
