@@ -3,28 +3,52 @@ seeds cover can be checked without a GPU (tests/test_streams_cpu.py).
 
 An operation is a string: a pass ("pass_a", "pass_b": full passes with two models; "forward": a forward-only pass), a switch ("flip": the
 other statistics mode, scan contexts only; "alpha_on" / "alpha_off": hf_set_alpha_stats), a decoder with parameters other than the last
-pass's ("viterbi", "sample", "viterbi_minlen"), or one of GETTERS.
+pass's ("viterbi", "sample", "viterbi_minlen", and in generation 3 the three of MINLEN_DECODERS), or one of GETTERS.
 
-There are two GENERATIONS of sequences.  What rnd.choice draws depends on the tuple it draws from, so the getters and decoders a seed
+There are three GENERATIONS of sequences.  What rnd.choice draws depends on the tuple it draws from, so the getters and decoders a seed
 was chosen with are pinned to it: generation 1 is the ten getters and two decoders the first four seeds were committed with (their
 lists never change: tests/test_streams_cpu.py holds a digest of them), generation 2 adds the breakpoint and long-run getters and the
 minimum-length decoder.  The seeds of generation 2 were chosen on the CPU: with the tuples extended in the order below, random sets of
 four seeds below 1000 were drawn until `coverage` met the conditions of test_streams_cpu.test_committed_seeds_cover_every_getter for all
 thirteen getters and every operation occurred.  At lengths 40 and 48 no set did in 20 000 draws (thirteen getters need more getter
 calls than ten); at length 64 such a search ends within a few hundred draws (random.Random(0).sample(range(1000), 4): the 328th), and
-the set below is one that an earlier search of this kind met after 183."""
+the set below is one that an earlier search of this kind met after 183.
+
+Generation 3 adds the three newest decoders (MINLEN_DECODERS) to the thirteen getters and three decoders of generation 2.  These carry
+state from call to call: hf_viterbi_minlen_joined shares its decoder state with hf_viterbi_minlen, and the forward lanes of
+hf_minlen_posterior and hf_sample_paths_minlen and the sampler's per-sample slab grow with a call's arguments and never shrink.  So
+in generation 3 the arguments of a decoder call come from its ORDINAL, the number of earlier calls of the same decoder in the sequence
+(`decoder_arguments`): the minimum lengths from LENS_CYCLE (16, 64, 4, 64 and 7 lanes: the buffer grows, then serves narrower calls),
+the sample count of "sample_minlen" from SAMPLE_CYCLE (padded to 64, 128, 64, 64 words per window) and the joined vector of
+"viterbi_minlen_joined" from JOIN_CYCLE (`join_vector`).  Its seeds were chosen on the CPU as those of generation 2 were:
+random.Random(0).sample(range(1000), 4) was drawn until the set was disjoint from the seeds of generations 1 and 2 and met, at length
+64, the getter conditions above and the conditions of test_streams_cpu.test_generation_3_covers_the_decoders (`decoder_coverage`:
+every decoder twice, each new decoder after a forward-only pass and three times in one sequence, both orders on the shared state, for
+each buffer one call that grows it and two that do not, three join kinds).  The 328th draw, (586, 294, 195, 107), meets the getter
+conditions with the six decoders too, but each of the three buffers has only ONE call in its sequences that does not grow it; the
+first draw that meets everything is the 3071st, the set below (the seventh disjoint set that meets the getter conditions)."""
 import random
 
 GETTERS = ("labels", "posterior", "forward_backward", "interval_log_probs", "count_moments", "run_moments", "path_entropy",
            "path_log_probs", "entropy_profile", "alpha_stats", "breakpoints", "breakpoint_profile", "long_run_log_probs")
 PASSES = ("pass_a", "pass_b", "forward")
 DECODERS = ("viterbi", "sample", "viterbi_minlen")
+MINLEN_DECODERS = ("minlen_posterior", "sample_minlen", "viterbi_minlen_joined")
 SWITCHES = ("flip", "alpha_on", "alpha_off")
 # generation -> (getters, decoders, length, seeds)
 GENERATIONS = {
     1: (GETTERS[:10], DECODERS[:2], 40, (148, 97, 63, 0)),
     2: (GETTERS, DECODERS, 64, (812, 661, 955, 426)),
+    3: (GETTERS, DECODERS + MINLEN_DECODERS, 64, (207, 692, 582, 391)),
 }
+# generation 3: the n-th call of a decoder in a sequence (from 0) takes entry n % len of these
+LENS_CYCLE = ((3, 5, 1, 7), (16, 16, 16, 16), (1, 1, 1, 1), (61, 1, 1, 1), (2, 1, 1, 3))      # 16, 64, 4, 64 and 7 lanes
+SAMPLE_CYCLE = (8, 65, 3, 64)                                  # samples per call of "sample_minlen"
+JOIN_CYCLE = ("null", "all", "random", "zeros")                # the joined vector of "viterbi_minlen_joined" (join_vector)
+JOIN_SEED = 20261020
+MINLEN_USERS = ("viterbi_minlen",) + MINLEN_DECODERS           # the decoders that take minimum lengths
+SHARED_STATE = ("viterbi_minlen", "viterbi_minlen_joined")     # two entry points, one decoder state
+BUFFERS = {"minlen_posterior": ("fwd",), "sample_minlen": ("fwd", "samples")}      # decoder -> its buffers that grow and never shrink
 LENGTH = GENERATIONS[1][2]
 SEEDS = GENERATIONS[1][3]
 
@@ -102,4 +126,81 @@ def coverage(seeds=None, generation: int = 1, length=None):
                 cov[op]["first_after_full"] += 1
             if st["prev"] in decoders:
                 cov[op]["after_decoder"] += 1
+    return cov
+
+
+def join_vector(kind, n_chunks):
+    """The joined vector of JOIN_CYCLE's entry `kind` for a track of n_chunks chunks: None ("null": a NULL pointer) or a list of 0/1
+    with [0] = 0.  "all": every chunk continues its predecessor, one group spans the track; "random": Bernoulli(1/2), seeded;
+    "zeros": nothing is joined.  The vectors are synthetic (the ABI takes any vector)."""
+    if kind == "null":
+        return None
+    if kind == "all":
+        return [0] + [1] * (n_chunks - 1) if n_chunks else []
+    if kind == "zeros":
+        return [0] * n_chunks
+    assert kind == "random"
+    rnd = random.Random(JOIN_SEED)
+    return [0 if c == 0 else int(rnd.random() < 0.5) for c in range(n_chunks)]
+
+
+def decoder_arguments(ops, generation: int = 3):
+    """(op, args, grows) for every operation.  For a decoder, `args` is a dict: "ordinal" (the number of earlier calls of the same decoder
+    in `ops`), and what the decoder takes of "min_len", "n_samples" (sample_minlen) and "join" (viterbi_minlen_joined: an entry of
+    JOIN_CYCLE); `grows` is the tuple of the decoder's BUFFERS this call grows: "fwd" when its lengths have more lanes than those of
+    every earlier call of the decoder, "samples" when it asks for more samples than every earlier call (the first call grows all of
+    them: it allocates them).  Below generation 3 "viterbi_minlen" takes LENS_CYCLE[0] in every call.  For any other operation `args`
+    is None and `grows` is ()."""
+    count, lanes, samples = {}, {}, {}
+    for op in ops:
+        if op not in DECODERS + MINLEN_DECODERS:
+            yield op, None, ()
+            continue
+        n = count.get(op, 0)
+        count[op] = n + 1
+        args, grows = {"ordinal": n}, []
+        if op in MINLEN_USERS:
+            args["min_len"] = LENS_CYCLE[n % len(LENS_CYCLE) if generation >= 3 else 0]
+        if op == "sample_minlen":
+            args["n_samples"] = SAMPLE_CYCLE[n % len(SAMPLE_CYCLE)]
+        if op == "viterbi_minlen_joined":
+            args["join"] = JOIN_CYCLE[n % len(JOIN_CYCLE)]
+        if op in BUFFERS:
+            if sum(args["min_len"]) > lanes.get(op, 0):
+                lanes[op] = sum(args["min_len"])
+                grows.append("fwd")
+            if "samples" in BUFFERS[op] and args["n_samples"] > samples.get(op, 0):
+                samples[op] = args["n_samples"]
+                grows.append("samples")
+        yield op, args, tuple(grows)
+
+
+def decoder_coverage(seeds=None, generation: int = 3):
+    """What the decoder calls of the sequences of `seeds` (default: the generation's) cover, from the generator alone:
+    "calls": decoder -> calls over all sequences; "after_forward": decoder -> calls while the last pass is a forward-only one;
+    "most_in_one": decoder -> the most calls within one sequence; "minlen_then_joined" / "joined_then_minlen": how often, among the
+    calls on the shared state in one sequence (other operations may lie between them), a "viterbi_minlen" is followed by a
+    "viterbi_minlen_joined" and the reverse; "grows" / "reuses": (decoder, buffer) -> calls that grow the buffer / that do not;
+    "joins": the entries of JOIN_CYCLE used."""
+    decoders = GENERATIONS[generation][1]
+    cov = dict(calls={d: 0 for d in decoders}, after_forward={d: 0 for d in decoders}, most_in_one={d: 0 for d in decoders},
+               minlen_then_joined=0, joined_then_minlen=0, grows={(d, b): 0 for d in BUFFERS for b in BUFFERS[d]},
+               reuses={(d, b): 0 for d in BUFFERS for b in BUFFERS[d]}, joins=set())
+    for seed in GENERATIONS[generation][3] if seeds is None else seeds:
+        ops = sequence(seed, generation)
+        shared = None
+        for (op, st), (_, args, grows) in zip(replay(ops), decoder_arguments(ops, generation)):
+            if args is None:
+                continue
+            cov["calls"][op] += 1
+            cov["after_forward"][op] += st["last_pass"] == "forward"
+            cov["most_in_one"][op] = max(cov["most_in_one"][op], args["ordinal"] + 1)
+            if op in SHARED_STATE:
+                if shared is not None and shared != op:
+                    cov["minlen_then_joined" if op == "viterbi_minlen_joined" else "joined_then_minlen"] += 1
+                shared = op
+            for b in BUFFERS.get(op, ()):
+                cov["grows" if b in grows else "reuses"][(op, b)] += 1
+            if "join" in args:
+                cov["joins"].add(args["join"])
     return cov

@@ -2,7 +2,13 @@
 kind runs at least twice after a full pass, at least once as the FIRST getter after a full pass (its lazy state is built then), at
 least once directly after a decoder call with other parameters, and — for the refusals — at least once after a forward-only pass.
 This holds for each generation of sequences by itself: for the ten getters of the first over its seeds, and for all thirteen getters
-over the seeds of the second alone."""
+over the seeds of the second alone, and over those of the third alone.
+
+Generation 3 adds the three decoders that carry state from call to call (hf_minlen_posterior, hf_sample_paths_minlen,
+hf_viterbi_minlen_joined), with arguments that change from call to call (stream_sequences.decoder_arguments).  For its committed seeds
+the generator alone shows: every one of the six decoders at least twice; each new decoder after a forward-only pass, and three times
+within one sequence; hf_viterbi_minlen and hf_viterbi_minlen_joined, which share their state, in both orders; for each buffer that
+grows and never shrinks a call that grows it and two that run in it narrower; three kinds of joined vector."""
 import hashlib
 import json
 
@@ -11,6 +17,8 @@ import stream_sequences as SQ
 GENS = sorted(SQ.GENERATIONS)
 # sha256 of json.dumps of the four lists of generation 1, computed at the commit before the second generation was added
 GENERATION_1_DIGEST = "6ec2eb0113304e64909753fbb9f77679807ef5142128e2cd98f557c75c994049"
+# ... of generation 2, computed at the commit before the third generation was added
+GENERATION_2_DIGEST = "cfe3109ad41025538fc2df9a07ae10a96d7d46c5efa387711191474a632d5957"
 
 
 def test_generations():
@@ -27,6 +35,88 @@ def test_the_first_generation_is_what_it_was():
     seqs = [SQ.sequence(s) for s in SQ.SEEDS]
     assert seqs == [SQ.sequence(s, 1) for s in SQ.GENERATIONS[1][3]]
     assert hashlib.sha256(json.dumps(seqs).encode()).hexdigest() == GENERATION_1_DIGEST
+
+
+def test_the_second_generation_is_what_it_was():
+    seqs = [SQ.sequence(s, 2) for s in SQ.GENERATIONS[2][3]]
+    assert hashlib.sha256(json.dumps(seqs).encode()).hexdigest() == GENERATION_2_DIGEST
+    for ops in seqs:                                       # below generation 3 the minimum-length decoder keeps its one set of lengths
+        assert all(args["min_len"] == (3, 5, 1, 7) and grows == () for op, args, grows in SQ.decoder_arguments(ops, 2) if op == "viterbi_minlen")
+
+
+def test_generation_3():
+    g3, d3, l3, s3 = SQ.GENERATIONS[3]
+    assert g3 == SQ.GETTERS and d3 == SQ.DECODERS + SQ.MINLEN_DECODERS and l3 == 64 and len(s3) == 4
+    assert SQ.MINLEN_DECODERS == ("minlen_posterior", "sample_minlen", "viterbi_minlen_joined")
+    assert not set(s3) & (set(SQ.GENERATIONS[1][3]) | set(SQ.GENERATIONS[2][3]))
+    assert SQ.LENS_CYCLE == ((3, 5, 1, 7), (16, 16, 16, 16), (1, 1, 1, 1), (61, 1, 1, 1), (2, 1, 1, 3))
+    assert [sum(m) for m in SQ.LENS_CYCLE] == [16, 64, 4, 64, 7] and all(min(m) >= 1 for m in SQ.LENS_CYCLE)
+    assert SQ.SAMPLE_CYCLE == (8, 65, 3, 64) and [-(-k // 64) * 64 for k in SQ.SAMPLE_CYCLE] == [64, 128, 64, 64]
+    assert SQ.JOIN_CYCLE == ("null", "all", "random", "zeros")
+
+
+def test_join_vectors():
+    assert SQ.join_vector("null", 10) is None
+    assert SQ.join_vector("all", 10) == [0] + [1] * 9 and SQ.join_vector("zeros", 10) == [0] * 10
+    r = SQ.join_vector("random", 10)
+    assert r == SQ.join_vector("random", 10) and len(r) == 10 and r[0] == 0 and set(r) == {0, 1}
+    assert r not in (SQ.join_vector("all", 10), SQ.join_vector("zeros", 10))
+    for kind in SQ.JOIN_CYCLE[1:]:
+        assert SQ.join_vector(kind, 1) == [0] and SQ.join_vector(kind, 0) == []
+
+
+def test_decoder_arguments():
+    ops = ["alpha_on", "pass_a"] + ["sample_minlen"] * 5 + ["labels"] + ["minlen_posterior"] * 6 + ["viterbi_minlen_joined"] * 5 + \
+        ["viterbi", "viterbi_minlen", "viterbi_minlen", "sample"]
+    out = list(SQ.decoder_arguments(ops))
+    assert [o for o, _, _ in out] == ops and out[0][1:] == (None, ()) and out[7][1:] == (None, ())
+    smp, post, join = out[2:7], out[8:14], out[14:19]
+    assert [a["ordinal"] for _, a, _ in smp] == [0, 1, 2, 3, 4]
+    assert [a["n_samples"] for _, a, _ in smp] == [8, 65, 3, 64, 8] and [a["min_len"] for _, a, _ in smp] == list(SQ.LENS_CYCLE)
+    assert [g for _, _, g in smp] == [("fwd", "samples"), ("fwd", "samples"), (), (), ()]
+    assert [a["min_len"] for _, a, _ in post] == list(SQ.LENS_CYCLE) + [SQ.LENS_CYCLE[0]] and all("n_samples" not in a and "join" not in a for _, a, _ in post)
+    assert [g for _, _, g in post] == [("fwd",), ("fwd",), (), (), (), ()]
+    assert [a["join"] for _, a, _ in join] == ["null", "all", "random", "zeros", "null"] and all(g == () for _, _, g in join)
+    assert out[19][1] == {"ordinal": 0} and out[22][1] == {"ordinal": 0}
+    assert [a["min_len"] for _, a, _ in out[20:22]] == list(SQ.LENS_CYCLE[:2])             # a count of its own per decoder
+    assert [a["min_len"] for _, a, _ in list(SQ.decoder_arguments(ops, 2))[20:22]] == [SQ.LENS_CYCLE[0]] * 2
+    # 64 lanes after 16 grow the lanes; a narrower call after a wider one does not, whatever lay between
+    ops = ["minlen_posterior", "sample_minlen", "minlen_posterior", "forward", "minlen_posterior", "sample_minlen"]
+    assert [g for _, _, g in SQ.decoder_arguments(ops)] == [("fwd",), ("fwd", "samples"), ("fwd",), (), (), ("fwd", "samples")]
+
+
+def test_generation_3_covers_the_decoders():
+    cov = SQ.decoder_coverage()
+    assert cov == SQ.decoder_coverage(SQ.GENERATIONS[3][3], 3)
+    assert sorted(cov["calls"]) == sorted(SQ.DECODERS + SQ.MINLEN_DECODERS) and len(cov["calls"]) == 6
+    for d, n in cov["calls"].items():
+        assert n >= 2, (d, n)
+    for d in SQ.MINLEN_DECODERS:
+        assert cov["after_forward"][d] >= 1, d
+        assert cov["most_in_one"][d] >= 3, d               # one grow and one narrower reuse on a single context
+    assert cov["minlen_then_joined"] >= 1 and cov["joined_then_minlen"] >= 1
+    assert sorted(cov["grows"]) == [("minlen_posterior", "fwd"), ("sample_minlen", "fwd"), ("sample_minlen", "samples")]
+    for buf in cov["grows"]:
+        assert cov["grows"][buf] >= 1 and cov["reuses"][buf] >= 2, (buf, cov["grows"][buf], cov["reuses"][buf])
+    assert len(cov["joins"]) >= 3 and cov["joins"] <= set(SQ.JOIN_CYCLE)
+    # within one sequence: a call that grows the buffer, later one with fewer lanes (samples) in the buffer the wider call left
+    for d, b in cov["grows"]:
+        key = (lambda a: sum(a["min_len"])) if b == "fwd" else (lambda a: a["n_samples"])
+        found = False
+        for seed in SQ.GENERATIONS[3][3]:
+            sizes = [(key(a), b in g) for op, a, g in SQ.decoder_arguments(SQ.sequence(seed, 3)) if op == d]
+            found |= any(grew and i > 0 and any(n < size for n, _ in sizes[i + 1:]) for i, (size, grew) in enumerate(sizes))
+        assert found, (d, b)
+
+
+def test_decoder_coverage_counts():
+    """decoder_coverage on generation 2, whose sequences hold no call it could miscount: no new decoder, no shared state in two orders."""
+    cov = SQ.decoder_coverage(generation=2)
+    assert sorted(cov["calls"]) == sorted(SQ.DECODERS) and all(n >= 1 for n in cov["calls"].values())
+    assert cov["minlen_then_joined"] == 0 == cov["joined_then_minlen"] and cov["joins"] == set()
+    assert all(n == 0 for n in list(cov["grows"].values()) + list(cov["reuses"].values()))
+    n = sum(op == "viterbi_minlen" for s in SQ.GENERATIONS[2][3] for op in SQ.sequence(s, 2))
+    assert cov["calls"]["viterbi_minlen"] == n
 
 
 def test_sequences_are_reproducible_and_of_the_stated_length():
@@ -80,3 +170,13 @@ def test_replay_bookkeeping():
         if op in SQ.GETTERS and s["prev"] in SQ.DECODERS:
             cov[op] += 1
     assert cov["long_run_log_probs"] == 1 and cov["breakpoint_profile"] == 1 and cov["breakpoints"] == 0
+    # the decoders of generation 3: no pass, no getter, whatever their arguments
+    ops = ["alpha_off", "pass_a", "minlen_posterior", "posterior", "sample_minlen", "viterbi_minlen_joined", "forward", "sample_minlen",
+           "labels", "viterbi_minlen_joined", "alpha_on", "pass_b", "viterbi_minlen", "alpha_stats"]
+    st = [s for _, s in SQ.replay(ops)]
+    assert st[3]["prev"] == "minlen_posterior" and st[3]["last_pass"] == "pass_a" and not st[3]["getter_since_pass"]
+    assert st[5]["prev"] == "sample_minlen" and st[5]["getter_since_pass"] and st[6]["prev"] == "viterbi_minlen_joined"
+    assert st[7]["last_pass"] == "forward" and st[8]["prev"] == "sample_minlen" and not st[8]["getter_since_pass"]
+    assert st[9]["last_pass"] == "forward" and st[9]["getter_since_pass"]
+    assert st[13]["prev"] == "viterbi_minlen" and st[13]["alpha_answers"] and not st[13]["getter_since_pass"]
+    assert [op for op, s in SQ.replay(ops) if s["last_pass"] == "forward" and op in SQ.MINLEN_DECODERS] == ["sample_minlen", "viterbi_minlen_joined"]

@@ -1,5 +1,6 @@
 """The C ABI on caller-owned streams and in mixed call orders (DESIGN.md "Streams"): the pass, the thirteen getters (the breakpoint and
-long-run getters among them), hf_viterbi, hf_sample_paths, hf_viterbi_minlen and the batch.
+long-run getters among them), the six decoders (hf_viterbi, hf_sample_paths, hf_viterbi_minlen, hf_minlen_posterior,
+hf_sample_paths_minlen, hf_viterbi_minlen_joined) and the batch.
 
 Every entry point that enqueues GPU work takes a `void *stream`; the getters run on the stream of the last pass.  Here the stream is a
 non-blocking one of the caller's (tests/hip_streams.py), and directly in front of every library call the caller enqueues filler work on
@@ -8,7 +9,17 @@ stream's work and sees stale data.  Right after an entry point that is asynchron
 say hipErrorNotReady: the filler was long enough to matter.
 
 Every comparison is BITWISE (np.array_equal, equal return codes) against a twin that makes the same calls on stream 0 without filler:
-the library promises bitwise reproducibility, so there is no tolerance."""
+the library promises bitwise reproducibility, so there is no tolerance.
+
+The three newest decoders carry state from call to call: hf_viterbi_minlen_joined shares hf_viterbi_minlen's decoder state (backpointer
+words, final lanes, chunk scores indexed per chunk by one and per group by the other), and the forward lanes of hf_minlen_posterior and
+hf_sample_paths_minlen and the sampler's per-sample slab are sized by a call's arguments, grow and never shrink.  The sequences of
+generation 3 (tests/stream_sequences.py) therefore change the arguments from call to call (lanes 16, 64, 4, 64, 7; samples 8, 65, 3,
+64; four kinds of joined vector), and because stale state would be equally wrong on the twin, every decoder call of such a sequence
+is also compared, bitwise, with the same call on a FRESH context that has run nothing else.  test_generation_3_arguments_equal_the_references
+ties those fresh-context results to the float64 numpy references of the features' own tests.  A call that grows a buffer frees the
+old one, and hipFree waits for the device: there the busy-stream check only records what it finds (printed; pytest -s)."""
+import collections
 import ctypes as C
 import functools
 import json
@@ -23,7 +34,16 @@ import pytest
 from flagger_amd import _native as N
 from flagger_amd import hmm, synth
 import hip_streams as HS
+import minlen_joined_ref
+import minlen_post_ref
+import minlen_ref
+import minlen_sample_ref
 import stream_sequences as SQ
+import test_minlen_gpu as TML
+import test_minlen_joined_gpu as TMJ
+import test_minlen_post_gpu as TMP
+import test_minlen_sample_gpu as TMS
+import viterbi_ref
 from test_posterior_gpu import _ranges, _regions_store, _sizes_store
 
 pytestmark = pytest.mark.gpu
@@ -215,6 +235,8 @@ class Side:
         self.h = HS.hip()
         self.contexts = []
         self.busy_checked = 0
+        self.busy = collections.Counter()      # (entry point, "asserted" | "grow, busy" | "grow, idle") -> calls (the three newest decoders)
+        self.last_samples = {}                 # context -> the samples of its last hf_sample_paths_minlen
 
     @property
     def stream(self):
@@ -228,6 +250,18 @@ class Side:
         if s and self.non_blocking:            # (a null-stream operation inside the call waits for a blocking stream: no hazard, and no claim)
             assert self.h.stream_query(s) == HS.hipErrorNotReady, "%s returned with its stream idle: the filler is too short, or the call blocked" % what
             self.busy_checked += 1
+
+    def check_busy(self, s, what, grows=()):
+        """assert_busy for a call of `what` that grows none of its buffers.  A call that grows one (`grows`: the buffers, as
+        stream_sequences.decoder_arguments names them) frees the old one, and hipFree waits for the device by design: no claim there,
+        only the record of whether the stream was still busy."""
+        if not (s and self.non_blocking):
+            return
+        if not grows:
+            self.assert_busy(s, what)
+            self.busy[what, "asserted"] += 1
+        else:
+            self.busy[what, "grow, busy" if self.h.stream_query(s) == HS.hipErrorNotReady else "grow, idle"] += 1
 
     def context(self, stream=None, model=None, alpha_stats=False):
         algo, mode, env = KINDS[self.kind]
@@ -326,14 +360,122 @@ class Side:
         assert r1 == N.HF_OK and r2 == N.HF_OK
         return N.HF_OK, (labels, ll, np.float64(lp.value))
 
-    def decoder(self, em, which, model, s=None):
-        return {"viterbi": self.viterbi, "sample": self.sample, "viterbi_minlen": self.viterbi_minlen}[which](em, model, s)
+    def viterbi_minlen_joined(self, em, model, s=None, min_len=MIN_LEN, join="null"):
+        """hf_viterbi_minlen_joined + hf_viterbi_minlen_finish on stream `s` with the joined vector stream_sequences.join_vector(join)
+        and the getters it shares with hf_viterbi_minlen: (code, (labels, chunk scores, score)).  Asynchronous "as hf_viterbi_minlen
+        is": the stream is still busy when it returns, in every call."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        p, lp = model.params(), C.c_double(0.0)
+        ml = (C.c_int32 * 4)(*min_len)
+        jv = SQ.join_vector(join, self.store.n_chunks)
+        ja = None if jv is None else np.asarray(jv, np.uint8)
+        self.delay(s)
+        rc = L.hf_viterbi_minlen_joined(em._h, C.byref(p), ml, None if ja is None else ja.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.check_busy(s, "hf_viterbi_minlen_joined")
+        rc = L.hf_viterbi_minlen_finish(em._h, C.byref(lp), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        ll = np.empty(self.store.n_chunks, dtype=np.float64)
+        self.delay(s)
+        r1 = L.hf_get_viterbi_minlen_labels(em._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
+        r2 = L.hf_get_viterbi_minlen_chunk_log_probs(em._h, ll.ctypes.data_as(C.POINTER(C.c_double)))
+        assert r1 == N.HF_OK and r2 == N.HF_OK
+        return N.HF_OK, (labels, ll, np.float64(lp.value))
+
+    def _minlen_posterior_results(self, em):
+        """(code, (posterior over every window in a chunk, labels, chunk log mass, chunk log Z_adm)) of the getters."""
+        L, n, pd = N.lib(), self.store.n_windows, C.POINTER(C.c_double)
+        assert self.J.n == n                                   # (every window of these stores lies in a chunk)
+        post = np.empty((n, 4), dtype=np.float64)
+        labels = np.empty(n, dtype=np.int8)
+        mass, lza = np.empty(self.store.n_chunks, dtype=np.float64), np.empty(self.store.n_chunks, dtype=np.float64)
+        for rc in (L.hf_get_minlen_posterior(em._h, 0, n, post.ctypes.data_as(pd)),
+                   L.hf_get_minlen_posterior_labels(em._h, labels.ctypes.data_as(C.POINTER(C.c_int8))),
+                   L.hf_get_minlen_chunk_log_mass(em._h, mass.ctypes.data_as(pd), lza.ctypes.data_as(pd))):
+            if rc != N.HF_OK:
+                return int(rc), ()
+        return N.HF_OK, (post, labels, mass, lza)
+
+    def minlen_posterior(self, em, model, s=None, min_len=MIN_LEN, grows=()):
+        """hf_minlen_posterior + hf_minlen_posterior_finish on stream `s` and its getters: (code, (posterior, labels, chunk log mass,
+        chunk log Z_adm, total)).  `grows`: the buffers the call grows (check_busy)."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        p, tot = model.params(), C.c_double(0.0)
+        ml = (C.c_int32 * 4)(*min_len)
+        self.delay(s)
+        rc = L.hf_minlen_posterior(em._h, C.byref(p), ml, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.check_busy(s, "hf_minlen_posterior", grows)
+        rc = L.hf_minlen_posterior_finish(em._h, C.byref(tot), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.delay(s)
+        code, arrays = self._minlen_posterior_results(em)
+        assert code == N.HF_OK
+        return N.HF_OK, arrays + (np.float64(tot.value),)
+
+    def _minlen_samples(self, em, n):
+        """(code, (int8[n][n_windows],)) of hf_get_minlen_sample_labels; the sample behind the last one is refused."""
+        L = N.lib()
+        out = np.empty((n, self.store.n_windows), dtype=np.int8)
+        for k in range(n):
+            rc = L.hf_get_minlen_sample_labels(em._h, k, out[k].ctypes.data_as(C.POINTER(C.c_int8)))
+            if rc != N.HF_OK:
+                return int(rc), ()
+        spare = np.empty(self.store.n_windows, dtype=np.int8)
+        assert L.hf_get_minlen_sample_labels(em._h, n, spare.ctypes.data_as(C.POINTER(C.c_int8))) == N.HF_E_ARG
+        return N.HF_OK, (out,)
+
+    def sample_minlen(self, em, model, s=None, min_len=MIN_LEN, n=SAMPLES, seed=SAMPLE_SEED, grows=()):
+        """hf_sample_paths_minlen + hf_sample_minlen_finish on stream `s` and the samples' labels: (code, (int8[n][n_windows],)).
+        `grows`: the buffers the call grows (check_busy)."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        assert em.minlen_sample_capacity(min_len) >= n
+        p = model.params()
+        ml = (C.c_int32 * 4)(*min_len)
+        self.delay(s)
+        rc = L.hf_sample_paths_minlen(em._h, C.byref(p), ml, 0, n, seed, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.check_busy(s, "hf_sample_paths_minlen", grows)
+        rc = L.hf_sample_minlen_finish(em._h, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.last_samples[id(em)] = n
+        self.delay(s)
+        code, arrays = self._minlen_samples(em, n)
+        assert code == N.HF_OK
+        return N.HF_OK, arrays
+
+    def decoder(self, em, which, model, s=None, args=None, grows=()):
+        """Decoder `which` with the arguments stream_sequences.decoder_arguments gives for the call (default: MIN_LEN, SAMPLES, no join)."""
+        args = args or {}
+        kw = {"min_len": args["min_len"]} if "min_len" in args else {}
+        if which == "minlen_posterior":
+            return self.minlen_posterior(em, model, s, grows=grows, **kw)
+        if which == "sample_minlen":
+            return self.sample_minlen(em, model, s, n=args.get("n_samples", SAMPLES), grows=grows, **kw)
+        if which == "viterbi_minlen_joined":
+            return self.viterbi_minlen_joined(em, model, s, join=args.get("join", "null"), **kw)
+        if which == "viterbi_minlen":
+            return self.viterbi_minlen(em, model, s, **kw)
+        return {"viterbi": self.viterbi, "sample": self.sample}[which](em, model, s)
 
     def stored(self, em, which, s=None):
         """What the getters of decoder `which` answer now, behind a delay: (code, arrays) with the arrays in the order of the decoder's
-        own record (its score, a value of the finish call, is not stored)."""
+        own record (its score, a value of the finish call, is not stored).  "viterbi_minlen" and "viterbi_minlen_joined" share their
+        state and their getters: either name reads the results of the later of the two calls.  "sample_minlen": as many samples as
+        that decoder's last call on `em` drew."""
         L = N.lib()
         self.delay((em.stream.value or 0) if s is None else s)
+        if which == "minlen_posterior":
+            return self._minlen_posterior_results(em)
+        if which == "sample_minlen":
+            return self._minlen_samples(em, self.last_samples[id(em)])
         if which == "sample":
             out = np.empty((SAMPLES, self.store.n_windows), dtype=np.int8)
             for k in range(SAMPLES):
@@ -544,11 +686,136 @@ def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
             _equal(rec[g + " after the decoders again"], rec[g + " alone"], g)
 
 
+SIX = SQ.DECODERS + SQ.MINLEN_DECODERS
+FAMILY_ARGS = {"min_len": MIN_LEN, "n_samples": SAMPLES, "join": "random"}
+FAMILY = [pytest.param(n, k, id="%s-%s" % (n, k)) for n in ("config2", "sizes") for k in ("seq", "scan-rows")]
+
+
+@pytest.mark.parametrize("where", ["same-stream", "second-stream"])
+@pytest.mark.parametrize("name,kind", FAMILY)
+def test_minlen_family_with_other_parameters(name, kind, where, monkeypatch):
+    """All six decoders with parameters other than the pass's, on the pass's stream or on a second non-blocking stream, twice: the two
+    runs are equal (the second grows no buffer: the stream is still busy when each of the new entry points returns), afterwards every
+    getter still answers for the pass, and each decoder's stored results are its own last ones.  hf_viterbi_minlen and
+    hf_viterbi_minlen_joined share their state: the stored results are those of the later of the two, in every chunk entry (the exact
+    zeros a joined call leaves in a group's other chunks included), and nothing of the earlier one's — in either order."""
+    def scenario(side):
+        ma, mb = _model(name, "a"), _model(name, "b")
+        s2 = side.streams[1] if where == "second-stream" else None
+        em = side.context(alpha_stats=True)
+        rec = {"pass b": [side.estep(em, mb)]}
+        for d in SIX:
+            rec[d + " a"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS, SQ.BUFFERS.get(d, ()))]       # (a first call grows every buffer)
+        for g in _getters_of(side):
+            rec[g + " after the decoders"] = side.getter(em, g)
+        for d in SIX:
+            rec[d + " a again"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS)]
+        for g in _getters_of(side):
+            rec[g + " after the decoders again"] = side.getter(em, g)
+        for d in SIX:                                             # "viterbi_minlen": the shared state, the joined call the later one
+            rec[d + " stored"] = [side.stored(em, d, s2)]
+        rec["viterbi_minlen a, after the joined call"] = [side.viterbi_minlen(em, ma, s2)]
+        rec["viterbi_minlen stored, after the joined call"] = [side.stored(em, "viterbi_minlen", s2)]
+        alone = side.context(alpha_stats=True)
+        rec["alone pass b"] = [side.estep(alone, mb)]
+        for g in _getters_of(side):
+            rec[g + " alone"] = side.getter(alone, g)
+        if side.stream:
+            print("%s %s %s: busy-stream checks in the family: %s" % (name, kind, where, _busy_counts(side.busy)))
+        return rec
+
+    rec = _run_both(name, kind, monkeypatch, scenario, n_streams=2)
+    store = _input(name)[0]
+    assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls)), {t: _codes(c) for t, c in rec.items()}
+    for d in SIX:
+        _equal(rec[d + " a"], rec[d + " a again"], d)
+    for d in ("viterbi", "sample", "minlen_posterior", "sample_minlen", "viterbi_minlen_joined"):
+        _stored_equals(rec[d + " stored"][0], rec[d + " a again"][0], d + " stored")
+    # the shared state: the joined call was the later one; then hf_viterbi_minlen is
+    joined, minlen = rec["viterbi_minlen_joined a again"][0], rec["viterbi_minlen a again"][0]
+    assert sum(SQ.join_vector("random", store.n_chunks)) >= 1
+    assert not np.array_equal(joined[1][1], minlen[1][1])                                          # (the two differ, so a mix would show)
+    _stored_equals(rec["viterbi_minlen stored"][0], joined, "the shared state after the joined call")
+    _check_chunk_entries(store, rec["viterbi_minlen stored"][0][1][1], "viterbi_minlen_joined", FAMILY_ARGS)
+    _equal(rec["viterbi_minlen a, after the joined call"], rec["viterbi_minlen a again"], "hf_viterbi_minlen after a joined call")
+    _stored_equals(rec["viterbi_minlen stored, after the joined call"][0], minlen, "the shared state after hf_viterbi_minlen")
+    _check_chunk_entries(store, rec["viterbi_minlen stored, after the joined call"][0][1][1], "viterbi_minlen", FAMILY_ARGS)
+    assert not np.array_equal(rec["viterbi_minlen a"][0][1][0], rec["viterbi a"][0][1][0])         # the constraint bites
+    for g in GETTERS:
+        if g + " alone" in rec:
+            _equal(rec[g + " after the decoders"], rec[g + " alone"], g)
+            _equal(rec[g + " after the decoders again"], rec[g + " alone"], g)
+
+
+# ---- c2. the arguments of generation 3 against the float64 references ------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _reference(decoder, which, min_len, n_samples, join):
+    """The numpy reference of one decoder call on input "sizes" with model `which`, computed once."""
+    store, _, _, alpha = _input("sizes")[:4]
+    model = _model("sizes", which)
+    if decoder == "viterbi_minlen":
+        return minlen_ref.reference(store, model, alpha, min_len)
+    if decoder == "viterbi_minlen_joined":
+        return viterbi_ref.tables(store, model, alpha)           # (the feature's checker computes the reference from the tables)
+    if decoder == "minlen_posterior":
+        return minlen_post_ref.reference(store, model, alpha, min_len)
+    assert decoder == "sample_minlen"
+    return minlen_sample_ref.reference(store, model, alpha, min_len, SAMPLE_SEED, range(n_samples))
+
+
+def _cycle_arguments(decoder, ordinal):
+    """What stream_sequences.decoder_arguments gives the call number `ordinal` of `decoder`."""
+    return list(SQ.decoder_arguments([decoder] * (ordinal + 1)))[-1][1]
+
+
+ANCHORS = [pytest.param(d, n, id="%s-%d" % (d, n)) for d in SQ.MINLEN_USERS for n in range(len(SQ.LENS_CYCLE))]
+
+
+@pytest.mark.parametrize("decoder,ordinal", ANCHORS)
+def test_generation_3_arguments_equal_the_references(decoder, ordinal):
+    """Input "sizes", both models, a fresh context per call on a caller's busy stream: the arguments of the first five calls of a decoder
+    in a generation-3 sequence (every entry of LENS_CYCLE and SAMPLE_CYCLE, every kind of join; no sequence of the committed seeds holds
+    more than four calls of one decoder) against the float64 numpy references of the features' own device tests, with their checkers and
+    tolerances (the sampler's near ties as tests/test_minlen_sample_gpu.py handles them).  test_mixed_orders compares every decoder
+    call of a sequence bitwise with such a fresh context, so this ties the mixed-order results to the references.  The whole store is
+    anchored: one reference on its 18 828 windows takes 1 to 3 s."""
+    import time
+    args = _cycle_arguments(decoder, ordinal)
+    min_len = args["min_len"]
+    store = _input("sizes")[0]
+    with HS.Streams() as streams:
+        side = Side("sizes", "scan-rows", [streams.new(True)])
+        try:
+            for which in "ab":
+                t0 = time.perf_counter()
+                ref = _reference(decoder, which, min_len, args.get("n_samples"), args.get("join"))
+                t1 = time.perf_counter()
+                em = side.context()
+                code, got = side.decoder(em, decoder, _model("sizes", which), None, args, SQ.BUFFERS.get(decoder, ()))
+                em.close()
+                print("%s %s model %s: reference %.2f s, device call with its getters %.2f s" % (decoder, args, which, t1 - t0, time.perf_counter() - t1))
+                assert code == N.HF_OK, (decoder, args, which, code)          # (the "all" join among them: no HF_E_SCALE on this input)
+                if decoder == "viterbi_minlen":
+                    TML._check(store, ref, min_len, (got[0], got[1], float(got[2])))
+                elif decoder == "viterbi_minlen_joined":
+                    TMJ._check(store.chunk_off, ref, SQ.join_vector(args["join"], store.n_chunks), min_len, (got[0], got[1], float(got[2])))
+                elif decoder == "minlen_posterior":
+                    TMP._check(store, ref, (got[0], got[1], got[2], got[3], float(got[4])), "%s model %s" % (min_len, which))
+                else:
+                    TMS._check(store, ref, got[0], min_len)
+            print("%s %d: busy-stream checks on the anchors' fresh contexts: %s" % (decoder, ordinal, _busy_counts(side.busy)))
+        finally:
+            side.close()
+
+
 # ---- d. mixed orders ----------------------------------------------------------------------------------------------------------------
 def _mixed_scenario(side, seed, generation=1):
     """One sequence of tests/stream_sequences.py on a context; after every getter, the same getter on a FRESH context that ran only the last
     pass (with the switches as they stood then, and as they stand now for the getter).  At the end every decoder's stored results are
-    read again: they are what that decoder returned at its last call in the sequence."""
+    read again: they are what that decoder returned at its last call in the sequence (hf_viterbi_minlen and hf_viterbi_minlen_joined
+    share their state: what the later of the two returned).  In generation 3 the decoders' arguments change from call to call
+    (stream_sequences.decoder_arguments), and after every decoder call the same call runs on a fresh context that has run nothing
+    else: bitwise the same results and codes, whatever the context's buffers held from wider calls or the other entry point."""
     name = side.name
     scan = KINDS[side.kind][0] == N.HF_ALGO_SCAN
     base_mode = KINDS[side.kind][1]
@@ -584,8 +851,22 @@ def _mixed_scenario(side, seed, generation=1):
             f.close()
         return fresh_cache[key]
 
+    def fresh_decoder(op, which, args):
+        """The same decoder call on a context that has run nothing else: no pass, no other decoder, no earlier call of this one."""
+        key = (op, which, args.get("min_len"), args.get("n_samples"), args.get("join"))
+        if key not in fresh_decoders:
+            f = side.context()
+            before = collections.Counter(side.busy)
+            fresh_decoders[key] = side.decoder(f, op, models[which], None, args, SQ.BUFFERS.get(op, ()))      # (a first call grows every buffer)
+            fresh_busy.update(side.busy - before)             # (counted apart from the sequence's own calls)
+            side.busy = before
+            f.close()
+        return fresh_decoders[key]
+
+    fresh_decoders, compared, fresh_busy = {}, collections.Counter(), collections.Counter()
+    ops = SQ.sequence(seed, generation)
     fwd_model = "pass_a"
-    for i, (op, st) in enumerate(SQ.replay(SQ.sequence(seed, generation))):
+    for i, ((op, st), (_, args, grows)) in enumerate(zip(SQ.replay(ops), SQ.decoder_arguments(ops, generation))):
         tag = "%02d %s" % (i, op)
         if op in ("pass_a", "pass_b"):
             rec[tag] = [run_pass(em, op, None)]
@@ -599,10 +880,14 @@ def _mixed_scenario(side, seed, generation=1):
                 em.set_stats_mode(base_mode if st["flipped"] else other_mode)
         elif op in ("alpha_on", "alpha_off"):
             rec[tag] = [_call(em.set_alpha_stats, op == "alpha_on")]
-        elif op in SQ.DECODERS:
-            other = models["pass_b" if last_model == "pass_a" else "pass_a"]                     # parameters other than the last pass's
-            rec[tag] = [side.decoder(em, op, other)]
-            last_decoded[op] = tag
+        elif op in SQ.DECODERS + SQ.MINLEN_DECODERS:
+            which = "pass_b" if last_model == "pass_a" else "pass_a"                             # parameters other than the last pass's
+            rec[tag] = [side.decoder(em, op, models[which], None, args, grows)]
+            last_decoded["viterbi_minlen" if op in SQ.SHARED_STATE else op] = (tag, op, args)    # one record for the shared state: the later call
+            if generation >= 3 and side.stream:                                                   # (once: the twin equals this side)
+                _equal(rec[tag], [fresh_decoder(op, which, args)], "%s %s against a fresh context" % (tag, args))
+                assert _codes(rec[tag]) == [N.HF_OK], (tag, args, _codes(rec[tag]))
+                compared[op] += 1
         else:
             got = side.getter(em, op)
             rec[tag] = got
@@ -616,10 +901,34 @@ def _mixed_scenario(side, seed, generation=1):
                 assert _codes(got) == [N.HF_OK], (tag, _codes(got))
             else:
                 assert _codes(got) == [N.HF_E_ARG], (tag, _codes(got))
-    for op, tag in last_decoded.items():
-        rec["stored " + op] = [side.stored(em, op)]
-        _stored_equals(rec["stored " + op][0], rec[tag][0], "the stored results of %s at the end" % tag)
+    for key, (tag, op, args) in last_decoded.items():
+        rec["stored " + key] = [side.stored(em, key)]
+        _stored_equals(rec["stored " + key][0], rec[tag][0], "the stored results of %s at the end" % tag)
+        if key == "viterbi_minlen":                          # the shared state answers to both getters' contracts, for the later call
+            _check_chunk_entries(side.store, rec["stored " + key][0][1][1], op, args)
+    if generation >= 3 and side.stream:
+        calls = collections.Counter(op for op in ops if op in SQ.DECODERS + SQ.MINLEN_DECODERS)
+        assert compared == calls, (compared, calls)
+        print("%s %s seed %d: decoder calls compared with a fresh context: %s; %d fresh contexts" % (name, side.kind, seed, dict(compared), len(fresh_decoders)))
+        print("%s %s seed %d: busy-stream checks in the sequence: %s" % (name, side.kind, seed, _busy_counts(side.busy)))
+        print("%s %s seed %d: busy-stream checks on the fresh contexts: %s" % (name, side.kind, seed, _busy_counts(fresh_busy)))
     return rec
+
+
+def _busy_counts(counter):
+    """Side.busy for printing: {"entry point, asserted | grow, busy | grow, idle": calls}."""
+    return {"%s, %s" % k: v for k, v in sorted(counter.items())}
+
+
+def _check_chunk_entries(store, chunk_ll, op, args):
+    """The chunk scores the shared minimum-length state holds after a call of `op`: hf_viterbi_minlen leaves a score (a log-probability,
+    never 0.0) in the entry of every chunk with windows; hf_viterbi_minlen_joined leaves one in the entry of every group's first chunk
+    and exactly 0.0 in the entries of the group's other chunks."""
+    T = np.diff(np.asarray(store.chunk_off, np.int64))
+    first = np.zeros(T.size, bool)
+    first[minlen_joined_ref.group_first_chunks(store.chunk_off, SQ.join_vector(args["join"], T.size) if op == "viterbi_minlen_joined" else None)] = True
+    assert np.all(chunk_ll[~first] == 0.0) and not np.signbit(chunk_ll[~first]).any(), (op, args)
+    assert np.all(chunk_ll[first & (T > 0)] != 0.0), (op, args)
 
 
 def _mixed_cases(generation, tag):
@@ -629,8 +938,9 @@ def _mixed_cases(generation, tag):
          for i, (n, k) in enumerate((n, k) for n in ("sizes", "regions", "negative_binomial") for k in ("seq", "scan-rows", "scan-chunks-3-sub-passes"))]
 
 
-# generation 1: the ten getters and two decoders its seeds were chosen with; generation 2: all thirteen getters and three decoders
-MIXED = _mixed_cases(1, "") + _mixed_cases(2, "gen2-")
+# generation 1: the ten getters and two decoders its seeds were chosen with; generation 2: all thirteen getters and three decoders;
+# generation 3: the thirteen getters and all six decoders, the decoders' arguments changing from call to call
+MIXED = _mixed_cases(1, "") + _mixed_cases(2, "gen2-") + _mixed_cases(3, "gen3-")
 
 
 @pytest.mark.parametrize("name,kind,generation,seed", MIXED)
