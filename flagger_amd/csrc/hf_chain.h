@@ -1,6 +1,7 @@
 // hf_chain.h — the core of the walkers of a chain expanded by run length, one lane of a 64-lane wavefront per expanded state:
-// hf_viterbi_minlen (hf_minlen.h; over whole contigs: hf_minlen_joined.h), hf_get_long_run_log_probs (hf_longrun.h) and hf_minlen_posterior (hf_minlen_post.h).  Three things,
-// each here once: the wave primitives, the lane geometry of the minimum-run-length expansion, the forward row staging (its tile and rules).
+// hf_viterbi_minlen and, over whole contigs, hf_viterbi_minlen_joined (hf_minlen.h), hf_get_long_run_log_probs (hf_longrun.h) and
+// hf_minlen_posterior (hf_minlen_post.h).  Three things, each here once: the wave primitives, the lane geometry of the minimum-run-length
+// expansion, the forward row staging (its tile and rules).
 //
 // THE EXPANSION by minimum run lengths.  min_len[s] >= 1 windows per state, sum <= 64.  Lanes (s, d), d = 1 .. min_len[s]: "in state s,
 // the current run has d windows so far"; at d = min_len[s] "at least that many" (the SATURATED lane; d = 1 is the ENTRY lane; with
@@ -110,6 +111,17 @@ __device__ __forceinline__ int ch_len(unsigned mpack, int s) { return (int) ((mp
     __attribute__((unused)) const bool is_entry = active && d == 1, is_sat = active && d == m && m > 1; \
     const bool excl = m > 1; \
     const int diag = active ? 5 * s : 16
+
+// One step of a walk back through the backpointer words of hf_minlen.h: from (cs, cd) at a window to its predecessor's, by the window's
+// word w.  An entry lane goes to the saturated lane of its predecessor; any other one lane down, unless the saturated lane stayed.
+template <class W>
+__device__ __forceinline__ void ch_step_back(unsigned mpack, W w, int& cs, int& cd) {
+    const int p = (int) (w >> (2 * cs)) & 3, stayed = (int) (w >> (8 + cs)) & 1;
+    const bool entry = cd == 1;
+    const int down = (cd < ch_len(mpack, cs)) | (stayed ^ 1);
+    cd = entry ? ch_len(mpack, p) : cd - down;
+    cs = entry ? p : cs;
+}
 
 // ---- forward row staging: the tile (the turn of it is written out in the three forward kernels, see above) -------------------------
 typedef double ChainTile[65][17];

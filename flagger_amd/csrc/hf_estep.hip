@@ -440,22 +440,27 @@ struct Viterbi : LabelDecoder {
 // minimum-run-length Viterbi (hf_minlen.h): rows always in window order, one 16-bit backpointer word per window; the chunk values: the scores
 struct MinLenViterbi : LabelDecoder {
     uint16_t* d_bp = nullptr; uint8_t* d_final = nullptr;     // ... and the final lane of every chunk
-    // hf_viterbi_minlen_joined (hf_minlen_joined.h): the groups of a call, window ranges [G + 1] and first chunks [G], G <= C
+    // hf_viterbi_minlen_joined: the groups of a call, window ranges [G + 1] and first chunks [G], G <= C
     int64_t* d_goff = nullptr; int32_t* d_gchunk = nullptr;
     std::vector<int64_t> h_goff; std::vector<int32_t> h_gchunk;
 };
 
-// posterior path sampling (hf_sample.h).  The per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more.
-struct Sampler : Decoder {
+// THE PER-SAMPLE PART of the two samplers: `cap` samples in a slab of its own, replaced when a call asks for more (smp_grow); a sampler
+// adds its own per-sample arrays, taken from the same slab
+struct SampleSet {
     Slab samples;
     int cap = 0;
     uint64_t* d_keys = nullptr;                // [cap] key_k
-    uint8_t* d_maps = nullptr;                 // [cap][n_slots] (SCAN, slot order) / [cap][N] (SEQ, window order) map bytes
-    int8_t* d_final = nullptr;                 // [cap][C] final states (SCAN)
-    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: [cap][nseg][64], [cap][nseg], [cap][nseg]
     int8_t* d_label = nullptr;                 // [cap][N], the layout of hf_labels_dev per sample
     std::vector<uint64_t> h_keys;
     int n = 0;                                 // samples of the last call (the getters answer for it once it is finished)
+};
+
+// posterior path sampling (hf_sample.h)
+struct Sampler : Decoder, SampleSet {
+    uint8_t* d_maps = nullptr;                 // [cap][n_slots] (SCAN, slot order) / [cap][N] (SEQ, window order) map bytes
+    int8_t* d_final = nullptr;                 // [cap][C] final states (SCAN)
+    uint8_t* d_lmap = nullptr; uint8_t* d_smap = nullptr; uint8_t* d_sexit = nullptr;   // SCAN: [cap][nseg][64], [cap][nseg], [cap][nseg]
     void release() { samples.release(); Decoder::release(); }
 };
 
@@ -482,19 +487,12 @@ struct MinLenPosterior : LabelDecoder {
 };
 
 // admissible path sampling (hf_minlen_sample.h): rows in window order, forward lanes of its own (as MinLenPosterior::fwd), log Z_adm per
-// chunk; the per-sample part holds `cap` samples in a slab of its own, replaced when a call asks for more (as Sampler::samples)
-struct MinLenSampler : Decoder {
+// chunk, its per-sample arrays behind SampleSet's
+struct MinLenSampler : Decoder, SampleSet {
     DevBuf fwd;
     double* d_chunk = nullptr;                 // [C] log Z_adm (k_mlp_fwd writes it; nothing returns it)
-    Slab samples;
-    int cap = 0;
-    size_t samples_bytes = 0;                  // what `samples` holds
-    uint64_t* d_keys = nullptr;                // [cap] key_k
     uint16_t* d_words = nullptr;               // [N][Kp] words of k_mlv_fwd's format, Kp = a call's samples padded to HF_MLS_GROUP
     uint8_t* d_final = nullptr;                // [C][Kp] final lanes
-    int8_t* d_label = nullptr;                 // [cap][N]
-    std::vector<uint64_t> h_keys;
-    int n = 0;                                 // samples of the last call
     void release() { fwd.release(); samples.release(); Decoder::release(); }
 };
 
@@ -2272,7 +2270,43 @@ int hf_sample_capacity(const hf_ctx* ctx) {
     return cap > HF_SMP_MAX_PER_CALL ? HF_SMP_MAX_PER_CALL : (int) cap;
 }
 
-// the sampler's buffers for n samples (the per-sample slab replaced when it holds fewer) and the keys of samples first .. first + n - 1
+// ---- the per-sample part of a sampler (SampleSet) ----
+// room for n samples: the slab replaced by one of exactly `arrays` (the sampler's per-sample arrays at n samples) when it holds fewer
+template <class A> static int smp_grow(SampleSet& s, int n, A&& arrays) {
+    if (n <= s.cap) return HF_OK;
+    s.samples.release();
+    s.cap = 0;
+    const int rc = dec_take(s.samples, arrays);
+    if (rc) return rc;
+    s.cap = n;
+    return HF_OK;
+}
+
+// the keys of samples first .. first + n - 1 (synchronous)
+static int smp_keys(SampleSet& s, int64_t first, int n, uint64_t seed) {
+    s.h_keys.resize((size_t) n);
+    for (int k = 0; k < n; k++) s.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first + k));
+    HIPCHK(hipMemcpy(s.d_keys, s.h_keys.data(), (size_t) n * 8, hipMemcpyHostToDevice));
+    return HF_OK;
+}
+
+// dec_finish; the run counts as finished
+static int smp_finish(const Track& tr, Decoder& d, void* stream) {
+    const int rc = dec_finish(tr, d, stream);
+    if (rc) return rc;
+    d.done = true;
+    return HF_OK;
+}
+
+// the labels of sample k of the last call, for the getter `who`
+static int smp_labels(const Track& tr, const SampleSet& s, const char* who, int k, int8_t* labels_host) {
+    if (k < 0 || k >= s.n) return set_err(HF_E_ARG, std::string(who) + ": k out of range");
+    HIPCHK(hipSetDevice(tr.device));
+    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, s.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+// the sampler's buffers for n samples and the keys of samples first .. first + n - 1
 static int smp_prepare(hf_ctx* ctx, int64_t first, int n, uint64_t seed) {
     const Track& tr = ctx->tr; Sampler& s = ctx->smp;
     if (n > s.cap) {
@@ -2281,18 +2315,8 @@ static int smp_prepare(hf_ctx* ctx, int64_t first, int n, uint64_t seed) {
         if (n > cap) return set_err(HF_E_ARG, "hf_sample_paths: n_samples exceeds hf_sample_capacity (" + std::to_string(cap) + ")");
     }
     int rc = dec_alloc(tr, s, [&](auto&& f) { dec_arrays(tr, s, false, f); });
-    if (rc) return rc;
-    if (n > s.cap) {
-        s.samples.release();
-        s.cap = 0;
-        rc = dec_take(s.samples, [&](auto&& f) { smp_arrays(tr, s, (size_t) n, f); });
-        if (rc) return rc;
-        s.cap = n;
-    }
-    s.h_keys.resize((size_t) n);
-    for (int k = 0; k < n; k++) s.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first + k));
-    HIPCHK(hipMemcpy(s.d_keys, s.h_keys.data(), (size_t) n * 8, hipMemcpyHostToDevice));
-    return HF_OK;
+    if (rc || (rc = smp_grow(s, n, [&](auto&& f) { smp_arrays(tr, s, (size_t) n, f); }))) return rc;
+    return smp_keys(s, first, n, seed);
 }
 
 int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n_samples, uint64_t seed, void* stream) {
@@ -2325,19 +2349,12 @@ int hf_sample_paths(hf_ctx* ctx, const hf_params* p, int64_t first_sample, int n
 
 int hf_sample_finish(hf_ctx* ctx, void* stream) {
     if (!ctx || !ctx->smp.launched) return set_err(HF_E_ARG, "hf_sample_finish: no hf_sample_paths to finish");
-    const int rc = dec_finish(ctx->tr, ctx->smp, stream);
-    if (rc) return rc;
-    ctx->smp.done = true;
-    return HF_OK;
+    return smp_finish(ctx->tr, ctx->smp, stream);
 }
 
 int hf_get_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->smp.done) return set_err(HF_E_ARG, "hf_get_sample_labels: no finished hf_sample_paths");
-    if (k < 0 || k >= ctx->smp.n) return set_err(HF_E_ARG, "hf_get_sample_labels: k out of range");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->smp.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
+    return smp_labels(ctx->tr, ctx->smp, "hf_get_sample_labels", k, labels_host);
 }
 
 
@@ -2991,8 +3008,10 @@ int hf_get_breakpoint_profile(hf_ctx* ctx, int64_t first, int64_t last, uint8_t 
 
 // ------------------------------------------------------------------------------------------
 // minimum-run-length Viterbi (hf_minlen.h): a decoder of its own beside hf_viterbi, one code path for both kinds of context (rows in
-// window order, one wavefront per chunk).  Last in the file, its kernels included, so that no other kernel's code moves.  With it comes
-// hf_chain.h, the core it shares with the two sections after it: wave primitives, lane geometry, row staging.
+// window order, one wavefront per chunk).  hf_viterbi_minlen_joined applies the rule to groups of joined chunks: the same decoder
+// (ctx->mlv, its buffers, hf_viterbi_minlen_finish and the two getters) and the same host run (mlv_run, which cuts the groups of a
+// call); its forward walk is a second body, k_mlvj_fwd, included last in this file.  With it comes hf_chain.h, the core it shares with the sections after it: wave primitives, lane geometry,
+// row staging; and minlen_front, the front of every call of the family.
 // ------------------------------------------------------------------------------------------
 #include "hf_minlen.h"
 
@@ -3017,29 +3036,71 @@ static int minlen_check(const std::string& who, const int32_t min_len[4], int64_
     return HF_OK;
 }
 
-int hf_viterbi_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
-    const std::string w = "hf_viterbi_minlen";
+// The front of every call of the family, error messages naming the entry point `w`: the refusal of a null argument, minlen_check (it
+// leaves the sum of the lengths in `lanes`), `refuse` (what else the entry point refuses before it touches the decoder), then dec_front
+// on the context's decoder `dec` with prepare(track, decoder), which may use `lanes`.
+template <class D, class Refuse, class Prep>
+static int minlen_front(hf_ctx* ctx, D hf_ctx::* dec, const hf_params* p, const int32_t min_len[4], hipStream_t st, const std::string& w,
+                        Refuse&& refuse, Prep&& prepare, int64_t& lanes, const double*& nbE) {
     if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
-    int64_t lanes = 0;
     int rc = minlen_check(w, min_len, &lanes);
+    if (rc || (rc = refuse())) return rc;
+    return dec_front(ctx->tr, ctx->*dec, p, st, w, [&] { return prepare(ctx->tr, ctx->*dec); }, nbE);
+}
+
+// hf_viterbi_minlen (!whole: a block of the walks is a chunk) and hf_viterbi_minlen_joined (whole: a group of joined chunks, cut here;
+// joined null: every chunk a group of its own)
+static int mlv_run(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], bool whole, const uint8_t* joined, hipStream_t st,
+                   const std::string& w) {
+    int64_t lanes = 0;
+    const double* nbE = nullptr;
+    int rc = minlen_front(ctx, &hf_ctx::mlv, p, min_len, st, w,
+                          [&] { return whole && joined && ctx->tr.C > 0 && joined[0]
+                                           ? set_err(HF_E_ARG, w + ": joined[0] must be 0 (the first chunk continues nothing)") : (int) HF_OK; },
+                          [](const Track& tr, MinLenViterbi& v) { return dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); }); }, lanes, nbE);
     if (rc) return rc;
     const Track& tr = ctx->tr;
     MinLenViterbi& v = ctx->mlv;
-    hipStream_t st = (hipStream_t) stream;
-    const double* nbE = nullptr;
-    rc = dec_front(tr, v, p, st, w, [&] { return dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); }); }, nbE);
-    if (rc || (rc = dec_clear_outputs(tr, v, 1, st))) return rc;
+    if ((rc = dec_clear_outputs(tr, v, 1, st))) return rc;
     if (dec_work(tr)) {
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        const int64_t* d_boff = tr.d_off;               // the window ranges of the walks' blocks
+        unsigned B = (unsigned) tr.C;
+        if (whole) {
+            // a chunk starts a group unless it is joined to its predecessor and both have windows (a chunk without windows has no part)
+            const std::vector<int64_t>& off = tr.h_off;
+            v.h_goff.clear(); v.h_gchunk.clear();
+            for (int c = 0; c < tr.C; c++) {
+                const bool cont = c > 0 && joined && joined[c] && off[(size_t) c + 1] > off[(size_t) c] && off[(size_t) c] > off[(size_t) c - 1];
+                if (!cont) { v.h_gchunk.push_back(c); v.h_goff.push_back(off[(size_t) c]); }
+            }
+            v.h_goff.push_back(off[(size_t) tr.C]);
+            const size_t G = v.h_gchunk.size();
+            HIPCHK(hipMemcpyAsync(v.d_goff, v.h_goff.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(v.d_gchunk, v.h_gchunk.data(), G * 4, hipMemcpyHostToDevice, st));
+            d_boff = v.d_goff; B = (unsigned) G;
+        }
         hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
                            v.d_rows, v.d_flags);
-        hipLaunchKernelGGL(k_mlv_fwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
-                           (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_chunk, v.d_flags);
-        hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, (int) min_len[0], (int) min_len[1], (int) min_len[2],
-                           (int) min_len[3], v.d_bp, v.d_final, v.d_label);
+        if (whole)
+            hipLaunchKernelGGL(k_mlvj_fwd, dim3(B), dim3(64), 0, st, d_boff, v.d_gchunk, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, v.d_bp,
+                               v.d_final, v.d_chunk, v.d_flags);
+        else
+            hipLaunchKernelGGL(k_mlv_fwd, dim3(B), dim3(64), 0, st, d_boff, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, v.d_bp, v.d_final,
+                               v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mlv_back, dim3(B), dim3(64), 0, st, d_boff, l0, l1, l2, l3, v.d_bp, v.d_final, v.d_label);
     }
     HIPCHK(hipGetLastError());
     v.launched = true;
     return HF_OK;
+}
+
+int hf_viterbi_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    return mlv_run(ctx, p, min_len, false, nullptr, (hipStream_t) stream, "hf_viterbi_minlen");
+}
+
+int hf_viterbi_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, void* stream) {
+    return mlv_run(ctx, p, min_len, true, joined, (hipStream_t) stream, "hf_viterbi_minlen_joined");
 }
 
 int hf_viterbi_minlen_finish(hf_ctx* ctx, double* log_prob_host, void* stream) {
@@ -3163,15 +3224,10 @@ template <class F> static void mlp_arrays(const Track& tr, MinLenPosterior& v, F
 
 int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
     const std::string w = "hf_minlen_posterior";
-    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
-    int64_t lanes = 0;
-    int rc = minlen_check(w, min_len, &lanes);
-    if (rc) return rc;
-    const Track& tr = ctx->tr;
-    MinLenPosterior& v = ctx->mlp;
     hipStream_t st = (hipStream_t) stream;
+    int64_t lanes = 0;
     const double* nbE = nullptr;
-    rc = dec_front(tr, v, p, st, w, [&] {
+    int rc = minlen_front(ctx, &hf_ctx::mlp, p, min_len, st, w, [] { return (int) HF_OK; }, [&](const Track& tr, MinLenPosterior& v) {
         // the forward lanes: what the decoder holds of them already counts as free
         const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
         if (f_bytes > v.fwd.cap) {
@@ -3182,8 +3238,11 @@ int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4
         }
         const int rc = dec_alloc(tr, v, [&](auto&& f) { mlp_arrays(tr, v, f); });
         return rc ? rc : v.fwd.reserve(f_bytes, w);
-    }, nbE);
-    if (rc || (rc = dec_clear_outputs(tr, v, 2, st))) return rc;
+    }, lanes, nbE);
+    if (rc) return rc;
+    const Track& tr = ctx->tr;
+    MinLenPosterior& v = ctx->mlp;
+    if ((rc = dec_clear_outputs(tr, v, 2, st))) return rc;
     if (dec_work(tr)) {
         double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
         hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
@@ -3270,7 +3329,7 @@ static int mls_capacity(const hf_ctx* ctx, int64_t lanes, const std::string& w) 
     double fixed = 0.0;
     mls_arrays(tr, v, [&](auto&, size_t bytes) { fixed += (double) Slab::granule(bytes); });
     const double f_bytes = (double) tr.N * (double) lanes * 8.0;
-    const double held = (v.alloc ? fixed : 0.0) + (double) v.fwd.cap + (double) v.samples_bytes;
+    const double held = (v.alloc ? fixed : 0.0) + (double) v.fwd.cap + (v.cap ? (double) v.samples.first : 0.0);   // (Slab::release keeps `first`)
     const double budget = 0.9 * ((double) free_b + held) - fixed - f_bytes;
     if (budget < mls_sample_bytes(tr, v, 1)) {
         set_err(HF_E_ARG, w + ": the rows, the forward lanes (" + std::to_string((size_t) f_bytes) + " bytes) and one sample do not fit nine tenths of the free device memory");
@@ -3295,17 +3354,14 @@ int hf_minlen_sample_capacity(const hf_ctx* ctx, const int32_t min_len[4]) {
 int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], int64_t first_sample, int n_samples, uint64_t seed,
                            void* stream) {
     const std::string w = "hf_sample_paths_minlen";
-    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
-    int64_t lanes = 0;
-    int rc = minlen_check(w, min_len, &lanes);
-    if (rc) return rc;
-    if (n_samples < 1) return set_err(HF_E_ARG, w + ": n_samples must be >= 1");
-    if (first_sample < 0) return set_err(HF_E_ARG, w + ": first_sample must be >= 0");
-    const Track& tr = ctx->tr;
-    MinLenSampler& v = ctx->mls;
     hipStream_t st = (hipStream_t) stream;
+    int64_t lanes = 0;
     const double* nbE = nullptr;
-    rc = dec_front(tr, v, p, st, w, [&] {
+    int rc = minlen_front(ctx, &hf_ctx::mls, p, min_len, st, w, [&] {
+        if (n_samples < 1) return set_err(HF_E_ARG, w + ": n_samples must be >= 1");
+        if (first_sample < 0) return set_err(HF_E_ARG, w + ": first_sample must be >= 0");
+        return (int) HF_OK;
+    }, [&](const Track& tr, MinLenSampler& v) {
         const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
         if (n_samples > v.cap || f_bytes > v.fwd.cap) {
             const int cap = mls_capacity(ctx, lanes, w);
@@ -3314,19 +3370,12 @@ int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_le
         }
         int rc = dec_alloc(tr, v, [&](auto&& f) { mls_arrays(tr, v, f); });
         if (rc || (rc = v.fwd.reserve(f_bytes, w))) return rc;
-        if (n_samples > v.cap) {
-            v.samples.release();
-            v.cap = 0; v.samples_bytes = 0;
-            rc = dec_take(v.samples, [&](auto&& f) { mls_sample_arrays(tr, v, (size_t) n_samples, f); });
-            if (rc) return rc;
-            v.cap = n_samples; v.samples_bytes = v.samples.first;
-        }
-        v.h_keys.resize((size_t) n_samples);
-        for (int k = 0; k < n_samples; k++) v.h_keys[(size_t) k] = hf_sample_key(seed, (uint64_t) (first_sample + k));
-        HIPCHK(hipMemcpy(v.d_keys, v.h_keys.data(), (size_t) n_samples * 8, hipMemcpyHostToDevice));
-        return (int) HF_OK;
-    }, nbE);
+        rc = smp_grow(v, n_samples, [&](auto&& f) { mls_sample_arrays(tr, v, (size_t) n_samples, f); });
+        return rc ? rc : smp_keys(v, first_sample, n_samples, seed);
+    }, lanes, nbE);
     if (rc) return rc;
+    const Track& tr = ctx->tr;
+    MinLenSampler& v = ctx->mls;
     if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) n_samples * (size_t) tr.N, st));   // (windows outside every chunk: label -1)
     if (dec_work(tr)) {
         const int K = n_samples, Kp = (int) mls_pad((size_t) K);
@@ -3350,62 +3399,14 @@ int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_le
 
 int hf_sample_minlen_finish(hf_ctx* ctx, void* stream) {
     if (!ctx || !ctx->mls.launched) return set_err(HF_E_ARG, "hf_sample_minlen_finish: no hf_sample_paths_minlen to finish");
-    const int rc = dec_finish(ctx->tr, ctx->mls, stream);
-    if (rc) return rc;
-    ctx->mls.done = true;
-    return HF_OK;
+    return smp_finish(ctx->tr, ctx->mls, stream);
 }
 
 int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->mls.done) return set_err(HF_E_ARG, "hf_get_minlen_sample_labels: no finished hf_sample_paths_minlen");
-    if (k < 0 || k >= ctx->mls.n) return set_err(HF_E_ARG, "hf_get_minlen_sample_labels: k out of range");
-    const Track& tr = ctx->tr;
-    HIPCHK(hipSetDevice(tr.device));
-    if (tr.N > 0) HIPCHK(hipMemcpy(labels_host, ctx->mls.d_label + (int64_t) k * tr.N, (size_t) tr.N, hipMemcpyDeviceToHost));
-    return HF_OK;
+    return smp_labels(ctx->tr, ctx->mls, "hf_get_minlen_sample_labels", k, labels_host);
 }
 
 
-// ------------------------------------------------------------------------------------------
-// minimum-run-length Viterbi over whole contigs (hf_minlen_joined.h): hf_viterbi_minlen's decoder with the rule applied to groups of
-// joined chunks.  It shares ctx->mlv, its buffers, hf_viterbi_minlen_finish and the two getters; the groups of a call are cut here.  Last
-// in the file, its kernel included, so that no other kernel's code moves.
-// ------------------------------------------------------------------------------------------
+// k_mlvj_fwd, the forward walk of hf_viterbi_minlen_joined (mlv_run above launches it).  Last in the file: hf_minlen_joined.h says why.
 #include "hf_minlen_joined.h"
-
-int hf_viterbi_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, void* stream) {
-    const std::string w = "hf_viterbi_minlen_joined";
-    if (!ctx || !p || !min_len) return set_err(HF_E_ARG, w + ": bad argument");
-    int64_t lanes = 0;
-    int rc = minlen_check(w, min_len, &lanes);
-    if (rc) return rc;
-    const Track& tr = ctx->tr;
-    if (joined && tr.C > 0 && joined[0]) return set_err(HF_E_ARG, w + ": joined[0] must be 0 (the first chunk continues nothing)");
-    MinLenViterbi& v = ctx->mlv;
-    hipStream_t st = (hipStream_t) stream;
-    const double* nbE = nullptr;
-    rc = dec_front(tr, v, p, st, w, [&] { return dec_alloc(tr, v, [&](auto&& f) { mlv_arrays(tr, v, f); }); }, nbE);
-    if (rc || (rc = dec_clear_outputs(tr, v, 1, st))) return rc;
-    if (dec_work(tr)) {
-        // a chunk starts a group unless it is joined to its predecessor and both have windows (a chunk without windows has no part)
-        const std::vector<int64_t>& off = tr.h_off;
-        v.h_goff.clear(); v.h_gchunk.clear();
-        for (int c = 0; c < tr.C; c++) {
-            const bool cont = c > 0 && joined && joined[c] && off[(size_t) c + 1] > off[(size_t) c] && off[(size_t) c] > off[(size_t) c - 1];
-            if (!cont) { v.h_gchunk.push_back(c); v.h_goff.push_back(off[(size_t) c]); }
-        }
-        v.h_goff.push_back(off[(size_t) tr.C]);
-        const size_t G = v.h_gchunk.size();
-        HIPCHK(hipMemcpyAsync(v.d_goff, v.h_goff.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(v.d_gchunk, v.h_gchunk.data(), G * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_mlv_rows, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
-                           v.d_rows, v.d_flags);
-        hipLaunchKernelGGL(k_mlvj_fwd, dim3((unsigned) G), dim3(64), 0, st, v.d_goff, v.d_gchunk, tr.d_rec, v.d_params, v.d_rows,
-                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], v.d_bp, v.d_final, v.d_chunk, v.d_flags);
-        hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) G), dim3(64), 0, st, v.d_goff, (int) min_len[0], (int) min_len[1], (int) min_len[2],
-                           (int) min_len[3], v.d_bp, v.d_final, v.d_label);
-    }
-    HIPCHK(hipGetLastError());
-    v.launched = true;
-    return HF_OK;
-}

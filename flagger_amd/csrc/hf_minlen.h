@@ -14,6 +14,18 @@
 //   end          max over all lanes in lane order of delta[(s, d)] + end[s], strict > (the exempt right end)
 // With all four lengths 1 this is hf_viterbi's recurrence and tie rule.
 //
+// OVER WHOLE CONTIGS (hf_viterbi_minlen_joined): the same decoder with the rule applied to GROUPS of joined chunks instead of chunks.
+// joined[c] != 0 says that chunk c continues chunk c-1 (the rule of hf_get_run_moments); a group is a maximal sequence of chunks joined
+// to each other, one contiguous window range, and only a run that contains the group's first or last window is exempt.  Chunks stay
+// independent chains: the weight of a group's path is the product of its chunks' weights, first * prod A_t * end per chunk.
+// The chain is the one above: its lanes, its entry, in-between and saturated steps, its tie rules, in logs.  What differs:
+//   window 0 and the end   are the group's first window and the end column of the group's last window
+//   a joined chunk-first window t (the first window of a chunk that is not the group's first) is an ordinary step with the row
+//                          J_t[p][s] = log end_{c-1}[p] + log first_c[s],  end_{c-1}[p] = trans[r_{t-1}][p][4],
+//                          first_c[s] row pre = 0 of the chunk-first row as k_mlv_rows stores it; -inf when either term is -inf.  The
+//                          run counter runs on across the boundary.
+// HF_FLAG_NAN also for a NaN in an end column read at a joined boundary.
+//
 // Numerics: LOGS.  k_mlv_rows stores log of every entry of the row (-inf for 0), so a step of the chain is one add and one compare and
 // nothing under- or overflows at any chunk length; the (mantissa, exponent) form of hf_decode.h would need a wave-wide maximum per
 // window.  A chunk's score is the maximum itself.  HF_FLAG_NAN: a NaN in a row (k_mlv_rows, as dec_row) or in the end column;
@@ -26,9 +38,23 @@
 // saturated lane stayed (clear: it arrived from d-1).  An owning lane keeps its own decisions of 16 windows in a register, 2 bits per
 // window; after the 16, lane l builds the word of window l from the eight owning lanes' registers, read at their (uniform) lane
 // indices, and the words of 64 windows go out in one store.
-// k_mlv_back: one 64-lane workgroup per chunk walks back from the chunk's final lane: lane q loads the word of window t-q, and (s, d)
-// is carried through the 64 words in registers on the scalar side — a word's address does not depend on the state — while lane q
-// keeps label[t-q] for one store.
+// k_mlvj_fwd: k_mlv_fwd's walk with one 64-lane workgroup per GROUP.  Rows come from k_mlv_rows unchanged.  Inside a group every window
+// past the first whose record carries the chunk-first bit is a joined chunk-first window, so the group ranges are all the host uploads.
+// The lane that stages such a window writes J_t into the tile in place of the staged row (four logs of the previous window's region's
+// end column, once per boundary, off the chain); the step itself reads its five operands from the tile as everywhere.  The record word
+// of the next 64 windows waits in a register beside their rows.  The word of a joined chunk-first window is read like any other, so the
+// walk back is k_mlv_back over the group ranges.  A group is as long as a contig: the window index is 64-bit wherever k_mlv_fwd's is.
+// TWO BODIES, ON PURPOSE.  k_mlvj_fwd is k_mlv_fwd line for line but for the block (goff / gchunk for off / c), the record word nr beside
+// the rows, the J_t branch of the staging lane and the early `bad`: a fix to the tie rule, the word format or the flags goes into both.
+// As one template <bool JOINED> body behind two __global__ wrappers k_mlv_fwd kept its code (operands of commutative instructions
+// swapped) and k_mlvj_fwd its registers, LDS and per-window loops, with one more v_mov in the per-64-window loop and other registers;
+// on the MI355X k_mlvj_fwd then took 9984 and 9906 us against 9800 and 9810 us (configs[2]), ten times what the two runs of the old
+// code are apart, so the walks stay written out, as the turn of the tile does in hf_chain.h (profiles/minlen_front_cfg2.txt).  And
+// k_mlvj_fwd stays the LAST kernel of the translation unit (hf_minlen_joined.h): its own text, put next to k_mlv_fwd or behind
+// k_mlv_back in this header, is compiled into k_mlv_fwd's longer per-window loops (59 / 117 -> 62 / 120 instructions).
+// k_mlv_back: one 64-lane workgroup per chunk (per group) walks back from its final lane: lane q loads the word of window t-q, and
+// (s, d) is carried through the 64 words in registers on the scalar side — a word's address does not depend on the state — while lane
+// q keeps label[t-q] for one store.
 #pragma once
 #include "hf_chain.h"
 
@@ -146,15 +172,13 @@ __global__ void __launch_bounds__(64) k_mlv_back(const int64_t* __restrict__ off
         int lab = 0;
         for (int q = 0; q < n; q++) {
             lab = lane == q ? cs : lab;
-            const int w = __builtin_amdgcn_readlane(wd, q);
-            // an entry lane: to the saturated lane of its predecessor; else one lane down, unless the saturated lane stayed
-            const int p = (w >> (2 * cs)) & 3, stayed = (w >> (8 + cs)) & 1;
-            const bool entry = cd == 1;
-            const int down = (cd < ch_len(mpack, cs)) | (stayed ^ 1);
-            cd = entry ? ch_len(mpack, p) : cd - down;
-            cs = entry ? p : cs;
+            ch_step_back(mpack, __builtin_amdgcn_readlane(wd, q), cs, cd);
         }
         if (lane < n) label[t0 + hi - lane] = (int8_t) lab;
     }
 }
 
+// k_mlvj_fwd is defined in hf_minlen_joined.h, which hf_estep.hip includes behind every other kernel (see above)
+__global__ void k_mlvj_fwd(const int64_t* __restrict__ goff, const int32_t* __restrict__ gchunk, const uint32_t* __restrict__ rec,
+                           const DevParams* __restrict__ P, const double2* __restrict__ rows, int m0, int m1, int m2, int m3, uint16_t* __restrict__ bp,
+                           uint8_t* __restrict__ final_lane, double* __restrict__ ll, unsigned* __restrict__ flags);

@@ -1,24 +1,7 @@
-// hf_minlen_joined.h — minimum-run-length Viterbi over whole contigs (hf_viterbi_minlen_joined): hf_minlen.h's decoder with the rule
-// applied to GROUPS of joined chunks instead of chunks.  joined[c] != 0 says that chunk c continues chunk c-1 (the rule of
-// hf_get_run_moments); a group is a maximal sequence of chunks joined to each other, one contiguous window range, and only a run that
-// contains the group's first or last window is exempt.  Chunks stay independent chains: the weight of a group's path is the product of
-// its chunks' weights, first * prod A_t * end per chunk.
-//
-// The chain is hf_minlen.h's: its lanes, its entry, in-between and saturated steps, its tie rules, in logs.  What differs:
-//   window 0 and the end   are the group's first window and the end column of the group's last window
-//   a joined chunk-first window t (the first window of a chunk that is not the group's first) is an ordinary step with the row
-//                          J_t[p][s] = log end_{c-1}[p] + log first_c[s],  end_{c-1}[p] = trans[r_{t-1}][p][4],
-//                          first_c[s] row pre = 0 of the chunk-first row as k_mlv_rows stores it; -inf when either term is -inf.  The
-//                          run counter runs on across the boundary.
-//
-// k_mlvj_fwd: k_mlv_fwd's walk with one 64-lane workgroup per GROUP.  Rows come from k_mlv_rows unchanged.  Inside a group every window
-// past the first whose record carries the chunk-first bit is a joined chunk-first window, so the group ranges are all the host uploads.
-// The lane that stages such a window writes J_t into the tile in place of the staged row (four logs of the previous window's region's
-// end column, once per boundary, off the chain); the step itself reads its five operands from the tile as everywhere.  The record word
-// of the next 64 windows waits in a register beside their rows.  Backpointer words are k_mlv_fwd's, and the word of a joined chunk-first
-// window is read like any other, so the walk back is k_mlv_back over the group ranges.  A group is as long as a contig: the window
-// index is 64-bit wherever k_mlv_fwd's is.
-// HF_FLAG_NAN also for a NaN in an end column read at a joined boundary.
+// hf_minlen_joined.h — k_mlvj_fwd, the forward walk of hf_viterbi_minlen_joined: k_mlv_fwd's walk with one 64-lane workgroup per group of
+// joined chunks.  The rule, the kernel's description and why it is a second body are in hf_minlen.h; why it is a file of its own, included
+// last in hf_estep.hip: there its code is what it has been; in hf_minlen.h, behind k_mlv_fwd or behind k_mlv_back, the compiler gives its
+// per-window loops the longer form of k_mlv_fwd's (59 / 117 -> 62 / 120 instructions; profiles/minlen_front_cfg2.txt).
 #pragma once
 #include "hf_minlen.h"
 

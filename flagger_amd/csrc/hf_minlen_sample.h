@@ -174,12 +174,7 @@ __global__ void __launch_bounds__(64) k_mls_back(int64_t N, const int64_t* __res
                 const int q = q0 + j;
                 if (q < n) {
                     acc = acc << 8 | (unsigned) cs;
-                    // an entry lane: to the saturated lane of its predecessor; else one lane down, unless the saturated lane stayed
-                    const int p = (int) (w[j] >> (2 * cs)) & 3, stayed = (int) (w[j] >> (8 + cs)) & 1;
-                    const bool entry = cd == 1;
-                    const int down = (cd < ch_len(mpack, cs)) | (stayed ^ 1);
-                    cd = entry ? ch_len(mpack, p) : cd - down;
-                    cs = entry ? p : cs;
+                    ch_step_back(mpack, w[j], cs, cd);
                     if ((q & 3) == 3) tile[lane][(63 - q) >> 2] = acc;
                 }
             }

@@ -546,13 +546,18 @@ class EMList:
         """Most-probable-path decoding (hf_viterbi + hf_viterbi_finish): (labels, chunk_log_probs, log_prob).  The last pass's
         results (labels(), posterior(), forward_backward()) are left as they were."""
         p = model.params()
-        lp = C.c_double(0.0)
         N.check(self._L.hf_viterbi(self._h, C.byref(p), self.stream), "hf_viterbi")
-        N.check(self._L.hf_viterbi_finish(self._h, C.byref(lp), self.stream), "hf_viterbi_finish")
+        return self._decoded("viterbi")
+
+    def _decoded(self, prefix: str):
+        """(labels, chunk_log_probs, log_prob) of the launched decoder hf_<prefix>: its _finish, then hf_get_<prefix>_labels and _chunk_log_probs."""
+        fin, lab, chunk = "hf_%s_finish" % prefix, "hf_get_%s_labels" % prefix, "hf_get_%s_chunk_log_probs" % prefix
+        lp = C.c_double(0.0)
+        N.check(getattr(self._L, fin)(self._h, C.byref(lp), self.stream), fin)
         labels = np.empty(self.store.n_windows, dtype=np.int8)
-        N.check(self._L.hf_get_viterbi_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_viterbi_labels")
+        N.check(getattr(self._L, lab)(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), lab)
         ll = np.empty(self.store.n_chunks, dtype=np.float64)
-        N.check(self._L.hf_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_chunk_log_probs")
+        N.check(getattr(self._L, chunk)(self._h, _dptr(ll)), chunk)
         return labels, ll, float(lp.value)
 
     @staticmethod
@@ -572,7 +577,6 @@ class EMList:
         a group's score in the entry of its first chunk and 0.0 in the others."""
         ml = self._four_lengths("viterbi_minlen", min_len)
         p = model.params()
-        lp = C.c_double(0.0)
         mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
         if joined is None:
             N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), mlp, self.stream), "hf_viterbi_minlen")
@@ -582,12 +586,7 @@ class EMList:
                 raise ValueError("viterbi_minlen: joined must have one entry per chunk")
             N.check(self._L.hf_viterbi_minlen_joined(self._h, C.byref(p), mlp, jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream),
                     "hf_viterbi_minlen_joined")
-        N.check(self._L.hf_viterbi_minlen_finish(self._h, C.byref(lp), self.stream), "hf_viterbi_minlen_finish")
-        labels = np.empty(self.store.n_windows, dtype=np.int8)
-        N.check(self._L.hf_get_viterbi_minlen_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_viterbi_minlen_labels")
-        ll = np.empty(self.store.n_chunks, dtype=np.float64)
-        N.check(self._L.hf_get_viterbi_minlen_chunk_log_probs(self._h, _dptr(ll)), "hf_get_viterbi_minlen_chunk_log_probs")
-        return labels, ll, float(lp.value)
+        return self._decoded("viterbi_minlen")
 
     def minlen_posterior(self, model: HMM, min_len) -> "MinLenPosterior":
         """The posterior given that every run has at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at a chunk's
@@ -626,12 +625,17 @@ class EMList:
         if cap < 1:
             raise N.HFError(N.HF_E_ARG, "hf_sample_capacity: no room for one sample")
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        for k0 in range(0, n_samples, cap):
-            n = min(cap, n_samples - k0)
-            N.check(self._L.hf_sample_paths(self._h, C.byref(p), int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths")
-            N.check(self._L.hf_sample_finish(self._h, self.stream), "hf_sample_finish")
+        return self._drawn(out, cap, "hf_sample_finish", "hf_get_sample_labels", lambda k0, n: N.check(
+            self._L.hf_sample_paths(self._h, C.byref(p), int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths"))
+
+    def _drawn(self, out: np.ndarray, cap: int, finish: str, get: str, draw) -> np.ndarray:
+        """`out` filled in calls of at most `cap` samples: draw(k0, n) launches those of rows k0 .. k0 + n - 1; `finish`, `get`: the sampler's."""
+        for k0 in range(0, len(out), cap):
+            n = min(cap, len(out) - k0)
+            draw(k0, n)
+            N.check(getattr(self._L, finish)(self._h, self.stream), finish)
             for k in range(n):
-                N.check(self._L.hf_get_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_sample_labels")
+                N.check(getattr(self._L, get)(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), get)
         return out
 
     def minlen_sample_capacity(self, min_len) -> int:
@@ -658,13 +662,8 @@ class EMList:
             raise N.HFError(N.HF_E_ARG, "hf_minlen_sample_capacity")
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
-        for k0 in range(0, n_samples, cap):
-            n = min(cap, n_samples - k0)
-            N.check(self._L.hf_sample_paths_minlen(self._h, C.byref(p), mlp, int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths_minlen")
-            N.check(self._L.hf_sample_minlen_finish(self._h, self.stream), "hf_sample_minlen_finish")
-            for k in range(n):
-                N.check(self._L.hf_get_minlen_sample_labels(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_minlen_sample_labels")
-        return out
+        return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: N.check(
+            self._L.hf_sample_paths_minlen(self._h, C.byref(p), mlp, int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths_minlen"))
 
     def interval_log_probs(self, first, last, mask) -> np.ndarray:
         """Exact interval probabilities under the model of the last full pass (hf_get_interval_log_probs): for every job i,

@@ -502,7 +502,7 @@ int hf_viterbi_minlen_finish(hf_ctx *ctx, double *log_prob_host, void *stream);
 int hf_get_viterbi_minlen_labels(hf_ctx *ctx, int8_t *labels_host);                   /* [n_windows] */
 int hf_get_viterbi_minlen_chunk_log_probs(hf_ctx *ctx, double *out_host);             /* [n_chunks] */
 
-/* Minimum-run-length Viterbi over whole contigs (flagger_amd/csrc/hf_minlen_joined.h): hf_viterbi_minlen with the rule applied to GROUPS
+/* Minimum-run-length Viterbi over whole contigs (flagger_amd/csrc/hf_minlen.h): hf_viterbi_minlen with the rule applied to GROUPS
  * of joined chunks instead of chunks.  joined follows the rule hf_get_run_moments states: NULL means all 0; joined[0] must be 0;
  * joined[c] != 0 says that chunk c continues chunk c-1; a chunk without windows has no part, so it ends a group whatever its own entry
  * and its successor's entry say.  A GROUP is a maximal sequence of chunks joined to each other; chunk offsets are one array, so a group
