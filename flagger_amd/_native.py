@@ -137,12 +137,15 @@ def lib() -> C.CDLL:
     sig("hf_get_viterbi_minlen_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_viterbi_minlen_chunk_log_probs", C.c_int, vp, pd)
     sig("hf_minlen_posterior", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), vp)
+    sig("hf_minlen_posterior_joined", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), vp)
     sig("hf_minlen_posterior_finish", C.c_int, vp, pd, vp)
     sig("hf_get_minlen_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_minlen_posterior_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_minlen_chunk_log_mass", C.c_int, vp, pd, pd)
     sig("hf_minlen_sample_capacity", C.c_int, vp, C.POINTER(C.c_int32))
     sig("hf_sample_paths_minlen", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), i64, C.c_int, C.c_uint64, vp)
+    sig("hf_sample_paths_minlen_joined", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), i64, C.c_int,
+        C.c_uint64, vp)
     sig("hf_sample_minlen_finish", C.c_int, vp, vp)
     sig("hf_get_minlen_sample_labels", C.c_int, vp, C.c_int, C.POINTER(C.c_int8))
     sig("hf_sample_capacity", C.c_int, vp)

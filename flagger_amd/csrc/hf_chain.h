@@ -1,6 +1,6 @@
 // hf_chain.h — the core of the walkers of a chain expanded by run length, one lane of a 64-lane wavefront per expanded state:
 // hf_viterbi_minlen and, over whole contigs, hf_viterbi_minlen_joined (hf_minlen.h), hf_get_long_run_log_probs (hf_longrun.h) and
-// hf_minlen_posterior (hf_minlen_post.h).  Three things, each here once: the wave primitives, the lane geometry of the minimum-run-length
+// hf_minlen_posterior (hf_minlen_post.h; over whole contigs hf_minlen_post_joined.h).  Three things, each here once: the wave primitives, the lane geometry of the minimum-run-length
 // expansion, the forward row staging (its tile and rules).
 //
 // THE EXPANSION by minimum run lengths.  min_len[s] >= 1 windows per state, sum <= 64.  Lanes (s, d), d = 1 .. min_len[s]: "in state s,

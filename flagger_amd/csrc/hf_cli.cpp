@@ -53,7 +53,7 @@ static double peak_rss_gb() { struct rusage r; getrusage(RUSAGE_SELF, &r); retur
 enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
-    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs
+    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -96,6 +96,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"constrainedPosterior", no_argument, nullptr, kOptConstrainedPosterior},       // the posterior UNDER --minimumLengths (hf_minlen_posterior; --cons is its shortest prefix: --c, --co, --con were ambiguous in the reference)
     {"admissibleSamples", required_argument, nullptr, kOptAdmissibleSamples},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
     {"wholeContigs", no_argument, nullptr, kOptWholeContigs},             // --enforceMinimumLengths over the joined chunks of a contig (hf_viterbi_minlen_joined; nothing else starts with --wh, --w was ambiguous already; not `j...`: --j stays --jointEntropy)
+    {"mergedChunks", no_argument, nullptr, kOptMergedChunks},             // --constrainedPosterior and --admissibleSamples over the joined chunks of a contig (hf_minlen_posterior_joined, hf_sample_paths_minlen_joined; nothing else starts with --me, --m was ambiguous already)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -209,7 +210,13 @@ static void usage(const char* program) {
             "                                      posterior probability that every run meets its length (runs at a chunk's ends are exempt; chunks\n"
             "                                      are independent, their logs add), and posterior_prediction_min_lengths.bed: the posterior BED of\n"
             "                                      -P given that the path meets the lengths; the final labels and every other output stay as they\n"
-            "                                      are; one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      are; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --mergedChunks               with --constrainedPosterior and / or --admissibleSamples: the minimum lengths hold over the whole\n"
+            "                                      contig, not per chunk: chunks adjacent in the chunk list with the same contig name are joined (the\n"
+            "                                      rule of --numBlocks and --wholeContigs), a run counts across their boundary, and only runs at the\n"
+            "                                      ends of such a group are exempt; the files keep their names and formats, admissible_mass.tsv gains\n"
+            "                                      one column, log_mass_per_chunk_rule (the mass under the per-chunk rule); it does not touch\n"
+            "                                      --viterbi; one GPU, not with --gpus N>1 or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -233,7 +240,7 @@ struct Options {
     int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0, initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, wholeContigs = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
+    bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
     int admissibleSamples = 0; bool admissibleSet = false;
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
@@ -311,9 +318,10 @@ struct Run {
         if (rc == HF_OK) rc = hf_viterbi_minlen_finish(ctx, log_prob, nullptr);
         return rc != HF_OK ? rc : hf_get_viterbi_minlen_labels(ctx, out);
     }
-    int minlen_posterior(hfm_model* m, const int32_t min_len[4], double* log_mass_total) {
+    // (joined: null for the per-chunk rule, else the rule over the groups of joined chunks, --mergedChunks)
+    int minlen_posterior(hfm_model* m, const int32_t min_len[4], const uint8_t* joined, double* log_mass_total) {
         const hf_params p = params(m);
-        const int rc = hf_minlen_posterior(ctx, &p, min_len, nullptr);
+        const int rc = joined ? hf_minlen_posterior_joined(ctx, &p, min_len, joined, nullptr) : hf_minlen_posterior(ctx, &p, min_len, nullptr);
         return rc != HF_OK ? rc : hf_minlen_posterior_finish(ctx, log_mass_total, nullptr);
     }
     int posterior(int64_t first, int64_t n, double* out) {
@@ -991,8 +999,11 @@ static int write_kept_blocks(hf_ctx* ctx, const hfio_table* tab, const std::vect
 //   admissible_mass.tsv                      a header line and a line with the four lengths in windows; then a header line and one row for
 //                                            the whole track ("all") and one per contig (order of first appearance in the chunk list):
 //                                            chunks, windows, log_mass = the chunks' log P(path admissible | data) summed in list order.
+//                                            perChunkRule (--mergedChunks: the chunks' masses of a run under the per-chunk rule, while the
+//                                            context holds the run over the joined chunks) adds the column log_mass_per_chunk_rule.
 //   posterior_prediction_min_lengths.bed     hfio_write_posterior_bed with the constrained posterior and its argmax labels
-static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32_t minLenWindows[4], const std::string& dir) {
+static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32_t minLenWindows[4], const std::string& dir,
+                                       const std::vector<double>* perChunkRule = nullptr) {
     const int64_t N = hfio_n_windows(tab);
     const int C = hfio_n_chunks(tab);
     hf_windows w{};
@@ -1000,19 +1011,20 @@ static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32
     std::vector<double> mass((size_t) std::max(C, 1));
     int rc = hf_get_minlen_chunk_log_mass(ctx, mass.data(), nullptr);
     if (rc != HF_OK) return rc;
-    struct Row { std::string name; int chunks; int64_t n; double log_mass; };
+    struct Row { std::string name; int chunks; int64_t n; double log_mass, per_chunk; };
     std::vector<Row> rows;
-    rows.push_back(Row{"all", 0, 0, 0.0});
+    rows.push_back(Row{"all", 0, 0, 0.0, 0.0});
     std::map<std::string, size_t> ctgRow;
     for (int c = 0; c < C; c++) {
         const std::string ctg = hfio_chunk_ctg(tab, c);
         auto it = ctgRow.find(ctg);
-        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{ctg, 0, 0, 0.0}); }
+        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{ctg, 0, 0, 0.0, 0.0}); }
         for (size_t ri : {(size_t) 0, it->second}) {
             Row& r = rows[ri];
             r.chunks++;
             r.n += w.chunk_off[c + 1] - w.chunk_off[c];
             r.log_mass += mass[(size_t) c];
+            if (perChunkRule) r.per_chunk += (*perChunkRule)[(size_t) c];
         }
     }
     const std::string tp = dir + "/admissible_mass.tsv";
@@ -1020,8 +1032,12 @@ static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32
     if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
     fprintf(f, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\n%d\t%d\t%d\t%d\n", minLenWindows[0], minLenWindows[1],
             minLenWindows[2], minLenWindows[3]);
-    fprintf(f, "#scope\tchunks\twindows\tlog_mass\n");
-    for (const Row& r : rows) fprintf(f, "%s\t%d\t%ld\t%.17g\n", r.name.c_str(), r.chunks, (long) r.n, r.log_mass + 0.0);
+    fprintf(f, "#scope\tchunks\twindows\tlog_mass%s\n", perChunkRule ? "\tlog_mass_per_chunk_rule" : "");
+    for (const Row& r : rows) {
+        fprintf(f, "%s\t%d\t%ld\t%.17g", r.name.c_str(), r.chunks, (long) r.n, r.log_mass + 0.0);
+        if (perChunkRule) fprintf(f, "\t%.17g", r.per_chunk + 0.0);
+        fprintf(f, "\n");
+    }
     if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
     std::vector<double> post((size_t) N * 4);
     std::vector<int8_t> lab((size_t) N);
@@ -1144,7 +1160,7 @@ static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
     {'B', &Options::dumpBin}, {'k', &Options::writeBenchmarkingStatsPerIteration}, {'w', &Options::writeParamsPerIter}, {'P', &Options::writePosterior},
     {'s', &Options::acceleration}, {kOptViterbi, &Options::viterbi}, {kOptRunConfidence, &Options::runConfidence}, {kOptExactTotals, &Options::exactTotals},
     {kOptNumBlocks, &Options::numBlocks}, {kOptRunBoundaries, &Options::runBoundaries}, {kOptJointEntropy, &Options::jointEntropy}, {kOptFitAlpha, &Options::fitAlpha},
-    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}};
+    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}, {kOptMergedChunks, &Options::mergedChunks}};
 static const struct { int code; const char* Options::*text; } kTextOptions[] = {
     {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
     {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath}};
@@ -1306,7 +1322,7 @@ static bool min_len_windows(Run& s, int W) {
     if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
     std::string who;                                           // the options that walk the expanded chain, as given
     for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
-                          o.admissibleSet ? "admissibleSamples" : nullptr})
+                          o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr})
         if (n) who += (who.empty() ? "" : ", --") + std::string(n);
     fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
             ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
@@ -1346,8 +1362,10 @@ static bool check_options(Run& s) {
         {"--wholeContigs", o.wholeContigs, o.viterbi && o.enforceMinLen ? nullptr : "needs --viterbi --enforceMinimumLengths", kOneGpuNoLoopback},
         {"--enforceMinimumLengths", o.enforceMinLen, o.viterbi ? nullptr : "needs --viterbi", kOneGpuNoLoopback},
         {"--keptBlocks", o.keptBlocks, needsMinLen, kOneGpuNoLoopback},
-        {"--constrainedPosterior", o.constrainedPost, needsMinLen, kOneGpuNoLoopback},
-        {"--admissibleSamples", o.admissibleSet, o.admissibleSamples < 1 ? positive : needsMinLen, kOneGpuNoLoopback},
+        // (--mergedChunks is refused wherever the option it acts on is: that option's line names it too, its own row comes last)
+        {o.mergedChunks ? "--constrainedPosterior --mergedChunks" : "--constrainedPosterior", o.constrainedPost, needsMinLen, kOneGpuNoLoopback},
+        {o.mergedChunks ? "--admissibleSamples --mergedChunks" : "--admissibleSamples", o.admissibleSet, o.admissibleSamples < 1 ? positive : needsMinLen, kOneGpuNoLoopback},
+        {"--mergedChunks", o.mergedChunks, o.constrainedPost || o.admissibleSet ? nullptr : "needs --constrainedPosterior or --admissibleSamples", kOneGpuNoLoopback},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
@@ -1752,10 +1770,12 @@ static PathSampler posterior_sampler(hf_ctx* ctx, uint64_t seed) {
                        },
                        [ctx](int k, int8_t* out) { return hf_get_sample_labels(ctx, k, out); }};
 }
-static PathSampler admissible_sampler(hf_ctx* ctx, const int32_t* ml, uint64_t seed) {
+// (joined: null for the per-chunk rule, else the rule over the groups of joined chunks, --mergedChunks)
+static PathSampler admissible_sampler(hf_ctx* ctx, const int32_t* ml, const uint8_t* joined, uint64_t seed) {
     return PathSampler{[ctx, ml] { return hf_minlen_sample_capacity(ctx, ml); },
-                       [ctx, ml, seed](const hf_params* p, int64_t first, int n) {
-                           const int rc = hf_sample_paths_minlen(ctx, p, ml, first, n, seed, nullptr);
+                       [ctx, ml, joined, seed](const hf_params* p, int64_t first, int n) {
+                           const int rc = joined ? hf_sample_paths_minlen_joined(ctx, p, ml, joined, first, n, seed, nullptr)
+                                                 : hf_sample_paths_minlen(ctx, p, ml, first, n, seed, nullptr);
                            return rc == HF_OK ? hf_sample_minlen_finish(ctx, nullptr) : rc;
                        },
                        [ctx](int k, int8_t* out) { return hf_get_minlen_sample_labels(ctx, k, out); }};
@@ -1771,6 +1791,9 @@ static int late_outputs(Run& s, EmRun& em) {
     const std::string& dir = em.dir;
     const std::vector<Region>* const regions = o.regionProbsPath ? &s.regions : nullptr;
     const int32_t* const mw = s.minLenWindows;
+    // --mergedChunks: the two options below apply the lengths over the joined chunks of a contig
+    const std::vector<uint8_t> joinedChunks = o.mergedChunks ? joined_chunks(tab) : std::vector<uint8_t>();
+    const uint8_t* const joined = o.mergedChunks ? joinedChunks.data() : nullptr;
     double t0 = 0.0;
     struct LateOutput { bool wanted; const char *who, *done; std::function<int()> write; };
     const LateOutput outputs[] = {
@@ -1788,17 +1811,28 @@ static int late_outputs(Run& s, EmRun& em) {
         {o.keptBlocks, "--keptBlocks needs", "kept_block_probabilities.tsv is written", [&] { return write_kept_blocks(ctx, tab, regions, mw, o.labelNames, dir); }},
         // (a decoder of its own: it reads the final parameters, not the last pass; its line carries the mass it found)
         {o.constrainedPost, "--constrainedPosterior needs", nullptr, [&] {
-             double logMass = 0.0;
-             int rc = s.minlen_posterior(em.model, mw, &logMass);
-             if (rc == HF_OK) rc = write_constrained_posterior(ctx, tab, mw, dir);
-             if (rc == HF_OK) fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
+             double logMass = 0.0, perChunkMass = 0.0;
+             // --mergedChunks: one run under the per-chunk rule first, for the column the whole-contig masses are compared with
+             std::vector<double> perChunk;
+             int rc = HF_OK;
+             if (joined) {
+                 perChunk.resize((size_t) std::max(hfio_n_chunks(tab), 1));
+                 rc = s.minlen_posterior(em.model, mw, nullptr, &perChunkMass);
+                 if (rc == HF_OK) rc = hf_get_minlen_chunk_log_mass(ctx, perChunk.data(), nullptr);
+             }
+             if (rc == HF_OK) rc = s.minlen_posterior(em.model, mw, joined, &logMass);
+             if (rc == HF_OK) rc = write_constrained_posterior(ctx, tab, mw, dir, joined ? &perChunk : nullptr);
+             if (rc == HF_OK && joined)
+                 fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows over merged chunks keep posterior mass exp(%.6f) (per chunk: exp(%.6f)); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
+                         ts(), mw[0], mw[1], mw[2], mw[3], logMass, perChunkMass, (real_time() - t0) * 1e3);
+             else if (rc == HF_OK) fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows keep posterior mass exp(%.6f); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
                                       ts(), mw[0], mw[1], mw[2], mw[3], logMass, (real_time() - t0) * 1e3);
              return rc;
          }},
         {o.admissibleSamples > 0, "--admissibleSamples needs", "admissible_samples_summary.tsv and admissible_label_runs_support.bed are written", [&] {
-             fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows, seed %llu) ...\n", ts(),
-                     o.admissibleSamples, mw[0], mw[1], mw[2], mw[3], (unsigned long long) o.uncertaintySeed);
-             return write_sample_outputs(admissible_sampler(ctx, mw, o.uncertaintySeed), em.model, tab, labels, o.admissibleSamples, o.labelNames, dir,
+             fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows%s, seed %llu) ...\n", ts(),
+                     o.admissibleSamples, mw[0], mw[1], mw[2], mw[3], joined ? " over merged chunks" : "", (unsigned long long) o.uncertaintySeed);
+             return write_sample_outputs(admissible_sampler(ctx, mw, joined, o.uncertaintySeed), em.model, tab, labels, o.admissibleSamples, o.labelNames, dir,
                                          "admissible_samples_summary.tsv", "admissible_label_runs_support.bed");
          }},
     };

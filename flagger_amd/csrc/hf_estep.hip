@@ -483,7 +483,9 @@ struct DevBuf {
 struct MinLenPosterior : LabelDecoder {
     DevBuf fwd;
     double* d_post = nullptr;
-    void release() { fwd.release(); Decoder::release(); }
+    // hf_minlen_posterior_joined: the group-as-chunk offsets [C + 1] and the joined chunk-first windows [<= C] of a call (mlg_cut)
+    DevBuf grp; std::vector<int64_t> h_grp;
+    void release() { grp.release(); fwd.release(); Decoder::release(); }
 };
 
 // admissible path sampling (hf_minlen_sample.h): rows in window order, forward lanes of its own (as MinLenPosterior::fwd), log Z_adm per
@@ -493,7 +495,8 @@ struct MinLenSampler : Decoder, SampleSet {
     double* d_chunk = nullptr;                 // [C] log Z_adm (k_mlp_fwd writes it; nothing returns it)
     uint16_t* d_words = nullptr;               // [N][Kp] words of k_mlv_fwd's format, Kp = a call's samples padded to HF_MLS_GROUP
     uint8_t* d_final = nullptr;                // [C][Kp] final lanes
-    void release() { fwd.release(); samples.release(); Decoder::release(); }
+    DevBuf grp; std::vector<int64_t> h_grp;    // hf_sample_paths_minlen_joined: as MinLenPosterior's
+    void release() { grp.release(); fwd.release(); samples.release(); Decoder::release(); }
 };
 
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
@@ -3222,12 +3225,14 @@ template <class F> static void mlp_arrays(const Track& tr, MinLenPosterior& v, F
     f(v.d_post, (size_t) tr.N * 32); f(v.d_label, (size_t) tr.N); f(v.d_chunk, (size_t) tr.C * 16);
 }
 
-int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
-    const std::string w = "hf_minlen_posterior";
-    hipStream_t st = (hipStream_t) stream;
+// hf_minlen_posterior and hf_minlen_posterior_joined (hf_minlen_post_joined.h, at the end of this file): one front, the rows, then
+// `walks(track, decoder, forward lanes)` launches the entry point's two walks; `refuse`: what it refuses beyond the family's front
+template <class Refuse, class Walks>
+static int mlp_run(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], hipStream_t st, const std::string& w, Refuse&& refuse,
+                   Walks&& walks) {
     int64_t lanes = 0;
     const double* nbE = nullptr;
-    int rc = minlen_front(ctx, &hf_ctx::mlp, p, min_len, st, w, [] { return (int) HF_OK; }, [&](const Track& tr, MinLenPosterior& v) {
+    int rc = minlen_front(ctx, &hf_ctx::mlp, p, min_len, st, w, refuse, [&](const Track& tr, MinLenPosterior& v) {
         // the forward lanes: what the decoder holds of them already counts as free
         const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
         if (f_bytes > v.fwd.cap) {
@@ -3244,17 +3249,24 @@ int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4
     MinLenPosterior& v = ctx->mlp;
     if ((rc = dec_clear_outputs(tr, v, 2, st))) return rc;
     if (dec_work(tr)) {
-        double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
         hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
                            v.d_rows, v.d_flags);
-        hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows,
-                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_chunk, v.d_flags);
-        hipLaunchKernelGGL(k_mlp_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
-                           (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_post, v.d_label, v.d_flags);
+        if ((rc = walks(tr, v, reinterpret_cast<double*>(v.fwd.d_buf)))) return rc;
     }
     HIPCHK(hipGetLastError());
     v.launched = true;
     return HF_OK;
+}
+
+int hf_minlen_posterior(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    hipStream_t st = (hipStream_t) stream;
+    return mlp_run(ctx, p, min_len, st, "hf_minlen_posterior", [] { return (int) HF_OK; }, [&](const Track& tr, MinLenPosterior& v, double* d_F) {
+        hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows,
+                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mlp_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
+                           (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_post, v.d_label, v.d_flags);
+        return (int) HF_OK;
+    });
 }
 
 int hf_minlen_posterior_finish(hf_ctx* ctx, double* log_mass_total_host, void* stream) {
@@ -3351,16 +3363,17 @@ int hf_minlen_sample_capacity(const hf_ctx* ctx, const int32_t min_len[4]) {
     return rc ? rc : mls_capacity(ctx, lanes, w);
 }
 
-int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], int64_t first_sample, int n_samples, uint64_t seed,
-                           void* stream) {
-    const std::string w = "hf_sample_paths_minlen";
-    hipStream_t st = (hipStream_t) stream;
+// hf_sample_paths_minlen and hf_sample_paths_minlen_joined (hf_minlen_post_joined.h, at the end of this file): one front, the rows, then
+// `walks(track, sampler, forward lanes, K, Kp)` launches the entry point's kernels; `refuse`: what it refuses beyond the common checks
+template <class Refuse, class Walks>
+static int mls_run(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], int64_t first_sample, int n_samples, uint64_t seed,
+                   hipStream_t st, const std::string& w, Refuse&& refuse, Walks&& walks) {
     int64_t lanes = 0;
     const double* nbE = nullptr;
     int rc = minlen_front(ctx, &hf_ctx::mls, p, min_len, st, w, [&] {
         if (n_samples < 1) return set_err(HF_E_ARG, w + ": n_samples must be >= 1");
         if (first_sample < 0) return set_err(HF_E_ARG, w + ": first_sample must be >= 0");
-        return (int) HF_OK;
+        return (int) refuse();
     }, [&](const Track& tr, MinLenSampler& v) {
         const size_t f_bytes = (size_t) tr.N * (size_t) lanes * 8;
         if (n_samples > v.cap || f_bytes > v.fwd.cap) {
@@ -3378,11 +3391,23 @@ int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_le
     MinLenSampler& v = ctx->mls;
     if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(v.d_label, 0xff, (size_t) n_samples * (size_t) tr.N, st));   // (windows outside every chunk: label -1)
     if (dec_work(tr)) {
-        const int K = n_samples, Kp = (int) mls_pad((size_t) K);
+        hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
+                           v.d_rows, v.d_flags);
+        if ((rc = walks(tr, v, reinterpret_cast<double*>(v.fwd.d_buf), n_samples, (int) mls_pad((size_t) n_samples)))) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    v.n = n_samples;
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], int64_t first_sample, int n_samples, uint64_t seed,
+                           void* stream) {
+    hipStream_t st = (hipStream_t) stream;
+    return mls_run(ctx, p, min_len, first_sample, n_samples, seed, st, "hf_sample_paths_minlen", [] { return (int) HF_OK; },
+                   [&](const Track& tr, MinLenSampler& v, double* d_F, int K, int Kp) {
         const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
-        double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
         const unsigned NB = (unsigned) ((tr.N + 255) / 256);
-        hipLaunchKernelGGL(k_dec_rows_win, dim3(NB), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE, v.d_rows, v.d_flags);
         hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 1), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1,
                            l2, l3, d_F, v.d_chunk, v.d_flags);
         hipLaunchKernelGGL(k_mls_draw, dim3(NB), dim3(256), 0, st, tr.N, tr.d_rec, v.d_rows, l0, l1, l2, l3, d_F, v.d_keys, K, Kp, v.d_words);
@@ -3390,11 +3415,8 @@ int hf_sample_paths_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_le
                            v.d_keys, K, Kp, v.d_final);
         hipLaunchKernelGGL(k_mls_back, dim3((unsigned) tr.C, (unsigned) (Kp / HF_MLS_GROUP)), dim3(64), 0, st, tr.N, tr.d_off, l0, l1, l2, l3,
                            v.d_words, v.d_final, K, Kp, v.d_label);
-    }
-    HIPCHK(hipGetLastError());
-    v.n = n_samples;
-    v.launched = true;
-    return HF_OK;
+        return (int) HF_OK;
+    });
 }
 
 int hf_sample_minlen_finish(hf_ctx* ctx, void* stream) {
@@ -3405,6 +3427,83 @@ int hf_sample_minlen_finish(hf_ctx* ctx, void* stream) {
 int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
     if (!ctx || !labels_host || !ctx->mls.done) return set_err(HF_E_ARG, "hf_get_minlen_sample_labels: no finished hf_sample_paths_minlen");
     return smp_labels(ctx->tr, ctx->mls, "hf_get_minlen_sample_labels", k, labels_host);
+}
+
+
+// ------------------------------------------------------------------------------------------
+// the posterior and the sampler over groups of joined chunks (hf_minlen_post_joined.h): hf_minlen_posterior_joined shares ctx->mlp, its
+// finish and its getters with hf_minlen_posterior (mlp_run above), hf_sample_paths_minlen_joined shares ctx->mls with
+// hf_sample_paths_minlen (mls_run above).  The kernels are second bodies launched over the group-as-chunk offsets.  Here, in front of
+// hf_minlen_joined.h, no other kernel's code moves.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_post_joined.h"
+
+// The groups of a call as a chunk list, hf_viterbi_minlen_joined's rule (a chunk continues its predecessor when it is joined to it and
+// both have windows): h[0 .. C] the offsets in which a group's first chunk holds the group's window range and its other chunks none,
+// h[C + 1 ..] the joined chunk-first windows.  Uploaded to `grp` on `st`; returns the number of those windows in *nb.
+static int mlg_cut(const Track& tr, const uint8_t* joined, DevBuf& grp, std::vector<int64_t>& h, hipStream_t st, const std::string& w, int* nb) {
+    const std::vector<int64_t>& off = tr.h_off;
+    const size_t C = (size_t) tr.C;
+    auto cont = [&](size_t c) { return c > 0 && c < C && joined && joined[c] && off[c + 1] > off[c] && off[c] > off[c - 1]; };
+    h.assign(C + 1, 0);
+    h[C] = off[C];
+    int64_t gend = off[C];
+    for (size_t c = C; c-- > 0;) {
+        if (!cont(c + 1)) gend = off[c + 1];               // chunk c is the last of its group
+        h[c] = cont(c) ? gend : off[c];
+    }
+    for (size_t c = 1; c < C; c++) if (cont(c)) h.push_back(off[c]);
+    *nb = (int) (h.size() - (C + 1));
+    const int rc = grp.reserve((2 * C + 1) * 8, w);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(grp.d_buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    return HF_OK;
+}
+
+static int mlg_refuse(const hf_ctx* ctx, const uint8_t* joined, const std::string& w) {
+    return joined && ctx->tr.C > 0 && joined[0] ? set_err(HF_E_ARG, w + ": joined[0] must be 0 (the first chunk continues nothing)") : (int) HF_OK;
+}
+
+int hf_minlen_posterior_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, void* stream) {
+    const std::string w = "hf_minlen_posterior_joined";
+    hipStream_t st = (hipStream_t) stream;
+    return mlp_run(ctx, p, min_len, st, w, [&] { return mlg_refuse(ctx, joined, w); }, [&](const Track& tr, MinLenPosterior& v, double* d_F) {
+        int nb = 0;
+        const int rc = mlg_cut(tr, joined, v.grp, v.h_grp, st, w, &nb);
+        if (rc) return rc;
+        const int64_t* d_goff = reinterpret_cast<const int64_t*>(v.grp.d_buf);
+        hipLaunchKernelGGL(k_mlpj_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, d_goff, tr.d_rec, v.d_params, v.d_rows,
+                           (int) min_len[0], (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mlpj_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, d_goff, tr.d_rec, v.d_params, v.d_rows, (int) min_len[0],
+                           (int) min_len[1], (int) min_len[2], (int) min_len[3], d_F, v.d_post, v.d_label, v.d_flags);
+        return (int) HF_OK;
+    });
+}
+
+int hf_sample_paths_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, int64_t first_sample,
+                                  int n_samples, uint64_t seed, void* stream) {
+    const std::string w = "hf_sample_paths_minlen_joined";
+    hipStream_t st = (hipStream_t) stream;
+    return mls_run(ctx, p, min_len, first_sample, n_samples, seed, st, w, [&] { return mlg_refuse(ctx, joined, w); },
+                   [&](const Track& tr, MinLenSampler& v, double* d_F, int K, int Kp) {
+        int nb = 0;
+        const int rc = mlg_cut(tr, joined, v.grp, v.h_grp, st, w, &nb);
+        if (rc) return rc;
+        const int64_t* d_goff = reinterpret_cast<const int64_t*>(v.grp.d_buf);
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        const unsigned NB = (unsigned) ((tr.N + 255) / 256);
+        hipLaunchKernelGGL(k_mlpj_fwd, dim3((unsigned) tr.C, 1), dim3(64), 0, st, (int) tr.C, d_goff, tr.d_rec, v.d_params, v.d_rows, l0, l1,
+                           l2, l3, d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mls_draw, dim3(NB), dim3(256), 0, st, tr.N, tr.d_rec, v.d_rows, l0, l1, l2, l3, d_F, v.d_keys, K, Kp, v.d_words);
+        if (nb > 0)
+            hipLaunchKernelGGL(k_mlsj_bound, dim3((unsigned) nb), dim3(256), 0, st, d_goff + tr.C + 1, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2,
+                               l3, d_F, v.d_keys, K, Kp, v.d_words);
+        hipLaunchKernelGGL(k_mls_final, dim3((unsigned) tr.C), dim3(64), 0, st, tr.N, d_goff, tr.d_rec, v.d_params, l0, l1, l2, l3, d_F,
+                           v.d_keys, K, Kp, v.d_final);
+        hipLaunchKernelGGL(k_mls_back, dim3((unsigned) tr.C, (unsigned) (Kp / HF_MLS_GROUP)), dim3(64), 0, st, tr.N, d_goff, l0, l1, l2, l3,
+                           v.d_words, v.d_final, K, Kp, v.d_label);
+        return (int) HF_OK;
+    });
 }
 
 

@@ -37,6 +37,11 @@
 // k_mlp_bwd: one 64-lane workgroup per chunk walks back with B in registers: the lane above by DPP, the four entry lanes by readlane, a
 // lane reads its row A[s][0..3] and A[s][s]; F_t comes back 64 windows at a time through LDS (the block before is in registers while this
 // one is walked).  Lanes 0..3 write post[t][lane]; lane q keeps the label of the block's window q for one store.
+//
+// SECOND BODIES.  hf_minlen_post_joined.h holds k_mlpj_fwd and k_mlpj_bwd, these two walks over groups of joined chunks
+// (hf_minlen_posterior_joined, hf_sample_paths_minlen_joined): copies with another staging of the tile, not a template parameter of
+// these kernels (what a shared template did to k_mlv_fwd).  A FIX TO A SUM ORDER OR TO THE RESCALING THEREFORE GOES INTO
+// BOTH BODIES: a group of one chunk must give these kernels' bits.
 #pragma once
 #include "hf_chain.h"
 

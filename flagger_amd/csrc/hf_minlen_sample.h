@@ -32,6 +32,9 @@
 //              by k_mlv_back's rule in vector registers, no readlane per window; the words of the next 16 windows are in flight while
 //              these are stepped.  Labels: four windows per dword into an LDS tile [sample][window] (64 x 64 bytes, rows padded to 17
 //              dwords), then sample after sample the wavefront writes that sample's 64 consecutive labels.
+// hf_sample_paths_minlen_joined (hf_minlen_post_joined.h) launches k_mls_draw, k_mls_final and k_mls_back unchanged, the last two over
+// the group-as-chunk offsets, and fills in the words of the joined chunk-first windows with k_mlsj_bound, which forms its weights by
+// k_mls_draw's operations: a change to the draw rule or to the scaling before the products goes into both.
 #pragma once
 #include "hf_chain.h"
 #include "hf_sample.h"

@@ -588,15 +588,29 @@ class EMList:
                     "hf_viterbi_minlen_joined")
         return self._decoded("viterbi_minlen")
 
-    def minlen_posterior(self, model: HMM, min_len) -> "MinLenPosterior":
+    def _joined_u8(self, who: str, joined) -> np.ndarray:
+        """joined as the uint8[n_chunks] the C ABI takes; `who` names the caller in the refusal."""
+        jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
+        if jn.size != int(self._L.hf_n_chunks(self._h)):
+            raise ValueError("%s: joined must have one entry per chunk" % who)
+        return jn
+
+    def minlen_posterior(self, model: HMM, min_len, joined=None) -> "MinLenPosterior":
         """The posterior given that every run has at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at a chunk's
         ends are exempt; hf_minlen_posterior + hf_minlen_posterior_finish), and the posterior mass the rule keeps.  The last pass's
-        results, viterbi()'s, viterbi_minlen()'s and the sampler's are left as they were."""
+        results, viterbi()'s, viterbi_minlen()'s and the sampler's are left as they were.  joined: None, or a bool array of n_chunks
+        as for viterbi_minlen: the rule then holds over every group of joined chunks (hf_minlen_posterior_joined), and
+        chunk_log_mass / chunk_log_z_adm hold a group's value in the entry of its first chunk and 0.0 in the others."""
         ml = self._four_lengths("minlen_posterior", min_len)
         p = model.params()
         tot = C.c_double(0.0)
+        jn = None if joined is None else self._joined_u8("minlen_posterior", joined)
         self._mlp_run = getattr(self, "_mlp_run", 0) + 1     # (older results stop answering posterior(): the context holds one run)
-        N.check(self._L.hf_minlen_posterior(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_minlen_posterior")
+        if jn is None:
+            N.check(self._L.hf_minlen_posterior(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_minlen_posterior")
+        else:
+            N.check(self._L.hf_minlen_posterior_joined(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream), "hf_minlen_posterior_joined")
         N.check(self._L.hf_minlen_posterior_finish(self._h, C.byref(tot), self.stream), "hf_minlen_posterior_finish")
         labels = np.empty(self.store.n_windows, dtype=np.int8)
         N.check(self._L.hf_get_minlen_posterior_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_minlen_posterior_labels")
@@ -646,12 +660,14 @@ class EMList:
             raise N.HFError(cap, "hf_minlen_sample_capacity")
         return cap
 
-    def sample_paths_minlen(self, model: HMM, min_len, n_samples: int, seed: int, first_sample: int = 0) -> np.ndarray:
+    def sample_paths_minlen(self, model: HMM, min_len, n_samples: int, seed: int, first_sample: int = 0, joined=None) -> np.ndarray:
         """Samples first_sample .. first_sample + n_samples - 1 of the posterior given that every run has at least min_len[s] windows
         (runs at a chunk's ends are exempt; hf_sample_paths_minlen, in calls of at most minlen_sample_capacity samples):
         int8[n_samples][n_windows], every chunk's path admissible, -1 outside chunks.  The last pass's results and every other
-        decoder's are left as they were."""
+        decoder's are left as they were.  joined: None, or a bool array of n_chunks as for viterbi_minlen: every path is then
+        admissible over its group of joined chunks (hf_sample_paths_minlen_joined)."""
         ml = self._four_lengths("sample_paths_minlen", min_len)
+        jn = None if joined is None else self._joined_u8("sample_paths_minlen", joined)
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError("sample_paths_minlen: n_samples must be >= 1")
@@ -662,6 +678,11 @@ class EMList:
             raise N.HFError(N.HF_E_ARG, "hf_minlen_sample_capacity")
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
+        if jn is not None:
+            jp = jn.ctypes.data_as(C.POINTER(C.c_uint8))
+            return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: N.check(
+                self._L.hf_sample_paths_minlen_joined(self._h, C.byref(p), mlp, jp, int(first_sample) + k0, n, seed, self.stream),
+                "hf_sample_paths_minlen_joined"))
         return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: N.check(
             self._L.hf_sample_paths_minlen(self._h, C.byref(p), mlp, int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths_minlen"))
 
@@ -939,13 +960,16 @@ class MinLenPosterior:
         return out
 
 
-def EM_runMinLengthPosteriorForList(emList, model: HMM, min_len) -> MinLenPosterior:
+def EM_runMinLengthPosteriorForList(emList, model: HMM, min_len, joined=None) -> MinLenPosterior:
     """The posterior under minimum run lengths (no counterpart in the reference): per-window label probabilities given that every run
     of state s has at least min_len[s] windows, runs at a chunk's ends exempt, and the posterior mass of those paths per chunk.
-    `emList`: an EMList."""
+    joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole groups of joined chunks and
+    only runs at a group's ends are exempt.  `emList`: an EMList."""
     if not hasattr(emList, "minlen_posterior"):
         raise TypeError("EM_runMinLengthPosteriorForList: %s has no minimum-run-length posterior" % type(emList).__name__)
-    return emList.minlen_posterior(model, min_len)
+    if joined is None:
+        return emList.minlen_posterior(model, min_len)
+    return emList.minlen_posterior(model, min_len, joined)
 
 
 def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:
@@ -956,12 +980,15 @@ def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.n
     return emList.sample_paths(model, n_samples, seed)
 
 
-def EM_sampleMinLengthPathsForList(emList, model: HMM, min_len, n_samples: int, seed: int) -> np.ndarray:
+def EM_sampleMinLengthPathsForList(emList, model: HMM, min_len, n_samples: int, seed: int, joined=None) -> np.ndarray:
     """n_samples admissible paths drawn from the posterior under minimum run lengths with the model's current parameters (no counterpart
-    in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k, min_len) alone.  `emList`: an EMList."""
+    in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k, min_len) alone.  joined[c] says that chunk c continues
+    chunk c - 1 (joined_chunks): every path is then admissible over its whole group of joined chunks.  `emList`: an EMList."""
     if not hasattr(emList, "sample_paths_minlen"):
         raise TypeError("EM_sampleMinLengthPathsForList: %s has no admissible path sampler" % type(emList).__name__)
-    return emList.sample_paths_minlen(model, min_len, n_samples, seed)
+    if joined is None:
+        return emList.sample_paths_minlen(model, min_len, n_samples, seed)
+    return emList.sample_paths_minlen(model, min_len, n_samples, seed, joined=joined)
 
 
 def EM_getIntervalLogProbsForList(emList, first, last, mask) -> np.ndarray:

@@ -626,6 +626,49 @@ int hf_sample_paths_minlen(hf_ctx *ctx, const hf_params *p, const int32_t min_le
 int hf_sample_minlen_finish(hf_ctx *ctx, void *stream);
 int hf_get_minlen_sample_labels(hf_ctx *ctx, int k, int8_t *labels_host);      /* sample first_sample + k, [n_windows], -1 outside chunks */
 
+/* The posterior and the sampler over whole contigs (flagger_amd/csrc/hf_minlen_post_joined.h): hf_minlen_posterior and
+ * hf_sample_paths_minlen with the rule applied to GROUPS of joined chunks.  joined and the groups are exactly those of
+ * hf_viterbi_minlen_joined: NULL means all 0; joined[0] != 0 is HF_E_ARG; a chunk without windows ends a group whatever the entries
+ * say; a group is one contiguous window range.
+ * NORMATIVE RESTATEMENT.  The joined call on (chunk list, joined) is the per-chunk call on a modified chunk list: in that list each
+ * group's first chunk holds the group's whole window range and the group's other chunks hold no windows, and the row of every joined
+ * chunk-first window t (first window of chunk c, joined to c-1) is replaced by
+ *               J_t[p][s] = end_{c-1}[p] * first_c[s],   end_{c-1}[p] = trans[r_{t-1}][p][4],  first_c[s] = row pre = 0 of the
+ *               chunk-first row,
+ * formed first as one double, then used like any A_t[p][s]; end is taken at the group's last window.  Everything else follows:
+ *   recursions and sums   the F and B recursions, every sum order and the tree of the wave sums are hf_minlen_posterior's.
+ *   run counter           it runs on across the boundary: staying goes (s, d) -> (s, min(d+1, m_s)); a change needs the saturated lane of
+ *                         p and enters (s, 1); p == s is excluded when m_s > 1.
+ *   rescaling             at a walk's first vector and after every 8th step, counted from the GROUP's first window (F) or last window
+ *                         (B).  No further rescaling is made at a joined boundary: J_t is the size of any row (a transition probability
+ *                         times first[s]), so a period still passes at most nine rows.
+ *   the products F_t B_t  the frexp form of hf_minlen_posterior.
+ *   Z                     the plain 4-state chain over the same rows of the group, from the same kernel and operations.
+ *   hf_get_minlen_chunk_log_mass   the group's log_mass and log Z_adm in the entry of the group's first chunk, exactly 0.0 in the
+ *                         entries of its other chunks; the list-order sum of hf_minlen_posterior_finish is then the track's.
+ *   sampler               the draw rule, candidate lists, scaling of the eight F_{t-1} values, word format and uniforms are
+ *                         hf_sample_paths_minlen's.  The draw of window t uses uniform index t, the joined chunk-first windows
+ *                         included, which draw with A_t := J_t.  The final lane of a group uses index n_windows + c, c the group's
+ *                         FIRST chunk: a group's sample depends on (seed, absolute sample index, its own windows, lengths) and not on
+ *                         how other contigs are joined.  The indices n_windows + c of the group's other chunks go unused.
+ *   errors                HF_E_NAN also for a NaN in an end column read at a joined boundary; HF_E_SCALE per group; every other
+ *                         refusal is the per-chunk entry point's (lengths, capacity, the forward lanes within nine tenths of the free
+ *                         device memory).
+ * Exact cases.  joined NULL or all zero gives hf_minlen_posterior / hf_sample_paths_minlen bit for bit: post, labels, both per-chunk
+ * arrays, the total and every sample.  All four lengths 1, any joined: log_mass is exactly 0.0 in every entry, and post equals
+ * hf_get_posterior of a full pass to rounding (the boundary row is of rank one).  A group's log_mass is never above the sum of its
+ * chunks' per-chunk log_mass, to rounding; its log Z (log Z_adm - log_mass) equals the sum of its chunks' per-chunk log Z, to rounding.
+ * Every sampled group path is admissible over the group, and a path of hf_viterbi_minlen_joined has non-zero probability.
+ * Each call is asynchronous and shares its decoder's state with the per-chunk entry point: hf_minlen_posterior_finish and the
+ * posterior's getters, hf_sample_minlen_finish and hf_get_minlen_sample_labels answer for the last finished run of either entry point,
+ * and hf_minlen_sample_capacity holds for both.  The outputs are bitwise the same on both kinds of context, across repeated calls and on
+ * any stream; the samples however they are grouped into calls.  hf_batch_* and hf_multi_* have no counterpart. */
+int hf_minlen_posterior_joined(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4],
+                               const uint8_t *joined /* [n_chunks], NULL: none */, void *stream);
+int hf_sample_paths_minlen_joined(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4],
+                                  const uint8_t *joined /* [n_chunks], NULL: none */,
+                                  int64_t first_sample, int n_samples, uint64_t seed, void *stream);
+
 /* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
  * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
  *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]
