@@ -3,9 +3,10 @@ seeds cover can be checked without a GPU (tests/test_streams_cpu.py).
 
 An operation is a string: a pass ("pass_a", "pass_b": full passes with two models; "forward": a forward-only pass), a switch ("flip": the
 other statistics mode, scan contexts only; "alpha_on" / "alpha_off": hf_set_alpha_stats), a decoder with parameters other than the last
-pass's ("viterbi", "sample", "viterbi_minlen", and in generation 3 the three of MINLEN_DECODERS), or one of GETTERS.
+pass's ("viterbi", "sample", "viterbi_minlen", from generation 3 the three of MINLEN_DECODERS and in generation 4 the two of
+JOINED_DECODERS), or one of GETTERS.
 
-There are three GENERATIONS of sequences.  What rnd.choice draws depends on the tuple it draws from, so the getters and decoders a seed
+There are four GENERATIONS of sequences.  What rnd.choice draws depends on the tuple it draws from, so the getters and decoders a seed
 was chosen with are pinned to it: generation 1 is the ten getters and two decoders the first four seeds were committed with (their
 lists never change: tests/test_streams_cpu.py holds a digest of them), generation 2 adds the breakpoint and long-run getters and the
 minimum-length decoder.  The seeds of generation 2 were chosen on the CPU: with the tuples extended in the order below, random sets of
@@ -26,7 +27,22 @@ random.Random(0).sample(range(1000), 4) was drawn until the set was disjoint fro
 every decoder twice, each new decoder after a forward-only pass and three times in one sequence, both orders on the shared state, for
 each buffer one call that grows it and two that do not, three join kinds).  The 328th draw, (586, 294, 195, 107), meets the getter
 conditions with the six decoders too, but each of the three buffers has only ONE call in its sequences that does not grow it; the
-first draw that meets everything is the 3071st, the set below (the seventh disjoint set that meets the getter conditions)."""
+first draw that meets everything is the 3071st, the set below (the seventh disjoint set that meets the getter conditions).
+
+Generation 4 adds the two whole-contig entry points of JOINED_DECODERS: hf_minlen_posterior_joined runs in hf_minlen_posterior's state
+and hf_sample_paths_minlen_joined in hf_sample_paths_minlen's (STATES), as hf_viterbi_minlen_joined runs in hf_viterbi_minlen's.  A
+buffer belongs to the STATE: the forward lanes and the per-sample slab grow with whichever of a state's two entry points asks for more
+and then serve the narrower calls of both, and each of the two states takes a further buffer, "grp" (the groups of a call as a chunk
+list), on its first joined call.  `decoder_arguments` therefore counts `grows` per state.  The new decoders take LENS_CYCLE by their
+own ordinals, JOIN_CYCLE one entry ahead of "viterbi_minlen_joined" (ordinal + 1: all, random, zeros, null — a sequence then holds
+joined calls of different entry points with different vectors), and "sample_minlen_joined" its sample count from
+JOINED_SAMPLE_CYCLE (padded to 64, 192, 64, 64 words per window: three wavefront groups, then narrower calls in them).  The seeds
+were chosen as those of generation 3 were: random.Random(0).sample(range(1000), 4) was drawn until the set was disjoint from the seeds
+of generations 1 to 3 and met the getter conditions and those of test_streams_cpu.test_generation_4_covers_the_decoders
+(`state_coverage`: all eight decoders twice; each new one after a forward-only pass, three times in one sequence and with three join
+kinds; both orders of the two entry points of each of the three states; per buffer of a state one call that grows it and two that do
+not; per buffer and entry point a call narrower than what the OTHER entry point left in the buffer).  At length 64 no set did in
+20 000 draws; at length 80 the 1268th draw is the set below."""
 import random
 
 GETTERS = ("labels", "posterior", "forward_backward", "interval_log_probs", "count_moments", "run_moments", "path_entropy",
@@ -34,21 +50,30 @@ GETTERS = ("labels", "posterior", "forward_backward", "interval_log_probs", "cou
 PASSES = ("pass_a", "pass_b", "forward")
 DECODERS = ("viterbi", "sample", "viterbi_minlen")
 MINLEN_DECODERS = ("minlen_posterior", "sample_minlen", "viterbi_minlen_joined")
+JOINED_DECODERS = ("minlen_posterior_joined", "sample_minlen_joined")      # a tuple of its own, appended: rnd.choice of generation 3 is pinned
 SWITCHES = ("flip", "alpha_on", "alpha_off")
 # generation -> (getters, decoders, length, seeds)
 GENERATIONS = {
     1: (GETTERS[:10], DECODERS[:2], 40, (148, 97, 63, 0)),
     2: (GETTERS, DECODERS, 64, (812, 661, 955, 426)),
     3: (GETTERS, DECODERS + MINLEN_DECODERS, 64, (207, 692, 582, 391)),
+    4: (GETTERS, DECODERS + MINLEN_DECODERS + JOINED_DECODERS, 80, (879, 717, 395, 670)),
 }
 # generation 3: the n-th call of a decoder in a sequence (from 0) takes entry n % len of these
 LENS_CYCLE = ((3, 5, 1, 7), (16, 16, 16, 16), (1, 1, 1, 1), (61, 1, 1, 1), (2, 1, 1, 3))      # 16, 64, 4, 64 and 7 lanes
 SAMPLE_CYCLE = (8, 65, 3, 64)                                  # samples per call of "sample_minlen"
 JOIN_CYCLE = ("null", "all", "random", "zeros")                # the joined vector of "viterbi_minlen_joined" (join_vector)
 JOIN_SEED = 20261020
-MINLEN_USERS = ("viterbi_minlen",) + MINLEN_DECODERS           # the decoders that take minimum lengths
+JOINED_SAMPLE_CYCLE = (8, 130, 3, 64)                          # samples per call of "sample_minlen_joined"
+JOIN_PHASE = {"viterbi_minlen_joined": 0, "minlen_posterior_joined": 1, "sample_minlen_joined": 1}      # decoder -> its start in JOIN_CYCLE
+MINLEN_USERS = ("viterbi_minlen",) + MINLEN_DECODERS           # the decoders that take minimum lengths (to generation 3)
 SHARED_STATE = ("viterbi_minlen", "viterbi_minlen_joined")     # two entry points, one decoder state
 BUFFERS = {"minlen_posterior": ("fwd",), "sample_minlen": ("fwd", "samples")}      # decoder -> its buffers that grow and never shrink
+# decoder -> the state of the context it runs in: two entry points each, the per-chunk one first
+STATES = {"viterbi_minlen": "mlv", "viterbi_minlen_joined": "mlv", "minlen_posterior": "mlp", "minlen_posterior_joined": "mlp",
+          "sample_minlen": "mls", "sample_minlen_joined": "mls"}
+STATE_BUFFERS = {"mlp": ("fwd",), "mls": ("fwd", "samples")}   # state -> its buffers that grow with a call's arguments and never shrink
+ALL_DECODERS = DECODERS + MINLEN_DECODERS + JOINED_DECODERS
 LENGTH = GENERATIONS[1][2]
 SEEDS = GENERATIONS[1][3]
 
@@ -144,35 +169,51 @@ def join_vector(kind, n_chunks):
     return [0 if c == 0 else int(rnd.random() < 0.5) for c in range(n_chunks)]
 
 
-def decoder_arguments(ops, generation: int = 3):
-    """(op, args, grows) for every operation.  For a decoder, `args` is a dict: "ordinal" (the number of earlier calls of the same decoder
-    in `ops`), and what the decoder takes of "min_len", "n_samples" (sample_minlen) and "join" (viterbi_minlen_joined: an entry of
-    JOIN_CYCLE); `grows` is the tuple of the decoder's BUFFERS this call grows: "fwd" when its lengths have more lanes than those of
-    every earlier call of the decoder, "samples" when it asks for more samples than every earlier call (the first call grows all of
-    them: it allocates them).  Below generation 3 "viterbi_minlen" takes LENS_CYCLE[0] in every call.  For any other operation `args`
-    is None and `grows` is ()."""
-    count, lanes, samples = {}, {}, {}
+def _decoder_calls(ops, generation):
+    """(op, args, grows, narrower) for every operation: decoder_arguments' three, and for a decoder the tuple of its state's buffers in
+    which this call is narrower than what the state's OTHER entry point left there (that one grew the buffer last, to more than this
+    call asks for)."""
+    count, size, owner, cut = {}, {}, {}, set()
     for op in ops:
-        if op not in DECODERS + MINLEN_DECODERS:
-            yield op, None, ()
+        if op not in ALL_DECODERS:
+            yield op, None, (), ()
             continue
         n = count.get(op, 0)
         count[op] = n + 1
-        args, grows = {"ordinal": n}, []
-        if op in MINLEN_USERS:
+        args, grows, narrower = {"ordinal": n}, [], []
+        if op in STATES:
             args["min_len"] = LENS_CYCLE[n % len(LENS_CYCLE) if generation >= 3 else 0]
         if op == "sample_minlen":
             args["n_samples"] = SAMPLE_CYCLE[n % len(SAMPLE_CYCLE)]
-        if op == "viterbi_minlen_joined":
-            args["join"] = JOIN_CYCLE[n % len(JOIN_CYCLE)]
-        if op in BUFFERS:
-            if sum(args["min_len"]) > lanes.get(op, 0):
-                lanes[op] = sum(args["min_len"])
-                grows.append("fwd")
-            if "samples" in BUFFERS[op] and args["n_samples"] > samples.get(op, 0):
-                samples[op] = args["n_samples"]
-                grows.append("samples")
-        yield op, args, tuple(grows)
+        if op == "sample_minlen_joined":
+            args["n_samples"] = JOINED_SAMPLE_CYCLE[n % len(JOINED_SAMPLE_CYCLE)]
+        if op in JOIN_PHASE:
+            args["join"] = JOIN_CYCLE[(n + JOIN_PHASE[op]) % len(JOIN_CYCLE)]
+        state = STATES.get(op)
+        for b in STATE_BUFFERS.get(state, ()):
+            want = sum(args["min_len"]) if b == "fwd" else args["n_samples"]
+            if want > size.get((state, b), 0):
+                size[state, b], owner[state, b] = want, op
+                grows.append(b)
+            elif want < size[state, b] and owner[state, b] != op:
+                narrower.append(b)
+        if op in JOINED_DECODERS and state not in cut:         # the state's first joined call takes "grp"
+            cut.add(state)
+            grows.append("grp")
+        yield op, args, tuple(grows), tuple(narrower)
+
+
+def decoder_arguments(ops, generation: int = 3):
+    """(op, args, grows) for every operation.  For a decoder, `args` is a dict: "ordinal" (the number of earlier calls of the same decoder
+    in `ops`), and what the decoder takes of "min_len", "n_samples" (sample_minlen: SAMPLE_CYCLE, sample_minlen_joined:
+    JOINED_SAMPLE_CYCLE) and "join" (an entry of JOIN_CYCLE, from the decoder's JOIN_PHASE on); `grows` is the tuple of the buffers
+    this call grows.  They belong to the decoder's STATE (STATE_BUFFERS), whichever of the state's two entry points is called: "fwd"
+    when the lengths have more lanes than those of every earlier call in the state, "samples" when it asks for more samples than every
+    earlier call in the state (the state's first call grows all of them: it allocates them), and "grp" in the state's first call of
+    an entry point of JOINED_DECODERS.  Below generation 3 "viterbi_minlen" takes LENS_CYCLE[0] in every call.  For any other
+    operation `args` is None and `grows` is ()."""
+    for op, args, grows, _ in _decoder_calls(ops, generation):
+        yield op, args, grows
 
 
 def decoder_coverage(seeds=None, generation: int = 3):
@@ -203,4 +244,47 @@ def decoder_coverage(seeds=None, generation: int = 3):
                 cov["grows" if b in grows else "reuses"][(op, b)] += 1
             if "join" in args:
                 cov["joins"].add(args["join"])
+    return cov
+
+
+def state_coverage(seeds=None, generation: int = 4):
+    """What the decoder calls of the sequences of `seeds` (default: the generation's) cover, per STATE, from the generator alone:
+    "calls", "after_forward", "most_in_one": as decoder_coverage's; "joins": decoder -> the entries of JOIN_CYCLE it is called with;
+    "orders": (state, earlier entry point, later entry point) -> how often, among the calls in that state in one sequence (other
+    operations may lie between them), the one is followed by the other; "grows" / "reuses": (state, buffer) -> calls in the state
+    that grow the buffer / that do not; "narrower": (state, buffer, decoder) -> calls of the decoder with less than what the state's
+    other entry point left in the buffer; "first_joined": state -> calls that take "grp"."""
+    decoders = GENERATIONS[generation][1]
+    pairs = {}
+    for d in decoders:
+        if d in STATES:
+            pairs.setdefault(STATES[d], []).append(d)
+    cov = dict(calls={d: 0 for d in decoders}, after_forward={d: 0 for d in decoders}, most_in_one={d: 0 for d in decoders},
+               joins={d: set() for d in decoders if d in JOIN_PHASE},
+               orders={(s, a, b): 0 for s, p in pairs.items() for a in p for b in p if a != b},
+               grows={(s, b): 0 for s in STATE_BUFFERS for b in STATE_BUFFERS[s]}, reuses={(s, b): 0 for s in STATE_BUFFERS for b in STATE_BUFFERS[s]},
+               narrower={(s, b, d): 0 for s in STATE_BUFFERS for b in STATE_BUFFERS[s] for d in pairs.get(s, ())},
+               first_joined={s: 0 for s in STATE_BUFFERS})
+    for seed in GENERATIONS[generation][3] if seeds is None else seeds:
+        ops = sequence(seed, generation)
+        last = {}
+        for (op, st), (_, args, grows, narrower) in zip(replay(ops), _decoder_calls(ops, generation)):
+            if args is None:
+                continue
+            cov["calls"][op] += 1
+            cov["after_forward"][op] += st["last_pass"] == "forward"
+            cov["most_in_one"][op] = max(cov["most_in_one"][op], args["ordinal"] + 1)
+            if "join" in args:
+                cov["joins"][op].add(args["join"])
+            state = STATES.get(op)
+            if state is None:
+                continue
+            if last.get(state, op) != op:
+                cov["orders"][state, last[state], op] += 1
+            last[state] = op
+            for b in STATE_BUFFERS.get(state, ()):
+                cov["grows" if b in grows else "reuses"][state, b] += 1
+                cov["narrower"][state, b, op] += b in narrower
+            if "grp" in grows:
+                cov["first_joined"][state] += 1
     return cov

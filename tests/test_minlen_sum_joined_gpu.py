@@ -27,6 +27,7 @@ from flagger_amd import hmm, synth
 from hip_streams import Streams
 from test_bruteforce_cpu import _tiny_store
 from test_sampling_gpu import _near_tie_events
+import test_sampling_gpu as TSG
 from test_viterbi_cpu import perturbed_model
 import floor_cases as FC
 import geometry_cases as G
@@ -172,6 +173,123 @@ def test_samples_depend_on_their_own_group_alone():
     assert np.array_equal(other[:, 528:], whole[:, 528:]) and not np.array_equal(other[:, :321], whole[:, :321])
     per_chunk = em.sample_paths_minlen(model, ml, 64, 5)
     assert np.array_equal(other[:, off[4]:off[5]], per_chunk[:, off[4]:off[5]])      # a chunk that is a group of its own
+    em.close()
+
+
+# ---- the sample axis ---------------------------------------------------------------------------------------------------------------
+
+MANY = 577                                                 # pads to 640 words per window: ten wavefront groups, the last of ONE sample
+HIGH = 2 ** 40 + 3                                         # an absolute sample index no 32-bit integer holds
+
+
+@functools.lru_cache(maxsize=None)
+def _boundary_sample_refs(min_len, first, n):
+    """(the joined sampler's reference, the per-chunk sampler's) for samples first .. first + n - 1 of the boundary store."""
+    store, _, _, (A, end) = _boundary()
+    off, ks = store.chunk_off, range(first, first + n)
+    return (SR.sample(R.sample_tables(A, end, off, tuple(BOUNDARY_JOINED), min_len), SAMPLE_SEED, ks, store.n_windows),
+            SR.sample(SR.tables(A, end, off, min_len), SAMPLE_SEED, ks, store.n_windows))
+
+
+@pytest.mark.parametrize("min_len", LENS)
+def test_sample_counts_beyond_one_block_of_k_mlsj_bound(min_len):
+    """577 samples in one call, joined and per chunk.  The minimum-length samplers ran at 70 samples at the most so far (128 padded): here
+    k_mlsj_bound's loop over the samples (256 threads) makes three trips, the last a ragged one of 65, k_mls_back runs with gridDim.y =
+    10 and k_mls_final's loop ten times, and the last wavefront group holds a single sample.  Against the reference over range(577)
+    (its smallest margin over the four lengths sets, joined and per chunk, is 1.3e-6 for windows and 1.0e-5 for final lanes, so the
+    near-tie rule has nothing to excuse: _quiet_reference asserts 1e-9), every sample admissible over its group (_check_samples);
+    bitwise: the two kinds of context, rows [0:65] against a call of 65 in the slab the 577 left, and rows [256:577] against
+    first_sample = 256, n = 321 on a second, fresh context."""
+    store, model, _, _ = _boundary()
+    off = store.chunk_off
+    ref_j, ref_c = (_quiet_reference(r) for r in _boundary_sample_refs(min_len, 0, MANY))
+    res = []
+    for algo in ALGOS:
+        em = hmm.EMList(store, model, algo=algo)
+        assert em.minlen_sample_capacity(min_len) >= MANY        # one call each
+        res.append((em.sample_paths_minlen(model, min_len, MANY, SAMPLE_SEED, joined=BOUNDARY_JOINED),
+                    em.sample_paths_minlen(model, min_len, MANY, SAMPLE_SEED),
+                    em.sample_paths_minlen(model, min_len, 65, SAMPLE_SEED, joined=BOUNDARY_JOINED),
+                    em.sample_paths_minlen(model, min_len, 65, SAMPLE_SEED)))
+        em.close()
+        em = hmm.EMList(store, model, algo=algo)
+        res[-1] += (em.sample_paths_minlen(model, min_len, MANY - 256, SAMPLE_SEED, first_sample=256, joined=BOUNDARY_JOINED),)
+        res[-1] += (em.sample_paths_minlen(model, min_len, MANY - 256, SAMPLE_SEED, first_sample=256),)
+        em.close()
+    joined, chunk, joined65, chunk65, joined_tail, chunk_tail = res[0]
+    assert joined.shape == chunk.shape == (MANY, store.n_windows)
+    _check_samples(off, BOUNDARY_JOINED, ref_j, joined, min_len)
+    _check_samples(off, None, ref_c, chunk, min_len)
+    assert all(np.array_equal(x, y) for x, y in zip(res[0], res[1]))             # the two kinds of context
+    assert np.array_equal(joined[:65], joined65) and np.array_equal(chunk[:65], chunk65)
+    assert np.array_equal(joined[256:], joined_tail) and np.array_equal(chunk[256:], chunk_tail)
+    if min_len != ONES:
+        assert not np.array_equal(joined[256:], chunk[256:])                    # the join bites behind the first 256 samples too
+
+
+def test_absolute_sample_indices_are_64_bit():
+    """first_sample = 2^40 + 3, 70 samples of the three samplers on the boundary store against the references over range(2^40 + 3,
+    2^40 + 73) (their smallest margins are 5.1e-6 and more; sampling_ref.ffbs reports margin 0 at chunk-first windows by its own
+    convention, so hf_sample_paths goes through test_sampling_gpu._check as it stands).  hf_sample_key takes the index as 64 bits:
+    truncated to 32 it would be 3, and the rows would be those of first_sample = 3, from which the references differ in 9 % of the
+    labels."""
+    store, model, _, _ = _boundary()
+    off = store.chunk_off
+    ml = LENS[0]
+    refs = {first: _boundary_sample_refs(ml, first, 70) for first in (HIGH, 3)}
+    res = []
+    for algo in ALGOS:
+        em = hmm.EMList(store, model, algo=algo)
+        res.append({first: (em.sample_paths(model, 70, SAMPLE_SEED, first_sample=first),
+                            em.sample_paths_minlen(model, ml, 70, SAMPLE_SEED, first_sample=first),
+                            em.sample_paths_minlen(model, ml, 70, SAMPLE_SEED, first_sample=first, joined=BOUNDARY_JOINED)) for first in (HIGH, 3)})
+        em.close()
+    for first in (HIGH, 3):
+        plain, chunk, joined = res[0][first]
+        TSG._check(store, model, synth.HIFI_ALPHA, plain, SAMPLE_SEED, first=first)
+        _check_samples(off, None, _quiet_reference(refs[first][1]), chunk, ml)
+        _check_samples(off, BOUNDARY_JOINED, _quiet_reference(refs[first][0]), joined, ml)
+        assert all(np.array_equal(x, y) for x, y in zip(res[0][first], res[1][first]))
+    for high, low in zip(res[0][HIGH], res[0][3]):
+        assert np.mean(high != low) > 0.01                  # (independent samples differ in about 9 % of the labels)
+
+
+def test_requests_above_the_capacity_are_split_into_calls(monkeypatch):
+    """EMList._drawn, the Python path alone: with the capacity forced to 24, a request for 70 samples arrives as calls of 24, 24 and 22
+    with first_sample + k0 passed on and rows k0 .. written; bitwise the one-call result of a context with its own capacity, for the
+    three samplers, from first_sample 0 and 5.  (The capacity of these cards is about 60 000 samples: no request in the suite is split
+    otherwise.)"""
+    store, model, _, _ = _boundary()
+    ml = LENS[0]
+
+    def draws(em, first):
+        return (em.sample_paths(model, 70, SAMPLE_SEED, first_sample=first),
+                em.sample_paths_minlen(model, ml, 70, SAMPLE_SEED, first_sample=first),
+                em.sample_paths_minlen(model, ml, 70, SAMPLE_SEED, first_sample=first, joined=BOUNDARY_JOINED))
+
+    em = hmm.EMList(store, model)
+    assert em.sample_capacity >= 70 and em.minlen_sample_capacity(ml) >= 70
+    want = {first: draws(em, first) for first in (0, 5)}
+    em.close()
+    assert not np.array_equal(want[0][1], want[5][1]) and np.array_equal(want[0][1][5:], want[5][1][:65])
+    em = hmm.EMList(store, model)
+    calls = []
+    drawn = em._drawn
+
+    def spy(out, cap, finish, get, draw):
+        def counted(k0, n):
+            calls.append((cap, k0, n))
+            return draw(k0, n)
+        return drawn(out, cap, finish, get, counted)
+
+    monkeypatch.setattr(hmm.EMList, "sample_capacity", property(lambda self: 24))
+    monkeypatch.setattr(em, "minlen_sample_capacity", lambda min_len: 24)
+    monkeypatch.setattr(em, "_drawn", spy)
+    for first in (0, 5):
+        got = draws(em, first)
+        for name, x, y in zip(("sample_paths", "sample_paths_minlen", "sample_paths_minlen, joined"), got, want[first]):
+            assert x.shape == y.shape and np.array_equal(x, y), (name, first)
+    assert calls == [(24, 0, 24), (24, 24, 24), (24, 48, 22)] * 6
     em.close()
 
 

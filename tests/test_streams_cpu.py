@@ -2,13 +2,18 @@
 kind runs at least twice after a full pass, at least once as the FIRST getter after a full pass (its lazy state is built then), at
 least once directly after a decoder call with other parameters, and — for the refusals — at least once after a forward-only pass.
 This holds for each generation of sequences by itself: for the ten getters of the first over its seeds, and for all thirteen getters
-over the seeds of the second alone, and over those of the third alone.
+over the seeds of the second alone, over those of the third alone, and over those of the fourth alone.
 
 Generation 3 adds the three decoders that carry state from call to call (hf_minlen_posterior, hf_sample_paths_minlen,
 hf_viterbi_minlen_joined), with arguments that change from call to call (stream_sequences.decoder_arguments).  For its committed seeds
 the generator alone shows: every one of the six decoders at least twice; each new decoder after a forward-only pass, and three times
 within one sequence; hf_viterbi_minlen and hf_viterbi_minlen_joined, which share their state, in both orders; for each buffer that
-grows and never shrinks a call that grows it and two that run in it narrower; three kinds of joined vector."""
+grows and never shrinks a call that grows it and two that run in it narrower; three kinds of joined vector.
+
+Generation 4 adds hf_minlen_posterior_joined and hf_sample_paths_minlen_joined, which run in the states of hf_minlen_posterior and
+hf_sample_paths_minlen: buffers belong to the state, so `grows` is counted per state (test_decoder_arguments_per_state), and the
+conditions on its seeds are per state too (test_generation_4_covers_the_decoders).  Generations 2 and 3 are pinned by digests, and
+generation 3's arguments by a digest of decoder_arguments' output."""
 import hashlib
 import json
 
@@ -19,6 +24,9 @@ GENS = sorted(SQ.GENERATIONS)
 GENERATION_1_DIGEST = "6ec2eb0113304e64909753fbb9f77679807ef5142128e2cd98f557c75c994049"
 # ... of generation 2, computed at the commit before the third generation was added
 GENERATION_2_DIGEST = "cfe3109ad41025538fc2df9a07ae10a96d7d46c5efa387711191474a632d5957"
+# ... of generation 3, and of [[list(x) for x in decoder_arguments(ops, 3)] for its four lists], computed at the commit before the fourth
+GENERATION_3_DIGEST = "bf34ea6f0e6b37fccca0177b0adb5d40285eb7e5b429bc29e413d700b8b09acf"
+GENERATION_3_ARGUMENTS_DIGEST = "2b02656ee578cda898329139d7c62169d527abbb17e041671e482d4b3cf29697"
 
 
 def test_generations():
@@ -55,6 +63,27 @@ def test_generation_3():
     assert SQ.JOIN_CYCLE == ("null", "all", "random", "zeros")
 
 
+def test_the_third_generation_is_what_it_was():
+    seqs = [SQ.sequence(s, 3) for s in SQ.GENERATIONS[3][3]]
+    assert hashlib.sha256(json.dumps(seqs).encode()).hexdigest() == GENERATION_3_DIGEST
+    args = [[list(x) for x in SQ.decoder_arguments(ops, 3)] for ops in seqs]
+    assert hashlib.sha256(json.dumps(args).encode()).hexdigest() == GENERATION_3_ARGUMENTS_DIGEST
+    assert args == [[list(x) for x in SQ.decoder_arguments(ops)] for ops in seqs]
+
+
+def test_generation_4():
+    g4, d4, l4, s4 = SQ.GENERATIONS[4]
+    assert g4 == SQ.GETTERS and len(g4) == 13 and l4 in (64, 80, 96) and len(s4) == 4
+    assert d4 == SQ.DECODERS + SQ.MINLEN_DECODERS + SQ.JOINED_DECODERS == SQ.ALL_DECODERS and len(d4) == 8
+    assert SQ.JOINED_DECODERS == ("minlen_posterior_joined", "sample_minlen_joined")
+    assert not set(s4) & (set(SQ.GENERATIONS[1][3]) | set(SQ.GENERATIONS[2][3]) | set(SQ.GENERATIONS[3][3]))
+    assert SQ.JOINED_SAMPLE_CYCLE == (8, 130, 3, 64) and [-(-k // 64) * 64 for k in SQ.JOINED_SAMPLE_CYCLE] == [64, 192, 64, 64]
+    assert SQ.JOIN_PHASE["viterbi_minlen_joined"] == 0 and all(SQ.JOIN_PHASE[d] % len(SQ.JOIN_CYCLE) != 0 for d in SQ.JOINED_DECODERS)
+    assert sorted(SQ.STATES.values()) == ["mlp"] * 2 + ["mls"] * 2 + ["mlv"] * 2 and set(SQ.STATES) == set(d4) - {"viterbi", "sample"}
+    assert (SQ.STATES["minlen_posterior_joined"], SQ.STATES["sample_minlen_joined"]) == (SQ.STATES["minlen_posterior"], SQ.STATES["sample_minlen"])
+    assert SQ.STATE_BUFFERS == {SQ.STATES[d]: b for d, b in SQ.BUFFERS.items()}
+
+
 def test_join_vectors():
     assert SQ.join_vector("null", 10) is None
     assert SQ.join_vector("all", 10) == [0] + [1] * 9 and SQ.join_vector("zeros", 10) == [0] * 10
@@ -83,6 +112,80 @@ def test_decoder_arguments():
     # 64 lanes after 16 grow the lanes; a narrower call after a wider one does not, whatever lay between
     ops = ["minlen_posterior", "sample_minlen", "minlen_posterior", "forward", "minlen_posterior", "sample_minlen"]
     assert [g for _, _, g in SQ.decoder_arguments(ops)] == [("fwd",), ("fwd", "samples"), ("fwd",), (), (), ("fwd", "samples")]
+
+
+def test_decoder_arguments_per_state():
+    """The buffers belong to the state: a joined call after a wider per-chunk call grows nothing, and the reverse; "grp" is taken in the
+    state's first joined call alone."""
+    ops = ["minlen_posterior", "minlen_posterior_joined", "minlen_posterior_joined", "minlen_posterior", "minlen_posterior_joined",
+           "labels", "sample_minlen_joined", "sample_minlen_joined", "sample_minlen", "sample_minlen", "sample_minlen_joined", "sample_minlen",
+           "viterbi_minlen_joined", "sample_minlen_joined"]
+    out = list(SQ._decoder_calls(ops, 4))
+    assert [(o, a, g) for o, a, g, _ in out] == list(SQ.decoder_arguments(ops, 4)) and out[5] == ("labels", None, (), ())
+    post, smp = out[:5], out[6:12] + out[13:]
+    assert [sum(a["min_len"]) for _, a, _, _ in post] == [16, 16, 64, 64, 4]              # an ordinal of its own per decoder
+    assert [a.get("join") for _, a, _, _ in post] == [None, "all", "random", None, "zeros"]
+    assert [g for _, _, g, _ in post] == [("fwd",), ("grp",), ("fwd",), (), ()]
+    assert [n for _, _, _, n in post] == [(), (), (), (), ()]                            # (the 4 lanes run in the joined call's own 64)
+    assert [a["n_samples"] for _, a, _, _ in smp] == [8, 130, 8, 65, 3, 3, 64]
+    assert [sum(a["min_len"]) for _, a, _, _ in smp] == [16, 64, 16, 64, 4, 4, 64]
+    assert [a.get("join") for _, a, _, _ in smp] == ["all", "random", None, None, "zeros", None, "null"]
+    assert [g for _, _, g, _ in smp] == [("fwd", "samples", "grp"), ("fwd", "samples"), (), (), (), (), ()]
+    assert [n for _, _, _, n in smp] == [(), (), ("fwd", "samples"), ("samples",), (), ("fwd", "samples"), ()]
+    assert out[12][1]["join"] == "null" and out[12][2:] == ((), ())                      # the joined Viterbi run keeps its phase, and has no such buffer
+    # the reverse: the per-chunk entry point grows, the joined one runs narrower in what it left, and still takes "grp"
+    ops = ["sample_minlen", "sample_minlen", "sample_minlen_joined", "minlen_posterior", "minlen_posterior", "minlen_posterior_joined"]
+    out = list(SQ._decoder_calls(ops, 4))
+    assert [g for _, _, g, _ in out] == [("fwd", "samples"), ("fwd", "samples"), ("grp",), ("fwd",), ("fwd",), ("grp",)]
+    assert [n for _, _, _, n in out] == [(), (), ("fwd", "samples"), (), (), ("fwd",)]
+    # generation 3's names alone: what the count per decoder gave
+    ops = ["minlen_posterior", "sample_minlen", "minlen_posterior", "forward", "minlen_posterior", "sample_minlen"]
+    assert [g for _, _, g in SQ.decoder_arguments(ops, 4)] == [("fwd",), ("fwd", "samples"), ("fwd",), (), (), ("fwd", "samples")]
+
+
+def test_generation_4_covers_the_decoders():
+    cov = SQ.state_coverage()
+    assert cov == SQ.state_coverage(SQ.GENERATIONS[4][3], 4)
+    assert sorted(cov["calls"]) == sorted(SQ.ALL_DECODERS) and len(cov["calls"]) == 8
+    for d, n in cov["calls"].items():
+        assert n >= 2, (d, n)
+    for d in SQ.JOINED_DECODERS:
+        assert cov["after_forward"][d] >= 1, d
+        assert cov["most_in_one"][d] >= 3, d
+        assert len(cov["joins"][d]) >= 3 and cov["joins"][d] <= set(SQ.JOIN_CYCLE), (d, cov["joins"][d])
+    # both orders of the two entry points of every shared state, within a sequence
+    assert sorted({s for s, _, _ in cov["orders"]}) == ["mlp", "mls", "mlv"] and len(cov["orders"]) == 6
+    for key, n in cov["orders"].items():
+        assert n >= 1, key
+    assert sorted(cov["grows"]) == [("mlp", "fwd"), ("mls", "fwd"), ("mls", "samples")] == sorted(cov["reuses"])
+    for buf in cov["grows"]:
+        assert cov["grows"][buf] >= 1 and cov["reuses"][buf] >= 2, (buf, cov["grows"][buf], cov["reuses"][buf])
+    # per buffer and entry point: a call narrower than what the OTHER entry point left in the buffer
+    assert len(cov["narrower"]) == 6 and {d for _, _, d in cov["narrower"]} == {"minlen_posterior", "sample_minlen"} | set(SQ.JOINED_DECODERS)
+    for key, n in cov["narrower"].items():
+        assert n >= 1, key
+    assert all(n >= 1 for n in cov["first_joined"].values())
+    # the sample axis: 130 samples (three wavefront groups) are drawn, and a narrower call of either entry point follows in that slab
+    for seed in SQ.GENERATIONS[4][3]:
+        sizes = [(op, a["n_samples"]) for op, a, _ in SQ.decoder_arguments(SQ.sequence(seed, 4), 4) if a and "n_samples" in a]
+        if ("sample_minlen_joined", 130) in sizes:
+            after = sizes[sizes.index(("sample_minlen_joined", 130)) + 1:]
+            if any(op == "sample_minlen" for op, _ in after):
+                break
+    else:
+        raise AssertionError("no sequence runs hf_sample_paths_minlen in the slab a joined call of 130 samples left")
+
+
+def test_state_coverage_counts():
+    """state_coverage on generation 3, whose sequences hold no call of the new entry points: its counts are decoder_coverage's."""
+    cov, old = SQ.state_coverage(generation=3), SQ.decoder_coverage()
+    assert cov["calls"] == old["calls"] and cov["after_forward"] == old["after_forward"] and cov["most_in_one"] == old["most_in_one"]
+    assert cov["joins"] == {"viterbi_minlen_joined": old["joins"]} and cov["first_joined"] == {"mlp": 0, "mls": 0}
+    assert cov["orders"] == {("mlv", "viterbi_minlen", "viterbi_minlen_joined"): old["minlen_then_joined"],
+                             ("mlv", "viterbi_minlen_joined", "viterbi_minlen"): old["joined_then_minlen"]}
+    for (d, b), n in old["grows"].items():
+        assert cov["grows"][SQ.STATES[d], b] == n and cov["reuses"][SQ.STATES[d], b] == old["reuses"][d, b]
+    assert all(n == 0 for n in cov["narrower"].values())
 
 
 def test_generation_3_covers_the_decoders():

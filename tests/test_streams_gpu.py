@@ -1,6 +1,6 @@
 """The C ABI on caller-owned streams and in mixed call orders (DESIGN.md "Streams"): the pass, the thirteen getters (the breakpoint and
-long-run getters among them), the six decoders (hf_viterbi, hf_sample_paths, hf_viterbi_minlen, hf_minlen_posterior,
-hf_sample_paths_minlen, hf_viterbi_minlen_joined) and the batch.
+long-run getters among them), the eight decoders (hf_viterbi, hf_sample_paths, hf_viterbi_minlen, hf_minlen_posterior,
+hf_sample_paths_minlen, hf_viterbi_minlen_joined, hf_minlen_posterior_joined, hf_sample_paths_minlen_joined) and the batch.
 
 Every entry point that enqueues GPU work takes a `void *stream`; the getters run on the stream of the last pass.  Here the stream is a
 non-blocking one of the caller's (tests/hip_streams.py), and directly in front of every library call the caller enqueues filler work on
@@ -18,7 +18,16 @@ generation 3 (tests/stream_sequences.py) therefore change the arguments from cal
 64; four kinds of joined vector), and because stale state would be equally wrong on the twin, every decoder call of such a sequence
 is also compared, bitwise, with the same call on a FRESH context that has run nothing else.  test_generation_3_arguments_equal_the_references
 ties those fresh-context results to the float64 numpy references of the features' own tests.  A call that grows a buffer frees the
-old one, and hipFree waits for the device: there the busy-stream check only records what it finds (printed; pytest -s)."""
+old one, and hipFree waits for the device: there the busy-stream check only records what it finds (printed; pytest -s).
+
+Generation 4 adds the two whole-contig entry points hf_minlen_posterior_joined and hf_sample_paths_minlen_joined.  They run in the
+states of hf_minlen_posterior and hf_sample_paths_minlen, so a state's forward lanes and per-sample slab are grown by either entry
+point and serve the narrower calls of both (samples 8, 130, 3, 64 for the joined sampler: three wavefront groups of padded samples,
+then one), and each state takes one more buffer, the groups of a call as a chunk list, in its first joined call, which uploads into
+it from a host vector of the state's in every joined call.  The busy-stream claim is made for both under their own names wherever
+stream_sequences.decoder_arguments says the call grows nothing; the stored results are read per state; and
+test_generation_4_arguments_equal_the_references ties the fresh-context results to the references of
+tests/test_minlen_sum_joined_gpu.py."""
 import collections
 import ctypes as C
 import functools
@@ -38,11 +47,14 @@ import minlen_joined_ref
 import minlen_post_ref
 import minlen_ref
 import minlen_sample_ref
+import minlen_sum_joined_ref
+import sampling_ref
 import stream_sequences as SQ
 import test_minlen_gpu as TML
 import test_minlen_joined_gpu as TMJ
 import test_minlen_post_gpu as TMP
 import test_minlen_sample_gpu as TMS
+import test_minlen_sum_joined_gpu as TSJ
 import viterbi_ref
 from test_posterior_gpu import _ranges, _regions_store, _sizes_store
 
@@ -235,8 +247,8 @@ class Side:
         self.h = HS.hip()
         self.contexts = []
         self.busy_checked = 0
-        self.busy = collections.Counter()      # (entry point, "asserted" | "grow, busy" | "grow, idle") -> calls (the three newest decoders)
-        self.last_samples = {}                 # context -> the samples of its last hf_sample_paths_minlen
+        self.busy = collections.Counter()      # (entry point, "asserted" | "grow, busy" | "grow, idle") -> calls (the five newest decoders)
+        self.last_samples = {}                 # context -> the samples of the last run in its sampler state (either entry point)
 
     @property
     def stream(self):
@@ -451,10 +463,65 @@ class Side:
         assert code == N.HF_OK
         return N.HF_OK, arrays
 
+    def _joined_pointer(self, join):
+        """(the uint8 array that holds stream_sequences.join_vector(join), its pointer for the C ABI): (None, None) for "null"."""
+        jv = SQ.join_vector(join, self.store.n_chunks)
+        if jv is None:
+            return None, None
+        ja = np.asarray(jv, np.uint8)
+        return ja, ja.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def minlen_posterior_joined(self, em, model, s=None, min_len=MIN_LEN, join="null", grows=()):
+        """hf_minlen_posterior_joined + hf_minlen_posterior_finish on stream `s` with the joined vector stream_sequences.join_vector(join)
+        and the getters it shares with hf_minlen_posterior: (code, (posterior, labels, chunk log mass, chunk log Z_adm, total)).
+        Asynchronous "as hf_minlen_posterior is": the stream is still busy when it returns, unless the call grows a buffer (`grows`)."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        p, tot = model.params(), C.c_double(0.0)
+        ml = (C.c_int32 * 4)(*min_len)
+        ja, jp = self._joined_pointer(join)
+        self.delay(s)
+        rc = L.hf_minlen_posterior_joined(em._h, C.byref(p), ml, jp, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.check_busy(s, "hf_minlen_posterior_joined", grows)
+        rc = L.hf_minlen_posterior_finish(em._h, C.byref(tot), C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.delay(s)
+        code, arrays = self._minlen_posterior_results(em)
+        assert code == N.HF_OK
+        return N.HF_OK, arrays + (np.float64(tot.value),)
+
+    def sample_minlen_joined(self, em, model, s=None, min_len=MIN_LEN, n=SAMPLES, seed=SAMPLE_SEED, join="null", grows=()):
+        """hf_sample_paths_minlen_joined + hf_sample_minlen_finish on stream `s` with the joined vector
+        stream_sequences.join_vector(join) and the getter it shares with hf_sample_paths_minlen: (code, (int8[n][n_windows],))."""
+        L, s = N.lib(), (em.stream.value or 0) if s is None else s
+        assert em.minlen_sample_capacity(min_len) >= n
+        p = model.params()
+        ml = (C.c_int32 * 4)(*min_len)
+        ja, jp = self._joined_pointer(join)
+        self.delay(s)
+        rc = L.hf_sample_paths_minlen_joined(em._h, C.byref(p), ml, jp, 0, n, seed, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.check_busy(s, "hf_sample_paths_minlen_joined", grows)
+        rc = L.hf_sample_minlen_finish(em._h, C.c_void_p(s))
+        if rc != N.HF_OK:
+            return int(rc), ()
+        self.last_samples[id(em)] = n
+        self.delay(s)
+        code, arrays = self._minlen_samples(em, n)
+        assert code == N.HF_OK
+        return N.HF_OK, arrays
+
     def decoder(self, em, which, model, s=None, args=None, grows=()):
         """Decoder `which` with the arguments stream_sequences.decoder_arguments gives for the call (default: MIN_LEN, SAMPLES, no join)."""
         args = args or {}
         kw = {"min_len": args["min_len"]} if "min_len" in args else {}
+        if which == "minlen_posterior_joined":
+            return self.minlen_posterior_joined(em, model, s, join=args.get("join", "null"), grows=grows, **kw)
+        if which == "sample_minlen_joined":
+            return self.sample_minlen_joined(em, model, s, n=args.get("n_samples", SAMPLES), join=args.get("join", "null"), grows=grows, **kw)
         if which == "minlen_posterior":
             return self.minlen_posterior(em, model, s, grows=grows, **kw)
         if which == "sample_minlen":
@@ -468,13 +535,14 @@ class Side:
     def stored(self, em, which, s=None):
         """What the getters of decoder `which` answer now, behind a delay: (code, arrays) with the arrays in the order of the decoder's
         own record (its score, a value of the finish call, is not stored).  "viterbi_minlen" and "viterbi_minlen_joined" share their
-        state and their getters: either name reads the results of the later of the two calls.  "sample_minlen": as many samples as
-        that decoder's last call on `em` drew."""
+        state and their getters: either name reads the results of the later of the two calls, and so do "minlen_posterior" and
+        "minlen_posterior_joined", "sample_minlen" and "sample_minlen_joined" (as many samples as the later of the two calls on `em`
+        drew)."""
         L = N.lib()
         self.delay((em.stream.value or 0) if s is None else s)
-        if which == "minlen_posterior":
+        if which in ("minlen_posterior", "minlen_posterior_joined"):
             return self._minlen_posterior_results(em)
-        if which == "sample_minlen":
+        if which in ("sample_minlen", "sample_minlen_joined"):
             return self._minlen_samples(em, self.last_samples[id(em)])
         if which == "sample":
             out = np.empty((SAMPLES, self.store.n_windows), dtype=np.int8)
@@ -492,6 +560,15 @@ class Side:
         if r1 != N.HF_OK or r2 != N.HF_OK:
             return int(r1 or r2), ()
         return N.HF_OK, (labels, ll)
+
+
+# decoder -> the name under which Side.stored reads its state, where two entry points share one
+STATE_READER = {"viterbi_minlen_joined": "viterbi_minlen", "minlen_posterior_joined": "minlen_posterior", "sample_minlen_joined": "sample_minlen"}
+
+
+def _first_call_grows(decoder):
+    """What the first call of `decoder` on a context grows: every buffer of its state, and "grp" where it is a joined entry point."""
+    return SQ.STATE_BUFFERS.get(SQ.STATES.get(decoder), ()) + (("grp",) if decoder in SQ.JOINED_DECODERS else ())
 
 
 def _stored_equals(stored, returned, what):
@@ -687,35 +764,55 @@ def test_decoders_with_other_parameters(name, kind, where, monkeypatch):
 
 
 SIX = SQ.DECODERS + SQ.MINLEN_DECODERS
+EIGHT = SIX + SQ.JOINED_DECODERS
 FAMILY_ARGS = {"min_len": MIN_LEN, "n_samples": SAMPLES, "join": "random"}
+FAMILY_ZEROS = dict(FAMILY_ARGS, join="zeros")
 FAMILY = [pytest.param(n, k, id="%s-%s" % (n, k)) for n in ("config2", "sizes") for k in ("seq", "scan-rows")]
 
 
 @pytest.mark.parametrize("where", ["same-stream", "second-stream"])
 @pytest.mark.parametrize("name,kind", FAMILY)
 def test_minlen_family_with_other_parameters(name, kind, where, monkeypatch):
-    """All six decoders with parameters other than the pass's, on the pass's stream or on a second non-blocking stream, twice: the two
+    """All eight decoders with parameters other than the pass's, on the pass's stream or on a second non-blocking stream, twice: the two
     runs are equal (the second grows no buffer: the stream is still busy when each of the new entry points returns), afterwards every
     getter still answers for the pass, and each decoder's stored results are its own last ones.  hf_viterbi_minlen and
     hf_viterbi_minlen_joined share their state: the stored results are those of the later of the two, in every chunk entry (the exact
-    zeros a joined call leaves in a group's other chunks included), and nothing of the earlier one's — in either order."""
+    zeros a joined call leaves in a group's other chunks included), and nothing of the earlier one's — in either order.  So do
+    hf_minlen_posterior and hf_minlen_posterior_joined (both arrays of hf_get_minlen_chunk_log_mass), and hf_sample_paths_minlen and
+    hf_sample_paths_minlen_joined: the six are read once the six have run (the per-chunk entry points the later ones), the two
+    shared states again after the joined calls, and again after a per-chunk call that follows those.  At the end both joined entry
+    points run with another joined vector (all zero: nothing is joined) and with the first again: the results are those of a context
+    that ran that call alone and, the header's exact case, those of the per-chunk entry point, so the groups of the call before are
+    gone from the state's device buffer."""
     def scenario(side):
         ma, mb = _model(name, "a"), _model(name, "b")
         s2 = side.streams[1] if where == "second-stream" else None
         em = side.context(alpha_stats=True)
         rec = {"pass b": [side.estep(em, mb)]}
-        for d in SIX:
-            rec[d + " a"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS, SQ.BUFFERS.get(d, ()))]       # (a first call grows every buffer)
+        for d in EIGHT:                                           # (a state's first call grows every buffer, its first joined call "grp")
+            rec[d + " a"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS, SQ.BUFFERS.get(d, ()) + (("grp",) if d in SQ.JOINED_DECODERS else ()))]
         for g in _getters_of(side):
             rec[g + " after the decoders"] = side.getter(em, g)
         for d in SIX:
             rec[d + " a again"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS)]
+        for d in SIX:                                             # "viterbi_minlen": the shared state, the joined call the later one
+            rec[d + " stored"] = [side.stored(em, d, s2)]
+        for d in SQ.JOINED_DECODERS:                              # per-chunk, then joined
+            rec[d + " a again"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS)]
         for g in _getters_of(side):
             rec[g + " after the decoders again"] = side.getter(em, g)
-        for d in SIX:                                             # "viterbi_minlen": the shared state, the joined call the later one
+        for d in SQ.JOINED_DECODERS:
             rec[d + " stored"] = [side.stored(em, d, s2)]
         rec["viterbi_minlen a, after the joined call"] = [side.viterbi_minlen(em, ma, s2)]
         rec["viterbi_minlen stored, after the joined call"] = [side.stored(em, "viterbi_minlen", s2)]
+        for d in SQ.JOINED_DECODERS:                              # joined, then per-chunk
+            rec[STATE_READER[d] + " a, after the joined call"] = [side.decoder(em, STATE_READER[d], ma, s2, FAMILY_ARGS)]
+            rec[STATE_READER[d] + " stored, after the joined call"] = [side.stored(em, STATE_READER[d], s2)]
+        fresh = side.context()
+        for d in SQ.JOINED_DECODERS:                              # another joined vector, then the first again: the groups are cut per call
+            rec[d + " a, zeros"] = [side.decoder(em, d, ma, s2, FAMILY_ZEROS)]
+            rec[d + " a, random again"] = [side.decoder(em, d, ma, s2, FAMILY_ARGS)]
+            rec[d + " a, zeros, alone"] = [side.decoder(fresh, d, ma, s2, FAMILY_ZEROS, _first_call_grows(d))]
         alone = side.context(alpha_stats=True)
         rec["alone pass b"] = [side.estep(alone, mb)]
         for g in _getters_of(side):
@@ -727,7 +824,7 @@ def test_minlen_family_with_other_parameters(name, kind, where, monkeypatch):
     rec = _run_both(name, kind, monkeypatch, scenario, n_streams=2)
     store = _input(name)[0]
     assert all(c == N.HF_OK for calls in rec.values() for c in _codes(calls)), {t: _codes(c) for t, c in rec.items()}
-    for d in SIX:
+    for d in EIGHT:
         _equal(rec[d + " a"], rec[d + " a again"], d)
     for d in ("viterbi", "sample", "minlen_posterior", "sample_minlen", "viterbi_minlen_joined"):
         _stored_equals(rec[d + " stored"][0], rec[d + " a again"][0], d + " stored")
@@ -741,6 +838,25 @@ def test_minlen_family_with_other_parameters(name, kind, where, monkeypatch):
     _stored_equals(rec["viterbi_minlen stored, after the joined call"][0], minlen, "the shared state after hf_viterbi_minlen")
     _check_chunk_entries(store, rec["viterbi_minlen stored, after the joined call"][0][1][1], "viterbi_minlen", FAMILY_ARGS)
     assert not np.array_equal(rec["viterbi_minlen a"][0][1][0], rec["viterbi a"][0][1][0])         # the constraint bites
+    # the two newer shared states: the joined call the later one, then the per-chunk call
+    for d in SQ.JOINED_DECODERS:
+        per_chunk = STATE_READER[d]
+        joined, chunk = rec[d + " a again"][0], rec[per_chunk + " a again"][0]
+        assert not np.array_equal(joined[1][0], chunk[1][0]), d                                    # (the two differ, so a mix would show)
+        _stored_equals(rec[d + " stored"][0], joined, "the shared state after " + d)
+        _equal(rec[per_chunk + " a, after the joined call"], rec[per_chunk + " a again"], per_chunk + " after a joined call")
+        _stored_equals(rec[per_chunk + " stored, after the joined call"][0], chunk, "the shared state after " + per_chunk)
+    for tag, op in (("minlen_posterior_joined stored", "minlen_posterior_joined"), ("minlen_posterior stored", "minlen_posterior"),
+                    ("minlen_posterior stored, after the joined call", "minlen_posterior")):
+        _check_mass_entries(store, rec[tag][0][1][2], rec[tag][0][1][3], op, FAMILY_ARGS)
+    joined, chunk = rec["minlen_posterior_joined a again"][0][1], rec["minlen_posterior a again"][0][1]
+    assert not np.array_equal(joined[2], chunk[2]) and not np.array_equal(joined[3], chunk[3])
+    for d in SQ.JOINED_DECODERS:
+        _equal(rec[d + " a, zeros"], rec[d + " a, zeros, alone"], d + " with another joined vector")
+        _equal(rec[d + " a, random again"], rec[d + " a again"], d + " with the first joined vector again")
+        _equal(rec[d + " a, zeros"], rec[STATE_READER[d] + " a again"], d + " with nothing joined against the per-chunk entry point")
+        assert _differ(rec[d + " a, zeros"], rec[d + " a again"]), d
+    _check_mass_entries(store, rec["minlen_posterior_joined a, zeros"][0][1][2], rec["minlen_posterior_joined a, zeros"][0][1][3], "minlen_posterior_joined", FAMILY_ZEROS)
     for g in GETTERS:
         if g + " alone" in rec:
             _equal(rec[g + " after the decoders"], rec[g + " alone"], g)
@@ -763,9 +879,9 @@ def _reference(decoder, which, min_len, n_samples, join):
     return minlen_sample_ref.reference(store, model, alpha, min_len, SAMPLE_SEED, range(n_samples))
 
 
-def _cycle_arguments(decoder, ordinal):
+def _cycle_arguments(decoder, ordinal, generation=3):
     """What stream_sequences.decoder_arguments gives the call number `ordinal` of `decoder`."""
-    return list(SQ.decoder_arguments([decoder] * (ordinal + 1)))[-1][1]
+    return list(SQ.decoder_arguments([decoder] * (ordinal + 1), generation))[-1][1]
 
 
 ANCHORS = [pytest.param(d, n, id="%s-%d" % (d, n)) for d in SQ.MINLEN_USERS for n in range(len(SQ.LENS_CYCLE))]
@@ -808,12 +924,66 @@ def test_generation_3_arguments_equal_the_references(decoder, ordinal):
             side.close()
 
 
+@functools.lru_cache(maxsize=None)
+def _sizes_tables(which):
+    """(log tables, linear rows) of input "sizes" under model `which`, as the joined references take them."""
+    store, _, _, alpha = _input("sizes")[:4]
+    model = _model("sizes", which)
+    return viterbi_ref.tables(store, model, alpha), sampling_ref.rows(store, model, alpha)
+
+
+ANCHORS_4 = [pytest.param(d, n, w, id="%s-%d-%s" % (d, n, w)) for d in SQ.JOINED_DECODERS for n in range(len(SQ.LENS_CYCLE)) for w in "ab"]
+
+
+@pytest.mark.parametrize("decoder,ordinal,which", ANCHORS_4)
+def test_generation_4_arguments_equal_the_references(decoder, ordinal, which):
+    """Input "sizes", both models, a fresh context per call on a caller's busy stream: the arguments of the first five calls of the two
+    whole-contig entry points in a generation-4 sequence (every entry of LENS_CYCLE and JOINED_SAMPLE_CYCLE, the joins all, random,
+    zeros, null, all) against the float64 numpy references of tests/test_minlen_sum_joined_gpu.py (minlen_sum_joined_ref.posterior_tables;
+    sample_tables fed to minlen_sample_ref.sample), with that file's checkers at their tolerances.  Before a case is relied on, the
+    reference itself is checked: Z_adm > 0 in every group (a finite log Z_adm), and no draw of the sampler's reference within 1e-9 of
+    a boundary (_quiet_reference).  Both hold for every case here, the "all" join (one group of 18 828 windows) included, with log
+    Z_adm between -57 959 and -39 578 and margins of 2.1e-7 and more.  One reference takes 1 to 2 s, so a case is one model."""
+    import time
+    args = _cycle_arguments(decoder, ordinal, 4)
+    min_len = args["min_len"]
+    store = _input("sizes")[0]
+    off = store.chunk_off
+    joined = SQ.join_vector(args["join"], store.n_chunks)
+    (logA, logend), (A, end) = _sizes_tables(which)
+    t0 = time.perf_counter()
+    if decoder == "minlen_posterior_joined":
+        ref = minlen_sum_joined_ref.posterior_tables(logA, logend, off, joined, min_len)
+        gf = minlen_joined_ref.group_first_chunks(off, joined)
+        assert np.all(np.isfinite(ref[2][gf])) and np.all(np.isfinite(ref[1][gf])), (args, ref[2][gf])       # Z_adm > 0 in every group
+    else:
+        ref = TSJ._quiet_reference(minlen_sample_ref.sample(minlen_sum_joined_ref.sample_tables(A, end, off, joined, min_len), SAMPLE_SEED,
+                                                            range(args["n_samples"]), store.n_windows))
+    t1 = time.perf_counter()
+    with HS.Streams() as streams:
+        side = Side("sizes", "scan-rows", [streams.new(True)])
+        try:
+            em = side.context()
+            code, got = side.decoder(em, decoder, _model("sizes", which), None, args, _first_call_grows(decoder))
+            em.close()
+            print("%s %s model %s: reference %.2f s, device call with its getters %.2f s" % (decoder, args, which, t1 - t0, time.perf_counter() - t1))
+            assert code == N.HF_OK, (decoder, args, which, code)
+            if decoder == "minlen_posterior_joined":
+                TSJ._check_post(store, joined, ref, (got[0], got[1], got[2], got[3], float(got[4])), "%s %s model %s" % (min_len, args["join"], which))
+            else:
+                TSJ._check_samples(off, joined, ref, got[0], min_len)
+            print("%s %d: busy-stream checks on the anchor's fresh context: %s" % (decoder, ordinal, _busy_counts(side.busy)))
+        finally:
+            side.close()
+
+
 # ---- d. mixed orders ----------------------------------------------------------------------------------------------------------------
 def _mixed_scenario(side, seed, generation=1):
     """One sequence of tests/stream_sequences.py on a context; after every getter, the same getter on a FRESH context that ran only the last
     pass (with the switches as they stood then, and as they stand now for the getter).  At the end every decoder's stored results are
     read again: they are what that decoder returned at its last call in the sequence (hf_viterbi_minlen and hf_viterbi_minlen_joined
-    share their state: what the later of the two returned).  In generation 3 the decoders' arguments change from call to call
+    share their state: what the later of the two returned; so do the two pairs of generation 4, and after the posterior's the chunk
+    entries are checked as well: _check_mass_entries).  From generation 3 on the decoders' arguments change from call to call
     (stream_sequences.decoder_arguments), and after every decoder call the same call runs on a fresh context that has run nothing
     else: bitwise the same results and codes, whatever the context's buffers held from wider calls or the other entry point."""
     name = side.name
@@ -857,7 +1027,7 @@ def _mixed_scenario(side, seed, generation=1):
         if key not in fresh_decoders:
             f = side.context()
             before = collections.Counter(side.busy)
-            fresh_decoders[key] = side.decoder(f, op, models[which], None, args, SQ.BUFFERS.get(op, ()))      # (a first call grows every buffer)
+            fresh_decoders[key] = side.decoder(f, op, models[which], None, args, _first_call_grows(op))      # (a first call grows every buffer)
             fresh_busy.update(side.busy - before)             # (counted apart from the sequence's own calls)
             side.busy = before
             f.close()
@@ -880,10 +1050,10 @@ def _mixed_scenario(side, seed, generation=1):
                 em.set_stats_mode(base_mode if st["flipped"] else other_mode)
         elif op in ("alpha_on", "alpha_off"):
             rec[tag] = [_call(em.set_alpha_stats, op == "alpha_on")]
-        elif op in SQ.DECODERS + SQ.MINLEN_DECODERS:
+        elif op in SQ.ALL_DECODERS:
             which = "pass_b" if last_model == "pass_a" else "pass_a"                             # parameters other than the last pass's
             rec[tag] = [side.decoder(em, op, models[which], None, args, grows)]
-            last_decoded["viterbi_minlen" if op in SQ.SHARED_STATE else op] = (tag, op, args)    # one record for the shared state: the later call
+            last_decoded[STATE_READER.get(op, op)] = (tag, op, args)                             # one record per shared state: the later call
             if generation >= 3 and side.stream:                                                   # (once: the twin equals this side)
                 _equal(rec[tag], [fresh_decoder(op, which, args)], "%s %s against a fresh context" % (tag, args))
                 assert _codes(rec[tag]) == [N.HF_OK], (tag, args, _codes(rec[tag]))
@@ -906,8 +1076,10 @@ def _mixed_scenario(side, seed, generation=1):
         _stored_equals(rec["stored " + key][0], rec[tag][0], "the stored results of %s at the end" % tag)
         if key == "viterbi_minlen":                          # the shared state answers to both getters' contracts, for the later call
             _check_chunk_entries(side.store, rec["stored " + key][0][1][1], op, args)
+        if key == "minlen_posterior":
+            _check_mass_entries(side.store, rec["stored " + key][0][1][2], rec["stored " + key][0][1][3], op, args)
     if generation >= 3 and side.stream:
-        calls = collections.Counter(op for op in ops if op in SQ.DECODERS + SQ.MINLEN_DECODERS)
+        calls = collections.Counter(op for op in ops if op in SQ.ALL_DECODERS)
         assert compared == calls, (compared, calls)
         print("%s %s seed %d: decoder calls compared with a fresh context: %s; %d fresh contexts" % (name, side.kind, seed, dict(compared), len(fresh_decoders)))
         print("%s %s seed %d: busy-stream checks in the sequence: %s" % (name, side.kind, seed, _busy_counts(side.busy)))
@@ -931,6 +1103,26 @@ def _check_chunk_entries(store, chunk_ll, op, args):
     assert np.all(chunk_ll[first & (T > 0)] != 0.0), (op, args)
 
 
+def _check_mass_entries(store, log_mass, log_z_adm, op, args):
+    """_check_chunk_entries' twin for hf_get_minlen_chunk_log_mass, the two arrays the posterior's shared state holds after a call of
+    `op`: hf_minlen_posterior_joined leaves a group's values in the entry of its first chunk and exactly 0.0, without a sign bit, in
+    the entries of the group's other chunks, in both arrays; hf_minlen_posterior leaves its values in the entry of every chunk, a
+    chunk being a group of its own.  log Z_adm is not 0.0 wherever the group has windows (the log-probability of the data under the
+    rule), so a per-chunk call leaves no entry of a chunk with windows at 0.0.  log_mass makes no such claim: it IS exactly 0.0 where
+    the rule excludes nothing (one or two windows: a run that touches an end of the group is exempt) or less than half an ulp of Z
+    (config2 under (61, 1, 1, 1): chunks without an Err window worth 1e-16 of their mass), and with all four lengths 1 it is exactly
+    0.0 in every entry, the header's exact case; its entries are compared bitwise with a fresh context's instead."""
+    goff, gf, _ = minlen_joined_ref.group_offsets(store.chunk_off, SQ.join_vector(args["join"], store.n_chunks) if op == "minlen_posterior_joined" else None)
+    size = np.diff(goff)
+    inner = np.ones(store.n_chunks, bool)
+    inner[gf] = False
+    for x in (log_mass, log_z_adm):
+        assert np.all(x[inner] == 0.0) and not np.signbit(x[inner]).any(), (op, args)
+    assert np.all(log_z_adm[gf[size > 0]] != 0.0), (op, args)
+    if max(args["min_len"]) == 1:
+        assert np.all(log_mass == 0.0) and not np.signbit(log_mass).any(), (op, args)
+
+
 def _mixed_cases(generation, tag):
     seeds = SQ.GENERATIONS[generation][3]
     return [pytest.param("config2", k, generation, s, id="config2-%s-%sseed%d" % (k, tag, s)) for k in KINDS for s in seeds] + \
@@ -939,8 +1131,9 @@ def _mixed_cases(generation, tag):
 
 
 # generation 1: the ten getters and two decoders its seeds were chosen with; generation 2: all thirteen getters and three decoders;
-# generation 3: the thirteen getters and all six decoders, the decoders' arguments changing from call to call
-MIXED = _mixed_cases(1, "") + _mixed_cases(2, "gen2-") + _mixed_cases(3, "gen3-")
+# generation 3: the thirteen getters and six decoders, the decoders' arguments changing from call to call; generation 4: all eight
+# decoders, the two whole-contig entry points of the posterior and the sampler in the states of the per-chunk ones
+MIXED = _mixed_cases(1, "") + _mixed_cases(2, "gen2-") + _mixed_cases(3, "gen3-") + _mixed_cases(4, "gen4-")
 
 
 @pytest.mark.parametrize("name,kind,generation,seed", MIXED)
