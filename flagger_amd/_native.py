@@ -146,6 +146,7 @@ def lib() -> C.CDLL:
     sig("hf_sample_paths_minlen", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), i64, C.c_int, C.c_uint64, vp)
     sig("hf_sample_paths_minlen_joined", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), i64, C.c_int,
         C.c_uint64, vp)
+    sig("hf_get_mea_labels", C.c_int, vp, pd, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int8), pd, pd)
     sig("hf_sample_minlen_finish", C.c_int, vp, vp)
     sig("hf_get_minlen_sample_labels", C.c_int, vp, C.c_int, C.POINTER(C.c_int8))
     sig("hf_sample_capacity", C.c_int, vp)

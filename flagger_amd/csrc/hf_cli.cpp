@@ -53,7 +53,8 @@ static double peak_rss_gb() { struct rusage r; getrusage(RUSAGE_SELF, &r); retur
 enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
-    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks
+    kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks,
+    kOptExpectedAccuracy, kOptExpectedGains
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -97,6 +98,8 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"admissibleSamples", required_argument, nullptr, kOptAdmissibleSamples},    // N paths drawn from the posterior UNDER --minimumLengths (hf_sample_paths_minlen; nothing else starts with --ad)
     {"wholeContigs", no_argument, nullptr, kOptWholeContigs},             // --enforceMinimumLengths over the joined chunks of a contig (hf_viterbi_minlen_joined; nothing else starts with --wh, --w was ambiguous already; not `j...`: --j stays --jointEntropy)
     {"mergedChunks", no_argument, nullptr, kOptMergedChunks},             // --constrainedPosterior and --admissibleSamples over the joined chunks of a contig (hf_minlen_posterior_joined, hf_sample_paths_minlen_joined; nothing else starts with --me, --m was ambiguous already)
+    {"expectedAccuracy", required_argument, nullptr, kOptExpectedAccuracy},   // final labels by maximum expected accuracy UNDER --minimumLengths, chunks | contigs (hf_get_mea_labels; both new names start with --exp: --ex was ambiguous already, --e and --ex stay --exchange)
+    {"expectedGains", required_argument, nullptr, kOptExpectedGains},         // its 4x4 gain matrix [identity]
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -216,7 +219,19 @@ static void usage(const char* program) {
             "                                      rule of --numBlocks and --wholeContigs), a run counts across their boundary, and only runs at the\n"
             "                                      ends of such a group are exempt; the files keep their names and formats, admissible_mass.tsv gains\n"
             "                                      one column, log_mass_per_chunk_rule (the mass under the per-chunk rule); it does not touch\n"
-            "                                      --viterbi; one GPU, not with --gpus N>1 or --sweepAlpha\n");
+            "                                      --viterbi; one GPU, not with --gpus N>1 or --sweepAlpha\n"
+            "         --expectedAccuracy chunks|contigs   the final labels (final BED, final summary tables) are the labelling of the LARGEST\n"
+            "                                      EXPECTED NUMBER OF CORRECTLY LABELLED WINDOWS under the posterior of the final pass AMONG THE\n"
+            "                                      LABELLINGS WHOSE RUNS MEET --minimumLengths (lengths in windows as for --enforceMinimumLengths, at\n"
+            "                                      most 64 windows in sum): the exact form of what the final BED approximates by relabelling short\n"
+            "                                      runs of the posterior argmax.  chunks: runs at a chunk's ends are exempt; contigs: the lengths\n"
+            "                                      hold over the joined chunks of a contig.  Writes expected_accuracy.tsv (per contig and for the\n"
+            "                                      track: windows, the unconstrained bound, the gain of the final BED's own rule, the gain decoded,\n"
+            "                                      whether the final BED's own labelling has positive probability); every other file is the run's\n"
+            "                                      without the option.  Needs --minimumLengths; not with --viterbi; one GPU, not with --gpus N>1,\n"
+            "                                      HF_LOOPBACK_RANKS or --sweepAlpha\n"
+            "         --expectedGains FILE         with --expectedAccuracy: a 4x4 tab-separated gain matrix, rows the true label, columns the label\n"
+            "                                      called (Err, Dup, Hap, Col); the labelling of the largest expected gain is decoded [identity]\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -243,6 +258,7 @@ struct Options {
     bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
     int admissibleSamples = 0; bool admissibleSet = false;
+    const char *expectedAccuracy = nullptr, *expectedGainsPath = nullptr;   // chunks | contigs; the gain TSV
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
@@ -270,6 +286,7 @@ struct Run {
     std::vector<std::string> sweepPaths;                       // --sweepAlpha: the TSVs of the list and what they hold
     std::vector<std::vector<double>> sweepAlphas;
     double alpha[16] = {0};                                    // --alphaTsv
+    double gains[16] = {1, 0, 0, 0,  0, 1, 0, 0,  0, 0, 1, 0,  0, 0, 0, 1};   // --expectedGains [truth * 4 + called]
     int32_t minLenWindows[4] = {1, 1, 1, 1};                   // --minimumLengths in windows (min_len_windows)
     hf_windows w{};                                            // the table's windows, once the input is read (load_input)
     int64_t N = 0; int nChunks = 0;
@@ -1163,7 +1180,8 @@ static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
     {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}, {kOptMergedChunks, &Options::mergedChunks}};
 static const struct { int code; const char* Options::*text; } kTextOptions[] = {
     {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
-    {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath}};
+    {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath},
+    {kOptExpectedAccuracy, &Options::expectedAccuracy}, {kOptExpectedGains, &Options::expectedGainsPath}};
 static const struct { int code; int Options::*number; } kIntOptions[] = {
     {'n', &Options::numberOfIterations}, {'p', &Options::numberOfCollapsedComps}, {'@', &Options::threads}, {'C', &Options::chunkLen}, {'W', &Options::windowLen},
     {kOptDevice, &Options::device}, {kOptGpus, &Options::nGpus}};
@@ -1319,16 +1337,43 @@ static bool min_len_windows(Run& s, int W) {
                     ts(), o.minLenPerState[0], o.minLenPerState[1], o.minLenPerState[3], mw[0], mw[1], mw[2], mw[3], W, HF_LONGRUN_MAX_LANES - 6);
             return false;
         }
-    if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet) || sum <= HF_MINLEN_MAX_LANES) return true;
+    if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet || o.expectedAccuracy) || sum <= HF_MINLEN_MAX_LANES) return true;
     std::string who;                                           // the options that walk the expanded chain, as given
     for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
-                          o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr})
+                          o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr, o.expectedAccuracy ? "expectedAccuracy" : nullptr})
         if (n) who += (who.empty() ? "" : ", --") + std::string(n);
     fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
             ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
     return false;
 }
-static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet; }
+static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet || o.expectedAccuracy; }
+
+// --expectedGains: four lines of four tab-separated numbers, rows the true label, columns the label called, read line by line and
+// token by token as the alpha TSV is; unlike an alpha a gain may be any finite number up to 1e100 in magnitude.  false: not such a file
+static bool read_gains_tsv(const char* path, double gains[16]) {
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    char* line = nullptr; size_t cap = 0;
+    int rows = 0;
+    bool ok = true;
+    while (ok && getline(&line, &cap, f) != -1) {
+        size_t L = strlen(line);
+        while (L > 0 && (line[L - 1] == '\n' || line[L - 1] == '\r')) line[--L] = '\0';
+        if (L == 0) continue;                                  // (an empty line, e.g. behind the last row)
+        int j = 0; char* save = nullptr;
+        for (char* tok = strtok_r(line, "\t", &save); tok && ok; tok = strtok_r(nullptr, "\t", &save)) {
+            char* end = nullptr;
+            const double v = strtod(tok, &end);
+            ok = rows < 4 && j < 4 && end != tok && *end == '\0' && std::fabs(v) <= 1e100;   // (a NaN fails the comparison)
+            if (ok) gains[rows * 4 + j++] = v;
+        }
+        ok = ok && j == 4;
+        rows++;
+    }
+    free(line);
+    fclose(f);
+    return ok && rows == 4;
+}
 
 // Everything that can be refused before the input is read, in a fixed order (tests/test_cli_refusals_cpu.py: of two bad options the one
 // checked first is reported).  false: refused (said).  Fills in the session: regions, sweep list, alpha, and the options the preset decides.
@@ -1366,9 +1411,17 @@ static bool check_options(Run& s) {
         {o.mergedChunks ? "--constrainedPosterior --mergedChunks" : "--constrainedPosterior", o.constrainedPost, needsMinLen, kOneGpuNoLoopback},
         {o.mergedChunks ? "--admissibleSamples --mergedChunks" : "--admissibleSamples", o.admissibleSet, o.admissibleSamples < 1 ? positive : needsMinLen, kOneGpuNoLoopback},
         {"--mergedChunks", o.mergedChunks, o.constrainedPost || o.admissibleSet ? nullptr : "needs --constrainedPosterior or --admissibleSamples", kOneGpuNoLoopback},
+        {"--expectedAccuracy", o.expectedAccuracy != nullptr,
+         o.expectedAccuracy && strcmp(o.expectedAccuracy, "chunks") != 0 && strcmp(o.expectedAccuracy, "contigs") != 0 ? "can be chunks or contigs" : needsMinLen, kNoGpuRule},
+        {"--expectedAccuracy", o.expectedAccuracy != nullptr, o.viterbi ? "cannot be combined with --viterbi" : nullptr, kOneGpuNoLoopback},
+        {"--expectedGains", o.expectedGainsPath != nullptr, o.expectedAccuracy ? nullptr : "needs --expectedAccuracy", kNoGpuRule},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
+    if (o.expectedGainsPath && !read_gains_tsv(o.expectedGainsPath, s.gains)) {
+        fprintf(stderr, "[%s] Error: --expectedGains: %s is not a file of 4x4 tab-separated finite numbers.\n", ts(), o.expectedGainsPath);
+        return false;
+    }
     if (!o.inputPath) { fprintf(stderr, "[%s] Error: Input path cannot be NULL.\n", ts()); return false; }
     if (o.convergenceTol <= 0.0 || o.convergenceTol > 1.0) { fprintf(stderr, "[%s] Error: convergence tol = %2.f should be between 0 and 1.\n", ts(), o.convergenceTol); return false; }
     if (!o.outputDir) { fprintf(stderr, "[%s] Error: --outputDir, -o should be specified.\n", ts()); return false; }
@@ -1548,7 +1601,7 @@ struct EmRun {
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
     double emStart = 0.0, emTime = 0.0, emWall = 0.0;
     std::vector<double> passMs;                             // HF_CLI_TIMING: every E-step of the loop
-    std::vector<int8_t> labels, vlabels;                    // of the final pass; of --viterbi
+    std::vector<int8_t> labels, vlabels;                    // of the final pass; of --viterbi or --expectedAccuracy
     const int8_t* finalLabels = nullptr;                    // the one of the two that the final BED and tables take
     int die(int r) { res.status = r; return die_estep(r); }
 };
@@ -1664,7 +1717,91 @@ static long long short_inner_runs(const hf_windows& w, const std::vector<uint8_t
     return count;
 }
 
-// 5b. the final inference: the last pass, its labels, --viterbi and --enforceMinimumLengths with the cost file
+// --expectedAccuracy chunks|contigs: the labelling of the largest expected gain under --minimumLengths (hf_get_mea_labels) into
+// `decoded`, and expected_accuracy.tsv: per contig (in the order of first appearance) and for the track (the sum of the contig rows, in
+// row order) the windows, the unconstrained bound sum_t max_k g_t(k), the gain of the labels the final BED would carry without the
+// option (`argmax`, the labels of the final pass, with every run, merged over the joined chunks of a contig, shorter than its length in
+// windows turned to Hap), the gain decoded, and whether the final BED's own labelling is supported: every chunk's part of it has
+// positive probability (hf_get_path_log_probs).  g_t(k) on the host: hf_get_posterior's gamma and the getter's order of additions.
+static int expected_accuracy(Run& s, const int8_t* argmax, std::vector<int8_t>& decoded, const std::string& dir) {
+    const Options& o = s.opt;
+    const int64_t N = s.N;
+    const int C = s.w.n_chunks;
+    const int64_t* const off = s.w.chunk_off;
+    const int32_t* const mw = s.minLenWindows;
+    const double* const W = s.gains;
+    const std::vector<uint8_t> joined = joined_chunks(s.tab);
+    decoded.assign((size_t) N, -1);
+    std::vector<double> block((size_t) C, 0.0), post((size_t) N * 4);
+    double total = 0.0;
+    int rc = hf_get_mea_labels(s.ctx, o.expectedGainsPath ? W : nullptr, mw, strcmp(o.expectedAccuracy, "contigs") == 0 ? joined.data() : nullptr,
+                               decoded.data(), block.data(), &total);
+    if (rc != HF_OK) return rc;
+    if ((rc = s.posterior(0, N, post.data())) != HF_OK) return rc;
+    // the final BED's own rule, in windows
+    std::vector<int8_t> rule(argmax, argmax + N);
+    for (int c0 = 0; c0 < C;) {
+        int c1 = c0 + 1;
+        while (c1 < C && joined[(size_t) c1] && off[c1 + 1] > off[c1] && off[c1] > off[c1 - 1]) c1++;
+        for (int64_t a = off[c0]; a < off[c1];) {
+            int64_t b = a;
+            while (b + 1 < off[c1] && argmax[b + 1] == argmax[a]) b++;
+            if (argmax[a] >= 0 && argmax[a] < 4 && b - a + 1 < mw[argmax[a]])
+                for (int64_t t = a; t <= b; t++) rule[(size_t) t] = 2;
+            a = b + 1;
+        }
+        c0 = c1;
+    }
+    std::vector<int64_t> first, last;
+    std::vector<int> jobChunk;
+    for (int c = 0; c < C; c++)
+        if (off[c + 1] > off[c]) { first.push_back(off[c]); last.push_back(off[c + 1] - 1); jobChunk.push_back(c); }
+    std::vector<double> lp(first.size());
+    if ((rc = hf_get_path_log_probs(s.ctx, (int64_t) first.size(), first.data(), last.data(), rule.data(), lp.data())) != HF_OK) return rc;
+    std::vector<char> chunkSupported((size_t) C, 1);
+    for (size_t j = 0; j < lp.size(); j++) chunkSupported[(size_t) jobChunk[j]] = lp[j] > -HUGE_VAL;
+    struct Row { std::string scope; long long windows = 0; double argmaxGain = 0.0, ruleGain = 0.0, decodedGain = 0.0; bool supported = true; };
+    std::vector<Row> rows;
+    std::map<std::string, size_t> rowOf;
+    for (int c = 0; c < C; c++) {
+        const std::string ctg = hfio_chunk_ctg(s.tab, c);
+        auto it = rowOf.find(ctg);
+        if (it == rowOf.end()) { it = rowOf.emplace(ctg, rows.size()).first; rows.push_back(Row{}); rows.back().scope = ctg; }
+        Row& r = rows[it->second];
+        r.windows += off[c + 1] - off[c];
+        r.decodedGain += block[(size_t) c];
+        r.supported = r.supported && chunkSupported[(size_t) c];
+        for (int64_t t = off[c]; t < off[c + 1]; t++) {
+            const double* g = &post[(size_t) t * 4];
+            double best = -HUGE_VAL;
+            for (int k = 0; k < 4; k++) {
+                const double gk = ((g[0] * W[k] + g[1] * W[4 + k]) + g[2] * W[8 + k]) + g[3] * W[12 + k];
+                if (gk > best) best = gk;
+                if (k == rule[(size_t) t]) r.ruleGain += gk;
+            }
+            r.argmaxGain += best;
+        }
+    }
+    Row track;
+    track.scope = "track";
+    for (const Row& r : rows) {
+        track.windows += r.windows; track.argmaxGain += r.argmaxGain; track.ruleGain += r.ruleGain; track.decodedGain += r.decodedGain;
+        track.supported = track.supported && r.supported;
+    }
+    rows.push_back(track);
+    const std::string tp = dir + "/expected_accuracy.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\twindows\tgain_argmax\tgain_final_bed_rule\tgain_decoded\tfinal_bed_rule_supported\n");
+    for (const Row& r : rows)
+        fprintf(f, "%s\t%lld\t%.17g\t%.17g\t%.17g\t%d\n", r.scope.c_str(), r.windows, r.argmaxGain, r.ruleGain, r.decodedGain, r.supported ? 1 : 0);
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows (%s): expected gain %.6f (unconstrained bound %.6f, the final BED's own rule %.6f)\n",
+            ts(), mw[0], mw[1], mw[2], mw[3], o.expectedAccuracy, track.decodedGain, track.argmaxGain, track.ruleGain);
+    return HF_OK;
+}
+
+// 5b. the final inference: the last pass, its labels, --expectedAccuracy with its table, --viterbi and --enforceMinimumLengths with the cost file
 static int final_inference(Run& s, EmRun& em) {
     const Options& o = s.opt;
     const std::string& dir = em.dir;
@@ -1691,6 +1828,14 @@ static int final_inference(Run& s, EmRun& em) {
     em.labels.resize((size_t) N);
     if ((rc = s.labels(em.labels.data())) != HF_OK) return em.die(rc);
     em.finalLabels = em.labels.data();
+    // --expectedAccuracy: the final BED and the final tables take the labelling of the largest expected gain under --minimumLengths
+    if (o.expectedAccuracy) {
+        if (!has_single_gpu_context(s, "--expectedAccuracy needs")) return EXIT_FAILURE;
+        fprintf(stderr, "[%s] [Final Inference] Maximum expected accuracy under the minimum run lengths (%s) ...\n", ts(), o.expectedAccuracy);
+        if ((rc = expected_accuracy(s, em.labels.data(), em.vlabels, dir)) != HF_OK) return em.die(rc);
+        em.finalLabels = em.vlabels.data();
+        return 0;
+    }
     // --viterbi: the final BED and the final tables take the most probable path under the final parameters; everything else
     // (the posterior BED of -P among it) keeps the posterior labels of the final pass
     if (!o.viterbi) return 0;

@@ -499,6 +499,21 @@ struct MinLenSampler : Decoder, SampleSet {
     void release() { grp.release(); fwd.release(); samples.release(); Decoder::release(); }
 };
 
+// maximum-expected-accuracy decoding under minimum run lengths (hf_mea.h): a getter of the last full pass with a state of its own, the
+// slab allocated by its first call: gain rows, backpointer words, labels, block scores, final lanes, the unit-end parameter block and
+// the flag word; the group-as-chunk offsets of a call (mlg_cut) in a buffer beside it
+struct MeaDecoder {
+    Slab slab;
+    bool alloc = false;
+    double2* d_rows = nullptr;                 // [N][8] window order, k_mlv_rows' layout
+    uint16_t* d_bp = nullptr; int8_t* d_label = nullptr;
+    double* d_score = nullptr; uint8_t* d_final = nullptr;     // [C] per block
+    DevParams* d_params = nullptr;             // trans[s][4] = 1.0 in every region, 0 elsewhere: the walks' end column of zeros
+    unsigned* d_flags = nullptr;
+    DevBuf grp; std::vector<int64_t> h_grp;
+    void release() { grp.release(); slab.release(); alloc = false; }
+};
+
 // the alpha statistics (hf_alpha.h): the switch, the plan of the pairs (built by the first call) and buffers of their own
 struct AlphaStats {
     bool on = false;          // hf_set_alpha_stats
@@ -531,6 +546,7 @@ struct hf_ctx {
     DevBuf en, en_lab;        // hf_entropy.h: pieces, parts, piece sums, results / the profile's two arrays; the labels of a call
     DevBuf bp;                // hf_breakpoint.h: pieces, parts, piece products, the chain's vectors, the windows' weights, results
     DevBuf lr;                // hf_longrun.h: parts, groups, results
+    MeaDecoder mea;           // hf_mea.h: hf_get_mea_labels
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1053,6 +1069,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->en_lab.release();
     ctx->bp.release();
     ctx->lr.release();
+    ctx->mea.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -3430,6 +3447,11 @@ int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
 }
 
 
+// k_mea_rows, the one kernel of hf_get_mea_labels (its host side stands behind mlg_cut below).  Here, in front of
+// hf_minlen_post_joined.h, no other kernel's code moves.
+#include "hf_mea.h"
+
+
 // ------------------------------------------------------------------------------------------
 // the posterior and the sampler over groups of joined chunks (hf_minlen_post_joined.h): hf_minlen_posterior_joined shares ctx->mlp, its
 // finish and its getters with hf_minlen_posterior (mlp_run above), hf_sample_paths_minlen_joined shares ctx->mls with
@@ -3504,6 +3526,93 @@ int hf_sample_paths_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t
                            v.d_words, v.d_final, K, Kp, v.d_label);
         return (int) HF_OK;
     });
+}
+
+
+// ------------------------------------------------------------------------------------------
+// maximum-expected-accuracy decoding under minimum run lengths (hf_mea.h): a getter of the last full pass, synchronous on the pass's
+// stream as the range getters are.  k_mea_rows turns the pass's posterior into gain rows; k_mlv_fwd and k_mlv_back walk them as they
+// are, over the chunk offsets or mlg_cut's group-as-chunk offsets, with the getter's unit-end parameter block.  Buffers of its own
+// (ctx->mea): the last pass, every decoder's and sampler's results and the next hf_estep stay as they are.
+// ------------------------------------------------------------------------------------------
+int hf_get_mea_labels(hf_ctx* ctx, const double* gain, const int32_t min_len[4], const uint8_t* joined, int8_t* labels_host,
+                      double* block_gain_host, double* total_gain_host) {
+    const std::string who = "hf_get_mea_labels";
+    if (!ctx || !min_len) return set_err(HF_E_ARG, who + ": bad argument");
+    if (!labels_host) return set_err(HF_E_ARG, who + ": NULL label array");
+    int64_t lanes = 0;
+    int rc = minlen_check(who, min_len, &lanes);
+    if (rc || (rc = mlg_refuse(ctx, joined, who))) return rc;
+    MeaGain W;
+    for (int o = 0; o < 16; o++) {
+        W.w[o] = gain ? gain[o] : ((o >> 2) == (o & 3) ? 1.0 : 0.0);
+        if (!(std::fabs(W.w[o]) <= 1e100)) return set_err(HF_E_ARG, who + ": every gain must be finite and at most 1e100 in magnitude");
+    }
+    if (!ctx->pass.have_full)
+        return set_err(HF_E_ARG, who + ": no HF_MODE_FULL pass to answer for (none yet, or the last pass was forward-only)");
+    const Track& tr = ctx->tr;
+    MeaDecoder& m = ctx->mea;
+    PassView pv;
+    rc = pass_view(ctx, who, dec_work(tr) ? 1 : 0, pv);
+    if (rc) return rc;
+    hipStream_t st = ctx->pass.last_stream;
+    if (block_gain_host) for (int64_t c = 0; c < tr.C; c++) block_gain_host[c] = 0.0;
+    if (total_gain_host) *total_gain_host = 0.0;
+    if (!dec_work(tr)) {
+        if (tr.N > 0) std::memset(labels_host, 0xff, (size_t) tr.N);
+        return HF_OK;
+    }
+    if (!m.alloc) {
+        const size_t sizes[7] = {(size_t) tr.N * 128, (size_t) tr.N * 2, (size_t) tr.N, (size_t) tr.C * 8, (size_t) tr.C, tr.params_bytes, 4};
+        size_t total = 0;
+        for (size_t b : sizes) total += Slab::granule(b);
+        m.slab.first = total;
+        void* ptr[7];
+        for (int i = 0; i < 7; i++)
+            if (!(ptr[i] = m.slab.alloc(sizes[i]))) { m.slab.release(); return set_err(HF_E_HIP, who + ": out of device memory"); }
+        m.d_rows = static_cast<double2*>(ptr[0]); m.d_bp = static_cast<uint16_t*>(ptr[1]); m.d_label = static_cast<int8_t*>(ptr[2]);
+        m.d_score = static_cast<double*>(ptr[3]); m.d_final = static_cast<uint8_t*>(ptr[4]); m.d_params = static_cast<DevParams*>(ptr[5]);
+        m.d_flags = static_cast<unsigned*>(ptr[6]);
+        // the unit-end parameter block: all zero but trans[s][4] = 1.0 of every region (k_mlv_fwd reads nothing else of it)
+        std::vector<double> img(tr.params_bytes / 8, 0.0);
+        DevParams* hp = reinterpret_cast<DevParams*>(img.data());
+        hp->n_regions = tr.R;
+        for (int r = 0; r < tr.R; r++)
+            for (int s = 0; s < 4; s++) hp->reg[r].trans[s][4] = 1.0;
+        HIPCHK(hipMemcpy(m.d_params, img.data(), tr.params_bytes, hipMemcpyHostToDevice));
+        m.alloc = true;
+    }
+    HIPCHK(hipMemsetAsync(m.d_flags, 0, 4, st));
+    if (!all_in_chunks(tr)) HIPCHK(hipMemsetAsync(m.d_label, 0xff, (size_t) tr.N, st));   // (windows outside every chunk: label -1)
+    const int64_t* d_boff = tr.d_off;                   // the window ranges of the walks' blocks: chunks, or groups as chunks
+    if (joined) {
+        int nb = 0;
+        if ((rc = mlg_cut(tr, joined, m.grp, m.h_grp, st, who, &nb))) return rc;
+        d_boff = reinterpret_cast<const int64_t*>(m.grp.d_buf);
+    }
+    const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+    by_algo(tr, [&](auto S) {
+        constexpr bool SEQ = decltype(S)::value;
+        hipLaunchKernelGGL(k_mea_rows<SEQ>, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, (int) tr.C, tr.d_off, pv, W, m.d_rows,
+                           m.d_flags);
+    });
+    hipLaunchKernelGGL(k_mlv_fwd, dim3((unsigned) tr.C), dim3(64), 0, st, d_boff, tr.d_rec, m.d_params, m.d_rows, l0, l1, l2, l3, m.d_bp, m.d_final,
+                       m.d_score, m.d_flags);
+    hipLaunchKernelGGL(k_mlv_back, dim3((unsigned) tr.C), dim3(64), 0, st, d_boff, l0, l1, l2, l3, m.d_bp, m.d_final, m.d_label);
+    HIPCHK(hipGetLastError());
+    unsigned fl = 0;
+    std::vector<double> score((size_t) tr.C);
+    HIPCHK(hipMemcpyAsync(&fl, m.d_flags, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(score.data(), m.d_score, (size_t) tr.C * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(labels_host, m.d_label, (size_t) tr.N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (fl & HF_FLAG_NAN) return set_err(HF_E_NAN, who + ": a NaN in a gain row");
+    if (fl & HF_FLAG_SCALE) return set_err(HF_E_SCALE, who + ": a block has no admissible supported labelling");
+    double tot = 0.0;
+    for (int64_t c = 0; c < tr.C; c++) tot += score[(size_t) c];          // chunk-list order
+    if (block_gain_host) std::memcpy(block_gain_host, score.data(), (size_t) tr.C * 8);
+    if (total_gain_host) *total_gain_host = tot;
+    return HF_OK;
 }
 
 

@@ -619,6 +619,30 @@ class EMList:
         N.check(self._L.hf_get_minlen_chunk_log_mass(self._h, _dptr(mass), _dptr(lza)), "hf_get_minlen_chunk_log_mass")
         return MinLenPosterior(self, labels, mass, lza, float(tot.value))
 
+    def mea_labels(self, min_len=(1, 1, 1, 1), joined=None, gain=None):
+        """Maximum-expected-accuracy decoding under minimum run lengths (hf_get_mea_labels): among the labellings whose runs have at
+        least min_len[s] windows (runs at a chunk's ends exempt), the one with the largest expected gain under the posterior of the
+        last full pass: (labels, block_gain, total_gain).  gain: None for the identity (the expected number of correctly labelled
+        windows), or a 4x4 matrix, gain[s][k] the gain of calling k when the truth is s.  joined: None, or a bool array of n_chunks
+        as for viterbi_minlen: the rule then holds over every group of joined chunks, and block_gain holds a group's score in the
+        entry of its first chunk and 0.0 in the others.  The last pass's results and every decoder's are left as they were."""
+        ml = self._four_lengths("mea_labels", min_len)
+        jn = None if joined is None else self._joined_u8("mea_labels", joined)
+        gp = None
+        if gain is not None:
+            g = np.asarray(gain, dtype=np.float64)
+            if g.shape != (4, 4):
+                raise ValueError("mea_labels: gain is a 4x4 matrix (rows: true label, columns: called label)")
+            g = np.ascontiguousarray(g)
+            gp = _dptr(g)
+        labels = np.empty(self.store.n_windows, dtype=np.int8)
+        block = np.empty(self.store.n_chunks, dtype=np.float64)
+        tot = C.c_double(0.0)
+        N.check(self._L.hf_get_mea_labels(self._h, gp, ml.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          labels.ctypes.data_as(C.POINTER(C.c_int8)), _dptr(block), C.byref(tot)), "hf_get_mea_labels")
+        return labels, block, float(tot.value)
+
     @property
     def sample_capacity(self) -> int:
         """Samples one hf_sample_paths call may draw (nine tenths of the free device memory; hf_sample_capacity)."""
@@ -970,6 +994,17 @@ def EM_runMinLengthPosteriorForList(emList, model: HMM, min_len, joined=None) ->
     if joined is None:
         return emList.minlen_posterior(model, min_len)
     return emList.minlen_posterior(model, min_len, joined)
+
+
+def EM_getMaxExpectedGainLabelsForList(emList, min_len, joined=None, gain=None):
+    """Maximum-expected-accuracy decoding under minimum run lengths (the exact form of what the reference's final BED approximates by
+    relabelling short runs of the posterior argmax): among the labellings whose runs of state s have at least min_len[s] windows, the
+    one with the largest expected gain under the posterior of the last full pass; gain None counts correctly labelled windows.
+    Returns (labels: int8[n_windows], block_gain: float64[n_chunks], total_gain: float).  joined[c] says that chunk c continues chunk
+    c - 1 (joined_chunks): the rule then holds over whole groups of joined chunks.  `emList`: an EMList."""
+    if not hasattr(emList, "mea_labels"):
+        raise TypeError("EM_getMaxExpectedGainLabelsForList: %s has no maximum-expected-accuracy decoder" % type(emList).__name__)
+    return emList.mea_labels(min_len, joined, gain)
 
 
 def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:

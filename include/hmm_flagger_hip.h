@@ -669,6 +669,45 @@ int hf_sample_paths_minlen_joined(hf_ctx *ctx, const hf_params *p, const int32_t
                                   const uint8_t *joined /* [n_chunks], NULL: none */,
                                   int64_t first_sample, int n_samples, uint64_t seed, void *stream);
 
+/* Maximum-expected-accuracy decoding under minimum run lengths (flagger_amd/csrc/hf_mea.h): to posterior argmax what hf_viterbi_minlen
+ * is to hf_viterbi.  Among the labellings whose runs meet the minimum lengths, the one with the largest expected gain under the
+ * posterior of the last HF_MODE_FULL pass; with the identity gain, the largest expected number of correctly labelled windows.  A getter
+ * of that pass, as hf_get_interval_log_probs is: no parameters, synchronous on the pass's stream.
+ * Posterior and gains.  For a window t of a chunk, with f_t, b_t of the pass (hf_get_forward_backward):
+ *   p_s        = f_t[s] * b_t[s]
+ *   gamma_t(s) = p_s / (((p_0 + p_1) + p_2) + p_3)                 hf_get_posterior's value to rounding
+ *   g_t(k)     = ((gamma_t(0) W[0][k] + gamma_t(1) W[1][k]) + gamma_t(2) W[2][k]) + gamma_t(3) W[3][k]
+ * gain[s * 4 + k] = W[s][k] is the gain of calling k when the truth is s; NULL means the identity.  The expected gain of a labelling
+ * is the sum over its windows of g_t(l_t).
+ * Blocks.  joined and the groups are exactly those of hf_viterbi_minlen_joined (NULL: none joined; joined[0] != 0 is HF_E_ARG; a chunk
+ * without windows ends a group).  A BLOCK is a chunk (joined NULL) or a group.
+ * ADMISSIBLE: every maximal run of state s in the block's label sequence has at least min_len[s] windows; a run that contains the
+ * block's first or last window is exempt.  The family's rule, lanes and limits: 1 <= min_len[s], sum <= HF_MINLEN_MAX_LANES.
+ * SUPPORTED: the computed gamma_t(l_t) > 0 at every window, and A_t[l_{t-1}][l_t] > 0 at every window that is not the first of its
+ * chunk (A_t: the row of the pass).  A step across a joined chunk boundary carries no condition of its own: the two chains are
+ * independent, and the first condition at the two windows already implies end[p] > 0 and first[k] > 0.  In exact arithmetic, supported
+ * means that every chunk's path has positive probability.
+ * Result.  Per block, the admissible supported labelling with the largest expected gain: the walk of hf_viterbi_minlen in (max, +)
+ * over gain rows in place of log rows and with an end column of zeros.  The rows:
+ *   gk_t(k)   = g_t(k) if gamma_t(k) > 0, else -inf
+ *   G_t[p][k] = gk_t(k)                                 at a chunk-first window (the four rows alike: the first window of a block and a
+ *                                                       joined boundary are served by the same row)
+ *   G_t[p][k] = gk_t(k) if A_t[p][k] > 0, else -inf     at every other window
+ * Entry lanes, in-between lanes, saturated lanes, the exclusion of p == s, strict > with the lowest candidate winning, and the final
+ * lane as the first largest in lane order are hf_viterbi_minlen's, word for word.  A block's score is its maximum;
+ * block_gain_host[c] holds the score of chunk c, or with joined a group's score in the entry of its first chunk and 0.0 in the
+ * others; *total_gain_host is their sum in list order.  A chunk without windows scores 0.0; windows outside every chunk get label -1.
+ * HF_E_SCALE: a block has no admissible supported labelling.  HF_E_NAN: a NaN in a gain row.  HF_E_ARG: no full pass to answer for, the
+ * length cases of hf_viterbi_minlen, joined[0] != 0, a NULL label array, a gain entry that is not finite or above 1e100 in magnitude.
+ * Exact cases: lengths 1 with the identity give posterior argmax wherever the two largest posteriors differ by more than rounding;
+ * a gain scaled by a power of two gives the same labels and scores scaled exactly.  Repeated calls return the same bits; HF_ALGO_SCAN
+ * and HF_ALGO_SEQ contexts agree to rounding only (their f and b differ in the last bit).
+ * Its buffers are its own (allocated by the first call): the last pass, every decoder's and sampler's results and the next hf_estep
+ * are bitwise unaffected.  hf_batch_* and hf_multi_* have no counterpart. */
+int hf_get_mea_labels(hf_ctx *ctx, const double *gain /* [16], NULL: identity */, const int32_t min_len[4],
+                      const uint8_t *joined /* [n_chunks], NULL: none */, int8_t *labels_host /* [n_windows] */,
+                      double *block_gain_host /* [n_chunks] or NULL */, double *total_gain_host /* or NULL */);
+
 /* Posterior path sampling (forward filtering, backward sampling; flagger_amd/csrc/hf_sample.h): with the parameters `p` and the
  * quantities hf_viterbi uses, a sample of a chunk of T windows is a path s_0..s_{T-1} drawn with probability proportional to
  *   first[s_0] * prod_{t>=1} A_t[s_{t-1}][s_t] * end[s_{T-1}]
