@@ -54,7 +54,7 @@ enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
     kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks,
-    kOptExpectedAccuracy, kOptExpectedGains
+    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -100,6 +100,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"mergedChunks", no_argument, nullptr, kOptMergedChunks},             // --constrainedPosterior and --admissibleSamples over the joined chunks of a contig (hf_minlen_posterior_joined, hf_sample_paths_minlen_joined; nothing else starts with --me, --m was ambiguous already)
     {"expectedAccuracy", required_argument, nullptr, kOptExpectedAccuracy},   // final labels by maximum expected accuracy UNDER --minimumLengths, chunks | contigs (hf_get_mea_labels; both new names start with --exp: --ex was ambiguous already, --e and --ex stay --exchange)
     {"expectedGains", required_argument, nullptr, kOptExpectedGains},         // its 4x4 gain matrix [identity]
+    {"lengthConstrainedEM", no_argument, nullptr, kOptLengthConstrainedEM},     // the EM iterations fit UNDER --minimumLengths (hf_estep_minlen; --l stays --labelNames: parse_options' kept[])
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -231,7 +232,14 @@ static void usage(const char* program) {
             "                                      without the option.  Needs --minimumLengths; not with --viterbi; one GPU, not with --gpus N>1,\n"
             "                                      HF_LOOPBACK_RANKS or --sweepAlpha\n"
             "         --expectedGains FILE         with --expectedAccuracy: a 4x4 tab-separated gain matrix, rows the true label, columns the label\n"
-            "                                      called (Err, Dup, Hap, Col); the labelling of the largest expected gain is decoded [identity]\n");
+            "                                      called (Err, Dup, Hap, Col); the labelling of the largest expected gain is decoded [identity]\n"
+            "         --lengthConstrainedEM        with --minimumLengths: the EM iterations take their statistics from the posterior GIVEN THAT EVERY\n"
+            "                                      RUN MEETS --minimumLengths (lengths in windows as for --enforceMinimumLengths, at most 64 in sum;\n"
+            "                                      runs at a chunk's ends are exempt), so the model is fitted for the constrained decoders: the\n"
+            "                                      iteration rows of loglikelihood.tsv hold the objective, the sum of log Z_adm, and\n"
+            "                                      length_constrained_em.tsv per iteration log Z_adm, log Z and their difference; the final inference\n"
+            "                                      pass and every output stay the plain ones.  Not with --accelerate, --fitAlpha or --modelType\n"
+            "                                      negative_binomial; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -255,7 +263,7 @@ struct Options {
     int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0, initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false;
+    bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false, lengthConstrainedEM = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
     int admissibleSamples = 0; bool admissibleSet = false;
     const char *expectedAccuracy = nullptr, *expectedGainsPath = nullptr;   // chunks | contigs; the gain TSV
@@ -340,6 +348,12 @@ struct Run {
         const hf_params p = params(m);
         const int rc = joined ? hf_minlen_posterior_joined(ctx, &p, min_len, joined, nullptr) : hf_minlen_posterior(ctx, &p, min_len, nullptr);
         return rc != HF_OK ? rc : hf_minlen_posterior_finish(ctx, log_mass_total, nullptr);
+    }
+    // the E-step under min_len windows per state (one GPU): the statistics, and the plain sum of log Z of the same parameters
+    int estep_minlen(hfm_model* m, const int32_t min_len[4], double* out, double* log_z) {
+        const hf_params p = params(m);
+        const int rc = hf_estep_minlen(ctx, &p, min_len, nullptr);
+        return rc != HF_OK ? rc : hf_estep_minlen_finish(ctx, out, log_z, nullptr);
     }
     int posterior(int64_t first, int64_t n, double* out) {
         return multi ? hf_multi_get_posterior(multi, first, n, out) : hf_get_posterior(ctx, first, n, out);
@@ -1177,7 +1191,8 @@ static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
     {'B', &Options::dumpBin}, {'k', &Options::writeBenchmarkingStatsPerIteration}, {'w', &Options::writeParamsPerIter}, {'P', &Options::writePosterior},
     {'s', &Options::acceleration}, {kOptViterbi, &Options::viterbi}, {kOptRunConfidence, &Options::runConfidence}, {kOptExactTotals, &Options::exactTotals},
     {kOptNumBlocks, &Options::numBlocks}, {kOptRunBoundaries, &Options::runBoundaries}, {kOptJointEntropy, &Options::jointEntropy}, {kOptFitAlpha, &Options::fitAlpha},
-    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}, {kOptMergedChunks, &Options::mergedChunks}};
+    {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}, {kOptMergedChunks, &Options::mergedChunks},
+    {kOptLengthConstrainedEM, &Options::lengthConstrainedEM}};
 static const struct { int code; const char* Options::*text; } kTextOptions[] = {
     {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
     {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath},
@@ -1195,9 +1210,10 @@ static bool parse_options(int argc, char* argv[], Options& o) {
     o.program = strrchr(argv[0], '/');
     o.program = o.program ? o.program + 1 : argv[0];
     // "--e" and "--ex" were unique prefixes of --exchange until --exactTotals came, "--ru" and "--run" of --runConfidence until
-    // --runBoundaries came: they keep their meaning (the rule of long_options above: a prefix that resolved once resolves to the same
-    // option in every later build)
-    static const struct { const char *pre, *full; } kept[] = {{"--ex", "--exchange"}, {"--e", "--exchange"}, {"--run", "--runConfidence"}, {"--ru", "--runConfidence"}};
+    // --runBoundaries came, "--l" of --labelNames until --lengthConstrainedEM came: they keep their meaning (the rule of long_options
+    // above: a prefix that resolved once resolves to the same option in every later build)
+    static const struct { const char *pre, *full; } kept[] = {{"--ex", "--exchange"}, {"--e", "--exchange"}, {"--run", "--runConfidence"}, {"--ru", "--runConfidence"},
+                                                              {"--l", "--labelNames"}};
     static std::vector<std::string> rewritten;                   // (argv points into it from here on)
     rewritten.reserve((size_t) argc);
     for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; i++)
@@ -1337,16 +1353,17 @@ static bool min_len_windows(Run& s, int W) {
                     ts(), o.minLenPerState[0], o.minLenPerState[1], o.minLenPerState[3], mw[0], mw[1], mw[2], mw[3], W, HF_LONGRUN_MAX_LANES - 6);
             return false;
         }
-    if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet || o.expectedAccuracy) || sum <= HF_MINLEN_MAX_LANES) return true;
+    if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet || o.expectedAccuracy || o.lengthConstrainedEM) || sum <= HF_MINLEN_MAX_LANES) return true;
     std::string who;                                           // the options that walk the expanded chain, as given
     for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
-                          o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr, o.expectedAccuracy ? "expectedAccuracy" : nullptr})
+                          o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr, o.expectedAccuracy ? "expectedAccuracy" : nullptr,
+                          o.lengthConstrainedEM ? "lengthConstrainedEM" : nullptr})
         if (n) who += (who.empty() ? "" : ", --") + std::string(n);
     fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
             ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
     return false;
 }
-static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet || o.expectedAccuracy; }
+static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet || o.expectedAccuracy || o.lengthConstrainedEM; }
 
 // --expectedGains: four lines of four tab-separated numbers, rows the true label, columns the label called, read line by line and
 // token by token as the alpha TSV is; unlike an alpha a gain may be any finite number up to 1e100 in magnitude.  false: not such a file
@@ -1415,6 +1432,11 @@ static bool check_options(Run& s) {
          o.expectedAccuracy && strcmp(o.expectedAccuracy, "chunks") != 0 && strcmp(o.expectedAccuracy, "contigs") != 0 ? "can be chunks or contigs" : needsMinLen, kNoGpuRule},
         {"--expectedAccuracy", o.expectedAccuracy != nullptr, o.viterbi ? "cannot be combined with --viterbi" : nullptr, kOneGpuNoLoopback},
         {"--expectedGains", o.expectedGainsPath != nullptr, o.expectedAccuracy ? nullptr : "needs --expectedAccuracy", kNoGpuRule},
+        {"--lengthConstrainedEM", o.lengthConstrainedEM, needsMinLen, kNoGpuRule},
+        {"--lengthConstrainedEM", o.lengthConstrainedEM, o.acceleration ? "cannot be combined with --accelerate (SQUAREM under the constraint is not built)" : nullptr, kNoGpuRule},
+        {"--lengthConstrainedEM", o.lengthConstrainedEM, o.fitAlpha ? "cannot be combined with --fitAlpha (the alpha statistics come from the plain pass)" : nullptr, kNoGpuRule},
+        {"--lengthConstrainedEM", o.lengthConstrainedEM, o.modelType != HF_MODEL_NEGATIVE_BINOMIAL ? nullptr :
+                                   "needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial statistics are another path)", kOneGpuNoLoopback},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
@@ -1594,7 +1616,7 @@ struct EmRun {
     hfm_model* model;
     const std::string& dir;
     RunResult& res;
-    FILE *llf = nullptr, *atf = nullptr;                    // loglikelihood.tsv, --fitAlpha's alpha_trace.tsv
+    FILE *llf = nullptr, *atf = nullptr, *lcf = nullptr;    // loglikelihood.tsv, --fitAlpha's alpha_trace.tsv, --lengthConstrainedEM's length_constrained_em.tsv
     std::vector<double> alphaStats;
     int iter = 1, passes = 0;
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
@@ -1611,6 +1633,18 @@ static int timed_full_pass(Run& s, EmRun& em) {
     const double dt = real_time() - t0;
     em.emTime += dt; em.passes++;
     if (s.opt.phaseTiming) em.passMs.push_back(dt * 1e3);
+    return r;
+}
+
+// --lengthConstrainedEM: the E-step under --minimumLengths in the place of a full pass, and its row of length_constrained_em.tsv
+static int timed_minlen_pass(Run& s, EmRun& em) {
+    const double t0 = real_time();
+    double logZ = 0.0;
+    const int r = s.estep_minlen(em.model, s.minLenWindows, s.stats.data(), &logZ);
+    const double dt = real_time() - t0;
+    em.emTime += dt; em.passes++;
+    if (s.opt.phaseTiming) em.passMs.push_back(dt * 1e3);
+    if (r == HF_OK) fprintf(em.lcf, "%d\t%.4f\t%.4f\t%.4f\n", em.iter - 1, s.stats[0], logZ, s.stats[0] - logZ);
     return r;
 }
 
@@ -1634,16 +1668,29 @@ static int em_loop(Run& s, EmRun& em) {
             for (int k = 0; k < 16; k++) fprintf(em.atf, "\t%s_%d_%d", what, k / 4, k % 4);
         fprintf(em.atf, "\n");
     }
+    if (o.lengthConstrainedEM) {
+        if (!has_single_gpu_context(s, "--lengthConstrainedEM needs")) return EXIT_FAILURE;
+        em.lcf = fopen((dir + "/length_constrained_em.tsv").c_str(), "w");
+        if (!em.lcf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
+        fprintf(em.lcf, "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n");
+        fprintf(stderr, "[%s] --lengthConstrainedEM: the EM iterations fit under minimum run lengths of %d,%d,%d,%d windows (Err,Dup,Hap,Col)\n", ts(),
+                s.minLenWindows[0], s.minLenWindows[1], s.minLenWindows[2], s.minLenWindows[3]);
+    }
     em.emStart = real_time();
     int& iter = em.iter;
     while (iter <= o.numberOfIterations && !converged) {
         fprintf(stderr, "[%s] [Iteration %s = %d] Running EM jobs for %d chunks (on GPU %d) ...\n", ts(), accelerated, iter, s.nChunks, o.device);
-        if ((rc = timed_full_pass(s, em)) != HF_OK) return em.die(rc);
+        const bool tablesDue = o.writeBenchmarkingStatsPerIteration || iter == 1;   // hmm_flagger.c:360-379
+        const std::string tablesName = iter == 1 ? "initial" : iteration_suffix(o.acceleration, iter - 1);
+        if (o.lengthConstrainedEM) {
+            // the tables of an iteration are those of the plain pass with its parameters; the statistics are the constrained step's
+            if (tablesDue && ((rc = timed_full_pass(s, em)) != HF_OK || (rc = write_summary(s, dir, tablesName, nullptr)) != HF_OK)) return em.die(rc);
+            if ((rc = timed_minlen_pass(s, em)) != HF_OK) return em.die(rc);
+        } else if ((rc = timed_full_pass(s, em)) != HF_OK) return em.die(rc);
         fprintf(stderr, "[%s] [Iteration %s = %d] EM jobs are all finished.\n", ts(), accelerated, iter);
         loglikelihood_row(em.llf, iter, o.acceleration, s.stats[0]);
         em.res.ll = s.stats[0]; em.res.have_ll = true;
-        if ((o.writeBenchmarkingStatsPerIteration || iter == 1) &&   // hmm_flagger.c:360-379
-            (rc = write_summary(s, dir, iter == 1 ? "initial" : iteration_suffix(o.acceleration, iter - 1), nullptr)) != HF_OK) return em.die(rc);
+        if (!o.lengthConstrainedEM && tablesDue && (rc = write_summary(s, dir, tablesName, nullptr)) != HF_OK) return em.die(rc);
         if (o.acceleration) {                                // hmm_flagger.c:382-416
             fprintf(stderr, "[%s] [Iteration accelerated = %d] Running SQUAREM acceleration.\n", ts(), iter);
             auto estep_cb = [&s, &em](hfm_model* m, int mode, double* st) -> int {   // (the whole accelerated iteration is timed as one block)
@@ -1815,6 +1862,7 @@ static int final_inference(Run& s, EmRun& em) {
     em.res.ll = s.stats[0]; em.res.have_ll = true;
     fclose(em.llf);
     em.llf = nullptr;
+    if (em.lcf) { fclose(em.lcf); em.lcf = nullptr; }
     write_params(em.model, dir, "final");
     if (o.fitAlpha) {        // four tab-separated rows that --alphaTsv reads back to the same doubles
         double a[16];
@@ -1998,7 +2046,7 @@ static int run_em(Run& s, hfm_model* model, const std::string& dir, RunResult& r
     fprintf(stderr, "[%s] Running EM for estimating parameters. \n", ts());
     EmRun em{model, dir, res};
     if (!(em.llf = open_loglikelihood(dir))) return EXIT_FAILURE;
-    FileCloser llfClose{em.llf}, atfClose{em.atf};
+    FileCloser llfClose{em.llf}, atfClose{em.atf}, lcfClose{em.lcf};
     write_params(model, dir, "initial");
     for (int (*stage)(Run&, EmRun&) : {em_loop, final_inference, final_outputs, late_outputs}) {
         const int r = stage(s, em);

@@ -499,6 +499,20 @@ struct MinLenSampler : Decoder, SampleSet {
     void release() { grp.release(); fwd.release(); samples.release(); Decoder::release(); }
 };
 
+// the E-step under minimum run lengths (hf_minlen_em.h): a decoder front (parameter block, rows in window order, flag word), the forward
+// lanes and xi_adm in one buffer sized by the lengths of a call, and a pass state of its own over the context's track, as each model of a
+// batch has one: this call's tables (k_tables), tile and chunk statistics, the total.  The chunk values [2][C]: log Z_adm, log Z; ll0:
+// the slot ranges k_chunk_stats sums into element 0, one slot per chunk
+struct MinLenEM : Decoder {
+    DevBuf fwd;                                // F [N][sum of the lengths] | xi_adm [N][16]
+    double* d_xi = nullptr;                    // inside fwd (set by every call)
+    double* d_chunk = nullptr; int32_t* d_ll0 = nullptr;
+    Pass pass; bool pass_made = false;
+    std::vector<double> h_total, h_chunk;      // of the last finished call: the reduced vector, the chunk values
+    void release() { if (pass_made) drop_pass(); fwd.release(); Decoder::release(); }
+    void drop_pass();
+};
+
 // maximum-expected-accuracy decoding under minimum run lengths (hf_mea.h): a getter of the last full pass with a state of its own, the
 // slab allocated by its first call: gain rows, backpointer words, labels, block scores, final lanes, the unit-end parameter block and
 // the flag word; the group-as-chunk offsets of a call (mlg_cut) in a buffer beside it
@@ -547,6 +561,7 @@ struct hf_ctx {
     DevBuf bp;                // hf_breakpoint.h: pieces, parts, piece products, the chain's vectors, the windows' weights, results
     DevBuf lr;                // hf_longrun.h: parts, groups, results
     MeaDecoder mea;           // hf_mea.h: hf_get_mea_labels
+    MinLenEM mle;             // hf_minlen_em.h: hf_estep_minlen
 };
 
 // ------------------------------------------------------------------------------------------
@@ -978,6 +993,8 @@ static void pass_destroy(Pass& ps) {
     if (ps.h_total) { hipDeviceSynchronize(); pin_cache().release(reinterpret_cast<char*>(ps.h_total)); }
 }
 
+void MinLenEM::drop_pass() { pass_destroy(pass); pass_made = false; }
+
 #include "hf_create.h"
 
 extern "C" {
@@ -1070,6 +1087,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->bp.release();
     ctx->lr.release();
     ctx->mea.release();
+    ctx->mle.release();
     ctx->tr.slab.release();
     delete ctx;
 }
@@ -3612,6 +3630,167 @@ int hf_get_mea_labels(hf_ctx* ctx, const double* gain, const int32_t min_len[4],
     for (int64_t c = 0; c < tr.C; c++) tot += score[(size_t) c];          // chunk-list order
     if (block_gain_host) std::memcpy(block_gain_host, score.data(), (size_t) tr.C * 8);
     if (total_gain_host) *total_gain_host = tot;
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// the E-step under minimum run lengths (hf_minlen_em.h): the expected sufficient statistics under the posterior over admissible paths,
+// in hf_finish's layout.  The family's front (minlen_front) on a decoder of its own, k_tables into a pass state of its own, k_mlp_fwd as
+// it is, k_mle_bwd, k_mle_tile, then k_chunk_stats and k_reduce as they are.  One code path for both kinds of context.  Behind every other
+// section, its kernels included, and in front of k_mlvj_fwd alone, which keeps its code only as the file's last kernel.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_em.h"
+
+template <class F> static void mle_arrays(const Track& tr, MinLenEM& v, F&& f) {
+    dec_front_arrays(tr, v, (size_t) tr.N, f);
+    f(v.d_chunk, (size_t) tr.C * 16); f(v.d_ll0, ((size_t) tr.C + 1) * 4);
+}
+
+template <int KT>
+static int mle_launch_stats(const Track& tr, MinLenEM& v, hipStream_t st, int ncol) {
+    Pass& ps = v.pass;
+    if (tr.ntiles > 0) {
+        const TileGeom g = tile_geom(tr, k_mle_tile<KT>, (size_t) (3 * ncol > 28 ? 3 * ncol : 28) * 65 * 8, false);
+        if (!g.ok) return set_err(HF_E_ARG, "hf_estep_minlen: the accumulators of one wavefront do not fit the LDS of one workgroup");
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mle_tile<KT>), dim3(g.blocks), dim3(g.threads), g.lds, st, tr.ntiles, tr.d_tile_desc, tr.d_rec,
+                           row_src(ps), ps.d_params, v.d_xi, tr.d_regmask, ps.d_tile_stats);
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chunk_stats<KT>), dim3((unsigned) tr.C), dim3(128), 0, st, tr.d_chunk_tile0, v.d_ll0, tr.d_regmask,
+                       ps.d_tile_stats, v.d_chunk, ps.d_params, ps.d_chunk_stats_own, tr.V, tr.K, tr.ntiles > 0 ? 1 : 0);
+    return HF_OK;
+}
+
+int hf_estep_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    hipStream_t st = (hipStream_t) stream;
+    const std::string w = "hf_estep_minlen";
+    int64_t lanes = 0;
+    const double* nbE = nullptr;
+    int rc = minlen_front(ctx, &hf_ctx::mle, p, min_len, st, w, [&] {
+        return p->model_type == HF_MODEL_NEGATIVE_BINOMIAL
+                   ? set_err(HF_E_ARG, w + ": the negative_binomial model is not supported (its statistics are another path)") : (int) HF_OK;
+    }, [&](const Track& tr, MinLenEM& v) {
+        // the forward lanes and xi_adm: what the decoder holds of them already counts as free
+        const size_t f_bytes = Slab::granule((size_t) tr.N * (size_t) lanes * 8), bytes = f_bytes + (size_t) tr.N * 128;
+        if (bytes > v.fwd.cap) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            if ((double) bytes > 0.9 * ((double) free_b + (double) v.fwd.cap))
+                return set_err(HF_E_ARG, w + ": the forward lanes and xi_adm need " + std::to_string(bytes) + " bytes (n_windows x (sum of the lengths x 8 + 128)), above nine tenths of the free device memory");
+        }
+        const bool first = !v.alloc;
+        int rc = dec_alloc(tr, v, [&](auto&& f) { mle_arrays(tr, v, f); });
+        if (rc) return rc;
+        if (first) {   // one slot per chunk: k_chunk_stats' element 0 is the chunk's log Z_adm
+            std::vector<int32_t> ll0((size_t) tr.C + 1);
+            for (size_t c = 0; c < ll0.size(); c++) ll0[c] = (int32_t) c;
+            HIPCHK(hipMemcpy(v.d_ll0, ll0.data(), ll0.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (!v.pass_made) {
+            v.pass_made = true;
+            if ((rc = pass_create(tr, ctx->pass, &v.pass))) { v.drop_pass(); return rc; }
+            HIPCHK(hipDeviceSynchronize());   // (pass_create clears its arrays on the null stream; `st` may not wait for that one)
+        }
+        if ((rc = v.fwd.reserve(bytes, w))) return rc;
+        v.d_xi = reinterpret_cast<double*>(v.fwd.d_buf + f_bytes);
+        return (int) HF_OK;
+    }, lanes, nbE);
+    if (rc) return rc;
+    const Track& tr = ctx->tr;
+    MinLenEM& v = ctx->mle;
+    Pass& ps = v.pass;
+    if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_chunk, 0, (size_t) tr.C * 16, st));
+    if (tr.C > 0) {
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
+        HIPCHK(hipMemcpyAsync(ps.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
+        {   // this call's tables; the kernel clears the flag word it is given, as dec_front has done
+            const int jobs = (seg_pass(tr) ? tr.n_combo : tr.n_keys) + tr.n_slow;
+            const NoKParams none{0};
+#define HF_MLE_TABLES(J) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables<J, false>), dim3((unsigned) ((jobs + J - 1) / J + (jobs == 0))), dim3(256), 0, st, \
+                                            ps.tabwork, ps.d_params, v.d_flags, none, ps.d_params)
+            if (jobs < 64 * 1024) HF_MLE_TABLES(HF_TABLE_JOBS_SMALL); else HF_MLE_TABLES(HF_TABLE_JOBS_LARGE);
+#undef HF_MLE_TABLES
+        }
+        if (dec_work(tr)) {
+            hipLaunchKernelGGL(k_dec_rows_win, dim3((unsigned) ((tr.N + 255) / 256)), dim3(256), 0, st, tr.N, tr.d_rec, tr.d_beta, v.d_params, nbE,
+                               v.d_rows, v.d_flags);
+            hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3,
+                               d_F, v.d_chunk, v.d_flags);
+            hipLaunchKernelGGL(k_mle_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, d_F, v.d_xi,
+                               v.d_flags);
+        }
+        const int kc = p->ncomp[3];
+        rc = kc <= 4 ? mle_launch_stats<4>(tr, v, st, kc) : kc <= 8 ? mle_launch_stats<8>(tr, v, st, kc) : mle_launch_stats<16>(tr, v, st, kc);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_reduce, dim3((unsigned) (tr.V + 1)), dim3(64), 0, st, ps.d_chunk_stats_own, (const int32_t*) nullptr, (int64_t) tr.C, tr.V,
+                           ps.d_total, v.d_flags, 0, 0, 0);
+    }
+    HIPCHK(hipGetLastError());
+    v.launched = true;
+    return HF_OK;
+}
+
+int hf_estep_minlen_finish(hf_ctx* ctx, double* stats_host, double* log_z_host, void* stream) {
+    if (!ctx || !stats_host || !ctx->mle.launched) return set_err(HF_E_ARG, "hf_estep_minlen_finish: no hf_estep_minlen to finish");
+    const Track& tr = ctx->tr;
+    MinLenEM& v = ctx->mle;
+    const int rc = dec_finish(tr, v, stream);
+    if (rc) return rc;
+    v.h_total.assign((size_t) tr.V, 0.0);
+    v.h_chunk.assign((size_t) tr.C * 2, 0.0);
+    if (tr.C > 0) {
+        HIPCHK(hipMemcpy(v.h_total.data(), v.pass.d_total, (size_t) tr.V * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(v.h_chunk.data(), v.d_chunk, (size_t) tr.C * 16, hipMemcpyDeviceToHost));
+    }
+    std::memcpy(stats_host, v.h_total.data(), (size_t) tr.V * 8);
+    if (log_z_host) {
+        double z = 0.0;
+        for (int64_t c = 0; c < tr.C; c++) z += v.h_chunk[(size_t) (tr.C + c)];   // chunk-list order
+        *log_z_host = z;
+    }
+    v.done = true;
+    return HF_OK;
+}
+
+int hf_get_minlen_pair_posterior(hf_ctx* ctx, int64_t first, int64_t n, double* xi_host) {
+    const std::string w = "hf_get_minlen_pair_posterior";
+    if (!ctx || !xi_host || !ctx->mle.done) return set_err(HF_E_ARG, w + ": no finished hf_estep_minlen");
+    const Track& tr = ctx->tr;
+    if (first < 0 || n < 0 || first + n > tr.N) return set_err(HF_E_ARG, w + ": bad range");
+    if (n > 0 && !in_chunks(tr, first, first + n - 1)) return set_err(HF_E_ARG, w + ": the range holds a window outside every chunk");
+    HIPCHK(hipSetDevice(tr.device));
+    if (n > 0) HIPCHK(hipMemcpy(xi_host, ctx->mle.d_xi + first * 16, (size_t) n * 128, hipMemcpyDeviceToHost));
+    return HF_OK;
+}
+
+int hf_get_minlen_em_chunk_stats(hf_ctx* ctx, double* chunk_stats_host, double* log_z_adm_host, double* log_z_host) {
+    const std::string w = "hf_get_minlen_em_chunk_stats";
+    if (!ctx || !ctx->mle.done) return set_err(HF_E_ARG, w + ": no finished hf_estep_minlen");
+    const Track& tr = ctx->tr;
+    const MinLenEM& v = ctx->mle;
+    HIPCHK(hipSetDevice(tr.device));
+    if (chunk_stats_host && tr.C > 0)
+        HIPCHK(hipMemcpy(chunk_stats_host, v.pass.d_chunk_stats_own, (size_t) tr.C * (size_t) tr.V * 8, hipMemcpyDeviceToHost));
+    if (log_z_adm_host && tr.C > 0) std::memcpy(log_z_adm_host, v.h_chunk.data(), (size_t) tr.C * 8);
+    if (log_z_host && tr.C > 0) std::memcpy(log_z_host, v.h_chunk.data() + tr.C, (size_t) tr.C * 8);
+    return HF_OK;
+}
+
+// hf_em_iterate with the constrained E-step: the model's log-likelihood becomes element 0, the sum of log Z_adm
+int hf_em_iterate_minlen(hf_ctx* ctx, hfm_model* model, const int32_t min_len[4], int do_mstep, double tol, double* stats_host,
+                         double* log_z_host, int* converged, void* stream) {
+    if (!ctx || !model || !min_len || !stats_host) return set_err(HF_E_ARG, "hf_em_iterate_minlen: bad argument");
+    hf_params p;
+    hfm_params(model, &p);
+    int rc = hf_estep_minlen(ctx, &p, min_len, stream);
+    if (rc == HF_OK) rc = hf_estep_minlen_finish(ctx, stats_host, log_z_host, stream);
+    if (rc != HF_OK) return rc;
+    hfm_set_loglikelihood(model, stats_host[0]);
+    if (do_mstep) {
+        const int cv = hfm_estimate(model, stats_host, tol);
+        if (converged) *converged = cv;
+    }
     return HF_OK;
 }
 

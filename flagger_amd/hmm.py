@@ -619,6 +619,51 @@ class EMList:
         N.check(self._L.hf_get_minlen_chunk_log_mass(self._h, _dptr(mass), _dptr(lza)), "hf_get_minlen_chunk_log_mass")
         return MinLenPosterior(self, labels, mass, lza, float(tot.value))
 
+    def estep_minlen(self, model: HMM, min_len):
+        """The E-step under minimum run lengths (hf_estep_minlen + hf_estep_minlen_finish): (stats, log_z).  stats has finish()'s
+        layout and holds the expected sufficient statistics under the posterior over the paths whose runs have at least min_len[s]
+        windows (runs at a chunk's ends are exempt), element 0 the sum of log Z_adm; log_z is the sum of the plain log Z of the same
+        parameters.  The last pass's results, every decoder's and the next pass are left as they were."""
+        ml = self._four_lengths("estep_minlen", min_len)
+        p = model.params()
+        N.check(self._L.hf_estep_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_estep_minlen")
+        out = np.empty(self.stats_len, dtype=np.float64)
+        lz = C.c_double(0.0)
+        N.check(self._L.hf_estep_minlen_finish(self._h, _dptr(out), C.byref(lz), self.stream), "hf_estep_minlen_finish")
+        return out, float(lz.value)
+
+    def minlen_pair_posterior(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """xi_adm[t][p][s] = P(s_{t-1} = p, s_t = s | data, path admissible) of the last estep_minlen / em_iterate_minlen for windows
+        [first, first + n): shape (n, 4, 4); zeros at a chunk's first window (hf_get_minlen_pair_posterior)."""
+        n = self.store.n_windows - first if n is None else n
+        out = np.empty((n, 4, 4), dtype=np.float64)
+        N.check(self._L.hf_get_minlen_pair_posterior(self._h, int(first), int(n), _dptr(out)), "hf_get_minlen_pair_posterior")
+        return out
+
+    def minlen_em_chunk_stats(self):
+        """(chunk_stats [n_chunks][stats_len], log_z_adm [n_chunks], log_z [n_chunks]) of the last estep_minlen / em_iterate_minlen
+        (hf_get_minlen_em_chunk_stats)."""
+        nc = self.store.n_chunks
+        cs = np.empty((nc, self.stats_len), dtype=np.float64)
+        lza = np.empty(nc, dtype=np.float64)
+        lz = np.empty(nc, dtype=np.float64)
+        N.check(self._L.hf_get_minlen_em_chunk_stats(self._h, _dptr(cs), _dptr(lza), _dptr(lz)), "hf_get_minlen_em_chunk_stats")
+        return cs, lza, lz
+
+    def em_iterate_minlen(self, model: "HMM", min_len, do_mstep: bool = True, tol: float = 1e-3) -> bool:
+        """em_iterate with the E-step under minimum run lengths (hf_em_iterate_minlen): the statistics in model.estimators are
+        expectations over admissible paths, model.loglikelihood the objective sum of log Z_adm, self.last_log_z the plain sum of
+        log Z of the parameters the step ran with; returns the convergence flag of the M-step."""
+        ml = self._four_lengths("em_iterate_minlen", min_len)
+        stats = np.empty(self.stats_len, dtype=np.float64)
+        cv, lz = C.c_int(0), C.c_double(0.0)
+        N.check(self._L.hf_em_iterate_minlen(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)), int(do_mstep), tol, _dptr(stats),
+                                             C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen")
+        model.estimators = stats
+        model.loglikelihood = float(stats[0])
+        self.last_log_z = float(lz.value)
+        return bool(cv.value)
+
     def mea_labels(self, min_len=(1, 1, 1, 1), joined=None, gain=None):
         """Maximum-expected-accuracy decoding under minimum run lengths (hf_get_mea_labels): among the labellings whose runs have at
         least min_len[s] windows (runs at a chunk's ends exempt), the one with the largest expected gain under the posterior of the
@@ -914,6 +959,18 @@ def EM_runOneIterationForList(emList, model: HMM, threads: int = 0) -> None:
         stats = emList.finish()
     model.estimators = stats
     model.loglikelihood = float(stats[0])
+
+
+def EM_runOneMinLengthIterationForList(emList, model: HMM, min_len) -> float:
+    """EM_runOneIterationForList with the E-step under minimum run lengths (no counterpart in the reference): model.estimators holds the
+    expected statistics under the posterior over admissible paths, model.loglikelihood the sum of log Z_adm.  Returns the plain sum of
+    log Z of the same parameters.  `emList`: an EMList."""
+    if not hasattr(emList, "estep_minlen"):
+        raise TypeError("EM_runOneMinLengthIterationForList: %s has no E-step under minimum run lengths" % type(emList).__name__)
+    stats, log_z = emList.estep_minlen(model, min_len)
+    model.estimators = stats
+    model.loglikelihood = float(stats[0])
+    return log_z
 
 
 def EM_runForwardForList(emList, model: HMM, threads: int = 0) -> None:
@@ -1257,12 +1314,20 @@ def HMM_resetEstimators(model: HMM) -> None:
 def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergenceTol: float = 0.001,
                   outputDir: Optional[str] = None, writeParameterStatsPerIteration: bool = False,
                   is_writer: bool = True, fitAlpha: bool = False, fitAlphaEntries=FIT_ALPHA_ENTRIES, fitAlphaMax: float = FIT_ALPHA_MAX,
-                  fitAlphaEvery: int = 2) -> List[float]:
+                  fitAlphaEvery: int = 2, constrainedMinLen=None) -> List[float]:
     """EM outer loop of hmm_flagger.c:285-488 (no --accelerate here: that loop is flagger_amd/csrc/hf_squarem.h, driven by the command line).  Returns the
     log-likelihood of every E-pass (the rows of loglikelihood.tsv).
+    constrainedMinLen (an EMList only; four window counts): the EM iterations run on the E-step under minimum run lengths
+    (em_iterate_minlen), so their rows hold the objective sum of log Z_adm, and length_constrained_em.tsv holds per iteration
+    log Z_adm, log Z and their difference; the final inference pass stays the plain pass with the fitted parameters.
     fitAlpha (an EMList only): the k-th iteration, k = 1, 2, ..., is an alpha-iteration when k is a multiple of fitAlphaEvery — its pass is
     followed by HMM_estimateAlpha alone; the others are ordinary iterations (HMM_estimateParameters alone).  The run has converged when
     the latest iteration of each kind reported convergence."""
+    if constrainedMinLen is not None:
+        if fitAlpha:
+            raise ValueError("runHMMFlagger: constrainedMinLen cannot be combined with fitAlpha")
+        return _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
+                                    is_writer, constrainedMinLen)
     if fitAlpha:
         return _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
                                       is_writer, fitAlphaEntries, fitAlphaMax, int(fitAlphaEvery))
@@ -1298,6 +1363,52 @@ def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergence
         llf.close()
         model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
         model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
+    return lls
+
+
+LCEM_HEADER = "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n"
+
+
+def _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration, is_writer,
+                         min_len) -> List[float]:
+    if not hasattr(emList, "em_iterate_minlen"):
+        raise TypeError("runHMMFlagger(constrainedMinLen=...): %s has no E-step under minimum run lengths" % type(emList).__name__)
+    if model.modelType == MODEL_NEGATIVE_BINOMIAL:
+        raise ValueError("constrainedMinLen: the negative_binomial model is not supported")
+    lls: List[float] = []
+    write = outputDir is not None and is_writer
+    llf = lcf = None
+    if write:
+        llf = open(os.path.join(outputDir, "loglikelihood.tsv"), "w")
+        llf.write("#Iteration\tEffective_Iteration\tLoglikelihood\n")
+        lcf = open(os.path.join(outputDir, "length_constrained_em.tsv"), "w")
+        lcf.write(LCEM_HEADER)
+        model.writeTransitionTsv(os.path.join(outputDir, "transition_initial.tsv"))
+        model.writeEmissionTsv(os.path.join(outputDir, "emission_initial.tsv"))
+    it, converged = 1, False
+    try:
+        while it <= numberOfIterations and not converged:
+            converged = emList.em_iterate_minlen(model, min_len, True, convergenceTol)
+            lls.append(model.loglikelihood)
+            if llf:
+                llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
+                lcf.write("%d\t%.4f\t%.4f\t%.4f\n" % (it - 1, model.loglikelihood, emList.last_log_z, model.loglikelihood - emList.last_log_z))
+            HMM_resetEstimators(model)
+            if write and writeParameterStatsPerIteration:
+                model.writeTransitionTsv(os.path.join(outputDir, f"transition_iteration_{it}.tsv"))
+                model.writeEmissionTsv(os.path.join(outputDir, f"emission_iteration_{it}.tsv"))
+            it += 1
+        EM_runOneIterationForList(emList, model)   # final inference: the plain pass with the fitted parameters
+        lls.append(model.loglikelihood)
+        if llf:
+            llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
+            model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
+            model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
+    finally:
+        if llf:
+            llf.close()
+        if lcf:
+            lcf.close()
     return lls
 
 

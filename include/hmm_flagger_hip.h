@@ -587,6 +587,55 @@ int hf_get_minlen_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *post_
 int hf_get_minlen_posterior_labels(hf_ctx *ctx, int8_t *labels_host);                 /* [n_windows], -1 outside chunks */
 int hf_get_minlen_chunk_log_mass(hf_ctx *ctx, double *log_mass_host, double *log_z_adm_host);       /* [n_chunks]; log_z_adm_host may be NULL */
 
+/* The E-step under minimum run lengths (flagger_amd/csrc/hf_minlen_em.h): the expected sufficient statistics of EM_updateEstimators
+ * under the posterior over ADMISSIBLE paths, in hf_finish's layout (hf_chunk_stats_len), for the unchanged M-step (hfm_estimate).  An
+ * EM over it maximises sum over chunks of log Z_adm = log P(data, path admissible | theta) instead of log P(data | theta).
+ * first[s], A_t[p][s], end[s], min_len[4], the lanes (s, d), the lane index, admissibility (runs touching a chunk's first or last
+ * window are exempt), the recursions of F_t and B_t, every sum order inside them and the rescaling are exactly hf_minlen_posterior's;
+ * F is the bits its forward kernel stores.  For a chunk of T windows and every pair (t-1, t), 1 <= t <= T-1, m_s = min_len[s]:
+ *   p != s:           u_t[p][s] = F_{t-1}[(p, m_p)] * A_t[p][s] * B_t[(s, 1)]
+ *   p == s, m_s == 1: u_t[s][s] = F_{t-1}[(s, 1)] * A_t[s][s] * B_t[(s, 1)]
+ *   p == s, m_s > 1:  u_t[s][s] = sum over d = 2..m_s of c_d * A_t[s][s] * B_t[(s, d)],
+ *                     c_d = F_{t-1}[(s, d-1)] for d < m_s, c_{m_s} = F_{t-1}[(s, m_s - 1)] + F_{t-1}[(s, m_s)]
+ *   tot_t = sum over s ascending of ((u_t[0][s] + u_t[1][s]) + u_t[2][s]) + u_t[3][s], accumulated from the left
+ *   xi_adm_t[p][s] = u_t[p][s] / tot_t = P(s_{t-1} = p, s_t = s | data, path admissible)
+ * THE ORDER OF EVERY PRODUCT AND SUM.  A term x * a * y (x of F_{t-1}, or c_d; a of A_t; y of B_t) is formed from the three frexp
+ * mantissas (in [1/2, 1), 0 for a zero) as (mx * ma) * my, with the exponent sum e = ex + ea + ey.  e_t is the largest e over the
+ * window's terms that are not 0 (the 12 or more terms u_t[p][s] of a single product and the terms of every sum over d), and a term
+ * enters as (mx * ma) * my * 2^max(e - e_t, -2000): F_{t-1} and B_t each sit anywhere in their own rescaling period, so the plain
+ * product could underflow although no factor does; the largest term of a window is in [1/8, 1), and the power of two cancels in
+ * xi_adm.  The sum over d is the fixed tree of hf_minlen_posterior's wave sums with 0 in the lanes that take no part.  tot_t as above.
+ * Identities: sum_p xi_adm_t[p][s] = post[t][s] and sum_s xi_adm_t[p][s] = post[t-1][p] of hf_minlen_posterior, to rounding; with all
+ * four lengths 1, xi_adm_t is the plain pass's xi_t = f_{t-1}[p] * A_t[p][s] * b_t[s] / 1e-4, to rounding.
+ * STATISTICS.  Element 0 of a chunk's vector is that chunk's log Z_adm, bit for bit what hf_get_minlen_chunk_log_mass returns as
+ * log_z_adm.  Every other element is the estimator arithmetic of the per-chunk statistics of hf_estep (transition counts, the trunc-exp
+ * numerator and denominator, the one-component Gaussian states, the collapsed state's component loop with the component rows of THIS
+ * call's tables), term for term, over the same pairs (w-1, w), w = 2..T-1 (the reference's skipped first pair included), with
+ * xi_adm_w[p][s] in the place of count / terminationProb: xi_adm is normalised already, nothing is divided by the termination
+ * probability.  The chunk vectors are summed in the order of hf_reduce_chunks.  A chunk of one or two windows has no such pair: statistics
+ * of exactly zero behind element 0; a chunk without windows the vector of zeros.  WITH ALL FOUR LENGTHS 1 element 0 is log Z, which
+ * holds the end column end[s]; the log-likelihood of hf_estep (the sum of the log scales) leaves it out, so the two differ by the
+ * chunks' log sum_s f_{T-1}[s] end[s] while every other element agrees with hf_estep + hf_finish to rounding.
+ * hf_estep_minlen is asynchronous on `stream`; hf_estep_minlen_finish waits for that stream, translates the flags and copies the
+ * summed vector [hf_chunk_stats_len] to stats_host and, when log_z_host is not NULL, the sum over chunks in list order of log Z (the
+ * plain chain's, from the same forward kernel) to *log_z_host.  HF_E_SCALE: a chunk whose Z_adm (or Z) or a window whose tot_t is not
+ * > 0.  HF_E_NAN: a NaN in a row, in the end column, in a chunk's sum or in tot_t.
+ * hf_get_minlen_pair_posterior: xi_adm of windows first .. first + n - 1 of the last FINISHED call, [n][16] with entry p * 4 + s;
+ * the first window of a chunk holds zeros; a range that touches a window outside every chunk is HF_E_ARG.
+ * hf_get_minlen_em_chunk_stats: the per-chunk vectors [n_chunks][hf_chunk_stats_len], log Z_adm [n_chunks] and log Z [n_chunks] of the
+ * last finished call; each array may be NULL.
+ * HF_E_ARG: a NULL argument, a length below 1, a sum above HF_MINLEN_MAX_LANES, a getter or a finish before its call; model_type
+ * negative_binomial (its statistics are another path; hf_last_error says so); the forward lanes (n_windows x sum(min_len) x 8 bytes)
+ * plus xi_adm (n_windows x 128 bytes) do not fit nine tenths of the free device memory (hf_last_error names the size).
+ * The call has a parameter block, tables, rows, forward lanes, xi_adm, tile and chunk statistics of its own: the context's last full
+ * pass and every getter of it, hf_viterbi*, both samplers, hf_minlen_posterior and the next hf_estep are bitwise unaffected.  One code
+ * path serves HF_ALGO_SCAN and HF_ALGO_SEQ contexts: the outputs are bitwise the same on both kinds of context, across repeated calls
+ * and on any stream.  hf_batch_* and hf_multi_* have no counterpart, and there is no whole-contig (joined) form. */
+int hf_estep_minlen(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4], void *stream);
+int hf_estep_minlen_finish(hf_ctx *ctx, double *stats_host, double *log_z_host /* may be NULL */, void *stream);
+int hf_get_minlen_pair_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *xi_host);          /* [n][16], p-major */
+int hf_get_minlen_em_chunk_stats(hf_ctx *ctx, double *chunk_stats_host, double *log_z_adm_host, double *log_z_host);
+
 /* Admissible path sampling (flagger_amd/csrc/hf_minlen_sample.h): whole paths drawn from the posterior under minimum run lengths.
  * first[s], A_t[p][s], end[s], min_len[4], admissibility (runs that contain a chunk's first or last window are exempt), the lanes (s, d)
  * and the lane index are hf_viterbi_minlen's; F_t is hf_minlen_posterior's forward vector: the same recursion, sum orders and rescaling,

@@ -82,6 +82,13 @@ void hfm_set_loglikelihood(hfm_model *m, double ll);
 int hf_em_iterate(hf_ctx *ctx, hfm_model *model, int mode, int do_mstep, double tol, double *stats_host, int *converged,
                   void *stream);
 
+/* hf_em_iterate with the E-step under minimum run lengths (hf_estep_minlen, include/hmm_flagger_hip.h): the statistics are expectations
+ * over admissible paths, hfm_estimate is unchanged, and the model's log-likelihood becomes element 0, the sum over chunks of log Z_adm:
+ * the objective this EM maximises.  log_z_host (may be NULL): the sum of the plain log Z of the same parameters.  Always a full
+ * E-step; do_mstep = 0 leaves the model as it is. */
+int hf_em_iterate_minlen(hf_ctx *ctx, hfm_model *model, const int32_t min_len[4], int do_mstep, double tol, double *stats_host,
+                         double *log_z_host, int *converged, void *stream);
+
 /* hf_em_iterate for the models of a batch (hf_batch_create): one batched E-step of models[i] = the batch's model active[i] with the
  * parameters of model_objs[i], then per model its log-likelihood, and (do_mstep, full passes, status HF_OK) hfm_estimate with its
  * convergence test.  stats_host: [n_active][hf_chunk_stats_len]; status[i]: HF_E_* of model active[i]; converged[i] (may be NULL).
