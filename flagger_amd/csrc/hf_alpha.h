@@ -23,7 +23,7 @@
 // leaves: b_t in the record at pos[t], f_{t-1} in the one at pos_f[t-1]) — in either statistics mode, and with the pair (0, 1) of every
 // chunk like any other pair — HF_ALGO_SEQ from the tiles of k_fwd_seq / k_bwd_seq.
 //
-// PLAN, built by the first call of a context (hf_estep.hip alpha_plan): the pairs of all chunks sorted by the region of window t and, inside
+// PLAN, built by the first call of a context (hf_getters.h alpha_plan): the pairs of all chunks sorted by the region of window t and, inside
 // a region, HF_ALGO_SCAN by the position of t's pair record (the statistics plan keeps the records of one row of A together, so a
 // wavefront reads contiguous records and few rows), HF_ALGO_SEQ by t; cut into blocks of at most HF_AL_BLOCK pairs of ONE region.
 //   k_alpha_pairs  one workgroup of 256 lanes per block: lane l takes pairs l, l + 256, ... of the block in that order (32 accumulators in

@@ -1,11 +1,11 @@
 // hf_batch.h — many models on one context (hf_batch_*, include/hmm_flagger_hip.h): every model of a batch is one more PASS over the
-// context's TRACK (hf_estep.hip: Track, Pass).  The windows, the segment plan, the rows stream arow, the statistics plan and the job list of
+// context's TRACK (hf_host.h: Track, Pass).  The windows, the segment plan, the rows stream arow, the statistics plan and the job list of
 // k_tables are the track's and are read by every model; everything a pass, hf_finish or a getter writes (parameter block, tables, lutA,
 // hand-off flags and epochs, pair records, sums, labels, flags, totals, the pinned result block) is the model's Pass, made by pass_create as
 // the context's own is.  A pass of model m is the ordinary enqueue_pass / pass_finish of its Pass: the same kernels, the same launch
 // geometry, the same arithmetic in the same order as hf_estep on the context — so the results are the single path's bits, and a NaN or an
 // underflow in one model raises that model's flag word only.  The context's own pass is never written by a batch.  Included once, at the
-// end of hf_estep.hip.
+// end of hf_estep.hip (in front of hf_getters.h).
 
 struct hf_batch {
     hf_ctx* ctx = nullptr;

@@ -331,6 +331,7 @@ __global__ void __launch_bounds__(128) k_chunk_stats(const int32_t* __restrict__
 // Error flags ride along as element V: this context's flag word, OR-ed with the flag rows of an exchange buffer
 // (n_ranks > 0: rank k's word is element 0 of row k*rows_per_rank + flag_row, written by k_flag_row) so that every rank
 // of a multi-GPU pass reports the same error.
+#ifndef HF_HELPERS_ONLY   // (plain kernels: compiled by the unit that owns them alone, hf_host.h)
 __global__ void __launch_bounds__(64) k_reduce(const double* __restrict__ chunk_stats, const int32_t* __restrict__ row_index,
                                                int64_t n_chunks, int64_t V, double* __restrict__ out,
                                                const unsigned* __restrict__ flags, int n_ranks, int rows_per_rank, int flag_row) {
@@ -356,3 +357,4 @@ __global__ void __launch_bounds__(64) k_reduce(const double* __restrict__ chunk_
 __global__ void k_flag_row(const unsigned* __restrict__ flags, double* __restrict__ row) {
     if (threadIdx.x == 0) row[0] = (double) *flags;
 }
+#endif

@@ -167,6 +167,7 @@ __device__ __forceinline__ void dec_seg_maps(const SegDesc& d, int j, unsigned m
 
 // ---- rows ----------------------------------------------------------------------------------------------------------------------
 // HF_ALGO_SCAN: one workgroup of 64 per segment, slot-ordered pieces
+#ifndef HF_HELPERS_ONLY   // (the plain kernels of this file: compiled by the unit that owns them alone, hf_host.h)
 __global__ void __launch_bounds__(64) k_dec_rows_seg(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ rec,
                                                      const double* __restrict__ beta, const DevParams* __restrict__ P,
                                                      const double* __restrict__ nbE, double2* __restrict__ rows, unsigned* __restrict__ flags) {
@@ -183,6 +184,7 @@ __global__ void __launch_bounds__(64) k_dec_rows_seg(const SegDesc* __restrict__
     }
     if (nan) atomicOr(flags, nan);
 }
+#endif
 
 // HF_ALGO_SEQ: one thread per window, window order.  LOG: the log of every entry (-inf for 0), k_mlv_rows of hf_minlen.h
 template <bool LOG>
@@ -202,11 +204,13 @@ __device__ __forceinline__ void dec_rows_win(int64_t N, const uint32_t* __restri
     for (int k = 0; k < 8; k++) rows[t * 8 + k] = make_double2(a[2 * k], a[2 * k + 1]);
     if (nan) atomicOr(flags, nan);
 }
+#ifndef HF_HELPERS_ONLY
 __global__ void __launch_bounds__(256) k_dec_rows_win(int64_t N, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
                                                       const DevParams* __restrict__ P, const double* __restrict__ nbE,
                                                       double2* __restrict__ rows, unsigned* __restrict__ flags) {
     dec_rows_win<false>(N, rec, beta, P, nbE, rows, flags);
 }
+#endif
 
 // ---- A: lane products and their exclusive scan over the lanes --------------------------------------------------------------------
 // P[seg][k][lane] (16 doubles, k-major: coalesced), S[seg][16]; with a score also PE[seg][lane], SE[seg]
@@ -291,6 +295,7 @@ __device__ __forceinline__ int dec_enter(const double* __restrict__ vin, const d
 }
 
 // ---- D: exit states (sexit[k][seg]), labels (label[k][window]); blockIdx.y = sample k ------------------------------------------------
+#ifndef HF_HELPERS_ONLY
 __global__ void __launch_bounds__(64) k_dec_exits(int C, int G, const int32_t* __restrict__ cseg0, const uint8_t* __restrict__ smap,
                                                   const int8_t* __restrict__ final_state, uint8_t* __restrict__ sexit) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
@@ -328,3 +333,4 @@ __global__ void __launch_bounds__(64) k_dec_back(const SegDesc* __restrict__ seg
         s = dec_map_apply(mk[(int64_t) d.slot0 + (int64_t) i * 64 + j], s);
     }
 }
+#endif

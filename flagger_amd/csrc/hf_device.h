@@ -47,6 +47,8 @@ __device__ unsigned long long g_kstamp[64 * 4 + 1];
 // slow0 = position in the slow list of the tile's first slow window
 struct TileDesc { long long t0; int T; int base; int chunk; int slow0; };
 #define HF_AROW_CLASSES 9   // transition classes of an interior window: the 8 validity masks, 8 = region change (first window: 9)
+#define HF_NB_NX (HF_NB_MAX_COVERAGE + 1)   // entries per (region, state) of the negative-binomial tables (hf_nb.h; the decoders' table)
+#define HF_TAB_STRIDE 136   // doubles per region of the LDS transition tables (hf_scan.h fill_tab; the host sizes the LDS by it)
 // one segment of a chunk = one workgroup of the segment kernels (hf_seg.h), built once in hf_create
 struct SegDesc {
     long long t0;            // global index of the segment's first window

@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(64) k_mlv_back(const int64_t* __restrict__ off
     }
 }
 
-// k_mlvj_fwd is defined in hf_minlen_joined.h, which hf_estep.hip includes behind every other kernel (see above)
+// k_mlvj_fwd is defined in hf_minlen_joined.h, which hf_minlen.hip includes behind every other kernel header of the family (see above)
 __global__ void k_mlvj_fwd(const int64_t* __restrict__ goff, const int32_t* __restrict__ gchunk, const uint32_t* __restrict__ rec,
                            const DevParams* __restrict__ P, const double2* __restrict__ rows, int m0, int m1, int m2, int m3, uint16_t* __restrict__ bp,
                            uint8_t* __restrict__ final_lane, double* __restrict__ ll, unsigned* __restrict__ flags);

@@ -21,6 +21,7 @@
 // RESCALING OR AN ESTIMATOR TERM GOES INTO BOTH BODIES.
 #pragma once
 #include "hf_minlen_post.h"
+#include "hf_chunks.h"      // k_mle_tile: load_recs, tile_slow_index, row_ptr (hf_scan.h), StatAccSmall
 
 // the frexp form of a term's factor: mantissa (0 for a zero) and exponent
 __device__ __forceinline__ double mle_mant(double v, int& e) { return frexp(v, &e); }

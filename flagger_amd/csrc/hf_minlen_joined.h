@@ -1,7 +1,8 @@
 // hf_minlen_joined.h — k_mlvj_fwd, the forward walk of hf_viterbi_minlen_joined: k_mlv_fwd's walk with one 64-lane workgroup per group of
-// joined chunks.  The rule, the kernel's description and why it is a second body are in hf_minlen.h; why it is a file of its own, included
-// last in hf_estep.hip: there its code is what it has been; in hf_minlen.h, behind k_mlv_fwd or behind k_mlv_back, the compiler gives its
-// per-window loops the longer form of k_mlv_fwd's (59 / 117 -> 62 / 120 instructions; profiles/minlen_front_cfg2.txt).
+// joined chunks.  The rule, the kernel's description and why it is a second body are in hf_minlen.h; why it is a file of its own, the
+// LAST KERNEL HEADER OF hf_minlen.hip: there its code is what it has been; in hf_minlen.h, behind k_mlv_fwd or behind k_mlv_back, the
+// compiler gives its per-window loops the longer form of k_mlv_fwd's (59 / 117 -> 62 / 120 instructions;
+// profiles/minlen_front_cfg2.txt).  The rule binds inside that unit only: no other unit's text stands in front of this kernel or behind it.
 #pragma once
 #include "hf_minlen.h"
 

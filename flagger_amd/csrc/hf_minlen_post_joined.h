@@ -23,8 +23,8 @@
 // and a period passes at most nine rows as before.
 // Flags: HF_FLAG_NAN also for a NaN in an end column read at a joined boundary (the forward staging lane raises it).
 //
-// This file is included last but one in hf_estep.hip, in front of hf_minlen_joined.h: there no existing kernel's code moves
-// (profiles/minlen_post_joined_asm.txt).
+// In hf_minlen.hip this file stands behind hf_mea.h and in front of hf_minlen_em.h and hf_minlen_joined.h, its place since it was added:
+// there no kernel of the family moved (profiles/minlen_post_joined_asm.txt, profiles/split_units_asm.txt).
 #pragma once
 #include "hf_minlen_post.h"
 #include "hf_minlen_sample.h"

@@ -14,7 +14,7 @@
 #pragma once
 #include "hf_scan.h"
 
-#define HF_NB_NX (HF_NB_MAX_COVERAGE + 1)
+// HF_NB_NX: hf_device.h
 #define HF_NB_TILE_VEC (16 + 4 * 256)     // per (tile, region): trans[16], hist[4][256] (bins >= 250 stay zero)
 
 struct NbTables {                          // device copies of hf_params.nb_*

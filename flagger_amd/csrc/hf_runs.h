@@ -33,7 +33,7 @@
 //                the same tree.  Every product is renormalised by 2^-e, shared by the three matrices (mo_norm).
 //   k_run_chain  one thread per part: (v, v', v'') and (u, u') from window a through the part's pieces in order, all five by the 2^-e of
 //                v, then the dot products.  Out: the seven numbers E[R], Var(R), s, e, Cov(R, E0), Cov(R, S0), Cov(S0, E0).
-// The parts of a job are stitched on the host (hf_get_run_moments in hf_estep.hip), left to right.  Nothing depends on the other jobs of
+// The parts of a job are stitched on the host (hf_get_run_moments in hf_getters.h), left to right.  Nothing depends on the other jobs of
 // a call.  S = all four states: d_a = 0 and D_t = 0 exactly, so Var(R) = 0.0 and every covariance is 0.0, E[R] = 1.0, s = e = 1.0.
 #pragma once
 #include "hf_view.h"

@@ -92,6 +92,7 @@ __device__ __forceinline__ unsigned smp_final_weights(const DevParams* __restric
 }
 
 // ---- C: replay: map bytes of every sample (maps[k][slot]), final states (final[k][chunk]) ----------------------------------------------
+#ifndef HF_HELPERS_ONLY   // (plain kernels, to the end of the file: compiled by the unit that owns them alone, hf_host.h)
 __global__ void __launch_bounds__(64) k_smp_replay(const SegDesc* __restrict__ segs, const uint32_t* __restrict__ rec,
                                                    const DevParams* __restrict__ P, const double2* __restrict__ rows,
                                                    const double* __restrict__ Pm, const double* __restrict__ vin,
@@ -190,3 +191,4 @@ __global__ void __launch_bounds__(64) k_smp_seq(const int64_t* __restrict__ off,
         }
     }
 }
+#endif

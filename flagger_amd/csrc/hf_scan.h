@@ -22,7 +22,7 @@ struct M4 { double m[16]; };   // row-major: m[pre*4 + s]
 
 // Conditional-transition and start tables of every region, staged once per block in LDS (136 doubles per region:
 // tcond[8][16], start[4], pad): the per-window lookup no longer waits on global memory behind the window record.
-#define HF_TAB_STRIDE 136
+// HF_TAB_STRIDE: hf_device.h
 __device__ __forceinline__ void fill_tab(const DevParams* __restrict__ P, double* __restrict__ s_tab) {
     const int n = P->n_regions * HF_TAB_STRIDE;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -227,6 +227,7 @@ __device__ __forceinline__ void tab_sync() {
 // the job list of a context, once (hf_create): job < n_keys is the (emission key [, transition class]) pair keys[job] / cls[job] of an interior
 // window, job - n_keys < n_slow the slow window slow_w[k] with its own beta (round 5: a pass used to rebuild this from keys / records /
 // betas every time — three dependent global loads at the head of a latency-bound kernel)
+#ifndef HF_HELPERS_ONLY   // (a plain kernel: compiled by the unit that owns it alone, hf_host.h)
 __global__ void __launch_bounds__(256) k_build_jobs(int n_keys, const int32_t* __restrict__ keys, const int32_t* __restrict__ cls, int n_slow,
                                                     const int64_t* __restrict__ slow_w, const uint32_t* __restrict__ rec, const double* __restrict__ beta,
                                                     int M, int64_t n_lut_rows, double beta_star, TableJob* __restrict__ jobs) {
@@ -250,6 +251,7 @@ __global__ void __launch_bounds__(256) k_build_jobs(int n_keys, const int32_t* _
     if (cls) J.flags |= (cls[job] & 0xff) << 8;
     jobs[job] = J;
 }
+#endif
 
 // the job of thread tid (< JOBS) of the unit whose first job is job0 (one 48-byte load; idle past the list's end)
 template <int JOBS>

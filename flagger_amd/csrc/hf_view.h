@@ -1,6 +1,6 @@
 // hf_view.h — what the last HF_MODE_FULL pass left on the device, as the getters' kernels read it (hf_interval.h, hf_moments.h, hf_runs.h,
 // hf_entropy.h, hf_alpha.h): one struct passed by value, the row A_t of a window and the scaled forward and backward vectors f_t, b_t
-// (hf_get_forward_backward).  The host fills it in one place (view_of in hf_estep.hip); the pointers of the other algorithm are null.
+// (hf_get_forward_backward).  The host fills it in one place (view_of in hf_getters.h); the pointers of the other algorithm are null.
 //   HF_ALGO_SCAN  rows: the pass's deduplicated rows of A (lutA through arow; bit 31 marks a chunk-first window), stored state-major
 //                 (o = s * 4 + pre, hf_seg.h HF_PS) and transposed on load.  f, b: the pair records (b_t: second half of the record at
 //                 pos[t], f_t: first half of the one at pos_f[t])

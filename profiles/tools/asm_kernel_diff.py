@@ -8,6 +8,7 @@ bytes, scratch bytes and the length in instructions of every loop body (the inst
 branches), before and after.  A kernel named by --family (a substring of its demangled or mangled name) may differ as long as no
 resource figure and no loop body grew; any other kernel must be identical.  Exit status 1 when that does not hold.  --table prints the
 figures of the family's kernels in AFTER.s.
+Either file may be the concatenation of several translation units' assemblies (cat unit1.s unit2.s ...): kernels are found by name.
 """
 import argparse
 import re

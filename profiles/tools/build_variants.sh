@@ -10,7 +10,7 @@ HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -w -I../.
 for spec in "$@"; do
   name=${spec%%=*}; extra=${spec#*=}
   ( /opt/rocm/bin/hipcc $HIPFLAGS $extra -c hf_estep.hip -o variants/hf_estep.$name.o &&
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC variants/hf_estep.$name.o hf_multi.o hf_model.o hf_io.o hf_summary.o -o variants/libhmmflagger_hip.$name.so -lrccl -lz -lpthread &&
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC variants/hf_estep.$name.o hf_decoders.o hf_minlen.o hf_multi.o hf_model.o hf_io.o hf_summary.o -o variants/libhmmflagger_hip.$name.so -lrccl -lz -lpthread &&
     rm -f variants/hf_estep.$name.o && echo "built $name [$extra]" || echo "FAILED $name" ) &
 done
 wait
