@@ -143,6 +143,7 @@ def lib() -> C.CDLL:
     sig("hf_get_minlen_posterior_labels", C.c_int, vp, C.POINTER(C.c_int8))
     sig("hf_get_minlen_chunk_log_mass", C.c_int, vp, pd, pd)
     sig("hf_estep_minlen", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), vp)
+    sig("hf_estep_minlen_joined", C.c_int, vp, C.POINTER(hf_params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), vp)
     sig("hf_estep_minlen_finish", C.c_int, vp, pd, pd, vp)
     sig("hf_get_minlen_pair_posterior", C.c_int, vp, i64, i64, pd)
     sig("hf_get_minlen_em_chunk_stats", C.c_int, vp, pd, pd, pd)
@@ -247,6 +248,7 @@ def lib() -> C.CDLL:
     sig("hfm_estimate_alpha", C.c_int, vp, pd, pd, C.POINTER(C.c_uint8), dbl, dbl, dbl)
     sig("hf_em_iterate", C.c_int, vp, vp, C.c_int, C.c_int, dbl, pd, C.POINTER(C.c_int), vp)
     sig("hf_em_iterate_minlen", C.c_int, vp, vp, C.POINTER(C.c_int32), C.c_int, dbl, pd, pd, C.POINTER(C.c_int), vp)
+    sig("hf_em_iterate_minlen_joined", C.c_int, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int, dbl, pd, pd, C.POINTER(C.c_int), vp)
     # summary tables (include/hmm_flagger_summary.h)
     sig("hfs_write_all_tables", C.c_int, C.POINTER(hfs_input), C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, dbl, C.c_int)
     sig("hfs_last_error", C.c_char_p)

@@ -54,7 +54,7 @@ enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
     kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks,
-    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM
+    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM, kOptCrossChunkEM
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -101,6 +101,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"expectedAccuracy", required_argument, nullptr, kOptExpectedAccuracy},   // final labels by maximum expected accuracy UNDER --minimumLengths, chunks | contigs (hf_get_mea_labels; both new names start with --exp: --ex was ambiguous already, --e and --ex stay --exchange)
     {"expectedGains", required_argument, nullptr, kOptExpectedGains},         // its 4x4 gain matrix [identity]
     {"lengthConstrainedEM", no_argument, nullptr, kOptLengthConstrainedEM},     // the EM iterations fit UNDER --minimumLengths (hf_estep_minlen; --l stays --labelNames: parse_options' kept[])
+    {"crossChunkEM", no_argument, nullptr, kOptCrossChunkEM},             // --lengthConstrainedEM over the joined chunks of a contig (hf_estep_minlen_joined; nothing else starts with --cr, --c was ambiguous already, --le stays --lengthConstrainedEM, --l --labelNames)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -239,7 +240,11 @@ static void usage(const char* program) {
             "                                      iteration rows of loglikelihood.tsv hold the objective, the sum of log Z_adm, and\n"
             "                                      length_constrained_em.tsv per iteration log Z_adm, log Z and their difference; the final inference\n"
             "                                      pass and every output stay the plain ones.  Not with --accelerate, --fitAlpha or --modelType\n"
-            "                                      negative_binomial; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n");
+            "                                      negative_binomial; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n"
+            "         --crossChunkEM               with --lengthConstrainedEM: the lengths hold over the joined chunks of a contig (the rule of\n"
+            "                                      --wholeContigs and of the final BED), only runs at a contig's ends are exempt: the rows of\n"
+            "                                      loglikelihood.tsv and length_constrained_em.tsv hold the sums over contigs; every other output\n"
+            "                                      stays as it is\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -263,7 +268,7 @@ struct Options {
     int numberOfIterations = 100, numberOfCollapsedComps = -1, chunkLen = 20000000, windowLen = -1, threads = 4;
     double convergenceTol = 0.001, maxHighMapqRatio = 0.25, minHighMapqRatio = 0.75, minReadFractionAtEnds = -1.0, initialRandomDeviation = 0.0;
     bool adjustContigEnds = true, writeParamsPerIter = false, writePosterior = false, dumpBin = false, acceleration = false;
-    bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false, lengthConstrainedEM = false;
+    bool viterbi = false, enforceMinLen = false, wholeContigs = false, mergedChunks = false, keptBlocks = false, constrainedPost = false, minLenGiven = false, lengthConstrainedEM = false, crossChunkEM = false;
     int uncertaintySamples = 0; bool uncertaintySet = false, uncertaintySeedBad = false; uint64_t uncertaintySeed = 0;
     int admissibleSamples = 0; bool admissibleSet = false;
     const char *expectedAccuracy = nullptr, *expectedGainsPath = nullptr;   // chunks | contigs; the gain TSV
@@ -350,9 +355,10 @@ struct Run {
         return rc != HF_OK ? rc : hf_minlen_posterior_finish(ctx, log_mass_total, nullptr);
     }
     // the E-step under min_len windows per state (one GPU): the statistics, and the plain sum of log Z of the same parameters
-    int estep_minlen(hfm_model* m, const int32_t min_len[4], double* out, double* log_z) {
+    // (joined: null for the per-chunk rule, else the rule over the groups of joined chunks, --crossChunkEM)
+    int estep_minlen(hfm_model* m, const int32_t min_len[4], const uint8_t* joined, double* out, double* log_z) {
         const hf_params p = params(m);
-        const int rc = hf_estep_minlen(ctx, &p, min_len, nullptr);
+        const int rc = joined ? hf_estep_minlen_joined(ctx, &p, min_len, joined, nullptr) : hf_estep_minlen(ctx, &p, min_len, nullptr);
         return rc != HF_OK ? rc : hf_estep_minlen_finish(ctx, out, log_z, nullptr);
     }
     int posterior(int64_t first, int64_t n, double* out) {
@@ -1192,7 +1198,7 @@ static const struct { int code; bool Options::*flag; } kFlagOptions[] = {
     {'s', &Options::acceleration}, {kOptViterbi, &Options::viterbi}, {kOptRunConfidence, &Options::runConfidence}, {kOptExactTotals, &Options::exactTotals},
     {kOptNumBlocks, &Options::numBlocks}, {kOptRunBoundaries, &Options::runBoundaries}, {kOptJointEntropy, &Options::jointEntropy}, {kOptFitAlpha, &Options::fitAlpha},
     {kOptEnforceMinLen, &Options::enforceMinLen}, {kOptKeptBlocks, &Options::keptBlocks}, {kOptConstrainedPosterior, &Options::constrainedPost}, {kOptWholeContigs, &Options::wholeContigs}, {kOptMergedChunks, &Options::mergedChunks},
-    {kOptLengthConstrainedEM, &Options::lengthConstrainedEM}};
+    {kOptLengthConstrainedEM, &Options::lengthConstrainedEM}, {kOptCrossChunkEM, &Options::crossChunkEM}};
 static const struct { int code; const char* Options::*text; } kTextOptions[] = {
     {'i', &Options::inputPath}, {'N', &Options::trackName}, {'a', &Options::binArrayFilePath}, {'c', &Options::contigListPath}, {'A', &Options::alphaTsvPath},
     {'o', &Options::outputDir}, {kOptSweepAlpha, &Options::sweepListPath}, {kOptRegionProbs, &Options::regionProbsPath},
@@ -1357,7 +1363,7 @@ static bool min_len_windows(Run& s, int W) {
     std::string who;                                           // the options that walk the expanded chain, as given
     for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
                           o.admissibleSet ? "admissibleSamples" : nullptr, o.mergedChunks ? "mergedChunks" : nullptr, o.expectedAccuracy ? "expectedAccuracy" : nullptr,
-                          o.lengthConstrainedEM ? "lengthConstrainedEM" : nullptr})
+                          o.lengthConstrainedEM ? "lengthConstrainedEM" : nullptr, o.crossChunkEM ? "crossChunkEM" : nullptr})
         if (n) who += (who.empty() ? "" : ", --") + std::string(n);
     fprintf(stderr, "[%s] Error: --%s: the minimum lengths are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col), above %d in sum.\n",
             ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
@@ -1437,6 +1443,7 @@ static bool check_options(Run& s) {
         {"--lengthConstrainedEM", o.lengthConstrainedEM, o.fitAlpha ? "cannot be combined with --fitAlpha (the alpha statistics come from the plain pass)" : nullptr, kNoGpuRule},
         {"--lengthConstrainedEM", o.lengthConstrainedEM, o.modelType != HF_MODEL_NEGATIVE_BINOMIAL ? nullptr :
                                    "needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial statistics are another path)", kOneGpuNoLoopback},
+        {"--crossChunkEM", o.crossChunkEM, o.lengthConstrainedEM ? nullptr : "needs --lengthConstrainedEM", kNoGpuRule},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
@@ -1618,6 +1625,7 @@ struct EmRun {
     RunResult& res;
     FILE *llf = nullptr, *atf = nullptr, *lcf = nullptr;    // loglikelihood.tsv, --fitAlpha's alpha_trace.tsv, --lengthConstrainedEM's length_constrained_em.tsv
     std::vector<double> alphaStats;
+    std::vector<uint8_t> crossJoined;                       // --crossChunkEM: joined_chunks of the table (empty: the per-chunk rule)
     int iter = 1, passes = 0;
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
@@ -1636,11 +1644,13 @@ static int timed_full_pass(Run& s, EmRun& em) {
     return r;
 }
 
+static std::vector<uint8_t> joined_chunks(const hfio_table* tab);
+
 // --lengthConstrainedEM: the E-step under --minimumLengths in the place of a full pass, and its row of length_constrained_em.tsv
 static int timed_minlen_pass(Run& s, EmRun& em) {
     const double t0 = real_time();
     double logZ = 0.0;
-    const int r = s.estep_minlen(em.model, s.minLenWindows, s.stats.data(), &logZ);
+    const int r = s.estep_minlen(em.model, s.minLenWindows, em.crossJoined.empty() ? nullptr : em.crossJoined.data(), s.stats.data(), &logZ);
     const double dt = real_time() - t0;
     em.emTime += dt; em.passes++;
     if (s.opt.phaseTiming) em.passMs.push_back(dt * 1e3);
@@ -1673,8 +1683,10 @@ static int em_loop(Run& s, EmRun& em) {
         em.lcf = fopen((dir + "/length_constrained_em.tsv").c_str(), "w");
         if (!em.lcf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
         fprintf(em.lcf, "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n");
-        fprintf(stderr, "[%s] --lengthConstrainedEM: the EM iterations fit under minimum run lengths of %d,%d,%d,%d windows (Err,Dup,Hap,Col)\n", ts(),
-                s.minLenWindows[0], s.minLenWindows[1], s.minLenWindows[2], s.minLenWindows[3]);
+        if (o.crossChunkEM) em.crossJoined = joined_chunks(s.tab);
+        fprintf(stderr, "[%s] --lengthConstrainedEM%s: the EM iterations fit under minimum run lengths of %d,%d,%d,%d windows (Err,Dup,Hap,Col)%s\n", ts(),
+                o.crossChunkEM ? " --crossChunkEM" : "", s.minLenWindows[0], s.minLenWindows[1], s.minLenWindows[2], s.minLenWindows[3],
+                o.crossChunkEM ? " over the joined chunks of a contig (only runs at a contig's ends are exempt)" : "");
     }
     em.emStart = real_time();
     int& iter = em.iter;
@@ -1737,7 +1749,7 @@ static int em_loop(Run& s, EmRun& em) {
     return 0;
 }
 
-// --wholeContigs: joined[c], chunk c continues chunk c-1 (adjacent in the chunk list, the same contig name: the rule of --numBlocks)
+// --wholeContigs, --crossChunkEM: joined[c], chunk c continues chunk c-1 (adjacent in the chunk list, the same contig name: the rule of --numBlocks)
 static std::vector<uint8_t> joined_chunks(const hfio_table* tab) {
     const int C = hfio_n_chunks(tab);
     std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);

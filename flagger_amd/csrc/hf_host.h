@@ -303,7 +303,8 @@ struct MinLenEM : Decoder {
     double* d_chunk = nullptr; int32_t* d_ll0 = nullptr;
     Pass pass; bool pass_made = false;
     std::vector<double> h_total, h_chunk;      // of the last finished call: the reduced vector, the chunk values
-    void release() { if (pass_made) drop_pass(); fwd.release(); Decoder::release(); }
+    DevBuf grp; std::vector<int64_t> h_grp;    // hf_estep_minlen_joined: as MinLenPosterior's
+    void release() { if (pass_made) drop_pass(); grp.release(); fwd.release(); Decoder::release(); }
     void drop_pass();
 };
 

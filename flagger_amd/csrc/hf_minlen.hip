@@ -1,7 +1,7 @@
 // hf_minlen.hip — the minimum-run-length family of the C ABI (include/hmm_flagger_hip.h), a translation unit of its own: Viterbi
 // (hf_minlen.h, hf_minlen_joined.h), the posterior (hf_minlen_post.h), admissible path sampling (hf_minlen_sample.h), the two over groups
-// of joined chunks (hf_minlen_post_joined.h), maximum-expected-accuracy decoding (hf_mea.h) and the E-step (hf_minlen_em.h), kernels and
-// host side.  The context and the decoders' shared host side come from hf_host.h; kernels of the other units (k_dec_rows_win, k_tables,
+// of joined chunks (hf_minlen_post_joined.h), maximum-expected-accuracy decoding (hf_mea.h) and the E-step, per chunk and over groups
+// (hf_minlen_em.h, hf_minlen_em_joined.h), kernels and host side.  The context and the decoders' shared host side come from hf_host.h; kernels of the other units (k_dec_rows_win, k_tables,
 // k_chunk_stats, k_reduce) are launched through their owners' launchers.  THE ORDER OF THE KERNEL HEADERS BELOW IS PART OF THE BUILD
 // (DESIGN.md 7k-m): each stands where it stood in the one-unit file relative to the others of this family, hf_minlen_joined.h last.
 // Nothing outside this unit bears on its kernels' code.
@@ -540,14 +540,18 @@ static int mle_launch_tile(const Track& tr, MinLenEM& v, hipStream_t st, int nco
     return HF_OK;
 }
 
-int hf_estep_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
-    hipStream_t st = (hipStream_t) stream;
-    const std::string w = "hf_estep_minlen";
+// hf_estep_minlen and hf_estep_minlen_joined (hf_minlen_em_joined.h, below): one front, this call's tables, the rows, then
+// `walks(track, decoder, forward lanes)` launches the entry point's two walks; everything behind them (k_mle_tile, k_chunk_stats,
+// k_reduce) is shared; `refuse`: what the entry point refuses beyond the negative_binomial model and the family's front
+template <class Refuse, class Walks>
+static int mle_run(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], hipStream_t st, const std::string& w, Refuse&& refuse,
+                   Walks&& walks) {
     int64_t lanes = 0;
     const double* nbE = nullptr;
     int rc = minlen_front(ctx, &hf_ctx::mle, p, min_len, st, w, [&] {
-        return p->model_type == HF_MODEL_NEGATIVE_BINOMIAL
-                   ? set_err(HF_E_ARG, w + ": the negative_binomial model is not supported (its statistics are another path)") : (int) HF_OK;
+        if (p->model_type == HF_MODEL_NEGATIVE_BINOMIAL)
+            return set_err(HF_E_ARG, w + ": the negative_binomial model is not supported (its statistics are another path)");
+        return (int) refuse();
     }, [&](const Track& tr, MinLenEM& v) {
         const size_t f_bytes = Slab::granule((size_t) tr.N * (size_t) lanes * 8), bytes = f_bytes + (size_t) tr.N * 128;
         int rc = mem_refuse(w, "the forward lanes and xi_adm", bytes, v.fwd.cap, "n_windows x (sum of the lengths x 8 + 128)");
@@ -574,16 +578,12 @@ int hf_estep_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], v
     Pass& ps = v.pass;
     if (tr.C > 0) HIPCHK(hipMemsetAsync(v.d_chunk, 0, (size_t) tr.C * 16, st));
     if (tr.C > 0) {
-        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
         double* d_F = reinterpret_cast<double*>(v.fwd.d_buf);
         HIPCHK(hipMemcpyAsync(ps.d_params, v.h_params, tr.params_bytes, hipMemcpyHostToDevice, st));
         launch_tables(ps, v.d_flags, false, st);   // this call's tables; the kernel clears the flag word it is given, as dec_front has done
         if (dec_work(tr)) {
             dec_launch_rows_win(tr, v, nbE, st);
-            hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3,
-                               d_F, v.d_chunk, v.d_flags);
-            hipLaunchKernelGGL(k_mle_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, d_F, v.d_xi,
-                               v.d_flags);
+            if ((rc = walks(tr, v, d_F))) return rc;
         }
         const int kc = p->ncomp[3];
         if (tr.ntiles > 0) {
@@ -596,6 +596,18 @@ int hf_estep_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], v
     HIPCHK(hipGetLastError());
     v.launched = true;
     return HF_OK;
+}
+
+int hf_estep_minlen(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], void* stream) {
+    hipStream_t st = (hipStream_t) stream;
+    return mle_run(ctx, p, min_len, st, "hf_estep_minlen", [] { return (int) HF_OK; }, [&](const Track& tr, MinLenEM& v, double* d_F) {
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3,
+                           d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mle_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, tr.d_off, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, d_F, v.d_xi,
+                           v.d_flags);
+        return (int) HF_OK;
+    });
 }
 
 int hf_estep_minlen_finish(hf_ctx* ctx, double* stats_host, double* log_z_host, void* stream) {
@@ -645,6 +657,45 @@ int hf_em_iterate_minlen(hf_ctx* ctx, hfm_model* model, const int32_t min_len[4]
     hf_params p;
     hfm_params(model, &p);
     int rc = hf_estep_minlen(ctx, &p, min_len, stream);
+    if (rc == HF_OK) rc = hf_estep_minlen_finish(ctx, stats_host, log_z_host, stream);
+    if (rc != HF_OK) return rc;
+    em_step_tail(model, stats_host, do_mstep != 0, tol, converged);
+    return HF_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------
+// the E-step over groups of joined chunks (hf_minlen_em_joined.h): hf_estep_minlen_joined shares ctx->mle, its finish and its getters
+// with hf_estep_minlen (mle_run above).  k_mlpj_fwd as it is and k_mlej_bwd, a second body of k_mle_bwd, over mlg_cut's group-as-chunk
+// offsets; the statistics run over the track's own tile plan as before, so a group's log Z_adm and log Z sit in its first chunk's
+// entries (and its element 0) and its other chunks hold 0.0 there.
+// ------------------------------------------------------------------------------------------
+#include "hf_minlen_em_joined.h"
+
+int hf_estep_minlen_joined(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], const uint8_t* joined, void* stream) {
+    const std::string w = "hf_estep_minlen_joined";
+    hipStream_t st = (hipStream_t) stream;
+    return mle_run(ctx, p, min_len, st, w, [&] { return mlg_refuse(ctx, joined, w); }, [&](const Track& tr, MinLenEM& v, double* d_F) {
+        int nb = 0;
+        const int rc = mlg_cut(tr, joined, v.grp, v.h_grp, st, w, &nb);
+        if (rc) return rc;
+        const int64_t* d_goff = reinterpret_cast<const int64_t*>(v.grp.d_buf);
+        const int l0 = (int) min_len[0], l1 = (int) min_len[1], l2 = (int) min_len[2], l3 = (int) min_len[3];
+        hipLaunchKernelGGL(k_mlpj_fwd, dim3((unsigned) tr.C, 2), dim3(64), 0, st, (int) tr.C, d_goff, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3,
+                           d_F, v.d_chunk, v.d_flags);
+        hipLaunchKernelGGL(k_mlej_bwd, dim3((unsigned) tr.C), dim3(64), 0, st, d_goff, tr.d_rec, v.d_params, v.d_rows, l0, l1, l2, l3, d_F, v.d_xi,
+                           v.d_flags);
+        return (int) HF_OK;
+    });
+}
+
+// hf_em_iterate_minlen with the E-step over groups of joined chunks: element 0 is the sum over groups of log Z_adm
+int hf_em_iterate_minlen_joined(hf_ctx* ctx, hfm_model* model, const int32_t min_len[4], const uint8_t* joined, int do_mstep, double tol,
+                                double* stats_host, double* log_z_host, int* converged, void* stream) {
+    if (!ctx || !model || !min_len || !stats_host) return set_err(HF_E_ARG, "hf_em_iterate_minlen_joined: bad argument");
+    hf_params p;
+    hfm_params(model, &p);
+    int rc = hf_estep_minlen_joined(ctx, &p, min_len, joined, stream);
     if (rc == HF_OK) rc = hf_estep_minlen_finish(ctx, stats_host, log_z_host, stream);
     if (rc != HF_OK) return rc;
     em_step_tail(model, stats_host, do_mstep != 0, tol, converged);

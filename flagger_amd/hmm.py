@@ -619,14 +619,21 @@ class EMList:
         N.check(self._L.hf_get_minlen_chunk_log_mass(self._h, _dptr(mass), _dptr(lza)), "hf_get_minlen_chunk_log_mass")
         return MinLenPosterior(self, labels, mass, lza, float(tot.value))
 
-    def estep_minlen(self, model: HMM, min_len):
+    def estep_minlen(self, model: HMM, min_len, joined=None):
         """The E-step under minimum run lengths (hf_estep_minlen + hf_estep_minlen_finish): (stats, log_z).  stats has finish()'s
         layout and holds the expected sufficient statistics under the posterior over the paths whose runs have at least min_len[s]
         windows (runs at a chunk's ends are exempt), element 0 the sum of log Z_adm; log_z is the sum of the plain log Z of the same
-        parameters.  The last pass's results, every decoder's and the next pass are left as they were."""
+        parameters.  The last pass's results, every decoder's and the next pass are left as they were.  joined: None, or a bool array
+        of n_chunks as for viterbi_minlen: the rule then holds over every group of joined chunks (hf_estep_minlen_joined), element 0
+        and log_z are sums over groups, and minlen_em_chunk_stats holds a group's values in the entries of its first chunk."""
         ml = self._four_lengths("estep_minlen", min_len)
         p = model.params()
-        N.check(self._L.hf_estep_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_estep_minlen")
+        if joined is None:
+            N.check(self._L.hf_estep_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_estep_minlen")
+        else:
+            jn = self._joined_u8("estep_minlen", joined)
+            N.check(self._L.hf_estep_minlen_joined(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream), "hf_estep_minlen_joined")
         out = np.empty(self.stats_len, dtype=np.float64)
         lz = C.c_double(0.0)
         N.check(self._L.hf_estep_minlen_finish(self._h, _dptr(out), C.byref(lz), self.stream), "hf_estep_minlen_finish")
@@ -650,15 +657,22 @@ class EMList:
         N.check(self._L.hf_get_minlen_em_chunk_stats(self._h, _dptr(cs), _dptr(lza), _dptr(lz)), "hf_get_minlen_em_chunk_stats")
         return cs, lza, lz
 
-    def em_iterate_minlen(self, model: "HMM", min_len, do_mstep: bool = True, tol: float = 1e-3) -> bool:
+    def em_iterate_minlen(self, model: "HMM", min_len, do_mstep: bool = True, tol: float = 1e-3, joined=None) -> bool:
         """em_iterate with the E-step under minimum run lengths (hf_em_iterate_minlen): the statistics in model.estimators are
         expectations over admissible paths, model.loglikelihood the objective sum of log Z_adm, self.last_log_z the plain sum of
-        log Z of the parameters the step ran with; returns the convergence flag of the M-step."""
+        log Z of the parameters the step ran with; returns the convergence flag of the M-step.  joined: as for estep_minlen
+        (hf_em_iterate_minlen_joined): both sums are then over the groups of joined chunks."""
         ml = self._four_lengths("em_iterate_minlen", min_len)
         stats = np.empty(self.stats_len, dtype=np.float64)
         cv, lz = C.c_int(0), C.c_double(0.0)
-        N.check(self._L.hf_em_iterate_minlen(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)), int(do_mstep), tol, _dptr(stats),
-                                             C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen")
+        if joined is None:
+            N.check(self._L.hf_em_iterate_minlen(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)), int(do_mstep), tol,
+                                                 _dptr(stats), C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen")
+        else:
+            jn = self._joined_u8("em_iterate_minlen", joined)
+            N.check(self._L.hf_em_iterate_minlen_joined(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        jn.ctypes.data_as(C.POINTER(C.c_uint8)), int(do_mstep), tol, _dptr(stats),
+                                                        C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen_joined")
         model.estimators = stats
         model.loglikelihood = float(stats[0])
         self.last_log_z = float(lz.value)
@@ -961,13 +975,14 @@ def EM_runOneIterationForList(emList, model: HMM, threads: int = 0) -> None:
     model.loglikelihood = float(stats[0])
 
 
-def EM_runOneMinLengthIterationForList(emList, model: HMM, min_len) -> float:
+def EM_runOneMinLengthIterationForList(emList, model: HMM, min_len, joined=None) -> float:
     """EM_runOneIterationForList with the E-step under minimum run lengths (no counterpart in the reference): model.estimators holds the
     expected statistics under the posterior over admissible paths, model.loglikelihood the sum of log Z_adm.  Returns the plain sum of
-    log Z of the same parameters.  `emList`: an EMList."""
+    log Z of the same parameters.  joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole
+    groups of joined chunks and both sums run over the groups.  `emList`: an EMList."""
     if not hasattr(emList, "estep_minlen"):
         raise TypeError("EM_runOneMinLengthIterationForList: %s has no E-step under minimum run lengths" % type(emList).__name__)
-    stats, log_z = emList.estep_minlen(model, min_len)
+    stats, log_z = emList.estep_minlen(model, min_len) if joined is None else emList.estep_minlen(model, min_len, joined)
     model.estimators = stats
     model.loglikelihood = float(stats[0])
     return log_z
@@ -1314,20 +1329,24 @@ def HMM_resetEstimators(model: HMM) -> None:
 def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergenceTol: float = 0.001,
                   outputDir: Optional[str] = None, writeParameterStatsPerIteration: bool = False,
                   is_writer: bool = True, fitAlpha: bool = False, fitAlphaEntries=FIT_ALPHA_ENTRIES, fitAlphaMax: float = FIT_ALPHA_MAX,
-                  fitAlphaEvery: int = 2, constrainedMinLen=None) -> List[float]:
+                  fitAlphaEvery: int = 2, constrainedMinLen=None, constrainedJoined=None) -> List[float]:
     """EM outer loop of hmm_flagger.c:285-488 (no --accelerate here: that loop is flagger_amd/csrc/hf_squarem.h, driven by the command line).  Returns the
     log-likelihood of every E-pass (the rows of loglikelihood.tsv).
     constrainedMinLen (an EMList only; four window counts): the EM iterations run on the E-step under minimum run lengths
     (em_iterate_minlen), so their rows hold the objective sum of log Z_adm, and length_constrained_em.tsv holds per iteration
     log Z_adm, log Z and their difference; the final inference pass stays the plain pass with the fitted parameters.
+    constrainedJoined (only with constrainedMinLen; a bool array of n_chunks, joined_chunks(store) derives it): those iterations run on
+    the E-step over groups of joined chunks (em_iterate_minlen(joined=...)); the same files, the values are the sums over groups.
     fitAlpha (an EMList only): the k-th iteration, k = 1, 2, ..., is an alpha-iteration when k is a multiple of fitAlphaEvery — its pass is
     followed by HMM_estimateAlpha alone; the others are ordinary iterations (HMM_estimateParameters alone).  The run has converged when
     the latest iteration of each kind reported convergence."""
+    if constrainedJoined is not None and constrainedMinLen is None:
+        raise ValueError("runHMMFlagger: constrainedJoined needs constrainedMinLen")
     if constrainedMinLen is not None:
         if fitAlpha:
             raise ValueError("runHMMFlagger: constrainedMinLen cannot be combined with fitAlpha")
         return _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
-                                    is_writer, constrainedMinLen)
+                                    is_writer, constrainedMinLen, constrainedJoined)
     if fitAlpha:
         return _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
                                       is_writer, fitAlphaEntries, fitAlphaMax, int(fitAlphaEvery))
@@ -1370,7 +1389,7 @@ LCEM_HEADER = "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n"
 
 
 def _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration, is_writer,
-                         min_len) -> List[float]:
+                         min_len, joined=None) -> List[float]:
     if not hasattr(emList, "em_iterate_minlen"):
         raise TypeError("runHMMFlagger(constrainedMinLen=...): %s has no E-step under minimum run lengths" % type(emList).__name__)
     if model.modelType == MODEL_NEGATIVE_BINOMIAL:
@@ -1388,7 +1407,8 @@ def _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outp
     it, converged = 1, False
     try:
         while it <= numberOfIterations and not converged:
-            converged = emList.em_iterate_minlen(model, min_len, True, convergenceTol)
+            converged = (emList.em_iterate_minlen(model, min_len, True, convergenceTol) if joined is None else
+                         emList.em_iterate_minlen(model, min_len, True, convergenceTol, joined=joined))
             lls.append(model.loglikelihood)
             if llf:
                 llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))

@@ -630,11 +630,40 @@ int hf_get_minlen_chunk_log_mass(hf_ctx *ctx, double *log_mass_host, double *log
  * The call has a parameter block, tables, rows, forward lanes, xi_adm, tile and chunk statistics of its own: the context's last full
  * pass and every getter of it, hf_viterbi*, both samplers, hf_minlen_posterior and the next hf_estep are bitwise unaffected.  One code
  * path serves HF_ALGO_SCAN and HF_ALGO_SEQ contexts: the outputs are bitwise the same on both kinds of context, across repeated calls
- * and on any stream.  hf_batch_* and hf_multi_* have no counterpart, and there is no whole-contig (joined) form. */
+ * and on any stream.  hf_batch_* and hf_multi_* have no counterpart; hf_estep_minlen_joined below is the whole-contig form. */
 int hf_estep_minlen(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4], void *stream);
 int hf_estep_minlen_finish(hf_ctx *ctx, double *stats_host, double *log_z_host /* may be NULL */, void *stream);
 int hf_get_minlen_pair_posterior(hf_ctx *ctx, int64_t first, int64_t n, double *xi_host);          /* [n][16], p-major */
 int hf_get_minlen_em_chunk_stats(hf_ctx *ctx, double *chunk_stats_host, double *log_z_adm_host, double *log_z_host);
+
+/* The E-step under minimum run lengths over groups of joined chunks (flagger_amd/csrc/hf_minlen_em_joined.h): hf_estep_minlen with
+ * hf_viterbi_minlen_joined's rule, under which only the runs at a GROUP's ends are exempt.  An EM over it maximises the sum over
+ * groups of log Z_adm(group), the mass of the set the whole-contig decoders decode in.  It is asynchronous on `stream`, finished by
+ * hf_estep_minlen_finish and read by hf_get_minlen_pair_posterior and hf_get_minlen_em_chunk_stats; it shares its state with
+ * hf_estep_minlen as hf_minlen_posterior_joined shares hf_minlen_posterior's: a later call of either replaces the earlier one's results.
+ * joined[c] != 0 joins chunk c to chunk c - 1; a chunk continues its predecessor when it is joined to it and both have windows.
+ * DEFINITION.  The joined call on (chunk list, joined) is hf_estep_minlen's definition on the GROUP-AS-CHUNK list, in which a group's
+ * first chunk holds the group's whole window range and its other chunks hold none, with the row of every joined chunk-first window t
+ * (first window of chunk c, joined to c - 1) replaced by
+ *   J_t[p][s] = end_{c-1}[p] * first_c[s]      end_{c-1}[p] = trans[region of window t-1][p][4], first_c[s] = first[s] of chunk c
+ * formed as ONE DOUBLE first and then used as A_t[p][s] wherever the definition above reads A_t; `end` is taken at the group's last
+ * window.  F is the bits the forward kernel of hf_minlen_posterior_joined stores; the backward recursion, its sum orders and its
+ * rescaling (at the walk's first vector and after every 8th step, counted from the group's last window) are that call's.
+ * PAIR POSTERIOR.  xi_adm_t is the formula above for every t >= 1 inside a group, with A_t := J_t at a joined chunk-first window (the
+ * boundary pair), and zero at a group's first window.  Identities: sum_p xi_adm_t[p][s] = post[t][s] and sum_s xi_adm_t[p][s] =
+ * post[t-1][p] of hf_minlen_posterior_joined, to rounding.  With all four lengths 1, J_t has rank 1 and a group factorises into its
+ * chunks: xi_adm, the statistics and the sum of log Z_adm agree with hf_estep_minlen's to rounding, and at a joined chunk-first window
+ * xi_adm_t[p][s] = post[t-1][p] * post[t][s].
+ * STATISTICS.  The estimator arithmetic is hf_estep_minlen's, unchanged, over the track's own pairs (w-1, w), w = 2..T_c-1 of each
+ * ORIGINAL chunk c, with the joined call's xi_adm as the counts: the reference's estimators never see a boundary pair, under this rule
+ * as under the other.  log Z_adm and log Z of a group sit in the entry of the group's first chunk, its other chunks hold exactly 0.0;
+ * element 0 of a chunk's statistics vector follows the same rule, so element 0 of the total is the sum over groups of log Z_adm and
+ * *log_z_host of the finish the sum over groups of log Z.
+ * joined == NULL or all zeros: every output is bitwise hf_estep_minlen's.
+ * HF_E_ARG: what hf_estep_minlen refuses (hf_last_error names hf_estep_minlen_joined), and joined[0] != 0.  What the call leaves
+ * untouched, the two kinds of context, repeated calls and streams: as hf_estep_minlen. */
+int hf_estep_minlen_joined(hf_ctx *ctx, const hf_params *p, const int32_t min_len[4], const uint8_t *joined /* [n_chunks] or NULL */,
+                           void *stream);
 
 /* Admissible path sampling (flagger_amd/csrc/hf_minlen_sample.h): whole paths drawn from the posterior under minimum run lengths.
  * first[s], A_t[p][s], end[s], min_len[4], admissibility (runs that contain a chunk's first or last window are exempt), the lanes (s, d)

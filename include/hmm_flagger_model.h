@@ -89,6 +89,11 @@ int hf_em_iterate(hf_ctx *ctx, hfm_model *model, int mode, int do_mstep, double 
 int hf_em_iterate_minlen(hf_ctx *ctx, hfm_model *model, const int32_t min_len[4], int do_mstep, double tol, double *stats_host,
                          double *log_z_host, int *converged, void *stream);
 
+/* hf_em_iterate_minlen with the E-step over groups of joined chunks (hf_estep_minlen_joined; joined: [n_chunks] or NULL): the model's
+ * log-likelihood becomes the sum over groups of log Z_adm, *log_z_host the sum over groups of log Z. */
+int hf_em_iterate_minlen_joined(hf_ctx *ctx, hfm_model *model, const int32_t min_len[4], const uint8_t *joined, int do_mstep, double tol,
+                                double *stats_host, double *log_z_host, int *converged, void *stream);
+
 /* hf_em_iterate for the models of a batch (hf_batch_create): one batched E-step of models[i] = the batch's model active[i] with the
  * parameters of model_objs[i], then per model its log-likelihood, and (do_mstep, full passes, status HF_OK) hfm_estimate with its
  * convergence test.  stats_host: [n_active][hf_chunk_stats_len]; status[i]: HF_E_* of model active[i]; converged[i] (may be NULL).
