@@ -124,6 +124,8 @@ def lib() -> C.CDLL:
     sig("hf_get_breakpoint_profile", C.c_int, vp, i64, i64, C.c_uint8, C.c_uint8, pd, pd)
     sig("hf_get_long_run_log_probs", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
         C.POINTER(C.c_uint8), pd, pd)
+    sig("hf_get_run_lengths", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32,
+        C.POINTER(C.c_uint8), pd)
     sig("hf_set_alpha_stats", C.c_int, vp, C.c_int)
     sig("hf_alpha_stats_len", i64, vp)
     sig("hf_get_alpha_stats", C.c_int, vp, pd)

@@ -54,7 +54,7 @@ enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
     kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks,
-    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM, kOptCrossChunkEM
+    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM, kOptCrossChunkEM, kOptRunLengths
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -102,6 +102,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"expectedGains", required_argument, nullptr, kOptExpectedGains},         // its 4x4 gain matrix [identity]
     {"lengthConstrainedEM", no_argument, nullptr, kOptLengthConstrainedEM},     // the EM iterations fit UNDER --minimumLengths (hf_estep_minlen; --l stays --labelNames: parse_options' kept[])
     {"crossChunkEM", no_argument, nullptr, kOptCrossChunkEM},             // --lengthConstrainedEM over the joined chunks of a contig (hf_estep_minlen_joined; nothing else starts with --cr, --c was ambiguous already, --le stays --lengthConstrainedEM, --l --labelNames)
+    {"runLengths", required_argument, nullptr, kOptRunLengths},          // the exact block-length spectrum up to L windows (hf_get_run_lengths; no reference option starts with r, --ru and --run stay --runConfidence: parse_options' kept[]; --runL is its shortest prefix)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -244,7 +245,15 @@ static void usage(const char* program) {
             "         --crossChunkEM               with --lengthConstrainedEM: the lengths hold over the joined chunks of a contig (the rule of\n"
             "                                      --wholeContigs and of the final BED), only runs at a contig's ends are exempt: the rows of\n"
             "                                      loglikelihood.tsv and length_constrained_em.tsv hold the sums over contigs; every other output\n"
-            "                                      stays as it is\n");
+            "                                      stays as it is\n"
+            "         --runLengths L               after the final inference, write label_block_lengths_exact.tsv: for the whole track and every\n"
+            "                                      contig, and for the label sets Err, Dup, Hap, Col and Err+Dup+Col, the exact posterior expectation\n"
+            "                                      of the number of blocks of every length 1..L windows and of more than L (L in 1..64), beside the\n"
+            "                                      counts in the final labels; blocks are merged across the chunks of a contig (the rule of\n"
+            "                                      --numBlocks).  With --minimumLengths also label_blocks_kept_exact.tsv: per scope and label the\n"
+            "                                      expected blocks, the expected blocks at or above the label's minimum (lengths in windows as for\n"
+            "                                      --enforceMinimumLengths; L must reach the largest of them less one) and the expected windows in the\n"
+            "                                      shorter ones; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -273,6 +282,7 @@ struct Options {
     int admissibleSamples = 0; bool admissibleSet = false;
     const char *expectedAccuracy = nullptr, *expectedGainsPath = nullptr;   // chunks | contigs; the gain TSV
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
+    int runLengths = 0; bool runLengthsSet = false;   // --runLengths L
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -957,6 +967,98 @@ static int write_exact_blocks(hf_ctx* ctx, const hfio_table* tab, const int8_t* 
     return HF_OK;
 }
 
+// --runLengths L: the exact block-length spectrum (hf_get_run_lengths) under the model of the last full pass.
+//   label_block_lengths_exact.tsv   per scope ("all" and every contig by name, order of first appearance in the chunk list: the sums
+//                                   over its maximal runs of consecutive chunks, in list order) and label set (Err, Dup, Hap, Col,
+//                                   Err+Dup+Col) one row per length 1..L and a row ">L": blocks_final_labels (the runs of that length of
+//                                   the set in the final labels) and blocks_expected.  Runs go on across chunks by the rule of --numBlocks.
+//   label_blocks_kept_exact.tsv     with --minimumLengths (minLenWindows not null): per scope and label its minimum in windows, the
+//                                   expected blocks, the expected blocks at or above the minimum (bin ">L" included) and the expected
+//                                   windows in the shorter ones, sum_{l < min} l N_l.
+static int write_block_lengths(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, int L, const int32_t* minLenWindows,
+                               const std::string& dir) {
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
+    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
+    const size_t B = (size_t) L + 1;
+    struct Scope { std::string name; std::vector<std::pair<int, int>> ranges; };      // a scope: its name and its chunk ranges [c0, c1)
+    std::vector<Scope> scopes;
+    scopes.push_back(Scope{"all", {}});
+    if (C > 0) scopes.back().ranges.push_back({0, C});
+    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
+    std::map<std::string, size_t> ctgScope;
+    for (int c = 0; c < C; c++) {
+        const std::string ctg = hfio_chunk_ctg(tab, c);
+        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
+        auto it = ctgScope.find(ctg);
+        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
+        auto& rg = scopes[it->second].ranges;
+        if (!rg.empty() && rg.back().second == c) rg.back().second = c + 1;
+        else rg.push_back({c, c + 1});
+    }
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> mask;
+    for (const Scope& sc : scopes)
+        for (const auto& rg : sc.ranges) {
+            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
+            for (int k = 0; k < 5; k++) { first.push_back(w.chunk_off[rg.first]); last.push_back(w.chunk_off[rg.second] - 1); mask.push_back(kSets[k]); }
+        }
+    std::vector<double> spec(first.size() * B);
+    const int rc = hf_get_run_lengths(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), L, joined.data(), spec.data());
+    if (rc != HF_OK) return rc;
+    const std::string tp = dir + "/label_block_lengths_exact.tsv", kp = dir + "/label_blocks_kept_exact.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    FILE* g = minLenWindows ? fopen(kp.c_str(), "w") : nullptr;
+    if (minLenWindows && !g) { fclose(f); hf_cli_set_error(kp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#scope\tlabel_set\tlength\tblocks_final_labels\tblocks_expected\n");
+    if (g) fprintf(g, "#scope\tlabel\tmin_len_windows\tblocks_expected\tblocks_expected_kept\twindows_expected_dropped\n");
+    size_t j = 0;
+    std::vector<int64_t> finalBlocks(5 * B);
+    std::vector<double> m(5 * B);
+    for (const Scope& sc : scopes) {
+        std::fill(finalBlocks.begin(), finalBlocks.end(), 0);
+        std::fill(m.begin(), m.end(), 0.0);                               // sums over the ranges, list order
+        for (const auto& rg : sc.ranges) {
+            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
+            int64_t run[5] = {0, 0, 0, 0, 0};                             // the windows of the set's current run
+            auto close = [&](int k) { if (run[k] > 0) finalBlocks[(size_t) k * B + (size_t) std::min<int64_t>(run[k], L + 1) - 1]++; run[k] = 0; };
+            for (int c = rg.first; c < rg.second; c++) {
+                if (c > rg.first && !joined[(size_t) c]) for (int k = 0; k < 5; k++) close(k);
+                for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
+                    const int l = finalLabels[t];
+                    for (int k = 0; k < 5; k++) {
+                        if (l >= 0 && l <= 3 && ((kSets[k] >> l) & 1)) run[k]++;
+                        else close(k);
+                    }
+                }
+            }
+            for (int k = 0; k < 5; k++) close(k);
+            for (int k = 0; k < 5; k++, j++)
+                for (size_t b = 0; b < B; b++) m[(size_t) k * B + b] += spec[j * B + b];
+        }
+        for (int k = 0; k < 5; k++)
+            for (size_t b = 0; b < B; b++) {
+                if (b < (size_t) L) fprintf(f, "%s\t%s\t%zu\t%ld\t%.10g\n", sc.name.c_str(), kSetNames[k], b + 1, (long) finalBlocks[(size_t) k * B + b], m[(size_t) k * B + b]);
+                else fprintf(f, "%s\t%s\t>%d\t%ld\t%.10g\n", sc.name.c_str(), kSetNames[k], L, (long) finalBlocks[(size_t) k * B + b], m[(size_t) k * B + b]);
+            }
+        for (int k = 0; g && k < 4; k++) {
+            double all = 0.0, kept = 0.0, dropped = 0.0;                  // in bin order
+            for (size_t b = 0; b < B; b++) {
+                const double x = m[(size_t) k * B + b];
+                all += x;
+                if ((int64_t) b + 1 >= minLenWindows[k]) kept += x; else dropped += (double) (b + 1) * x;
+            }
+            fprintf(g, "%s\t%s\t%d\t%.10g\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (int) minLenWindows[k], all, kept, dropped);
+        }
+    }
+    if (fclose(f) != 0) { if (g) fclose(g); hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    if (g && fclose(g) != 0) { hf_cli_set_error(kp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --keptBlocks: the exact probability that a scope holds a block of a label that --minimumLengths would keep (hf_get_long_run_log_probs)
 // under the model of the last full pass.
 //   kept_block_probabilities.tsv   one row for the whole track ("all"), one per contig (order of first appearance in the chunk list) and,
@@ -1280,6 +1382,7 @@ static bool parse_options(int argc, char* argv[], Options& o) {
                 break;
             }
             case kOptAdmissibleSamples: o.admissibleSet = true; o.admissibleSamples = positive_int(optarg); break;
+            case kOptRunLengths: o.runLengthsSet = true; o.runLengths = positive_int(optarg); break;
             case kOptFitAlphaEntries: {                          // pre,state[:pre,state...]
                 o.fitAlphaOptions = true;
                 memset(o.fitAlphaMask, 0, sizeof o.fitAlphaMask);
@@ -1359,6 +1462,12 @@ static bool min_len_windows(Run& s, int W) {
                     ts(), o.minLenPerState[0], o.minLenPerState[1], o.minLenPerState[3], mw[0], mw[1], mw[2], mw[3], W, HF_LONGRUN_MAX_LANES - 6);
             return false;
         }
+    // --runLengths with --minimumLengths: the bins below a label's minimum are counted one by one, so the spectrum must reach them
+    if (o.runLengthsSet && o.minLenGiven && o.runLengths < *std::max_element(mw, mw + 4) - 1) {
+        fprintf(stderr, "[%s] Error: --runLengths %d: --minimumLengths %d,%d,%d (Err,Dup,Col) are %d,%d,%d,%d windows of %d bases (Err,Dup,Hap,Col); label_blocks_kept_exact.tsv needs --runLengths of at least %d.\n",
+                ts(), o.runLengths, o.minLenPerState[0], o.minLenPerState[1], o.minLenPerState[3], mw[0], mw[1], mw[2], mw[3], W, *std::max_element(mw, mw + 4) - 1);
+        return false;
+    }
     if (!(o.enforceMinLen || o.constrainedPost || o.admissibleSet || o.expectedAccuracy || o.lengthConstrainedEM) || sum <= HF_MINLEN_MAX_LANES) return true;
     std::string who;                                           // the options that walk the expanded chain, as given
     for (const char* n : {o.enforceMinLen ? "enforceMinimumLengths" : nullptr, o.wholeContigs ? "wholeContigs" : nullptr, o.constrainedPost ? "constrainedPosterior" : nullptr,
@@ -1369,7 +1478,7 @@ static bool min_len_windows(Run& s, int W) {
             ts(), who.c_str(), mw[0], mw[1], mw[2], mw[3], W, HF_MINLEN_MAX_LANES);
     return false;
 }
-static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet || o.expectedAccuracy || o.lengthConstrainedEM; }
+static bool uses_min_len_windows(const Options& o) { return o.enforceMinLen || o.keptBlocks || o.constrainedPost || o.admissibleSet || o.expectedAccuracy || o.lengthConstrainedEM || (o.runLengthsSet && o.minLenGiven); }
 
 // --expectedGains: four lines of four tab-separated numbers, rows the true label, columns the label called, read line by line and
 // token by token as the alpha TSV is; unlike an alpha a gain may be any finite number up to 1e100 in magnitude.  false: not such a file
@@ -1444,6 +1553,7 @@ static bool check_options(Run& s) {
         {"--lengthConstrainedEM", o.lengthConstrainedEM, o.modelType != HF_MODEL_NEGATIVE_BINOMIAL ? nullptr :
                                    "needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial statistics are another path)", kOneGpuNoLoopback},
         {"--crossChunkEM", o.crossChunkEM, o.lengthConstrainedEM ? nullptr : "needs --lengthConstrainedEM", kNoGpuRule},
+        {"--runLengths", o.runLengthsSet, o.runLengths < 1 || o.runLengths > HF_RUN_LENGTHS_MAX ? "should be a number of windows between 1 and 64" : nullptr, kOneGpuNoLoopback},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
@@ -2012,6 +2122,8 @@ static int late_outputs(Run& s, EmRun& em) {
         {o.runBoundaries, "--runBoundaries needs", "final_label_run_boundaries.tsv is written", [&] { return write_run_boundaries(ctx, tab, labels, dir); }},
         {o.exactTotals, "--exactTotals needs", "label_totals_exact.tsv is written", [&] { return write_exact_totals(ctx, tab, labels, dir); }},
         {o.numBlocks, "--numBlocks needs", "label_blocks_exact.tsv is written", [&] { return write_exact_blocks(ctx, tab, labels, dir); }},
+        {o.runLengthsSet, "--runLengths needs", o.minLenGiven ? "label_block_lengths_exact.tsv and label_blocks_kept_exact.tsv are written" : "label_block_lengths_exact.tsv is written",
+         [&] { return write_block_lengths(ctx, tab, labels, o.runLengths, o.minLenGiven ? mw : nullptr, dir); }},
         {o.jointEntropy, "--jointEntropy needs", "path_uncertainty.tsv is written", [&] { return write_path_uncertainty(ctx, tab, labels, dir); }},
         {o.keptBlocks, "--keptBlocks needs", "kept_block_probabilities.tsv is written", [&] { return write_kept_blocks(ctx, tab, regions, mw, o.labelNames, dir); }},
         // (a decoder of its own: it reads the final parameters, not the last pass; its line carries the mass it found)

@@ -864,6 +864,33 @@ class EMList:
                                                   _dptr(none), _dptr(some)), "hf_get_long_run_log_probs")
         return none, some
 
+    def run_lengths(self, first, last, mask, max_len, joined=None) -> np.ndarray:
+        """The exact block-length spectrum under the model of the last full pass (hf_get_run_lengths): for every job i, the expected
+        number of maximal runs of windows of first[i]..last[i] (inclusive) whose state is in the set mask[i], by length: column l - 1
+        the runs of exactly l windows, l = 1..max_len, column max_len the runs of more than max_len windows (max_len 1..64, one for
+        the call).  joined: as for run_moments, a run goes on across a joined chunk boundary -> float64[n, max_len + 1].  Scalars
+        broadcast."""
+        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("run_lengths: a state mask must be 1..15")
+        L = int(max_len)
+        if L != max_len or not 1 <= L <= 64:
+            raise ValueError("run_lengths: max_len must be a number of windows in 1..64")
+        jn = None
+        if joined is not None:
+            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
+            if jn.size != int(self._L.hf_n_chunks(self._h)):
+                raise ValueError("run_lengths: joined must have one entry per chunk")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        out = np.empty((f.size, L + 1), dtype=np.float64)
+        N.check(self._L.hf_get_run_lengths(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)), L,
+                                           None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)), _dptr(out)),
+                "hf_get_run_lengths")
+        return out
+
     def path_entropy(self, first, last) -> np.ndarray:
         """Exact path entropy under the model of the last full pass (hf_get_path_entropy): for every job i, the Shannon entropy in nats
         of the joint posterior distribution of the labels of the windows first[i]..last[i] (inclusive; chunks are independent chains)
@@ -1131,6 +1158,15 @@ def EM_getLongRunLogProbsForList(emList, first, last, mask, min_len, joined=None
     if not hasattr(emList, "long_run_log_probs"):
         raise TypeError("EM_getLongRunLogProbsForList: %s has no long-run getter" % type(emList).__name__)
     return emList.long_run_log_probs(first, last, mask, min_len, joined)
+
+
+def EM_getRunLengthsForList(emList, first, last, mask, max_len, joined=None) -> np.ndarray:
+    """The expected number of blocks (maximal runs of windows) of first[i]..last[i] whose state lies in mask[i], by length 1..max_len
+    and above, under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run goes on
+    across the boundary (no counterpart in the reference): float64[n, max_len + 1].  `emList`: an EMList."""
+    if not hasattr(emList, "run_lengths"):
+        raise TypeError("EM_getRunLengthsForList: %s has no run-length getter" % type(emList).__name__)
+    return emList.run_lengths(first, last, mask, max_len, joined)
 
 
 def EM_getPathEntropyForList(emList, first, last) -> np.ndarray:

@@ -423,6 +423,41 @@ int hf_get_breakpoint_profile(hf_ctx *ctx, int64_t first, int64_t last, uint8_t 
 int hf_get_long_run_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
                               const int32_t *min_len, const uint8_t *joined /* [n_chunks], NULL: none */,
                               double *log_p_none_host, double *log_p_some_host /* either may be NULL, not both */);
+/* The exact block-length spectrum (flagger_amd/csrc/hf_runlen.hip), under the model of the last HF_MODE_FULL pass like hf_get_posterior:
+ * how many blocks of a label set of every length the posterior expects.  Job i is the window range first[i]..last[i] (global,
+ * inclusive, it may span chunks) and a state set S = state_mask[i] (1..15); max_len = L, 1..HF_RUN_LENGTHS_MAX, is one for the call;
+ * joined[n_chunks] is that of hf_get_run_moments with the same meaning and the same joined[0] == 0 rule.  Parts, joins and groups are
+ * those of hf_get_long_run_log_probs.  A RUN is a maximal stretch of consecutive windows of a group's concatenated sequence whose state
+ * is in S; it is clipped at the job's ends and the state may change inside S.
+ *   spectrum[i][l-1] = E[number of runs of exactly l windows | data], l = 1..L
+ *   spectrum[i][L]   = E[number of runs of more than L windows | data]
+ * each summed over the job's groups in chunk order.  Chunks are independent chains given the data.
+ * PER PART [a, b] (chunk-local), with f, b the pass's scaled vectors and A_t its rows; only ratios are formed, so no scale is needed:
+ *   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q'], a < u <= b   (the posterior chain; q' = 0..3 in order; a denominator of
+ *                                                                           0 gives a zero row: no mass can reach it)
+ *   sigma_a[s] = gamma_a(s);  sigma_t[s] = sum_{p not in S} f_{t-1}[p] A_t[p][s] b_t[s] / sum_{p,s} f_{t-1}[p] A_t[p][s] b_t[s], t > a
+ * for s in S, zero outside (the pair posterior of a run start, summed over p in order, never formed as gamma - xi).  The run started at
+ * t walks from v_1 = sigma_t; at age d it stands at window u = t + d - 1.  At u = b it is OPEN at b: sum v_d goes to Rc[d], or to W if
+ * t = a.  Otherwise w = v_d Q_{u+1}; sum_{q not in S} w[q] closes a run of exactly d windows, into I[d] for t > a or Lc[d] for t = a
+ * (left-touching), and v_{d+1} = w o 1_S.  A run still in S at age L + 1 adds sum v_{L+1} to bin "> L" of I or Lc and is dropped: it is
+ * counted once, where it saturates.  A part yields I[1..L+1], Lc[1..L+1], Rc[1..L], W, s = gamma_a(S), e = gamma_b(S) and its length T.
+ * A GROUP is stitched on the host left to right (flagger_amd/csrc/hf_runlen_stitch.h), from o[1..L] = 0, O = 0, N = 0, for every part:
+ *   N += I;  N[l'] += o[l'] (1 - s);  for l = 1..L+1: N[l] += (1 - O) Lc[l] and N[min(l' + l, L + 1)] += o[l'] Lc[l], l' = 1..L;
+ *   T <= L: the new o gets (1 - O) W at T and o[l'] W at l' + T (N[L + 1] where l' + T > L);  the new o[d] += Rc[d];  O = e
+ * and N[l'] += o[l'] after the last part.
+ * Exact cases: a job's values depend only on (first, last, mask, L, joined) and the pass, bitwise: not on the other jobs of the call,
+ * their order, their number or the device batch (HF_RL_BATCH_PARTS, HF_RL_BATCH_PIECES); joined all zero is NULL; without a join a job
+ * is bitwise the left-to-right sum of its parts asked as separate jobs; bin "> L" is exactly 0.0 when no group of the job has more than
+ * L windows; every bin is >= 0 and never NaN, also on emission-floor stretches and where S has posterior 0 (every bin 0.0 then).
+ * Synchronous on the pass's stream; the first call after an EM pass of the default algorithm re-runs the segment kernel once, as
+ * hf_get_posterior's does, also in several sub-passes.  HF_ALGO_SCAN and HF_ALGO_SEQ, all three model types.  Buffers of its own:
+ * nothing an EM pass or another getter reads is written.  n = 0 is a successful no-op.  HF_E_ARG: the cases of
+ * hf_get_interval_log_probs, max_len outside 1..HF_RUN_LENGTHS_MAX, joined[0] != 0, a NULL output with n > 0; any bad job refuses the
+ * whole call.  hf_batch_* and hf_multi_* have no counterpart. */
+#define HF_RUN_LENGTHS_MAX 64
+int hf_get_run_lengths(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
+                       int32_t max_len /* L, 1..HF_RUN_LENGTHS_MAX, one for the call */,
+                       const uint8_t *joined /* [n_chunks], NULL: none */, double *spectrum_host /* [n][L + 1] */);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
