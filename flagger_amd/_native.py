@@ -126,6 +126,7 @@ def lib() -> C.CDLL:
         C.POINTER(C.c_uint8), pd, pd)
     sig("hf_get_run_lengths", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32,
         C.POINTER(C.c_uint8), pd)
+    sig("hf_get_count_distribution", C.c_int, vp, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, pd)
     sig("hf_set_alpha_stats", C.c_int, vp, C.c_int)
     sig("hf_alpha_stats_len", i64, vp)
     sig("hf_get_alpha_stats", C.c_int, vp, pd)

@@ -13,6 +13,7 @@
 #include "../../include/hmm_flagger_io.h"
 #include "../../include/hmm_flagger_model.h"
 #include "../../include/hmm_flagger_multi.h"
+#include "hf_countdist_stitch.h"
 #include "hf_jobs.h"
 #include "hf_squarem.h"
 #include <getopt.h>
@@ -54,7 +55,7 @@ enum LongOnly {
     kOptDevice = 1001, kOptHipAlgo, kOptGpus, kOptExchange, kOptViterbi, kOptSweepAlpha, kOptUncertaintySamples, kOptUncertaintySeed,
     kOptRunConfidence, kOptRegionProbs, kOptFitAlpha, kOptFitAlphaEntries, kOptFitAlphaMax, kOptFitAlphaEvery, kOptExactTotals,
     kOptNumBlocks, kOptJointEntropy, kOptRunBoundaries, kOptEnforceMinLen, kOptKeptBlocks, kOptConstrainedPosterior, kOptAdmissibleSamples, kOptWholeContigs, kOptMergedChunks,
-    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM, kOptCrossChunkEM, kOptRunLengths
+    kOptExpectedAccuracy, kOptExpectedGains, kOptLengthConstrainedEM, kOptCrossChunkEM, kOptRunLengths, kOptTotalsDistribution
 };
 static struct option long_options[] = {                   // hmm_flagger.c:578-608
     {"input", required_argument, nullptr, 'i'}, {"preset", required_argument, nullptr, 'x'},
@@ -103,6 +104,7 @@ static struct option long_options[] = {                   // hmm_flagger.c:578-6
     {"lengthConstrainedEM", no_argument, nullptr, kOptLengthConstrainedEM},     // the EM iterations fit UNDER --minimumLengths (hf_estep_minlen; --l stays --labelNames: parse_options' kept[])
     {"crossChunkEM", no_argument, nullptr, kOptCrossChunkEM},             // --lengthConstrainedEM over the joined chunks of a contig (hf_estep_minlen_joined; nothing else starts with --cr, --c was ambiguous already, --le stays --lengthConstrainedEM, --l --labelNames)
     {"runLengths", required_argument, nullptr, kOptRunLengths},          // the exact block-length spectrum up to L windows (hf_get_run_lengths; no reference option starts with r, --ru and --run stay --runConfidence: parse_options' kept[]; --runL is its shortest prefix)
+    {"totalsDistribution", required_argument, nullptr, kOptTotalsDistribution},   // the exact distribution of a region's label totals up to K windows (hf_get_count_distribution; no option starts with --to: it is its shortest prefix, --t was ambiguous already, --th stays --threads and --tr --trackName)
     {nullptr, 0, nullptr, 0}};
 
 static void usage(const char* program) {
@@ -253,7 +255,12 @@ static void usage(const char* program) {
             "                                      --numBlocks).  With --minimumLengths also label_blocks_kept_exact.tsv: per scope and label the\n"
             "                                      expected blocks, the expected blocks at or above the label's minimum (lengths in windows as for\n"
             "                                      --enforceMinimumLengths; L must reach the largest of them less one) and the expected windows in the\n"
-            "                                      shorter ones; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n");
+            "                                      shorter ones; one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n"
+            "         --totalsDistribution K       with --regionProbs FILE: after the final inference, write region_label_totals_exact.tsv: for every\n"
+            "                                      region and the label sets Err, Dup, Hap, Col and Err+Dup+Col the exact posterior distribution of the\n"
+            "                                      NUMBER OF WINDOWS of the region in the set: p_0 .. p_K and p_gtK (K in 1..62), their mean (NA where\n"
+            "                                      p_gtK > 0) and the quantiles q025, q50, q975 (the smallest k whose cumulative probability reaches the\n"
+            "                                      level; >K beyond the bins); one GPU, not with --gpus N>1, HF_LOOPBACK_RANKS or --sweepAlpha\n");
 }
 
 static bool dir_exists(const char* p) { struct stat sb; return stat(p, &sb) == 0 && S_ISDIR(sb.st_mode); }
@@ -283,6 +290,7 @@ struct Options {
     const char *expectedAccuracy = nullptr, *expectedGainsPath = nullptr;   // chunks | contigs; the gain TSV
     bool runConfidence = false, exactTotals = false, numBlocks = false, jointEntropy = false, runBoundaries = false;
     int runLengths = 0; bool runLengthsSet = false;   // --runLengths L
+    int totalsDistribution = 0; bool totalsDistributionSet = false;   // --totalsDistribution K
     const char* regionProbsPath = nullptr;
     bool fitAlpha = false, fitAlphaBad = false, fitAlphaOptions = false;
     uint8_t fitAlphaMask[16] = {1, 0, 1, 0,  0, 1, 1, 0,  1, 1, 1, 1,  0, 0, 1, 1};   // the ten entries the reference's tuner frees
@@ -1059,6 +1067,75 @@ static int write_block_lengths(hf_ctx* ctx, const hfio_table* tab, const int8_t*
     return HF_OK;
 }
 
+// --totalsDistribution K: the exact distribution of a region's label totals (hf_get_count_distribution) under the model of the last full
+// pass.
+//   region_label_totals_exact.tsv   per region (file order) and label set (Err, Dup, Hap, Col, Err+Dup+Col) one row: the leading columns
+//                                   of region_label_probabilities.tsv (ctg start end name n_windows: the windows whose bases meet
+//                                   [start, end)), label_set, mean = sum k p_k in increasing k (NA where p_gtK > 0), q025 q50 q975 (the
+//                                   smallest k whose cumulative sum in increasing k reaches the level; >K when bin K does not reach it),
+//                                   then p_0 .. p_K p_gtK.  A region without windows: NA in every column behind label_set.
+// A region's windows are a union of index ranges that lie in different chunks (region_windows), so its distribution is the convolution
+// of its ranges' in range order: the getter's own stitch (hf_countdist_stitch.h).
+static int write_region_totals(hf_ctx* ctx, const hfio_table* tab, const std::vector<Region>& regions, int K, const std::string& dir) {
+    const int C = hfio_n_chunks(tab);
+    hf_windows w{};
+    hfio_windows(tab, &w);
+    std::vector<int64_t> wbases;
+    window_bases(w, C, wbases, nullptr);
+    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
+    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
+    const size_t B = cd_part_len(K);
+    std::vector<std::vector<int64_t>> wins;
+    std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
+    region_windows(tab, w, C, wbases, regions, wins, ranges);
+    std::vector<int64_t> first, last;
+    std::vector<uint8_t> mask;
+    for (size_t i = 0; i < regions.size(); i++)
+        for (const auto& r : ranges[i])
+            for (int k = 0; k < 5; k++) { first.push_back(r.first); last.push_back(r.second); mask.push_back(kSets[k]); }
+    std::vector<double> dist(first.size() * B);
+    const int rc = hf_get_count_distribution(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), K, dist.data());
+    if (rc != HF_OK) return rc;
+    const std::string tp = dir + "/region_label_totals_exact.tsv";
+    FILE* f = fopen(tp.c_str(), "w");
+    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    fprintf(f, "#ctg\tstart\tend\tname\tn_windows\tlabel_set\tmean\tq025\tq50\tq975");
+    for (int k = 0; k <= K; k++) fprintf(f, "\tp_%d", k);
+    fprintf(f, "\tp_gtK\n");
+    size_t j = 0;                                                  // the region's first job
+    CdStitch stitch(K);
+    std::vector<double> p(B);
+    for (size_t i = 0; i < regions.size(); i++) {
+        const Region& g = regions[i];
+        for (int k = 0; k < 5; k++) {
+            fprintf(f, "%s\t%ld\t%ld\t%s\t%zu\t%s", g.ctg.c_str(), (long) g.start, (long) g.end, g.name.c_str(), wins[i].size(), kSetNames[k]);
+            if (wins[i].empty()) {
+                for (size_t b = 0; b < B + 4; b++) fprintf(f, "\tNA");
+                fprintf(f, "\n");
+                continue;
+            }
+            stitch.begin();
+            for (size_t r = 0; r < ranges[i].size(); r++) stitch.part(&dist[(j + r * 5 + (size_t) k) * B]);
+            stitch.end(p.data());
+            double mean = 0.0, cum = 0.0;
+            int q[3] = {-1, -1, -1};                               // (-1: beyond bin K)
+            static const double kLevels[3] = {0.025, 0.5, 0.975};
+            for (int b = 0; b <= K; b++) {
+                mean += (double) b * p[(size_t) b];
+                cum += p[(size_t) b];
+                for (int l = 0; l < 3; l++) if (q[l] < 0 && cum >= kLevels[l]) q[l] = b;
+            }
+            if (p[B - 1] > 0.0) fprintf(f, "\tNA"); else fprintf(f, "\t%.6f", mean);
+            for (int l = 0; l < 3; l++) { if (q[l] < 0) fprintf(f, "\t>%d", K); else fprintf(f, "\t%d", q[l]); }
+            for (size_t b = 0; b < B; b++) fprintf(f, "\t%.6g", p[b]);
+            fprintf(f, "\n");
+        }
+        j += ranges[i].size() * 5;
+    }
+    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    return HF_OK;
+}
+
 // --keptBlocks: the exact probability that a scope holds a block of a label that --minimumLengths would keep (hf_get_long_run_log_probs)
 // under the model of the last full pass.
 //   kept_block_probabilities.tsv   one row for the whole track ("all"), one per contig (order of first appearance in the chunk list) and,
@@ -1383,6 +1460,7 @@ static bool parse_options(int argc, char* argv[], Options& o) {
             }
             case kOptAdmissibleSamples: o.admissibleSet = true; o.admissibleSamples = positive_int(optarg); break;
             case kOptRunLengths: o.runLengthsSet = true; o.runLengths = positive_int(optarg); break;
+            case kOptTotalsDistribution: o.totalsDistributionSet = true; o.totalsDistribution = positive_int(optarg); break;
             case kOptFitAlphaEntries: {                          // pre,state[:pre,state...]
                 o.fitAlphaOptions = true;
                 memset(o.fitAlphaMask, 0, sizeof o.fitAlphaMask);
@@ -1554,6 +1632,8 @@ static bool check_options(Run& s) {
                                    "needs --modelType gaussian or trunc_exp_gaussian (the negative_binomial statistics are another path)", kOneGpuNoLoopback},
         {"--crossChunkEM", o.crossChunkEM, o.lengthConstrainedEM ? nullptr : "needs --lengthConstrainedEM", kNoGpuRule},
         {"--runLengths", o.runLengthsSet, o.runLengths < 1 || o.runLengths > HF_RUN_LENGTHS_MAX ? "should be a number of windows between 1 and 64" : nullptr, kOneGpuNoLoopback},
+        {"--totalsDistribution", o.totalsDistributionSet, o.totalsDistribution < 1 || o.totalsDistribution > HF_COUNT_DIST_MAX ? "should be a number of windows between 1 and 62" :
+                                  o.regionProbsPath ? nullptr : "needs --regionProbs", kOneGpuNoLoopback},
     };
     // (every line of the region file is checked here)
     if (!check_rows(o, beforeRegions) || (o.regionProbsPath && !read_regions(o.regionProbsPath, s.regions)) || !check_rows(o, afterRegions)) return false;
@@ -2152,6 +2232,8 @@ static int late_outputs(Run& s, EmRun& em) {
              return write_sample_outputs(admissible_sampler(ctx, mw, joined, o.uncertaintySeed), em.model, tab, labels, o.admissibleSamples, o.labelNames, dir,
                                          "admissible_samples_summary.tsv", "admissible_label_runs_support.bed");
          }},
+        {o.totalsDistributionSet, "--totalsDistribution needs", "region_label_totals_exact.tsv is written",
+         [&] { return write_region_totals(ctx, tab, *regions, o.totalsDistribution, dir); }},
     };
     for (const LateOutput& out : outputs) {
         if (!out.wanted) continue;

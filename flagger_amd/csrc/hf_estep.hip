@@ -18,7 +18,7 @@
 //                k_fwd_seq / k_bwd_seq (one wavefront per chunk, sequential recurrences)
 // There is no CPU fallback: without a HIP device hf_create fails with HF_E_NOGPU.
 //
-// The library is four translation units over one host header (hf_host.h: the slab, the track, the pass and decoder states, the context,
+// The library is five translation units over one host header (hf_host.h: the slab, the track, the pass and decoder states, the context,
 // what crosses a unit boundary):
 //   hf_estep.hip     this one: host pool and pinned cache, hf_create.h, the pass, hf_finish and the exchange entry points, the lazy getters
 //                    of the pass (hf_get_labels / _posterior / _forward_backward), profiling, self-tests, hf_batch.h; at its end
@@ -27,6 +27,7 @@
 //   hf_decoders.hip  hf_decode.h, hf_viterbi.h, hf_sample.h: hf_viterbi*, hf_sample_*
 //   hf_minlen.hip    the minimum-run-length family: hf_minlen*.h, hf_mea.h
 //   hf_runlen.hip    the block-length spectrum hf_get_run_lengths (its host-only stitch: hf_runlen_stitch.h)
+//   hf_countdist.hip the distribution of label totals hf_get_count_distribution (its host-only stitch: hf_countdist_stitch.h)
 // Every kernel is compiled in exactly one of them; the other units reach this unit's kernels through launch_tables, launch_chunk_stats
 // and launch_reduce.
 #include "hf_host.h"
@@ -768,6 +769,7 @@ void hf_destroy(hf_ctx* ctx) {
     ctx->bp.release();
     ctx->lr.release();
     ctx->rl.release();
+    ctx->cd.release();
     ctx->mea.release();
     ctx->mle.release();
     ctx->tr.slab.release();

@@ -27,7 +27,7 @@ static_assert(HF_IV_PIECE == 512 && HF_MO_PIECE == 512 && HF_RN_PIECE == 512 && 
 // What every range getter refuses, in this order: n < 0, `early` (a refusal of the getter's own that ranks here, or nullptr), NULL arrays,
 // no full pass, `late` (the same), and job by job a bad range, a window outside every chunk, a state mask outside 1..15 (state_mask ==
 // nullptr: the getter has none) and a region outside -1..n_regions-1 (region == nullptr: no filter).
-// (declared in hf_host.h, with the defaults region = early = late = nullptr: hf_runlen.hip's getter calls it too)
+// (declared in hf_host.h, with the defaults region = early = late = nullptr: the getters of hf_runlen.hip and hf_countdist.hip call it too)
 int rg_check(const hf_ctx* ctx, const std::string& who, int64_t n, bool null_array, const int64_t* first, const int64_t* last,
              const uint8_t* state_mask, const int32_t* region, const char* early, const char* late) {
     const Track& tr = ctx->tr;

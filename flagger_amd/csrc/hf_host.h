@@ -1,8 +1,8 @@
 // hf_host.h — the host side that the translation units of libhmmflagger_hip.so share: the error string, the slab, the track, the pass
 // state, the decoders' states and the context; the host functions that cross a unit boundary; the host templates that take lambdas.
 // No kernel is defined here.  Units: hf_estep.hip (context, hf_create, the pass, hf_batch.h, and hf_getters.h: range getters, alpha
-// statistics), hf_decoders.hip (Viterbi, path sampling), hf_minlen.hip (the minimum-run-length family) and hf_runlen.hip (the block-length
-// spectrum).  EVERY __global__ FUNCTION IS
+// statistics), hf_decoders.hip (Viterbi, path sampling), hf_minlen.hip (the minimum-run-length family), hf_runlen.hip (the block-length
+// spectrum) and hf_countdist.hip (the distribution of label totals).  EVERY __global__ FUNCTION IS
 // COMPILED IN EXACTLY ONE UNIT: a unit that needs another's kernel calls the owner's launcher
 // declared below (a second copy of a plain kernel is a duplicate symbol at link time), and a unit that needs only the __device__ helpers
 // of a header whose kernels another unit owns defines HF_HELPERS_ONLY in front of its includes.
@@ -357,6 +357,7 @@ struct hf_ctx {
     DevBuf bp;                // hf_breakpoint.h: pieces, parts, piece products, the chain's vectors, the windows' weights, results
     DevBuf lr;                // hf_longrun.h: parts, groups, results
     DevBuf rl;                // hf_runlen.hip: pieces, parts, piece bins, part records
+    DevBuf cd;                // hf_countdist.hip: pieces, parts, piece transfers, part distributions
     MeaDecoder mea;           // hf_mea.h: hf_get_mea_labels
     MinLenEM mle;             // hf_minlen_em.h: hf_estep_minlen
 };

@@ -891,6 +891,26 @@ class EMList:
                 "hf_get_run_lengths")
         return out
 
+    def count_distribution(self, first, last, mask, max_count) -> np.ndarray:
+        """The exact distribution of label totals under the model of the last full pass (hf_get_count_distribution): for every job i,
+        the posterior probability that exactly k windows of first[i]..last[i] (inclusive) have a state in the set mask[i]: column k
+        for k = 0..max_count, column max_count + 1 the probability of more than max_count windows (max_count 1..62, one for the
+        call) -> float64[n, max_count + 2].  Scalars broadcast."""
+        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
+        if m.size and (m.min() < 0 or m.max() > 255):
+            raise ValueError("count_distribution: a state mask must be 1..15")
+        K = int(max_count)
+        if K != max_count or not -2**31 <= K < 2**31:
+            raise ValueError("count_distribution: max_count must be a whole number of windows (the library refuses one outside 1..62)")
+        f = np.ascontiguousarray(f.ravel(), np.int64)
+        l = np.ascontiguousarray(l.ravel(), np.int64)
+        m = np.ascontiguousarray(m.ravel(), np.uint8)
+        out = np.empty((f.size, max(K, 0) + 2), dtype=np.float64)
+        N.check(self._L.hf_get_count_distribution(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)), K,
+                                                  _dptr(out)), "hf_get_count_distribution")
+        return out
+
     def path_entropy(self, first, last) -> np.ndarray:
         """Exact path entropy under the model of the last full pass (hf_get_path_entropy): for every job i, the Shannon entropy in nats
         of the joint posterior distribution of the labels of the windows first[i]..last[i] (inclusive; chunks are independent chains)
@@ -1167,6 +1187,15 @@ def EM_getRunLengthsForList(emList, first, last, mask, max_len, joined=None) -> 
     if not hasattr(emList, "run_lengths"):
         raise TypeError("EM_getRunLengthsForList: %s has no run-length getter" % type(emList).__name__)
     return emList.run_lengths(first, last, mask, max_len, joined)
+
+
+def EM_getCountDistributionForList(emList, first, last, mask, max_count) -> np.ndarray:
+    """The posterior distribution of the number of windows of first[i]..last[i] whose state lies in mask[i], under the model of the
+    last full pass, per job: P(N = k), k = 0..max_count, and P(N > max_count) (no counterpart in the reference):
+    float64[n, max_count + 2].  `emList`: an EMList."""
+    if not hasattr(emList, "count_distribution"):
+        raise TypeError("EM_getCountDistributionForList: %s has no count-distribution getter" % type(emList).__name__)
+    return emList.count_distribution(first, last, mask, max_count)
 
 
 def EM_getPathEntropyForList(emList, first, last) -> np.ndarray:

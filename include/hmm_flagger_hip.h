@@ -458,6 +458,45 @@ int hf_get_long_run_log_probs(hf_ctx *ctx, int64_t n, const int64_t *first, cons
 int hf_get_run_lengths(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
                        int32_t max_len /* L, 1..HF_RUN_LENGTHS_MAX, one for the call */,
                        const uint8_t *joined /* [n_chunks], NULL: none */, double *spectrum_host /* [n][L + 1] */);
+/* The exact distribution of label totals (flagger_amd/csrc/hf_countdist.hip), under the model of the last HF_MODE_FULL pass like
+ * hf_get_posterior: how probable it is that exactly k windows of a range carry a label of a set.  Job i is the window range
+ * first[i]..last[i] (global, inclusive, it may span chunks; refusals and parts are those of hf_get_interval_log_probs) and a state set
+ * S = state_mask[i] (1..15); max_count = K, 1..HF_COUNT_DIST_MAX, is one for the call.  N = sum_t 1[s_t in S] over the job's windows:
+ *   dist[i][k]     = P(N = k | data), k = 0..K
+ *   dist[i][K + 1] = P(N > K | data)
+ * K + 2 <= 64 bins.  The unit is windows; there is no region filter and no `joined` argument: a total does not depend on how chunks
+ * are joined.  (hf_get_count_moments gives the mean and variance of the same N without a bound on it.)
+ * PER PART [a, b] (chunk-local), with f, b the pass's scaled vectors and A_t its rows; only ratios are formed, so no scale is needed:
+ *   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q'], a < u <= b   (hf_get_run_lengths' posterior chain; q' = 0..3 in order; a
+ *                                                                           denominator of 0 gives a zero row: no mass can reach it)
+ *   gamma_a[s] = f_a[s] b_a[s] / sum_s' f_a[s'] b_a[s']                     (s' in order; all 0.0 where the pass left no weight)
+ * The walk carries v[s][k], k = 0..K and K + 1 for "more than K": v_a[s][1_S[s]] = gamma_a[s], every other entry 0.  Per window
+ * u = a+1..b: w[q][k] = ((v[0][k] Q_u[0][q] + v[1][k] Q_u[1][q]) + v[2][k] Q_u[2][q]) + v[3][k] Q_u[3][q]; for q not in S v[q][k] = w[q][k];
+ * for q in S v[q][k] = w[q][k-1] for 1 <= k <= K, v[q][0] = 0 and v[q][K+1] = w[q][K+1] + w[q][K].  The part's distribution is
+ * ((v_b[0][k] + v_b[1][k]) + v_b[2][k]) + v_b[3][k].  Every bin is a sum of non-negative terms; "> K" is carried, never formed as 1 - sum.
+ * ON THE DEVICE the walk runs piece by piece of the getters' 512-window grid: a piece yields its transfer M[p][q][k] (the walk above
+ * from the unit vector "state p in front of the piece, no window counted", k = 0..K+1), and the part takes its pieces in order,
+ *   k <= K:  c[p][q] = sum_{j=0..k} v[p][j] M[p][q][k-j]                            (one accumulator from 0.0, j ascending)
+ *   "> K":   c[p][q] = sum_{j=0..K+1} v[p][j] r_j,  r_j = sum_{m=K+1-j..K+1} M[p][q][m]
+ * where r_j is ONE running tail sum that takes M[p][q][K+1-j] at step j: it adds M downwards from the "> K" bin, r_0 = 0.0 + M[p][q][K+1],
+ * and the outer sum is one accumulator from 0.0, j ascending (index K + 1 of v is its own "> K" bin, which meets the whole of M); then
+ * v[q] = ((c[0][q] + c[1][q]) + c[2][q]) + c[3][q].  A part with a = b has no piece and is gamma_a alone.
+ * A JOB is the truncated convolution of its parts' distributions in chunk order, on the host (flagger_amd/csrc/hf_countdist_stitch.h): the
+ * first part as it is, every further part d folded in by the same two sums (acc for v[p], d for M[p][q]).  Chunks are independent
+ * chains given the data.
+ * Exact cases: a job's values depend only on (first, last, mask, K) and the pass, bitwise: not on the other jobs of the call, their
+ * order, their number or the device batch (HF_CD_BATCH_PARTS, HF_CD_BATCH_PIECES); a job over several chunks is bitwise the host stitch
+ * of its parts asked as separate jobs; for a job of T windows the bins k > T are exactly 0.0, so bin "> K" is exactly 0.0 when T <= K;
+ * with mask 15 every bin but T (bin "> K" when T > K) is exactly 0.0; every bin is >= 0 and never NaN, also on emission-floor stretches
+ * and where S has posterior 0 (bin 0 carries the mass then).
+ * Synchronous on the pass's stream; the first call after an EM pass of the default algorithm re-runs the segment kernel once, as
+ * hf_get_posterior's does, also in several sub-passes.  HF_ALGO_SCAN and HF_ALGO_SEQ, all three model types.  Buffers of its own:
+ * nothing an EM pass, a decoder or another getter reads is written.  n = 0 is a successful no-op.  HF_E_ARG: the cases of
+ * hf_get_interval_log_probs, max_count outside 1..HF_COUNT_DIST_MAX, a NULL output with n > 0; any bad job refuses the whole call.
+ * hf_batch_* and hf_multi_* have no counterpart. */
+#define HF_COUNT_DIST_MAX 62
+int hf_get_count_distribution(hf_ctx *ctx, int64_t n, const int64_t *first, const int64_t *last, const uint8_t *state_mask,
+                              int32_t max_count /* K, 1..HF_COUNT_DIST_MAX, one for the call */, double *dist_host /* [n][K + 2] */);
 /* The alpha statistics (flagger_amd/csrc/hf_alpha.h): what an EM needs to fit the matrix alpha[pre][s] itself.  Models gaussian and
  * trunc_exp_gaussian.  For a pair of windows (t-1, t) of one chunk, t >= 1, with r the region of window t, x and x_prev the coverage of t
  * and t-1 as the pass sees them (8 bits), beta = beta_t:
