@@ -1,7 +1,7 @@
 // hf_chain.h — the core of the walkers of a chain expanded by run length, one lane of a 64-lane wavefront per expanded state:
 // hf_viterbi_minlen and, over whole contigs, hf_viterbi_minlen_joined (hf_minlen.h), hf_get_long_run_log_probs (hf_longrun.h) and
-// hf_minlen_posterior (hf_minlen_post.h; over whole contigs hf_minlen_post_joined.h).  Three things, each here once: the wave primitives, the lane geometry of the minimum-run-length
-// expansion, the forward row staging (its tile and rules).
+// hf_minlen_posterior (hf_minlen_post.h; over whole contigs hf_minlen_post_joined.h).  Four things, each here once: the wave primitives, the lane geometry of the minimum-run-length
+// expansion, the forward row staging (its tile and rules), and the posterior chain that hf_runlen.hip and hf_countdist.hip walk.
 //
 // THE EXPANSION by minimum run lengths.  min_len[s] >= 1 windows per state, sum <= 64.  Lanes (s, d), d = 1 .. min_len[s]: "in state s,
 // the current run has d windows so far"; at d = min_len[s] "at least that many" (the SATURATED lane; d = 1 is the ENTRY lane; with
@@ -121,6 +121,32 @@ __device__ __forceinline__ void ch_step_back(unsigned mpack, W w, int& cs, int& 
     const int down = (cd < ch_len(mpack, cs)) | (stayed ^ 1);
     cd = entry ? ch_len(mpack, p) : cd - down;
     cs = entry ? p : cs;
+}
+
+// ---- the posterior chain of the lane-per-age and lane-per-bin walkers (hf_runlen.hip, hf_countdist.hip) --------------------------
+// Given the data the states of a chunk are a Markov chain.  Its rows at a window with row A of the pass and backward vector b:
+// r[p * 4 + q] = Q[p][q] = A[p][q] b[q] / sum_q' A[p][q'] b[q'] (q' = 0..3 in order); a row whose denominator is 0 is a zero row
+__device__ __forceinline__ void ch_post_rows(const double A[16], const double b[4], double r[16]) {
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        double y[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) y[q] = A[p * 4 + q] * b[q];
+        const double den = ((y[0] + y[1]) + y[2]) + y[3];
+#pragma unroll
+        for (int q = 0; q < 4; q++) r[p * 4 + q] = den > 0.0 ? y[q] / den : 0.0;
+    }
+}
+
+// ... and its start at a part's first window: g[s] = f[s] b[s] / sum_s' f[s'] b[s'] (s' in order) for the states of the bit set `keep`,
+// 0.0 for the others and where the sum is 0
+__device__ __forceinline__ void ch_post_start(const double f[4], const double b[4], int keep, double g[4]) {
+    double y[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) y[s] = f[s] * b[s];
+    const double tot = ((y[0] + y[1]) + y[2]) + y[3];
+#pragma unroll
+    for (int s = 0; s < 4; s++) g[s] = (((keep >> s) & 1) && tot > 0.0) ? y[s] / tot : 0.0;
 }
 
 // ---- forward row staging: the tile (the turn of it is written out in the three forward kernels, see above) -------------------------

@@ -5,9 +5,9 @@
 // its own only (hf_ctx::cd).
 //
 // Definition.  Given the data the states of a chunk are a Markov chain, and only ratios of the pass's values are formed:
-//   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q']       the posterior chain of hf_runlen.hip, a < u <= b (q' = 0..3 in order;
-//                                                                   a row whose denominator is 0 is a zero row: no mass reaches it)
-//   gamma_a[s] = f_a[s] b_a[s] / sum_s' f_a[s'] b_a[s']             the start at the part's first window (s' in order; 0.0 where the sum is 0)
+//   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q']       the posterior chain, a < u <= b (ch_post_rows of hf_chain.h: q' = 0..3 in
+//                                                                   order; a row whose denominator is 0 is a zero row: no mass reaches it)
+//   gamma_a[s] = f_a[s] b_a[s] / sum_s' f_a[s'] b_a[s']             the start at the part's first window (ch_post_start: 0.0 where the sum is 0)
 // The walk carries v[s][k], "in state s, k windows of S so far" (k = 0 .. K, and K + 1 for "more than K"): v_a[s][1_S[s]] = gamma_a[s];
 // per window u, w[q][k] = ((v[0][k] Q[0][q] + v[1][k] Q[1][q]) + v[2][k] Q[2][q]) + v[3][k] Q[3][q]; a column q outside S keeps w, a
 // column in S moves up one bin: v[q][k] = w[q][k - 1], v[q][0] = 0, v[q][> K] = w[q][> K] + w[q][K].  The part's distribution is
@@ -29,11 +29,10 @@
 //                  r_0 = 0.0 + M[p][q][K + 1]; index K + 1 of v is its own "> K" bin, which meets the whole of M).  Then
 //                  v[q] = ((c[0][q] + c[1][q]) + c[2][q]) + c[3][q].  At the end the lane sums its bin over q in state order.  A part with
 //                  a == b has no piece and is gamma_a alone.
-// The host convolves the parts of a job in chunk order (hf_countdist_stitch.h, the same two sums).  A piece depends on (its windows, S, K)
-// alone and a part on (a, b, S, K), so a job's bits do not depend on the other jobs of a call, their order or the device batch.
+// The host side is rg_run of hf_rg.h; its fold convolves the parts of a job in chunk order (hf_countdist_stitch.h, the same two sums).
+// A piece depends on (its windows, S, K) alone and a part on (a, b, S, K), so a job's bits depend on no other job, order or device batch.
 #define HF_HELPERS_ONLY   // of hf_decode.h (kernels: hf_decoders.hip)
-#include "hf_host.h"
-#include "hf_jobs.h"
+#include "hf_rg.h"
 #include "hf_view.h"
 #include "hf_chain.h"
 #include "hf_countdist_stitch.h"
@@ -44,7 +43,7 @@ static_assert(HF_COUNT_DIST_MAX + 2 == 64, "one lane per bin");
 #define HF_CD_STRIDE 17       // doubles per window of the tile: Q [16] | pad
 
 // parts, and pieces of 512 windows, per device batch (a piece's result is 16 (K + 2) doubles, a part's K + 2).  The environment
-// variables of the same names lower them (tests).
+// variables of the same names lower them (rg_cap; tests).
 #ifndef HF_CD_BATCH_PARTS
 #define HF_CD_BATCH_PARTS (1 << 16)
 #endif
@@ -61,15 +60,7 @@ __device__ __forceinline__ void cd_window(const PassView& pv, int c, long long x
     double A[16], b[4];
     mo_b<SEQ>(pv, c, x, b);
     iv_row<SEQ>(pv, x, A);
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        double y[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) y[q] = A[p * 4 + q] * b[q];
-        const double den = ((y[0] + y[1]) + y[2]) + y[3];
-#pragma unroll
-        for (int q = 0; q < 4; q++) r[p * 4 + q] = den > 0.0 ? y[q] / den : 0.0;
-    }
+    ch_post_rows(A, b, r);
 }
 
 // out[g]: M[p][q][k] at (p * 4 + q) * (K + 2) + k, k = 0 .. K + 1
@@ -147,11 +138,9 @@ __global__ void __launch_bounds__(64) k_cd_chain(const CdPart* __restrict__ part
     {
         double f[4], b[4], g[4];
         mo_fb<SEQ>(pv, pt.c, pt.a, f, b);
+        ch_post_start(f, b, 15, g);
 #pragma unroll
-        for (int s = 0; s < 4; s++) g[s] = f[s] * b[s];
-        const double tot = ((g[0] + g[1]) + g[2]) + g[3];
-#pragma unroll
-        for (int s = 0; s < 4; s++) v[s] = (lane == ((mask >> s) & 1) && tot > 0.0) ? g[s] / tot : 0.0;
+        for (int s = 0; s < 4; s++) v[s] = lane == ((mask >> s) & 1) ? g[s] : 0.0;
     }
     for (int g = pt.p0; g < pt.p1; g++) {
         const double* __restrict__ src = pm + (int64_t) g * (16 * B);
@@ -188,11 +177,6 @@ __global__ void __launch_bounds__(64) k_cd_chain(const CdPart* __restrict__ part
     if (live) out[(int64_t) blockIdx.x * B + lane] = ((v[0] + v[1]) + v[2]) + v[3];
 }
 
-static size_t cd_cap(const char* name, size_t dflt) {
-    if (const char* e = std::getenv(name)) { const long v = std::atol(e); if (v >= 1) return std::min<size_t>((size_t) v, dflt); }
-    return dflt;
-}
-
 int hf_get_count_distribution(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, int32_t max_count,
                               double* dist_host) {
     const std::string who = "hf_get_count_distribution";
@@ -207,42 +191,21 @@ int hf_get_count_distribution(hf_ctx* ctx, int64_t n, const int64_t* first, cons
     hipStream_t st = ctx->pass.last_stream;
     const int K = (int) max_count;
     const size_t B = cd_part_len(K), PM = 16 * B;
-    const size_t cap_pieces = cd_cap("HF_CD_BATCH_PIECES", HF_CD_BATCH_PIECES), cap_parts = cd_cap("HF_CD_BATCH_PARTS", HF_CD_BATCH_PARTS);
-    JobCut<CdPiece, CdPart, HF_CD_PIECE> jc;
-    std::vector<double> val;
     CdStitch stitch(K);
-    for (int64_t j0 = 0; j0 < n;) {
-        const int64_t j1 = jc.cut(tr.h_off, n, first, last, j0, cap_pieces, cap_parts,
-            [&](int64_t j, int c, int64_t a, int64_t b) { return CdPart{a, b, 0, 0, state_mask[j], c}; },
-            [](const CdPart& pt, int64_t t, int len) { return CdPiece{t, len, pt.mask, pt.c, 0}; });
-        const size_t np = jc.pieces.size(), nq = jc.parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(CdPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(CdPart));
-        const size_t o_out = o_pm + Slab::granule(np * PM * 8);
-        rc = ctx->cd.reserve(o_out + Slab::granule(nq * B * 8), who);
-        if (rc) return rc;
-        CdPiece* d_pieces = reinterpret_cast<CdPiece*>(ctx->cd.d_buf);
-        CdPart* d_parts = reinterpret_cast<CdPart*>(ctx->cd.d_buf + o_parts);
-        double* d_pm = reinterpret_cast<double*>(ctx->cd.d_buf + o_pm);
-        double* d_out = reinterpret_cast<double*>(ctx->cd.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(CdPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(CdPart), hipMemcpyHostToDevice, st));
-        by_algo(tr, [&](auto S) {
-            constexpr bool SEQ = decltype(S)::value;
-            if (np) hipLaunchKernelGGL(k_cd_piece<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, K, d_pm);
-            hipLaunchKernelGGL(k_cd_chain<SEQ>, dim3((unsigned) nq), dim3(64), 0, st, d_parts, d_pm, pv, K, d_out);
-        });
-        HIPCHK(hipGetLastError());
-        val.resize(nq * B);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * B * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {
-            // the parts of a job in chunk order (hf_countdist_stitch.h)
+    return rg_run<CdPiece, CdPart, HF_CD_PIECE>(ctx, who, ctx->cd, n, first, last, rg_cap("HF_CD_BATCH_PIECES", HF_CD_BATCH_PIECES),
+        rg_cap("HF_CD_BATCH_PARTS", HF_CD_BATCH_PARTS), PM * 8, 0, B,
+        [&](int64_t j, int c, int64_t a, int64_t b) { return CdPart{a, b, 0, 0, state_mask[j], c}; },
+        [](const CdPart& pt, int64_t t, int len) { return CdPiece{t, len, pt.mask, pt.c, 0}; },
+        [&](const RgBatch<CdPiece, CdPart>& bt) {      // (the chain kernel: one workgroup per part)
+            by_algo(tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                if (bt.np) hipLaunchKernelGGL(k_cd_piece<SEQ>, bt.piece_grid(), dim3(64), 0, st, bt.pieces, pv, K, bt.pm);
+                hipLaunchKernelGGL(k_cd_chain<SEQ>, dim3((unsigned) bt.nq), dim3(64), 0, st, bt.parts, bt.pm, pv, K, bt.out);
+            });
+        },
+        [&](int64_t j, const CdPart*, const double* val, int64_t k0, int64_t k1) {      // (hf_countdist_stitch.h)
             stitch.begin();
-            const int64_t k0 = jc.job_p0[(size_t) (j - j0)], k1 = jc.job_p0[(size_t) (j - j0) + 1];
             for (int64_t k = k0; k < k1; k++) stitch.part(&val[(size_t) k * B]);
             stitch.end(dist_host + (size_t) j * B);
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }

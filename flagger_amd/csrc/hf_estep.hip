@@ -22,14 +22,14 @@
 // what crosses a unit boundary):
 //   hf_estep.hip     this one: host pool and pinned cache, hf_create.h, the pass, hf_finish and the exchange entry points, the lazy getters
 //                    of the pass (hf_get_labels / _posterior / _forward_backward), profiling, self-tests, hf_batch.h; at its end
-//                    hf_getters.h: the range getters and the alpha statistics, host side and kernels (hf_jobs.h, hf_view.h,
-//                    hf_interval.h, hf_alpha.h, hf_moments.h, hf_runs.h, hf_entropy.h, hf_breakpoint.h, hf_longrun.h)
+//                    hf_getters.h: the range getters and the alpha statistics, host side and kernels (hf_view.h, hf_interval.h,
+//                    hf_alpha.h, hf_moments.h, hf_runs.h, hf_entropy.h, hf_breakpoint.h, hf_longrun.h; rg_check, pass_view for every unit)
 //   hf_decoders.hip  hf_decode.h, hf_viterbi.h, hf_sample.h: hf_viterbi*, hf_sample_*
 //   hf_minlen.hip    the minimum-run-length family: hf_minlen*.h, hf_mea.h
 //   hf_runlen.hip    the block-length spectrum hf_get_run_lengths (its host-only stitch: hf_runlen_stitch.h)
 //   hf_countdist.hip the distribution of label totals hf_get_count_distribution (its host-only stitch: hf_countdist_stitch.h)
 // Every kernel is compiled in exactly one of them; the other units reach this unit's kernels through launch_tables, launch_chunk_stats
-// and launch_reduce.
+// and launch_reduce.  The units with range getters share hf_rg.h (static templates: the batch loop over hf_jobs.h, scratch layout, caps).
 #include "hf_host.h"
 
 thread_local std::string g_err;

@@ -6,15 +6,12 @@
 // INCLUDED AT THE END OF hf_estep.hip, as hf_batch.h is, not a unit of its own: compiled without the pass kernels in the same module,
 // k_alpha_pairs<*> and k_ent_piece<*> come out with other instructions around their __shfl_down (DESIGN.md 7k-m has the measurement).
 //
-// THE SCAFFOLD of the four piece / chain getters (interval, count moments, run moments, entropy and labelling log-probability): rg_check
-// refuses what every one of them refuses, pass_view says where the pass left its rows, f and b (hf_view.h), and rg_run takes the jobs through the
-// device batch by batch: it cuts a batch into chunk-local parts and their pieces (hf_jobs.h), lays out the getter's scratch (pieces |
-// parts | per-piece results, one or two arrays | per-part results), uploads, launches the getter's piece kernel and then its chain
-// kernel, fetches the parts' results and hands the parts of every job, in chunk order, to the getter's fold.  A getter keeps its record
-// builders, its scratch sizes, its two launches and its fold.
+// THE SCAFFOLD of every range getter, here and in hf_runlen.hip and hf_countdist.hip: rg_check refuses what every one of them refuses,
+// pass_view says where the pass left its rows, f and b (hf_view.h), and hf_rg.h takes the jobs through the device batch by batch: the
+// piece / chain getters (interval, count moments, run moments, entropy and labelling log-probability) through its rg_run, keeping their
+// record builders, scratch sizes, two launches and fold; the breakpoint and long-run getters with a body of their own for rg_batches.
 #pragma once
-#include "hf_host.h"
-#include "hf_jobs.h"
+#include "hf_rg.h"
 #include "hf_view.h"
 #include "hf_interval.h"
 #include "hf_moments.h"
@@ -74,52 +71,6 @@ int pass_view(hf_ctx* ctx, const std::string& who, int64_t n, PassView& pv) {
         if (rc) return rc;
     }
     pv = view_of(ctx);
-    return HF_OK;
-}
-
-// a batch on the device: np pieces, nq parts, the per-piece results pm and px of the piece kernel, the per-part results of the chain kernel
-template <class Piece, class Part>
-struct RgBatch {
-    size_t np, nq;
-    const Piece* pieces; const Part* parts;
-    double* pm; double* px; double* out;
-    dim3 piece_grid() const { return dim3((unsigned) np); }                  // one 64-lane workgroup per piece
-    dim3 chain_grid() const { return dim3((unsigned) ((nq + 63) / 64)); }    // one thread per part
-};
-
-// The jobs of a call, batch by batch, on the stream of the pass.  pm_bytes, px_bytes: the piece kernel's results per piece (px_bytes == 0:
-// one array only); out_doubles: the chain kernel's results per part.  launch(batch) enqueues the two kernels (the piece kernel only when
-// the batch has pieces); fold(job, parts, val, k0, k1) gets the host's part records and the results of the batch and writes the value
-// of the job from its parts k0 .. k1 - 1.
-template <class Piece, class Part, int64_t GRID, class MkPart, class MkPiece, class Launch, class Fold>
-static int rg_run(hf_ctx* ctx, const std::string& who, DevBuf& buf, int64_t n, const int64_t* first, const int64_t* last, size_t cap_pieces,
-                  size_t cap_parts, size_t pm_bytes, size_t px_bytes, size_t out_doubles, MkPart&& mk_part, MkPiece&& mk_piece, Launch&& launch,
-                  Fold&& fold) {
-    hipStream_t st = ctx->pass.last_stream;
-    JobCut<Piece, Part, GRID> jc;
-    std::vector<double> val;
-    for (int64_t j0 = 0; j0 < n;) {
-        const int64_t j1 = jc.cut(ctx->tr.h_off, n, first, last, j0, cap_pieces, cap_parts, mk_part, mk_piece);
-        const size_t np = jc.pieces.size(), nq = jc.parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(Piece)), o_pm = o_parts + Slab::granule(nq * sizeof(Part));
-        const size_t o_px = o_pm + Slab::granule(np * pm_bytes), o_out = px_bytes ? o_px + Slab::granule(np * px_bytes) : o_px;
-        const int rc = buf.reserve(o_out + Slab::granule(nq * out_doubles * 8), who);
-        if (rc) return rc;
-        Piece* d_pieces = reinterpret_cast<Piece*>(buf.d_buf);
-        Part* d_parts = reinterpret_cast<Part*>(buf.d_buf + o_parts);
-        const RgBatch<Piece, Part> bt{np, nq, d_pieces, d_parts, reinterpret_cast<double*>(buf.d_buf + o_pm),
-                                      px_bytes ? reinterpret_cast<double*>(buf.d_buf + o_px) : nullptr, reinterpret_cast<double*>(buf.d_buf + o_out)};
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(Piece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(Part), hipMemcpyHostToDevice, st));
-        launch(bt);
-        HIPCHK(hipGetLastError());
-        val.resize(nq * out_doubles);
-        HIPCHK(hipMemcpyAsync(val.data(), bt.out, nq * out_doubles * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++)      // the parts of a job in chunk order
-            fold(j, jc.parts.data(), val.data(), jc.job_p0[(size_t) (j - j0)], jc.job_p0[(size_t) (j - j0) + 1]);
-        j0 = j1;
-    }
     return HF_OK;
 }
 
@@ -361,7 +312,7 @@ int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
         },
         [&](int64_t j, const RnPart* parts, const double* val, int64_t k0, int64_t k1) {
             // the parts of a job in chunk order.  x = (E[R], Var(R), s, e, Cov(R, E0), Cov(R, S0), Cov(S0, E0)) of a part; part k is joined
-            // to part k - 1 when it lies in the next chunk and that chunk continues the one before.  Three sums, each left to right:
+            // to part k - 1 by the join rule of hf_jobs.h.  Three sums, each left to right:
             //   mean = sum E[R] - sum_joined q,  var = sum Var(R) + sum_joined [...] + 2 sum_{both joined} [...]   (q = e_{k-1} s_k)
             // so a job without a join is the plain sum of its parts.
             double m = 0.0, mq = 0.0, v = 0.0, vj = 0.0, vjj = 0.0;
@@ -369,11 +320,7 @@ int hf_get_run_moments(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
             for (int64_t k = k0; k < k1; k++) {
                 const double* x = &val[(size_t) k * HF_RN_OUT];
                 m += x[0]; v += x[1];
-                bool join = false;
-                if (k > k0 && joined) {
-                    const int c = parts[(size_t) k].c;
-                    join = parts[(size_t) k - 1].c == c - 1 && joined[c] != 0;
-                }
+                const bool join = part_joined(parts, k, k0, joined);
                 if (join) {
                     const double* y = x - HF_RN_OUT;      // the part before
                     const double q = y[3] * x[2];
@@ -494,7 +441,7 @@ int hf_get_entropy_profile(hf_ctx* ctx, int64_t first, int64_t n, double* marg_h
 
 // ------------------------------------------------------------------------------------------
 // exact breakpoint posteriors (hf_breakpoint.h): the first range getter with a value per window of a job.  It shares rg_check, pass_view
-// and the job cutter with the others; bp_run is rg_run's sibling for four launches and the per-window weight arrays of a batch.
+// and the batch loop (rg_batches) with the others; bp_run is rg_run's sibling for four launches and the per-window weight arrays of a batch.
 // ------------------------------------------------------------------------------------------
 #include "hf_breakpoint.h"
 
@@ -506,62 +453,50 @@ static int bp_run(hf_ctx* ctx, const std::string& who, const PassView& pv, int64
                   const uint8_t* um, const uint8_t* vm, const BpProbs& pr, double* lpe_host, int64_t* quant_host, int64_t* mode_host,
                   double* mode_p_host, double* prof_host) {
     hipStream_t st = ctx->pass.last_stream;
-    DevBuf& buf = ctx->bp;
-    JobCut<BpPiece, BpPart, HF_BP_PIECE> jc;
     std::vector<double> vd;
     std::vector<long long> vi;
     constexpr size_t NI = HF_BP_MAX_PROBS + 1;
-    for (int64_t j0 = 0; j0 < n;) {
-        long long nw = 0;      // windows with a weight so far in the batch
-        const int64_t j1 = jc.cut(ctx->tr.h_off, n, first, last, j0, HF_BP_BATCH_PIECES, HF_BP_BATCH_PARTS,
-            [&](int64_t j, int c, int64_t a, int64_t b) { BpPart pt{a, b, nw, 0, 0, um[j], vm[j], c, 0}; nw += b - a; return pt; },
-            [](const BpPart& pt, int64_t t, int len) { return BpPiece{t, pt.w0 + (t - pt.a - 1), len, pt.um, pt.vm, 0}; });
-        const size_t np = jc.pieces.size(), nq = jc.parts.size();
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += Slab::granule(bytes); return at; };
-        const size_t o_pieces = take(np * sizeof(BpPiece)), o_parts = take(nq * sizeof(BpPart)), o_pm = take(np * 48 * 8), o_pe = take(np * 4 * 4);
-        const size_t o_lv = take(np * 4 * 8), o_le = take(np * 8), o_rv = take(np * 4 * 8), o_re = take(np * 8), o_nn = take(nq * 8);
-        const size_t o_wm = take((size_t) nw * 8), o_we = take((size_t) nw * 4), o_prof = prof_host ? take((size_t) nw * 8) : 0;
-        const size_t o_outd = take(nq * 2 * 8), o_outi = take(nq * NI * 8);
-        const int rc = buf.reserve(o, who);
-        if (rc) return rc;
-        char* d = buf.d_buf;
-        BpPiece* d_pieces = reinterpret_cast<BpPiece*>(d + o_pieces);
-        BpPart* d_parts = reinterpret_cast<BpPart*>(d + o_parts);
-        double* d_pm = reinterpret_cast<double*>(d + o_pm); int* d_pe = reinterpret_cast<int*>(d + o_pe);
-        double* d_lv = reinterpret_cast<double*>(d + o_lv); long long* d_le = reinterpret_cast<long long*>(d + o_le);
-        double* d_rv = reinterpret_cast<double*>(d + o_rv); long long* d_re = reinterpret_cast<long long*>(d + o_re);
-        double* d_nn = reinterpret_cast<double*>(d + o_nn);
-        double* d_wm = reinterpret_cast<double*>(d + o_wm); int* d_we = reinterpret_cast<int*>(d + o_we);
-        double* d_prof = prof_host ? reinterpret_cast<double*>(d + o_prof) : nullptr;
-        double* d_outd = reinterpret_cast<double*>(d + o_outd); long long* d_outi = reinterpret_cast<long long*>(d + o_outi);
-        HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(BpPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(BpPart), hipMemcpyHostToDevice, st));
-        by_algo(ctx->tr, [&](auto S) {
-            constexpr bool SEQ = decltype(S)::value;
-            hipLaunchKernelGGL(k_bp_piece<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_pm, d_pe);
-            hipLaunchKernelGGL(k_bp_chain<SEQ>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe, pv, d_lv, d_le,
-                               d_rv, d_re, d_nn);
-            hipLaunchKernelGGL(k_bp_weights<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_lv, d_le, d_rv, d_re, d_wm, d_we);
-        });
-        hipLaunchKernelGGL(k_bp_quant, dim3((unsigned) nq), dim3(64), 0, st, d_parts, d_wm, d_we, d_nn, pr, d_outd, d_outi, d_prof);
-        HIPCHK(hipGetLastError());
-        vd.resize(nq * 2);
-        vi.resize(nq * NI);
-        HIPCHK(hipMemcpyAsync(vd.data(), d_outd, nq * 2 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(vi.data(), d_outi, nq * NI * 8, hipMemcpyDeviceToHost, st));
-        if (prof_host) HIPCHK(hipMemcpyAsync(prof_host, d_prof, (size_t) nw * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {      // a job is one part
-            const size_t k = (size_t) jc.job_p0[(size_t) (j - j0)];
+    long long nw = 0;      // windows with a weight so far in the batch being cut
+    return rg_batches<BpPiece, BpPart, HF_BP_PIECE>(ctx, n, first, last, HF_BP_BATCH_PIECES, HF_BP_BATCH_PARTS,
+        [&](int64_t j, int c, int64_t a, int64_t b) { BpPart pt{a, b, nw, 0, 0, um[j], vm[j], c, 0}; nw += b - a; return pt; },
+        [](const BpPart& pt, int64_t t, int len) { return BpPiece{t, pt.w0 + (t - pt.a - 1), len, pt.um, pt.vm, 0}; },
+        [&](const auto& jc, int64_t) -> int {
+            const size_t np = jc.pieces.size(), nq = jc.parts.size(), nwb = (size_t) std::exchange(nw, 0LL);      // (the next cut starts a batch)
+            BpPiece* d_pieces; BpPart* d_parts;
+            double *d_pm, *d_lv, *d_rv, *d_nn, *d_wm, *d_prof = nullptr, *d_outd;
+            int *d_pe, *d_we; long long *d_le, *d_re, *d_outi;
+            const int rc = rg_take(ctx->bp, who, [&](auto f) {
+                f(d_pieces, np * sizeof(BpPiece)); f(d_parts, nq * sizeof(BpPart)); f(d_pm, np * 48 * 8); f(d_pe, np * 4 * 4);
+                f(d_lv, np * 4 * 8); f(d_le, np * 8); f(d_rv, np * 4 * 8); f(d_re, np * 8); f(d_nn, nq * 8);
+                f(d_wm, nwb * 8); f(d_we, nwb * 4); if (prof_host) f(d_prof, nwb * 8);
+                f(d_outd, nq * 2 * 8); f(d_outi, nq * NI * 8);
+            });
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(BpPiece), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(BpPart), hipMemcpyHostToDevice, st));
+            by_algo(ctx->tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                hipLaunchKernelGGL(k_bp_piece<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_pm, d_pe);
+                hipLaunchKernelGGL(k_bp_chain<SEQ>, dim3((unsigned) ((nq + 63) / 64)), dim3(64), 0, st, (int) nq, d_parts, d_pm, d_pe, pv, d_lv, d_le,
+                                   d_rv, d_re, d_nn);
+                hipLaunchKernelGGL(k_bp_weights<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, d_lv, d_le, d_rv, d_re, d_wm, d_we);
+            });
+            hipLaunchKernelGGL(k_bp_quant, dim3((unsigned) nq), dim3(64), 0, st, d_parts, d_wm, d_we, d_nn, pr, d_outd, d_outi, d_prof);
+            HIPCHK(hipGetLastError());
+            vd.resize(nq * 2);
+            vi.resize(nq * NI);
+            HIPCHK(hipMemcpyAsync(vd.data(), d_outd, nq * 2 * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(vi.data(), d_outi, nq * NI * 8, hipMemcpyDeviceToHost, st));
+            if (prof_host) HIPCHK(hipMemcpyAsync(prof_host, d_prof, nwb * 8, hipMemcpyDeviceToHost, st));
+            return HF_OK;
+        },
+        [&](const auto& jc, int64_t j, size_t i) {      // a job is one part
+            const size_t k = (size_t) jc.job_p0[i];
             if (lpe_host) lpe_host[j] = vd[k * 2];
             if (mode_p_host) mode_p_host[j] = vd[k * 2 + 1];
             if (mode_host) mode_host[j] = vi[k * NI];
             for (int q = 0; q < pr.n; q++) quant_host[j * pr.n + q] = vi[k * NI + 1 + (size_t) q];
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }
 
 // what the two calls refuse beyond rg_check (which has taken the ranges and the left masks), job by job
@@ -628,18 +563,13 @@ int hf_get_breakpoint_profile(hf_ctx* ctx, int64_t first, int64_t last, uint8_t 
 static_assert(HF_LONGRUN_MAX_LANES == 64, "one wavefront holds the expanded chain");
 
 // parts, and windows in pieces of 512 (the grid of the other getters), per device batch: a group is one workgroup and a window one step
-// of it, so the caps bound a launch's run time, not its memory.  The environment variables of the same names lower them (tests).
+// of it, so the caps bound a launch's run time, not its memory.  The environment variables of the same names lower them (rg_cap; tests).
 #ifndef HF_LR_BATCH_PARTS
 #define HF_LR_BATCH_PARTS (1 << 16)
 #endif
 #ifndef HF_LR_BATCH_PIECES
 #define HF_LR_BATCH_PIECES (1 << 18)
 #endif
-
-static size_t lr_cap(const char* name, size_t dflt) {
-    if (const char* e = std::getenv(name)) { const long v = std::atol(e); if (v >= 1) return std::min<size_t>((size_t) v, dflt); }
-    return dflt;
-}
 
 // log(1 - exp(x)), x <= 0
 static double lr_log1mexp(double x) { return x > -0.69314718055994530942 ? std::log(-std::expm1(x)) : std::log1p(-std::exp(x)); }
@@ -661,40 +591,37 @@ int hf_get_long_run_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
     rc = pass_view(ctx, who, n, pv);
     if (rc || n == 0) return rc;
     hipStream_t st = ctx->pass.last_stream;
-    const size_t cap_pieces = lr_cap("HF_LR_BATCH_PIECES", HF_LR_BATCH_PIECES), cap_parts = lr_cap("HF_LR_BATCH_PARTS", HF_LR_BATCH_PARTS);
-    JobCut<LrPiece, LrPart, 512> jc;
     std::vector<LrGroup> groups;
     std::vector<int64_t> job_g0;
     std::vector<double> val;
-    for (int64_t j0 = 0; j0 < n;) {
-        const int64_t j1 = jc.cut(tr.h_off, n, first, last, j0, cap_pieces, cap_parts,
-            [](int64_t, int c, int64_t a, int64_t b) { return LrPart{a, b, 0, 0, c, 0}; },
-            [](const LrPart&, int64_t, int) { return LrPiece{0}; });
-        group_parts(jc.parts, jc.job_p0, joined, groups, job_g0,
-            [&](int64_t j, int64_t q0, int64_t q1) { return LrGroup{(int) q0, (int) q1, state_mask[j0 + j], min_len[j0 + j]}; });
-        const size_t nq = jc.parts.size(), ng = groups.size();
-        const size_t o_groups = Slab::granule(nq * sizeof(LrPart)), o_out = o_groups + Slab::granule(ng * sizeof(LrGroup));
-        rc = ctx->lr.reserve(o_out + Slab::granule(ng * 2 * 8), who);
-        if (rc) return rc;
-        LrPart* d_parts = reinterpret_cast<LrPart*>(ctx->lr.d_buf);
-        LrGroup* d_groups = reinterpret_cast<LrGroup*>(ctx->lr.d_buf + o_groups);
-        double* d_out = reinterpret_cast<double*>(ctx->lr.d_buf + o_out);
-        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(LrPart), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_groups, groups.data(), ng * sizeof(LrGroup), hipMemcpyHostToDevice, st));
-        by_algo(tr, [&](auto S) {
-            constexpr bool SEQ = decltype(S)::value;
-            hipLaunchKernelGGL(k_lr_chain<SEQ>, dim3((unsigned) ng), dim3(64), 0, st, d_groups, d_parts, pv, d_out);
-        });
-        HIPCHK(hipGetLastError());
-        val.resize(ng * 2);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, ng * 2 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {
+    return rg_batches<LrPiece, LrPart, 512>(ctx, n, first, last, rg_cap("HF_LR_BATCH_PIECES", HF_LR_BATCH_PIECES),
+        rg_cap("HF_LR_BATCH_PARTS", HF_LR_BATCH_PARTS),
+        [](int64_t, int c, int64_t a, int64_t b) { return LrPart{a, b, 0, 0, c, 0}; },
+        [](const LrPart&, int64_t, int) { return LrPiece{0}; },
+        [&](const auto& jc, int64_t j0) -> int {      // (no piece is uploaded: they count windows for the cap)
+            group_parts(jc.parts, jc.job_p0, joined, groups, job_g0,
+                [&](int64_t j, int64_t q0, int64_t q1) { return LrGroup{(int) q0, (int) q1, state_mask[j0 + j], min_len[j0 + j]}; });
+            const size_t nq = jc.parts.size(), ng = groups.size();
+            LrPart* d_parts; LrGroup* d_groups; double* d_out;
+            const int rc = rg_take(ctx->lr, who, [&](auto f) { f(d_parts, nq * sizeof(LrPart)); f(d_groups, ng * sizeof(LrGroup)); f(d_out, ng * 2 * 8); });
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(LrPart), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_groups, groups.data(), ng * sizeof(LrGroup), hipMemcpyHostToDevice, st));
+            by_algo(tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                hipLaunchKernelGGL(k_lr_chain<SEQ>, dim3((unsigned) ng), dim3(64), 0, st, d_groups, d_parts, pv, d_out);
+            });
+            HIPCHK(hipGetLastError());
+            val.resize(ng * 2);
+            HIPCHK(hipMemcpyAsync(val.data(), d_out, ng * 2 * 8, hipMemcpyDeviceToHost, st));
+            return HF_OK;
+        },
+        [&](const auto&, int64_t j, size_t i) {
             // the groups of a job in chunk order: log_p_none is their left-to-right sum.  log_p_some: -inf when no group can hold a run,
             // the kernel's own value (accurate however small) when exactly one can, else log(1 - exp(log_p_none))
             double none = 0.0, some = -__builtin_inf();
             int hits = 0;
-            for (int64_t g = job_g0[(size_t) (j - j0)]; g < job_g0[(size_t) (j - j0) + 1]; g++) {
+            for (int64_t g = job_g0[i]; g < job_g0[i + 1]; g++) {
                 none += val[(size_t) g * 2];
                 const double s = val[(size_t) g * 2 + 1];
                 if (!(s == -__builtin_inf())) { hits++; some = s; }
@@ -702,8 +629,5 @@ int hf_get_long_run_log_probs(hf_ctx* ctx, int64_t n, const int64_t* first, cons
             if (hits > 1) some = lr_log1mexp(none);
             if (log_p_none_host) log_p_none_host[j] = none;
             if (log_p_some_host) log_p_some_host[j] = some;
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }

@@ -1,18 +1,19 @@
-// hf_jobs.h — how the range getters (hf_get_interval_log_probs, hf_get_count_moments, hf_get_run_moments, hf_get_path_entropy,
-// hf_get_path_log_probs) cut a call's jobs into device work.  Host code only, no HIP header: tests/test_jobcut_cpu.py compiles it with
-// the host compiler (jobcut_check.cpp).
+// hf_jobs.h — how every range getter (the interval, count-moment, run-moment, entropy, breakpoint and long-run getters of hf_getters.h,
+// hf_get_run_lengths, hf_get_count_distribution) cuts a call's jobs into device work; hf_rg.h runs the batches.  Host code only, no HIP
+// header: tests/test_jobcut_cpu.py compiles it with the host compiler (jobcut_check.cpp).
 //
 // THE CUTTING RULE.  A job is a window range [first, last] inside the chunks.  It becomes one PART per chunk it touches, [a, b] = the
 // job's windows in that chunk, in chunk order; chunks without windows are skipped.  A part's interior windows (a, b] become PIECES, cut at
 // global window indices that are multiples of GRID: a piece therefore depends on its job alone, and a part with a == b has none.
 //
 // THE BATCHING RULE.  A call's jobs go to the device in batches, in order: a job joins the batch while the batch holds fewer than
-// cap_pieces pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split.  The caller gives the caps (the
-// getters': HF_IV_BATCH_*, HF_MO_BATCH_* of hf_estep.hip).
+// cap_pieces pieces and fewer than cap_parts parts; a batch holds at least one job; a job is never split.  The caller gives the caps
+// (every getter's HF_*_BATCH_PIECES and HF_*_BATCH_PARTS stand with its code: hf_estep.hip, hf_getters.h, hf_runlen.hip, hf_countdist.hip).
 //
-// THE GROUPING RULE (hf_get_long_run_log_probs).  joined[c] != 0 says that chunk c continues chunk c - 1 (joined == nullptr: no chunk
-// does).  Part k of a job is joined to part k - 1 when it lies in the next chunk and that chunk has joined != 0; a chunk without windows
-// has no part, so it ends a sequence of joined chunks.  A GROUP is a maximal sequence of parts joined to each other.
+// THE JOIN RULE (hf_get_run_moments, hf_get_long_run_log_probs, hf_get_run_lengths), part_joined below.  joined[c] != 0 says that chunk c
+// continues chunk c - 1 (joined == nullptr: no chunk does).  Part k of a job is joined to part k - 1 when it lies in the next chunk and
+// that chunk has joined != 0; a chunk without windows has no part, so it ends a sequence of joined chunks, and a job's first part is
+// joined to nothing.  A GROUP (group_parts) is a maximal sequence of parts joined to each other.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -58,18 +59,22 @@ struct JobCut {
     }
 };
 
-// The groups of a cut batch, in order: mk_group(job index in the batch, q0, q1) builds the group of parts q0 .. q1 - 1 (Part has an int
-// member c, its chunk).  job_g0: the first group of every job of the batch, and the end.
+// the join rule: is part k of the job whose first part is k0 joined to part k - 1?  (Part has an int member c, its chunk)
+template <class Part>
+inline bool part_joined(const Part* parts, int64_t k, int64_t k0, const uint8_t* joined) {
+    return k > k0 && joined && parts[k].c == parts[k - 1].c + 1 && joined[parts[k].c] != 0;
+}
+
+// The groups of a cut batch, in order: mk_group(job index in the batch, q0, q1) builds the group of parts q0 .. q1 - 1.
+// job_g0: the first group of every job of the batch, and the end.
 template <class Part, class Group, class MkGroup>
 void group_parts(const std::vector<Part>& parts, const std::vector<int64_t>& job_p0, const uint8_t* joined, std::vector<Group>& groups,
                  std::vector<int64_t>& job_g0, MkGroup&& mk_group) {
     groups.clear(); job_g0.clear();
     for (size_t j = 0; j + 1 < job_p0.size(); j++) {
         job_g0.push_back((int64_t) groups.size());
-        for (int64_t q0 = job_p0[j], q = q0 + 1; q0 < job_p0[j + 1]; q++) {
-            const bool join = q < job_p0[j + 1] && joined && parts[(size_t) q].c == parts[(size_t) q - 1].c + 1 && joined[parts[(size_t) q].c] != 0;
-            if (!join) { groups.push_back(mk_group((int64_t) j, q0, q)); q0 = q; }
-        }
+        for (int64_t q0 = job_p0[j], q = q0 + 1; q0 < job_p0[j + 1]; q++)
+            if (q == job_p0[j + 1] || !part_joined(parts.data(), q, job_p0[j], joined)) { groups.push_back(mk_group((int64_t) j, q0, q)); q0 = q; }
     }
     job_g0.push_back((int64_t) groups.size());
 }

@@ -4,9 +4,9 @@
 // rows, forward and backward vectors (hf_view.h, through pass_view of hf_host.h) and writes buffers of its own only (hf_ctx::rl).
 //
 // Definition.  Given the data the states of a chunk are a Markov chain, and only ratios of the pass's values are formed:
-//   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q']       the posterior chain, a < u <= b (the sum over q' = 0..3 in order; a
-//                                                                   row whose denominator is 0 is a zero row: no mass reaches it)
-//   sigma_a[s] = f_a[s] b_a[s] / sum_s' f_a[s'] b_a[s']             the start mass of a run at the part's first window a, s in S
+//   Q_u[p][q]  = A_u[p][q] b_u[q] / sum_q' A_u[p][q'] b_u[q']       the posterior chain, a < u <= b (ch_post_rows of hf_chain.h: the sum
+//                                                                   over q' = 0..3 in order; a row whose denominator is 0 is a zero row)
+//   sigma_a[s] = f_a[s] b_a[s] / sum_s' f_a[s'] b_a[s']             the start mass of a run at the part's first window a, s in S (ch_post_start)
 //   sigma_t[s] = sum_{p not in S} f_{t-1}[p] A_t[p][s] b_t[s] / sum_{p, s'} f_{t-1}[p] A_t[p][s'] b_t[s']    at t > a (both sums over
 //                                                                   p, then s', in order; the numerator by a select, never gamma - xi)
 // The run started at t walks from v_1 = sigma_t; at age d it stands at window u = t + d - 1.  If u = b it is OPEN at b.  Otherwise
@@ -28,11 +28,10 @@
 //                  A bin is accumulated in window order in one lane: no atomics, no cross-lane sums, one order.
 // k_rl_chain<SEQ>  one 64-lane workgroup per part, lane = bin: the pieces' bins summed in piece order, the open masses of the last piece
 //                  (the whole part in S, W, taken out of them), gamma_a(S) and gamma_b(S), and the parts of one window.
-// The host stitches the parts of every group of joined chunks (hf_runlen_stitch.h) and sums a job's groups in chunk order.  A piece
-// depends on (a, its windows, S, L) alone, so a job's bits do not depend on the other jobs of a call, their order or the device batch.
+// The host side is rg_run of hf_rg.h; its fold stitches the parts of every group of joined chunks (hf_runlen_stitch.h) and sums a job's
+// groups in chunk order.  A piece depends on (a, its windows, S, L) alone, so a job's bits depend on no other job, order or device batch.
 #define HF_HELPERS_ONLY   // of hf_decode.h (kernels: hf_decoders.hip)
-#include "hf_host.h"
-#include "hf_jobs.h"
+#include "hf_rg.h"
 #include "hf_view.h"
 #include "hf_chain.h"
 #include "hf_runlen_stitch.h"
@@ -43,7 +42,7 @@ static_assert(HF_RUN_LENGTHS_MAX == 64, "one lane per age");
 #define HF_RL_STRIDE 21       // doubles per window of the tile: Q [16] | sigma [4] | pad
 
 // parts, and pieces of 512 windows, per device batch (a piece's results are 3 (L + 1) doubles, a part's 3 (L + 1) + 2).  The environment
-// variables of the same names lower them (tests).
+// variables of the same names lower them (rg_cap; tests).
 #ifndef HF_RL_BATCH_PARTS
 #define HF_RL_BATCH_PARTS (1 << 16)
 #endif
@@ -53,16 +52,6 @@ static_assert(HF_RUN_LENGTHS_MAX == 64, "one lane per age");
 
 struct RlPiece { long long t0, a; int n, mask, c, last; };   // windows t0 .. t0 + n - 1 of the part that starts at a (chunk c); last: it holds b
 struct RlPart { long long a, b; int p0, p1, mask, c; };      // chunk-local part [a, b] of chunk c, its pieces p0 .. p1 - 1
-
-// sigma_a[s] of a part's first window
-__device__ __forceinline__ void rl_first(const double f[4], const double b[4], int mask, double sg[4]) {
-    double g[4];
-#pragma unroll
-    for (int s = 0; s < 4; s++) g[s] = f[s] * b[s];
-    const double tot = ((g[0] + g[1]) + g[2]) + g[3];
-#pragma unroll
-    for (int s = 0; s < 4; s++) sg[s] = (((mask >> s) & 1) && tot > 0.0) ? g[s] / tot : 0.0;
-}
 
 // gamma_t(S), hf_get_posterior's value (0.0 where the pass left no weight)
 __device__ __forceinline__ double rl_gamma(const double f[4], const double b[4], int mask) {
@@ -85,11 +74,12 @@ __device__ __forceinline__ void rl_window(const PassView& pv, int c, long long x
         mo_f<SEQ>(pv, c, x, f);
 #pragma unroll
         for (int k = 0; k < 16; k++) r[k] = 0.0;
-        rl_first(f, b, mask, r + 16);
+        ch_post_start(f, b, mask, r + 16);      // sigma_a
         return;
     }
     iv_row<SEQ>(pv, x, A);
     mo_f<SEQ>(pv, c, x - 1, f);
+    // (the rows of Q as ch_post_rows forms them, written out: formed in front of this nest they lengthen k_rl_piece's loop)
     double tot = 0.0, num[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int p = 0; p < 4; p++) {
@@ -195,7 +185,7 @@ __global__ void __launch_bounds__(64) k_rl_chain(const RlPart* __restrict__ part
     double W = 0.0;
     if (T == 1) {
         double sg[4];
-        rl_first(f, b, pt.mask, sg);
+        ch_post_start(f, b, pt.mask, sg);
         W = ((sg[0] + sg[1]) + sg[2]) + sg[3];
     } else if (T <= L) {
         W = pm[(pt.p1 - 1) * PM + 2 * (L + 1) + (T - 1)];
@@ -203,11 +193,6 @@ __global__ void __launch_bounds__(64) k_rl_chain(const RlPart* __restrict__ part
     o[2 * (L + 1) + L] = W;
     o[PM] = rl_gamma(f, b, pt.mask);
     o[PM + 1] = rl_gamma(fe, be, pt.mask);
-}
-
-static size_t rl_cap(const char* name, size_t dflt) {
-    if (const char* e = std::getenv(name)) { const long v = std::atol(e); if (v >= 1) return std::min<size_t>((size_t) v, dflt); }
-    return dflt;
 }
 
 int hf_get_run_lengths(hf_ctx* ctx, int64_t n, const int64_t* first, const int64_t* last, const uint8_t* state_mask, int32_t max_len,
@@ -225,52 +210,29 @@ int hf_get_run_lengths(hf_ctx* ctx, int64_t n, const int64_t* first, const int64
     hipStream_t st = ctx->pass.last_stream;
     const int L = (int) max_len;
     const size_t PM = 3 * ((size_t) L + 1), PS = rl_part_len(L);
-    const size_t cap_pieces = rl_cap("HF_RL_BATCH_PIECES", HF_RL_BATCH_PIECES), cap_parts = rl_cap("HF_RL_BATCH_PARTS", HF_RL_BATCH_PARTS);
-    JobCut<RlPiece, RlPart, HF_RL_PIECE> jc;
-    std::vector<double> val;
     RlStitch stitch(L);
-    for (int64_t j0 = 0; j0 < n;) {
-        const int64_t j1 = jc.cut(tr.h_off, n, first, last, j0, cap_pieces, cap_parts,
-            [&](int64_t j, int c, int64_t a, int64_t b) { return RlPart{a, b, 0, 0, state_mask[j], c}; },
-            [](const RlPart& pt, int64_t t, int len) { return RlPiece{t, pt.a, len, pt.mask, pt.c, t + len - 1 == pt.b ? 1 : 0}; });
-        const size_t np = jc.pieces.size(), nq = jc.parts.size();
-        const size_t o_parts = Slab::granule(np * sizeof(RlPiece)), o_pm = o_parts + Slab::granule(nq * sizeof(RlPart));
-        const size_t o_out = o_pm + Slab::granule(np * PM * 8);
-        rc = ctx->rl.reserve(o_out + Slab::granule(nq * PS * 8), who);
-        if (rc) return rc;
-        RlPiece* d_pieces = reinterpret_cast<RlPiece*>(ctx->rl.d_buf);
-        RlPart* d_parts = reinterpret_cast<RlPart*>(ctx->rl.d_buf + o_parts);
-        double* d_pm = reinterpret_cast<double*>(ctx->rl.d_buf + o_pm);
-        double* d_out = reinterpret_cast<double*>(ctx->rl.d_buf + o_out);
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces, jc.pieces.data(), np * sizeof(RlPiece), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_parts, jc.parts.data(), nq * sizeof(RlPart), hipMemcpyHostToDevice, st));
-        by_algo(tr, [&](auto S) {
-            constexpr bool SEQ = decltype(S)::value;
-            if (np) hipLaunchKernelGGL(k_rl_piece<SEQ>, dim3((unsigned) np), dim3(64), 0, st, d_pieces, pv, L, d_pm);
-            hipLaunchKernelGGL(k_rl_chain<SEQ>, dim3((unsigned) nq), dim3(64), 0, st, d_parts, d_pm, pv, L, d_out);
-        });
-        HIPCHK(hipGetLastError());
-        val.resize(nq * PS);
-        HIPCHK(hipMemcpyAsync(val.data(), d_out, nq * PS * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int64_t j = j0; j < j1; j++) {
-            // the parts of a job in chunk order; a part is joined to the one before it when it lies in the next chunk and that chunk
-            // continues its predecessor (hf_jobs.h, the grouping rule).  A job's bins: its groups' bins, summed in chunk order
+    return rg_run<RlPiece, RlPart, HF_RL_PIECE>(ctx, who, ctx->rl, n, first, last, rg_cap("HF_RL_BATCH_PIECES", HF_RL_BATCH_PIECES),
+        rg_cap("HF_RL_BATCH_PARTS", HF_RL_BATCH_PARTS), PM * 8, 0, PS,
+        [&](int64_t j, int c, int64_t a, int64_t b) { return RlPart{a, b, 0, 0, state_mask[j], c}; },
+        [](const RlPart& pt, int64_t t, int len) { return RlPiece{t, pt.a, len, pt.mask, pt.c, t + len - 1 == pt.b ? 1 : 0}; },
+        [&](const RgBatch<RlPiece, RlPart>& bt) {      // (the chain kernel: one workgroup per part)
+            by_algo(tr, [&](auto S) {
+                constexpr bool SEQ = decltype(S)::value;
+                if (bt.np) hipLaunchKernelGGL(k_rl_piece<SEQ>, bt.piece_grid(), dim3(64), 0, st, bt.pieces, pv, L, bt.pm);
+                hipLaunchKernelGGL(k_rl_chain<SEQ>, dim3((unsigned) bt.nq), dim3(64), 0, st, bt.parts, bt.pm, pv, L, bt.out);
+            });
+        },
+        [&](int64_t j, const RlPart* parts, const double* val, int64_t k0, int64_t k1) {
+            // a job's bins: its groups' bins, summed in chunk order
             double* acc = spectrum_host + (size_t) j * ((size_t) L + 1);
             for (int l = 0; l <= L; l++) acc[l] = 0.0;
-            const int64_t k0 = jc.job_p0[(size_t) (j - j0)], k1 = jc.job_p0[(size_t) (j - j0) + 1];
             for (int64_t k = k0; k < k1; k++) {
-                const RlPart& pt = jc.parts[(size_t) k];
-                const bool join = k > k0 && joined && jc.parts[(size_t) k - 1].c == pt.c - 1 && joined[pt.c] != 0;
-                if (!join) {
+                if (!part_joined(parts, k, k0, joined)) {
                     if (k > k0) stitch.end(acc);
                     stitch.begin();
                 }
-                stitch.part(&val[(size_t) k * PS], pt.b - pt.a + 1);
+                stitch.part(&val[(size_t) k * PS], parts[k].b - parts[k].a + 1);
             }
             if (k1 > k0) stitch.end(acc);
-        }
-        j0 = j1;
-    }
-    return HF_OK;
+        });
 }

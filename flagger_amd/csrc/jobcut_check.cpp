@@ -6,13 +6,49 @@
 //   0 job batch n_parts n_pieces 0 0      a job and the device batch it lands in
 //   1 job chunk a b p0 p1                 its parts, in order, each followed by
 //   2 job chunk t n g k                   the part's pieces: windows t .. t + n - 1, g = the piece's index and k = the part's in the batch
+// Before that, on every run, the join rule against answers written out by hand: a wrong one goes to stderr and ends it with status 3.
 #include "hf_jobs.h"
 #include <cstdio>
+#include <string>
 
 struct Piece { long long t; int n, c; long long job; };
 struct Part { long long a, b; int p0, p1, c; long long job; };
+struct Group { long long q0, q1; };
+static Part mk_part(int64_t j, int c, int64_t a, int64_t b) { return Part{a, b, 0, 0, c, j}; }
+static Piece mk_piece(const Part& pt, int64_t t, int len) { return Piece{t, len, pt.c, pt.job}; }
+
+// One call of jobs on the chunk offsets `off`; want: a letter per part in order, 'J' joined to the part before it, '.' not.  The groups
+// must begin exactly at the '.' parts.
+static bool join_case(const char* name, std::vector<int64_t> off, std::vector<int64_t> first, std::vector<int64_t> last, const uint8_t* joined,
+                      const std::string& want) {
+    JobCut<Piece, Part, 512> jc;
+    jc.cut(off, (int64_t) first.size(), first.data(), last.data(), 0, 1 << 20, 1 << 20, mk_part, mk_piece);
+    std::vector<Group> groups; std::vector<int64_t> job_g0;
+    group_parts(jc.parts, jc.job_p0, joined, groups, job_g0, [](int64_t, int64_t q0, int64_t q1) { return Group{q0, q1}; });
+    std::string got, heads(jc.parts.size(), 'J');
+    for (size_t j = 0; j + 1 < jc.job_p0.size(); j++)
+        for (int64_t k = jc.job_p0[j]; k < jc.job_p0[j + 1]; k++) got += part_joined(jc.parts.data(), k, jc.job_p0[j], joined) ? 'J' : '.';
+    for (const Group& g : groups) heads[(size_t) g.q0] = '.';
+    const bool ok = got == want && heads == want && job_g0.size() == jc.job_p0.size();
+    if (!ok) std::fprintf(stderr, "join rule, %s: want %s, part_joined %s, group_parts %s\n", name, want.c_str(), got.c_str(), heads.c_str());
+    return ok;
+}
+
+// chunks 0 .. 4 of ten windows, chunk 2 without windows; and three chunks of ten
+static bool join_rule() {
+    const std::vector<int64_t> gap{0, 10, 20, 20, 30, 40}, three{0, 10, 20, 30};
+    const uint8_t all5[] = {0, 1, 1, 1, 1}, some5[] = {0, 0, 1, 1, 0}, all3[] = {0, 1, 1};
+    bool ok = join_case("joined == nullptr", gap, {0}, {39}, nullptr, "....");
+    ok &= join_case("a chunk without windows ends the sequence", gap, {0}, {39}, all5, ".J.J");
+    ok &= join_case("joined[c] == 0", gap, {0}, {39}, some5, "....");
+    ok &= join_case("three chunks all joined", three, {0}, {29}, all3, ".JJ");
+    // (the first parts of jobs 2 and 3 follow, in the batch, a part of the chunk before theirs, which theirs continues)
+    ok &= join_case("a job's first part", three, {10, 0, 10, 25}, {29, 9, 19, 25}, all3, ".J...");
+    return ok;
+}
 
 int main(int argc, char** argv) {
+    if (!join_rule()) return 3;
     FILE* f = argc == 2 ? std::fopen(argv[1], "r") : nullptr;
     if (!f) { std::fprintf(stderr, "usage: jobcut_check FILE\n"); return 2; }
     long long cap_pieces, cap_parts, n_off, n;
@@ -30,9 +66,7 @@ int main(int argc, char** argv) {
     JobCut<Piece, Part, 512> jc;
     int batch = 0;
     for (int64_t j0 = 0; j0 < n; batch++) {
-        const int64_t j1 = jc.cut(off, n, first.data(), last.data(), j0, (size_t) cap_pieces, (size_t) cap_parts,
-                                  [](int64_t j, int c, int64_t a, int64_t b) { return Part{a, b, 0, 0, c, j}; },
-                                  [](const Part& pt, int64_t t, int len) { return Piece{t, len, pt.c, pt.job}; });
+        const int64_t j1 = jc.cut(off, n, first.data(), last.data(), j0, (size_t) cap_pieces, (size_t) cap_parts, mk_part, mk_piece);
         for (int64_t j = j0; j < j1; j++) {
             const int64_t k0 = jc.job_p0[(size_t) (j - j0)], k1 = jc.job_p0[(size_t) (j - j0) + 1];
             std::printf("0 %lld %d %lld %d 0 0\n", (long long) j, batch, (long long) (k1 - k0), jc.parts[(size_t) k1 - 1].p1 - jc.parts[(size_t) k0].p0);
