@@ -8,13 +8,16 @@
 //                      in windows (min_len_windows, called again once a .bin input has shown its window length)
 //   load_input, make_model, create_context   the table and the collapsed components; createModel; one hf_ctx or the sharded GPU list
 //   run_em             one whole run into a directory: em_loop, final_inference, final_outputs, late_outputs
+//                      late_outputs builds one Report from the session and hands it to the writers of hf_cli_reports.h, one per report file;
+//                      which chunks are joined, what a group is and the scopes "all" + every contig are defined once, in hf_cli_scopes.h
+//                      (final_inference's --wholeContigs and --expectedAccuracy read them there too)
 //   sweep_batched | sweep_sequential, write_sweep_table   --sweepAlpha: every candidate through hf_batch, or through run_em
 #include "../../include/hmm_flagger_hip.h"
 #include "../../include/hmm_flagger_io.h"
 #include "../../include/hmm_flagger_model.h"
 #include "../../include/hmm_flagger_multi.h"
+#include "hf_cli_scopes.h"
 #include "hf_countdist_stitch.h"
-#include "hf_jobs.h"
 #include "hf_squarem.h"
 #include <getopt.h>
 #include <sys/resource.h>
@@ -470,141 +473,6 @@ static void write_params(const hfm_model* m, const std::string& dir, const std::
     hfm_write_emission_tsv(m, (dir + "/emission_" + suffix + ".tsv").c_str());
 }
 
-// --uncertaintySamples: N posterior path samples (hf_sample_paths) with the final parameters, reduced on the host per sample as each
-// group of hf_sample_capacity samples comes down.  Two files:
-//   posterior_samples_summary.tsv   per (region, label): the final labels' bases, and over the samples the mean, standard deviation
-//                                   (divisor N - 1) and the values at index floor(q (N-1)) of the sorted N (q = 0.025, 0.5, 0.975) of the
-//                                   bases, and the mean of the windows; region "all", then region_<r>
-//   final_label_runs_support.bed    per maximal run of equal final label over consecutive windows of one contig (the runs of
-//                                   hfio_write_final_bed before --minimumLengths): the fraction of samples in which the whole run has
-//                                   that label, and the mean over samples of the fraction of its windows that have it
-static const char* const kRunLabelNames[] = {"Err", "Dup", "Hap", "Col"};   // the final BED's names (hf_io.cpp kLabelNames)
-
-// window i of chunk c covers [s + i W, min(s + (i+1) W - 1, e)]: its number of bases (and, with wreg, its region)
-static void window_bases(const hf_windows& w, int C, std::vector<int64_t>& wbases, std::vector<int32_t>* wreg) {
-    wbases.assign((size_t) w.n_windows, 0);
-    if (wreg) wreg->assign((size_t) w.n_windows, 0);
-    for (int c = 0; c < C; c++)
-        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-            const int64_t i = t - w.chunk_off[c];
-            const int64_t s = (int64_t) w.chunk_s[c] + i * w.window_len;
-            const int64_t e = std::min<int64_t>((int64_t) w.chunk_s[c] + (i + 1) * w.window_len - 1, (int64_t) w.chunk_e[c]);
-            wbases[(size_t) t] = e - s + 1;
-            if (wreg) (*wreg)[(size_t) t] = (int32_t) (w.annot[t] >> 58);
-        }
-}
-
-// the runs of the final labels (final_label_runs_support.bed, final_label_runs_confidence.bed): a new run where the label changes or a
-// chunk starts a different contig; windows a .. b - 1, bases s .. e; runOf (optional): every window's run
-struct LRun { int64_t a, b; int label; int64_t s, e; const char* ctg; };
-static std::vector<LRun> label_runs(const hfio_table* tab, const hf_windows& w, int C, const std::vector<int64_t>& wbases,
-                                    const int8_t* finalLabels, std::vector<int32_t>* runOf) {
-    std::vector<LRun> runs;
-    if (runOf) runOf->assign((size_t) w.n_windows, 0);
-    const char* preCtg = nullptr;
-    for (int c = 0; c < C; c++) {
-        const char* ctg = hfio_chunk_ctg(tab, c);
-        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-            const int64_t i = t - w.chunk_off[c];
-            const int64_t s = (int64_t) w.chunk_s[c] + i * w.window_len;
-            const int64_t e = s + wbases[(size_t) t] - 1;
-            const bool newCtg = t == w.chunk_off[c] && (!preCtg || strcmp(preCtg, ctg) != 0);
-            if (runs.empty() || newCtg || runs.back().label != finalLabels[t]) runs.push_back(LRun{t, t, finalLabels[t], s, e, ctg});
-            runs.back().b = t + 1; runs.back().e = e;
-            if (runOf) (*runOf)[(size_t) t] = (int32_t) (runs.size() - 1);
-            if (t == w.chunk_off[c]) preCtg = ctg;
-        }
-    }
-    return runs;
-}
-
-// The sampler: capacity() = samples per call (< 1: none fit, or an HF_E_* code), draw(p, first, n) = the call and its finish,
-// labels(k, out) = sample k of the last call.  --admissibleSamples writes the same two files from hf_sample_paths_minlen.
-struct PathSampler {
-    std::function<int()> capacity;
-    std::function<int(const hf_params*, int64_t, int)> draw;
-    std::function<int(int, int8_t*)> labels;
-};
-static int write_sample_outputs(const PathSampler& smp, hfm_model* model, const hfio_table* tab, const int8_t* finalLabels, int nSamples,
-                                const std::vector<std::string>& labelNames, const std::string& dir, const char* summaryName,
-                                const char* supportName) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<int64_t> wbases;
-    std::vector<int32_t> wreg;
-    window_bases(w, C, wbases, &wreg);
-    std::vector<int32_t> runOf;
-    const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, &runOf);
-    const size_t G = (size_t) R + 1, NR = runs.size();
-    std::vector<int64_t> basesS((size_t) nSamples * G * 4), winS(G * 4, 0), cnt(NR);
-    std::vector<double> support(NR, 0.0), meanFrac(NR, 0.0);
-    std::vector<int64_t> basesFinal(G * 4, 0);
-    for (int64_t t = 0; t < N; t++) {
-        const int l = finalLabels[t];
-        if (l < 0 || l > 3) continue;
-        basesFinal[(size_t) l] += wbases[(size_t) t];
-        basesFinal[((size_t) wreg[(size_t) t] + 1) * 4 + (size_t) l] += wbases[(size_t) t];
-    }
-    std::vector<int8_t> lab((size_t) N);
-    hf_params p;
-    hfm_params(model, &p);
-    const int cap = smp.capacity();
-    if (cap < 1) return cap < 0 ? cap : HF_E_ARG;
-    for (int k0 = 0; k0 < nSamples; k0 += cap) {
-        const int n = std::min(cap, nSamples - k0);
-        int rc = smp.draw(&p, k0, n);
-        if (rc != HF_OK) return rc;
-        for (int k = 0; k < n; k++) {
-            if ((rc = smp.labels(k, lab.data())) != HF_OK) return rc;
-            int64_t* b = basesS.data() + (size_t) (k0 + k) * G * 4;
-            std::fill(cnt.begin(), cnt.end(), 0);
-            for (int64_t t = 0; t < N; t++) {
-                const size_t l = (size_t) lab[(size_t) t], g = (size_t) wreg[(size_t) t] + 1;
-                b[l] += wbases[(size_t) t]; b[g * 4 + l] += wbases[(size_t) t];
-                winS[l]++; winS[g * 4 + l]++;
-                const int32_t r = runOf[(size_t) t];
-                cnt[(size_t) r] += (int) l == runs[(size_t) r].label;
-            }
-            for (size_t r = 0; r < NR; r++) {
-                const int64_t len = runs[r].b - runs[r].a;
-                support[r] += cnt[r] == len;
-                meanFrac[r] += (double) cnt[r] / (double) len;
-            }
-        }
-    }
-    const std::string sp = dir + "/" + summaryName;
-    FILE* f = fopen(sp.c_str(), "w");
-    if (!f) { hf_cli_set_error(sp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#Region\tLabel\tBases_Final\tBases_Mean\tBases_SD\tBases_Q025\tBases_Q500\tBases_Q975\tWindows_Mean\n");
-    std::vector<int64_t> v((size_t) nSamples);
-    for (size_t g = 0; g < G; g++)
-        for (size_t l = 0; l < 4; l++) {
-            double mean = 0.0, ss = 0.0;
-            for (int k = 0; k < nSamples; k++) { v[(size_t) k] = basesS[((size_t) k * G + g) * 4 + l]; mean += (double) v[(size_t) k]; }
-            mean /= nSamples;
-            for (int k = 0; k < nSamples; k++) ss += ((double) v[(size_t) k] - mean) * ((double) v[(size_t) k] - mean);
-            const double sd = nSamples > 1 ? std::sqrt(ss / (nSamples - 1)) : 0.0;
-            std::sort(v.begin(), v.end());
-            auto q = [&](double x) { return v[(size_t) std::floor(x * (nSamples - 1))]; };
-            const std::string region = g == 0 ? std::string("all") : "region_" + std::to_string(g - 1);
-            const char* name = labelNames.size() > l ? labelNames[l].c_str() : kRunLabelNames[l];
-            fprintf(f, "%s\t%s\t%ld\t%.4f\t%.4f\t%ld\t%ld\t%ld\t%.4f\n", region.c_str(), name, (long) basesFinal[g * 4 + l], mean, sd,
-                    (long) q(0.025), (long) q(0.5), (long) q(0.975), (double) winS[g * 4 + l] / nSamples);
-        }
-    if (fclose(f) != 0) { hf_cli_set_error(sp + " cannot be written"); return HF_E_ARG; }
-    const std::string bp = dir + "/" + supportName;
-    f = fopen(bp.c_str(), "w");
-    if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#ctg\tstart\tend\tlabel\tsupport\tmean_fraction\n");
-    for (size_t r = 0; r < NR; r++)
-        fprintf(f, "%s\t%ld\t%ld\t%s\t%.4f\t%.4f\n", runs[r].ctg, (long) runs[r].s, (long) runs[r].e + 1,
-                runs[r].label >= 0 && runs[r].label < 4 ? kRunLabelNames[runs[r].label] : "Unk", support[r] / nSamples, meanFrac[r] / nSamples);
-    if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
 // --regionProbs: the regions of a BED3+ file (ctg start end [name]), every line checked before the input is read
 static bool read_regions(const char* path, std::vector<Region>& regions) {
     FILE* f = fopen(path, "r");
@@ -647,693 +515,8 @@ static bool read_regions(const char* path, std::vector<Region>& regions) {
     return ok;
 }
 
-// The windows of every region (those whose bases meet [start, end) on the region's contig), sorted, and the same as maximal ranges of
-// consecutive window indices; a region on an unknown contig has none.
-static void region_windows(const hfio_table* tab, const hf_windows& w, int C, const std::vector<int64_t>& wbases, const std::vector<Region>& regions,
-                           std::vector<std::vector<int64_t>>& wins, std::vector<std::vector<std::pair<int64_t, int64_t>>>& ranges) {
-    // every contig's windows in base order: (first base, last base, window)
-    std::map<std::string, std::vector<std::array<int64_t, 3>>> byCtg;
-    for (int c = 0; c < C; c++) {
-        auto& v = byCtg[hfio_chunk_ctg(tab, c)];
-        for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-            const int64_t s = (int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len;
-            v.push_back({s, s + wbases[(size_t) t] - 1, t});
-        }
-    }
-    for (auto& kv : byCtg) std::sort(kv.second.begin(), kv.second.end());
-    wins.assign(regions.size(), {});
-    ranges.assign(regions.size(), {});
-    for (size_t i = 0; i < regions.size(); i++) {
-        const Region& g = regions[i];
-        auto it = byCtg.find(g.ctg);
-        if (it == byCtg.end()) continue;
-        for (const auto& x : it->second)
-            if (x[0] < g.end && x[1] >= g.start) wins[i].push_back(x[2]);
-        std::sort(wins[i].begin(), wins[i].end());
-        for (int64_t t : wins[i]) {
-            if (!ranges[i].empty() && ranges[i].back().second + 1 == t) ranges[i].back().second = t;
-            else ranges[i].push_back({t, t});
-        }
-    }
-}
-
-// --runConfidence / --regionProbs: exact label probabilities of windows ranges (hf_get_interval_log_probs) under the model of the last
-// full pass, and the mean posterior (hf_get_posterior).
-//   final_label_runs_confidence.bed    per run of final_label_runs_support.bed (same rows, same order): p_all = P(every window has the
-//                                      run's label), qual = min(100, -10 log10(1 - p_all)), mean_posterior of that label
-//   region_label_probabilities.tsv     per region (file order), for every label L: p_any_L = P(some window has L), p_all_L, mean_L over
-//                                      the windows whose bases meet [start, end) (a union of index ranges: the sum of their logs)
-static int write_interval_outputs(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, bool runConfidence,
-                                  const std::vector<Region>* regions, const std::vector<std::string>& labelNames, const std::string& dir) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<int64_t> wbases;
-    window_bases(w, C, wbases, nullptr);
-    std::vector<double> post((size_t) N * 4);
-    int rc = N > 0 ? hf_get_posterior(ctx, 0, N, post.data()) : HF_OK;
-    if (rc != HF_OK) return rc;
-    auto mean_post = [&](int64_t a, int64_t b, int l) {   // windows a .. b - 1
-        double m = 0.0;
-        for (int64_t t = a; t < b; t++) m += post[(size_t) t * 4 + (size_t) l];
-        return m / (double) (b - a);
-    };
-    if (runConfidence) {
-        const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, nullptr);
-        std::vector<int64_t> first, last;
-        std::vector<uint8_t> mask;
-        for (const LRun& r : runs)
-            if (r.label >= 0 && r.label < 4) { first.push_back(r.a); last.push_back(r.b - 1); mask.push_back((uint8_t) (1u << r.label)); }
-        std::vector<double> lp(first.size());
-        if ((rc = hf_get_interval_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), lp.data())) != HF_OK) return rc;
-        const std::string bp = dir + "/final_label_runs_confidence.bed";
-        FILE* f = fopen(bp.c_str(), "w");
-        if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
-        fprintf(f, "#ctg\tstart\tend\tlabel\tp_all\tqual\tmean_posterior\n");
-        size_t k = 0;
-        for (const LRun& r : runs) {
-            const bool lab = r.label >= 0 && r.label < 4;
-            fprintf(f, "%s\t%ld\t%ld\t%s\t", r.ctg, (long) r.s, (long) r.e + 1, lab ? kRunLabelNames[r.label] : "Unk");
-            if (!lab) { fprintf(f, "NA\tNA\tNA\n"); continue; }
-            const double l = lp[k++];
-            const double miss = -std::expm1(l);
-            const double qual = miss > 0.0 ? std::min(100.0, -10.0 * std::log10(miss)) + 0.0 : 100.0;
-            fprintf(f, "%.6g\t%.2f\t%.6f\n", std::exp(l), qual, mean_post(r.a, r.b, r.label));
-        }
-        if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
-    }
-    if (regions) {
-        // the windows of every region, as maximal index ranges; one job per range and mask (Err..Col alone, and all but each)
-        std::vector<std::vector<int64_t>> wins;
-        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
-        region_windows(tab, w, C, wbases, *regions, wins, ranges);
-        std::vector<int64_t> first, last;
-        std::vector<uint8_t> mask;
-        for (size_t i = 0; i < regions->size(); i++) {
-            for (const auto& r : ranges[i])
-                for (int m = 0; m < 8; m++) { first.push_back(r.first); last.push_back(r.second); mask.push_back((uint8_t) (m < 4 ? 1u << m : 15u & ~(1u << (m - 4)))); }
-        }
-        std::vector<double> lp(first.size());
-        if ((rc = hf_get_interval_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), lp.data())) != HF_OK) return rc;
-        const std::string rp = dir + "/region_label_probabilities.tsv";
-        FILE* f = fopen(rp.c_str(), "w");
-        if (!f) { hf_cli_set_error(rp + " cannot be opened"); return HF_E_ARG; }
-        fprintf(f, "#ctg\tstart\tend\tname\tn_windows");
-        for (int l = 0; l < 4; l++) {
-            const char* name = labelNames.size() > (size_t) l ? labelNames[(size_t) l].c_str() : kRunLabelNames[l];
-            fprintf(f, "\tp_any_%s\tp_all_%s\tmean_%s", name, name, name);
-        }
-        fprintf(f, "\n");
-        size_t k = 0;
-        for (size_t i = 0; i < regions->size(); i++) {
-            const Region& g = (*regions)[i];
-            fprintf(f, "%s\t%ld\t%ld\t%s\t%zu", g.ctg.c_str(), (long) g.start, (long) g.end, g.name.c_str(), wins[i].size());
-            double all[4] = {0, 0, 0, 0}, none[4] = {0, 0, 0, 0};     // sums over the ranges, range order
-            for (size_t r = 0; r < ranges[i].size(); r++, k += 8)
-                for (int l = 0; l < 4; l++) { all[l] += lp[k + (size_t) l]; none[l] += lp[k + 4 + (size_t) l]; }
-            for (int l = 0; l < 4; l++) {
-                if (wins[i].empty()) { fprintf(f, "\tNA\tNA\tNA"); continue; }
-                double m = 0.0;
-                for (int64_t t : wins[i]) m += post[(size_t) t * 4 + (size_t) l];
-                fprintf(f, "\t%.6g\t%.6g\t%.6f", -std::expm1(none[l]) + 0.0, std::exp(all[l]), m / (double) wins[i].size());
-            }
-            fprintf(f, "\n");
-        }
-        if (fclose(f) != 0) { hf_cli_set_error(rp + " cannot be written"); return HF_E_ARG; }
-    }
-    return HF_OK;
-}
-
-// --exactTotals: exact posterior mean and standard deviation of the label totals (hf_get_count_moments, HF_COUNT_BASES) under the model
-// of the last full pass.
-//   label_totals_exact.tsv   one row per scope and label set.  Scopes: "all", every contig by name (order of first appearance in the
-//                            chunk list; a contig's chunks are independent chains, so its mean and variance are the sums over its
-//                            maximal runs of consecutive chunks, in list order), region_<r> for every annotation region (the whole
-//                            track with the region filter r).  Label sets: Err, Dup, Hap, Col, Err+Dup+Col.  Columns: windows (of
-//                            the scope), bases_final_labels (bases whose final label lies in the set), bases_expected, bases_sd.
-static int write_exact_totals(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab), R = hfio_n_regions(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<int64_t> wbases;
-    std::vector<int32_t> wreg;
-    window_bases(w, C, wbases, &wreg);
-    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
-    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
-    // a scope: its name, its window ranges [a, b), its region filter
-    struct Scope { std::string name; std::vector<std::pair<int64_t, int64_t>> ranges; int region; };
-    std::vector<Scope> scopes;
-    scopes.push_back(Scope{"all", {}, -1});
-    if (N > 0) scopes.back().ranges.push_back({0, N});
-    std::map<std::string, size_t> ctgScope;
-    for (int c = 0; c < C; c++) {
-        const int64_t a = w.chunk_off[c], b = w.chunk_off[c + 1];
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        auto it = ctgScope.find(ctg);
-        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}, -1}); }
-        if (a == b) continue;
-        auto& rg = scopes[it->second].ranges;
-        if (!rg.empty() && rg.back().second == a) rg.back().second = b;
-        else rg.push_back({a, b});
-    }
-    for (int r = 0; r < R; r++) {
-        scopes.push_back(Scope{"region_" + std::to_string(r), {}, r});
-        if (N > 0) scopes.back().ranges.push_back({0, N});
-    }
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> mask;
-    std::vector<int32_t> region;
-    for (const Scope& sc : scopes)
-        for (const auto& rg : sc.ranges)
-            for (int k = 0; k < 5; k++) { first.push_back(rg.first); last.push_back(rg.second - 1); mask.push_back(kSets[k]); region.push_back(sc.region); }
-    std::vector<double> mean(first.size()), var(first.size());
-    const int rc = hf_get_count_moments(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), region.data(), HF_COUNT_BASES,
-                                        mean.data(), var.data());
-    if (rc != HF_OK) return rc;
-    const std::string tp = dir + "/label_totals_exact.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#scope\tlabel_set\twindows\tbases_final_labels\tbases_expected\tbases_sd\n");
-    size_t j = 0;
-    for (const Scope& sc : scopes) {
-        int64_t windows = 0, finalBases[5] = {0, 0, 0, 0, 0};
-        double m[5] = {0, 0, 0, 0, 0}, v[5] = {0, 0, 0, 0, 0};       // sums over the ranges, list order
-        for (const auto& rg : sc.ranges) {
-            for (int64_t t = rg.first; t < rg.second; t++) {
-                if (sc.region >= 0 && wreg[(size_t) t] != sc.region) continue;
-                windows++;
-                const int l = finalLabels[t];
-                if (l < 0 || l > 3) continue;
-                for (int k = 0; k < 5; k++) if ((kSets[k] >> l) & 1) finalBases[k] += wbases[(size_t) t];
-            }
-            for (int k = 0; k < 5; k++, j++) { m[k] += mean[j]; v[k] += var[j]; }
-        }
-        for (int k = 0; k < 5; k++)
-            fprintf(f, "%s\t%s\t%ld\t%ld\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (long) windows, (long) finalBases[k], m[k], std::sqrt(v[k]));
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --runBoundaries: the exact posterior of the position of every boundary between two runs of the final labels (hf_get_breakpoints,
-// hf_get_breakpoint_profile) under the model of the last full pass.
-//   final_label_run_boundaries.tsv   one row per two adjacent runs of final_label_runs_support.bed on one contig, in run order.  With m the
-//                                    first window of the right run and m - 1, m in one chunk, the job is first = max(start of the left
-//                                    run, first window of the chunk), last = min(end of the right run, last window of the chunk), U =
-//                                    {left label}, V = {right label}: p_event = P(the range switches exactly once, U -> V), and given
-//                                    that, p_called = p_m, lo / median / hi = the 2.5 / 50 / 97.5 % quantiles and mode, mode_p.  pos, lo,
-//                                    median, hi and mode are the first base of the window named.  A boundary at a chunk start, and a job
-//                                    without weight, have NA from p_event on.
-static int write_run_boundaries(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<int64_t> wbases;
-    window_bases(w, C, wbases, nullptr);
-    const std::vector<LRun> runs = label_runs(tab, w, C, wbases, finalLabels, nullptr);
-    auto chunk_of = [&](int64_t t) { return (int) (std::upper_bound(w.chunk_off, w.chunk_off + C + 1, t) - w.chunk_off) - 1; };
-    auto base_of = [&](int c, int64_t t) { return (long) ((int64_t) w.chunk_s[c] + (t - w.chunk_off[c]) * w.window_len); };
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> um, vm;
-    std::vector<int> job(runs.size(), -1), chunk(runs.size(), 0);      // of the boundary between runs i - 1 and i
-    for (size_t i = 1; i < runs.size(); i++) {
-        const LRun &l = runs[i - 1], &r = runs[i];
-        const int c = chunk_of(r.a);
-        chunk[i] = c;
-        if (l.b != r.a || r.a == w.chunk_off[c] || l.label < 0 || l.label > 3 || r.label < 0 || r.label > 3 || l.label == r.label) continue;
-        job[i] = (int) first.size();
-        first.push_back(std::max<int64_t>(l.a, w.chunk_off[c]));
-        last.push_back(std::min<int64_t>(r.b, w.chunk_off[c + 1]) - 1);
-        um.push_back((uint8_t) (1u << l.label));
-        vm.push_back((uint8_t) (1u << r.label));
-    }
-    const int64_t n = (int64_t) first.size();
-    const double probs[3] = {0.025, 0.5, 0.975};
-    std::vector<double> lpe((size_t) n), modeP((size_t) n), pCalled((size_t) n, 0.0), prof;
-    std::vector<int64_t> quant((size_t) n * 3), mode((size_t) n);
-    int rc = hf_get_breakpoints(ctx, n, first.data(), last.data(), um.data(), vm.data(), 3, probs, lpe.data(), quant.data(), mode.data(), modeP.data());
-    if (rc != HF_OK) return rc;
-    for (size_t i = 1; i < runs.size(); i++) {      // p_called: one profile per boundary
-        if (job[i] < 0) continue;
-        const size_t k = (size_t) job[i];
-        double lp = 0.0;
-        prof.resize((size_t) (last[k] - first[k]));
-        if ((rc = hf_get_breakpoint_profile(ctx, first[k], last[k], um[k], vm[k], prof.data(), &lp)) != HF_OK) return rc;
-        pCalled[k] = prof[(size_t) (runs[i].a - first[k] - 1)];
-    }
-    const std::string bp = dir + "/final_label_run_boundaries.tsv";
-    FILE* f = fopen(bp.c_str(), "w");
-    if (!f) { hf_cli_set_error(bp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#ctg\tpos\tleft\tright\tp_event\tp_called\tlo\tmedian\thi\tmode\tmode_p\n");
-    for (size_t i = 1; i < runs.size(); i++) {
-        const LRun &l = runs[i - 1], &r = runs[i];
-        if (strcmp(l.ctg, r.ctg) != 0) continue;      // (the first run of a contig has no boundary on its left)
-        const int c = chunk[i];
-        fprintf(f, "%s\t%ld\t%s\t%s\t", r.ctg, (long) r.s, l.label >= 0 && l.label < 4 ? kRunLabelNames[l.label] : "Unk",
-                r.label >= 0 && r.label < 4 ? kRunLabelNames[r.label] : "Unk");
-        const int k = job[i];
-        if (k < 0 || mode[(size_t) k] < 0 || !(lpe[(size_t) k] > -INFINITY)) { fprintf(f, "NA\tNA\tNA\tNA\tNA\tNA\tNA\n"); continue; }
-        fprintf(f, "%.6g\t%.6g\t%ld\t%ld\t%ld\t%ld\t%.6g\n", std::exp(lpe[(size_t) k]), pCalled[(size_t) k], base_of(c, quant[(size_t) k * 3]),
-                base_of(c, quant[(size_t) k * 3 + 1]), base_of(c, quant[(size_t) k * 3 + 2]), base_of(c, mode[(size_t) k]), modeP[(size_t) k]);
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(bp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --numBlocks: exact posterior mean and standard deviation of the block counts (hf_get_run_moments) under the model of the last full pass.
-//   label_blocks_exact.tsv   one row per scope and label set.  Scopes: "all" and every contig by name (order of first appearance in the
-//                            chunk list; its mean and variance are the sums over its maximal runs of consecutive chunks, in list
-//                            order).  No annotation-region scope: a block does not belong to one region.  Label sets: Err, Dup, Hap,
-//                            Col, Err+Dup+Col.  Columns: blocks_final_labels (the runs of the set in the final labels), blocks_expected,
-//                            blocks_sd.  A run continues from chunk c-1 into chunk c where the two are adjacent in the chunk list and
-//                            carry the same contig name: the rule hfio_write_final_bed merges by, so that for a single label and the
-//                            default --minimumLengths blocks_final_labels of "all" is the number of the label's rows in the final BED.
-static int write_exact_blocks(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
-    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
-    // a scope: its name and its chunk ranges [c0, c1)
-    struct Scope { std::string name; std::vector<std::pair<int, int>> ranges; };
-    std::vector<Scope> scopes;
-    scopes.push_back(Scope{"all", {}});
-    if (C > 0) scopes.back().ranges.push_back({0, C});
-    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
-    std::map<std::string, size_t> ctgScope;
-    for (int c = 0; c < C; c++) {
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
-        auto it = ctgScope.find(ctg);
-        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
-        auto& rg = scopes[it->second].ranges;
-        if (!rg.empty() && rg.back().second == c) rg.back().second = c + 1;
-        else rg.push_back({c, c + 1});
-    }
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> mask;
-    for (const Scope& sc : scopes)
-        for (const auto& rg : sc.ranges) {
-            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
-            for (int k = 0; k < 5; k++) { first.push_back(w.chunk_off[rg.first]); last.push_back(w.chunk_off[rg.second] - 1); mask.push_back(kSets[k]); }
-        }
-    std::vector<double> mean(first.size()), var(first.size());
-    const int rc = hf_get_run_moments(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), joined.data(), mean.data(), var.data());
-    if (rc != HF_OK) return rc;
-    (void) N;
-    const std::string tp = dir + "/label_blocks_exact.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#scope\tlabel_set\tblocks_final_labels\tblocks_expected\tblocks_sd\n");
-    size_t j = 0;
-    for (const Scope& sc : scopes) {
-        int64_t finalBlocks[5] = {0, 0, 0, 0, 0};
-        double m[5] = {0, 0, 0, 0, 0}, v[5] = {0, 0, 0, 0, 0};       // sums over the ranges, list order
-        for (const auto& rg : sc.ranges) {
-            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
-            bool in[5] = {false, false, false, false, false};        // the window before lies in the set and continues into this one
-            for (int c = rg.first; c < rg.second; c++) {
-                if (c == rg.first || !joined[(size_t) c]) for (int k = 0; k < 5; k++) in[k] = false;
-                for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-                    const int l = finalLabels[t];
-                    for (int k = 0; k < 5; k++) {
-                        const bool now = l >= 0 && l <= 3 && ((kSets[k] >> l) & 1);
-                        if (now && !in[k]) finalBlocks[k]++;
-                        in[k] = now;
-                    }
-                }
-            }
-            for (int k = 0; k < 5; k++, j++) { m[k] += mean[j]; v[k] += var[j]; }
-        }
-        for (int k = 0; k < 5; k++)
-            fprintf(f, "%s\t%s\t%ld\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (long) finalBlocks[k], m[k], std::sqrt(v[k]));
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --runLengths L: the exact block-length spectrum (hf_get_run_lengths) under the model of the last full pass.
-//   label_block_lengths_exact.tsv   per scope ("all" and every contig by name, order of first appearance in the chunk list: the sums
-//                                   over its maximal runs of consecutive chunks, in list order) and label set (Err, Dup, Hap, Col,
-//                                   Err+Dup+Col) one row per length 1..L and a row ">L": blocks_final_labels (the runs of that length of
-//                                   the set in the final labels) and blocks_expected.  Runs go on across chunks by the rule of --numBlocks.
-//   label_blocks_kept_exact.tsv     with --minimumLengths (minLenWindows not null): per scope and label its minimum in windows, the
-//                                   expected blocks, the expected blocks at or above the minimum (bin ">L" included) and the expected
-//                                   windows in the shorter ones, sum_{l < min} l N_l.
-static int write_block_lengths(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, int L, const int32_t* minLenWindows,
-                               const std::string& dir) {
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
-    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
-    const size_t B = (size_t) L + 1;
-    struct Scope { std::string name; std::vector<std::pair<int, int>> ranges; };      // a scope: its name and its chunk ranges [c0, c1)
-    std::vector<Scope> scopes;
-    scopes.push_back(Scope{"all", {}});
-    if (C > 0) scopes.back().ranges.push_back({0, C});
-    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
-    std::map<std::string, size_t> ctgScope;
-    for (int c = 0; c < C; c++) {
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
-        auto it = ctgScope.find(ctg);
-        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
-        auto& rg = scopes[it->second].ranges;
-        if (!rg.empty() && rg.back().second == c) rg.back().second = c + 1;
-        else rg.push_back({c, c + 1});
-    }
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> mask;
-    for (const Scope& sc : scopes)
-        for (const auto& rg : sc.ranges) {
-            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
-            for (int k = 0; k < 5; k++) { first.push_back(w.chunk_off[rg.first]); last.push_back(w.chunk_off[rg.second] - 1); mask.push_back(kSets[k]); }
-        }
-    std::vector<double> spec(first.size() * B);
-    const int rc = hf_get_run_lengths(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), L, joined.data(), spec.data());
-    if (rc != HF_OK) return rc;
-    const std::string tp = dir + "/label_block_lengths_exact.tsv", kp = dir + "/label_blocks_kept_exact.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    FILE* g = minLenWindows ? fopen(kp.c_str(), "w") : nullptr;
-    if (minLenWindows && !g) { fclose(f); hf_cli_set_error(kp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#scope\tlabel_set\tlength\tblocks_final_labels\tblocks_expected\n");
-    if (g) fprintf(g, "#scope\tlabel\tmin_len_windows\tblocks_expected\tblocks_expected_kept\twindows_expected_dropped\n");
-    size_t j = 0;
-    std::vector<int64_t> finalBlocks(5 * B);
-    std::vector<double> m(5 * B);
-    for (const Scope& sc : scopes) {
-        std::fill(finalBlocks.begin(), finalBlocks.end(), 0);
-        std::fill(m.begin(), m.end(), 0.0);                               // sums over the ranges, list order
-        for (const auto& rg : sc.ranges) {
-            if (w.chunk_off[rg.first] == w.chunk_off[rg.second]) continue;
-            int64_t run[5] = {0, 0, 0, 0, 0};                             // the windows of the set's current run
-            auto close = [&](int k) { if (run[k] > 0) finalBlocks[(size_t) k * B + (size_t) std::min<int64_t>(run[k], L + 1) - 1]++; run[k] = 0; };
-            for (int c = rg.first; c < rg.second; c++) {
-                if (c > rg.first && !joined[(size_t) c]) for (int k = 0; k < 5; k++) close(k);
-                for (int64_t t = w.chunk_off[c]; t < w.chunk_off[c + 1]; t++) {
-                    const int l = finalLabels[t];
-                    for (int k = 0; k < 5; k++) {
-                        if (l >= 0 && l <= 3 && ((kSets[k] >> l) & 1)) run[k]++;
-                        else close(k);
-                    }
-                }
-            }
-            for (int k = 0; k < 5; k++) close(k);
-            for (int k = 0; k < 5; k++, j++)
-                for (size_t b = 0; b < B; b++) m[(size_t) k * B + b] += spec[j * B + b];
-        }
-        for (int k = 0; k < 5; k++)
-            for (size_t b = 0; b < B; b++) {
-                if (b < (size_t) L) fprintf(f, "%s\t%s\t%zu\t%ld\t%.10g\n", sc.name.c_str(), kSetNames[k], b + 1, (long) finalBlocks[(size_t) k * B + b], m[(size_t) k * B + b]);
-                else fprintf(f, "%s\t%s\t>%d\t%ld\t%.10g\n", sc.name.c_str(), kSetNames[k], L, (long) finalBlocks[(size_t) k * B + b], m[(size_t) k * B + b]);
-            }
-        for (int k = 0; g && k < 4; k++) {
-            double all = 0.0, kept = 0.0, dropped = 0.0;                  // in bin order
-            for (size_t b = 0; b < B; b++) {
-                const double x = m[(size_t) k * B + b];
-                all += x;
-                if ((int64_t) b + 1 >= minLenWindows[k]) kept += x; else dropped += (double) (b + 1) * x;
-            }
-            fprintf(g, "%s\t%s\t%d\t%.10g\t%.10g\t%.10g\n", sc.name.c_str(), kSetNames[k], (int) minLenWindows[k], all, kept, dropped);
-        }
-    }
-    if (fclose(f) != 0) { if (g) fclose(g); hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    if (g && fclose(g) != 0) { hf_cli_set_error(kp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --totalsDistribution K: the exact distribution of a region's label totals (hf_get_count_distribution) under the model of the last full
-// pass.
-//   region_label_totals_exact.tsv   per region (file order) and label set (Err, Dup, Hap, Col, Err+Dup+Col) one row: the leading columns
-//                                   of region_label_probabilities.tsv (ctg start end name n_windows: the windows whose bases meet
-//                                   [start, end)), label_set, mean = sum k p_k in increasing k (NA where p_gtK > 0), q025 q50 q975 (the
-//                                   smallest k whose cumulative sum in increasing k reaches the level; >K when bin K does not reach it),
-//                                   then p_0 .. p_K p_gtK.  A region without windows: NA in every column behind label_set.
-// A region's windows are a union of index ranges that lie in different chunks (region_windows), so its distribution is the convolution
-// of its ranges' in range order: the getter's own stitch (hf_countdist_stitch.h).
-static int write_region_totals(hf_ctx* ctx, const hfio_table* tab, const std::vector<Region>& regions, int K, const std::string& dir) {
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<int64_t> wbases;
-    window_bases(w, C, wbases, nullptr);
-    static const uint8_t kSets[5] = {1, 2, 4, 8, 11};
-    static const char* const kSetNames[5] = {"Err", "Dup", "Hap", "Col", "Err+Dup+Col"};
-    const size_t B = cd_part_len(K);
-    std::vector<std::vector<int64_t>> wins;
-    std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
-    region_windows(tab, w, C, wbases, regions, wins, ranges);
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> mask;
-    for (size_t i = 0; i < regions.size(); i++)
-        for (const auto& r : ranges[i])
-            for (int k = 0; k < 5; k++) { first.push_back(r.first); last.push_back(r.second); mask.push_back(kSets[k]); }
-    std::vector<double> dist(first.size() * B);
-    const int rc = hf_get_count_distribution(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), K, dist.data());
-    if (rc != HF_OK) return rc;
-    const std::string tp = dir + "/region_label_totals_exact.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#ctg\tstart\tend\tname\tn_windows\tlabel_set\tmean\tq025\tq50\tq975");
-    for (int k = 0; k <= K; k++) fprintf(f, "\tp_%d", k);
-    fprintf(f, "\tp_gtK\n");
-    size_t j = 0;                                                  // the region's first job
-    CdStitch stitch(K);
-    std::vector<double> p(B);
-    for (size_t i = 0; i < regions.size(); i++) {
-        const Region& g = regions[i];
-        for (int k = 0; k < 5; k++) {
-            fprintf(f, "%s\t%ld\t%ld\t%s\t%zu\t%s", g.ctg.c_str(), (long) g.start, (long) g.end, g.name.c_str(), wins[i].size(), kSetNames[k]);
-            if (wins[i].empty()) {
-                for (size_t b = 0; b < B + 4; b++) fprintf(f, "\tNA");
-                fprintf(f, "\n");
-                continue;
-            }
-            stitch.begin();
-            for (size_t r = 0; r < ranges[i].size(); r++) stitch.part(&dist[(j + r * 5 + (size_t) k) * B]);
-            stitch.end(p.data());
-            double mean = 0.0, cum = 0.0;
-            int q[3] = {-1, -1, -1};                               // (-1: beyond bin K)
-            static const double kLevels[3] = {0.025, 0.5, 0.975};
-            for (int b = 0; b <= K; b++) {
-                mean += (double) b * p[(size_t) b];
-                cum += p[(size_t) b];
-                for (int l = 0; l < 3; l++) if (q[l] < 0 && cum >= kLevels[l]) q[l] = b;
-            }
-            if (p[B - 1] > 0.0) fprintf(f, "\tNA"); else fprintf(f, "\t%.6f", mean);
-            for (int l = 0; l < 3; l++) { if (q[l] < 0) fprintf(f, "\t>%d", K); else fprintf(f, "\t%d", q[l]); }
-            for (size_t b = 0; b < B; b++) fprintf(f, "\t%.6g", p[b]);
-            fprintf(f, "\n");
-        }
-        j += ranges[i].size() * 5;
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --keptBlocks: the exact probability that a scope holds a block of a label that --minimumLengths would keep (hf_get_long_run_log_probs)
-// under the model of the last full pass.
-//   kept_block_probabilities.tsv   one row for the whole track ("all"), one per contig (order of first appearance in the chunk list) and,
-//                                  with --regionProbs FILE, one per region in file order (a region without windows: NA).  Per label L:
-//                                  min_windows_L (the length in windows), p_block_L = P(some run of at least that many consecutive
-//                                  windows of L), p_none_L = 1 - p_block_L.  A run goes on from chunk c-1 into chunk c where the two are
-//                                  adjacent in the chunk list and carry the same contig name (the rule of --numBlocks); the pieces of a
-//                                  scope that no such join connects are independent, and their log_p_none add.
-static int write_kept_blocks(hf_ctx* ctx, const hfio_table* tab, const std::vector<Region>* regions, const int32_t minLenWindows[4],
-                             const std::vector<std::string>& labelNames, const std::string& dir) {
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    // a row: scope, name, its windows and its window ranges [first, last]
-    struct Row { const char* scope; std::string name; int64_t n; std::vector<std::pair<int64_t, int64_t>> ranges; };
-    std::vector<Row> rows;
-    rows.push_back(Row{"all", "all", 0, {}});
-    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
-    std::map<std::string, size_t> ctgRow;
-    for (int c = 0; c < C; c++) {
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        joined[(size_t) c] = c > 0 && ctg == hfio_chunk_ctg(tab, c - 1);
-        auto it = ctgRow.find(ctg);
-        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{"contig", ctg, 0, {}}); }
-        if (w.chunk_off[c] == w.chunk_off[c + 1]) continue;
-        for (size_t ri : {(size_t) 0, it->second}) {
-            Row& r = rows[ri];
-            r.n += w.chunk_off[c + 1] - w.chunk_off[c];
-            if (!r.ranges.empty() && r.ranges.back().second + 1 == w.chunk_off[c]) r.ranges.back().second = w.chunk_off[c + 1] - 1;
-            else r.ranges.push_back({w.chunk_off[c], w.chunk_off[c + 1] - 1});
-        }
-    }
-    if (regions) {
-        std::vector<int64_t> wbases;
-        window_bases(w, C, wbases, nullptr);
-        std::vector<std::vector<int64_t>> wins;
-        std::vector<std::vector<std::pair<int64_t, int64_t>>> ranges;
-        region_windows(tab, w, C, wbases, *regions, wins, ranges);
-        for (size_t i = 0; i < regions->size(); i++) rows.push_back(Row{"region", (*regions)[i].name, (int64_t) wins[i].size(), ranges[i]});
-    }
-    std::vector<int64_t> first, last;
-    std::vector<uint8_t> mask;
-    std::vector<int32_t> len;
-    for (const Row& r : rows)
-        for (const auto& rg : r.ranges)
-            for (int l = 0; l < 4; l++) { first.push_back(rg.first); last.push_back(rg.second); mask.push_back((uint8_t) (1u << l)); len.push_back(minLenWindows[l]); }
-    std::vector<double> none(first.size());
-    const int rc = hf_get_long_run_log_probs(ctx, (int64_t) first.size(), first.data(), last.data(), mask.data(), len.data(), joined.data(),
-                                             none.data(), nullptr);
-    if (rc != HF_OK) return rc;
-    const std::string tp = dir + "/kept_block_probabilities.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#scope\tname\tn_windows");
-    for (int l = 0; l < 4; l++) {
-        const char* name = labelNames.size() > (size_t) l ? labelNames[(size_t) l].c_str() : kRunLabelNames[l];
-        fprintf(f, "\tmin_windows_%s\tp_block_%s\tp_none_%s", name, name, name);
-    }
-    fprintf(f, "\n");
-    size_t j = 0;
-    for (const Row& r : rows) {
-        fprintf(f, "%s\t%s\t%ld", r.scope, r.name.c_str(), (long) r.n);
-        double s[4] = {0, 0, 0, 0};                                   // sums over the ranges, in order
-        for (size_t k = 0; k < r.ranges.size(); k++)
-            for (int l = 0; l < 4; l++) s[l] += none[j++];
-        for (int l = 0; l < 4; l++) {
-            if (r.n == 0) fprintf(f, "\tNA\tNA\tNA");
-            else fprintf(f, "\t%d\t%.6g\t%.6g", (int) minLenWindows[l], -std::expm1(s[l]) + 0.0, std::exp(s[l]));
-        }
-        fprintf(f, "\n");
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --constrainedPosterior: the posterior under --minimumLengths (hf_minlen_posterior, run by the caller) and the mass the rule keeps.
-//   admissible_mass.tsv                      a header line and a line with the four lengths in windows; then a header line and one row for
-//                                            the whole track ("all") and one per contig (order of first appearance in the chunk list):
-//                                            chunks, windows, log_mass = the chunks' log P(path admissible | data) summed in list order.
-//                                            perChunkRule (--mergedChunks: the chunks' masses of a run under the per-chunk rule, while the
-//                                            context holds the run over the joined chunks) adds the column log_mass_per_chunk_rule.
-//   posterior_prediction_min_lengths.bed     hfio_write_posterior_bed with the constrained posterior and its argmax labels
-static int write_constrained_posterior(hf_ctx* ctx, hfio_table* tab, const int32_t minLenWindows[4], const std::string& dir,
-                                       const std::vector<double>* perChunkRule = nullptr) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    std::vector<double> mass((size_t) std::max(C, 1));
-    int rc = hf_get_minlen_chunk_log_mass(ctx, mass.data(), nullptr);
-    if (rc != HF_OK) return rc;
-    struct Row { std::string name; int chunks; int64_t n; double log_mass, per_chunk; };
-    std::vector<Row> rows;
-    rows.push_back(Row{"all", 0, 0, 0.0, 0.0});
-    std::map<std::string, size_t> ctgRow;
-    for (int c = 0; c < C; c++) {
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        auto it = ctgRow.find(ctg);
-        if (it == ctgRow.end()) { it = ctgRow.emplace(ctg, rows.size()).first; rows.push_back(Row{ctg, 0, 0, 0.0, 0.0}); }
-        for (size_t ri : {(size_t) 0, it->second}) {
-            Row& r = rows[ri];
-            r.chunks++;
-            r.n += w.chunk_off[c + 1] - w.chunk_off[c];
-            r.log_mass += mass[(size_t) c];
-            if (perChunkRule) r.per_chunk += (*perChunkRule)[(size_t) c];
-        }
-    }
-    const std::string tp = dir + "/admissible_mass.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#min_windows_Err\tmin_windows_Dup\tmin_windows_Hap\tmin_windows_Col\n%d\t%d\t%d\t%d\n", minLenWindows[0], minLenWindows[1],
-            minLenWindows[2], minLenWindows[3]);
-    fprintf(f, "#scope\tchunks\twindows\tlog_mass%s\n", perChunkRule ? "\tlog_mass_per_chunk_rule" : "");
-    for (const Row& r : rows) {
-        fprintf(f, "%s\t%d\t%ld\t%.17g", r.name.c_str(), r.chunks, (long) r.n, r.log_mass + 0.0);
-        if (perChunkRule) fprintf(f, "\t%.17g", r.per_chunk + 0.0);
-        fprintf(f, "\n");
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    std::vector<double> post((size_t) N * 4);
-    std::vector<int8_t> lab((size_t) N);
-    if ((rc = hf_get_minlen_posterior(ctx, 0, N, post.data())) != HF_OK) return rc;
-    if ((rc = hf_get_minlen_posterior_labels(ctx, lab.data())) != HF_OK) return rc;
-    const std::string pp = dir + "/posterior_prediction_min_lengths.bed";
-    if (hfio_write_posterior_bed(tab, post.data(), lab.data(), pp.c_str()) != 0) { hf_cli_set_error(pp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
-
-// --jointEntropy: exact path entropy and log-probability of the final labels (hf_get_path_entropy, hf_get_path_log_probs,
-// hf_get_entropy_profile) under the model of the last full pass.
-//   path_uncertainty.tsv   one row per scope.  Scopes: "all" and every contig by name (order of first appearance in the chunk list; chunks
-//                          are independent chains, so a contig's values are the sums over its maximal runs of consecutive chunks, in list
-//                          order: the rule of --numBlocks).  Columns: windows, path_entropy_nats, entropy_nats_per_window,
-//                          window_entropy_sum_nats (the sum of the per-window posterior entropies in window order: what the posterior
-//                          alone gives), final_labels_log_prob (-inf where the labels are impossible, NA where a label of the scope is
-//                          outside 0..3).
-static int write_path_uncertainty(hf_ctx* ctx, const hfio_table* tab, const int8_t* finalLabels, const std::string& dir) {
-    const int64_t N = hfio_n_windows(tab);
-    const int C = hfio_n_chunks(tab);
-    hf_windows w{};
-    hfio_windows(tab, &w);
-    // a scope: its name and its window ranges [a, b)
-    struct Scope { std::string name; std::vector<std::pair<int64_t, int64_t>> ranges; };
-    std::vector<Scope> scopes;
-    scopes.push_back(Scope{"all", {}});
-    if (N > 0) scopes.back().ranges.push_back({0, N});
-    std::map<std::string, size_t> ctgScope;
-    for (int c = 0; c < C; c++) {
-        const int64_t a = w.chunk_off[c], b = w.chunk_off[c + 1];
-        const std::string ctg = hfio_chunk_ctg(tab, c);
-        auto it = ctgScope.find(ctg);
-        if (it == ctgScope.end()) { it = ctgScope.emplace(ctg, scopes.size()).first; scopes.push_back(Scope{ctg, {}}); }
-        if (a == b) continue;
-        auto& rg = scopes[it->second].ranges;
-        if (!rg.empty() && rg.back().second == a) rg.back().second = b;
-        else rg.push_back({a, b});
-    }
-    // the jobs: every range of every scope; the labelled ones only where every label of the range is a state
-    std::vector<int64_t> first, last, lfirst, llast;
-    std::vector<char> labelled;
-    for (const Scope& sc : scopes)
-        for (const auto& rg : sc.ranges) {
-            first.push_back(rg.first); last.push_back(rg.second - 1);
-            bool ok = true;
-            for (int64_t t = rg.first; t < rg.second && ok; t++) ok = finalLabels[t] >= 0 && finalLabels[t] <= 3;
-            labelled.push_back(ok);
-            if (ok) { lfirst.push_back(rg.first); llast.push_back(rg.second - 1); }
-        }
-    std::vector<double> ent(first.size()), lp(lfirst.size()), marg((size_t) N);
-    int rc = hf_get_path_entropy(ctx, (int64_t) first.size(), first.data(), last.data(), ent.data());
-    if (rc != HF_OK) return rc;
-    if ((rc = hf_get_path_log_probs(ctx, (int64_t) lfirst.size(), lfirst.data(), llast.data(), finalLabels, lp.data())) != HF_OK) return rc;
-    if (N > 0 && (rc = hf_get_entropy_profile(ctx, 0, N, marg.data(), nullptr)) != HF_OK) return rc;
-    const std::string tp = dir + "/path_uncertainty.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
-    fprintf(f, "#scope\twindows\tpath_entropy_nats\tentropy_nats_per_window\twindow_entropy_sum_nats\tfinal_labels_log_prob\n");
-    size_t j = 0, jl = 0;
-    for (const Scope& sc : scopes) {
-        int64_t windows = 0;
-        double h = 0.0, hw = 0.0, l = 0.0;       // sums over the ranges, list order
-        bool known = true;
-        for (const auto& rg : sc.ranges) {
-            windows += rg.second - rg.first;
-            h += ent[j];
-            for (int64_t t = rg.first; t < rg.second; t++) hw += marg[(size_t) t];
-            if (labelled[j]) l += lp[jl++];
-            else known = false;
-            j++;
-        }
-        fprintf(f, "%s\t%ld\t%.9g\t%.9g\t%.9g\t", sc.name.c_str(), (long) windows, h, windows > 0 ? h / (double) windows : 0.0, hw);
-        if (!known) fprintf(f, "NA\n");
-        else if (std::isinf(l)) fprintf(f, "-inf\n");
-        else fprintf(f, "%.9g\n", l);
-    }
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
-    return HF_OK;
-}
+// the report files of late_outputs: Report, Jobs, TableFile and every write_* (the scopes and joins: hf_cli_scopes.h)
+#include "hf_cli_reports.h"
 
 // --sweepAlpha: the alpha TSV paths of the list (blank lines and lines starting with '#' skipped), every TSV read and checked
 static bool read_sweep_list(const char* listPath, std::vector<std::string>& paths, std::vector<std::vector<double>>& alphas) {
@@ -1815,7 +998,7 @@ struct EmRun {
     RunResult& res;
     FILE *llf = nullptr, *atf = nullptr, *lcf = nullptr;    // loglikelihood.tsv, --fitAlpha's alpha_trace.tsv, --lengthConstrainedEM's length_constrained_em.tsv
     std::vector<double> alphaStats;
-    std::vector<uint8_t> crossJoined;                       // --crossChunkEM: joined_chunks of the table (empty: the per-chunk rule)
+    std::vector<uint8_t> crossJoined;                       // --crossChunkEM: joined_by_contig of the table (empty: the per-chunk rule)
     int iter = 1, passes = 0;
     // EM+decode time (BASELINE metric): E-steps (decode included), M-steps and SQUAREM's algebra; writing the
     // log-likelihood, parameter and summary files and the log lines is output and not counted (it is still part of `emWall`)
@@ -1833,8 +1016,6 @@ static int timed_full_pass(Run& s, EmRun& em) {
     if (s.opt.phaseTiming) em.passMs.push_back(dt * 1e3);
     return r;
 }
-
-static std::vector<uint8_t> joined_chunks(const hfio_table* tab);
 
 // --lengthConstrainedEM: the E-step under --minimumLengths in the place of a full pass, and its row of length_constrained_em.tsv
 static int timed_minlen_pass(Run& s, EmRun& em) {
@@ -1873,7 +1054,7 @@ static int em_loop(Run& s, EmRun& em) {
         em.lcf = fopen((dir + "/length_constrained_em.tsv").c_str(), "w");
         if (!em.lcf) { fprintf(stderr, "[%s] Error: cannot write into %s\n", ts(), dir.c_str()); return EXIT_FAILURE; }
         fprintf(em.lcf, "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n");
-        if (o.crossChunkEM) em.crossJoined = joined_chunks(s.tab);
+        if (o.crossChunkEM) em.crossJoined = joined_by_contig(chunk_list(s.tab, s.w));
         fprintf(stderr, "[%s] --lengthConstrainedEM%s: the EM iterations fit under minimum run lengths of %d,%d,%d,%d windows (Err,Dup,Hap,Col)%s\n", ts(),
                 o.crossChunkEM ? " --crossChunkEM" : "", s.minLenWindows[0], s.minLenWindows[1], s.minLenWindows[2], s.minLenWindows[3],
                 o.crossChunkEM ? " over the joined chunks of a contig (only runs at a contig's ends are exempt)" : "");
@@ -1939,22 +1120,13 @@ static int em_loop(Run& s, EmRun& em) {
     return 0;
 }
 
-// --wholeContigs, --crossChunkEM: joined[c], chunk c continues chunk c-1 (adjacent in the chunk list, the same contig name: the rule of --numBlocks)
-static std::vector<uint8_t> joined_chunks(const hfio_table* tab) {
-    const int C = hfio_n_chunks(tab);
-    std::vector<uint8_t> joined((size_t) std::max(C, 1), 0);
-    for (int c = 1; c < C; c++) joined[(size_t) c] = std::string(hfio_chunk_ctg(tab, c)) == hfio_chunk_ctg(tab, c - 1);
-    return joined;
-}
-
-// ... and the maximal runs of `labels`, merged over every group of joined chunks (a chunk without windows ends a group), that touch
-// neither end of their group and have fewer than min_len windows of their label
-static long long short_inner_runs(const hf_windows& w, const std::vector<uint8_t>& joined, const int8_t* labels, const int32_t min_len[4]) {
+// --wholeContigs: the maximal runs of `labels`, merged over every group of joined chunks (group_end, hf_cli_scopes.h), that touch neither
+// end of their group and have fewer than min_len windows of their label
+static long long short_inner_runs(const ChunkList& list, const std::vector<uint8_t>& joined, const int8_t* labels, const int32_t min_len[4]) {
     long long count = 0;
-    for (int c0 = 0; c0 < w.n_chunks;) {
-        int c1 = c0 + 1;
-        while (c1 < w.n_chunks && joined[(size_t) c1] && w.chunk_off[c1 + 1] > w.chunk_off[c1] && w.chunk_off[c1] > w.chunk_off[c1 - 1]) c1++;
-        const int64_t t0 = w.chunk_off[c0], t1 = w.chunk_off[c1];
+    for (int c0 = 0; c0 < list.C;) {
+        const int c1 = group_end(list, joined.data(), c0);
+        const int64_t t0 = list.off[c0], t1 = list.off[c1];
         for (int64_t a = t0; a < t1;) {
             int64_t b = a;
             while (b + 1 < t1 && labels[b + 1] == labels[a]) b++;
@@ -1967,7 +1139,7 @@ static long long short_inner_runs(const hf_windows& w, const std::vector<uint8_t
 }
 
 // --expectedAccuracy chunks|contigs: the labelling of the largest expected gain under --minimumLengths (hf_get_mea_labels) into
-// `decoded`, and expected_accuracy.tsv: per contig (in the order of first appearance) and for the track (the sum of the contig rows, in
+// `decoded`, and expected_accuracy.tsv: per contig (the scopes of hf_cli_scopes.h behind "all") and for the track (the sum of the contig rows, in
 // row order) the windows, the unconstrained bound sum_t max_k g_t(k), the gain of the labels the final BED would carry without the
 // option (`argmax`, the labels of the final pass, with every run, merged over the joined chunks of a contig, shorter than its length in
 // windows turned to Hap), the gain decoded, and whether the final BED's own labelling is supported: every chunk's part of it has
@@ -1979,7 +1151,8 @@ static int expected_accuracy(Run& s, const int8_t* argmax, std::vector<int8_t>& 
     const int64_t* const off = s.w.chunk_off;
     const int32_t* const mw = s.minLenWindows;
     const double* const W = s.gains;
-    const std::vector<uint8_t> joined = joined_chunks(s.tab);
+    const ChunkList list = chunk_list(s.tab, s.w);
+    const std::vector<uint8_t> joined = joined_by_contig(list);
     decoded.assign((size_t) N, -1);
     std::vector<double> block((size_t) C, 0.0), post((size_t) N * 4);
     double total = 0.0;
@@ -1990,8 +1163,7 @@ static int expected_accuracy(Run& s, const int8_t* argmax, std::vector<int8_t>& 
     // the final BED's own rule, in windows
     std::vector<int8_t> rule(argmax, argmax + N);
     for (int c0 = 0; c0 < C;) {
-        int c1 = c0 + 1;
-        while (c1 < C && joined[(size_t) c1] && off[c1 + 1] > off[c1] && off[c1] > off[c1 - 1]) c1++;
+        const int c1 = group_end(list, joined.data(), c0);
         for (int64_t a = off[c0]; a < off[c1];) {
             int64_t b = a;
             while (b + 1 < off[c1] && argmax[b + 1] == argmax[a]) b++;
@@ -2001,22 +1173,20 @@ static int expected_accuracy(Run& s, const int8_t* argmax, std::vector<int8_t>& 
         }
         c0 = c1;
     }
-    std::vector<int64_t> first, last;
+    Jobs jobs;
     std::vector<int> jobChunk;
     for (int c = 0; c < C; c++)
-        if (off[c + 1] > off[c]) { first.push_back(off[c]); last.push_back(off[c + 1] - 1); jobChunk.push_back(c); }
-    std::vector<double> lp(first.size());
-    if ((rc = hf_get_path_log_probs(s.ctx, (int64_t) first.size(), first.data(), last.data(), rule.data(), lp.data())) != HF_OK) return rc;
+        if (off[c + 1] > off[c]) { jobs.add(off[c], off[c + 1]); jobChunk.push_back(c); }
+    std::vector<double> lp((size_t) jobs.n());
+    if ((rc = hf_get_path_log_probs(s.ctx, jobs.n(), jobs.first.data(), jobs.last.data(), rule.data(), lp.data())) != HF_OK) return rc;
     std::vector<char> chunkSupported((size_t) C, 1);
     for (size_t j = 0; j < lp.size(); j++) chunkSupported[(size_t) jobChunk[j]] = lp[j] > -HUGE_VAL;
     struct Row { std::string scope; long long windows = 0; double argmaxGain = 0.0, ruleGain = 0.0, decodedGain = 0.0; bool supported = true; };
-    std::vector<Row> rows;
-    std::map<std::string, size_t> rowOf;
+    const Scopes sc = contig_scopes(list);
+    std::vector<Row> rows(sc.scopes.size() - 1);               // the contigs; the track's row comes last here
+    for (size_t i = 0; i < rows.size(); i++) rows[i].scope = sc.scopes[i + 1].name;
     for (int c = 0; c < C; c++) {
-        const std::string ctg = hfio_chunk_ctg(s.tab, c);
-        auto it = rowOf.find(ctg);
-        if (it == rowOf.end()) { it = rowOf.emplace(ctg, rows.size()).first; rows.push_back(Row{}); rows.back().scope = ctg; }
-        Row& r = rows[it->second];
+        Row& r = rows[sc.scope_of_chunk[(size_t) c] - 1];
         r.windows += off[c + 1] - off[c];
         r.decodedGain += block[(size_t) c];
         r.supported = r.supported && chunkSupported[(size_t) c];
@@ -2038,13 +1208,12 @@ static int expected_accuracy(Run& s, const int8_t* argmax, std::vector<int8_t>& 
         track.supported = track.supported && r.supported;
     }
     rows.push_back(track);
-    const std::string tp = dir + "/expected_accuracy.tsv";
-    FILE* f = fopen(tp.c_str(), "w");
-    if (!f) { hf_cli_set_error(tp + " cannot be opened"); return HF_E_ARG; }
+    TableFile f;
+    if ((rc = f.open(dir + "/expected_accuracy.tsv")) != HF_OK) return rc;
     fprintf(f, "#scope\twindows\tgain_argmax\tgain_final_bed_rule\tgain_decoded\tfinal_bed_rule_supported\n");
     for (const Row& r : rows)
         fprintf(f, "%s\t%lld\t%.17g\t%.17g\t%.17g\t%d\n", r.scope.c_str(), r.windows, r.argmaxGain, r.ruleGain, r.decodedGain, r.supported ? 1 : 0);
-    if (fclose(f) != 0) { hf_cli_set_error(tp + " cannot be written"); return HF_E_ARG; }
+    if ((rc = f.close()) != HF_OK) return rc;
     fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows (%s): expected gain %.6f (unconstrained bound %.6f, the final BED's own rule %.6f)\n",
             ts(), mw[0], mw[1], mw[2], mw[3], o.expectedAccuracy, track.decodedGain, track.argmaxGain, track.ruleGain);
     return HF_OK;
@@ -2105,9 +1274,10 @@ static int final_inference(Run& s, EmRun& em) {
         double pclp = 0.0;
         long long shortRuns = 0;
         if (o.wholeContigs) {
-            const std::vector<uint8_t> joined = joined_chunks(s.tab);
+            const ChunkList list = chunk_list(s.tab, s.w);
+            const std::vector<uint8_t> joined = joined_by_contig(list);
             pclp = clp;
-            shortRuns = short_inner_runs(s.w, joined, clabels.data(), mw);
+            shortRuns = short_inner_runs(list, joined, clabels.data(), mw);
             if ((rc = s.viterbi_minlen_joined(em.model, mw, joined.data(), clabels.data(), &clp)) != HF_OK) return em.die(rc);
         }
         int differ = 0;
@@ -2181,44 +1351,41 @@ static PathSampler admissible_sampler(hf_ctx* ctx, const int32_t* ml, const uint
 static int late_outputs(Run& s, EmRun& em) {
     const Options& o = s.opt;
     hf_ctx* const ctx = s.ctx;
-    hfio_table* const tab = s.tab;
-    const int8_t* const labels = em.finalLabels;
-    const std::string& dir = em.dir;
-    const std::vector<Region>* const regions = o.regionProbsPath ? &s.regions : nullptr;
     const int32_t* const mw = s.minLenWindows;
-    // --mergedChunks: the two options below apply the lengths over the joined chunks of a contig
-    const std::vector<uint8_t> joinedChunks = o.mergedChunks ? joined_chunks(tab) : std::vector<uint8_t>();
-    const uint8_t* const joined = o.mergedChunks ? joinedChunks.data() : nullptr;
+    std::unique_ptr<Report> rep;      // what the writers share: built for the first output that is wanted
+    // --mergedChunks: --constrainedPosterior and --admissibleSamples apply the lengths over the joined chunks of a contig
+    auto merged = [&] { return o.mergedChunks ? rep->joined.data() : nullptr; };
     double t0 = 0.0;
     struct LateOutput { bool wanted; const char *who, *done; std::function<int()> write; };
     const LateOutput outputs[] = {
         {o.uncertaintySamples > 0, "--uncertaintySamples needs", "posterior_samples_summary.tsv and final_label_runs_support.bed are written", [&] {
              fprintf(stderr, "[%s] [Final Inference] Drawing %d posterior state paths (seed %llu) ...\n", ts(), o.uncertaintySamples, (unsigned long long) o.uncertaintySeed);
-             return write_sample_outputs(posterior_sampler(ctx, o.uncertaintySeed), em.model, tab, labels, o.uncertaintySamples, o.labelNames, dir,
-                                         "posterior_samples_summary.tsv", "final_label_runs_support.bed");
+             return write_sample_outputs(*rep, posterior_sampler(ctx, o.uncertaintySeed), em.model, o.uncertaintySamples, "posterior_samples_summary.tsv",
+                                         "final_label_runs_support.bed");
          }},
         {o.runConfidence || o.regionProbsPath, "--runConfidence and --regionProbs need", "exact interval probabilities written",
-         [&] { return write_interval_outputs(ctx, tab, labels, o.runConfidence, regions, o.labelNames, dir); }},
-        {o.runBoundaries, "--runBoundaries needs", "final_label_run_boundaries.tsv is written", [&] { return write_run_boundaries(ctx, tab, labels, dir); }},
-        {o.exactTotals, "--exactTotals needs", "label_totals_exact.tsv is written", [&] { return write_exact_totals(ctx, tab, labels, dir); }},
-        {o.numBlocks, "--numBlocks needs", "label_blocks_exact.tsv is written", [&] { return write_exact_blocks(ctx, tab, labels, dir); }},
+         [&] { return write_interval_outputs(*rep, o.runConfidence); }},
+        {o.runBoundaries, "--runBoundaries needs", "final_label_run_boundaries.tsv is written", [&] { return write_run_boundaries(*rep); }},
+        {o.exactTotals, "--exactTotals needs", "label_totals_exact.tsv is written", [&] { return write_exact_totals(*rep); }},
+        {o.numBlocks, "--numBlocks needs", "label_blocks_exact.tsv is written", [&] { return write_exact_blocks(*rep); }},
         {o.runLengthsSet, "--runLengths needs", o.minLenGiven ? "label_block_lengths_exact.tsv and label_blocks_kept_exact.tsv are written" : "label_block_lengths_exact.tsv is written",
-         [&] { return write_block_lengths(ctx, tab, labels, o.runLengths, o.minLenGiven ? mw : nullptr, dir); }},
-        {o.jointEntropy, "--jointEntropy needs", "path_uncertainty.tsv is written", [&] { return write_path_uncertainty(ctx, tab, labels, dir); }},
-        {o.keptBlocks, "--keptBlocks needs", "kept_block_probabilities.tsv is written", [&] { return write_kept_blocks(ctx, tab, regions, mw, o.labelNames, dir); }},
+         [&] { return write_block_lengths(*rep, o.runLengths, o.minLenGiven ? mw : nullptr); }},
+        {o.jointEntropy, "--jointEntropy needs", "path_uncertainty.tsv is written", [&] { return write_path_uncertainty(*rep); }},
+        {o.keptBlocks, "--keptBlocks needs", "kept_block_probabilities.tsv is written", [&] { return write_kept_blocks(*rep); }},
         // (a decoder of its own: it reads the final parameters, not the last pass; its line carries the mass it found)
         {o.constrainedPost, "--constrainedPosterior needs", nullptr, [&] {
+             const uint8_t* const joined = merged();
              double logMass = 0.0, perChunkMass = 0.0;
              // --mergedChunks: one run under the per-chunk rule first, for the column the whole-contig masses are compared with
              std::vector<double> perChunk;
              int rc = HF_OK;
              if (joined) {
-                 perChunk.resize((size_t) std::max(hfio_n_chunks(tab), 1));
+                 perChunk.resize((size_t) std::max(rep->C, 1));
                  rc = s.minlen_posterior(em.model, mw, nullptr, &perChunkMass);
                  if (rc == HF_OK) rc = hf_get_minlen_chunk_log_mass(ctx, perChunk.data(), nullptr);
              }
              if (rc == HF_OK) rc = s.minlen_posterior(em.model, mw, joined, &logMass);
-             if (rc == HF_OK) rc = write_constrained_posterior(ctx, tab, mw, dir, joined ? &perChunk : nullptr);
+             if (rc == HF_OK) rc = write_constrained_posterior(*rep, joined ? &perChunk : nullptr);
              if (rc == HF_OK && joined)
                  fprintf(stderr, "[%s] [Final Inference] Minimum run lengths %d,%d,%d,%d windows over merged chunks keep posterior mass exp(%.6f) (per chunk: exp(%.6f)); admissible_mass.tsv and posterior_prediction_min_lengths.bed are written (%.1f ms).\n",
                          ts(), mw[0], mw[1], mw[2], mw[3], logMass, perChunkMass, (real_time() - t0) * 1e3);
@@ -2228,17 +1395,17 @@ static int late_outputs(Run& s, EmRun& em) {
          }},
         {o.admissibleSamples > 0, "--admissibleSamples needs", "admissible_samples_summary.tsv and admissible_label_runs_support.bed are written", [&] {
              fprintf(stderr, "[%s] [Final Inference] Drawing %d admissible state paths (minimum run lengths %d,%d,%d,%d windows%s, seed %llu) ...\n", ts(),
-                     o.admissibleSamples, mw[0], mw[1], mw[2], mw[3], joined ? " over merged chunks" : "", (unsigned long long) o.uncertaintySeed);
-             return write_sample_outputs(admissible_sampler(ctx, mw, joined, o.uncertaintySeed), em.model, tab, labels, o.admissibleSamples, o.labelNames, dir,
+                     o.admissibleSamples, mw[0], mw[1], mw[2], mw[3], merged() ? " over merged chunks" : "", (unsigned long long) o.uncertaintySeed);
+             return write_sample_outputs(*rep, admissible_sampler(ctx, mw, merged(), o.uncertaintySeed), em.model, o.admissibleSamples,
                                          "admissible_samples_summary.tsv", "admissible_label_runs_support.bed");
          }},
-        {o.totalsDistributionSet, "--totalsDistribution needs", "region_label_totals_exact.tsv is written",
-         [&] { return write_region_totals(ctx, tab, *regions, o.totalsDistribution, dir); }},
+        {o.totalsDistributionSet, "--totalsDistribution needs", "region_label_totals_exact.tsv is written", [&] { return write_region_totals(*rep, o.totalsDistribution); }},
     };
     for (const LateOutput& out : outputs) {
         if (!out.wanted) continue;
         if (!has_single_gpu_context(s, out.who)) return EXIT_FAILURE;
         t0 = real_time();
+        if (!rep) rep.reset(new Report(s, em.finalLabels, em.dir));
         const int rc = out.write();
         if (rc != HF_OK) return em.die(rc);
         if (out.done) fprintf(stderr, "[%s] [Final Inference] %s (%.1f ms).\n", ts(), out.done, (real_time() - t0) * 1e3);

@@ -59,7 +59,15 @@ struct JobCut {
     }
 };
 
-// the join rule: is part k of the job whose first part is k0 joined to part k - 1?  (Part has an int member c, its chunk)
+// THE statement of "chunk c continues chunk c - 1" over a chunk list (off: the C chunks' first windows and the end): it is joined to it
+// and both have windows.  The groups of the whole-contig decoders (hf_minlen.hip) and of the command line (hf_cli_scopes.h group_end)
+// are the maximal sequences of chunks that continue each other.
+inline bool chunk_continues(const int64_t* off, int64_t C, const uint8_t* joined, int64_t c) {
+    return c > 0 && c < C && joined && joined[c] != 0 && off[c + 1] > off[c] && off[c] > off[c - 1];
+}
+
+// the join rule: is part k of the job whose first part is k0 joined to part k - 1?  (Part has an int member c, its chunk.)  This is
+// chunk_continues over parts: a chunk without windows has no part, so two parts in chunks c - 1 and c say that both have windows.
 template <class Part>
 inline bool part_joined(const Part* parts, int64_t k, int64_t k0, const uint8_t* joined) {
     return k > k0 && joined && parts[k].c == parts[k - 1].c + 1 && joined[parts[k].c] != 0;

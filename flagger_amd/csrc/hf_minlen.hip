@@ -7,6 +7,7 @@
 // Nothing outside this unit bears on its kernels' code.
 #define HF_HELPERS_ONLY   // of hf_decode.h, hf_sample.h (kernels: hf_decoders.hip) and hf_scan.h, hf_chunks.h (kernels: hf_estep.hip)
 #include "hf_host.h"
+#include "hf_jobs.h"   // chunk_continues: the one statement of which chunks form a group
 
 // ------------------------------------------------------------------------------------------
 // minimum-run-length Viterbi (hf_minlen.h): a decoder of its own beside hf_viterbi, one code path for both kinds of context (rows in
@@ -108,8 +109,7 @@ static int mlv_run(hf_ctx* ctx, const hf_params* p, const int32_t min_len[4], bo
             const std::vector<int64_t>& off = tr.h_off;
             v.h_goff.clear(); v.h_gchunk.clear();
             for (int c = 0; c < tr.C; c++) {
-                const bool cont = c > 0 && joined && joined[c] && off[(size_t) c + 1] > off[(size_t) c] && off[(size_t) c] > off[(size_t) c - 1];
-                if (!cont) { v.h_gchunk.push_back(c); v.h_goff.push_back(off[(size_t) c]); }
+                if (!chunk_continues(off.data(), tr.C, joined, c)) { v.h_gchunk.push_back(c); v.h_goff.push_back(off[(size_t) c]); }
             }
             v.h_goff.push_back(off[(size_t) tr.C]);
             const size_t G = v.h_gchunk.size();
@@ -374,7 +374,7 @@ int hf_get_minlen_sample_labels(hf_ctx* ctx, int k, int8_t* labels_host) {
 static int mlg_cut(const Track& tr, const uint8_t* joined, DevBuf& grp, std::vector<int64_t>& h, hipStream_t st, const std::string& w, int* nb) {
     const std::vector<int64_t>& off = tr.h_off;
     const size_t C = (size_t) tr.C;
-    auto cont = [&](size_t c) { return c > 0 && c < C && joined && joined[c] && off[c + 1] > off[c] && off[c] > off[c - 1]; };
+    auto cont = [&](size_t c) { return chunk_continues(off.data(), (int64_t) C, joined, (int64_t) c); };
     h.assign(C + 1, 0);
     h[C] = off[C];
     int64_t gend = off[C];

@@ -6,7 +6,7 @@
 //   0 job batch n_parts n_pieces 0 0      a job and the device batch it lands in
 //   1 job chunk a b p0 p1                 its parts, in order, each followed by
 //   2 job chunk t n g k                   the part's pieces: windows t .. t + n - 1, g = the piece's index and k = the part's in the batch
-// Before that, on every run, the join rule against answers written out by hand: a wrong one goes to stderr and ends it with status 3.
+// Before that, on every run, the join rule (part_joined, group_parts) and chunk_continues against answers written out by hand: a wrong one goes to stderr and ends it with status 3.
 #include "hf_jobs.h"
 #include <cstdio>
 #include <string>
@@ -44,6 +44,19 @@ static bool join_rule() {
     ok &= join_case("three chunks all joined", three, {0}, {29}, all3, ".JJ");
     // (the first parts of jobs 2 and 3 follow, in the batch, a part of the chunk before theirs, which theirs continues)
     ok &= join_case("a job's first part", three, {10, 0, 10, 25}, {29, 9, 19, 25}, all3, ".J...");
+    // chunk_continues, a letter per chunk: the chunk without windows continues nothing and nothing continues it
+    auto continues = [&](const char* name, const std::vector<int64_t>& off, const uint8_t* joined, const std::string& want) {
+        const int64_t C = (int64_t) off.size() - 1;
+        std::string got;
+        for (int64_t c = 0; c < C; c++) got += chunk_continues(off.data(), C, joined, c) ? 'J' : '.';
+        const bool good = got == want && !chunk_continues(off.data(), C, joined, C);      // (behind the list: nothing)
+        if (!good) std::fprintf(stderr, "chunk_continues, %s: want %s, got %s\n", name, want.c_str(), got.c_str());
+        return good;
+    };
+    ok &= continues("joined == nullptr", gap, nullptr, ".....");
+    ok &= continues("a chunk without windows", gap, all5, ".J..J");
+    ok &= continues("joined[c] == 0", gap, some5, ".....");
+    ok &= continues("three chunks all joined", three, all3, ".JJ");
     return ok;
 }
 
