@@ -15,6 +15,7 @@ result does not depend on the number of GPUs.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -31,7 +32,40 @@ STATE_NAMES = ("Err", "Dup", "Hap", "Col")
 
 
 def _dptr(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    return a.ctypes.data_as(N.p_double)
+
+
+def _ptr(a: Optional[np.ndarray]):
+    """The pointer the C ABI takes for the array `a`, by its dtype; None (an argument left out) stays None."""
+    return None if a is None else a.ctypes.data_as(N.pointer_of[a.dtype.name])
+
+
+def _unwritten(shape, dtype, fill=None) -> np.ndarray:
+    """An output array for the library to write into: uninitialised, or holding `fill` where the library may leave entries alone."""
+    return np.empty(shape, dtype=dtype) if fill is None else np.full(shape, fill, dtype=dtype)
+
+
+# a column of state sets (bit s = state s) for _jobs: Python refuses what no uint8 holds, the library the empty set and 16..255
+_MASK = (np.uint8, 0, 255, "a state mask must be 1..15")
+_INT32 = (np.int32, -2 ** 31, 2 ** 31 - 1)
+
+
+def _jobs(who: str, first, last, *columns) -> List[np.ndarray]:
+    """The job front of the range getters: first, last (int64) and every further column (values, dtype) or (values, dtype, lo, hi,
+    what) broadcast against each other, then each ravelled into a contiguous array of its dtype, in the order given.  A column with
+    a range raises ValueError("<who>: <what>") where a value lies outside lo..hi; whatever passes is the library's to judge."""
+    columns = ((first, np.int64), (last, np.int64)) + columns
+    out = []
+    for a, (_, dtype, *bounds) in zip(np.broadcast_arrays(*[np.asarray(c[0], np.int64) for c in columns]), columns):
+        if bounds and a.size and (a.min() < bounds[0] or a.max() > bounds[1]):
+            raise ValueError("%s: %s" % (who, bounds[2]))
+        out.append(np.ascontiguousarray(a.ravel(), dtype))
+    return out
+
+
+def _outputs(n: int, *specs) -> List[np.ndarray]:
+    """One uninitialised output array per spec for n jobs: a dtype gives shape (n,), (dtype, k) gives (n, k)."""
+    return [np.empty((n,) + spec[1:], dtype=spec[0]) if isinstance(spec, tuple) else np.empty(n, dtype=spec) for spec in specs]
 
 
 class HMM:
@@ -132,8 +166,7 @@ def getBestNumberOfCollapsedComps(store: WindowStore) -> int:
     """hmm_flagger.c:105-111 with the [2,10] clamp of :1012-1013."""
     cov = np.ascontiguousarray(store.cov, dtype=np.uint16)
     rc = np.asarray(store.region_coverages, dtype=np.int32)
-    k = N.lib().hfm_best_collapsed_comps(cov.ctypes.data_as(C.POINTER(C.c_uint16)), cov.size,
-                                         rc.ctypes.data_as(C.POINTER(C.c_int32)), rc.size)
+    k = N.lib().hfm_best_collapsed_comps(_ptr(cov), cov.size, _ptr(rc), rc.size)
     if k < 0:
         raise ValueError("a region coverage of 0 in the header")
     return k
@@ -144,7 +177,7 @@ def createModel(modelType: int, numberOfCollapsedComps: int, store: WindowStore,
     """hmm_flagger.c:164-237 (initialRandomDev = 0)."""
     rc = np.asarray(store.region_coverages, dtype=np.int32)
     a = np.ascontiguousarray(alphaMatrix, dtype=np.float64)
-    h = N.lib().hfm_create(modelType, numberOfCollapsedComps, rc.ctypes.data_as(C.POINTER(C.c_int32)), rc.size,
+    h = N.lib().hfm_create(modelType, numberOfCollapsedComps, _ptr(rc), rc.size,
                            int(store.start_only), store.avg_alignment_len, store.window_len, _dptr(a),
                            maxHighMapqRatio, minHighMapqRatio)
     if not h:
@@ -165,14 +198,8 @@ def _windows_struct(store: WindowStore, model: "HMM", adjustContigEnds: bool, mi
         e=np.ascontiguousarray(store.chunk_e, np.int32), cl=np.ascontiguousarray(store.chunk_ctg_len, np.int32))
     w = N.hf_windows()
     w.n_windows, w.n_chunks = store.n_windows, store.n_chunks
-    w.chunk_off = k["off"].ctypes.data_as(C.POINTER(C.c_int64))
-    w.cov = k["cov"].ctypes.data_as(C.POINTER(C.c_uint16))
-    w.mapq = k["mapq"].ctypes.data_as(C.POINTER(C.c_uint16))
-    w.clip = k["clip"].ctypes.data_as(C.POINTER(C.c_uint16))
-    w.annot = k["annot"].ctypes.data_as(C.POINTER(C.c_uint64))
-    w.chunk_s = k["s"].ctypes.data_as(C.POINTER(C.c_int32))
-    w.chunk_e = k["e"].ctypes.data_as(C.POINTER(C.c_int32))
-    w.chunk_ctg_len = k["cl"].ctypes.data_as(C.POINTER(C.c_int32))
+    w.chunk_off, w.cov, w.mapq, w.clip, w.annot = _ptr(k["off"]), _ptr(k["cov"]), _ptr(k["mapq"]), _ptr(k["clip"]), _ptr(k["annot"])
+    w.chunk_s, w.chunk_e, w.chunk_ctg_len = _ptr(k["s"]), _ptr(k["e"]), _ptr(k["cl"])
     w.window_len, w.mean_read_len = store.window_len, store.avg_alignment_len
     w.adjust_contig_ends, w.min_read_frac = int(adjustContigEnds), float(minReadFractionAtEnds)
     w.max_high_mapq_ratio = L.hfm_max_high_mapq_ratio(model._h)
@@ -199,18 +226,31 @@ class MultiEMList:
     def __init__(self, store: WindowStore, model: "HMM", n_devices: int, adjustContigEnds: bool = True,
                  minReadFractionAtEnds: float = 0.95, devices: Optional[Sequence[int]] = None, algo: int = N.HF_ALGO_SCAN,
                  exchange: int = N.HF_EXCHANGE_CHUNKS, transport: int = N.HF_TRANSPORT_RCCL):
-        L = N.lib()
-        self._L, self.store = L, store
+        w = self._set_up(store, model, adjustContigEnds, minReadFractionAtEnds)
+        dev = (C.c_int * n_devices)(*devices) if devices is not None else None
+        h = C.c_void_p()
+        self._check(self._L.hf_multi_create(C.byref(w), self.n_regions, self.max_comps, n_devices, dev, algo, exchange, transport, C.byref(h)),
+                    "hf_multi_create")
+        self._h, self.world = h, n_devices
+
+    # what labels() and posterior() hold where the library writes nothing: None leaves the array uninitialised (this class: every
+    # window is some shard's)
+    _labels_fill = _posterior_fill = None
+
+    def _set_up(self, store: WindowStore, model: "HMM", adjustContigEnds: bool, minReadFractionAtEnds: float):
+        """What either constructor needs before its hf_multi_create*: the hf_windows of the store (returned; self._keep holds its
+        arrays), the layout of the statistics vector and the vector itself."""
+        self._L, self.store = N.lib(), store
         w, self._keep = _windows_struct(store, model, adjustContigEnds, minReadFractionAtEnds)
         self.n_regions, self.max_comps = model.numberOfRegions, model.maxNumberOfComps
         self.stats_len = N.stats_len(self.n_regions, self.max_comps)
-        dev = (C.c_int * n_devices)(*devices) if devices is not None else None
-        h = C.c_void_p()
-        rc = L.hf_multi_create(C.byref(w), self.n_regions, self.max_comps, n_devices, dev, algo, exchange, transport, C.byref(h))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_create")
-        self._h, self.world = h, n_devices
         self._stats = np.empty(self.stats_len, dtype=np.float64)
+        return w
+
+    @staticmethod
+    def _check(rc: int, where: str) -> None:
+        if rc != N.HF_OK:
+            raise MultiHFError(rc, where)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -222,9 +262,7 @@ class MultiEMList:
 
     def run_sharded(self, model: "HMM", mode: int) -> np.ndarray:
         p = model.params()
-        rc = self._L.hf_multi_estep(self._h, C.byref(p), mode, _dptr(self._stats))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_estep")
+        self._check(self._L.hf_multi_estep(self._h, C.byref(p), mode, _dptr(self._stats)), "hf_multi_estep")
         return self._stats.copy()
 
     def em_iterate(self, model: "HMM", do_mstep: bool = True, tol: float = 1e-3, mode: int = N.HF_MODE_FULL) -> bool:
@@ -235,7 +273,7 @@ class MultiEMList:
             self._cv_ref = C.byref(self._cv)
         rc = self._L.hf_multi_em_iterate(self._h, model._h, mode, int(do_mstep), tol, self._stats_ptr, self._cv_ref)
         if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_em_iterate")
+            self._check(rc, "hf_multi_em_iterate")
         model.estimators = self._stats
         model.loglikelihood = float(self._stats[0])
         return bool(self._cv.value)
@@ -249,18 +287,19 @@ class MultiEMList:
         return [(int(self._L.hf_multi_shard_chunks(self._h, r)), int(self._L.hf_multi_shard_windows(self._h, r))) for r in range(self.world)]
 
     def labels(self) -> np.ndarray:
-        out = np.empty(self.store.n_windows, dtype=np.int8)
-        rc = self._L.hf_multi_get_labels(self._h, out.ctypes.data_as(C.POINTER(C.c_int8)))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_labels")
+        """The labels of the last full pass, int8[n_windows] (hf_multi_get_labels).  RankEMList: labels of ALL windows' positions, but
+        only this rank's range is known here: the others are -1 (hf_multi_get_labels fills this rank's windows at their global
+        positions).  Use local_labels() for the rank's own slice."""
+        out = _unwritten(self.store.n_windows, np.int8, self._labels_fill)
+        self._check(self._L.hf_multi_get_labels(self._h, _ptr(out)), "hf_multi_get_labels")
         return out
 
     def posterior(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Posteriors of windows first .. first + n (hf_multi_get_posterior).  RankEMList: rows of windows that other ranks hold are
+        NaN."""
         n = self.store.n_windows - first if n is None else n
-        out = np.empty((n, 4), dtype=np.float64)
-        rc = self._L.hf_multi_get_posterior(self._h, first, n, _dptr(out))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_posterior")
+        out = _unwritten((n, 4), np.float64, self._posterior_fill)
+        self._check(self._L.hf_multi_get_posterior(self._h, first, n, _dptr(out)), "hf_multi_get_posterior")
         return out
 
     def viterbi(self, model: "HMM"):
@@ -268,17 +307,11 @@ class MultiEMList:
         labels of other ranks' windows are -1, the scores cover every chunk."""
         p = model.params()
         lp = C.c_double(0.0)
-        rc = self._L.hf_multi_viterbi(self._h, C.byref(p), C.byref(lp))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_viterbi")
+        self._check(self._L.hf_multi_viterbi(self._h, C.byref(p), C.byref(lp)), "hf_multi_viterbi")
         labels = np.full(self.store.n_windows, -1, dtype=np.int8)
-        rc = self._L.hf_multi_get_viterbi_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8)))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_viterbi_labels")
+        self._check(self._L.hf_multi_get_viterbi_labels(self._h, _ptr(labels)), "hf_multi_get_viterbi_labels")
         ll = np.empty(self.store.n_chunks, dtype=np.float64)
-        rc = self._L.hf_multi_get_viterbi_chunk_log_probs(self._h, _dptr(ll))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_viterbi_chunk_log_probs")
+        self._check(self._L.hf_multi_get_viterbi_chunk_log_probs(self._h, _dptr(ll)), "hf_multi_get_viterbi_chunk_log_probs")
         return labels, ll, float(lp.value)
 
 
@@ -300,20 +333,15 @@ class RankEMList(MultiEMList):
     def __init__(self, store: WindowStore, model: "HMM", world: int, rank: int, device: int, unique_id: bytes,
                  adjustContigEnds: bool = True, minReadFractionAtEnds: float = 0.95, algo: int = N.HF_ALGO_SCAN,
                  exchange: int = N.HF_EXCHANGE_CHUNKS):
-        L = N.lib()
-        self._L, self.store = L, store
-        w, self._keep = _windows_struct(store, model, adjustContigEnds, minReadFractionAtEnds)
-        self.n_regions, self.max_comps = model.numberOfRegions, model.maxNumberOfComps
-        self.stats_len = N.stats_len(self.n_regions, self.max_comps)
+        w = self._set_up(store, model, adjustContigEnds, minReadFractionAtEnds)
+        L = self._L
         if len(unique_id) != HF_COMM_ID_BYTES:
             raise ValueError("unique_id must be the %d bytes of comm_unique_id()" % HF_COMM_ID_BYTES)
         self._id = C.create_string_buffer(unique_id, HF_COMM_ID_BYTES)
         h = C.c_void_p()
-        rc = L.hf_multi_create_rank(C.byref(w), self.n_regions, self.max_comps, world, rank, device, algo, exchange, self._id, C.byref(h))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_create_rank")
+        self._check(L.hf_multi_create_rank(C.byref(w), self.n_regions, self.max_comps, world, rank, device, algo, exchange, self._id, C.byref(h)),
+                    "hf_multi_create_rank")
         self._h, self.world, self.rank = h, world, rank
-        self._stats = np.empty(self.stats_len, dtype=np.float64)
         self.first_window = int(L.hf_multi_local_first_window(h))
         self.n_local_windows = int(L.hf_multi_local_windows(h))
         # borrowed view of the rank's context: profiling switches and kernel times (bench.py)
@@ -326,23 +354,7 @@ class RankEMList(MultiEMList):
             self.em._h = None
         super().close()
 
-    def labels(self) -> np.ndarray:
-        """Labels of ALL windows' positions, but only this rank's range is known here: the others are -1 (hf_multi_get_labels
-        fills this rank's windows at their global positions).  Use local_labels() for the rank's own slice."""
-        out = np.full(self.store.n_windows, -1, dtype=np.int8)
-        rc = self._L.hf_multi_get_labels(self._h, out.ctypes.data_as(C.POINTER(C.c_int8)))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_labels")
-        return out
-
-    def posterior(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
-        """Posteriors of windows first .. first + n; rows of windows that other ranks hold are NaN."""
-        n = self.store.n_windows - first if n is None else n
-        out = np.full((n, 4), np.nan, dtype=np.float64)
-        rc = self._L.hf_multi_get_posterior(self._h, first, n, _dptr(out))
-        if rc != N.HF_OK:
-            raise MultiHFError(rc, "hf_multi_get_posterior")
-        return out
+    _labels_fill, _posterior_fill = -1, np.nan       # the windows of other ranks, which the library leaves alone
 
     def local_labels(self) -> np.ndarray:
         """Labels of this rank's windows (global positions first_window .. first_window + n_local_windows)."""
@@ -532,7 +544,7 @@ class EMList:
     # --- results ---
     def labels(self) -> np.ndarray:
         out = np.empty(self.store.n_windows, dtype=np.int8)
-        N.check(self._L.hf_get_labels(self._h, out.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_labels")
+        N.check(self._L.hf_get_labels(self._h, _ptr(out)), "hf_get_labels")
         return out
 
     def posterior(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
@@ -555,7 +567,7 @@ class EMList:
         lp = C.c_double(0.0)
         N.check(getattr(self._L, fin)(self._h, C.byref(lp), self.stream), fin)
         labels = np.empty(self.store.n_windows, dtype=np.int8)
-        N.check(getattr(self._L, lab)(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), lab)
+        N.check(getattr(self._L, lab)(self._h, _ptr(labels)), lab)
         ll = np.empty(self.store.n_chunks, dtype=np.float64)
         N.check(getattr(self._L, chunk)(self._h, _dptr(ll)), chunk)
         return labels, ll, float(lp.value)
@@ -577,23 +589,24 @@ class EMList:
         a group's score in the entry of its first chunk and 0.0 in the others."""
         ml = self._four_lengths("viterbi_minlen", min_len)
         p = model.params()
-        mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
-        if joined is None:
-            N.check(self._L.hf_viterbi_minlen(self._h, C.byref(p), mlp, self.stream), "hf_viterbi_minlen")
-        else:
-            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
-            if jn.size != int(self._L.hf_n_chunks(self._h)):
-                raise ValueError("viterbi_minlen: joined must have one entry per chunk")
-            N.check(self._L.hf_viterbi_minlen_joined(self._h, C.byref(p), mlp, jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream),
-                    "hf_viterbi_minlen_joined")
+        self._minlen("viterbi_minlen", C.byref(p), ml, self._joined_u8("viterbi_minlen", joined), self.stream)
         return self._decoded("viterbi_minlen")
 
-    def _joined_u8(self, who: str, joined) -> np.ndarray:
-        """joined as the uint8[n_chunks] the C ABI takes; `who` names the caller in the refusal."""
+    def _joined_u8(self, who: str, joined) -> Optional[np.ndarray]:
+        """joined as the uint8[n_chunks] the C ABI takes, None (no joins) as None; `who` names the caller in the refusal."""
+        if joined is None:
+            return None
         jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
         if jn.size != int(self._L.hf_n_chunks(self._h)):
             raise ValueError("%s: joined must have one entry per chunk" % who)
         return jn
+
+    def _minlen(self, base: str, head, ml: np.ndarray, jn: Optional[np.ndarray], *tail) -> None:
+        """The one fork of the minimum-run-length family: hf_<base>(ctx, head, min_len, *tail), or, with joins, hf_<base>_joined(ctx,
+        head, min_len, joined, *tail).  head: the parameters or the model handle; ml, jn: what _four_lengths and _joined_u8 returned.
+        An error names the entry point that was called."""
+        name = "hf_" + base if jn is None else "hf_%s_joined" % base
+        N.check(getattr(self._L, name)(self._h, head, _ptr(ml), *(() if jn is None else (_ptr(jn),)), *tail), name)
 
     def minlen_posterior(self, model: HMM, min_len, joined=None) -> "MinLenPosterior":
         """The posterior given that every run has at least min_len[s] windows (states 0 Err, 1 Dup, 2 Hap, 3 Col; runs at a chunk's
@@ -604,16 +617,12 @@ class EMList:
         ml = self._four_lengths("minlen_posterior", min_len)
         p = model.params()
         tot = C.c_double(0.0)
-        jn = None if joined is None else self._joined_u8("minlen_posterior", joined)
+        jn = self._joined_u8("minlen_posterior", joined)
         self._mlp_run = getattr(self, "_mlp_run", 0) + 1     # (older results stop answering posterior(): the context holds one run)
-        if jn is None:
-            N.check(self._L.hf_minlen_posterior(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_minlen_posterior")
-        else:
-            N.check(self._L.hf_minlen_posterior_joined(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                       jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream), "hf_minlen_posterior_joined")
+        self._minlen("minlen_posterior", C.byref(p), ml, jn, self.stream)
         N.check(self._L.hf_minlen_posterior_finish(self._h, C.byref(tot), self.stream), "hf_minlen_posterior_finish")
         labels = np.empty(self.store.n_windows, dtype=np.int8)
-        N.check(self._L.hf_get_minlen_posterior_labels(self._h, labels.ctypes.data_as(C.POINTER(C.c_int8))), "hf_get_minlen_posterior_labels")
+        N.check(self._L.hf_get_minlen_posterior_labels(self._h, _ptr(labels)), "hf_get_minlen_posterior_labels")
         mass = np.empty(self.store.n_chunks, dtype=np.float64)
         lza = np.empty(self.store.n_chunks, dtype=np.float64)
         N.check(self._L.hf_get_minlen_chunk_log_mass(self._h, _dptr(mass), _dptr(lza)), "hf_get_minlen_chunk_log_mass")
@@ -628,12 +637,7 @@ class EMList:
         and log_z are sums over groups, and minlen_em_chunk_stats holds a group's values in the entries of its first chunk."""
         ml = self._four_lengths("estep_minlen", min_len)
         p = model.params()
-        if joined is None:
-            N.check(self._L.hf_estep_minlen(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_estep_minlen")
-        else:
-            jn = self._joined_u8("estep_minlen", joined)
-            N.check(self._L.hf_estep_minlen_joined(self._h, C.byref(p), ml.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   jn.ctypes.data_as(C.POINTER(C.c_uint8)), self.stream), "hf_estep_minlen_joined")
+        self._minlen("estep_minlen", C.byref(p), ml, self._joined_u8("estep_minlen", joined), self.stream)
         out = np.empty(self.stats_len, dtype=np.float64)
         lz = C.c_double(0.0)
         N.check(self._L.hf_estep_minlen_finish(self._h, _dptr(out), C.byref(lz), self.stream), "hf_estep_minlen_finish")
@@ -665,14 +669,8 @@ class EMList:
         ml = self._four_lengths("em_iterate_minlen", min_len)
         stats = np.empty(self.stats_len, dtype=np.float64)
         cv, lz = C.c_int(0), C.c_double(0.0)
-        if joined is None:
-            N.check(self._L.hf_em_iterate_minlen(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)), int(do_mstep), tol,
-                                                 _dptr(stats), C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen")
-        else:
-            jn = self._joined_u8("em_iterate_minlen", joined)
-            N.check(self._L.hf_em_iterate_minlen_joined(self._h, model._h, ml.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                        jn.ctypes.data_as(C.POINTER(C.c_uint8)), int(do_mstep), tol, _dptr(stats),
-                                                        C.byref(lz), C.byref(cv), self.stream), "hf_em_iterate_minlen_joined")
+        self._minlen("em_iterate_minlen", model._h, ml, self._joined_u8("em_iterate_minlen", joined), int(do_mstep), tol, _dptr(stats),
+                     C.byref(lz), C.byref(cv), self.stream)
         model.estimators = stats
         model.loglikelihood = float(stats[0])
         self.last_log_z = float(lz.value)
@@ -686,7 +684,7 @@ class EMList:
         as for viterbi_minlen: the rule then holds over every group of joined chunks, and block_gain holds a group's score in the
         entry of its first chunk and 0.0 in the others.  The last pass's results and every decoder's are left as they were."""
         ml = self._four_lengths("mea_labels", min_len)
-        jn = None if joined is None else self._joined_u8("mea_labels", joined)
+        jn = self._joined_u8("mea_labels", joined)
         gp = None
         if gain is not None:
             g = np.asarray(gain, dtype=np.float64)
@@ -697,9 +695,7 @@ class EMList:
         labels = np.empty(self.store.n_windows, dtype=np.int8)
         block = np.empty(self.store.n_chunks, dtype=np.float64)
         tot = C.c_double(0.0)
-        N.check(self._L.hf_get_mea_labels(self._h, gp, ml.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                          labels.ctypes.data_as(C.POINTER(C.c_int8)), _dptr(block), C.byref(tot)), "hf_get_mea_labels")
+        N.check(self._L.hf_get_mea_labels(self._h, gp, _ptr(ml), _ptr(jn), _ptr(labels), _dptr(block), C.byref(tot)), "hf_get_mea_labels")
         return labels, block, float(tot.value)
 
     @property
@@ -732,13 +728,13 @@ class EMList:
             draw(k0, n)
             N.check(getattr(self._L, finish)(self._h, self.stream), finish)
             for k in range(n):
-                N.check(getattr(self._L, get)(self._h, k, out[k0 + k].ctypes.data_as(C.POINTER(C.c_int8))), get)
+                N.check(getattr(self._L, get)(self._h, k, _ptr(out[k0 + k])), get)
         return out
 
     def minlen_sample_capacity(self, min_len) -> int:
         """Samples one hf_sample_paths_minlen call may draw at these lengths (hf_minlen_sample_capacity)."""
         ml = self._four_lengths("minlen_sample_capacity", min_len)
-        cap = int(self._L.hf_minlen_sample_capacity(self._h, ml.ctypes.data_as(C.POINTER(C.c_int32))))
+        cap = int(self._L.hf_minlen_sample_capacity(self._h, _ptr(ml)))
         if cap < 0:
             raise N.HFError(cap, "hf_minlen_sample_capacity")
         return cap
@@ -750,7 +746,7 @@ class EMList:
         decoder's are left as they were.  joined: None, or a bool array of n_chunks as for viterbi_minlen: every path is then
         admissible over its group of joined chunks (hf_sample_paths_minlen_joined)."""
         ml = self._four_lengths("sample_paths_minlen", min_len)
-        jn = None if joined is None else self._joined_u8("sample_paths_minlen", joined)
+        jn = self._joined_u8("sample_paths_minlen", joined)
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError("sample_paths_minlen: n_samples must be >= 1")
@@ -760,29 +756,16 @@ class EMList:
         if cap < 1:
             raise N.HFError(N.HF_E_ARG, "hf_minlen_sample_capacity")
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        mlp = ml.ctypes.data_as(C.POINTER(C.c_int32))
-        if jn is not None:
-            jp = jn.ctypes.data_as(C.POINTER(C.c_uint8))
-            return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: N.check(
-                self._L.hf_sample_paths_minlen_joined(self._h, C.byref(p), mlp, jp, int(first_sample) + k0, n, seed, self.stream),
-                "hf_sample_paths_minlen_joined"))
-        return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: N.check(
-            self._L.hf_sample_paths_minlen(self._h, C.byref(p), mlp, int(first_sample) + k0, n, seed, self.stream), "hf_sample_paths_minlen"))
+        return self._drawn(out, cap, "hf_sample_minlen_finish", "hf_get_minlen_sample_labels", lambda k0, n: self._minlen(
+            "sample_paths_minlen", C.byref(p), ml, jn, int(first_sample) + k0, n, seed, self.stream))
 
     def interval_log_probs(self, first, last, mask) -> np.ndarray:
         """Exact interval probabilities under the model of the last full pass (hf_get_interval_log_probs): for every job i,
         log P(every window of first[i]..last[i] (inclusive) has a state in the set mask[i] (bit s = state s) | data) -> float64[n].
         Scalars broadcast against arrays.  P(some window in state k) = -expm1 of the job with mask 15 & ~(1 << k)."""
-        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("interval_log_probs: a state mask must be 1..15")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        out = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_interval_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  _dptr(out)), "hf_get_interval_log_probs")
+        f, l, m = _jobs("interval_log_probs", first, last, (mask, *_MASK))
+        out, = _outputs(f.size, np.float64)
+        N.check(self._L.hf_get_interval_log_probs(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), _dptr(out)), "hf_get_interval_log_probs")
         return out
 
     def count_moments(self, first, last, mask, region=None, unit="windows"):
@@ -793,21 +776,10 @@ class EMList:
         units = {"windows": N.HF_COUNT_WINDOWS, "bases": N.HF_COUNT_BASES}
         if unit not in units:
             raise ValueError("count_moments: unit must be 'windows' or 'bases'")
-        f, l, m, r = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64),
-                                         np.asarray(-1 if region is None else region, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("count_moments: a state mask must be 1..15")
-        if r.size and (r.min() < -2 ** 31 or r.max() >= 2 ** 31):
-            raise ValueError("count_moments: a region must be -1 or a region index")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        r = np.ascontiguousarray(r.ravel(), np.int32)
-        mean = np.empty(f.size, dtype=np.float64)
-        var = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_count_moments(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                             None if region is None else r.ctypes.data_as(C.POINTER(C.c_int32)), units[unit],
+        f, l, m, r = _jobs("count_moments", first, last, (mask, *_MASK),
+                           (-1 if region is None else region, *_INT32, "a region must be -1 or a region index"))
+        mean, var = _outputs(f.size, np.float64, np.float64)
+        N.check(self._L.hf_get_count_moments(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), None if region is None else _ptr(r), units[unit],
                                              _dptr(mean), _dptr(var)), "hf_get_count_moments")
         return mean, var
 
@@ -816,23 +788,10 @@ class EMList:
         i, of the number of maximal runs of windows of first[i]..last[i] (inclusive) whose state is in the set mask[i].  joined: None, or
         a bool array of n_chunks, joined[c] true where chunk c continues chunk c - 1 (a run across that boundary is one run; joined[0]
         must be false) -> (mean float64[n], var float64[n]).  Scalars broadcast."""
-        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("run_moments: a state mask must be 1..15")
-        jn = None
-        if joined is not None:
-            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
-            if jn.size != int(self._L.hf_n_chunks(self._h)):
-                raise ValueError("run_moments: joined must have one entry per chunk")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        mean = np.empty(f.size, dtype=np.float64)
-        var = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_run_moments(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                           None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                           _dptr(mean), _dptr(var)), "hf_get_run_moments")
+        f, l, m = _jobs("run_moments", first, last, (mask, *_MASK))
+        jn = self._joined_u8("run_moments", joined)
+        mean, var = _outputs(f.size, np.float64, np.float64)
+        N.check(self._L.hf_get_run_moments(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), _ptr(jn), _dptr(mean), _dptr(var)), "hf_get_run_moments")
         return mean, var
 
     def long_run_log_probs(self, first, last, mask, min_len, joined=None):
@@ -840,28 +799,12 @@ class EMList:
         windows first[i]..last[i] (inclusive) hold a run of at least min_len[i] consecutive windows whose state is in the set mask[i]
         (the states may change inside the set).  joined: as for run_moments, a run goes on across a joined chunk boundary
         -> (log_p_none float64[n], log_p_some float64[n]): log P(no such run | data), log P(some such run | data).  Scalars broadcast."""
-        f, l, m, k = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64),
-                                         np.asarray(min_len, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("long_run_log_probs: a state mask must be 1..15")
-        if k.size and (k.min() < -2 ** 31 or k.max() >= 2 ** 31):
-            raise ValueError("long_run_log_probs: a length must be a positive number of windows")
-        jn = None
-        if joined is not None:
-            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
-            if jn.size != int(self._L.hf_n_chunks(self._h)):
-                raise ValueError("long_run_log_probs: joined must have one entry per chunk")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        k = np.ascontiguousarray(k.ravel(), np.int32)
-        none = np.empty(f.size, dtype=np.float64)
-        some = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_long_run_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  k.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                  None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  _dptr(none), _dptr(some)), "hf_get_long_run_log_probs")
+        f, l, m, k = _jobs("long_run_log_probs", first, last, (mask, *_MASK),
+                           (min_len, *_INT32, "a length must be a positive number of windows"))
+        jn = self._joined_u8("long_run_log_probs", joined)
+        none, some = _outputs(f.size, np.float64, np.float64)
+        N.check(self._L.hf_get_long_run_log_probs(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), _ptr(k), _ptr(jn), _dptr(none), _dptr(some)),
+                "hf_get_long_run_log_probs")
         return none, some
 
     def run_lengths(self, first, last, mask, max_len, joined=None) -> np.ndarray:
@@ -870,25 +813,13 @@ class EMList:
         the runs of exactly l windows, l = 1..max_len, column max_len the runs of more than max_len windows (max_len 1..64, one for
         the call).  joined: as for run_moments, a run goes on across a joined chunk boundary -> float64[n, max_len + 1].  Scalars
         broadcast."""
-        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("run_lengths: a state mask must be 1..15")
+        f, l, m = _jobs("run_lengths", first, last, (mask, *_MASK))
         L = int(max_len)
-        if L != max_len or not 1 <= L <= 64:
+        if L != max_len or not 1 <= L <= 64:                  # (refused here: the output's width comes from it)
             raise ValueError("run_lengths: max_len must be a number of windows in 1..64")
-        jn = None
-        if joined is not None:
-            jn = np.ascontiguousarray(np.asarray(joined).ravel() != 0, np.uint8)
-            if jn.size != int(self._L.hf_n_chunks(self._h)):
-                raise ValueError("run_lengths: joined must have one entry per chunk")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        out = np.empty((f.size, L + 1), dtype=np.float64)
-        N.check(self._L.hf_get_run_lengths(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)), L,
-                                           None if jn is None else jn.ctypes.data_as(C.POINTER(C.c_uint8)), _dptr(out)),
-                "hf_get_run_lengths")
+        jn = self._joined_u8("run_lengths", joined)
+        out, = _outputs(f.size, (np.float64, L + 1))
+        N.check(self._L.hf_get_run_lengths(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), L, _ptr(jn), _dptr(out)), "hf_get_run_lengths")
         return out
 
     def count_distribution(self, first, last, mask, max_count) -> np.ndarray:
@@ -896,50 +827,36 @@ class EMList:
         the posterior probability that exactly k windows of first[i]..last[i] (inclusive) have a state in the set mask[i]: column k
         for k = 0..max_count, column max_count + 1 the probability of more than max_count windows (max_count 1..62, one for the
         call) -> float64[n, max_count + 2].  Scalars broadcast."""
-        f, l, m = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(mask, np.int64))
-        if m.size and (m.min() < 0 or m.max() > 255):
-            raise ValueError("count_distribution: a state mask must be 1..15")
+        f, l, m = _jobs("count_distribution", first, last, (mask, *_MASK))
         K = int(max_count)
-        if K != max_count or not -2**31 <= K < 2**31:
+        if K != max_count or not -2**31 <= K < 2**31:         # (unlike run_lengths' max_len, a K outside 1..62 goes on to the library)
             raise ValueError("count_distribution: max_count must be a whole number of windows (the library refuses one outside 1..62)")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        m = np.ascontiguousarray(m.ravel(), np.uint8)
-        out = np.empty((f.size, max(K, 0) + 2), dtype=np.float64)
-        N.check(self._L.hf_get_count_distribution(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  l.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_uint8)), K,
-                                                  _dptr(out)), "hf_get_count_distribution")
+        out, = _outputs(f.size, (np.float64, max(K, 0) + 2))
+        N.check(self._L.hf_get_count_distribution(self._h, f.size, _ptr(f), _ptr(l), _ptr(m), K, _dptr(out)), "hf_get_count_distribution")
         return out
 
     def path_entropy(self, first, last) -> np.ndarray:
         """Exact path entropy under the model of the last full pass (hf_get_path_entropy): for every job i, the Shannon entropy in nats
         of the joint posterior distribution of the labels of the windows first[i]..last[i] (inclusive; chunks are independent chains)
         -> float64[n].  exp of it is the effective number of plausible labellings of the range.  Scalars broadcast."""
-        f, l = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64))
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        out = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_path_entropy(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            l.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(out)), "hf_get_path_entropy")
+        f, l = _jobs("path_entropy", first, last)
+        out, = _outputs(f.size, np.float64)
+        N.check(self._L.hf_get_path_entropy(self._h, f.size, _ptr(f), _ptr(l), _dptr(out)), "hf_get_path_entropy")
         return out
 
     def path_log_probs(self, first, last, labels) -> np.ndarray:
         """Exact log-probability of a labelling under the model of the last full pass (hf_get_path_log_probs): for every job i,
         log P(the windows first[i]..last[i] (inclusive) have the labels labels[first[i]..last[i]] | data) -> float64[n], -inf where the
         labelling is impossible.  labels: n_windows values 0..3, read only inside the jobs' ranges.  Scalars broadcast."""
-        f, l = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64))
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
+        f, l = _jobs("path_log_probs", first, last)
         lab = np.asarray(labels)
         if lab.ndim != 1 or lab.size != self.store.n_windows:
             raise ValueError("path_log_probs: labels must hold one label per window")
         if lab.dtype != np.int8:
             lab = np.clip(lab, -128, 127)                      # (a label outside 0..3 stays outside)
         lab = np.ascontiguousarray(lab, np.int8)
-        out = np.empty(f.size, dtype=np.float64)
-        N.check(self._L.hf_get_path_log_probs(self._h, f.size, f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              l.ctypes.data_as(C.POINTER(C.c_int64)), lab.ctypes.data_as(C.POINTER(C.c_int8)),
-                                              _dptr(out)), "hf_get_path_log_probs")
+        out, = _outputs(f.size, np.float64)
+        N.check(self._L.hf_get_path_log_probs(self._h, f.size, _ptr(f), _ptr(l), _ptr(lab), _dptr(out)), "hf_get_path_log_probs")
         return out
 
     def entropy_profile(self, first: int = 0, n: Optional[int] = None):
@@ -959,24 +876,11 @@ class EMList:
         -> (log_p_event float64[n], the log-probability that the range switches exactly once in that way; quantiles int64[n, len(probs)],
         the smallest k whose cumulated p reaches probs[j]; mode int64[n], the k of largest p; mode_p float64[n]).  A job without weight
         gives (-inf, -1, -1, 0.0).  Scalars broadcast."""
-        f, l, u, v = np.broadcast_arrays(np.asarray(first, np.int64), np.asarray(last, np.int64), np.asarray(left_mask, np.int64),
-                                         np.asarray(right_mask, np.int64))
-        if u.size and (min(u.min(), v.min()) < 0 or max(u.max(), v.max()) > 255):
-            raise ValueError("breakpoints: a state mask must be 1..15")
-        f = np.ascontiguousarray(f.ravel(), np.int64)
-        l = np.ascontiguousarray(l.ravel(), np.int64)
-        u = np.ascontiguousarray(u.ravel(), np.uint8)
-        v = np.ascontiguousarray(v.ravel(), np.uint8)
+        f, l, u, v = _jobs("breakpoints", first, last, (left_mask, *_MASK), (right_mask, *_MASK))
         q = np.ascontiguousarray(np.asarray(probs, np.float64).ravel())
-        lpe = np.empty(f.size, dtype=np.float64)
-        quant = np.empty((f.size, q.size), dtype=np.int64)
-        mode = np.empty(f.size, dtype=np.int64)
-        mode_p = np.empty(f.size, dtype=np.float64)
-        i64p = C.POINTER(C.c_int64)
-        N.check(self._L.hf_get_breakpoints(self._h, f.size, f.ctypes.data_as(i64p), l.ctypes.data_as(i64p),
-                                           u.ctypes.data_as(C.POINTER(C.c_uint8)), v.ctypes.data_as(C.POINTER(C.c_uint8)), q.size, _dptr(q),
-                                           _dptr(lpe), quant.ctypes.data_as(i64p), mode.ctypes.data_as(i64p), _dptr(mode_p)),
-                "hf_get_breakpoints")
+        lpe, quant, mode, mode_p = _outputs(f.size, np.float64, (np.int64, q.size), np.int64, np.float64)
+        N.check(self._L.hf_get_breakpoints(self._h, f.size, _ptr(f), _ptr(l), _ptr(u), _ptr(v), q.size, _dptr(q),
+                                           _dptr(lpe), _ptr(quant), _ptr(mode), _dptr(mode_p)), "hf_get_breakpoints")
         return lpe, quant, mode, mode_p
 
     def breakpoint_profile(self, first: int, last: int, left_mask: int, right_mask: int):
@@ -984,7 +888,7 @@ class EMList:
         first + 1 + i is the first of the right side, given that the range switches once; log_p_event).  The values the batch call
         derives its quantiles and mode from, bit for bit."""
         if not (0 <= int(left_mask) <= 255 and 0 <= int(right_mask) <= 255):
-            raise ValueError("breakpoint_profile: a state mask must be 1..15")
+            raise ValueError("breakpoint_profile: " + _MASK[3])
         p = np.empty(max(int(last) - int(first), 0), dtype=np.float64)
         lpe = np.empty(1, dtype=np.float64)
         N.check(self._L.hf_get_breakpoint_profile(self._h, int(first), int(last), int(left_mask), int(right_mask), _dptr(p), _dptr(lpe)),
@@ -1010,6 +914,13 @@ class EMList:
         return f, b, sc
 
 
+def _method_of(emList, name: str, who: str, what: str):
+    """emList.<name> for the wrapper `who`, or its TypeError: any list with that method will do, one without it has no <what>."""
+    if not hasattr(emList, name):
+        raise TypeError("%s: %s has no %s" % (who, type(emList).__name__, what))
+    return getattr(emList, name)
+
+
 def EM_runOneIterationForList(emList, model: HMM, threads: int = 0) -> None:
     """hmm.c:739-763.  `threads` is accepted for signature compatibility; the result never depended
     on it.  `emList` is an EMList or a dist.ShardedEMList."""
@@ -1027,9 +938,8 @@ def EM_runOneMinLengthIterationForList(emList, model: HMM, min_len, joined=None)
     expected statistics under the posterior over admissible paths, model.loglikelihood the sum of log Z_adm.  Returns the plain sum of
     log Z of the same parameters.  joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole
     groups of joined chunks and both sums run over the groups.  `emList`: an EMList."""
-    if not hasattr(emList, "estep_minlen"):
-        raise TypeError("EM_runOneMinLengthIterationForList: %s has no E-step under minimum run lengths" % type(emList).__name__)
-    stats, log_z = emList.estep_minlen(model, min_len) if joined is None else emList.estep_minlen(model, min_len, joined)
+    estep_minlen = _method_of(emList, "estep_minlen", "EM_runOneMinLengthIterationForList", "E-step under minimum run lengths")
+    stats, log_z = estep_minlen(model, min_len) if joined is None else estep_minlen(model, min_len, joined)
     model.estimators = stats
     model.loglikelihood = float(stats[0])
     return log_z
@@ -1049,9 +959,7 @@ def EM_runViterbiForList(emList, model: HMM):
     """Most-probable-path decoding of every chunk with the model's current parameters (no counterpart in the reference, which
     decodes by posterior argmax only): (labels: int8[n_windows], chunk_log_probs: float64[n_chunks], log_prob: float), the run's
     score being the sum of the chunk scores in list order.  `emList`: an EMList, MultiEMList or RankEMList."""
-    if not hasattr(emList, "viterbi"):
-        raise TypeError("EM_runViterbiForList: %s has no most-probable-path decoder" % type(emList).__name__)
-    return emList.viterbi(model)
+    return _method_of(emList, "viterbi", "EM_runViterbiForList", "most-probable-path decoder")(model)
 
 
 def EM_runMinLengthViterbiForList(emList, model: HMM, min_len, joined=None):
@@ -1059,11 +967,10 @@ def EM_runMinLengthViterbiForList(emList, model: HMM, min_len, joined=None):
     the best path among those whose runs of state s have at least min_len[s] windows, runs at a chunk's ends exempt.  Returns what
     EM_runViterbiForList returns.  joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole
     groups of joined chunks and only runs at a group's ends are exempt.  `emList`: an EMList."""
-    if not hasattr(emList, "viterbi_minlen"):
-        raise TypeError("EM_runMinLengthViterbiForList: %s has no minimum-run-length decoder" % type(emList).__name__)
+    viterbi_minlen = _method_of(emList, "viterbi_minlen", "EM_runMinLengthViterbiForList", "minimum-run-length decoder")
     if joined is None:
-        return emList.viterbi_minlen(model, min_len)
-    return emList.viterbi_minlen(model, min_len, joined)
+        return viterbi_minlen(model, min_len)
+    return viterbi_minlen(model, min_len, joined)
 
 
 def joined_chunks(store) -> np.ndarray:
@@ -1108,11 +1015,10 @@ def EM_runMinLengthPosteriorForList(emList, model: HMM, min_len, joined=None) ->
     of state s has at least min_len[s] windows, runs at a chunk's ends exempt, and the posterior mass of those paths per chunk.
     joined[c] says that chunk c continues chunk c - 1 (joined_chunks): the rule then holds over whole groups of joined chunks and
     only runs at a group's ends are exempt.  `emList`: an EMList."""
-    if not hasattr(emList, "minlen_posterior"):
-        raise TypeError("EM_runMinLengthPosteriorForList: %s has no minimum-run-length posterior" % type(emList).__name__)
+    minlen_posterior = _method_of(emList, "minlen_posterior", "EM_runMinLengthPosteriorForList", "minimum-run-length posterior")
     if joined is None:
-        return emList.minlen_posterior(model, min_len)
-    return emList.minlen_posterior(model, min_len, joined)
+        return minlen_posterior(model, min_len)
+    return minlen_posterior(model, min_len, joined)
 
 
 def EM_getMaxExpectedGainLabelsForList(emList, min_len, joined=None, gain=None):
@@ -1121,114 +1027,89 @@ def EM_getMaxExpectedGainLabelsForList(emList, min_len, joined=None, gain=None):
     one with the largest expected gain under the posterior of the last full pass; gain None counts correctly labelled windows.
     Returns (labels: int8[n_windows], block_gain: float64[n_chunks], total_gain: float).  joined[c] says that chunk c continues chunk
     c - 1 (joined_chunks): the rule then holds over whole groups of joined chunks.  `emList`: an EMList."""
-    if not hasattr(emList, "mea_labels"):
-        raise TypeError("EM_getMaxExpectedGainLabelsForList: %s has no maximum-expected-accuracy decoder" % type(emList).__name__)
-    return emList.mea_labels(min_len, joined, gain)
+    return _method_of(emList, "mea_labels", "EM_getMaxExpectedGainLabelsForList", "maximum-expected-accuracy decoder")(min_len, joined, gain)
 
 
 def EM_samplePathsForList(emList, model: HMM, n_samples: int, seed: int) -> np.ndarray:
     """Draws of whole state paths from P(path | data) with the model's current parameters (forward filtering, backward sampling; no
     counterpart in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k) alone.  `emList`: an EMList."""
-    if not hasattr(emList, "sample_paths"):
-        raise TypeError("EM_samplePathsForList: %s has no path sampler" % type(emList).__name__)
-    return emList.sample_paths(model, n_samples, seed)
+    return _method_of(emList, "sample_paths", "EM_samplePathsForList", "path sampler")(model, n_samples, seed)
 
 
 def EM_sampleMinLengthPathsForList(emList, model: HMM, min_len, n_samples: int, seed: int, joined=None) -> np.ndarray:
     """n_samples admissible paths drawn from the posterior under minimum run lengths with the model's current parameters (no counterpart
     in the reference): int8[n_samples][n_windows], sample k drawn from (seed, k, min_len) alone.  joined[c] says that chunk c continues
     chunk c - 1 (joined_chunks): every path is then admissible over its whole group of joined chunks.  `emList`: an EMList."""
-    if not hasattr(emList, "sample_paths_minlen"):
-        raise TypeError("EM_sampleMinLengthPathsForList: %s has no admissible path sampler" % type(emList).__name__)
+    sample_paths_minlen = _method_of(emList, "sample_paths_minlen", "EM_sampleMinLengthPathsForList", "admissible path sampler")
     if joined is None:
-        return emList.sample_paths_minlen(model, min_len, n_samples, seed)
-    return emList.sample_paths_minlen(model, min_len, n_samples, seed, joined=joined)
+        return sample_paths_minlen(model, min_len, n_samples, seed)
+    return sample_paths_minlen(model, min_len, n_samples, seed, joined=joined)
 
 
 def EM_getIntervalLogProbsForList(emList, first, last, mask) -> np.ndarray:
     """log P(every window of first[i]..last[i] has a state in mask[i] | data) under the model of the last full pass, per job (no
     counterpart in the reference): float64[n].  `emList`: an EMList."""
-    if not hasattr(emList, "interval_log_probs"):
-        raise TypeError("EM_getIntervalLogProbsForList: %s has no interval getter" % type(emList).__name__)
-    return emList.interval_log_probs(first, last, mask)
+    return _method_of(emList, "interval_log_probs", "EM_getIntervalLogProbsForList", "interval getter")(first, last, mask)
 
 
 def EM_getCountMomentsForList(emList, first, last, mask, region=None, unit="windows"):
     """Exact posterior (mean, variance) of the number of windows (or bases) of first[i]..last[i] whose state lies in mask[i], optionally
     only those of annotation region region[i], under the model of the last full pass, per job (no counterpart in the reference):
     (float64[n], float64[n]).  `emList`: an EMList."""
-    if not hasattr(emList, "count_moments"):
-        raise TypeError("EM_getCountMomentsForList: %s has no count-moments getter" % type(emList).__name__)
-    return emList.count_moments(first, last, mask, region, unit)
+    return _method_of(emList, "count_moments", "EM_getCountMomentsForList", "count-moments getter")(first, last, mask, region, unit)
 
 
 def EM_getRunMomentsForList(emList, first, last, mask, joined=None):
     """Exact posterior (mean, variance) of the number of blocks (maximal runs of windows) of first[i]..last[i] whose state lies in
     mask[i], under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run across
     the boundary counts once (no counterpart in the reference): (float64[n], float64[n]).  `emList`: an EMList."""
-    if not hasattr(emList, "run_moments"):
-        raise TypeError("EM_getRunMomentsForList: %s has no run-moments getter" % type(emList).__name__)
-    return emList.run_moments(first, last, mask, joined)
+    return _method_of(emList, "run_moments", "EM_getRunMomentsForList", "run-moments getter")(first, last, mask, joined)
 
 
 def EM_getLongRunLogProbsForList(emList, first, last, mask, min_len, joined=None):
     """(log P(no run), log P(some run)) of at least min_len[i] consecutive windows of first[i]..last[i] whose state lies in mask[i],
     under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run goes on across the
     boundary (no counterpart in the reference): (float64[n], float64[n]).  `emList`: an EMList."""
-    if not hasattr(emList, "long_run_log_probs"):
-        raise TypeError("EM_getLongRunLogProbsForList: %s has no long-run getter" % type(emList).__name__)
-    return emList.long_run_log_probs(first, last, mask, min_len, joined)
+    return _method_of(emList, "long_run_log_probs", "EM_getLongRunLogProbsForList", "long-run getter")(first, last, mask, min_len, joined)
 
 
 def EM_getRunLengthsForList(emList, first, last, mask, max_len, joined=None) -> np.ndarray:
     """The expected number of blocks (maximal runs of windows) of first[i]..last[i] whose state lies in mask[i], by length 1..max_len
     and above, under the model of the last full pass, per job; joined[c] says that chunk c continues chunk c - 1, so that a run goes on
     across the boundary (no counterpart in the reference): float64[n, max_len + 1].  `emList`: an EMList."""
-    if not hasattr(emList, "run_lengths"):
-        raise TypeError("EM_getRunLengthsForList: %s has no run-length getter" % type(emList).__name__)
-    return emList.run_lengths(first, last, mask, max_len, joined)
+    return _method_of(emList, "run_lengths", "EM_getRunLengthsForList", "run-length getter")(first, last, mask, max_len, joined)
 
 
 def EM_getCountDistributionForList(emList, first, last, mask, max_count) -> np.ndarray:
     """The posterior distribution of the number of windows of first[i]..last[i] whose state lies in mask[i], under the model of the
     last full pass, per job: P(N = k), k = 0..max_count, and P(N > max_count) (no counterpart in the reference):
     float64[n, max_count + 2].  `emList`: an EMList."""
-    if not hasattr(emList, "count_distribution"):
-        raise TypeError("EM_getCountDistributionForList: %s has no count-distribution getter" % type(emList).__name__)
-    return emList.count_distribution(first, last, mask, max_count)
+    return _method_of(emList, "count_distribution", "EM_getCountDistributionForList", "count-distribution getter")(first, last, mask, max_count)
 
 
 def EM_getPathEntropyForList(emList, first, last) -> np.ndarray:
     """Exact Shannon entropy (nats) of the posterior distribution over the label paths of the windows first[i]..last[i], under the model
     of the last full pass, per job (no counterpart in the reference): float64[n].  `emList`: an EMList."""
-    if not hasattr(emList, "path_entropy"):
-        raise TypeError("EM_getPathEntropyForList: %s has no path-entropy getter" % type(emList).__name__)
-    return emList.path_entropy(first, last)
+    return _method_of(emList, "path_entropy", "EM_getPathEntropyForList", "path-entropy getter")(first, last)
 
 
 def EM_getPathLogProbsForList(emList, first, last, labels) -> np.ndarray:
     """log P(the windows first[i]..last[i] have the labels labels[first[i]..last[i]] | data) under the model of the last full pass, per
     job (no counterpart in the reference): float64[n].  `emList`: an EMList."""
-    if not hasattr(emList, "path_log_probs"):
-        raise TypeError("EM_getPathLogProbsForList: %s has no path log-probability getter" % type(emList).__name__)
-    return emList.path_log_probs(first, last, labels)
+    return _method_of(emList, "path_log_probs", "EM_getPathLogProbsForList", "path log-probability getter")(first, last, labels)
 
 
 def EM_getEntropyProfileForList(emList, first: int = 0, n: Optional[int] = None):
     """(marg, cond): per window, the entropy of its posterior and the entropy of its label given the label of the window before, under
     the model of the last full pass (no counterpart in the reference).  `emList`: an EMList."""
-    if not hasattr(emList, "entropy_profile"):
-        raise TypeError("EM_getEntropyProfileForList: %s has no entropy profile" % type(emList).__name__)
-    return emList.entropy_profile(first, n)
+    return _method_of(emList, "entropy_profile", "EM_getEntropyProfileForList", "entropy profile")(first, n)
 
 
 def EM_getBreakpointsForList(emList, first, last, left_mask, right_mask, probs=(0.025, 0.5, 0.975)):
     """(log_p_event, quantiles, mode, mode_p) of the window at which first[i]..last[i] switches from a state of left_mask[i] to one of
     right_mask[i], given that it switches once, under the model of the last full pass, per job (no counterpart in the reference).
     `emList`: an EMList."""
-    if not hasattr(emList, "breakpoints"):
-        raise TypeError("EM_getBreakpointsForList: %s has no breakpoint getter" % type(emList).__name__)
-    return emList.breakpoints(first, last, left_mask, right_mask, probs)
+    return _method_of(emList, "breakpoints", "EM_getBreakpointsForList", "breakpoint getter")(first, last, left_mask, right_mask, probs)
 
 
 class EMBatch:
@@ -1272,7 +1153,7 @@ class EMBatch:
         if n < 0:
             raise N.HFError(n, "hf_batch_handoff")
         flags = np.zeros(n, dtype=np.uint32)
-        n = int(self._L.hf_batch_handoff(self._b, int(m), C.byref(epoch), flags.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        n = int(self._L.hf_batch_handoff(self._b, int(m), C.byref(epoch), _ptr(flags), n))
         if n < 0:
             raise N.HFError(n, "hf_batch_handoff")
         return int(epoch.value), flags
@@ -1305,13 +1186,13 @@ class EMBatch:
         for i, m in enumerate(ms):
             ps[i] = m.params()
         self._keep = ms                                  # (the parameter views point into the models until the pass is enqueued)
-        N.check(self._L.hf_batch_estep(self._b, ps, act.ctypes.data_as(C.POINTER(C.c_int32)), len(act), mode, self.stream), "hf_batch_estep")
+        N.check(self._L.hf_batch_estep(self._b, ps, _ptr(act), len(act), mode, self.stream), "hf_batch_estep")
         return act
 
     def finish(self, n_active: int):
         stats = np.empty((n_active, self.stats_len), dtype=np.float64)
         status = np.zeros(n_active, dtype=np.int32)
-        N.check(self._L.hf_batch_finish(self._b, _dptr(stats), status.ctypes.data_as(C.POINTER(C.c_int32)), self.stream), "hf_batch_finish")
+        N.check(self._L.hf_batch_finish(self._b, _dptr(stats), _ptr(status), self.stream), "hf_batch_finish")
         return stats, status
 
     def estep(self, models: Optional[Sequence[HMM]] = None, active=None, mode: int = N.HF_MODE_FULL):
@@ -1322,7 +1203,7 @@ class EMBatch:
 
     def labels(self, m: int) -> np.ndarray:
         out = np.empty(self.em.store.n_windows, dtype=np.int8)
-        N.check(self._L.hf_batch_get_labels(self._b, int(m), out.ctypes.data_as(C.POINTER(C.c_int8))), "hf_batch_get_labels")
+        N.check(self._L.hf_batch_get_labels(self._b, int(m), _ptr(out)), "hf_batch_get_labels")
         return out
 
     def posterior(self, m: int, first: int = 0, n: Optional[int] = None) -> np.ndarray:
@@ -1379,7 +1260,7 @@ def HMM_estimateAlpha(model: HMM, alphaStats: np.ndarray, convergenceTol: float,
     if a.size != 32 * model.numberOfRegions:
         raise ValueError("HMM_estimateAlpha: alphaStats must hold 32 doubles per region")
     mask = np.ascontiguousarray(alpha_free_mask(entries).ravel())
-    rc = N.lib().hfm_estimate_alpha(model._h, _dptr(a), _dptr(st), mask.ctypes.data_as(C.POINTER(C.c_uint8)), float(lo), float(hi),
+    rc = N.lib().hfm_estimate_alpha(model._h, _dptr(a), _dptr(st), _ptr(mask), float(lo), float(hi),
                                     float(convergenceTol))
     if rc < 0:
         raise ValueError("HMM_estimateAlpha: bad argument (bounds outside [0, 1), or a negative_binomial model)")
@@ -1396,7 +1277,7 @@ def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergence
                   is_writer: bool = True, fitAlpha: bool = False, fitAlphaEntries=FIT_ALPHA_ENTRIES, fitAlphaMax: float = FIT_ALPHA_MAX,
                   fitAlphaEvery: int = 2, constrainedMinLen=None, constrainedJoined=None) -> List[float]:
     """EM outer loop of hmm_flagger.c:285-488 (no --accelerate here: that loop is flagger_amd/csrc/hf_squarem.h, driven by the command line).  Returns the
-    log-likelihood of every E-pass (the rows of loglikelihood.tsv).
+    log-likelihood of every E-pass (the rows of the log-likelihood table, _RunFiles).
     constrainedMinLen (an EMList only; four window counts): the EM iterations run on the E-step under minimum run lengths
     (em_iterate_minlen), so their rows hold the objective sum of log Z_adm, and length_constrained_em.tsv holds per iteration
     log Z_adm, log Z and their difference; the final inference pass stays the plain pass with the fitted parameters.
@@ -1407,149 +1288,161 @@ def runHMMFlagger(emList, model: HMM, numberOfIterations: int = 100, convergence
     the latest iteration of each kind reported convergence."""
     if constrainedJoined is not None and constrainedMinLen is None:
         raise ValueError("runHMMFlagger: constrainedJoined needs constrainedMinLen")
-    if constrainedMinLen is not None:
+    variant = "minlen" if constrainedMinLen is not None else "alpha" if fitAlpha else "plain"
+    files = _RunFiles(outputDir if is_writer else None, writeParameterStatsPerIteration, variant)
+    if variant == "minlen":
         if fitAlpha:
             raise ValueError("runHMMFlagger: constrainedMinLen cannot be combined with fitAlpha")
-        return _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
-                                    is_writer, constrainedMinLen, constrainedJoined)
-    if fitAlpha:
-        return _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration,
-                                      is_writer, fitAlphaEntries, fitAlphaMax, int(fitAlphaEvery))
-    lls: List[float] = []
-    llf = None
-    write = outputDir is not None and is_writer
-    if write:
-        llf = open(os.path.join(outputDir, "loglikelihood.tsv"), "w")
-        llf.write("#Iteration\tEffective_Iteration\tLoglikelihood\n")
-        model.writeTransitionTsv(os.path.join(outputDir, "transition_initial.tsv"))
-        model.writeEmissionTsv(os.path.join(outputDir, "emission_initial.tsv"))
-    it, converged = 1, False
-    fused = hasattr(emList, "em_iterate")      # single GPU: E-step + M-step in one native call
-    while it <= numberOfIterations and not converged:
-        if fused:
-            converged = emList.em_iterate(model, True, convergenceTol)
-        else:
-            EM_runOneIterationForList(emList, model)
-        lls.append(model.loglikelihood)
-        if llf:
-            llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-        if not fused:
-            converged = HMM_estimateParameters(model, convergenceTol)
-        HMM_resetEstimators(model)
-        if write and writeParameterStatsPerIteration:
-            model.writeTransitionTsv(os.path.join(outputDir, f"transition_iteration_{it}.tsv"))
-            model.writeEmissionTsv(os.path.join(outputDir, f"emission_iteration_{it}.tsv"))
-        it += 1
-    EM_runOneIterationForList(emList, model)   # final inference, hmm_flagger.c:464
-    lls.append(model.loglikelihood)
-    if llf:
-        llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-        llf.close()
-        model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
-        model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
-    return lls
+        step = _minlen_step(emList, model, convergenceTol, files, constrainedMinLen, constrainedJoined)
+    elif variant == "alpha":
+        step = _alpha_step(emList, model, convergenceTol, files, fitAlphaEntries, fitAlphaMax, int(fitAlphaEvery))
+        emList.set_alpha_stats(True)
+    else:
+        step = _plain_step(emList, model, convergenceTol)
+    try:
+        with files:
+            return _em_loop(emList, model, numberOfIterations, files, step)
+    finally:
+        if variant == "alpha":
+            emList.set_alpha_stats(False)
 
 
 LCEM_HEADER = "#Iteration\tLog_Z_adm\tLog_Z\tLog_mass\n"
 
 
-def _runHMMFlaggerMinLen(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration, is_writer,
-                         min_len, joined=None) -> List[float]:
-    if not hasattr(emList, "em_iterate_minlen"):
-        raise TypeError("runHMMFlagger(constrainedMinLen=...): %s has no E-step under minimum run lengths" % type(emList).__name__)
-    if model.modelType == MODEL_NEGATIVE_BINOMIAL:
-        raise ValueError("constrainedMinLen: the negative_binomial model is not supported")
+class _RunFiles:
+    """The files of one runHMMFlagger run, opened on entering and closed on leaving its `with` block: the log-likelihood table, the
+    table of the variant ("minlen": length_constrained_em.tsv, "alpha": alpha_trace.tsv, "plain": none), the parameter files and,
+    for "alpha", alpha_fitted.tsv.  Every name, header and row format of the run is here; without a directory nothing is written."""
+    TABLES = {"plain": None, "minlen": ("length_constrained_em.tsv", LCEM_HEADER), "alpha": ("alpha_trace.tsv", "")}
+
+    def __init__(self, outputDir: Optional[str], everyIteration: bool, variant: str):
+        self.dir, self.every_iteration, self.variant = outputDir, everyIteration, variant
+        self._ll = self._table = None
+        self._open = contextlib.ExitStack()
+
+    def _opened(self, name: str, header: str):
+        f = self._open.enter_context(open(os.path.join(self.dir, name), "w"))
+        f.write(header)
+        return f
+
+    def __enter__(self):
+        try:
+            if self.dir is not None:
+                self._ll = self._opened("loglikelihood.tsv", "#Iteration\tEffective_Iteration\tLoglikelihood\n")
+                if self.TABLES[self.variant]:
+                    self._table = self._opened(*self.TABLES[self.variant])
+        except BaseException:
+            self._open.close()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        self._open.close()
+
+    def loglikelihood(self, iteration: int, ll: float) -> None:
+        if self._ll:
+            self._ll.write("%d\t%d\t%.4f\n" % (iteration, iteration, ll))
+
+    def constrained_row(self, iteration: int, log_z_adm: float, log_z: float) -> None:
+        if self._table:
+            self._table.write("%d\t%.4f\t%.4f\t%.4f\n" % (iteration, log_z_adm, log_z, log_z_adm - log_z))
+
+    def alpha_trace_row(self, iteration: int, model: HMM, stats: np.ndarray) -> None:
+        """The iteration, its log-likelihood, the alpha matrix the pass ran with and the alpha statistics summed over the regions."""
+        if self._table:
+            self._table.write("\t".join(["%d" % iteration, "%.17g" % model.loglikelihood] + ["%.17g" % v for v in model.alpha.ravel()] +
+                                        ["%.17g" % v for v in stats.ravel()]) + "\n")
+
+    def parameters(self, model: HMM, point: str) -> None:
+        """transition_<point>.tsv and emission_<point>.tsv; point: "initial" (transition_initial.tsv), "iteration_<k>" or "final"."""
+        if self.dir is not None:
+            model.writeTransitionTsv(os.path.join(self.dir, "transition_%s.tsv" % point))
+            model.writeEmissionTsv(os.path.join(self.dir, "emission_%s.tsv" % point))
+
+    def iteration(self, model: HMM, it: int) -> None:
+        if self.every_iteration:
+            self.parameters(model, "iteration_%d" % it)
+
+    def final(self, model: HMM) -> None:
+        self.parameters(model, "final")
+        if self.dir is not None and self.variant == "alpha":
+            with open(os.path.join(self.dir, "alpha_fitted.tsv"), "w") as f:
+                for row in model.alpha:
+                    f.write("\t".join("%.17g" % v for v in row) + "\n")
+
+
+def _em_loop(emList, model: HMM, numberOfIterations: int, files: _RunFiles, step) -> List[float]:
+    """The EM outer loop, once for every variant.  step(it, record) runs iteration `it`: its pass, then record() (the pass's
+    log-likelihood into the returned list and its row into the table), then whatever moves the parameters; it returns whether the
+    run has converged.  The final inference pass is the plain pass with the fitted parameters (hmm_flagger.c:464)."""
     lls: List[float] = []
-    write = outputDir is not None and is_writer
-    llf = lcf = None
-    if write:
-        llf = open(os.path.join(outputDir, "loglikelihood.tsv"), "w")
-        llf.write("#Iteration\tEffective_Iteration\tLoglikelihood\n")
-        lcf = open(os.path.join(outputDir, "length_constrained_em.tsv"), "w")
-        lcf.write(LCEM_HEADER)
-        model.writeTransitionTsv(os.path.join(outputDir, "transition_initial.tsv"))
-        model.writeEmissionTsv(os.path.join(outputDir, "emission_initial.tsv"))
     it, converged = 1, False
-    try:
-        while it <= numberOfIterations and not converged:
-            converged = (emList.em_iterate_minlen(model, min_len, True, convergenceTol) if joined is None else
-                         emList.em_iterate_minlen(model, min_len, True, convergenceTol, joined=joined))
-            lls.append(model.loglikelihood)
-            if llf:
-                llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-                lcf.write("%d\t%.4f\t%.4f\t%.4f\n" % (it - 1, model.loglikelihood, emList.last_log_z, model.loglikelihood - emList.last_log_z))
-            HMM_resetEstimators(model)
-            if write and writeParameterStatsPerIteration:
-                model.writeTransitionTsv(os.path.join(outputDir, f"transition_iteration_{it}.tsv"))
-                model.writeEmissionTsv(os.path.join(outputDir, f"emission_iteration_{it}.tsv"))
-            it += 1
-        EM_runOneIterationForList(emList, model)   # final inference: the plain pass with the fitted parameters
+
+    def record():
         lls.append(model.loglikelihood)
-        if llf:
-            llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-            model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
-            model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
-    finally:
-        if llf:
-            llf.close()
-        if lcf:
-            lcf.close()
+        files.loglikelihood(it - 1, model.loglikelihood)
+
+    files.parameters(model, "initial")
+    while it <= numberOfIterations and not converged:
+        converged = step(it, record)
+        HMM_resetEstimators(model)
+        files.iteration(model, it)
+        it += 1
+    EM_runOneIterationForList(emList, model)
+    record()
+    files.final(model)
     return lls
 
 
-def _runHMMFlaggerFitAlpha(emList, model, numberOfIterations, convergenceTol, outputDir, writeParameterStatsPerIteration, is_writer,
-                           entries, alphaMax, every) -> List[float]:
-    if not hasattr(emList, "alpha_stats"):
-        raise TypeError("runHMMFlagger(fitAlpha=True): %s has no alpha statistics" % type(emList).__name__)
+def _plain_step(emList, model: HMM, tol: float):
+    """An ordinary iteration: one native call where the list has the fused one (single GPU: E-step + M-step), else the pass, then
+    HMM_estimateParameters."""
+    fused = hasattr(emList, "em_iterate")
+
+    def step(it, record):
+        if fused:
+            converged = emList.em_iterate(model, True, tol)
+        else:
+            EM_runOneIterationForList(emList, model)
+        record()
+        return converged if fused else HMM_estimateParameters(model, tol)
+    return step
+
+
+def _minlen_step(emList, model: HMM, tol: float, files: _RunFiles, min_len, joined):
+    """An iteration on the E-step under minimum run lengths (em_iterate_minlen; `joined` is passed only where it is given)."""
+    em_iterate_minlen = _method_of(emList, "em_iterate_minlen", "runHMMFlagger(constrainedMinLen=...)", "E-step under minimum run lengths")
+    if model.modelType == MODEL_NEGATIVE_BINOMIAL:
+        raise ValueError("constrainedMinLen: the negative_binomial model is not supported")
+    joins = {} if joined is None else {"joined": joined}
+
+    def step(it, record):
+        converged = em_iterate_minlen(model, min_len, True, tol, **joins)
+        record()
+        files.constrained_row(it - 1, model.loglikelihood, emList.last_log_z)
+        return converged
+    return step
+
+
+def _alpha_step(emList, model: HMM, tol: float, files: _RunFiles, entries, alphaMax: float, every: int):
+    """The pass, then HMM_estimateAlpha alone in every `every`-th iteration and HMM_estimateParameters alone in the others; converged
+    when the latest iteration of each kind was."""
+    _method_of(emList, "alpha_stats", "runHMMFlagger(fitAlpha=True)", "alpha statistics")
     if every < 1:
         raise ValueError("fitAlphaEvery must be at least 1")
     if model.modelType == MODEL_NEGATIVE_BINOMIAL:
         raise ValueError("fitAlpha: the negative_binomial emission has no alpha")
     alpha_free_mask(entries)
-    emList.set_alpha_stats(True)
-    lls: List[float] = []
-    write = outputDir is not None and is_writer
-    llf = trf = None
-    if write:
-        llf = open(os.path.join(outputDir, "loglikelihood.tsv"), "w")
-        llf.write("#Iteration\tEffective_Iteration\tLoglikelihood\n")
-        trf = open(os.path.join(outputDir, "alpha_trace.tsv"), "w")
-        model.writeTransitionTsv(os.path.join(outputDir, "transition_initial.tsv"))
-        model.writeEmissionTsv(os.path.join(outputDir, "emission_initial.tsv"))
-    it = 1
-    conv_em, conv_alpha = False, False
-    try:
-        while it <= numberOfIterations and not (conv_em and conv_alpha):
-            EM_runOneIterationForList(emList, model)
-            lls.append(model.loglikelihood)
-            if llf:
-                llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-            if it % every == 0:
-                st = emList.alpha_stats().sum(axis=0)
-                if trf:
-                    trf.write("\t".join(["%d" % (it - 1), "%.17g" % model.loglikelihood] + ["%.17g" % v for v in model.alpha.ravel()] +
-                                        ["%.17g" % v for v in st.ravel()]) + "\n")
-                conv_alpha = HMM_estimateAlpha(model, emList.alpha_stats(), convergenceTol, entries, 0.0, alphaMax)
-            else:
-                conv_em = HMM_estimateParameters(model, convergenceTol)
-            HMM_resetEstimators(model)
-            if write and writeParameterStatsPerIteration:
-                model.writeTransitionTsv(os.path.join(outputDir, f"transition_iteration_{it}.tsv"))
-                model.writeEmissionTsv(os.path.join(outputDir, f"emission_iteration_{it}.tsv"))
-            it += 1
-        EM_runOneIterationForList(emList, model)   # final inference
-        lls.append(model.loglikelihood)
-        if llf:
-            llf.write("%d\t%d\t%.4f\n" % (it - 1, it - 1, model.loglikelihood))
-            model.writeTransitionTsv(os.path.join(outputDir, "transition_final.tsv"))
-            model.writeEmissionTsv(os.path.join(outputDir, "emission_final.tsv"))
-            with open(os.path.join(outputDir, "alpha_fitted.tsv"), "w") as f:
-                for row in model.alpha:
-                    f.write("\t".join("%.17g" % v for v in row) + "\n")
-    finally:
-        if llf:
-            llf.close()
-        if trf:
-            trf.close()
-        emList.set_alpha_stats(False)
-    return lls
+    converged = {"em": False, "alpha": False}
+
+    def step(it, record):
+        EM_runOneIterationForList(emList, model)
+        record()
+        if it % every == 0:
+            files.alpha_trace_row(it - 1, model, emList.alpha_stats().sum(axis=0))
+            converged["alpha"] = HMM_estimateAlpha(model, emList.alpha_stats(), tol, entries, 0.0, alphaMax)
+        else:
+            converged["em"] = HMM_estimateParameters(model, tol)
+        return converged["em"] and converged["alpha"]
+    return step
